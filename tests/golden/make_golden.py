@@ -16,6 +16,8 @@ Writes
                      image_320x240.jpg and of split_output.jpg (the one saved output the
                      reference ships, split_image_blur.c:548-553) — data, for a loose
                      PSNR sanity check; JPEG-lossy, never bit-exact.
+  "ref_cases" section  FNV-1a-64 of the inputs and the reference kernel's outputs for the LCG and random images and the
+                     Approach-2 splits that tests/test_oracle.py::test_against_reference_kernel_when_present checks.
   "stream" section   the WHOLE headline stream (5000 x 256x256x3, image i = LCG seeded 0x9E3779B9 ^ i)
                      through the reference kernel: FNV-1a-64 of the 983 040 000 output bytes laid end to end, and the
                      FNV of the 5000 per-image output hashes (little-endian u64 each) — what the GPU tests assert for
@@ -32,6 +34,7 @@ Fixtures are data (inputs/expected outputs); no reference source is stored.
 
     python tests/golden/make_golden.py --stream-only     # recompute only the "stream" section (keeps the rest)
     python tests/golden/make_golden.py --multi-gpu-only  # recompute only "bands8192" / "stream50k" (keeps the rest)
+    python tests/golden/make_golden.py --ref-cases-only  # recompute only "ref_cases" (keeps the rest)
 """
 import json
 import os
@@ -117,8 +120,37 @@ def stream50k_section(n: int = 50000, h: int = 256, w: int = 256, c: int = 3, th
     return sec
 
 
+REF_CASE_SHAPES = [(1, 1, 3), (3, 5, 3), (2, 2, 3), (16, 16, 3), (33, 17, 3), (33, 17, 1), (31, 29, 4), (48, 64, 2),
+                   (1, 64, 3), (64, 1, 3), (64, 80, 3), (240, 320, 3), (256, 256, 3)]
+
+
+def ref_cases_section() -> dict:
+    """The inputs of tests/test_oracle.py::test_against_reference_kernel_when_present — per shape an LCG image, then one
+    from default_rng(7) drawn in this order — and the 320x240 LCG image split at four rows: FNV-1a-64 of each input and of
+    the reference kernel's output, so that the test pins the oracle to the reference kernel where oracle/_ref is absent."""
+    rng = np.random.default_rng(7)
+    sec = {"blur": [], "split": []}
+    for (h, w, c) in REF_CASE_SHAPES:
+        for kind, img in (("lcg", O.lcg_image(h, w, c)), ("rng", rng.integers(0, 256, (h, w, c), dtype=np.uint8))):
+            out = O.ref_blur(img)
+            assert np.array_equal(out, O.blur(img, 1)), f"oracle != reference at {h}x{w}x{c} {kind}"
+            sec["blur"].append({"h": h, "w": w, "c": c, "kind": kind, "in_fnv": hx(O.fnv1a64(img)), "out_fnv": hx(O.fnv1a64(out))})
+    img = O.lcg_image(240, 320, 3)
+    for split in (1, 39, 120, 239):
+        out = O.ref_split_blur(img, split)
+        sec["split"].append({"h": 240, "w": 320, "c": 3, "split_row": split, "out_fnv": hx(O.fnv1a64(out))})
+    return sec
+
+
 def main() -> None:
     O.build(ref=True)
+    if "--ref-cases-only" in sys.argv:
+        path = os.path.join(HERE, "blur_golden.json")
+        gold = json.load(open(path))
+        gold["ref_cases"] = ref_cases_section()
+        with open(path, "w") as f:
+            json.dump(gold, f, indent=1)
+        return
     if "--multi-gpu-only" in sys.argv:
         path = os.path.join(HERE, "blur_golden.json")
         gold = json.load(open(path))
@@ -180,6 +212,7 @@ def main() -> None:
         gold["k5_unpinned"].append({"h": h, "w": w, "c": c, "out_fnv": hx(O.fnv1a64(out)),
                                     "first": out.reshape(-1)[:8].tolist()})
 
+    gold["ref_cases"] = ref_cases_section()
     gold["stream"] = stream_section()
     gold["bands8192"] = bands8192_section()
     gold["stream50k"] = stream50k_section()

@@ -365,7 +365,7 @@ def test_bench_spawns_its_own_ranks(pkg):
     import sys
     import torch
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    cmd = [sys.executable, os.path.join(pkg.ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--ramp-seconds", "0.05"]
+    cmd = [sys.executable, os.path.join(pkg.ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--ramp-seconds", "0.05", "--full"]
     r = subprocess.run(cmd + ["--images", "700"], cwd=pkg.ROOT, env=dict(env, MI_BLUR_BENCH_BACKEND="gloo", MI_BLUR_BENCH_DEVICE="0"),
                        capture_output=True, text=True, timeout=600)
     d = _bench_line(r)
@@ -434,7 +434,7 @@ def test_bench_a2_four_rank_rehearsal_has_middle_ranks(pkg):
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(MI_BLUR_BENCH_BACKEND="gloo", MI_BLUR_BENCH_DEVICE="0")
-    r = subprocess.run([sys.executable, os.path.join(pkg.ROOT, "bench.py"), "--workload", "a2", "--gpus", "4", "--steps", "10", "--warmup", "2"],
+    r = subprocess.run([sys.executable, os.path.join(pkg.ROOT, "bench.py"), "--workload", "a2", "--gpus", "4", "--steps", "10", "--warmup", "2", "--full"],
                        cwd=pkg.ROOT, env=env, capture_output=True, text=True, timeout=900)
     d = _bench_line(r)
     assert d["n_gpus"] == 4 and d["scaling"] == "strong" and d["config"]["rows_per_gpu"] == 2048
@@ -453,7 +453,7 @@ def test_bench_a2_two_rank_rehearsal(pkg):
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(MI_BLUR_BENCH_BACKEND="gloo", MI_BLUR_BENCH_DEVICE="0")
-    r = subprocess.run([sys.executable, os.path.join(pkg.ROOT, "bench.py"), "--workload", "a2", "--gpus", "2", "--steps", "10", "--warmup", "2"],
+    r = subprocess.run([sys.executable, os.path.join(pkg.ROOT, "bench.py"), "--workload", "a2", "--gpus", "2", "--steps", "10", "--warmup", "2", "--full"],
                        cwd=pkg.ROOT, env=env, capture_output=True, text=True, timeout=600)
     d = _bench_line(r)
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["value"] > 0
@@ -468,12 +468,12 @@ def test_bench_a2_two_rank_rehearsal(pkg):
 
 @pytest.mark.gpu
 def test_bench_default_line_carries_every_single_gpu_config(pkg):
-    """The default N=1 line: configs[1] as `value`, plus configs[2] (hd1080_5x5 with its own frac), configs[4] at N=1
+    """The --full N=1 line: configs[1] as `value`, plus configs[2] (hd1080_5x5 with its own frac), configs[4] at N=1
     (a2_8192_1gpu, whose output hashes like the reference kernel's), the PCIe-inclusive rate at batch 35 and 500, the
     sustained repeat, roofline and cpu_baseline."""
     import sys
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(pkg.ROOT, "bench.py"), "--steps", "20", "--warmup", "5"], cwd=pkg.ROOT, env=env,
+    r = subprocess.run([sys.executable, os.path.join(pkg.ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--full"], cwd=pkg.ROOT, env=env,
                        capture_output=True, text=True, timeout=900)
     d = _bench_line(r)
     assert d["n_gpus"] == 1 and d["dtype"] == "u8" and "configs[1]" in d["config"]["workload"] and d["vs_baseline"] is None
@@ -498,6 +498,49 @@ def test_bench_default_line_carries_every_single_gpu_config(pkg):
     pg = ex["e2e_pcie_inclusive"]["batch_35_pageable"]          # malloc'd caller buffers: through the pinned staging, served by the batch server
     assert pg["img_s"] > 0 and pg["kernel"] == "blur_server_kernel" and pg["zero_copy_submits"] > 0 and "pageable" in pg["buffers"]
     assert d["per_batch_launches"]["launches_per_step"] == 143
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_and_dumped_outputs(pkg, O, tmp_path):
+    """A plain run (no --full) times exactly --steps steps and carries the headline only.  --dump-outputs writes what the
+    last timed step computed — a seeded sample of whole output images (a2: rows of the 8192^2 band) in float32 and the byte
+    sum of every one in float64 — under 64 MB, and the sampled units equal the oracle's blur of the same seeded inputs."""
+    import sys
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    bench = [sys.executable, os.path.join(pkg.ROOT, "bench.py")]
+    full_only = {"cpu_baseline", "parity", "extra", "sustained", "sustained_img_s", "per_batch_launches", "batch_completion_us",
+                 "release_mode_us"}
+
+    out = tmp_path / "a1"
+    r = subprocess.run(bench + ["--steps", "7", "--warmup", "2", "--dump-outputs", str(out)], cwd=pkg.ROOT, env=env,
+                       capture_output=True, text=True, timeout=600)
+    d = _bench_line(r)
+    assert (d["metric"], d["unit"], d["higher_is_better"], d["dtype"]) == ("images_per_sec", "img/s", True, "u8")
+    assert d["steps"] == 7 and d["roofline"]["launches_timed"] == 7 and "configs[1]" in d["config"]["workload"]
+    assert abs(d["ms_per_step"] - 5000 / d["value"] * 1e3) < 2e-4 and not full_only & set(d)
+    images, index, sums = (np.load(out / f) for f in ("images.npy", "image_index.npy", "image_sum.npy"))
+    assert (images.dtype, index.dtype, sums.dtype) == (np.float32, np.float64, np.float64)
+    assert images.shape == (64, 256, 256, 3) and sums.shape == (5000,) and sum(f.stat().st_size for f in out.iterdir()) < 64e6
+    idx = index.astype(np.int64)
+    assert np.all(np.diff(idx) > 0) and 0 <= idx[0] and idx[-1] < 5000
+    for k, i in enumerate(idx):
+        assert np.array_equal(images[k], O.blur(O.lcg_stream(1, 256, 256, 3, first_index=int(i))[0], 1)), i
+    assert np.array_equal(sums[idx], images.reshape(64, -1).sum(axis=1, dtype=np.float64))
+    want = O.blur_batch(O.lcg_stream(300, 256, 256, 3), 1)
+    assert np.array_equal(sums[:300], want.reshape(300, -1).sum(axis=1, dtype=np.float64))
+
+    out = tmp_path / "a2"
+    r = subprocess.run(bench + ["--workload", "a2", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)], cwd=pkg.ROOT, env=env,
+                       capture_output=True, text=True, timeout=600)
+    d = _bench_line(r)
+    assert d["steps"] == 3 and d["config"]["steps_per_form"] == 3 and "step_decomposition" not in d["config"] and not full_only & set(d)
+    rows, index, sums = (np.load(out / f) for f in ("rows.npy", "row_index.npy", "row_sum.npy"))
+    assert rows.dtype == np.float32 and rows.shape == (512, 8192, 3) and sums.shape == (8192,)
+    img = O.lcg_image(8192, 8192, 3)
+    for k, y in enumerate(index.astype(np.int64)):        # a row's blur needs its neighbours only; the image edges clamp
+        y0 = max(0, y - 1)
+        assert np.array_equal(rows[k], O.blur(np.ascontiguousarray(img[y0:y + 2]), 1)[y - y0]), y
+    assert np.array_equal(sums[index.astype(np.int64)], rows.reshape(512, -1).sum(axis=1, dtype=np.float64))
 
 
 @pytest.mark.gpu

@@ -126,17 +126,28 @@ def test_restatements_agree(O, h, w, c):
             assert np.array_equal(a, O.np_blur(img, r))
 
 
-def test_against_reference_kernel_when_present(O):
-    """Strongest pin: the unmodified reference kernel itself (oracle/_ref)."""
-    if not O.ref_available():
-        pytest.skip("oracle/_ref not built (only buildable where /root/reference exists)")
+def test_against_reference_kernel_when_present(O, golden):
+    """Strongest pin: the unmodified reference kernel itself — its answers on these inputs as committed data
+    (tests/golden "ref_cases"), and oracle/_ref live where it was built."""
+    live = O.ref_available()
+    cases = iter(golden["ref_cases"]["blur"])
     rng = np.random.default_rng(7)
     for (h, w, c) in SHAPES + [(240, 320, 3), (256, 256, 3)]:
-        for img in (O.lcg_image(h, w, c), rng.integers(0, 256, (h, w, c), dtype=np.uint8)):
-            assert np.array_equal(O.ref_blur(img), O.blur(img, 1)), (h, w, c)
+        for kind, img in (("lcg", O.lcg_image(h, w, c)), ("rng", rng.integers(0, 256, (h, w, c), dtype=np.uint8))):
+            e = next(cases)
+            assert (e["h"], e["w"], e["c"], e["kind"]) == (h, w, c, kind)
+            assert f"{O.fnv1a64(img):016x}" == e["in_fnv"], ("the fixture was made from other inputs", h, w, c, kind)
+            assert f"{O.fnv1a64(O.blur(img, 1)):016x}" == e["out_fnv"], (h, w, c, kind)
+            if live:
+                assert np.array_equal(O.ref_blur(img), O.blur(img, 1)), (h, w, c)
+    assert next(cases, None) is None
     img = O.lcg_image(240, 320, 3)
-    for split in (1, 39, 120, 239):
-        assert np.array_equal(O.ref_split_blur(img, split), O.a2_split_blur(img, split, 1))
+    splits = golden["ref_cases"]["split"]
+    assert [e["split_row"] for e in splits] == [1, 39, 120, 239]
+    for e in splits:
+        assert f"{O.fnv1a64(O.a2_split_blur(img, e['split_row'], 1)):016x}" == e["out_fnv"], e["split_row"]
+        if live:
+            assert np.array_equal(O.ref_split_blur(img, e["split_row"]), O.a2_split_blur(img, e["split_row"], 1))
 
 
 def test_splitk_equals_whole(O):

@@ -26,7 +26,7 @@ run_cfg() {   # name, bench args...
 }
 
 if [ $PART != b ]; then
-run_cfg a1                                                                  # the judged command: python bench.py (fused stream + every secondary point)
+run_cfg a1 --full                                                           # the judged command, fused stream, with every secondary point
 run_cfg a1_batched --dispatch batched --no-cpu-baseline --no-extra           # one launch per batch, 4 streams
 run_cfg a1_serial --dispatch batched --streams 1 --time-every 4 --no-cpu-baseline --no-extra   # same launches, one stream: dispatches do not overlap
 run_cfg a1_one_launch --batch 5000 --streams 1 --time-every 1 --no-cpu-baseline --no-extra   # whole stream in one launch (HBM-bound point)
