@@ -31,6 +31,7 @@ DEVICE_CPU = -1
 VARIANT_AUTO, VARIANT_GENERIC, VARIANT_TILED, VARIANT_STREAM, VARIANT_DIRECT = 0, 1, 2, 3, 4
 OK, ERR_INVALID, ERR_NO_DEVICE, ERR_NOMEM, ERR_STATE, ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5
 UNIQUE_ID_BYTES = 128
+SEP_MAX_RADIUS = 16
 PEER_HANDLE_BYTES = 64
 
 
@@ -43,8 +44,8 @@ def _newer(target: str, sources: list[str]) -> bool:
 
 def build_native(force: bool = False, verbose: bool = False) -> str:
     """Compile libmi_blur.so (hipcc, --offload-arch=gfx950) and the C++ hosts, in-tree."""
-    srcs = [os.path.join(CSRC, f) for f in ("blur_kernels.hip", "layout_kernels.hip", "mi_blur_api.cpp", "cpu_device.cpp")]
-    deps = srcs + [os.path.join(CSRC, f) for f in ("blur_launch.h", "cpu_device.h")] + [HEADER]
+    srcs = [os.path.join(CSRC, f) for f in ("blur_kernels.hip", "sep_kernels.hip", "layout_kernels.hip", "mi_blur_api.cpp", "cpu_device.cpp")]
+    deps = srcs + [os.path.join(CSRC, f) for f in ("blur_launch.h", "cpu_device.h", "sep_taps.h")] + [HEADER]
     if force or not _newer(LIB_PATH, deps):
         cmd = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra",
                "-o", LIB_PATH] + srcs + ["-ldl", "-lpthread"]
@@ -88,6 +89,31 @@ class A2Geometry(C.Structure):
 
 class Band(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("row_begin", "row_end", "halo_top", "halo_bottom")]
+
+
+class SepKernel(C.Structure):
+    """mi_blur_sep_kernel: per axis a radius (0..16), 2r+1 taps summing to 2^b (b <= 8)."""
+    _fields_ = [("rx", C.c_int), ("ry", C.c_int), ("bx", C.c_int), ("by", C.c_int),
+                ("wx", C.c_uint16 * (2 * SEP_MAX_RADIUS + 1)), ("wy", C.c_uint16 * (2 * SEP_MAX_RADIUS + 1))]
+
+    @classmethod
+    def from_taps(cls, wx, wy=None) -> "SepKernel":
+        """Taps per axis (sequences of odd length <= 33, each summing to a power of two <= 256); wy None = wx."""
+        wy = wx if wy is None else wy
+        k = cls()
+        for axis, taps in (("x", list(wx)), ("y", list(wy))):
+            n, total = len(taps), int(sum(taps))
+            if n % 2 != 1 or n > 2 * SEP_MAX_RADIUS + 1 or total <= 0 or total & (total - 1):
+                raise ValueError(f"taps {axis}: odd length <= {2 * SEP_MAX_RADIUS + 1}, summing to a power of two")
+            setattr(k, "r" + axis, n // 2)
+            setattr(k, "b" + axis, total.bit_length() - 1)
+            arr = getattr(k, "w" + axis)
+            for i, t in enumerate(taps):
+                arr[i] = int(t)
+        return k
+
+    def taps(self) -> tuple[list[int], list[int]]:
+        return list(self.wx[:2 * self.rx + 1]), list(self.wy[:2 * self.ry + 1])
 
 
 class MiBlurError(RuntimeError):
@@ -159,6 +185,12 @@ def lib() -> C.CDLL:
         "mi_blur_resident_run": (i, [vp, i, i, i]),
         "mi_blur_timed_coverage": (None, [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "mi_blur_cpu_run": (i, [u8p, u8p, i, i, i, i, i, i]),
+        "mi_blur_gauss_taps": (i, [C.c_double, i, i, C.POINTER(C.c_uint16), C.POINTER(i)]),
+        "mi_blur_sep_kernel_gauss": (i, [C.c_double, C.c_double, i, i, C.POINTER(SepKernel)]),
+        "mi_blur_enqueue_sep": (i, [u8p, u8p, i, i, i, i, C.POINTER(SepKernel), vp]),
+        "mi_blur_enqueue_sep_band": (i, [u8p, u8p, i, i, i, i, i, C.POINTER(SepKernel), vp]),
+        "mi_blur_cpu_run_sep": (i, [u8p, u8p, i, i, i, i, C.POINTER(SepKernel), i]),
+        "mi_blur_ctx_set_kernel": (i, [vp, C.POINTER(SepKernel)]),
         "mi_blur_fill_synthetic": (None, [u8p, i, i, i, i, i, i]),
         "mi_blur_fnv1a64": (C.c_uint64, [u8p, C.c_size_t]),
         "mi_blur_debug_zc_trace": (i, [vp, C.POINTER(C.c_uint64), i, C.POINTER(i), C.POINTER(C.c_uint)]),
@@ -215,6 +247,22 @@ def device_cpulist(device: int) -> tuple[str, int]:
     return (buf.value.decode() if rc == OK else "", node.value)
 
 
+def gauss_taps(sigma: float, radius: int = 0, bits: int = 8) -> list[int]:
+    """Integer Gaussian taps (mi_blur_gauss_taps): 2r'+1 values summing to 2^bits, r' the trimmed radius."""
+    taps = (C.c_uint16 * (2 * SEP_MAX_RADIUS + 1))()
+    r = C.c_int()
+    check(lib().mi_blur_gauss_taps(float(sigma), int(radius), int(bits), taps, C.byref(r)), "mi_blur_gauss_taps")
+    return list(taps[:2 * r.value + 1])
+
+
+def gauss_kernel(sigma: float, sigma_y: float | None = None, radius: int = 0, bits: int = 8) -> SepKernel:
+    """Both axes (mi_blur_sep_kernel_gauss); sigma_y None = sigma."""
+    k = SepKernel()
+    check(lib().mi_blur_sep_kernel_gauss(float(sigma), float(sigma_y or 0.0), int(radius), int(bits), C.byref(k)),
+          "mi_blur_sep_kernel_gauss")
+    return k
+
+
 def a2_split(height: int, gpu_ratio: float, halo: int = 1) -> dict:
     g = A2Geometry()
     lib().mi_blur_a2_split(height, gpu_ratio, halo, C.byref(g))
@@ -254,6 +302,16 @@ class Context:
             self.close()
         except Exception:
             pass
+
+    def set_kernel(self, kernel: "SepKernel") -> None:
+        """A separable kernel in place of the radius, for every submit (before the first one only)."""
+        check(lib().mi_blur_ctx_set_kernel(self.h, C.byref(kernel)), "mi_blur_ctx_set_kernel")
+        self.kernel = kernel
+
+    def submit_bands(self, host_in, host_out, n_images: int, host_image_stride: int, band_rows: int,
+                     halo_top: int, halo_bottom: int) -> None:
+        check(lib().mi_blur_submit_bands(self.h, host_in, host_out, n_images, host_image_stride, band_rows, halo_top,
+                                         halo_bottom), "mi_blur_submit_bands")
 
     def submit(self, host_in, host_out, n_images: int) -> None:
         check(lib().mi_blur_submit(self.h, host_in, host_out, n_images), "mi_blur_submit")
@@ -365,3 +423,34 @@ def blur(images, ksize: int = 3, device: int = 0, batch: int = 0):
             ctx.submit(a.ctypes.data + i * isz, out.ctypes.data + i * isz, m)
         ctx.sync()
     return out[0] if single else out
+
+
+def gaussian_blur(images, sigma: float, sigma_y: float | None = None, radius: int = 0, device: int = 0, batch: int = 0):
+    """Gaussian blur of any sigma (anisotropic with sigma_y), numpy in -> numpy out, like blur().
+
+    Integer taps from gauss_taps (8 bits per axis), radius 0 = ceil(3 sigma) clamped to [1, 16] per axis.  images: (H, W),
+    (H, W, C) or (N, H, W, C) uint8; the result has the same shape.  device: HIP ordinal, or DEVICE_CPU.  Goes through mi_blur_create /
+    mi_blur_ctx_set_kernel / mi_blur_submit / mi_blur_sync."""
+    import numpy as np
+    a = np.ascontiguousarray(images)
+    if a.dtype != np.uint8 or a.ndim not in (2, 3, 4):
+        raise ValueError("gaussian_blur: a uint8 array of shape (H, W), (H, W, C) or (N, H, W, C)")
+    kernel = gauss_kernel(sigma, sigma_y, radius)
+    shape = a.shape
+    if a.ndim == 2:
+        a = a[None, :, :, None]
+    elif a.ndim == 3:
+        a = a[None]
+    n, h, w, c = a.shape
+    out = np.empty_like(a)
+    if n == 0 or a.size == 0:
+        return out.reshape(shape)
+    per = min(n, batch if batch > 0 else 4096)
+    isz = h * w * c
+    with Context(device, w, h, c, 1, max_batch=per, n_slots=2) as ctx:
+        ctx.set_kernel(kernel)
+        for i in range(0, n, per):
+            m = min(per, n - i)
+            ctx.submit(a.ctypes.data + i * isz, out.ctypes.data + i * isz, m)
+        ctx.sync()
+    return out.reshape(shape)

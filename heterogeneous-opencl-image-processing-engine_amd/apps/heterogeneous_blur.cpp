@@ -1,7 +1,7 @@
 // heterogeneous_blur — Approach 1 (image-level distribution) host, MI355X-native.
 //
 //   heterogeneous_blur {cpu|gpu|both} [gpu_ratio] [batch]  [--image F | --synthetic | --size WxH] [--channels C]
-//                      [--ksize 3|5] [--images N] [--gpus G] [--slots S] [--threads T] [--resident [--fused]]
+//                      [--ksize 3|5 | --sigma S [--sigma-y S] [--radius R]] [--images N] [--gpus G] [--slots S] [--threads T] [--resident [--fused]]
 //                      [--verbose] [--csv FILE] [--save FILE]
 //                      [--frames DIR|PATTERN|FILE [--save-dir DIR] [--planar-out | --native-layout]]   (cpu | gpu)
 //
@@ -94,7 +94,10 @@ int main(int argc, char **argv)
     printf("Number of batches: %d\n", NUM_BATCHES);
     printf("Work-group size: %dx%d\n", local_work_size, local_work_size);
     printf("Execution mode : %d\n", mode);
-    printf("Blur kernel: %dx%d\n", opt.ksize, opt.ksize);
+    mi_blur_sep_kernel sep{};
+    const bool use_sep = sep_kernel_of(opt, &sep);
+    if (use_sep) print_sep_kernel(sep, opt.sigma, opt.sigma_y);
+    else printf("Blur kernel: %dx%d\n", opt.ksize, opt.ksize);
     printf("================================================\n\n");
 
     if (!frame_files.empty()) {
@@ -137,6 +140,7 @@ int main(int argc, char **argv)
     if (mode != 2) {
         mi_check(mi_blur_create(&cpu.ctx, MI_BLUR_DEVICE_CPU, width, height, channels, radius, BATCH_SIZE, nslots, opt.threads),
                  "Failed to create CPU context");
+        if (use_sep) mi_check(mi_blur_ctx_set_kernel(cpu.ctx, &sep), "Failed to set the blur kernel");
         const unsigned hc = std::thread::hardware_concurrency();
         cpu.name = "host threads x" + std::to_string(opt.threads > 0 ? opt.threads : std::min((int)(hc ? hc : 1), 16));
         printf("CPU device: %s\n", cpu.name.c_str());
@@ -154,6 +158,7 @@ int main(int argc, char **argv)
         mi_check(per_gpu_feeders ? mi_blur_create(&gpus[g].ctx, hip_ordinal(g), width, height, channels, radius, feed_piece, nslots * feed_pieces, 0)
                                  : mi_blur_create(&gpus[g].ctx, hip_ordinal(g), width, height, channels, radius, BATCH_SIZE, nslots, 0),
                  "Failed to create GPU context");
+        if (use_sep) mi_check(mi_blur_ctx_set_kernel(gpus[g].ctx, &sep), "Failed to set the blur kernel");
         gpus[g].name = "HIP device " + std::to_string(hip_ordinal(g)) + (virtual_gpus() ? " (logical GPU " + std::to_string(g) + ")" : "");
         printf("GPU device: %s\n", gpus[g].name.c_str());
         gpus[g].submitted.assign(NUM_BATCHES, 0);
@@ -539,6 +544,8 @@ static int run_frames(const Options &opt, int mode, int BATCH_SIZE, const std::v
     for (int g = 0; g < G; g++) {
         mi_check(mi_blur_create(&ctx[g], mode == 1 ? MI_BLUR_DEVICE_CPU : hip_ordinal(g), width, height, ctx_channels, radius, BATCH_SIZE * per_frame,
                                 per_dev_slots, opt.threads), "Failed to create context");
+        mi_blur_sep_kernel sep{};
+        if (sep_kernel_of(opt, &sep)) mi_check(mi_blur_ctx_set_kernel(ctx[g], &sep), "Failed to set the blur kernel");
         if (mode == 2) { printf("GPU device: HIP device %d\n", hip_ordinal(g)); report_placement(g, hip_ordinal(g), g == 0); }
         else printf("CPU device: host threads\n");
     }

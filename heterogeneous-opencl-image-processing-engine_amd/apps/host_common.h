@@ -159,6 +159,10 @@ struct Options {
     bool synthetic = false;              // --synthetic
     int syn_w = 320, syn_h = 240, syn_c = 3;   // --size WxH, --channels C
     int ksize = 3;                       // --ksize 3|5
+    bool ksize_given = false;
+    double sigma = 0.0;                  // --sigma S [--sigma-y S] [--radius R]: separable Gaussian of that sigma (radius 0 = ceil(3 sigma),
+    double sigma_y = 0.0;                //              at most 16) instead of --ksize; mi_blur_ctx_set_kernel on every context
+    int sep_radius = 0;
     int images = 5000;                   // --images N   (NUM_IMAGES, heterogeneous_blur.c:44)
     bool images_given = false;
     int gpus = 1;                        // --gpus G
@@ -207,7 +211,10 @@ inline int parse_flags(int argc, char **argv, Options &o)
         else if (a == "--synthetic") o.synthetic = true;
         else if (a == "--size") { if (sscanf(next("--size"), "%dx%d", &o.syn_w, &o.syn_h) != 2 || o.syn_w <= 0 || o.syn_h <= 0) { printf("Error: --size WxH\n"); exit(-1); } o.synthetic = true; o.size_given = true; }
         else if (a == "--channels") o.syn_c = atoi(next("--channels"));
-        else if (a == "--ksize") { o.ksize = atoi(next("--ksize")); if (o.ksize != 3 && o.ksize != 5) { printf("Error: --ksize must be 3 or 5\n"); exit(-1); } }
+        else if (a == "--ksize") { o.ksize = atoi(next("--ksize")); if (o.ksize != 3 && o.ksize != 5) { printf("Error: --ksize must be 3 or 5\n"); exit(-1); } o.ksize_given = true; }
+        else if (a == "--sigma") { o.sigma = atof(next("--sigma")); if (!(o.sigma > 0.0)) { printf("Error: --sigma must be > 0\n"); exit(-1); } }
+        else if (a == "--sigma-y") { o.sigma_y = atof(next("--sigma-y")); if (!(o.sigma_y > 0.0)) { printf("Error: --sigma-y must be > 0\n"); exit(-1); } }
+        else if (a == "--radius") { o.sep_radius = atoi(next("--radius")); if (o.sep_radius < 1 || o.sep_radius > MI_BLUR_SEP_MAX_RADIUS) { printf("Error: --radius must be 1..%d\n", MI_BLUR_SEP_MAX_RADIUS); exit(-1); } }
         else if (a == "--images") { o.images = atoi(next("--images")); if (o.images < 1) { printf("Error: --images must be >= 1\n"); exit(-1); } o.images_given = true; }
         else if (a == "--gpus") o.gpus = atoi(next("--gpus"));
         else if (a == "--slots") { o.slots = atoi(next("--slots")); if (o.slots < 1) o.slots = 1; o.slots_given = true; }
@@ -230,7 +237,30 @@ inline int parse_flags(int argc, char **argv, Options &o)
         else if (a == "--transport") { o.transport = next("--transport"); if (o.transport != "rccl" && o.transport != "p2p" && o.transport != "pull" && o.transport != "peer") { printf("Error: --transport rccl|p2p|pull|peer\n"); exit(-1); } }
         else { printf("Error: unknown option %s\n", a.c_str()); exit(-1); }
     }
+    if (o.sigma > 0.0 && o.ksize_given) { printf("Error: --sigma and --ksize exclude each other\n"); exit(-1); }
+    if (o.sigma <= 0.0 && (o.sigma_y > 0.0 || o.sep_radius > 0)) { printf("Error: --sigma-y and --radius need --sigma\n"); exit(-1); }
+    if (o.sigma > 0.0 && o.resident) { printf("Error: --sigma does not run --resident\n"); exit(-1); }
     return npos;
+}
+
+// --sigma: the separable Gaussian every context of the run is given (mi_blur_sep_kernel_gauss, 8-bit taps per axis).
+inline bool sep_kernel_of(const Options &o, mi_blur_sep_kernel *k)
+{
+    if (o.sigma <= 0.0) return false;
+    if (mi_blur_sep_kernel_gauss(o.sigma, o.sigma_y, o.sep_radius, 8, k) != MI_BLUR_OK) {
+        printf("Error: no Gaussian taps for sigma %g / %g, radius %d\n", o.sigma, o.sigma_y, o.sep_radius);
+        exit(-1);
+    }
+    return true;
+}
+inline void print_sep_kernel(const mi_blur_sep_kernel &k, double sx, double sy)
+{
+    printf("Blur kernel: %dx%d separable Gaussian, sigma %g x %g\n", 2 * k.rx + 1, 2 * k.ry + 1, sx, sy > 0.0 ? sy : sx);
+    printf("Taps x (/%d):", 1 << k.bx);
+    for (int i = 0; i <= 2 * k.rx; i++) printf(" %d", k.wx[i]);
+    printf("\nTaps y (/%d):", 1 << k.by);
+    for (int j = 0; j <= 2 * k.ry; j++) printf(" %d", k.wy[j]);
+    printf("\n");
 }
 
 constexpr double HBM_PEAK_GBS = 8000.0;   // MI355X HBM3E spec; ~6290 GB/s measured copy ceiling

@@ -1,6 +1,6 @@
 // split_image_blur — Approach 2 (split-image + halo) host, MI355X-native.
 //
-//   split_image_blur [gpu_ratio] [batch]  [--image F | --synthetic | --size WxH] [--channels C] [--ksize 3|5]
+//   split_image_blur [gpu_ratio] [batch]  [--image F | --synthetic | --size WxH] [--channels C] [--ksize 3|5 | --sigma S [--sigma-y S] [--radius R]]
 //                    [--images N] [--gpus G] [--slots S] [--threads T] [--verbose] [--csv FILE] [--save FILE]
 //   split_image_blur --resident [--gpus G] [--size WxH] [--ksize 3|5] [--iters N] [--iterate] [--overlap]
 //                    [--transport rccl|p2p|pull|peer] [--save FILE]
@@ -44,7 +44,11 @@ int main(int argc, char **argv)
     const int npos = parse_flags(argc, argv, opt);
     if (opt.resident) return run_resident(opt);
     const int NUM_IMAGES = opt.images;
-    const int HALO = opt.ksize == 3 ? 1 : 2;
+    mi_blur_sep_kernel sep{};
+    const bool use_sep = sep_kernel_of(opt, &sep);
+    // --sigma: the halo is the kernel's vertical radius (at least one row, so the split geometry stays the reference's)
+    const int HALO = use_sep ? std::max(1, sep.ry) : opt.ksize == 3 ? 1 : 2;
+    const int ctx_radius = use_sep ? 1 : HALO;          // contexts take the separable kernel right after creation
 
     if (npos > 1) {
         gpu_ratio = atof(argv[1]);
@@ -72,6 +76,7 @@ int main(int argc, char **argv)
     printf("Work-group size: %dx%d\n", local_work_size, local_work_size);
     printf("GPU ratio: %.1f%% (rows to GPU)\n", gpu_ratio * 100);
     printf("Halo size: %d row(s)\n", HALO);
+    if (use_sep) print_sep_kernel(sep, opt.sigma, opt.sigma_y);
     printf("================================================\n\n");
 
     // ---------------- load original image (split_image_blur.c:106-139)
@@ -111,8 +116,9 @@ int main(int argc, char **argv)
     Part cpu;
     cpu.in_row0 = 0; cpu.band_rows = geo.cpu_input_rows; cpu.halo_top = 0; cpu.halo_bottom = HALO;
     cpu.out_row0 = 0; cpu.out_rows = geo.cpu_output_rows;
-    mi_check(mi_blur_create(&cpu.ctx, MI_BLUR_DEVICE_CPU, width, height, channels, HALO, BATCH_SIZE, nslots, opt.threads),
+    mi_check(mi_blur_create(&cpu.ctx, MI_BLUR_DEVICE_CPU, width, height, channels, ctx_radius, BATCH_SIZE, nslots, opt.threads),
              "Failed to create CPU context");
+    if (use_sep) mi_check(mi_blur_ctx_set_kernel(cpu.ctx, &sep), "Failed to set the blur kernel");
     cpu.name = "host threads";
     printf("CPU device: %s\n", cpu.name.c_str());
     std::vector<Part> gpus(G);
@@ -127,7 +133,8 @@ int main(int argc, char **argv)
         p.in_row0 = p.out_row0 - p.halo_top;
         p.band_rows = p.out_rows + p.halo_top + p.halo_bottom;
         if (p.out_rows <= 0) { printf("Error: more GPUs than GPU rows\n"); return -1; }
-        mi_check(mi_blur_create(&p.ctx, hip_ordinal(g), width, height, channels, HALO, BATCH_SIZE, nslots, 0), "Failed to create GPU context");
+        mi_check(mi_blur_create(&p.ctx, hip_ordinal(g), width, height, channels, ctx_radius, BATCH_SIZE, nslots, 0), "Failed to create GPU context");
+        if (use_sep) mi_check(mi_blur_ctx_set_kernel(p.ctx, &sep), "Failed to set the blur kernel");
         p.name = "HIP device " + std::to_string(hip_ordinal(g));
         printf("GPU device: %s (rows %d-%d)\n", p.name.c_str(), p.out_row0, p.out_row0 + p.out_rows - 1);
     }

@@ -1246,6 +1246,7 @@ bool tiled_eligible(const void *in, const void *out, int width, int channels)
 
 static thread_local const char *g_last_kernel = "";
 const char *last_kernel() { return g_last_kernel; }
+void set_last_kernel(const char *name) { g_last_kernel = name; }
 
 static inline int hip_status(hipError_t e) { return e == hipSuccess ? MI_BLUR_OK : MI_BLUR_ERR_HIP_BASE - (int)e; }
 
@@ -1713,6 +1714,7 @@ static int launch_generic(const LaunchDesc &d)
 
 int launch(const LaunchDesc &d)
 {
+    if (d.sep) return launch_sep(d);
     if (!d.in || !d.out || d.in == d.out) return MI_BLUR_ERR_INVALID;
     if (d.width <= 0 || d.band_rows <= 0 || d.channels <= 0 || d.n_images < 0) return MI_BLUR_ERR_INVALID;
     if (d.radius != 1 && d.radius != 2) return MI_BLUR_ERR_INVALID;

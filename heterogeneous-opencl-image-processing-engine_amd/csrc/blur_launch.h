@@ -4,9 +4,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sep_taps.h"
+
 namespace mi_blur {
 
 struct LaunchDesc {
+    const SepTaps *sep;     // non-null: this separable kernel instead of `radius` (launch_sep, sep_kernels.hip)
     const uint8_t *in;      // device, n_images bands of band_rows rows, laid end to end
     uint8_t *out;           // device, n_images blocks of (y1-y0) rows
     int width, band_rows, channels, radius;
@@ -24,8 +27,14 @@ struct LaunchDesc {
     hipEvent_t start, stop; // optional: dispatch start/stop timestamps (hipExtLaunchKernel)
 };
 
-// Returns MI_BLUR_OK or a negative mi_blur_status.
+// Returns MI_BLUR_OK or a negative mi_blur_status.  d.sep set: handed to launch_sep.
 int launch(const LaunchDesc &d);
+// Separable kernel of d.sep (sep_kernels.hip): the aligned LDS-tiled kernel or the generic one.  Honours in/out strides,
+// bands [y0, y1) and the per-image 32-bit offsets of launch(); ignores max_blocks, concurrent and variant (AUTO);
+// halo_top / halo_bottom: MI_BLUR_ERR_UNSUPPORTED.
+int launch_sep(const LaunchDesc &d);
+// Sets what last_kernel() reports for the calling thread.
+void set_last_kernel(const char *name);
 
 // Fused stream (blur_fused_kernel): one dispatch over d.n_images images whose blocks are ordered in batches of
 // batch_images; every block of batch b adds *waves_per_block (1) to one of count[kb .. kb+k-1], k = *counters_per_batch

@@ -160,10 +160,55 @@ void cpu_blur_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, int R, 
     }
 }
 
+// The same two passes at runtime taps: vertical sums <= 255 * 256 (16 bits), horizontal sums < 2^24 in 32 bits, one
+// truncating shift.  R = 1 | 2 with the binomial taps is what cpu_blur_rows computes.
+void cpu_blur_rows_sep(const uint8_t *in, uint8_t *out, int W, int H, int C, const SepTaps &k, int y_begin, int y_end,
+                       int out_row_shift)
+{
+    const int pitch = W * C, pad = k.rx * C, nj = 2 * k.ry + 1;
+    std::vector<uint16_t> scratch((size_t)pitch + 2 * pad);
+    uint16_t *v = scratch.data() + pad;               // v[-pad .. pitch+pad)
+    std::vector<uint32_t> acc((size_t)pitch);
+    const uint8_t *rows[2 * SEP_MAX_R + 1];
+    uint16_t wy[2 * SEP_MAX_R + 1], wx[2 * SEP_MAX_R + 1];
+    for (int j = 0; j < nj; j++) wy[j] = (uint16_t)k.wy[SEP_MAX_R - k.ry + j];
+    for (int i = 0; i <= 2 * k.rx; i++) wx[i] = (uint16_t)k.wx[SEP_MAX_R - k.rx + i];
+    for (int y = y_begin; y < y_end; y++) {
+        for (int j = 0; j < nj; j++) rows[j] = in + (size_t)std::min(std::max(y + j - k.ry, 0), H - 1) * pitch;
+        {
+            const uint8_t *a = rows[0];
+            const uint16_t w0 = wy[0];
+            for (int b = 0; b < pitch; b++) v[b] = (uint16_t)(w0 * a[b]);
+        }
+        for (int j = 1; j < nj; j++) {
+            const uint8_t *a = rows[j];
+            const uint16_t w = wy[j];
+            if (w) for (int b = 0; b < pitch; b++) v[b] = (uint16_t)(v[b] + w * a[b]);
+        }
+        for (int q = 1; q <= pad; q++) {
+            v[-q] = v[((-q % C) + C) % C];
+            v[pitch + q - 1] = v[pitch - C + ((q - 1) % C)];
+        }
+        uint32_t *s = acc.data();
+        {
+            const uint16_t *a = v - pad;
+            const uint32_t w0 = wx[0];
+            for (int b = 0; b < pitch; b++) s[b] = w0 * a[b];
+        }
+        for (int i = 1; i <= 2 * k.rx; i++) {
+            const uint16_t *a = v + (i - k.rx) * C;
+            const uint32_t w = wx[i];
+            if (w) for (int b = 0; b < pitch; b++) s[b] += w * a[b];
+        }
+        uint8_t *o = out + (size_t)(y - out_row_shift) * pitch;
+        for (int b = 0; b < pitch; b++) o[b] = (uint8_t)(s[b] >> k.shift);
+    }
+}
+
 // n_images bands of band_rows rows; output rows [y0,y1) of each.  Threads take whole
 // images when there are enough of them, else row slices of each image.
 void cpu_blur_batch(const uint8_t *in, uint8_t *out, int W, int band_rows, int C, int R, int n_images,
-                    int y0, int y1, int n_threads, size_t in_stride, size_t out_stride)
+                    int y0, int y1, int n_threads, size_t in_stride, size_t out_stride, const SepTaps *sep)
 {
     if (n_images <= 0) return;
     if (n_threads <= 0) n_threads = hardware_threads();
@@ -185,7 +230,8 @@ void cpu_blur_batch(const uint8_t *in, uint8_t *out, int W, int band_rows, int C
             if (it >= items) break;
             const int img = (int)(it / slices), s = (int)(it % slices);
             const int ys = y0 + (int)((long long)rows * s / slices), ye = y0 + (int)((long long)rows * (s + 1) / slices);
-            cpu_blur_rows(in + img * in_stride, out + img * out_stride, W, band_rows, C, R, ys, ye, y0);
+            if (sep) cpu_blur_rows_sep(in + img * in_stride, out + img * out_stride, W, band_rows, C, *sep, ys, ye, y0);
+            else cpu_blur_rows(in + img * in_stride, out + img * out_stride, W, band_rows, C, R, ys, ye, y0);
         }
     };
     const int nt = (int)std::min<long long>(n_threads, items);

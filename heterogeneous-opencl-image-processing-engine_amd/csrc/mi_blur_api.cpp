@@ -15,6 +15,8 @@
 
 #include <algorithm>
 #include <chrono>
+#include <climits>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -166,6 +168,86 @@ extern "C" int mi_blur_enqueue_band_peer(const uint8_t *d_in, uint8_t *d_out, in
     d.radius = radius; d.n_images = 1; d.y0 = out_row_begin; d.y1 = out_row_end;
     d.variant = MI_BLUR_VARIANT_AUTO; d.stream = (hipStream_t)stream;
     d.halo_top = top_src; d.halo_bottom = bottom_src;
+    return launch(d);
+}
+
+// ----------------------------------------------------------------------------------
+// separable kernels of any radius up to 16 (no reference analogue)
+// ----------------------------------------------------------------------------------
+// Validate a mi_blur_sep_kernel and centre its taps for the kernels (sep_taps.h).
+static int sep_prepare(const mi_blur_sep_kernel *k, SepTaps *t)
+{
+    if (!k || !t) return MI_BLUR_ERR_INVALID;
+    if (k->rx < 0 || k->rx > MI_BLUR_SEP_MAX_RADIUS || k->ry < 0 || k->ry > MI_BLUR_SEP_MAX_RADIUS) return MI_BLUR_ERR_INVALID;
+    if (k->bx < 0 || k->bx > 8 || k->by < 0 || k->by > 8) return MI_BLUR_ERR_INVALID;
+    *t = SepTaps{};
+    long long sx = 0, sy = 0;
+    for (int i = 0; i <= 2 * k->rx; i++) { sx += k->wx[i]; t->wx[SEP_MAX_R - k->rx + i] = k->wx[i]; }
+    for (int j = 0; j <= 2 * k->ry; j++) { sy += k->wy[j]; t->wy[SEP_MAX_R - k->ry + j] = k->wy[j]; }
+    if (sx != (1LL << k->bx) || sy != (1LL << k->by)) return MI_BLUR_ERR_INVALID;
+    t->rx = k->rx; t->ry = k->ry; t->shift = k->bx + k->by;
+    return MI_BLUR_OK;
+}
+
+extern "C" int mi_blur_gauss_taps(double sigma, int radius, int bits, uint16_t *taps, int *radius_out)
+{
+    if (!taps || !(sigma > 0.0) || radius < 0 || radius > MI_BLUR_SEP_MAX_RADIUS || bits < 0 || bits > 8) return MI_BLUR_ERR_INVALID;
+    const int r = radius ? radius : (int)std::min(16.0, std::max(1.0, std::ceil(3.0 * sigma)));
+    double w[2 * MI_BLUR_SEP_MAX_RADIUS + 1], sum = 0.0;
+    for (int i = -r; i <= r; i++) { w[i + r] = std::exp(-(double)i * i / (2.0 * sigma * sigma)); sum += w[i + r]; }
+    long long t[2 * MI_BLUR_SEP_MAX_RADIUS + 1], tsum = 0;
+    const double scale = (double)(1 << bits);
+    for (int i = 0; i <= 2 * r; i++) { t[i] = (long long)std::floor(w[i] * scale / sum + 0.5); tsum += t[i]; }
+    t[r] += (1LL << bits) - tsum;                       // the centre absorbs the rounding
+    if (t[r] <= 0) return MI_BLUR_ERR_INVALID;
+    int re = r;                                         // drop outer pairs that rounded to 0
+    while (re > 0 && t[r - re] == 0 && t[r + re] == 0) re--;
+    for (int i = 0; i <= 2 * re; i++) taps[i] = (uint16_t)t[r - re + i];
+    if (radius_out) *radius_out = re;
+    return MI_BLUR_OK;
+}
+
+extern "C" int mi_blur_sep_kernel_gauss(double sigma_x, double sigma_y, int radius, int bits, mi_blur_sep_kernel *k)
+{
+    if (!k) return MI_BLUR_ERR_INVALID;
+    if (sigma_y <= 0.0) sigma_y = sigma_x;
+    mi_blur_sep_kernel g{};
+    int rc = mi_blur_gauss_taps(sigma_x, radius, bits, g.wx, &g.rx);
+    if (rc) return rc;
+    rc = mi_blur_gauss_taps(sigma_y, radius, bits, g.wy, &g.ry);
+    if (rc) return rc;
+    g.bx = g.by = bits;
+    *k = g;
+    return MI_BLUR_OK;
+}
+
+extern "C" int mi_blur_enqueue_sep_band(const uint8_t *d_in, uint8_t *d_out, int width, int band_rows, int channels,
+                                        int out_row_begin, int out_row_end, const mi_blur_sep_kernel *k, void *stream)
+{
+    SepTaps t;
+    const int rc = sep_prepare(k, &t);
+    if (rc) return rc;
+    if (mi_blur_device_count() <= 0) return MI_BLUR_ERR_NO_DEVICE;
+    LaunchDesc d{};
+    d.sep = &t;
+    d.in = d_in; d.out = d_out; d.width = width; d.band_rows = band_rows; d.channels = channels;
+    d.n_images = 1; d.y0 = out_row_begin; d.y1 = out_row_end;
+    d.variant = MI_BLUR_VARIANT_AUTO; d.stream = (hipStream_t)stream;
+    return launch(d);
+}
+
+extern "C" int mi_blur_enqueue_sep(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int n_images,
+                                   const mi_blur_sep_kernel *k, void *stream)
+{
+    SepTaps t;
+    const int rc = sep_prepare(k, &t);
+    if (rc) return rc;
+    if (mi_blur_device_count() <= 0) return MI_BLUR_ERR_NO_DEVICE;
+    LaunchDesc d{};
+    d.sep = &t;
+    d.in = d_in; d.out = d_out; d.width = width; d.band_rows = height; d.channels = channels;
+    d.n_images = n_images; d.y0 = 0; d.y1 = height;
+    d.variant = MI_BLUR_VARIANT_AUTO; d.stream = (hipStream_t)stream;
     return launch(d);
 }
 
@@ -323,6 +405,11 @@ struct mi_blur_ctx {
     // CPU device
     std::vector<CpuJob *> cpu_jobs;
     CpuWorker *cpu_worker = nullptr;
+    // separable kernel (mi_blur_ctx_set_kernel): replaces R in every submit
+    bool has_sep = false;
+    SepTaps sep{};
+    bool submitted = false;                                      // set_kernel only before this
+    const SepTaps *sep_or_null() const { return has_sep ? &sep : nullptr; }
     bool is_cpu() const { return device == MI_BLUR_DEVICE_CPU; }
 };
 
@@ -712,6 +799,7 @@ extern "C" void mi_blur_destroy(mi_blur_ctx *c)
 // than the running server's): the caller launches the batch the classic way.
 static int zc_server_submit(mi_blur_ctx *c, Slot &s, const LaunchDesc &d, const Tunables &tun)
 {
+    if (c->has_sep) return MI_BLUR_ERR_UNSUPPORTED;         // the server's tiles are the radius-1|2 kernel's: one launch per batch
     if (c->slots.size() > ZC_RING) return MI_BLUR_ERR_UNSUPPORTED;
     if (!c->zc) {
         ZcServer *z = new (std::nothrow) ZcServer;
@@ -797,11 +885,14 @@ static int submit_common(mi_blur_ctx *c, const uint8_t *host_in, uint8_t *host_o
     const size_t in_bytes = band_in * n_images, out_bytes = band_out * n_images;
     if (in_stride == 0) in_stride = band_in;
     if (out_stride == 0) out_stride = band_out;
+    c->submitted = true;
     if (c->is_cpu()) {
         CpuJob *j = new (std::nothrow) CpuJob;
         if (!j) return MI_BLUR_ERR_NOMEM;
         const int W = c->W, C = c->C, R = c->R, nt = c->n_threads;
-        j->work = [=]() { cpu_blur_batch(host_in, host_out, W, band_rows, C, R, n_images, y0, y1, nt, in_stride, out_stride); };
+        const bool has_sep = c->has_sep;
+        const SepTaps sep = c->sep;
+        j->work = [=]() { cpu_blur_batch(host_in, host_out, W, band_rows, C, R, n_images, y0, y1, nt, in_stride, out_stride, has_sep ? &sep : nullptr); };
         if (!c->cpu_worker) { c->cpu_worker = new (std::nothrow) CpuWorker; if (!c->cpu_worker) { delete j; return MI_BLUR_ERR_NOMEM; } }
         c->cpu_worker->push(j);
         c->cpu_jobs.push_back(j);
@@ -833,6 +924,7 @@ static int submit_common(mi_blur_ctx *c, const uint8_t *host_in, uint8_t *host_o
                 LaunchDesc d{};
                 d.in = zin; d.out = zout; d.width = c->W; d.band_rows = band_rows; d.channels = c->C;
                 d.radius = c->R; d.n_images = n_images; d.y0 = y0; d.y1 = y1; d.variant = MI_BLUR_VARIANT_AUTO;
+                d.sep = c->sep_or_null();
                 d.in_stride = (long long)in_stride; d.out_stride = (long long)out_stride;
                 // small batches stay with one launch each: the server's hand-off (descriptor over the link, poller, completion
                 // word, the host's wait) costs ~26 us per batch against ~8 us for a launch — below ~1.3 MB each way the launch
@@ -902,6 +994,7 @@ static int submit_common(mi_blur_ctx *c, const uint8_t *host_in, uint8_t *host_o
                 LaunchDesc d{};
                 d.in = zin; d.out = zout; d.width = c->W; d.band_rows = band_rows; d.channels = c->C;
                 d.radius = c->R; d.n_images = n_images; d.y0 = y0; d.y1 = y1; d.variant = MI_BLUR_VARIANT_AUTO;
+                d.sep = c->sep_or_null();
                 d.in_stride = (long long)src_stride; d.out_stride = (long long)zout_stride;
                 rc = zc_server_submit(c, s, d, tun);
                 if (rc == MI_BLUR_OK) {
@@ -928,6 +1021,7 @@ static int submit_common(mi_blur_ctx *c, const uint8_t *host_in, uint8_t *host_o
         LaunchDesc d{};
         d.in = s.d_in; d.out = s.d_out; d.width = c->W; d.band_rows = band_rows; d.channels = c->C;
         d.radius = c->R; d.n_images = n_images; d.y0 = y0; d.y1 = y1; d.variant = MI_BLUR_VARIANT_AUTO;
+        d.sep = c->sep_or_null();
         d.stream = s.stream; d.start = s.ks; d.stop = s.ke;
         d.concurrent = (int)c->slots.size();
         rc = launch(d);
@@ -990,14 +1084,17 @@ extern "C" int mi_blur_submit_planar(mi_blur_ctx *c, const uint8_t *host_planar_
     if (n_images < 0 || n_images > c->max_batch) return MI_BLUR_ERR_INVALID;
     if (n_images == 0) return MI_BLUR_OK;
     const size_t bytes = c->image_bytes * (size_t)n_images;
+    c->submitted = true;
     if (c->is_cpu()) {
         CpuJob *j = new (std::nothrow) CpuJob;
         if (!j) return MI_BLUR_ERR_NOMEM;
         const int W = c->W, H = c->H, C = c->C, R = c->R, nt = c->n_threads;
+        const bool has_sep = c->has_sep;
+        const SepTaps sep = c->sep;
         j->work = [=]() {
             std::vector<uint8_t> a(bytes), b(planar_out ? bytes : 0);
             cpu_repack(host_planar_in, a.data(), W, H, C, n_images, true, nt);
-            cpu_blur_batch(a.data(), planar_out ? b.data() : host_out, W, H, C, R, n_images, 0, H, nt);
+            cpu_blur_batch(a.data(), planar_out ? b.data() : host_out, W, H, C, R, n_images, 0, H, nt, 0, 0, has_sep ? &sep : nullptr);
             if (planar_out) cpu_repack(b.data(), host_out, W, H, C, n_images, false, nt);
         };
         if (!c->cpu_worker) { c->cpu_worker = new (std::nothrow) CpuWorker; if (!c->cpu_worker) { delete j; return MI_BLUR_ERR_NOMEM; } }
@@ -1030,6 +1127,7 @@ extern "C" int mi_blur_submit_planar(mi_blur_ctx *c, const uint8_t *host_planar_
         LaunchDesc d{};
         d.in = s.d_in; d.out = s.d_out; d.width = c->W; d.band_rows = c->H; d.channels = c->C;
         d.radius = c->R; d.n_images = n_images; d.y0 = 0; d.y1 = c->H; d.variant = MI_BLUR_VARIANT_AUTO;
+        d.sep = c->sep_or_null();
         d.stream = s.stream; d.start = s.ks; d.stop = s.ke;
         d.concurrent = (int)c->slots.size();
         rc = launch(d);
@@ -1050,6 +1148,19 @@ extern "C" int mi_blur_submit_planar(mi_blur_ctx *c, const uint8_t *host_planar_
     c->tm.bytes_alg += 2ull * bytes;
     c->tm.images += (uint64_t)n_images;
     c->tm.launches += 1;
+    return MI_BLUR_OK;
+}
+
+// A separable kernel in place of the context's radius, for every submit from now on (before the first one only).
+extern "C" int mi_blur_ctx_set_kernel(mi_blur_ctx *c, const mi_blur_sep_kernel *k)
+{
+    if (!c || !k) return MI_BLUR_ERR_INVALID;
+    if (c->submitted) return MI_BLUR_ERR_STATE;
+    SepTaps t;
+    const int rc = sep_prepare(k, &t);
+    if (rc) return rc;
+    c->sep = t;
+    c->has_sep = true;
     return MI_BLUR_OK;
 }
 
@@ -1228,6 +1339,7 @@ extern "C" void *mi_blur_resident_out(mi_blur_ctx *c) { return c ? c->pool_out :
 extern "C" int mi_blur_resident_run(mi_blur_ctx *c, int n_images, int batch, int timed_every)
 {
     if (!c || n_images < 0 || batch <= 0) return MI_BLUR_ERR_INVALID;
+    if (c->has_sep) return MI_BLUR_ERR_UNSUPPORTED;
     if (c->is_cpu() || !c->pool_in) return MI_BLUR_ERR_STATE;
     if (batch > c->pool_images) return MI_BLUR_ERR_INVALID;
     HIP_TRY(hipSetDevice(c->device));
@@ -1274,6 +1386,7 @@ static size_t fused_words(int cap) { return 8 * (size_t)cap + 16384; }
 extern "C" int mi_blur_resident_run_fused(mi_blur_ctx *c, int n_images, int batch, int timed)
 {
     if (!c || n_images <= 0 || batch <= 0) return MI_BLUR_ERR_INVALID;
+    if (c->has_sep) return MI_BLUR_ERR_UNSUPPORTED;
     if (c->is_cpu() || !c->pool_in) return MI_BLUR_ERR_STATE;
     if (n_images > c->pool_images) return MI_BLUR_ERR_INVALID;           // one contiguous run of the pool
     HIP_TRY(hipSetDevice(c->device));
@@ -1416,6 +1529,19 @@ extern "C" int mi_blur_cpu_run(const uint8_t *in, uint8_t *out, int width, int h
         return MI_BLUR_ERR_INVALID;
     if (radius != 1 && radius != 2) return MI_BLUR_ERR_INVALID;
     cpu_blur_batch(in, out, width, height, channels, radius, n_images, 0, height, n_threads);
+    return MI_BLUR_OK;
+}
+
+extern "C" int mi_blur_cpu_run_sep(const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,
+                                   const mi_blur_sep_kernel *k, int n_threads)
+{
+    if (!in || !out || in == out || width <= 0 || height <= 0 || channels <= 0 || n_images < 0)
+        return MI_BLUR_ERR_INVALID;
+    if ((long long)width * channels * height > INT_MAX) return MI_BLUR_ERR_INVALID;
+    SepTaps t;
+    const int rc = sep_prepare(k, &t);
+    if (rc) return rc;
+    cpu_blur_batch(in, out, width, height, channels, 0, n_images, 0, height, n_threads, 0, 0, &t);
     return MI_BLUR_OK;
 }
 

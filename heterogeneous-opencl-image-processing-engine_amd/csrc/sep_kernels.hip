@@ -1,0 +1,374 @@
+// sep_kernels.hip — gfx950 kernels of the separable integer blur of any radius up to 16 (mi_blur_enqueue_sep,
+// include/mi_blur.h):
+//   out[y][x][c] = ( sum_j wy[j] * sum_i wx[i] * in[clamp(y+j-ry)][clamp(x+i-rx)][c] ) >> (bx + by)
+// Taps sum to 2^bx / 2^by <= 256, so a one-axis sum is <= 255 * 256 = 65280 (16 bits) and the full sum < 2^24: every
+// order of evaluation gives the same bits, which licenses a vertical pass in packed 16-bit fields followed by a
+// horizontal one in 32 bits.
+//
+// Tiled kernel (blur_sep_tiled_kernel<C, RB>): rows of whole 16-byte chunks, 16-byte aligned buffers and strides, 1-4
+// channels.  One workgroup = one tile of SEP_TH output rows x ncols (<= 32) chunk columns:
+//   * stage (SEP_TH + 2 ry) rows x (ncols + 2 HC) chunks in LDS with global_load_lds_dwordx4 (LDS-DMA, 16 B per lane; the
+//     LDS image of 64 consecutive tile slots is the 64 lanes in order), source rows clamped to the band.  HC = the halo
+//     chunks either side that the radius bucket RB needs (RB * C bytes).  Halo chunks outside the image row are not
+//     loaded: they are filled with copies of the edge pixel's channels, so the x-clamp costs nothing later;
+//   * vertical pass: each thread takes one chunk column (halo chunks included) and SEP_RPG output rows, walks the
+//     SEP_RPG + 2 ry staged rows once and adds every row into the outputs it belongs to — every dword split into its
+//     even / odd bytes as two 16-bit fields, v_pk_mad_u16 with the row's tap (2 MACs per lane-op).  The sums replace the
+//     staged bytes in LDS (16-bit, even / odd fields kept apart);
+//   * horizontal pass: each thread takes one output chunk, reads the 2 HC + 1 chunks of sums around it and adds the
+//     2 rx + 1 taps at byte offsets d * C (the field pairs are whole dwords or one v_alignbit of two) with v_dot2_u32_u16
+//     against (w, 0) / (0, w); one shift, re-interleave, one 16-byte store.
+//   Taps are kernel arguments (scalar loads), rx and ry runtime bounds; RB in {4, 8, 16} only sizes the registers of
+//   the horizontal window.  4 channels x 3 buckets = 12 instantiations.
+//
+// Generic kernel (blur_sep_generic_kernel): one output byte per thread, any shape, runtime taps.  Correct everywhere,
+// fast nowhere.
+#include "blur_launch.h"
+#include "../../include/mi_blur.h"
+
+#include <hip/hip_ext.h>
+#include <limits.h>
+#include <stdint.h>
+#include <algorithm>
+#include <utility>
+
+namespace mi_blur {
+
+namespace {
+
+typedef unsigned short sep_u16x2 __attribute__((ext_vector_type(2)));
+typedef unsigned int sep_u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ sep_u16x2 pk16(uint32_t x) { return __builtin_bit_cast(sep_u16x2, x); }
+__device__ __forceinline__ uint32_t pk32(sep_u16x2 x) { return __builtin_bit_cast(uint32_t, x); }
+
+constexpr int SEP_TH = 32;          // output rows per tile
+constexpr int SEP_RPG = 8;          // output rows per thread in the vertical pass
+constexpr int SEP_NCOLS = 32;       // at most this many output chunk columns per tile
+constexpr int SEP_THREADS = 256;
+
+constexpr int sep_halo_chunks(int C, int RB) { return (RB * C + 15) / 16; }
+
+struct SepTiledParams {
+    const uint8_t *in;
+    uint8_t *out;
+    long long in_stride, out_stride;  // bytes per band / output block
+    int pitch, cpr;                   // bytes per row, 16-byte chunks per row
+    int H, y0, y1;                    // band rows (clamp range), output rows [y0, y1)
+    int ncols, nstrips, ntiles_y;
+    int rx, ry, shift;
+    unsigned nblocks;
+    int xcd;                          // 1 = each XCD takes a contiguous run of tiles (halo rows stay in its L2)
+    unsigned wx[2 * SEP_MAX_R + 1];   // centred horizontal taps
+    unsigned wy2[2 * SEP_MAX_R + 1];  // centred vertical taps, the weight in both 16-bit halves
+};
+
+// blockIdx -> tile: blocks b and b+8 share an XCD (round-robin dispatch); one contiguous eighth of the tiles per XCD.
+__device__ __forceinline__ unsigned sep_xcd_contiguous(unsigned L, unsigned n)
+{
+    const unsigned q = n >> 3, r = n & 7u, x = L & 7u, k = L >> 3;
+    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + k;
+}
+
+// Field pair at byte offset K from the PI-parity bytes of output dword I, out of the window of 16-bit sums: E[j] / O[j]
+// hold the sums of window bytes 4j, 4j+2 / 4j+1, 4j+3, the window starting HC chunks left of the output chunk.
+template <int HC, int K, int PI, int I, int N>
+__device__ __forceinline__ uint32_t sep_tap(const uint32_t (&E)[N], const uint32_t (&O)[N])
+{
+    constexpr int q0 = 16 * HC + 4 * I + PI + K;
+    static_assert(q0 >= 0 && q0 + 2 < 4 * N, "tap outside the window");
+    constexpr int e0 = q0 >> 1, j = e0 >> 1;
+    const uint32_t (&A)[N] = (q0 & 1) ? O : E;
+    if constexpr ((e0 & 1) == 0) return A[j];
+    else return __builtin_amdgcn_alignbit(A[j + 1], A[j], 16);
+}
+
+// One tap of the horizontal pass: the pixel d columns away (byte offset d * C), skipped beyond the runtime radius.
+// v_dot2_u32_u16 against (w, 0) / (0, w) adds w times the low / high field of a field pair to a 32-bit sum.
+template <int C, int HC, int D, int N>
+__device__ __forceinline__ void sep_htap(const uint32_t (&E)[N], const uint32_t (&O)[N], const unsigned *wx, int rx,
+                                         uint32_t (&lo)[2][4], uint32_t (&hi)[2][4])
+{
+    if (D < -rx || D > rx) return;                      // uniform
+    const uint32_t w = wx[SEP_MAX_R + D];
+    const sep_u16x2 wl = pk16(w), wh = pk16(w << 16);
+    auto mac = [&](uint32_t f, int PI, int I) {
+        lo[PI][I] = __builtin_amdgcn_udot2(pk16(f), wl, lo[PI][I], false);
+        hi[PI][I] = __builtin_amdgcn_udot2(pk16(f), wh, hi[PI][I], false);
+    };
+    mac(sep_tap<HC, D * C, 0, 0>(E, O), 0, 0); mac(sep_tap<HC, D * C, 1, 0>(E, O), 1, 0);
+    mac(sep_tap<HC, D * C, 0, 1>(E, O), 0, 1); mac(sep_tap<HC, D * C, 1, 1>(E, O), 1, 1);
+    mac(sep_tap<HC, D * C, 0, 2>(E, O), 0, 2); mac(sep_tap<HC, D * C, 1, 2>(E, O), 1, 2);
+    mac(sep_tap<HC, D * C, 0, 3>(E, O), 0, 3); mac(sep_tap<HC, D * C, 1, 3>(E, O), 1, 3);
+}
+template <int C, int HC, int RB, int... Ds, int N>
+__device__ __forceinline__ void sep_hpass(std::integer_sequence<int, Ds...>, const uint32_t (&E)[N], const uint32_t (&O)[N],
+                                          const unsigned *wx, int rx, uint32_t (&lo)[2][4], uint32_t (&hi)[2][4])
+{
+    (sep_htap<C, HC, Ds - RB>(E, O, wx, rx, lo, hi), ...);
+}
+
+template <int C, int RB>
+__global__ __launch_bounds__(SEP_THREADS) void blur_sep_tiled_kernel(const SepTiledParams p)
+{
+    constexpr int HC = sep_halo_chunks(C, RB);
+    constexpr int NW = 4 * (2 * HC + 1);            // window dwords per parity
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    const int t = threadIdx.x;
+    const unsigned L = p.xcd ? sep_xcd_contiguous(blockIdx.x, p.nblocks) : blockIdx.x;
+    const int strip = (int)(L % (unsigned)p.nstrips);
+    const unsigned t2 = L / (unsigned)p.nstrips;
+    const int ty = (int)(t2 % (unsigned)p.ntiles_y);
+    const int img = (int)(t2 / (unsigned)p.ntiles_y);
+
+    const int ty0 = p.y0 + ty * SEP_TH;                 // first output row of the tile (band coordinates)
+    const int rows_out = min(SEP_TH, p.y1 - ty0);
+    const int x0c = strip * p.ncols;
+    const int nc = min(p.ncols, p.cpr - x0c);
+    const int ncw = nc + 2 * HC;                        // staged chunk columns: tile chunk cc = row chunk x0c - HC + cc
+    const int ry = p.ry;
+    const int nrows = rows_out + 2 * ry;
+    const uint8_t *img_in = p.in + (long long)img * p.in_stride;
+
+    // ---- stage: slot s = row * ncw + cc; one wave-instruction moves 64 consecutive slots
+    {
+        const int lane = t & 63, wv = t >> 6;
+        const int nslots = nrows * ncw;
+        for (int u = wv; u * 64 < nslots; u += SEP_THREADS / 64) {
+            const int s = u * 64 + lane;
+            if (s < nslots) {
+                const int row = s / ncw, cc = s - row * ncw;
+                const int gc = x0c - HC + cc;
+                if (gc >= 0 && gc < p.cpr) {
+                    const int sr = min(max(ty0 - ry + row, 0), p.H - 1);
+                    const uint8_t *g = img_in + ((unsigned)sr * (unsigned)p.pitch + (unsigned)gc * 16u);
+                    __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1))) *)g,
+                                                     (void __attribute__((address_space(3))) *)(lds + (size_t)u * 64 * 16), 16, 0, 0);
+                }
+            }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __syncthreads();
+    // x-clamp: halo chunks outside the row get copies of the first / last pixel's channels (same channel, p mod C)
+    if (x0c < HC || x0c + nc + HC > p.cpr) {
+        const int nedge = nrows * 2 * HC;
+        for (int i = t; i < nedge; i += SEP_THREADS) {
+            const int row = i / (2 * HC), h = i - row * (2 * HC);
+            const int cc = h < HC ? h : nc + h;         // the HC left halo chunks, then the HC right ones
+            const int gc = x0c - HC + cc;
+            if (gc >= 0 && gc < p.cpr) continue;
+            uint8_t *rowl = lds + (size_t)row * ncw * 16u;
+            const int base = (x0c - HC) * 16;           // row byte at tile byte 0
+            uint32_t v[4];
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                uint32_t w = 0;
+#pragma unroll
+                for (int b = 0; b < 4; b++) {
+                    const int pos = gc * 16 + 4 * q + b;
+                    const int src = pos < 0 ? ((pos % C) + C) % C : p.pitch - C + (pos - p.pitch) % C;
+                    w |= (uint32_t)rowl[src - base] << (8 * b);
+                }
+                v[q] = w;
+            }
+            *reinterpret_cast<uint4 *>(rowl + cc * 16) = make_uint4(v[0], v[1], v[2], v[3]);
+        }
+        __syncthreads();
+    }
+
+    // ---- vertical pass: thread = (chunk column cc, row group g); every staged row read once
+    const int ngrp = (rows_out + SEP_RPG - 1) / SEP_RPG;
+    const bool vact = t < ncw * ngrp;
+    const int g = t / ncw, vcc = t - g * ncw;
+    uint32_t acc[SEP_RPG][8];
+#pragma unroll
+    for (int m = 0; m < SEP_RPG; m++)
+#pragma unroll
+        for (int k = 0; k < 8; k++) acc[m][k] = 0u;
+    if (vact) {
+        const uint8_t *lp = lds + ((size_t)g * SEP_RPG * ncw + vcc) * 16u;
+        const int span = SEP_RPG + 2 * ry;
+        for (int e = 0; e < span; e++) {                // staged rows g*RPG + e; rows past the tile feed unstored outputs only
+            const uint4 x = *reinterpret_cast<const uint4 *>(lp + (size_t)e * ncw * 16u);
+            const uint32_t xs[4] = {x.x, x.y, x.z, x.w};
+            uint32_t f[8];
+#pragma unroll
+            for (int k = 0; k < 4; k++) { f[k] = xs[k] & 0x00ff00ffu; f[4 + k] = (xs[k] >> 8) & 0x00ff00ffu; }
+#pragma unroll
+            for (int m = 0; m < SEP_RPG; m++) {
+                const int j = e - m;                    // tap index 0..2ry of this row for output row g*RPG + m (uniform)
+                if (j >= 0 && j <= 2 * ry) {
+                    const sep_u16x2 w = pk16(p.wy2[SEP_MAX_R - ry + j]);
+#pragma unroll
+                    for (int k = 0; k < 8; k++) acc[m][k] = pk32(pk16(f[k]) * w + pk16(acc[m][k]));
+                }
+            }
+        }
+    }
+    __syncthreads();                                    // every staged byte read: the sums take the tile's place
+    if (vact) {
+#pragma unroll
+        for (int m = 0; m < SEP_RPG; m++) {
+            uint4 *vp = reinterpret_cast<uint4 *>(lds + ((size_t)(g * SEP_RPG + m) * ncw + vcc) * 32u);
+            vp[0] = make_uint4(acc[m][0], acc[m][1], acc[m][2], acc[m][3]);
+            vp[1] = make_uint4(acc[m][4], acc[m][5], acc[m][6], acc[m][7]);
+        }
+    }
+    __syncthreads();
+
+    // ---- horizontal pass: thread = one output chunk; 32-bit sums, one shift
+    const int rx = p.rx, shift = p.shift;
+    uint8_t *out_img = p.out + (long long)img * p.out_stride;
+    for (int i = t; i < rows_out * nc; i += SEP_THREADS) {
+        const int k = i / nc, col = i - k * nc;
+        uint32_t E[NW], O[NW];
+        const uint4 *vp = reinterpret_cast<const uint4 *>(lds + ((size_t)k * ncw + col) * 32u);
+#pragma unroll
+        for (int w = 0; w < 2 * HC + 1; w++) {
+            const uint4 a = vp[2 * w], b = vp[2 * w + 1];
+            E[4 * w] = a.x; E[4 * w + 1] = a.y; E[4 * w + 2] = a.z; E[4 * w + 3] = a.w;
+            O[4 * w] = b.x; O[4 * w + 1] = b.y; O[4 * w + 2] = b.z; O[4 * w + 3] = b.w;
+        }
+        uint32_t lo[2][4] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}}, hi[2][4] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};
+        sep_hpass<C, HC, RB>(std::make_integer_sequence<int, 2 * RB + 1>{}, E, O, p.wx, rx, lo, hi);
+        uint32_t o[4];
+#pragma unroll
+        for (int I = 0; I < 4; I++)                     // bytes 4I, 4I+1, 4I+2, 4I+3 = even lo, odd lo, even hi, odd hi
+            o[I] = (lo[0][I] >> shift) | ((lo[1][I] >> shift) << 8) | ((hi[0][I] >> shift) << 16) | ((hi[1][I] >> shift) << 24);
+        uint8_t *op = out_img + (size_t)(ty0 - p.y0 + k) * (size_t)p.pitch + (size_t)(x0c + col) * 16u;
+        sep_u32x4 v; v.x = o[0]; v.y = o[1]; v.z = o[2]; v.w = o[3];
+        *reinterpret_cast<sep_u32x4 *>(op) = v;
+    }
+}
+
+struct SepGenericParams {
+    const uint8_t *in;
+    uint8_t *out;
+    long long in_stride, out_stride, block, total;   // block = output bytes per band (rows * pitch)
+    int width, channels, pitch, H, y0;
+    int rx, ry, shift;
+    unsigned wx[2 * SEP_MAX_R + 1], wy[2 * SEP_MAX_R + 1];
+};
+
+__global__ __launch_bounds__(256) void blur_sep_generic_kernel(const SepGenericParams p)
+{
+    const long long step = (long long)gridDim.x * blockDim.x;
+    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < p.total; idx += step) {
+        const long long img = idx / p.block;
+        const long long rem = idx - img * p.block;
+        const int y = p.y0 + (int)(rem / p.pitch);
+        const int b = (int)(rem % p.pitch);
+        const int x = b / p.channels, c = b - x * p.channels;
+        const uint8_t *src = p.in + img * p.in_stride;
+        unsigned sum = 0;
+        for (int j = -p.ry; j <= p.ry; j++) {
+            const int ny = min(max(y + j, 0), p.H - 1);
+            const uint8_t *rowp = src + (size_t)ny * (size_t)p.pitch + c;
+            unsigned h = 0;
+            for (int i = -p.rx; i <= p.rx; i++) {
+                const int nx = min(max(x + i, 0), p.width - 1);
+                h += (unsigned)rowp[(size_t)nx * (size_t)p.channels] * p.wx[SEP_MAX_R + i];
+            }
+            sum += h * p.wy[SEP_MAX_R + j];
+        }
+        p.out[img * p.out_stride + rem] = (uint8_t)(sum >> p.shift);
+    }
+}
+
+inline int sep_hip_status(hipError_t e) { return e == hipSuccess ? MI_BLUR_OK : MI_BLUR_ERR_HIP_BASE - (int)e; }
+
+template <typename K, typename P>
+int sep_do_launch(K kernel, dim3 grid, dim3 block, size_t lds, const LaunchDesc &d, const P &params)
+{
+    if (d.start || d.stop)
+        hipExtLaunchKernelGGL(kernel, grid, block, lds, d.stream, d.start, d.stop, 0, params);
+    else
+        hipLaunchKernelGGL(kernel, grid, block, lds, d.stream, params);
+    return sep_hip_status(hipGetLastError());
+}
+
+template <int C>
+int launch_sep_tiled_c(const LaunchDesc &d, const SepTiledParams &p, dim3 grid, int rb)
+{
+    auto lds_of = [&](int HC) {
+        const int ncw = p.ncols + 2 * HC;               // sums: SEP_TH rows x ncw chunks x 32 B >= the staged bytes
+        return (size_t)SEP_TH * ncw * 32u;
+    };
+    const dim3 block(SEP_THREADS);
+    if (rb == 4) return sep_do_launch(blur_sep_tiled_kernel<C, 4>, grid, block, lds_of(sep_halo_chunks(C, 4)), d, p);
+    if (rb == 8) return sep_do_launch(blur_sep_tiled_kernel<C, 8>, grid, block, lds_of(sep_halo_chunks(C, 8)), d, p);
+    return sep_do_launch(blur_sep_tiled_kernel<C, 16>, grid, block, lds_of(sep_halo_chunks(C, 16)), d, p);
+}
+
+int launch_sep_tiled(const LaunchDesc &d)
+{
+    set_last_kernel("blur_sep_tiled_kernel");
+    const SepTaps &k = *d.sep;
+    const int pitch = d.width * d.channels, cpr = pitch / 16, rows = d.y1 - d.y0;
+    SepTiledParams p{};
+    p.in = d.in; p.out = d.out;
+    p.in_stride = d.in_stride ? d.in_stride : (long long)d.band_rows * pitch;
+    p.out_stride = d.out_stride ? d.out_stride : (long long)rows * pitch;
+    p.pitch = pitch; p.cpr = cpr; p.H = d.band_rows; p.y0 = d.y0; p.y1 = d.y1;
+    p.nstrips = (cpr + SEP_NCOLS - 1) / SEP_NCOLS;
+    p.ncols = (cpr + p.nstrips - 1) / p.nstrips;
+    p.ntiles_y = (rows + SEP_TH - 1) / SEP_TH;
+    p.rx = k.rx; p.ry = k.ry; p.shift = k.shift;
+    for (int i = 0; i <= 2 * SEP_MAX_R; i++) { p.wx[i] = k.wx[i]; p.wy2[i] = k.wy[i] | (k.wy[i] << 16); }
+    const long long nblocks = (long long)d.n_images * p.ntiles_y * p.nstrips;
+    if (nblocks > 0x7fffffffLL) return MI_BLUR_ERR_INVALID;
+    p.nblocks = (unsigned)nblocks;
+    p.xcd = nblocks >= 16 ? 1 : 0;
+    const int rb = k.rx <= 4 ? 4 : k.rx <= 8 ? 8 : 16;
+    const dim3 grid((unsigned)nblocks);
+    switch (d.channels) {
+    case 1: return launch_sep_tiled_c<1>(d, p, grid, rb);
+    case 2: return launch_sep_tiled_c<2>(d, p, grid, rb);
+    case 3: return launch_sep_tiled_c<3>(d, p, grid, rb);
+    case 4: return launch_sep_tiled_c<4>(d, p, grid, rb);
+    }
+    return MI_BLUR_ERR_INVALID;
+}
+
+int launch_sep_generic(const LaunchDesc &d)
+{
+    set_last_kernel("blur_sep_generic_kernel");
+    const SepTaps &k = *d.sep;
+    const int pitch = d.width * d.channels, rows = d.y1 - d.y0;
+    SepGenericParams p{};
+    p.in = d.in; p.out = d.out;
+    p.block = (long long)rows * pitch;
+    p.in_stride = d.in_stride ? d.in_stride : (long long)d.band_rows * pitch;
+    p.out_stride = d.out_stride ? d.out_stride : p.block;
+    p.total = p.block * d.n_images;
+    p.width = d.width; p.channels = d.channels; p.pitch = pitch; p.H = d.band_rows; p.y0 = d.y0;
+    p.rx = k.rx; p.ry = k.ry; p.shift = k.shift;
+    for (int i = 0; i <= 2 * SEP_MAX_R; i++) { p.wx[i] = k.wx[i]; p.wy[i] = k.wy[i]; }
+    long long blocks = (p.total + 255) / 256;
+    if (blocks > 256LL * 64) blocks = 256LL * 64;       // grid-stride the rest
+    return sep_do_launch(blur_sep_generic_kernel, dim3((unsigned)blocks), dim3(256), 0, d, p);
+}
+
+}  // namespace
+
+int launch_sep(const LaunchDesc &d)
+{
+    if (!d.sep || !d.in || !d.out || d.in == d.out) return MI_BLUR_ERR_INVALID;
+    if (d.width <= 0 || d.band_rows <= 0 || d.channels <= 0 || d.n_images < 0) return MI_BLUR_ERR_INVALID;
+    if (d.y0 < 0 || d.y1 > d.band_rows || d.y0 >= d.y1) return MI_BLUR_ERR_INVALID;
+    if ((long long)d.width * d.channels > INT_MAX / 2) return MI_BLUR_ERR_INVALID;
+    if ((long long)d.width * d.channels * d.band_rows > INT_MAX) return MI_BLUR_ERR_INVALID;  // per-image 32-bit
+    const SepTaps &k = *d.sep;
+    if (k.rx < 0 || k.rx > SEP_MAX_R || k.ry < 0 || k.ry > SEP_MAX_R || k.shift < 0 || k.shift > 16) return MI_BLUR_ERR_INVALID;
+    if (d.halo_top || d.halo_bottom) return MI_BLUR_ERR_UNSUPPORTED;
+    const long long pitch = (long long)d.width * d.channels;
+    const long long dense_in = (long long)d.band_rows * pitch, dense_out = (long long)(d.y1 - d.y0) * pitch;
+    if (d.in_stride < 0 || d.out_stride < 0 || (d.in_stride && d.in_stride < dense_in) || (d.out_stride && d.out_stride < dense_out))
+        return MI_BLUR_ERR_INVALID;
+    if (d.n_images == 0) return MI_BLUR_OK;
+    const bool aligned = d.channels <= 4 && pitch % 16 == 0 && (uintptr_t)d.in % 16 == 0 && (uintptr_t)d.out % 16 == 0 &&
+                         d.in_stride % 16 == 0 && d.out_stride % 16 == 0;
+    return aligned ? launch_sep_tiled(d) : launch_sep_generic(d);
+}
+
+}  // namespace mi_blur

@@ -65,7 +65,8 @@ typedef enum mi_blur_variant {
 const char *mi_blur_strerror(int status);
 int mi_blur_version(void);
 /* Which kernel the calling thread's most recent launch went to ("blur_tiled_kernel", "blur_direct_kernel",
- * "blur_fused_kernel", "blur_tiled_loop_kernel", "blur_stream_kernel", "blur_generic_kernel"; "" before the first):
+ * "blur_fused_kernel", "blur_tiled_loop_kernel", "blur_stream_kernel", "blur_generic_kernel", "blur_sep_tiled_kernel",
+ * "blur_sep_generic_kernel"; "" before the first):
  * reports name the kernel a profiler will show.  Static string, never NULL. */
 const char *mi_blur_last_kernel(void);
 
@@ -353,6 +354,43 @@ int mi_blur_resident_peek(mi_blur_ctx *ctx, int pool_index, uint8_t *host_out, i
  * ---------------------------------------------------------------------- */
 int mi_blur_cpu_run(const uint8_t *in, uint8_t *out, int width, int height, int channels,
                     int radius, int n_images, int n_threads);
+
+/* ------------------------------------------------------------------------
+ * Separable integer kernels of any radius up to 16 (Gaussian of any sigma, anisotropic included; no reference
+ * analogue).  Per axis: radius rx / ry in 0..16, non-negative taps wx[2rx+1] / wy[2ry+1] summing to 2^bx / 2^by,
+ * 0 <= bx, by <= 8 (unused tap slots are ignored).  Clamp-to-edge, exact integer arithmetic, one truncating shift:
+ *   out[y][x][c] = ( sum_j wy[j] * sum_i wx[i] * in[clamp(y+j-ry)][clamp(x+i-rx)][c] ) >> (bx + by)
+ * so wx = wy = {1,2,1} (2 + 2) is exactly the radius-1 kernel above and {1,4,6,4,1} (4 + 4) exactly radius 2.
+ * ---------------------------------------------------------------------- */
+#define MI_BLUR_SEP_MAX_RADIUS 16
+typedef struct mi_blur_sep_kernel {
+    int rx, ry, bx, by;
+    uint16_t wx[2 * MI_BLUR_SEP_MAX_RADIUS + 1], wy[2 * MI_BLUR_SEP_MAX_RADIUS + 1];
+} mi_blur_sep_kernel;
+
+/* Integer Gaussian taps.  r = radius, or ceil(3 sigma) clamped to [1,16] when radius is 0; w_i = exp(-i^2/(2 sigma^2))
+ * (double), t_i = floor(w_i * 2^bits / sum w + 0.5), the centre tap absorbs 2^bits - sum t, outer tap pairs that are both 0
+ * are dropped.  taps receives 2*r'+1 values, *radius_out the effective radius r'.  bits 0..8 (8 is the usual choice).
+ * MI_BLUR_ERR_INVALID: sigma <= 0, radius outside 0..16, bits outside 0..8, or a centre tap that is not positive. */
+int mi_blur_gauss_taps(double sigma, int radius, int bits, uint16_t *taps, int *radius_out);
+/* Both axes: sigma_y <= 0 means sigma_y = sigma_x; radius (0 = automatic) applies to each axis, each trimmed on its own. */
+int mi_blur_sep_kernel_gauss(double sigma_x, double sigma_y, int radius, int bits, mi_blur_sep_kernel *k);
+
+/* mi_blur_enqueue / mi_blur_enqueue_band with a separable kernel (same buffers, same band semantics; asynchronous).
+ * Rows of whole 16-byte chunks at 16-byte aligned addresses with 1-4 channels take the LDS-tiled two-pass kernel
+ * (blur_sep_tiled_kernel), every other shape the one-byte-per-thread kernel (blur_sep_generic_kernel). */
+int mi_blur_enqueue_sep(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int n_images,
+                        const mi_blur_sep_kernel *k, void *stream);
+int mi_blur_enqueue_sep_band(const uint8_t *d_in, uint8_t *d_out, int width, int band_rows, int channels,
+                             int out_row_begin, int out_row_end, const mi_blur_sep_kernel *k, void *stream);
+/* mi_blur_cpu_run with a separable kernel. */
+int mi_blur_cpu_run_sep(const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,
+                        const mi_blur_sep_kernel *k, int n_threads);
+/* Give a context a separable kernel in place of the radius it was created with.  Only before its first submit
+ * (MI_BLUR_ERR_STATE after).  Every submit form then uses it (mi_blur_submit, _band, _bands, _planar; pinned or pageable
+ * memory; GPU or CPU device); such submits never go through the batch server (one launch per submit instead), and
+ * the resident runs (mi_blur_resident_run, _run_fused) return MI_BLUR_ERR_UNSUPPORTED.  The context keeps a copy. */
+int mi_blur_ctx_set_kernel(mi_blur_ctx *ctx, const mi_blur_sep_kernel *k);
 
 /* Developer diagnostics.  With mi_blur_set_option("debug_xcd_times", 1) every workgroup of the tiled kernel leaves its
  * start and end time (100 MHz ticks) in a slot of the XCD it ran on; this call waits for the device, returns per XCD the
