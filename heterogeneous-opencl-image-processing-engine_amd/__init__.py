@@ -32,6 +32,7 @@ VARIANT_AUTO, VARIANT_GENERIC, VARIANT_TILED, VARIANT_STREAM, VARIANT_DIRECT = 0
 OK, ERR_INVALID, ERR_NO_DEVICE, ERR_NOMEM, ERR_STATE, ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5
 UNIQUE_ID_BYTES = 128
 SEP_MAX_RADIUS = 16
+MEDIAN_MAX_RADIUS = 7
 PEER_HANDLE_BYTES = 64
 
 
@@ -44,7 +45,7 @@ def _newer(target: str, sources: list[str]) -> bool:
 
 def build_native(force: bool = False, verbose: bool = False) -> str:
     """Compile libmi_blur.so (hipcc, --offload-arch=gfx950) and the C++ hosts, in-tree."""
-    srcs = [os.path.join(CSRC, f) for f in ("blur_kernels.hip", "sep_kernels.hip", "layout_kernels.hip", "mi_blur_api.cpp", "cpu_device.cpp")]
+    srcs = [os.path.join(CSRC, f) for f in ("blur_kernels.hip", "sep_kernels.hip", "median_kernels.hip", "layout_kernels.hip", "mi_blur_api.cpp", "cpu_device.cpp")]
     deps = srcs + [os.path.join(CSRC, f) for f in ("blur_launch.h", "cpu_device.h", "sep_taps.h")] + [HEADER]
     if force or not _newer(LIB_PATH, deps):
         cmd = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra",
@@ -191,6 +192,10 @@ def lib() -> C.CDLL:
         "mi_blur_enqueue_sep_band": (i, [u8p, u8p, i, i, i, i, i, C.POINTER(SepKernel), vp]),
         "mi_blur_cpu_run_sep": (i, [u8p, u8p, i, i, i, i, C.POINTER(SepKernel), i]),
         "mi_blur_ctx_set_kernel": (i, [vp, C.POINTER(SepKernel)]),
+        "mi_blur_enqueue_median": (i, [u8p, u8p, i, i, i, i, i, vp]),
+        "mi_blur_enqueue_median_band": (i, [u8p, u8p, i, i, i, i, i, i, vp]),
+        "mi_blur_cpu_run_median": (i, [u8p, u8p, i, i, i, i, i, i]),
+        "mi_blur_ctx_set_median": (i, [vp, i]),
         "mi_blur_fill_synthetic": (None, [u8p, i, i, i, i, i, i]),
         "mi_blur_fnv1a64": (C.c_uint64, [u8p, C.c_size_t]),
         "mi_blur_debug_zc_trace": (i, [vp, C.POINTER(C.c_uint64), i, C.POINTER(i), C.POINTER(C.c_uint)]),
@@ -302,6 +307,11 @@ class Context:
             self.close()
         except Exception:
             pass
+
+    def set_median(self, radius: int) -> None:
+        """The median of that radius (1..7) in place of the blur, for every submit (before the first one only)."""
+        check(lib().mi_blur_ctx_set_median(self.h, int(radius)), "mi_blur_ctx_set_median")
+        self.median_radius = int(radius)
 
     def set_kernel(self, kernel: "SepKernel") -> None:
         """A separable kernel in place of the radius, for every submit (before the first one only)."""
@@ -449,6 +459,38 @@ def gaussian_blur(images, sigma: float, sigma_y: float | None = None, radius: in
     isz = h * w * c
     with Context(device, w, h, c, 1, max_batch=per, n_slots=2) as ctx:
         ctx.set_kernel(kernel)
+        for i in range(0, n, per):
+            m = min(per, n - i)
+            ctx.submit(a.ctypes.data + i * isz, out.ctypes.data + i * isz, m)
+        ctx.sync()
+    return out.reshape(shape)
+
+
+def median_blur(images, ksize: int = 3, device: int = 0, batch: int = 0):
+    """Median blur with a ksize x ksize window (ksize odd, 3..15), numpy in -> numpy out, like blur().
+
+    Edges clamp; every output byte is the exact median of its window.  images: (H, W), (H, W, C) or (N, H, W, C) uint8;
+    the result has the same shape.  device: HIP ordinal, or DEVICE_CPU.  Goes through mi_blur_create /
+    mi_blur_ctx_set_median / mi_blur_submit / mi_blur_sync."""
+    import numpy as np
+    if ksize % 2 != 1 or not 3 <= ksize <= 2 * MEDIAN_MAX_RADIUS + 1:
+        raise ValueError(f"median_blur: ksize must be odd, 3..{2 * MEDIAN_MAX_RADIUS + 1}")
+    a = np.ascontiguousarray(images)
+    if a.dtype != np.uint8 or a.ndim not in (2, 3, 4):
+        raise ValueError("median_blur: a uint8 array of shape (H, W), (H, W, C) or (N, H, W, C)")
+    shape = a.shape
+    if a.ndim == 2:
+        a = a[None, :, :, None]
+    elif a.ndim == 3:
+        a = a[None]
+    n, h, w, c = a.shape
+    out = np.empty_like(a)
+    if n == 0 or a.size == 0:
+        return out.reshape(shape)
+    per = min(n, batch if batch > 0 else 4096)
+    isz = h * w * c
+    with Context(device, w, h, c, 1, max_batch=per, n_slots=2) as ctx:
+        ctx.set_median(ksize // 2)
         for i in range(0, n, per):
             m = min(per, n - i)
             ctx.submit(a.ctypes.data + i * isz, out.ctypes.data + i * isz, m)

@@ -1,7 +1,7 @@
 // heterogeneous_blur — Approach 1 (image-level distribution) host, MI355X-native.
 //
 //   heterogeneous_blur {cpu|gpu|both} [gpu_ratio] [batch]  [--image F | --synthetic | --size WxH] [--channels C]
-//                      [--ksize 3|5 | --sigma S [--sigma-y S] [--radius R]] [--images N] [--gpus G] [--slots S] [--threads T] [--resident [--fused]]
+//                      [--ksize 3|5 | --sigma S [--sigma-y S] [--radius R] | --median K] [--images N] [--gpus G] [--slots S] [--threads T] [--resident [--fused]]
 //                      [--verbose] [--csv FILE] [--save FILE]
 //                      [--frames DIR|PATTERN|FILE [--save-dir DIR] [--planar-out | --native-layout]]   (cpu | gpu)
 //
@@ -96,7 +96,9 @@ int main(int argc, char **argv)
     printf("Execution mode : %d\n", mode);
     mi_blur_sep_kernel sep{};
     const bool use_sep = sep_kernel_of(opt, &sep);
-    if (use_sep) print_sep_kernel(sep, opt.sigma, opt.sigma_y);
+    const int median_r = median_radius_of(opt);
+    if (median_r) printf("Blur kernel: %dx%d median\n", opt.median, opt.median);
+    else if (use_sep) print_sep_kernel(sep, opt.sigma, opt.sigma_y);
     else printf("Blur kernel: %dx%d\n", opt.ksize, opt.ksize);
     printf("================================================\n\n");
 
@@ -141,6 +143,7 @@ int main(int argc, char **argv)
         mi_check(mi_blur_create(&cpu.ctx, MI_BLUR_DEVICE_CPU, width, height, channels, radius, BATCH_SIZE, nslots, opt.threads),
                  "Failed to create CPU context");
         if (use_sep) mi_check(mi_blur_ctx_set_kernel(cpu.ctx, &sep), "Failed to set the blur kernel");
+        if (median_r) mi_check(mi_blur_ctx_set_median(cpu.ctx, median_r), "Failed to set the median");
         const unsigned hc = std::thread::hardware_concurrency();
         cpu.name = "host threads x" + std::to_string(opt.threads > 0 ? opt.threads : std::min((int)(hc ? hc : 1), 16));
         printf("CPU device: %s\n", cpu.name.c_str());
@@ -159,6 +162,7 @@ int main(int argc, char **argv)
                                  : mi_blur_create(&gpus[g].ctx, hip_ordinal(g), width, height, channels, radius, BATCH_SIZE, nslots, 0),
                  "Failed to create GPU context");
         if (use_sep) mi_check(mi_blur_ctx_set_kernel(gpus[g].ctx, &sep), "Failed to set the blur kernel");
+        if (median_r) mi_check(mi_blur_ctx_set_median(gpus[g].ctx, median_r), "Failed to set the median");
         gpus[g].name = "HIP device " + std::to_string(hip_ordinal(g)) + (virtual_gpus() ? " (logical GPU " + std::to_string(g) + ")" : "");
         printf("GPU device: %s\n", gpus[g].name.c_str());
         gpus[g].submitted.assign(NUM_BATCHES, 0);
@@ -546,6 +550,7 @@ static int run_frames(const Options &opt, int mode, int BATCH_SIZE, const std::v
                                 per_dev_slots, opt.threads), "Failed to create context");
         mi_blur_sep_kernel sep{};
         if (sep_kernel_of(opt, &sep)) mi_check(mi_blur_ctx_set_kernel(ctx[g], &sep), "Failed to set the blur kernel");
+        if (median_radius_of(opt)) mi_check(mi_blur_ctx_set_median(ctx[g], median_radius_of(opt)), "Failed to set the median");
         if (mode == 2) { printf("GPU device: HIP device %d\n", hip_ordinal(g)); report_placement(g, hip_ordinal(g), g == 0); }
         else printf("CPU device: host threads\n");
     }

@@ -163,6 +163,7 @@ struct Options {
     double sigma = 0.0;                  // --sigma S [--sigma-y S] [--radius R]: separable Gaussian of that sigma (radius 0 = ceil(3 sigma),
     double sigma_y = 0.0;                //              at most 16) instead of --ksize; mi_blur_ctx_set_kernel on every context
     int sep_radius = 0;
+    int median = 0;                      // --median K (odd, 3..15): the KxK median instead of --ksize; mi_blur_ctx_set_median on every context
     int images = 5000;                   // --images N   (NUM_IMAGES, heterogeneous_blur.c:44)
     bool images_given = false;
     int gpus = 1;                        // --gpus G
@@ -212,6 +213,10 @@ inline int parse_flags(int argc, char **argv, Options &o)
         else if (a == "--size") { if (sscanf(next("--size"), "%dx%d", &o.syn_w, &o.syn_h) != 2 || o.syn_w <= 0 || o.syn_h <= 0) { printf("Error: --size WxH\n"); exit(-1); } o.synthetic = true; o.size_given = true; }
         else if (a == "--channels") o.syn_c = atoi(next("--channels"));
         else if (a == "--ksize") { o.ksize = atoi(next("--ksize")); if (o.ksize != 3 && o.ksize != 5) { printf("Error: --ksize must be 3 or 5\n"); exit(-1); } o.ksize_given = true; }
+        else if (a == "--median") {
+            o.median = atoi(next("--median"));
+            if (o.median < 3 || o.median > 2 * MI_BLUR_MEDIAN_MAX_RADIUS + 1 || o.median % 2 == 0) { printf("Error: --median must be odd, 3..%d\n", 2 * MI_BLUR_MEDIAN_MAX_RADIUS + 1); exit(-1); }
+        }
         else if (a == "--sigma") { o.sigma = atof(next("--sigma")); if (!(o.sigma > 0.0)) { printf("Error: --sigma must be > 0\n"); exit(-1); } }
         else if (a == "--sigma-y") { o.sigma_y = atof(next("--sigma-y")); if (!(o.sigma_y > 0.0)) { printf("Error: --sigma-y must be > 0\n"); exit(-1); } }
         else if (a == "--radius") { o.sep_radius = atoi(next("--radius")); if (o.sep_radius < 1 || o.sep_radius > MI_BLUR_SEP_MAX_RADIUS) { printf("Error: --radius must be 1..%d\n", MI_BLUR_SEP_MAX_RADIUS); exit(-1); } }
@@ -240,6 +245,8 @@ inline int parse_flags(int argc, char **argv, Options &o)
     if (o.sigma > 0.0 && o.ksize_given) { printf("Error: --sigma and --ksize exclude each other\n"); exit(-1); }
     if (o.sigma <= 0.0 && (o.sigma_y > 0.0 || o.sep_radius > 0)) { printf("Error: --sigma-y and --radius need --sigma\n"); exit(-1); }
     if (o.sigma > 0.0 && o.resident) { printf("Error: --sigma does not run --resident\n"); exit(-1); }
+    if (o.median && (o.ksize_given || o.sigma > 0.0)) { printf("Error: --median excludes --ksize and --sigma\n"); exit(-1); }
+    if (o.median && o.resident) { printf("Error: --median does not run --resident\n"); exit(-1); }
     return npos;
 }
 
@@ -253,6 +260,9 @@ inline bool sep_kernel_of(const Options &o, mi_blur_sep_kernel *k)
     }
     return true;
 }
+// --median K: the radius every context of the run is given (mi_blur_ctx_set_median); 0 = no median.
+inline int median_radius_of(const Options &o) { return o.median / 2; }
+
 inline void print_sep_kernel(const mi_blur_sep_kernel &k, double sx, double sy)
 {
     printf("Blur kernel: %dx%d separable Gaussian, sigma %g x %g\n", 2 * k.rx + 1, 2 * k.ry + 1, sx, sy > 0.0 ? sy : sx);

@@ -1,6 +1,6 @@
 // split_image_blur — Approach 2 (split-image + halo) host, MI355X-native.
 //
-//   split_image_blur [gpu_ratio] [batch]  [--image F | --synthetic | --size WxH] [--channels C] [--ksize 3|5 | --sigma S [--sigma-y S] [--radius R]]
+//   split_image_blur [gpu_ratio] [batch]  [--image F | --synthetic | --size WxH] [--channels C] [--ksize 3|5 | --sigma S [--sigma-y S] [--radius R] | --median K]
 //                    [--images N] [--gpus G] [--slots S] [--threads T] [--verbose] [--csv FILE] [--save FILE]
 //   split_image_blur --resident [--gpus G] [--size WxH] [--ksize 3|5] [--iters N] [--iterate] [--overlap]
 //                    [--transport rccl|p2p|pull|peer] [--save FILE]
@@ -47,8 +47,10 @@ int main(int argc, char **argv)
     mi_blur_sep_kernel sep{};
     const bool use_sep = sep_kernel_of(opt, &sep);
     // --sigma: the halo is the kernel's vertical radius (at least one row, so the split geometry stays the reference's)
-    const int HALO = use_sep ? std::max(1, sep.ry) : opt.ksize == 3 ? 1 : 2;
-    const int ctx_radius = use_sep ? 1 : HALO;          // contexts take the separable kernel right after creation
+    const int median_r = median_radius_of(opt);
+    // --median K: the halo is the median's radius
+    const int HALO = median_r ? median_r : use_sep ? std::max(1, sep.ry) : opt.ksize == 3 ? 1 : 2;
+    const int ctx_radius = (use_sep || median_r) ? 1 : HALO;   // contexts take the separable kernel / median right after creation
 
     if (npos > 1) {
         gpu_ratio = atof(argv[1]);
@@ -77,6 +79,7 @@ int main(int argc, char **argv)
     printf("GPU ratio: %.1f%% (rows to GPU)\n", gpu_ratio * 100);
     printf("Halo size: %d row(s)\n", HALO);
     if (use_sep) print_sep_kernel(sep, opt.sigma, opt.sigma_y);
+    if (median_r) printf("Blur kernel: %dx%d median\n", opt.median, opt.median);
     printf("================================================\n\n");
 
     // ---------------- load original image (split_image_blur.c:106-139)
@@ -119,6 +122,7 @@ int main(int argc, char **argv)
     mi_check(mi_blur_create(&cpu.ctx, MI_BLUR_DEVICE_CPU, width, height, channels, ctx_radius, BATCH_SIZE, nslots, opt.threads),
              "Failed to create CPU context");
     if (use_sep) mi_check(mi_blur_ctx_set_kernel(cpu.ctx, &sep), "Failed to set the blur kernel");
+    if (median_r) mi_check(mi_blur_ctx_set_median(cpu.ctx, median_r), "Failed to set the median");
     cpu.name = "host threads";
     printf("CPU device: %s\n", cpu.name.c_str());
     std::vector<Part> gpus(G);
@@ -135,6 +139,7 @@ int main(int argc, char **argv)
         if (p.out_rows <= 0) { printf("Error: more GPUs than GPU rows\n"); return -1; }
         mi_check(mi_blur_create(&p.ctx, hip_ordinal(g), width, height, channels, ctx_radius, BATCH_SIZE, nslots, 0), "Failed to create GPU context");
         if (use_sep) mi_check(mi_blur_ctx_set_kernel(p.ctx, &sep), "Failed to set the blur kernel");
+        if (median_r) mi_check(mi_blur_ctx_set_median(p.ctx, median_r), "Failed to set the median");
         p.name = "HIP device " + std::to_string(hip_ordinal(g));
         printf("GPU device: %s (rows %d-%d)\n", p.name.c_str(), p.out_row0, p.out_row0 + p.out_rows - 1);
     }

@@ -1714,6 +1714,7 @@ static int launch_generic(const LaunchDesc &d)
 
 int launch(const LaunchDesc &d)
 {
+    if (d.median_radius) return launch_median(d);
     if (d.sep) return launch_sep(d);
     if (!d.in || !d.out || d.in == d.out) return MI_BLUR_ERR_INVALID;
     if (d.width <= 0 || d.band_rows <= 0 || d.channels <= 0 || d.n_images < 0) return MI_BLUR_ERR_INVALID;

@@ -10,6 +10,7 @@ namespace mi_blur {
 
 struct LaunchDesc {
     const SepTaps *sep;     // non-null: this separable kernel instead of `radius` (launch_sep, sep_kernels.hip)
+    int median_radius;      // 1..7: the median of that radius instead of `radius` (launch_median, median_kernels.hip); 0 = none
     const uint8_t *in;      // device, n_images bands of band_rows rows, laid end to end
     uint8_t *out;           // device, n_images blocks of (y1-y0) rows
     int width, band_rows, channels, radius;
@@ -27,12 +28,16 @@ struct LaunchDesc {
     hipEvent_t start, stop; // optional: dispatch start/stop timestamps (hipExtLaunchKernel)
 };
 
-// Returns MI_BLUR_OK or a negative mi_blur_status.  d.sep set: handed to launch_sep.
+// Returns MI_BLUR_OK or a negative mi_blur_status.  d.median_radius set: handed to launch_median; d.sep set: to launch_sep.
 int launch(const LaunchDesc &d);
 // Separable kernel of d.sep (sep_kernels.hip): the aligned LDS-tiled kernel or the generic one.  Honours in/out strides,
 // bands [y0, y1) and the per-image 32-bit offsets of launch(); ignores max_blocks, concurrent and variant (AUTO);
 // halo_top / halo_bottom: MI_BLUR_ERR_UNSUPPORTED.
 int launch_sep(const LaunchDesc &d);
+// Median of radius d.median_radius (median_kernels.hip): the register-window kernel for radius 1|2 on aligned rows of
+// 1-4 channels, the generic one otherwise.  Honours in/out strides, bands [y0, y1) and the 64-bit image offsets of
+// launch(); ignores max_blocks, concurrent and variant (AUTO); halo_top / halo_bottom: MI_BLUR_ERR_UNSUPPORTED.
+int launch_median(const LaunchDesc &d);
 // Sets what last_kernel() reports for the calling thread.
 void set_last_kernel(const char *name);
 

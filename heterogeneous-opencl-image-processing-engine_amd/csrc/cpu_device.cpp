@@ -205,10 +205,46 @@ void cpu_blur_rows_sep(const uint8_t *in, uint8_t *out, int W, int H, int C, con
     }
 }
 
+// Huang's running median: per output row and channel one 256-bin histogram of the (2R+1)^2 window, slid along the row
+// (one column of 2R+1 values out, one in), with the current median m and lt = #{window values < m} kept up to date, so
+// a pixel costs O(R) plus the few steps m moves.  Exact: m is the smallest value with lt + hist[m] > k.
+void cpu_median_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, int R, int y_begin, int y_end, int out_row_shift)
+{
+    const int pitch = W * C, D = 2 * R + 1, k = (D * D - 1) / 2;
+    const uint8_t *rows[2 * 7 + 1];
+    int hist[256];
+    for (int y = y_begin; y < y_end; y++) {
+        for (int j = 0; j < D; j++) rows[j] = in + (size_t)std::min(std::max(y + j - R, 0), H - 1) * pitch;
+        uint8_t *o = out + (size_t)(y - out_row_shift) * pitch;
+        for (int c = 0; c < C; c++) {
+            std::fill(hist, hist + 256, 0);
+            for (int i = -R; i <= R; i++) {
+                const int xo = std::min(std::max(i, 0), W - 1) * C + c;
+                for (int j = 0; j < D; j++) hist[rows[j][xo]]++;
+            }
+            int m = 0, lt = 0;
+            for (int x = 0; x < W; x++) {
+                if (x > 0) {
+                    const int xr = std::min(std::max(x - R - 1, 0), W - 1) * C + c;   // column leaving the window
+                    const int xa = std::min(x + R, W - 1) * C + c;                      // column entering it
+                    for (int j = 0; j < D; j++) {
+                        const int vr = rows[j][xr], va = rows[j][xa];
+                        hist[vr]--; if (vr < m) lt--;
+                        hist[va]++; if (va < m) lt++;
+                    }
+                }
+                while (lt > k) { m--; lt -= hist[m]; }
+                while (lt + hist[m] <= k) { lt += hist[m]; m++; }
+                o[x * C + c] = (uint8_t)m;
+            }
+        }
+    }
+}
+
 // n_images bands of band_rows rows; output rows [y0,y1) of each.  Threads take whole
 // images when there are enough of them, else row slices of each image.
 void cpu_blur_batch(const uint8_t *in, uint8_t *out, int W, int band_rows, int C, int R, int n_images,
-                    int y0, int y1, int n_threads, size_t in_stride, size_t out_stride, const SepTaps *sep)
+                    int y0, int y1, int n_threads, size_t in_stride, size_t out_stride, const SepTaps *sep, int median_r)
 {
     if (n_images <= 0) return;
     if (n_threads <= 0) n_threads = hardware_threads();
@@ -230,7 +266,8 @@ void cpu_blur_batch(const uint8_t *in, uint8_t *out, int W, int band_rows, int C
             if (it >= items) break;
             const int img = (int)(it / slices), s = (int)(it % slices);
             const int ys = y0 + (int)((long long)rows * s / slices), ye = y0 + (int)((long long)rows * (s + 1) / slices);
-            if (sep) cpu_blur_rows_sep(in + img * in_stride, out + img * out_stride, W, band_rows, C, *sep, ys, ye, y0);
+            if (median_r) cpu_median_rows(in + img * in_stride, out + img * out_stride, W, band_rows, C, median_r, ys, ye, y0);
+            else if (sep) cpu_blur_rows_sep(in + img * in_stride, out + img * out_stride, W, band_rows, C, *sep, ys, ye, y0);
             else cpu_blur_rows(in + img * in_stride, out + img * out_stride, W, band_rows, C, R, ys, ye, y0);
         }
     };

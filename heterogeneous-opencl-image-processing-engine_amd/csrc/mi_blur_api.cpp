@@ -251,6 +251,39 @@ extern "C" int mi_blur_enqueue_sep(const uint8_t *d_in, uint8_t *d_out, int widt
     return launch(d);
 }
 
+// ----------------------------------------------------------------------------------
+// median blur, radius 1..7 (no reference analogue)
+// ----------------------------------------------------------------------------------
+static bool median_radius_ok(int r) { return r >= 1 && r <= MI_BLUR_MEDIAN_MAX_RADIUS; }
+
+extern "C" int mi_blur_enqueue_median_band(const uint8_t *d_in, uint8_t *d_out, int width, int band_rows, int channels,
+                                           int radius, int out_row_begin, int out_row_end, void *stream)
+{
+    if (!median_radius_ok(radius) || !d_in || !d_out || d_in == d_out || width <= 0 || band_rows <= 0 || channels <= 0)
+        return MI_BLUR_ERR_INVALID;
+    if (mi_blur_device_count() <= 0) return MI_BLUR_ERR_NO_DEVICE;
+    LaunchDesc d{};
+    d.median_radius = radius;
+    d.in = d_in; d.out = d_out; d.width = width; d.band_rows = band_rows; d.channels = channels;
+    d.n_images = 1; d.y0 = out_row_begin; d.y1 = out_row_end;
+    d.variant = MI_BLUR_VARIANT_AUTO; d.stream = (hipStream_t)stream;
+    return launch(d);
+}
+
+extern "C" int mi_blur_enqueue_median(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int radius,
+                                      int n_images, void *stream)
+{
+    if (!median_radius_ok(radius) || !d_in || !d_out || d_in == d_out || width <= 0 || height <= 0 || channels <= 0 || n_images < 0)
+        return MI_BLUR_ERR_INVALID;
+    if (mi_blur_device_count() <= 0) return MI_BLUR_ERR_NO_DEVICE;
+    LaunchDesc d{};
+    d.median_radius = radius;
+    d.in = d_in; d.out = d_out; d.width = width; d.band_rows = height; d.channels = channels;
+    d.n_images = n_images; d.y0 = 0; d.y1 = height;
+    d.variant = MI_BLUR_VARIANT_AUTO; d.stream = (hipStream_t)stream;
+    return launch(d);
+}
+
 // Frame layout on the device (replaces the host loops heterogeneous_blur.c:125-134 and split_image_blur.c:40-56).
 extern "C" int mi_blur_planar_to_interleaved(const uint8_t *d_planar, uint8_t *d_interleaved, int width, int height,
                                              int channels, int n_images, void *stream)
@@ -410,6 +443,8 @@ struct mi_blur_ctx {
     SepTaps sep{};
     bool submitted = false;                                      // set_kernel only before this
     const SepTaps *sep_or_null() const { return has_sep ? &sep : nullptr; }
+    // median (mi_blur_ctx_set_median): 1..7 replaces R in every submit; 0 = none.  One filter at a time: has_sep is false then.
+    int median_r = 0;
     bool is_cpu() const { return device == MI_BLUR_DEVICE_CPU; }
 };
 
@@ -799,7 +834,7 @@ extern "C" void mi_blur_destroy(mi_blur_ctx *c)
 // than the running server's): the caller launches the batch the classic way.
 static int zc_server_submit(mi_blur_ctx *c, Slot &s, const LaunchDesc &d, const Tunables &tun)
 {
-    if (c->has_sep) return MI_BLUR_ERR_UNSUPPORTED;         // the server's tiles are the radius-1|2 kernel's: one launch per batch
+    if (c->has_sep || c->median_r) return MI_BLUR_ERR_UNSUPPORTED;   // the server's tiles are the radius-1|2 kernel's: one launch per batch
     if (c->slots.size() > ZC_RING) return MI_BLUR_ERR_UNSUPPORTED;
     if (!c->zc) {
         ZcServer *z = new (std::nothrow) ZcServer;
@@ -892,7 +927,8 @@ static int submit_common(mi_blur_ctx *c, const uint8_t *host_in, uint8_t *host_o
         const int W = c->W, C = c->C, R = c->R, nt = c->n_threads;
         const bool has_sep = c->has_sep;
         const SepTaps sep = c->sep;
-        j->work = [=]() { cpu_blur_batch(host_in, host_out, W, band_rows, C, R, n_images, y0, y1, nt, in_stride, out_stride, has_sep ? &sep : nullptr); };
+        const int median_r = c->median_r;
+        j->work = [=]() { cpu_blur_batch(host_in, host_out, W, band_rows, C, R, n_images, y0, y1, nt, in_stride, out_stride, has_sep ? &sep : nullptr, median_r); };
         if (!c->cpu_worker) { c->cpu_worker = new (std::nothrow) CpuWorker; if (!c->cpu_worker) { delete j; return MI_BLUR_ERR_NOMEM; } }
         c->cpu_worker->push(j);
         c->cpu_jobs.push_back(j);
@@ -925,6 +961,7 @@ static int submit_common(mi_blur_ctx *c, const uint8_t *host_in, uint8_t *host_o
                 d.in = zin; d.out = zout; d.width = c->W; d.band_rows = band_rows; d.channels = c->C;
                 d.radius = c->R; d.n_images = n_images; d.y0 = y0; d.y1 = y1; d.variant = MI_BLUR_VARIANT_AUTO;
                 d.sep = c->sep_or_null();
+                d.median_radius = c->median_r;
                 d.in_stride = (long long)in_stride; d.out_stride = (long long)out_stride;
                 // small batches stay with one launch each: the server's hand-off (descriptor over the link, poller, completion
                 // word, the host's wait) costs ~26 us per batch against ~8 us for a launch — below ~1.3 MB each way the launch
@@ -995,6 +1032,7 @@ static int submit_common(mi_blur_ctx *c, const uint8_t *host_in, uint8_t *host_o
                 d.in = zin; d.out = zout; d.width = c->W; d.band_rows = band_rows; d.channels = c->C;
                 d.radius = c->R; d.n_images = n_images; d.y0 = y0; d.y1 = y1; d.variant = MI_BLUR_VARIANT_AUTO;
                 d.sep = c->sep_or_null();
+                d.median_radius = c->median_r;
                 d.in_stride = (long long)src_stride; d.out_stride = (long long)zout_stride;
                 rc = zc_server_submit(c, s, d, tun);
                 if (rc == MI_BLUR_OK) {
@@ -1022,6 +1060,7 @@ static int submit_common(mi_blur_ctx *c, const uint8_t *host_in, uint8_t *host_o
         d.in = s.d_in; d.out = s.d_out; d.width = c->W; d.band_rows = band_rows; d.channels = c->C;
         d.radius = c->R; d.n_images = n_images; d.y0 = y0; d.y1 = y1; d.variant = MI_BLUR_VARIANT_AUTO;
         d.sep = c->sep_or_null();
+        d.median_radius = c->median_r;
         d.stream = s.stream; d.start = s.ks; d.stop = s.ke;
         d.concurrent = (int)c->slots.size();
         rc = launch(d);
@@ -1091,10 +1130,11 @@ extern "C" int mi_blur_submit_planar(mi_blur_ctx *c, const uint8_t *host_planar_
         const int W = c->W, H = c->H, C = c->C, R = c->R, nt = c->n_threads;
         const bool has_sep = c->has_sep;
         const SepTaps sep = c->sep;
+        const int median_r = c->median_r;
         j->work = [=]() {
             std::vector<uint8_t> a(bytes), b(planar_out ? bytes : 0);
             cpu_repack(host_planar_in, a.data(), W, H, C, n_images, true, nt);
-            cpu_blur_batch(a.data(), planar_out ? b.data() : host_out, W, H, C, R, n_images, 0, H, nt, 0, 0, has_sep ? &sep : nullptr);
+            cpu_blur_batch(a.data(), planar_out ? b.data() : host_out, W, H, C, R, n_images, 0, H, nt, 0, 0, has_sep ? &sep : nullptr, median_r);
             if (planar_out) cpu_repack(b.data(), host_out, W, H, C, n_images, false, nt);
         };
         if (!c->cpu_worker) { c->cpu_worker = new (std::nothrow) CpuWorker; if (!c->cpu_worker) { delete j; return MI_BLUR_ERR_NOMEM; } }
@@ -1128,6 +1168,7 @@ extern "C" int mi_blur_submit_planar(mi_blur_ctx *c, const uint8_t *host_planar_
         d.in = s.d_in; d.out = s.d_out; d.width = c->W; d.band_rows = c->H; d.channels = c->C;
         d.radius = c->R; d.n_images = n_images; d.y0 = 0; d.y1 = c->H; d.variant = MI_BLUR_VARIANT_AUTO;
         d.sep = c->sep_or_null();
+        d.median_radius = c->median_r;
         d.stream = s.stream; d.start = s.ks; d.stop = s.ke;
         d.concurrent = (int)c->slots.size();
         rc = launch(d);
@@ -1161,6 +1202,18 @@ extern "C" int mi_blur_ctx_set_kernel(mi_blur_ctx *c, const mi_blur_sep_kernel *
     if (rc) return rc;
     c->sep = t;
     c->has_sep = true;
+    c->median_r = 0;
+    return MI_BLUR_OK;
+}
+
+// The median of that radius in place of the context's blur, for every submit from now on (before the first one only).
+extern "C" int mi_blur_ctx_set_median(mi_blur_ctx *c, int radius)
+{
+    if (!c) return MI_BLUR_ERR_INVALID;
+    if (c->submitted) return MI_BLUR_ERR_STATE;
+    if (!median_radius_ok(radius)) return MI_BLUR_ERR_INVALID;
+    c->median_r = radius;
+    c->has_sep = false;
     return MI_BLUR_OK;
 }
 
@@ -1339,7 +1392,7 @@ extern "C" void *mi_blur_resident_out(mi_blur_ctx *c) { return c ? c->pool_out :
 extern "C" int mi_blur_resident_run(mi_blur_ctx *c, int n_images, int batch, int timed_every)
 {
     if (!c || n_images < 0 || batch <= 0) return MI_BLUR_ERR_INVALID;
-    if (c->has_sep) return MI_BLUR_ERR_UNSUPPORTED;
+    if (c->has_sep || c->median_r) return MI_BLUR_ERR_UNSUPPORTED;
     if (c->is_cpu() || !c->pool_in) return MI_BLUR_ERR_STATE;
     if (batch > c->pool_images) return MI_BLUR_ERR_INVALID;
     HIP_TRY(hipSetDevice(c->device));
@@ -1386,7 +1439,7 @@ static size_t fused_words(int cap) { return 8 * (size_t)cap + 16384; }
 extern "C" int mi_blur_resident_run_fused(mi_blur_ctx *c, int n_images, int batch, int timed)
 {
     if (!c || n_images <= 0 || batch <= 0) return MI_BLUR_ERR_INVALID;
-    if (c->has_sep) return MI_BLUR_ERR_UNSUPPORTED;
+    if (c->has_sep || c->median_r) return MI_BLUR_ERR_UNSUPPORTED;
     if (c->is_cpu() || !c->pool_in) return MI_BLUR_ERR_STATE;
     if (n_images > c->pool_images) return MI_BLUR_ERR_INVALID;           // one contiguous run of the pool
     HIP_TRY(hipSetDevice(c->device));
@@ -1542,6 +1595,17 @@ extern "C" int mi_blur_cpu_run_sep(const uint8_t *in, uint8_t *out, int width, i
     const int rc = sep_prepare(k, &t);
     if (rc) return rc;
     cpu_blur_batch(in, out, width, height, channels, 0, n_images, 0, height, n_threads, 0, 0, &t);
+    return MI_BLUR_OK;
+}
+
+extern "C" int mi_blur_cpu_run_median(const uint8_t *in, uint8_t *out, int width, int height, int channels, int radius,
+                                      int n_images, int n_threads)
+{
+    if (!in || !out || in == out || width <= 0 || height <= 0 || channels <= 0 || n_images < 0)
+        return MI_BLUR_ERR_INVALID;
+    if (!median_radius_ok(radius)) return MI_BLUR_ERR_INVALID;
+    if ((long long)width * channels * height > INT_MAX) return MI_BLUR_ERR_INVALID;
+    cpu_blur_batch(in, out, width, height, channels, 0, n_images, 0, height, n_threads, 0, 0, nullptr, radius);
     return MI_BLUR_OK;
 }
 

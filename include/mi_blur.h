@@ -66,7 +66,7 @@ const char *mi_blur_strerror(int status);
 int mi_blur_version(void);
 /* Which kernel the calling thread's most recent launch went to ("blur_tiled_kernel", "blur_direct_kernel",
  * "blur_fused_kernel", "blur_tiled_loop_kernel", "blur_stream_kernel", "blur_generic_kernel", "blur_sep_tiled_kernel",
- * "blur_sep_generic_kernel"; "" before the first):
+ * "blur_sep_generic_kernel", "blur_median_fast_kernel", "blur_median_generic_kernel"; "" before the first):
  * reports name the kernel a profiler will show.  Static string, never NULL. */
 const char *mi_blur_last_kernel(void);
 
@@ -391,6 +391,32 @@ int mi_blur_cpu_run_sep(const uint8_t *in, uint8_t *out, int width, int height, 
  * memory; GPU or CPU device); such submits never go through the batch server (one launch per submit instead), and
  * the resident runs (mi_blur_resident_run, _run_fused) return MI_BLUR_ERR_UNSUPPORTED.  The context keeps a copy. */
 int mi_blur_ctx_set_kernel(mi_blur_ctx *ctx, const mi_blur_sep_kernel *k);
+
+/* ------------------------------------------------------------------------
+ * Median blur, windows 3x3 to 15x15 (no reference analogue).  For a radius r in 1..MI_BLUR_MEDIAN_MAX_RADIUS, with
+ * clamp-to-edge as everywhere else:
+ *   out[y][x][c] = the k-th smallest (0-based, k = ((2r+1)^2 - 1) / 2) of
+ *                  { in[clamp(y+j, 0, H-1)][clamp(x+i, 0, W-1)][c] : -r <= i, j <= r }
+ * The window count is odd, so the result is one exact byte; the GPU and the CPU device agree byte for byte.
+ * ---------------------------------------------------------------------- */
+#define MI_BLUR_MEDIAN_MAX_RADIUS 7
+
+/* mi_blur_enqueue / mi_blur_enqueue_band with the median of that radius (same buffers, same band semantics: clamping at
+ * the band's own edges, only rows [out_row_begin, out_row_end) written; asynchronous).  Radius 1 and 2 on rows of whole
+ * 16-byte chunks at 16-byte aligned addresses with 1-4 channels take blur_median_fast_kernel, every other case
+ * blur_median_generic_kernel.  MI_BLUR_ERR_INVALID: radius outside 1..7, null or equal buffers, non-positive sizes. */
+int mi_blur_enqueue_median(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int radius,
+                           int n_images, void *stream);
+int mi_blur_enqueue_median_band(const uint8_t *d_in, uint8_t *d_out, int width, int band_rows, int channels, int radius,
+                                int out_row_begin, int out_row_end, void *stream);
+/* mi_blur_cpu_run with the median (a sliding per-channel histogram along each row). */
+int mi_blur_cpu_run_median(const uint8_t *in, uint8_t *out, int width, int height, int channels, int radius,
+                           int n_images, int n_threads);
+/* Give a context the median of that radius in place of its blur, with the rules of mi_blur_ctx_set_kernel: only before
+ * the first submit (MI_BLUR_ERR_STATE after), every submit form then uses it, never through the batch server, resident
+ * runs MI_BLUR_ERR_UNSUPPORTED.  A context holds one filter: mi_blur_ctx_set_kernel and this call each replace what the
+ * other set before. */
+int mi_blur_ctx_set_median(mi_blur_ctx *ctx, int radius);
 
 /* Developer diagnostics.  With mi_blur_set_option("debug_xcd_times", 1) every workgroup of the tiled kernel leaves its
  * start and end time (100 MHz ticks) in a slot of the XCD it ran on; this call waits for the device, returns per XCD the
