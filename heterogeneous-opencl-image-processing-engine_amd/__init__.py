@@ -46,7 +46,7 @@ def _newer(target: str, sources: list[str]) -> bool:
 def build_native(force: bool = False, verbose: bool = False) -> str:
     """Compile libmi_blur.so (hipcc, --offload-arch=gfx950) and the C++ hosts, in-tree."""
     srcs = [os.path.join(CSRC, f) for f in ("blur_kernels.hip", "sep_kernels.hip", "median_kernels.hip", "layout_kernels.hip", "mi_blur_api.cpp", "cpu_device.cpp")]
-    deps = srcs + [os.path.join(CSRC, f) for f in ("blur_launch.h", "cpu_device.h", "sep_taps.h")] + [HEADER]
+    deps = srcs + [os.path.join(CSRC, f) for f in ("blur_launch.h", "cpu_device.h", "filter.h")] + [HEADER]
     if force or not _newer(LIB_PATH, deps):
         cmd = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra",
                "-o", LIB_PATH] + srcs + ["-ldl", "-lpthread"]
@@ -404,19 +404,19 @@ class Context:
         return n.value, b.value
 
 
-def blur(images, ksize: int = 3, device: int = 0, batch: int = 0):
-    """Convenience for Python callers: the reference's blur of a stack of interleaved uint8 images, numpy in -> numpy out.
-
-    images: (H, W), (H, W, C) or (N, H, W, C) uint8.  ksize 3 (the reference kernel, gaussian_kernel.cl:36-41) or
-    5.  device: HIP ordinal, or DEVICE_CPU for the host-thread device.  batch: images per submit (0 = all at once, at most 4096).
-    Goes through mi_blur_create / mi_blur_submit / mi_blur_sync like any host; there is no other code path behind it."""
+def _images(images, name: str):
+    """images as a contiguous uint8 array of shape (H, W), (H, W, C) or (N, H, W, C); ValueError otherwise."""
     import numpy as np
     a = np.ascontiguousarray(images)
     if a.dtype != np.uint8 or a.ndim not in (2, 3, 4):
-        raise ValueError("blur: a uint8 array of shape (H, W), (H, W, C) or (N, H, W, C)")
-    if ksize not in (3, 5):
-        raise ValueError("blur: ksize 3 or 5")
-    single = a.ndim in (2, 3)
+        raise ValueError(f"{name}: a uint8 array of shape (H, W), (H, W, C) or (N, H, W, C)")
+    return a
+
+
+def _filter_images(a, radius: int, device: int, batch: int, configure=None):
+    """The numpy driver of blur, gaussian_blur and median_blur: a (from _images) through mi_blur_create (radius) /
+    configure(ctx) / mi_blur_submit / mi_blur_sync.  Returns the output as (N, H, W, C)."""
+    import numpy as np
     if a.ndim == 2:
         a = a[None, :, :, None]
     elif a.ndim == 3:
@@ -424,15 +424,31 @@ def blur(images, ksize: int = 3, device: int = 0, batch: int = 0):
     n, h, w, c = a.shape
     out = np.empty_like(a)
     if n == 0 or a.size == 0:
-        return out[0] if single else out
+        return out
     per = min(n, batch if batch > 0 else 4096)
     isz = h * w * c
-    with Context(device, w, h, c, (ksize - 1) // 2, max_batch=per, n_slots=2) as ctx:
+    with Context(device, w, h, c, radius, max_batch=per, n_slots=2) as ctx:
+        if configure:
+            configure(ctx)
         for i in range(0, n, per):
             m = min(per, n - i)
             ctx.submit(a.ctypes.data + i * isz, out.ctypes.data + i * isz, m)
         ctx.sync()
-    return out[0] if single else out
+    return out
+
+
+def blur(images, ksize: int = 3, device: int = 0, batch: int = 0):
+    """Convenience for Python callers: the reference's blur of a stack of interleaved uint8 images, numpy in -> numpy out.
+
+    images: (H, W), (H, W, C) or (N, H, W, C) uint8.  ksize 3 (the reference kernel, gaussian_kernel.cl:36-41) or
+    5.  device: HIP ordinal, or DEVICE_CPU for the host-thread device.  batch: images per submit (0 = all at once, at most 4096).
+    Goes through mi_blur_create / mi_blur_submit / mi_blur_sync like any host; there is no other code path behind it.
+    A single image comes back as (H, W, C), a 2-D one as (H, W, 1)."""
+    a = _images(images, "blur")
+    if ksize not in (3, 5):
+        raise ValueError("blur: ksize 3 or 5")
+    out = _filter_images(a, (ksize - 1) // 2, device, batch)
+    return out[0] if a.ndim in (2, 3) else out
 
 
 def gaussian_blur(images, sigma: float, sigma_y: float | None = None, radius: int = 0, device: int = 0, batch: int = 0):
@@ -441,29 +457,9 @@ def gaussian_blur(images, sigma: float, sigma_y: float | None = None, radius: in
     Integer taps from gauss_taps (8 bits per axis), radius 0 = ceil(3 sigma) clamped to [1, 16] per axis.  images: (H, W),
     (H, W, C) or (N, H, W, C) uint8; the result has the same shape.  device: HIP ordinal, or DEVICE_CPU.  Goes through mi_blur_create /
     mi_blur_ctx_set_kernel / mi_blur_submit / mi_blur_sync."""
-    import numpy as np
-    a = np.ascontiguousarray(images)
-    if a.dtype != np.uint8 or a.ndim not in (2, 3, 4):
-        raise ValueError("gaussian_blur: a uint8 array of shape (H, W), (H, W, C) or (N, H, W, C)")
+    a = _images(images, "gaussian_blur")
     kernel = gauss_kernel(sigma, sigma_y, radius)
-    shape = a.shape
-    if a.ndim == 2:
-        a = a[None, :, :, None]
-    elif a.ndim == 3:
-        a = a[None]
-    n, h, w, c = a.shape
-    out = np.empty_like(a)
-    if n == 0 or a.size == 0:
-        return out.reshape(shape)
-    per = min(n, batch if batch > 0 else 4096)
-    isz = h * w * c
-    with Context(device, w, h, c, 1, max_batch=per, n_slots=2) as ctx:
-        ctx.set_kernel(kernel)
-        for i in range(0, n, per):
-            m = min(per, n - i)
-            ctx.submit(a.ctypes.data + i * isz, out.ctypes.data + i * isz, m)
-        ctx.sync()
-    return out.reshape(shape)
+    return _filter_images(a, 1, device, batch, lambda ctx: ctx.set_kernel(kernel)).reshape(a.shape)
 
 
 def median_blur(images, ksize: int = 3, device: int = 0, batch: int = 0):
@@ -472,27 +468,7 @@ def median_blur(images, ksize: int = 3, device: int = 0, batch: int = 0):
     Edges clamp; every output byte is the exact median of its window.  images: (H, W), (H, W, C) or (N, H, W, C) uint8;
     the result has the same shape.  device: HIP ordinal, or DEVICE_CPU.  Goes through mi_blur_create /
     mi_blur_ctx_set_median / mi_blur_submit / mi_blur_sync."""
-    import numpy as np
     if ksize % 2 != 1 or not 3 <= ksize <= 2 * MEDIAN_MAX_RADIUS + 1:
         raise ValueError(f"median_blur: ksize must be odd, 3..{2 * MEDIAN_MAX_RADIUS + 1}")
-    a = np.ascontiguousarray(images)
-    if a.dtype != np.uint8 or a.ndim not in (2, 3, 4):
-        raise ValueError("median_blur: a uint8 array of shape (H, W), (H, W, C) or (N, H, W, C)")
-    shape = a.shape
-    if a.ndim == 2:
-        a = a[None, :, :, None]
-    elif a.ndim == 3:
-        a = a[None]
-    n, h, w, c = a.shape
-    out = np.empty_like(a)
-    if n == 0 or a.size == 0:
-        return out.reshape(shape)
-    per = min(n, batch if batch > 0 else 4096)
-    isz = h * w * c
-    with Context(device, w, h, c, 1, max_batch=per, n_slots=2) as ctx:
-        ctx.set_median(ksize // 2)
-        for i in range(0, n, per):
-            m = min(per, n - i)
-            ctx.submit(a.ctypes.data + i * isz, out.ctypes.data + i * isz, m)
-        ctx.sync()
-    return out.reshape(shape)
+    a = _images(images, "median_blur")
+    return _filter_images(a, 1, device, batch, lambda ctx: ctx.set_median(ksize // 2)).reshape(a.shape)

@@ -94,12 +94,8 @@ int main(int argc, char **argv)
     printf("Number of batches: %d\n", NUM_BATCHES);
     printf("Work-group size: %dx%d\n", local_work_size, local_work_size);
     printf("Execution mode : %d\n", mode);
-    mi_blur_sep_kernel sep{};
-    const bool use_sep = sep_kernel_of(opt, &sep);
-    const int median_r = median_radius_of(opt);
-    if (median_r) printf("Blur kernel: %dx%d median\n", opt.median, opt.median);
-    else if (use_sep) print_sep_kernel(sep, opt.sigma, opt.sigma_y);
-    else printf("Blur kernel: %dx%d\n", opt.ksize, opt.ksize);
+    const HostFilter filter = filter_of(opt);
+    print_filter(filter);
     printf("================================================\n\n");
 
     if (!frame_files.empty()) {
@@ -112,7 +108,6 @@ int main(int argc, char **argv)
     Image img = load_image(input_filename, opt.syn_w, opt.syn_h, opt.syn_c, opt.synthetic);
     if (!opt.save_input.empty()) save_one_image(opt.save_input.c_str(), img.px.data(), img.width, img.height, img.channels);
     const int width = img.width, height = img.height, channels = img.channels;
-    const int radius = opt.ksize == 3 ? 1 : 2;
     printf("Original image loaded: %dx%d, %d channels\n", width, height, channels);
     const size_t image_size = (size_t)width * height * channels;
     printf("Size of one image: %zu bytes (%.2f KB)\n", image_size, image_size / 1024.0);
@@ -140,10 +135,9 @@ int main(int argc, char **argv)
     Dev cpu;
     std::vector<Dev> gpus(G);
     if (mode != 2) {
-        mi_check(mi_blur_create(&cpu.ctx, MI_BLUR_DEVICE_CPU, width, height, channels, radius, BATCH_SIZE, nslots, opt.threads),
+        mi_check(mi_blur_create(&cpu.ctx, MI_BLUR_DEVICE_CPU, width, height, channels, filter.radius, BATCH_SIZE, nslots, opt.threads),
                  "Failed to create CPU context");
-        if (use_sep) mi_check(mi_blur_ctx_set_kernel(cpu.ctx, &sep), "Failed to set the blur kernel");
-        if (median_r) mi_check(mi_blur_ctx_set_median(cpu.ctx, median_r), "Failed to set the median");
+        set_filter(cpu.ctx, filter);
         const unsigned hc = std::thread::hardware_concurrency();
         cpu.name = "host threads x" + std::to_string(opt.threads > 0 ? opt.threads : std::min((int)(hc ? hc : 1), 16));
         printf("CPU device: %s\n", cpu.name.c_str());
@@ -158,11 +152,10 @@ int main(int argc, char **argv)
     const int feed_pieces = per_gpu_feeders ? std::max(1, std::min(4, (share_max + 63) / 64)) : 1;
     const int feed_piece = (share_max + feed_pieces - 1) / feed_pieces;
     for (int g = 0; g < G; g++) {
-        mi_check(per_gpu_feeders ? mi_blur_create(&gpus[g].ctx, hip_ordinal(g), width, height, channels, radius, feed_piece, nslots * feed_pieces, 0)
-                                 : mi_blur_create(&gpus[g].ctx, hip_ordinal(g), width, height, channels, radius, BATCH_SIZE, nslots, 0),
+        mi_check(per_gpu_feeders ? mi_blur_create(&gpus[g].ctx, hip_ordinal(g), width, height, channels, filter.radius, feed_piece, nslots * feed_pieces, 0)
+                                 : mi_blur_create(&gpus[g].ctx, hip_ordinal(g), width, height, channels, filter.radius, BATCH_SIZE, nslots, 0),
                  "Failed to create GPU context");
-        if (use_sep) mi_check(mi_blur_ctx_set_kernel(gpus[g].ctx, &sep), "Failed to set the blur kernel");
-        if (median_r) mi_check(mi_blur_ctx_set_median(gpus[g].ctx, median_r), "Failed to set the median");
+        set_filter(gpus[g].ctx, filter);
         gpus[g].name = "HIP device " + std::to_string(hip_ordinal(g)) + (virtual_gpus() ? " (logical GPU " + std::to_string(g) + ")" : "");
         printf("GPU device: %s\n", gpus[g].name.c_str());
         gpus[g].submitted.assign(NUM_BATCHES, 0);
@@ -522,7 +515,7 @@ static int run_frames(const Options &opt, int mode, int BATCH_SIZE, const std::v
     const int NB = (N + BATCH_SIZE - 1) / BATCH_SIZE;
     int width = 0, height = 0, channels = 0;
     if (!probe_frame(files[0], width, height, channels)) { printf("Error: cannot read frame %s\n", files[0].c_str()); return -1; }
-    const int radius = opt.ksize == 3 ? 1 : 2;
+    const HostFilter filter = filter_of(opt);
     const size_t image_size = (size_t)width * height * channels;
     printf("Frame geometry (from %s): %dx%d, %d channels, %zu bytes\n", files[0].c_str(), width, height, channels, image_size);
     const int G = mode == 1 ? 1 : opt.gpus;
@@ -546,11 +539,9 @@ static int run_frames(const Options &opt, int mode, int BATCH_SIZE, const std::v
     const int ctx_channels = planes_as_images ? 1 : channels, per_frame = planes_as_images ? channels : 1;
     std::vector<mi_blur_ctx *> ctx(G, nullptr);
     for (int g = 0; g < G; g++) {
-        mi_check(mi_blur_create(&ctx[g], mode == 1 ? MI_BLUR_DEVICE_CPU : hip_ordinal(g), width, height, ctx_channels, radius, BATCH_SIZE * per_frame,
-                                per_dev_slots, opt.threads), "Failed to create context");
-        mi_blur_sep_kernel sep{};
-        if (sep_kernel_of(opt, &sep)) mi_check(mi_blur_ctx_set_kernel(ctx[g], &sep), "Failed to set the blur kernel");
-        if (median_radius_of(opt)) mi_check(mi_blur_ctx_set_median(ctx[g], median_radius_of(opt)), "Failed to set the median");
+        mi_check(mi_blur_create(&ctx[g], mode == 1 ? MI_BLUR_DEVICE_CPU : hip_ordinal(g), width, height, ctx_channels, filter.radius,
+                                BATCH_SIZE * per_frame, per_dev_slots, opt.threads), "Failed to create context");
+        set_filter(ctx[g], filter);
         if (mode == 2) { printf("GPU device: HIP device %d\n", hip_ordinal(g)); report_placement(g, hip_ordinal(g), g == 0); }
         else printf("CPU device: host threads\n");
     }

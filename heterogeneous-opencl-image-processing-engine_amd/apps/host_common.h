@@ -250,22 +250,43 @@ inline int parse_flags(int argc, char **argv, Options &o)
     return npos;
 }
 
-// --sigma: the separable Gaussian every context of the run is given (mi_blur_sep_kernel_gauss, 8-bit taps per axis).
-inline bool sep_kernel_of(const Options &o, mi_blur_sep_kernel *k)
+// The one filter every context of the run is given, from --ksize, --sigma or --median (they exclude each other).
+struct HostFilter {
+    int radius;                 // --ksize 3|5: 1|2.  Every context is created with it (1 under --sigma and --median).
+    bool sep;                   // --sigma: this separable Gaussian (mi_blur_sep_kernel_gauss, 8-bit taps per axis)
+    mi_blur_sep_kernel k;
+    double sigma, sigma_y;
+    int median;                 // --median K: the KxK median, radius K / 2; 0 = none
+};
+
+inline HostFilter filter_of(const Options &o)
 {
-    if (o.sigma <= 0.0) return false;
-    if (mi_blur_sep_kernel_gauss(o.sigma, o.sigma_y, o.sep_radius, 8, k) != MI_BLUR_OK) {
+    HostFilter f{o.ksize == 3 ? 1 : 2, o.sigma > 0.0, {}, o.sigma, o.sigma_y, o.median};
+    if (f.sep && mi_blur_sep_kernel_gauss(o.sigma, o.sigma_y, o.sep_radius, 8, &f.k) != MI_BLUR_OK) {
         printf("Error: no Gaussian taps for sigma %g / %g, radius %d\n", o.sigma, o.sigma_y, o.sep_radius);
         exit(-1);
     }
-    return true;
+    return f;
 }
-// --median K: the radius every context of the run is given (mi_blur_ctx_set_median); 0 = no median.
-inline int median_radius_of(const Options &o) { return o.median / 2; }
 
-inline void print_sep_kernel(const mi_blur_sep_kernel &k, double sx, double sy)
+// Give a context made with f.radius the filter (mi_blur_ctx_set_kernel / mi_blur_ctx_set_median; nothing for --ksize).
+inline void set_filter(mi_blur_ctx *ctx, const HostFilter &f)
 {
-    printf("Blur kernel: %dx%d separable Gaussian, sigma %g x %g\n", 2 * k.rx + 1, 2 * k.ry + 1, sx, sy > 0.0 ? sy : sx);
+    if (f.sep) mi_check(mi_blur_ctx_set_kernel(ctx, &f.k), "Failed to set the blur kernel");
+    if (f.median) mi_check(mi_blur_ctx_set_median(ctx, f.median / 2), "Failed to set the median");
+}
+
+// Rows a band needs on each side: the median's radius, the Gaussian's vertical radius (at least one row, so that the
+// split geometry stays the reference's), or the box radius.
+inline int filter_halo(const HostFilter &f) { return f.median ? f.median / 2 : f.sep ? std::max(1, f.k.ry) : f.radius; }
+
+// The banner's "Blur kernel" line (with the taps of a Gaussian).
+inline void print_filter(const HostFilter &f)
+{
+    if (f.median) { printf("Blur kernel: %dx%d median\n", f.median, f.median); return; }
+    if (!f.sep) { printf("Blur kernel: %dx%d\n", 2 * f.radius + 1, 2 * f.radius + 1); return; }
+    const mi_blur_sep_kernel &k = f.k;
+    printf("Blur kernel: %dx%d separable Gaussian, sigma %g x %g\n", 2 * k.rx + 1, 2 * k.ry + 1, f.sigma, f.sigma_y > 0.0 ? f.sigma_y : f.sigma);
     printf("Taps x (/%d):", 1 << k.bx);
     for (int i = 0; i <= 2 * k.rx; i++) printf(" %d", k.wx[i]);
     printf("\nTaps y (/%d):", 1 << k.by);

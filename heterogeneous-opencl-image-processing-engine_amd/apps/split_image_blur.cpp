@@ -44,13 +44,8 @@ int main(int argc, char **argv)
     const int npos = parse_flags(argc, argv, opt);
     if (opt.resident) return run_resident(opt);
     const int NUM_IMAGES = opt.images;
-    mi_blur_sep_kernel sep{};
-    const bool use_sep = sep_kernel_of(opt, &sep);
-    // --sigma: the halo is the kernel's vertical radius (at least one row, so the split geometry stays the reference's)
-    const int median_r = median_radius_of(opt);
-    // --median K: the halo is the median's radius
-    const int HALO = median_r ? median_r : use_sep ? std::max(1, sep.ry) : opt.ksize == 3 ? 1 : 2;
-    const int ctx_radius = (use_sep || median_r) ? 1 : HALO;   // contexts take the separable kernel / median right after creation
+    const HostFilter filter = filter_of(opt);
+    const int HALO = filter_halo(filter);
 
     if (npos > 1) {
         gpu_ratio = atof(argv[1]);
@@ -78,8 +73,7 @@ int main(int argc, char **argv)
     printf("Work-group size: %dx%d\n", local_work_size, local_work_size);
     printf("GPU ratio: %.1f%% (rows to GPU)\n", gpu_ratio * 100);
     printf("Halo size: %d row(s)\n", HALO);
-    if (use_sep) print_sep_kernel(sep, opt.sigma, opt.sigma_y);
-    if (median_r) printf("Blur kernel: %dx%d median\n", opt.median, opt.median);
+    if (filter.sep || filter.median) print_filter(filter);
     printf("================================================\n\n");
 
     // ---------------- load original image (split_image_blur.c:106-139)
@@ -119,10 +113,9 @@ int main(int argc, char **argv)
     Part cpu;
     cpu.in_row0 = 0; cpu.band_rows = geo.cpu_input_rows; cpu.halo_top = 0; cpu.halo_bottom = HALO;
     cpu.out_row0 = 0; cpu.out_rows = geo.cpu_output_rows;
-    mi_check(mi_blur_create(&cpu.ctx, MI_BLUR_DEVICE_CPU, width, height, channels, ctx_radius, BATCH_SIZE, nslots, opt.threads),
+    mi_check(mi_blur_create(&cpu.ctx, MI_BLUR_DEVICE_CPU, width, height, channels, filter.radius, BATCH_SIZE, nslots, opt.threads),
              "Failed to create CPU context");
-    if (use_sep) mi_check(mi_blur_ctx_set_kernel(cpu.ctx, &sep), "Failed to set the blur kernel");
-    if (median_r) mi_check(mi_blur_ctx_set_median(cpu.ctx, median_r), "Failed to set the median");
+    set_filter(cpu.ctx, filter);
     cpu.name = "host threads";
     printf("CPU device: %s\n", cpu.name.c_str());
     std::vector<Part> gpus(G);
@@ -137,9 +130,8 @@ int main(int argc, char **argv)
         p.in_row0 = p.out_row0 - p.halo_top;
         p.band_rows = p.out_rows + p.halo_top + p.halo_bottom;
         if (p.out_rows <= 0) { printf("Error: more GPUs than GPU rows\n"); return -1; }
-        mi_check(mi_blur_create(&p.ctx, hip_ordinal(g), width, height, channels, ctx_radius, BATCH_SIZE, nslots, 0), "Failed to create GPU context");
-        if (use_sep) mi_check(mi_blur_ctx_set_kernel(p.ctx, &sep), "Failed to set the blur kernel");
-        if (median_r) mi_check(mi_blur_ctx_set_median(p.ctx, median_r), "Failed to set the median");
+        mi_check(mi_blur_create(&p.ctx, hip_ordinal(g), width, height, channels, filter.radius, BATCH_SIZE, nslots, 0), "Failed to create GPU context");
+        set_filter(p.ctx, filter);
         p.name = "HIP device " + std::to_string(hip_ordinal(g));
         printf("GPU device: %s (rows %d-%d)\n", p.name.c_str(), p.out_row0, p.out_row0 + p.out_rows - 1);
     }

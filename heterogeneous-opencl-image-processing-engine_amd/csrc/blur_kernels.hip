@@ -1381,7 +1381,7 @@ static int launch_fused_r(const LaunchDesc &d, const TiledParams &p, const Fused
 static int tiled_geometry(const LaunchDesc &d, const Tunables &tun, bool ragged, bool fused, int rpg_forced, TiledParams &p,
                           unsigned *block_threads, size_t *lds_bytes)
 {
-    const int R = d.radius;
+    const int R = d.filter->radius;
     const int pitch = d.width * d.channels, cpr = (pitch + 15) / 16, rows = d.y1 - d.y0;   // ragged: last chunk partial
     // Output rows per thread.  8 amortises the 2R priming rows of the sliding window best when the grid is
     // large; small and mid-size grids (a batch of 35 256x256 images is ~840 waves at 8 rows) finish sooner
@@ -1441,7 +1441,7 @@ static int launch_tiled(const LaunchDesc &d, const Tunables &tun, bool ragged = 
 {
     if (!(fused && fused->geometry_only))
         g_last_kernel = fused ? "blur_fused_kernel" : (d.max_blocks > 0 && !ragged && d.channels <= 4 ? "blur_tiled_loop_kernel" : "blur_tiled_kernel");
-    const int R = d.radius;
+    const int R = d.filter->radius;
     TiledParams p{};
     unsigned threads = 0;
     size_t lds = 0;
@@ -1509,8 +1509,8 @@ int zc_fill_batch(const LaunchDesc &d, ZcGeometry *geo, ZcBatch *b, unsigned *n_
     size_t lds = 0;
     const int rpg = tiled_geometry(d, tun, ragged, false, 4, p, &threads, &lds);
     if (rpg < 0) return rpg;
-    if (geo->threads == 0) { geo->threads = threads; geo->lds = lds; geo->rpg = rpg; geo->channels = d.channels; geo->radius = d.radius; geo->ragged = ragged ? 1 : 0; }
-    else if (geo->threads != threads || geo->lds != lds || geo->rpg != rpg || geo->channels != d.channels || geo->radius != d.radius ||
+    if (geo->threads == 0) { geo->threads = threads; geo->lds = lds; geo->rpg = rpg; geo->channels = d.channels; geo->radius = d.filter->radius; geo->ragged = ragged ? 1 : 0; }
+    else if (geo->threads != threads || geo->lds != lds || geo->rpg != rpg || geo->channels != d.channels || geo->radius != d.filter->radius ||
              geo->ragged != (ragged ? 1 : 0))
         return MI_BLUR_ERR_UNSUPPORTED;                                      // another tile shape than the running server's
     memset(b->params, 0, sizeof b->params);
@@ -1561,7 +1561,8 @@ int launch_fused_watch(const unsigned *count, unsigned n_batches, unsigned tiles
 int launch_fused(const LaunchDesc &d, const FusedDesc &f)
 {
     if (!d.in || !d.out || d.in == d.out || (!f.count && !f.geometry_only) || f.batch_images <= 0) return MI_BLUR_ERR_INVALID;
-    if (d.width <= 0 || d.band_rows <= 0 || d.n_images <= 0 || (d.radius != 1 && d.radius != 2)) return MI_BLUR_ERR_INVALID;
+    if (!d.filter || d.filter->kind != FilterKind::BOX) return MI_BLUR_ERR_INVALID;
+    if (d.width <= 0 || d.band_rows <= 0 || d.n_images <= 0 || (d.filter->radius != 1 && d.filter->radius != 2)) return MI_BLUR_ERR_INVALID;
     if (d.y0 != 0 || d.y1 != d.band_rows || d.in_stride || d.out_stride) return MI_BLUR_ERR_INVALID;
     if ((long long)d.width * d.channels * d.band_rows > INT_MAX) return MI_BLUR_ERR_INVALID;
     const Tunables &tn = f.tun ? *f.tun : tunables();
@@ -1594,7 +1595,7 @@ static int launch_stream(const LaunchDesc &d, const Tunables &tun)
             const double waves = (double)d.n_images * nb * cpr / 64.0;
             const double rounds = waves / slots;
             const double full = rounds >= 1.0 ? rounds / ceil(rounds - 1e-9) : rounds;
-            const double score = full * bh / (bh + 2.0 * d.radius);
+            const double score = full * bh / (bh + 2.0 * d.filter->radius);
             if (score > best + 1e-9) { best = score; BH = bh; }
         }
         // small grids (well under one round of resident waves): shorter bands, more waves
@@ -1612,7 +1613,7 @@ static int launch_stream(const LaunchDesc &d, const Tunables &tun)
     p.updown = tun.stream_updown;
     const dim3 grid((unsigned)nblocks), block(256);
     const size_t lds = 4 * STREAM_D * STREAM_ROWB;
-    switch (d.channels * 10 + d.radius) {
+    switch (d.channels * 10 + d.filter->radius) {
     case 11: return do_launch(blur_stream_kernel<1, 1>, grid, block, lds, d, p);
     case 12: return do_launch(blur_stream_kernel<1, 2>, grid, block, lds, d, p);
     case 21: return do_launch(blur_stream_kernel<2, 1>, grid, block, lds, d, p);
@@ -1664,7 +1665,7 @@ static int launch_direct_bh(const LaunchDesc &d, const Tunables &tun)
         if constexpr (BH == 8) {
             p.top = d.halo_top; p.bottom = d.halo_bottom;
             g_last_kernel = "blur_direct_kernel (peer halo rows)";
-            switch (d.channels * 10 + d.radius) {
+            switch (d.channels * 10 + d.filter->radius) {
             case 11: return do_launch(blur_direct_kernel<1, 1, 8, true>, grid, block, 0, d, p);
             case 12: return do_launch(blur_direct_kernel<1, 2, 8, true>, grid, block, 0, d, p);
             case 21: return do_launch(blur_direct_kernel<2, 1, 8, true>, grid, block, 0, d, p);
@@ -1678,10 +1679,10 @@ static int launch_direct_bh(const LaunchDesc &d, const Tunables &tun)
         return MI_BLUR_ERR_INVALID;
     }
     if constexpr (BH != 8) {
-        return d.radius == 1 ? do_launch(blur_direct_kernel<3, 1, BH>, grid, block, 0, d, p)
+        return d.filter->radius == 1 ? do_launch(blur_direct_kernel<3, 1, BH>, grid, block, 0, d, p)
                              : do_launch(blur_direct_kernel<3, 2, BH>, grid, block, 0, d, p);
     } else {
-        switch (d.channels * 10 + d.radius) {
+        switch (d.channels * 10 + d.filter->radius) {
         case 11: return do_launch(blur_direct_kernel<1, 1, BH>, grid, block, 0, d, p);
         case 12: return do_launch(blur_direct_kernel<1, 2, BH>, grid, block, 0, d, p);
         case 21: return do_launch(blur_direct_kernel<2, 1, BH>, grid, block, 0, d, p);
@@ -1708,23 +1709,24 @@ static int launch_generic(const LaunchDesc &d)
     long long blocks = (p.total + 255) / 256;
     if (blocks > 256LL * 64) blocks = 256LL * 64;   // grid-stride the rest
     const dim3 grid((unsigned)blocks), block(256);
-    return d.radius == 1 ? do_launch(blur_generic_kernel<1>, grid, block, 0, d, p)
+    return d.filter->radius == 1 ? do_launch(blur_generic_kernel<1>, grid, block, 0, d, p)
                          : do_launch(blur_generic_kernel<2>, grid, block, 0, d, p);
 }
 
 int launch(const LaunchDesc &d)
 {
-    if (d.median_radius) return launch_median(d);
-    if (d.sep) return launch_sep(d);
+    if (!d.filter) return MI_BLUR_ERR_INVALID;
+    if (d.filter->kind == FilterKind::SEP) return launch_sep(d);
+    if (d.filter->kind == FilterKind::MEDIAN) return launch_median(d);
     if (!d.in || !d.out || d.in == d.out) return MI_BLUR_ERR_INVALID;
     if (d.width <= 0 || d.band_rows <= 0 || d.channels <= 0 || d.n_images < 0) return MI_BLUR_ERR_INVALID;
-    if (d.radius != 1 && d.radius != 2) return MI_BLUR_ERR_INVALID;
+    if (d.filter->radius != 1 && d.filter->radius != 2) return MI_BLUR_ERR_INVALID;
     if (d.y0 < 0 || d.y1 > d.band_rows || d.y0 >= d.y1) return MI_BLUR_ERR_INVALID;
     if ((long long)d.width * d.channels > INT_MAX / 2) return MI_BLUR_ERR_INVALID;
     if ((long long)d.width * d.channels * d.band_rows > INT_MAX) return MI_BLUR_ERR_INVALID;  // per-image 32-bit
     if (d.n_images == 0) return MI_BLUR_OK;
     const Tunables tun = tunables();                  // one coherent set of knobs for this launch
-    const bool wide = wide_channels(d.channels, d.radius);
+    const bool wide = wide_channels(d.channels, d.filter->radius);
     const long long row_bytes = (long long)d.width * d.channels;
     const bool can_tile = wide ? (row_bytes % 16 == 0 && (uintptr_t)d.in % 16 == 0 && (uintptr_t)d.out % 16 == 0)
                                : tiled_eligible(d.in, d.out, d.width, d.channels);
@@ -1760,7 +1762,7 @@ int launch(const LaunchDesc &d)
         // Zero-copy submits keep the capped-grid tiled kernel.
         if (direct_fits(d) && d.max_blocks <= 0 &&
             (tun.prefer_direct == 2 ||
-             (tun.prefer_direct == 1 && (d.radius == 2 || (dense_out * d.n_images <= (128LL << 20) && d.concurrent <= 1)))))
+             (tun.prefer_direct == 1 && (d.filter->radius == 2 || (dense_out * d.n_images <= (128LL << 20) && d.concurrent <= 1)))))
             return launch_direct(d, tun);
         return launch_tiled(d, tun);
     case MI_BLUR_VARIANT_GENERIC: return launch_generic(d);

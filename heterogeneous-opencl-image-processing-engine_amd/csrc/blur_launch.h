@@ -4,16 +4,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "sep_taps.h"
+#include "filter.h"
 
 namespace mi_blur {
 
 struct LaunchDesc {
-    const SepTaps *sep;     // non-null: this separable kernel instead of `radius` (launch_sep, sep_kernels.hip)
-    int median_radius;      // 1..7: the median of that radius instead of `radius` (launch_median, median_kernels.hip); 0 = none
+    const Filter *filter;   // what to apply (filter.h); the caller keeps it alive until launch() returns
     const uint8_t *in;      // device, n_images bands of band_rows rows, laid end to end
     uint8_t *out;           // device, n_images blocks of (y1-y0) rows
-    int width, band_rows, channels, radius;
+    int width, band_rows, channels;
     int n_images;
     int y0, y1;             // output rows [y0,y1) of each band
     long long in_stride, out_stride;  // bytes between consecutive bands / output blocks; 0 = laid end to end.
@@ -28,13 +27,14 @@ struct LaunchDesc {
     hipEvent_t start, stop; // optional: dispatch start/stop timestamps (hipExtLaunchKernel)
 };
 
-// Returns MI_BLUR_OK or a negative mi_blur_status.  d.median_radius set: handed to launch_median; d.sep set: to launch_sep.
+// Returns MI_BLUR_OK or a negative mi_blur_status.  A SEP filter is handed to launch_sep, a MEDIAN one to launch_median;
+// launch_fused and zc_fill_batch take BOX filters only.
 int launch(const LaunchDesc &d);
-// Separable kernel of d.sep (sep_kernels.hip): the aligned LDS-tiled kernel or the generic one.  Honours in/out strides,
+// Separable kernel of d.filter->taps (sep_kernels.hip): the aligned LDS-tiled kernel or the generic one.  Honours in/out strides,
 // bands [y0, y1) and the per-image 32-bit offsets of launch(); ignores max_blocks, concurrent and variant (AUTO);
 // halo_top / halo_bottom: MI_BLUR_ERR_UNSUPPORTED.
 int launch_sep(const LaunchDesc &d);
-// Median of radius d.median_radius (median_kernels.hip): the register-window kernel for radius 1|2 on aligned rows of
+// Median of radius d.filter->radius (median_kernels.hip): the register-window kernel for radius 1|2 on aligned rows of
 // 1-4 channels, the generic one otherwise.  Honours in/out strides, bands [y0, y1) and the 64-bit image offsets of
 // launch(); ignores max_blocks, concurrent and variant (AUTO); halo_top / halo_bottom: MI_BLUR_ERR_UNSUPPORTED.
 int launch_median(const LaunchDesc &d);

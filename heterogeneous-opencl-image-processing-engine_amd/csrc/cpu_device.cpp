@@ -243,8 +243,8 @@ void cpu_median_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, int R
 
 // n_images bands of band_rows rows; output rows [y0,y1) of each.  Threads take whole
 // images when there are enough of them, else row slices of each image.
-void cpu_blur_batch(const uint8_t *in, uint8_t *out, int W, int band_rows, int C, int R, int n_images,
-                    int y0, int y1, int n_threads, size_t in_stride, size_t out_stride, const SepTaps *sep, int median_r)
+void cpu_blur_batch(const uint8_t *in, uint8_t *out, int W, int band_rows, int C, const Filter &f, int n_images,
+                    int y0, int y1, int n_threads, size_t in_stride, size_t out_stride)
 {
     if (n_images <= 0) return;
     if (n_threads <= 0) n_threads = hardware_threads();
@@ -266,9 +266,11 @@ void cpu_blur_batch(const uint8_t *in, uint8_t *out, int W, int band_rows, int C
             if (it >= items) break;
             const int img = (int)(it / slices), s = (int)(it % slices);
             const int ys = y0 + (int)((long long)rows * s / slices), ye = y0 + (int)((long long)rows * (s + 1) / slices);
-            if (median_r) cpu_median_rows(in + img * in_stride, out + img * out_stride, W, band_rows, C, median_r, ys, ye, y0);
-            else if (sep) cpu_blur_rows_sep(in + img * in_stride, out + img * out_stride, W, band_rows, C, *sep, ys, ye, y0);
-            else cpu_blur_rows(in + img * in_stride, out + img * out_stride, W, band_rows, C, R, ys, ye, y0);
+            const uint8_t *src = in + img * in_stride;
+            uint8_t *dst = out + img * out_stride;
+            if (f.kind == FilterKind::MEDIAN) cpu_median_rows(src, dst, W, band_rows, C, f.radius, ys, ye, y0);
+            else if (f.kind == FilterKind::SEP) cpu_blur_rows_sep(src, dst, W, band_rows, C, f.taps, ys, ye, y0);
+            else cpu_blur_rows(src, dst, W, band_rows, C, f.radius, ys, ye, y0);
         }
     };
     const int nt = (int)std::min<long long>(n_threads, items);

@@ -3,7 +3,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include "sep_taps.h"
+#include "filter.h"
 
 namespace mi_blur {
 
@@ -15,10 +15,14 @@ void cpu_blur_rows_sep(const uint8_t *in, uint8_t *out, int W, int H, int C, con
                        int out_row_shift);
 // Rows [y_begin, y_end) of the median of radius R (1..7): a sliding per-channel histogram along each row.
 void cpu_median_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, int R, int y_begin, int y_end, int out_row_shift);
-// sep non-null: that separable kernel, R ignored.  median_r > 0: the median of that radius, R and sep ignored.
-void cpu_blur_batch(const uint8_t *in, uint8_t *out, int W, int band_rows, int C, int R, int n_images,
-                    int y0, int y1, int n_threads, size_t in_stride = 0, size_t out_stride = 0, const SepTaps *sep = nullptr,
-                    int median_r = 0);
+void cpu_blur_batch(const uint8_t *in, uint8_t *out, int W, int band_rows, int C, const Filter &f, int n_images,
+                    int y0, int y1, int n_threads, size_t in_stride = 0, size_t out_stride = 0);
+// The box blur of radius R (1|2): the form the host-only sanitizer harness (tests/san_cpu_device.cpp) drives.
+inline void cpu_blur_batch(const uint8_t *in, uint8_t *out, int W, int band_rows, int C, int R, int n_images,
+                           int y0, int y1, int n_threads, size_t in_stride = 0, size_t out_stride = 0)
+{
+    cpu_blur_batch(in, out, W, band_rows, C, Filter{FilterKind::BOX, R, {}}, n_images, y0, y1, n_threads, in_stride, out_stride);
+}
 // planar (CImg storage: all of channel 0, then channel 1, ...) <-> interleaved, n_images frames, a few pool threads
 void cpu_repack(const uint8_t *src, uint8_t *dst, int W, int H, int C, int n_images, bool planar_to_interleaved, int n_threads);
 void copy_blocks(uint8_t *dst, size_t dst_stride, const uint8_t *src, size_t src_stride, size_t bytes, int n, int n_threads);

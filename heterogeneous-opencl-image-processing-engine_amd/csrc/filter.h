@@ -1,0 +1,57 @@
+// filter.h — internal: the one filter a launch, a context or a CPU run applies, in the form the GPU kernels
+// (blur_kernels.hip, sep_kernels.hip, median_kernels.hip) and the CPU device (cpu_device.cpp) take it.  Plain C++, no HIP.
+#pragma once
+
+#include "../../include/mi_blur.h"
+
+namespace mi_blur {
+
+constexpr int SEP_MAX_R = 16;
+
+// A validated separable kernel (mi_blur_sep_kernel).  Taps CENTRED: wx[SEP_MAX_R + d] = weight of the pixel d columns
+// away, 0 beyond the radius (likewise wy for rows), so loops unrolled over d index them with compile-time constants.
+struct SepTaps {
+    int rx, ry, shift;      // shift = bx + by: the one truncating shift at the end
+    unsigned wx[2 * SEP_MAX_R + 1], wy[2 * SEP_MAX_R + 1];
+};
+
+enum class FilterKind { BOX, SEP, MEDIAN };
+
+// BOX: the fixed 3x3 / 5x5 kernel of `radius` 1|2.  SEP: the separable kernel `taps`.  MEDIAN: the median of `radius` 1..7.
+struct Filter {
+    FilterKind kind;
+    int radius;             // BOX and MEDIAN
+    SepTaps taps;           // SEP
+};
+
+// The constructors validate: MI_BLUR_OK, or MI_BLUR_ERR_INVALID with *f untouched.
+inline int filter_box(int radius, Filter *f)
+{
+    if (radius != 1 && radius != 2) return MI_BLUR_ERR_INVALID;
+    *f = Filter{FilterKind::BOX, radius, {}};
+    return MI_BLUR_OK;
+}
+
+inline int filter_sep(const mi_blur_sep_kernel *k, Filter *f)
+{
+    if (!k || !f) return MI_BLUR_ERR_INVALID;
+    if (k->rx < 0 || k->rx > MI_BLUR_SEP_MAX_RADIUS || k->ry < 0 || k->ry > MI_BLUR_SEP_MAX_RADIUS) return MI_BLUR_ERR_INVALID;
+    if (k->bx < 0 || k->bx > 8 || k->by < 0 || k->by > 8) return MI_BLUR_ERR_INVALID;
+    SepTaps t{};
+    long long sx = 0, sy = 0;
+    for (int i = 0; i <= 2 * k->rx; i++) { sx += k->wx[i]; t.wx[SEP_MAX_R - k->rx + i] = k->wx[i]; }
+    for (int j = 0; j <= 2 * k->ry; j++) { sy += k->wy[j]; t.wy[SEP_MAX_R - k->ry + j] = k->wy[j]; }
+    if (sx != (1LL << k->bx) || sy != (1LL << k->by)) return MI_BLUR_ERR_INVALID;
+    t.rx = k->rx; t.ry = k->ry; t.shift = k->bx + k->by;
+    *f = Filter{FilterKind::SEP, 0, t};
+    return MI_BLUR_OK;
+}
+
+inline int filter_median(int radius, Filter *f)
+{
+    if (radius < 1 || radius > MI_BLUR_MEDIAN_MAX_RADIUS) return MI_BLUR_ERR_INVALID;
+    *f = Filter{FilterKind::MEDIAN, radius, {}};
+    return MI_BLUR_OK;
+}
+
+}  // namespace mi_blur

@@ -310,14 +310,14 @@ int launch_median_fast(const LaunchDesc &d)
     p.in_stride = d.in_stride ? d.in_stride : (long long)d.band_rows * pitch;
     p.out_stride = d.out_stride ? d.out_stride : (long long)rows * pitch;
     p.pitch = pitch; p.cpr = cpr; p.H = d.band_rows; p.y0 = d.y0; p.y1 = d.y1;
-    const int bh = med_bh(d.median_radius);
+    const int bh = med_bh(d.filter->radius);
     p.nbands = (rows + bh - 1) / bh;
     p.total = (long long)d.n_images * p.nbands * cpr;
     const long long waves = (p.total + 61) / 62, nblocks = (waves + 3) / 4;
     p.nblocks = (unsigned)nblocks;
     p.xcd = nblocks >= 16 ? 1 : 0;
     const dim3 grid((unsigned)nblocks), block(256);
-    switch (d.channels * 10 + d.median_radius) {
+    switch (d.channels * 10 + d.filter->radius) {
     case 11: return med_do_launch(blur_median_fast_kernel<1, 1, med_bh(1)>, grid, block, d, p);
     case 12: return med_do_launch(blur_median_fast_kernel<1, 2, med_bh(2)>, grid, block, d, p);
     case 21: return med_do_launch(blur_median_fast_kernel<2, 1, med_bh(1)>, grid, block, d, p);
@@ -344,7 +344,7 @@ int launch_median_generic(const LaunchDesc &d)
     long long blocks = (p.total + 255) / 256;
     if (blocks > 256LL * 64) blocks = 256LL * 64;       // grid-stride the rest
     const dim3 grid((unsigned)blocks), block(256);
-    switch (d.median_radius) {
+    switch (d.filter->radius) {
     case 1: return med_do_launch(blur_median_generic_kernel<1>, grid, block, d, p);
     case 2: return med_do_launch(blur_median_generic_kernel<2>, grid, block, d, p);
     case 3: return med_do_launch(blur_median_generic_kernel<3>, grid, block, d, p);
@@ -360,9 +360,9 @@ int launch_median_generic(const LaunchDesc &d)
 
 int launch_median(const LaunchDesc &d)
 {
-    if (!d.in || !d.out || d.in == d.out) return MI_BLUR_ERR_INVALID;
+    if (!d.filter || d.filter->kind != FilterKind::MEDIAN || !d.in || !d.out || d.in == d.out) return MI_BLUR_ERR_INVALID;
     if (d.width <= 0 || d.band_rows <= 0 || d.channels <= 0 || d.n_images < 0) return MI_BLUR_ERR_INVALID;
-    if (d.median_radius < 1 || d.median_radius > MI_BLUR_MEDIAN_MAX_RADIUS) return MI_BLUR_ERR_INVALID;
+    if (d.filter->radius < 1 || d.filter->radius > MI_BLUR_MEDIAN_MAX_RADIUS) return MI_BLUR_ERR_INVALID;
     if (d.y0 < 0 || d.y1 > d.band_rows || d.y0 >= d.y1) return MI_BLUR_ERR_INVALID;
     if ((long long)d.width * d.channels > INT_MAX / 2) return MI_BLUR_ERR_INVALID;
     if ((long long)d.width * d.channels * d.band_rows > INT_MAX) return MI_BLUR_ERR_INVALID;  // per-image 32-bit
@@ -374,7 +374,7 @@ int launch_median(const LaunchDesc &d)
     if (d.n_images == 0) return MI_BLUR_OK;
     // the fast kernel numbers its work (images x row bands x chunk columns) in 32 bits
     const long long fast_work = (long long)d.n_images * ((d.y1 - d.y0 + 3) / 4) * (pitch / 16);
-    const bool fast = d.median_radius <= 2 && d.channels <= 4 && pitch % 16 == 0 && (uintptr_t)d.in % 16 == 0 &&
+    const bool fast = d.filter->radius <= 2 && d.channels <= 4 && pitch % 16 == 0 && (uintptr_t)d.in % 16 == 0 &&
                       (uintptr_t)d.out % 16 == 0 && d.in_stride % 16 == 0 && d.out_stride % 16 == 0 && fast_work < 0x7fffffffLL;
     return fast ? launch_median_fast(d) : launch_median_generic(d);
 }

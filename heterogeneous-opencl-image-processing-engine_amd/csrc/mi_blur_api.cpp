@@ -129,16 +129,30 @@ extern "C" int mi_blur_set_option(const char *key, int value)
 // ----------------------------------------------------------------------------------
 // kernel level   (clSetKernelArg x5 + clEnqueueNDRangeKernel)
 // ----------------------------------------------------------------------------------
+// One launch of f on device memory.  Every check of f and of the arguments that the export makes before asking for a
+// device is done by its caller; launch() checks the rest.
+static int enqueue_filter(const Filter &f, const uint8_t *d_in, uint8_t *d_out, int width, int band_rows, int channels,
+                          int n_images, int y0, int y1, int variant, void *stream, const uint8_t *halo_top = nullptr,
+                          const uint8_t *halo_bottom = nullptr)
+{
+    if (mi_blur_device_count() <= 0) return MI_BLUR_ERR_NO_DEVICE;
+    LaunchDesc d{};
+    d.filter = &f;
+    d.in = d_in; d.out = d_out; d.width = width; d.band_rows = band_rows; d.channels = channels;
+    d.n_images = n_images; d.y0 = y0; d.y1 = y1; d.variant = variant; d.stream = (hipStream_t)stream;
+    d.halo_top = halo_top; d.halo_bottom = halo_bottom;
+    return launch(d);
+}
+
+// The box radius is not checked here: launch() rejects a bad one, after the device check.
+static Filter box_unchecked(int radius) { return Filter{FilterKind::BOX, radius, {}}; }
+
 extern "C" int mi_blur_enqueue_ex(const uint8_t *d_in, uint8_t *d_out, int width, int band_rows, int channels,
                                   int radius, int n_images, int out_row_begin, int out_row_end, int variant,
                                   void *stream)
 {
-    if (mi_blur_device_count() <= 0) return MI_BLUR_ERR_NO_DEVICE;
-    LaunchDesc d{};
-    d.in = d_in; d.out = d_out; d.width = width; d.band_rows = band_rows; d.channels = channels;
-    d.radius = radius; d.n_images = n_images; d.y0 = out_row_begin; d.y1 = out_row_end;
-    d.variant = variant; d.stream = (hipStream_t)stream;
-    return launch(d);
+    return enqueue_filter(box_unchecked(radius), d_in, d_out, width, band_rows, channels, n_images, out_row_begin,
+                          out_row_end, variant, stream);
 }
 
 extern "C" int mi_blur_enqueue(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels,
@@ -160,35 +174,13 @@ extern "C" int mi_blur_enqueue_band_peer(const uint8_t *d_in, uint8_t *d_out, in
                                          int radius, int out_row_begin, int out_row_end, const uint8_t *top_src,
                                          const uint8_t *bottom_src, void *stream)
 {
-    if (mi_blur_device_count() <= 0) return MI_BLUR_ERR_NO_DEVICE;
-    if (!top_src && !bottom_src)
-        return mi_blur_enqueue_band(d_in, d_out, width, band_rows, channels, radius, out_row_begin, out_row_end, stream);
-    LaunchDesc d{};
-    d.in = d_in; d.out = d_out; d.width = width; d.band_rows = band_rows; d.channels = channels;
-    d.radius = radius; d.n_images = 1; d.y0 = out_row_begin; d.y1 = out_row_end;
-    d.variant = MI_BLUR_VARIANT_AUTO; d.stream = (hipStream_t)stream;
-    d.halo_top = top_src; d.halo_bottom = bottom_src;
-    return launch(d);
+    return enqueue_filter(box_unchecked(radius), d_in, d_out, width, band_rows, channels, 1, out_row_begin, out_row_end,
+                          MI_BLUR_VARIANT_AUTO, stream, top_src, bottom_src);
 }
 
 // ----------------------------------------------------------------------------------
 // separable kernels of any radius up to 16 (no reference analogue)
 // ----------------------------------------------------------------------------------
-// Validate a mi_blur_sep_kernel and centre its taps for the kernels (sep_taps.h).
-static int sep_prepare(const mi_blur_sep_kernel *k, SepTaps *t)
-{
-    if (!k || !t) return MI_BLUR_ERR_INVALID;
-    if (k->rx < 0 || k->rx > MI_BLUR_SEP_MAX_RADIUS || k->ry < 0 || k->ry > MI_BLUR_SEP_MAX_RADIUS) return MI_BLUR_ERR_INVALID;
-    if (k->bx < 0 || k->bx > 8 || k->by < 0 || k->by > 8) return MI_BLUR_ERR_INVALID;
-    *t = SepTaps{};
-    long long sx = 0, sy = 0;
-    for (int i = 0; i <= 2 * k->rx; i++) { sx += k->wx[i]; t->wx[SEP_MAX_R - k->rx + i] = k->wx[i]; }
-    for (int j = 0; j <= 2 * k->ry; j++) { sy += k->wy[j]; t->wy[SEP_MAX_R - k->ry + j] = k->wy[j]; }
-    if (sx != (1LL << k->bx) || sy != (1LL << k->by)) return MI_BLUR_ERR_INVALID;
-    t->rx = k->rx; t->ry = k->ry; t->shift = k->bx + k->by;
-    return MI_BLUR_OK;
-}
-
 extern "C" int mi_blur_gauss_taps(double sigma, int radius, int bits, uint16_t *taps, int *radius_out)
 {
     if (!taps || !(sigma > 0.0) || radius < 0 || radius > MI_BLUR_SEP_MAX_RADIUS || bits < 0 || bits > 8) return MI_BLUR_ERR_INVALID;
@@ -224,64 +216,40 @@ extern "C" int mi_blur_sep_kernel_gauss(double sigma_x, double sigma_y, int radi
 extern "C" int mi_blur_enqueue_sep_band(const uint8_t *d_in, uint8_t *d_out, int width, int band_rows, int channels,
                                         int out_row_begin, int out_row_end, const mi_blur_sep_kernel *k, void *stream)
 {
-    SepTaps t;
-    const int rc = sep_prepare(k, &t);
+    Filter f;
+    const int rc = filter_sep(k, &f);
     if (rc) return rc;
-    if (mi_blur_device_count() <= 0) return MI_BLUR_ERR_NO_DEVICE;
-    LaunchDesc d{};
-    d.sep = &t;
-    d.in = d_in; d.out = d_out; d.width = width; d.band_rows = band_rows; d.channels = channels;
-    d.n_images = 1; d.y0 = out_row_begin; d.y1 = out_row_end;
-    d.variant = MI_BLUR_VARIANT_AUTO; d.stream = (hipStream_t)stream;
-    return launch(d);
+    return enqueue_filter(f, d_in, d_out, width, band_rows, channels, 1, out_row_begin, out_row_end, MI_BLUR_VARIANT_AUTO, stream);
 }
 
 extern "C" int mi_blur_enqueue_sep(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int n_images,
                                    const mi_blur_sep_kernel *k, void *stream)
 {
-    SepTaps t;
-    const int rc = sep_prepare(k, &t);
+    Filter f;
+    const int rc = filter_sep(k, &f);
     if (rc) return rc;
-    if (mi_blur_device_count() <= 0) return MI_BLUR_ERR_NO_DEVICE;
-    LaunchDesc d{};
-    d.sep = &t;
-    d.in = d_in; d.out = d_out; d.width = width; d.band_rows = height; d.channels = channels;
-    d.n_images = n_images; d.y0 = 0; d.y1 = height;
-    d.variant = MI_BLUR_VARIANT_AUTO; d.stream = (hipStream_t)stream;
-    return launch(d);
+    return enqueue_filter(f, d_in, d_out, width, height, channels, n_images, 0, height, MI_BLUR_VARIANT_AUTO, stream);
 }
 
 // ----------------------------------------------------------------------------------
 // median blur, radius 1..7 (no reference analogue)
 // ----------------------------------------------------------------------------------
-static bool median_radius_ok(int r) { return r >= 1 && r <= MI_BLUR_MEDIAN_MAX_RADIUS; }
-
 extern "C" int mi_blur_enqueue_median_band(const uint8_t *d_in, uint8_t *d_out, int width, int band_rows, int channels,
                                            int radius, int out_row_begin, int out_row_end, void *stream)
 {
-    if (!median_radius_ok(radius) || !d_in || !d_out || d_in == d_out || width <= 0 || band_rows <= 0 || channels <= 0)
+    Filter f;
+    if (filter_median(radius, &f) || !d_in || !d_out || d_in == d_out || width <= 0 || band_rows <= 0 || channels <= 0)
         return MI_BLUR_ERR_INVALID;
-    if (mi_blur_device_count() <= 0) return MI_BLUR_ERR_NO_DEVICE;
-    LaunchDesc d{};
-    d.median_radius = radius;
-    d.in = d_in; d.out = d_out; d.width = width; d.band_rows = band_rows; d.channels = channels;
-    d.n_images = 1; d.y0 = out_row_begin; d.y1 = out_row_end;
-    d.variant = MI_BLUR_VARIANT_AUTO; d.stream = (hipStream_t)stream;
-    return launch(d);
+    return enqueue_filter(f, d_in, d_out, width, band_rows, channels, 1, out_row_begin, out_row_end, MI_BLUR_VARIANT_AUTO, stream);
 }
 
 extern "C" int mi_blur_enqueue_median(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int radius,
                                       int n_images, void *stream)
 {
-    if (!median_radius_ok(radius) || !d_in || !d_out || d_in == d_out || width <= 0 || height <= 0 || channels <= 0 || n_images < 0)
+    Filter f;
+    if (filter_median(radius, &f) || !d_in || !d_out || d_in == d_out || width <= 0 || height <= 0 || channels <= 0 || n_images < 0)
         return MI_BLUR_ERR_INVALID;
-    if (mi_blur_device_count() <= 0) return MI_BLUR_ERR_NO_DEVICE;
-    LaunchDesc d{};
-    d.median_radius = radius;
-    d.in = d_in; d.out = d_out; d.width = width; d.band_rows = height; d.channels = channels;
-    d.n_images = n_images; d.y0 = 0; d.y1 = height;
-    d.variant = MI_BLUR_VARIANT_AUTO; d.stream = (hipStream_t)stream;
-    return launch(d);
+    return enqueue_filter(f, d_in, d_out, width, height, channels, n_images, 0, height, MI_BLUR_VARIANT_AUTO, stream);
 }
 
 // Frame layout on the device (replaces the host loops heterogeneous_blur.c:125-134 and split_image_blur.c:40-56).
@@ -400,7 +368,8 @@ struct CpuWorker {
 }  // namespace
 
 struct mi_blur_ctx {
-    int device = 0, W = 0, H = 0, C = 0, R = 1, max_batch = 0, n_threads = 0;
+    int device = 0, W = 0, H = 0, C = 0, max_batch = 0, n_threads = 0;
+    Filter filter{};                                             // every submit applies it: mi_blur_create's radius, or set_kernel / set_median
     size_t image_bytes = 0;
     std::vector<Slot> slots;
     int next_slot = 0;
@@ -438,13 +407,7 @@ struct mi_blur_ctx {
     // CPU device
     std::vector<CpuJob *> cpu_jobs;
     CpuWorker *cpu_worker = nullptr;
-    // separable kernel (mi_blur_ctx_set_kernel): replaces R in every submit
-    bool has_sep = false;
-    SepTaps sep{};
-    bool submitted = false;                                      // set_kernel only before this
-    const SepTaps *sep_or_null() const { return has_sep ? &sep : nullptr; }
-    // median (mi_blur_ctx_set_median): 1..7 replaces R in every submit; 0 = none.  One filter at a time: has_sep is false then.
-    int median_r = 0;
+    bool submitted = false;                                      // set_kernel / set_median only before this
     bool is_cpu() const { return device == MI_BLUR_DEVICE_CPU; }
 };
 
@@ -613,11 +576,12 @@ extern "C" int mi_blur_create(mi_blur_ctx **out_ctx, int device, int width, int 
     if (!out_ctx) return MI_BLUR_ERR_INVALID;
     *out_ctx = nullptr;
     if (width <= 0 || height <= 0 || channels <= 0 || max_batch <= 0 || n_slots <= 0) return MI_BLUR_ERR_INVALID;
-    if (radius != 1 && radius != 2) return MI_BLUR_ERR_INVALID;
+    Filter box;
+    if (filter_box(radius, &box)) return MI_BLUR_ERR_INVALID;
     if ((long long)width * channels * height > 0x7fffffffLL) return MI_BLUR_ERR_INVALID;
     mi_blur_ctx *c = new (std::nothrow) mi_blur_ctx;
     if (!c) return MI_BLUR_ERR_NOMEM;
-    c->device = device; c->W = width; c->H = height; c->C = channels; c->R = radius;
+    c->device = device; c->W = width; c->H = height; c->C = channels; c->filter = box;
     c->max_batch = max_batch;
     // 0 = automatic: all cores up to 16.  Waking hundreds of workers for a ~1 ms batch costs more than it returns
     // (256-thread host, 256x256x3, batch 35: 8.5 k img/s with 256 workers, 235 k with 16, 190 k with 32); ask explicitly for more.
@@ -834,7 +798,7 @@ extern "C" void mi_blur_destroy(mi_blur_ctx *c)
 // than the running server's): the caller launches the batch the classic way.
 static int zc_server_submit(mi_blur_ctx *c, Slot &s, const LaunchDesc &d, const Tunables &tun)
 {
-    if (c->has_sep || c->median_r) return MI_BLUR_ERR_UNSUPPORTED;   // the server's tiles are the radius-1|2 kernel's: one launch per batch
+    if (c->filter.kind != FilterKind::BOX) return MI_BLUR_ERR_UNSUPPORTED;   // the server's tiles are the radius-1|2 kernel's: one launch per batch
     if (c->slots.size() > ZC_RING) return MI_BLUR_ERR_UNSUPPORTED;
     if (!c->zc) {
         ZcServer *z = new (std::nothrow) ZcServer;
@@ -907,6 +871,154 @@ static int zc_server_submit(mi_blur_ctx *c, Slot &s, const LaunchDesc &d, const 
     return MI_BLUR_OK;
 }
 
+// The launch of the context's filter over n_images bands of band_rows rows (output rows [y0, y1) of each): dense strides,
+// AUTO variant, no stream and no events yet.  Every launch a context makes starts here.
+static LaunchDesc ctx_launch(const mi_blur_ctx *c, const uint8_t *in, uint8_t *out, int band_rows, int n_images, int y0, int y1)
+{
+    LaunchDesc d{};
+    d.filter = &c->filter;
+    d.in = in; d.out = out; d.width = c->W; d.band_rows = band_rows; d.channels = c->C;
+    d.n_images = n_images; d.y0 = y0; d.y1 = y1; d.variant = MI_BLUR_VARIANT_AUTO;
+    return d;
+}
+
+// What one submit adds to the context's counters.  h2d / d2h: the bytes that cross the host link (none on the CPU device).
+static void count_submit(mi_blur_ctx *c, int n_images, size_t out_bytes, size_t h2d, size_t d2h, bool zero_copy)
+{
+    c->tm.bytes_h2d += h2d; c->tm.bytes_d2h += d2h;
+    c->tm.bytes_alg += 2ull * out_bytes;
+    c->tm.images += (uint64_t)n_images;
+    c->tm.launches += 1;
+    if (zero_copy) c->zero_copy_launches += 1;
+}
+
+// A submit on the CPU device: `work` runs on the context's worker thread, after the submits before it.
+static int cpu_enqueue(mi_blur_ctx *c, std::function<void()> work)
+{
+    CpuJob *j = new (std::nothrow) CpuJob;
+    if (!j) return MI_BLUR_ERR_NOMEM;
+    if (!c->cpu_worker) { c->cpu_worker = new (std::nothrow) CpuWorker; if (!c->cpu_worker) { delete j; return MI_BLUR_ERR_NOMEM; } }
+    j->work = std::move(work);
+    c->cpu_worker->push(j);
+    c->cpu_jobs.push_back(j);
+    return MI_BLUR_OK;
+}
+
+namespace {
+// One submit of caller memory: n_images bands of band_rows rows, in_stride bytes apart from `in`; output rows [y0, y1) of
+// each, out_stride bytes apart from `out`.  band_in / band_out: the bytes of one band / one output block.
+struct HostBatch {
+    const uint8_t *in;
+    uint8_t *out;
+    int band_rows, n_images, y0, y1;
+    size_t band_in, band_out, in_stride, out_stride;
+    size_t in_bytes() const { return band_in * (size_t)n_images; }
+    size_t out_bytes() const { return band_out * (size_t)n_images; }
+};
+}  // namespace
+
+// Hand the batch of d (pinned memory the kernel works on in place) to the batch server.  MI_BLUR_ERR_UNSUPPORTED: not
+// taken, the caller launches it another way.
+static int submit_to_server(mi_blur_ctx *c, Slot &s, const HostBatch &b, const LaunchDesc &d, const Tunables &tun)
+{
+    const int rc = zc_server_submit(c, s, d, tun);
+    if (rc == MI_BLUR_ERR_UNSUPPORTED) s.zc_server = false;
+    if (rc) return rc;
+    s.zero_copy = true; s.busy = true;
+    count_submit(c, b.n_images, b.out_bytes(), b.in_bytes(), b.out_bytes(), true);
+    return MI_BLUR_OK;
+}
+
+// Both caller buffers pinned (zin / zout: their device addresses): the kernel reads and writes them in place over PCIe.
+// On this platform one kernel moving both directions sustains ~70 GB/s (35 each way) while the copy engines give ~55 GB/s
+// one way at a time and collapse to ~28 GB/s total when H2D and D2H overlap (profiles/r01_zero_copy.txt): +33-40 %
+// images/s end to end.  Each zero-copy launch keeps only "zero_copy_blocks" workgroups resident (they loop over the
+// tiles) and consecutive launches alternate over up to "zero_copy_streams" of the context's streams, so that reads
+// of one tile and writes of another keep both directions of the link busy (profiles/r02_e2e.txt).
+static int submit_in_place(mi_blur_ctx *c, Slot &s, const HostBatch &b, const uint8_t *zin, uint8_t *zout, const Tunables &tun)
+{
+    s.out_staged = false; s.user_out = b.out; s.out_bytes = b.out_bytes(); s.out_band = b.band_out; s.out_stride = b.out_stride;
+    s.out_n = b.n_images;
+    // consecutive zero-copy launches alternate over the first zn streams of the context
+    const int zn = std::max(1, std::min(tun.zero_copy_streams, (int)c->slots.size()));
+    const hipStream_t zs = c->slots[(c->zero_copy_launches % (uint64_t)zn)].stream;
+    // one dispatch packet, nothing else: the kernel's own stop event doubles as the completion event (every
+    // extra hipEventRecord is a barrier packet between two kernels)
+    LaunchDesc d = ctx_launch(c, zin, zout, b.band_rows, b.n_images, b.y0, b.y1);
+    d.in_stride = (long long)b.in_stride; d.out_stride = (long long)b.out_stride;
+    // small batches stay with one launch each: the server's hand-off (descriptor over the link, poller, completion
+    // word, the host's wait) costs ~26 us per batch against ~8 us for a launch — below ~1.3 MB each way the launch
+    // wins, by up to 3x for a single 256x256 frame (profiles/r03_e2e_shape_sweep.txt)
+    if (tun.zero_copy_server && b.out_bytes() >= (size_t)tun.zero_copy_server_min_kb * 1024u) {
+        const int rc = submit_to_server(c, s, b, d, tun);
+        if (rc != MI_BLUR_ERR_UNSUPPORTED) return rc;
+    }
+    const bool with_events = tun.zero_copy_events != 0;
+    d.stream = zs;
+    if (with_events) { d.start = s.ks; d.stop = s.ke; }
+    s.zc_plain = !with_events; s.zc_stream = zs;
+    d.max_blocks = tun.zero_copy_blocks;
+    // once per sync window, in front of its first launch (and again every ~10 s of a window that never syncs,
+    // so the float milliseconds since the reference keep their resolution)
+    if (with_events && (!c->zc_ref_valid || c->zc_covered_ms > 10e3)) {
+        if (!c->zc_ref) HIP_TRY(hipEventCreate(&c->zc_ref));
+        HIP_TRY(hipEventRecord(c->zc_ref, zs));
+        c->zc_ref_valid = true; c->zc_covered_ms = 0.0;
+    }
+    const int rc = launch(d);
+    if (rc) return rc;
+    s.zero_copy = true;                            // only now: a failed launch leaves the slot idle and staged
+    s.busy = true;
+    count_submit(c, b.n_images, b.out_bytes(), b.in_bytes(), b.out_bytes(), true);
+    return MI_BLUR_OK;
+}
+
+// Pageable caller memory (the reference's malloc'd batch buffers, kept as they are): the staging buffers ARE pinned, so
+// the batch server takes the batch from them in place — staging in -> blur -> staging out as one kernel stream over the
+// link — instead of a DMA copy each way around a launch (copies in both directions at once collapse to ~28 GB/s in
+// total on this platform, profiles/r01_pcie_probe.txt).  What stays is the host's own gather / scatter between the
+// caller's memory and the staging.  src / src_stride: where the batch's input now is.  MI_BLUR_ERR_UNSUPPORTED: not taken.
+// (any batch size: for small batches too the server on the staging beats two DMA copies around a launch — a single
+// 256x256 frame per submit: 78 k against 36 k img/s)
+static int submit_staged_server(mi_blur_ctx *c, Slot &s, const HostBatch &b, const uint8_t *src, size_t src_stride,
+                                const Tunables &tun)
+{
+    const uint8_t *zin = pinned_device_ptr(src);
+    uint8_t *zout = pinned_device_ptr(s.out_staged ? s.h_out : b.out);
+    if (!zin || !zout) return MI_BLUR_ERR_UNSUPPORTED;
+    LaunchDesc d = ctx_launch(c, zin, zout, b.band_rows, b.n_images, b.y0, b.y1);
+    d.in_stride = (long long)src_stride; d.out_stride = (long long)(s.out_staged ? b.band_out : b.out_stride);
+    return submit_to_server(c, s, b, d, tun);
+}
+
+// DMA copy in, launch on the slot's device buffers, DMA copy out, all on the slot's stream.  A strided batch (src_stride
+// or out_stride not dense) takes a 2-D copy that gathers / scatters the bands.
+static int submit_dma(mi_blur_ctx *c, Slot &s, const HostBatch &b, const uint8_t *src, size_t src_stride)
+{
+    int rc = slot_device(c, s);
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(s.ev[0], s.stream));
+    if (src_stride == b.band_in)
+        HIP_TRY(hipMemcpyAsync(s.d_in, src, b.in_bytes(), hipMemcpyHostToDevice, s.stream));
+    else
+        HIP_TRY(hipMemcpy2DAsync(s.d_in, b.band_in, src, src_stride, b.band_in, (size_t)b.n_images, hipMemcpyHostToDevice, s.stream));
+    HIP_TRY(hipEventRecord(s.ev[1], s.stream));
+    LaunchDesc d = ctx_launch(c, s.d_in, s.d_out, b.band_rows, b.n_images, b.y0, b.y1);
+    d.stream = s.stream; d.start = s.ks; d.stop = s.ke;
+    d.concurrent = (int)c->slots.size();
+    rc = launch(d);
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(s.ev[2], s.stream));
+    if (s.out_staged || b.out_stride == b.band_out)
+        HIP_TRY(hipMemcpyAsync(s.out_staged ? s.h_out : b.out, s.d_out, b.out_bytes(), hipMemcpyDeviceToHost, s.stream));
+    else
+        HIP_TRY(hipMemcpy2DAsync(b.out, b.out_stride, s.d_out, b.band_out, b.band_out, (size_t)b.n_images, hipMemcpyDeviceToHost, s.stream));
+    HIP_TRY(hipEventRecord(s.ev[3], s.stream));
+    s.busy = true;
+    count_submit(c, b.n_images, b.out_bytes(), b.in_bytes(), b.out_bytes(), false);
+    return MI_BLUR_OK;
+}
+
 // One batch through a slot: Write -> NDRange -> Read (heterogeneous_blur.c:520-533), but one
 // launch (and one DMA each way) for the whole batch instead of one triple per image.
 // in_stride/out_stride: bytes between consecutive images' first band row / first output row in
@@ -917,167 +1029,48 @@ static int submit_common(mi_blur_ctx *c, const uint8_t *host_in, uint8_t *host_o
 {
     const size_t pitch = (size_t)c->W * c->C;
     const size_t band_in = pitch * band_rows, band_out = pitch * (size_t)(y1 - y0);
-    const size_t in_bytes = band_in * n_images, out_bytes = band_out * n_images;
-    if (in_stride == 0) in_stride = band_in;
-    if (out_stride == 0) out_stride = band_out;
+    const HostBatch b{host_in, host_out, band_rows, n_images, y0, y1, band_in, band_out,
+                      in_stride ? in_stride : band_in, out_stride ? out_stride : band_out};
     c->submitted = true;
     if (c->is_cpu()) {
-        CpuJob *j = new (std::nothrow) CpuJob;
-        if (!j) return MI_BLUR_ERR_NOMEM;
-        const int W = c->W, C = c->C, R = c->R, nt = c->n_threads;
-        const bool has_sep = c->has_sep;
-        const SepTaps sep = c->sep;
-        const int median_r = c->median_r;
-        j->work = [=]() { cpu_blur_batch(host_in, host_out, W, band_rows, C, R, n_images, y0, y1, nt, in_stride, out_stride, has_sep ? &sep : nullptr, median_r); };
-        if (!c->cpu_worker) { c->cpu_worker = new (std::nothrow) CpuWorker; if (!c->cpu_worker) { delete j; return MI_BLUR_ERR_NOMEM; } }
-        c->cpu_worker->push(j);
-        c->cpu_jobs.push_back(j);
-    } else {
-        HIP_TRY(hipSetDevice(c->device));
-        Slot &s = c->slots[c->next_slot];
-        c->next_slot = (c->next_slot + 1) % (int)c->slots.size();
-        int rc = finish_slot(c, s);
+        const int W = c->W, C = c->C, nt = c->n_threads;
+        const int rc = cpu_enqueue(c, [=, f = c->filter]() {
+            cpu_blur_batch(b.in, b.out, W, band_rows, C, f, n_images, y0, y1, nt, b.in_stride, b.out_stride);
+        });
         if (rc) return rc;
-        // Zero-copy: when both caller buffers are pinned the kernel reads and writes them in place over PCIe.  On this
-        // platform one kernel moving both directions sustains ~70 GB/s (35 each way) while the copy engines give ~55 GB/s
-        // one way at a time and collapse to ~28 GB/s total when H2D and D2H overlap (profiles/r01_zero_copy.txt): +33-40 %
-        // images/s end to end.  Each zero-copy launch keeps only "zero_copy_blocks" workgroups resident (they loop over the
-        // tiles) and consecutive launches alternate over up to "zero_copy_streams" of the context's streams, so that reads
-        // of one tile and writes of another keep both directions of the link busy (profiles/r02_e2e.txt).
-        const Tunables tun = tunables();    // ONE copy of the knobs for this submit
-        if (tun.zero_copy) {
-            const uint8_t *zin = pinned_device_ptr(host_in);
-            uint8_t *zout = pinned_device_ptr(host_out);
-            const bool dense = in_stride == band_in && out_stride == band_out;
-            if (zin && zout && (dense || (tiled_eligible(zin, zout, c->W, c->C) && in_stride % 16 == 0 && out_stride % 16 == 0))) {
-                s.out_staged = false; s.user_out = host_out; s.out_bytes = out_bytes; s.out_band = band_out; s.out_stride = out_stride;
-                s.out_n = n_images;
-                // consecutive zero-copy launches alternate over the first zn streams of the context
-                const int zn = std::max(1, std::min(tun.zero_copy_streams, (int)c->slots.size()));
-                const hipStream_t zs = c->slots[(c->zero_copy_launches % (uint64_t)zn)].stream;
-                // one dispatch packet, nothing else: the kernel's own stop event doubles as the completion event (every
-                // extra hipEventRecord is a barrier packet between two kernels)
-                LaunchDesc d{};
-                d.in = zin; d.out = zout; d.width = c->W; d.band_rows = band_rows; d.channels = c->C;
-                d.radius = c->R; d.n_images = n_images; d.y0 = y0; d.y1 = y1; d.variant = MI_BLUR_VARIANT_AUTO;
-                d.sep = c->sep_or_null();
-                d.median_radius = c->median_r;
-                d.in_stride = (long long)in_stride; d.out_stride = (long long)out_stride;
-                // small batches stay with one launch each: the server's hand-off (descriptor over the link, poller, completion
-                // word, the host's wait) costs ~26 us per batch against ~8 us for a launch — below ~1.3 MB each way the launch
-                // wins, by up to 3x for a single 256x256 frame (profiles/r03_e2e_shape_sweep.txt)
-                if (tun.zero_copy_server && out_bytes >= (size_t)tun.zero_copy_server_min_kb * 1024u) {
-                    rc = zc_server_submit(c, s, d, tun);
-                    if (rc == MI_BLUR_OK) {
-                        s.zero_copy = true; s.busy = true;
-                        c->tm.bytes_h2d += in_bytes; c->tm.bytes_d2h += out_bytes;
-                        c->tm.bytes_alg += 2ull * out_bytes;
-                        c->tm.images += (uint64_t)n_images;
-                        c->tm.launches += 1;
-                        c->zero_copy_launches += 1;
-                        return MI_BLUR_OK;
-                    }
-                    if (rc != MI_BLUR_ERR_UNSUPPORTED) return rc;
-                    s.zc_server = false;
-                }
-                const bool with_events = tun.zero_copy_events != 0;
-                d.stream = zs;
-                if (with_events) { d.start = s.ks; d.stop = s.ke; }
-                s.zc_plain = !with_events; s.zc_stream = zs;
-                d.max_blocks = tun.zero_copy_blocks;
-                // once per sync window, in front of its first launch (and again every ~10 s of a window that never syncs,
-                // so the float milliseconds since the reference keep their resolution)
-                if (with_events && (!c->zc_ref_valid || c->zc_covered_ms > 10e3)) {
-                    if (!c->zc_ref) HIP_TRY(hipEventCreate(&c->zc_ref));
-                    HIP_TRY(hipEventRecord(c->zc_ref, zs));
-                    c->zc_ref_valid = true; c->zc_covered_ms = 0.0;
-                }
-                rc = launch(d);
-                if (rc) return rc;
-                s.zero_copy = true;                            // only now: a failed launch leaves the slot idle and staged
-                s.busy = true;
-                c->tm.bytes_h2d += in_bytes; c->tm.bytes_d2h += out_bytes;
-                c->tm.bytes_alg += 2ull * out_bytes;
-                c->tm.images += (uint64_t)n_images;
-                c->tm.launches += 1;
-                c->zero_copy_launches += 1;
-                return MI_BLUR_OK;
-            }
-        }
-        const bool in_pinned = is_pinned(host_in);
-        s.zero_copy = false;
-        s.out_staged = !is_pinned(host_out);
-        s.user_out = host_out; s.out_bytes = out_bytes; s.out_band = band_out; s.out_stride = out_stride; s.out_n = n_images;
-        const uint8_t *src = host_in;
-        size_t src_stride = in_stride;
-        rc = slot_staging(c, s, !in_pinned, s.out_staged);
-        if (rc) return rc;
-        if (!in_pinned) {                       // pageable caller memory: gather into the slot's pinned staging
-            copy_blocks(s.h_in, band_in, host_in, in_stride, band_in, n_images, STAGING_COPY_THREADS);
-            src = s.h_in; src_stride = band_in;
-        }
-        // Pageable caller memory (the reference's malloc'd batch buffers, kept as they are): the staging buffers ARE pinned, so
-        // the batch server takes the batch from them in place — staging in -> blur -> staging out as one kernel stream over the
-        // link — instead of a DMA copy each way around a launch (copies in both directions at once collapse to ~28 GB/s in
-        // total on this platform, profiles/r01_pcie_probe.txt).  What stays is the host's own gather / scatter between the
-        // caller's memory and the staging.
-        // (any batch size: for small batches too the server on the staging beats two DMA copies around a launch — a single
-        // 256x256 frame per submit: 78 k against 36 k img/s)
-        if (tun.zero_copy && tun.zero_copy_server && tun.staged_server) {
-            const uint8_t *zin = pinned_device_ptr(src);
-            uint8_t *zout = pinned_device_ptr(s.out_staged ? s.h_out : host_out);
-            const size_t zout_stride = s.out_staged ? band_out : out_stride;
-            if (zin && zout) {
-                LaunchDesc d{};
-                d.in = zin; d.out = zout; d.width = c->W; d.band_rows = band_rows; d.channels = c->C;
-                d.radius = c->R; d.n_images = n_images; d.y0 = y0; d.y1 = y1; d.variant = MI_BLUR_VARIANT_AUTO;
-                d.sep = c->sep_or_null();
-                d.median_radius = c->median_r;
-                d.in_stride = (long long)src_stride; d.out_stride = (long long)zout_stride;
-                rc = zc_server_submit(c, s, d, tun);
-                if (rc == MI_BLUR_OK) {
-                    s.zero_copy = true; s.busy = true;
-                    c->tm.bytes_h2d += in_bytes; c->tm.bytes_d2h += out_bytes;
-                    c->tm.bytes_alg += 2ull * out_bytes;
-                    c->tm.images += (uint64_t)n_images;
-                    c->tm.launches += 1;
-                    c->zero_copy_launches += 1;
-                    return MI_BLUR_OK;
-                }
-                if (rc != MI_BLUR_ERR_UNSUPPORTED) return rc;
-                s.zc_server = false;
-            }
-        }
-        rc = slot_device(c, s);
-        if (rc) return rc;
-        HIP_TRY(hipEventRecord(s.ev[0], s.stream));
-        if (src_stride == band_in)
-            HIP_TRY(hipMemcpyAsync(s.d_in, src, in_bytes, hipMemcpyHostToDevice, s.stream));
-        else
-            HIP_TRY(hipMemcpy2DAsync(s.d_in, band_in, src, src_stride, band_in, (size_t)n_images, hipMemcpyHostToDevice, s.stream));
-        HIP_TRY(hipEventRecord(s.ev[1], s.stream));
-        LaunchDesc d{};
-        d.in = s.d_in; d.out = s.d_out; d.width = c->W; d.band_rows = band_rows; d.channels = c->C;
-        d.radius = c->R; d.n_images = n_images; d.y0 = y0; d.y1 = y1; d.variant = MI_BLUR_VARIANT_AUTO;
-        d.sep = c->sep_or_null();
-        d.median_radius = c->median_r;
-        d.stream = s.stream; d.start = s.ks; d.stop = s.ke;
-        d.concurrent = (int)c->slots.size();
-        rc = launch(d);
-        if (rc) return rc;
-        HIP_TRY(hipEventRecord(s.ev[2], s.stream));
-        if (s.out_staged || out_stride == band_out)
-            HIP_TRY(hipMemcpyAsync(s.out_staged ? s.h_out : host_out, s.d_out, out_bytes, hipMemcpyDeviceToHost, s.stream));
-        else
-            HIP_TRY(hipMemcpy2DAsync(host_out, out_stride, s.d_out, band_out, band_out, (size_t)n_images, hipMemcpyDeviceToHost, s.stream));
-        HIP_TRY(hipEventRecord(s.ev[3], s.stream));
-        s.busy = true;
-        c->tm.bytes_h2d += in_bytes; c->tm.bytes_d2h += out_bytes;
+        count_submit(c, n_images, b.out_bytes(), 0, 0, false);
+        return MI_BLUR_OK;
     }
-    c->tm.bytes_alg += 2ull * out_bytes;
-    c->tm.images += (uint64_t)n_images;
-    c->tm.launches += 1;
-    return MI_BLUR_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    Slot &s = c->slots[c->next_slot];
+    c->next_slot = (c->next_slot + 1) % (int)c->slots.size();
+    int rc = finish_slot(c, s);
+    if (rc) return rc;
+    const Tunables tun = tunables();    // ONE copy of the knobs for this submit
+    if (tun.zero_copy) {
+        const uint8_t *zin = pinned_device_ptr(host_in);
+        uint8_t *zout = pinned_device_ptr(host_out);
+        const bool dense = b.in_stride == band_in && b.out_stride == band_out;
+        if (zin && zout && (dense || (tiled_eligible(zin, zout, c->W, c->C) && b.in_stride % 16 == 0 && b.out_stride % 16 == 0)))
+            return submit_in_place(c, s, b, zin, zout, tun);
+    }
+    const bool in_pinned = is_pinned(host_in);
+    s.zero_copy = false;
+    s.out_staged = !is_pinned(host_out);
+    s.user_out = host_out; s.out_bytes = b.out_bytes(); s.out_band = band_out; s.out_stride = b.out_stride; s.out_n = n_images;
+    const uint8_t *src = host_in;
+    size_t src_stride = b.in_stride;
+    rc = slot_staging(c, s, !in_pinned, s.out_staged);
+    if (rc) return rc;
+    if (!in_pinned) {                       // pageable caller memory: gather into the slot's pinned staging
+        copy_blocks(s.h_in, band_in, host_in, b.in_stride, band_in, n_images, STAGING_COPY_THREADS);
+        src = s.h_in; src_stride = band_in;
+    }
+    if (tun.zero_copy && tun.zero_copy_server && tun.staged_server) {
+        rc = submit_staged_server(c, s, b, src, src_stride, tun);
+        if (rc != MI_BLUR_ERR_UNSUPPORTED) return rc;
+    }
+    return submit_dma(c, s, b, src, src_stride);
 }
 
 extern "C" int mi_blur_submit(mi_blur_ctx *c, const uint8_t *host_in, uint8_t *host_out, int n_images)
@@ -1125,70 +1118,62 @@ extern "C" int mi_blur_submit_planar(mi_blur_ctx *c, const uint8_t *host_planar_
     const size_t bytes = c->image_bytes * (size_t)n_images;
     c->submitted = true;
     if (c->is_cpu()) {
-        CpuJob *j = new (std::nothrow) CpuJob;
-        if (!j) return MI_BLUR_ERR_NOMEM;
-        const int W = c->W, H = c->H, C = c->C, R = c->R, nt = c->n_threads;
-        const bool has_sep = c->has_sep;
-        const SepTaps sep = c->sep;
-        const int median_r = c->median_r;
-        j->work = [=]() {
-            std::vector<uint8_t> a(bytes), b(planar_out ? bytes : 0);
-            cpu_repack(host_planar_in, a.data(), W, H, C, n_images, true, nt);
-            cpu_blur_batch(a.data(), planar_out ? b.data() : host_out, W, H, C, R, n_images, 0, H, nt, 0, 0, has_sep ? &sep : nullptr, median_r);
-            if (planar_out) cpu_repack(b.data(), host_out, W, H, C, n_images, false, nt);
-        };
-        if (!c->cpu_worker) { c->cpu_worker = new (std::nothrow) CpuWorker; if (!c->cpu_worker) { delete j; return MI_BLUR_ERR_NOMEM; } }
-        c->cpu_worker->push(j);
-        c->cpu_jobs.push_back(j);
-    } else {
-        HIP_TRY(hipSetDevice(c->device));
-        Slot &s = c->slots[c->next_slot];
-        c->next_slot = (c->next_slot + 1) % (int)c->slots.size();
-        int rc = finish_slot(c, s);
-        if (rc) return rc;
-        s.zero_copy = false;
-        // source the repack-in kernel can read: the caller's frames if they are pinned, the slot's pinned staging otherwise
-        const uint8_t *src = pinned_device_ptr(host_planar_in);
-        rc = slot_device(c, s);
-        if (!rc) rc = slot_staging(c, s, !src, !pinned_device_ptr(host_out));
-        if (rc) return rc;
-        if (!src) {
-            copy_blocks(s.h_in, bytes, host_planar_in, bytes, bytes, 1, STAGING_COPY_THREADS);
-            src = pinned_device_ptr(s.h_in);
-            if (!src) return MI_BLUR_ERR_STATE;
-        }
-        uint8_t *dst_pinned = pinned_device_ptr(host_out);
-        s.out_staged = !dst_pinned;
-        s.user_out = host_out; s.out_bytes = bytes; s.out_band = bytes; s.out_stride = bytes; s.out_n = 1;
-        HIP_TRY(hipEventRecord(s.ev[0], s.stream));
-        rc = launch_planar_to_interleaved(src, s.d_in, c->W, c->H, c->C, n_images, s.stream);
-        if (rc) return rc;
-        HIP_TRY(hipEventRecord(s.ev[1], s.stream));
-        LaunchDesc d{};
-        d.in = s.d_in; d.out = s.d_out; d.width = c->W; d.band_rows = c->H; d.channels = c->C;
-        d.radius = c->R; d.n_images = n_images; d.y0 = 0; d.y1 = c->H; d.variant = MI_BLUR_VARIANT_AUTO;
-        d.sep = c->sep_or_null();
-        d.median_radius = c->median_r;
-        d.stream = s.stream; d.start = s.ks; d.stop = s.ke;
-        d.concurrent = (int)c->slots.size();
-        rc = launch(d);
-        if (rc) return rc;
-        HIP_TRY(hipEventRecord(s.ev[2], s.stream));
-        if (planar_out) {
-            uint8_t *dst = dst_pinned ? dst_pinned : pinned_device_ptr(s.h_out);
-            if (!dst) return MI_BLUR_ERR_STATE;
-            rc = launch_interleaved_to_planar(s.d_out, dst, c->W, c->H, c->C, n_images, s.stream);
-            if (rc) return rc;
-        } else {
-            HIP_TRY(hipMemcpyAsync(s.out_staged ? s.h_out : host_out, s.d_out, bytes, hipMemcpyDeviceToHost, s.stream));
-        }
-        HIP_TRY(hipEventRecord(s.ev[3], s.stream));
-        s.busy = true;
-        c->tm.bytes_h2d += bytes; c->tm.bytes_d2h += bytes;
+        // the scratch frames are allocated here, not in the job, so that running out of memory is a status
+        uint8_t *a = new (std::nothrow) uint8_t[bytes], *b = planar_out ? new (std::nothrow) uint8_t[bytes] : nullptr;
+        const int W = c->W, H = c->H, C = c->C, nt = c->n_threads;
+        int rc = !a || (planar_out && !b) ? MI_BLUR_ERR_NOMEM : MI_BLUR_OK;
+        if (!rc)
+            rc = cpu_enqueue(c, [=, f = c->filter]() {
+                cpu_repack(host_planar_in, a, W, H, C, n_images, true, nt);
+                cpu_blur_batch(a, planar_out ? b : host_out, W, H, C, f, n_images, 0, H, nt);
+                if (planar_out) cpu_repack(b, host_out, W, H, C, n_images, false, nt);
+                delete[] a;
+                delete[] b;
+            });
+        if (rc) { delete[] a; delete[] b; return rc; }
+        count_submit(c, n_images, bytes, 0, 0, false);
+        return MI_BLUR_OK;
     }
-    c->tm.bytes_alg += 2ull * bytes;
-    c->tm.images += (uint64_t)n_images;
-    c->tm.launches += 1;
+    HIP_TRY(hipSetDevice(c->device));
+    Slot &s = c->slots[c->next_slot];
+    c->next_slot = (c->next_slot + 1) % (int)c->slots.size();
+    int rc = finish_slot(c, s);
+    if (rc) return rc;
+    s.zero_copy = false;
+    // source the repack-in kernel can read: the caller's frames if they are pinned, the slot's pinned staging otherwise
+    const uint8_t *src = pinned_device_ptr(host_planar_in);
+    rc = slot_device(c, s);
+    if (!rc) rc = slot_staging(c, s, !src, !pinned_device_ptr(host_out));
+    if (rc) return rc;
+    if (!src) {
+        copy_blocks(s.h_in, bytes, host_planar_in, bytes, bytes, 1, STAGING_COPY_THREADS);
+        src = pinned_device_ptr(s.h_in);
+        if (!src) return MI_BLUR_ERR_STATE;
+    }
+    uint8_t *dst_pinned = pinned_device_ptr(host_out);
+    s.out_staged = !dst_pinned;
+    s.user_out = host_out; s.out_bytes = bytes; s.out_band = bytes; s.out_stride = bytes; s.out_n = 1;
+    HIP_TRY(hipEventRecord(s.ev[0], s.stream));
+    rc = launch_planar_to_interleaved(src, s.d_in, c->W, c->H, c->C, n_images, s.stream);
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(s.ev[1], s.stream));
+    LaunchDesc d = ctx_launch(c, s.d_in, s.d_out, c->H, n_images, 0, c->H);
+    d.stream = s.stream; d.start = s.ks; d.stop = s.ke;
+    d.concurrent = (int)c->slots.size();
+    rc = launch(d);
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(s.ev[2], s.stream));
+    if (planar_out) {
+        uint8_t *dst = dst_pinned ? dst_pinned : pinned_device_ptr(s.h_out);
+        if (!dst) return MI_BLUR_ERR_STATE;
+        rc = launch_interleaved_to_planar(s.d_out, dst, c->W, c->H, c->C, n_images, s.stream);
+        if (rc) return rc;
+    } else {
+        HIP_TRY(hipMemcpyAsync(s.out_staged ? s.h_out : host_out, s.d_out, bytes, hipMemcpyDeviceToHost, s.stream));
+    }
+    HIP_TRY(hipEventRecord(s.ev[3], s.stream));
+    s.busy = true;
+    count_submit(c, n_images, bytes, bytes, bytes, false);
     return MI_BLUR_OK;
 }
 
@@ -1197,12 +1182,10 @@ extern "C" int mi_blur_ctx_set_kernel(mi_blur_ctx *c, const mi_blur_sep_kernel *
 {
     if (!c || !k) return MI_BLUR_ERR_INVALID;
     if (c->submitted) return MI_BLUR_ERR_STATE;
-    SepTaps t;
-    const int rc = sep_prepare(k, &t);
+    Filter f;
+    const int rc = filter_sep(k, &f);
     if (rc) return rc;
-    c->sep = t;
-    c->has_sep = true;
-    c->median_r = 0;
+    c->filter = f;
     return MI_BLUR_OK;
 }
 
@@ -1211,9 +1194,9 @@ extern "C" int mi_blur_ctx_set_median(mi_blur_ctx *c, int radius)
 {
     if (!c) return MI_BLUR_ERR_INVALID;
     if (c->submitted) return MI_BLUR_ERR_STATE;
-    if (!median_radius_ok(radius)) return MI_BLUR_ERR_INVALID;
-    c->median_r = radius;
-    c->has_sep = false;
+    Filter f;
+    if (filter_median(radius, &f)) return MI_BLUR_ERR_INVALID;
+    c->filter = f;
     return MI_BLUR_OK;
 }
 
@@ -1273,9 +1256,8 @@ static int place_pool(mi_blur_ctx *c, size_t bytes, int pool_images, int trials)
         std::vector<float> best((size_t)n_ok * n_ok, 1e30f);
         if (hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) {
             auto pass = [&](int i, int j) {
-                LaunchDesc d{};
-                d.in = in[i]; d.out = out[j]; d.width = c->W; d.band_rows = c->H; d.channels = c->C; d.radius = c->R;
-                d.n_images = pool_images; d.y0 = 0; d.y1 = c->H; d.variant = MI_BLUR_VARIANT_AUTO; d.stream = st;
+                LaunchDesc d = ctx_launch(c, in[i], out[j], c->H, pool_images, 0, c->H);
+                d.stream = st;
                 return launch(d);
             };
             int rc = MI_BLUR_OK;
@@ -1392,7 +1374,7 @@ extern "C" void *mi_blur_resident_out(mi_blur_ctx *c) { return c ? c->pool_out :
 extern "C" int mi_blur_resident_run(mi_blur_ctx *c, int n_images, int batch, int timed_every)
 {
     if (!c || n_images < 0 || batch <= 0) return MI_BLUR_ERR_INVALID;
-    if (c->has_sep || c->median_r) return MI_BLUR_ERR_UNSUPPORTED;
+    if (c->filter.kind != FilterKind::BOX) return MI_BLUR_ERR_UNSUPPORTED;
     if (c->is_cpu() || !c->pool_in) return MI_BLUR_ERR_STATE;
     if (batch > c->pool_images) return MI_BLUR_ERR_INVALID;
     HIP_TRY(hipSetDevice(c->device));
@@ -1403,11 +1385,9 @@ extern "C" int mi_blur_resident_run(mi_blur_ctx *c, int n_images, int batch, int
         if (c->cursor + b > c->pool_images) c->cursor = 0;
         Slot &s = c->slots[c->rr];
         c->rr = (c->rr + 1) % (int)c->slots.size();
-        LaunchDesc d{};
-        d.in = c->pool_in + (size_t)c->cursor * c->image_bytes;
-        d.out = c->pool_out + (size_t)c->cursor * c->image_bytes;
-        d.width = c->W; d.band_rows = c->H; d.channels = c->C; d.radius = c->R; d.n_images = b;
-        d.y0 = 0; d.y1 = c->H; d.variant = MI_BLUR_VARIANT_AUTO; d.stream = s.stream;
+        LaunchDesc d = ctx_launch(c, c->pool_in + (size_t)c->cursor * c->image_bytes, c->pool_out + (size_t)c->cursor * c->image_bytes,
+                                  c->H, b, 0, c->H);
+        d.stream = s.stream;
         d.concurrent = (int)c->slots.size();
         if (timed) {
             if (c->ev_used == c->ev_pool.size()) {
@@ -1439,7 +1419,7 @@ static size_t fused_words(int cap) { return 8 * (size_t)cap + 16384; }
 extern "C" int mi_blur_resident_run_fused(mi_blur_ctx *c, int n_images, int batch, int timed)
 {
     if (!c || n_images <= 0 || batch <= 0) return MI_BLUR_ERR_INVALID;
-    if (c->has_sep || c->median_r) return MI_BLUR_ERR_UNSUPPORTED;
+    if (c->filter.kind != FilterKind::BOX) return MI_BLUR_ERR_UNSUPPORTED;
     if (c->is_cpu() || !c->pool_in) return MI_BLUR_ERR_STATE;
     if (n_images > c->pool_images) return MI_BLUR_ERR_INVALID;           // one contiguous run of the pool
     HIP_TRY(hipSetDevice(c->device));
@@ -1468,11 +1448,9 @@ extern "C" int mi_blur_resident_run_fused(mi_blur_ctx *c, int n_images, int batc
     }
     if (c->cursor + n_images > c->pool_images) c->cursor = 0;
     Slot &s = c->slots[0];
-    LaunchDesc d{};
-    d.in = c->pool_in + (size_t)c->cursor * c->image_bytes;
-    d.out = c->pool_out + (size_t)c->cursor * c->image_bytes;
-    d.width = c->W; d.band_rows = c->H; d.channels = c->C; d.radius = c->R; d.n_images = n_images;
-    d.y0 = 0; d.y1 = c->H; d.variant = MI_BLUR_VARIANT_TILED; d.stream = s.stream;
+    LaunchDesc d = ctx_launch(c, c->pool_in + (size_t)c->cursor * c->image_bytes, c->pool_out + (size_t)c->cursor * c->image_bytes,
+                              c->H, n_images, 0, c->H);
+    d.variant = MI_BLUR_VARIANT_TILED; d.stream = s.stream;
     // The launch geometry (blocks per batch) depends on the tuning knobs as well as on the shape: take ONE copy of the
     // knobs, ask for the geometry first, launch with the same copy.
     const Tunables tun = tunables();
@@ -1575,38 +1553,37 @@ extern "C" int mi_blur_resident_peek(mi_blur_ctx *c, int pool_index, uint8_t *ho
 // ----------------------------------------------------------------------------------
 // CPU device kernel + helpers
 // ----------------------------------------------------------------------------------
-extern "C" int mi_blur_cpu_run(const uint8_t *in, uint8_t *out, int width, int height, int channels, int radius,
-                               int n_images, int n_threads)
+// Every failure here is MI_BLUR_ERR_INVALID, so the order of the checks does not show.  Only the separable and median runs
+// refuse images of more than INT_MAX bytes, as before.
+static int cpu_run_filter(const Filter &f, const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,
+                          int n_threads)
 {
     if (!in || !out || in == out || width <= 0 || height <= 0 || channels <= 0 || n_images < 0)
         return MI_BLUR_ERR_INVALID;
-    if (radius != 1 && radius != 2) return MI_BLUR_ERR_INVALID;
-    cpu_blur_batch(in, out, width, height, channels, radius, n_images, 0, height, n_threads);
+    if (f.kind != FilterKind::BOX && (long long)width * channels * height > INT_MAX) return MI_BLUR_ERR_INVALID;
+    cpu_blur_batch(in, out, width, height, channels, f, n_images, 0, height, n_threads);
     return MI_BLUR_OK;
+}
+
+extern "C" int mi_blur_cpu_run(const uint8_t *in, uint8_t *out, int width, int height, int channels, int radius,
+                               int n_images, int n_threads)
+{
+    Filter f;
+    return filter_box(radius, &f) ? MI_BLUR_ERR_INVALID : cpu_run_filter(f, in, out, width, height, channels, n_images, n_threads);
 }
 
 extern "C" int mi_blur_cpu_run_sep(const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,
                                    const mi_blur_sep_kernel *k, int n_threads)
 {
-    if (!in || !out || in == out || width <= 0 || height <= 0 || channels <= 0 || n_images < 0)
-        return MI_BLUR_ERR_INVALID;
-    if ((long long)width * channels * height > INT_MAX) return MI_BLUR_ERR_INVALID;
-    SepTaps t;
-    const int rc = sep_prepare(k, &t);
-    if (rc) return rc;
-    cpu_blur_batch(in, out, width, height, channels, 0, n_images, 0, height, n_threads, 0, 0, &t);
-    return MI_BLUR_OK;
+    Filter f;
+    return filter_sep(k, &f) ? MI_BLUR_ERR_INVALID : cpu_run_filter(f, in, out, width, height, channels, n_images, n_threads);
 }
 
 extern "C" int mi_blur_cpu_run_median(const uint8_t *in, uint8_t *out, int width, int height, int channels, int radius,
                                       int n_images, int n_threads)
 {
-    if (!in || !out || in == out || width <= 0 || height <= 0 || channels <= 0 || n_images < 0)
-        return MI_BLUR_ERR_INVALID;
-    if (!median_radius_ok(radius)) return MI_BLUR_ERR_INVALID;
-    if ((long long)width * channels * height > INT_MAX) return MI_BLUR_ERR_INVALID;
-    cpu_blur_batch(in, out, width, height, channels, 0, n_images, 0, height, n_threads, 0, 0, nullptr, radius);
-    return MI_BLUR_OK;
+    Filter f;
+    return filter_median(radius, &f) ? MI_BLUR_ERR_INVALID : cpu_run_filter(f, in, out, width, height, channels, n_images, n_threads);
 }
 
 extern "C" void mi_blur_fill_synthetic(uint8_t *host, int width, int height, int channels, int first_index,

@@ -303,7 +303,7 @@ int launch_sep_tiled_c(const LaunchDesc &d, const SepTiledParams &p, dim3 grid, 
 int launch_sep_tiled(const LaunchDesc &d)
 {
     set_last_kernel("blur_sep_tiled_kernel");
-    const SepTaps &k = *d.sep;
+    const SepTaps &k = d.filter->taps;
     const int pitch = d.width * d.channels, cpr = pitch / 16, rows = d.y1 - d.y0;
     SepTiledParams p{};
     p.in = d.in; p.out = d.out;
@@ -333,7 +333,7 @@ int launch_sep_tiled(const LaunchDesc &d)
 int launch_sep_generic(const LaunchDesc &d)
 {
     set_last_kernel("blur_sep_generic_kernel");
-    const SepTaps &k = *d.sep;
+    const SepTaps &k = d.filter->taps;
     const int pitch = d.width * d.channels, rows = d.y1 - d.y0;
     SepGenericParams p{};
     p.in = d.in; p.out = d.out;
@@ -353,12 +353,12 @@ int launch_sep_generic(const LaunchDesc &d)
 
 int launch_sep(const LaunchDesc &d)
 {
-    if (!d.sep || !d.in || !d.out || d.in == d.out) return MI_BLUR_ERR_INVALID;
+    if (!d.filter || d.filter->kind != FilterKind::SEP || !d.in || !d.out || d.in == d.out) return MI_BLUR_ERR_INVALID;
     if (d.width <= 0 || d.band_rows <= 0 || d.channels <= 0 || d.n_images < 0) return MI_BLUR_ERR_INVALID;
     if (d.y0 < 0 || d.y1 > d.band_rows || d.y0 >= d.y1) return MI_BLUR_ERR_INVALID;
     if ((long long)d.width * d.channels > INT_MAX / 2) return MI_BLUR_ERR_INVALID;
     if ((long long)d.width * d.channels * d.band_rows > INT_MAX) return MI_BLUR_ERR_INVALID;  // per-image 32-bit
-    const SepTaps &k = *d.sep;
+    const SepTaps &k = d.filter->taps;
     if (k.rx < 0 || k.rx > SEP_MAX_R || k.ry < 0 || k.ry > SEP_MAX_R || k.shift < 0 || k.shift > 16) return MI_BLUR_ERR_INVALID;
     if (d.halo_top || d.halo_bottom) return MI_BLUR_ERR_UNSUPPORTED;
     const long long pitch = (long long)d.width * d.channels;
