@@ -1,0 +1,224 @@
+"""Shared by test_kernel_proofs_gpu.py and test_kernel_proofs_host.py (not a test module): the pattern sets that prove the
+median networks by the 0-1 principle, and numpy restatements of the definitions in include/mi_blur.h that do not touch
+the product.
+
+The 0-1 principle: a selection built only from min / max (and byte copies) commutes with every monotone map, so if it is
+right on every two-valued window it is right on every window.  For radius r a window is D = 2r+1 columns of D rows; one
+column is a D-bit value v whose bit b is "high" in row b.  The cyclic de Bruijn sequence B(2^D, D) holds every run of D
+consecutive column values exactly once, so one image row of it shows every two-valued window exactly once.  Row y of
+an image shows bit (y + phase) mod D of each column value: a window centred on an interior row sees a rotation of the
+bits, which is a bijection on column values, so every interior row sees every window.
+"""
+import functools
+import math
+
+import numpy as np
+from numpy.lib.stride_tricks import sliding_window_view
+
+MEDIAN_PAIRS = [(0, 255), (127, 128)]     # (low, high): any one proves the network; the second catches top-bit pack errors
+
+
+def med_bh(r):
+    """Output rows per lane of blur_median_fast_kernel (radius 1: 8, radius 2: 4)."""
+    return 8 if r == 1 else 4
+
+
+def fast_align(c):
+    """Smallest pixel count whose row is a whole number of 16-byte chunks."""
+    return 16 // math.gcd(c, 16)
+
+
+@functools.lru_cache(maxsize=None)
+def debruijn(m, n):
+    """Cyclic de Bruijn sequence B(2^m, n) for prime n, by the FKM construction: the Lyndon words of length 1 and n over
+    2^m letters, in lexicographic order, concatenated.  Returns uint8 (m <= 8) of length 2^(m n); the linear sequence is
+    this plus its first n-1 letters."""
+    assert n in (2, 3, 5, 7) and m * n <= 30
+    k = 1 << m
+    mask = (1 << (m * n)) - 1
+    w = np.arange(1 << (m * n), dtype=np.int64)            # word w: letter j = digit j from the top, base 2^m
+    rot_min = np.full_like(w, mask + 1)
+    for s in range(1, n):                                   # the n-1 nontrivial rotations
+        sh = m * s
+        np.minimum(rot_min, ((w << sh) | (w >> (m * n - sh))) & mask, out=rot_min)
+    lyndon = w < rot_min                                    # strictly below every rotation: Lyndon of length n
+    const = (w % ((mask) // (k - 1))) == 0                  # aaaa...a: the Lyndon word "a" of length 1, in its place
+    keep = lyndon | const
+    words = w[keep]
+    lens = np.where(lyndon[keep], n, 1)
+    del w, rot_min, lyndon, const, keep
+    starts = np.cumsum(lens) - lens
+    total = int(lens.sum())
+    assert total == 1 << (m * n)
+    rep = np.repeat(words, lens)
+    j = np.arange(total, dtype=np.int64) - np.repeat(starts, lens)
+    # a constant word contributes its first letter: the top digit, like letter 0 of a length-n word
+    digit = (rep >> (m * (n - 1 - j))) & (k - 1)
+    return digit.astype(np.uint8)
+
+
+def window_codes(seq, m, n):
+    """Integer code of every run of n consecutive letters of the LINEAR sequence (seq + its first n-1 letters)."""
+    lin = np.concatenate([seq, seq[:n - 1]]).astype(np.int64)
+    code = np.zeros(len(seq), np.int64)
+    for j in range(n):
+        code = (code << m) | lin[j:j + len(seq)]
+    return code
+
+
+# ---------------------------------------------------------------- pattern sets (numpy form; the GPU module builds the same on the device)
+CHANNEL_OFFSET = 0x2F0B5                   # stream offset of channel c: c * CHANNEL_OFFSET (odd channels also complemented)
+
+
+def row_bit(y, c, d):
+    """Bit of the column value that row y of channel c shows."""
+    return (y + c) % d
+
+
+def stream_width(r, c, shift):
+    """Width of the interior-stream image: `shift` pad pixels, the 2^(D D) columns of B(2^D, D) plus 2r, rounded up to
+    whole chunks."""
+    d = 2 * r + 1
+    w = shift + (1 << (d * d)) + 2 * r
+    a = fast_align(c)
+    return (w + a - 1) // a * a
+
+
+def stream_mask_np(seq, r, c, shift, x0=0, w=None, h=None):
+    """0/1 mask (1, H, W, C) of the interior stream: pixel x of channel c shows column value seq[(x - shift +
+    c * CHANNEL_OFFSET) mod len]; row y its bit row_bit(y, c); odd channels complemented.  x0 / w crop columns."""
+    d = 2 * r + 1
+    h = med_bh(r) + 2 * r if h is None else h
+    w = stream_width(r, c, shift) - x0 if w is None else w
+    n = len(seq)
+    out = np.empty((1, h, w, c), np.uint8)
+    x = np.arange(x0, x0 + w, dtype=np.int64)
+    for ch in range(c):
+        v = seq[(x - shift + ch * CHANNEL_OFFSET) % n]
+        for y in range(h):
+            out[0, y, :, ch] = ((v >> row_bit(y, ch, d)) & 1) ^ (ch & 1)
+    return out
+
+
+def edge_width(r, c):
+    """Narrowest width of whole chunks with at least 4r pixels: the first and last 2r columns are distinct."""
+    a = fast_align(c)
+    return max(a, (4 * r + a - 1) // a * a)
+
+
+EDGE_MUL, EDGE_ADD = 0x9E3B5, 0x3A5A5      # the right edge enumerates combinations in the order i -> i * MUL + ADD (odd MUL)
+
+
+def edge_combos(r):
+    d = 2 * r + 1
+    return 1 << (d * 2 * r)
+
+
+def edge_mask_np(r, c):
+    """0/1 mask (N, H, W, C) of the edge batch: image i's first 2r columns are the base-2^D digits of combination
+    (i + c * CHANNEL_OFFSET) mod N, its last 2r those of a permuted combination, the columns between a fixed filler."""
+    d = 2 * r + 1
+    nc = edge_combos(r)
+    h, w = med_bh(r) + 2 * r, edge_width(r, c)
+    out = np.empty((nc, h, w, c), np.uint8)
+    i = np.arange(nc, dtype=np.int64)
+    for ch in range(c):
+        left = (i + ch * CHANNEL_OFFSET) % nc
+        right = (left * EDGE_MUL + EDGE_ADD) % nc
+        cols = np.empty((nc, w), np.int64)
+        for x in range(w):
+            cols[:, x] = (i * 7 + x * 13 + ch) % (1 << d)
+        for k in range(2 * r):
+            cols[:, k] = (left >> (d * k)) & ((1 << d) - 1)
+            cols[:, w - 2 * r + k] = (right >> (d * k)) & ((1 << d) - 1)
+        for y in range(h):
+            out[:, y, :, ch] = ((cols >> row_bit(y, ch, d)) & 1) ^ (ch & 1)
+    return out
+
+
+def high_count_np(mask, r):
+    """Number of high values in the clamped (2r+1)^2 window of every pixel of a 0/1 mask (N, H, W, C)."""
+    n, h, w, c = mask.shape
+    v = np.zeros(mask.shape, np.uint8)
+    for j in range(-r, r + 1):
+        v += mask[:, np.clip(np.arange(h) + j, 0, h - 1)]
+    p = np.concatenate([np.repeat(v[:, :, :1], r, axis=2), v, np.repeat(v[:, :, -1:], r, axis=2)], axis=2)
+    cnt = np.zeros(mask.shape, np.uint8)
+    for i in range(2 * r + 1):
+        cnt += p[:, :, i:i + w]
+    return cnt
+
+
+def two_valued(mask, lo, hi):
+    return np.where(mask.astype(bool), np.uint8(hi), np.uint8(lo))
+
+
+def median_from_count(cnt, r, lo, hi):
+    """The k-th smallest of a window of lo / hi values is hi exactly when more than k values are high."""
+    k = ((2 * r + 1) ** 2 - 1) // 2
+    return np.where(cnt >= k + 1, np.uint8(hi), np.uint8(lo))
+
+
+# ---------------------------------------------------------------- restatements of the definitions in include/mi_blur.h
+def ref_median(img, r):
+    """img (N, H, W, C) uint8: edge padding by r, every (2r+1)^2 window, the k-th smallest (k = ((2r+1)^2 - 1) / 2)."""
+    d = 2 * r + 1
+    p = np.pad(img, ((0, 0), (r, r), (r, r), (0, 0)), mode="edge")
+    flat = sliding_window_view(p, (d, d), axis=(1, 2)).reshape(img.shape + (d * d,))
+    k = (d * d - 1) // 2
+    return np.partition(flat, k, axis=-1)[..., k].astype(np.uint8)
+
+
+def ref_sep(img, wx, wy):
+    """img (N, H, W, C) uint8: edge padding, exact int64 sums, one shift by log2(sum wx) + log2(sum wy)."""
+    rx, ry = len(wx) // 2, len(wy) // 2
+    shift = int(sum(wx)).bit_length() - 1 + int(sum(wy)).bit_length() - 1
+    n, h, w, c = img.shape
+    p = np.pad(img.astype(np.int64), ((0, 0), (ry, ry), (rx, rx), (0, 0)), mode="edge")
+    hs = sum(int(wx[i]) * p[:, :, i:i + w, :] for i in range(2 * rx + 1))
+    vs = sum(int(wy[j]) * hs[:, j:j + h, :, :] for j in range(2 * ry + 1))
+    return (vs >> shift).astype(np.uint8)
+
+
+def rand_taps(rng, r, bits):
+    """2r+1 non-negative taps summing to 2^bits."""
+    if r == 0:
+        return [1 << bits]
+    cuts = np.sort(rng.integers(0, (1 << bits) + 1, size=2 * r))
+    return np.diff(np.concatenate([[0], cuts, [1 << bits]])).tolist()
+
+
+def one_hot(rb, d, b):
+    """Taps of radius rb: 2^b at offset d, 0 elsewhere."""
+    t = [0] * (2 * rb + 1)
+    t[rb + d] = 1 << b
+    return t
+
+
+def shifted(img, d, axis):
+    """img moved by d pixels along axis 1 (rows) or 2 (columns), clamped: out[.., x, ..] = img[.., clamp(x + d), ..]."""
+    n = img.shape[axis]
+    return np.take(img, np.clip(np.arange(n) + d, 0, n - 1), axis=axis)
+
+
+ONE_HOT_BUCKETS = (4, 8, 16)               # blur_sep_tiled_kernel's radius buckets RB
+ONE_HOT_CPR = (1, 40)                      # one chunk; more than one strip of 32 chunk columns
+
+
+def chunk_cols(cpr, c):
+    """cpr rounded to the nearest chunk count that whole pixels of c channels fill (a multiple of 3 for c = 3)."""
+    a = fast_align(c) * c // 16                       # chunks per aligned pixel run
+    return max(a, int(round(cpr / a)) * a)
+
+
+def one_hot_cases():
+    """(c, axis, rb, d, b, w, h): a one-hot tap 2^b at offset d of a radius-rb axis (2 = horizontal, 1 = vertical; the
+    other axis [1]), on rows of one chunk column and of 40 (a tile of more than one 32-column strip)."""
+    for c in range(1, 5):
+        for cpr in ONE_HOT_CPR:
+            w = chunk_cols(cpr, c) * 16 // c
+            for axis, h in ((2, 6), (1, 40)):
+                for rb in ONE_HOT_BUCKETS:
+                    for d in range(-rb, rb + 1):
+                        for b in (0, 8):
+                            yield c, axis, rb, d, b, w, h
