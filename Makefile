@@ -10,7 +10,7 @@ CSRC    := $(PKG)/csrc
 APPS    := $(PKG)/apps
 LIB     := $(PKG)/libmi_blur.so
 LIBSRC  := $(CSRC)/blur_kernels.hip $(CSRC)/sep_kernels.hip $(CSRC)/median_kernels.hip $(CSRC)/layout_kernels.hip $(CSRC)/mi_blur_api.cpp $(CSRC)/cpu_device.cpp
-LIBDEPS := $(LIBSRC) $(CSRC)/blur_launch.h $(CSRC)/cpu_device.h $(CSRC)/filter.h include/mi_blur.h
+LIBDEPS := $(LIBSRC) $(CSRC)/blur_launch.h $(CSRC)/kernel_common.h $(CSRC)/cpu_device.h $(CSRC)/filter.h include/mi_blur.h
 APPFLAGS := -O2 -std=c++17 -Wall -Wextra -I include
 ifdef CIMG
 APPFLAGS += -DMI_BLUR_WITH_CIMG -I $(CIMG)

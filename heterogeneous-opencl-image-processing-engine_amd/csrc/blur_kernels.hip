@@ -53,12 +53,8 @@
 //
 // Generic kernel: one output byte per thread, any shape (rows shorter than 16 bytes, more than 4
 // channels).  Correct everywhere, fast nowhere.
-#include "blur_launch.h"
-#include "../../include/mi_blur.h"
+#include "kernel_common.h"
 
-#include <hip/hip_ext.h>
-#include <type_traits>
-#include <limits.h>
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -70,9 +66,6 @@ namespace mi_blur {
 // ----------------------------------------------------------------------------------
 // device helpers
 // ----------------------------------------------------------------------------------
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ u16x2 as_pk(uint32_t x) { return __builtin_bit_cast(u16x2, x); }
 __device__ __forceinline__ uint32_t as_u32(u16x2 x) { return __builtin_bit_cast(uint32_t, x); }
 
@@ -297,28 +290,7 @@ __device__ __forceinline__ void store_chunk_ragged(uint8_t *q, u32x4 v, int n)
 // ----------------------------------------------------------------------------------
 // LDS-tiled vector kernel
 // ----------------------------------------------------------------------------------
-// blockIdx -> tile.  Blocks b and b+8 share an XCD (round-robin dispatch); give each XCD a contiguous run of the
-// n tiles so tile-edge halo rows are L2 hits.  A bijection of [0, n).  Speed only.
-__device__ __forceinline__ unsigned xcd_contiguous(unsigned L, unsigned n)
-{
-    const unsigned q = n >> 3, r = n & 7u, x = L & 7u, k = L >> 3;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + k;
-}
-// The same idea at a finer grain: runs of `run` consecutive tiles (tiles that share halo rows: an image, a few tile rows)
-// are dealt to the XCDs in turn, so an XCD's tiles still find their neighbours' rows in its own L2 while its stream walks
-// the WHOLE buffer instead of one eighth of it.  A bijection of [0, n): the last n mod 8*run tiles map to themselves.
-__device__ __forceinline__ unsigned xcd_runs(unsigned L, unsigned n, unsigned run)
-{
-    const unsigned span = 8u * run, full = n - n % span;
-    if (L >= full) return L;
-    const unsigned x = L & 7u, k = L >> 3, j = k / run, o = k - j * run;
-    return (j * 8u + x) * run + o;
-}
-__device__ __forceinline__ unsigned xcd_map(unsigned L, unsigned n, int mode)
-{
-    return mode == 0 ? L : mode == 1 ? xcd_contiguous(L, n) : xcd_runs(L, n, (unsigned)mode);
-}
-
+// (blockIdx -> tile maps: xcd_map, kernel_common.h)
 // 16-byte output store that writes through the (per-XCD, mutually non-coherent) L2 to memory: when its vmcnt has
 // drained the bytes are visible device-wide without an L2 write-back fence.  Fused stream only.
 __device__ __forceinline__ void store16_write_through(uint8_t *q, u32x4 v)
@@ -932,10 +904,7 @@ __global__ __launch_bounds__(256) void blur_stream_kernel(const StreamParams p)
     const unsigned ring_off = (unsigned)(unsigned long long)((__attribute__((address_space(3))) uint8_t *)ring);   // LDS byte address
 
     unsigned B = blockIdx.x;
-    if (p.xcd) {
-        const unsigned n = p.nblocks, q = n >> 3, r = n & 7u, x = B & 7u, k = B >> 3;
-        B = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + k;
-    }
+    if (p.xcd) B = xcd_contiguous(B, p.nblocks);
     const unsigned last = (unsigned)p.total - 1u;                       // host keeps total < 2^31
     const unsigned f0 = (B * 4u + (unsigned)wave) * 64u;
     const unsigned f_raw = f0 + (unsigned)lane;
@@ -1070,6 +1039,7 @@ __global__ __launch_bounds__(256) void blur_direct_kernel(const DirectParams p)
     constexpr int WIN = 2 * R + 1, NR = BH + 2 * R;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const unsigned B = xcd_map(blockIdx.x, p.nblocks, p.xcd);
+    // (this lane decode and the DPP window below have a twin in blur_median_fast_kernel: a shared helper changed the generated code)
     const long long fl = (long long)(B * 4u + (unsigned)wave) * 62 - 1 + lane;
     const bool inrange = fl >= 0 && fl < p.total;
     const unsigned f = (unsigned)(fl < 0 ? 0 : (fl >= p.total ? p.total - 1 : fl));
@@ -1185,20 +1155,14 @@ static std::mutex &tunables_mutex() { static std::mutex m; return m; }
 static Tunables &tunables_storage()
 {
     static Tunables t = [] {
-        Tunables v{};                                    // everything 0 / off unless named here (rpg 0 / stream_bh 0 = choose per launch)
-        v.stage_dma = 1; v.xcd_remap = 1; v.zero_copy = 1; v.ragged = 1;
-        v.zero_copy_streams = 4; v.zero_copy_blocks = 24; v.stream_updown = 1; v.prefer_direct = 1; v.direct_bh = 8; v.fused_window = 8;
-        v.zero_copy_server = 1; v.zero_copy_server_min_kb = 1280; v.staged_server = 1; v.zero_copy_workers = 48; v.zero_copy_idle_us = 300; v.zero_copy_budget = 256; v.zero_copy_tickets = 1;
-        v.zero_copy_events = 1;
-        v.fused_tail = 30; v.fused_tail_blocks = 25; v.fused_adds_per_word = 32;
-        v.resident_place_trials = 4;
-        if (const char *e = getenv("MI_BLUR_PLACE_TRIALS")) { const int r = atoi(e); if (r >= 0 && r <= 8) v.resident_place_trials = r; }
-        if (const char *e = getenv("MI_BLUR_STAGED_SERVER")) v.staged_server = atoi(e) != 0;
-        if (const char *e = getenv("MI_BLUR_FUSED_TAIL")) { const int r = atoi(e); if (r >= 0 && r <= 500) v.fused_tail = r; }
-        if (const char *e = getenv("MI_BLUR_STAGE")) v.stage_dma = strcmp(e, "reg") != 0;
-        if (const char *e = getenv("MI_BLUR_RPG")) { const int r = atoi(e); v.rpg = (r == 4 || r == 8 || r == 16) ? r : 0; }
-        if (const char *e = getenv("MI_BLUR_XCD")) v.xcd_remap = atoi(e) != 0;
-        if (const char *e = getenv("MI_BLUR_DIRECT")) { const int r = atoi(e); if (r >= 0 && r <= 2) v.prefer_direct = r; }
+        Tunables v{};
+        for (const Knob &k : KNOBS) {
+            v.*k.field = k.def;
+            const char *e = k.env ? getenv(k.env) : nullptr;
+            if (!e) continue;
+            if (k.field == &Tunables::stage_dma) v.stage_dma = strcmp(e, "reg") != 0;     // "dma" | "reg", not a number
+            else knob_set(k, v, atoi(e));                                                // out of range: the default stays
+        }
         return v;
     }();
     return t;
@@ -1248,52 +1212,25 @@ static thread_local const char *g_last_kernel = "";
 const char *last_kernel() { return g_last_kernel; }
 void set_last_kernel(const char *name) { g_last_kernel = name; }
 
-static inline int hip_status(hipError_t e) { return e == hipSuccess ? MI_BLUR_OK : MI_BLUR_ERR_HIP_BASE - (int)e; }
-
-template <typename K, typename P>
-static int do_launch(K kernel, dim3 grid, dim3 block, size_t lds, const LaunchDesc &d, const P &params)
-{
-    if (d.start || d.stop)
-        hipExtLaunchKernelGGL(kernel, grid, block, lds, d.stream, d.start, d.stop, 0, params);
-    else
-        hipLaunchKernelGGL(kernel, grid, block, lds, d.stream, params);
-    return hip_status(hipGetLastError());
-}
-
+// rpg is 4 | 8 | 16 (tiled_geometry), 4 | 8 where the ragged, capped-grid, A/B or wide forms are taken.  The bool template
+// arguments go through dispatch as 1 | 0.
 template <int C, int R>
 static int launch_tiled_cr(const LaunchDesc &d, const TiledParams &p, dim3 grid, dim3 block, size_t lds,
                            int rpg, bool dma, bool ragged, bool row_shuffle, int experiment)
 {
-    if (ragged) {
-        if (dma)
-            return rpg == 4 ? do_launch(blur_tiled_kernel<C, R, 4, true, false, true>, grid, block, lds, d, p)
-                            : do_launch(blur_tiled_kernel<C, R, 8, true, false, true>, grid, block, lds, d, p);
-        return rpg == 4 ? do_launch(blur_tiled_kernel<C, R, 4, false, false, true>, grid, block, lds, d, p)
-                        : do_launch(blur_tiled_kernel<C, R, 8, false, false, true>, grid, block, lds, d, p);
-    }
-    if (d.max_blocks > 0 && dma && rpg != 16 && grid.x > (unsigned)d.max_blocks) {
-        const dim3 capped((unsigned)d.max_blocks);
-        return rpg == 4 ? do_launch(blur_tiled_loop_kernel<C, R, 4>, capped, block, lds, d, p)
-                        : do_launch(blur_tiled_loop_kernel<C, R, 8>, capped, block, lds, d, p);
-    }
-    if (experiment && dma && C == 3 && rpg != 16) {
-        constexpr int OTHER = 1 - rowpass_default<R>;
-        return rpg == 4 ? do_launch(blur_tiled_x_kernel<C, R, 4, OTHER>, grid, block, lds, d, p)
-                        : do_launch(blur_tiled_x_kernel<C, R, 8, OTHER>, grid, block, lds, d, p);
-    }
-    if (row_shuffle && dma) {
-        if (rpg == 16) return do_launch(blur_tiled_kernel<C, R, 16, true, true>, grid, block, lds, d, p);
-        if (rpg == 4) return do_launch(blur_tiled_kernel<C, R, 4, true, true>, grid, block, lds, d, p);
-        return do_launch(blur_tiled_kernel<C, R, 8, true, true>, grid, block, lds, d, p);
-    }
-    if (rpg == 16)
-        return dma ? do_launch(blur_tiled_kernel<C, R, 16, true>, grid, block, lds, d, p)
-                   : do_launch(blur_tiled_kernel<C, R, 16, false>, grid, block, lds, d, p);
-    if (rpg == 4)
-        return dma ? do_launch(blur_tiled_kernel<C, R, 4, true>, grid, block, lds, d, p)
-                   : do_launch(blur_tiled_kernel<C, R, 4, false>, grid, block, lds, d, p);
-    return dma ? do_launch(blur_tiled_kernel<C, R, 8, true>, grid, block, lds, d, p)
-               : do_launch(blur_tiled_kernel<C, R, 8, false>, grid, block, lds, d, p);
+    if (ragged)
+        return dispatch<1, 0>(dma, [&](auto DMA) {
+            return dispatch<4, 8>(rpg, [&](auto RPG) { return do_launch(blur_tiled_kernel<C, R, RPG, DMA != 0, false, true>, grid, block, lds, d, p); });
+        });
+    if (d.max_blocks > 0 && dma && rpg != 16 && grid.x > (unsigned)d.max_blocks)
+        return dispatch<4, 8>(rpg, [&](auto RPG) { return do_launch(blur_tiled_loop_kernel<C, R, RPG>, dim3((unsigned)d.max_blocks), block, lds, d, p); });
+    if (experiment && dma && C == 3 && rpg != 16)
+        return dispatch<4, 8>(rpg, [&](auto RPG) { return do_launch(blur_tiled_x_kernel<C, R, RPG, 1 - rowpass_default<R>>, grid, block, lds, d, p); });
+    if (row_shuffle && dma)
+        return dispatch<16, 4, 8>(rpg, [&](auto RPG) { return do_launch(blur_tiled_kernel<C, R, RPG, true, true>, grid, block, lds, d, p); });
+    return dispatch<16, 4, 8>(rpg, [&](auto RPG) {
+        return dispatch<1, 0>(dma, [&](auto DMA) { return do_launch(blur_tiled_kernel<C, R, RPG, DMA != 0>, grid, block, lds, d, p); });
+    });
 }
 
 // 5 to 8 channels, 3x3 only (the +-C byte taps still fall inside the 8 + 16 + 8-byte window; 5x5 would need +-2C): the
@@ -1302,11 +1239,9 @@ static int launch_tiled_cr(const LaunchDesc &d, const TiledParams &p, dim3 grid,
 template <int C>
 static int launch_tiled_wide(const LaunchDesc &d, const TiledParams &p, dim3 grid, dim3 block, size_t lds, int rpg, bool ragged)
 {
-    if (ragged)
-        return rpg == 4 ? do_launch(blur_tiled_kernel<C, 1, 4, true, false, true>, grid, block, lds, d, p)
-                        : do_launch(blur_tiled_kernel<C, 1, 8, true, false, true>, grid, block, lds, d, p);
-    return rpg == 4 ? do_launch(blur_tiled_kernel<C, 1, 4, true>, grid, block, lds, d, p)
-                    : do_launch(blur_tiled_kernel<C, 1, 8, true>, grid, block, lds, d, p);
+    return dispatch<1, 0>(ragged, [&](auto RAG) {
+        return dispatch<4, 8>(rpg, [&](auto RPG) { return do_launch(blur_tiled_kernel<C, 1, RPG, true, false, RAG != 0>, grid, block, lds, d, p); });
+    });
 }
 
 static bool wide_channels(int channels, int radius) { return channels >= 5 && channels <= 8 && radius == 1; }
@@ -1315,65 +1250,25 @@ template <int R>
 static int launch_tiled_r(const LaunchDesc &d, const TiledParams &p, dim3 grid, dim3 block, size_t lds,
                           int rpg, bool dma, bool ragged, bool row_shuffle, int experiment)
 {
-    if constexpr (R == 1) {
-        switch (d.channels) {
-        case 5: return launch_tiled_wide<5>(d, p, grid, block, lds, rpg, ragged);
-        case 6: return launch_tiled_wide<6>(d, p, grid, block, lds, rpg, ragged);
-        case 7: return launch_tiled_wide<7>(d, p, grid, block, lds, rpg, ragged);
-        case 8: return launch_tiled_wide<8>(d, p, grid, block, lds, rpg, ragged);
-        }
-    }
-    switch (d.channels) {
-    case 1: return launch_tiled_cr<1, R>(d, p, grid, block, lds, rpg, dma, ragged, row_shuffle, experiment);
-    case 2: return launch_tiled_cr<2, R>(d, p, grid, block, lds, rpg, dma, ragged, row_shuffle, experiment);
-    case 3: return launch_tiled_cr<3, R>(d, p, grid, block, lds, rpg, dma, ragged, row_shuffle, experiment);
-    case 4: return launch_tiled_cr<4, R>(d, p, grid, block, lds, rpg, dma, ragged, row_shuffle, experiment);
-    }
-    return MI_BLUR_ERR_INVALID;
+    if constexpr (R == 1)
+        if (d.channels > 4) return dispatch<5, 6, 7, 8>(d.channels, [&](auto C) { return launch_tiled_wide<C>(d, p, grid, block, lds, rpg, ragged); });
+    return dispatch<1, 2, 3, 4>(d.channels, [&](auto C) { return launch_tiled_cr<C, R>(d, p, grid, block, lds, rpg, dma, ragged, row_shuffle, experiment); });
 }
 
 template <int R>
 static int launch_fused_r(const LaunchDesc &d, const TiledParams &p, const FusedParams &f, dim3 grid, dim3 block, size_t lds, int rpg, bool ragged = false)
 {
-    auto go = [&](auto kernel) {
-        if (d.start || d.stop) hipExtLaunchKernelGGL(kernel, grid, block, lds, d.stream, d.start, d.stop, 0, p, f);
-        else hipLaunchKernelGGL(kernel, grid, block, lds, d.stream, p, f);
-        return hip_status(hipGetLastError());
-    };
     if (ragged) {                                        // rows/thread 8, the tail kernel (its tail may be empty)
         if (!f.tail_ctr || rpg != 8) return MI_BLUR_ERR_INVALID;
-        switch (d.channels) {
-        case 1: return go(blur_fused_tail_kernel<1, R, 8, true>);
-        case 2: return go(blur_fused_tail_kernel<2, R, 8, true>);
-        case 3: return go(blur_fused_tail_kernel<3, R, 8, true>);
-        case 4: return go(blur_fused_tail_kernel<4, R, 8, true>);
-        }
-        return MI_BLUR_ERR_INVALID;
+        return dispatch<1, 2, 3, 4>(d.channels, [&](auto C) { return do_launch(blur_fused_tail_kernel<C, R, 8, true>, grid, block, lds, d, p, f); });
     }
-    if (f.tail_ctr) {
-        switch (d.channels * 10 + rpg) {
-        case 14: return go(blur_fused_tail_kernel<1, R, 4>);
-        case 18: return go(blur_fused_tail_kernel<1, R, 8>);
-        case 24: return go(blur_fused_tail_kernel<2, R, 4>);
-        case 28: return go(blur_fused_tail_kernel<2, R, 8>);
-        case 34: return go(blur_fused_tail_kernel<3, R, 4>);
-        case 38: return go(blur_fused_tail_kernel<3, R, 8>);
-        case 44: return go(blur_fused_tail_kernel<4, R, 4>);
-        case 48: return go(blur_fused_tail_kernel<4, R, 8>);
-        }
-        return MI_BLUR_ERR_INVALID;
-    }
-    switch (d.channels * 10 + rpg) {
-    case 14: return go(blur_fused_kernel<1, R, 4>);
-    case 18: return go(blur_fused_kernel<1, R, 8>);
-    case 24: return go(blur_fused_kernel<2, R, 4>);
-    case 28: return go(blur_fused_kernel<2, R, 8>);
-    case 34: return go(blur_fused_kernel<3, R, 4>);
-    case 38: return go(blur_fused_kernel<3, R, 8>);
-    case 44: return go(blur_fused_kernel<4, R, 4>);
-    case 48: return go(blur_fused_kernel<4, R, 8>);
-    }
-    return MI_BLUR_ERR_INVALID;
+    if (f.tail_ctr)
+        return dispatch<1, 2, 3, 4>(d.channels, [&](auto C) {
+            return dispatch<4, 8>(rpg, [&](auto RPG) { return do_launch(blur_fused_tail_kernel<C, R, RPG>, grid, block, lds, d, p, f); });
+        });
+    return dispatch<1, 2, 3, 4>(d.channels, [&](auto C) {
+        return dispatch<4, 8>(rpg, [&](auto RPG) { return do_launch(blur_fused_kernel<C, R, RPG>, grid, block, lds, d, p, f); });
+    });
 }
 
 // Tile geometry of one launch of the tiled kernel family: fills p and returns the output rows per thread it chose.
@@ -1394,10 +1289,8 @@ static int tiled_geometry(const LaunchDesc &d, const Tunables &tun, bool ragged,
     if ((ragged || fused || d.channels > 4) && rpg == 16) rpg = 8;
 
     p = TiledParams{};
-    p.in = d.in; p.out = d.out;
-    p.in_stride = d.in_stride ? d.in_stride : (long long)d.band_rows * pitch;
-    p.out_stride = d.out_stride ? d.out_stride : (long long)rows * pitch;
-    p.pitch = pitch; p.cpr = cpr; p.H = d.band_rows; p.y0 = d.y0; p.y1 = d.y1;
+    fill_band(p, d);
+    p.cpr = cpr; p.y1 = d.y1;
     p.nstrips = (cpr + 61) / 62;               // ncols + 2 halo chunks <= 64 lanes: one row per wave-instruction
     p.ncols = (cpr + p.nstrips - 1) / p.nstrips;
 
@@ -1478,7 +1371,7 @@ static int launch_tiled(const LaunchDesc &d, const Tunables &tun, bool ragged = 
                 f.nextra = ntail + (unsigned)((long long)ntail * std::max(10, tun.fused_tail_blocks) / 100);
                 g_last_kernel = "blur_fused_tail_kernel";
                 const dim3 tgrid(f.nstatic + f.nextra);
-                return R == 1 ? launch_fused_r<1>(d, p, f, tgrid, block, lds, rpg, ragged) : launch_fused_r<2>(d, p, f, tgrid, block, lds, rpg, ragged);
+                return dispatch<1, 2>(R, [&](auto Rc) { return launch_fused_r<Rc>(d, p, f, tgrid, block, lds, rpg, ragged); });
             }
         }
         if (ragged) {      // ragged rows, no tail: the same kernel with every tile mapped to a block
@@ -1486,10 +1379,11 @@ static int launch_tiled(const LaunchDesc &d, const Tunables &tun, bool ragged = 
             f.tail_ctr = fused->tail_ctr; f.ntail = 0; f.nstatic = (unsigned)nblocks; f.nextra = 0;
             g_last_kernel = "blur_fused_tail_kernel";
         }
-        return R == 1 ? launch_fused_r<1>(d, p, f, grid, block, lds, rpg, ragged) : launch_fused_r<2>(d, p, f, grid, block, lds, rpg, ragged);
+        return dispatch<1, 2>(R, [&](auto Rc) { return launch_fused_r<Rc>(d, p, f, grid, block, lds, rpg, ragged); });
     }
-    return R == 1 ? launch_tiled_r<1>(d, p, grid, block, lds, rpg, tun.stage_dma != 0, ragged, tun.row_shuffle != 0, tun.experiment)
-                  : launch_tiled_r<2>(d, p, grid, block, lds, rpg, tun.stage_dma != 0, ragged, tun.row_shuffle != 0, tun.experiment);
+    return dispatch<1, 2>(R, [&](auto Rc) {
+        return launch_tiled_r<Rc>(d, p, grid, block, lds, rpg, tun.stage_dma != 0, ragged, tun.row_shuffle != 0, tun.experiment);
+    });
 }
 
 // ---- zero-copy batch server: host side of the launch interface (blur_launch.h)
@@ -1525,37 +1419,20 @@ int zc_launch_server(const ZcGeometry &geo, ZcHostCtl *ctl, ZcDevCtl *dev, unsig
     if (!ctl || !dev || n_workers == 0 || geo.threads == 0 || geo.rpg != 4) return MI_BLUR_ERR_INVALID;
     g_last_kernel = "blur_server_kernel";
     const dim3 grid(n_workers + 1), block(geo.threads);
-    auto go = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, grid, block, geo.lds, stream, ctl, dev, seq, budget, idle_ticks, trace, fixed_share);
-        return hip_status(hipGetLastError());
-    };
-    switch (geo.channels * 100 + geo.radius * 10 + geo.ragged) {
-    case 110: return go(blur_server_kernel<1, 1, 4, false>);
-    case 120: return go(blur_server_kernel<1, 2, 4, false>);
-    case 210: return go(blur_server_kernel<2, 1, 4, false>);
-    case 220: return go(blur_server_kernel<2, 2, 4, false>);
-    case 310: return go(blur_server_kernel<3, 1, 4, false>);
-    case 320: return go(blur_server_kernel<3, 2, 4, false>);
-    case 410: return go(blur_server_kernel<4, 1, 4, false>);
-    case 420: return go(blur_server_kernel<4, 2, 4, false>);
-    case 111: return go(blur_server_kernel<1, 1, 4, true>);
-    case 121: return go(blur_server_kernel<1, 2, 4, true>);
-    case 211: return go(blur_server_kernel<2, 1, 4, true>);
-    case 221: return go(blur_server_kernel<2, 2, 4, true>);
-    case 311: return go(blur_server_kernel<3, 1, 4, true>);
-    case 321: return go(blur_server_kernel<3, 2, 4, true>);
-    case 411: return go(blur_server_kernel<4, 1, 4, true>);
-    case 421: return go(blur_server_kernel<4, 2, 4, true>);
-    }
-    return MI_BLUR_ERR_INVALID;
+    return dispatch<0, 1>(geo.ragged, [&](auto RAG) {
+        return dispatch<1, 2, 3, 4>(geo.channels, [&](auto C) {
+            return dispatch<1, 2>(geo.radius, [&](auto R) {
+                return do_launch(blur_server_kernel<C, R, 4, RAG != 0>, grid, block, geo.lds, stream, ctl, dev, seq, budget, idle_ticks, trace, fixed_share);
+            });
+        });
+    });
 }
 
 int launch_fused_watch(const unsigned *count, unsigned n_batches, unsigned tiles_per_batch, unsigned total_blocks, unsigned per_block,
                        unsigned long long *host_word, unsigned pass_seq, hipStream_t stream, unsigned counters_per_batch)
 {
     if (!count || !host_word || n_batches == 0 || tiles_per_batch == 0 || counters_per_batch < 8 || (counters_per_batch & (counters_per_batch - 1))) return MI_BLUR_ERR_INVALID;
-    hipLaunchKernelGGL(fused_watch_kernel, dim3(1), dim3(64), 0, stream, count, n_batches, tiles_per_batch, total_blocks, per_block, host_word, pass_seq, counters_per_batch);
-    return hip_status(hipGetLastError());
+    return do_launch(fused_watch_kernel, dim3(1), dim3(64), 0, stream, count, n_batches, tiles_per_batch, total_blocks, per_block, host_word, pass_seq, counters_per_batch);
 }
 
 int launch_fused(const LaunchDesc &d, const FusedDesc &f)
@@ -1575,12 +1452,10 @@ int launch_fused(const LaunchDesc &d, const FusedDesc &f)
 static int launch_stream(const LaunchDesc &d, const Tunables &tun)
 {
     g_last_kernel = "blur_stream_kernel";
-    const int pitch = d.width * d.channels, cpr = pitch / 16, rows = d.y1 - d.y0;
+    const int cpr = d.width * d.channels / 16, rows = d.y1 - d.y0;
     StreamParams p{};
-    p.in = d.in; p.out = d.out;
-    p.in_stride = (long long)d.band_rows * pitch;
-    p.out_stride = (long long)rows * pitch;
-    p.pitch = pitch; p.cpr = cpr; p.H = d.band_rows; p.y0 = d.y0; p.y1 = d.y1;
+    fill_band(p, d);                                 // (strides: dense or 0 here, launch() sends the others to the tiled kernel)
+    p.cpr = cpr; p.y1 = d.y1;
     // Band height: tall bands re-read fewer halo rows (2R/BH), short ones give small grids enough waves.  A wave lives as
     // long as its band is tall and ~16 waves fit a CU, so the launch runs in "rounds" of resident waves: pick the band
     // count whose last round is fullest (a launch of 1.5 rounds runs its second half at half occupancy), weighted by the
@@ -1613,104 +1488,53 @@ static int launch_stream(const LaunchDesc &d, const Tunables &tun)
     p.updown = tun.stream_updown;
     const dim3 grid((unsigned)nblocks), block(256);
     const size_t lds = 4 * STREAM_D * STREAM_ROWB;
-    switch (d.channels * 10 + d.filter->radius) {
-    case 11: return do_launch(blur_stream_kernel<1, 1>, grid, block, lds, d, p);
-    case 12: return do_launch(blur_stream_kernel<1, 2>, grid, block, lds, d, p);
-    case 21: return do_launch(blur_stream_kernel<2, 1>, grid, block, lds, d, p);
-    case 22: return do_launch(blur_stream_kernel<2, 2>, grid, block, lds, d, p);
-    case 31: return do_launch(blur_stream_kernel<3, 1>, grid, block, lds, d, p);
-    case 32: return do_launch(blur_stream_kernel<3, 2>, grid, block, lds, d, p);
-    case 41: return do_launch(blur_stream_kernel<4, 1>, grid, block, lds, d, p);
-    case 42: return do_launch(blur_stream_kernel<4, 2>, grid, block, lds, d, p);
-    }
-    return MI_BLUR_ERR_INVALID;
+    return dispatch<1, 2, 3, 4>(d.channels, [&](auto C) {
+        return dispatch<1, 2>(d.filter->radius, [&](auto R) { return do_launch(blur_stream_kernel<C, R>, grid, block, lds, d, p); });
+    });
 }
 
-template <int BH>
-static int launch_direct_bh(const LaunchDesc &d, const Tunables &tun);
-
-// The direct kernel numbers its work in 32 bits: images x bands x chunk columns.
-static bool direct_fits(const LaunchDesc &d)
-{
-    const long long cpr = (long long)d.width * d.channels / 16, rows = d.y1 - d.y0;
-    return (long long)d.n_images * ((rows + 3) / 4) * cpr < 0x7fffffffLL;
-}
-
-static int launch_direct(const LaunchDesc &d, const Tunables &tun)
-{
-    if (d.channels == 3 && tun.direct_bh == 4) return launch_direct_bh<4>(d, tun);
-    if (d.channels == 3 && tun.direct_bh == 16) return launch_direct_bh<16>(d, tun);
-    if (d.channels == 3 && tun.direct_bh == 12) return launch_direct_bh<12>(d, tun);
-    return launch_direct_bh<8>(d, tun);
-}
-
+// BH = output rows per lane: 8; 4 | 12 | 16 exist for C = 3 only ("direct_bh", A/B runs), and without peer halo rows.
 template <int BH>
 static int launch_direct_bh(const LaunchDesc &d, const Tunables &tun)
 {
     g_last_kernel = "blur_direct_kernel";
-    const int pitch = d.width * d.channels, cpr = pitch / 16, rows = d.y1 - d.y0;
     DirectParams p{};
-    p.in = d.in; p.out = d.out;
-    p.in_stride = (long long)d.band_rows * pitch;
-    p.out_stride = (long long)rows * pitch;
-    p.pitch = pitch; p.cpr = cpr; p.H = d.band_rows; p.y0 = d.y0; p.y1 = d.y1;
-    p.nbands = (rows + BH - 1) / BH;
-    p.total = (long long)d.n_images * p.nbands * cpr;
+    fill_band(p, d);
+    p.cpr = p.pitch / 16; p.y1 = d.y1;
+    const dim3 grid = direct_grid(p, d, BH), block(256);
     if (p.total >= 0x7fffffffLL) return MI_BLUR_ERR_INVALID;
-    const long long waves = (p.total + 61) / 62, nblocks = (waves + 3) / 4;
-    p.nblocks = (unsigned)nblocks;
-    p.xcd = (tun.xcd_remap && nblocks >= 16) ? 1 : 0;
-    const dim3 grid((unsigned)nblocks), block(256);
-    if (d.halo_top || d.halo_bottom) {
-        if constexpr (BH == 8) {
+    p.xcd = (tun.xcd_remap && p.nblocks >= 16) ? 1 : 0;
+    const bool peer = d.halo_top || d.halo_bottom;
+    if constexpr (BH != 8) {
+        if (peer) return MI_BLUR_ERR_INVALID;
+        return dispatch<1, 2>(d.filter->radius, [&](auto R) { return do_launch(blur_direct_kernel<3, R, BH>, grid, block, 0, d, p); });
+    } else {
+        if (peer) {
             p.top = d.halo_top; p.bottom = d.halo_bottom;
             g_last_kernel = "blur_direct_kernel (peer halo rows)";
-            switch (d.channels * 10 + d.filter->radius) {
-            case 11: return do_launch(blur_direct_kernel<1, 1, 8, true>, grid, block, 0, d, p);
-            case 12: return do_launch(blur_direct_kernel<1, 2, 8, true>, grid, block, 0, d, p);
-            case 21: return do_launch(blur_direct_kernel<2, 1, 8, true>, grid, block, 0, d, p);
-            case 22: return do_launch(blur_direct_kernel<2, 2, 8, true>, grid, block, 0, d, p);
-            case 31: return do_launch(blur_direct_kernel<3, 1, 8, true>, grid, block, 0, d, p);
-            case 32: return do_launch(blur_direct_kernel<3, 2, 8, true>, grid, block, 0, d, p);
-            case 41: return do_launch(blur_direct_kernel<4, 1, 8, true>, grid, block, 0, d, p);
-            case 42: return do_launch(blur_direct_kernel<4, 2, 8, true>, grid, block, 0, d, p);
-            }
+            return dispatch<1, 2, 3, 4>(d.channels, [&](auto C) {
+                return dispatch<1, 2>(d.filter->radius, [&](auto R) { return do_launch(blur_direct_kernel<C, R, 8, true>, grid, block, 0, d, p); });
+            });
         }
-        return MI_BLUR_ERR_INVALID;
+        return dispatch<1, 2, 3, 4>(d.channels, [&](auto C) {
+            return dispatch<1, 2>(d.filter->radius, [&](auto R) { return do_launch(blur_direct_kernel<C, R, 8>, grid, block, 0, d, p); });
+        });
     }
-    if constexpr (BH != 8) {
-        return d.filter->radius == 1 ? do_launch(blur_direct_kernel<3, 1, BH>, grid, block, 0, d, p)
-                             : do_launch(blur_direct_kernel<3, 2, BH>, grid, block, 0, d, p);
-    } else {
-        switch (d.channels * 10 + d.filter->radius) {
-        case 11: return do_launch(blur_direct_kernel<1, 1, BH>, grid, block, 0, d, p);
-        case 12: return do_launch(blur_direct_kernel<1, 2, BH>, grid, block, 0, d, p);
-        case 21: return do_launch(blur_direct_kernel<2, 1, BH>, grid, block, 0, d, p);
-        case 22: return do_launch(blur_direct_kernel<2, 2, BH>, grid, block, 0, d, p);
-        case 31: return do_launch(blur_direct_kernel<3, 1, BH>, grid, block, 0, d, p);
-        case 32: return do_launch(blur_direct_kernel<3, 2, BH>, grid, block, 0, d, p);
-        case 41: return do_launch(blur_direct_kernel<4, 1, BH>, grid, block, 0, d, p);
-        case 42: return do_launch(blur_direct_kernel<4, 2, BH>, grid, block, 0, d, p);
-        }
-        return MI_BLUR_ERR_INVALID;
-    }
+}
+
+static int launch_direct(const LaunchDesc &d, const Tunables &tun)
+{
+    return dispatch<4, 16, 12, 8>(d.channels == 3 ? tun.direct_bh : 8, [&](auto BH) { return launch_direct_bh<BH>(d, tun); });
 }
 
 static int launch_generic(const LaunchDesc &d)
 {
     g_last_kernel = "blur_generic_kernel";
     GenericParams p{};
-    const int pitch = d.width * d.channels, rows = d.y1 - d.y0;
-    p.in = d.in; p.out = d.out;
-    p.in_stride = (long long)d.band_rows * pitch;
-    p.out_stride = (long long)rows * pitch;
+    fill_band(p, d);
     p.total = p.out_stride * d.n_images;
-    p.width = d.width; p.channels = d.channels; p.pitch = pitch; p.H = d.band_rows; p.y0 = d.y0;
-    long long blocks = (p.total + 255) / 256;
-    if (blocks > 256LL * 64) blocks = 256LL * 64;   // grid-stride the rest
-    const dim3 grid((unsigned)blocks), block(256);
-    return d.filter->radius == 1 ? do_launch(blur_generic_kernel<1>, grid, block, 0, d, p)
-                         : do_launch(blur_generic_kernel<2>, grid, block, 0, d, p);
+    p.width = d.width; p.channels = d.channels;
+    return dispatch<1, 2>(d.filter->radius, [&](auto R) { return do_launch(blur_generic_kernel<R>, byte_grid(p.total), dim3(256), 0, d, p); });
 }
 
 int launch(const LaunchDesc &d)
@@ -1718,13 +1542,9 @@ int launch(const LaunchDesc &d)
     if (!d.filter) return MI_BLUR_ERR_INVALID;
     if (d.filter->kind == FilterKind::SEP) return launch_sep(d);
     if (d.filter->kind == FilterKind::MEDIAN) return launch_median(d);
-    if (!d.in || !d.out || d.in == d.out) return MI_BLUR_ERR_INVALID;
-    if (d.width <= 0 || d.band_rows <= 0 || d.channels <= 0 || d.n_images < 0) return MI_BLUR_ERR_INVALID;
+    if (const int st = check_desc(d, FilterKind::BOX)) return st;
     if (d.filter->radius != 1 && d.filter->radius != 2) return MI_BLUR_ERR_INVALID;
-    if (d.y0 < 0 || d.y1 > d.band_rows || d.y0 >= d.y1) return MI_BLUR_ERR_INVALID;
-    if ((long long)d.width * d.channels > INT_MAX / 2) return MI_BLUR_ERR_INVALID;
-    if ((long long)d.width * d.channels * d.band_rows > INT_MAX) return MI_BLUR_ERR_INVALID;  // per-image 32-bit
-    if (d.n_images == 0) return MI_BLUR_OK;
+    if (d.n_images == 0) return MI_BLUR_OK;           // before the strides are looked at (launch_sep / launch_median: after)
     const Tunables tun = tunables();                  // one coherent set of knobs for this launch
     const bool wide = wide_channels(d.channels, d.filter->radius);
     const long long row_bytes = (long long)d.width * d.channels;
@@ -1739,11 +1559,9 @@ int launch(const LaunchDesc &d)
         Tunables t8 = tun; t8.direct_bh = 8;
         return launch_direct(d, t8);
     }
-    const long long dense_in = (long long)d.band_rows * d.width * d.channels, dense_out = (long long)(d.y1 - d.y0) * d.width * d.channels;
-    if ((d.in_stride && d.in_stride != dense_in) || (d.out_stride && d.out_stride != dense_out)) {
+    if ((d.in_stride && d.in_stride != dense_in(d)) || (d.out_stride && d.out_stride != dense_out(d))) {
         // spaced-out bands (a caller's buffer used in place): tiled kernel only
-        if (d.in_stride < 0 || d.out_stride < 0 || (d.in_stride && d.in_stride < dense_in) || (d.out_stride && d.out_stride < dense_out))
-            return MI_BLUR_ERR_INVALID;
+        if (strides_too_small(d)) return MI_BLUR_ERR_INVALID;
         if (!can_tile || d.in_stride % 16 || d.out_stride % 16) return MI_BLUR_ERR_UNSUPPORTED;
         if (d.variant != MI_BLUR_VARIANT_AUTO && d.variant != MI_BLUR_VARIANT_TILED) return MI_BLUR_ERR_UNSUPPORTED;
         return launch_tiled(d, tun);
@@ -1762,7 +1580,7 @@ int launch(const LaunchDesc &d)
         // Zero-copy submits keep the capped-grid tiled kernel.
         if (direct_fits(d) && d.max_blocks <= 0 &&
             (tun.prefer_direct == 2 ||
-             (tun.prefer_direct == 1 && (d.filter->radius == 2 || (dense_out * d.n_images <= (128LL << 20) && d.concurrent <= 1)))))
+             (tun.prefer_direct == 1 && (d.filter->radius == 2 || (dense_out(d) * d.n_images <= (128LL << 20) && d.concurrent <= 1)))))
             return launch_direct(d, tun);
         return launch_tiled(d, tun);
     case MI_BLUR_VARIANT_GENERIC: return launch_generic(d);

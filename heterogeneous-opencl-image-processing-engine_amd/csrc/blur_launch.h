@@ -1,5 +1,5 @@
 // blur_launch.h — internal (not part of the C ABI): launch interface between
-// mi_blur_api.cpp and the gfx950 kernels in blur_kernels.hip.
+// mi_blur_api.cpp and the gfx950 kernels in the four .hip files (what those share among themselves: kernel_common.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -125,8 +125,8 @@ const char *last_kernel();
 // True when the LDS-tiled vector kernel can take this shape.
 bool tiled_eligible(const void *in, const void *out, int width, int channels);
 
-// Tunables: defaults from env (MI_BLUR_STAGE=dma|reg, MI_BLUR_RPG=4|8|16, MI_BLUR_XCD=0|1), changeable at run time
-// through mi_blur_set_option.  Process-wide, kept behind a mutex: tunables() returns a coherent COPY and every launch
+// Tunables: defaults and their environment variables (MI_BLUR_STAGE=dma|reg, MI_BLUR_RPG=4|8|16, MI_BLUR_XCD=0|1, ...) from
+// the KNOBS table below, changeable at run time through mi_blur_set_option.  Process-wide, kept behind a mutex: tunables() returns a coherent COPY and every launch
 // works from the one copy it took when it started, so flipping a knob while another thread launches is not a data race
 // (that launch sees the old set or the new one, never a mix).
 struct Tunables {
@@ -163,6 +163,61 @@ struct Tunables {
     int zero_copy_events; // zero-copy submits: 1 = the dispatch carries start/stop timestamp events (kernel bucket + completion),
                          // 0 = plain launch, completion by stream synchronise (timing experiment: no kernel bucket)
 };
+// Every knob once: its mi_blur_set_option key, its field, what values it takes, its default and the environment variable
+// (or nullptr) that may replace the default when the library starts.  FLAG: any value, stored as 0 | 1.  RANGE: lo .. hi.
+// ONE_OF: the values whose bit is set in lo (all below 31).  tunables_storage() (blur_kernels.hip) builds the defaults and
+// reads the environment from this table — a value it does not accept is ignored — and mi_blur_set_option looks its key up here.
+enum class KnobKind { FLAG, RANGE, ONE_OF };
+struct Knob { const char *key; int Tunables::*field; KnobKind kind; int lo, hi, def; const char *env; };
+constexpr int knob_bits(int a, int b, int c, int d) { return 1 << a | 1 << b | 1 << c | 1 << d; }
+static constexpr Knob KNOBS[] = {
+    {"stage_dma", &Tunables::stage_dma, KnobKind::FLAG, 0, 1, 1, "MI_BLUR_STAGE"},        // the variable also takes "dma" | "reg"
+    {"rows_per_thread", &Tunables::rpg, KnobKind::ONE_OF, knob_bits(0, 4, 8, 16), 0, 0, "MI_BLUR_RPG"},   // 0 = choose per launch
+    {"xcd_remap", &Tunables::xcd_remap, KnobKind::FLAG, 0, 1, 1, "MI_BLUR_XCD"},
+    {"debug_copy", &Tunables::debug_copy, KnobKind::FLAG, 0, 1, 0, nullptr},              // ablation only (output is NOT a blur)
+    {"row_shuffle", &Tunables::row_shuffle, KnobKind::FLAG, 0, 1, 0, nullptr},
+    {"prefer_stream", &Tunables::prefer_stream, KnobKind::FLAG, 0, 1, 0, nullptr},
+    {"zero_copy", &Tunables::zero_copy, KnobKind::FLAG, 0, 1, 1, nullptr},
+    {"ragged_tiled", &Tunables::ragged, KnobKind::FLAG, 0, 1, 1, nullptr},
+    {"stream_band_rows", &Tunables::stream_bh, KnobKind::RANGE, 0, 4096, 0, nullptr},     // 0 = choose per launch
+    {"fused_release", &Tunables::fused_release, KnobKind::FLAG, 0, 1, 0, nullptr},
+    {"experiment", &Tunables::experiment, KnobKind::FLAG, 0, 1, 0, nullptr},
+    {"stream_updown", &Tunables::stream_updown, KnobKind::FLAG, 0, 1, 1, nullptr},
+    {"zero_copy_streams", &Tunables::zero_copy_streams, KnobKind::RANGE, 1, 8, 4, nullptr},
+    {"zero_copy_blocks", &Tunables::zero_copy_blocks, KnobKind::RANGE, 0, 1 << 20, 24, nullptr},
+    {"prefer_direct", &Tunables::prefer_direct, KnobKind::RANGE, 0, 2, 1, "MI_BLUR_DIRECT"},
+    {"direct_bh", &Tunables::direct_bh, KnobKind::ONE_OF, knob_bits(4, 8, 12, 16), 0, 8, nullptr},
+    {"fused_adds_per_word", &Tunables::fused_adds_per_word, KnobKind::RANGE, 4, 4096, 32, nullptr},
+    {"fused_tail_blocks", &Tunables::fused_tail_blocks, KnobKind::RANGE, 10, 800, 25, nullptr},
+    {"fused_tail", &Tunables::fused_tail, KnobKind::RANGE, 0, 500, 30, "MI_BLUR_FUSED_TAIL"},
+    {"fused_window", &Tunables::fused_window, KnobKind::RANGE, 1, 4096, 8, nullptr},
+    {"debug_xcd_times", &Tunables::debug_xcd_times, KnobKind::FLAG, 0, 1, 0, nullptr},
+    {"zero_copy_events", &Tunables::zero_copy_events, KnobKind::FLAG, 0, 1, 1, nullptr},
+    {"zero_copy_server", &Tunables::zero_copy_server, KnobKind::FLAG, 0, 1, 1, nullptr},
+    {"staged_server", &Tunables::staged_server, KnobKind::FLAG, 0, 1, 1, "MI_BLUR_STAGED_SERVER"},
+    {"zero_copy_server_min_kb", &Tunables::zero_copy_server_min_kb, KnobKind::RANGE, 0, 1 << 20, 1280, nullptr},
+    {"zero_copy_trace", &Tunables::zero_copy_trace, KnobKind::FLAG, 0, 1, 0, nullptr},
+    {"zero_copy_tickets", &Tunables::zero_copy_tickets, KnobKind::FLAG, 0, 1, 1, nullptr},
+    {"zero_copy_spin", &Tunables::zero_copy_spin, KnobKind::FLAG, 0, 1, 0, nullptr},
+    {"zero_copy_debug_base", &Tunables::zero_copy_debug_base, KnobKind::RANGE, 0, 1 << 20, 0, nullptr},
+    {"resident_place_trials", &Tunables::resident_place_trials, KnobKind::RANGE, 0, 8, 4, "MI_BLUR_PLACE_TRIALS"},
+    {"zero_copy_workers", &Tunables::zero_copy_workers, KnobKind::RANGE, 1, 2048, 48, nullptr},
+    {"zero_copy_idle_us", &Tunables::zero_copy_idle_us, KnobKind::RANGE, 10, 100000, 300, nullptr},
+    {"zero_copy_budget", &Tunables::zero_copy_budget, KnobKind::RANGE, 1, 1 << 20, 256, nullptr},
+    {"xcd_run", &Tunables::xcd_run, KnobKind::RANGE, 0, 1 << 20, 0, nullptr},
+};
+// Stores `value` in the knob's field of t if the knob accepts it; false (t untouched) otherwise.
+static inline bool knob_set(const Knob &k, Tunables &t, int value)
+{
+    switch (k.kind) {
+    case KnobKind::FLAG: t.*k.field = value != 0; return true;
+    case KnobKind::RANGE: if (value < k.lo || value > k.hi) return false; break;
+    case KnobKind::ONE_OF: if (value < 0 || value > 30 || !((k.lo >> value) & 1)) return false; break;
+    }
+    t.*k.field = value;
+    return true;
+}
+
 Tunables tunables();
 unsigned long long *debug_xcd_buffer();
 unsigned debug_xcd_slots();

@@ -14,14 +14,9 @@
 // W*H not a multiple of 16 (or C > 4, or unaligned pointers) takes a byte-per-thread kernel.
 // (A planar stream can also be blurred with no repack at all: it IS a stream of n*C one-channel images —
 // mi_blur_enqueue(..., channels = 1, n_images = n*C); see INTEGRATION.md.)
-#include "blur_launch.h"
-#include "../../include/mi_blur.h"
-
-#include <limits.h>
+#include "kernel_common.h"
 
 namespace mi_blur {
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // One 4-pixel group: in[c] / out[k] are dwords.  P2I: in[c] = 4 consecutive bytes of plane c, out = the 4*C
 // interleaved bytes (out byte j = plane j%C, pixel j/C).  !P2I: in = 4*C interleaved bytes, out[c] = plane c.
@@ -130,8 +125,6 @@ __global__ __launch_bounds__(256) void repack_bytes_kernel(const LayoutParams p)
     }
 }
 
-static inline int hip_status(hipError_t e) { return e == hipSuccess ? MI_BLUR_OK : MI_BLUR_ERR_HIP_BASE - (int)e; }
-
 template <bool P2I>
 static int repack(const uint8_t *src, uint8_t *dst, int width, int height, int channels, int n_images, hipStream_t stream)
 {
@@ -146,19 +139,9 @@ static int repack(const uint8_t *src, uint8_t *dst, int width, int height, int c
         p.groups = p.plane / 16 * n_images;
         const long long blocks = (p.groups + 255) / 256;
         if (blocks > 0x7fffffffLL) return MI_BLUR_ERR_INVALID;
-        const dim3 grid((unsigned)blocks), block(256);
-        switch (channels) {
-        case 1: hipLaunchKernelGGL((repack16_kernel<1, P2I>), grid, block, 0, stream, p); break;
-        case 2: hipLaunchKernelGGL((repack16_kernel<2, P2I>), grid, block, 0, stream, p); break;
-        case 3: hipLaunchKernelGGL((repack16_kernel<3, P2I>), grid, block, 0, stream, p); break;
-        case 4: hipLaunchKernelGGL((repack16_kernel<4, P2I>), grid, block, 0, stream, p); break;
-        }
-    } else {
-        long long blocks = (p.total_bytes + 255) / 256;
-        if (blocks > 256LL * 64) blocks = 256LL * 64;
-        hipLaunchKernelGGL((repack_bytes_kernel<P2I>), dim3((unsigned)blocks), dim3(256), 0, stream, p);
+        return dispatch<1, 2, 3, 4>(channels, [&](auto C) { return do_launch(repack16_kernel<C, P2I>, dim3((unsigned)blocks), dim3(256), 0, stream, p); });
     }
-    return hip_status(hipGetLastError());
+    return do_launch(repack_bytes_kernel<P2I>, byte_grid(p.total_bytes), dim3(256), 0, stream, p);
 }
 
 // Halo pull (mi_blur_halo_pull): up to two runs of `bytes` bytes, each from a (peer) source into this rank's halo rows.
@@ -185,8 +168,7 @@ int launch_halo_pull(const uint8_t *top_src, uint8_t *top_dst, const uint8_t *bo
     PullParams p{};
     p.src[0] = top_src; p.dst[0] = top_dst; p.src[1] = bottom_src; p.dst[1] = bottom_dst; p.bytes = bytes;
     const unsigned blocks = (unsigned)((bytes + 16 * 256 - 1) / (16 * 256));
-    hipLaunchKernelGGL(halo_pull_kernel, dim3(blocks, 2), dim3(256), 0, stream, p);
-    return hip_status(hipGetLastError());
+    return do_launch(halo_pull_kernel, dim3(blocks, 2), dim3(256), 0, stream, p);
 }
 
 int launch_planar_to_interleaved(const uint8_t *src, uint8_t *dst, int w, int h, int c, int n, hipStream_t s) { return repack<true>(src, dst, w, h, c, n, s); }

@@ -4,7 +4,7 @@
 // exact count), so all of them agree with the CPU device byte for byte.
 //
 // Fast kernel (blur_median_fast_kernel<C, R>), radius 1 and 2: rows of whole 16-byte chunks, 16-byte aligned buffers and
-// strides, 1-4 channels.  The direct kernel's layout (blur_kernels.hip): a lane owns one 16-byte chunk column and BH (8 | 4)
+// strides, 1-4 channels.  The direct kernel's layout (blur_kernels.hip; its host side is shared, kernel_common.h): a lane owns one 16-byte chunk column and BH (8 | 4)
 // output rows, loads the BH + 2R rows of it straight into registers, takes the 8 bytes either side from the
 // neighbouring lanes (DPP wave shifts; lanes 0 and 63 only supply them, 62 lanes per wave compute), and replaces them by
 // copies of the edge pixel's channels at the row ends (one v_perm of its own first / last dword).  No LDS, no barrier.
@@ -22,13 +22,8 @@
 // Generic kernel (blur_median_generic_kernel<R>): one output byte per thread, any shape, radius 1..7.  The window is held in
 // registers as 16-bit fields, two per dword, and the result found bit by bit from the top: t = ans | bit is kept when at
 // most k window values are below t, counted two fields per subtraction.  Correct everywhere, fast nowhere.
-#include "blur_launch.h"
-#include "../../include/mi_blur.h"
+#include "kernel_common.h"
 
-#include <hip/hip_ext.h>
-#include <limits.h>
-#include <stdint.h>
-#include <type_traits>
 #include <utility>
 
 namespace mi_blur {
@@ -37,8 +32,6 @@ namespace {
 
 constexpr int med_bh(int R) { return R == 1 ? 8 : 4; }   // output rows per lane, fast kernel (radius 2: registers)
 constexpr uint32_t MED_PAD = 0xffffffffu;
-
-typedef unsigned int med_u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ uint32_t mn(uint32_t a, uint32_t b) { return a < b ? a : b; }
 __device__ __forceinline__ uint32_t mx(uint32_t a, uint32_t b) { return a < b ? b : a; }
@@ -95,13 +88,6 @@ struct MedFastParams {
     int xcd;
 };
 
-// blockIdx -> work block: blocks b and b+8 share an XCD (round-robin dispatch); one contiguous eighth per XCD.
-__device__ __forceinline__ unsigned med_xcd_contiguous(unsigned L, unsigned n)
-{
-    const unsigned q = n >> 3, r = n & 7u, x = L & 7u, k = L >> 3;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + k;
-}
-
 // v_perm_b32 selector that fills a halo dword from the edge dword x of the row (same channel, position mod C).
 // LEFT: halo dword h (0: row bytes -8..-5, 1: -4..-1) from the row's first dword; right: h (0: bytes 16..19 of the last
 // chunk, 1: 20..23) from its last dword.
@@ -136,7 +122,8 @@ __global__ __launch_bounds__(256) void blur_median_fast_kernel(const MedFastPara
 {
     constexpr int NR = BH + 2 * R, HB = R * C;          // rows loaded, halo bytes used either side
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned B = p.xcd ? med_xcd_contiguous(blockIdx.x, p.nblocks) : blockIdx.x;
+    const unsigned B = p.xcd ? xcd_contiguous(blockIdx.x, p.nblocks) : blockIdx.x;
+    // (this lane decode and the DPP window below have a twin in blur_direct_kernel: a shared helper changed the generated code)
     const long long fl = (long long)(B * 4u + (unsigned)wave) * 62 - 1 + lane;
     const bool inrange = fl >= 0 && fl < p.total;
     const unsigned f = (unsigned)(fl < 0 ? 0 : (fl >= p.total ? p.total - 1 : fl));
@@ -229,12 +216,12 @@ __global__ __launch_bounds__(256) void blur_median_fast_kernel(const MedFastPara
             }
         }
         if (i < rows_out) {
-            med_u32x4 st;
+            u32x4 st;
             st.x = o[0] | (o[1] << 8) | (o[2] << 16) | (o[3] << 24);
             st.y = o[4] | (o[5] << 8) | (o[6] << 16) | (o[7] << 24);
             st.z = o[8] | (o[9] << 8) | (o[10] << 16) | (o[11] << 24);
             st.w = o[12] | (o[13] << 8) | (o[14] << 16) | (o[15] << 24);
-            *reinterpret_cast<med_u32x4 *>(dst + (size_t)i * (size_t)p.pitch) = st;
+            *reinterpret_cast<u32x4 *>(dst + (size_t)i * (size_t)p.pitch) = st;
         }
     };
     med_unrolled(out_row, std::make_integer_sequence<int, BH>{});
@@ -289,93 +276,44 @@ __global__ __launch_bounds__(256) void blur_median_generic_kernel(const MedGener
     }
 }
 
-inline int med_hip_status(hipError_t e) { return e == hipSuccess ? MI_BLUR_OK : MI_BLUR_ERR_HIP_BASE - (int)e; }
-
-template <typename K, typename P>
-int med_do_launch(K kernel, dim3 grid, dim3 block, const LaunchDesc &d, const P &params)
-{
-    if (d.start || d.stop)
-        hipExtLaunchKernelGGL(kernel, grid, block, 0, d.stream, d.start, d.stop, 0, params);
-    else
-        hipLaunchKernelGGL(kernel, grid, block, 0, d.stream, params);
-    return med_hip_status(hipGetLastError());
-}
-
 int launch_median_fast(const LaunchDesc &d)
 {
     set_last_kernel("blur_median_fast_kernel");
-    const int pitch = d.width * d.channels, cpr = pitch / 16, rows = d.y1 - d.y0;
     MedFastParams p{};
-    p.in = d.in; p.out = d.out;
-    p.in_stride = d.in_stride ? d.in_stride : (long long)d.band_rows * pitch;
-    p.out_stride = d.out_stride ? d.out_stride : (long long)rows * pitch;
-    p.pitch = pitch; p.cpr = cpr; p.H = d.band_rows; p.y0 = d.y0; p.y1 = d.y1;
-    const int bh = med_bh(d.filter->radius);
-    p.nbands = (rows + bh - 1) / bh;
-    p.total = (long long)d.n_images * p.nbands * cpr;
-    const long long waves = (p.total + 61) / 62, nblocks = (waves + 3) / 4;
-    p.nblocks = (unsigned)nblocks;
-    p.xcd = nblocks >= 16 ? 1 : 0;
-    const dim3 grid((unsigned)nblocks), block(256);
-    switch (d.channels * 10 + d.filter->radius) {
-    case 11: return med_do_launch(blur_median_fast_kernel<1, 1, med_bh(1)>, grid, block, d, p);
-    case 12: return med_do_launch(blur_median_fast_kernel<1, 2, med_bh(2)>, grid, block, d, p);
-    case 21: return med_do_launch(blur_median_fast_kernel<2, 1, med_bh(1)>, grid, block, d, p);
-    case 22: return med_do_launch(blur_median_fast_kernel<2, 2, med_bh(2)>, grid, block, d, p);
-    case 31: return med_do_launch(blur_median_fast_kernel<3, 1, med_bh(1)>, grid, block, d, p);
-    case 32: return med_do_launch(blur_median_fast_kernel<3, 2, med_bh(2)>, grid, block, d, p);
-    case 41: return med_do_launch(blur_median_fast_kernel<4, 1, med_bh(1)>, grid, block, d, p);
-    case 42: return med_do_launch(blur_median_fast_kernel<4, 2, med_bh(2)>, grid, block, d, p);
-    }
-    return MI_BLUR_ERR_INVALID;
+    fill_band(p, d);
+    p.cpr = p.pitch / 16; p.y1 = d.y1;
+    const dim3 grid = direct_grid(p, d, med_bh(d.filter->radius)), block(256);
+    p.xcd = p.nblocks >= 16 ? 1 : 0;
+    return dispatch<1, 2, 3, 4>(d.channels, [&](auto C) {
+        return dispatch<1, 2>(d.filter->radius, [&](auto R) { return do_launch(blur_median_fast_kernel<C, R, med_bh(R)>, grid, block, 0, d, p); });
+    });
 }
 
 int launch_median_generic(const LaunchDesc &d)
 {
     set_last_kernel("blur_median_generic_kernel");
-    const int pitch = d.width * d.channels, rows = d.y1 - d.y0;
     MedGenericParams p{};
-    p.in = d.in; p.out = d.out;
-    p.block = (long long)rows * pitch;
-    p.in_stride = d.in_stride ? d.in_stride : (long long)d.band_rows * pitch;
-    p.out_stride = d.out_stride ? d.out_stride : p.block;
+    fill_band(p, d);
+    p.block = dense_out(d);
     p.total = p.block * d.n_images;
-    p.width = d.width; p.channels = d.channels; p.pitch = pitch; p.H = d.band_rows; p.y0 = d.y0;
-    long long blocks = (p.total + 255) / 256;
-    if (blocks > 256LL * 64) blocks = 256LL * 64;       // grid-stride the rest
-    const dim3 grid((unsigned)blocks), block(256);
-    switch (d.filter->radius) {
-    case 1: return med_do_launch(blur_median_generic_kernel<1>, grid, block, d, p);
-    case 2: return med_do_launch(blur_median_generic_kernel<2>, grid, block, d, p);
-    case 3: return med_do_launch(blur_median_generic_kernel<3>, grid, block, d, p);
-    case 4: return med_do_launch(blur_median_generic_kernel<4>, grid, block, d, p);
-    case 5: return med_do_launch(blur_median_generic_kernel<5>, grid, block, d, p);
-    case 6: return med_do_launch(blur_median_generic_kernel<6>, grid, block, d, p);
-    case 7: return med_do_launch(blur_median_generic_kernel<7>, grid, block, d, p);
-    }
-    return MI_BLUR_ERR_INVALID;
+    p.width = d.width; p.channels = d.channels;
+    return dispatch<1, 2, 3, 4, 5, 6, 7>(d.filter->radius, [&](auto R) {
+        return do_launch(blur_median_generic_kernel<R>, byte_grid(p.total), dim3(256), 0, d, p);
+    });
 }
 
 }  // namespace
 
 int launch_median(const LaunchDesc &d)
 {
-    if (!d.filter || d.filter->kind != FilterKind::MEDIAN || !d.in || !d.out || d.in == d.out) return MI_BLUR_ERR_INVALID;
-    if (d.width <= 0 || d.band_rows <= 0 || d.channels <= 0 || d.n_images < 0) return MI_BLUR_ERR_INVALID;
+    if (const int st = check_desc(d, FilterKind::MEDIAN)) return st;
     if (d.filter->radius < 1 || d.filter->radius > MI_BLUR_MEDIAN_MAX_RADIUS) return MI_BLUR_ERR_INVALID;
-    if (d.y0 < 0 || d.y1 > d.band_rows || d.y0 >= d.y1) return MI_BLUR_ERR_INVALID;
-    if ((long long)d.width * d.channels > INT_MAX / 2) return MI_BLUR_ERR_INVALID;
-    if ((long long)d.width * d.channels * d.band_rows > INT_MAX) return MI_BLUR_ERR_INVALID;  // per-image 32-bit
     if (d.halo_top || d.halo_bottom) return MI_BLUR_ERR_UNSUPPORTED;
+    if (strides_too_small(d)) return MI_BLUR_ERR_INVALID;
+    if (d.n_images == 0) return MI_BLUR_OK;             // after the strides (launch(): before)
     const long long pitch = (long long)d.width * d.channels;
-    const long long dense_in = (long long)d.band_rows * pitch, dense_out = (long long)(d.y1 - d.y0) * pitch;
-    if (d.in_stride < 0 || d.out_stride < 0 || (d.in_stride && d.in_stride < dense_in) || (d.out_stride && d.out_stride < dense_out))
-        return MI_BLUR_ERR_INVALID;
-    if (d.n_images == 0) return MI_BLUR_OK;
-    // the fast kernel numbers its work (images x row bands x chunk columns) in 32 bits
-    const long long fast_work = (long long)d.n_images * ((d.y1 - d.y0 + 3) / 4) * (pitch / 16);
     const bool fast = d.filter->radius <= 2 && d.channels <= 4 && pitch % 16 == 0 && (uintptr_t)d.in % 16 == 0 &&
-                      (uintptr_t)d.out % 16 == 0 && d.in_stride % 16 == 0 && d.out_stride % 16 == 0 && fast_work < 0x7fffffffLL;
+                      (uintptr_t)d.out % 16 == 0 && d.in_stride % 16 == 0 && d.out_stride % 16 == 0 && direct_fits(d);
     return fast ? launch_median_fast(d) : launch_median_generic(d);
 }
 

@@ -87,41 +87,8 @@ extern "C" int mi_blur_set_option(const char *key, int value)
 {
     if (!key) return MI_BLUR_ERR_INVALID;
     Tunables t = tunables();      // copy, edit, publish: launches in other threads see the old set or the new one
-    if (!strcmp(key, "stage_dma")) t.stage_dma = value != 0;
-    else if (!strcmp(key, "rows_per_thread")) { if (value != 0 && value != 4 && value != 8 && value != 16) return MI_BLUR_ERR_INVALID; t.rpg = value; }
-    else if (!strcmp(key, "xcd_remap")) t.xcd_remap = value != 0;
-    else if (!strcmp(key, "debug_copy")) t.debug_copy = value != 0;   // ablation only (output is NOT a blur)
-    else if (!strcmp(key, "row_shuffle")) t.row_shuffle = value != 0;
-    else if (!strcmp(key, "prefer_stream")) t.prefer_stream = value != 0;
-    else if (!strcmp(key, "zero_copy")) t.zero_copy = value != 0;
-    else if (!strcmp(key, "ragged_tiled")) t.ragged = value != 0;
-    else if (!strcmp(key, "stream_band_rows")) { if (value < 0 || value > 4096) return MI_BLUR_ERR_INVALID; t.stream_bh = value; }
-    else if (!strcmp(key, "fused_release")) t.fused_release = value != 0;
-    else if (!strcmp(key, "experiment")) t.experiment = value != 0;
-    else if (!strcmp(key, "stream_updown")) t.stream_updown = value != 0;
-    else if (!strcmp(key, "zero_copy_streams")) { if (value < 1 || value > 8) return MI_BLUR_ERR_INVALID; t.zero_copy_streams = value; }
-    else if (!strcmp(key, "zero_copy_blocks")) { if (value < 0 || value > (1 << 20)) return MI_BLUR_ERR_INVALID; t.zero_copy_blocks = value; }
-    else if (!strcmp(key, "prefer_direct")) { if (value < 0 || value > 2) return MI_BLUR_ERR_INVALID; t.prefer_direct = value; }
-    else if (!strcmp(key, "direct_bh")) { if (value != 4 && value != 8 && value != 12 && value != 16) return MI_BLUR_ERR_INVALID; t.direct_bh = value; }
-    else if (!strcmp(key, "fused_adds_per_word")) { if (value < 4 || value > 4096) return MI_BLUR_ERR_INVALID; t.fused_adds_per_word = value; }
-    else if (!strcmp(key, "fused_tail_blocks")) { if (value < 10 || value > 800) return MI_BLUR_ERR_INVALID; t.fused_tail_blocks = value; }
-    else if (!strcmp(key, "fused_tail")) { if (value < 0 || value > 500) return MI_BLUR_ERR_INVALID; t.fused_tail = value; }
-    else if (!strcmp(key, "fused_window")) { if (value < 1 || value > 4096) return MI_BLUR_ERR_INVALID; t.fused_window = value; }
-    else if (!strcmp(key, "debug_xcd_times")) t.debug_xcd_times = value != 0;
-    else if (!strcmp(key, "zero_copy_events")) t.zero_copy_events = value != 0;
-    else if (!strcmp(key, "zero_copy_server")) t.zero_copy_server = value != 0;
-    else if (!strcmp(key, "staged_server")) t.staged_server = value != 0;
-    else if (!strcmp(key, "zero_copy_server_min_kb")) { if (value < 0 || value > (1 << 20)) return MI_BLUR_ERR_INVALID; t.zero_copy_server_min_kb = value; }
-    else if (!strcmp(key, "zero_copy_trace")) t.zero_copy_trace = value != 0;
-    else if (!strcmp(key, "zero_copy_tickets")) t.zero_copy_tickets = value != 0;
-    else if (!strcmp(key, "zero_copy_spin")) t.zero_copy_spin = value != 0;
-    else if (!strcmp(key, "zero_copy_debug_base")) { if (value < 0 || value > (1 << 20)) return MI_BLUR_ERR_INVALID; t.zero_copy_debug_base = value; }
-    else if (!strcmp(key, "resident_place_trials")) { if (value < 0 || value > 8) return MI_BLUR_ERR_INVALID; t.resident_place_trials = value; }
-    else if (!strcmp(key, "zero_copy_workers")) { if (value < 1 || value > 2048) return MI_BLUR_ERR_INVALID; t.zero_copy_workers = value; }
-    else if (!strcmp(key, "zero_copy_idle_us")) { if (value < 10 || value > 100000) return MI_BLUR_ERR_INVALID; t.zero_copy_idle_us = value; }
-    else if (!strcmp(key, "zero_copy_budget")) { if (value < 1 || value > (1 << 20)) return MI_BLUR_ERR_INVALID; t.zero_copy_budget = value; }
-    else if (!strcmp(key, "xcd_run")) { if (value < 0 || value > (1 << 20)) return MI_BLUR_ERR_INVALID; t.xcd_run = value; }
-    else return MI_BLUR_ERR_INVALID;
+    const Knob *k = std::find_if(std::begin(KNOBS), std::end(KNOBS), [&](const Knob &r) { return !strcmp(r.key, key); });
+    if (k == std::end(KNOBS) || !knob_set(*k, t, value)) return MI_BLUR_ERR_INVALID;
     set_tunables(t);
     return MI_BLUR_OK;
 }

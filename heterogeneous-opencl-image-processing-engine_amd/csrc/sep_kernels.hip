@@ -23,12 +23,8 @@
 //
 // Generic kernel (blur_sep_generic_kernel): one output byte per thread, any shape, runtime taps.  Correct everywhere,
 // fast nowhere.
-#include "blur_launch.h"
-#include "../../include/mi_blur.h"
+#include "kernel_common.h"
 
-#include <hip/hip_ext.h>
-#include <limits.h>
-#include <stdint.h>
 #include <algorithm>
 #include <utility>
 
@@ -36,10 +32,8 @@ namespace mi_blur {
 
 namespace {
 
-typedef unsigned short sep_u16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int sep_u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ sep_u16x2 pk16(uint32_t x) { return __builtin_bit_cast(sep_u16x2, x); }
-__device__ __forceinline__ uint32_t pk32(sep_u16x2 x) { return __builtin_bit_cast(uint32_t, x); }
+__device__ __forceinline__ u16x2 pk16(uint32_t x) { return __builtin_bit_cast(u16x2, x); }
+__device__ __forceinline__ uint32_t pk32(u16x2 x) { return __builtin_bit_cast(uint32_t, x); }
 
 constexpr int SEP_TH = 32;          // output rows per tile
 constexpr int SEP_RPG = 8;          // output rows per thread in the vertical pass
@@ -62,13 +56,6 @@ struct SepTiledParams {
     unsigned wy2[2 * SEP_MAX_R + 1];  // centred vertical taps, the weight in both 16-bit halves
 };
 
-// blockIdx -> tile: blocks b and b+8 share an XCD (round-robin dispatch); one contiguous eighth of the tiles per XCD.
-__device__ __forceinline__ unsigned sep_xcd_contiguous(unsigned L, unsigned n)
-{
-    const unsigned q = n >> 3, r = n & 7u, x = L & 7u, k = L >> 3;
-    return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + k;
-}
-
 // Field pair at byte offset K from the PI-parity bytes of output dword I, out of the window of 16-bit sums: E[j] / O[j]
 // hold the sums of window bytes 4j, 4j+2 / 4j+1, 4j+3, the window starting HC chunks left of the output chunk.
 template <int HC, int K, int PI, int I, int N>
@@ -90,7 +77,7 @@ __device__ __forceinline__ void sep_htap(const uint32_t (&E)[N], const uint32_t 
 {
     if (D < -rx || D > rx) return;                      // uniform
     const uint32_t w = wx[SEP_MAX_R + D];
-    const sep_u16x2 wl = pk16(w), wh = pk16(w << 16);
+    const u16x2 wl = pk16(w), wh = pk16(w << 16);
     auto mac = [&](uint32_t f, int PI, int I) {
         lo[PI][I] = __builtin_amdgcn_udot2(pk16(f), wl, lo[PI][I], false);
         hi[PI][I] = __builtin_amdgcn_udot2(pk16(f), wh, hi[PI][I], false);
@@ -114,7 +101,7 @@ __global__ __launch_bounds__(SEP_THREADS) void blur_sep_tiled_kernel(const SepTi
     constexpr int NW = 4 * (2 * HC + 1);            // window dwords per parity
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const int t = threadIdx.x;
-    const unsigned L = p.xcd ? sep_xcd_contiguous(blockIdx.x, p.nblocks) : blockIdx.x;
+    const unsigned L = p.xcd ? xcd_contiguous(blockIdx.x, p.nblocks) : blockIdx.x;
     const int strip = (int)(L % (unsigned)p.nstrips);
     const unsigned t2 = L / (unsigned)p.nstrips;
     const int ty = (int)(t2 % (unsigned)p.ntiles_y);
@@ -198,7 +185,7 @@ __global__ __launch_bounds__(SEP_THREADS) void blur_sep_tiled_kernel(const SepTi
             for (int m = 0; m < SEP_RPG; m++) {
                 const int j = e - m;                    // tap index 0..2ry of this row for output row g*RPG + m (uniform)
                 if (j >= 0 && j <= 2 * ry) {
-                    const sep_u16x2 w = pk16(p.wy2[SEP_MAX_R - ry + j]);
+                    const u16x2 w = pk16(p.wy2[SEP_MAX_R - ry + j]);
 #pragma unroll
                     for (int k = 0; k < 8; k++) acc[m][k] = pk32(pk16(f[k]) * w + pk16(acc[m][k]));
                 }
@@ -236,8 +223,8 @@ __global__ __launch_bounds__(SEP_THREADS) void blur_sep_tiled_kernel(const SepTi
         for (int I = 0; I < 4; I++)                     // bytes 4I, 4I+1, 4I+2, 4I+3 = even lo, odd lo, even hi, odd hi
             o[I] = (lo[0][I] >> shift) | ((lo[1][I] >> shift) << 8) | ((hi[0][I] >> shift) << 16) | ((hi[1][I] >> shift) << 24);
         uint8_t *op = out_img + (size_t)(ty0 - p.y0 + k) * (size_t)p.pitch + (size_t)(x0c + col) * 16u;
-        sep_u32x4 v; v.x = o[0]; v.y = o[1]; v.z = o[2]; v.w = o[3];
-        *reinterpret_cast<sep_u32x4 *>(op) = v;
+        u32x4 v; v.x = o[0]; v.y = o[1]; v.z = o[2]; v.w = o[3];
+        *reinterpret_cast<u32x4 *>(op) = v;
     }
 }
 
@@ -275,41 +262,15 @@ __global__ __launch_bounds__(256) void blur_sep_generic_kernel(const SepGenericP
     }
 }
 
-inline int sep_hip_status(hipError_t e) { return e == hipSuccess ? MI_BLUR_OK : MI_BLUR_ERR_HIP_BASE - (int)e; }
-
-template <typename K, typename P>
-int sep_do_launch(K kernel, dim3 grid, dim3 block, size_t lds, const LaunchDesc &d, const P &params)
-{
-    if (d.start || d.stop)
-        hipExtLaunchKernelGGL(kernel, grid, block, lds, d.stream, d.start, d.stop, 0, params);
-    else
-        hipLaunchKernelGGL(kernel, grid, block, lds, d.stream, params);
-    return sep_hip_status(hipGetLastError());
-}
-
-template <int C>
-int launch_sep_tiled_c(const LaunchDesc &d, const SepTiledParams &p, dim3 grid, int rb)
-{
-    auto lds_of = [&](int HC) {
-        const int ncw = p.ncols + 2 * HC;               // sums: SEP_TH rows x ncw chunks x 32 B >= the staged bytes
-        return (size_t)SEP_TH * ncw * 32u;
-    };
-    const dim3 block(SEP_THREADS);
-    if (rb == 4) return sep_do_launch(blur_sep_tiled_kernel<C, 4>, grid, block, lds_of(sep_halo_chunks(C, 4)), d, p);
-    if (rb == 8) return sep_do_launch(blur_sep_tiled_kernel<C, 8>, grid, block, lds_of(sep_halo_chunks(C, 8)), d, p);
-    return sep_do_launch(blur_sep_tiled_kernel<C, 16>, grid, block, lds_of(sep_halo_chunks(C, 16)), d, p);
-}
-
 int launch_sep_tiled(const LaunchDesc &d)
 {
     set_last_kernel("blur_sep_tiled_kernel");
     const SepTaps &k = d.filter->taps;
-    const int pitch = d.width * d.channels, cpr = pitch / 16, rows = d.y1 - d.y0;
+    const int rows = d.y1 - d.y0;
     SepTiledParams p{};
-    p.in = d.in; p.out = d.out;
-    p.in_stride = d.in_stride ? d.in_stride : (long long)d.band_rows * pitch;
-    p.out_stride = d.out_stride ? d.out_stride : (long long)rows * pitch;
-    p.pitch = pitch; p.cpr = cpr; p.H = d.band_rows; p.y0 = d.y0; p.y1 = d.y1;
+    fill_band(p, d);
+    const int cpr = p.pitch / 16;
+    p.cpr = cpr; p.y1 = d.y1;
     p.nstrips = (cpr + SEP_NCOLS - 1) / SEP_NCOLS;
     p.ncols = (cpr + p.nstrips - 1) / p.nstrips;
     p.ntiles_y = (rows + SEP_TH - 1) / SEP_TH;
@@ -319,53 +280,40 @@ int launch_sep_tiled(const LaunchDesc &d)
     if (nblocks > 0x7fffffffLL) return MI_BLUR_ERR_INVALID;
     p.nblocks = (unsigned)nblocks;
     p.xcd = nblocks >= 16 ? 1 : 0;
-    const int rb = k.rx <= 4 ? 4 : k.rx <= 8 ? 8 : 16;
-    const dim3 grid((unsigned)nblocks);
-    switch (d.channels) {
-    case 1: return launch_sep_tiled_c<1>(d, p, grid, rb);
-    case 2: return launch_sep_tiled_c<2>(d, p, grid, rb);
-    case 3: return launch_sep_tiled_c<3>(d, p, grid, rb);
-    case 4: return launch_sep_tiled_c<4>(d, p, grid, rb);
-    }
-    return MI_BLUR_ERR_INVALID;
+    const dim3 grid((unsigned)nblocks), block(SEP_THREADS);
+    return dispatch<1, 2, 3, 4>(d.channels, [&](auto C) {
+        return dispatch<4, 8, 16>(k.rx <= 4 ? 4 : k.rx <= 8 ? 8 : 16, [&](auto RB) {
+            const int ncw = p.ncols + 2 * sep_halo_chunks(C, RB);      // sums: SEP_TH rows x ncw chunks x 32 B >= the staged bytes
+            return do_launch(blur_sep_tiled_kernel<C, RB>, grid, block, (size_t)SEP_TH * ncw * 32u, d, p);
+        });
+    });
 }
 
 int launch_sep_generic(const LaunchDesc &d)
 {
     set_last_kernel("blur_sep_generic_kernel");
     const SepTaps &k = d.filter->taps;
-    const int pitch = d.width * d.channels, rows = d.y1 - d.y0;
     SepGenericParams p{};
-    p.in = d.in; p.out = d.out;
-    p.block = (long long)rows * pitch;
-    p.in_stride = d.in_stride ? d.in_stride : (long long)d.band_rows * pitch;
-    p.out_stride = d.out_stride ? d.out_stride : p.block;
+    fill_band(p, d);
+    p.block = dense_out(d);
     p.total = p.block * d.n_images;
-    p.width = d.width; p.channels = d.channels; p.pitch = pitch; p.H = d.band_rows; p.y0 = d.y0;
+    p.width = d.width; p.channels = d.channels;
     p.rx = k.rx; p.ry = k.ry; p.shift = k.shift;
     for (int i = 0; i <= 2 * SEP_MAX_R; i++) { p.wx[i] = k.wx[i]; p.wy[i] = k.wy[i]; }
-    long long blocks = (p.total + 255) / 256;
-    if (blocks > 256LL * 64) blocks = 256LL * 64;       // grid-stride the rest
-    return sep_do_launch(blur_sep_generic_kernel, dim3((unsigned)blocks), dim3(256), 0, d, p);
+    return do_launch(blur_sep_generic_kernel, byte_grid(p.total), dim3(256), 0, d, p);
 }
 
 }  // namespace
 
 int launch_sep(const LaunchDesc &d)
 {
-    if (!d.filter || d.filter->kind != FilterKind::SEP || !d.in || !d.out || d.in == d.out) return MI_BLUR_ERR_INVALID;
-    if (d.width <= 0 || d.band_rows <= 0 || d.channels <= 0 || d.n_images < 0) return MI_BLUR_ERR_INVALID;
-    if (d.y0 < 0 || d.y1 > d.band_rows || d.y0 >= d.y1) return MI_BLUR_ERR_INVALID;
-    if ((long long)d.width * d.channels > INT_MAX / 2) return MI_BLUR_ERR_INVALID;
-    if ((long long)d.width * d.channels * d.band_rows > INT_MAX) return MI_BLUR_ERR_INVALID;  // per-image 32-bit
+    if (const int st = check_desc(d, FilterKind::SEP)) return st;
     const SepTaps &k = d.filter->taps;
     if (k.rx < 0 || k.rx > SEP_MAX_R || k.ry < 0 || k.ry > SEP_MAX_R || k.shift < 0 || k.shift > 16) return MI_BLUR_ERR_INVALID;
     if (d.halo_top || d.halo_bottom) return MI_BLUR_ERR_UNSUPPORTED;
+    if (strides_too_small(d)) return MI_BLUR_ERR_INVALID;
+    if (d.n_images == 0) return MI_BLUR_OK;             // after the strides (launch(): before)
     const long long pitch = (long long)d.width * d.channels;
-    const long long dense_in = (long long)d.band_rows * pitch, dense_out = (long long)(d.y1 - d.y0) * pitch;
-    if (d.in_stride < 0 || d.out_stride < 0 || (d.in_stride && d.in_stride < dense_in) || (d.out_stride && d.out_stride < dense_out))
-        return MI_BLUR_ERR_INVALID;
-    if (d.n_images == 0) return MI_BLUR_OK;
     const bool aligned = d.channels <= 4 && pitch % 16 == 0 && (uintptr_t)d.in % 16 == 0 && (uintptr_t)d.out % 16 == 0 &&
                          d.in_stride % 16 == 0 && d.out_stride % 16 == 0;
     return aligned ? launch_sep_tiled(d) : launch_sep_generic(d);

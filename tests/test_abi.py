@@ -107,6 +107,45 @@ def test_argument_validation(pkg, L):
         assert L.mi_blur_resident_alloc(ctx.h, 4) == pkg.ERR_STATE                          # CPU device has no HBM pool
 
 
+def test_set_option_accepts_and_refuses_what_it_did(pkg, L):
+    """Every key of mi_blur_set_option with its lowest and highest value, one below and one above, and an unknown key.  The
+    expected statuses are literals recorded from the library as it was when every key had its own branch there."""
+    OK, INVALID = 0, -1
+    assert (pkg.OK, pkg.ERR_INVALID) == (OK, INVALID)
+    flags = {"stage_dma": 1, "xcd_remap": 1, "debug_copy": 0, "row_shuffle": 0, "prefer_stream": 0, "zero_copy": 1, "ragged_tiled": 1,
+             "fused_release": 0, "experiment": 0, "stream_updown": 1, "debug_xcd_times": 0, "zero_copy_events": 1, "zero_copy_server": 1,
+             "staged_server": 1, "zero_copy_trace": 0, "zero_copy_tickets": 1, "zero_copy_spin": 0}          # key: default
+    ranges = {"stream_band_rows": (0, 4096, 0), "zero_copy_streams": (1, 8, 4), "zero_copy_blocks": (0, 1 << 20, 24),
+              "prefer_direct": (0, 2, 1), "fused_adds_per_word": (4, 4096, 32), "fused_tail_blocks": (10, 800, 25),
+              "fused_tail": (0, 500, 30), "fused_window": (1, 4096, 8), "zero_copy_server_min_kb": (0, 1 << 20, 1280),
+              "zero_copy_debug_base": (0, 1 << 20, 0), "resident_place_trials": (0, 8, 4), "zero_copy_workers": (1, 2048, 48),
+              "zero_copy_idle_us": (10, 100000, 300), "zero_copy_budget": (1, 1 << 20, 256), "xcd_run": (0, 1 << 20, 0)}   # key: lo, hi, default
+    lists = {"rows_per_thread": ((0, 4, 8, 16), (-1, 1, 2, 12, 17, 32, 36), 0),
+             "direct_bh": ((4, 8, 12, 16), (-1, 0, 3, 5, 17, 32, 36, 40), 8)}                                # key: accepted, refused, default
+    assert len(flags) + len(ranges) + len(lists) == 34
+    got = []
+    try:
+        for key in flags:                      # any value is taken (stored as 0 | 1)
+            got += [(key, v, L.mi_blur_set_option(key.encode(), v), OK) for v in (0, 1, -1, 2, 2**31 - 1, -2**31)]
+        for key, (lo, hi, _) in ranges.items():
+            got += [(key, lo, L.mi_blur_set_option(key.encode(), lo), OK), (key, hi, L.mi_blur_set_option(key.encode(), hi), OK),
+                    (key, lo - 1, L.mi_blur_set_option(key.encode(), lo - 1), INVALID),
+                    (key, hi + 1, L.mi_blur_set_option(key.encode(), hi + 1), INVALID),
+                    (key, -2**31, L.mi_blur_set_option(key.encode(), -2**31), INVALID),
+                    (key, 2**31 - 1, L.mi_blur_set_option(key.encode(), 2**31 - 1), INVALID)]
+        for key, (good, bad, _) in lists.items():
+            got += [(key, v, L.mi_blur_set_option(key.encode(), v), OK) for v in good]
+            got += [(key, v, L.mi_blur_set_option(key.encode(), v), INVALID) for v in bad + (-2**31, 2**31 - 1)]
+        for key in (b"no_such_knob", b"", b"rpg", b"ragged", b"stream_bh", b"stage_dm", b"stage_dma ", b"STAGE_DMA"):   # field names are not keys
+            got.append((key.decode(), 1, L.mi_blur_set_option(key, 1), INVALID))
+        got.append((None, 1, L.mi_blur_set_option(None, 1), INVALID))
+    finally:                                   # back to the built-in defaults
+        for key, default in list(flags.items()) + [(k, v[2]) for k, v in list(ranges.items()) + list(lists.items())]:
+            assert L.mi_blur_set_option(key.encode(), default) == OK, key
+    wrong = [g for g in got if g[2] != g[3]]
+    assert not wrong, wrong
+
+
 def test_a1_partition_matches_reference_formula(pkg, O):
     for mode in (0, 1, 2):
         for bc in (1, 30, 35, 500, 1200):

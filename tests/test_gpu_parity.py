@@ -1806,3 +1806,93 @@ def test_random_shapes_auto_dispatch(pkg, L, O, torch_cuda):
                 assert np.array_equal(got, want), (case, h, w, c, r, n, y0, y1, opts)
     finally:
         reset_opts(L)
+
+
+@pytest.mark.parametrize("family", ["box", "sep", "median"])
+def test_launch_statuses_are_pinned(pkg, L, torch_cuda, family):
+    """The status of every refusal (and of the empty launch) of the three filter families, through the enqueue exports and
+    mi_blur_submit_bands on a context of that kind.  The expected values are literals recorded from the library as it was
+    before the kernel files got one shared argument check; every figure is printed before the assertion."""
+    INT_MAX = 2**31 - 1
+    OK, INVALID = 0, -1
+    assert (pkg.OK, pkg.ERR_INVALID) == (OK, INVALID)
+    d = torch_cuda.zeros(4096, dtype=torch_cuda.uint8, device="cuda")
+    p, q = d.data_ptr(), d.data_ptr() + 2048
+    k = pkg.gauss_kernel(1.0)
+    bad_radius_taps = pkg.gauss_kernel(1.0)
+    bad_radius_taps.rx = 17
+    bad_sum_taps = pkg.gauss_kernel(1.0)
+    bad_sum_taps.wy[0] += 1
+
+    # one image, rows [y0, y1) of a band: a, b = pointers, geometry (w, h, c), r = radius (box, median) or taps (sep)
+    def band(a, b, w, h, c, y0, y1, r=None):
+        if family == "box":
+            return L.mi_blur_enqueue_ex(a, b, w, h, c, 1 if r is None else r, 1, y0, y1, 0, None)
+        if family == "sep":
+            return L.mi_blur_enqueue_sep_band(a, b, w, h, c, y0, y1, C.byref(k if r is None else r), None)
+        return L.mi_blur_enqueue_median_band(a, b, w, h, c, 1 if r is None else r, y0, y1, None)
+
+    # n whole images
+    def batch(a, b, w, h, c, n, r=None):
+        if family == "box":
+            return L.mi_blur_enqueue_ex(a, b, w, h, c, 1 if r is None else r, n, 0, h, 0, None)
+        if family == "sep":
+            return L.mi_blur_enqueue_sep(a, b, w, h, c, n, C.byref(k if r is None else r), None)
+        return L.mi_blur_enqueue_median(a, b, w, h, c, 1 if r is None else r, n, None)
+
+    bad_r = {"box": [0, 3, -1], "sep": [bad_radius_taps, bad_sum_taps], "median": [0, 8, -1]}[family]
+    cases = [
+        ("null in", band(None, q, 16, 8, 3, 0, 8), INVALID),
+        ("null out", band(p, None, 16, 8, 3, 0, 8), INVALID),
+        ("in == out", band(p, p, 16, 8, 3, 0, 8), INVALID),
+        ("width 0", band(p, q, 0, 8, 3, 0, 8), INVALID),
+        ("width -1", band(p, q, -1, 8, 3, 0, 8), INVALID),
+        ("rows 0", band(p, q, 16, 0, 3, 0, 0), INVALID),
+        ("rows -1", band(p, q, 16, -1, 3, 0, -1), INVALID),
+        ("channels 0", band(p, q, 16, 8, 0, 0, 8), INVALID),
+        ("channels -1", band(p, q, 16, 8, -1, 0, 8), INVALID),
+        ("n_images -1", batch(p, q, 16, 8, 3, -1), INVALID),
+        ("y0 > y1", band(p, q, 16, 8, 3, 6, 2), INVALID),
+        ("y0 == y1", band(p, q, 16, 8, 3, 3, 3), INVALID),
+        ("y0 < 0", band(p, q, 16, 8, 3, -1, 8), INVALID),
+        ("y1 > band_rows", band(p, q, 16, 8, 3, 0, 9), INVALID),
+        ("row > INT_MAX / 2 bytes", band(p, q, INT_MAX // 2 // 4 + 1, 1, 4, 0, 1), INVALID),
+        ("image > INT_MAX bytes", band(p, q, 65536, 8193, 4, 0, 8193), INVALID),
+        ("n_images 0", batch(p, q, 16, 8, 3, 0), OK),
+        ("n_images 0, null in", batch(None, q, 16, 8, 3, 0), INVALID),
+        ("n_images 0, y1 > band_rows", L.mi_blur_enqueue_ex(p, q, 16, 8, 3, 1, 0, 0, 9, 0, None) if family == "box" else None, INVALID),
+        ("n_images 0, image > INT_MAX bytes", batch(p, q, 65536, 8193, 4, 0), INVALID),
+    ]
+    cases += [(f"bad radius / taps #{i}", band(p, q, 16, 8, 3, 0, 8, r), INVALID) for i, r in enumerate(bad_r)]
+    cases += [(f"n_images 0, bad radius / taps #{i}", batch(p, q, 16, 8, 3, 0, r), INVALID) for i, r in enumerate(bad_r)]
+
+    # strides: only mi_blur_submit_bands passes one down.  Pageable buffers; n_images <= 1, so no address depends on the stride.
+    w, h, c, n = 64, 32, 3, 2
+    a = np.zeros((n, h, w, c), np.uint8)
+    b = np.zeros_like(a)
+    isz, band_bytes = h * w * c, 16 * w * c
+    with pkg.Context(0, w, h, c, 1, max_batch=n, n_slots=2) as ctx:
+        if family == "sep":
+            ctx.set_kernel(k)
+        if family == "median":
+            ctx.set_median(1)
+        sb = lambda n_images, stride, rows=16: L.mi_blur_submit_bands(ctx.h, a.ctypes.data, b.ctypes.data, n_images, stride, rows, 1, 1)
+        cases += [
+            ("bands: stride too small", sb(1, band_bytes - 16), INVALID),
+            ("bands: stride 0", sb(1, 0), INVALID),
+            ("bands: n_images 0", sb(0, isz), OK),
+            ("bands: n_images 0, stride too small", sb(0, band_bytes - 16), INVALID),
+            ("bands: n_images 0, negative stride", sb(0, 2**64 - 16), OK),
+            ("bands: n_images 0, band_rows 0", sb(0, isz, 0), INVALID),
+            ("bands: n_images -1", sb(-1, isz), INVALID),
+            ("bands: n_images > max_batch", sb(n + 1, isz), INVALID),
+            ("bands: negative stride", sb(1, 2**64 - 16), OK),
+            ("bands: dense stride", sb(1, band_bytes), OK),
+            ("bands: whole-image stride", sb(n, isz), OK),
+        ]
+        ctx.sync()
+    cases = [(what, got, want) for what, got, want in cases if got is not None]
+    for what, got, want in cases:
+        print(f"{family}: {what}: {got} (recorded {want})")
+    wrong = [(what, got, want) for what, got, want in cases if got != want]
+    assert not wrong, wrong
