@@ -33,6 +33,8 @@ OK, ERR_INVALID, ERR_NO_DEVICE, ERR_NOMEM, ERR_STATE, ERR_UNSUPPORTED = 0, -1, -
 UNIQUE_ID_BYTES = 128
 SEP_MAX_RADIUS = 16
 MEDIAN_MAX_RADIUS = 7
+MORPH_MAX_RADIUS = 16
+MORPH_ERODE, MORPH_DILATE, MORPH_GRADIENT = 0, 1, 2
 PEER_HANDLE_BYTES = 64
 
 
@@ -45,7 +47,7 @@ def _newer(target: str, sources: list[str]) -> bool:
 
 def build_native(force: bool = False, verbose: bool = False) -> str:
     """Compile libmi_blur.so (hipcc, --offload-arch=gfx950) and the C++ hosts, in-tree."""
-    srcs = [os.path.join(CSRC, f) for f in ("blur_kernels.hip", "sep_kernels.hip", "median_kernels.hip", "layout_kernels.hip", "mi_blur_api.cpp", "cpu_device.cpp")]
+    srcs = [os.path.join(CSRC, f) for f in ("blur_kernels.hip", "sep_kernels.hip", "median_kernels.hip", "morph_kernels.hip", "layout_kernels.hip", "mi_blur_api.cpp", "cpu_device.cpp")]
     deps = srcs + [os.path.join(CSRC, f) for f in ("blur_launch.h", "kernel_common.h", "cpu_device.h", "filter.h")] + [HEADER]
     if force or not _newer(LIB_PATH, deps):
         cmd = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra",
@@ -196,6 +198,10 @@ def lib() -> C.CDLL:
         "mi_blur_enqueue_median_band": (i, [u8p, u8p, i, i, i, i, i, i, vp]),
         "mi_blur_cpu_run_median": (i, [u8p, u8p, i, i, i, i, i, i]),
         "mi_blur_ctx_set_median": (i, [vp, i]),
+        "mi_blur_enqueue_morph": (i, [u8p, u8p, i, i, i, i, i, i, i, vp]),
+        "mi_blur_enqueue_morph_band": (i, [u8p, u8p, i, i, i, i, i, i, i, i, vp]),
+        "mi_blur_cpu_run_morph": (i, [u8p, u8p, i, i, i, i, i, i, i, i]),
+        "mi_blur_ctx_set_morph": (i, [vp, i, i, i]),
         "mi_blur_fill_synthetic": (None, [u8p, i, i, i, i, i, i]),
         "mi_blur_fnv1a64": (C.c_uint64, [u8p, C.c_size_t]),
         "mi_blur_debug_zc_trace": (i, [vp, C.POINTER(C.c_uint64), i, C.POINTER(i), C.POINTER(C.c_uint)]),
@@ -313,6 +319,11 @@ class Context:
         check(lib().mi_blur_ctx_set_median(self.h, int(radius)), "mi_blur_ctx_set_median")
         self.median_radius = int(radius)
 
+    def set_morph(self, op: int, rx: int, ry: int) -> None:
+        """Erode / dilate / gradient (MORPH_*) over (2 rx + 1) x (2 ry + 1) in place of the blur (before the first submit only)."""
+        check(lib().mi_blur_ctx_set_morph(self.h, int(op), int(rx), int(ry)), "mi_blur_ctx_set_morph")
+        self.morph = (int(op), int(rx), int(ry))
+
     def set_kernel(self, kernel: "SepKernel") -> None:
         """A separable kernel in place of the radius, for every submit (before the first one only)."""
         check(lib().mi_blur_ctx_set_kernel(self.h, C.byref(kernel)), "mi_blur_ctx_set_kernel")
@@ -414,7 +425,7 @@ def _images(images, name: str):
 
 
 def _filter_images(a, radius: int, device: int, batch: int, configure=None):
-    """The numpy driver of blur, gaussian_blur and median_blur: a (from _images) through mi_blur_create (radius) /
+    """The numpy driver of blur, gaussian_blur, median_blur and the morphology functions: a (from _images) through mi_blur_create (radius) /
     configure(ctx) / mi_blur_submit / mi_blur_sync.  Returns the output as (N, H, W, C)."""
     import numpy as np
     if a.ndim == 2:
@@ -472,3 +483,36 @@ def median_blur(images, ksize: int = 3, device: int = 0, batch: int = 0):
         raise ValueError(f"median_blur: ksize must be odd, 3..{2 * MEDIAN_MAX_RADIUS + 1}")
     a = _images(images, "median_blur")
     return _filter_images(a, 1, device, batch, lambda ctx: ctx.set_median(ksize // 2)).reshape(a.shape)
+
+
+def _morph(name: str, op: int, images, ksize, device: int, batch: int):
+    import operator
+    try:
+        kx, ky = (ksize, ksize) if not isinstance(ksize, (tuple, list)) else ksize
+        kx, ky = operator.index(kx), operator.index(ky)
+    except (TypeError, ValueError):
+        raise ValueError(f"{name}: ksize is an odd int or a pair (kx, ky) of odd ints") from None
+    for k in (kx, ky):
+        if k % 2 != 1 or not 1 <= k <= 2 * MORPH_MAX_RADIUS + 1:
+            raise ValueError(f"{name}: ksize must be odd, 1..{2 * MORPH_MAX_RADIUS + 1}")
+    a = _images(images, name)
+    return _filter_images(a, 1, device, batch, lambda ctx: ctx.set_morph(op, kx // 2, ky // 2)).reshape(a.shape)
+
+
+def erode(images, ksize=3, device: int = 0, batch: int = 0):
+    """Greyscale erosion: per channel the minimum of a kx x ky window, numpy in -> numpy out, like blur().
+
+    ksize: an odd int, or a pair (kx, ky) of odd ints (columns, rows), each 1..33.  Edges clamp (pixels outside the image
+    are ignored).  images: (H, W), (H, W, C) or (N, H, W, C) uint8; the result has the same shape.  device: HIP ordinal,
+    or DEVICE_CPU.  Goes through mi_blur_create / mi_blur_ctx_set_morph / mi_blur_submit / mi_blur_sync."""
+    return _morph("erode", MORPH_ERODE, images, ksize, device, batch)
+
+
+def dilate(images, ksize=3, device: int = 0, batch: int = 0):
+    """Greyscale dilation: per channel the maximum of a kx x ky window; arguments as erode()."""
+    return _morph("dilate", MORPH_DILATE, images, ksize, device, batch)
+
+
+def morph_gradient(images, ksize=3, device: int = 0, batch: int = 0):
+    """Morphological gradient: per channel the window maximum minus the window minimum; arguments as erode()."""
+    return _morph("morph_gradient", MORPH_GRADIENT, images, ksize, device, batch)

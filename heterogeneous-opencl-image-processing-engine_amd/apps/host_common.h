@@ -164,6 +164,8 @@ struct Options {
     double sigma_y = 0.0;                //              at most 16) instead of --ksize; mi_blur_ctx_set_kernel on every context
     int sep_radius = 0;
     int median = 0;                      // --median K (odd, 3..15): the KxK median instead of --ksize; mi_blur_ctx_set_median on every context
+    int morph = 0;                       // --erode K | --dilate K | --morph-gradient K (odd, 3..33): the KxK window minimum / maximum / their
+    int morph_op = 0;                    //              difference instead of --ksize; mi_blur_ctx_set_morph on every context
     int images = 5000;                   // --images N   (NUM_IMAGES, heterogeneous_blur.c:44)
     bool images_given = false;
     int gpus = 1;                        // --gpus G
@@ -217,6 +219,12 @@ inline int parse_flags(int argc, char **argv, Options &o)
             o.median = atoi(next("--median"));
             if (o.median < 3 || o.median > 2 * MI_BLUR_MEDIAN_MAX_RADIUS + 1 || o.median % 2 == 0) { printf("Error: --median must be odd, 3..%d\n", 2 * MI_BLUR_MEDIAN_MAX_RADIUS + 1); exit(-1); }
         }
+        else if (a == "--erode" || a == "--dilate" || a == "--morph-gradient") {
+            if (o.morph) { printf("Error: --erode, --dilate and --morph-gradient exclude each other\n"); exit(-1); }
+            o.morph = atoi(next(a.c_str()));
+            o.morph_op = a == "--erode" ? MI_BLUR_MORPH_ERODE : a == "--dilate" ? MI_BLUR_MORPH_DILATE : MI_BLUR_MORPH_GRADIENT;
+            if (o.morph < 3 || o.morph > 2 * MI_BLUR_MORPH_MAX_RADIUS + 1 || o.morph % 2 == 0) { printf("Error: %s must be odd, 3..%d\n", a.c_str(), 2 * MI_BLUR_MORPH_MAX_RADIUS + 1); exit(-1); }
+        }
         else if (a == "--sigma") { o.sigma = atof(next("--sigma")); if (!(o.sigma > 0.0)) { printf("Error: --sigma must be > 0\n"); exit(-1); } }
         else if (a == "--sigma-y") { o.sigma_y = atof(next("--sigma-y")); if (!(o.sigma_y > 0.0)) { printf("Error: --sigma-y must be > 0\n"); exit(-1); } }
         else if (a == "--radius") { o.sep_radius = atoi(next("--radius")); if (o.sep_radius < 1 || o.sep_radius > MI_BLUR_SEP_MAX_RADIUS) { printf("Error: --radius must be 1..%d\n", MI_BLUR_SEP_MAX_RADIUS); exit(-1); } }
@@ -247,21 +255,25 @@ inline int parse_flags(int argc, char **argv, Options &o)
     if (o.sigma > 0.0 && o.resident) { printf("Error: --sigma does not run --resident\n"); exit(-1); }
     if (o.median && (o.ksize_given || o.sigma > 0.0)) { printf("Error: --median excludes --ksize and --sigma\n"); exit(-1); }
     if (o.median && o.resident) { printf("Error: --median does not run --resident\n"); exit(-1); }
+    if (o.morph && (o.ksize_given || o.sigma > 0.0 || o.median)) { printf("Error: --erode, --dilate and --morph-gradient exclude --ksize, --sigma and --median\n"); exit(-1); }
+    if (o.morph && o.resident) { printf("Error: --erode, --dilate and --morph-gradient do not run --resident\n"); exit(-1); }
     return npos;
 }
 
-// The one filter every context of the run is given, from --ksize, --sigma or --median (they exclude each other).
+// The one filter every context of the run is given, from --ksize, --sigma, --median or --erode / --dilate / --morph-gradient
+// (they exclude each other).
 struct HostFilter {
-    int radius;                 // --ksize 3|5: 1|2.  Every context is created with it (1 under --sigma and --median).
+    int radius;                 // --ksize 3|5: 1|2.  Every context is created with it (1 under every other filter).
     bool sep;                   // --sigma: this separable Gaussian (mi_blur_sep_kernel_gauss, 8-bit taps per axis)
     mi_blur_sep_kernel k;
     double sigma, sigma_y;
     int median;                 // --median K: the KxK median, radius K / 2; 0 = none
+    int morph, morph_op;        // --erode | --dilate | --morph-gradient K: the KxK window extremum (mi_blur_morph_op), radius K / 2; 0 = none
 };
 
 inline HostFilter filter_of(const Options &o)
 {
-    HostFilter f{o.ksize == 3 ? 1 : 2, o.sigma > 0.0, {}, o.sigma, o.sigma_y, o.median};
+    HostFilter f{o.ksize == 3 ? 1 : 2, o.sigma > 0.0, {}, o.sigma, o.sigma_y, o.median, o.morph, o.morph_op};
     if (f.sep && mi_blur_sep_kernel_gauss(o.sigma, o.sigma_y, o.sep_radius, 8, &f.k) != MI_BLUR_OK) {
         printf("Error: no Gaussian taps for sigma %g / %g, radius %d\n", o.sigma, o.sigma_y, o.sep_radius);
         exit(-1);
@@ -269,21 +281,27 @@ inline HostFilter filter_of(const Options &o)
     return f;
 }
 
-// Give a context made with f.radius the filter (mi_blur_ctx_set_kernel / mi_blur_ctx_set_median; nothing for --ksize).
+// Give a context made with f.radius the filter (mi_blur_ctx_set_kernel / _set_median / _set_morph; nothing for --ksize).
 inline void set_filter(mi_blur_ctx *ctx, const HostFilter &f)
 {
     if (f.sep) mi_check(mi_blur_ctx_set_kernel(ctx, &f.k), "Failed to set the blur kernel");
     if (f.median) mi_check(mi_blur_ctx_set_median(ctx, f.median / 2), "Failed to set the median");
+    if (f.morph) mi_check(mi_blur_ctx_set_morph(ctx, f.morph_op, f.morph / 2, f.morph / 2), "Failed to set the morphology filter");
 }
 
-// Rows a band needs on each side: the median's radius, the Gaussian's vertical radius (at least one row, so that the
+// Rows a band needs on each side: the median's or the morphology window's radius, the Gaussian's vertical radius (at least one row, so that the
 // split geometry stays the reference's), or the box radius.
-inline int filter_halo(const HostFilter &f) { return f.median ? f.median / 2 : f.sep ? std::max(1, f.k.ry) : f.radius; }
+inline int filter_halo(const HostFilter &f) { return f.morph ? f.morph / 2 : f.median ? f.median / 2 : f.sep ? std::max(1, f.k.ry) : f.radius; }
 
 // The banner's "Blur kernel" line (with the taps of a Gaussian).
 inline void print_filter(const HostFilter &f)
 {
     if (f.median) { printf("Blur kernel: %dx%d median\n", f.median, f.median); return; }
+    if (f.morph) {
+        printf("Blur kernel: %dx%d %s\n", f.morph, f.morph,
+               f.morph_op == MI_BLUR_MORPH_ERODE ? "erode" : f.morph_op == MI_BLUR_MORPH_DILATE ? "dilate" : "morphological gradient");
+        return;
+    }
     if (!f.sep) { printf("Blur kernel: %dx%d\n", 2 * f.radius + 1, 2 * f.radius + 1); return; }
     const mi_blur_sep_kernel &k = f.k;
     printf("Blur kernel: %dx%d separable Gaussian, sigma %g x %g\n", 2 * k.rx + 1, 2 * k.ry + 1, f.sigma, f.sigma_y > 0.0 ? f.sigma_y : f.sigma);

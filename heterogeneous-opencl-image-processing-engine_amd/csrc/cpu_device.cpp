@@ -241,6 +241,40 @@ void cpu_median_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, int R
     }
 }
 
+// Window minimum and / or maximum, separably: per output row the extremum of the 2 ry + 1 source rows (clamped to the band)
+// into an edge-replicated scratch row, then the extremum of the 2 rx + 1 pixels along it.  Byte loops that vectorise.
+void cpu_morph_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, int op, int rx, int ry, int y_begin, int y_end,
+                    int out_row_shift)
+{
+    const int pitch = W * C, pad = rx * C;
+    const bool want_lo = op != MI_BLUR_MORPH_DILATE, want_hi = op != MI_BLUR_MORPH_ERODE;
+    std::vector<uint8_t> scratch(2 * ((size_t)pitch + 2 * pad) + 2 * (size_t)pitch);
+    uint8_t *vlo = scratch.data() + pad, *vhi = vlo + pitch + 2 * pad;   // v[-pad .. pitch+pad)
+    uint8_t *hlo = vhi + pitch + pad, *hhi = hlo + pitch;
+    for (int y = y_begin; y < y_end; y++) {
+        for (int j = -ry; j <= ry; j++) {
+            const uint8_t *a = in + (size_t)std::min(std::max(y + j, 0), H - 1) * pitch;
+            if (j == -ry) { memcpy(vlo, a, pitch); memcpy(vhi, a, pitch); continue; }
+            if (want_lo) for (int b = 0; b < pitch; b++) vlo[b] = std::min(vlo[b], a[b]);
+            if (want_hi) for (int b = 0; b < pitch; b++) vhi[b] = std::max(vhi[b], a[b]);
+        }
+        for (int q = 1; q <= pad; q++) {
+            vlo[-q] = vlo[((-q % C) + C) % C]; vlo[pitch + q - 1] = vlo[pitch - C + ((q - 1) % C)];
+            vhi[-q] = vhi[((-q % C) + C) % C]; vhi[pitch + q - 1] = vhi[pitch - C + ((q - 1) % C)];
+        }
+        uint8_t *o = out + (size_t)(y - out_row_shift) * pitch;
+        uint8_t *lo = op == MI_BLUR_MORPH_ERODE ? o : hlo, *hi = op == MI_BLUR_MORPH_DILATE ? o : hhi;
+        if (want_lo) memcpy(lo, vlo - pad, pitch);
+        if (want_hi) memcpy(hi, vhi - pad, pitch);
+        for (int i = 1; i <= 2 * rx; i++) {
+            const uint8_t *a = vlo + (i - rx) * C, *b2 = vhi + (i - rx) * C;
+            if (want_lo) for (int b = 0; b < pitch; b++) lo[b] = std::min(lo[b], a[b]);
+            if (want_hi) for (int b = 0; b < pitch; b++) hi[b] = std::max(hi[b], b2[b]);
+        }
+        if (op == MI_BLUR_MORPH_GRADIENT) for (int b = 0; b < pitch; b++) o[b] = (uint8_t)(hi[b] - lo[b]);
+    }
+}
+
 // n_images bands of band_rows rows; output rows [y0,y1) of each.  Threads take whole
 // images when there are enough of them, else row slices of each image.
 void cpu_blur_batch(const uint8_t *in, uint8_t *out, int W, int band_rows, int C, const Filter &f, int n_images,
@@ -268,7 +302,8 @@ void cpu_blur_batch(const uint8_t *in, uint8_t *out, int W, int band_rows, int C
             const int ys = y0 + (int)((long long)rows * s / slices), ye = y0 + (int)((long long)rows * (s + 1) / slices);
             const uint8_t *src = in + img * in_stride;
             uint8_t *dst = out + img * out_stride;
-            if (f.kind == FilterKind::MEDIAN) cpu_median_rows(src, dst, W, band_rows, C, f.radius, ys, ye, y0);
+            if (f.kind == FilterKind::MORPH) cpu_morph_rows(src, dst, W, band_rows, C, f.morph_op, f.morph_rx, f.morph_ry, ys, ye, y0);
+            else if (f.kind == FilterKind::MEDIAN) cpu_median_rows(src, dst, W, band_rows, C, f.radius, ys, ye, y0);
             else if (f.kind == FilterKind::SEP) cpu_blur_rows_sep(src, dst, W, band_rows, C, f.taps, ys, ye, y0);
             else cpu_blur_rows(src, dst, W, band_rows, C, f.radius, ys, ye, y0);
         }

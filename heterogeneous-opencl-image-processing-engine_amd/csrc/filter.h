@@ -1,5 +1,5 @@
 // filter.h — internal: the one filter a launch, a context or a CPU run applies, in the form the GPU kernels
-// (blur_kernels.hip, sep_kernels.hip, median_kernels.hip) and the CPU device (cpu_device.cpp) take it.  Plain C++, no HIP.
+// (blur_kernels.hip, sep_kernels.hip, median_kernels.hip, morph_kernels.hip) and the CPU device (cpu_device.cpp) take it.  Plain C++, no HIP.
 #pragma once
 
 #include "../../include/mi_blur.h"
@@ -15,13 +15,15 @@ struct SepTaps {
     unsigned wx[2 * SEP_MAX_R + 1], wy[2 * SEP_MAX_R + 1];
 };
 
-enum class FilterKind { BOX, SEP, MEDIAN };
+enum class FilterKind { BOX, SEP, MEDIAN, MORPH };
 
 // BOX: the fixed 3x3 / 5x5 kernel of `radius` 1|2.  SEP: the separable kernel `taps`.  MEDIAN: the median of `radius` 1..7.
+// MORPH: the window minimum / maximum / their difference (`morph_op`) over (2 morph_rx + 1) x (2 morph_ry + 1).
 struct Filter {
     FilterKind kind;
     int radius;             // BOX and MEDIAN
     SepTaps taps;           // SEP
+    int morph_op = 0, morph_rx = 0, morph_ry = 0;   // MORPH (mi_blur_morph_op, radii 0..16); last, so {kind, radius, taps} still initialises a Filter
 };
 
 // The constructors validate: MI_BLUR_OK, or MI_BLUR_ERR_INVALID with *f untouched.
@@ -51,6 +53,15 @@ inline int filter_median(int radius, Filter *f)
 {
     if (radius < 1 || radius > MI_BLUR_MEDIAN_MAX_RADIUS) return MI_BLUR_ERR_INVALID;
     *f = Filter{FilterKind::MEDIAN, radius, {}};
+    return MI_BLUR_OK;
+}
+
+inline int filter_morph(int op, int rx, int ry, Filter *f)
+{
+    if (op != MI_BLUR_MORPH_ERODE && op != MI_BLUR_MORPH_DILATE && op != MI_BLUR_MORPH_GRADIENT) return MI_BLUR_ERR_INVALID;
+    if (rx < 0 || rx > MI_BLUR_MORPH_MAX_RADIUS || ry < 0 || ry > MI_BLUR_MORPH_MAX_RADIUS) return MI_BLUR_ERR_INVALID;
+    *f = Filter{FilterKind::MORPH, 0, {}};
+    f->morph_op = op; f->morph_rx = rx; f->morph_ry = ry;
     return MI_BLUR_OK;
 }
 

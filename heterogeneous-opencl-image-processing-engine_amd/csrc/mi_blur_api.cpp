@@ -219,6 +219,27 @@ extern "C" int mi_blur_enqueue_median(const uint8_t *d_in, uint8_t *d_out, int w
     return enqueue_filter(f, d_in, d_out, width, height, channels, n_images, 0, height, MI_BLUR_VARIANT_AUTO, stream);
 }
 
+// ----------------------------------------------------------------------------------
+// erode / dilate / morphological gradient, radii 0..16 per axis (no reference analogue)
+// ----------------------------------------------------------------------------------
+extern "C" int mi_blur_enqueue_morph_band(const uint8_t *d_in, uint8_t *d_out, int width, int band_rows, int channels, int op,
+                                          int rx, int ry, int out_row_begin, int out_row_end, void *stream)
+{
+    Filter f;
+    if (filter_morph(op, rx, ry, &f) || !d_in || !d_out || d_in == d_out || width <= 0 || band_rows <= 0 || channels <= 0)
+        return MI_BLUR_ERR_INVALID;
+    return enqueue_filter(f, d_in, d_out, width, band_rows, channels, 1, out_row_begin, out_row_end, MI_BLUR_VARIANT_AUTO, stream);
+}
+
+extern "C" int mi_blur_enqueue_morph(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int op, int rx,
+                                     int ry, int n_images, void *stream)
+{
+    Filter f;
+    if (filter_morph(op, rx, ry, &f) || !d_in || !d_out || d_in == d_out || width <= 0 || height <= 0 || channels <= 0 || n_images < 0)
+        return MI_BLUR_ERR_INVALID;
+    return enqueue_filter(f, d_in, d_out, width, height, channels, n_images, 0, height, MI_BLUR_VARIANT_AUTO, stream);
+}
+
 // Frame layout on the device (replaces the host loops heterogeneous_blur.c:125-134 and split_image_blur.c:40-56).
 extern "C" int mi_blur_planar_to_interleaved(const uint8_t *d_planar, uint8_t *d_interleaved, int width, int height,
                                              int channels, int n_images, void *stream)
@@ -336,7 +357,7 @@ struct CpuWorker {
 
 struct mi_blur_ctx {
     int device = 0, W = 0, H = 0, C = 0, max_batch = 0, n_threads = 0;
-    Filter filter{};                                             // every submit applies it: mi_blur_create's radius, or set_kernel / set_median
+    Filter filter{};                                             // every submit applies it: mi_blur_create's radius, or set_kernel / set_median / set_morph
     size_t image_bytes = 0;
     std::vector<Slot> slots;
     int next_slot = 0;
@@ -374,7 +395,7 @@ struct mi_blur_ctx {
     // CPU device
     std::vector<CpuJob *> cpu_jobs;
     CpuWorker *cpu_worker = nullptr;
-    bool submitted = false;                                      // set_kernel / set_median only before this
+    bool submitted = false;                                      // set_kernel / set_median / set_morph only before this
     bool is_cpu() const { return device == MI_BLUR_DEVICE_CPU; }
 };
 
@@ -1167,6 +1188,17 @@ extern "C" int mi_blur_ctx_set_median(mi_blur_ctx *c, int radius)
     return MI_BLUR_OK;
 }
 
+// The window minimum / maximum / gradient in place of the context's blur, for every submit from now on (before the first one only).
+extern "C" int mi_blur_ctx_set_morph(mi_blur_ctx *c, int op, int rx, int ry)
+{
+    if (!c) return MI_BLUR_ERR_INVALID;
+    if (c->submitted) return MI_BLUR_ERR_STATE;
+    Filter f;
+    if (filter_morph(op, rx, ry, &f)) return MI_BLUR_ERR_INVALID;
+    c->filter = f;
+    return MI_BLUR_OK;
+}
+
 // Wait for the OLDEST submit still in flight (its output is then in caller memory), so a host
 // that rotates n_slots batch buffers can refill the oldest one while the newer ones run.
 extern "C" int mi_blur_wait_oldest(mi_blur_ctx *c)
@@ -1520,7 +1552,7 @@ extern "C" int mi_blur_resident_peek(mi_blur_ctx *c, int pool_index, uint8_t *ho
 // ----------------------------------------------------------------------------------
 // CPU device kernel + helpers
 // ----------------------------------------------------------------------------------
-// Every failure here is MI_BLUR_ERR_INVALID, so the order of the checks does not show.  Only the separable and median runs
+// Every failure here is MI_BLUR_ERR_INVALID, so the order of the checks does not show.  Only the separable, median and morphology runs
 // refuse images of more than INT_MAX bytes, as before.
 static int cpu_run_filter(const Filter &f, const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,
                           int n_threads)
@@ -1551,6 +1583,13 @@ extern "C" int mi_blur_cpu_run_median(const uint8_t *in, uint8_t *out, int width
 {
     Filter f;
     return filter_median(radius, &f) ? MI_BLUR_ERR_INVALID : cpu_run_filter(f, in, out, width, height, channels, n_images, n_threads);
+}
+
+extern "C" int mi_blur_cpu_run_morph(const uint8_t *in, uint8_t *out, int width, int height, int channels, int op, int rx, int ry,
+                                     int n_images, int n_threads)
+{
+    Filter f;
+    return filter_morph(op, rx, ry, &f) ? MI_BLUR_ERR_INVALID : cpu_run_filter(f, in, out, width, height, channels, n_images, n_threads);
 }
 
 extern "C" void mi_blur_fill_synthetic(uint8_t *host, int width, int height, int channels, int first_index,

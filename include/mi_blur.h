@@ -66,7 +66,8 @@ const char *mi_blur_strerror(int status);
 int mi_blur_version(void);
 /* Which kernel the calling thread's most recent launch went to ("blur_tiled_kernel", "blur_direct_kernel",
  * "blur_fused_kernel", "blur_tiled_loop_kernel", "blur_stream_kernel", "blur_generic_kernel", "blur_sep_tiled_kernel",
- * "blur_sep_generic_kernel", "blur_median_fast_kernel", "blur_median_generic_kernel"; "" before the first):
+ * "blur_sep_generic_kernel", "blur_median_fast_kernel", "blur_median_generic_kernel", "blur_morph_tiled_kernel",
+ * "blur_morph_generic_kernel"; "" before the first):
  * reports name the kernel a profiler will show.  Static string, never NULL. */
 const char *mi_blur_last_kernel(void);
 
@@ -417,6 +418,39 @@ int mi_blur_cpu_run_median(const uint8_t *in, uint8_t *out, int width, int heigh
  * runs MI_BLUR_ERR_UNSUPPORTED.  A context holds one filter: mi_blur_ctx_set_kernel and this call each replace what the
  * other set before. */
 int mi_blur_ctx_set_median(mi_blur_ctx *ctx, int radius);
+
+/* ------------------------------------------------------------------------
+ * Greyscale morphology, windows up to 33x33 (no reference analogue).  For radii rx, ry in 0..MI_BLUR_MORPH_MAX_RADIUS,
+ * independent per axis, with clamp-to-edge as everywhere else:
+ *   lo[y][x][c] = min { in[clamp(y+j, 0, H-1)][clamp(x+i, 0, W-1)][c] : -rx <= i <= rx, -ry <= j <= ry }
+ *   hi[y][x][c] = max { the same set }
+ *   MI_BLUR_MORPH_ERODE -> lo     MI_BLUR_MORPH_DILATE -> hi     MI_BLUR_MORPH_GRADIENT -> hi - lo   (0..255, no wrap)
+ * Channels never mix.  rx = ry = 0 is valid: ERODE and DILATE copy, GRADIENT writes zeros.  Clamping equals ignoring the
+ * pixels outside the image: a clamped coordinate always lands on a pixel that is already in the window, so this is
+ * OpenCV's default border for erode / dilate.  Exact: the GPU and the CPU device agree byte for byte.
+ * Opening and closing are two calls by the caller (erode then dilate, dilate then erode); a caller that works in bands
+ * needs a halo of 2 ry rows for them, ry for each single call.
+ * ---------------------------------------------------------------------- */
+#define MI_BLUR_MORPH_MAX_RADIUS 16
+typedef enum mi_blur_morph_op { MI_BLUR_MORPH_ERODE = 0, MI_BLUR_MORPH_DILATE = 1, MI_BLUR_MORPH_GRADIENT = 2 } mi_blur_morph_op;
+
+/* mi_blur_enqueue / mi_blur_enqueue_band with that window extremum (same buffers, same band semantics: clamping at the
+ * band's own edges, only rows [out_row_begin, out_row_end) written; asynchronous; n_images == 0 is MI_BLUR_OK).  Rows of
+ * whole 16-byte chunks at 16-byte aligned addresses with 1-4 channels take blur_morph_tiled_kernel at every radius, every
+ * other case blur_morph_generic_kernel.  MI_BLUR_ERR_INVALID (before MI_BLUR_ERR_NO_DEVICE): an unknown op, a radius
+ * outside 0..16, null or equal buffers, non-positive sizes. */
+int mi_blur_enqueue_morph(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int op, int rx, int ry,
+                          int n_images, void *stream);
+int mi_blur_enqueue_morph_band(const uint8_t *d_in, uint8_t *d_out, int width, int band_rows, int channels, int op, int rx,
+                               int ry, int out_row_begin, int out_row_end, void *stream);
+/* mi_blur_cpu_run with the window extremum (a vertical and a horizontal pass per row, exact). */
+int mi_blur_cpu_run_morph(const uint8_t *in, uint8_t *out, int width, int height, int channels, int op, int rx, int ry,
+                          int n_images, int n_threads);
+/* Give a context that window extremum in place of its blur, with the rules of mi_blur_ctx_set_median: only before the
+ * first submit (MI_BLUR_ERR_STATE after), every submit form then uses it, never through the batch server, resident runs
+ * MI_BLUR_ERR_UNSUPPORTED.  A context holds one filter: mi_blur_ctx_set_kernel, mi_blur_ctx_set_median and this call each
+ * replace what another set before. */
+int mi_blur_ctx_set_morph(mi_blur_ctx *ctx, int op, int rx, int ry);
 
 /* Developer diagnostics.  With mi_blur_set_option("debug_xcd_times", 1) every workgroup of the tiled kernel leaves its
  * start and end time (100 MHz ticks) in a slot of the XCD it ran on; this call waits for the device, returns per XCD the
