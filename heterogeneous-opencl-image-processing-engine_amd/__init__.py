@@ -35,6 +35,7 @@ SEP_MAX_RADIUS = 16
 MEDIAN_MAX_RADIUS = 7
 MORPH_MAX_RADIUS = 16
 MORPH_ERODE, MORPH_DILATE, MORPH_GRADIENT = 0, 1, 2
+BILATERAL_MAX_RADIUS = 8
 PEER_HANDLE_BYTES = 64
 
 
@@ -47,7 +48,7 @@ def _newer(target: str, sources: list[str]) -> bool:
 
 def build_native(force: bool = False, verbose: bool = False) -> str:
     """Compile libmi_blur.so (hipcc, --offload-arch=gfx950) and the C++ hosts, in-tree."""
-    srcs = [os.path.join(CSRC, f) for f in ("blur_kernels.hip", "sep_kernels.hip", "median_kernels.hip", "morph_kernels.hip", "layout_kernels.hip", "mi_blur_api.cpp", "cpu_device.cpp")]
+    srcs = [os.path.join(CSRC, f) for f in ("blur_kernels.hip", "sep_kernels.hip", "median_kernels.hip", "morph_kernels.hip", "bilateral_kernels.hip", "layout_kernels.hip", "mi_blur_api.cpp", "cpu_device.cpp")]
     deps = srcs + [os.path.join(CSRC, f) for f in ("blur_launch.h", "kernel_common.h", "cpu_device.h", "filter.h")] + [HEADER]
     if force or not _newer(LIB_PATH, deps):
         cmd = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra",
@@ -117,6 +118,40 @@ class SepKernel(C.Structure):
 
     def taps(self) -> tuple[list[int], list[int]]:
         return list(self.wx[:2 * self.rx + 1]), list(self.wy[:2 * self.ry + 1])
+
+
+class Bilateral(C.Structure):
+    """mi_blur_bilateral: a radius r (1..8), the spatial table S over the (2r+1) x (2r+1) window (row-major at the front of
+    `spatial`) and the range table R over |neighbour - centre|."""
+    _fields_ = [("radius", C.c_int), ("spatial", C.c_uint8 * (17 * 17)), ("range", C.c_uint8 * 256)]
+
+    @classmethod
+    def from_tables(cls, spatial_2d, range_256) -> "Bilateral":
+        """spatial_2d: (2r+1) rows of (2r+1) weights 0..255, r in 1..8; range_256: 256 weights 0..255.  The library
+        validates the rest (centre and R[0] non-zero, sum S <= 65535) when the kernel is used."""
+        rows = [list(row) for row in spatial_2d]
+        n = len(rows)
+        rng = list(range_256)
+        if n % 2 != 1 or not 3 <= n <= 2 * BILATERAL_MAX_RADIUS + 1 or any(len(row) != n for row in rows):
+            raise ValueError(f"Bilateral.from_tables: spatial_2d is square with an odd side, 3..{2 * BILATERAL_MAX_RADIUS + 1}")
+        if len(rng) != 256:
+            raise ValueError("Bilateral.from_tables: range_256 has 256 entries")
+        flat = [int(v) for row in rows for v in row]
+        rng = [int(v) for v in rng]
+        if any(not 0 <= v <= 255 for v in flat + rng):
+            raise ValueError("Bilateral.from_tables: weights are 0..255")
+        k = cls()
+        k.radius = n // 2
+        k.spatial[:n * n] = flat
+        k.range[:] = rng
+        return k
+
+    @classmethod
+    def gauss(cls, sigma_space: float, sigma_range: float, radius: int) -> "Bilateral":
+        """Gaussian tables (mi_blur_bilateral_gauss); sigma_space <= 0 means radius / 2."""
+        k = cls()
+        check(lib().mi_blur_bilateral_gauss(float(sigma_space), float(sigma_range), int(radius), C.byref(k)), "mi_blur_bilateral_gauss")
+        return k
 
 
 class MiBlurError(RuntimeError):
@@ -202,6 +237,11 @@ def lib() -> C.CDLL:
         "mi_blur_enqueue_morph_band": (i, [u8p, u8p, i, i, i, i, i, i, i, i, vp]),
         "mi_blur_cpu_run_morph": (i, [u8p, u8p, i, i, i, i, i, i, i, i]),
         "mi_blur_ctx_set_morph": (i, [vp, i, i, i]),
+        "mi_blur_bilateral_gauss": (i, [C.c_double, C.c_double, i, C.POINTER(Bilateral)]),
+        "mi_blur_enqueue_bilateral": (i, [u8p, u8p, i, i, i, i, C.POINTER(Bilateral), vp]),
+        "mi_blur_enqueue_bilateral_band": (i, [u8p, u8p, i, i, i, i, i, C.POINTER(Bilateral), vp]),
+        "mi_blur_cpu_run_bilateral": (i, [u8p, u8p, i, i, i, i, C.POINTER(Bilateral), i]),
+        "mi_blur_ctx_set_bilateral": (i, [vp, C.POINTER(Bilateral)]),
         "mi_blur_fill_synthetic": (None, [u8p, i, i, i, i, i, i]),
         "mi_blur_fnv1a64": (C.c_uint64, [u8p, C.c_size_t]),
         "mi_blur_debug_zc_trace": (i, [vp, C.POINTER(C.c_uint64), i, C.POINTER(i), C.POINTER(C.c_uint)]),
@@ -324,6 +364,11 @@ class Context:
         check(lib().mi_blur_ctx_set_morph(self.h, int(op), int(rx), int(ry)), "mi_blur_ctx_set_morph")
         self.morph = (int(op), int(rx), int(ry))
 
+    def set_bilateral(self, k: "Bilateral") -> None:
+        """The bilateral filter k in place of the blur, for every submit (before the first one only)."""
+        check(lib().mi_blur_ctx_set_bilateral(self.h, C.byref(k)), "mi_blur_ctx_set_bilateral")
+        self.bilateral = k
+
     def set_kernel(self, kernel: "SepKernel") -> None:
         """A separable kernel in place of the radius, for every submit (before the first one only)."""
         check(lib().mi_blur_ctx_set_kernel(self.h, C.byref(kernel)), "mi_blur_ctx_set_kernel")
@@ -425,7 +470,7 @@ def _images(images, name: str):
 
 
 def _filter_images(a, radius: int, device: int, batch: int, configure=None):
-    """The numpy driver of blur, gaussian_blur, median_blur and the morphology functions: a (from _images) through mi_blur_create (radius) /
+    """The numpy driver of blur, gaussian_blur, median_blur, the morphology functions and bilateral_filter: a (from _images) through mi_blur_create (radius) /
     configure(ctx) / mi_blur_submit / mi_blur_sync.  Returns the output as (N, H, W, C)."""
     import numpy as np
     if a.ndim == 2:
@@ -516,3 +561,21 @@ def dilate(images, ksize=3, device: int = 0, batch: int = 0):
 def morph_gradient(images, ksize=3, device: int = 0, batch: int = 0):
     """Morphological gradient: per channel the window maximum minus the window minimum; arguments as erode()."""
     return _morph("morph_gradient", MORPH_GRADIENT, images, ksize, device, batch)
+
+
+def bilateral_filter(images, ksize: int = 5, sigma_color: float = 25.0, sigma_space: float = 0.0, device: int = 0, batch: int = 0):
+    """Bilateral filter (edge-preserving smoothing) with a ksize x ksize window, numpy in -> numpy out, like blur().
+
+    ksize: odd, 3..17.  sigma_color: the range Gaussian's sigma in grey levels (> 0).  sigma_space: the spatial Gaussian's
+    sigma in pixels; <= 0 means ksize / 4.  The tables are integers (Bilateral.gauss), so the result is exact and the same
+    on every device.  Each channel is filtered on its own: for colour images this differs from OpenCV's bilateralFilter,
+    which measures the range distance in colour space.  images: (H, W), (H, W, C) or (N, H, W, C) uint8; the result has
+    the same shape.  device: HIP ordinal, or DEVICE_CPU.  Goes through mi_blur_create / mi_blur_ctx_set_bilateral /
+    mi_blur_submit / mi_blur_sync."""
+    if not isinstance(ksize, int) or isinstance(ksize, bool) or ksize % 2 != 1 or not 3 <= ksize <= 2 * BILATERAL_MAX_RADIUS + 1:
+        raise ValueError(f"bilateral_filter: ksize must be odd, 3..{2 * BILATERAL_MAX_RADIUS + 1}")
+    if not sigma_color > 0:
+        raise ValueError("bilateral_filter: sigma_color must be > 0")
+    a = _images(images, "bilateral_filter")
+    k = Bilateral.gauss(sigma_space if sigma_space > 0 else ksize / 4.0, sigma_color, ksize // 2)
+    return _filter_images(a, 1, device, batch, lambda ctx: ctx.set_bilateral(k)).reshape(a.shape)

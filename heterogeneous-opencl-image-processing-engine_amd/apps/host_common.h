@@ -166,6 +166,10 @@ struct Options {
     int median = 0;                      // --median K (odd, 3..15): the KxK median instead of --ksize; mi_blur_ctx_set_median on every context
     int morph = 0;                       // --erode K | --dilate K | --morph-gradient K (odd, 3..33): the KxK window minimum / maximum / their
     int morph_op = 0;                    //              difference instead of --ksize; mi_blur_ctx_set_morph on every context
+    int bilateral = 0;                   // --bilateral K (odd, 3..17): the KxK bilateral filter instead of --ksize; mi_blur_ctx_set_bilateral on every
+    double sigma_color = 25.0;           //              context.  --sigma-color S: the range sigma in grey levels; --sigma-space S: the spatial
+    double sigma_space = 0.0;            //              sigma in pixels, 0 = K/4
+    bool sigma_color_given = false, sigma_space_given = false;
     int images = 5000;                   // --images N   (NUM_IMAGES, heterogeneous_blur.c:44)
     bool images_given = false;
     int gpus = 1;                        // --gpus G
@@ -225,6 +229,12 @@ inline int parse_flags(int argc, char **argv, Options &o)
             o.morph_op = a == "--erode" ? MI_BLUR_MORPH_ERODE : a == "--dilate" ? MI_BLUR_MORPH_DILATE : MI_BLUR_MORPH_GRADIENT;
             if (o.morph < 3 || o.morph > 2 * MI_BLUR_MORPH_MAX_RADIUS + 1 || o.morph % 2 == 0) { printf("Error: %s must be odd, 3..%d\n", a.c_str(), 2 * MI_BLUR_MORPH_MAX_RADIUS + 1); exit(-1); }
         }
+        else if (a == "--bilateral") {
+            o.bilateral = atoi(next("--bilateral"));
+            if (o.bilateral < 3 || o.bilateral > 2 * MI_BLUR_BILATERAL_MAX_RADIUS + 1 || o.bilateral % 2 == 0) { printf("Error: --bilateral must be odd, 3..%d\n", 2 * MI_BLUR_BILATERAL_MAX_RADIUS + 1); exit(-1); }
+        }
+        else if (a == "--sigma-color") { o.sigma_color = atof(next("--sigma-color")); o.sigma_color_given = true; if (!(o.sigma_color > 0.0)) { printf("Error: --sigma-color must be > 0\n"); exit(-1); } }
+        else if (a == "--sigma-space") { o.sigma_space = atof(next("--sigma-space")); o.sigma_space_given = true; if (!(o.sigma_space >= 0.0)) { printf("Error: --sigma-space must be >= 0\n"); exit(-1); } }
         else if (a == "--sigma") { o.sigma = atof(next("--sigma")); if (!(o.sigma > 0.0)) { printf("Error: --sigma must be > 0\n"); exit(-1); } }
         else if (a == "--sigma-y") { o.sigma_y = atof(next("--sigma-y")); if (!(o.sigma_y > 0.0)) { printf("Error: --sigma-y must be > 0\n"); exit(-1); } }
         else if (a == "--radius") { o.sep_radius = atoi(next("--radius")); if (o.sep_radius < 1 || o.sep_radius > MI_BLUR_SEP_MAX_RADIUS) { printf("Error: --radius must be 1..%d\n", MI_BLUR_SEP_MAX_RADIUS); exit(-1); } }
@@ -257,10 +267,13 @@ inline int parse_flags(int argc, char **argv, Options &o)
     if (o.median && o.resident) { printf("Error: --median does not run --resident\n"); exit(-1); }
     if (o.morph && (o.ksize_given || o.sigma > 0.0 || o.median)) { printf("Error: --erode, --dilate and --morph-gradient exclude --ksize, --sigma and --median\n"); exit(-1); }
     if (o.morph && o.resident) { printf("Error: --erode, --dilate and --morph-gradient do not run --resident\n"); exit(-1); }
+    if (o.bilateral && (o.ksize_given || o.sigma > 0.0 || o.median || o.morph)) { printf("Error: --bilateral excludes --ksize, --sigma, --median, --erode, --dilate and --morph-gradient\n"); exit(-1); }
+    if (o.bilateral && o.resident) { printf("Error: --bilateral does not run --resident\n"); exit(-1); }
+    if (!o.bilateral && (o.sigma_color_given || o.sigma_space_given)) { printf("Error: --sigma-color and --sigma-space need --bilateral\n"); exit(-1); }
     return npos;
 }
 
-// The one filter every context of the run is given, from --ksize, --sigma, --median or --erode / --dilate / --morph-gradient
+// The one filter every context of the run is given, from --ksize, --sigma, --median, --erode / --dilate / --morph-gradient or --bilateral
 // (they exclude each other).
 struct HostFilter {
     int radius;                 // --ksize 3|5: 1|2.  Every context is created with it (1 under every other filter).
@@ -269,34 +282,43 @@ struct HostFilter {
     double sigma, sigma_y;
     int median;                 // --median K: the KxK median, radius K / 2; 0 = none
     int morph, morph_op;        // --erode | --dilate | --morph-gradient K: the KxK window extremum (mi_blur_morph_op), radius K / 2; 0 = none
+    int bilateral;              // --bilateral K: the KxK bilateral filter `bil` (mi_blur_bilateral_gauss), radius K / 2; 0 = none
+    double sigma_color, sigma_space;
+    mi_blur_bilateral bil;
 };
 
 inline HostFilter filter_of(const Options &o)
 {
-    HostFilter f{o.ksize == 3 ? 1 : 2, o.sigma > 0.0, {}, o.sigma, o.sigma_y, o.median, o.morph, o.morph_op};
+    HostFilter f{o.ksize == 3 ? 1 : 2, o.sigma > 0.0, {}, o.sigma, o.sigma_y, o.median, o.morph, o.morph_op, o.bilateral, o.sigma_color, o.sigma_space > 0.0 ? o.sigma_space : o.bilateral / 4.0, {}};
     if (f.sep && mi_blur_sep_kernel_gauss(o.sigma, o.sigma_y, o.sep_radius, 8, &f.k) != MI_BLUR_OK) {
         printf("Error: no Gaussian taps for sigma %g / %g, radius %d\n", o.sigma, o.sigma_y, o.sep_radius);
+        exit(-1);
+    }
+    if (f.bilateral && mi_blur_bilateral_gauss(f.sigma_space, f.sigma_color, f.bilateral / 2, &f.bil) != MI_BLUR_OK) {
+        printf("Error: no bilateral tables for sigma_color %g, sigma_space %g, window %d\n", f.sigma_color, f.sigma_space, f.bilateral);
         exit(-1);
     }
     return f;
 }
 
-// Give a context made with f.radius the filter (mi_blur_ctx_set_kernel / _set_median / _set_morph; nothing for --ksize).
+// Give a context made with f.radius the filter (mi_blur_ctx_set_kernel / _set_median / _set_morph / _set_bilateral; nothing for --ksize).
 inline void set_filter(mi_blur_ctx *ctx, const HostFilter &f)
 {
     if (f.sep) mi_check(mi_blur_ctx_set_kernel(ctx, &f.k), "Failed to set the blur kernel");
     if (f.median) mi_check(mi_blur_ctx_set_median(ctx, f.median / 2), "Failed to set the median");
     if (f.morph) mi_check(mi_blur_ctx_set_morph(ctx, f.morph_op, f.morph / 2, f.morph / 2), "Failed to set the morphology filter");
+    if (f.bilateral) mi_check(mi_blur_ctx_set_bilateral(ctx, &f.bil), "Failed to set the bilateral filter");
 }
 
-// Rows a band needs on each side: the median's or the morphology window's radius, the Gaussian's vertical radius (at least one row, so that the
+// Rows a band needs on each side: the median's, the morphology window's or the bilateral window's radius, the Gaussian's vertical radius (at least one row, so that the
 // split geometry stays the reference's), or the box radius.
-inline int filter_halo(const HostFilter &f) { return f.morph ? f.morph / 2 : f.median ? f.median / 2 : f.sep ? std::max(1, f.k.ry) : f.radius; }
+inline int filter_halo(const HostFilter &f) { return f.bilateral ? f.bilateral / 2 : f.morph ? f.morph / 2 : f.median ? f.median / 2 : f.sep ? std::max(1, f.k.ry) : f.radius; }
 
 // The banner's "Blur kernel" line (with the taps of a Gaussian).
 inline void print_filter(const HostFilter &f)
 {
     if (f.median) { printf("Blur kernel: %dx%d median\n", f.median, f.median); return; }
+    if (f.bilateral) { printf("Blur kernel: %dx%d bilateral (sigma_color %g, sigma_space %g)\n", f.bilateral, f.bilateral, f.sigma_color, f.sigma_space); return; }
     if (f.morph) {
         printf("Blur kernel: %dx%d %s\n", f.morph, f.morph,
                f.morph_op == MI_BLUR_MORPH_ERODE ? "erode" : f.morph_op == MI_BLUR_MORPH_DILATE ? "dilate" : "morphological gradient");

@@ -275,6 +275,34 @@ void cpu_morph_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, int op
     }
 }
 
+// The bilateral filter as include/mi_blur.h defines it: per output byte the taps of the window with a non-zero spatial
+// weight, 32-bit unsigned sums (exact: filter_bilateral bounds the spatial sum), one rounding division.
+void cpu_bilateral_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, const Filter &f, int y_begin, int y_end,
+                        int out_row_shift)
+{
+    const int pitch = W * C, r = f.bil_r;
+    for (int y = y_begin; y < y_end; y++) {
+        uint8_t *o = out + (size_t)(y - out_row_shift) * pitch;
+        for (int x = 0; x < W; x++) {
+            for (int c = 0; c < C; c++) {
+                const unsigned v0 = in[(size_t)y * pitch + (size_t)x * C + c];
+                uint32_t num = 0, den = 0;
+                for (int j = -r; j <= r; j++) {
+                    const uint8_t *row = in + (size_t)std::min(std::max(y + j, 0), H - 1) * pitch + c;
+                    const uint8_t *s = f.bil_s + (j + 8) * 17 + 8;
+                    for (int i = -r; i <= r; i++) {
+                        if (!s[i]) continue;
+                        const unsigned v = row[(size_t)std::min(std::max(x + i, 0), W - 1) * C];
+                        const uint32_t w = (uint32_t)s[i] * f.bil_range[v > v0 ? v - v0 : v0 - v];
+                        den += w; num += w * v;
+                    }
+                }
+                o[(size_t)x * C + c] = (uint8_t)((num + den / 2) / den);
+            }
+        }
+    }
+}
+
 // n_images bands of band_rows rows; output rows [y0,y1) of each.  Threads take whole
 // images when there are enough of them, else row slices of each image.
 void cpu_blur_batch(const uint8_t *in, uint8_t *out, int W, int band_rows, int C, const Filter &f, int n_images,
@@ -302,7 +330,8 @@ void cpu_blur_batch(const uint8_t *in, uint8_t *out, int W, int band_rows, int C
             const int ys = y0 + (int)((long long)rows * s / slices), ye = y0 + (int)((long long)rows * (s + 1) / slices);
             const uint8_t *src = in + img * in_stride;
             uint8_t *dst = out + img * out_stride;
-            if (f.kind == FilterKind::MORPH) cpu_morph_rows(src, dst, W, band_rows, C, f.morph_op, f.morph_rx, f.morph_ry, ys, ye, y0);
+            if (f.kind == FilterKind::BILATERAL) cpu_bilateral_rows(src, dst, W, band_rows, C, f, ys, ye, y0);
+            else if (f.kind == FilterKind::MORPH) cpu_morph_rows(src, dst, W, band_rows, C, f.morph_op, f.morph_rx, f.morph_ry, ys, ye, y0);
             else if (f.kind == FilterKind::MEDIAN) cpu_median_rows(src, dst, W, band_rows, C, f.radius, ys, ye, y0);
             else if (f.kind == FilterKind::SEP) cpu_blur_rows_sep(src, dst, W, band_rows, C, f.taps, ys, ye, y0);
             else cpu_blur_rows(src, dst, W, band_rows, C, f.radius, ys, ye, y0);

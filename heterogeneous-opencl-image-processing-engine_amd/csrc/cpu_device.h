@@ -18,6 +18,9 @@ void cpu_median_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, int R
 // Rows [y_begin, y_end) of the window minimum / maximum / gradient (mi_blur_morph_op) over (2 rx + 1) x (2 ry + 1).
 void cpu_morph_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, int op, int rx, int ry, int y_begin, int y_end,
                     int out_row_shift);
+// Rows [y_begin, y_end) of the bilateral filter of f (f.bil_r, f.bil_s, f.bil_range): plain integer loops, exact.
+void cpu_bilateral_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, const Filter &f, int y_begin, int y_end,
+                        int out_row_shift);
 void cpu_blur_batch(const uint8_t *in, uint8_t *out, int W, int band_rows, int C, const Filter &f, int n_images,
                     int y0, int y1, int n_threads, size_t in_stride = 0, size_t out_stride = 0);
 // The box blur of radius R (1|2): the form the host-only sanitizer harness (tests/san_cpu_device.cpp) drives.

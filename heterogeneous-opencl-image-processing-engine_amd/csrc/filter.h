@@ -1,5 +1,5 @@
 // filter.h — internal: the one filter a launch, a context or a CPU run applies, in the form the GPU kernels
-// (blur_kernels.hip, sep_kernels.hip, median_kernels.hip, morph_kernels.hip) and the CPU device (cpu_device.cpp) take it.  Plain C++, no HIP.
+// (blur_kernels.hip, sep_kernels.hip, median_kernels.hip, morph_kernels.hip, bilateral_kernels.hip) and the CPU device (cpu_device.cpp) take it.  Plain C++, no HIP.
 #pragma once
 
 #include "../../include/mi_blur.h"
@@ -15,15 +15,19 @@ struct SepTaps {
     unsigned wx[2 * SEP_MAX_R + 1], wy[2 * SEP_MAX_R + 1];
 };
 
-enum class FilterKind { BOX, SEP, MEDIAN, MORPH };
+enum class FilterKind { BOX, SEP, MEDIAN, MORPH, BILATERAL };
 
 // BOX: the fixed 3x3 / 5x5 kernel of `radius` 1|2.  SEP: the separable kernel `taps`.  MEDIAN: the median of `radius` 1..7.
 // MORPH: the window minimum / maximum / their difference (`morph_op`) over (2 morph_rx + 1) x (2 morph_ry + 1).
+// BILATERAL: the bilateral filter of radius `bil_r` with the spatial table `bil_s` (CENTRED in the 17 x 17 frame:
+// bil_s[(j + 8) * 17 + (i + 8)] = S[j][i], 0 beyond the radius) and the range table `bil_range`.
 struct Filter {
     FilterKind kind;
     int radius;             // BOX and MEDIAN
     SepTaps taps;           // SEP
-    int morph_op = 0, morph_rx = 0, morph_ry = 0;   // MORPH (mi_blur_morph_op, radii 0..16); last, so {kind, radius, taps} still initialises a Filter
+    int morph_op = 0, morph_rx = 0, morph_ry = 0;   // MORPH (mi_blur_morph_op, radii 0..16); after taps, so {kind, radius, taps} still initialises a Filter
+    int bil_r = 0;          // BILATERAL (radius 1..8)
+    uint8_t bil_s[17 * 17] = {}, bil_range[256] = {};
 };
 
 // The constructors validate: MI_BLUR_OK, or MI_BLUR_ERR_INVALID with *f untouched.
@@ -62,6 +66,22 @@ inline int filter_morph(int op, int rx, int ry, Filter *f)
     if (rx < 0 || rx > MI_BLUR_MORPH_MAX_RADIUS || ry < 0 || ry > MI_BLUR_MORPH_MAX_RADIUS) return MI_BLUR_ERR_INVALID;
     *f = Filter{FilterKind::MORPH, 0, {}};
     f->morph_op = op; f->morph_rx = rx; f->morph_ry = ry;
+    return MI_BLUR_OK;
+}
+
+inline int filter_bilateral(const mi_blur_bilateral *k, Filter *f)
+{
+    if (!k || !f) return MI_BLUR_ERR_INVALID;
+    const int r = k->radius, n = 2 * r + 1;
+    if (r < 1 || r > MI_BLUR_BILATERAL_MAX_RADIUS) return MI_BLUR_ERR_INVALID;
+    long long sum = 0;
+    for (int q = 0; q < n * n; q++) sum += k->spatial[q];
+    if (k->spatial[r * n + r] == 0 || k->range[0] == 0 || sum > 65535) return MI_BLUR_ERR_INVALID;
+    *f = Filter{FilterKind::BILATERAL, 0, {}};
+    f->bil_r = r;
+    for (int j = 0; j < n; j++)
+        for (int i = 0; i < n; i++) f->bil_s[(j - r + 8) * 17 + (i - r + 8)] = k->spatial[j * n + i];
+    for (int d = 0; d < 256; d++) f->bil_range[d] = k->range[d];
     return MI_BLUR_OK;
 }
 

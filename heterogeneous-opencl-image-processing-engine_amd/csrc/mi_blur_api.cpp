@@ -240,6 +240,43 @@ extern "C" int mi_blur_enqueue_morph(const uint8_t *d_in, uint8_t *d_out, int wi
     return enqueue_filter(f, d_in, d_out, width, height, channels, n_images, 0, height, MI_BLUR_VARIANT_AUTO, stream);
 }
 
+// ----------------------------------------------------------------------------------
+// bilateral filter, radius 1..8, integer tables (no reference analogue)
+// ----------------------------------------------------------------------------------
+extern "C" int mi_blur_bilateral_gauss(double sigma_space, double sigma_range, int radius, mi_blur_bilateral *k)
+{
+    if (!k || !(sigma_range > 0.0) || radius < 1 || radius > MI_BLUR_BILATERAL_MAX_RADIUS) return MI_BLUR_ERR_INVALID;
+    if (!(sigma_space > 0.0)) sigma_space = radius / 2.0;
+    mi_blur_bilateral g{};
+    g.radius = radius;
+    const int n = 2 * radius + 1;
+    for (int j = -radius; j <= radius; j++)
+        for (int i = -radius; i <= radius; i++)
+            g.spatial[(j + radius) * n + (i + radius)] =
+                (uint8_t)std::floor(128.0 * std::exp(-(double)(i * i + j * j) / (2.0 * sigma_space * sigma_space)) + 0.5);
+    for (int d = 0; d < 256; d++) g.range[d] = (uint8_t)std::floor(255.0 * std::exp(-(double)d * d / (2.0 * sigma_range * sigma_range)) + 0.5);
+    *k = g;
+    return MI_BLUR_OK;
+}
+
+extern "C" int mi_blur_enqueue_bilateral_band(const uint8_t *d_in, uint8_t *d_out, int width, int band_rows, int channels,
+                                              int out_row_begin, int out_row_end, const mi_blur_bilateral *k, void *stream)
+{
+    Filter f;
+    if (filter_bilateral(k, &f) || !d_in || !d_out || d_in == d_out || width <= 0 || band_rows <= 0 || channels <= 0)
+        return MI_BLUR_ERR_INVALID;
+    return enqueue_filter(f, d_in, d_out, width, band_rows, channels, 1, out_row_begin, out_row_end, MI_BLUR_VARIANT_AUTO, stream);
+}
+
+extern "C" int mi_blur_enqueue_bilateral(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int n_images,
+                                         const mi_blur_bilateral *k, void *stream)
+{
+    Filter f;
+    if (filter_bilateral(k, &f) || !d_in || !d_out || d_in == d_out || width <= 0 || height <= 0 || channels <= 0 || n_images < 0)
+        return MI_BLUR_ERR_INVALID;
+    return enqueue_filter(f, d_in, d_out, width, height, channels, n_images, 0, height, MI_BLUR_VARIANT_AUTO, stream);
+}
+
 // Frame layout on the device (replaces the host loops heterogeneous_blur.c:125-134 and split_image_blur.c:40-56).
 extern "C" int mi_blur_planar_to_interleaved(const uint8_t *d_planar, uint8_t *d_interleaved, int width, int height,
                                              int channels, int n_images, void *stream)
@@ -357,7 +394,7 @@ struct CpuWorker {
 
 struct mi_blur_ctx {
     int device = 0, W = 0, H = 0, C = 0, max_batch = 0, n_threads = 0;
-    Filter filter{};                                             // every submit applies it: mi_blur_create's radius, or set_kernel / set_median / set_morph
+    Filter filter{};                                             // every submit applies it: mi_blur_create's radius, or set_kernel / set_median / set_morph / set_bilateral
     size_t image_bytes = 0;
     std::vector<Slot> slots;
     int next_slot = 0;
@@ -395,7 +432,7 @@ struct mi_blur_ctx {
     // CPU device
     std::vector<CpuJob *> cpu_jobs;
     CpuWorker *cpu_worker = nullptr;
-    bool submitted = false;                                      // set_kernel / set_median / set_morph only before this
+    bool submitted = false;                                      // set_kernel / set_median / set_morph / set_bilateral only before this
     bool is_cpu() const { return device == MI_BLUR_DEVICE_CPU; }
 };
 
@@ -1199,6 +1236,17 @@ extern "C" int mi_blur_ctx_set_morph(mi_blur_ctx *c, int op, int rx, int ry)
     return MI_BLUR_OK;
 }
 
+// The bilateral filter *k in place of the context's blur, for every submit from now on (before the first one only).
+extern "C" int mi_blur_ctx_set_bilateral(mi_blur_ctx *c, const mi_blur_bilateral *k)
+{
+    if (!c) return MI_BLUR_ERR_INVALID;
+    if (c->submitted) return MI_BLUR_ERR_STATE;
+    Filter f;
+    if (filter_bilateral(k, &f)) return MI_BLUR_ERR_INVALID;
+    c->filter = f;
+    return MI_BLUR_OK;
+}
+
 // Wait for the OLDEST submit still in flight (its output is then in caller memory), so a host
 // that rotates n_slots batch buffers can refill the oldest one while the newer ones run.
 extern "C" int mi_blur_wait_oldest(mi_blur_ctx *c)
@@ -1552,7 +1600,7 @@ extern "C" int mi_blur_resident_peek(mi_blur_ctx *c, int pool_index, uint8_t *ho
 // ----------------------------------------------------------------------------------
 // CPU device kernel + helpers
 // ----------------------------------------------------------------------------------
-// Every failure here is MI_BLUR_ERR_INVALID, so the order of the checks does not show.  Only the separable, median and morphology runs
+// Every failure here is MI_BLUR_ERR_INVALID, so the order of the checks does not show.  Only the separable, median, morphology and bilateral runs
 // refuse images of more than INT_MAX bytes, as before.
 static int cpu_run_filter(const Filter &f, const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,
                           int n_threads)
@@ -1590,6 +1638,13 @@ extern "C" int mi_blur_cpu_run_morph(const uint8_t *in, uint8_t *out, int width,
 {
     Filter f;
     return filter_morph(op, rx, ry, &f) ? MI_BLUR_ERR_INVALID : cpu_run_filter(f, in, out, width, height, channels, n_images, n_threads);
+}
+
+extern "C" int mi_blur_cpu_run_bilateral(const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,
+                                         const mi_blur_bilateral *k, int n_threads)
+{
+    Filter f;
+    return filter_bilateral(k, &f) ? MI_BLUR_ERR_INVALID : cpu_run_filter(f, in, out, width, height, channels, n_images, n_threads);
 }
 
 extern "C" void mi_blur_fill_synthetic(uint8_t *host, int width, int height, int channels, int first_index,

@@ -67,7 +67,7 @@ int mi_blur_version(void);
 /* Which kernel the calling thread's most recent launch went to ("blur_tiled_kernel", "blur_direct_kernel",
  * "blur_fused_kernel", "blur_tiled_loop_kernel", "blur_stream_kernel", "blur_generic_kernel", "blur_sep_tiled_kernel",
  * "blur_sep_generic_kernel", "blur_median_fast_kernel", "blur_median_generic_kernel", "blur_morph_tiled_kernel",
- * "blur_morph_generic_kernel"; "" before the first):
+ * "blur_morph_generic_kernel", "blur_bilateral_tiled_kernel", "blur_bilateral_generic_kernel"; "" before the first):
  * reports name the kernel a profiler will show.  Static string, never NULL. */
 const char *mi_blur_last_kernel(void);
 
@@ -451,6 +451,52 @@ int mi_blur_cpu_run_morph(const uint8_t *in, uint8_t *out, int width, int height
  * MI_BLUR_ERR_UNSUPPORTED.  A context holds one filter: mi_blur_ctx_set_kernel, mi_blur_ctx_set_median and this call each
  * replace what another set before. */
 int mi_blur_ctx_set_morph(mi_blur_ctx *ctx, int op, int rx, int ry);
+
+/* ------------------------------------------------------------------------
+ * Bilateral filter, windows 3x3 to 17x17 (no reference analogue): the edge-preserving smoother.  Defined by two integer
+ * tables, so it is exact: a spatial table S over the (2r+1) x (2r+1) window, r in 1..MI_BLUR_BILATERAL_MAX_RADIUS, and a
+ * range table R over the absolute difference to the centre sample.  Per output byte, with v0 = in[y][x][c] and
+ * v = in[clamp(y+j, 0, H-1)][clamp(x+i, 0, W-1)][c] over -r <= i, j <= r (clamp-to-edge as everywhere else):
+ *   w   = S[j][i] * R[|v - v0|]
+ *   den = sum w          num = sum w * v
+ *   out[y][x][c] = (num + den / 2) / den          (unsigned integer division: round half up)
+ * Channels never mix: each channel is filtered on its own, like every other filter here.  For colour images this differs
+ * from OpenCV's bilateralFilter, which measures the range distance in colour space; for one channel the definition is
+ * the same up to the integer tables.  A valid kernel has S[0][0] > 0 and R[0] > 0 (so den >= 1) and sum S <= 65535 (so
+ * num + den / 2 < 2^32: 32-bit unsigned sums are exact).  A tap with S = 0 contributes nothing: a table zero-padded to a
+ * larger radius gives the same bytes, and an anisotropic or round window is zeros in the table.  The GPU and the CPU
+ * device agree byte for byte.
+ * ---------------------------------------------------------------------- */
+#define MI_BLUR_BILATERAL_MAX_RADIUS 8
+typedef struct mi_blur_bilateral {
+    int radius;                       /* r in 1..8: window (2r+1) x (2r+1) */
+    uint8_t spatial[17 * 17];         /* S[j][i] at spatial[(j + r) * (2r + 1) + (i + r)], -r <= i, j <= r; rest ignored */
+    uint8_t range[256];               /* R[d], d = |neighbour - centre| */
+} mi_blur_bilateral;
+
+/* Gaussian tables, computed in double: S[j][i] = floor(128 exp(-(i^2 + j^2) / (2 sigma_space^2)) + 0.5),
+ * R[d] = floor(255 exp(-d^2 / (2 sigma_range^2)) + 0.5); sigma_space <= 0 means radius / 2.0.  The centre is 128 and R[0]
+ * is 255 by construction.  MI_BLUR_ERR_INVALID: sigma_range <= 0, a radius outside 1..8, a null k. */
+int mi_blur_bilateral_gauss(double sigma_space, double sigma_range, int radius, mi_blur_bilateral *k);
+
+/* mi_blur_enqueue / mi_blur_enqueue_band with that bilateral filter (same buffers, same band semantics: clamping at the
+ * band's own edges, only rows [out_row_begin, out_row_end) written; asynchronous; n_images == 0 is MI_BLUR_OK).  The tables
+ * travel in the kernel arguments: nothing is allocated, nothing needs freeing, *k may change as soon as the call returns.
+ * Rows of whole 16-byte chunks at 16-byte aligned addresses with 1-4 channels take blur_bilateral_tiled_kernel at every
+ * radius, every other case blur_bilateral_generic_kernel.  MI_BLUR_ERR_INVALID (before MI_BLUR_ERR_NO_DEVICE): a null k, a
+ * radius outside 1..8, S[0][0] == 0, R[0] == 0, sum S > 65535, null or equal buffers, non-positive sizes. */
+int mi_blur_enqueue_bilateral(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int n_images,
+                              const mi_blur_bilateral *k, void *stream);
+int mi_blur_enqueue_bilateral_band(const uint8_t *d_in, uint8_t *d_out, int width, int band_rows, int channels,
+                                   int out_row_begin, int out_row_end, const mi_blur_bilateral *k, void *stream);
+/* mi_blur_cpu_run with the bilateral filter (plain integer loops, exact). */
+int mi_blur_cpu_run_bilateral(const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,
+                              const mi_blur_bilateral *k, int n_threads);
+/* Give a context that bilateral filter in place of its blur, with the rules of mi_blur_ctx_set_median: only before the
+ * first submit (MI_BLUR_ERR_STATE after), every submit form then uses it, never through the batch server, resident runs
+ * MI_BLUR_ERR_UNSUPPORTED.  A context holds one filter: mi_blur_ctx_set_kernel, mi_blur_ctx_set_median,
+ * mi_blur_ctx_set_morph and this call each replace what another set before.  The context keeps a copy. */
+int mi_blur_ctx_set_bilateral(mi_blur_ctx *ctx, const mi_blur_bilateral *k);
 
 /* Developer diagnostics.  With mi_blur_set_option("debug_xcd_times", 1) every workgroup of the tiled kernel leaves its
  * start and end time (100 MHz ticks) in a slot of the XCD it ran on; this call waits for the device, returns per XCD the

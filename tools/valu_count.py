@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Static instruction counts of the hot kernels from the gfx950 assembly (hipcc -S): VALU / LDS / VMEM per wave and VALU
 per output dword (the unrolled row loop is straight-line code; a thread writes rows_per_thread x 4 output dwords).
-    python tools/valu_count.py > profiles/<tag>_valu_counts.txt          (build container, no GPU needed)"""
+    python tools/valu_count.py > profiles/<tag>_valu_counts.txt          (build container, no GPU needed)
+    python tools/valu_count.py --bilateral      the window-row loop of blur_bilateral_tiled_kernel<3, RC>: VALU and ds_read
+                                                per output byte and window row, and per tap of the class's 2 RC + 1 columns"""
 import os, re, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "heterogeneous-opencl-image-processing-engine_amd", "csrc", "blur_kernels.hip")
@@ -40,5 +42,27 @@ def main():
               f"v_pk_mad {c('v_pk_mad'):4d}  ds_read {c('ds_read'):3d}  vmem {c('global_') + c('buffer_'):3d}  s_waitcnt {c('s_waitcnt'):3d}")
 
 
+def bilateral():
+    src = os.path.join(os.path.dirname(SRC), "bilateral_kernels.hip")
+    with tempfile.TemporaryDirectory() as d:
+        out = os.path.join(d, "k.s")
+        subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-o", out, src],
+                       check=True, stderr=subprocess.DEVNULL)
+        text = open(out).read().splitlines()
+    print("blur_bilateral_tiled_kernel<C, RC>, gfx950, hipcc -O3: the window-row loop (one pass = one window row of one output dword = 4 output bytes)")
+    for ch in (1, 3, 4):
+        for rc in (2, 4, 8):
+            sym = f"_ZN7mi_blur12_GLOBAL__N_127blur_bilateral_tiled_kernelILi{ch}ELi{rc}EEEvNS0_14BilTiledParamsIXT0_EEE"
+            a = next(i for i, l in enumerate(text) if l.startswith(sym + ":"))
+            b = next(i for i in range(a, len(text)) if text[i].startswith(".Lfunc_end"))
+            la = next(i for i in range(a, b) if "Inner Loop Header: Depth=2" in text[i])
+            lb = next(i for i in range(la, b) if "s_cbranch" in text[i])
+            ops = [l.split()[0] for l in text[la:lb + 1] if re.match(r"^\s+[a-z]", l)]
+            valu, ds, gather = sum(o.startswith("v_") for o in ops), sum(o.startswith("ds_read") for o in ops), sum(o == "ds_read_u8" for o in ops)
+            cols = 2 * rc + 1
+            print(f"C={ch} RC={rc}: per row pass VALU {valu:4d}  ds_read {ds:3d} (of them ds_read_u8 {gather:3d})  s_waitcnt {sum(o == 's_waitcnt' for o in ops):2d}"
+                  f"   per output byte and row: VALU {valu / 4:6.1f}  ds_read {ds / 4:5.1f}   per tap of the {cols} columns: VALU {valu / 4 / cols:4.2f}  ds_read {ds / 4 / cols:4.2f}")
+
+
 if __name__ == "__main__":
-    main()
+    bilateral() if "--bilateral" in sys.argv[1:] else main()
