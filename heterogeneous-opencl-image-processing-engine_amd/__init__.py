@@ -36,6 +36,11 @@ MEDIAN_MAX_RADIUS = 7
 MORPH_MAX_RADIUS = 16
 MORPH_ERODE, MORPH_DILATE, MORPH_GRADIENT = 0, 1, 2
 BILATERAL_MAX_RADIUS = 8
+CONV_MAX_RADIUS = 7
+CONV_SAT, CONV_ABS, CONV_MAG = 0, 1, 2
+CONV_MODES = {"sat": CONV_SAT, "abs": CONV_ABS, "mag": CONV_MAG}
+CONV_PRESETS = {"sobel_x": 0, "sobel_y": 1, "sobel_mag": 2, "scharr_x": 3, "scharr_y": 4, "scharr_mag": 5,
+                "laplacian4": 6, "laplacian8": 7, "sharpen": 8, "emboss": 9}
 PEER_HANDLE_BYTES = 64
 
 
@@ -48,7 +53,7 @@ def _newer(target: str, sources: list[str]) -> bool:
 
 def build_native(force: bool = False, verbose: bool = False) -> str:
     """Compile libmi_blur.so (hipcc, --offload-arch=gfx950) and the C++ hosts, in-tree."""
-    srcs = [os.path.join(CSRC, f) for f in ("blur_kernels.hip", "sep_kernels.hip", "median_kernels.hip", "morph_kernels.hip", "bilateral_kernels.hip", "layout_kernels.hip", "mi_blur_api.cpp", "cpu_device.cpp")]
+    srcs = [os.path.join(CSRC, f) for f in ("blur_kernels.hip", "sep_kernels.hip", "median_kernels.hip", "morph_kernels.hip", "bilateral_kernels.hip", "conv_kernels.hip", "layout_kernels.hip", "mi_blur_api.cpp", "cpu_device.cpp")]
     deps = srcs + [os.path.join(CSRC, f) for f in ("blur_launch.h", "kernel_common.h", "cpu_device.h", "filter.h")] + [HEADER]
     if force or not _newer(LIB_PATH, deps):
         cmd = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra",
@@ -154,6 +159,59 @@ class Bilateral(C.Structure):
         return k
 
 
+class Conv(C.Structure):
+    """mi_blur_conv: radii rx, ry (0..7), a mode (CONV_SAT | CONV_ABS | CONV_MAG), a shift (0..16), a bias and the signed
+    16-bit taps K (and K2 for CONV_MAG), row-major at the front of `k` / `k2`.  Correlation: no flip."""
+    _fields_ = [("rx", C.c_int), ("ry", C.c_int), ("mode", C.c_int), ("shift", C.c_int), ("bias", C.c_int32),
+                ("k", C.c_int16 * (15 * 15)), ("k2", C.c_int16 * (15 * 15))]
+
+    @classmethod
+    def from_taps(cls, kernel_2d, shift: int = 0, bias: int = 0, mode="sat", kernel2_2d=None) -> "Conv":
+        """kernel_2d: (2 ry + 1) rows of (2 rx + 1) integer taps, radii 0..7; kernel2_2d (mode "mag" only): the second
+        table, same shape.  mode: "sat" | "abs" | "mag" or a CONV_* value.  The library validates the rest (shift, bias,
+        sum |K| <= 65535) when the kernel is used."""
+        m = CONV_MODES.get(mode, mode) if isinstance(mode, str) else mode
+        if m not in (CONV_SAT, CONV_ABS, CONV_MAG):
+            raise ValueError('Conv.from_taps: mode is "sat", "abs" or "mag"')
+        if (kernel2_2d is not None) != (m == CONV_MAG):
+            raise ValueError('Conv.from_taps: kernel2_2d goes with mode "mag", and only with it')
+        k = cls()
+        shape = None
+        for name, table in (("k", kernel_2d), ("k2", kernel2_2d)):
+            if table is None:
+                continue
+            rows = [list(row) for row in table]
+            ny, nx = len(rows), len(rows[0]) if rows else 0
+            if ny % 2 != 1 or nx % 2 != 1 or ny > 2 * CONV_MAX_RADIUS + 1 or nx > 2 * CONV_MAX_RADIUS + 1 or any(len(r) != nx for r in rows):
+                raise ValueError(f"Conv.from_taps: a table has odd sides, 1..{2 * CONV_MAX_RADIUS + 1}")
+            if shape is not None and shape != (ny, nx):
+                raise ValueError("Conv.from_taps: kernel2_2d has the shape of kernel_2d")
+            shape = (ny, nx)
+            raw = [v for row in rows for v in row]
+            flat = [int(v) for v in raw]
+            if any(f != v for f, v in zip(flat, raw)) or any(not -32768 <= f <= 32767 for f in flat):
+                raise ValueError("Conv.from_taps: taps are integers -32768..32767")
+            getattr(k, name)[:nx * ny] = flat
+        k.ry, k.rx = shape[0] // 2, shape[1] // 2
+        k.mode, k.shift, k.bias = int(m), int(shift), int(bias)
+        return k
+
+    @classmethod
+    def preset(cls, name: str) -> "Conv":
+        """A ready 3x3 kernel (mi_blur_conv_preset): one of CONV_PRESETS' names."""
+        if name not in CONV_PRESETS:
+            raise ValueError(f"Conv.preset: one of {sorted(CONV_PRESETS)}")
+        k = cls()
+        check(lib().mi_blur_conv_preset(CONV_PRESETS[name], C.byref(k)), "mi_blur_conv_preset")
+        return k
+
+    def taps(self):
+        """(K, K2) as lists of rows; K2 is None unless the mode is CONV_MAG."""
+        nx, ny = 2 * self.rx + 1, 2 * self.ry + 1
+        t = lambda a: [list(a[j * nx:(j + 1) * nx]) for j in range(ny)]
+        return t(self.k), t(self.k2) if self.mode == CONV_MAG else None
+
+
 class MiBlurError(RuntimeError):
     def __init__(self, status: int, what: str):
         super().__init__(f"{what}: status {status} ({lib().mi_blur_strerror(status).decode()})")
@@ -242,6 +300,11 @@ def lib() -> C.CDLL:
         "mi_blur_enqueue_bilateral_band": (i, [u8p, u8p, i, i, i, i, i, C.POINTER(Bilateral), vp]),
         "mi_blur_cpu_run_bilateral": (i, [u8p, u8p, i, i, i, i, C.POINTER(Bilateral), i]),
         "mi_blur_ctx_set_bilateral": (i, [vp, C.POINTER(Bilateral)]),
+        "mi_blur_conv_preset": (i, [i, C.POINTER(Conv)]),
+        "mi_blur_enqueue_conv": (i, [u8p, u8p, i, i, i, i, C.POINTER(Conv), vp]),
+        "mi_blur_enqueue_conv_band": (i, [u8p, u8p, i, i, i, i, i, C.POINTER(Conv), vp]),
+        "mi_blur_cpu_run_conv": (i, [u8p, u8p, i, i, i, i, C.POINTER(Conv), i]),
+        "mi_blur_ctx_set_conv": (i, [vp, C.POINTER(Conv)]),
         "mi_blur_fill_synthetic": (None, [u8p, i, i, i, i, i, i]),
         "mi_blur_fnv1a64": (C.c_uint64, [u8p, C.c_size_t]),
         "mi_blur_debug_zc_trace": (i, [vp, C.POINTER(C.c_uint64), i, C.POINTER(i), C.POINTER(C.c_uint)]),
@@ -369,6 +432,11 @@ class Context:
         check(lib().mi_blur_ctx_set_bilateral(self.h, C.byref(k)), "mi_blur_ctx_set_bilateral")
         self.bilateral = k
 
+    def set_conv(self, k: "Conv") -> None:
+        """The signed 2-D convolution k in place of the blur, for every submit (before the first one only)."""
+        check(lib().mi_blur_ctx_set_conv(self.h, C.byref(k)), "mi_blur_ctx_set_conv")
+        self.conv = k
+
     def set_kernel(self, kernel: "SepKernel") -> None:
         """A separable kernel in place of the radius, for every submit (before the first one only)."""
         check(lib().mi_blur_ctx_set_kernel(self.h, C.byref(kernel)), "mi_blur_ctx_set_kernel")
@@ -470,7 +538,7 @@ def _images(images, name: str):
 
 
 def _filter_images(a, radius: int, device: int, batch: int, configure=None):
-    """The numpy driver of blur, gaussian_blur, median_blur, the morphology functions and bilateral_filter: a (from _images) through mi_blur_create (radius) /
+    """The numpy driver of blur, gaussian_blur, median_blur, the morphology functions, bilateral_filter and the convolutions: a (from _images) through mi_blur_create (radius) /
     configure(ctx) / mi_blur_submit / mi_blur_sync.  Returns the output as (N, H, W, C)."""
     import numpy as np
     if a.ndim == 2:
@@ -579,3 +647,50 @@ def bilateral_filter(images, ksize: int = 5, sigma_color: float = 25.0, sigma_sp
     a = _images(images, "bilateral_filter")
     k = Bilateral.gauss(sigma_space if sigma_space > 0 else ksize / 4.0, sigma_color, ksize // 2)
     return _filter_images(a, 1, device, batch, lambda ctx: ctx.set_bilateral(k)).reshape(a.shape)
+
+
+def _conv(name: str, images, k: "Conv", device: int, batch: int):
+    a = _images(images, name)
+    return _filter_images(a, 1, device, batch, lambda ctx: ctx.set_conv(k)).reshape(a.shape)
+
+
+def filter2d(images, kernel, shift: int = 0, bias: int = 0, mode: str = "sat", kernel2=None, device: int = 0, batch: int = 0):
+    """2-D correlation with signed integer taps (OpenCV filter2D's convention: no flip), numpy in -> numpy out, like blur().
+
+    kernel: rows of integer taps, odd sides up to 15 x 15, sum |K| <= 65535.  Per channel acc = sum K * window;
+    mode "sat": clamp((acc + bias) >> shift), "abs": clamp((|acc| + bias) >> shift), "mag" (with kernel2, same shape):
+    clamp((|acc| + |acc2| + bias) >> shift), each clamped to 0..255; the shift is a floor.  Edges clamp.  images: (H, W),
+    (H, W, C) or (N, H, W, C) uint8; the result has the same shape.  device: HIP ordinal, or DEVICE_CPU.  Goes through
+    mi_blur_create / mi_blur_ctx_set_conv / mi_blur_submit / mi_blur_sync."""
+    import numpy as np
+    tab = lambda t: None if t is None else np.asarray(t).tolist()
+    k = Conv.from_taps(tab(kernel), shift, bias, mode, tab(kernel2))
+    return _conv("filter2d", images, k, device, batch)
+
+
+def _gradient(name: str, images, axis: str, device: int, batch: int):
+    if axis not in ("x", "y", "mag"):
+        raise ValueError(f'{name}: axis is "x", "y" or "mag"')
+    return _conv(name, images, Conv.preset(f"{name}_{axis}"), device, batch)
+
+
+def sobel(images, axis: str = "mag", device: int = 0, batch: int = 0):
+    """Sobel edge map: axis "x" | "y": min(255, |gradient|) along that axis; "mag": min(255, |gx| + |gy|).  Arguments as filter2d()."""
+    return _gradient("sobel", images, axis, device, batch)
+
+
+def scharr(images, axis: str = "mag", device: int = 0, batch: int = 0):
+    """Scharr edge map (taps 3, 10, 3): axis as sobel()."""
+    return _gradient("scharr", images, axis, device, batch)
+
+
+def laplacian(images, connectivity: int = 4, device: int = 0, batch: int = 0):
+    """min(255, |Laplacian|) with the 4- or the 8-neighbour 3x3 kernel.  Arguments as filter2d()."""
+    if connectivity not in (4, 8):
+        raise ValueError("laplacian: connectivity is 4 or 8")
+    return _conv("laplacian", images, Conv.preset(f"laplacian{connectivity}"), device, batch)
+
+
+def sharpen(images, device: int = 0, batch: int = 0):
+    """The 3x3 sharpening kernel [0 -1 0; -1 5 -1; 0 -1 0], saturated to 0..255.  Arguments as filter2d()."""
+    return _conv("sharpen", images, Conv.preset("sharpen"), device, batch)

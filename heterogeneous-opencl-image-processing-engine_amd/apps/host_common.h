@@ -170,6 +170,8 @@ struct Options {
     double sigma_color = 25.0;           //              context.  --sigma-color S: the range sigma in grey levels; --sigma-space S: the spatial
     double sigma_space = 0.0;            //              sigma in pixels, 0 = K/4
     bool sigma_color_given = false, sigma_space_given = false;
+    std::string conv;                    // --conv NAME (sobel-x | sobel-y | sobel | scharr-x | scharr-y | scharr | laplacian | laplacian8 | sharpen |
+    int conv_preset = -1;                //              emboss): that 3x3 convolution instead of --ksize; mi_blur_ctx_set_conv on every context
     int images = 5000;                   // --images N   (NUM_IMAGES, heterogeneous_blur.c:44)
     bool images_given = false;
     int gpus = 1;                        // --gpus G
@@ -233,6 +235,13 @@ inline int parse_flags(int argc, char **argv, Options &o)
             o.bilateral = atoi(next("--bilateral"));
             if (o.bilateral < 3 || o.bilateral > 2 * MI_BLUR_BILATERAL_MAX_RADIUS + 1 || o.bilateral % 2 == 0) { printf("Error: --bilateral must be odd, 3..%d\n", 2 * MI_BLUR_BILATERAL_MAX_RADIUS + 1); exit(-1); }
         }
+        else if (a == "--conv") {
+            static const char *const names[] = {"sobel-x", "sobel-y", "sobel", "scharr-x", "scharr-y", "scharr", "laplacian", "laplacian8", "sharpen", "emboss"};
+            o.conv = next("--conv");
+            o.conv_preset = -1;
+            for (int q = 0; q < 10; q++) if (o.conv == names[q]) o.conv_preset = q;      // the order of mi_blur_conv_preset_id
+            if (o.conv_preset < 0) { printf("Error: --conv sobel-x|sobel-y|sobel|scharr-x|scharr-y|scharr|laplacian|laplacian8|sharpen|emboss\n"); exit(-1); }
+        }
         else if (a == "--sigma-color") { o.sigma_color = atof(next("--sigma-color")); o.sigma_color_given = true; if (!(o.sigma_color > 0.0)) { printf("Error: --sigma-color must be > 0\n"); exit(-1); } }
         else if (a == "--sigma-space") { o.sigma_space = atof(next("--sigma-space")); o.sigma_space_given = true; if (!(o.sigma_space >= 0.0)) { printf("Error: --sigma-space must be >= 0\n"); exit(-1); } }
         else if (a == "--sigma") { o.sigma = atof(next("--sigma")); if (!(o.sigma > 0.0)) { printf("Error: --sigma must be > 0\n"); exit(-1); } }
@@ -270,10 +279,12 @@ inline int parse_flags(int argc, char **argv, Options &o)
     if (o.bilateral && (o.ksize_given || o.sigma > 0.0 || o.median || o.morph)) { printf("Error: --bilateral excludes --ksize, --sigma, --median, --erode, --dilate and --morph-gradient\n"); exit(-1); }
     if (o.bilateral && o.resident) { printf("Error: --bilateral does not run --resident\n"); exit(-1); }
     if (!o.bilateral && (o.sigma_color_given || o.sigma_space_given)) { printf("Error: --sigma-color and --sigma-space need --bilateral\n"); exit(-1); }
+    if (o.conv_preset >= 0 && (o.ksize_given || o.sigma > 0.0 || o.median || o.morph || o.bilateral)) { printf("Error: --conv excludes --ksize, --sigma, --median, --erode, --dilate, --morph-gradient and --bilateral\n"); exit(-1); }
+    if (o.conv_preset >= 0 && o.resident) { printf("Error: --conv does not run --resident\n"); exit(-1); }
     return npos;
 }
 
-// The one filter every context of the run is given, from --ksize, --sigma, --median, --erode / --dilate / --morph-gradient or --bilateral
+// The one filter every context of the run is given, from --ksize, --sigma, --median, --erode / --dilate / --morph-gradient, --bilateral or --conv
 // (they exclude each other).
 struct HostFilter {
     int radius;                 // --ksize 3|5: 1|2.  Every context is created with it (1 under every other filter).
@@ -285,11 +296,14 @@ struct HostFilter {
     int bilateral;              // --bilateral K: the KxK bilateral filter `bil` (mi_blur_bilateral_gauss), radius K / 2; 0 = none
     double sigma_color, sigma_space;
     mi_blur_bilateral bil;
+    int conv_preset;            // --conv NAME: the 3x3 convolution `conv` (mi_blur_conv_preset) called `conv_name`; -1 = none
+    std::string conv_name;
+    mi_blur_conv conv;
 };
 
 inline HostFilter filter_of(const Options &o)
 {
-    HostFilter f{o.ksize == 3 ? 1 : 2, o.sigma > 0.0, {}, o.sigma, o.sigma_y, o.median, o.morph, o.morph_op, o.bilateral, o.sigma_color, o.sigma_space > 0.0 ? o.sigma_space : o.bilateral / 4.0, {}};
+    HostFilter f{o.ksize == 3 ? 1 : 2, o.sigma > 0.0, {}, o.sigma, o.sigma_y, o.median, o.morph, o.morph_op, o.bilateral, o.sigma_color, o.sigma_space > 0.0 ? o.sigma_space : o.bilateral / 4.0, {}, o.conv_preset, o.conv, {}};
     if (f.sep && mi_blur_sep_kernel_gauss(o.sigma, o.sigma_y, o.sep_radius, 8, &f.k) != MI_BLUR_OK) {
         printf("Error: no Gaussian taps for sigma %g / %g, radius %d\n", o.sigma, o.sigma_y, o.sep_radius);
         exit(-1);
@@ -298,26 +312,32 @@ inline HostFilter filter_of(const Options &o)
         printf("Error: no bilateral tables for sigma_color %g, sigma_space %g, window %d\n", f.sigma_color, f.sigma_space, f.bilateral);
         exit(-1);
     }
+    if (f.conv_preset >= 0 && mi_blur_conv_preset(f.conv_preset, &f.conv) != MI_BLUR_OK) {
+        printf("Error: no convolution kernel %s\n", f.conv_name.c_str());
+        exit(-1);
+    }
     return f;
 }
 
-// Give a context made with f.radius the filter (mi_blur_ctx_set_kernel / _set_median / _set_morph / _set_bilateral; nothing for --ksize).
+// Give a context made with f.radius the filter (mi_blur_ctx_set_kernel / _set_median / _set_morph / _set_bilateral / _set_conv; nothing for --ksize).
 inline void set_filter(mi_blur_ctx *ctx, const HostFilter &f)
 {
     if (f.sep) mi_check(mi_blur_ctx_set_kernel(ctx, &f.k), "Failed to set the blur kernel");
     if (f.median) mi_check(mi_blur_ctx_set_median(ctx, f.median / 2), "Failed to set the median");
     if (f.morph) mi_check(mi_blur_ctx_set_morph(ctx, f.morph_op, f.morph / 2, f.morph / 2), "Failed to set the morphology filter");
     if (f.bilateral) mi_check(mi_blur_ctx_set_bilateral(ctx, &f.bil), "Failed to set the bilateral filter");
+    if (f.conv_preset >= 0) mi_check(mi_blur_ctx_set_conv(ctx, &f.conv), "Failed to set the convolution");
 }
 
-// Rows a band needs on each side: the median's, the morphology window's or the bilateral window's radius, the Gaussian's vertical radius (at least one row, so that the
+// Rows a band needs on each side: the convolution's vertical radius, the median's, the morphology window's or the bilateral window's radius, the Gaussian's vertical radius (at least one row, so that the
 // split geometry stays the reference's), or the box radius.
-inline int filter_halo(const HostFilter &f) { return f.bilateral ? f.bilateral / 2 : f.morph ? f.morph / 2 : f.median ? f.median / 2 : f.sep ? std::max(1, f.k.ry) : f.radius; }
+inline int filter_halo(const HostFilter &f) { return f.conv_preset >= 0 ? f.conv.ry : f.bilateral ? f.bilateral / 2 : f.morph ? f.morph / 2 : f.median ? f.median / 2 : f.sep ? std::max(1, f.k.ry) : f.radius; }
 
 // The banner's "Blur kernel" line (with the taps of a Gaussian).
 inline void print_filter(const HostFilter &f)
 {
     if (f.median) { printf("Blur kernel: %dx%d median\n", f.median, f.median); return; }
+    if (f.conv_preset >= 0) { printf("Blur kernel: %dx%d convolution (%s)\n", 2 * f.conv.rx + 1, 2 * f.conv.ry + 1, f.conv_name.c_str()); return; }
     if (f.bilateral) { printf("Blur kernel: %dx%d bilateral (sigma_color %g, sigma_space %g)\n", f.bilateral, f.bilateral, f.sigma_color, f.sigma_space); return; }
     if (f.morph) {
         printf("Blur kernel: %dx%d %s\n", f.morph, f.morph,

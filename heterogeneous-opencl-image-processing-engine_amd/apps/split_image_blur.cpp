@@ -1,6 +1,6 @@
 // split_image_blur — Approach 2 (split-image + halo) host, MI355X-native.
 //
-//   split_image_blur [gpu_ratio] [batch]  [--image F | --synthetic | --size WxH] [--channels C] [--ksize 3|5 | --sigma S [--sigma-y S] [--radius R] | --median K | --erode K | --dilate K | --morph-gradient K | --bilateral K [--sigma-color S] [--sigma-space S]]
+//   split_image_blur [gpu_ratio] [batch]  [--image F | --synthetic | --size WxH] [--channels C] [--ksize 3|5 | --sigma S [--sigma-y S] [--radius R] | --median K | --erode K | --dilate K | --morph-gradient K | --bilateral K [--sigma-color S] [--sigma-space S] | --conv NAME]
 //                    [--images N] [--gpus G] [--slots S] [--threads T] [--verbose] [--csv FILE] [--save FILE]
 //   split_image_blur --resident [--gpus G] [--size WxH] [--ksize 3|5] [--iters N] [--iterate] [--overlap]
 //                    [--transport rccl|p2p|pull|peer] [--save FILE]
@@ -73,7 +73,7 @@ int main(int argc, char **argv)
     printf("Work-group size: %dx%d\n", local_work_size, local_work_size);
     printf("GPU ratio: %.1f%% (rows to GPU)\n", gpu_ratio * 100);
     printf("Halo size: %d row(s)\n", HALO);
-    if (filter.sep || filter.median || filter.morph || filter.bilateral) print_filter(filter);
+    if (filter.sep || filter.median || filter.morph || filter.bilateral || filter.conv_preset >= 0) print_filter(filter);
     printf("================================================\n\n");
 
     // ---------------- load original image (split_image_blur.c:106-139)

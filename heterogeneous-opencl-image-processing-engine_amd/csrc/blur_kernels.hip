@@ -1544,9 +1544,10 @@ int launch(const LaunchDesc &d)
     if (d.filter->kind == FilterKind::MEDIAN) return launch_median(d);
     if (d.filter->kind == FilterKind::MORPH) return launch_morph(d);
     if (d.filter->kind == FilterKind::BILATERAL) return launch_bilateral(d);
+    if (d.filter->kind == FilterKind::CONV) return launch_conv(d);
     if (const int st = check_desc(d, FilterKind::BOX)) return st;
     if (d.filter->radius != 1 && d.filter->radius != 2) return MI_BLUR_ERR_INVALID;
-    if (d.n_images == 0) return MI_BLUR_OK;           // before the strides are looked at (launch_sep / launch_median / launch_morph / launch_bilateral: after)
+    if (d.n_images == 0) return MI_BLUR_OK;           // before the strides are looked at (launch_sep / launch_median / launch_morph / launch_bilateral / launch_conv: after)
     const Tunables tun = tunables();                  // one coherent set of knobs for this launch
     const bool wide = wide_channels(d.channels, d.filter->radius);
     const long long row_bytes = (long long)d.width * d.channels;

@@ -1,5 +1,5 @@
 // blur_launch.h — internal (not part of the C ABI): launch interface between
-// mi_blur_api.cpp and the gfx950 kernels in the six .hip files (what those share among themselves: kernel_common.h).
+// mi_blur_api.cpp and the gfx950 kernels in the seven .hip files (what those share among themselves: kernel_common.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -28,7 +28,7 @@ struct LaunchDesc {
 };
 
 // Returns MI_BLUR_OK or a negative mi_blur_status.  A SEP filter is handed to launch_sep, a MEDIAN one to launch_median,
-// a MORPH one to launch_morph, a BILATERAL one to launch_bilateral;
+// a MORPH one to launch_morph, a BILATERAL one to launch_bilateral, a CONV one to launch_conv;
 // launch_fused and zc_fill_batch take BOX filters only.
 int launch(const LaunchDesc &d);
 // Separable kernel of d.filter->taps (sep_kernels.hip): the aligned LDS-tiled kernel or the generic one.  Honours in/out strides,
@@ -47,6 +47,10 @@ int launch_morph(const LaunchDesc &d);
 // in the kernel arguments.  Honours in/out strides, bands [y0, y1) and the 64-bit image offsets of launch(); ignores
 // max_blocks, concurrent and variant (AUTO); halo_top / halo_bottom: MI_BLUR_ERR_UNSUPPORTED.
 int launch_bilateral(const LaunchDesc &d);
+// Signed 2-D convolution of d.filter (conv_kernels.hip): the aligned LDS-tiled kernel or the generic one; the taps travel in
+// the kernel arguments.  Honours in/out strides, bands [y0, y1) and the 64-bit image offsets of launch(); ignores
+// max_blocks, concurrent and variant (AUTO); halo_top / halo_bottom: MI_BLUR_ERR_UNSUPPORTED.
+int launch_conv(const LaunchDesc &d);
 // Sets what last_kernel() reports for the calling thread.
 void set_last_kernel(const char *name);
 

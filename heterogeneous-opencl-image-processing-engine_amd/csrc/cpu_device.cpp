@@ -303,6 +303,43 @@ void cpu_bilateral_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, co
     }
 }
 
+// The signed convolution as include/mi_blur.h defines it: per output row an int32 accumulator row; per window row an
+// edge-replicated copy of the (clamped) source row, then one multiply-add pass along it per non-zero tap.
+void cpu_conv_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, const Filter &f, int y_begin, int y_end,
+                   int out_row_shift)
+{
+    const int pitch = W * C, rx = f.conv_rx, ry = f.conv_ry, pad = rx * C;
+    const bool mag = f.conv_mode == MI_BLUR_CONV_MAG;
+    std::vector<uint8_t> rowbuf((size_t)pitch + 2 * pad);
+    std::vector<int32_t> accbuf(2 * (size_t)pitch);
+    uint8_t *v = rowbuf.data() + pad;                    // v[-pad .. pitch + pad)
+    int32_t *acc = accbuf.data(), *acc2 = acc + pitch;
+    for (int y = y_begin; y < y_end; y++) {
+        std::fill(accbuf.begin(), accbuf.end(), 0);
+        for (int j = -ry; j <= ry; j++) {
+            memcpy(v, in + (size_t)std::min(std::max(y + j, 0), H - 1) * pitch, pitch);
+            for (int q = 1; q <= pad; q++) { v[-q] = v[((-q % C) + C) % C]; v[pitch + q - 1] = v[pitch - C + ((q - 1) % C)]; }
+            for (int t = 0; t < (mag ? 2 : 1); t++) {
+                const int16_t *k = f.conv_k[t] + (j + 7) * 15 + 7;
+                int32_t *a = t ? acc2 : acc;
+                for (int i = -rx; i <= rx; i++) {
+                    const int32_t w = k[i];
+                    if (!w) continue;
+                    const uint8_t *s = v + i * C;
+                    for (int b = 0; b < pitch; b++) a[b] += w * s[b];
+                }
+            }
+        }
+        uint8_t *o = out + (size_t)(y - out_row_shift) * pitch;
+        for (int b = 0; b < pitch; b++) {
+            int32_t a = f.conv_mode == MI_BLUR_CONV_SAT ? acc[b] : std::abs(acc[b]);
+            if (mag) a += std::abs(acc2[b]);
+            a = (a + f.conv_bias) >> f.conv_shift;       // arithmetic shift: the floor
+            o[b] = (uint8_t)std::min(std::max(a, 0), 255);
+        }
+    }
+}
+
 // n_images bands of band_rows rows; output rows [y0,y1) of each.  Threads take whole
 // images when there are enough of them, else row slices of each image.
 void cpu_blur_batch(const uint8_t *in, uint8_t *out, int W, int band_rows, int C, const Filter &f, int n_images,
@@ -330,7 +367,8 @@ void cpu_blur_batch(const uint8_t *in, uint8_t *out, int W, int band_rows, int C
             const int ys = y0 + (int)((long long)rows * s / slices), ye = y0 + (int)((long long)rows * (s + 1) / slices);
             const uint8_t *src = in + img * in_stride;
             uint8_t *dst = out + img * out_stride;
-            if (f.kind == FilterKind::BILATERAL) cpu_bilateral_rows(src, dst, W, band_rows, C, f, ys, ye, y0);
+            if (f.kind == FilterKind::CONV) cpu_conv_rows(src, dst, W, band_rows, C, f, ys, ye, y0);
+            else if (f.kind == FilterKind::BILATERAL) cpu_bilateral_rows(src, dst, W, band_rows, C, f, ys, ye, y0);
             else if (f.kind == FilterKind::MORPH) cpu_morph_rows(src, dst, W, band_rows, C, f.morph_op, f.morph_rx, f.morph_ry, ys, ye, y0);
             else if (f.kind == FilterKind::MEDIAN) cpu_median_rows(src, dst, W, band_rows, C, f.radius, ys, ye, y0);
             else if (f.kind == FilterKind::SEP) cpu_blur_rows_sep(src, dst, W, band_rows, C, f.taps, ys, ye, y0);

@@ -19,6 +19,9 @@ void cpu_median_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, int R
 void cpu_morph_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, int op, int rx, int ry, int y_begin, int y_end,
                     int out_row_shift);
 // Rows [y_begin, y_end) of the bilateral filter of f (f.bil_r, f.bil_s, f.bil_range): plain integer loops, exact.
+// Rows [y_begin, y_end) of the signed convolution of f (f.conv_*): plain integer loops, exact.
+void cpu_conv_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, const Filter &f, int y_begin, int y_end,
+                   int out_row_shift);
 void cpu_bilateral_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, const Filter &f, int y_begin, int y_end,
                         int out_row_shift);
 void cpu_blur_batch(const uint8_t *in, uint8_t *out, int W, int band_rows, int C, const Filter &f, int n_images,

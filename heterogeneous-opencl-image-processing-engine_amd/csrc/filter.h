@@ -1,5 +1,5 @@
 // filter.h — internal: the one filter a launch, a context or a CPU run applies, in the form the GPU kernels
-// (blur_kernels.hip, sep_kernels.hip, median_kernels.hip, morph_kernels.hip, bilateral_kernels.hip) and the CPU device (cpu_device.cpp) take it.  Plain C++, no HIP.
+// (blur_kernels.hip, sep_kernels.hip, median_kernels.hip, morph_kernels.hip, bilateral_kernels.hip, conv_kernels.hip) and the CPU device (cpu_device.cpp) take it.  Plain C++, no HIP.
 #pragma once
 
 #include "../../include/mi_blur.h"
@@ -15,12 +15,14 @@ struct SepTaps {
     unsigned wx[2 * SEP_MAX_R + 1], wy[2 * SEP_MAX_R + 1];
 };
 
-enum class FilterKind { BOX, SEP, MEDIAN, MORPH, BILATERAL };
+enum class FilterKind { BOX, SEP, MEDIAN, MORPH, BILATERAL, CONV };
 
 // BOX: the fixed 3x3 / 5x5 kernel of `radius` 1|2.  SEP: the separable kernel `taps`.  MEDIAN: the median of `radius` 1..7.
 // MORPH: the window minimum / maximum / their difference (`morph_op`) over (2 morph_rx + 1) x (2 morph_ry + 1).
 // BILATERAL: the bilateral filter of radius `bil_r` with the spatial table `bil_s` (CENTRED in the 17 x 17 frame:
 // bil_s[(j + 8) * 17 + (i + 8)] = S[j][i], 0 beyond the radius) and the range table `bil_range`.
+// CONV: the signed 2-D convolution (mi_blur_conv) of radii `conv_rx`, `conv_ry` with the taps CENTRED in the 15 x 15 frame:
+// conv_k[t][(j + 7) * 15 + (i + 7)] = K[j][i] (t = 0) or K2[j][i] (t = 1, MAG only; zeros otherwise), 0 beyond the radii.
 struct Filter {
     FilterKind kind;
     int radius;             // BOX and MEDIAN
@@ -28,6 +30,9 @@ struct Filter {
     int morph_op = 0, morph_rx = 0, morph_ry = 0;   // MORPH (mi_blur_morph_op, radii 0..16); after taps, so {kind, radius, taps} still initialises a Filter
     int bil_r = 0;          // BILATERAL (radius 1..8)
     uint8_t bil_s[17 * 17] = {}, bil_range[256] = {};
+    int conv_rx = 0, conv_ry = 0, conv_mode = 0, conv_shift = 0;   // CONV (radii 0..7, mi_blur_conv_mode, shift 0..16)
+    int32_t conv_bias = 0;
+    int16_t conv_k[2][15 * 15] = {};
 };
 
 // The constructors validate: MI_BLUR_OK, or MI_BLUR_ERR_INVALID with *f untouched.
@@ -82,6 +87,27 @@ inline int filter_bilateral(const mi_blur_bilateral *k, Filter *f)
     for (int j = 0; j < n; j++)
         for (int i = 0; i < n; i++) f->bil_s[(j - r + 8) * 17 + (i - r + 8)] = k->spatial[j * n + i];
     for (int d = 0; d < 256; d++) f->bil_range[d] = k->range[d];
+    return MI_BLUR_OK;
+}
+
+inline int filter_conv(const mi_blur_conv *k, Filter *f)
+{
+    if (!k || !f) return MI_BLUR_ERR_INVALID;
+    if (k->mode != MI_BLUR_CONV_SAT && k->mode != MI_BLUR_CONV_ABS && k->mode != MI_BLUR_CONV_MAG) return MI_BLUR_ERR_INVALID;
+    if (k->rx < 0 || k->rx > MI_BLUR_CONV_MAX_RADIUS || k->ry < 0 || k->ry > MI_BLUR_CONV_MAX_RADIUS) return MI_BLUR_ERR_INVALID;
+    if (k->shift < 0 || k->shift > 16 || k->bias > (1 << 24) || k->bias < -(1 << 24)) return MI_BLUR_ERR_INVALID;
+    const int nx = 2 * k->rx + 1, ny = 2 * k->ry + 1, tables = k->mode == MI_BLUR_CONV_MAG ? 2 : 1;
+    for (int t = 0; t < tables; t++) {
+        const int16_t *src = t ? k->k2 : k->k;
+        long long sum = 0;
+        for (int q = 0; q < nx * ny; q++) sum += src[q] < 0 ? -(long long)src[q] : src[q];
+        if (sum > 65535) return MI_BLUR_ERR_INVALID;
+    }
+    *f = Filter{FilterKind::CONV, 0, {}};
+    f->conv_rx = k->rx; f->conv_ry = k->ry; f->conv_mode = k->mode; f->conv_shift = k->shift; f->conv_bias = k->bias;
+    for (int t = 0; t < tables; t++)
+        for (int j = 0; j < ny; j++)
+            for (int i = 0; i < nx; i++) f->conv_k[t][(j - k->ry + 7) * 15 + (i - k->rx + 7)] = (t ? k->k2 : k->k)[j * nx + i];
     return MI_BLUR_OK;
 }
 

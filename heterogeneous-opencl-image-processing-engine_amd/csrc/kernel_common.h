@@ -1,5 +1,5 @@
-// kernel_common.h — internal (not part of the C ABI): what the six kernel files (blur_kernels.hip, sep_kernels.hip,
-// median_kernels.hip, morph_kernels.hip, bilateral_kernels.hip, layout_kernels.hip) share below launch(): the launch call, the blockIdx -> tile maps, the template
+// kernel_common.h — internal (not part of the C ABI): what the seven kernel files (blur_kernels.hip, sep_kernels.hip,
+// median_kernels.hip, morph_kernels.hip, bilateral_kernels.hip, conv_kernels.hip, layout_kernels.hip) share below launch(): the launch call, the blockIdx -> tile maps, the template
 // dispatch, the argument checks and parameter fill every family repeats, and the host side of the direct layout.
 // Everything here has internal linkage, so libmi_blur.so exports nothing from it.
 #pragma once
@@ -76,7 +76,7 @@ static int dispatch(int v, F &&f)
     return status;
 }
 
-// The argument checks launch(), launch_sep(), launch_median(), launch_morph() and launch_bilateral() share; every one of them is MI_BLUR_ERR_INVALID.
+// The argument checks launch(), launch_sep(), launch_median(), launch_morph(), launch_bilateral() and launch_conv() share; every one of them is MI_BLUR_ERR_INVALID.
 // What differs between the families (radius / taps, halo rows, strides, where n_images == 0 is answered) stays in them.
 static inline int check_desc(const LaunchDesc &d, FilterKind kind)
 {

@@ -277,6 +277,60 @@ extern "C" int mi_blur_enqueue_bilateral(const uint8_t *d_in, uint8_t *d_out, in
     return enqueue_filter(f, d_in, d_out, width, height, channels, n_images, 0, height, MI_BLUR_VARIANT_AUTO, stream);
 }
 
+// ----------------------------------------------------------------------------------
+// 2-D convolution with signed integer taps, radii 0..7 per axis (no reference analogue)
+// ----------------------------------------------------------------------------------
+extern "C" int mi_blur_conv_preset(int preset, mi_blur_conv *k)
+{
+    static const int16_t SOBEL[9] = {-1, 0, 1, -2, 0, 2, -1, 0, 1}, SCHARR[9] = {-3, 0, 3, -10, 0, 10, -3, 0, 3};
+    static const int16_t LAP4[9] = {0, 1, 0, 1, -4, 1, 0, 1, 0}, LAP8[9] = {1, 1, 1, 1, -8, 1, 1, 1, 1};
+    static const int16_t SHARPEN[9] = {0, -1, 0, -1, 5, -1, 0, -1, 0}, EMBOSS[9] = {-2, -1, 0, -1, 1, 1, 0, 1, 2};
+    if (!k || preset < MI_BLUR_CONV_SOBEL_X || preset > MI_BLUR_CONV_EMBOSS) return MI_BLUR_ERR_INVALID;
+    mi_blur_conv g{};
+    g.rx = g.ry = 1;
+    g.mode = MI_BLUR_CONV_ABS;
+    const int16_t *x = nullptr, *y = nullptr;           // x: taken as is; y: taken transposed
+    switch (preset) {
+    case MI_BLUR_CONV_SOBEL_X: x = SOBEL; break;
+    case MI_BLUR_CONV_SOBEL_Y: y = SOBEL; break;
+    case MI_BLUR_CONV_SOBEL_MAG: x = y = SOBEL; g.mode = MI_BLUR_CONV_MAG; break;
+    case MI_BLUR_CONV_SCHARR_X: x = SCHARR; break;
+    case MI_BLUR_CONV_SCHARR_Y: y = SCHARR; break;
+    case MI_BLUR_CONV_SCHARR_MAG: x = y = SCHARR; g.mode = MI_BLUR_CONV_MAG; break;
+    case MI_BLUR_CONV_LAPLACIAN4: x = LAP4; break;
+    case MI_BLUR_CONV_LAPLACIAN8: x = LAP8; break;
+    case MI_BLUR_CONV_SHARPEN: x = SHARPEN; g.mode = MI_BLUR_CONV_SAT; break;
+    default: x = EMBOSS; g.mode = MI_BLUR_CONV_SAT; g.bias = 128; break;
+    }
+    int16_t *ydst = x ? g.k2 : g.k;                     // the y table is the second one only beside an x table
+    for (int j = 0; j < 3; j++)
+        for (int i = 0; i < 3; i++) {
+            if (x) g.k[j * 3 + i] = x[j * 3 + i];
+            if (y) ydst[j * 3 + i] = y[i * 3 + j];
+        }
+    *k = g;
+    return MI_BLUR_OK;
+}
+
+extern "C" int mi_blur_enqueue_conv_band(const uint8_t *d_in, uint8_t *d_out, int width, int band_rows, int channels,
+                                         int out_row_begin, int out_row_end, const mi_blur_conv *k, void *stream)
+{
+    Filter f;
+    if (filter_conv(k, &f) || !d_in || !d_out || d_in == d_out || width <= 0 || band_rows <= 0 || channels <= 0 ||
+        out_row_begin < 0 || out_row_end > band_rows || out_row_begin >= out_row_end)
+        return MI_BLUR_ERR_INVALID;
+    return enqueue_filter(f, d_in, d_out, width, band_rows, channels, 1, out_row_begin, out_row_end, MI_BLUR_VARIANT_AUTO, stream);
+}
+
+extern "C" int mi_blur_enqueue_conv(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int n_images,
+                                    const mi_blur_conv *k, void *stream)
+{
+    Filter f;
+    if (filter_conv(k, &f) || !d_in || !d_out || d_in == d_out || width <= 0 || height <= 0 || channels <= 0 || n_images < 0)
+        return MI_BLUR_ERR_INVALID;
+    return enqueue_filter(f, d_in, d_out, width, height, channels, n_images, 0, height, MI_BLUR_VARIANT_AUTO, stream);
+}
+
 // Frame layout on the device (replaces the host loops heterogeneous_blur.c:125-134 and split_image_blur.c:40-56).
 extern "C" int mi_blur_planar_to_interleaved(const uint8_t *d_planar, uint8_t *d_interleaved, int width, int height,
                                              int channels, int n_images, void *stream)
@@ -394,7 +448,7 @@ struct CpuWorker {
 
 struct mi_blur_ctx {
     int device = 0, W = 0, H = 0, C = 0, max_batch = 0, n_threads = 0;
-    Filter filter{};                                             // every submit applies it: mi_blur_create's radius, or set_kernel / set_median / set_morph / set_bilateral
+    Filter filter{};                                             // every submit applies it: mi_blur_create's radius, or set_kernel / set_median / set_morph / set_bilateral / set_conv
     size_t image_bytes = 0;
     std::vector<Slot> slots;
     int next_slot = 0;
@@ -432,7 +486,7 @@ struct mi_blur_ctx {
     // CPU device
     std::vector<CpuJob *> cpu_jobs;
     CpuWorker *cpu_worker = nullptr;
-    bool submitted = false;                                      // set_kernel / set_median / set_morph / set_bilateral only before this
+    bool submitted = false;                                      // set_kernel / set_median / set_morph / set_bilateral / set_conv only before this
     bool is_cpu() const { return device == MI_BLUR_DEVICE_CPU; }
 };
 
@@ -1247,6 +1301,17 @@ extern "C" int mi_blur_ctx_set_bilateral(mi_blur_ctx *c, const mi_blur_bilateral
     return MI_BLUR_OK;
 }
 
+// The convolution *k in place of the context's blur, for every submit from now on (before the first one only).
+extern "C" int mi_blur_ctx_set_conv(mi_blur_ctx *c, const mi_blur_conv *k)
+{
+    if (!c) return MI_BLUR_ERR_INVALID;
+    if (c->submitted) return MI_BLUR_ERR_STATE;
+    Filter f;
+    if (filter_conv(k, &f)) return MI_BLUR_ERR_INVALID;
+    c->filter = f;
+    return MI_BLUR_OK;
+}
+
 // Wait for the OLDEST submit still in flight (its output is then in caller memory), so a host
 // that rotates n_slots batch buffers can refill the oldest one while the newer ones run.
 extern "C" int mi_blur_wait_oldest(mi_blur_ctx *c)
@@ -1600,7 +1665,7 @@ extern "C" int mi_blur_resident_peek(mi_blur_ctx *c, int pool_index, uint8_t *ho
 // ----------------------------------------------------------------------------------
 // CPU device kernel + helpers
 // ----------------------------------------------------------------------------------
-// Every failure here is MI_BLUR_ERR_INVALID, so the order of the checks does not show.  Only the separable, median, morphology and bilateral runs
+// Every failure here is MI_BLUR_ERR_INVALID, so the order of the checks does not show.  Only the separable, median, morphology, bilateral and convolution runs
 // refuse images of more than INT_MAX bytes, as before.
 static int cpu_run_filter(const Filter &f, const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,
                           int n_threads)
@@ -1645,6 +1710,13 @@ extern "C" int mi_blur_cpu_run_bilateral(const uint8_t *in, uint8_t *out, int wi
 {
     Filter f;
     return filter_bilateral(k, &f) ? MI_BLUR_ERR_INVALID : cpu_run_filter(f, in, out, width, height, channels, n_images, n_threads);
+}
+
+extern "C" int mi_blur_cpu_run_conv(const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,
+                                    const mi_blur_conv *k, int n_threads)
+{
+    Filter f;
+    return filter_conv(k, &f) ? MI_BLUR_ERR_INVALID : cpu_run_filter(f, in, out, width, height, channels, n_images, n_threads);
 }
 
 extern "C" void mi_blur_fill_synthetic(uint8_t *host, int width, int height, int channels, int first_index,

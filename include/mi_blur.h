@@ -67,7 +67,8 @@ int mi_blur_version(void);
 /* Which kernel the calling thread's most recent launch went to ("blur_tiled_kernel", "blur_direct_kernel",
  * "blur_fused_kernel", "blur_tiled_loop_kernel", "blur_stream_kernel", "blur_generic_kernel", "blur_sep_tiled_kernel",
  * "blur_sep_generic_kernel", "blur_median_fast_kernel", "blur_median_generic_kernel", "blur_morph_tiled_kernel",
- * "blur_morph_generic_kernel", "blur_bilateral_tiled_kernel", "blur_bilateral_generic_kernel"; "" before the first):
+ * "blur_morph_generic_kernel", "blur_bilateral_tiled_kernel", "blur_bilateral_generic_kernel", "blur_conv_tiled_kernel",
+ * "blur_conv_generic_kernel"; "" before the first):
  * reports name the kernel a profiler will show.  Static string, never NULL. */
 const char *mi_blur_last_kernel(void);
 
@@ -497,6 +498,66 @@ int mi_blur_cpu_run_bilateral(const uint8_t *in, uint8_t *out, int width, int he
  * MI_BLUR_ERR_UNSUPPORTED.  A context holds one filter: mi_blur_ctx_set_kernel, mi_blur_ctx_set_median,
  * mi_blur_ctx_set_morph and this call each replace what another set before.  The context keeps a copy. */
 int mi_blur_ctx_set_bilateral(mi_blur_ctx *ctx, const mi_blur_bilateral *k);
+
+/* ------------------------------------------------------------------------
+ * 2-D convolution with signed integer taps, windows up to 15x15 (no reference analogue): derivatives and edge maps (Sobel,
+ * Scharr, Laplacian), sharpening, emboss, or any kernel the caller writes down.  Radii rx, ry in
+ * 0..MI_BLUR_CONV_MAX_RADIUS, independent per axis; taps K[j][i], -ry <= j <= ry, -rx <= i <= rx, signed 16-bit.
+ * This is CORRELATION, not flipped convolution (OpenCV filter2D's convention): K[j][i] multiplies the sample j rows
+ * below and i columns to the right.  Clamp-to-edge as everywhere else; channels never mix.  Exact, in integers:
+ *   acc  = sum_{j,i} K[j][i]  * in[clamp(y+j, 0, H-1)][clamp(x+i, 0, W-1)][c]          (int32)
+ *   acc2 = sum_{j,i} K2[j][i] * in[...]                                                 (MAG only, same radii)
+ *   MI_BLUR_CONV_SAT : out = clamp( floor((acc + bias)            / 2^shift), 0, 255)
+ *   MI_BLUR_CONV_ABS : out = clamp( floor((|acc| + bias)          / 2^shift), 0, 255)
+ *   MI_BLUR_CONV_MAG : out = clamp( floor((|acc| + |acc2| + bias) / 2^shift), 0, 255)
+ * bias is added before the shift (floor: towards minus infinity): rounding is bias = 1 << (shift - 1), an output offset of
+ * 128 is 128 << shift; with bias = 0 the shift truncates like the blur kernels', so {1,2,1} x {1,2,1} with shift 4 in SAT
+ * mode gives the bytes of radius 1.  A kernel is valid when the mode is known, 0 <= shift <= 16, |bias| <= 2^24 and
+ * sum |K| <= 65535 (the same for K2 in MAG; k2 is ignored otherwise): then |acc| < 2^24, every intermediate stays below
+ * 2^27, and 24-bit multiplies with 32-bit sums are exact.  An all-zero kernel is valid.  A table zero-padded to larger
+ * radii gives the same bytes.  The GPU and the CPU device agree byte for byte.
+ * ---------------------------------------------------------------------- */
+#define MI_BLUR_CONV_MAX_RADIUS 7
+typedef enum mi_blur_conv_mode { MI_BLUR_CONV_SAT = 0, MI_BLUR_CONV_ABS = 1, MI_BLUR_CONV_MAG = 2 } mi_blur_conv_mode;
+typedef struct mi_blur_conv {
+    int rx, ry;                       /* window (2 rx + 1) columns x (2 ry + 1) rows, each radius 0..7 */
+    int mode;                         /* mi_blur_conv_mode */
+    int shift;                        /* 0..16 */
+    int32_t bias;                     /* |bias| <= 2^24, added before the shift */
+    int16_t k[15 * 15], k2[15 * 15];  /* K[j][i] at k[(j + ry) * (2 rx + 1) + (i + rx)]; rest ignored; k2: MAG only */
+} mi_blur_conv;
+
+/* Ready kernels, 3x3, which the caller may then edit (all shift 0):
+ *   SOBEL_X [-1 0 1; -2 0 2; -1 0 1] ABS     SOBEL_Y its transpose, ABS     SOBEL_MAG both, MAG
+ *   SCHARR_X [-3 0 3; -10 0 10; -3 0 3] ABS  SCHARR_Y its transpose, ABS    SCHARR_MAG both, MAG
+ *   LAPLACIAN4 [0 1 0; 1 -4 1; 0 1 0] ABS    LAPLACIAN8 [1 1 1; 1 -8 1; 1 1 1] ABS
+ *   SHARPEN [0 -1 0; -1 5 -1; 0 -1 0] SAT    EMBOSS [-2 -1 0; -1 1 1; 0 1 2] SAT, bias 128 */
+typedef enum mi_blur_conv_preset_id {
+    MI_BLUR_CONV_SOBEL_X = 0, MI_BLUR_CONV_SOBEL_Y = 1, MI_BLUR_CONV_SOBEL_MAG = 2,
+    MI_BLUR_CONV_SCHARR_X = 3, MI_BLUR_CONV_SCHARR_Y = 4, MI_BLUR_CONV_SCHARR_MAG = 5,
+    MI_BLUR_CONV_LAPLACIAN4 = 6, MI_BLUR_CONV_LAPLACIAN8 = 7, MI_BLUR_CONV_SHARPEN = 8, MI_BLUR_CONV_EMBOSS = 9
+} mi_blur_conv_preset_id;
+/* MI_BLUR_ERR_INVALID: an unknown preset, a null k. */
+int mi_blur_conv_preset(int preset, mi_blur_conv *k);
+
+/* mi_blur_enqueue / mi_blur_enqueue_band with that convolution (same buffers, same band semantics: clamping at the band's
+ * own edges, only rows [out_row_begin, out_row_end) written; asynchronous; n_images == 0 is MI_BLUR_OK).  The tables travel
+ * in the kernel arguments: nothing is allocated, *k may change as soon as the call returns.  Rows of whole 16-byte chunks
+ * at 16-byte aligned addresses with 1-4 channels take blur_conv_tiled_kernel at every radius pair, every other case
+ * blur_conv_generic_kernel.  MI_BLUR_ERR_INVALID (before MI_BLUR_ERR_NO_DEVICE): a null or invalid k, null or equal
+ * buffers, non-positive sizes. */
+int mi_blur_enqueue_conv(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int n_images,
+                         const mi_blur_conv *k, void *stream);
+int mi_blur_enqueue_conv_band(const uint8_t *d_in, uint8_t *d_out, int width, int band_rows, int channels,
+                              int out_row_begin, int out_row_end, const mi_blur_conv *k, void *stream);
+/* mi_blur_cpu_run with the convolution (plain integer loops, exact). */
+int mi_blur_cpu_run_conv(const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,
+                         const mi_blur_conv *k, int n_threads);
+/* Give a context that convolution in place of its blur, with the rules of mi_blur_ctx_set_bilateral: only before the
+ * first submit (MI_BLUR_ERR_STATE after), every submit form then uses it, never through the batch server, resident runs
+ * MI_BLUR_ERR_UNSUPPORTED.  It replaces what another setter set before.  The context keeps a copy.  A caller that works
+ * in bands needs a halo of ry rows. */
+int mi_blur_ctx_set_conv(mi_blur_ctx *ctx, const mi_blur_conv *k);
 
 /* Developer diagnostics.  With mi_blur_set_option("debug_xcd_times", 1) every workgroup of the tiled kernel leaves its
  * start and end time (100 MHz ticks) in a slot of the XCD it ran on; this call waits for the device, returns per XCD the
