@@ -31,25 +31,16 @@ struct LaunchDesc {
 // a MORPH one to launch_morph, a BILATERAL one to launch_bilateral, a CONV one to launch_conv;
 // launch_fused and zc_fill_batch take BOX filters only.
 int launch(const LaunchDesc &d);
-// Separable kernel of d.filter->taps (sep_kernels.hip): the aligned LDS-tiled kernel or the generic one.  Honours in/out strides,
-// bands [y0, y1) and the per-image 32-bit offsets of launch(); ignores max_blocks, concurrent and variant (AUTO);
-// halo_top / halo_bottom: MI_BLUR_ERR_UNSUPPORTED.
+// The other families, each in the .hip file of its name: the separable kernel of d.filter->taps, the median of
+// d.filter->radius, the window minimum / maximum / gradient, the bilateral filter and the signed 2-D convolution of
+// d.filter (the last two carry their tables in the kernel arguments).  Each chooses between its fast kernel for rows of
+// whole 16-byte chunks, 1-4 channels, aligned buffers and strides (LDS-tiled; the median's register-window kernel, radius
+// 1|2 only) and its generic one.  All honour in/out strides, bands [y0, y1) and the 64-bit image offsets of launch();
+// ignore max_blocks, concurrent and variant (AUTO); halo_top / halo_bottom: MI_BLUR_ERR_UNSUPPORTED.
 int launch_sep(const LaunchDesc &d);
-// Median of radius d.filter->radius (median_kernels.hip): the register-window kernel for radius 1|2 on aligned rows of
-// 1-4 channels, the generic one otherwise.  Honours in/out strides, bands [y0, y1) and the 64-bit image offsets of
-// launch(); ignores max_blocks, concurrent and variant (AUTO); halo_top / halo_bottom: MI_BLUR_ERR_UNSUPPORTED.
 int launch_median(const LaunchDesc &d);
-// Window minimum / maximum / gradient of d.filter (morph_kernels.hip): the aligned LDS-tiled kernel or the generic one.
-// Honours in/out strides, bands [y0, y1) and the 64-bit image offsets of launch(); ignores max_blocks, concurrent and
-// variant (AUTO); halo_top / halo_bottom: MI_BLUR_ERR_UNSUPPORTED.
 int launch_morph(const LaunchDesc &d);
-// Bilateral filter of d.filter (bilateral_kernels.hip): the aligned LDS-tiled kernel or the generic one; the tables travel
-// in the kernel arguments.  Honours in/out strides, bands [y0, y1) and the 64-bit image offsets of launch(); ignores
-// max_blocks, concurrent and variant (AUTO); halo_top / halo_bottom: MI_BLUR_ERR_UNSUPPORTED.
 int launch_bilateral(const LaunchDesc &d);
-// Signed 2-D convolution of d.filter (conv_kernels.hip): the aligned LDS-tiled kernel or the generic one; the taps travel in
-// the kernel arguments.  Honours in/out strides, bands [y0, y1) and the 64-bit image offsets of launch(); ignores
-// max_blocks, concurrent and variant (AUTO); halo_top / halo_bottom: MI_BLUR_ERR_UNSUPPORTED.
 int launch_conv(const LaunchDesc &d);
 // Sets what last_kernel() reports for the calling thread.
 void set_last_kernel(const char *name);

@@ -1,6 +1,7 @@
 // kernel_common.h — internal (not part of the C ABI): what the seven kernel files (blur_kernels.hip, sep_kernels.hip,
 // median_kernels.hip, morph_kernels.hip, bilateral_kernels.hip, conv_kernels.hip, layout_kernels.hip) share below launch(): the launch call, the blockIdx -> tile maps, the template
-// dispatch, the argument checks and parameter fill every family repeats, and the host side of the direct layout.
+// dispatch, the argument checks and parameter fill every family repeats, the host side of the direct layout, and the
+// LDS tile of the sep, morph, bilateral and conv kernels (its coordinates, its staging, its launch geometry).
 // Everything here has internal linkage, so libmi_blur.so exports nothing from it.
 #pragma once
 #include "blur_launch.h"
@@ -42,6 +43,122 @@ __device__ __forceinline__ unsigned xcd_map(unsigned L, unsigned n, int mode)
     return mode == 0 ? L : mode == 1 ? xcd_contiguous(L, n) : xcd_runs(L, n, (unsigned)mode);
 }
 
+__device__ __forceinline__ u16x2 pk16(uint32_t x) { return __builtin_bit_cast(u16x2, x); }
+__device__ __forceinline__ uint32_t pk32(u16x2 x) { return __builtin_bit_cast(uint32_t, x); }
+// Byte idx of a window row held in the dwords W; idx is a constant wherever this is called (unrolled loops).
+template <int N>
+__device__ __forceinline__ uint32_t window_byte(const uint32_t (&W)[N], int idx) { return (W[idx >> 2] >> (8 * (idx & 3))) & 0xffu; }
+
+// The LDS tile blur_sep_tiled_kernel, blur_morph_tiled_kernel, blur_bilateral_tiled_kernel and blur_conv_tiled_kernel
+// work on: rows of whole 16-byte chunks, one workgroup of TILE_THREADS = one tile of TILE_TH output rows x ncols
+// (<= TILE_NCOLS) chunk columns, staged with ry rows above and below and HC halo chunks either side.  The helpers take
+// the kernel arguments they need as scalars: handed the parameter struct by reference the kernels grow by a third.
+constexpr int TILE_TH = 32;         // output rows per tile
+constexpr int TILE_NCOLS = 32;      // at most this many output chunk columns per tile
+constexpr int TILE_THREADS = 256;
+
+struct TileCoords {
+    int img;                        // image of the batch
+    int ty0, rows_out;              // first output row of the tile (band coordinates), output rows (<= TILE_TH)
+    int x0c, nc;                    // first output chunk column, output chunk columns (<= ncols)
+    int ncw, nrows;                 // staged chunk columns (tile chunk cc = row chunk x0c - HC + cc) and rows
+};
+// blockIdx -> tile (fill_tiles() is the host side: strips fastest, then tile rows, then images).
+template <int HC>
+__device__ __forceinline__ TileCoords tile_coords(int xcd, unsigned nblocks, int nstrips, int ntiles_y, int ncols, int cpr, int y0,
+                                                  int y1, int ry)
+{
+    const unsigned L = xcd ? xcd_contiguous(blockIdx.x, nblocks) : blockIdx.x;
+    const int strip = (int)(L % (unsigned)nstrips);
+    const unsigned t2 = L / (unsigned)nstrips;
+    const int ty = (int)(t2 % (unsigned)ntiles_y);
+    TileCoords tc;
+    tc.img = (int)(t2 / (unsigned)ntiles_y);
+    tc.ty0 = y0 + ty * TILE_TH;
+    tc.rows_out = min(TILE_TH, y1 - tc.ty0);
+    tc.x0c = strip * ncols;
+    tc.nc = min(ncols, cpr - tc.x0c);
+    tc.ncw = tc.nc + 2 * HC;
+    tc.nrows = tc.rows_out + 2 * ry;
+    return tc;
+}
+
+// Stages tc's nrows x ncw chunks of the image at img_in (rows of cpr chunks, `pitch` bytes; source rows clamped to
+// [0, H)) at `tile` and returns after the barrier that makes them visible to thread t's workgroup.
+//   * slot s = row * ncw + cc; global_load_lds_dwordx4 (LDS-DMA, 16 B per lane) moves 64 consecutive slots per
+//     wave-instruction: their LDS image is the 64 lanes in order;
+//   * halo chunks outside the image row are not loaded: they get copies of the first / last pixel's channels (same
+//     channel, position mod C), so the x-clamp costs the passes nothing.  A row narrower than the halo has them on both
+//     sides of its only strip; their source is the row itself, which no thread of this loop writes.
+template <int C, int HC>
+__device__ __forceinline__ void stage_tile(uint8_t *tile, const uint8_t *img_in, int cpr, int H, int pitch, const TileCoords &tc, int ry, int t)
+{
+    const int ty0 = tc.ty0, x0c = tc.x0c, nc = tc.nc, ncw = tc.ncw, nrows = tc.nrows;
+    {
+        const int lane = t & 63, wv = t >> 6;
+        const int nslots = nrows * ncw;
+        for (int u = wv; u * 64 < nslots; u += TILE_THREADS / 64) {
+            const int s = u * 64 + lane;
+            if (s < nslots) {
+                const int row = s / ncw, cc = s - row * ncw;
+                const int gc = x0c - HC + cc;
+                if (gc >= 0 && gc < cpr) {
+                    const int sr = min(max(ty0 - ry + row, 0), H - 1);
+                    const uint8_t *g = img_in + ((unsigned)sr * (unsigned)pitch + (unsigned)gc * 16u);
+                    __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1))) *)g,
+                                                     (void __attribute__((address_space(3))) *)(tile + (size_t)u * 64 * 16), 16, 0, 0);
+                }
+            }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __syncthreads();
+    if (x0c < HC || x0c + nc + HC > cpr) {
+        const int nedge = nrows * 2 * HC;
+        for (int i = t; i < nedge; i += TILE_THREADS) {
+            const int row = i / (2 * HC), h = i - row * (2 * HC);
+            const int cc = h < HC ? h : nc + h;         // the HC left halo chunks, then the HC right ones
+            const int gc = x0c - HC + cc;
+            if (gc >= 0 && gc < cpr) continue;
+            uint8_t *rowl = tile + (size_t)row * ncw * 16u;
+            const int base = (x0c - HC) * 16;           // row byte at tile byte 0
+            uint32_t v[4];
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                uint32_t w = 0;
+#pragma unroll
+                for (int b = 0; b < 4; b++) {
+                    const int pos = gc * 16 + 4 * q + b;
+                    const int src = pos < 0 ? ((pos % C) + C) % C : pitch - C + (pos - pitch) % C;
+                    w |= (uint32_t)rowl[src - base] << (8 * b);
+                }
+                v[q] = w;
+            }
+            *reinterpret_cast<uint4 *>(rowl + cc * 16) = make_uint4(v[0], v[1], v[2], v[3]);
+        }
+        __syncthreads();
+    }
+}
+
+// Output byte idx of a byte-per-thread (generic) kernel: block = output bytes per band, so idx = img * block + rem and
+// rem = (y - y0) * pitch + b, b = x * channels + c.  src = the image's band.
+struct BytePos {
+    long long img, rem;
+    int y, b, x, c;
+    const uint8_t *src;
+};
+__device__ __forceinline__ BytePos byte_pos(long long idx, long long block, int pitch, int channels, int y0, const uint8_t *in, long long in_stride)
+{
+    BytePos q;
+    q.img = idx / block;
+    q.rem = idx - q.img * block;
+    q.y = y0 + (int)(q.rem / pitch);
+    q.b = (int)(q.rem % pitch);
+    q.x = q.b / channels; q.c = q.b - q.x * channels;
+    q.src = in + q.img * in_stride;
+    return q;
+}
+
 // ----------------------------------------------------------------------------------
 // host side
 // ----------------------------------------------------------------------------------
@@ -76,8 +193,7 @@ static int dispatch(int v, F &&f)
     return status;
 }
 
-// The argument checks launch(), launch_sep(), launch_median(), launch_morph(), launch_bilateral() and launch_conv() share; every one of them is MI_BLUR_ERR_INVALID.
-// What differs between the families (radius / taps, halo rows, strides, where n_images == 0 is answered) stays in them.
+// The argument checks launch() and launch_checks() share; every one of them is MI_BLUR_ERR_INVALID.
 static inline int check_desc(const LaunchDesc &d, FilterKind kind)
 {
     if (!d.filter || d.filter->kind != kind || !d.in || !d.out || d.in == d.out) return MI_BLUR_ERR_INVALID;
@@ -94,6 +210,27 @@ static inline bool strides_too_small(const LaunchDesc &d)
 {
     return d.in_stride < 0 || d.out_stride < 0 || (d.in_stride && d.in_stride < dense_in(d)) || (d.out_stride && d.out_stride < dense_out(d));
 }
+// What launch_sep(), launch_median(), launch_morph(), launch_bilateral() and launch_conv() answer before they choose a
+// kernel, in this order: check_desc, the family's own check of the filter (filter_ok(filter) false: MI_BLUR_ERR_INVALID),
+// halo pointers (MI_BLUR_ERR_UNSUPPORTED), the strides, and only then the empty batch (MI_BLUR_OK; launch() answers it
+// before the strides).  LAUNCH_GO, which is no status: there is something to launch.
+constexpr int LAUNCH_GO = 1;
+template <typename F>
+static int launch_checks(const LaunchDesc &d, FilterKind kind, F &&filter_ok)
+{
+    if (const int st = check_desc(d, kind)) return st;
+    if (!filter_ok(*d.filter)) return MI_BLUR_ERR_INVALID;
+    if (d.halo_top || d.halo_bottom) return MI_BLUR_ERR_UNSUPPORTED;
+    if (strides_too_small(d)) return MI_BLUR_ERR_INVALID;
+    return d.n_images == 0 ? MI_BLUR_OK : LAUNCH_GO;
+}
+// Rows of whole 16-byte chunks, 1-4 channels, 16-byte aligned buffers and strides: what the tiled kernels (and the
+// median's register-window kernel) take.
+static inline bool tile_aligned(const LaunchDesc &d)
+{
+    return d.channels <= 4 && (long long)d.width * d.channels % 16 == 0 && (uintptr_t)d.in % 16 == 0 && (uintptr_t)d.out % 16 == 0 &&
+           d.in_stride % 16 == 0 && d.out_stride % 16 == 0;
+}
 
 // The members every kernel's parameter struct has under the same names (a template, not a base struct: the structs'
 // names and layouts are the kernels' mangled names and kernarg layouts).  Stride 0 = laid end to end.
@@ -106,11 +243,39 @@ static void fill_band(P &p, const LaunchDesc &d)
     p.out_stride = d.out_stride ? d.out_stride : dense_out(d);
 }
 
+// fill_band plus the tile decomposition of the tiled kernels' parameter structs (tile_coords() is the device side) and
+// the grid, one workgroup per tile.  MI_BLUR_ERR_INVALID when the tiles do not number in 31 bits.
+template <typename P>
+static int fill_tiles(P &p, const LaunchDesc &d, dim3 *grid)
+{
+    fill_band(p, d);
+    p.cpr = p.pitch / 16; p.y1 = d.y1;
+    p.nstrips = (p.cpr + TILE_NCOLS - 1) / TILE_NCOLS;
+    p.ncols = (p.cpr + p.nstrips - 1) / p.nstrips;
+    p.ntiles_y = (d.y1 - d.y0 + TILE_TH - 1) / TILE_TH;
+    const long long nblocks = (long long)d.n_images * p.ntiles_y * p.nstrips;
+    if (nblocks > 0x7fffffffLL) return MI_BLUR_ERR_INVALID;
+    p.nblocks = (unsigned)nblocks;
+    p.xcd = nblocks >= 16 ? 1 : 0;
+    *grid = dim3((unsigned)nblocks);
+    return MI_BLUR_OK;
+}
+
 // Grid of a byte-per-thread kernel: 256 threads per block, capped; the kernel grid-strides the rest.
 static inline dim3 byte_grid(long long total)
 {
     const long long blocks = (total + 255) / 256;
     return dim3((unsigned)(blocks > 256LL * 64 ? 256LL * 64 : blocks));
+}
+// fill_band plus what byte_pos() takes, for the generic kernels' parameter structs; returns the grid.
+template <typename P>
+static dim3 fill_generic(P &p, const LaunchDesc &d)
+{
+    fill_band(p, d);
+    p.block = dense_out(d);
+    p.total = p.block * d.n_images;
+    p.width = d.width; p.channels = d.channels;
+    return byte_grid(p.total);
 }
 
 // The direct layout (blur_direct_kernel, blur_median_fast_kernel): lanes are consecutive 16-byte chunk columns of the

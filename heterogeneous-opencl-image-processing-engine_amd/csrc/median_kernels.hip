@@ -240,23 +240,19 @@ __global__ __launch_bounds__(256) void blur_median_generic_kernel(const MedGener
     constexpr int D = 2 * R + 1, N = D * D, NW = (N + 1) / 2, K = (N - 1) / 2;
     const long long step = (long long)gridDim.x * blockDim.x;
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < p.total; idx += step) {
-        const long long img = idx / p.block;
-        const long long rem = idx - img * p.block;
-        const int y = p.y0 + (int)(rem / p.pitch);
-        const int b = (int)(rem % p.pitch);
-        const int x = b / p.channels, c = b - x * p.channels;
-        const uint8_t *src = p.in + img * p.in_stride + c;
+        const BytePos q = byte_pos(idx, p.block, p.pitch, p.channels, p.y0, p.in, p.in_stride);
+        const uint8_t *src = q.src + q.c;
         uint32_t V[NW];
 #pragma unroll
         for (int e = 0; e < NW; e++) V[e] = 0u;
         V[NW - 1] = 255u << 16;                         // N is odd: the spare field holds 255, never below a candidate
 #pragma unroll
         for (int j = 0; j < D; j++) {
-            const uint8_t *rowp = src + (size_t)min(max(y + j - R, 0), p.H - 1) * (size_t)p.pitch;
+            const uint8_t *rowp = src + (size_t)min(max(q.y + j - R, 0), p.H - 1) * (size_t)p.pitch;
 #pragma unroll
             for (int i = 0; i < D; i++) {
                 const int e = j * D + i;
-                const uint32_t v = rowp[(size_t)min(max(x + i - R, 0), p.width - 1) * (size_t)p.channels];
+                const uint32_t v = rowp[(size_t)min(max(q.x + i - R, 0), p.width - 1) * (size_t)p.channels];
                 V[e >> 1] |= v << (16 * (e & 1));
             }
         }
@@ -272,7 +268,7 @@ __global__ __launch_bounds__(256) void blur_median_generic_kernel(const MedGener
             const uint32_t below = ((acc & 0xffffu) + (acc >> 16)) >> 8;
             if (below <= (uint32_t)K) ans = t;
         }
-        p.out[img * p.out_stride + rem] = (uint8_t)ans;
+        p.out[q.img * p.out_stride + q.rem] = (uint8_t)ans;
     }
 }
 
@@ -293,12 +289,9 @@ int launch_median_generic(const LaunchDesc &d)
 {
     set_last_kernel("blur_median_generic_kernel");
     MedGenericParams p{};
-    fill_band(p, d);
-    p.block = dense_out(d);
-    p.total = p.block * d.n_images;
-    p.width = d.width; p.channels = d.channels;
+    const dim3 grid = fill_generic(p, d);
     return dispatch<1, 2, 3, 4, 5, 6, 7>(d.filter->radius, [&](auto R) {
-        return do_launch(blur_median_generic_kernel<R>, byte_grid(p.total), dim3(256), 0, d, p);
+        return do_launch(blur_median_generic_kernel<R>, grid, dim3(256), 0, d, p);
     });
 }
 
@@ -306,14 +299,9 @@ int launch_median_generic(const LaunchDesc &d)
 
 int launch_median(const LaunchDesc &d)
 {
-    if (const int st = check_desc(d, FilterKind::MEDIAN)) return st;
-    if (d.filter->radius < 1 || d.filter->radius > MI_BLUR_MEDIAN_MAX_RADIUS) return MI_BLUR_ERR_INVALID;
-    if (d.halo_top || d.halo_bottom) return MI_BLUR_ERR_UNSUPPORTED;
-    if (strides_too_small(d)) return MI_BLUR_ERR_INVALID;
-    if (d.n_images == 0) return MI_BLUR_OK;             // after the strides (launch(): before)
-    const long long pitch = (long long)d.width * d.channels;
-    const bool fast = d.filter->radius <= 2 && d.channels <= 4 && pitch % 16 == 0 && (uintptr_t)d.in % 16 == 0 &&
-                      (uintptr_t)d.out % 16 == 0 && d.in_stride % 16 == 0 && d.out_stride % 16 == 0 && direct_fits(d);
+    const int st = launch_checks(d, FilterKind::MEDIAN, [](const Filter &f) { return f.radius >= 1 && f.radius <= MI_BLUR_MEDIAN_MAX_RADIUS; });
+    if (st != LAUNCH_GO) return st;
+    const bool fast = d.filter->radius <= 2 && tile_aligned(d) && direct_fits(d);
     return fast ? launch_median_fast(d) : launch_median_generic(d);
 }
 

@@ -5,12 +5,10 @@
 // gives the same bytes as the 2-D window.
 //
 // Tiled kernel (blur_morph_tiled_kernel<C, OP, HC>): the shapes of blur_sep_tiled_kernel — rows of whole 16-byte chunks,
-// 16-byte aligned buffers and strides, 1-4 channels.  One workgroup = one tile of MORPH_TH output rows x ncols (<= 32)
+// 16-byte aligned buffers and strides, 1-4 channels.  One workgroup = one tile of TILE_TH output rows x ncols (<= 32)
 // chunk columns:
-//   * stage (MORPH_TH + 2 ry) rows x (ncols + 2 HC) chunks in LDS with global_load_lds_dwordx4, source rows clamped to the
-//     band, halo chunks outside the image row filled with the edge pixel's channels: sep_kernels.hip's staging, step for step
-//     (a twin, not a shared helper: blur_sep_tiled_kernel's code object stays what it was).  HC = ceil(rx * C / 16) halo
-//     chunks either side, at least 1;
+//   * stage (TILE_TH + 2 ry) rows x (ncols + 2 HC) chunks in LDS (stage_tile, kernel_common.h), x-clamp included.
+//     HC = ceil(rx * C / 16) halo chunks either side, at least 1;
 //   * the extrema live in 16-bit fields: a dword x carries its odd bytes as the HIGH bytes of its two fields already, and
 //     x << 8 carries the even ones there.  The high byte of v_pk_min_u16 / v_pk_max_u16 of two fields is the min / max of
 //     their high bytes whatever the low bytes hold, so one lane-operation reduces two bytes and nothing is ever masked;
@@ -39,8 +37,6 @@ namespace mi_blur {
 
 namespace {
 
-__device__ __forceinline__ u16x2 pk16(uint32_t x) { return __builtin_bit_cast(u16x2, x); }
-__device__ __forceinline__ uint32_t pk32(u16x2 x) { return __builtin_bit_cast(uint32_t, x); }
 template <bool MX>
 __device__ __forceinline__ uint32_t ext2(uint32_t a, uint32_t b)
 {
@@ -49,11 +45,8 @@ __device__ __forceinline__ uint32_t ext2(uint32_t a, uint32_t b)
 // Bytes back from the field form: the odd bytes from o, the even ones from the high bytes of e's fields.
 __device__ __forceinline__ uint32_t unfield(uint32_t e, uint32_t o) { return (o & 0xff00ff00u) | ((e >> 8) & 0x00ff00ffu); }
 
-constexpr int MORPH_TH = 32;        // output rows per tile
 constexpr int MORPH_RPG = 8;        // output rows per thread in the vertical pass
-constexpr int MORPH_NCOLS = 32;     // at most this many output chunk columns per tile
 constexpr int MORPH_NCH = 2;        // output chunks per thread in the horizontal pass
-constexpr int MORPH_THREADS = 256;
 
 constexpr int morph_hc(int C, int rx) { return rx * C <= 16 ? 1 : (rx * C + 15) / 16; }
 constexpr int morph_log2(int n) { int k = 0; while ((2 << k) <= n) k++; return k; }   // largest k with 2^k <= n
@@ -188,14 +181,14 @@ __device__ __forceinline__ void morph_htile(const MorphTiledParams &p, const uin
 {
     if constexpr (morph_hc(C, RX) == HC) {
         const int npairs = (nc + MORPH_NCH - 1) / MORPH_NCH;
-        for (int i = t; i < rows_out * npairs; i += MORPH_THREADS) {
+        for (int i = t; i < rows_out * npairs; i += TILE_THREADS) {
             const int k = i / npairs, col = (i - k * npairs) * MORPH_NCH;
             const uint8_t *lp = lds + ((size_t)k * ncw + col) * 16u;
             uint32_t r[4 * MORPH_NCH];
             if constexpr (OP == MI_BLUR_MORPH_GRADIENT) {
                 uint32_t lo[4 * MORPH_NCH];
                 morph_hpass<C, HC, RX, false>(lp, lo);
-                morph_hpass<C, HC, RX, true>(lp + (size_t)MORPH_TH * ncw * 16u, r);
+                morph_hpass<C, HC, RX, true>(lp + (size_t)TILE_TH * ncw * 16u, r);
 #pragma unroll
                 for (int j = 0; j < 4 * MORPH_NCH; j++) r[j] -= lo[j];     // bytewise hi >= lo: no borrow
             } else {
@@ -220,71 +213,14 @@ __device__ __forceinline__ void morph_hswitch(std::integer_sequence<int, RXs...>
 }
 
 template <int C, int OP, int HC>
-__global__ __launch_bounds__(MORPH_THREADS) void blur_morph_tiled_kernel(const MorphTiledParams p)
+__global__ __launch_bounds__(TILE_THREADS) void blur_morph_tiled_kernel(const MorphTiledParams p)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const int t = threadIdx.x;
-    const unsigned L = p.xcd ? xcd_contiguous(blockIdx.x, p.nblocks) : blockIdx.x;
-    const int strip = (int)(L % (unsigned)p.nstrips);
-    const unsigned t2 = L / (unsigned)p.nstrips;
-    const int ty = (int)(t2 % (unsigned)p.ntiles_y);
-    const int img = (int)(t2 / (unsigned)p.ntiles_y);
-
-    const int ty0 = p.y0 + ty * MORPH_TH;               // first output row of the tile (band coordinates)
-    const int rows_out = min(MORPH_TH, p.y1 - ty0);
-    const int x0c = strip * p.ncols;
-    const int nc = min(p.ncols, p.cpr - x0c);
-    const int ncw = nc + 2 * HC;                        // staged chunk columns: tile chunk cc = row chunk x0c - HC + cc
     const int ry = p.ry;
-    const int nrows = rows_out + 2 * ry;
-    const uint8_t *img_in = p.in + (long long)img * p.in_stride;
-
-    // ---- stage: slot s = row * ncw + cc; one wave-instruction moves 64 consecutive slots
-    {
-        const int lane = t & 63, wv = t >> 6;
-        const int nslots = nrows * ncw;
-        for (int u = wv; u * 64 < nslots; u += MORPH_THREADS / 64) {
-            const int s = u * 64 + lane;
-            if (s < nslots) {
-                const int row = s / ncw, cc = s - row * ncw;
-                const int gc = x0c - HC + cc;
-                if (gc >= 0 && gc < p.cpr) {
-                    const int sr = min(max(ty0 - ry + row, 0), p.H - 1);
-                    const uint8_t *g = img_in + ((unsigned)sr * (unsigned)p.pitch + (unsigned)gc * 16u);
-                    __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1))) *)g,
-                                                     (void __attribute__((address_space(3))) *)(lds + (size_t)u * 64 * 16), 16, 0, 0);
-                }
-            }
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __syncthreads();
-    // x-clamp: halo chunks outside the row get copies of the first / last pixel's channels (same channel, p mod C)
-    if (x0c < HC || x0c + nc + HC > p.cpr) {
-        const int nedge = nrows * 2 * HC;
-        for (int i = t; i < nedge; i += MORPH_THREADS) {
-            const int row = i / (2 * HC), h = i - row * (2 * HC);
-            const int cc = h < HC ? h : nc + h;         // the HC left halo chunks, then the HC right ones
-            const int gc = x0c - HC + cc;
-            if (gc >= 0 && gc < p.cpr) continue;
-            uint8_t *rowl = lds + (size_t)row * ncw * 16u;
-            const int base = (x0c - HC) * 16;           // row byte at tile byte 0
-            uint32_t v[4];
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                uint32_t w = 0;
-#pragma unroll
-                for (int b = 0; b < 4; b++) {
-                    const int pos = gc * 16 + 4 * q + b;
-                    const int src = pos < 0 ? ((pos % C) + C) % C : p.pitch - C + (pos - p.pitch) % C;
-                    w |= (uint32_t)rowl[src - base] << (8 * b);
-                }
-                v[q] = w;
-            }
-            *reinterpret_cast<uint4 *>(rowl + cc * 16) = make_uint4(v[0], v[1], v[2], v[3]);
-        }
-        __syncthreads();
-    }
+    const TileCoords tc = tile_coords<HC>(p.xcd, p.nblocks, p.nstrips, p.ntiles_y, p.ncols, p.cpr, p.y0, p.y1, ry);
+    const int img = tc.img, ty0 = tc.ty0, rows_out = tc.rows_out, x0c = tc.x0c, nc = tc.nc, ncw = tc.ncw;
+    stage_tile<C, HC>(lds, p.in + (long long)img * p.in_stride, p.cpr, p.H, p.pitch, tc, ry, t);
 
     // ---- vertical pass: thread = (chunk column cc, row group g); every staged row read once
     const int ngrp = (rows_out + MORPH_RPG - 1) / MORPH_RPG;
@@ -335,8 +271,8 @@ __global__ __launch_bounds__(MORPH_THREADS) void blur_morph_tiled_kernel(const M
             const uint32_t(&a)[8] = morph_min(OP) ? acc[m].lo : acc[m].hi;
             *reinterpret_cast<uint4 *>(vp) = make_uint4(unfield(a[0], a[4]), unfield(a[1], a[5]), unfield(a[2], a[6]), unfield(a[3], a[7]));
             if constexpr (OP == MI_BLUR_MORPH_GRADIENT) {
-                const uint32_t(&b)[8] = acc[m].hi;      // second plane: MORPH_TH rows further on
-                *reinterpret_cast<uint4 *>(vp + (size_t)MORPH_TH * ncw * 16u) =
+                const uint32_t(&b)[8] = acc[m].hi;      // second plane: TILE_TH rows further on
+                *reinterpret_cast<uint4 *>(vp + (size_t)TILE_TH * ncw * 16u) =
                     make_uint4(unfield(b[0], b[4]), unfield(b[1], b[5]), unfield(b[2], b[6]), unfield(b[3], b[7]));
             }
         }
@@ -360,23 +296,18 @@ __global__ __launch_bounds__(256) void blur_morph_generic_kernel(const MorphGene
 {
     const long long step = (long long)gridDim.x * blockDim.x;
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < p.total; idx += step) {
-        const long long img = idx / p.block;
-        const long long rem = idx - img * p.block;
-        const int y = p.y0 + (int)(rem / p.pitch);
-        const int b = (int)(rem % p.pitch);
-        const int x = b / p.channels, c = b - x * p.channels;
-        const uint8_t *src = p.in + img * p.in_stride;
+        const BytePos q = byte_pos(idx, p.block, p.pitch, p.channels, p.y0, p.in, p.in_stride);
         unsigned lo = 255u, hi = 0u;
         for (int j = -p.ry; j <= p.ry; j++) {
-            const int ny = min(max(y + j, 0), p.H - 1);
-            const uint8_t *rowp = src + (size_t)ny * (size_t)p.pitch + c;
+            const int ny = min(max(q.y + j, 0), p.H - 1);
+            const uint8_t *rowp = q.src + (size_t)ny * (size_t)p.pitch + q.c;
             for (int i = -p.rx; i <= p.rx; i++) {
-                const int nx = min(max(x + i, 0), p.width - 1);
+                const int nx = min(max(q.x + i, 0), p.width - 1);
                 const unsigned v = rowp[(size_t)nx * (size_t)p.channels];
                 lo = min(lo, v); hi = max(hi, v);
             }
         }
-        p.out[img * p.out_stride + rem] = (uint8_t)(p.op == MI_BLUR_MORPH_ERODE ? lo : p.op == MI_BLUR_MORPH_DILATE ? hi : hi - lo);
+        p.out[q.img * p.out_stride + q.rem] = (uint8_t)(p.op == MI_BLUR_MORPH_ERODE ? lo : p.op == MI_BLUR_MORPH_DILATE ? hi : hi - lo);
     }
 }
 
@@ -384,26 +315,17 @@ int launch_morph_tiled(const LaunchDesc &d)
 {
     set_last_kernel("blur_morph_tiled_kernel");
     const Filter &f = *d.filter;
-    const int rows = d.y1 - d.y0;
     MorphTiledParams p{};
-    fill_band(p, d);
-    const int cpr = p.pitch / 16;
-    p.cpr = cpr; p.y1 = d.y1;
-    p.nstrips = (cpr + MORPH_NCOLS - 1) / MORPH_NCOLS;
-    p.ncols = (cpr + p.nstrips - 1) / p.nstrips;
-    p.ntiles_y = (rows + MORPH_TH - 1) / MORPH_TH;
+    dim3 grid;
+    if (const int st = fill_tiles(p, d, &grid)) return st;
     p.rx = f.morph_rx; p.ry = f.morph_ry;
-    const long long nblocks = (long long)d.n_images * p.ntiles_y * p.nstrips;
-    if (nblocks > 0x7fffffffLL) return MI_BLUR_ERR_INVALID;
-    p.nblocks = (unsigned)nblocks;
-    p.xcd = nblocks >= 16 ? 1 : 0;
-    const dim3 grid((unsigned)nblocks), block(MORPH_THREADS);
+    const dim3 block(TILE_THREADS);
     const int hc = morph_hc(d.channels, p.rx);
-    // the staged rows, then in their place one plane of MORPH_TH rows per extremum; the last thread of a row of the
+    // the staged rows, then in their place one plane of TILE_TH rows per extremum; the last thread of a row of the
     // horizontal pass may read one chunk past its plane (an output chunk it does not store)
     const size_t row_bytes = (size_t)(p.ncols + 2 * hc) * 16u;
     const size_t planes = f.morph_op == MI_BLUR_MORPH_GRADIENT ? 2 : 1;
-    const size_t lds = std::max((size_t)(MORPH_TH + 2 * p.ry), planes * MORPH_TH) * row_bytes + 16u;
+    const size_t lds = std::max((size_t)(TILE_TH + 2 * p.ry), planes * TILE_TH) * row_bytes + 16u;
     return dispatch<1, 2, 3, 4>(d.channels, [&](auto C) {
         return dispatch<MI_BLUR_MORPH_ERODE, MI_BLUR_MORPH_DILATE, MI_BLUR_MORPH_GRADIENT>(f.morph_op, [&](auto OP) {
             return dispatch<1, 2, 3, 4>(hc, [&](auto HC) {
@@ -419,29 +341,21 @@ int launch_morph_generic(const LaunchDesc &d)
     set_last_kernel("blur_morph_generic_kernel");
     const Filter &f = *d.filter;
     MorphGenericParams p{};
-    fill_band(p, d);
-    p.block = dense_out(d);
-    p.total = p.block * d.n_images;
-    p.width = d.width; p.channels = d.channels;
+    const dim3 grid = fill_generic(p, d);
     p.op = f.morph_op; p.rx = f.morph_rx; p.ry = f.morph_ry;
-    return do_launch(blur_morph_generic_kernel, byte_grid(p.total), dim3(256), 0, d, p);
+    return do_launch(blur_morph_generic_kernel, grid, dim3(256), 0, d, p);
 }
 
 }  // namespace
 
 int launch_morph(const LaunchDesc &d)
 {
-    if (const int st = check_desc(d, FilterKind::MORPH)) return st;
-    const Filter &f = *d.filter;
-    if (f.morph_op < MI_BLUR_MORPH_ERODE || f.morph_op > MI_BLUR_MORPH_GRADIENT) return MI_BLUR_ERR_INVALID;
-    if (f.morph_rx < 0 || f.morph_rx > MI_BLUR_MORPH_MAX_RADIUS || f.morph_ry < 0 || f.morph_ry > MI_BLUR_MORPH_MAX_RADIUS) return MI_BLUR_ERR_INVALID;
-    if (d.halo_top || d.halo_bottom) return MI_BLUR_ERR_UNSUPPORTED;
-    if (strides_too_small(d)) return MI_BLUR_ERR_INVALID;
-    if (d.n_images == 0) return MI_BLUR_OK;             // after the strides (launch(): before)
-    const long long pitch = (long long)d.width * d.channels;
-    const bool aligned = d.channels <= 4 && pitch % 16 == 0 && (uintptr_t)d.in % 16 == 0 && (uintptr_t)d.out % 16 == 0 &&
-                         d.in_stride % 16 == 0 && d.out_stride % 16 == 0;
-    return aligned ? launch_morph_tiled(d) : launch_morph_generic(d);
+    const int st = launch_checks(d, FilterKind::MORPH, [](const Filter &f) {
+        return f.morph_op >= MI_BLUR_MORPH_ERODE && f.morph_op <= MI_BLUR_MORPH_GRADIENT && f.morph_rx >= 0 &&
+               f.morph_rx <= MI_BLUR_MORPH_MAX_RADIUS && f.morph_ry >= 0 && f.morph_ry <= MI_BLUR_MORPH_MAX_RADIUS;
+    });
+    if (st != LAUNCH_GO) return st;
+    return tile_aligned(d) ? launch_morph_tiled(d) : launch_morph_generic(d);
 }
 
 }  // namespace mi_blur

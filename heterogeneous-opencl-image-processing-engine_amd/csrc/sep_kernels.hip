@@ -6,11 +6,9 @@
 // horizontal one in 32 bits.
 //
 // Tiled kernel (blur_sep_tiled_kernel<C, RB>): rows of whole 16-byte chunks, 16-byte aligned buffers and strides, 1-4
-// channels.  One workgroup = one tile of SEP_TH output rows x ncols (<= 32) chunk columns:
-//   * stage (SEP_TH + 2 ry) rows x (ncols + 2 HC) chunks in LDS with global_load_lds_dwordx4 (LDS-DMA, 16 B per lane; the
-//     LDS image of 64 consecutive tile slots is the 64 lanes in order), source rows clamped to the band.  HC = the halo
-//     chunks either side that the radius bucket RB needs (RB * C bytes).  Halo chunks outside the image row are not
-//     loaded: they are filled with copies of the edge pixel's channels, so the x-clamp costs nothing later;
+// channels.  One workgroup = one tile of TILE_TH output rows x ncols (<= 32) chunk columns:
+//   * stage (TILE_TH + 2 ry) rows x (ncols + 2 HC) chunks in LDS (stage_tile, kernel_common.h), x-clamp included.  HC =
+//     the halo chunks either side that the radius bucket RB needs (RB * C bytes);
 //   * vertical pass: each thread takes one chunk column (halo chunks included) and SEP_RPG output rows, walks the
 //     SEP_RPG + 2 ry staged rows once and adds every row into the outputs it belongs to — every dword split into its
 //     even / odd bytes as two 16-bit fields, v_pk_mad_u16 with the row's tap (2 MACs per lane-op).  The sums replace the
@@ -32,13 +30,7 @@ namespace mi_blur {
 
 namespace {
 
-__device__ __forceinline__ u16x2 pk16(uint32_t x) { return __builtin_bit_cast(u16x2, x); }
-__device__ __forceinline__ uint32_t pk32(u16x2 x) { return __builtin_bit_cast(uint32_t, x); }
-
-constexpr int SEP_TH = 32;          // output rows per tile
 constexpr int SEP_RPG = 8;          // output rows per thread in the vertical pass
-constexpr int SEP_NCOLS = 32;       // at most this many output chunk columns per tile
-constexpr int SEP_THREADS = 256;
 
 constexpr int sep_halo_chunks(int C, int RB) { return (RB * C + 15) / 16; }
 
@@ -95,73 +87,16 @@ __device__ __forceinline__ void sep_hpass(std::integer_sequence<int, Ds...>, con
 }
 
 template <int C, int RB>
-__global__ __launch_bounds__(SEP_THREADS) void blur_sep_tiled_kernel(const SepTiledParams p)
+__global__ __launch_bounds__(TILE_THREADS) void blur_sep_tiled_kernel(const SepTiledParams p)
 {
     constexpr int HC = sep_halo_chunks(C, RB);
     constexpr int NW = 4 * (2 * HC + 1);            // window dwords per parity
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const int t = threadIdx.x;
-    const unsigned L = p.xcd ? xcd_contiguous(blockIdx.x, p.nblocks) : blockIdx.x;
-    const int strip = (int)(L % (unsigned)p.nstrips);
-    const unsigned t2 = L / (unsigned)p.nstrips;
-    const int ty = (int)(t2 % (unsigned)p.ntiles_y);
-    const int img = (int)(t2 / (unsigned)p.ntiles_y);
-
-    const int ty0 = p.y0 + ty * SEP_TH;                 // first output row of the tile (band coordinates)
-    const int rows_out = min(SEP_TH, p.y1 - ty0);
-    const int x0c = strip * p.ncols;
-    const int nc = min(p.ncols, p.cpr - x0c);
-    const int ncw = nc + 2 * HC;                        // staged chunk columns: tile chunk cc = row chunk x0c - HC + cc
     const int ry = p.ry;
-    const int nrows = rows_out + 2 * ry;
-    const uint8_t *img_in = p.in + (long long)img * p.in_stride;
-
-    // ---- stage: slot s = row * ncw + cc; one wave-instruction moves 64 consecutive slots
-    {
-        const int lane = t & 63, wv = t >> 6;
-        const int nslots = nrows * ncw;
-        for (int u = wv; u * 64 < nslots; u += SEP_THREADS / 64) {
-            const int s = u * 64 + lane;
-            if (s < nslots) {
-                const int row = s / ncw, cc = s - row * ncw;
-                const int gc = x0c - HC + cc;
-                if (gc >= 0 && gc < p.cpr) {
-                    const int sr = min(max(ty0 - ry + row, 0), p.H - 1);
-                    const uint8_t *g = img_in + ((unsigned)sr * (unsigned)p.pitch + (unsigned)gc * 16u);
-                    __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1))) *)g,
-                                                     (void __attribute__((address_space(3))) *)(lds + (size_t)u * 64 * 16), 16, 0, 0);
-                }
-            }
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __syncthreads();
-    // x-clamp: halo chunks outside the row get copies of the first / last pixel's channels (same channel, p mod C)
-    if (x0c < HC || x0c + nc + HC > p.cpr) {
-        const int nedge = nrows * 2 * HC;
-        for (int i = t; i < nedge; i += SEP_THREADS) {
-            const int row = i / (2 * HC), h = i - row * (2 * HC);
-            const int cc = h < HC ? h : nc + h;         // the HC left halo chunks, then the HC right ones
-            const int gc = x0c - HC + cc;
-            if (gc >= 0 && gc < p.cpr) continue;
-            uint8_t *rowl = lds + (size_t)row * ncw * 16u;
-            const int base = (x0c - HC) * 16;           // row byte at tile byte 0
-            uint32_t v[4];
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                uint32_t w = 0;
-#pragma unroll
-                for (int b = 0; b < 4; b++) {
-                    const int pos = gc * 16 + 4 * q + b;
-                    const int src = pos < 0 ? ((pos % C) + C) % C : p.pitch - C + (pos - p.pitch) % C;
-                    w |= (uint32_t)rowl[src - base] << (8 * b);
-                }
-                v[q] = w;
-            }
-            *reinterpret_cast<uint4 *>(rowl + cc * 16) = make_uint4(v[0], v[1], v[2], v[3]);
-        }
-        __syncthreads();
-    }
+    const TileCoords tc = tile_coords<HC>(p.xcd, p.nblocks, p.nstrips, p.ntiles_y, p.ncols, p.cpr, p.y0, p.y1, ry);
+    const int img = tc.img, ty0 = tc.ty0, rows_out = tc.rows_out, x0c = tc.x0c, nc = tc.nc, ncw = tc.ncw;
+    stage_tile<C, HC>(lds, p.in + (long long)img * p.in_stride, p.cpr, p.H, p.pitch, tc, ry, t);
 
     // ---- vertical pass: thread = (chunk column cc, row group g); every staged row read once
     const int ngrp = (rows_out + SEP_RPG - 1) / SEP_RPG;
@@ -206,7 +141,7 @@ __global__ __launch_bounds__(SEP_THREADS) void blur_sep_tiled_kernel(const SepTi
     // ---- horizontal pass: thread = one output chunk; 32-bit sums, one shift
     const int rx = p.rx, shift = p.shift;
     uint8_t *out_img = p.out + (long long)img * p.out_stride;
-    for (int i = t; i < rows_out * nc; i += SEP_THREADS) {
+    for (int i = t; i < rows_out * nc; i += TILE_THREADS) {
         const int k = i / nc, col = i - k * nc;
         uint32_t E[NW], O[NW];
         const uint4 *vp = reinterpret_cast<const uint4 *>(lds + ((size_t)k * ncw + col) * 32u);
@@ -241,24 +176,19 @@ __global__ __launch_bounds__(256) void blur_sep_generic_kernel(const SepGenericP
 {
     const long long step = (long long)gridDim.x * blockDim.x;
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < p.total; idx += step) {
-        const long long img = idx / p.block;
-        const long long rem = idx - img * p.block;
-        const int y = p.y0 + (int)(rem / p.pitch);
-        const int b = (int)(rem % p.pitch);
-        const int x = b / p.channels, c = b - x * p.channels;
-        const uint8_t *src = p.in + img * p.in_stride;
+        const BytePos q = byte_pos(idx, p.block, p.pitch, p.channels, p.y0, p.in, p.in_stride);
         unsigned sum = 0;
         for (int j = -p.ry; j <= p.ry; j++) {
-            const int ny = min(max(y + j, 0), p.H - 1);
-            const uint8_t *rowp = src + (size_t)ny * (size_t)p.pitch + c;
+            const int ny = min(max(q.y + j, 0), p.H - 1);
+            const uint8_t *rowp = q.src + (size_t)ny * (size_t)p.pitch + q.c;
             unsigned h = 0;
             for (int i = -p.rx; i <= p.rx; i++) {
-                const int nx = min(max(x + i, 0), p.width - 1);
+                const int nx = min(max(q.x + i, 0), p.width - 1);
                 h += (unsigned)rowp[(size_t)nx * (size_t)p.channels] * p.wx[SEP_MAX_R + i];
             }
             sum += h * p.wy[SEP_MAX_R + j];
         }
-        p.out[img * p.out_stride + rem] = (uint8_t)(sum >> p.shift);
+        p.out[q.img * p.out_stride + q.rem] = (uint8_t)(sum >> p.shift);
     }
 }
 
@@ -266,25 +196,16 @@ int launch_sep_tiled(const LaunchDesc &d)
 {
     set_last_kernel("blur_sep_tiled_kernel");
     const SepTaps &k = d.filter->taps;
-    const int rows = d.y1 - d.y0;
     SepTiledParams p{};
-    fill_band(p, d);
-    const int cpr = p.pitch / 16;
-    p.cpr = cpr; p.y1 = d.y1;
-    p.nstrips = (cpr + SEP_NCOLS - 1) / SEP_NCOLS;
-    p.ncols = (cpr + p.nstrips - 1) / p.nstrips;
-    p.ntiles_y = (rows + SEP_TH - 1) / SEP_TH;
+    dim3 grid;
+    if (const int st = fill_tiles(p, d, &grid)) return st;
     p.rx = k.rx; p.ry = k.ry; p.shift = k.shift;
     for (int i = 0; i <= 2 * SEP_MAX_R; i++) { p.wx[i] = k.wx[i]; p.wy2[i] = k.wy[i] | (k.wy[i] << 16); }
-    const long long nblocks = (long long)d.n_images * p.ntiles_y * p.nstrips;
-    if (nblocks > 0x7fffffffLL) return MI_BLUR_ERR_INVALID;
-    p.nblocks = (unsigned)nblocks;
-    p.xcd = nblocks >= 16 ? 1 : 0;
-    const dim3 grid((unsigned)nblocks), block(SEP_THREADS);
+    const dim3 block(TILE_THREADS);
     return dispatch<1, 2, 3, 4>(d.channels, [&](auto C) {
         return dispatch<4, 8, 16>(k.rx <= 4 ? 4 : k.rx <= 8 ? 8 : 16, [&](auto RB) {
-            const int ncw = p.ncols + 2 * sep_halo_chunks(C, RB);      // sums: SEP_TH rows x ncw chunks x 32 B >= the staged bytes
-            return do_launch(blur_sep_tiled_kernel<C, RB>, grid, block, (size_t)SEP_TH * ncw * 32u, d, p);
+            const int ncw = p.ncols + 2 * sep_halo_chunks(C, RB);      // sums: TILE_TH rows x ncw chunks x 32 B >= the staged bytes
+            return do_launch(blur_sep_tiled_kernel<C, RB>, grid, block, (size_t)TILE_TH * ncw * 32u, d, p);
         });
     });
 }
@@ -294,29 +215,22 @@ int launch_sep_generic(const LaunchDesc &d)
     set_last_kernel("blur_sep_generic_kernel");
     const SepTaps &k = d.filter->taps;
     SepGenericParams p{};
-    fill_band(p, d);
-    p.block = dense_out(d);
-    p.total = p.block * d.n_images;
-    p.width = d.width; p.channels = d.channels;
+    const dim3 grid = fill_generic(p, d);
     p.rx = k.rx; p.ry = k.ry; p.shift = k.shift;
     for (int i = 0; i <= 2 * SEP_MAX_R; i++) { p.wx[i] = k.wx[i]; p.wy[i] = k.wy[i]; }
-    return do_launch(blur_sep_generic_kernel, byte_grid(p.total), dim3(256), 0, d, p);
+    return do_launch(blur_sep_generic_kernel, grid, dim3(256), 0, d, p);
 }
 
 }  // namespace
 
 int launch_sep(const LaunchDesc &d)
 {
-    if (const int st = check_desc(d, FilterKind::SEP)) return st;
-    const SepTaps &k = d.filter->taps;
-    if (k.rx < 0 || k.rx > SEP_MAX_R || k.ry < 0 || k.ry > SEP_MAX_R || k.shift < 0 || k.shift > 16) return MI_BLUR_ERR_INVALID;
-    if (d.halo_top || d.halo_bottom) return MI_BLUR_ERR_UNSUPPORTED;
-    if (strides_too_small(d)) return MI_BLUR_ERR_INVALID;
-    if (d.n_images == 0) return MI_BLUR_OK;             // after the strides (launch(): before)
-    const long long pitch = (long long)d.width * d.channels;
-    const bool aligned = d.channels <= 4 && pitch % 16 == 0 && (uintptr_t)d.in % 16 == 0 && (uintptr_t)d.out % 16 == 0 &&
-                         d.in_stride % 16 == 0 && d.out_stride % 16 == 0;
-    return aligned ? launch_sep_tiled(d) : launch_sep_generic(d);
+    const int st = launch_checks(d, FilterKind::SEP, [](const Filter &f) {
+        const SepTaps &k = f.taps;
+        return k.rx >= 0 && k.rx <= SEP_MAX_R && k.ry >= 0 && k.ry <= SEP_MAX_R && k.shift >= 0 && k.shift <= 16;
+    });
+    if (st != LAUNCH_GO) return st;
+    return tile_aligned(d) ? launch_sep_tiled(d) : launch_sep_generic(d);
 }
 
 }  // namespace mi_blur
