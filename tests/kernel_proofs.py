@@ -1,6 +1,6 @@
 """Shared by test_kernel_proofs_gpu.py and test_kernel_proofs_host.py (not a test module): the pattern sets that prove the
-median networks by the 0-1 principle, and numpy restatements of the definitions in include/mi_blur.h that do not touch
-the product.
+median networks by the 0-1 principle, and the numpy restatements of the definitions in include/mi_blur.h (median_ref.py,
+sep_ref.py) that do not touch the product.
 
 The 0-1 principle: a selection built only from min / max (and byte copies) commutes with every monotone map, so if it is
 right on every two-valued window it is right on every window.  For radius r a window is D = 2r+1 columns of D rows; one
@@ -13,7 +13,9 @@ import functools
 import math
 
 import numpy as np
-from numpy.lib.stride_tricks import sliding_window_view
+
+from median_ref import ref_median  # noqa: F401  (kp.ref_median, kp.ref_sep, kp.rand_taps: the restatements the proofs use)
+from sep_ref import rand_taps, ref_sep  # noqa: F401
 
 MEDIAN_PAIRS = [(0, 255), (127, 128)]     # (low, high): any one proves the network; the second catches top-bit pack errors
 
@@ -160,34 +162,6 @@ def median_from_count(cnt, r, lo, hi):
 
 
 # ---------------------------------------------------------------- restatements of the definitions in include/mi_blur.h
-def ref_median(img, r):
-    """img (N, H, W, C) uint8: edge padding by r, every (2r+1)^2 window, the k-th smallest (k = ((2r+1)^2 - 1) / 2)."""
-    d = 2 * r + 1
-    p = np.pad(img, ((0, 0), (r, r), (r, r), (0, 0)), mode="edge")
-    flat = sliding_window_view(p, (d, d), axis=(1, 2)).reshape(img.shape + (d * d,))
-    k = (d * d - 1) // 2
-    return np.partition(flat, k, axis=-1)[..., k].astype(np.uint8)
-
-
-def ref_sep(img, wx, wy):
-    """img (N, H, W, C) uint8: edge padding, exact int64 sums, one shift by log2(sum wx) + log2(sum wy)."""
-    rx, ry = len(wx) // 2, len(wy) // 2
-    shift = int(sum(wx)).bit_length() - 1 + int(sum(wy)).bit_length() - 1
-    n, h, w, c = img.shape
-    p = np.pad(img.astype(np.int64), ((0, 0), (ry, ry), (rx, rx), (0, 0)), mode="edge")
-    hs = sum(int(wx[i]) * p[:, :, i:i + w, :] for i in range(2 * rx + 1))
-    vs = sum(int(wy[j]) * hs[:, j:j + h, :, :] for j in range(2 * ry + 1))
-    return (vs >> shift).astype(np.uint8)
-
-
-def rand_taps(rng, r, bits):
-    """2r+1 non-negative taps summing to 2^bits."""
-    if r == 0:
-        return [1 << bits]
-    cuts = np.sort(rng.integers(0, (1 << bits) + 1, size=2 * r))
-    return np.diff(np.concatenate([[0], cuts, [1 << bits]])).tolist()
-
-
 def one_hot(rb, d, b):
     """Taps of radius rb: 2^b at offset d, 0 elsewhere."""
     t = [0] * (2 * rb + 1)

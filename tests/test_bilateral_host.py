@@ -2,7 +2,6 @@
 hosts' --bilateral), CPU only: byte for byte against the numpy restatement of the definition in include/mi_blur.h
 (bilateral_ref.py), independent of the product.  The filter is defined by integer tables, so every comparison is equality."""
 import ctypes as C
-import os
 import subprocess
 
 import numpy as np
@@ -10,16 +9,14 @@ import pytest
 
 import bilateral_ref as br
 from bilateral_ref import ref_bilateral
+from filter_harness import (BILATERAL, MEDIAN, MORPH, SEP, apps, check_cpu_band_split_equals_whole, check_cpu_context,  # noqa: F401
+                            check_set_rules_order, cpu_run, read_ppm, write_ppm)
 
 RADII = tuple(range(1, 9))
 
 
 def cpu_bilateral(pkg, L, img, k, n_threads=3):
-    a = np.ascontiguousarray(img)
-    out = np.full_like(a, 0xA5)
-    n, h, w, c = a.shape
-    pkg.check(L.mi_blur_cpu_run_bilateral(a.ctypes.data, out.ctypes.data, w, h, c, n, C.byref(k), n_threads), "mi_blur_cpu_run_bilateral")
-    return out
+    return cpu_run(BILATERAL, pkg, L, img, k, n_threads)
 
 
 # ---------------------------------------------------------------- the restatement itself
@@ -244,37 +241,13 @@ def test_refusals(pkg, L):
 # ---------------------------------------------------------------- contexts
 def test_cpu_context_with_a_bilateral(pkg, L):
     rng = np.random.default_rng(11)
-    n, h, w, c = 3, 40, 24, 3
-    img = rng.integers(0, 256, size=(n, h, w, c), dtype=np.uint8)
-    for r, tables in ((1, br.gauss_tables(0, 25.0, 1)), (3, br.random_tables(rng, 3, zeros=0.3)), (8, br.gauss_tables(3.0, 40.0, 8))):
-        k = br.make_kernel(pkg, *tables)
-        want = ref_bilateral(img, *tables)
-        with pkg.Context(pkg.DEVICE_CPU, w, h, c, 1, max_batch=n, n_threads=2) as ctx:
-            ctx.set_bilateral(k)
-            k.range[0] = 0                                       # the context keeps a copy
-            out = np.zeros_like(img)
-            ctx.submit(img.ctypes.data, out.ctypes.data, n)
-            ctx.sync()
-            assert np.array_equal(out, want)
-            band = np.ascontiguousarray(img[0, 10:30])
-            bo = np.zeros((20 - 2 * r, w, c), np.uint8)
-            ctx.submit_band(band.ctypes.data, bo.ctypes.data, 20, r, r)
-            ctx.sync()
-            assert np.array_equal(bo, ref_bilateral(band[None], *tables)[0, r:20 - r])
-            bs = np.zeros_like(img)
-            pitch = w * c
-            ctx.submit_bands(img.ctypes.data + 10 * pitch, bs.ctypes.data + (10 + r) * pitch, n, h * pitch, 20, r, r)
-            ctx.sync()
-            assert np.array_equal(bs[:, 10 + r:30 - r], ref_bilateral(img[:, 10:30], *tables)[:, r:20 - r])
-            planar = np.ascontiguousarray(img.transpose(0, 3, 1, 2))
-            po = np.zeros_like(img)
-            ctx.submit_planar(planar.ctypes.data, po.ctypes.data, n)
-            ctx.sync()
-            assert np.array_equal(po, want)
-            good = br.make_kernel(pkg, *tables)
-            assert L.mi_blur_ctx_set_bilateral(ctx.h, C.byref(good)) == pkg.ERR_STATE
-            assert L.mi_blur_resident_run(ctx.h, 1, 1, 0) == pkg.ERR_UNSUPPORTED
-            assert L.mi_blur_resident_run_fused(ctx.h, 1, 1, 0) == pkg.ERR_UNSUPPORTED
+    img = rng.integers(0, 256, size=(3, 40, 24, 3), dtype=np.uint8)
+
+    def spoil(k):                                                # the context keeps a copy
+        k.range[0] = 0
+
+    for tables in (br.gauss_tables(0, 25.0, 1), br.random_tables(rng, 3, zeros=0.3), br.gauss_tables(3.0, 40.0, 8)):
+        check_cpu_context(BILATERAL, pkg, L, img, br.make_kernel(pkg, *tables), dict(n_threads=2), spoil=spoil)
 
 
 def test_band_split_with_halo_r_equals_whole(pkg, L):
@@ -282,74 +255,25 @@ def test_band_split_with_halo_r_equals_whole(pkg, L):
     h, w, c = 75, 23, 3
     img = rng.integers(0, 256, size=(1, h, w, c), dtype=np.uint8)
     for r in (1, 4, 8):
-        tables = br.random_tables(rng, r, zeros=0.2)
-        whole = ref_bilateral(img, *tables)
-        with pkg.Context(pkg.DEVICE_CPU, w, h, c, 1, max_batch=1, n_threads=2) as ctx:
-            ctx.set_bilateral(br.make_kernel(pkg, *tables))
-            for split in (r, h // 3, h // 2, h - r):
-                top_rows = min(h, split + r)
-                top_in = np.ascontiguousarray(img[0, :top_rows])
-                top = np.zeros((split, w, c), np.uint8)
-                ctx.submit_band(top_in.ctypes.data, top.ctypes.data, top_rows, 0, top_rows - split)
-                b0 = split - r
-                bot_in = np.ascontiguousarray(img[0, b0:])
-                bot = np.zeros((h - split, w, c), np.uint8)
-                ctx.submit_band(bot_in.ctypes.data, bot.ctypes.data, h - b0, r, 0)
-                ctx.sync()
-                assert np.array_equal(np.concatenate([top, bot]), whole[0]), (r, split)
+        k = br.make_kernel(pkg, *br.random_tables(rng, r, zeros=0.2))
+        check_cpu_band_split_equals_whole(BILATERAL, pkg, L, img, k, (r, h // 3, h // 2, h - r), dict(n_threads=2))
 
 
 def test_set_bilateral_rules(pkg, L):
     """A context holds one filter: set_kernel, set_median, set_morph and set_bilateral each replace what another set."""
     rng = np.random.default_rng(13)
-    n, h, w, c = 2, 20, 24, 3
-    img = rng.integers(0, 256, size=(n, h, w, c), dtype=np.uint8)
-
-    def run(*setters):
-        with pkg.Context(pkg.DEVICE_CPU, w, h, c, 1, max_batch=n) as ctx:
-            for s in setters:
-                s(ctx)
-            out = np.zeros_like(img)
-            ctx.submit(img.ctypes.data, out.ctypes.data, n)
-            ctx.sync()
-            return out
-
-    def via(fn, *args):
-        want = np.empty_like(img)
-        assert fn(img.ctypes.data, want.ctypes.data, w, h, c, *args) == pkg.OK
-        return want
-
+    img = rng.integers(0, 256, size=(2, 20, 24, 3), dtype=np.uint8)
     tables = br.gauss_tables(0, 30.0, 2)
     other = br.random_tables(rng, 4)
-    gauss = pkg.gauss_kernel(2.0)
-    kern = lambda ctx: ctx.set_kernel(gauss)
-    med = lambda ctx: ctx.set_median(2)
-    mor = lambda ctx: ctx.set_morph(pkg.MORPH_DILATE, 3, 1)
-    bil = lambda ctx: ctx.set_bilateral(br.make_kernel(pkg, *tables))
-    want_bil = ref_bilateral(img, *tables)
-    want_med = via(L.mi_blur_cpu_run_median, 2, n, 1)
-    want_kern = via(L.mi_blur_cpu_run_sep, n, C.byref(gauss), 1)
-    want_mor = via(L.mi_blur_cpu_run_morph, pkg.MORPH_DILATE, 3, 1, n, 1)
-    for before in ((kern,), (med,), (mor,), (kern, med, mor)):
-        assert np.array_equal(run(*before, bil), want_bil)
-    assert np.array_equal(run(bil, lambda ctx: ctx.set_bilateral(br.make_kernel(pkg, *other))), ref_bilateral(img, *other))
-    assert np.array_equal(run(bil, med), want_med)
-    assert np.array_equal(run(bil, kern), want_kern)
-    assert np.array_equal(run(bil, mor), want_mor)
-    with pkg.Context(pkg.DEVICE_CPU, w, h, c, 1, max_batch=n) as ctx:
-        k = br.make_kernel(pkg, *tables)
-        k.radius = 9
-        assert L.mi_blur_ctx_set_bilateral(ctx.h, C.byref(k)) == pkg.ERR_INVALID
-        k.radius = 2
-        k.range[0] = 0
-        assert L.mi_blur_ctx_set_bilateral(ctx.h, C.byref(k)) == pkg.ERR_INVALID
-        assert L.mi_blur_ctx_set_bilateral(ctx.h, None) == pkg.ERR_INVALID
-        assert L.mi_blur_ctx_set_bilateral(None, C.byref(br.make_kernel(pkg, *tables))) == pkg.ERR_INVALID
-        out = np.zeros_like(img)                                 # refused calls left the box blur in place
-        ctx.submit(img.ctypes.data, out.ctypes.data, n)
-        ctx.sync()
-        assert np.array_equal(out, via(L.mi_blur_cpu_run, 1, n, 1))
-        assert L.mi_blur_ctx_set_bilateral(ctx.h, C.byref(br.make_kernel(pkg, *tables))) == pkg.ERR_STATE
+    kern, med, mor = (SEP, pkg.gauss_kernel(2.0)), (MEDIAN, 2), (MORPH, (pkg.MORPH_DILATE, 3, 1))
+    bil = (BILATERAL, br.make_kernel(pkg, *tables))
+    bad_radius, bad_range = br.make_kernel(pkg, *tables), br.make_kernel(pkg, *tables)
+    bad_radius.radius = 9
+    bad_range.range[0] = 0
+    check_set_rules_order(BILATERAL, pkg, L, img,
+                          [(kern, bil), (med, bil), (mor, bil), (kern, med, mor, bil), (bil, (BILATERAL, br.make_kernel(pkg, *other))),
+                           (bil, med), (bil, kern), (bil, mor)],
+                          refused=[bad_radius, bad_range, None], good=bil[1])
 
 
 # ---------------------------------------------------------------- Python function
@@ -378,27 +302,6 @@ def test_bilateral_filter_on_the_cpu_device(pkg):
 
 
 # ---------------------------------------------------------------- hosts
-@pytest.fixture(scope="module")
-def apps(pkg):
-    pkg.build_native()
-    return os.path.join(pkg.APPS, "heterogeneous_blur"), os.path.join(pkg.APPS, "split_image_blur")
-
-
-def write_ppm(path, img):
-    h, w, _ = img.shape
-    with open(path, "wb") as f:
-        f.write(b"P6\n%d %d\n255\n" % (w, h))
-        f.write(img.tobytes())
-
-
-def read_ppm(path):
-    with open(path, "rb") as f:
-        assert f.readline().strip() == b"P6"
-        w, h = map(int, f.readline().split())
-        assert f.readline().strip() == b"255"
-        return np.frombuffer(f.read(), np.uint8).reshape(h, w, 3)
-
-
 def test_host_cpu_bilateral(apps, tmp_path):
     het, _ = apps
     rng = np.random.default_rng(9)

@@ -18,6 +18,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from filter_harness import write_ppm
+
 REF_CIMG_DIR = "/root/reference/CImg"
 REF_JPEG = "/root/reference/image_320x240.jpg"
 CONDA_JPEG_H = "/opt/conda/include/jpeglib.h"
@@ -50,13 +52,6 @@ def cimg_hosts(pkg, tmp_path_factory):
         assert r.returncode == 0, f"{app} does not compile with -DMI_BLUR_WITH_CIMG:\n{r.stderr[-3000:]}"
         exes[app] = str(exe)
     return exes, with_jpeg
-
-
-def write_ppm(path, img):
-    h, w, c = img.shape
-    with open(path, "wb") as f:
-        f.write(b"P6\n%d %d\n255\n" % (w, h))
-        f.write(img.tobytes())
 
 
 def read_image(path):

@@ -3,7 +3,6 @@ laplacian() / sharpen(), the hosts' --conv), CPU only: byte for byte against the
 include/mi_blur.h (conv_ref.py), independent of the product.  The filter is defined in integers, so every comparison is
 equality."""
 import ctypes as C
-import os
 import subprocess
 
 import numpy as np
@@ -11,17 +10,15 @@ import pytest
 
 import conv_ref as cr
 from conv_ref import ref_conv
+from filter_harness import (BILATERAL, CONV, MEDIAN, MORPH, SEP, apps, check_cpu_band_split_equals_whole, check_cpu_context,  # noqa: F401
+                            check_set_rules_order, cpu_run, read_ppm, write_ppm)
 
 # every rx and every ry, in a sample of pairs
 PAIRS = [(r, r) for r in range(8)] + [(0, 7), (7, 0), (1, 4), (4, 1), (2, 5), (5, 3), (3, 6), (6, 2), (1, 0), (0, 1), (7, 3), (2, 7)]
 
 
 def cpu_conv(pkg, L, img, k, n_threads=3):
-    a = np.ascontiguousarray(img)
-    out = np.full_like(a, 0xA5)
-    n, h, w, c = a.shape
-    pkg.check(L.mi_blur_cpu_run_conv(a.ctypes.data, out.ctypes.data, w, h, c, n, C.byref(k), n_threads), "mi_blur_cpu_run_conv")
-    return out
+    return cpu_run(CONV, pkg, L, img, k, n_threads)
 
 
 def run_spec(pkg, L, img, spec, n_threads=3):
@@ -288,37 +285,13 @@ def test_refusals(pkg, L):
 # ---------------------------------------------------------------- contexts
 def test_cpu_context_with_a_conv(pkg, L):
     rng = np.random.default_rng(12)
-    n, h, w, c = 3, 40, 24, 3
-    img = rng.integers(0, 256, size=(n, h, w, c), dtype=np.uint8)
+    img = rng.integers(0, 256, size=(3, 40, 24, 3), dtype=np.uint8)
+
+    def spoil(k):                                                    # the context keeps a copy
+        k.shift = 99
+
     for spec in (dict(K=SOBEL_X, mode="mag", K2=T(SOBEL_X)), cr.random_kernel(rng, 3, 2, zeros=0.3, mode="sat"), cr.random_kernel(rng, 1, 7, mode="abs")):
-        r = np.asarray(spec["K"]).shape[0] // 2
-        k = cr.make_kernel(pkg, **spec)
-        want = ref_conv(img, **spec)
-        with pkg.Context(pkg.DEVICE_CPU, w, h, c, 1, max_batch=n, n_threads=2) as ctx:
-            ctx.set_conv(k)
-            k.shift = 99                                             # the context keeps a copy
-            out = np.zeros_like(img)
-            ctx.submit(img.ctypes.data, out.ctypes.data, n)
-            ctx.sync()
-            assert np.array_equal(out, want)
-            band = np.ascontiguousarray(img[0, 10:30])
-            bo = np.zeros((20 - 2 * r, w, c), np.uint8)
-            ctx.submit_band(band.ctypes.data, bo.ctypes.data, 20, r, r)
-            ctx.sync()
-            assert np.array_equal(bo, ref_conv(band[None], **spec)[0, r:20 - r])
-            bs = np.zeros_like(img)
-            pitch = w * c
-            ctx.submit_bands(img.ctypes.data + 10 * pitch, bs.ctypes.data + (10 + r) * pitch, n, h * pitch, 20, r, r)
-            ctx.sync()
-            assert np.array_equal(bs[:, 10 + r:30 - r], ref_conv(img[:, 10:30], **spec)[:, r:20 - r])
-            planar = np.ascontiguousarray(img.transpose(0, 3, 1, 2))
-            po = np.zeros_like(img)
-            ctx.submit_planar(planar.ctypes.data, po.ctypes.data, n)
-            ctx.sync()
-            assert np.array_equal(po, want)
-            assert L.mi_blur_ctx_set_conv(ctx.h, C.byref(cr.make_kernel(pkg, **spec))) == pkg.ERR_STATE
-            assert L.mi_blur_resident_run(ctx.h, 1, 1, 0) == pkg.ERR_UNSUPPORTED
-            assert L.mi_blur_resident_run_fused(ctx.h, 1, 1, 0) == pkg.ERR_UNSUPPORTED
+        check_cpu_context(CONV, pkg, L, img, cr.make_kernel(pkg, **spec), dict(n_threads=2), spoil=spoil)
 
 
 def test_band_split_with_halo_ry_equals_whole(pkg, L):
@@ -326,73 +299,25 @@ def test_band_split_with_halo_ry_equals_whole(pkg, L):
     h, w, c = 75, 23, 3
     img = rng.integers(0, 256, size=(1, h, w, c), dtype=np.uint8)
     for (rx, ry, mode) in ((1, 1, "mag"), (5, 4, "sat"), (2, 7, "abs")):
-        spec = cr.random_kernel(rng, rx, ry, zeros=0.2, mode=mode)
-        whole = ref_conv(img, **spec)
-        with pkg.Context(pkg.DEVICE_CPU, w, h, c, 1, max_batch=1, n_threads=2) as ctx:
-            ctx.set_conv(cr.make_kernel(pkg, **spec))
-            for split in (ry, h // 3, h // 2, h - ry):
-                top_rows = min(h, split + ry)
-                top_in = np.ascontiguousarray(img[0, :top_rows])
-                top = np.zeros((split, w, c), np.uint8)
-                ctx.submit_band(top_in.ctypes.data, top.ctypes.data, top_rows, 0, top_rows - split)
-                b0 = split - ry
-                bot_in = np.ascontiguousarray(img[0, b0:])
-                bot = np.zeros((h - split, w, c), np.uint8)
-                ctx.submit_band(bot_in.ctypes.data, bot.ctypes.data, h - b0, ry, 0)
-                ctx.sync()
-                assert np.array_equal(np.concatenate([top, bot]), whole[0]), (rx, ry, split)
+        k = cr.make_kernel(pkg, **cr.random_kernel(rng, rx, ry, zeros=0.2, mode=mode))
+        check_cpu_band_split_equals_whole(CONV, pkg, L, img, k, (ry, h // 3, h // 2, h - ry), dict(n_threads=2))
 
 
 def test_set_conv_rules(pkg, L):
     """A context holds one filter: set_kernel, set_median, set_morph, set_bilateral and set_conv each replace what another set."""
     rng = np.random.default_rng(14)
-    n, h, w, c = 2, 20, 24, 3
-    img = rng.integers(0, 256, size=(n, h, w, c), dtype=np.uint8)
-
-    def run(*setters):
-        with pkg.Context(pkg.DEVICE_CPU, w, h, c, 1, max_batch=n) as ctx:
-            for s in setters:
-                s(ctx)
-            out = np.zeros_like(img)
-            ctx.submit(img.ctypes.data, out.ctypes.data, n)
-            ctx.sync()
-            return out
-
-    def via(fn, *args):
-        want = np.empty_like(img)
-        assert fn(img.ctypes.data, want.ctypes.data, w, h, c, *args) == pkg.OK
-        return want
-
+    img = rng.integers(0, 256, size=(2, 20, 24, 3), dtype=np.uint8)
     spec = cr.random_kernel(rng, 2, 1, mode="mag")
     other = cr.random_kernel(rng, 4, 3, mode="sat")
-    gauss = pkg.gauss_kernel(2.0)
-    bilat = pkg.Bilateral.gauss(0.0, 30.0, 2)
-    kern = lambda ctx: ctx.set_kernel(gauss)
-    med = lambda ctx: ctx.set_median(2)
-    mor = lambda ctx: ctx.set_morph(pkg.MORPH_DILATE, 3, 1)
-    bil = lambda ctx: ctx.set_bilateral(bilat)
-    conv = lambda ctx: ctx.set_conv(cr.make_kernel(pkg, **spec))
-    want_conv = ref_conv(img, **spec)
-    for before in ((kern,), (med,), (mor,), (bil,), (kern, med, mor, bil)):
-        assert np.array_equal(run(*before, conv), want_conv)
-    assert np.array_equal(run(conv, lambda ctx: ctx.set_conv(cr.make_kernel(pkg, **other))), ref_conv(img, **other))
-    assert np.array_equal(run(conv, med), via(L.mi_blur_cpu_run_median, 2, n, 1))
-    assert np.array_equal(run(conv, kern), via(L.mi_blur_cpu_run_sep, n, C.byref(gauss), 1))
-    assert np.array_equal(run(conv, mor), via(L.mi_blur_cpu_run_morph, pkg.MORPH_DILATE, 3, 1, n, 1))
-    assert np.array_equal(run(conv, bil), via(L.mi_blur_cpu_run_bilateral, n, C.byref(bilat), 1))
-    with pkg.Context(pkg.DEVICE_CPU, w, h, c, 1, max_batch=n) as ctx:
-        k = cr.make_kernel(pkg, **spec)
-        k.rx = 8
-        assert L.mi_blur_ctx_set_conv(ctx.h, C.byref(k)) == pkg.ERR_INVALID
-        k.rx, k.shift = 2, 17
-        assert L.mi_blur_ctx_set_conv(ctx.h, C.byref(k)) == pkg.ERR_INVALID
-        assert L.mi_blur_ctx_set_conv(ctx.h, None) == pkg.ERR_INVALID
-        assert L.mi_blur_ctx_set_conv(None, C.byref(cr.make_kernel(pkg, **spec))) == pkg.ERR_INVALID
-        out = np.zeros_like(img)                                     # refused calls left the box blur in place
-        ctx.submit(img.ctypes.data, out.ctypes.data, n)
-        ctx.sync()
-        assert np.array_equal(out, via(L.mi_blur_cpu_run, 1, n, 1))
-        assert L.mi_blur_ctx_set_conv(ctx.h, C.byref(cr.make_kernel(pkg, **spec))) == pkg.ERR_STATE
+    kern, med, mor = (SEP, pkg.gauss_kernel(2.0)), (MEDIAN, 2), (MORPH, (pkg.MORPH_DILATE, 3, 1))
+    bil, conv = (BILATERAL, pkg.Bilateral.gauss(0.0, 30.0, 2)), (CONV, cr.make_kernel(pkg, **spec))
+    bad_rx, bad_shift = cr.make_kernel(pkg, **spec), cr.make_kernel(pkg, **spec)
+    bad_rx.rx = 8
+    bad_shift.shift = 17
+    check_set_rules_order(CONV, pkg, L, img,
+                          [(kern, conv), (med, conv), (mor, conv), (bil, conv), (kern, med, mor, bil, conv),
+                           (conv, (CONV, cr.make_kernel(pkg, **other))), (conv, med), (conv, kern), (conv, mor), (conv, bil)],
+                          refused=[bad_rx, bad_shift, None], good=conv[1])
 
 
 # ---------------------------------------------------------------- Python functions
@@ -436,27 +361,6 @@ def test_python_functions_on_the_cpu_device(pkg):
 
 
 # ---------------------------------------------------------------- hosts
-@pytest.fixture(scope="module")
-def apps(pkg):
-    pkg.build_native()
-    return os.path.join(pkg.APPS, "heterogeneous_blur"), os.path.join(pkg.APPS, "split_image_blur")
-
-
-def write_ppm(path, img):
-    h, w, _ = img.shape
-    with open(path, "wb") as f:
-        f.write(b"P6\n%d %d\n255\n" % (w, h))
-        f.write(img.tobytes())
-
-
-def read_ppm(path):
-    with open(path, "rb") as f:
-        assert f.readline().strip() == b"P6"
-        w, h = map(int, f.readline().split())
-        assert f.readline().strip() == b"255"
-        return np.frombuffer(f.read(), np.uint8).reshape(h, w, 3)
-
-
 HOST_NAMES = {"sobel-x": "sobel_x", "sobel-y": "sobel_y", "sobel": "sobel_mag", "scharr-x": "scharr_x", "scharr-y": "scharr_y", "scharr": "scharr_mag",
               "laplacian": "laplacian4", "laplacian8": "laplacian8", "sharpen": "sharpen", "emboss": "emboss"}
 

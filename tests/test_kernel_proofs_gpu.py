@@ -15,21 +15,13 @@ import numpy as np
 import pytest
 
 import kernel_proofs as kp
+from filter_harness import torch_cuda  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 FAST, GENERIC = b"blur_median_fast_kernel", b"blur_median_generic_kernel"
 TILED = b"blur_sep_tiled_kernel"
 GUARD = 256
-
-
-@pytest.fixture(scope="module")
-def torch_cuda(L):
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    assert L.mi_blur_device_count() >= 1, "libmi_blur.so sees no HIP device"
-    torch.cuda.set_device(0)
-    return torch
 
 
 # ---------------------------------------------------------------- launches on device tensors, guard bytes around the output

@@ -1,45 +1,12 @@
 """Median blur (mi_blur_cpu_run_median, mi_blur_ctx_set_median, median_blur(), the hosts' --median), CPU only: against a
-numpy restatement of the definition in include/mi_blur.h, independent of the product."""
-import ctypes as C
-import os
+numpy restatement of the definition in include/mi_blur.h (median_ref.py), independent of the product."""
 import subprocess
 
 import numpy as np
 import pytest
-from numpy.lib.stride_tricks import sliding_window_view
 
-
-# ---------------------------------------------------------------- numpy restatement
-def ref_median(img, r):
-    """img (N, H, W, C) uint8: edge padding by r, every (2r+1)^2 window, the k-th smallest (k = ((2r+1)^2 - 1) / 2)."""
-    d = 2 * r + 1
-    p = np.pad(img, ((0, 0), (r, r), (r, r), (0, 0)), mode="edge")
-    win = sliding_window_view(p, (d, d), axis=(1, 2))            # N, H, W, C, d, d
-    flat = win.reshape(win.shape[:4] + (d * d,))
-    k = (d * d - 1) // 2
-    return np.partition(flat, k, axis=-1)[..., k].astype(np.uint8)
-
-
-def adversarial(rng, n, h, w, c):
-    """Images that stress ties and extremes: constant, salt-and-pepper, two- and few-valued, ramps, checkerboards."""
-    yy, xx = np.mgrid[0:h, 0:w]
-    out = [np.full((n, h, w, c), 77, np.uint8),
-           np.where(rng.random((n, h, w, c)) < 0.5, 0, 255).astype(np.uint8),
-           np.where(rng.random((n, h, w, c)) < 0.2, rng.choice([0, 255], (n, h, w, c)), 128).astype(np.uint8),
-           rng.choice(np.array([3, 200], np.uint8), (n, h, w, c)),
-           rng.choice(np.array([0, 1, 2, 254, 255], np.uint8), (n, h, w, c)),
-           np.broadcast_to(((xx * 7 + yy * 3) % 256).astype(np.uint8)[None, :, :, None], (n, h, w, c)).copy(),
-           np.broadcast_to((((xx + yy) % 2) * 255).astype(np.uint8)[None, :, :, None], (n, h, w, c)).copy()]
-    return out
-
-
-def cpu_median(pkg, L, img, r, n_threads=3):
-    a = np.ascontiguousarray(img)
-    out = np.full_like(a, 0xA5)
-    n, h, w, c = a.shape
-    pkg.check(L.mi_blur_cpu_run_median(a.ctypes.data, out.ctypes.data, w, h, c, r, n, n_threads), "mi_blur_cpu_run_median")
-    return out
-
+from filter_harness import MEDIAN, apps, check_cpu_band_split_equals_whole, check_cpu_context, cpu_run, read_ppm, write_ppm  # noqa: F401
+from median_ref import adversarial, ref_median
 
 # ---------------------------------------------------------------- mi_blur_cpu_run_median
 SHAPES = [(1, 1, 1, 3), (1, 1, 40, 3), (1, 37, 1, 1), (2, 5, 6, 4), (1, 9, 11, 5), (2, 17, 33, 3), (1, 24, 64, 1),
@@ -53,7 +20,7 @@ def test_cpu_run_median_random(pkg, L):
         for r in range(1, 8):
             want = ref_median(img, r)
             for nt in (1, 4):
-                assert np.array_equal(cpu_median(pkg, L, img, r, nt), want), ((n, h, w, c), r, nt)
+                assert np.array_equal(cpu_run(MEDIAN, pkg, L, img, r, nt), want), ((n, h, w, c), r, nt)
 
 
 def test_cpu_run_median_adversarial(pkg, L):
@@ -61,7 +28,7 @@ def test_cpu_run_median_adversarial(pkg, L):
     for (n, h, w, c) in ((1, 20, 32, 3), (2, 9, 7, 1), (1, 30, 17, 5)):
         for img in adversarial(rng, n, h, w, c):
             for r in (1, 2, 3, 7):
-                assert np.array_equal(cpu_median(pkg, L, img, r), ref_median(img, r)), ((n, h, w, c), r)
+                assert np.array_equal(cpu_run(MEDIAN, pkg, L, img, r, 3), ref_median(img, r)), ((n, h, w, c), r)
 
 
 def test_cpu_run_median_refusals(pkg, L):
@@ -95,37 +62,9 @@ def test_enqueue_median_without_a_device(pkg, L):
 # ---------------------------------------------------------------- CPU-device context
 def test_cpu_context_with_a_median(pkg, L):
     rng = np.random.default_rng(11)
-    n, h, w, c = 4, 37, 41, 3
-    img = rng.integers(0, 256, size=(n, h, w, c), dtype=np.uint8)
+    img = rng.integers(0, 256, size=(4, 37, 41, 3), dtype=np.uint8)
     for r in (1, 3):
-        want = ref_median(img, r)
-        with pkg.Context(pkg.DEVICE_CPU, w, h, c, 1, max_batch=n, n_slots=2, n_threads=3) as ctx:
-            ctx.set_median(r)
-            out = np.zeros_like(img)
-            ctx.submit(img.ctypes.data, out.ctypes.data, n)
-            ctx.sync()
-            assert np.array_equal(out, want)
-            # band with r halo rows: clamping at the band's own edges, interior rows only
-            band = np.ascontiguousarray(img[0, 10:30])
-            bo = np.zeros((20 - 2 * r, w, c), np.uint8)
-            ctx.submit_band(band.ctypes.data, bo.ctypes.data, 20, r, r)
-            ctx.sync()
-            assert np.array_equal(bo, ref_median(band[None], r)[0, r:20 - r])
-            # the same band of every image, strided
-            bs = np.zeros_like(img)
-            pitch = w * c
-            ctx.submit_bands(img.ctypes.data + 10 * pitch, bs.ctypes.data + (10 + r) * pitch, n, h * pitch, 20, r, r)
-            ctx.sync()
-            assert np.array_equal(bs[:, 10 + r:30 - r], ref_median(img[:, 10:30], r)[:, r:20 - r])
-            # planar in, interleaved out
-            planar = np.ascontiguousarray(img.transpose(0, 3, 1, 2))
-            po = np.zeros_like(img)
-            ctx.submit_planar(planar.ctypes.data, po.ctypes.data, n)
-            ctx.sync()
-            assert np.array_equal(po, want)
-            assert L.mi_blur_ctx_set_median(ctx.h, r) == pkg.ERR_STATE          # after the first submit
-            assert L.mi_blur_resident_run(ctx.h, 1, 1, 0) == pkg.ERR_UNSUPPORTED
-            assert L.mi_blur_resident_run_fused(ctx.h, 1, 1, 0) == pkg.ERR_UNSUPPORTED
+        check_cpu_context(MEDIAN, pkg, L, img, r, dict(n_slots=2, n_threads=3))
 
 
 def test_band_split_with_halo_r_equals_whole(pkg, L):
@@ -133,20 +72,7 @@ def test_band_split_with_halo_r_equals_whole(pkg, L):
     h, w, c = 45, 23, 3
     img = rng.integers(0, 256, size=(1, h, w, c), dtype=np.uint8)
     for r in (1, 2, 5):
-        whole = ref_median(img, r)
-        with pkg.Context(pkg.DEVICE_CPU, w, h, c, 1, max_batch=1, n_threads=2) as ctx:
-            ctx.set_median(r)
-            for split in (r, h // 3, h // 2, h - r):
-                top_rows = min(h, split + r)
-                top_in = np.ascontiguousarray(img[0, :top_rows])
-                top = np.zeros((split, w, c), np.uint8)
-                ctx.submit_band(top_in.ctypes.data, top.ctypes.data, top_rows, 0, top_rows - split)
-                b0 = split - r
-                bot_in = np.ascontiguousarray(img[0, b0:])
-                bot = np.zeros((h - split, w, c), np.uint8)
-                ctx.submit_band(bot_in.ctypes.data, bot.ctypes.data, h - b0, r, 0)
-                ctx.sync()
-                assert np.array_equal(np.concatenate([top, bot]), whole[0]), (r, split)
+        check_cpu_band_split_equals_whole(MEDIAN, pkg, L, img, r, (r, h // 3, h // 2, h - r), dict(n_threads=2))
 
 
 def test_set_median_rules(pkg, L):
@@ -190,27 +116,6 @@ def test_median_blur_on_the_cpu_device(pkg):
 
 
 # ---------------------------------------------------------------- hosts
-@pytest.fixture(scope="module")
-def apps(pkg):
-    pkg.build_native()
-    return os.path.join(pkg.APPS, "heterogeneous_blur"), os.path.join(pkg.APPS, "split_image_blur")
-
-
-def write_ppm(path, img):
-    h, w, _ = img.shape
-    with open(path, "wb") as f:
-        f.write(b"P6\n%d %d\n255\n" % (w, h))
-        f.write(img.tobytes())
-
-
-def read_ppm(path):
-    with open(path, "rb") as f:
-        assert f.readline().strip() == b"P6"
-        w, h = map(int, f.readline().split())
-        assert f.readline().strip() == b"255"
-        return np.frombuffer(f.read(), np.uint8).reshape(h, w, 3)
-
-
 def test_host_cpu_median(apps, tmp_path):
     het, _ = apps
     rng = np.random.default_rng(9)

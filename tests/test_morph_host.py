@@ -1,89 +1,26 @@
 """Erode / dilate / morphological gradient (mi_blur_cpu_run_morph, mi_blur_ctx_set_morph, erode() / dilate() /
 morph_gradient(), the hosts' --erode / --dilate / --morph-gradient), CPU only: byte for byte against a numpy restatement of
-the definition in include/mi_blur.h, independent of the product.
-
-Inputs: on uniformly random bytes a 33x33 minimum is 0 almost everywhere, so a window one pixel short would pass.  Every
-sweep therefore runs sparse impulses (single pixels of 0 and 255 in ONE channel on a background of 128, more than 33
-apart, on the image's first and last rows and columns among others: erode / dilate must paint exact rectangles in that
-channel only), slow ramps, checkerboards and low-amplitude noise; random bytes only at the small radii."""
-import os
+the definition in include/mi_blur.h (morph_ref.py, which also says why the inputs are what they are), independent of the
+product."""
 import subprocess
 
 import numpy as np
 import pytest
-from numpy.lib.stride_tricks import sliding_window_view
 
-ERODE, DILATE, GRADIENT = 0, 1, 2
-OPS = (ERODE, DILATE, GRADIENT)
-
-
-# ---------------------------------------------------------------- numpy restatement
-def _finish(lo, hi, op):
-    return lo if op == ERODE else hi if op == DILATE else (hi.astype(np.int16) - lo.astype(np.int16)).astype(np.uint8)
-
-
-def ref_morph_2d(img, op, rx, ry):
-    """The definition: img (N, H, W, C) uint8, edge padding by (ry, rx), min / max over every full 2-D window."""
-    p = np.pad(img, ((0, 0), (ry, ry), (rx, rx), (0, 0)), mode="edge")
-    win = sliding_window_view(p, (2 * ry + 1, 2 * rx + 1), axis=(1, 2))
-    return _finish(win.min(axis=(-2, -1)), win.max(axis=(-2, -1)), op)
-
-
-def ref_morph(img, op, rx, ry):
-    """The separable restatement (1-D windows along x, then along y); test_separable_restatement ties it to the 2-D one."""
-    p = np.pad(img, ((0, 0), (0, 0), (rx, rx), (0, 0)), mode="edge")
-    wx = sliding_window_view(p, 2 * rx + 1, axis=2)
-    lo, hi = wx.min(axis=-1), wx.max(axis=-1)
-    lo = sliding_window_view(np.pad(lo, ((0, 0), (ry, ry), (0, 0), (0, 0)), mode="edge"), 2 * ry + 1, axis=1).min(axis=-1)
-    hi = sliding_window_view(np.pad(hi, ((0, 0), (ry, ry), (0, 0), (0, 0)), mode="edge"), 2 * ry + 1, axis=1).max(axis=-1)
-    return _finish(lo, hi, op)
-
-
-# ---------------------------------------------------------------- inputs
-def impulse_batch(h, w, c, candidates):
-    """Images of 128 with single pixels of 0 / 255 (alternating) in one channel each at the candidate (y, x) positions;
-    positions closer than 34 in both axes go to different images, so every image's impulses are more than 33 apart."""
-    images = []                                                  # [(array, [(y, x), ...])]
-    for k, (y, x) in enumerate(dict.fromkeys((min(max(y, 0), h - 1), min(max(x, 0), w - 1)) for y, x in candidates)):
-        for img, taken in images:
-            if all(max(abs(y - yy), abs(x - xx)) > 33 for yy, xx in taken):
-                break
-        else:
-            img, taken = np.full((h, w, c), 128, np.uint8), []
-            images.append((img, taken))
-        img[y, x, k % c] = 0 if k % 2 else 255
-        taken.append((y, x))
-    return np.stack([img for img, _ in images])
-
-
-def corner_impulses(h, w, c):
-    cand = [(y, x) for y in (0, h // 2, h - 1) for x in (0, w // 2, w - 1)] + [(h // 3, w // 4), (1, 1), (h - 2, w - 2)]
-    return impulse_batch(h, w, c, cand)
-
-
-def structured(rng, n, h, w, c):
-    """Ramps, checkerboards (the median tests' adversarial() list) and noise of low amplitude: the extremum depends on the extent."""
-    yy, xx = np.mgrid[0:h, 0:w]
-    return [np.broadcast_to(((xx * 7 + yy * 3) % 256).astype(np.uint8)[None, :, :, None], (n, h, w, c)).copy(),
-            np.broadcast_to((((xx + yy) % 2) * 255).astype(np.uint8)[None, :, :, None], (n, h, w, c)).copy(),
-            rng.integers(100, 141, size=(n, h, w, c), dtype=np.uint8),
-            np.where(rng.random((n, h, w, c)) < 0.02, rng.choice([0, 255], (n, h, w, c)), 128).astype(np.uint8),
-            np.full((n, h, w, c), 77, np.uint8)]
+from filter_harness import (MEDIAN, MORPH, SEP, apps, check_cpu_band_split_equals_whole, check_cpu_context, check_set_rules_order,  # noqa: F401
+                            cpu_run, read_ppm, write_ppm)
+from morph_ref import DILATE, ERODE, GRADIENT, OPS, corner_impulses, ref_morph, ref_morph_2d, structured
 
 
 def inputs(rng, n, h, w, c, small):
-    out = [corner_impulses(h, w, c)] + structured(rng, n, h, w, c)
+    out = [corner_impulses(h, w, c)] + structured(rng, n, h, w, c, sparse_and_constant=True)
     if small:
         out.append(rng.integers(0, 256, size=(n, h, w, c), dtype=np.uint8))
     return out
 
 
 def cpu_morph(pkg, L, img, op, rx, ry, n_threads=3):
-    a = np.ascontiguousarray(img)
-    out = np.full_like(a, 0xA5)
-    n, h, w, c = a.shape
-    pkg.check(L.mi_blur_cpu_run_morph(a.ctypes.data, out.ctypes.data, w, h, c, op, rx, ry, n, n_threads), "mi_blur_cpu_run_morph")
-    return out
+    return cpu_run(MORPH, pkg, L, img, (op, rx, ry), n_threads)
 
 
 # ---------------------------------------------------------------- the yardstick itself
@@ -192,35 +129,8 @@ def test_cpu_context_with_a_morph(pkg, L):
     n, h, w, c = 4, 37, 41, 3
     img = rng.integers(100, 141, size=(n, h, w, c), dtype=np.uint8)
     img[0] = corner_impulses(h, w, c)[0]
-    for op, rx, ry in ((ERODE, 1, 1), (DILATE, 5, 3), (GRADIENT, 2, 4), (ERODE, 16, 0)):
-        want = ref_morph(img, op, rx, ry)
-        with pkg.Context(pkg.DEVICE_CPU, w, h, c, 1, max_batch=n, n_slots=2, n_threads=3) as ctx:
-            ctx.set_morph(op, rx, ry)
-            out = np.zeros_like(img)
-            ctx.submit(img.ctypes.data, out.ctypes.data, n)
-            ctx.sync()
-            assert np.array_equal(out, want)
-            # band with ry halo rows: clamping at the band's own edges, interior rows only
-            band = np.ascontiguousarray(img[0, 10:30])
-            bo = np.zeros((20 - 2 * ry, w, c), np.uint8)
-            ctx.submit_band(band.ctypes.data, bo.ctypes.data, 20, ry, ry)
-            ctx.sync()
-            assert np.array_equal(bo, ref_morph(band[None], op, rx, ry)[0, ry:20 - ry])
-            # the same band of every image, strided
-            bs = np.zeros_like(img)
-            pitch = w * c
-            ctx.submit_bands(img.ctypes.data + 10 * pitch, bs.ctypes.data + (10 + ry) * pitch, n, h * pitch, 20, ry, ry)
-            ctx.sync()
-            assert np.array_equal(bs[:, 10 + ry:30 - ry], ref_morph(img[:, 10:30], op, rx, ry)[:, ry:20 - ry])
-            # planar in, interleaved out
-            planar = np.ascontiguousarray(img.transpose(0, 3, 1, 2))
-            po = np.zeros_like(img)
-            ctx.submit_planar(planar.ctypes.data, po.ctypes.data, n)
-            ctx.sync()
-            assert np.array_equal(po, want)
-            assert L.mi_blur_ctx_set_morph(ctx.h, op, rx, ry) == pkg.ERR_STATE     # after the first submit
-            assert L.mi_blur_resident_run(ctx.h, 1, 1, 0) == pkg.ERR_UNSUPPORTED
-            assert L.mi_blur_resident_run_fused(ctx.h, 1, 1, 0) == pkg.ERR_UNSUPPORTED
+    for filt in ((ERODE, 1, 1), (DILATE, 5, 3), (GRADIENT, 2, 4), (ERODE, 16, 0)):
+        check_cpu_context(MORPH, pkg, L, img, filt, dict(n_slots=2, n_threads=3))
 
 
 def test_band_split_with_halo_ry_equals_whole(pkg, L):
@@ -230,67 +140,19 @@ def test_band_split_with_halo_ry_equals_whole(pkg, L):
     img[0, ::9, ::7, 1] = 255
     img[0, 4::9, 3::7, 2] = 0
     for op, rx, ry in ((ERODE, 2, 1), (DILATE, 1, 5), (GRADIENT, 3, 16), (DILATE, 4, 0)):
-        whole = ref_morph(img, op, rx, ry)
-        with pkg.Context(pkg.DEVICE_CPU, w, h, c, 1, max_batch=1, n_threads=2) as ctx:
-            ctx.set_morph(op, rx, ry)
-            for split in (max(ry, 1), h // 3, h // 2, h - max(ry, 1)):
-                top_rows = min(h, split + ry)
-                top_in = np.ascontiguousarray(img[0, :top_rows])
-                top = np.zeros((split, w, c), np.uint8)
-                ctx.submit_band(top_in.ctypes.data, top.ctypes.data, top_rows, 0, top_rows - split)
-                b0 = split - ry
-                bot_in = np.ascontiguousarray(img[0, b0:])
-                bot = np.zeros((h - split, w, c), np.uint8)
-                ctx.submit_band(bot_in.ctypes.data, bot.ctypes.data, h - b0, ry, 0)
-                ctx.sync()
-                assert np.array_equal(np.concatenate([top, bot]), whole[0]), (op, rx, ry, split)
+        splits = (max(ry, 1), h // 3, h // 2, h - max(ry, 1))
+        check_cpu_band_split_equals_whole(MORPH, pkg, L, img, (op, rx, ry), splits, dict(n_threads=2))
 
 
 def test_set_morph_rules(pkg, L):
     """A context holds one filter: set_kernel, set_median and set_morph each replace what another set before."""
     rng = np.random.default_rng(13)
-    n, h, w, c = 2, 20, 24, 3
-    img = rng.integers(100, 141, size=(n, h, w, c), dtype=np.uint8)
-
-    def run(*setters):
-        with pkg.Context(pkg.DEVICE_CPU, w, h, c, 1, max_batch=n) as ctx:
-            for s in setters:
-                s(ctx)
-            out = np.zeros_like(img)
-            ctx.submit(img.ctypes.data, out.ctypes.data, n)
-            ctx.sync()
-            return out
-
-    def via(fn, *args):
-        want = np.empty_like(img)
-        assert fn(img.ctypes.data, want.ctypes.data, w, h, c, *args) == pkg.OK
-        return want
-
-    gauss = pkg.gauss_kernel(2.0)
-    kern = lambda ctx: ctx.set_kernel(gauss)
-    med = lambda ctx: ctx.set_median(2)
-    mor = lambda ctx: ctx.set_morph(DILATE, 3, 1)
-    want_morph = ref_morph(img, DILATE, 3, 1)
-    want_med = via(L.mi_blur_cpu_run_median, 2, n, 1)
-    import ctypes as C
-    want_kern = via(L.mi_blur_cpu_run_sep, n, C.byref(gauss), 1)
-    assert np.array_equal(run(kern, mor), want_morph)
-    assert np.array_equal(run(med, mor), want_morph)
-    assert np.array_equal(run(kern, med, mor), want_morph)
-    assert np.array_equal(run(mor, lambda ctx: ctx.set_morph(ERODE, 0, 2)), ref_morph(img, ERODE, 0, 2))
-    assert np.array_equal(run(mor, med), want_med)
-    assert np.array_equal(run(mor, kern), want_kern)
-    assert np.array_equal(run(med, mor, kern), want_kern)
-    assert np.array_equal(run(kern, mor, med), want_med)
-    with pkg.Context(pkg.DEVICE_CPU, w, h, c, 1, max_batch=n) as ctx:
-        for op, rx, ry in ((-1, 1, 1), (3, 1, 1), (ERODE, -1, 0), (ERODE, 0, 17), (DILATE, 17, 17)):
-            assert L.mi_blur_ctx_set_morph(ctx.h, op, rx, ry) == pkg.ERR_INVALID
-        assert L.mi_blur_ctx_set_morph(None, ERODE, 1, 1) == pkg.ERR_INVALID
-        out = np.zeros_like(img)                                 # refused calls left the box blur in place
-        ctx.submit(img.ctypes.data, out.ctypes.data, n)
-        ctx.sync()
-        assert np.array_equal(out, via(L.mi_blur_cpu_run, 1, n, 1))
-        assert L.mi_blur_ctx_set_morph(ctx.h, ERODE, 1, 1) == pkg.ERR_STATE
+    img = rng.integers(100, 141, size=(2, 20, 24, 3), dtype=np.uint8)
+    kern, med, mor = (SEP, pkg.gauss_kernel(2.0)), (MEDIAN, 2), (MORPH, (DILATE, 3, 1))
+    check_set_rules_order(MORPH, pkg, L, img,
+                          [(kern, mor), (med, mor), (kern, med, mor), (mor, (MORPH, (ERODE, 0, 2))), (mor, med), (mor, kern),
+                           (med, mor, kern), (kern, mor, med)],
+                          refused=[(-1, 1, 1), (3, 1, 1), (ERODE, -1, 0), (ERODE, 0, 17), (DILATE, 17, 17)], good=(ERODE, 1, 1))
 
 
 # ---------------------------------------------------------------- Python functions
@@ -320,27 +182,6 @@ def test_morphology_functions_on_the_cpu_device(pkg):
 
 
 # ---------------------------------------------------------------- hosts
-@pytest.fixture(scope="module")
-def apps(pkg):
-    pkg.build_native()
-    return os.path.join(pkg.APPS, "heterogeneous_blur"), os.path.join(pkg.APPS, "split_image_blur")
-
-
-def write_ppm(path, img):
-    h, w, _ = img.shape
-    with open(path, "wb") as f:
-        f.write(b"P6\n%d %d\n255\n" % (w, h))
-        f.write(img.tobytes())
-
-
-def read_ppm(path):
-    with open(path, "rb") as f:
-        assert f.readline().strip() == b"P6"
-        w, h = map(int, f.readline().split())
-        assert f.readline().strip() == b"255"
-        return np.frombuffer(f.read(), np.uint8).reshape(h, w, 3)
-
-
 def test_host_cpu_morph(apps, tmp_path):
     het, _ = apps
     rng = np.random.default_rng(9)

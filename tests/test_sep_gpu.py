@@ -1,64 +1,21 @@
 """Separable kernels of any radius on a real MI355X (-m gpu): mi_blur_enqueue_sep / _band, a context given a kernel by
 mi_blur_ctx_set_kernel, gaussian_blur() and the hosts' --sigma, bit-exact against a numpy restatement of the definition
-in include/mi_blur.h (edge padding + exact int64 sums), and the binomial taps against the committed golden hashes."""
+in include/mi_blur.h (sep_ref.py: edge padding + exact int64 sums), and the binomial taps against the committed golden hashes."""
 import ctypes as C
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
+from filter_harness import (SEP, apps, check_batch_over_2gib, check_gpu_band_split_equals_whole, check_gpu_context,  # noqa: F401
+                            check_unaligned_pointers, gpu_run, read_ppm, torch_cuda, write_ppm)
+from sep_ref import rand_taps, ref_sep
+
 pytestmark = pytest.mark.gpu
 
 
-def ref_sep(img, wx, wy):
-    """img (N, H, W, C) uint8: edge padding, exact int64 sums, one shift."""
-    rx, ry = len(wx) // 2, len(wy) // 2
-    shift = int(sum(wx)).bit_length() - 1 + int(sum(wy)).bit_length() - 1
-    n, h, w, c = img.shape
-    p = np.pad(img.astype(np.int64), ((0, 0), (ry, ry), (rx, rx), (0, 0)), mode="edge")
-    hs = sum(int(wx[i]) * p[:, :, i:i + w, :] for i in range(2 * rx + 1))
-    vs = sum(int(wy[j]) * hs[:, j:j + h, :, :] for j in range(2 * ry + 1))
-    return (vs >> shift).astype(np.uint8)
-
-
-def rand_taps(rng, r, bits):
-    if r == 0:
-        return [1 << bits]
-    cuts = np.sort(rng.integers(0, (1 << bits) + 1, size=2 * r))
-    return np.diff(np.concatenate([[0], cuts, [1 << bits]])).tolist()
-
-
-@pytest.fixture(scope="module")
-def torch_cuda(L):
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    assert L.mi_blur_device_count() >= 1, "libmi_blur.so sees no HIP device"
-    torch.cuda.set_device(0)
-    return torch
-
-
-def gpu_sep(pkg, L, torch, host, wx, wy, offset_in=0, offset_out=0, y0=None, y1=None):
-    """host: N x H x W x C -> mi_blur_enqueue_sep (or _band for one image with y0/y1), with guard bytes around the output."""
-    n, h, w, c = host.shape
-    k = pkg.SepKernel.from_taps(wx, wy)
-    y0 = 0 if y0 is None else y0
-    y1 = h if y1 is None else y1
-    size_out = n * (y1 - y0) * w * c
-    d_in = torch.zeros(host.size + 64, dtype=torch.uint8, device="cuda")
-    d_in[offset_in:offset_in + host.size] = torch.from_numpy(host.reshape(-1)).cuda()
-    d_out = torch.full((size_out + 128,), 0x5A, dtype=torch.uint8, device="cuda")
-    s = torch.cuda.current_stream().cuda_stream
-    if y0 == 0 and y1 == h:
-        rc = L.mi_blur_enqueue_sep(d_in.data_ptr() + offset_in, d_out.data_ptr() + offset_out, w, h, c, n, C.byref(k), s)
-    else:
-        assert n == 1
-        rc = L.mi_blur_enqueue_sep_band(d_in.data_ptr() + offset_in, d_out.data_ptr() + offset_out, w, h, c, y0, y1, C.byref(k), s)
-    pkg.check(rc, "mi_blur_enqueue_sep")
-    torch.cuda.synchronize()
-    o = d_out.cpu().numpy()
-    assert (o[:offset_out] == 0x5A).all() and (o[offset_out + size_out:] == 0x5A).all(), "wrote outside the output"
-    return o[offset_out:offset_out + size_out].reshape(n, y1 - y0, w, c)
+def gpu_sep(pkg, L, torch, host, wx, wy, **kw):
+    return gpu_run(SEP, pkg, L, torch, host, pkg.SepKernel.from_taps(wx, wy), **kw)
 
 
 # aligned rows (tiled kernel) and everything else (generic kernel)
@@ -70,7 +27,7 @@ RADII = [(0, 0), (1, 1), (2, 2), (3, 5), (4, 0), (0, 4), (5, 8), (8, 3), (9, 9),
 
 def test_enqueue_sep_matches_numpy(pkg, L, torch_cuda):
     rng = np.random.default_rng(2024)
-    for shapes, kern in ((TILED_SHAPES, "blur_sep_tiled_kernel"), (GENERIC_SHAPES, "blur_sep_generic_kernel")):
+    for shapes, kern in ((TILED_SHAPES, SEP.fast), (GENERIC_SHAPES, SEP.generic)):
         for (n, h, w, c) in shapes:
             img = rng.integers(0, 256, size=(n, h, w, c), dtype=np.uint8)
             for rx, ry in RADII:
@@ -83,10 +40,8 @@ def test_enqueue_sep_matches_numpy(pkg, L, torch_cuda):
 def test_enqueue_sep_unaligned_pointers(pkg, L, torch_cuda):
     rng = np.random.default_rng(5)
     img = rng.integers(0, 256, size=(2, 40, 64, 3), dtype=np.uint8)
-    wx, wy = rand_taps(rng, 6, 8), rand_taps(rng, 3, 8)
-    for oi, oo in ((1, 0), (0, 7), (3, 5)):
-        assert np.array_equal(gpu_sep(pkg, L, torch_cuda, img, wx, wy, oi, oo), ref_sep(img, wx, wy))
-        assert L.mi_blur_last_kernel() == b"blur_sep_generic_kernel"
+    k = pkg.SepKernel.from_taps(rand_taps(rng, 6, 8), rand_taps(rng, 3, 8))
+    check_unaligned_pointers(SEP, pkg, L, torch_cuda, img, k, aligned_first=False)
 
 
 def test_enqueue_sep_adversarial(pkg, L, torch_cuda):
@@ -125,20 +80,11 @@ def test_binomial_taps_reproduce_the_golden_hashes(pkg, L, O, torch_cuda, golden
 
 def test_batch_over_2gib(pkg, L, torch_cuda):
     """A batch of more than 2^31 bytes: 64-bit image offsets, 32-bit offsets inside an image."""
-    torch = torch_cuda
     rng = np.random.default_rng(8)
     img = rng.integers(0, 256, size=(1, 1024, 1024, 3), dtype=np.uint8)
     n = 720                                                   # 2.26 GB in, as much out
-    k = pkg.gauss_kernel(2.0)
-    want = torch.from_numpy(ref_sep(img, *k.taps())[0]).cuda()
-    d_in = torch.from_numpy(img[0]).cuda().unsqueeze(0).repeat(n, 1, 1, 1)
-    d_out = torch.zeros_like(d_in)
-    pkg.check(L.mi_blur_enqueue_sep(d_in.data_ptr(), d_out.data_ptr(), 1024, 1024, 3, n, C.byref(k), None))
-    torch.cuda.synchronize()
-    for i in (0, 1, n // 2, n - 1):
-        assert bool((d_out[i] == want).all()), i
-    del d_in, d_out
-    torch.cuda.empty_cache()
+    check_batch_over_2gib(SEP, pkg, L, torch_cuda, img, [pkg.gauss_kernel(2.0)], n, same=(0, 1, n // 2, n - 1),
+                          patch_last=False, check_kernel=False)
 
 
 def test_bands_split_with_halo_ry_equal_whole(pkg, L, torch_cuda):
@@ -146,16 +92,9 @@ def test_bands_split_with_halo_ry_equal_whole(pkg, L, torch_cuda):
     for (h, w, c) in ((240, 320, 3), (64, 48, 4), (37, 17, 3)):
         img = rng.integers(0, 256, size=(1, h, w, c), dtype=np.uint8)
         k = pkg.gauss_kernel(1.5, 4.0)
-        wx, wy = k.taps()
-        ry = k.ry
-        whole = gpu_sep(pkg, L, torch_cuda, img, wx, wy)
-        assert np.array_equal(whole, ref_sep(img, wx, wy))
-        for split in (ry, h // 3, h // 2, h - ry):
-            top_rows = min(h, split + ry)
-            top = gpu_sep(pkg, L, torch_cuda, np.ascontiguousarray(img[:, :top_rows]), wx, wy, y0=0, y1=split)
-            b0 = split - ry
-            bot = gpu_sep(pkg, L, torch_cuda, np.ascontiguousarray(img[:, b0:]), wx, wy, y0=ry, y1=h - b0)
-            assert np.array_equal(np.concatenate([top, bot], axis=1), whole), (h, w, c, split)
+        whole = gpu_run(SEP, pkg, L, torch_cuda, img, k)
+        assert np.array_equal(whole, ref_sep(img, *k.taps()))
+        check_gpu_band_split_equals_whole(SEP, pkg, L, torch_cuda, img, k, whole, (k.ry, h // 3, h // 2, h - k.ry))
 
 
 def test_context_with_a_kernel(pkg, L, torch_cuda):
@@ -164,57 +103,7 @@ def test_context_with_a_kernel(pkg, L, torch_cuda):
     rng = np.random.default_rng(21)
     n, h, w, c = 6, 240, 320, 3                                # 1.38 MB of output per submit: the server size class
     img = rng.integers(0, 256, size=(n, h, w, c), dtype=np.uint8)
-    k = pkg.gauss_kernel(2.5, 1.0)
-    wx, wy = k.taps()
-    want = ref_sep(img, wx, wy)
-    isz = img[0].size
-    with pkg.Context(0, w, h, c, 1, max_batch=n, n_slots=3) as ctx:
-        ctx.set_kernel(k)
-        # pageable
-        out = np.zeros_like(img)
-        ctx.submit(img.ctypes.data, out.ctypes.data, n)
-        ctx.sync()
-        assert np.array_equal(out, want)
-        assert L.mi_blur_last_kernel() == b"blur_sep_tiled_kernel"
-        # pinned: in place over the host link, one launch per submit
-        pin_in, pin_out = L.mi_blur_host_alloc(img.size), L.mi_blur_host_alloc(img.size)
-        try:
-            a = np.ctypeslib.as_array((C.c_uint8 * img.size).from_address(pin_in)).reshape(img.shape)
-            b = np.ctypeslib.as_array((C.c_uint8 * img.size).from_address(pin_out)).reshape(img.shape)
-            a[:] = img
-            z0 = L.mi_blur_zero_copy_launches(ctx.h)
-            for _ in range(3):
-                b[:] = 0
-                ctx.submit(pin_in, pin_out, n)
-                ctx.sync()
-                assert np.array_equal(b, want)
-            assert L.mi_blur_zero_copy_launches(ctx.h) == z0 + 3
-            assert L.mi_blur_last_kernel() == b"blur_sep_tiled_kernel"
-        finally:
-            L.mi_blur_host_free(pin_in)
-            L.mi_blur_host_free(pin_out)
-        # strided bands: rows [60, 180) of every image with ry halo rows, into the same rows of the output
-        ry = k.ry
-        bo = np.zeros_like(img)
-        pitch = w * c
-        ctx.submit_bands(img.ctypes.data + (60 - ry) * pitch, bo.ctypes.data + 60 * pitch, n, isz, 120 + 2 * ry, ry, ry)
-        ctx.sync()
-        assert np.array_equal(bo[:, 60:180], want[:, 60:180]) and not bo[:, :60].any() and not bo[:, 180:].any()
-        # one band
-        so = np.zeros((100, w, c), np.uint8)
-        ctx.submit_band(img[1].ctypes.data + (50 - ry) * pitch, so.ctypes.data, 100 + 2 * ry, ry, ry)
-        ctx.sync()
-        assert np.array_equal(so, want[1, 50:150])
-        # planar in, interleaved out
-        planar = np.ascontiguousarray(img.transpose(0, 3, 1, 2))
-        po = np.zeros_like(img)
-        ctx.submit_planar(planar.ctypes.data, po.ctypes.data, n)
-        ctx.sync()
-        assert np.array_equal(po, want)
-        assert L.mi_blur_ctx_set_kernel(ctx.h, C.byref(k)) == pkg.ERR_STATE
-        ctx.resident_alloc(2)
-        assert L.mi_blur_resident_run(ctx.h, 2, 1, 0) == pkg.ERR_UNSUPPORTED
-        assert L.mi_blur_resident_run_fused(ctx.h, 2, 1, 0) == pkg.ERR_UNSUPPORTED
+    check_gpu_context(SEP, pkg, L, img, pkg.gauss_kernel(2.5, 1.0), pinned_repeats=3)
     # a context without a kernel still takes the batch server for the same pinned submits
     with pkg.Context(0, w, h, c, 1, max_batch=n, n_slots=3) as ctx:
         pin_in, pin_out = L.mi_blur_host_alloc(img.size), L.mi_blur_host_alloc(img.size)
@@ -240,24 +129,8 @@ def test_gaussian_blur_python(pkg, torch_cuda):
     assert np.array_equal(pkg.gaussian_blur(g, 3.0), ref_sep(g[None, :, :, None], *pkg.gauss_kernel(3.0).taps())[0, :, :, 0])
 
 
-def write_ppm(path, img):
-    h, w, _ = img.shape
-    with open(path, "wb") as f:
-        f.write(b"P6\n%d %d\n255\n" % (w, h))
-        f.write(img.tobytes())
-
-
-def read_ppm(path):
-    with open(path, "rb") as f:
-        assert f.readline().strip() == b"P6"
-        w, h = map(int, f.readline().split())
-        assert f.readline().strip() == b"255"
-        return np.frombuffer(f.read(), np.uint8).reshape(h, w, 3)
-
-
-def test_hosts_sigma_on_the_gpu(pkg, torch_cuda, tmp_path):
-    pkg.build_native()
-    het, spl = os.path.join(pkg.APPS, "heterogeneous_blur"), os.path.join(pkg.APPS, "split_image_blur")
+def test_hosts_sigma_on_the_gpu(pkg, apps, torch_cuda, tmp_path):
+    het, spl = apps
     rng = np.random.default_rng(40)
     img = rng.integers(0, 256, size=(240, 320, 3), dtype=np.uint8)
     write_ppm(tmp_path / "in.ppm", img)

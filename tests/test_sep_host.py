@@ -1,47 +1,13 @@
 """Separable kernels of any radius (mi_blur_gauss_taps, mi_blur_cpu_run_sep, mi_blur_ctx_set_kernel, the hosts' --sigma),
-CPU only: against a numpy restatement of the definition in include/mi_blur.h, independent of the product."""
+CPU only: against a numpy restatement of the definition in include/mi_blur.h (sep_ref.py), independent of the product."""
 import ctypes as C
-import math
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
-
-# ---------------------------------------------------------------- numpy restatements
-def ref_taps(sigma, radius=0, bits=8):
-    """mi_blur_gauss_taps as the header defines it; None where it must return MI_BLUR_ERR_INVALID."""
-    if not sigma > 0 or not 0 <= radius <= 16 or not 0 <= bits <= 8:
-        return None
-    r = radius or min(16, max(1, math.ceil(3 * sigma)))
-    w = np.array([math.exp(-(i * i) / (2.0 * sigma * sigma)) for i in range(-r, r + 1)])
-    t = np.floor(w * (1 << bits) / w.sum() + 0.5).astype(np.int64)
-    t[r] += (1 << bits) - t.sum()
-    if t[r] <= 0:
-        return None
-    while r > 0 and t[0] == 0 and t[-1] == 0:
-        t, r = t[1:-1], r - 1
-    return t.tolist()
-
-
-def ref_sep(img, wx, wy):
-    """img (N, H, W, C) uint8: edge padding, exact int64 sums, one shift."""
-    rx, ry = len(wx) // 2, len(wy) // 2
-    shift = int(sum(wx)).bit_length() - 1 + int(sum(wy)).bit_length() - 1
-    n, h, w, c = img.shape
-    p = np.pad(img.astype(np.int64), ((0, 0), (ry, ry), (rx, rx), (0, 0)), mode="edge")
-    hs = sum(int(wx[i]) * p[:, :, i:i + w, :] for i in range(2 * rx + 1))
-    vs = sum(int(wy[j]) * hs[:, j:j + h, :, :] for j in range(2 * ry + 1))
-    return (vs >> shift).astype(np.uint8)
-
-
-def rand_taps(rng, r, bits):
-    """2r+1 non-negative taps summing to 2^bits (asymmetric)."""
-    if r == 0:
-        return [1 << bits]
-    cuts = np.sort(rng.integers(0, (1 << bits) + 1, size=2 * r))
-    return np.diff(np.concatenate([[0], cuts, [1 << bits]])).tolist()
+from filter_harness import SEP, apps, check_cpu_context, cpu_run, read_ppm, write_ppm  # noqa: F401
+from sep_ref import rand_taps, ref_sep, ref_taps
 
 
 @pytest.fixture(scope="module")
@@ -50,12 +16,7 @@ def sep(pkg, L):
 
 
 def cpu_sep(pkg, L, img, wx, wy, n_threads=3):
-    k = pkg.SepKernel.from_taps(wx, wy)
-    a = np.ascontiguousarray(img)
-    out = np.full_like(a, 0xA5)
-    n, h, w, c = a.shape
-    pkg.check(L.mi_blur_cpu_run_sep(a.ctypes.data, out.ctypes.data, w, h, c, n, C.byref(k), n_threads), "mi_blur_cpu_run_sep")
-    return out
+    return cpu_run(SEP, pkg, L, img, pkg.SepKernel.from_taps(wx, wy), n_threads)
 
 
 # ---------------------------------------------------------------- taps
@@ -168,36 +129,8 @@ def test_cpu_context_with_a_kernel(sep, L):
     rng = np.random.default_rng(11)
     n, h, w, c = 5, 37, 41, 3
     img = rng.integers(0, 256, size=(n, h, w, c), dtype=np.uint8)
-    k = sep.gauss_kernel(2.0, 1.0)
-    wx, wy = k.taps()
-    want = ref_sep(img, wx, wy)
-    with sep.Context(sep.DEVICE_CPU, w, h, c, 1, max_batch=n, n_slots=2, n_threads=3) as ctx:
-        ctx.set_kernel(k)
-        out = np.zeros_like(img)
-        ctx.submit(img.ctypes.data, out.ctypes.data, n)
-        ctx.sync()
-        assert np.array_equal(out, want)
-        # band with halo rows: clamping at the band's own edges, interior rows only
-        band = img[0, 10:30]
-        bo = np.zeros((20 - 3 - 2, w, c), np.uint8)
-        ctx.submit_band(band.ctypes.data, bo.ctypes.data, 20, 3, 2)
-        ctx.sync()
-        assert np.array_equal(bo, ref_sep(band[None], wx, wy)[0, 3:18])
-        # the same band of every image, strided
-        bs = np.zeros_like(img)
-        pitch = w * c
-        ctx.submit_bands(img.ctypes.data + 10 * pitch, bs.ctypes.data + 13 * pitch, n, h * pitch, 20, 3, 2)
-        ctx.sync()
-        assert np.array_equal(bs[:, 13:28], ref_sep(img[:, 10:30], wx, wy)[:, 3:18])
-        # planar in, interleaved out
-        planar = np.ascontiguousarray(img.transpose(0, 3, 1, 2))
-        po = np.zeros_like(img)
-        ctx.submit_planar(planar.ctypes.data, po.ctypes.data, n)
-        ctx.sync()
-        assert np.array_equal(po, want)
-        assert L.mi_blur_ctx_set_kernel(ctx.h, C.byref(k)) == sep.ERR_STATE              # after the first submit
-        assert L.mi_blur_resident_run(ctx.h, 1, 1, 0) == sep.ERR_UNSUPPORTED
-        assert L.mi_blur_resident_run_fused(ctx.h, 1, 1, 0) == sep.ERR_UNSUPPORTED
+    # halo rows 3 above and 2 below whatever the kernel's own radius (sigma_y 1: 3)
+    check_cpu_context(SEP, sep, L, img, sep.gauss_kernel(2.0, 1.0), dict(n_slots=2, n_threads=3), halos=(3, 2))
     with sep.Context(sep.DEVICE_CPU, w, h, c, 1, max_batch=n) as ctx:
         bad = sep.SepKernel.from_taps([1, 2, 1]); bad.bx = 1
         assert L.mi_blur_ctx_set_kernel(ctx.h, C.byref(bad)) == sep.ERR_INVALID
@@ -218,27 +151,6 @@ def test_gaussian_blur_on_the_cpu_device(sep):
 
 
 # ---------------------------------------------------------------- hosts
-@pytest.fixture(scope="module")
-def apps(pkg):
-    pkg.build_native()
-    return os.path.join(pkg.APPS, "heterogeneous_blur"), os.path.join(pkg.APPS, "split_image_blur")
-
-
-def write_ppm(path, img):
-    h, w, _ = img.shape
-    with open(path, "wb") as f:
-        f.write(b"P6\n%d %d\n255\n" % (w, h))
-        f.write(img.tobytes())
-
-
-def read_ppm(path):
-    with open(path, "rb") as f:
-        assert f.readline().strip() == b"P6"
-        w, h = map(int, f.readline().split())
-        assert f.readline().strip() == b"255"
-        return np.frombuffer(f.read(), np.uint8).reshape(h, w, 3)
-
-
 def test_host_cpu_sigma(sep, apps, tmp_path):
     het, _ = apps
     rng = np.random.default_rng(9)
