@@ -309,6 +309,7 @@ def lib() -> C.CDLL:
         "mi_blur_fnv1a64": (C.c_uint64, [u8p, C.c_size_t]),
         "mi_blur_debug_zc_trace": (i, [vp, C.POINTER(C.c_uint64), i, C.POINTER(i), C.POINTER(C.c_uint)]),
         "mi_blur_debug_xcd_times": (i, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), i]),
+        "mi_blur_debug_xcd_raw": (i, [C.POINTER(C.c_uint64), C.c_size_t, C.c_size_t]),
         "mi_blur_a1_partition": (None, [i, i, C.c_float, C.POINTER(i), C.POINTER(i)]),
         "mi_blur_shard_range": (None, [C.c_longlong, i, i, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]),
         "mi_blur_a2_split": (None, [i, C.c_float, i, C.POINTER(A2Geometry)]),

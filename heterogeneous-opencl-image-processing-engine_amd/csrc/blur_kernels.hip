@@ -526,6 +526,10 @@ struct FusedParams {
     // end of the grid draw them from *tail_ctr one by one and leave when none is left
     unsigned *tail_ctr;
     unsigned nstatic, ntail, nextra;
+    // overlap gate ("fused_overlap"; nullptr = none): the workgroup numbered gate_block stores the pass's sequence number here
+    // when it starts, which lets the next pass, queued on the other stream behind fused_gate_kernel, begin while this one ends
+    unsigned *gate;
+    unsigned gate_block, gate_seq;
 };
 
 template <int C, int R, int RPG>
@@ -566,6 +570,10 @@ __global__ __launch_bounds__(256) void blur_fused_tail_kernel(const TiledParams 
 {
     // (one call site of the tile code, reached by both kinds of block: with the tile code inside a ticket loop the same
     // compiler schedules the whole kernel 2.6x slower)
+    const unsigned long long t0 = p.xcd_times ? __builtin_amdgcn_s_memrealtime() : 0ull;
+    // Sequence numbers only grow, so a waiter that compares with a signed difference cannot miss this store.  One lane, a
+    // relaxed store at agent scope: nothing of the pass is ordered by it, the gate only says how far the pass has come.
+    if (f.gate && blockIdx.x == f.gate_block && threadIdx.x == 0) __hip_atomic_store(f.gate, f.gate_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     unsigned tile, w;
     if (blockIdx.x >= f.nstatic) {
         __shared__ unsigned s_ticket;
@@ -593,6 +601,23 @@ __global__ __launch_bounds__(256) void blur_fused_tail_kernel(const TiledParams 
     if (threadIdx.x == 0) {
         if (f.release) __hip_atomic_fetch_add(&f.count[b * f.kcount + ((w ^ (w >> 3)) & (f.kcount - 1u))], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
         else __hip_atomic_fetch_add(&f.count[b * f.kcount + ((w ^ (w >> 3)) & (f.kcount - 1u))], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (p.xcd_times) xcd_time_mark(p.xcd_times, t0);      // diagnostics; extra workgroups that drew no tile leave no stamp
+}
+
+// One wave in front of a fused pass on the context's second stream: it ends when the pass before it (on the other stream)
+// has raised the gate to `want` or beyond — compared as a signed difference, the numbers wrap — or after ZC_HARD_TICKS.
+// The stream then starts the pass queued behind it whatever the reason was: the gate decides WHEN that pass starts, nothing else.
+__global__ __launch_bounds__(64) void fused_gate_kernel(const unsigned *gate, unsigned want)
+{
+    const unsigned long long t0 = wall_clock64();
+    for (;;) {
+        unsigned v = 0;
+        if (threadIdx.x == 0) v = __hip_atomic_load(gate, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        v = __builtin_amdgcn_readfirstlane(v);
+        if ((int)(v - want) >= 0) return;
+        if (wall_clock64() - t0 > ZC_HARD_TICKS) return;
+        __builtin_amdgcn_s_sleep(2);
     }
 }
 
@@ -1360,19 +1385,29 @@ static int launch_tiled(const LaunchDesc &d, const Tunables &tun, bool ragged = 
         if (fused->tiles_per_batch) *fused->tiles_per_batch = (unsigned)tpb;
         if (fused->waves_per_block) *fused->waves_per_block = 1;      // one count per block
         if (fused->total_blocks) *fused->total_blocks = (unsigned)nblocks;
+        // tiles of the dynamic tail these knobs give the pass (0 = every tile is mapped to a workgroup)
+        const unsigned ntail = tun.fused_tail > 0 && fused->tail_ctr && nblocks >= 8192 ? (unsigned)(nblocks * tun.fused_tail / 1000) : 0u;
+        if (fused->tail_tiles) *fused->tail_tiles = ntail >= 8 ? ntail : 0u;
         if (fused->geometry_only) return MI_BLUR_OK;
         p.debug_copy = 0;
         // dynamic tail ("fused_tail" t, per mille of the pass's tiles; 0 = off): worth it only when the pass is many rounds of
         // resident workgroups long; the counter comes from a small ring so that passes in flight on different streams do not share one
-        if (tun.fused_tail > 0 && fused->tail_ctr && nblocks >= 8192) {
-            const unsigned ntail = (unsigned)(nblocks * tun.fused_tail / 1000);
-            if (ntail >= 8) {
-                f.tail_ctr = fused->tail_ctr; f.ntail = ntail; f.nstatic = (unsigned)nblocks - ntail;
-                f.nextra = ntail + (unsigned)((long long)ntail * std::max(10, tun.fused_tail_blocks) / 100);
-                g_last_kernel = "blur_fused_tail_kernel";
-                const dim3 tgrid(f.nstatic + f.nextra);
-                return dispatch<1, 2>(R, [&](auto Rc) { return launch_fused_r<Rc>(d, p, f, tgrid, block, lds, rpg, ragged); });
+        if (ntail >= 8) {
+            f.tail_ctr = fused->tail_ctr; f.ntail = ntail; f.nstatic = (unsigned)nblocks - ntail;
+            f.nextra = ntail + (unsigned)((long long)ntail * std::max(10, tun.fused_tail_blocks) / 100);
+            g_last_kernel = "blur_fused_tail_kernel";
+            const dim3 tgrid(f.nstatic + f.nextra);
+            // overlap gate ("fused_overlap" v): raised by the workgroup that starts when v per mille of the pass's tiles are
+            // still to be handed out — with v = "fused_tail" that is the first ticket-drawing workgroup
+            if (fused->gate && tun.fused_overlap > 0 && !ragged) {
+                const long long ahead = nblocks * tun.fused_overlap / 1000;
+                f.gate = fused->gate; f.gate_seq = fused->seq;
+                f.gate_block = (unsigned)std::min<long long>(std::max<long long>(nblocks - ahead, 0), (long long)tgrid.x - 1);
             }
+            // diagnostics: consecutive passes of up to 65536 workgroups stamp 16 regions of the slot buffer in turn, so that the
+            // stamps of back-to-back passes can be read together (mi_blur_debug_xcd_raw)
+            if (p.xcd_times && tgrid.x <= 65536u) p.xcd_times += 2ull * 65536ull * (fused->seq & 15u);
+            return dispatch<1, 2>(R, [&](auto Rc) { return launch_fused_r<Rc>(d, p, f, tgrid, block, lds, rpg, ragged); });
         }
         if (ragged) {      // ragged rows, no tail: the same kernel with every tile mapped to a block
             if (!fused->tail_ctr) return MI_BLUR_ERR_UNSUPPORTED;
@@ -1433,6 +1468,12 @@ int launch_fused_watch(const unsigned *count, unsigned n_batches, unsigned tiles
 {
     if (!count || !host_word || n_batches == 0 || tiles_per_batch == 0 || counters_per_batch < 8 || (counters_per_batch & (counters_per_batch - 1))) return MI_BLUR_ERR_INVALID;
     return do_launch(fused_watch_kernel, dim3(1), dim3(64), 0, stream, count, n_batches, tiles_per_batch, total_blocks, per_block, host_word, pass_seq, counters_per_batch);
+}
+
+int launch_fused_gate(const unsigned *gate, unsigned want, hipStream_t stream)
+{
+    if (!gate) return MI_BLUR_ERR_INVALID;
+    return do_launch(fused_gate_kernel, dim3(1), dim3(64), 0, stream, gate, want);
 }
 
 int launch_fused(const LaunchDesc &d, const FusedDesc &f)

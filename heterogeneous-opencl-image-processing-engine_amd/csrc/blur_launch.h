@@ -60,9 +60,15 @@ struct FusedDesc {
     unsigned *tail_ctr;     // device word, zero between passes: ticket counter of the pass's dynamic tail ("fused_tail"); nullptr = none
     long long count_words;  // how many words `count` holds (0 = at least 8 per batch, the minimum)
     unsigned *counters_per_batch;   // geometry output: counters each batch uses (8 .. 256; count[k * b .. k * b + k - 1] belong to batch b)
+    unsigned *tail_tiles;   // geometry output: tiles of the pass's dynamic tail (0 = blur_fused_kernel or an empty tail)
+    unsigned *gate;         // device word or nullptr: a pass with a dynamic tail stores `seq` there when "fused_overlap" per mille of
+    unsigned seq;           // it is left (one workgroup, once); also the number of the pass among the context's fused passes
 };
 int launch_fused(const LaunchDesc &d, const FusedDesc &f);
-// Watcher of one fused pass (fused_watch_kernel, one wave on a stream of its own): follows the per-batch counters and keeps
+// One wave on `stream` that ends when *gate has reached `want` (signed difference) or after ZC_HARD_TICKS (fused_gate_kernel):
+// whatever is queued behind it on that stream starts then.  A hint for WHEN, never a condition for correctness.
+int launch_fused_gate(const unsigned *gate, unsigned want, hipStream_t stream);
+// Watcher of one fused pass (fused_watch_kernel, one wave on a stream other than the pass's): follows the per-batch counters and keeps
 // *host_word (pinned host memory) = (pass_seq << 32) | leading batches complete, so the host reads a batch's completion
 // from its own memory instead of copying the counters back.  Ends when all n_batches are complete (or after a hard limit).
 int launch_fused_watch(const unsigned *count, unsigned n_batches, unsigned tiles_per_batch, unsigned total_blocks, unsigned per_block,
@@ -150,6 +156,8 @@ struct Tunables {
     int fused_tail;      // fused stream: per mille of a pass's tiles that are handed out dynamically at the end (0 = none)
     int fused_adds_per_word; // fused stream: a batch gets as many completion counters (8 .. 256) as keep the adds per counter and pass under this
     int fused_tail_blocks; // ... by (100 + this) % as many extra workgroups as there are tail tiles (one ticket each; default 100)
+    int fused_overlap;   // fused stream: 0 = every pass on one stream; v > 0 = consecutive passes with a dynamic tail alternate over two
+                         // streams and a pass starts when its predecessor has v per mille of its tiles left (default 30)
     int zero_copy_server;  // zero-copy submits of aligned shapes go through the batch server (one long-lived dispatch per stream of
                            // batches, blur_server_kernel) instead of one launch per batch: 1 (default) | 0
     int zero_copy_server_min_kb; // batch server: submits whose output is smaller than this many KiB take one launch each instead (default 1280)
@@ -194,6 +202,7 @@ static constexpr Knob KNOBS[] = {
     {"fused_adds_per_word", &Tunables::fused_adds_per_word, KnobKind::RANGE, 4, 4096, 32, nullptr},
     {"fused_tail_blocks", &Tunables::fused_tail_blocks, KnobKind::RANGE, 10, 800, 25, nullptr},
     {"fused_tail", &Tunables::fused_tail, KnobKind::RANGE, 0, 500, 30, "MI_BLUR_FUSED_TAIL"},
+    {"fused_overlap", &Tunables::fused_overlap, KnobKind::RANGE, 0, 500, 30, "MI_BLUR_FUSED_OVERLAP"},
     {"fused_window", &Tunables::fused_window, KnobKind::RANGE, 1, 4096, 8, nullptr},
     {"debug_xcd_times", &Tunables::debug_xcd_times, KnobKind::FLAG, 0, 1, 0, nullptr},
     {"zero_copy_events", &Tunables::zero_copy_events, KnobKind::FLAG, 0, 1, 1, nullptr},

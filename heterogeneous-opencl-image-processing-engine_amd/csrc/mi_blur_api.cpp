@@ -476,10 +476,19 @@ struct mi_blur_ctx {
     int fused_n = 0, fused_batch = 0;                            // its (n_images, batch): same again = counters keep counting up
     unsigned fused_passes = 0;                                   // passes accumulated in the counters since they were zeroed
     hipStream_t fused_poll = nullptr;
-    hipStream_t fused_watch = nullptr;                           // the watcher's own stream (peeks on fused_poll must not queue behind it)
     unsigned long long *fused_word = nullptr, *fused_word_dev = nullptr;   // watcher's progress word: pinned host memory + its device address
     unsigned fused_watch_seq = 0;                                // sequence number of the latest watched pass (0 = none)
     bool fused_watched = false;                                  // the latest pass has a watcher
+    bool fused_watch_busy = false;                               // a watcher was launched and its stream not waited for since
+    // overlap of consecutive fused passes ("fused_overlap"): they alternate between slot 0's stream and this one, each behind a
+    // one-wave gate kernel that ends when its predecessor raises the gate word (device memory, behind the counters).  The
+    // watcher of a watched pass runs here too.
+    hipStream_t fused_second = nullptr;
+    hipEvent_t fused_ev = nullptr;                               // orders the slot streams behind what fused_second holds
+    unsigned fused_seq = 0;                                      // number of the latest fused pass; only ever grows
+    bool fused_gated = false;                                    // that pass raises the gate word to fused_seq
+    bool fused_on_second = false;                                // ... and was issued to fused_second
+    bool fused_second_busy = false;                              // fused_second got a pass since the slot streams last waited for it
     ZcServer *zc = nullptr;                                      // batch server, made on the first submit that can use it
     std::vector<float> place_ms;                                 // resident pool: per-launch ms of each candidate placement tried
     int place_kept = 0;
@@ -685,6 +694,9 @@ extern "C" int mi_blur_create(mi_blur_ctx **out_ctx, int device, int width, int 
         if ((e = hipEventCreate(&s.ks)) != hipSuccess && fail(e)) break;
         if ((e = hipEventCreate(&s.ke)) != hipSuccess && fail(e)) break;
     }
+    // the fused stream's second stream comes right after the slots': HIP hands hardware queues to streams in creation order
+    if (!rc && (e = hipStreamCreateWithFlags(&c->fused_second, hipStreamNonBlocking)) != hipSuccess) fail(e);
+    if (!rc && (e = hipEventCreateWithFlags(&c->fused_ev, hipEventDisableTiming)) != hipSuccess) fail(e);
     if (rc) { mi_blur_destroy(c); return rc; }
     *out_ctx = c;
     return MI_BLUR_OK;
@@ -802,8 +814,10 @@ extern "C" int mi_blur_sync(mi_blur_ctx *c, mi_blur_timing *timing)
             if (rc) return rc;
         }
         for (auto &s : c->slots) HIP_TRY(hipStreamSynchronize(s.stream));
-        // a watched fused pass: its watcher (own stream) ends with the pass; after a sync the count it published is final
-        if (c->fused_watched && c->fused_watch) HIP_TRY(hipStreamSynchronize(c->fused_watch));
+        if (c->fused_second) HIP_TRY(hipStreamSynchronize(c->fused_second));      // every other fused pass runs there
+        c->fused_second_busy = false; c->fused_gated = false;        // drained: the next pass has nothing to overlap with, no gate kernel
+        // (a watched fused pass: its watcher, on the second stream, ends with the pass; after a sync the count it published is final)
+        c->fused_watch_busy = false;
         harvest_resident(c);
         c->zc_ref_valid = false;                                 // everything drained: the next zero-copy launch starts a new window
     }
@@ -844,6 +858,7 @@ extern "C" void mi_blur_destroy(mi_blur_ctx *c)
     if (!c->is_cpu()) {
         (void)hipSetDevice(c->device);
         for (auto &s : c->slots) { if (s.stream) (void)hipStreamSynchronize(s.stream); }
+        if (c->fused_second) (void)hipStreamSynchronize(c->fused_second);
         if (c->zc) {                                             // tell the servers to leave, wait for them, release
             ZcServer &z = *c->zc;
             if (z.ctl) __atomic_store_n(&z.ctl->quit, 1u, __ATOMIC_RELEASE);
@@ -864,8 +879,9 @@ extern "C" void mi_blur_destroy(mi_blur_ctx *c)
         if (c->fused_count) (void)hipFree(c->fused_count);
         if (c->fused_host) (void)hipHostFree(c->fused_host);
         if (c->fused_poll) { (void)hipStreamSynchronize(c->fused_poll); (void)hipStreamDestroy(c->fused_poll); }
-        if (c->fused_watch) { (void)hipStreamSynchronize(c->fused_watch); (void)hipStreamDestroy(c->fused_watch); }
         if (c->fused_word) (void)hipHostFree(c->fused_word);
+        if (c->fused_second) (void)hipStreamDestroy(c->fused_second);
+        if (c->fused_ev) (void)hipEventDestroy(c->fused_ev);
         if (c->pool_in) (void)hipFree(c->pool_in);
         if (c->pool_out) (void)hipFree(c->pool_out);
         (void)hipGetLastError();
@@ -1481,6 +1497,16 @@ extern "C" int mi_blur_resident_fill_synthetic(mi_blur_ctx *c, int first_index)
 extern "C" void *mi_blur_resident_in(mi_blur_ctx *c) { return c ? c->pool_in : nullptr; }
 extern "C" void *mi_blur_resident_out(mi_blur_ctx *c) { return c ? c->pool_out : nullptr; }
 
+// What follows on the slot streams comes after the fused passes that went to the second stream (an event; no host wait).
+static int fused_join(mi_blur_ctx *c)
+{
+    if (!c->fused_second_busy) return MI_BLUR_OK;
+    HIP_TRY(hipEventRecord(c->fused_ev, c->fused_second));
+    for (auto &s : c->slots) HIP_TRY(hipStreamWaitEvent(s.stream, c->fused_ev, 0));
+    c->fused_second_busy = false;
+    return MI_BLUR_OK;
+}
+
 // One pass of the stream over the resident pool: the batch loop of
 // heterogeneous_blur.c:418-427 with the transfers gone (data already in HBM).
 extern "C" int mi_blur_resident_run(mi_blur_ctx *c, int n_images, int batch, int timed_every)
@@ -1490,6 +1516,7 @@ extern "C" int mi_blur_resident_run(mi_blur_ctx *c, int n_images, int batch, int
     if (c->is_cpu() || !c->pool_in) return MI_BLUR_ERR_STATE;
     if (batch > c->pool_images) return MI_BLUR_ERR_INVALID;
     HIP_TRY(hipSetDevice(c->device));
+    { int rc = fused_join(c); if (rc) return rc; }
     int launch_idx = 0;
     for (int done = 0; done < n_images; done += batch, launch_idx++) {
         const int b = std::min(batch, n_images - done);
@@ -1527,6 +1554,9 @@ extern "C" int mi_blur_resident_run(mi_blur_ctx *c, int n_images, int batch, int
 // Words of the per-batch completion counters for a pool of `cap` images: 8 per batch at the smallest batch (one image), plus room
 // for a few batches of thousands of tiles to spread over up to 256 words each (two 8192x8192 frames are two batches of 3200 tiles)
 static size_t fused_words(int cap) { return 8 * (size_t)cap + 16384; }
+// Behind the counters: the ticket word of a pass's dynamic tail in two banks (passes alternate, so two passes in flight never
+// share one; each is zero between passes) and the overlap gate word, 128 bytes apart.
+constexpr size_t FUSED_TAIL_BANK = 32, FUSED_GATE_WORD = 64, FUSED_EXTRA_WORDS = 96;
 
 extern "C" int mi_blur_resident_run_fused(mi_blur_ctx *c, int n_images, int batch, int timed)
 {
@@ -1539,13 +1569,16 @@ extern "C" int mi_blur_resident_run_fused(mi_blur_ctx *c, int n_images, int batc
     if (nb > c->fused_cap) {
         // the previous pass may still be writing its flags
         for (auto &s : c->slots) HIP_TRY(hipStreamSynchronize(s.stream));
+        if (c->fused_second) HIP_TRY(hipStreamSynchronize(c->fused_second));
+        c->fused_second_busy = false; c->fused_gated = false;
         if (c->fused_count) { (void)hipFree(c->fused_count); c->fused_count = nullptr; }
         if (c->fused_host) { (void)hipHostFree(c->fused_host); c->fused_host = nullptr; }
         c->fused_cap = 0;
         const int cap = std::max(nb, c->pool_images);      // enough for any batch size on this pool: never reallocated
-        // (+16 words: the ticket counter of a pass's dynamic tail lives behind the batch counters; it is zero between passes)
-        HIP_TRY(hipMalloc((void **)&c->fused_count, sizeof(unsigned) * (fused_words(cap) + 16)));
-        HIP_TRY(hipMemset(c->fused_count + fused_words(cap), 0, sizeof(unsigned) * 16));
+        HIP_TRY(hipMalloc((void **)&c->fused_count, sizeof(unsigned) * (fused_words(cap) + FUSED_EXTRA_WORDS)));
+        HIP_TRY(hipMemset(c->fused_count + fused_words(cap), 0, sizeof(unsigned) * FUSED_EXTRA_WORDS));
+        // the gate word starts at the number of the latest pass (all of them are over), never below: it only ever grows
+        HIP_TRY(hipMemcpy(c->fused_count + fused_words(cap) + FUSED_GATE_WORD, &c->fused_seq, sizeof(unsigned), hipMemcpyHostToDevice));
         HIP_TRY(hipDeviceSynchronize());
         HIP_TRY(hipHostMalloc((void **)&c->fused_host, sizeof(unsigned) * fused_words(cap), hipHostMallocDefault));
         c->fused_cap = cap;
@@ -1566,19 +1599,39 @@ extern "C" int mi_blur_resident_run_fused(mi_blur_ctx *c, int n_images, int batc
     // The launch geometry (blocks per batch) depends on the tuning knobs as well as on the shape: take ONE copy of the
     // knobs, ask for the geometry first, launch with the same copy.
     const Tunables tun = tunables();
-    unsigned tpb = 0, wpb = 0, blocks = 0, kcnt = 8;
-    FusedDesc f{c->fused_count, batch, &tpb, &wpb, &blocks, &tun, true, c->fused_count + fused_words(c->fused_cap), (long long)fused_words(c->fused_cap), &kcnt};
+    unsigned tpb = 0, wpb = 0, blocks = 0, kcnt = 8, ntail = 0;
+    unsigned *const extra = c->fused_count + fused_words(c->fused_cap);
+    const unsigned seq = c->fused_seq + 1u;
+    FusedDesc f{c->fused_count, batch, &tpb, &wpb, &blocks, &tun, true, extra + (tun.fused_overlap > 0 ? (seq & 1u) * FUSED_TAIL_BANK : 0), (long long)fused_words(c->fused_cap), &kcnt,
+                &ntail, nullptr, seq};
     int rc = launch_fused(d, f);
     if (rc) return rc;
+    const bool same = n_images == c->fused_n && batch == c->fused_batch && tpb == c->fused_tpb && wpb == c->fused_wpb && kcnt == c->fused_k &&
+                      blocks == c->fused_blocks && c->fused_passes > 0 && c->fused_passes < (1u << 20);
+    // "fused_overlap": a pass with a dynamic tail on whole-chunk rows, unwatched, raises the gate word when it enters its tail.  The
+    // pass after it — if it is of the same kind and its counters count on — goes to the OTHER stream behind a gate kernel and starts
+    // there.  The gate is a hint: the gate kernel always ends, and nothing but the moment pass p+1 starts depends on it.  Every other
+    // pass stays on slot 0's stream, ordered by an event behind what the second stream still holds.
+    const bool raises = tun.fused_overlap > 0 && ntail > 0 && !(timed & 2) && tiled_eligible(d.in, d.out, c->W, c->C);
+    const bool overlap = raises && same && c->fused_gated;
+    if (overlap) {
+        d.stream = c->fused_on_second ? s.stream : c->fused_second;
+        rc = launch_fused_gate(extra + FUSED_GATE_WORD, c->fused_seq, d.stream);
+        if (rc) return rc;
+    } else {
+        rc = fused_join(c);          // (also in front of the zeroing fill below: the pass on the other stream still counts)
+        if (rc) return rc;
+    }
+    if (raises) f.gate = extra + FUSED_GATE_WORD;
     // Repeated passes of the same shape AND geometry do not zero the counters (that would be one more dispatch per
     // pass): every pass adds the same amounts, so batch b of pass p is complete when its counters sum to p x (its blocks).
-    if (n_images == c->fused_n && batch == c->fused_batch && tpb == c->fused_tpb && wpb == c->fused_wpb && kcnt == c->fused_k &&
-        blocks == c->fused_blocks && c->fused_passes > 0 && c->fused_passes < (1u << 20)) {
+    if (same) {
         c->fused_passes += 1;
     } else {
-        // the counters are about to be zeroed: a watcher of the previous pass must have seen that pass's last counts first
-        // (it ends with its pass; zeros under it would leave it waiting for its hard limit)
-        if (c->fused_watched && c->fused_watch) HIP_TRY(hipStreamSynchronize(c->fused_watch));
+        // the counters are about to be zeroed: a watcher of an earlier pass must have seen that pass's last counts first
+        // (it ends with its pass, but walks the batches one by one and may still be on its way when unwatched passes have
+        // followed; zeros under it would leave it waiting for its hard limit)
+        if (c->fused_watch_busy) { HIP_TRY(hipStreamSynchronize(c->fused_second)); c->fused_watch_busy = false; }
         HIP_TRY(hipMemsetAsync(c->fused_count, 0, sizeof(unsigned) * (size_t)kcnt * (size_t)nb, s.stream));
         c->fused_n = n_images; c->fused_batch = batch; c->fused_passes = 1;
         c->fused_tpb = tpb; c->fused_wpb = wpb; c->fused_blocks = blocks; c->fused_k = kcnt;
@@ -1589,16 +1642,11 @@ extern "C" int mi_blur_resident_run_fused(mi_blur_ctx *c, int n_images, int batc
         // a watcher wave keeps (pass, leading batches complete) in pinned host memory for this pass.  Counters that were just
         // zeroed must BE zero before it looks at them: it runs on its own stream, so wait for the fill.
         if (c->fused_passes == 1) HIP_TRY(hipStreamSynchronize(s.stream));
-        if (!c->fused_watch) HIP_TRY(hipStreamCreateWithFlags(&c->fused_watch, hipStreamNonBlocking));
         if (!c->fused_word) {
             HIP_TRY(hipHostMalloc((void **)&c->fused_word, sizeof(unsigned long long), hipHostMallocDefault));
             *c->fused_word = 0;
             HIP_TRY(hipHostGetDevicePointer((void **)&c->fused_word_dev, c->fused_word, 0));
         }
-        c->fused_watch_seq += 1;
-        rc = launch_fused_watch(c->fused_count, (unsigned)nb, tpb, blocks, wpb * c->fused_passes, c->fused_word_dev, c->fused_watch_seq, c->fused_watch, c->fused_k);
-        if (rc) return rc;
-        c->fused_watched = true;
     }
     if (timed & 1) {
         if (c->ev_used == c->ev_pool.size()) {
@@ -1612,12 +1660,28 @@ extern "C" int mi_blur_resident_run_fused(mi_blur_ctx *c, int n_images, int batc
     }
     f.geometry_only = false;
     rc = launch_fused(d, f);
-    if (rc) { c->fused_passes = 0; c->fused_batches = 0; return rc; }     // nothing ran: zero the counters next time
+    if (rc) { c->fused_passes = 0; c->fused_batches = 0; c->fused_gated = false; return rc; }     // nothing ran: zero the counters next time
+    c->fused_seq = seq;
+    c->fused_gated = raises;
+    c->fused_on_second = d.stream == c->fused_second;
+    if (c->fused_on_second) c->fused_second_busy = true;
     c->cursor += n_images;
     c->tm.launches += 1;
     c->tm.images += (uint64_t)n_images;
     c->tm.bytes_alg += 2ull * c->image_bytes * (uint64_t)n_images;
     if (timed & 1) { c->timed_launches += 1; c->timed_bytes_alg += 2ull * c->image_bytes * (uint64_t)n_images; }
+    if (timed & 2) {
+        // The watcher runs on the second stream (a watched pass never does; peeks on fused_poll must not queue behind it), so a
+        // context has as many streams as it had before the second one carried passes: streams beyond the hardware queues share
+        // one, and a queue runs its dispatches in order.  For the same reason it is queued AFTER its pass: in front of it on a
+        // shared queue it would hold the pass back until its own hard limit.
+        c->fused_watch_seq += 1;
+        rc = launch_fused_watch(c->fused_count, (unsigned)nb, tpb, blocks, wpb * c->fused_passes, c->fused_word_dev, c->fused_watch_seq, c->fused_second, c->fused_k);
+        if (rc) return rc;
+        c->fused_watched = true;
+        c->fused_watch_busy = true;
+        c->fused_second_busy = true;
+    }
     return MI_BLUR_OK;
 }
 
@@ -1746,6 +1810,17 @@ extern "C" int mi_blur_debug_xcd_times(uint64_t end_ticks[8], uint64_t begin_tic
     }
     for (int i = 0; i < 8; i++) { if (end_ticks) end_ticks[i] = e[i]; if (begin_ticks) begin_ticks[i] = b[i]; }
     if (rearm) HIP_TRY(hipMemset(d, 0, 16 * n));
+    return MI_BLUR_OK;
+}
+
+// Diagnostics (see mi_blur.h): the raw stamps of slots [first_slot, first_slot + n_slots).
+extern "C" int mi_blur_debug_xcd_raw(uint64_t *out, size_t first_slot, size_t n_slots)
+{
+    unsigned long long *d = debug_xcd_buffer();
+    if (!d) return MI_BLUR_ERR_NOMEM;
+    if (!out || first_slot > debug_xcd_slots() || n_slots > debug_xcd_slots() - first_slot) return MI_BLUR_ERR_INVALID;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, d + 2 * first_slot, 16 * n_slots, hipMemcpyDeviceToHost));
     return MI_BLUR_OK;
 }
 

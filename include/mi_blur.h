@@ -129,6 +129,14 @@ const char *mi_blur_last_kernel(void);
  *                      by ticket to spare workgroups at the end of the grid instead of being mapped to workgroups, so that an
  *                      XCD that runs ahead takes more of them (passes of >= 8192 tiles; -1.3..1.8 % per pass).  0 = static map
  *   "fused_tail_blocks" 25 (default): spare workgroups beyond the number of tail tiles, per cent
+ *   "fused_overlap"    30 (default; MI_BLUR_FUSED_OVERLAP in the environment) | 0 .. 500: consecutive fused passes that take the
+ *                      dynamic tail (whole-chunk rows, no watcher, same shape and batch) alternate between the context's first
+ *                      stream and a second one, and a pass starts when its predecessor has this many per mille of its tiles
+ *                      left to hand out instead of after its last workgroup has ended: the drain of one pass and the ramp of
+ *                      the next share the chip.  The predecessor stores its number in a gate word when it gets there; a one-wave
+ *                      kernel in front of the next pass waits for that (at most 10 s, then the pass runs anyway).  Outputs,
+ *                      counters and what mi_blur_resident_batches_done reports do not depend on it; a pass's own start-to-stop
+ *                      time gets longer by about the overlap (profiles/r09_fused_overlap.md).  0 = every pass on one stream
  *   "fused_release"    0 (default) | 1: how a block of the fused stream publishes "my outputs are in memory" — see
  *                      mi_blur_resident_run_fused */
 int mi_blur_set_option(const char *key, int value);
@@ -329,7 +337,7 @@ void mi_blur_timed_coverage(mi_blur_ctx *ctx, uint64_t *launches, uint64_t *byte
  * may still be running) without being the unit of DISPATCH.  n_images <= pool size (one contiguous run of the pool); 1-4 channels, rows of
  * at least 16 bytes — rows that are a multiple of 16 bytes take the aligned tiles, any other width their ragged form
  * (MI_BLUR_ERR_UNSUPPORTED otherwise).  `timed` is a bit set: 1 = the dispatch carries timestamp events like resident_run;
- * 2 = WATCH this pass: a one-wave kernel on a stream of its own follows the counters and keeps "leading batches complete" in
+ * 2 = WATCH this pass: a one-wave kernel on the context's second stream (never the pass's own) follows the counters and keeps "leading batches complete" in
  * pinned host memory, so that mi_blur_resident_batches_done is a read of the caller's own memory (tens of ns, no HIP call)
  * instead of a counter read-back (~18 us) — for hosts that consume batch by batch while the pass runs.
  * Asynchronous; follow with mi_blur_sync.
@@ -564,6 +572,12 @@ int mi_blur_ctx_set_conv(mi_blur_ctx *ctx, const mi_blur_conv *k);
  * LATEST end and the EARLIEST start seen since the last re-arm, and re-arms the slots when asked (call it once with
  * rearm = 1 before the launches to be examined).  Shows which XCD a launch waits for (profiles/r02_xcd_finish_times.txt). */
 int mi_blur_debug_xcd_times(uint64_t end_ticks[8], uint64_t begin_ticks[8], int rearm);
+
+/* The raw stamps behind mi_blur_debug_xcd_times: waits for the device and copies slots [first_slot, first_slot + n_slots) of the
+ * 2^20 slots, two words each: (end tick << 4 | XCD) and the start tick of the workgroup of that number, 0 = not written.  A fused
+ * pass with a dynamic tail of at most 65536 workgroups writes the region of 65536 slots numbered (its number among the context's
+ * fused passes) mod 16, so that up to 16 back-to-back passes can be read together (profiles/r09_fused_overlap.md). */
+int mi_blur_debug_xcd_raw(uint64_t *out, size_t first_slot, size_t n_slots);
 
 /* Developer diagnostics of the zero-copy batch server (mi_blur_set_option("zero_copy_trace", 1) before the context's first
  * zero-copy submit): per worker workgroup and batch, for the context's first 512 batches — device clock (100 MHz ticks)
