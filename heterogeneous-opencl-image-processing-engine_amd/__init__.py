@@ -41,6 +41,8 @@ CONV_SAT, CONV_ABS, CONV_MAG = 0, 1, 2
 CONV_MODES = {"sat": CONV_SAT, "abs": CONV_ABS, "mag": CONV_MAG}
 CONV_PRESETS = {"sobel_x": 0, "sobel_y": 1, "sobel_mag": 2, "scharr_x": 3, "scharr_y": 4, "scharr_mag": 5,
                 "laplacian4": 6, "laplacian8": 7, "sharpen": 8, "emboss": 9}
+DECIMATE_MAX = 4
+DOWN_PYR, DOWN_AREA2, DOWN_AREA4 = 0, 1, 2
 PEER_HANDLE_BYTES = 64
 
 
@@ -53,7 +55,7 @@ def _newer(target: str, sources: list[str]) -> bool:
 
 def build_native(force: bool = False, verbose: bool = False) -> str:
     """Compile libmi_blur.so (hipcc, --offload-arch=gfx950) and the C++ hosts, in-tree."""
-    srcs = [os.path.join(CSRC, f) for f in ("blur_kernels.hip", "sep_kernels.hip", "median_kernels.hip", "morph_kernels.hip", "bilateral_kernels.hip", "conv_kernels.hip", "layout_kernels.hip", "mi_blur_api.cpp", "cpu_device.cpp")]
+    srcs = [os.path.join(CSRC, f) for f in ("blur_kernels.hip", "sep_kernels.hip", "median_kernels.hip", "morph_kernels.hip", "bilateral_kernels.hip", "conv_kernels.hip", "sep_down_kernels.hip", "layout_kernels.hip", "mi_blur_api.cpp", "cpu_device.cpp")]
     deps = srcs + [os.path.join(CSRC, f) for f in ("blur_launch.h", "kernel_common.h", "cpu_device.h", "filter.h")] + [HEADER]
     if force or not _newer(LIB_PATH, deps):
         cmd = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra",
@@ -212,6 +214,11 @@ class Conv(C.Structure):
         return t(self.k), t(self.k2) if self.mode == CONV_MAG else None
 
 
+class Decimation(C.Structure):
+    """mi_blur_decimation: keep column ox + X*sx and row oy + Y*sy (strides 1..4, phases below them)."""
+    _fields_ = [("sx", C.c_int), ("sy", C.c_int), ("ox", C.c_int), ("oy", C.c_int)]
+
+
 class MiBlurError(RuntimeError):
     def __init__(self, status: int, what: str):
         super().__init__(f"{what}: status {status} ({lib().mi_blur_strerror(status).decode()})")
@@ -300,6 +307,11 @@ def lib() -> C.CDLL:
         "mi_blur_enqueue_bilateral_band": (i, [u8p, u8p, i, i, i, i, i, C.POINTER(Bilateral), vp]),
         "mi_blur_cpu_run_bilateral": (i, [u8p, u8p, i, i, i, i, C.POINTER(Bilateral), i]),
         "mi_blur_ctx_set_bilateral": (i, [vp, C.POINTER(Bilateral)]),
+        "mi_blur_decimated_size": (i, [i, i, C.POINTER(Decimation), C.POINTER(i), C.POINTER(i)]),
+        "mi_blur_sep_down_preset": (i, [i, C.POINTER(SepKernel), C.POINTER(Decimation)]),
+        "mi_blur_enqueue_sep_down": (i, [u8p, u8p, i, i, i, i, C.POINTER(SepKernel), C.POINTER(Decimation), vp]),
+        "mi_blur_cpu_run_sep_down": (i, [u8p, u8p, i, i, i, i, C.POINTER(SepKernel), C.POINTER(Decimation), i]),
+        "mi_blur_ctx_set_sep_down": (i, [vp, C.POINTER(SepKernel), C.POINTER(Decimation)]),
         "mi_blur_conv_preset": (i, [i, C.POINTER(Conv)]),
         "mi_blur_enqueue_conv": (i, [u8p, u8p, i, i, i, i, C.POINTER(Conv), vp]),
         "mi_blur_enqueue_conv_band": (i, [u8p, u8p, i, i, i, i, i, C.POINTER(Conv), vp]),
@@ -442,6 +454,13 @@ class Context:
         """A separable kernel in place of the radius, for every submit (before the first one only)."""
         check(lib().mi_blur_ctx_set_kernel(self.h, C.byref(kernel)), "mi_blur_ctx_set_kernel")
         self.kernel = kernel
+
+    def set_sep_down(self, kernel: "SepKernel", sx: int = 2, sy: int = 2, ox: int = 0, oy: int = 0) -> None:
+        """The decimating separable filter in place of the blur (before the first submit only): submit() then writes
+        images of decimated_size(W, H, sx, sy, ox, oy); the band, planar and resident forms are not supported."""
+        d = Decimation(int(sx), int(sy), int(ox), int(oy))
+        check(lib().mi_blur_ctx_set_sep_down(self.h, C.byref(kernel), C.byref(d)), "mi_blur_ctx_set_sep_down")
+        self.kernel, self.decimation = kernel, d
 
     def submit_bands(self, host_in, host_out, n_images: int, host_image_stride: int, band_rows: int,
                      halo_top: int, halo_bottom: int) -> None:
@@ -695,3 +714,66 @@ def laplacian(images, connectivity: int = 4, device: int = 0, batch: int = 0):
 def sharpen(images, device: int = 0, batch: int = 0):
     """The 3x3 sharpening kernel [0 -1 0; -1 5 -1; 0 -1 0], saturated to 0..255.  Arguments as filter2d()."""
     return _conv("sharpen", images, Conv.preset("sharpen"), device, batch)
+
+
+def decimated_size(w: int, h: int, sx: int = 2, sy: int = 2, ox: int = 0, oy: int = 0) -> tuple[int, int]:
+    """(Wo, Ho) of a w x h image of which column ox + X*sx and row oy + Y*sy are kept (mi_blur_decimated_size)."""
+    d = Decimation(int(sx), int(sy), int(ox), int(oy))
+    wo, ho = C.c_int(), C.c_int()
+    check(lib().mi_blur_decimated_size(int(w), int(h), C.byref(d), C.byref(wo), C.byref(ho)), "mi_blur_decimated_size")
+    return wo.value, ho.value
+
+
+def _down_images(a, kernel: "SepKernel", d: "Decimation", device: int, batch: int):
+    """The numpy driver of sep_down, pyr_down and area_down: _filter_images for a filter whose output is smaller than its
+    input.  a (from _images) through mi_blur_create / mi_blur_ctx_set_sep_down / mi_blur_submit / mi_blur_sync; returns
+    the output with the rank of a and the decimated H and W."""
+    import numpy as np
+    rank = a.ndim
+    if rank == 2:
+        a = a[None, :, :, None]
+    elif rank == 3:
+        a = a[None]
+    n, h, w, c = a.shape
+    if h == 0 or w == 0 or c == 0:
+        raise ValueError("decimating filters: images must not be empty")
+    wo, ho = decimated_size(w, h, d.sx, d.sy, d.ox, d.oy)
+    out = np.empty((n, ho, wo, c), dtype=np.uint8)
+    if n:
+        per = min(n, batch if batch > 0 else 4096)
+        isz, osz = h * w * c, ho * wo * c
+        with Context(device, w, h, c, 1, max_batch=per, n_slots=2) as ctx:
+            ctx.set_sep_down(kernel, d.sx, d.sy, d.ox, d.oy)
+            for i in range(0, n, per):
+                ctx.submit(a.ctypes.data + i * isz, out.ctypes.data + i * osz, min(per, n - i))
+            ctx.sync()
+    return out[0, :, :, 0] if rank == 2 else out[0] if rank == 3 else out
+
+
+def sep_down(images, kernel: "SepKernel", sx: int = 2, sy: int = 2, ox: int = 0, oy: int = 0, device: int = 0, batch: int = 0):
+    """Separable filter and subsampling in one pass, numpy in -> numpy out: the bytes of the separable filter `kernel`
+    (as gaussian_blur applies one) at column ox + X*sx and row oy + Y*sy, of which only those are computed.
+
+    Strides 1..4, phases below them.  images: (H, W), (H, W, C) or (N, H, W, C) uint8; the result has the same rank with
+    the decimated H and W (decimated_size).  device: HIP ordinal, or DEVICE_CPU.  Goes through mi_blur_create /
+    mi_blur_ctx_set_sep_down / mi_blur_submit / mi_blur_sync."""
+    return _down_images(_images(images, "sep_down"), kernel, Decimation(int(sx), int(sy), int(ox), int(oy)), device, batch)
+
+
+def _down_preset(name: str, images, preset: int, device: int, batch: int):
+    k, d = SepKernel(), Decimation()
+    check(lib().mi_blur_sep_down_preset(preset, C.byref(k), C.byref(d)), "mi_blur_sep_down_preset")
+    return _down_images(_images(images, name), k, d, device, batch)
+
+
+def pyr_down(images, device: int = 0, batch: int = 0):
+    """One pyramid level: the 5x5 binomial {1,4,6,4,1} and every second pixel, (H, W) -> ((H + 1) // 2, (W + 1) // 2).
+    OpenCV's pyrDown taps and sampling grid, but edges clamp and the shift truncates.  Arguments as sep_down()."""
+    return _down_preset("pyr_down", images, DOWN_PYR, device, batch)
+
+
+def area_down(images, factor: int = 2, device: int = 0, batch: int = 0):
+    """Area downscale by 2 or 4: the truncated mean of each factor x factor block (edge blocks clamp).  Arguments as sep_down()."""
+    if factor not in (2, 4):
+        raise ValueError("area_down: factor is 2 or 4")
+    return _down_preset("area_down", images, DOWN_AREA2 if factor == 2 else DOWN_AREA4, device, batch)

@@ -1,7 +1,7 @@
 // heterogeneous_blur — Approach 1 (image-level distribution) host, MI355X-native.
 //
 //   heterogeneous_blur {cpu|gpu|both} [gpu_ratio] [batch]  [--image F | --synthetic | --size WxH] [--channels C]
-//                      [--ksize 3|5 | --sigma S [--sigma-y S] [--radius R] | --median K | --erode K | --dilate K | --morph-gradient K | --bilateral K [--sigma-color S] [--sigma-space S] | --conv NAME] [--images N] [--gpus G] [--slots S] [--threads T] [--resident [--fused]]
+//                      [--ksize 3|5 | --sigma S [--sigma-y S] [--radius R] | --median K | --erode K | --dilate K | --morph-gradient K | --bilateral K [--sigma-color S] [--sigma-space S] | --conv NAME | --pyr-down] [--images N] [--gpus G] [--slots S] [--threads T] [--resident [--fused]]
 //                      [--verbose] [--csv FILE] [--save FILE]
 //                      [--frames DIR|PATTERN|FILE [--save-dir DIR] [--planar-out | --native-layout]]   (cpu | gpu)
 //
@@ -111,6 +111,10 @@ int main(int argc, char **argv)
     printf("Original image loaded: %dx%d, %d channels\n", width, height, channels);
     const size_t image_size = (size_t)width * height * channels;
     printf("Size of one image: %zu bytes (%.2f KB)\n", image_size, image_size / 1024.0);
+    // --pyr-down: every output image is the decimated one; out_image_size == image_size under every other filter
+    int out_width = width, out_height = height;
+    if (filter.pyr_down) print_pyr_down(filter, width, height, &out_width, &out_height);
+    const size_t out_image_size = (size_t)out_width * out_height * channels;
     printf("Original image source: %s\n\n", img.source.c_str());
     const uint8_t *original_image = img.px.data();
 
@@ -179,14 +183,14 @@ int main(int argc, char **argv)
             const size_t share = (size_t)share_max;
             for (int s = 0; s < nslots; s++) {
                 gin[g].push_back(batch_alloc(hip_ordinal(g), share * image_size));
-                gout[g].push_back(batch_alloc(hip_ordinal(g), share * image_size));
+                gout[g].push_back(batch_alloc(hip_ordinal(g), share * out_image_size));
                 if (!gin[g].back() || !gout[g].back()) { printf("Error: Failed to allocate batch memory\n"); return -1; }
             }
         }
     } else if (!opt.resident) {
         for (int s = 0; s < nslots; s++) {
             batch_input[s] = batch_alloc(-1, (size_t)BATCH_SIZE * image_size);
-            batch_output[s] = batch_alloc(-1, (size_t)BATCH_SIZE * image_size);
+            batch_output[s] = batch_alloc(-1, (size_t)BATCH_SIZE * out_image_size);
             if (!batch_input[s] || !batch_output[s]) { printf("Error: Failed to allocate batch memory\n"); return -1; }
         }
     } else {
@@ -283,13 +287,13 @@ int main(int argc, char **argv)
                         for (int q = 0; q < pieces_of[s] && feed_rc[g] == MI_BLUR_OK; q++) ok(mi_blur_wait_oldest(ctx));
                         if (feed_rc[g] != MI_BLUR_OK) break;
                         if (g == 0 && opt.save.size() && first_output.empty() && k == nslots)
-                            first_output.assign(gout[0][0], gout[0][0] + image_size);
+                            first_output.assign(gout[0][0], gout[0][0] + out_image_size);
                     }
                     int done = 0, pieces = 0;
                     while (done < n && feed_rc[g] == MI_BLUR_OK) {     // create batch image stream (:439-442) and hand it over, piece by piece
                         const int m = std::min(feed_piece, n - done);
                         rep.run(gin[g][s] + (size_t)done * image_size, original_image, image_size, m, !opt.malloc_buffers);
-                        ok(mi_blur_submit(ctx, gin[g][s] + (size_t)done * image_size, gout[g][s] + (size_t)done * image_size, m));
+                        ok(mi_blur_submit(ctx, gin[g][s] + (size_t)done * image_size, gout[g][s] + (size_t)done * out_image_size, m));
                         done += m; pieces++;
                     }
                     pieces_of[s] = pieces;
@@ -304,7 +308,7 @@ int main(int argc, char **argv)
         for (auto &t : feeders) t.join();
         for (int g = 0; g < G; g++) mi_check(feed_rc[g], "GPU feeder failed");
         total_images_gpu = NUM_IMAGES;
-        if (opt.save.size() && first_output.empty()) first_output.assign(gout[0][0], gout[0][0] + image_size);
+        if (opt.save.size() && first_output.empty()) first_output.assign(gout[0][0], gout[0][0] + out_image_size);
     } else if (opt.resident) {
         // one host thread per GPU: a stream of batch-35 launches is issue-rate-bound, so one thread feeding
         // G GPUs in turn would serialise them
@@ -380,7 +384,7 @@ int main(int argc, char **argv)
                     last_harvest_ms = now_ms;
                 }
                 if (opt.save.size() && first_output.empty() && batch - nslots == 0)
-                    first_output.assign(batch_output[s], batch_output[s] + image_size);
+                    first_output.assign(batch_output[s], batch_output[s] + out_image_size);
             }
             // create batch image stream (contiguous) — heterogeneous_blur.c:439-442
             replicate.run(batch_input[s], original_image, image_size, batch_count, mode == 2 && !opt.malloc_buffers);
@@ -400,8 +404,8 @@ int main(int argc, char **argv)
                 long long b, e;
                 mi_blur_shard_range(num_images_gpu, g, G, &b, &e);
                 if (e <= b) continue;
-                const size_t off = (size_t)(num_images_cpu + b) * image_size;
-                mi_check(mi_blur_submit(gpus[g].ctx, batch_input[s] + off, batch_output[s] + off, (int)(e - b)), "GPU submit failed");
+                const size_t off = (size_t)(num_images_cpu + b) * image_size, out_off = (size_t)(num_images_cpu + b) * out_image_size;
+                mi_check(mi_blur_submit(gpus[g].ctx, batch_input[s] + off, batch_output[s] + out_off, (int)(e - b)), "GPU submit failed");
                 gpus[g].submitted[batch] = 1;
             }
             if (opt.verbose) printf("  Batch %d submitted.\n\n", batch + 1);
@@ -423,14 +427,14 @@ int main(int argc, char **argv)
         // clFinish on every queue (heterogeneous_blur.c:538-539)
         if (cpu.ctx) mi_check(mi_blur_sync(cpu.ctx, &cpu.tm), "CPU sync failed");
         for (auto &d : gpus) mi_check(mi_blur_sync(d.ctx, &d.tm), "GPU sync failed");
-        if (opt.save.size() && first_output.empty()) first_output.assign(batch_output[0], batch_output[0] + image_size);
+        if (opt.save.size() && first_output.empty()) first_output.assign(batch_output[0], batch_output[0] + out_image_size);
     }
     const double time_end_total = get_time_ms();
     const double time_total_processing = time_end_total - time_start_total;
     printf("All batches finished!\n\n");
     if (opt.auto_ratio && mode == 0) printf("Auto ratio after %d per-batch updates: %.1f%% GPU\n\n", rebalances, gpu_ratio * 100);
     if (opt.save.size() && !first_output.empty()) {
-        save_one_image(opt.save.c_str(), first_output.data(), width, height, channels);
+        save_one_image(opt.save.c_str(), first_output.data(), out_width, out_height, channels);
         printf("Saved example output: %s\n\n", opt.save.c_str());
     }
 

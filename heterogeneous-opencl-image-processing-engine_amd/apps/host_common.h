@@ -172,6 +172,8 @@ struct Options {
     bool sigma_color_given = false, sigma_space_given = false;
     std::string conv;                    // --conv NAME (sobel-x | sobel-y | sobel | scharr-x | scharr-y | scharr | laplacian | laplacian8 | sharpen |
     int conv_preset = -1;                //              emboss): that 3x3 convolution instead of --ksize; mi_blur_ctx_set_conv on every context
+    bool pyr_down = false;               // --pyr-down: one pyramid level (MI_BLUR_DOWN_PYR) instead of --ksize: mi_blur_ctx_set_sep_down on every
+                                         //              context, outputs of the decimated size (heterogeneous_blur only: no bands)
     int images = 5000;                   // --images N   (NUM_IMAGES, heterogeneous_blur.c:44)
     bool images_given = false;
     int gpus = 1;                        // --gpus G
@@ -242,6 +244,7 @@ inline int parse_flags(int argc, char **argv, Options &o)
             for (int q = 0; q < 10; q++) if (o.conv == names[q]) o.conv_preset = q;      // the order of mi_blur_conv_preset_id
             if (o.conv_preset < 0) { printf("Error: --conv sobel-x|sobel-y|sobel|scharr-x|scharr-y|scharr|laplacian|laplacian8|sharpen|emboss\n"); exit(-1); }
         }
+        else if (a == "--pyr-down") o.pyr_down = true;
         else if (a == "--sigma-color") { o.sigma_color = atof(next("--sigma-color")); o.sigma_color_given = true; if (!(o.sigma_color > 0.0)) { printf("Error: --sigma-color must be > 0\n"); exit(-1); } }
         else if (a == "--sigma-space") { o.sigma_space = atof(next("--sigma-space")); o.sigma_space_given = true; if (!(o.sigma_space >= 0.0)) { printf("Error: --sigma-space must be >= 0\n"); exit(-1); } }
         else if (a == "--sigma") { o.sigma = atof(next("--sigma")); if (!(o.sigma > 0.0)) { printf("Error: --sigma must be > 0\n"); exit(-1); } }
@@ -281,6 +284,8 @@ inline int parse_flags(int argc, char **argv, Options &o)
     if (!o.bilateral && (o.sigma_color_given || o.sigma_space_given)) { printf("Error: --sigma-color and --sigma-space need --bilateral\n"); exit(-1); }
     if (o.conv_preset >= 0 && (o.ksize_given || o.sigma > 0.0 || o.median || o.morph || o.bilateral)) { printf("Error: --conv excludes --ksize, --sigma, --median, --erode, --dilate, --morph-gradient and --bilateral\n"); exit(-1); }
     if (o.conv_preset >= 0 && o.resident) { printf("Error: --conv does not run --resident\n"); exit(-1); }
+    if (o.pyr_down && (o.ksize_given || o.sigma > 0.0 || o.median || o.morph || o.bilateral || o.conv_preset >= 0)) { printf("Error: --pyr-down excludes --ksize, --sigma, --median, --erode, --dilate, --morph-gradient, --bilateral and --conv\n"); exit(-1); }
+    if (o.pyr_down && (o.resident || !o.frames.empty())) { printf("Error: --pyr-down excludes --resident and --frames\n"); exit(-1); }
     return npos;
 }
 
@@ -299,6 +304,9 @@ struct HostFilter {
     int conv_preset;            // --conv NAME: the 3x3 convolution `conv` (mi_blur_conv_preset) called `conv_name`; -1 = none
     std::string conv_name;
     mi_blur_conv conv;
+    bool pyr_down = false;      // --pyr-down: the decimating filter `down_k`, `down_d` (mi_blur_sep_down_preset, MI_BLUR_DOWN_PYR)
+    mi_blur_sep_kernel down_k{};
+    mi_blur_decimation down_d{};
 };
 
 inline HostFilter filter_of(const Options &o)
@@ -316,6 +324,11 @@ inline HostFilter filter_of(const Options &o)
         printf("Error: no convolution kernel %s\n", f.conv_name.c_str());
         exit(-1);
     }
+    f.pyr_down = o.pyr_down;
+    if (f.pyr_down && mi_blur_sep_down_preset(MI_BLUR_DOWN_PYR, &f.down_k, &f.down_d) != MI_BLUR_OK) {
+        printf("Error: no pyramid kernel\n");
+        exit(-1);
+    }
     return f;
 }
 
@@ -327,6 +340,15 @@ inline void set_filter(mi_blur_ctx *ctx, const HostFilter &f)
     if (f.morph) mi_check(mi_blur_ctx_set_morph(ctx, f.morph_op, f.morph / 2, f.morph / 2), "Failed to set the morphology filter");
     if (f.bilateral) mi_check(mi_blur_ctx_set_bilateral(ctx, &f.bil), "Failed to set the bilateral filter");
     if (f.conv_preset >= 0) mi_check(mi_blur_ctx_set_conv(ctx, &f.conv), "Failed to set the convolution");
+    if (f.pyr_down) mi_check(mi_blur_ctx_set_sep_down(ctx, &f.down_k, &f.down_d), "Failed to set the pyramid filter");
+}
+
+// The banner's "Blur kernel" line of --pyr-down, which needs the image size (print_filter() comes before the image is
+// loaded and prints nothing for it); *wo, *ho: the size of every output image.
+inline void print_pyr_down(const HostFilter &f, int width, int height, int *wo, int *ho)
+{
+    mi_check(mi_blur_decimated_size(width, height, &f.down_d, wo, ho), "Image too small for --pyr-down");
+    printf("Blur kernel: %dx%d pyramid down, %dx%d -> %dx%d\n", 2 * f.down_k.rx + 1, 2 * f.down_k.ry + 1, width, height, *wo, *ho);
 }
 
 // Rows a band needs on each side: the convolution's vertical radius, the median's, the morphology window's or the bilateral window's radius, the Gaussian's vertical radius (at least one row, so that the
@@ -336,6 +358,7 @@ inline int filter_halo(const HostFilter &f) { return f.conv_preset >= 0 ? f.conv
 // The banner's "Blur kernel" line (with the taps of a Gaussian).
 inline void print_filter(const HostFilter &f)
 {
+    if (f.pyr_down) return;     // print_pyr_down(), once the image size is known
     if (f.median) { printf("Blur kernel: %dx%d median\n", f.median, f.median); return; }
     if (f.conv_preset >= 0) { printf("Blur kernel: %dx%d convolution (%s)\n", 2 * f.conv.rx + 1, 2 * f.conv.ry + 1, f.conv_name.c_str()); return; }
     if (f.bilateral) { printf("Blur kernel: %dx%d bilateral (sigma_color %g, sigma_space %g)\n", f.bilateral, f.bilateral, f.sigma_color, f.sigma_space); return; }

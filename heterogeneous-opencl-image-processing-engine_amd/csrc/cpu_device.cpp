@@ -340,15 +340,60 @@ void cpu_conv_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, const F
     }
 }
 
+// Output rows [Y_begin, Y_end) of the decimating separable filter of f (f.taps, f.down_*) on one W x H image: the two
+// passes of cpu_blur_rows_sep at runtime taps, the vertical one on the kept rows only, the horizontal one at the kept
+// columns only.  out = the decimated image (dense).
+void cpu_sep_down_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, const Filter &f, int Y_begin, int Y_end)
+{
+    const SepTaps &k = f.taps;
+    const int pitch = W * C, pad = k.rx * C, nj = 2 * k.ry + 1, ni = 2 * k.rx + 1;
+    const int sx = f.down_sx, sy = f.down_sy, ox = f.down_ox, oy = f.down_oy;
+    const int Wo = down_cols(W, sx, ox), opitch = Wo * C;
+    std::vector<uint16_t> scratch((size_t)pitch + 2 * pad);
+    uint16_t *v = scratch.data() + pad;               // v[-pad .. pitch+pad)
+    uint16_t wy[2 * SEP_MAX_R + 1], wx[2 * SEP_MAX_R + 1];
+    for (int j = 0; j < nj; j++) wy[j] = (uint16_t)k.wy[SEP_MAX_R - k.ry + j];
+    for (int i = 0; i < ni; i++) wx[i] = (uint16_t)k.wx[SEP_MAX_R - k.rx + i];
+    for (int Y = Y_begin; Y < Y_end; Y++) {
+        const int y = oy + Y * sy;
+        {
+            const uint8_t *a = in + (size_t)std::min(std::max(y - k.ry, 0), H - 1) * pitch;
+            const uint16_t w0 = wy[0];
+            for (int b = 0; b < pitch; b++) v[b] = (uint16_t)(w0 * a[b]);
+        }
+        for (int j = 1; j < nj; j++) {
+            const uint8_t *a = in + (size_t)std::min(std::max(y + j - k.ry, 0), H - 1) * pitch;
+            const uint16_t w = wy[j];
+            if (w) for (int b = 0; b < pitch; b++) v[b] = (uint16_t)(v[b] + w * a[b]);
+        }
+        for (int q = 1; q <= pad; q++) {
+            v[-q] = v[((-q % C) + C) % C];
+            v[pitch + q - 1] = v[pitch - C + ((q - 1) % C)];
+        }
+        uint8_t *o = out + (size_t)Y * opitch;
+        for (int X = 0; X < Wo; X++) {
+            const uint16_t *a = v + (ox + X * sx - k.rx) * C;
+            for (int c = 0; c < C; c++) {
+                uint32_t s = 0;
+                for (int i = 0; i < ni; i++) s += (uint32_t)wx[i] * a[i * C + c];
+                o[X * C + c] = (uint8_t)(s >> k.shift);
+            }
+        }
+    }
+}
+
 // n_images bands of band_rows rows; output rows [y0,y1) of each.  Threads take whole
-// images when there are enough of them, else row slices of each image.
+// images when there are enough of them, else row slices of each image.  A SEP_DOWN filter: whole images only (y0 = 0,
+// y1 = band_rows); the output blocks are the decimated images and the row slices are cut in output rows.
 void cpu_blur_batch(const uint8_t *in, uint8_t *out, int W, int band_rows, int C, const Filter &f, int n_images,
                     int y0, int y1, int n_threads, size_t in_stride, size_t out_stride)
 {
     if (n_images <= 0) return;
     if (n_threads <= 0) n_threads = hardware_threads();
     if (in_stride == 0) in_stride = (size_t)W * C * band_rows;
-    if (out_stride == 0) out_stride = (size_t)W * C * (y1 - y0);
+    const bool down = f.kind == FilterKind::SEP_DOWN;
+    if (down) { y0 = 0; y1 = down_rows(band_rows, f.down_sy, f.down_oy); }   // from here on: output rows
+    if (out_stride == 0) out_stride = (size_t)(down ? down_cols(W, f.down_sx, f.down_ox) : W) * C * (y1 - y0);
     const int rows = y1 - y0;
     // work items: (image, row slice)
     // enough items for the threads to end together: a batch of 35 images on 16 threads is three rounds of whole images with the
@@ -367,7 +412,8 @@ void cpu_blur_batch(const uint8_t *in, uint8_t *out, int W, int band_rows, int C
             const int ys = y0 + (int)((long long)rows * s / slices), ye = y0 + (int)((long long)rows * (s + 1) / slices);
             const uint8_t *src = in + img * in_stride;
             uint8_t *dst = out + img * out_stride;
-            if (f.kind == FilterKind::CONV) cpu_conv_rows(src, dst, W, band_rows, C, f, ys, ye, y0);
+            if (down) cpu_sep_down_rows(src, dst, W, band_rows, C, f, ys, ye);
+            else if (f.kind == FilterKind::CONV) cpu_conv_rows(src, dst, W, band_rows, C, f, ys, ye, y0);
             else if (f.kind == FilterKind::BILATERAL) cpu_bilateral_rows(src, dst, W, band_rows, C, f, ys, ye, y0);
             else if (f.kind == FilterKind::MORPH) cpu_morph_rows(src, dst, W, band_rows, C, f.morph_op, f.morph_rx, f.morph_ry, ys, ye, y0);
             else if (f.kind == FilterKind::MEDIAN) cpu_median_rows(src, dst, W, band_rows, C, f.radius, ys, ye, y0);

@@ -24,6 +24,8 @@ void cpu_conv_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, const F
                    int out_row_shift);
 void cpu_bilateral_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, const Filter &f, int y_begin, int y_end,
                         int out_row_shift);
+// Output rows [Y_begin, Y_end) of the decimating separable filter of f (f.taps, f.down_*): kept rows and columns only.
+void cpu_sep_down_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, const Filter &f, int Y_begin, int Y_end);
 void cpu_blur_batch(const uint8_t *in, uint8_t *out, int W, int band_rows, int C, const Filter &f, int n_images,
                     int y0, int y1, int n_threads, size_t in_stride = 0, size_t out_stride = 0);
 // The box blur of radius R (1|2): the form the host-only sanitizer harness (tests/san_cpu_device.cpp) drives.

@@ -1,5 +1,5 @@
 // filter.h — internal: the one filter a launch, a context or a CPU run applies, in the form the GPU kernels
-// (blur_kernels.hip, sep_kernels.hip, median_kernels.hip, morph_kernels.hip, bilateral_kernels.hip, conv_kernels.hip) and the CPU device (cpu_device.cpp) take it.  Plain C++, no HIP.
+// (blur_kernels.hip, sep_kernels.hip, median_kernels.hip, morph_kernels.hip, bilateral_kernels.hip, conv_kernels.hip, sep_down_kernels.hip) and the CPU device (cpu_device.cpp) take it.  Plain C++, no HIP.
 #pragma once
 
 #include "../../include/mi_blur.h"
@@ -15,7 +15,7 @@ struct SepTaps {
     unsigned wx[2 * SEP_MAX_R + 1], wy[2 * SEP_MAX_R + 1];
 };
 
-enum class FilterKind { BOX, SEP, MEDIAN, MORPH, BILATERAL, CONV };
+enum class FilterKind { BOX, SEP, MEDIAN, MORPH, BILATERAL, CONV, SEP_DOWN };
 
 // BOX: the fixed 3x3 / 5x5 kernel of `radius` 1|2.  SEP: the separable kernel `taps`.  MEDIAN: the median of `radius` 1..7.
 // MORPH: the window minimum / maximum / their difference (`morph_op`) over (2 morph_rx + 1) x (2 morph_ry + 1).
@@ -23,6 +23,8 @@ enum class FilterKind { BOX, SEP, MEDIAN, MORPH, BILATERAL, CONV };
 // bil_s[(j + 8) * 17 + (i + 8)] = S[j][i], 0 beyond the radius) and the range table `bil_range`.
 // CONV: the signed 2-D convolution (mi_blur_conv) of radii `conv_rx`, `conv_ry` with the taps CENTRED in the 15 x 15 frame:
 // conv_k[t][(j + 7) * 15 + (i + 7)] = K[j][i] (t = 0) or K2[j][i] (t = 1, MAG only; zeros otherwise), 0 beyond the radii.
+// SEP_DOWN: the separable kernel `taps` on the whole image, of whose result only column down_ox + X * down_sx and row
+// down_oy + Y * down_sy are kept (mi_blur_decimation): the one kind whose output is smaller than its input.
 struct Filter {
     FilterKind kind;
     int radius;             // BOX and MEDIAN
@@ -33,7 +35,18 @@ struct Filter {
     int conv_rx = 0, conv_ry = 0, conv_mode = 0, conv_shift = 0;   // CONV (radii 0..7, mi_blur_conv_mode, shift 0..16)
     int32_t conv_bias = 0;
     int16_t conv_k[2][15 * 15] = {};
+    int down_sx = 1, down_sy = 1, down_ox = 0, down_oy = 0;   // SEP_DOWN (strides 1..4, phases below them); last, so the initialisers above stay
 };
+
+// Output size of a decimation of a W x H image: kept columns / rows (> 0 for a valid decimation, down_ok()).
+inline int down_cols(int W, int sx, int ox) { return (W - ox + sx - 1) / sx; }
+inline int down_rows(int H, int sy, int oy) { return (H - oy + sy - 1) / sy; }
+// A decimation that is valid for a W x H image: strides 1..4, phases below them and inside the image.
+inline bool down_ok(const mi_blur_decimation *d, int W, int H)
+{
+    return d && d->sx >= 1 && d->sx <= MI_BLUR_DECIMATE_MAX && d->sy >= 1 && d->sy <= MI_BLUR_DECIMATE_MAX && d->ox >= 0 &&
+           d->ox < d->sx && d->oy >= 0 && d->oy < d->sy && d->ox < W && d->oy < H;
+}
 
 // The constructors validate: MI_BLUR_OK, or MI_BLUR_ERR_INVALID with *f untouched.
 inline int filter_box(int radius, Filter *f)
@@ -55,6 +68,18 @@ inline int filter_sep(const mi_blur_sep_kernel *k, Filter *f)
     if (sx != (1LL << k->bx) || sy != (1LL << k->by)) return MI_BLUR_ERR_INVALID;
     t.rx = k->rx; t.ry = k->ry; t.shift = k->bx + k->by;
     *f = Filter{FilterKind::SEP, 0, t};
+    return MI_BLUR_OK;
+}
+
+// The taps as filter_sep; the strides and phases of *d (the image size is checked where it is known: down_ok()).
+inline int filter_sep_down(const mi_blur_sep_kernel *k, const mi_blur_decimation *d, Filter *f)
+{
+    if (!d || !f || !down_ok(d, MI_BLUR_DECIMATE_MAX, MI_BLUR_DECIMATE_MAX)) return MI_BLUR_ERR_INVALID;
+    Filter g;
+    if (const int rc = filter_sep(k, &g)) return rc;
+    g.kind = FilterKind::SEP_DOWN;
+    g.down_sx = d->sx; g.down_sy = d->sy; g.down_ox = d->ox; g.down_oy = d->oy;
+    *f = g;
     return MI_BLUR_OK;
 }
 

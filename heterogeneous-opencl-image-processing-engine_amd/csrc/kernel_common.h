@@ -1,5 +1,5 @@
-// kernel_common.h — internal (not part of the C ABI): what the seven kernel files (blur_kernels.hip, sep_kernels.hip,
-// median_kernels.hip, morph_kernels.hip, bilateral_kernels.hip, conv_kernels.hip, layout_kernels.hip) share below launch(): the launch call, the blockIdx -> tile maps, the template
+// kernel_common.h — internal (not part of the C ABI): what the eight kernel files (blur_kernels.hip, sep_kernels.hip,
+// median_kernels.hip, morph_kernels.hip, bilateral_kernels.hip, conv_kernels.hip, sep_down_kernels.hip, layout_kernels.hip) share below launch(): the launch call, the blockIdx -> tile maps, the template
 // dispatch, the argument checks and parameter fill every family repeats, the host side of the direct layout, and the
 // LDS tile of the sep, morph, bilateral and conv kernels (its coordinates, its staging, its launch geometry).
 // Everything here has internal linkage, so libmi_blur.so exports nothing from it.
@@ -49,8 +49,8 @@ __device__ __forceinline__ uint32_t pk32(u16x2 x) { return __builtin_bit_cast(ui
 template <int N>
 __device__ __forceinline__ uint32_t window_byte(const uint32_t (&W)[N], int idx) { return (W[idx >> 2] >> (8 * (idx & 3))) & 0xffu; }
 
-// The LDS tile blur_sep_tiled_kernel, blur_morph_tiled_kernel, blur_bilateral_tiled_kernel and blur_conv_tiled_kernel
-// work on: rows of whole 16-byte chunks, one workgroup of TILE_THREADS = one tile of TILE_TH output rows x ncols
+// The LDS tile blur_sep_tiled_kernel, blur_morph_tiled_kernel, blur_bilateral_tiled_kernel, blur_conv_tiled_kernel and
+// (in input coordinates) blur_sep_down_tiled_kernel work on: rows of whole 16-byte chunks, one workgroup of TILE_THREADS = one tile of TILE_TH output rows x ncols
 // (<= TILE_NCOLS) chunk columns, staged with ry rows above and below and HC halo chunks either side.  The helpers take
 // the kernel arguments they need as scalars: handed the parameter struct by reference the kernels grow by a third.
 constexpr int TILE_TH = 32;         // output rows per tile

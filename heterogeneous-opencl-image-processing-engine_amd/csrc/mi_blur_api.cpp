@@ -199,6 +199,43 @@ extern "C" int mi_blur_enqueue_sep(const uint8_t *d_in, uint8_t *d_out, int widt
 }
 
 // ----------------------------------------------------------------------------------
+// decimating separable filter: only the kept rows and columns are computed (no reference analogue)
+// ----------------------------------------------------------------------------------
+extern "C" int mi_blur_decimated_size(int width, int height, const mi_blur_decimation *d, int *out_width, int *out_height)
+{
+    if (!out_width || !out_height || width <= 0 || height <= 0 || !down_ok(d, width, height)) return MI_BLUR_ERR_INVALID;
+    *out_width = down_cols(width, d->sx, d->ox);
+    *out_height = down_rows(height, d->sy, d->oy);
+    return MI_BLUR_OK;
+}
+
+extern "C" int mi_blur_sep_down_preset(int preset, mi_blur_sep_kernel *k, mi_blur_decimation *d)
+{
+    if (!k || !d || preset < MI_BLUR_DOWN_PYR || preset > MI_BLUR_DOWN_AREA4) return MI_BLUR_ERR_INVALID;
+    static const uint16_t PYR[5] = {1, 4, 6, 4, 1}, AREA2[3] = {0, 1, 1}, AREA4[7] = {0, 0, 0, 1, 1, 1, 1};
+    const uint16_t *taps = preset == MI_BLUR_DOWN_PYR ? PYR : preset == MI_BLUR_DOWN_AREA2 ? AREA2 : AREA4;
+    const int r = preset == MI_BLUR_DOWN_PYR ? 2 : preset == MI_BLUR_DOWN_AREA2 ? 1 : 3;
+    const int bits = preset == MI_BLUR_DOWN_PYR ? 4 : preset == MI_BLUR_DOWN_AREA2 ? 1 : 2;
+    const int stride = preset == MI_BLUR_DOWN_AREA4 ? 4 : 2;
+    mi_blur_sep_kernel g{};
+    g.rx = g.ry = r; g.bx = g.by = bits;
+    for (int i = 0; i <= 2 * r; i++) g.wx[i] = g.wy[i] = taps[i];
+    *k = g;
+    *d = mi_blur_decimation{stride, stride, 0, 0};
+    return MI_BLUR_OK;
+}
+
+extern "C" int mi_blur_enqueue_sep_down(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int n_images,
+                                        const mi_blur_sep_kernel *k, const mi_blur_decimation *d, void *stream)
+{
+    Filter f;
+    if (filter_sep_down(k, d, &f) || !d_in || !d_out || d_in == d_out || width <= 0 || height <= 0 || channels <= 0 || n_images < 0 ||
+        !down_ok(d, width, height) || (long long)width * channels * height > INT_MAX)
+        return MI_BLUR_ERR_INVALID;
+    return enqueue_filter(f, d_in, d_out, width, height, channels, n_images, 0, height, MI_BLUR_VARIANT_AUTO, stream);
+}
+
+// ----------------------------------------------------------------------------------
 // median blur, radius 1..7 (no reference analogue)
 // ----------------------------------------------------------------------------------
 extern "C" int mi_blur_enqueue_median_band(const uint8_t *d_in, uint8_t *d_out, int width, int band_rows, int channels,
@@ -448,7 +485,7 @@ struct CpuWorker {
 
 struct mi_blur_ctx {
     int device = 0, W = 0, H = 0, C = 0, max_batch = 0, n_threads = 0;
-    Filter filter{};                                             // every submit applies it: mi_blur_create's radius, or set_kernel / set_median / set_morph / set_bilateral / set_conv
+    Filter filter{};                                             // every submit applies it: mi_blur_create's radius, or set_kernel / set_median / set_morph / set_bilateral / set_conv / set_sep_down
     size_t image_bytes = 0;
     std::vector<Slot> slots;
     int next_slot = 0;
@@ -495,7 +532,7 @@ struct mi_blur_ctx {
     // CPU device
     std::vector<CpuJob *> cpu_jobs;
     CpuWorker *cpu_worker = nullptr;
-    bool submitted = false;                                      // set_kernel / set_median / set_morph / set_bilateral / set_conv only before this
+    bool submitted = false;                                      // set_kernel / set_median / set_morph / set_bilateral / set_conv / set_sep_down only before this
     bool is_cpu() const { return device == MI_BLUR_DEVICE_CPU; }
 };
 
@@ -981,7 +1018,8 @@ static LaunchDesc ctx_launch(const mi_blur_ctx *c, const uint8_t *in, uint8_t *o
 static void count_submit(mi_blur_ctx *c, int n_images, size_t out_bytes, size_t h2d, size_t d2h, bool zero_copy)
 {
     c->tm.bytes_h2d += h2d; c->tm.bytes_d2h += d2h;
-    c->tm.bytes_alg += 2ull * out_bytes;
+    // the decimating filter reads whole images and writes smaller ones: input + output; every other filter 2 * output
+    c->tm.bytes_alg += c->filter.kind == FilterKind::SEP_DOWN ? (uint64_t)c->image_bytes * (uint64_t)n_images + out_bytes : 2ull * out_bytes;
     c->tm.images += (uint64_t)n_images;
     c->tm.launches += 1;
     if (zero_copy) c->zero_copy_launches += 1;
@@ -1123,7 +1161,10 @@ static int submit_common(mi_blur_ctx *c, const uint8_t *host_in, uint8_t *host_o
                          int y0, int y1, size_t in_stride, size_t out_stride)
 {
     const size_t pitch = (size_t)c->W * c->C;
-    const size_t band_in = pitch * band_rows, band_out = pitch * (size_t)(y1 - y0);
+    const size_t band_in = pitch * band_rows;
+    const size_t band_out = c->filter.kind == FilterKind::SEP_DOWN      // whole images only: the decimated image
+                                ? (size_t)down_cols(c->W, c->filter.down_sx, c->filter.down_ox) * c->C * (size_t)down_rows(c->H, c->filter.down_sy, c->filter.down_oy)
+                                : pitch * (size_t)(y1 - y0);
     const HostBatch b{host_in, host_out, band_rows, n_images, y0, y1, band_in, band_out,
                       in_stride ? in_stride : band_in, out_stride ? out_stride : band_out};
     c->submitted = true;
@@ -1180,6 +1221,7 @@ extern "C" int mi_blur_submit_band(mi_blur_ctx *c, const uint8_t *host_in, uint8
                                    int halo_top, int halo_bottom)
 {
     if (!c || !host_in || !host_out || host_in == host_out) return MI_BLUR_ERR_INVALID;
+    if (c->filter.kind == FilterKind::SEP_DOWN) return MI_BLUR_ERR_UNSUPPORTED;   // no band forms: a band's phase depends on where it starts
     if (band_rows <= 0 || band_rows > c->H || halo_top < 0 || halo_bottom < 0) return MI_BLUR_ERR_INVALID;
     if (halo_top + halo_bottom >= band_rows) return MI_BLUR_ERR_INVALID;
     return submit_common(c, host_in, host_out, band_rows, 1, halo_top, band_rows - halo_bottom, 0, 0);
@@ -1189,6 +1231,7 @@ extern "C" int mi_blur_submit_bands(mi_blur_ctx *c, const uint8_t *host_in, uint
                                     size_t host_image_stride, int band_rows, int halo_top, int halo_bottom)
 {
     if (!c || !host_in || !host_out || host_in == host_out) return MI_BLUR_ERR_INVALID;
+    if (c->filter.kind == FilterKind::SEP_DOWN) return MI_BLUR_ERR_UNSUPPORTED;
     if (n_images < 0 || n_images > c->max_batch) return MI_BLUR_ERR_INVALID;
     if (band_rows <= 0 || band_rows > c->H || halo_top < 0 || halo_bottom < 0) return MI_BLUR_ERR_INVALID;
     if (halo_top + halo_bottom >= band_rows) return MI_BLUR_ERR_INVALID;
@@ -1208,6 +1251,7 @@ extern "C" int mi_blur_submit_bands(mi_blur_ctx *c, const uint8_t *host_in, uint
 extern "C" int mi_blur_submit_planar(mi_blur_ctx *c, const uint8_t *host_planar_in, uint8_t *host_out, int n_images, int planar_out)
 {
     if (!c || !host_planar_in || !host_out || host_planar_in == host_out) return MI_BLUR_ERR_INVALID;
+    if (c->filter.kind == FilterKind::SEP_DOWN) return MI_BLUR_ERR_UNSUPPORTED;
     if (n_images < 0 || n_images > c->max_batch) return MI_BLUR_ERR_INVALID;
     if (n_images == 0) return MI_BLUR_OK;
     const size_t bytes = c->image_bytes * (size_t)n_images;
@@ -1280,6 +1324,17 @@ extern "C" int mi_blur_ctx_set_kernel(mi_blur_ctx *c, const mi_blur_sep_kernel *
     Filter f;
     const int rc = filter_sep(k, &f);
     if (rc) return rc;
+    c->filter = f;
+    return MI_BLUR_OK;
+}
+
+// The decimating separable filter in place of the context's blur, for mi_blur_submit from now on (before the first one only).
+extern "C" int mi_blur_ctx_set_sep_down(mi_blur_ctx *c, const mi_blur_sep_kernel *k, const mi_blur_decimation *d)
+{
+    if (!c || !k || !d) return MI_BLUR_ERR_INVALID;
+    if (c->submitted) return MI_BLUR_ERR_STATE;
+    Filter f;
+    if (filter_sep_down(k, d, &f) || !down_ok(d, c->W, c->H)) return MI_BLUR_ERR_INVALID;
     c->filter = f;
     return MI_BLUR_OK;
 }
@@ -1753,6 +1808,14 @@ extern "C" int mi_blur_cpu_run_sep(const uint8_t *in, uint8_t *out, int width, i
 {
     Filter f;
     return filter_sep(k, &f) ? MI_BLUR_ERR_INVALID : cpu_run_filter(f, in, out, width, height, channels, n_images, n_threads);
+}
+
+extern "C" int mi_blur_cpu_run_sep_down(const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,
+                                        const mi_blur_sep_kernel *k, const mi_blur_decimation *d, int n_threads)
+{
+    Filter f;
+    if (filter_sep_down(k, d, &f) || !down_ok(d, width, height)) return MI_BLUR_ERR_INVALID;
+    return cpu_run_filter(f, in, out, width, height, channels, n_images, n_threads);   // cpu_blur_batch takes the output size from f
 }
 
 extern "C" int mi_blur_cpu_run_median(const uint8_t *in, uint8_t *out, int width, int height, int channels, int radius,

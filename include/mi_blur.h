@@ -68,7 +68,7 @@ int mi_blur_version(void);
  * "blur_fused_kernel", "blur_tiled_loop_kernel", "blur_stream_kernel", "blur_generic_kernel", "blur_sep_tiled_kernel",
  * "blur_sep_generic_kernel", "blur_median_fast_kernel", "blur_median_generic_kernel", "blur_morph_tiled_kernel",
  * "blur_morph_generic_kernel", "blur_bilateral_tiled_kernel", "blur_bilateral_generic_kernel", "blur_conv_tiled_kernel",
- * "blur_conv_generic_kernel"; "" before the first):
+ * "blur_conv_generic_kernel", "blur_sep_down_tiled_kernel", "blur_sep_down_generic_kernel"; "" before the first):
  * reports name the kernel a profiler will show.  Static string, never NULL. */
 const char *mi_blur_last_kernel(void);
 
@@ -185,7 +185,8 @@ typedef struct mi_blur_timing {      /* cumulative since create / last reset; mi
                                         least one of them was executing, not the sum of their durations */
     double d2h_ms;                   /* transfer OUT (time_*_transfer_out) */
     uint64_t bytes_h2d, bytes_d2h;
-    uint64_t bytes_alg;              /* algorithmic bytes = 2*W*rows*C per image processed */
+    uint64_t bytes_alg;              /* algorithmic bytes = 2*W*rows*C per image processed; for a context with
+                                        mi_blur_ctx_set_sep_down: input bytes + output bytes, W*H*C + Wo*Ho*C per image */
     uint64_t images;
     uint64_t launches;
 } mi_blur_timing;
@@ -401,6 +402,55 @@ int mi_blur_cpu_run_sep(const uint8_t *in, uint8_t *out, int width, int height, 
  * memory; GPU or CPU device); such submits never go through the batch server (one launch per submit instead), and
  * the resident runs (mi_blur_resident_run, _run_fused) return MI_BLUR_ERR_UNSUPPORTED.  The context keeps a copy. */
 int mi_blur_ctx_set_kernel(mi_blur_ctx *ctx, const mi_blur_sep_kernel *k);
+
+/* ------------------------------------------------------------------------
+ * Decimating separable filter: low-pass and subsample in one pass (pyramid level, area downscale; no reference
+ * analogue).  Let F be the separable filter of mi_blur_enqueue_sep for the taps k on the whole W x H image (clamp-to-edge,
+ * exact integers, one truncating shift).  A decimation keeps column ox + X*sx and row oy + Y*sy of it:
+ *   Wo = (W - ox + sx - 1) / sx        Ho = (H - oy + sy - 1) / sy
+ *   out[Y][X][c] = F(in)[oy + Y*sy][ox + X*sx][c]        0 <= X < Wo, 0 <= Y < Ho
+ * The output is interleaved and dense: its pitch is Wo*C and images lie Wo*Ho*C bytes apart.  It is byte-identical to
+ * "filter, then subsample", and the GPU and the CPU device agree byte for byte; only the kept outputs are computed.
+ * Valid: 1 <= sx, sy <= MI_BLUR_DECIMATE_MAX, 0 <= ox < sx, 0 <= oy < sy, ox < W and oy < H (the output is never empty);
+ * k has the rules of mi_blur_sep_kernel.  sx = sy = 1 gives exactly the bytes of mi_blur_enqueue_sep.
+ * This is NOT OpenCV's pyrDown bit for bit: edges clamp here instead of reflecting, and the shift truncates instead of
+ * rounding.  The taps and the sampling grid of MI_BLUR_DOWN_PYR are pyrDown's.
+ * ---------------------------------------------------------------------- */
+#define MI_BLUR_DECIMATE_MAX 4
+typedef struct mi_blur_decimation { int sx, sy, ox, oy; } mi_blur_decimation;   /* keep column ox + X*sx, row oy + Y*sy */
+
+/* Wo and Ho of a width x height image under *d.  MI_BLUR_ERR_INVALID: a null pointer, width or height <= 0, or a
+ * decimation that is not valid for that size. */
+int mi_blur_decimated_size(int width, int height, const mi_blur_decimation *d, int *out_width, int *out_height);
+
+typedef enum mi_blur_down_preset_id {
+    MI_BLUR_DOWN_PYR = 0,            /* taps {1,4,6,4,1} on both axes, stride 2, offset 0: one pyramid level */
+    MI_BLUR_DOWN_AREA2 = 1,          /* taps {0,1,1}, stride 2, offset 0: the mean of each 2x2 block, >> 2 */
+    MI_BLUR_DOWN_AREA4 = 2           /* taps {0,0,0,1,1,1,1}, stride 4, offset 0: the mean of each 4x4 block, >> 4 */
+} mi_blur_down_preset_id;
+int mi_blur_sep_down_preset(int preset, mi_blur_sep_kernel *k, mi_blur_decimation *d);
+
+/* mi_blur_enqueue_sep that writes only the kept outputs: n_images images of width x height in, n_images images of
+ * Wo x Ho out (device memory, asynchronous; n_images == 0 is MI_BLUR_OK).  Every argument is checked before a device
+ * is asked for: MI_BLUR_ERR_INVALID comes before MI_BLUR_ERR_NO_DEVICE.
+ * blur_sep_down_tiled_kernel (LDS tile, vertical pass over the kept rows only, horizontal pass at the kept columns) takes
+ * exactly the launches with sx = sy = 2 (either phase on either axis), 1-4 channels, width*channels a multiple of 32 (so
+ * input rows and output rows are whole 16-byte chunks) and both pointers 16-byte aligned (and, where a context's in-place
+ * submit gives image strides, strides that are multiples of 16; this export's are dense, which they then are); every other launch goes to
+ * blur_sep_down_generic_kernel (one output byte per thread).  mi_blur_last_kernel() says which one ran. */
+int mi_blur_enqueue_sep_down(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int n_images,
+                             const mi_blur_sep_kernel *k, const mi_blur_decimation *d, void *stream);
+/* The same on the CPU device's threads (synchronous), computing only kept rows and kept columns. */
+int mi_blur_cpu_run_sep_down(const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,
+                             const mi_blur_sep_kernel *k, const mi_blur_decimation *d, int n_threads);
+/* Give a context (created with the INPUT width, height, channels) the decimating filter, with the rules of
+ * mi_blur_ctx_set_kernel: only before the first submit (MI_BLUR_ERR_STATE after); it replaces what another setter set
+ * and is replaced by them; the context keeps a copy.  MI_BLUR_ERR_INVALID also when *d is not valid for the context's
+ * size.  mi_blur_submit then writes n_images * Wo*Ho*C bytes to host_out: pageable caller memory, or pinned memory on
+ * both sides (in place, one launch per submit, never the batch server), on the GPU or the CPU device.  There are no
+ * band forms (a band's phase would depend on where it starts in the image): mi_blur_submit_band, _bands, _planar and
+ * both resident runs return MI_BLUR_ERR_UNSUPPORTED for such a context. */
+int mi_blur_ctx_set_sep_down(mi_blur_ctx *ctx, const mi_blur_sep_kernel *k, const mi_blur_decimation *d);
 
 /* ------------------------------------------------------------------------
  * Median blur, windows 3x3 to 15x15 (no reference analogue).  For a radius r in 1..MI_BLUR_MEDIAN_MAX_RADIUS, with
