@@ -43,6 +43,9 @@ CONV_PRESETS = {"sobel_x": 0, "sobel_y": 1, "sobel_mag": 2, "scharr_x": 3, "scha
                 "laplacian4": 6, "laplacian8": 7, "sharpen": 8, "emboss": 9}
 DECIMATE_MAX = 4
 DOWN_PYR, DOWN_AREA2, DOWN_AREA4 = 0, 1, 2
+RESIZE_MAX_DIM = 32768
+RESIZE_NEAREST, RESIZE_BILINEAR = 0, 1
+RESIZE_MODES = {"nearest": RESIZE_NEAREST, "bilinear": RESIZE_BILINEAR}
 PEER_HANDLE_BYTES = 64
 
 
@@ -55,7 +58,7 @@ def _newer(target: str, sources: list[str]) -> bool:
 
 def build_native(force: bool = False, verbose: bool = False) -> str:
     """Compile libmi_blur.so (hipcc, --offload-arch=gfx950) and the C++ hosts, in-tree."""
-    srcs = [os.path.join(CSRC, f) for f in ("blur_kernels.hip", "sep_kernels.hip", "median_kernels.hip", "morph_kernels.hip", "bilateral_kernels.hip", "conv_kernels.hip", "sep_down_kernels.hip", "layout_kernels.hip", "mi_blur_api.cpp", "cpu_device.cpp")]
+    srcs = [os.path.join(CSRC, f) for f in ("blur_kernels.hip", "sep_kernels.hip", "median_kernels.hip", "morph_kernels.hip", "bilateral_kernels.hip", "conv_kernels.hip", "sep_down_kernels.hip", "resize_kernels.hip", "layout_kernels.hip", "mi_blur_api.cpp", "cpu_device.cpp")]
     deps = srcs + [os.path.join(CSRC, f) for f in ("blur_launch.h", "kernel_common.h", "cpu_device.h", "filter.h")] + [HEADER]
     if force or not _newer(LIB_PATH, deps):
         cmd = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra",
@@ -219,6 +222,19 @@ class Decimation(C.Structure):
     _fields_ = [("sx", C.c_int), ("sy", C.c_int), ("ox", C.c_int), ("oy", C.c_int)]
 
 
+class Resize(C.Structure):
+    """mi_blur_resize: the output size and the mode (RESIZE_NEAREST | RESIZE_BILINEAR)."""
+    _fields_ = [("out_width", C.c_int), ("out_height", C.c_int), ("mode", C.c_int)]
+
+
+def _resize_mode(mode) -> int:
+    if isinstance(mode, str):
+        if mode not in RESIZE_MODES:
+            raise ValueError("resize: mode is 'bilinear' or 'nearest'")
+        return RESIZE_MODES[mode]
+    return int(mode)
+
+
 class MiBlurError(RuntimeError):
     def __init__(self, status: int, what: str):
         super().__init__(f"{what}: status {status} ({lib().mi_blur_strerror(status).decode()})")
@@ -312,6 +328,10 @@ def lib() -> C.CDLL:
         "mi_blur_enqueue_sep_down": (i, [u8p, u8p, i, i, i, i, C.POINTER(SepKernel), C.POINTER(Decimation), vp]),
         "mi_blur_cpu_run_sep_down": (i, [u8p, u8p, i, i, i, i, C.POINTER(SepKernel), C.POINTER(Decimation), i]),
         "mi_blur_ctx_set_sep_down": (i, [vp, C.POINTER(SepKernel), C.POINTER(Decimation)]),
+        "mi_blur_resize_coord": (i, [i, i, i, i, C.POINTER(i), C.POINTER(i), C.POINTER(i)]),
+        "mi_blur_enqueue_resize": (i, [u8p, u8p, i, i, i, i, C.POINTER(Resize), vp]),
+        "mi_blur_cpu_run_resize": (i, [u8p, u8p, i, i, i, i, C.POINTER(Resize), i]),
+        "mi_blur_ctx_set_resize": (i, [vp, C.POINTER(Resize)]),
         "mi_blur_conv_preset": (i, [i, C.POINTER(Conv)]),
         "mi_blur_enqueue_conv": (i, [u8p, u8p, i, i, i, i, C.POINTER(Conv), vp]),
         "mi_blur_enqueue_conv_band": (i, [u8p, u8p, i, i, i, i, i, C.POINTER(Conv), vp]),
@@ -461,6 +481,13 @@ class Context:
         d = Decimation(int(sx), int(sy), int(ox), int(oy))
         check(lib().mi_blur_ctx_set_sep_down(self.h, C.byref(kernel), C.byref(d)), "mi_blur_ctx_set_sep_down")
         self.kernel, self.decimation = kernel, d
+
+    def set_resize(self, out_width: int, out_height: int, mode="bilinear") -> None:
+        """The resize in place of the blur (before the first submit only): submit() then writes images of
+        out_width x out_height, which may be larger than the input; the band, planar and resident forms are not supported."""
+        r = Resize(int(out_width), int(out_height), _resize_mode(mode))
+        check(lib().mi_blur_ctx_set_resize(self.h, C.byref(r)), "mi_blur_ctx_set_resize")
+        self.resize_spec = r
 
     def submit_bands(self, host_in, host_out, n_images: int, host_image_stride: int, band_rows: int,
                      halo_top: int, halo_bottom: int) -> None:
@@ -777,3 +804,45 @@ def area_down(images, factor: int = 2, device: int = 0, batch: int = 0):
     if factor not in (2, 4):
         raise ValueError("area_down: factor is 2 or 4")
     return _down_preset("area_down", images, DOWN_AREA2 if factor == 2 else DOWN_AREA4, device, batch)
+
+
+def resize_coord(n_in: int, n_out: int, X: int, mode="bilinear") -> tuple[int, int, int]:
+    """(a, b, f) of one axis of the resize for output index X of n_out over n_in input samples (mi_blur_resize_coord):
+    input samples a <= b <= a + 1 and the weight f of b in 0..2048; nearest gives (i, i, 0)."""
+    a, b, f = C.c_int(), C.c_int(), C.c_int()
+    check(lib().mi_blur_resize_coord(int(n_in), int(n_out), _resize_mode(mode), int(X), C.byref(a), C.byref(b), C.byref(f)),
+          "mi_blur_resize_coord")
+    return a.value, b.value, f.value
+
+
+def resize(images, size, mode="bilinear", device: int = 0, batch: int = 0):
+    """Resize to size = (out_width, out_height), numpy in -> numpy out: exact fixed-point bilinear (11 fraction bits, one
+    final rounding) or nearest, pixel centres aligned, any ratio (include/mi_blur.h has the definition).
+
+    images: (H, W), (H, W, C) or (N, H, W, C) uint8; the result has the same rank with out_height and out_width.
+    device: HIP ordinal, or DEVICE_CPU.  A reduction by more than 2x aliases: area_down / pyr_down first.  Goes through
+    mi_blur_create / mi_blur_ctx_set_resize / mi_blur_submit / mi_blur_sync."""
+    import numpy as np
+    a = _images(images, "resize")
+    wo, ho = int(size[0]), int(size[1])
+    m = _resize_mode(mode)
+    rank = a.ndim
+    if rank == 2:
+        a = a[None, :, :, None]
+    elif rank == 3:
+        a = a[None]
+    n, h, w, c = a.shape
+    if h == 0 or w == 0 or c == 0:
+        raise ValueError("resize: images must not be empty")
+    if wo < 1 or ho < 1:
+        raise ValueError("resize: size is (out_width, out_height), both at least 1")
+    out = np.empty((n, ho, wo, c), dtype=np.uint8)
+    if n:
+        per = min(n, batch if batch > 0 else 4096)
+        isz, osz = h * w * c, ho * wo * c
+        with Context(device, w, h, c, 1, max_batch=per, n_slots=2) as ctx:
+            ctx.set_resize(wo, ho, m)
+            for i in range(0, n, per):
+                ctx.submit(a.ctypes.data + i * isz, out.ctypes.data + i * osz, min(per, n - i))
+            ctx.sync()
+    return out[0, :, :, 0] if rank == 2 else out[0] if rank == 3 else out

@@ -1,7 +1,7 @@
 // heterogeneous_blur — Approach 1 (image-level distribution) host, MI355X-native.
 //
 //   heterogeneous_blur {cpu|gpu|both} [gpu_ratio] [batch]  [--image F | --synthetic | --size WxH] [--channels C]
-//                      [--ksize 3|5 | --sigma S [--sigma-y S] [--radius R] | --median K | --erode K | --dilate K | --morph-gradient K | --bilateral K [--sigma-color S] [--sigma-space S] | --conv NAME | --pyr-down] [--images N] [--gpus G] [--slots S] [--threads T] [--resident [--fused]]
+//                      [--ksize 3|5 | --sigma S [--sigma-y S] [--radius R] | --median K | --erode K | --dilate K | --morph-gradient K | --bilateral K [--sigma-color S] [--sigma-space S] | --conv NAME | --pyr-down | --resize WxH [--nearest]] [--images N] [--gpus G] [--slots S] [--threads T] [--resident [--fused]]
 //                      [--verbose] [--csv FILE] [--save FILE]
 //                      [--frames DIR|PATTERN|FILE [--save-dir DIR] [--planar-out | --native-layout]]   (cpu | gpu)
 //
@@ -111,9 +111,10 @@ int main(int argc, char **argv)
     printf("Original image loaded: %dx%d, %d channels\n", width, height, channels);
     const size_t image_size = (size_t)width * height * channels;
     printf("Size of one image: %zu bytes (%.2f KB)\n", image_size, image_size / 1024.0);
-    // --pyr-down: every output image is the decimated one; out_image_size == image_size under every other filter
+    // --pyr-down / --resize: every output image is the decimated / resized one; out_image_size == image_size under every other filter
     int out_width = width, out_height = height;
     if (filter.pyr_down) print_pyr_down(filter, width, height, &out_width, &out_height);
+    if (filter.resize) print_resize(filter, width, height, &out_width, &out_height);
     const size_t out_image_size = (size_t)out_width * out_height * channels;
     printf("Original image source: %s\n\n", img.source.c_str());
     const uint8_t *original_image = img.px.data();

@@ -174,6 +174,8 @@ struct Options {
     int conv_preset = -1;                //              emboss): that 3x3 convolution instead of --ksize; mi_blur_ctx_set_conv on every context
     bool pyr_down = false;               // --pyr-down: one pyramid level (MI_BLUR_DOWN_PYR) instead of --ksize: mi_blur_ctx_set_sep_down on every
                                          //              context, outputs of the decimated size (heterogeneous_blur only: no bands)
+    int resize_w = 0, resize_h = 0;      // --resize WxH [--nearest]: resize every image to W x H (bilinear; --nearest: nearest) instead of --ksize:
+    bool nearest = false;                //              mi_blur_ctx_set_resize on every context, outputs of that size (heterogeneous_blur only: no bands)
     int images = 5000;                   // --images N   (NUM_IMAGES, heterogeneous_blur.c:44)
     bool images_given = false;
     int gpus = 1;                        // --gpus G
@@ -245,6 +247,12 @@ inline int parse_flags(int argc, char **argv, Options &o)
             if (o.conv_preset < 0) { printf("Error: --conv sobel-x|sobel-y|sobel|scharr-x|scharr-y|scharr|laplacian|laplacian8|sharpen|emboss\n"); exit(-1); }
         }
         else if (a == "--pyr-down") o.pyr_down = true;
+        else if (a == "--resize") {
+            char tail = 0;
+            if (sscanf(next("--resize"), "%dx%d%c", &o.resize_w, &o.resize_h, &tail) != 2 || o.resize_w < 1 || o.resize_h < 1 ||
+                o.resize_w > MI_BLUR_RESIZE_MAX_DIM || o.resize_h > MI_BLUR_RESIZE_MAX_DIM) { printf("Error: --resize WxH, each 1..%d\n", MI_BLUR_RESIZE_MAX_DIM); exit(-1); }
+        }
+        else if (a == "--nearest") o.nearest = true;
         else if (a == "--sigma-color") { o.sigma_color = atof(next("--sigma-color")); o.sigma_color_given = true; if (!(o.sigma_color > 0.0)) { printf("Error: --sigma-color must be > 0\n"); exit(-1); } }
         else if (a == "--sigma-space") { o.sigma_space = atof(next("--sigma-space")); o.sigma_space_given = true; if (!(o.sigma_space >= 0.0)) { printf("Error: --sigma-space must be >= 0\n"); exit(-1); } }
         else if (a == "--sigma") { o.sigma = atof(next("--sigma")); if (!(o.sigma > 0.0)) { printf("Error: --sigma must be > 0\n"); exit(-1); } }
@@ -286,6 +294,9 @@ inline int parse_flags(int argc, char **argv, Options &o)
     if (o.conv_preset >= 0 && o.resident) { printf("Error: --conv does not run --resident\n"); exit(-1); }
     if (o.pyr_down && (o.ksize_given || o.sigma > 0.0 || o.median || o.morph || o.bilateral || o.conv_preset >= 0)) { printf("Error: --pyr-down excludes --ksize, --sigma, --median, --erode, --dilate, --morph-gradient, --bilateral and --conv\n"); exit(-1); }
     if (o.pyr_down && (o.resident || !o.frames.empty())) { printf("Error: --pyr-down excludes --resident and --frames\n"); exit(-1); }
+    if (o.resize_w && (o.ksize_given || o.sigma > 0.0 || o.median || o.morph || o.bilateral || o.conv_preset >= 0 || o.pyr_down)) { printf("Error: --resize excludes --ksize, --sigma, --median, --erode, --dilate, --morph-gradient, --bilateral, --conv and --pyr-down\n"); exit(-1); }
+    if (o.resize_w && (o.resident || !o.frames.empty())) { printf("Error: --resize excludes --resident and --frames\n"); exit(-1); }
+    if (o.nearest && !o.resize_w) { printf("Error: --nearest needs --resize\n"); exit(-1); }
     return npos;
 }
 
@@ -307,6 +318,8 @@ struct HostFilter {
     bool pyr_down = false;      // --pyr-down: the decimating filter `down_k`, `down_d` (mi_blur_sep_down_preset, MI_BLUR_DOWN_PYR)
     mi_blur_sep_kernel down_k{};
     mi_blur_decimation down_d{};
+    bool resize = false;        // --resize WxH [--nearest]: the resize `rs` (mi_blur_ctx_set_resize)
+    mi_blur_resize rs{};
 };
 
 inline HostFilter filter_of(const Options &o)
@@ -329,6 +342,8 @@ inline HostFilter filter_of(const Options &o)
         printf("Error: no pyramid kernel\n");
         exit(-1);
     }
+    f.resize = o.resize_w > 0;
+    f.rs = mi_blur_resize{o.resize_w, o.resize_h, o.nearest ? MI_BLUR_RESIZE_NEAREST : MI_BLUR_RESIZE_BILINEAR};
     return f;
 }
 
@@ -341,6 +356,15 @@ inline void set_filter(mi_blur_ctx *ctx, const HostFilter &f)
     if (f.bilateral) mi_check(mi_blur_ctx_set_bilateral(ctx, &f.bil), "Failed to set the bilateral filter");
     if (f.conv_preset >= 0) mi_check(mi_blur_ctx_set_conv(ctx, &f.conv), "Failed to set the convolution");
     if (f.pyr_down) mi_check(mi_blur_ctx_set_sep_down(ctx, &f.down_k, &f.down_d), "Failed to set the pyramid filter");
+    if (f.resize) mi_check(mi_blur_ctx_set_resize(ctx, &f.rs), "Failed to set the resize");
+}
+
+// The banner's "Blur kernel" line of --resize (after the image is loaded, like print_pyr_down()); *wo, *ho: the size of
+// every output image.
+inline void print_resize(const HostFilter &f, int width, int height, int *wo, int *ho)
+{
+    *wo = f.rs.out_width; *ho = f.rs.out_height;
+    printf("Blur kernel: %s resize, %dx%d -> %dx%d\n", f.rs.mode == MI_BLUR_RESIZE_NEAREST ? "nearest" : "bilinear", width, height, *wo, *ho);
 }
 
 // The banner's "Blur kernel" line of --pyr-down, which needs the image size (print_filter() comes before the image is
@@ -358,7 +382,7 @@ inline int filter_halo(const HostFilter &f) { return f.conv_preset >= 0 ? f.conv
 // The banner's "Blur kernel" line (with the taps of a Gaussian).
 inline void print_filter(const HostFilter &f)
 {
-    if (f.pyr_down) return;     // print_pyr_down(), once the image size is known
+    if (f.pyr_down || f.resize) return;     // print_pyr_down() / print_resize(), once the image size is known
     if (f.median) { printf("Blur kernel: %dx%d median\n", f.median, f.median); return; }
     if (f.conv_preset >= 0) { printf("Blur kernel: %dx%d convolution (%s)\n", 2 * f.conv.rx + 1, 2 * f.conv.ry + 1, f.conv_name.c_str()); return; }
     if (f.bilateral) { printf("Blur kernel: %dx%d bilateral (sigma_color %g, sigma_space %g)\n", f.bilateral, f.bilateral, f.sigma_color, f.sigma_space); return; }

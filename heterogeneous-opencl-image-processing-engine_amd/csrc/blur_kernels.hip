@@ -1587,6 +1587,7 @@ int launch(const LaunchDesc &d)
     if (d.filter->kind == FilterKind::BILATERAL) return launch_bilateral(d);
     if (d.filter->kind == FilterKind::CONV) return launch_conv(d);
     if (d.filter->kind == FilterKind::SEP_DOWN) return launch_sep_down(d);
+    if (d.filter->kind == FilterKind::RESIZE) return launch_resize(d);
     if (const int st = check_desc(d, FilterKind::BOX)) return st;
     if (d.filter->radius != 1 && d.filter->radius != 2) return MI_BLUR_ERR_INVALID;
     if (d.n_images == 0) return MI_BLUR_OK;           // before the strides are looked at (launch_sep / launch_median / launch_morph / launch_bilateral / launch_conv: after)

@@ -1,5 +1,5 @@
 // blur_launch.h — internal (not part of the C ABI): launch interface between
-// mi_blur_api.cpp and the gfx950 kernels in the eight .hip files (what those share among themselves: kernel_common.h).
+// mi_blur_api.cpp and the gfx950 kernels in the nine .hip files (what those share among themselves: kernel_common.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -28,7 +28,7 @@ struct LaunchDesc {
 };
 
 // Returns MI_BLUR_OK or a negative mi_blur_status.  A SEP filter is handed to launch_sep, a MEDIAN one to launch_median,
-// a MORPH one to launch_morph, a BILATERAL one to launch_bilateral, a CONV one to launch_conv, a SEP_DOWN one to launch_sep_down;
+// a MORPH one to launch_morph, a BILATERAL one to launch_bilateral, a CONV one to launch_conv, a SEP_DOWN one to launch_sep_down, a RESIZE one to launch_resize;
 // launch_fused and zc_fill_batch take BOX filters only.
 int launch(const LaunchDesc &d);
 // The other families, each in the .hip file of its name: the separable kernel of d.filter->taps, the median of
@@ -47,6 +47,10 @@ int launch_conv(const LaunchDesc &d);
 // strides and 64-bit image offsets like the others; only the whole image: y0 != 0, y1 != band_rows, halo_top / halo_bottom
 // are MI_BLUR_ERR_UNSUPPORTED.
 int launch_sep_down(const LaunchDesc &d);
+// The resize (FilterKind::RESIZE, resize_kernels.hip): d.in = n_images images of band_rows x width, d.out = n_images
+// images of resize_h x resize_w (out_stride, when given, is measured against that, and may exceed in_stride).  The
+// contract of launch_sep_down: only the whole image, bands and halo pointers are MI_BLUR_ERR_UNSUPPORTED.
+int launch_resize(const LaunchDesc &d);
 // Sets what last_kernel() reports for the calling thread.
 void set_last_kernel(const char *name);
 

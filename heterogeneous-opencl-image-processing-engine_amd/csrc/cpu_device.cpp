@@ -382,9 +382,44 @@ void cpu_sep_down_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, con
     }
 }
 
+// Output rows [Y_begin, Y_end) of the resize of f (f.resize_*) on one W x H image; out = the resized image (dense).
+// xtab: resize_axis of every output column (resize_xtable: built once per call, shared by the threads).  BILINEAR blends
+// the two input rows at the two input columns in 32-bit unsigned, one rounding shift; NEAREST copies pixels.
+void cpu_resize_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, const Filter &f, int Y_begin, int Y_end, const ResizeCoord *xtab)
+{
+    const int Wo = f.resize_w, Ho = f.resize_h;
+    const size_t pitch = (size_t)W * C, opitch = (size_t)Wo * C;
+    for (int Y = Y_begin; Y < Y_end; Y++) {
+        const ResizeCoord cy = resize_axis(H, Ho, f.resize_mode, Y);
+        const uint8_t *ra = in + (size_t)cy.a * pitch, *rb = in + (size_t)cy.b * pitch;
+        uint8_t *o = out + (size_t)Y * opitch;
+        if (f.resize_mode == MI_BLUR_RESIZE_NEAREST) {
+            for (int X = 0; X < Wo; X++)
+                for (int c = 0; c < C; c++) o[(size_t)X * C + c] = ra[(size_t)xtab[X].a * C + c];
+            continue;
+        }
+        const uint32_t fy = (uint32_t)cy.f, gy = 2048u - fy;
+        for (int X = 0; X < Wo; X++) {
+            const uint32_t fx = (uint32_t)xtab[X].f, gx = 2048u - fx;
+            const size_t xa = (size_t)xtab[X].a * C, xb = (size_t)xtab[X].b * C;
+            for (int c = 0; c < C; c++) {
+                const uint32_t top = gx * ra[xa + c] + fx * ra[xb + c], bot = gx * rb[xa + c] + fx * rb[xb + c];
+                o[(size_t)X * C + c] = (uint8_t)((gy * top + fy * bot + (1u << 21)) >> 22);
+            }
+        }
+    }
+}
+
+std::vector<ResizeCoord> resize_xtable(int W, const Filter &f)
+{
+    std::vector<ResizeCoord> t((size_t)f.resize_w);
+    for (int X = 0; X < f.resize_w; X++) t[(size_t)X] = resize_axis(W, f.resize_w, f.resize_mode, X);
+    return t;
+}
+
 // n_images bands of band_rows rows; output rows [y0,y1) of each.  Threads take whole
-// images when there are enough of them, else row slices of each image.  A SEP_DOWN filter: whole images only (y0 = 0,
-// y1 = band_rows); the output blocks are the decimated images and the row slices are cut in output rows.
+// images when there are enough of them, else row slices of each image.  A SEP_DOWN or RESIZE filter: whole images only
+// (y0 = 0, y1 = band_rows); the output blocks are the decimated / resized images and the row slices are cut in output rows.
 void cpu_blur_batch(const uint8_t *in, uint8_t *out, int W, int band_rows, int C, const Filter &f, int n_images,
                     int y0, int y1, int n_threads, size_t in_stride, size_t out_stride)
 {
@@ -392,8 +427,11 @@ void cpu_blur_batch(const uint8_t *in, uint8_t *out, int W, int band_rows, int C
     if (n_threads <= 0) n_threads = hardware_threads();
     if (in_stride == 0) in_stride = (size_t)W * C * band_rows;
     const bool down = f.kind == FilterKind::SEP_DOWN;
+    const bool resize = f.kind == FilterKind::RESIZE;
     if (down) { y0 = 0; y1 = down_rows(band_rows, f.down_sy, f.down_oy); }   // from here on: output rows
-    if (out_stride == 0) out_stride = (size_t)(down ? down_cols(W, f.down_sx, f.down_ox) : W) * C * (y1 - y0);
+    if (resize) { y0 = 0; y1 = f.resize_h; }
+    if (out_stride == 0) out_stride = (size_t)(down ? down_cols(W, f.down_sx, f.down_ox) : resize ? f.resize_w : W) * C * (y1 - y0);
+    const std::vector<ResizeCoord> xtab = resize ? resize_xtable(W, f) : std::vector<ResizeCoord>();
     const int rows = y1 - y0;
     // work items: (image, row slice)
     // enough items for the threads to end together: a batch of 35 images on 16 threads is three rounds of whole images with the
@@ -413,6 +451,7 @@ void cpu_blur_batch(const uint8_t *in, uint8_t *out, int W, int band_rows, int C
             const uint8_t *src = in + img * in_stride;
             uint8_t *dst = out + img * out_stride;
             if (down) cpu_sep_down_rows(src, dst, W, band_rows, C, f, ys, ye);
+            else if (resize) cpu_resize_rows(src, dst, W, band_rows, C, f, ys, ye, xtab.data());
             else if (f.kind == FilterKind::CONV) cpu_conv_rows(src, dst, W, band_rows, C, f, ys, ye, y0);
             else if (f.kind == FilterKind::BILATERAL) cpu_bilateral_rows(src, dst, W, band_rows, C, f, ys, ye, y0);
             else if (f.kind == FilterKind::MORPH) cpu_morph_rows(src, dst, W, band_rows, C, f.morph_op, f.morph_rx, f.morph_ry, ys, ye, y0);

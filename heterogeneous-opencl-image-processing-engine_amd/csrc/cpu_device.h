@@ -3,6 +3,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "filter.h"
 
 namespace mi_blur {
@@ -26,6 +28,9 @@ void cpu_bilateral_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, co
                         int out_row_shift);
 // Output rows [Y_begin, Y_end) of the decimating separable filter of f (f.taps, f.down_*): kept rows and columns only.
 void cpu_sep_down_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, const Filter &f, int Y_begin, int Y_end);
+// Output rows [Y_begin, Y_end) of the resize of f (f.resize_*); xtab = resize_xtable(W, f), the x axis of every output column.
+void cpu_resize_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, const Filter &f, int Y_begin, int Y_end, const ResizeCoord *xtab);
+std::vector<ResizeCoord> resize_xtable(int W, const Filter &f);
 void cpu_blur_batch(const uint8_t *in, uint8_t *out, int W, int band_rows, int C, const Filter &f, int n_images,
                     int y0, int y1, int n_threads, size_t in_stride = 0, size_t out_stride = 0);
 // The box blur of radius R (1|2): the form the host-only sanitizer harness (tests/san_cpu_device.cpp) drives.

@@ -1,8 +1,10 @@
 // filter.h — internal: the one filter a launch, a context or a CPU run applies, in the form the GPU kernels
-// (blur_kernels.hip, sep_kernels.hip, median_kernels.hip, morph_kernels.hip, bilateral_kernels.hip, conv_kernels.hip, sep_down_kernels.hip) and the CPU device (cpu_device.cpp) take it.  Plain C++, no HIP.
+// (blur_kernels.hip, sep_kernels.hip, median_kernels.hip, morph_kernels.hip, bilateral_kernels.hip, conv_kernels.hip, sep_down_kernels.hip, resize_kernels.hip) and the CPU device (cpu_device.cpp) take it.  Plain C++, no HIP.
 #pragma once
 
 #include "../../include/mi_blur.h"
+
+#include <limits.h>
 
 namespace mi_blur {
 
@@ -15,7 +17,7 @@ struct SepTaps {
     unsigned wx[2 * SEP_MAX_R + 1], wy[2 * SEP_MAX_R + 1];
 };
 
-enum class FilterKind { BOX, SEP, MEDIAN, MORPH, BILATERAL, CONV, SEP_DOWN };
+enum class FilterKind { BOX, SEP, MEDIAN, MORPH, BILATERAL, CONV, SEP_DOWN, RESIZE };
 
 // BOX: the fixed 3x3 / 5x5 kernel of `radius` 1|2.  SEP: the separable kernel `taps`.  MEDIAN: the median of `radius` 1..7.
 // MORPH: the window minimum / maximum / their difference (`morph_op`) over (2 morph_rx + 1) x (2 morph_ry + 1).
@@ -24,7 +26,9 @@ enum class FilterKind { BOX, SEP, MEDIAN, MORPH, BILATERAL, CONV, SEP_DOWN };
 // CONV: the signed 2-D convolution (mi_blur_conv) of radii `conv_rx`, `conv_ry` with the taps CENTRED in the 15 x 15 frame:
 // conv_k[t][(j + 7) * 15 + (i + 7)] = K[j][i] (t = 0) or K2[j][i] (t = 1, MAG only; zeros otherwise), 0 beyond the radii.
 // SEP_DOWN: the separable kernel `taps` on the whole image, of whose result only column down_ox + X * down_sx and row
-// down_oy + Y * down_sy are kept (mi_blur_decimation): the one kind whose output is smaller than its input.
+// down_oy + Y * down_sy are kept (mi_blur_decimation): its output is smaller than its input.
+// RESIZE: the fixed-point resize (mi_blur_resize) to resize_w x resize_h in `resize_mode`: the output may be smaller or
+// larger than the input, in either axis.
 struct Filter {
     FilterKind kind;
     int radius;             // BOX and MEDIAN
@@ -35,8 +39,49 @@ struct Filter {
     int conv_rx = 0, conv_ry = 0, conv_mode = 0, conv_shift = 0;   // CONV (radii 0..7, mi_blur_conv_mode, shift 0..16)
     int32_t conv_bias = 0;
     int16_t conv_k[2][15 * 15] = {};
-    int down_sx = 1, down_sy = 1, down_ox = 0, down_oy = 0;   // SEP_DOWN (strides 1..4, phases below them); last, so the initialisers above stay
+    int down_sx = 1, down_sy = 1, down_ox = 0, down_oy = 0;   // SEP_DOWN (strides 1..4, phases below them); after the older fields, so the initialisers above stay
+    int resize_w = 0, resize_h = 0, resize_mode = 0;          // RESIZE (1..MI_BLUR_RESIZE_MAX_DIM each way, mi_blur_resize_mode); last, for the same reason
 };
+
+#if defined(__HIP__)
+#define MI_BLUR_HD __host__ __device__
+#else
+#define MI_BLUR_HD
+#endif
+// One axis of the resize (include/mi_blur.h, "Image resize"): output index X of n_out samples over n_in input samples,
+// pixel centres aligned.  BILINEAR: the two input samples a <= b <= a + 1 and the weight f of b in 0..2048.  NEAREST:
+// a = b = the input sample whose cell holds the output centre, f = 0.  The GPU kernels, the CPU device and
+// mi_blur_resize_coord all come through here.  1 <= n_in, n_out <= MI_BLUR_RESIZE_MAX_DIM keeps everything in 32 bits.
+struct ResizeCoord { int a, b, f; };
+MI_BLUR_HD inline ResizeCoord resize_axis(int n_in, int n_out, int mode, int X)
+{
+    const unsigned den = 2u * (unsigned)n_out;
+    ResizeCoord r;
+    if (mode == MI_BLUR_RESIZE_NEAREST) {
+        r.a = r.b = (int)(((unsigned)(2 * X + 1) * (unsigned)n_in) / den);
+        r.f = 0;
+        return r;
+    }
+    const int num = (2 * X + 1) * n_in - n_out;       // >= n_in - n_out > -den
+    int i0;
+    unsigned rem;
+    if (num < 0) { i0 = -1; rem = (unsigned)(num + (int)den); }
+    else { i0 = (int)((unsigned)num / den); rem = (unsigned)num - (unsigned)i0 * den; }
+    r.f = (int)((rem * 2048u + (unsigned)n_out) / den);
+    r.a = i0 < 0 ? 0 : i0 > n_in - 1 ? n_in - 1 : i0;
+    r.b = i0 + 1 > n_in - 1 ? n_in - 1 : i0 + 1;
+    return r;
+}
+// A resize that is valid for a W x H image of C channels: sizes 1..MI_BLUR_RESIZE_MAX_DIM both sides, a known mode, and
+// input and output images inside the per-image byte limits of a launch.
+inline bool resize_ok(const mi_blur_resize *r, int W, int H, int C)
+{
+    return r && r->out_width >= 1 && r->out_height >= 1 && r->out_width <= MI_BLUR_RESIZE_MAX_DIM && r->out_height <= MI_BLUR_RESIZE_MAX_DIM &&
+           W >= 1 && H >= 1 && C >= 1 && W <= MI_BLUR_RESIZE_MAX_DIM && H <= MI_BLUR_RESIZE_MAX_DIM &&
+           (r->mode == MI_BLUR_RESIZE_NEAREST || r->mode == MI_BLUR_RESIZE_BILINEAR) &&
+           (long long)W * C <= INT_MAX / 2 && (long long)W * C * H <= INT_MAX &&
+           (long long)r->out_width * C <= INT_MAX / 2 && (long long)r->out_width * C * r->out_height <= INT_MAX;
+}
 
 // Output size of a decimation of a W x H image: kept columns / rows (> 0 for a valid decimation, down_ok()).
 inline int down_cols(int W, int sx, int ox) { return (W - ox + sx - 1) / sx; }
@@ -80,6 +125,15 @@ inline int filter_sep_down(const mi_blur_sep_kernel *k, const mi_blur_decimation
     g.kind = FilterKind::SEP_DOWN;
     g.down_sx = d->sx; g.down_sy = d->sy; g.down_ox = d->ox; g.down_oy = d->oy;
     *f = g;
+    return MI_BLUR_OK;
+}
+
+// The target size and mode of *r (the image size is checked where it is known: resize_ok()).
+inline int filter_resize(const mi_blur_resize *r, Filter *f)
+{
+    if (!f || !resize_ok(r, 1, 1, 1)) return MI_BLUR_ERR_INVALID;
+    *f = Filter{FilterKind::RESIZE, 0, {}};
+    f->resize_w = r->out_width; f->resize_h = r->out_height; f->resize_mode = r->mode;
     return MI_BLUR_OK;
 }
 

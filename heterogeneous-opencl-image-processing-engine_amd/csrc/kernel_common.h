@@ -1,5 +1,5 @@
-// kernel_common.h — internal (not part of the C ABI): what the eight kernel files (blur_kernels.hip, sep_kernels.hip,
-// median_kernels.hip, morph_kernels.hip, bilateral_kernels.hip, conv_kernels.hip, sep_down_kernels.hip, layout_kernels.hip) share below launch(): the launch call, the blockIdx -> tile maps, the template
+// kernel_common.h — internal (not part of the C ABI): what the nine kernel files (blur_kernels.hip, sep_kernels.hip,
+// median_kernels.hip, morph_kernels.hip, bilateral_kernels.hip, conv_kernels.hip, sep_down_kernels.hip, resize_kernels.hip, layout_kernels.hip) share below launch(): the launch call, the blockIdx -> tile maps, the template
 // dispatch, the argument checks and parameter fill every family repeats, the host side of the direct layout, and the
 // LDS tile of the sep, morph, bilateral and conv kernels (its coordinates, its staging, its launch geometry).
 // Everything here has internal linkage, so libmi_blur.so exports nothing from it.

@@ -236,6 +236,28 @@ extern "C" int mi_blur_enqueue_sep_down(const uint8_t *d_in, uint8_t *d_out, int
 }
 
 // ----------------------------------------------------------------------------------
+// image resize: fixed-point bilinear and nearest, any output size (no reference analogue)
+// ----------------------------------------------------------------------------------
+extern "C" int mi_blur_resize_coord(int n_in, int n_out, int mode, int X, int *i0, int *i1, int *frac)
+{
+    if (!i0 || !i1 || !frac || n_in < 1 || n_out < 1 || n_in > MI_BLUR_RESIZE_MAX_DIM || n_out > MI_BLUR_RESIZE_MAX_DIM ||
+        (mode != MI_BLUR_RESIZE_NEAREST && mode != MI_BLUR_RESIZE_BILINEAR) || X < 0 || X >= n_out)
+        return MI_BLUR_ERR_INVALID;
+    const ResizeCoord r = resize_axis(n_in, n_out, mode, X);
+    *i0 = r.a; *i1 = r.b; *frac = r.f;
+    return MI_BLUR_OK;
+}
+
+extern "C" int mi_blur_enqueue_resize(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int n_images,
+                                      const mi_blur_resize *r, void *stream)
+{
+    Filter f;
+    if (filter_resize(r, &f) || !d_in || !d_out || d_in == d_out || n_images < 0 || !resize_ok(r, width, height, channels))
+        return MI_BLUR_ERR_INVALID;
+    return enqueue_filter(f, d_in, d_out, width, height, channels, n_images, 0, height, MI_BLUR_VARIANT_AUTO, stream);
+}
+
+// ----------------------------------------------------------------------------------
 // median blur, radius 1..7 (no reference analogue)
 // ----------------------------------------------------------------------------------
 extern "C" int mi_blur_enqueue_median_band(const uint8_t *d_in, uint8_t *d_out, int width, int band_rows, int channels,
@@ -485,7 +507,7 @@ struct CpuWorker {
 
 struct mi_blur_ctx {
     int device = 0, W = 0, H = 0, C = 0, max_batch = 0, n_threads = 0;
-    Filter filter{};                                             // every submit applies it: mi_blur_create's radius, or set_kernel / set_median / set_morph / set_bilateral / set_conv / set_sep_down
+    Filter filter{};                                             // every submit applies it: mi_blur_create's radius, or set_kernel / set_median / set_morph / set_bilateral / set_conv / set_sep_down / set_resize
     size_t image_bytes = 0;
     std::vector<Slot> slots;
     int next_slot = 0;
@@ -532,7 +554,7 @@ struct mi_blur_ctx {
     // CPU device
     std::vector<CpuJob *> cpu_jobs;
     CpuWorker *cpu_worker = nullptr;
-    bool submitted = false;                                      // set_kernel / set_median / set_morph / set_bilateral / set_conv / set_sep_down only before this
+    bool submitted = false;                                      // set_kernel / set_median / set_morph / set_bilateral / set_conv / set_sep_down / set_resize only before this
     bool is_cpu() const { return device == MI_BLUR_DEVICE_CPU; }
 };
 
@@ -739,20 +761,34 @@ extern "C" int mi_blur_create(mi_blur_ctx **out_ctx, int device, int width, int 
     return MI_BLUR_OK;
 }
 
+// Filters whose output image is not the input's size (SEP_DOWN, RESIZE): whole images only, bytes_alg = input + output.
+static bool own_output_size(const mi_blur_ctx *c) { return c->filter.kind == FilterKind::SEP_DOWN || c->filter.kind == FilterKind::RESIZE; }
+// Bytes of one output image of the context's filter on a whole input image.
+static size_t out_image_bytes(const mi_blur_ctx *c)
+{
+    const Filter &f = c->filter;
+    if (f.kind == FilterKind::SEP_DOWN) return (size_t)down_cols(c->W, f.down_sx, f.down_ox) * c->C * (size_t)down_rows(c->H, f.down_sy, f.down_oy);
+    if (f.kind == FilterKind::RESIZE) return (size_t)f.resize_w * c->C * (size_t)f.resize_h;
+    return c->image_bytes;
+}
+// Bytes of a slot's output buffers per image: a resize may write more than it reads.  The filter is known by the time a
+// slot's buffers are made (setters work only before the first submit); every other context: image_bytes, as before.
+static size_t slot_out_image_bytes(const mi_blur_ctx *c) { return std::max(c->image_bytes, out_image_bytes(c)); }
+
 // Lazily made slot buffers (see mi_blur_create).  HIP's allocation calls are synchronous with respect to the device only
 // where they must be; the slot's streams carry nothing that touches these buffers before they exist.
 static int slot_staging(mi_blur_ctx *c, Slot &s, bool in, bool out)
 {
-    const size_t bytes = c->image_bytes * (size_t)c->max_batch;
+    const size_t bytes = c->image_bytes * (size_t)c->max_batch, out_bytes = slot_out_image_bytes(c) * (size_t)c->max_batch;
     if (in && !s.h_in) HIP_TRY(hipHostMalloc((void **)&s.h_in, bytes, hipHostMallocDefault));
-    if (out && !s.h_out) HIP_TRY(hipHostMalloc((void **)&s.h_out, bytes, hipHostMallocDefault));
+    if (out && !s.h_out) HIP_TRY(hipHostMalloc((void **)&s.h_out, out_bytes, hipHostMallocDefault));
     return MI_BLUR_OK;
 }
 static int slot_device(mi_blur_ctx *c, Slot &s)
 {
-    const size_t bytes = c->image_bytes * (size_t)c->max_batch;
+    const size_t bytes = c->image_bytes * (size_t)c->max_batch, out_bytes = slot_out_image_bytes(c) * (size_t)c->max_batch;
     if (!s.d_in) HIP_TRY(hipMalloc((void **)&s.d_in, bytes));
-    if (!s.d_out) HIP_TRY(hipMalloc((void **)&s.d_out, bytes));
+    if (!s.d_out) HIP_TRY(hipMalloc((void **)&s.d_out, out_bytes));
     return MI_BLUR_OK;
 }
 
@@ -1018,8 +1054,8 @@ static LaunchDesc ctx_launch(const mi_blur_ctx *c, const uint8_t *in, uint8_t *o
 static void count_submit(mi_blur_ctx *c, int n_images, size_t out_bytes, size_t h2d, size_t d2h, bool zero_copy)
 {
     c->tm.bytes_h2d += h2d; c->tm.bytes_d2h += d2h;
-    // the decimating filter reads whole images and writes smaller ones: input + output; every other filter 2 * output
-    c->tm.bytes_alg += c->filter.kind == FilterKind::SEP_DOWN ? (uint64_t)c->image_bytes * (uint64_t)n_images + out_bytes : 2ull * out_bytes;
+    // the decimating filter and the resize read whole images and write images of another size: input + output; every other filter 2 * output
+    c->tm.bytes_alg += own_output_size(c) ? (uint64_t)c->image_bytes * (uint64_t)n_images + out_bytes : 2ull * out_bytes;
     c->tm.images += (uint64_t)n_images;
     c->tm.launches += 1;
     if (zero_copy) c->zero_copy_launches += 1;
@@ -1162,9 +1198,7 @@ static int submit_common(mi_blur_ctx *c, const uint8_t *host_in, uint8_t *host_o
 {
     const size_t pitch = (size_t)c->W * c->C;
     const size_t band_in = pitch * band_rows;
-    const size_t band_out = c->filter.kind == FilterKind::SEP_DOWN      // whole images only: the decimated image
-                                ? (size_t)down_cols(c->W, c->filter.down_sx, c->filter.down_ox) * c->C * (size_t)down_rows(c->H, c->filter.down_sy, c->filter.down_oy)
-                                : pitch * (size_t)(y1 - y0);
+    const size_t band_out = own_output_size(c) ? out_image_bytes(c) : pitch * (size_t)(y1 - y0);   // whole images only: the decimated / resized image
     const HostBatch b{host_in, host_out, band_rows, n_images, y0, y1, band_in, band_out,
                       in_stride ? in_stride : band_in, out_stride ? out_stride : band_out};
     c->submitted = true;
@@ -1221,7 +1255,7 @@ extern "C" int mi_blur_submit_band(mi_blur_ctx *c, const uint8_t *host_in, uint8
                                    int halo_top, int halo_bottom)
 {
     if (!c || !host_in || !host_out || host_in == host_out) return MI_BLUR_ERR_INVALID;
-    if (c->filter.kind == FilterKind::SEP_DOWN) return MI_BLUR_ERR_UNSUPPORTED;   // no band forms: a band's phase depends on where it starts
+    if (own_output_size(c)) return MI_BLUR_ERR_UNSUPPORTED;   // no band forms: a band's phase depends on where it starts
     if (band_rows <= 0 || band_rows > c->H || halo_top < 0 || halo_bottom < 0) return MI_BLUR_ERR_INVALID;
     if (halo_top + halo_bottom >= band_rows) return MI_BLUR_ERR_INVALID;
     return submit_common(c, host_in, host_out, band_rows, 1, halo_top, band_rows - halo_bottom, 0, 0);
@@ -1231,7 +1265,7 @@ extern "C" int mi_blur_submit_bands(mi_blur_ctx *c, const uint8_t *host_in, uint
                                     size_t host_image_stride, int band_rows, int halo_top, int halo_bottom)
 {
     if (!c || !host_in || !host_out || host_in == host_out) return MI_BLUR_ERR_INVALID;
-    if (c->filter.kind == FilterKind::SEP_DOWN) return MI_BLUR_ERR_UNSUPPORTED;
+    if (own_output_size(c)) return MI_BLUR_ERR_UNSUPPORTED;
     if (n_images < 0 || n_images > c->max_batch) return MI_BLUR_ERR_INVALID;
     if (band_rows <= 0 || band_rows > c->H || halo_top < 0 || halo_bottom < 0) return MI_BLUR_ERR_INVALID;
     if (halo_top + halo_bottom >= band_rows) return MI_BLUR_ERR_INVALID;
@@ -1251,7 +1285,7 @@ extern "C" int mi_blur_submit_bands(mi_blur_ctx *c, const uint8_t *host_in, uint
 extern "C" int mi_blur_submit_planar(mi_blur_ctx *c, const uint8_t *host_planar_in, uint8_t *host_out, int n_images, int planar_out)
 {
     if (!c || !host_planar_in || !host_out || host_planar_in == host_out) return MI_BLUR_ERR_INVALID;
-    if (c->filter.kind == FilterKind::SEP_DOWN) return MI_BLUR_ERR_UNSUPPORTED;
+    if (own_output_size(c)) return MI_BLUR_ERR_UNSUPPORTED;
     if (n_images < 0 || n_images > c->max_batch) return MI_BLUR_ERR_INVALID;
     if (n_images == 0) return MI_BLUR_OK;
     const size_t bytes = c->image_bytes * (size_t)n_images;
@@ -1335,6 +1369,17 @@ extern "C" int mi_blur_ctx_set_sep_down(mi_blur_ctx *c, const mi_blur_sep_kernel
     if (c->submitted) return MI_BLUR_ERR_STATE;
     Filter f;
     if (filter_sep_down(k, d, &f) || !down_ok(d, c->W, c->H)) return MI_BLUR_ERR_INVALID;
+    c->filter = f;
+    return MI_BLUR_OK;
+}
+
+// The resize in place of the context's blur, for mi_blur_submit from now on (before the first one only).
+extern "C" int mi_blur_ctx_set_resize(mi_blur_ctx *c, const mi_blur_resize *r)
+{
+    if (!c || !r) return MI_BLUR_ERR_INVALID;
+    if (c->submitted) return MI_BLUR_ERR_STATE;
+    Filter f;
+    if (filter_resize(r, &f) || !resize_ok(r, c->W, c->H, c->C)) return MI_BLUR_ERR_INVALID;
     c->filter = f;
     return MI_BLUR_OK;
 }
@@ -1815,6 +1860,14 @@ extern "C" int mi_blur_cpu_run_sep_down(const uint8_t *in, uint8_t *out, int wid
 {
     Filter f;
     if (filter_sep_down(k, d, &f) || !down_ok(d, width, height)) return MI_BLUR_ERR_INVALID;
+    return cpu_run_filter(f, in, out, width, height, channels, n_images, n_threads);   // cpu_blur_batch takes the output size from f
+}
+
+extern "C" int mi_blur_cpu_run_resize(const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,
+                                      const mi_blur_resize *r, int n_threads)
+{
+    Filter f;
+    if (filter_resize(r, &f) || !resize_ok(r, width, height, channels)) return MI_BLUR_ERR_INVALID;
     return cpu_run_filter(f, in, out, width, height, channels, n_images, n_threads);   // cpu_blur_batch takes the output size from f
 }
 

@@ -68,7 +68,8 @@ int mi_blur_version(void);
  * "blur_fused_kernel", "blur_tiled_loop_kernel", "blur_stream_kernel", "blur_generic_kernel", "blur_sep_tiled_kernel",
  * "blur_sep_generic_kernel", "blur_median_fast_kernel", "blur_median_generic_kernel", "blur_morph_tiled_kernel",
  * "blur_morph_generic_kernel", "blur_bilateral_tiled_kernel", "blur_bilateral_generic_kernel", "blur_conv_tiled_kernel",
- * "blur_conv_generic_kernel", "blur_sep_down_tiled_kernel", "blur_sep_down_generic_kernel"; "" before the first):
+ * "blur_conv_generic_kernel", "blur_sep_down_tiled_kernel", "blur_sep_down_generic_kernel",
+ * "blur_resize_tiled_kernel", "blur_resize_generic_kernel"; "" before the first):
  * reports name the kernel a profiler will show.  Static string, never NULL. */
 const char *mi_blur_last_kernel(void);
 
@@ -186,7 +187,7 @@ typedef struct mi_blur_timing {      /* cumulative since create / last reset; mi
     double d2h_ms;                   /* transfer OUT (time_*_transfer_out) */
     uint64_t bytes_h2d, bytes_d2h;
     uint64_t bytes_alg;              /* algorithmic bytes = 2*W*rows*C per image processed; for a context with
-                                        mi_blur_ctx_set_sep_down: input bytes + output bytes, W*H*C + Wo*Ho*C per image */
+                                        mi_blur_ctx_set_sep_down or mi_blur_ctx_set_resize: input bytes + output bytes, W*H*C + Wo*Ho*C per image */
     uint64_t images;
     uint64_t launches;
 } mi_blur_timing;
@@ -451,6 +452,71 @@ int mi_blur_cpu_run_sep_down(const uint8_t *in, uint8_t *out, int width, int hei
  * band forms (a band's phase would depend on where it starts in the image): mi_blur_submit_band, _bands, _planar and
  * both resident runs return MI_BLUR_ERR_UNSUPPORTED for such a context. */
 int mi_blur_ctx_set_sep_down(mi_blur_ctx *ctx, const mi_blur_sep_kernel *k, const mi_blur_decimation *d);
+
+/* ------------------------------------------------------------------------
+ * Image resize: exact fixed-point bilinear and nearest, any output size (no reference analogue).  The definition is
+ * exact integers; the GPU, the CPU device and a numpy restatement agree byte for byte.
+ *
+ * One axis with n_in input samples and n_out output samples uses pixel centres aligned (half-pixel mapping).  For
+ * output index X:
+ *   num = (2*X + 1) * n_in - n_out          den = 2 * n_out
+ *   i0  = floor(num / den)                  (floor towards minus infinity; i0 >= -1)
+ *   rem = num - i0 * den                    (0 <= rem < den)
+ *   f   = (rem * 2048 + n_out) / den        (0 .. 2048: the fraction rounded to 11 bits)
+ *   a   = clamp(i0, 0, n_in - 1)            b = clamp(i0 + 1, 0, n_in - 1)
+ *
+ * MI_BLUR_RESIZE_BILINEAR, with (xa, xb, fx) from the x axis and (ya, yb, fy) from the y axis, per channel:
+ *   s   = (2048-fy) * ((2048-fx) * in[ya][xa] + fx * in[ya][xb])
+ *       +       fy  * ((2048-fx) * in[yb][xa] + fx * in[yb][xb])
+ *   out = (s + (1 << 21)) >> 22
+ * s is at most 255 * 2^22 and the row blends at most 255 * 2^11, so everything fits in 32 bits unsigned.  The order of
+ * the two passes cannot change the value.  n_out == n_in gives rem = 0, so the launch is an identity.  A constant image
+ * stays constant.  The result differs from real-valued bilinear by less than 0.5 + 2*255/4096 ~ 0.63, so it is never
+ * more than 1 from the exact value rounded half up.
+ *
+ * MI_BLUR_RESIZE_NEAREST: i = ((2*X + 1) * n_in) / den.  This is the input pixel whose cell contains the output
+ * pixel's centre.  It is always in range, so it needs no clamp.
+ *
+ * Valid: 1 <= out_width, out_height; width, height, out_width, out_height each <= MI_BLUR_RESIZE_MAX_DIM = 32768, so
+ * num and rem * 2048 stay inside 32 bits; the per-image byte limits of a launch (W*C <= INT_MAX/2, W*C*H <= INT_MAX)
+ * apply to both the input image and the output image.  Any ratio is valid.
+ * This is NOT OpenCV's INTER_LINEAR bit for bit: the grid and the 11 fraction bits are the same, but the rounding is a
+ * single final one.  A reduction by more than 2x aliases (bilinear reads 2 x 2 input pixels whatever the ratio):
+ * mi_blur_enqueue_sep_down's area_down / pyr_down presets should come first for such reductions.
+ * The output is interleaved and dense: its pitch is Wo*C and images lie Wo*Ho*C bytes apart.
+ * ---------------------------------------------------------------------- */
+#define MI_BLUR_RESIZE_MAX_DIM 32768
+typedef enum mi_blur_resize_mode { MI_BLUR_RESIZE_NEAREST = 0, MI_BLUR_RESIZE_BILINEAR = 1 } mi_blur_resize_mode;
+typedef struct mi_blur_resize { int out_width, out_height, mode; } mi_blur_resize;
+
+/* (a, b, f) of one axis for output index X, through the same function the kernels and the CPU device use; NEAREST
+ * gives i, i, 0.  MI_BLUR_ERR_INVALID: a null pointer, n_in or n_out outside 1..MI_BLUR_RESIZE_MAX_DIM, an unknown mode,
+ * X outside [0, n_out). */
+int mi_blur_resize_coord(int n_in, int n_out, int mode, int X, int *i0, int *i1, int *frac);
+
+/* n_images images of width x height in, n_images images of r->out_width x r->out_height out (device memory,
+ * asynchronous; n_images == 0 is MI_BLUR_OK; image offsets are 64-bit).  Every argument is checked before a device is
+ * asked for: MI_BLUR_ERR_INVALID comes before MI_BLUR_ERR_NO_DEVICE.
+ * blur_resize_tiled_kernel (LDS tile of the input footprint, index tables in LDS, vertical blend, horizontal gather)
+ * takes exactly the launches with BILINEAR mode, 1-4 channels, out_width >= width and out_height >= height
+ * (enlargement or equality on both axes), width*channels and out_width*channels multiples of 16 (input and output
+ * rows are whole 16-byte chunks) and both pointers 16-byte aligned (and, where a context's in-place submit gives image
+ * strides, strides that are multiples of 16; this export's are dense, which they then are); every other launch (NEAREST,
+ * any reduction, 5+ channels, odd rows or pointers) goes to blur_resize_generic_kernel (one output byte per thread).
+ * mi_blur_last_kernel() says which one ran. */
+int mi_blur_enqueue_resize(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int n_images,
+                           const mi_blur_resize *r, void *stream);
+/* The same on the CPU device's threads (synchronous). */
+int mi_blur_cpu_run_resize(const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,
+                           const mi_blur_resize *r, int n_threads);
+/* Give a context (created with the INPUT width, height, channels) the resize, with the rules of
+ * mi_blur_ctx_set_sep_down: only before the first submit (MI_BLUR_ERR_STATE after); it replaces what another setter set
+ * and is replaced by them; the context keeps a copy.  MI_BLUR_ERR_INVALID also when *r is not valid for the context's
+ * size.  mi_blur_submit then writes n_images * Wo*Ho*C bytes to host_out, which may be MORE than it reads: pageable
+ * caller memory, or pinned memory on both sides (in place, one launch per submit, never the batch server), on the GPU
+ * or the CPU device.  mi_blur_submit_band, _bands, _planar and both resident runs return MI_BLUR_ERR_UNSUPPORTED for
+ * such a context. */
+int mi_blur_ctx_set_resize(mi_blur_ctx *ctx, const mi_blur_resize *r);
 
 /* ------------------------------------------------------------------------
  * Median blur, windows 3x3 to 15x15 (no reference analogue).  For a radius r in 1..MI_BLUR_MEDIAN_MAX_RADIUS, with
