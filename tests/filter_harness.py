@@ -1,10 +1,10 @@
-"""What the per-family test files (tests/test_{sep,median,morph,bilateral,conv}_{gpu,host}.py, tests/test_narrow_rows_gpu.py)
-share (not a test module, and not a conftest: fixtures reach a test file by plain import into its namespace).
+"""What the per-family test files (tests/test_{sep,median,morph,bilateral,conv}_{gpu,host}.py, tests/test_narrow_rows_gpu.py,
+tests/test_kernel_proofs_gpu.py, tests/test_large_shapes_gpu.py) share (not a test module, and not a conftest: fixtures reach a test file by plain import into its namespace).
 
 A Family holds what the families differ in: where each export wants the filter spliced into its argument list, the
 Context setter, the kernel names, the vertical halo and the numpy restatement.  A filter value is what those exports take:
-a SepKernel, a median radius, an (op, rx, ry) triple, a Bilateral, a Conv.  gpu_run / cpu_run launch one filter through
-the C ABI; the check_* functions are the bodies the family files had in common.  They take the family, one image and one
+a SepKernel, a median radius, an (op, rx, ry) triple, a Bilateral, a Conv.  gpu_run / dev_run / cpu_run launch one filter
+through the C ABI; the check_* functions are the bodies the family files had in common.  They take the family, one image and one
 filter (a list where a large buffer is shared) and every number the families' copies differed in; the loops over shapes,
 radii and tables, and the seeds, stay in the family files."""
 import ctypes as C
@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import conv_ref as cr
+import kernel_proofs as kp
 from bilateral_ref import ref_bilateral
 from median_ref import ref_median
 from morph_ref import ref_morph
@@ -137,6 +138,29 @@ def gpu_run(family, pkg, L, torch, host, filt, offset_in=0, offset_out=0, y0=Non
     o = d_out.cpu().numpy()
     assert (o[:offset_out] == 0x5A).all() and (o[offset_out + size_out:] == 0x5A).all(), "wrote outside the output"
     return o[offset_out:offset_out + size_out].reshape(n, y1 - y0, w, c)
+
+
+DEV_GUARD = 256
+
+
+def dev_run(family, pkg, L, torch, d_img, filt, y0=None, y1=None):
+    """d_img (N, H, W, C) uint8 on the device -> mi_blur_enqueue_* (or *_band for one image with y0 / y1), the output left
+    on the device: for sweeps of many small launches over one upload.  DEV_GUARD bytes of 0x5A either side of the output."""
+    n, h, w, c = d_img.shape
+    y0 = 0 if y0 is None else y0
+    y1 = h if y1 is None else y1
+    size = n * (y1 - y0) * w * c
+    out = torch.full((size + 2 * DEV_GUARD,), 0x5A, dtype=torch.uint8, device="cuda")
+    s = torch.cuda.current_stream().cuda_stream
+    if y0 == 0 and y1 == h:
+        rc = family.enqueue(L, d_img.data_ptr(), out.data_ptr() + DEV_GUARD, w, h, c, n, filt, s)
+    else:
+        assert n == 1
+        rc = family.enqueue_band(L, d_img.data_ptr(), out.data_ptr() + DEV_GUARD, w, h, c, y0, y1, filt, s)
+    pkg.check(rc, f"mi_blur_enqueue_{family.name}")
+    torch.cuda.synchronize()
+    assert bool((out[:DEV_GUARD] == 0x5A).all()) and bool((out[DEV_GUARD + size:] == 0x5A).all()), "wrote outside the output"
+    return out[DEV_GUARD:DEV_GUARD + size].reshape(n, y1 - y0, w, c)
 
 
 def cpu_run(family, pkg, L, img, filt, n_threads, prefill=True):
@@ -291,6 +315,78 @@ def check_synthetic_stream(family, pkg, L, torch, filters, shape, fill_threads, 
         assert np.array_equal(gpu_run(family, pkg, L, torch, host, filt), want), (family.name, filt)
         if check_kernel:
             assert L.mi_blur_last_kernel().decode() == family.kernel(filt)
+
+
+# ---------------------------------------------------------------- shared bodies: tile geometry of the tiled kernels
+# The sep, morph, bilateral and conv tiled kernels cut a launch into the same tiles (fill_tiles, kernel_common.h): TILE_ROWS
+# output rows x at most TILE_CHUNKS chunk columns, one workgroup each; from 16 workgroups on, the block -> tile remap is on.
+GEOMETRY_CPR = (1, 2, 3, 31, 32, 33, 64, 65, 97)                 # chunks per row, rounded to what whole pixels fill (kp.chunk_cols)
+GEOMETRY_ROWS = (1, 2, 7, 8, 9, 31, 32, 33, 64, 65)
+BAND_H, BAND_CPR = 130, (2, 33)
+BAND_Y0 = (0, 1, 31, 32, 33, 63, 64, 65)
+GRID_BATCHES = ((2, 32, 32), (15, 32, 32), (16, 32, 32), (3, 65, 65), (5, 33, 1), (9, 31, 33))     # (images, rows, chunks per row)
+REMAP_BLOCKS = 16
+
+
+def band_y1(y0, h=BAND_H):
+    return sorted({y0 + 1, 64, 65, 96, 97, h} - set(range(y0 + 1)))
+
+
+def tile_blocks(n, rows, cpr):
+    return n * -(-rows // TILE_ROWS) * -(-cpr // TILE_CHUNKS)
+
+
+def random_bytes(rng, n, h, w, c):
+    return rng.integers(0, 256, size=(n, h, w, c), dtype=np.uint8)
+
+
+def check_tiled_geometry_sweep(family, pkg, L, torch, rng, c, make_image, make_filter, n_edges):
+    """Every chunk count of GEOMETRY_CPR x every row count of GEOMETRY_ROWS for c channels, one image each, through the
+    tiled kernel.  make_filter(q) -> (filter, the kernel's bucket edges it sits on) for the q-th shape: the filter walks
+    its kernel's own edges as the shapes go by, and all n_edges combinations must have occurred."""
+    seen = set()
+    for i, cpr in enumerate(GEOMETRY_CPR):
+        w = kp.chunk_cols(cpr, c) * 16 // c
+        for j, rows in enumerate(GEOMETRY_ROWS):
+            filt, edge = make_filter(i * len(GEOMETRY_ROWS) + j)
+            seen.add(edge)
+            img = make_image(rng, 1, rows, w, c)
+            got = dev_run(family, pkg, L, torch, torch.from_numpy(img).cuda(), filt).cpu().numpy()
+            assert L.mi_blur_last_kernel().decode() == family.fast, (family.name, c, cpr, rows, edge)
+            assert np.array_equal(got, family.ref(img, filt)), (family.name, c, cpr, rows, edge)
+    assert len(seen) == n_edges, (family.name, c, sorted(seen))
+
+
+def check_bands_and_grids(family, pkg, L, torch, rng, make_image, band_filters, grid_filter, channels=(1, 2, 3, 4)):
+    """Bands of one image of BAND_H rows whose y0 / y1 sit on and next to tile boundaries (multiples of TILE_ROWS), on rows
+    of 2 and of 33 chunks, against the same rows of the whole image's restatement; then batches whose grid is below and
+    at or above REMAP_BLOCKS workgroups (the XCD remap off and on), both sides for every channel count.  band_filters:
+    callables rng -> filter, each called once per image, after the image is drawn; grid_filter likewise, per batch."""
+    for c in channels:
+        for cpr in BAND_CPR:
+            w = kp.chunk_cols(cpr, c) * 16 // c
+            img = make_image(rng, 1, BAND_H, w, c)
+            d_img = torch.from_numpy(img).cuda()
+            for make in band_filters:
+                filt = make(rng)
+                whole = family.ref(img, filt)
+                for y0 in BAND_Y0:
+                    for y1 in band_y1(y0):
+                        got = dev_run(family, pkg, L, torch, d_img, filt, y0, y1).cpu().numpy()
+                        assert L.mi_blur_last_kernel().decode() == family.fast
+                        assert np.array_equal(got, whole[:, y0:y1]), (family.name, c, cpr, y0, y1)
+    sides = set()
+    for c in channels:
+        for n, rows, cpr in GRID_BATCHES:
+            w = kp.chunk_cols(cpr, c) * 16 // c
+            nb = tile_blocks(n, rows, kp.chunk_cols(cpr, c))
+            sides.add((c, nb >= REMAP_BLOCKS))
+            img = make_image(rng, n, rows, w, c)
+            filt = grid_filter(rng)
+            got = dev_run(family, pkg, L, torch, torch.from_numpy(img).cuda(), filt).cpu().numpy()
+            assert L.mi_blur_last_kernel().decode() == family.fast
+            assert np.array_equal(got, family.ref(img, filt)), (family.name, c, n, rows, cpr, nb)
+    assert len(sides) == 2 * len(channels)
 
 
 # ---------------------------------------------------------------- shared bodies: CPU-device contexts

@@ -1,5 +1,6 @@
 """Shared by test_kernel_proofs_gpu.py and test_kernel_proofs_host.py (not a test module): the pattern sets that prove the
-median networks by the 0-1 principle, and the numpy restatements of the definitions in include/mi_blur.h (median_ref.py,
+median networks by the 0-1 principle, the check that morph_ref.py's proof images witness every window position of the
+morph kernels (at the end of this file), and the numpy restatements of the definitions in include/mi_blur.h (median_ref.py,
 sep_ref.py) that do not touch the product.
 
 The 0-1 principle: a selection built only from min / max (and byte copies) commutes with every monotone map, so if it is
@@ -196,3 +197,67 @@ def one_hot_cases():
                     for d in range(-rb, rb + 1):
                         for b in (0, 8):
                             yield c, axis, rb, d, b, w, h
+
+
+# ---------------------------------------------------------------- the morph proof: every window position witnessed
+# A composition of minima is the minimum over a set of source positions, so blur_morph_tiled_kernel (van Herk vertically,
+# doubling horizontally) is right iff the set of every output is right.  An image witnesses (position, offset d) when a
+# restatement whose window differs from the true one in offset d alone gives another byte there: d inside [-r, r] is a
+# window one tap short, d = -(r+1) or r+1 one tap long.
+MORPH_PROOF_C = (1, 2, 3, 4)
+MORPH_PROOF_RADII = tuple(range(17))
+MORPH_PROOF_SQUARE = (3, 4, 16)            # (r, r): the straight vertical taps' last radius, van Herk's first, the largest
+
+
+def morph_proof_cases(axis):
+    """(rx, ry) of the proof on axis 2 (horizontal image) or 1 (vertical image): every radius on the proved axis with the
+    other at 0, then the squares."""
+    line = [(r, 0) if axis == 2 else (0, r) for r in MORPH_PROOF_RADII]
+    return line + [(r, r) for r in MORPH_PROOF_SQUARE]
+
+
+def window_qualifies(n, r, d):
+    """Positions 0..n-1 whose source for offset d, clamped, is reached by no other offset of the clamped window [-r, r]:
+    at an image edge several offsets clamp to the same pixel, and those pairs cannot be witnessed by anything."""
+    x = np.arange(n)
+    others = np.array([i for i in range(-r, r + 1) if i != d])
+    src = np.clip(x + d, 0, n - 1)
+    return ~(np.clip(x[:, None] + others[None, :], 0, n - 1) == src[:, None]).any(axis=1)
+
+
+def morph_window_gaps(batch, axis, r):
+    """batch (B, H, W, C) of impulse images, axis 2 (windows along x) or 1 (along y).  For every offset d of -(r+1) .. r+1
+    the mutant's min and max (the window without d, or with d where it lies outside) against the true ones.  Returns the
+    (image, d, position) that qualify and are NOT witnessed by that image alone: position = (x, channel) on axis 2, where
+    some row must differ; = y on axis 1, where some byte of the row must differ.  Running extrema from both ends of the
+    window give every mutant in two passes per tap."""
+    n = batch.shape[axis]
+    gaps = []
+    planes = []
+    for fn in (np.minimum, np.maximum):
+        taps = [shifted(batch, i, axis) for i in range(-r - 1, r + 2)]           # taps[i + r + 1]
+        left, right = [None] * (2 * r + 3), [None] * (2 * r + 3)                 # left[j]: offsets -r .. j - r - 1; right[j]: j - r - 1 .. r
+        for j in range(1, 2 * r + 2):
+            left[j] = taps[j] if j == 1 else fn(left[j - 1], taps[j])
+        for j in range(2 * r + 1, 0, -1):
+            right[j] = taps[j] if j == 2 * r + 1 else fn(right[j + 1], taps[j])
+        true = left[2 * r + 1]
+        assert np.array_equal(true, right[1])
+        mutants = []
+        for j in range(2 * r + 3):
+            if j == 0 or j == 2 * r + 2:
+                mutants.append(fn(true, taps[j]))
+            elif j == 1:
+                mutants.append(right[2])
+            elif j == 2 * r + 1:
+                mutants.append(left[2 * r])
+            else:
+                mutants.append(fn(left[j - 1], right[j + 1]))
+        planes.append((true, mutants))
+    for j, d in enumerate(range(-r - 1, r + 2)):
+        differs = (planes[0][1][j] != planes[0][0]) | (planes[1][1][j] != planes[1][0])
+        seen = differs.any(axis=1) if axis == 2 else differs.any(axis=(2, 3))     # (B, W, C) or (B, H)
+        ok = window_qualifies(n, r, d)
+        missing = ~seen & (ok[None, :, None] if axis == 2 else ok[None, :])
+        gaps += [(d,) + tuple(int(v) for v in m) for m in np.argwhere(missing)[:4]]
+    return gaps

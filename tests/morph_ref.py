@@ -3,7 +3,8 @@ input builders tests/test_morph_host.py and tests/test_morph_gpu.py share (not a
 
 On uniformly random bytes a 33x33 minimum is 0 almost everywhere, so a window one pixel short would pass.  The builders
 therefore make sparse impulses (single pixels of 0 and 255 in ONE channel on a background of 128, more than 33 apart:
-erode / dilate must paint exact rectangles in that channel only), slow ramps, checkerboards and low-amplitude noise."""
+erode / dilate must paint exact rectangles in that channel only), slow ramps, checkerboards and low-amplitude noise.
+None of these witnesses every (byte position, offset) pair at every radius; the proof images at the end of this file do."""
 import numpy as np
 from numpy.lib.stride_tricks import sliding_window_view
 
@@ -23,14 +24,25 @@ def ref_morph_2d(img, op, rx, ry):
     return _finish(win.min(axis=(-2, -1)), win.max(axis=(-2, -1)), op)
 
 
+def _ext_1d(a, r, axis, fn):
+    """fn (np.minimum / np.maximum) over the 2r+1 taps along one axis, edge padding: one vectorised pass per tap."""
+    if r == 0:
+        return a
+    pad = [(0, 0)] * a.ndim
+    pad[axis] = (r, r)
+    p = np.pad(a, pad, mode="edge")
+    n = a.shape[axis]
+    cut = lambda i: p[(slice(None),) * axis + (slice(i, i + n),)]
+    out = cut(0).copy()
+    for i in range(1, 2 * r + 1):
+        fn(out, cut(i), out=out)
+    return out
+
+
 def ref_lo_hi(img, rx, ry):
     """The separable restatement (1-D windows along x, then along y); test_separable_restatement ties it to the 2-D one."""
-    p = np.pad(img, ((0, 0), (0, 0), (rx, rx), (0, 0)), mode="edge")
-    wx = sliding_window_view(p, 2 * rx + 1, axis=2)
-    lo, hi = wx.min(axis=-1), wx.max(axis=-1)
-    lo = sliding_window_view(np.pad(lo, ((0, 0), (ry, ry), (0, 0), (0, 0)), mode="edge"), 2 * ry + 1, axis=1).min(axis=-1)
-    hi = sliding_window_view(np.pad(hi, ((0, 0), (ry, ry), (0, 0), (0, 0)), mode="edge"), 2 * ry + 1, axis=1).max(axis=-1)
-    return lo, hi
+    return (_ext_1d(_ext_1d(img, rx, 2, np.minimum), ry, 1, np.minimum),
+            _ext_1d(_ext_1d(img, rx, 2, np.maximum), ry, 1, np.maximum))
 
 
 def ref_morph(img, op, rx, ry):
@@ -99,3 +111,39 @@ def mixed(rng, n, h, w, c):
     sp = rng.random((n, h, w, c)) < 0.002
     img[sp] = rng.choice(np.array([0, 255], np.uint8), int(sp.sum()))
     return img
+
+
+# ---------------------------------------------------------------- proof images: every window position witnessed
+# min / max compose to the min / max over a SET of source positions, so the kernel is right iff that set is right, and one
+# isolated impulse shows exactly which outputs contain its position.  Impulses PROOF_PERIOD apart: more than 33 + 1, so a
+# window of radius <= 16, and one a tap too long, holds at most one.  kernel_proofs.morph_window_gaps checks that the
+# images witness every (position, offset) pair that anything can witness.
+PROOF_PERIOD = 35
+PROOF_PAIRS = [(0, 128), (255, 128), (127, 128), (128, 127)]     # (impulse, background); the last two: top bits of the 16-bit fields
+PROOF_H_WIDTH = 16 * PROOF_PERIOD                                 # 560 pixels: whole chunks for 1-4 channels, 35 chunks for one
+PROOF_V_SHAPE = (2 * PROOF_PERIOD, 48)                            # 70 rows (two tiles and 6 rows) x 48 pixels (whole chunks for 1-4 channels)
+
+
+def _proof_batch(mask):
+    return np.stack([np.where(mask, np.uint8(v), np.uint8(bg)) for v, bg in PROOF_PAIRS])
+
+
+def proof_horizontal(c, period=PROOF_PERIOD, width=PROOF_H_WIDTH, drop_row=None):
+    """(4, period*c, width, c): row k*c + ch has impulses at the pixels x = k (mod period) in channel ch.  gcd(period, 32)
+    = 1 and width = 16 periods, so the impulses of the rows of one channel pass through every byte of the two chunks a
+    thread of the horizontal pass takes, at every offset, and touch both row ends.  drop_row leaves one row without
+    impulses (for showing that the sufficiency check notices)."""
+    mask = np.zeros((period * c, width, c), bool)
+    for k in range(period):
+        for ch in range(c):
+            mask[k * c + ch, k::period, ch] = k * c + ch != drop_row
+    return _proof_batch(mask)
+
+
+def proof_vertical(c, period=PROOF_PERIOD, shape=PROOF_V_SHAPE):
+    """(4, 70, 48, c): column x has impulses at the rows y = x (mod period), in channel x % c."""
+    h, w = shape
+    mask = np.zeros((h, w, c), bool)
+    for x in range(w):
+        mask[x % period::period, x, x % c] = True
+    return _proof_batch(mask)

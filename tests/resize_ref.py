@@ -28,11 +28,15 @@ def ref_axis(n_in, n_out, mode=BILINEAR):
     return np.clip(i0, 0, n_in - 1), np.clip(i0 + 1, 0, n_in - 1), f
 
 
-def ref_resize(img, wo, ho, mode=BILINEAR):
-    """img (N, H, W, C) uint8 -> (N, ho, wo, C) uint8."""
+def ref_resize(img, wo, ho, mode=BILINEAR, rows=None, first_row=0, height=None):
+    """img (N, H, W, C) uint8 -> (N, ho, wo, C) uint8.  rows = (Y0, Y1): output rows Y0 .. Y1 - 1 only, from a slab: img then
+    holds the rows from first_row on of an image of `height` rows, and must hold the a and b rows of those outputs."""
     n, h, w, c = img.shape
     xa, xb, fx = ref_axis(w, wo, mode)
-    ya, yb, fy = ref_axis(h, ho, mode)
+    ya, yb, fy = ref_axis(h if height is None else height, ho, mode)
+    if rows is not None:
+        ya, yb, fy = (v[rows[0]:rows[1]] for v in (ya - first_row, yb - first_row, fy))
+        assert ya.min() >= 0 and yb.max() < h
     if mode == NEAREST:
         return np.ascontiguousarray(img[:, ya][:, :, xa])
     v = img.astype(np.int64)

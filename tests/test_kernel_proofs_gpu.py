@@ -7,15 +7,25 @@ include/mi_blur.h (kernel_proofs.py), never from the product; every launch also 
   * blur_median_generic_kernel: two-valued images of every adjacent pair (v, v+1) and every (0, v), window counts on K
     and K+1, radius 1..7.
   * blur_sep_tiled_kernel and blur_median_fast_kernel: chunk counts, rows, radius buckets, bands and grids at and next
-    to the tile / wave boundaries; one-hot taps at every offset of every radius bucket."""
-import ctypes as C
+    to the tile / wave boundaries; one-hot taps at every offset of every radius bucket.
+  * blur_morph_tiled_kernel: proved window by window.  min / max compose to the min / max over a set of source
+    positions, so the kernel is right iff that set is right; the proof images (morph_ref.py) hold isolated impulses that
+    witness every (byte position, offset) pair at every radius (test_kernel_proofs_host.py checks that they do).
+  * blur_morph_tiled_kernel, blur_bilateral_tiled_kernel, blur_conv_tiled_kernel: the sep kernel's geometry sweep, bands
+    and grids, each filter walking its own kernel's bucket edges; blur_sep_down_tiled_kernel and blur_resize_tiled_kernel:
+    chunk and row counts around their tiles, every phase, the sizes around 1x, 2x and 3x."""
 import math
 
 import numpy as np
 import pytest
 
+import conv_ref as cr
 import kernel_proofs as kp
-from filter_harness import torch_cuda  # noqa: F401
+import morph_ref as mr
+from filter_harness import (BILATERAL, CONV, MORPH, SEP, check_bands_and_grids, check_tiled_geometry_sweep, dev_run, random_bytes,  # noqa: F401
+                            torch_cuda)
+from resize_ref import gpu_resize_run, ref_resize, takes_tiled
+from sep_down_ref import gpu_down_run
 
 pytestmark = pytest.mark.gpu
 
@@ -51,22 +61,7 @@ def median_dev(pkg, L, torch, d_img, r, y0=None, y1=None, offset_in=0):
 
 
 def sep_dev(pkg, L, torch, d_img, wx, wy, y0=None, y1=None):
-    n, h, w, c = d_img.shape
-    k = pkg.SepKernel.from_taps(wx, wy)
-    y0 = 0 if y0 is None else y0
-    y1 = h if y1 is None else y1
-    size = n * (y1 - y0) * w * c
-    out = torch.full((size + 2 * GUARD,), 0x5A, dtype=torch.uint8, device="cuda")
-    s = torch.cuda.current_stream().cuda_stream
-    if y0 == 0 and y1 == h:
-        rc = L.mi_blur_enqueue_sep(d_img.data_ptr(), out.data_ptr() + GUARD, w, h, c, n, C.byref(k), s)
-    else:
-        assert n == 1
-        rc = L.mi_blur_enqueue_sep_band(d_img.data_ptr(), out.data_ptr() + GUARD, w, h, c, y0, y1, C.byref(k), s)
-    pkg.check(rc, "mi_blur_enqueue_sep")
-    torch.cuda.synchronize()
-    assert bool((out[:GUARD] == 0x5A).all()) and bool((out[GUARD + size:] == 0x5A).all()), "wrote outside the output"
-    return out[GUARD:GUARD + size].reshape(n, y1 - y0, w, c)
+    return dev_run(SEP, pkg, L, torch, d_img, pkg.SepKernel.from_taps(wx, wy), y0, y1)
 
 
 def assert_same(torch, got, want, what):
@@ -207,42 +202,15 @@ def test_sep_tiled_geometry_sweep(pkg, L, torch_cuda):
         assert len(seen) == 24, c
 
 
-def sep_nblocks(n, rows, cpr):
-    nstrips = (cpr + 31) // 32
-    return n * ((rows + 31) // 32) * nstrips
+def sep_taps(pkg, rx, ry):
+    return lambda rng: pkg.SepKernel.from_taps(kp.rand_taps(rng, rx, 8), kp.rand_taps(rng, ry, 8))
 
 
 def test_sep_tiled_bands_and_grids(pkg, L, torch_cuda):
     """Bands whose y0 / y1 sit on and next to tile boundaries (multiples of 32); batches whose grid is below and at or
     above 16 blocks (the XCD remap off and on)."""
-    torch = torch_cuda
-    rng = np.random.default_rng(32)
-    h = 130
-    for c in range(1, 5):
-        for cpr in (2, 33):
-            w = kp.chunk_cols(cpr, c) * 16 // c
-            img = rng.integers(0, 256, size=(1, h, w, c), dtype=np.uint8)
-            d_img = torch.from_numpy(img).cuda()
-            for rx, ry in ((1, 16), (8, 3), (16, 9)):
-                wx, wy = kp.rand_taps(rng, rx, 8), kp.rand_taps(rng, ry, 8)
-                whole = kp.ref_sep(img, wx, wy)
-                for y0 in (0, 1, 31, 32, 33, 63, 64, 65):
-                    for y1 in sorted({y0 + 1, 64, 65, 96, 97, h} - set(range(y0 + 1))):
-                        got = sep_dev(pkg, L, torch, d_img, wx, wy, y0, y1).cpu().numpy()
-                        assert L.mi_blur_last_kernel() == TILED
-                        assert np.array_equal(got, whole[:, y0:y1]), (c, cpr, rx, ry, y0, y1)
-    sides = set()
-    for c in range(1, 5):
-        for n, rows, cpr in ((2, 32, 32), (15, 32, 32), (16, 32, 32), (3, 65, 65), (5, 33, 1), (9, 31, 33)):
-            w = kp.chunk_cols(cpr, c) * 16 // c
-            nb = sep_nblocks(n, rows, kp.chunk_cols(cpr, c))
-            sides.add((c, nb >= 16))
-            img = rng.integers(0, 256, size=(n, rows, w, c), dtype=np.uint8)
-            wx, wy = kp.rand_taps(rng, 5, 8), kp.rand_taps(rng, 4, 8)
-            got = sep_dev(pkg, L, torch, torch.from_numpy(img).cuda(), wx, wy).cpu().numpy()
-            assert L.mi_blur_last_kernel() == TILED
-            assert np.array_equal(got, kp.ref_sep(img, wx, wy)), (c, n, rows, cpr, nb)
-    assert len(sides) == 8
+    check_bands_and_grids(SEP, pkg, L, torch_cuda, np.random.default_rng(32), random_bytes,
+                          [sep_taps(pkg, rx, ry) for rx, ry in ((1, 16), (8, 3), (16, 9))], sep_taps(pkg, 5, 4))
 
 
 def test_sep_tiled_one_hot_taps(pkg, L, torch_cuda):
@@ -314,3 +282,159 @@ def test_median_fast_bands(pkg, L, torch_cuda):
                         got = median_dev(pkg, L, torch, d_img, r, y0, y1).cpu().numpy()
                         assert L.mi_blur_last_kernel() == FAST, (r, c, y0, y1)
                         assert np.array_equal(got, whole[:, y0:y1]), (r, c, cpr, y0, y1)
+
+
+# ---------------------------------------------------------------- the morph proof (window positions)
+def test_morph_tiled_proof_every_window_position(pkg, L, torch_cuda):
+    """The proof images at every radius 0..16 on the proved axis (the other at 0), then (3, 3), (4, 4) and (16, 16), for
+    1..4 channels and all three ops: an output whose window lacked a source byte, or held one too many, at any byte
+    position of the horizontal pass's two chunks or any row of the vertical pass's group, differs from the restatement."""
+    torch = torch_cuda
+    for axis in (2, 1):
+        for c in kp.MORPH_PROOF_C:
+            img = mr.proof_horizontal(c) if axis == 2 else mr.proof_vertical(c)
+            d_img = torch.from_numpy(img).cuda()
+            for rx, ry in kp.morph_proof_cases(axis):
+                lo, hi = (torch.from_numpy(a).cuda() for a in mr.ref_lo_hi(img, rx, ry))
+                for op, want in ((mr.ERODE, lo), (mr.DILATE, hi), (mr.GRADIENT, hi - lo)):
+                    got = dev_run(MORPH, pkg, L, torch, d_img, (op, rx, ry))
+                    assert L.mi_blur_last_kernel().decode() == MORPH.fast, (axis, c, op, rx, ry)
+                    assert_same(torch, got, want, f"morph axis={axis} C={c} op={op} rx={rx} ry={ry}")
+
+
+# ---------------------------------------------------------------- morph, bilateral, conv: geometry, bands, grids
+MORPH_RX = (0, 1, 4, 5, 8, 11, 16)        # morph_hc(C, rx) = ceil(rx C / 16), at least 1, changes along this list for every C > 1
+MORPH_RY = (0, 3, 4, 16)                  # straight taps up to 3, van Herk from 4
+CONV_RY = (0, 1, 7)
+
+
+def morph_filter(q):
+    rx, ry = MORPH_RX[q % 7], MORPH_RY[(q // 7) % 4]
+    return (mr.OPS[q % 3], rx, ry), (rx, ry)
+
+
+def bilateral_filter(pkg):
+    def make(q):
+        r = 1 + q % 8
+        return pkg.Bilateral.gauss(0.0, 10.0 + 5.0 * (q % 7), r), r
+    return make
+
+
+def conv_filter(pkg, rng):
+    def make(q):
+        rx, ry = q % 8, CONV_RY[(q // 8) % 3]                      # rx 0..7: all five column classes of blur_conv_tiled_kernel
+        return cr.make_kernel(pkg, **cr.random_kernel(rng, rx, ry, mode=cr.MODES[q % 3])), (rx, ry)
+    return make
+
+
+@pytest.mark.parametrize("c", [1, 2, 3, 4])
+def test_morph_tiled_geometry_sweep(pkg, L, torch_cuda, c):
+    check_tiled_geometry_sweep(MORPH, pkg, L, torch_cuda, np.random.default_rng(50 + c), c, mr.mixed, morph_filter, 28)
+
+
+@pytest.mark.parametrize("c", [1, 2, 3, 4])
+def test_bilateral_tiled_geometry_sweep(pkg, L, torch_cuda, c):
+    check_tiled_geometry_sweep(BILATERAL, pkg, L, torch_cuda, np.random.default_rng(60 + c), c, random_bytes, bilateral_filter(pkg), 8)
+
+
+@pytest.mark.parametrize("c", [1, 2, 3, 4])
+def test_conv_tiled_geometry_sweep(pkg, L, torch_cuda, c):
+    rng = np.random.default_rng(70 + c)
+    check_tiled_geometry_sweep(CONV, pkg, L, torch_cuda, rng, c, random_bytes, conv_filter(pkg, rng), 24)
+
+
+def test_morph_tiled_bands_and_grids(pkg, L, torch_cuda):
+    check_bands_and_grids(MORPH, pkg, L, torch_cuda, np.random.default_rng(51), mr.mixed,
+                          [lambda rng, f=f: f for f in ((mr.ERODE, 1, 16), (mr.DILATE, 8, 3), (mr.GRADIENT, 16, 9))],
+                          lambda rng: (mr.GRADIENT, 5, 4))
+
+
+@pytest.mark.parametrize("c", [1, 2, 3, 4])
+def test_bilateral_tiled_bands_and_grids(pkg, L, torch_cuda, c):
+    check_bands_and_grids(BILATERAL, pkg, L, torch_cuda, np.random.default_rng(61 + c), random_bytes,
+                          [lambda rng, r=r: pkg.Bilateral.gauss(0.0, 25.0, r) for r in (1, 8)],
+                          lambda rng: pkg.Bilateral.gauss(0.0, 25.0, 2), channels=(c,))
+
+
+def test_conv_tiled_bands_and_grids(pkg, L, torch_cuda):
+    def conv(rx, ry, mode):
+        return lambda rng: cr.make_kernel(pkg, **cr.random_kernel(rng, rx, ry, mode=mode))
+    check_bands_and_grids(CONV, pkg, L, torch_cuda, np.random.default_rng(71), random_bytes,
+                          [conv(1, 7, "sat"), conv(7, 1, "mag"), conv(4, 3, "abs")], conv(2, 2, "sat"))
+
+
+# ---------------------------------------------------------------- sep_down: geometry
+DOWN_PAIRS = (1, 2, 3, 15, 16, 17, 32, 33, 49)                    # input chunk PAIRS per row: an output row is that many chunks
+DOWN_RX = (0, 4, 5, 8, 9, 16)                                     # blur_sep_down_tiled_kernel's radius buckets RB
+DOWN_RY = (0, 1, 8, 16)
+DOWN_TILED = "blur_sep_down_tiled_kernel"
+
+
+def test_sep_down_tiled_geometry_sweep(pkg, L, torch_cuda):
+    """Every input chunk-pair count (whole groups of three pairs for 3 channels) x every input row count for 1..4
+    channels; the four phases cycle and (rx, ry) walk through all 24 bucket-edge pairs."""
+    rng = np.random.default_rng(81)
+    for c in range(1, 5):
+        seen, phases = set(), set()
+        for i, pairs in enumerate(DOWN_PAIRS):
+            pairs = max(3, int(round(pairs / 3)) * 3) if c == 3 else pairs
+            w = pairs * 32 // c
+            for j, rows in enumerate(SEP_ROWS):
+                q = i * len(SEP_ROWS) + j
+                rx, ry = DOWN_RX[q % 6], DOWN_RY[(q // 6) % 4]
+                ox, oy = (i + j) % 2, ((i + j) // 2 % 2 if rows > 1 else 0)        # oy < H: the output is never empty
+                seen.add((rx, ry))
+                phases.add((4 if rx <= 4 else 8 if rx <= 8 else 16, ox, oy))
+                wx, wy = kp.rand_taps(rng, rx, int(rng.integers(0, 9))), kp.rand_taps(rng, ry, int(rng.integers(0, 9)))
+                img = rng.integers(0, 256, size=(1, rows, w, c), dtype=np.uint8)
+                got = gpu_down_run(pkg, L, torch_cuda, img, pkg.SepKernel.from_taps(wx, wy), (2, 2, ox, oy))
+                assert L.mi_blur_last_kernel().decode() == DOWN_TILED, (c, pairs, rows)
+                assert np.array_equal(got, kp.ref_sep(img, wx, wy)[:, oy::2, ox::2]), (c, pairs, rows, rx, ry, ox, oy)
+        assert len(seen) == 24 and len(phases) == 12, c                   # every bucket-edge pair; every phase in every bucket
+
+
+# ---------------------------------------------------------------- resize: geometry
+RESIZE_CI = (1, 2, 3, 31, 32, 33)                                 # input chunks per row
+RESIZE_H = (1, 2, 31, 32, 33)
+RESIZE_TILED = "blur_resize_tiled_kernel"
+
+
+def resize_x_cases(c):
+    """(input chunks, output chunks): each input count with the counts at and next to 1x, 2x, 3x and 97, kept where the
+    output row is at least as wide as the input row (after rounding both to what whole pixels of c channels fill)."""
+    out = []
+    for ci in RESIZE_CI:
+        a = kp.chunk_cols(ci, c)
+        for co in (ci, ci + 1, 2 * ci - 1, 2 * ci, 2 * ci + 1, 3 * ci + 1, 97):
+            b = kp.chunk_cols(co, c)
+            if b >= a and (a, b) not in out:
+                out.append((a, b))
+    return out
+
+
+def resize_y_cases():
+    out = []
+    for h in RESIZE_H:
+        for ho in (h, h + 1, 2 * h - 1, 2 * h, 2 * h + 1, 32 * h + 1):
+            if ho >= h and (h, ho) not in out:
+                out.append((h, ho))
+    return out
+
+
+@pytest.mark.parametrize("c", [1, 2, 3, 4])
+def test_resize_tiled_geometry_sweep(pkg, L, torch_cuda, c):
+    """The x cases and the y cases paired cyclically (every one of either list occurs), through the tiled kernel."""
+    rng = np.random.default_rng(90 + c)
+    xs, ys = resize_x_cases(c), resize_y_cases()
+    used_x, used_y = set(), set()
+    for k in range(max(len(xs), len(ys))):
+        (ci, co), (h, ho) = xs[k % len(xs)], ys[(k + c) % len(ys)]
+        used_x.add((ci, co))
+        used_y.add((h, ho))
+        w, wo = ci * 16 // c, co * 16 // c
+        img = rng.integers(0, 256, size=(1, h, w, c), dtype=np.uint8)
+        assert takes_tiled(img.shape, wo, ho), (c, ci, co, h, ho)
+        got = gpu_resize_run(pkg, L, torch_cuda, img, wo, ho)
+        assert L.mi_blur_last_kernel().decode() == RESIZE_TILED, (c, ci, co, h, ho)
+        assert np.array_equal(got, ref_resize(img, wo, ho)), (c, ci, co, h, ho)
+    assert len(used_x) == len(xs) and len(used_y) == len(ys)

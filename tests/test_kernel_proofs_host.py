@@ -1,13 +1,18 @@
 """CPU-only half of the kernel proofs (see kernel_proofs.py): the de Bruijn generator the median proof rests on, and the
 CPU device (mi_blur_cpu_run_median, mi_blur_cpu_run_sep) on the same pattern sets and one-hot taps as the GPU module.
 The CPU median is a sliding histogram, not a min / max network, so for it these are coverage tests, not a proof; they
-tie both devices to one definition, and the count reference to an implementation other than the GPU's."""
+tie both devices to one definition, and the count reference to an implementation other than the GPU's.
+
+The morph proof (kernel_proofs.py, morph_ref.py): that the proof images witness every window position anything can
+witness, that the check notices weakened images, and the CPU device on the same images."""
 import ctypes as C
 import os
 
 import numpy as np
 
 import kernel_proofs as kp
+import morph_ref as mr
+from filter_harness import MORPH, cpu_run
 
 N_THREADS = min(16, os.cpu_count() or 1)
 
@@ -118,3 +123,52 @@ def test_cpu_sep_one_hot_taps(pkg, L):
         want = kp.shifted(img, d, axis)
         assert np.array_equal(want, kp.ref_sep(img, wx, wy)), (c, axis, rb, d, b)
         assert np.array_equal(out, want), (c, axis, rb, d, b, w)
+
+
+# ---------------------------------------------------------------- the morph proof images
+def proof_image(axis, c, **kw):
+    return mr.proof_horizontal(c, **kw) if axis == 2 else mr.proof_vertical(c, **kw)
+
+
+def test_morph_proof_images_witness_every_window_position():
+    """Each of the four value pairs on its own: a window without offset d, for every d of [-r, r], and a window with the
+    tap r+1 or -(r+1) added, differs from the true one at every byte column (horizontal image) or row (vertical image)
+    whose clamped source for d no other offset of the window reaches.  That is the only exclusion."""
+    for axis in (2, 1):
+        for c in kp.MORPH_PROOF_C:
+            img = proof_image(axis, c)
+            assert img.shape[1:] == ((mr.PROOF_PERIOD * c, mr.PROOF_H_WIDTH, c) if axis == 2 else mr.PROOF_V_SHAPE + (c,))
+            assert img.shape[2] * c % 16 == 0 and len(img) == len(mr.PROOF_PAIRS)
+            for r in (1, 4, 16):
+                assert kp.morph_window_gaps(img, axis, r) == [], (axis, c, r)
+
+
+def test_morph_sufficiency_check_notices_weakened_images():
+    """One row of the horizontal image without its impulses, and a period of 33 (a window of 33 then always holds an
+    impulse, so a tap too many shows nowhere), on either image: the check reports gaps."""
+    for c in (1, 3):
+        gaps = kp.morph_window_gaps(mr.proof_horizontal(c, drop_row=5 * c), 2, 16)
+        assert {d for d, *_ in gaps} == set(range(-17, 18)), c                # every offset has a column whose witness was that row
+        for axis in (2, 1):
+            gaps = kp.morph_window_gaps(proof_image(axis, c, period=33), axis, 16)
+            assert gaps and {d for d, *_ in gaps} == {-17, 17}, (axis, c)
+
+
+def test_window_qualifies_excludes_only_clamped_duplicates():
+    assert kp.window_qualifies(10, 2, -2).tolist() == [False, False] + [True] * 8     # x = 0, 1: offset -1 clamps to pixel 0 as well
+    assert kp.window_qualifies(10, 2, 0).tolist() == [False] + [True] * 8 + [False]   # at either end the centre is also a clamped tap
+    assert kp.window_qualifies(10, 2, 3).tolist() == [True] * 7 + [False] * 3         # a tap too many: pixel 9 is already the window's from x = 7 on
+    assert kp.window_qualifies(3, 16, 5).tolist() == [False] * 3                      # a row narrower than the window: every source is shared
+
+
+def test_cpu_morph_on_the_proof_images(pkg, L):
+    """mi_blur_cpu_run_morph on both images: every radius 0..16 on the proved axis with the other at 0, all three ops."""
+    for axis in (2, 1):
+        for c in kp.MORPH_PROOF_C:
+            img = proof_image(axis, c)
+            for r in kp.MORPH_PROOF_RADII:
+                rx, ry = (r, 0) if axis == 2 else (0, r)
+                lo, hi = mr.ref_lo_hi(img, rx, ry)
+                for op in mr.OPS:
+                    got = cpu_run(MORPH, pkg, L, img, (op, rx, ry), N_THREADS)
+                    assert np.array_equal(got, mr._finish(lo, hi, op)), (axis, c, op, rx, ry)

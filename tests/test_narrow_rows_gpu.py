@@ -1,12 +1,16 @@
 """Rows narrower than the halo on a real MI355X (-m gpu): the one corner of the tile staging the sep, morph, bilateral
 and conv kernels share (stage_tile, kernel_common.h) that the tile-edge sweeps of their own test files do not reach.
 With 1-3 chunks per row the only strip has halo chunks outside the row on BOTH sides, and the x-clamp fills them from
-a row that is the whole tile.  Byte for byte against the library's CPU device."""
+a row that is the whole tile.  Byte for byte against the library's CPU device.
+
+blur_sep_down_tiled_kernel stages with the same stager and needs rows of whole chunk pairs: its narrowest rows are one and
+two pairs wide, with up to 4 halo chunks outside the row on both sides at the largest radius."""
 import numpy as np
 import pytest
 
 import conv_ref as cr
 from filter_harness import BILATERAL, CONV, MORPH, SEP, cpu_run, gpu_run, torch_cuda  # noqa: F401
+from sep_down_ref import cpu_down_run, gpu_down_run
 from sep_ref import rand_taps
 
 pytestmark = pytest.mark.gpu
@@ -53,3 +57,28 @@ def test_rows_narrower_than_the_halo(pkg, L, torch_cuda, images, family, r):
             got = gpu_run(fam, pkg, L, torch_cuda, img.copy(), filt, offset_out=64)     # 64 guard bytes either side
             assert L.mi_blur_last_kernel().decode() == fam.fast, (w, c, h)
             assert np.array_equal(got, want), (w, c, h)
+
+
+DOWN_ROWS = [(32, 1), (16, 2), (8, 4), (16, 4), (32, 3)]         # (w, c): 2, 2, 2, 4 and 6 chunks per row (3 channels: one group of three pairs)
+DOWN_HEIGHTS = (1, 2, 33)
+
+
+@pytest.mark.parametrize("r", [1, 16])
+def test_sep_down_rows_narrower_than_the_halo(pkg, L, torch_cuda, r):
+    """Stride 2 x 2 at all four phases (one-row images: oy = 0 only, the output is never empty)."""
+    rng = np.random.default_rng(2000 + r)
+    k = pkg.SepKernel.from_taps(rand_taps(rng, r), rand_taps(rng, r))
+    for w, c in DOWN_ROWS:
+        assert w * c % 32 == 0 and w * c // 16 <= 6
+        for h in DOWN_HEIGHTS:
+            img = rng.integers(0, 256, size=(N, h, w, c), dtype=np.uint8)
+            flip = (np.arange(N)[:, None] + np.arange(h)[None, :]) % 2 == 1
+            img[:, :, 0, :] = np.where(flip, 255, 0)[:, :, None]
+            img[:, :, -1, :] = np.where(flip, 0, 255)[:, :, None]
+            for ox in (0, 1):
+                for oy in (0, 1) if h > 1 else (0,):
+                    dec = (2, 2, ox, oy)
+                    want = cpu_down_run(pkg, L, img, k, dec, 8)
+                    got = gpu_down_run(pkg, L, torch_cuda, img, k, dec, offset_out=64)       # 64 guard bytes either side
+                    assert L.mi_blur_last_kernel().decode() == "blur_sep_down_tiled_kernel", (w, c, h, dec)
+                    assert np.array_equal(got, want), (w, c, h, dec)
