@@ -58,8 +58,8 @@ def _newer(target: str, sources: list[str]) -> bool:
 
 def build_native(force: bool = False, verbose: bool = False) -> str:
     """Compile libmi_blur.so (hipcc, --offload-arch=gfx950) and the C++ hosts, in-tree."""
-    srcs = [os.path.join(CSRC, f) for f in ("blur_kernels.hip", "sep_kernels.hip", "median_kernels.hip", "morph_kernels.hip", "bilateral_kernels.hip", "conv_kernels.hip", "sep_down_kernels.hip", "resize_kernels.hip", "layout_kernels.hip", "mi_blur_api.cpp", "cpu_device.cpp")]
-    deps = srcs + [os.path.join(CSRC, f) for f in ("blur_launch.h", "kernel_common.h", "cpu_device.h", "filter.h")] + [HEADER]
+    srcs = [os.path.join(CSRC, f) for f in ("blur_kernels.hip", "sep_kernels.hip", "median_kernels.hip", "morph_kernels.hip", "bilateral_kernels.hip", "conv_kernels.hip", "sep_down_kernels.hip", "resize_kernels.hip", "layout_kernels.hip", "mi_blur_api.cpp", "comm_api.cpp", "cpu_device.cpp")]
+    deps = srcs + [os.path.join(CSRC, f) for f in ("api_internal.h", "blur_launch.h", "kernel_common.h", "cpu_device.h", "filter.h")] + [HEADER]
     if force or not _newer(LIB_PATH, deps):
         cmd = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra",
                "-o", LIB_PATH] + srcs + ["-ldl", "-lpthread"]
@@ -584,26 +584,27 @@ def _images(images, name: str):
     return a
 
 
-def _filter_images(a, radius: int, device: int, batch: int, configure=None):
-    """The numpy driver of blur, gaussian_blur, median_blur, the morphology functions, bilateral_filter and the convolutions: a (from _images) through mi_blur_create (radius) /
-    configure(ctx) / mi_blur_submit / mi_blur_sync.  Returns the output as (N, H, W, C)."""
+def _filter_images(a, radius: int, device: int, batch: int, configure=None, out_size=None):
+    """The numpy driver of every filter function: a (from _images) through mi_blur_create (radius) / configure(ctx) /
+    mi_blur_submit / mi_blur_sync.  Returns the output as (N, H, W, C), or as (N, Ho, Wo, C) for a filter whose output
+    has a size of its own: out_size = (Ho, Wo)."""
     import numpy as np
     if a.ndim == 2:
         a = a[None, :, :, None]
     elif a.ndim == 3:
         a = a[None]
     n, h, w, c = a.shape
-    out = np.empty_like(a)
+    ho, wo = out_size or (h, w)
+    out = np.empty((n, ho, wo, c), dtype=np.uint8)
     if n == 0 or a.size == 0:
         return out
     per = min(n, batch if batch > 0 else 4096)
-    isz = h * w * c
+    isz, osz = h * w * c, ho * wo * c
     with Context(device, w, h, c, radius, max_batch=per, n_slots=2) as ctx:
         if configure:
             configure(ctx)
         for i in range(0, n, per):
-            m = min(per, n - i)
-            ctx.submit(a.ctypes.data + i * isz, out.ctypes.data + i * isz, m)
+            ctx.submit(a.ctypes.data + i * isz, out.ctypes.data + i * osz, min(per, n - i))
         ctx.sync()
     return out
 
@@ -752,10 +753,8 @@ def decimated_size(w: int, h: int, sx: int = 2, sy: int = 2, ox: int = 0, oy: in
 
 
 def _down_images(a, kernel: "SepKernel", d: "Decimation", device: int, batch: int):
-    """The numpy driver of sep_down, pyr_down and area_down: _filter_images for a filter whose output is smaller than its
-    input.  a (from _images) through mi_blur_create / mi_blur_ctx_set_sep_down / mi_blur_submit / mi_blur_sync; returns
-    the output with the rank of a and the decimated H and W."""
-    import numpy as np
+    """The numpy driver of sep_down, pyr_down and area_down: a (from _images) through _filter_images with
+    mi_blur_ctx_set_sep_down; returns the output with the rank of a and the decimated H and W."""
     rank = a.ndim
     if rank == 2:
         a = a[None, :, :, None]
@@ -765,15 +764,7 @@ def _down_images(a, kernel: "SepKernel", d: "Decimation", device: int, batch: in
     if h == 0 or w == 0 or c == 0:
         raise ValueError("decimating filters: images must not be empty")
     wo, ho = decimated_size(w, h, d.sx, d.sy, d.ox, d.oy)
-    out = np.empty((n, ho, wo, c), dtype=np.uint8)
-    if n:
-        per = min(n, batch if batch > 0 else 4096)
-        isz, osz = h * w * c, ho * wo * c
-        with Context(device, w, h, c, 1, max_batch=per, n_slots=2) as ctx:
-            ctx.set_sep_down(kernel, d.sx, d.sy, d.ox, d.oy)
-            for i in range(0, n, per):
-                ctx.submit(a.ctypes.data + i * isz, out.ctypes.data + i * osz, min(per, n - i))
-            ctx.sync()
+    out = _filter_images(a, 1, device, batch, lambda ctx: ctx.set_sep_down(kernel, d.sx, d.sy, d.ox, d.oy), (ho, wo))
     return out[0, :, :, 0] if rank == 2 else out[0] if rank == 3 else out
 
 
@@ -822,7 +813,6 @@ def resize(images, size, mode="bilinear", device: int = 0, batch: int = 0):
     images: (H, W), (H, W, C) or (N, H, W, C) uint8; the result has the same rank with out_height and out_width.
     device: HIP ordinal, or DEVICE_CPU.  A reduction by more than 2x aliases: area_down / pyr_down first.  Goes through
     mi_blur_create / mi_blur_ctx_set_resize / mi_blur_submit / mi_blur_sync."""
-    import numpy as np
     a = _images(images, "resize")
     wo, ho = int(size[0]), int(size[1])
     m = _resize_mode(mode)
@@ -836,13 +826,5 @@ def resize(images, size, mode="bilinear", device: int = 0, batch: int = 0):
         raise ValueError("resize: images must not be empty")
     if wo < 1 or ho < 1:
         raise ValueError("resize: size is (out_width, out_height), both at least 1")
-    out = np.empty((n, ho, wo, c), dtype=np.uint8)
-    if n:
-        per = min(n, batch if batch > 0 else 4096)
-        isz, osz = h * w * c, ho * wo * c
-        with Context(device, w, h, c, 1, max_batch=per, n_slots=2) as ctx:
-            ctx.set_resize(wo, ho, m)
-            for i in range(0, n, per):
-                ctx.submit(a.ctypes.data + i * isz, out.ctypes.data + i * osz, min(per, n - i))
-            ctx.sync()
+    out = _filter_images(a, 1, device, batch, lambda ctx: ctx.set_resize(wo, ho, m), (ho, wo))
     return out[0, :, :, 0] if rank == 2 else out[0] if rank == 3 else out

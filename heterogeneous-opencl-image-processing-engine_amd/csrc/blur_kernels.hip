@@ -1578,19 +1578,11 @@ static int launch_generic(const LaunchDesc &d)
     return dispatch<1, 2>(d.filter->radius, [&](auto R) { return do_launch(blur_generic_kernel<R>, byte_grid(p.total), dim3(256), 0, d, p); });
 }
 
-int launch(const LaunchDesc &d)
+static int launch_box(const LaunchDesc &d)
 {
-    if (!d.filter) return MI_BLUR_ERR_INVALID;
-    if (d.filter->kind == FilterKind::SEP) return launch_sep(d);
-    if (d.filter->kind == FilterKind::MEDIAN) return launch_median(d);
-    if (d.filter->kind == FilterKind::MORPH) return launch_morph(d);
-    if (d.filter->kind == FilterKind::BILATERAL) return launch_bilateral(d);
-    if (d.filter->kind == FilterKind::CONV) return launch_conv(d);
-    if (d.filter->kind == FilterKind::SEP_DOWN) return launch_sep_down(d);
-    if (d.filter->kind == FilterKind::RESIZE) return launch_resize(d);
     if (const int st = check_desc(d, FilterKind::BOX)) return st;
     if (d.filter->radius != 1 && d.filter->radius != 2) return MI_BLUR_ERR_INVALID;
-    if (d.n_images == 0) return MI_BLUR_OK;           // before the strides are looked at (launch_sep / launch_median / launch_morph / launch_bilateral / launch_conv: after)
+    if (d.n_images == 0) return MI_BLUR_OK;           // before the strides are looked at (launch_checks(): after)
     const Tunables tun = tunables();                  // one coherent set of knobs for this launch
     const bool wide = wide_channels(d.channels, d.filter->radius);
     const long long row_bytes = (long long)d.width * d.channels;
@@ -1633,6 +1625,23 @@ int launch(const LaunchDesc &d)
     case MI_BLUR_VARIANT_TILED: return can_tile ? launch_tiled(d, tun) : can_rag ? launch_tiled(d, tun, true) : MI_BLUR_ERR_INVALID;
     case MI_BLUR_VARIANT_STREAM: return (can_tile && !wide) ? launch_stream(d, tun) : MI_BLUR_ERR_INVALID;
     case MI_BLUR_VARIANT_DIRECT: return (can_tile && !wide && direct_fits(d)) ? launch_direct(d, tun) : MI_BLUR_ERR_INVALID;
+    }
+    return MI_BLUR_ERR_INVALID;
+}
+
+// No default label: a FilterKind without a case is a -Wswitch warning of the build.
+int launch(const LaunchDesc &d)
+{
+    if (!d.filter) return MI_BLUR_ERR_INVALID;
+    switch (d.filter->kind) {
+    case FilterKind::BOX: return launch_box(d);
+    case FilterKind::SEP: return launch_sep(d);
+    case FilterKind::MEDIAN: return launch_median(d);
+    case FilterKind::MORPH: return launch_morph(d);
+    case FilterKind::BILATERAL: return launch_bilateral(d);
+    case FilterKind::CONV: return launch_conv(d);
+    case FilterKind::SEP_DOWN: return launch_sep_down(d);
+    case FilterKind::RESIZE: return launch_resize(d);
     }
     return MI_BLUR_ERR_INVALID;
 }

@@ -1,5 +1,5 @@
-// blur_launch.h — internal (not part of the C ABI): launch interface between
-// mi_blur_api.cpp and the gfx950 kernels in the nine .hip files (what those share among themselves: kernel_common.h).
+// blur_launch.h — internal (not part of the C ABI): launch interface between the files that implement the C ABI
+// (mi_blur_api.cpp, comm_api.cpp) and the gfx950 kernels in the .hip files (what those share among themselves: kernel_common.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -27,9 +27,8 @@ struct LaunchDesc {
     hipEvent_t start, stop; // optional: dispatch start/stop timestamps (hipExtLaunchKernel)
 };
 
-// Returns MI_BLUR_OK or a negative mi_blur_status.  A SEP filter is handed to launch_sep, a MEDIAN one to launch_median,
-// a MORPH one to launch_morph, a BILATERAL one to launch_bilateral, a CONV one to launch_conv, a SEP_DOWN one to launch_sep_down, a RESIZE one to launch_resize;
-// launch_fused and zc_fill_batch take BOX filters only.
+// Returns MI_BLUR_OK or a negative mi_blur_status.  Every filter kind but BOX is handed to the launch_* of its family
+// below; launch_fused and zc_fill_batch take BOX filters only.
 int launch(const LaunchDesc &d);
 // The other families, each in the .hip file of its name: the separable kernel of d.filter->taps, the median of
 // d.filter->radius, the window minimum / maximum / gradient, the bilateral filter and the signed 2-D convolution of

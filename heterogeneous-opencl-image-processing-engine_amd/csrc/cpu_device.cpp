@@ -410,28 +410,28 @@ void cpu_resize_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, const
     }
 }
 
+// Empty for any filter but a resize.
 std::vector<ResizeCoord> resize_xtable(int W, const Filter &f)
 {
+    if (f.kind != FilterKind::RESIZE) return {};
     std::vector<ResizeCoord> t((size_t)f.resize_w);
     for (int X = 0; X < f.resize_w; X++) t[(size_t)X] = resize_axis(W, f.resize_w, f.resize_mode, X);
     return t;
 }
 
 // n_images bands of band_rows rows; output rows [y0,y1) of each.  Threads take whole
-// images when there are enough of them, else row slices of each image.  A SEP_DOWN or RESIZE filter: whole images only
-// (y0 = 0, y1 = band_rows); the output blocks are the decimated / resized images and the row slices are cut in output rows.
+// images when there are enough of them, else row slices of each image.  A whole_image_only filter (filter.h): y0 = 0,
+// y1 = band_rows; the output blocks are the filter's own output images and the row slices are cut in output rows.
 void cpu_blur_batch(const uint8_t *in, uint8_t *out, int W, int band_rows, int C, const Filter &f, int n_images,
                     int y0, int y1, int n_threads, size_t in_stride, size_t out_stride)
 {
     if (n_images <= 0) return;
     if (n_threads <= 0) n_threads = hardware_threads();
     if (in_stride == 0) in_stride = (size_t)W * C * band_rows;
-    const bool down = f.kind == FilterKind::SEP_DOWN;
-    const bool resize = f.kind == FilterKind::RESIZE;
-    if (down) { y0 = 0; y1 = down_rows(band_rows, f.down_sy, f.down_oy); }   // from here on: output rows
-    if (resize) { y0 = 0; y1 = f.resize_h; }
-    if (out_stride == 0) out_stride = (size_t)(down ? down_cols(W, f.down_sx, f.down_ox) : resize ? f.resize_w : W) * C * (y1 - y0);
-    const std::vector<ResizeCoord> xtab = resize ? resize_xtable(W, f) : std::vector<ResizeCoord>();
+    const OutShape o = out_shape(f, W, band_rows, y0, y1);
+    if (whole_image_only(f)) { y0 = 0; y1 = o.rows; }           // from here on: output rows
+    if (out_stride == 0) out_stride = (size_t)o.width * C * o.rows;
+    const std::vector<ResizeCoord> xtab = resize_xtable(W, f);
     const int rows = y1 - y0;
     // work items: (image, row slice)
     // enough items for the threads to end together: a batch of 35 images on 16 threads is three rounds of whole images with the
@@ -450,14 +450,16 @@ void cpu_blur_batch(const uint8_t *in, uint8_t *out, int W, int band_rows, int C
             const int ys = y0 + (int)((long long)rows * s / slices), ye = y0 + (int)((long long)rows * (s + 1) / slices);
             const uint8_t *src = in + img * in_stride;
             uint8_t *dst = out + img * out_stride;
-            if (down) cpu_sep_down_rows(src, dst, W, band_rows, C, f, ys, ye);
-            else if (resize) cpu_resize_rows(src, dst, W, band_rows, C, f, ys, ye, xtab.data());
-            else if (f.kind == FilterKind::CONV) cpu_conv_rows(src, dst, W, band_rows, C, f, ys, ye, y0);
-            else if (f.kind == FilterKind::BILATERAL) cpu_bilateral_rows(src, dst, W, band_rows, C, f, ys, ye, y0);
-            else if (f.kind == FilterKind::MORPH) cpu_morph_rows(src, dst, W, band_rows, C, f.morph_op, f.morph_rx, f.morph_ry, ys, ye, y0);
-            else if (f.kind == FilterKind::MEDIAN) cpu_median_rows(src, dst, W, band_rows, C, f.radius, ys, ye, y0);
-            else if (f.kind == FilterKind::SEP) cpu_blur_rows_sep(src, dst, W, band_rows, C, f.taps, ys, ye, y0);
-            else cpu_blur_rows(src, dst, W, band_rows, C, f.radius, ys, ye, y0);
+            switch (f.kind) {                                   // no default label: a kind without a case is a -Wswitch warning
+            case FilterKind::BOX: cpu_blur_rows(src, dst, W, band_rows, C, f.radius, ys, ye, y0); break;
+            case FilterKind::SEP: cpu_blur_rows_sep(src, dst, W, band_rows, C, f.taps, ys, ye, y0); break;
+            case FilterKind::MEDIAN: cpu_median_rows(src, dst, W, band_rows, C, f.radius, ys, ye, y0); break;
+            case FilterKind::MORPH: cpu_morph_rows(src, dst, W, band_rows, C, f.morph_op, f.morph_rx, f.morph_ry, ys, ye, y0); break;
+            case FilterKind::BILATERAL: cpu_bilateral_rows(src, dst, W, band_rows, C, f, ys, ye, y0); break;
+            case FilterKind::CONV: cpu_conv_rows(src, dst, W, band_rows, C, f, ys, ye, y0); break;
+            case FilterKind::SEP_DOWN: cpu_sep_down_rows(src, dst, W, band_rows, C, f, ys, ye); break;
+            case FilterKind::RESIZE: cpu_resize_rows(src, dst, W, band_rows, C, f, ys, ye, xtab.data()); break;
+            }
         }
     };
     const int nt = (int)std::min<long long>(n_threads, items);

@@ -1,5 +1,5 @@
-// filter.h — internal: the one filter a launch, a context or a CPU run applies, in the form the GPU kernels
-// (blur_kernels.hip, sep_kernels.hip, median_kernels.hip, morph_kernels.hip, bilateral_kernels.hip, conv_kernels.hip, sep_down_kernels.hip, resize_kernels.hip) and the CPU device (cpu_device.cpp) take it.  Plain C++, no HIP.
+// filter.h — internal: the one filter a launch, a context or a CPU run applies, in the form the GPU kernels (the .hip
+// files) and the CPU device (cpu_device.cpp) take it, and the size of its output.  Plain C++, no HIP.
 #pragma once
 
 #include "../../include/mi_blur.h"
@@ -91,6 +91,20 @@ inline bool down_ok(const mi_blur_decimation *d, int W, int H)
 {
     return d && d->sx >= 1 && d->sx <= MI_BLUR_DECIMATE_MAX && d->sy >= 1 && d->sy <= MI_BLUR_DECIMATE_MAX && d->ox >= 0 &&
            d->ox < d->sx && d->oy >= 0 && d->oy < d->sy && d->ox < W && d->oy < H;
+}
+
+// The output geometry of a filter, for everything above the kernels (launch checks, slot sizes, counters, the CPU device).
+// whole_image_only: the output image is not the input's size, so the filter takes whole images only: no bands, no halo
+// rows, no planar or resident forms (a band's phase or source rows would depend on where it starts).
+inline bool whole_image_only(const Filter &f) { return f.kind == FilterKind::SEP_DOWN || f.kind == FilterKind::RESIZE; }
+// Width and rows of the output block of one band of band_rows rows x W of which rows [y0, y1) are asked for: those rows
+// at the input's width, or the filter's own output image (of the whole band) for a whole_image_only filter.
+struct OutShape { int width, rows; };
+inline OutShape out_shape(const Filter &f, int W, int band_rows, int y0, int y1)
+{
+    if (f.kind == FilterKind::SEP_DOWN) return {down_cols(W, f.down_sx, f.down_ox), down_rows(band_rows, f.down_sy, f.down_oy)};
+    if (f.kind == FilterKind::RESIZE) return {f.resize_w, f.resize_h};
+    return {W, y1 - y0};
 }
 
 // The constructors validate: MI_BLUR_OK, or MI_BLUR_ERR_INVALID with *f untouched.

@@ -1,6 +1,5 @@
-// kernel_common.h — internal (not part of the C ABI): what the nine kernel files (blur_kernels.hip, sep_kernels.hip,
-// median_kernels.hip, morph_kernels.hip, bilateral_kernels.hip, conv_kernels.hip, sep_down_kernels.hip, resize_kernels.hip, layout_kernels.hip) share below launch(): the launch call, the blockIdx -> tile maps, the template
-// dispatch, the argument checks and parameter fill every family repeats, the host side of the direct layout, and the
+// kernel_common.h — internal (not part of the C ABI): what the .hip files share below launch(): the launch call, the
+// blockIdx -> tile maps, the template dispatch, the argument checks and parameter fill every family repeats, the host side of the direct layout, and the
 // LDS tile of the sep, morph, bilateral and conv kernels (its coordinates, its staging, its launch geometry).
 // Everything here has internal linkage, so libmi_blur.so exports nothing from it.
 #pragma once
@@ -203,17 +202,23 @@ static inline int check_desc(const LaunchDesc &d, FilterKind kind)
     if ((long long)d.width * d.channels * d.band_rows > INT_MAX) return MI_BLUR_ERR_INVALID;  // per-image 32-bit
     return MI_BLUR_OK;
 }
-// Dense sizes of one band and one output block, and whether a stride given is negative or smaller than that.
+// Dense sizes of one band and one output block (out_shape(), filter.h: d.filter is set), and whether a stride given is
+// negative or smaller than that.
 static inline long long dense_in(const LaunchDesc &d) { return (long long)d.band_rows * d.width * d.channels; }
-static inline long long dense_out(const LaunchDesc &d) { return (long long)(d.y1 - d.y0) * d.width * d.channels; }
+static inline long long dense_out(const LaunchDesc &d)
+{
+    const OutShape o = out_shape(*d.filter, d.width, d.band_rows, d.y0, d.y1);
+    return (long long)o.rows * o.width * d.channels;
+}
 static inline bool strides_too_small(const LaunchDesc &d)
 {
     return d.in_stride < 0 || d.out_stride < 0 || (d.in_stride && d.in_stride < dense_in(d)) || (d.out_stride && d.out_stride < dense_out(d));
 }
-// What launch_sep(), launch_median(), launch_morph(), launch_bilateral() and launch_conv() answer before they choose a
-// kernel, in this order: check_desc, the family's own check of the filter (filter_ok(filter) false: MI_BLUR_ERR_INVALID),
-// halo pointers (MI_BLUR_ERR_UNSUPPORTED), the strides, and only then the empty batch (MI_BLUR_OK; launch() answers it
-// before the strides).  LAUNCH_GO, which is no status: there is something to launch.
+// What every family but the box blur answers before it chooses a kernel, in this order: check_desc, the family's own
+// check of the filter (filter_ok(filter) false: MI_BLUR_ERR_INVALID; a whole_image_only family checks it against the
+// image of d there too), the forms it does not take (halo pointers; rows other than the whole image for a
+// whole_image_only filter: MI_BLUR_ERR_UNSUPPORTED), the strides, and only then the empty batch (MI_BLUR_OK; launch()
+// answers it before the strides).  LAUNCH_GO, which is no status: there is something to launch.
 constexpr int LAUNCH_GO = 1;
 template <typename F>
 static int launch_checks(const LaunchDesc &d, FilterKind kind, F &&filter_ok)
@@ -221,6 +226,7 @@ static int launch_checks(const LaunchDesc &d, FilterKind kind, F &&filter_ok)
     if (const int st = check_desc(d, kind)) return st;
     if (!filter_ok(*d.filter)) return MI_BLUR_ERR_INVALID;
     if (d.halo_top || d.halo_bottom) return MI_BLUR_ERR_UNSUPPORTED;
+    if (whole_image_only(*d.filter) && (d.y0 != 0 || d.y1 != d.band_rows)) return MI_BLUR_ERR_UNSUPPORTED;
     if (strides_too_small(d)) return MI_BLUR_ERR_INVALID;
     return d.n_images == 0 ? MI_BLUR_OK : LAUNCH_GO;
 }
@@ -232,7 +238,7 @@ static inline bool tile_aligned(const LaunchDesc &d)
            d.in_stride % 16 == 0 && d.out_stride % 16 == 0;
 }
 
-// The members every kernel's parameter struct has under the same names (a template, not a base struct: the structs'
+// The members most kernels' parameter structs have under the same names (a template, not a base struct: the structs'
 // names and layouts are the kernels' mangled names and kernarg layouts).  Stride 0 = laid end to end.
 template <typename P>
 static void fill_band(P &p, const LaunchDesc &d)

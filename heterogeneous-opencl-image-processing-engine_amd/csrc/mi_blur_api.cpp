@@ -1,15 +1,11 @@
 // mi_blur_api.cpp — implementation of the C ABI declared in include/mi_blur.h.
 //
 // Each block names the reference OpenCL plumbing it replaces (paths relative to the
-// reference tree).  No torch, no OpenCL; HIP runtime + (lazily dlopen'ed) RCCL only.
-#include "../../include/mi_blur.h"
+// reference tree).  No torch, no OpenCL; HIP runtime only (the multi-GPU exports: comm_api.cpp).
+#include "api_internal.h"
 #include "blur_launch.h"
 #include "cpu_device.h"
 
-#include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
-
-#include <dlfcn.h>
 #include <sched.h>
 #include <time.h>
 
@@ -29,12 +25,6 @@
 #include <vector>
 
 using namespace mi_blur;
-
-#define HIP_TRY(expr)                                                       \
-    do {                                                                    \
-        hipError_t e_ = (expr);                                             \
-        if (e_ != hipSuccess) { (void)hipGetLastError(); return MI_BLUR_ERR_HIP_BASE - (int)e_; } \
-    } while (0)
 
 // Runtime default, applied when the library is loaded and only if the user has not set it: keep kernel
 // arguments in host memory (HIP_FORCE_DEV_KERNARG=0).  With the runtime's gfx9 default (a device-memory
@@ -96,12 +86,29 @@ extern "C" int mi_blur_set_option(const char *key, int value)
 // ----------------------------------------------------------------------------------
 // kernel level   (clSetKernelArg x5 + clEnqueueNDRangeKernel)
 // ----------------------------------------------------------------------------------
-// One launch of f on device memory.  Every check of f and of the arguments that the export makes before asking for a
-// device is done by its caller; launch() checks the rest.
-static int enqueue_filter(const Filter &f, const uint8_t *d_in, uint8_t *d_out, int width, int band_rows, int channels,
-                          int n_images, int y0, int y1, int variant, void *stream, const uint8_t *halo_top = nullptr,
-                          const uint8_t *halo_bottom = nullptr)
+// What an export checks itself, before it asks for a device; launch() checks everything (again) behind the device check.
+// Each family's exports were written from their neighbours', so the levels differ, and a caller without a GPU sees
+// which one an export has: an argument error below its level reads MI_BLUR_ERR_INVALID, one above it
+// MI_BLUR_ERR_NO_DEVICE.  Inherited and observable (tests/test_entry_statuses_host.py), so kept as it is.  Each level
+// adds to the one before it, the last two both to ARGS.
+enum class PreCheck {
+    NOTHING,    // box
+    FILTER,     // sep: the constructor's status
+    ARGS,       // median, morph, bilateral, conv: + pointers, dimensions, image count
+    ARGS_ROWS,  // conv_band: + the row range
+    ARGS_SIZE,  // sep_down, resize: + the image within INT_MAX bytes
+};
+
+// Every mi_blur_enqueue* export: one launch of f on device memory.  built: the status of f's constructor.
+static int enqueue_filter(int built, const Filter &f, PreCheck level, const uint8_t *d_in, uint8_t *d_out, int width,
+                          int band_rows, int channels, int n_images, int y0, int y1, int variant, void *stream,
+                          const uint8_t *halo_top = nullptr, const uint8_t *halo_bottom = nullptr)
 {
+    if (level >= PreCheck::FILTER && built) return built;
+    if (level >= PreCheck::ARGS && (!d_in || !d_out || d_in == d_out || width <= 0 || band_rows <= 0 || channels <= 0 || n_images < 0))
+        return MI_BLUR_ERR_INVALID;
+    if (level == PreCheck::ARGS_ROWS && (y0 < 0 || y1 > band_rows || y0 >= y1)) return MI_BLUR_ERR_INVALID;
+    if (level == PreCheck::ARGS_SIZE && (long long)width * channels * band_rows > INT_MAX) return MI_BLUR_ERR_INVALID;
     if (mi_blur_device_count() <= 0) return MI_BLUR_ERR_NO_DEVICE;
     LaunchDesc d{};
     d.filter = &f;
@@ -111,6 +118,19 @@ static int enqueue_filter(const Filter &f, const uint8_t *d_in, uint8_t *d_out, 
     return launch(d);
 }
 
+// The two filters whose validity depends on the image they are applied to: the constructor, then down_ok / resize_ok
+// against it.  The enqueue and cpu_run exports and the context setters all build them here.
+static int sep_down_for(const mi_blur_sep_kernel *k, const mi_blur_decimation *d, int W, int H, Filter *f)
+{
+    const int rc = filter_sep_down(k, d, f);
+    return rc ? rc : down_ok(d, W, H) ? MI_BLUR_OK : MI_BLUR_ERR_INVALID;
+}
+static int resize_for(const mi_blur_resize *r, int W, int H, int C, Filter *f)
+{
+    const int rc = filter_resize(r, f);
+    return rc ? rc : resize_ok(r, W, H, C) ? MI_BLUR_OK : MI_BLUR_ERR_INVALID;
+}
+
 // The box radius is not checked here: launch() rejects a bad one, after the device check.
 static Filter box_unchecked(int radius) { return Filter{FilterKind::BOX, radius, {}}; }
 
@@ -118,8 +138,8 @@ extern "C" int mi_blur_enqueue_ex(const uint8_t *d_in, uint8_t *d_out, int width
                                   int radius, int n_images, int out_row_begin, int out_row_end, int variant,
                                   void *stream)
 {
-    return enqueue_filter(box_unchecked(radius), d_in, d_out, width, band_rows, channels, n_images, out_row_begin,
-                          out_row_end, variant, stream);
+    return enqueue_filter(MI_BLUR_OK, box_unchecked(radius), PreCheck::NOTHING, d_in, d_out, width, band_rows, channels, n_images,
+                          out_row_begin, out_row_end, variant, stream);
 }
 
 extern "C" int mi_blur_enqueue(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels,
@@ -141,8 +161,8 @@ extern "C" int mi_blur_enqueue_band_peer(const uint8_t *d_in, uint8_t *d_out, in
                                          int radius, int out_row_begin, int out_row_end, const uint8_t *top_src,
                                          const uint8_t *bottom_src, void *stream)
 {
-    return enqueue_filter(box_unchecked(radius), d_in, d_out, width, band_rows, channels, 1, out_row_begin, out_row_end,
-                          MI_BLUR_VARIANT_AUTO, stream, top_src, bottom_src);
+    return enqueue_filter(MI_BLUR_OK, box_unchecked(radius), PreCheck::NOTHING, d_in, d_out, width, band_rows, channels, 1,
+                          out_row_begin, out_row_end, MI_BLUR_VARIANT_AUTO, stream, top_src, bottom_src);
 }
 
 // ----------------------------------------------------------------------------------
@@ -184,18 +204,16 @@ extern "C" int mi_blur_enqueue_sep_band(const uint8_t *d_in, uint8_t *d_out, int
                                         int out_row_begin, int out_row_end, const mi_blur_sep_kernel *k, void *stream)
 {
     Filter f;
-    const int rc = filter_sep(k, &f);
-    if (rc) return rc;
-    return enqueue_filter(f, d_in, d_out, width, band_rows, channels, 1, out_row_begin, out_row_end, MI_BLUR_VARIANT_AUTO, stream);
+    return enqueue_filter(filter_sep(k, &f), f, PreCheck::FILTER, d_in, d_out, width, band_rows, channels, 1, out_row_begin,
+                          out_row_end, MI_BLUR_VARIANT_AUTO, stream);
 }
 
 extern "C" int mi_blur_enqueue_sep(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int n_images,
                                    const mi_blur_sep_kernel *k, void *stream)
 {
     Filter f;
-    const int rc = filter_sep(k, &f);
-    if (rc) return rc;
-    return enqueue_filter(f, d_in, d_out, width, height, channels, n_images, 0, height, MI_BLUR_VARIANT_AUTO, stream);
+    return enqueue_filter(filter_sep(k, &f), f, PreCheck::FILTER, d_in, d_out, width, height, channels, n_images, 0, height,
+                          MI_BLUR_VARIANT_AUTO, stream);
 }
 
 // ----------------------------------------------------------------------------------
@@ -229,10 +247,8 @@ extern "C" int mi_blur_enqueue_sep_down(const uint8_t *d_in, uint8_t *d_out, int
                                         const mi_blur_sep_kernel *k, const mi_blur_decimation *d, void *stream)
 {
     Filter f;
-    if (filter_sep_down(k, d, &f) || !d_in || !d_out || d_in == d_out || width <= 0 || height <= 0 || channels <= 0 || n_images < 0 ||
-        !down_ok(d, width, height) || (long long)width * channels * height > INT_MAX)
-        return MI_BLUR_ERR_INVALID;
-    return enqueue_filter(f, d_in, d_out, width, height, channels, n_images, 0, height, MI_BLUR_VARIANT_AUTO, stream);
+    return enqueue_filter(sep_down_for(k, d, width, height, &f), f, PreCheck::ARGS_SIZE, d_in, d_out, width, height, channels,
+                          n_images, 0, height, MI_BLUR_VARIANT_AUTO, stream);
 }
 
 // ----------------------------------------------------------------------------------
@@ -252,9 +268,8 @@ extern "C" int mi_blur_enqueue_resize(const uint8_t *d_in, uint8_t *d_out, int w
                                       const mi_blur_resize *r, void *stream)
 {
     Filter f;
-    if (filter_resize(r, &f) || !d_in || !d_out || d_in == d_out || n_images < 0 || !resize_ok(r, width, height, channels))
-        return MI_BLUR_ERR_INVALID;
-    return enqueue_filter(f, d_in, d_out, width, height, channels, n_images, 0, height, MI_BLUR_VARIANT_AUTO, stream);
+    return enqueue_filter(resize_for(r, width, height, channels, &f), f, PreCheck::ARGS_SIZE, d_in, d_out, width, height,
+                          channels, n_images, 0, height, MI_BLUR_VARIANT_AUTO, stream);
 }
 
 // ----------------------------------------------------------------------------------
@@ -264,18 +279,16 @@ extern "C" int mi_blur_enqueue_median_band(const uint8_t *d_in, uint8_t *d_out, 
                                            int radius, int out_row_begin, int out_row_end, void *stream)
 {
     Filter f;
-    if (filter_median(radius, &f) || !d_in || !d_out || d_in == d_out || width <= 0 || band_rows <= 0 || channels <= 0)
-        return MI_BLUR_ERR_INVALID;
-    return enqueue_filter(f, d_in, d_out, width, band_rows, channels, 1, out_row_begin, out_row_end, MI_BLUR_VARIANT_AUTO, stream);
+    return enqueue_filter(filter_median(radius, &f), f, PreCheck::ARGS, d_in, d_out, width, band_rows, channels, 1,
+                          out_row_begin, out_row_end, MI_BLUR_VARIANT_AUTO, stream);
 }
 
 extern "C" int mi_blur_enqueue_median(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int radius,
                                       int n_images, void *stream)
 {
     Filter f;
-    if (filter_median(radius, &f) || !d_in || !d_out || d_in == d_out || width <= 0 || height <= 0 || channels <= 0 || n_images < 0)
-        return MI_BLUR_ERR_INVALID;
-    return enqueue_filter(f, d_in, d_out, width, height, channels, n_images, 0, height, MI_BLUR_VARIANT_AUTO, stream);
+    return enqueue_filter(filter_median(radius, &f), f, PreCheck::ARGS, d_in, d_out, width, height, channels, n_images, 0,
+                          height, MI_BLUR_VARIANT_AUTO, stream);
 }
 
 // ----------------------------------------------------------------------------------
@@ -285,18 +298,16 @@ extern "C" int mi_blur_enqueue_morph_band(const uint8_t *d_in, uint8_t *d_out, i
                                           int rx, int ry, int out_row_begin, int out_row_end, void *stream)
 {
     Filter f;
-    if (filter_morph(op, rx, ry, &f) || !d_in || !d_out || d_in == d_out || width <= 0 || band_rows <= 0 || channels <= 0)
-        return MI_BLUR_ERR_INVALID;
-    return enqueue_filter(f, d_in, d_out, width, band_rows, channels, 1, out_row_begin, out_row_end, MI_BLUR_VARIANT_AUTO, stream);
+    return enqueue_filter(filter_morph(op, rx, ry, &f), f, PreCheck::ARGS, d_in, d_out, width, band_rows, channels, 1,
+                          out_row_begin, out_row_end, MI_BLUR_VARIANT_AUTO, stream);
 }
 
 extern "C" int mi_blur_enqueue_morph(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int op, int rx,
                                      int ry, int n_images, void *stream)
 {
     Filter f;
-    if (filter_morph(op, rx, ry, &f) || !d_in || !d_out || d_in == d_out || width <= 0 || height <= 0 || channels <= 0 || n_images < 0)
-        return MI_BLUR_ERR_INVALID;
-    return enqueue_filter(f, d_in, d_out, width, height, channels, n_images, 0, height, MI_BLUR_VARIANT_AUTO, stream);
+    return enqueue_filter(filter_morph(op, rx, ry, &f), f, PreCheck::ARGS, d_in, d_out, width, height, channels, n_images, 0,
+                          height, MI_BLUR_VARIANT_AUTO, stream);
 }
 
 // ----------------------------------------------------------------------------------
@@ -322,18 +333,16 @@ extern "C" int mi_blur_enqueue_bilateral_band(const uint8_t *d_in, uint8_t *d_ou
                                               int out_row_begin, int out_row_end, const mi_blur_bilateral *k, void *stream)
 {
     Filter f;
-    if (filter_bilateral(k, &f) || !d_in || !d_out || d_in == d_out || width <= 0 || band_rows <= 0 || channels <= 0)
-        return MI_BLUR_ERR_INVALID;
-    return enqueue_filter(f, d_in, d_out, width, band_rows, channels, 1, out_row_begin, out_row_end, MI_BLUR_VARIANT_AUTO, stream);
+    return enqueue_filter(filter_bilateral(k, &f), f, PreCheck::ARGS, d_in, d_out, width, band_rows, channels, 1,
+                          out_row_begin, out_row_end, MI_BLUR_VARIANT_AUTO, stream);
 }
 
 extern "C" int mi_blur_enqueue_bilateral(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int n_images,
                                          const mi_blur_bilateral *k, void *stream)
 {
     Filter f;
-    if (filter_bilateral(k, &f) || !d_in || !d_out || d_in == d_out || width <= 0 || height <= 0 || channels <= 0 || n_images < 0)
-        return MI_BLUR_ERR_INVALID;
-    return enqueue_filter(f, d_in, d_out, width, height, channels, n_images, 0, height, MI_BLUR_VARIANT_AUTO, stream);
+    return enqueue_filter(filter_bilateral(k, &f), f, PreCheck::ARGS, d_in, d_out, width, height, channels, n_images, 0,
+                          height, MI_BLUR_VARIANT_AUTO, stream);
 }
 
 // ----------------------------------------------------------------------------------
@@ -375,19 +384,16 @@ extern "C" int mi_blur_enqueue_conv_band(const uint8_t *d_in, uint8_t *d_out, in
                                          int out_row_begin, int out_row_end, const mi_blur_conv *k, void *stream)
 {
     Filter f;
-    if (filter_conv(k, &f) || !d_in || !d_out || d_in == d_out || width <= 0 || band_rows <= 0 || channels <= 0 ||
-        out_row_begin < 0 || out_row_end > band_rows || out_row_begin >= out_row_end)
-        return MI_BLUR_ERR_INVALID;
-    return enqueue_filter(f, d_in, d_out, width, band_rows, channels, 1, out_row_begin, out_row_end, MI_BLUR_VARIANT_AUTO, stream);
+    return enqueue_filter(filter_conv(k, &f), f, PreCheck::ARGS_ROWS, d_in, d_out, width, band_rows, channels, 1,
+                          out_row_begin, out_row_end, MI_BLUR_VARIANT_AUTO, stream);
 }
 
 extern "C" int mi_blur_enqueue_conv(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int n_images,
                                     const mi_blur_conv *k, void *stream)
 {
     Filter f;
-    if (filter_conv(k, &f) || !d_in || !d_out || d_in == d_out || width <= 0 || height <= 0 || channels <= 0 || n_images < 0)
-        return MI_BLUR_ERR_INVALID;
-    return enqueue_filter(f, d_in, d_out, width, height, channels, n_images, 0, height, MI_BLUR_VARIANT_AUTO, stream);
+    return enqueue_filter(filter_conv(k, &f), f, PreCheck::ARGS, d_in, d_out, width, height, channels, n_images, 0, height,
+                          MI_BLUR_VARIANT_AUTO, stream);
 }
 
 // Frame layout on the device (replaces the host loops heterogeneous_blur.c:125-134 and split_image_blur.c:40-56).
@@ -507,7 +513,7 @@ struct CpuWorker {
 
 struct mi_blur_ctx {
     int device = 0, W = 0, H = 0, C = 0, max_batch = 0, n_threads = 0;
-    Filter filter{};                                             // every submit applies it: mi_blur_create's radius, or set_kernel / set_median / set_morph / set_bilateral / set_conv / set_sep_down / set_resize
+    Filter filter{};                                             // every submit applies it: mi_blur_create's radius, or what a mi_blur_ctx_set_* put in its place
     size_t image_bytes = 0;
     std::vector<Slot> slots;
     int next_slot = 0;
@@ -554,7 +560,7 @@ struct mi_blur_ctx {
     // CPU device
     std::vector<CpuJob *> cpu_jobs;
     CpuWorker *cpu_worker = nullptr;
-    bool submitted = false;                                      // set_kernel / set_median / set_morph / set_bilateral / set_conv / set_sep_down / set_resize only before this
+    bool submitted = false;                                      // the mi_blur_ctx_set_* work only before this
     bool is_cpu() const { return device == MI_BLUR_DEVICE_CPU; }
 };
 
@@ -761,19 +767,15 @@ extern "C" int mi_blur_create(mi_blur_ctx **out_ctx, int device, int width, int 
     return MI_BLUR_OK;
 }
 
-// Filters whose output image is not the input's size (SEP_DOWN, RESIZE): whole images only, bytes_alg = input + output.
-static bool own_output_size(const mi_blur_ctx *c) { return c->filter.kind == FilterKind::SEP_DOWN || c->filter.kind == FilterKind::RESIZE; }
-// Bytes of one output image of the context's filter on a whole input image.
-static size_t out_image_bytes(const mi_blur_ctx *c)
+// Bytes of the output block of one band of the context's filter (out_shape(), filter.h).
+static size_t out_band_bytes(const mi_blur_ctx *c, int band_rows, int y0, int y1)
 {
-    const Filter &f = c->filter;
-    if (f.kind == FilterKind::SEP_DOWN) return (size_t)down_cols(c->W, f.down_sx, f.down_ox) * c->C * (size_t)down_rows(c->H, f.down_sy, f.down_oy);
-    if (f.kind == FilterKind::RESIZE) return (size_t)f.resize_w * c->C * (size_t)f.resize_h;
-    return c->image_bytes;
+    const OutShape o = out_shape(c->filter, c->W, band_rows, y0, y1);
+    return (size_t)o.width * c->C * (size_t)o.rows;
 }
 // Bytes of a slot's output buffers per image: a resize may write more than it reads.  The filter is known by the time a
 // slot's buffers are made (setters work only before the first submit); every other context: image_bytes, as before.
-static size_t slot_out_image_bytes(const mi_blur_ctx *c) { return std::max(c->image_bytes, out_image_bytes(c)); }
+static size_t slot_out_image_bytes(const mi_blur_ctx *c) { return std::max(c->image_bytes, out_band_bytes(c, c->H, 0, c->H)); }
 
 // Lazily made slot buffers (see mi_blur_create).  HIP's allocation calls are synchronous with respect to the device only
 // where they must be; the slot's streams carry nothing that touches these buffers before they exist.
@@ -1054,8 +1056,8 @@ static LaunchDesc ctx_launch(const mi_blur_ctx *c, const uint8_t *in, uint8_t *o
 static void count_submit(mi_blur_ctx *c, int n_images, size_t out_bytes, size_t h2d, size_t d2h, bool zero_copy)
 {
     c->tm.bytes_h2d += h2d; c->tm.bytes_d2h += d2h;
-    // the decimating filter and the resize read whole images and write images of another size: input + output; every other filter 2 * output
-    c->tm.bytes_alg += own_output_size(c) ? (uint64_t)c->image_bytes * (uint64_t)n_images + out_bytes : 2ull * out_bytes;
+    // a filter that reads whole images and writes images of another size: input + output; every other filter 2 * output
+    c->tm.bytes_alg += whole_image_only(c->filter) ? (uint64_t)c->image_bytes * (uint64_t)n_images + out_bytes : 2ull * out_bytes;
     c->tm.images += (uint64_t)n_images;
     c->tm.launches += 1;
     if (zero_copy) c->zero_copy_launches += 1;
@@ -1198,7 +1200,7 @@ static int submit_common(mi_blur_ctx *c, const uint8_t *host_in, uint8_t *host_o
 {
     const size_t pitch = (size_t)c->W * c->C;
     const size_t band_in = pitch * band_rows;
-    const size_t band_out = own_output_size(c) ? out_image_bytes(c) : pitch * (size_t)(y1 - y0);   // whole images only: the decimated / resized image
+    const size_t band_out = out_band_bytes(c, band_rows, y0, y1);
     const HostBatch b{host_in, host_out, band_rows, n_images, y0, y1, band_in, band_out,
                       in_stride ? in_stride : band_in, out_stride ? out_stride : band_out};
     c->submitted = true;
@@ -1255,7 +1257,7 @@ extern "C" int mi_blur_submit_band(mi_blur_ctx *c, const uint8_t *host_in, uint8
                                    int halo_top, int halo_bottom)
 {
     if (!c || !host_in || !host_out || host_in == host_out) return MI_BLUR_ERR_INVALID;
-    if (own_output_size(c)) return MI_BLUR_ERR_UNSUPPORTED;   // no band forms: a band's phase depends on where it starts
+    if (whole_image_only(c->filter)) return MI_BLUR_ERR_UNSUPPORTED;   // no band forms: a band's phase depends on where it starts
     if (band_rows <= 0 || band_rows > c->H || halo_top < 0 || halo_bottom < 0) return MI_BLUR_ERR_INVALID;
     if (halo_top + halo_bottom >= band_rows) return MI_BLUR_ERR_INVALID;
     return submit_common(c, host_in, host_out, band_rows, 1, halo_top, band_rows - halo_bottom, 0, 0);
@@ -1265,7 +1267,7 @@ extern "C" int mi_blur_submit_bands(mi_blur_ctx *c, const uint8_t *host_in, uint
                                     size_t host_image_stride, int band_rows, int halo_top, int halo_bottom)
 {
     if (!c || !host_in || !host_out || host_in == host_out) return MI_BLUR_ERR_INVALID;
-    if (own_output_size(c)) return MI_BLUR_ERR_UNSUPPORTED;
+    if (whole_image_only(c->filter)) return MI_BLUR_ERR_UNSUPPORTED;
     if (n_images < 0 || n_images > c->max_batch) return MI_BLUR_ERR_INVALID;
     if (band_rows <= 0 || band_rows > c->H || halo_top < 0 || halo_bottom < 0) return MI_BLUR_ERR_INVALID;
     if (halo_top + halo_bottom >= band_rows) return MI_BLUR_ERR_INVALID;
@@ -1285,7 +1287,7 @@ extern "C" int mi_blur_submit_bands(mi_blur_ctx *c, const uint8_t *host_in, uint
 extern "C" int mi_blur_submit_planar(mi_blur_ctx *c, const uint8_t *host_planar_in, uint8_t *host_out, int n_images, int planar_out)
 {
     if (!c || !host_planar_in || !host_out || host_planar_in == host_out) return MI_BLUR_ERR_INVALID;
-    if (own_output_size(c)) return MI_BLUR_ERR_UNSUPPORTED;
+    if (whole_image_only(c->filter)) return MI_BLUR_ERR_UNSUPPORTED;
     if (n_images < 0 || n_images > c->max_batch) return MI_BLUR_ERR_INVALID;
     if (n_images == 0) return MI_BLUR_OK;
     const size_t bytes = c->image_bytes * (size_t)n_images;
@@ -1350,82 +1352,54 @@ extern "C" int mi_blur_submit_planar(mi_blur_ctx *c, const uint8_t *host_planar_
     return MI_BLUR_OK;
 }
 
-// A separable kernel in place of the context's radius, for every submit from now on (before the first one only).
+// Every mi_blur_ctx_set_*: the filter that build(&f) makes in place of the context's, for every submit from now on (before the
+// first one only; the whole_image_only ones for mi_blur_submit only).  null_arg: a required pointer argument is null,
+// which set_kernel, set_sep_down and set_resize answer before they look at the state; the other setters leave a null
+// table to the constructor, behind the state.
+template <typename B>
+static int ctx_set_filter(mi_blur_ctx *c, bool null_arg, B &&build)
+{
+    if (!c || null_arg) return MI_BLUR_ERR_INVALID;
+    if (c->submitted) return MI_BLUR_ERR_STATE;
+    Filter f;
+    if (const int rc = build(&f)) return rc;
+    c->filter = f;
+    return MI_BLUR_OK;
+}
+
 extern "C" int mi_blur_ctx_set_kernel(mi_blur_ctx *c, const mi_blur_sep_kernel *k)
 {
-    if (!c || !k) return MI_BLUR_ERR_INVALID;
-    if (c->submitted) return MI_BLUR_ERR_STATE;
-    Filter f;
-    const int rc = filter_sep(k, &f);
-    if (rc) return rc;
-    c->filter = f;
-    return MI_BLUR_OK;
+    return ctx_set_filter(c, !k, [&](Filter *f) { return filter_sep(k, f); });
 }
 
-// The decimating separable filter in place of the context's blur, for mi_blur_submit from now on (before the first one only).
 extern "C" int mi_blur_ctx_set_sep_down(mi_blur_ctx *c, const mi_blur_sep_kernel *k, const mi_blur_decimation *d)
 {
-    if (!c || !k || !d) return MI_BLUR_ERR_INVALID;
-    if (c->submitted) return MI_BLUR_ERR_STATE;
-    Filter f;
-    if (filter_sep_down(k, d, &f) || !down_ok(d, c->W, c->H)) return MI_BLUR_ERR_INVALID;
-    c->filter = f;
-    return MI_BLUR_OK;
+    return ctx_set_filter(c, !k || !d, [&](Filter *f) { return sep_down_for(k, d, c->W, c->H, f); });
 }
 
-// The resize in place of the context's blur, for mi_blur_submit from now on (before the first one only).
 extern "C" int mi_blur_ctx_set_resize(mi_blur_ctx *c, const mi_blur_resize *r)
 {
-    if (!c || !r) return MI_BLUR_ERR_INVALID;
-    if (c->submitted) return MI_BLUR_ERR_STATE;
-    Filter f;
-    if (filter_resize(r, &f) || !resize_ok(r, c->W, c->H, c->C)) return MI_BLUR_ERR_INVALID;
-    c->filter = f;
-    return MI_BLUR_OK;
+    return ctx_set_filter(c, !r, [&](Filter *f) { return resize_for(r, c->W, c->H, c->C, f); });
 }
 
-// The median of that radius in place of the context's blur, for every submit from now on (before the first one only).
 extern "C" int mi_blur_ctx_set_median(mi_blur_ctx *c, int radius)
 {
-    if (!c) return MI_BLUR_ERR_INVALID;
-    if (c->submitted) return MI_BLUR_ERR_STATE;
-    Filter f;
-    if (filter_median(radius, &f)) return MI_BLUR_ERR_INVALID;
-    c->filter = f;
-    return MI_BLUR_OK;
+    return ctx_set_filter(c, false, [&](Filter *f) { return filter_median(radius, f); });
 }
 
-// The window minimum / maximum / gradient in place of the context's blur, for every submit from now on (before the first one only).
 extern "C" int mi_blur_ctx_set_morph(mi_blur_ctx *c, int op, int rx, int ry)
 {
-    if (!c) return MI_BLUR_ERR_INVALID;
-    if (c->submitted) return MI_BLUR_ERR_STATE;
-    Filter f;
-    if (filter_morph(op, rx, ry, &f)) return MI_BLUR_ERR_INVALID;
-    c->filter = f;
-    return MI_BLUR_OK;
+    return ctx_set_filter(c, false, [&](Filter *f) { return filter_morph(op, rx, ry, f); });
 }
 
-// The bilateral filter *k in place of the context's blur, for every submit from now on (before the first one only).
 extern "C" int mi_blur_ctx_set_bilateral(mi_blur_ctx *c, const mi_blur_bilateral *k)
 {
-    if (!c) return MI_BLUR_ERR_INVALID;
-    if (c->submitted) return MI_BLUR_ERR_STATE;
-    Filter f;
-    if (filter_bilateral(k, &f)) return MI_BLUR_ERR_INVALID;
-    c->filter = f;
-    return MI_BLUR_OK;
+    return ctx_set_filter(c, false, [&](Filter *f) { return filter_bilateral(k, f); });
 }
 
-// The convolution *k in place of the context's blur, for every submit from now on (before the first one only).
 extern "C" int mi_blur_ctx_set_conv(mi_blur_ctx *c, const mi_blur_conv *k)
 {
-    if (!c) return MI_BLUR_ERR_INVALID;
-    if (c->submitted) return MI_BLUR_ERR_STATE;
-    Filter f;
-    if (filter_conv(k, &f)) return MI_BLUR_ERR_INVALID;
-    c->filter = f;
-    return MI_BLUR_OK;
+    return ctx_set_filter(c, false, [&](Filter *f) { return filter_conv(k, f); });
 }
 
 // Wait for the OLDEST submit still in flight (its output is then in caller memory), so a host
@@ -1829,12 +1803,13 @@ extern "C" int mi_blur_resident_peek(mi_blur_ctx *c, int pool_index, uint8_t *ho
 // ----------------------------------------------------------------------------------
 // CPU device kernel + helpers
 // ----------------------------------------------------------------------------------
-// Every failure here is MI_BLUR_ERR_INVALID, so the order of the checks does not show.  Only the separable, median, morphology, bilateral and convolution runs
-// refuse images of more than INT_MAX bytes, as before.
-static int cpu_run_filter(const Filter &f, const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,
-                          int n_threads)
+// Every mi_blur_cpu_run* export.  built: the status of f's constructor.  Every failure here is MI_BLUR_ERR_INVALID, so the
+// order of the checks does not show.  Every filter but the box blur refuses images of more than INT_MAX bytes, as before.
+// cpu_blur_batch takes the size of the output from f.
+static int cpu_run_filter(int built, const Filter &f, const uint8_t *in, uint8_t *out, int width, int height, int channels,
+                          int n_images, int n_threads)
 {
-    if (!in || !out || in == out || width <= 0 || height <= 0 || channels <= 0 || n_images < 0)
+    if (built || !in || !out || in == out || width <= 0 || height <= 0 || channels <= 0 || n_images < 0)
         return MI_BLUR_ERR_INVALID;
     if (f.kind != FilterKind::BOX && (long long)width * channels * height > INT_MAX) return MI_BLUR_ERR_INVALID;
     cpu_blur_batch(in, out, width, height, channels, f, n_images, 0, height, n_threads);
@@ -1845,58 +1820,56 @@ extern "C" int mi_blur_cpu_run(const uint8_t *in, uint8_t *out, int width, int h
                                int n_images, int n_threads)
 {
     Filter f;
-    return filter_box(radius, &f) ? MI_BLUR_ERR_INVALID : cpu_run_filter(f, in, out, width, height, channels, n_images, n_threads);
+    return cpu_run_filter(filter_box(radius, &f), f, in, out, width, height, channels, n_images, n_threads);
 }
 
 extern "C" int mi_blur_cpu_run_sep(const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,
                                    const mi_blur_sep_kernel *k, int n_threads)
 {
     Filter f;
-    return filter_sep(k, &f) ? MI_BLUR_ERR_INVALID : cpu_run_filter(f, in, out, width, height, channels, n_images, n_threads);
+    return cpu_run_filter(filter_sep(k, &f), f, in, out, width, height, channels, n_images, n_threads);
 }
 
 extern "C" int mi_blur_cpu_run_sep_down(const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,
                                         const mi_blur_sep_kernel *k, const mi_blur_decimation *d, int n_threads)
 {
     Filter f;
-    if (filter_sep_down(k, d, &f) || !down_ok(d, width, height)) return MI_BLUR_ERR_INVALID;
-    return cpu_run_filter(f, in, out, width, height, channels, n_images, n_threads);   // cpu_blur_batch takes the output size from f
+    return cpu_run_filter(sep_down_for(k, d, width, height, &f), f, in, out, width, height, channels, n_images, n_threads);
 }
 
 extern "C" int mi_blur_cpu_run_resize(const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,
                                       const mi_blur_resize *r, int n_threads)
 {
     Filter f;
-    if (filter_resize(r, &f) || !resize_ok(r, width, height, channels)) return MI_BLUR_ERR_INVALID;
-    return cpu_run_filter(f, in, out, width, height, channels, n_images, n_threads);   // cpu_blur_batch takes the output size from f
+    return cpu_run_filter(resize_for(r, width, height, channels, &f), f, in, out, width, height, channels, n_images, n_threads);
 }
 
 extern "C" int mi_blur_cpu_run_median(const uint8_t *in, uint8_t *out, int width, int height, int channels, int radius,
                                       int n_images, int n_threads)
 {
     Filter f;
-    return filter_median(radius, &f) ? MI_BLUR_ERR_INVALID : cpu_run_filter(f, in, out, width, height, channels, n_images, n_threads);
+    return cpu_run_filter(filter_median(radius, &f), f, in, out, width, height, channels, n_images, n_threads);
 }
 
 extern "C" int mi_blur_cpu_run_morph(const uint8_t *in, uint8_t *out, int width, int height, int channels, int op, int rx, int ry,
                                      int n_images, int n_threads)
 {
     Filter f;
-    return filter_morph(op, rx, ry, &f) ? MI_BLUR_ERR_INVALID : cpu_run_filter(f, in, out, width, height, channels, n_images, n_threads);
+    return cpu_run_filter(filter_morph(op, rx, ry, &f), f, in, out, width, height, channels, n_images, n_threads);
 }
 
 extern "C" int mi_blur_cpu_run_bilateral(const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,
                                          const mi_blur_bilateral *k, int n_threads)
 {
     Filter f;
-    return filter_bilateral(k, &f) ? MI_BLUR_ERR_INVALID : cpu_run_filter(f, in, out, width, height, channels, n_images, n_threads);
+    return cpu_run_filter(filter_bilateral(k, &f), f, in, out, width, height, channels, n_images, n_threads);
 }
 
 extern "C" int mi_blur_cpu_run_conv(const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,
                                     const mi_blur_conv *k, int n_threads)
 {
     Filter f;
-    return filter_conv(k, &f) ? MI_BLUR_ERR_INVALID : cpu_run_filter(f, in, out, width, height, channels, n_images, n_threads);
+    return cpu_run_filter(filter_conv(k, &f), f, in, out, width, height, channels, n_images, n_threads);
 }
 
 extern "C" void mi_blur_fill_synthetic(uint8_t *host, int width, int height, int channels, int first_index,
@@ -2002,366 +1975,4 @@ extern "C" void mi_blur_band_of(int height, int radius, int g, int G, mi_blur_ba
     b->row_end = (int)((long long)height * (g + 1) / G);
     b->halo_top = std::min(radius, b->row_begin);
     b->halo_bottom = std::min(radius, height - b->row_end);
-}
-
-// ----------------------------------------------------------------------------------
-// RCCL halo exchange (Approach 2 on resident row shards)
-// ----------------------------------------------------------------------------------
-namespace {
-
-struct Rccl {
-    void *h = nullptr;
-    decltype(&ncclGetUniqueId) GetUniqueId = nullptr;
-    decltype(&ncclCommInitRank) CommInitRank = nullptr;
-    decltype(&ncclCommInitAll) CommInitAll = nullptr;
-    decltype(&ncclCommDestroy) CommDestroy = nullptr;
-    decltype(&ncclCommCount) CommCount = nullptr;
-    decltype(&ncclCommUserRank) CommUserRank = nullptr;
-    decltype(&ncclSend) Send = nullptr;
-    decltype(&ncclRecv) Recv = nullptr;
-    decltype(&ncclGroupStart) GroupStart = nullptr;
-    decltype(&ncclGroupEnd) GroupEnd = nullptr;
-    bool ok = false;
-};
-
-Rccl &rccl()
-{
-    static Rccl r;
-    static std::once_flag once;
-    std::call_once(once, [] {
-        // A process that already holds an RCCL (torch's bundled librccl.so has no soname and is registered under
-        // that name) must keep using that one: a second copy would sit on the same HIP runtime.
-        for (const char *name : {"librccl.so", "librccl.so.1"}) {
-            r.h = dlopen(name, RTLD_NOW | RTLD_LOCAL | RTLD_NOLOAD);
-            if (r.h) break;
-        }
-        if (!r.h)
-            for (const char *name : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1", "/opt/rocm/lib/librccl.so"}) {
-                r.h = dlopen(name, RTLD_NOW | RTLD_LOCAL);
-                if (r.h) break;
-            }
-        if (!r.h) return;
-#define MI_SYM(field, sym) r.field = (decltype(r.field))dlsym(r.h, #sym)
-        MI_SYM(GetUniqueId, ncclGetUniqueId);
-        MI_SYM(CommInitRank, ncclCommInitRank);
-        MI_SYM(CommInitAll, ncclCommInitAll);
-        MI_SYM(CommDestroy, ncclCommDestroy);
-        MI_SYM(CommCount, ncclCommCount);
-        MI_SYM(CommUserRank, ncclCommUserRank);
-        MI_SYM(Send, ncclSend);
-        MI_SYM(Recv, ncclRecv);
-        MI_SYM(GroupStart, ncclGroupStart);
-        MI_SYM(GroupEnd, ncclGroupEnd);
-#undef MI_SYM
-        r.ok = r.GetUniqueId && r.CommInitRank && r.CommInitAll && r.CommDestroy && r.Send && r.Recv &&
-               r.GroupStart && r.GroupEnd;
-    });
-    return r;
-}
-
-inline int nccl_status(ncclResult_t e) { return e == ncclSuccess ? MI_BLUR_OK : MI_BLUR_ERR_RCCL_BASE - (int)e; }
-
-}  // namespace
-
-struct mi_blur_comm {
-    ncclComm_t comm = nullptr;
-    int n_ranks = 1, rank = 0, device = -1;
-    bool p2p = false;                            // single-process copy transport instead of RCCL
-    bool pull = false;                           // ... whose copies are PULLS: one small kernel per rank reads the neighbours' rows
-    hipEvent_t ev_prev = nullptr, ev_push = nullptr;
-};
-
-static_assert(sizeof(ncclUniqueId) == MI_BLUR_UNIQUE_ID_BYTES, "ncclUniqueId size");
-
-extern "C" int mi_blur_comm_unique_id(uint8_t id[MI_BLUR_UNIQUE_ID_BYTES])
-{
-    if (!id) return MI_BLUR_ERR_INVALID;
-    Rccl &r = rccl();
-    if (!r.ok) return MI_BLUR_ERR_UNSUPPORTED;
-    ncclUniqueId u;
-    int rc = nccl_status(r.GetUniqueId(&u));
-    if (rc) return rc;
-    memcpy(id, &u, sizeof u);
-    return MI_BLUR_OK;
-}
-
-extern "C" int mi_blur_comm_init_rank(mi_blur_comm **comm, int n_ranks, int rank,
-                                      const uint8_t id[MI_BLUR_UNIQUE_ID_BYTES])
-{
-    if (!comm || !id || n_ranks <= 0 || rank < 0 || rank >= n_ranks) return MI_BLUR_ERR_INVALID;
-    *comm = nullptr;
-    mi_blur_comm *c = new (std::nothrow) mi_blur_comm;
-    if (!c) return MI_BLUR_ERR_NOMEM;
-    c->n_ranks = n_ranks; c->rank = rank;
-    if (hipGetDevice(&c->device) != hipSuccess) { (void)hipGetLastError(); delete c; return MI_BLUR_ERR_NO_DEVICE; }
-    if (n_ranks > 1) {
-        Rccl &r = rccl();
-        if (!r.ok) { delete c; return MI_BLUR_ERR_UNSUPPORTED; }
-        ncclUniqueId u;
-        memcpy(&u, id, sizeof u);
-        int rc = nccl_status(r.CommInitRank(&c->comm, n_ranks, u, rank));
-        if (rc) { delete c; return rc; }
-    }
-    *comm = c;
-    return MI_BLUR_OK;
-}
-
-extern "C" int mi_blur_comm_init_all(mi_blur_comm **comms, int n_devices, const int *devices)
-{
-    if (!comms || n_devices <= 0) return MI_BLUR_ERR_INVALID;
-    std::vector<ncclComm_t> raw(n_devices, nullptr);
-    std::vector<int> devs(n_devices);
-    for (int i = 0; i < n_devices; i++) devs[i] = devices ? devices[i] : i;
-    if (n_devices > 1) {
-        Rccl &r = rccl();
-        if (!r.ok) return MI_BLUR_ERR_UNSUPPORTED;
-        int rc = nccl_status(r.CommInitAll(raw.data(), n_devices, devs.data()));
-        if (rc) return rc;
-    }
-    for (int i = 0; i < n_devices; i++) comms[i] = nullptr;
-    for (int i = 0; i < n_devices; i++) {
-        mi_blur_comm *c = new (std::nothrow) mi_blur_comm;
-        if (!c) {
-            // give back everything made so far: the wrappers already built (each destroys its RCCL communicator)
-            // and the raw communicators that have no wrapper yet
-            for (int j = 0; j < i; j++) { mi_blur_comm_destroy(comms[j]); comms[j] = nullptr; }
-            for (int j = i; j < n_devices; j++) if (raw[j]) (void)rccl().CommDestroy(raw[j]);
-            return MI_BLUR_ERR_NOMEM;
-        }
-        c->comm = raw[i]; c->n_ranks = n_devices; c->rank = i; c->device = devs[i];
-        comms[i] = c;
-    }
-    return MI_BLUR_OK;
-}
-
-// Single-process communicator set whose halo rows move with hipMemcpyPeerAsync instead of RCCL: the
-// fallback when RCCL is unavailable, and what lets the row-shard flow run with several shards per device.
-extern "C" int mi_blur_comm_init_p2p(mi_blur_comm **comms, int n_devices, const int *devices)
-{
-    if (!comms || n_devices <= 0) return MI_BLUR_ERR_INVALID;
-    const int ndev = mi_blur_device_count();
-    if (ndev <= 0) return MI_BLUR_ERR_NO_DEVICE;
-    for (int i = 0; i < n_devices; i++) comms[i] = nullptr;
-    // any failure gives back every rank made so far (mi_blur_comm_destroy releases the events a rank already holds)
-    auto fail = [&](int rc) {
-        for (int j = 0; j < n_devices; j++) { mi_blur_comm_destroy(comms[j]); comms[j] = nullptr; }
-        return rc;
-    };
-    for (int i = 0; i < n_devices; i++) {
-        mi_blur_comm *c = new (std::nothrow) mi_blur_comm;
-        if (!c) return fail(MI_BLUR_ERR_NOMEM);
-        c->n_ranks = n_devices; c->rank = i; c->device = devices ? devices[i] : i; c->p2p = true;
-        comms[i] = c;
-        if (c->device < 0 || c->device >= ndev) return fail(MI_BLUR_ERR_NO_DEVICE);
-        hipError_t e = hipSetDevice(c->device);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_prev, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_push, hipEventDisableTiming);
-        if (e != hipSuccess) { (void)hipGetLastError(); return fail(MI_BLUR_ERR_HIP_BASE - (int)e); }
-    }
-    for (int i = 0; i + 1 < n_devices; i++) {     // neighbours on different devices: enable direct access both ways (best effort)
-        const int a = comms[i]->device, b = comms[i + 1]->device;
-        if (a == b) continue;
-        int can = 0;
-        if (hipDeviceCanAccessPeer(&can, a, b) == hipSuccess && can) { (void)hipSetDevice(a); (void)hipDeviceEnablePeerAccess(b, 0); }
-        if (hipDeviceCanAccessPeer(&can, b, a) == hipSuccess && can) { (void)hipSetDevice(b); (void)hipDeviceEnablePeerAccess(a, 0); }
-        (void)hipGetLastError();
-    }
-    return MI_BLUR_OK;
-}
-
-// The same single-process set with the halo rows PULLED: every rank runs one small kernel (mi_blur_halo_pull's) that reads its
-// neighbours' edge rows through peer access, instead of pushing its own with two hipMemcpyPeerAsync.
-extern "C" int mi_blur_comm_init_pull(mi_blur_comm **comms, int n_devices, const int *devices)
-{
-    const int rc = mi_blur_comm_init_p2p(comms, n_devices, devices);
-    if (rc) return rc;
-    for (int i = 0; i < n_devices; i++) comms[i]->pull = true;
-    return MI_BLUR_OK;
-}
-
-// What a communicator IS, as the transport itself reports it: a bench line that says "RCCL carried the halos over N
-// ranks" quotes ncclCommCount / ncclCommUserRank, not the number it asked for.
-extern "C" int mi_blur_comm_info(mi_blur_comm *c, int *n_ranks, int *rank, int *transport)
-{
-    if (!c) return MI_BLUR_ERR_INVALID;
-    int n = c->n_ranks, r = c->rank, t = c->pull ? 3 : c->p2p ? 2 : (c->comm ? 1 : 0);
-    if (c->comm) {
-        Rccl &rc = rccl();
-        if (!rc.ok || !rc.CommCount || !rc.CommUserRank) return MI_BLUR_ERR_UNSUPPORTED;
-        int e = nccl_status(rc.CommCount(c->comm, &n));
-        if (!e) e = nccl_status(rc.CommUserRank(c->comm, &r));
-        if (e) return e;
-    }
-    if (n_ranks) *n_ranks = n;
-    if (rank) *rank = r;
-    if (transport) *transport = t;
-    return MI_BLUR_OK;
-}
-
-extern "C" void mi_blur_comm_destroy(mi_blur_comm *c)
-{
-    if (!c) return;
-    if (c->comm) (void)rccl().CommDestroy(c->comm);
-    if (c->ev_prev || c->ev_push) {
-        (void)hipSetDevice(c->device);
-        if (c->ev_prev) (void)hipEventDestroy(c->ev_prev);
-        if (c->ev_push) (void)hipEventDestroy(c->ev_push);
-    }
-    delete c;
-}
-
-static int halo_exchange_calls(Rccl &r, mi_blur_comm *c, uint8_t *d_band, size_t pitch, int owned_rows, int radius,
-                               hipStream_t stream)
-{
-    const int top = c->rank > 0 ? radius : 0;
-    const size_t n = pitch * (size_t)radius;
-    ncclResult_t e = ncclSuccess;
-    if (c->rank > 0) {
-        if ((e = r.Send(d_band + (size_t)top * pitch, n, ncclUint8, c->rank - 1, c->comm, stream)) != ncclSuccess) return nccl_status(e);
-        if ((e = r.Recv(d_band, n, ncclUint8, c->rank - 1, c->comm, stream)) != ncclSuccess) return nccl_status(e);
-    }
-    if (c->rank < c->n_ranks - 1) {
-        uint8_t *last = d_band + (size_t)(top + owned_rows - radius) * pitch;
-        if ((e = r.Send(last, n, ncclUint8, c->rank + 1, c->comm, stream)) != ncclSuccess) return nccl_status(e);
-        if ((e = r.Recv(d_band + (size_t)(top + owned_rows) * pitch, n, ncclUint8, c->rank + 1, c->comm, stream)) != ncclSuccess) return nccl_status(e);
-    }
-    return MI_BLUR_OK;
-}
-
-extern "C" int mi_blur_halo_exchange(mi_blur_comm *c, uint8_t *d_band, int width, int channels, int owned_rows,
-                                     int radius, void *stream)
-{
-    if (!c || !d_band || width <= 0 || channels <= 0 || radius < 1 || owned_rows < radius) return MI_BLUR_ERR_INVALID;
-    if (c->n_ranks == 1) return MI_BLUR_OK;            // nothing to exchange: both edges clamp
-    if (c->p2p) return MI_BLUR_ERR_STATE;              // the copy transport needs every rank: mi_blur_halo_exchange_all
-    Rccl &r = rccl();
-    if (!r.ok || !c->comm) return MI_BLUR_ERR_UNSUPPORTED;
-    int rc = nccl_status(r.GroupStart());
-    if (rc) return rc;
-    rc = halo_exchange_calls(r, c, d_band, (size_t)width * channels, owned_rows, radius, (hipStream_t)stream);
-    int rc2 = nccl_status(r.GroupEnd());
-    return rc ? rc : rc2;
-}
-
-// ----------------------------------------------------------------------------------
-// Halo pull: a rank reads its halo rows straight out of its neighbours' shards (peer memory) with one small kernel.
-// ----------------------------------------------------------------------------------
-static_assert(sizeof(hipIpcMemHandle_t) == MI_BLUR_PEER_HANDLE_BYTES, "hipIpcMemHandle_t size");
-
-extern "C" int mi_blur_peer_export(const void *d_ptr, uint8_t handle[MI_BLUR_PEER_HANDLE_BYTES], uint64_t *offset)
-{
-    if (!d_ptr || !handle || !offset) return MI_BLUR_ERR_INVALID;
-    if (mi_blur_device_count() <= 0) return MI_BLUR_ERR_NO_DEVICE;
-    // the handle names a whole allocation; callers (torch's caching allocator, for one) hand out pieces of bigger ones
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    HIP_TRY(hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)d_ptr));
-    hipIpcMemHandle_t h;
-    HIP_TRY(hipIpcGetMemHandle(&h, base));
-    memcpy(handle, &h, sizeof h);
-    *offset = (uint64_t)((const uint8_t *)d_ptr - (const uint8_t *)base);
-    return MI_BLUR_OK;
-}
-
-extern "C" int mi_blur_peer_open(const uint8_t handle[MI_BLUR_PEER_HANDLE_BYTES], uint64_t offset, void **d_ptr)
-{
-    if (!handle || !d_ptr) return MI_BLUR_ERR_INVALID;
-    *d_ptr = nullptr;
-    if (mi_blur_device_count() <= 0) return MI_BLUR_ERR_NO_DEVICE;
-    hipIpcMemHandle_t h;
-    memcpy(&h, handle, sizeof h);
-    void *base = nullptr;
-    HIP_TRY(hipIpcOpenMemHandle(&base, h, hipIpcMemLazyEnablePeerAccess));
-    *d_ptr = (uint8_t *)base + offset;
-    return MI_BLUR_OK;
-}
-
-extern "C" int mi_blur_peer_close(void *d_ptr, uint64_t offset)
-{
-    if (!d_ptr) return MI_BLUR_OK;
-    HIP_TRY(hipIpcCloseMemHandle((uint8_t *)d_ptr - offset));
-    return MI_BLUR_OK;
-}
-
-extern "C" int mi_blur_halo_pull(uint8_t *d_band, const uint8_t *top_src, const uint8_t *bottom_src, int width, int channels,
-                                 int owned_rows, int radius, void *stream)
-{
-    if (!d_band || width <= 0 || channels <= 0 || radius < 1 || owned_rows < radius) return MI_BLUR_ERR_INVALID;
-    if (mi_blur_device_count() <= 0) return MI_BLUR_ERR_NO_DEVICE;
-    const size_t pitch = (size_t)width * channels, n = pitch * (size_t)radius;
-    const size_t top = top_src ? (size_t)radius : 0;                      // layout: [halo_top rows][owned rows][halo_bottom rows]
-    return launch_halo_pull(top_src, d_band, bottom_src, d_band + (top + (size_t)owned_rows) * pitch, n, (hipStream_t)stream);
-}
-
-// All ranks of a single-process communicator set in ONE RCCL group (one host thread
-// driving G GPUs must not block on rank 0's group before enqueuing rank 1's).
-extern "C" int mi_blur_halo_exchange_all(mi_blur_comm **comms, int n, uint8_t **d_bands, int width, int channels,
-                                         const int *owned_rows, int radius, void **streams)
-{
-    if (!comms || !d_bands || !owned_rows || n <= 0) return MI_BLUR_ERR_INVALID;
-    if (n == 1) return MI_BLUR_OK;
-    for (int i = 0; i < n; i++) if (!comms[i] || owned_rows[i] < radius) return MI_BLUR_ERR_INVALID;
-    if (comms[0]->p2p) {
-        // Same rows, same offsets as the RCCL form; each rank PUSHES its edge rows into its neighbours' halo rows on
-        // its own stream.  Ordering by events: a push waits until the neighbour has finished whatever it queued
-        // before this call (its previous blur may still read those halo rows); a rank's later work waits for the
-        // pushes into its halos.
-        const size_t pitch = (size_t)width * channels, nbytes = pitch * (size_t)radius;
-        auto st = [&](int i) { return streams ? (hipStream_t)streams[i] : (hipStream_t) nullptr; };
-        auto top = [&](int i) { return i > 0 ? radius : 0; };
-        for (int i = 0; i < n; i++) {
-            HIP_TRY(hipSetDevice(comms[i]->device));
-            HIP_TRY(hipEventRecord(comms[i]->ev_prev, st(i)));
-        }
-        for (int i = 0; i < n; i++) {
-            HIP_TRY(hipSetDevice(comms[i]->device));
-            if (comms[0]->pull) {
-                // PULL: rank i reads the last owned rows of rank i-1 and the first owned rows of rank i+1 into its own halo rows
-                // with one kernel on its own stream, once both neighbours have finished what they queued before this call
-                // (their owned rows are final).  ev_push(i) = "rank i has read its neighbours' rows": they wait for it below
-                // before anything they queue later may overwrite those rows.
-                const uint8_t *top_src = nullptr, *bottom_src = nullptr;
-                if (i > 0) {
-                    HIP_TRY(hipStreamWaitEvent(st(i), comms[i - 1]->ev_prev, 0));
-                    top_src = d_bands[i - 1] + (size_t)(top(i - 1) + owned_rows[i - 1] - radius) * pitch;
-                }
-                if (i < n - 1) {
-                    HIP_TRY(hipStreamWaitEvent(st(i), comms[i + 1]->ev_prev, 0));
-                    bottom_src = d_bands[i + 1] + (size_t)top(i + 1) * pitch;
-                }
-                const int rc = launch_halo_pull(top_src, d_bands[i], bottom_src, d_bands[i] + (size_t)(top(i) + owned_rows[i]) * pitch, nbytes, st(i));
-                if (rc) return rc;
-                HIP_TRY(hipEventRecord(comms[i]->ev_push, st(i)));
-                continue;
-            }
-            if (i > 0) {          // first owned rows -> bottom halo of rank i-1
-                HIP_TRY(hipStreamWaitEvent(st(i), comms[i - 1]->ev_prev, 0));
-                uint8_t *dst = d_bands[i - 1] + (size_t)(top(i - 1) + owned_rows[i - 1]) * pitch;
-                HIP_TRY(hipMemcpyPeerAsync(dst, comms[i - 1]->device, d_bands[i] + (size_t)top(i) * pitch, comms[i]->device, nbytes, st(i)));
-            }
-            if (i < n - 1) {      // last owned rows -> top halo of rank i+1
-                HIP_TRY(hipStreamWaitEvent(st(i), comms[i + 1]->ev_prev, 0));
-                const uint8_t *src = d_bands[i] + (size_t)(top(i) + owned_rows[i] - radius) * pitch;
-                HIP_TRY(hipMemcpyPeerAsync(d_bands[i + 1], comms[i + 1]->device, src, comms[i]->device, nbytes, st(i)));
-            }
-            HIP_TRY(hipEventRecord(comms[i]->ev_push, st(i)));
-        }
-        for (int i = 0; i < n; i++) {
-            HIP_TRY(hipSetDevice(comms[i]->device));
-            if (i > 0) HIP_TRY(hipStreamWaitEvent(st(i), comms[i - 1]->ev_push, 0));
-            if (i < n - 1) HIP_TRY(hipStreamWaitEvent(st(i), comms[i + 1]->ev_push, 0));
-        }
-        return MI_BLUR_OK;
-    }
-    Rccl &r = rccl();
-    if (!r.ok) return MI_BLUR_ERR_UNSUPPORTED;
-    int rc = nccl_status(r.GroupStart());
-    if (rc) return rc;
-    for (int i = 0; i < n && !rc; i++) {
-        if (hipSetDevice(comms[i]->device) != hipSuccess) { (void)hipGetLastError(); rc = MI_BLUR_ERR_NO_DEVICE; break; }
-        rc = halo_exchange_calls(r, comms[i], d_bands[i], (size_t)width * channels, owned_rows[i], radius,
-                                 streams ? (hipStream_t)streams[i] : nullptr);
-    }
-    int rc2 = nccl_status(r.GroupEnd());
-    return rc ? rc : rc2;
 }

@@ -172,48 +172,42 @@ __global__ __launch_bounds__(256) void blur_resize_generic_kernel(const ResizeGe
     }
 }
 
-struct ResizeGeom { int Wo, Ho; long long opitch, dense; };
-ResizeGeom resize_geom(const LaunchDesc &d)
-{
-    ResizeGeom g;
-    g.Wo = d.filter->resize_w; g.Ho = d.filter->resize_h;
-    g.opitch = (long long)g.Wo * d.channels;
-    g.dense = g.opitch * g.Ho;
-    return g;
-}
+// Bytes of one row of the resized image.
+long long resize_opitch(const LaunchDesc &d) { return (long long)d.filter->resize_w * d.channels; }
 
 // BILINEAR, 1-4 channels, no reduction on either axis, input and output rows of whole 16-byte chunks, 16-byte aligned
 // buffers and strides.
-bool resize_tile_aligned(const LaunchDesc &d, const ResizeGeom &og)
+bool resize_tile_aligned(const LaunchDesc &d)
 {
-    return d.filter->resize_mode == MI_BLUR_RESIZE_BILINEAR && d.channels <= 4 && og.Wo >= d.width && og.Ho >= d.band_rows &&
-           (long long)d.width * d.channels % 16 == 0 && og.opitch % 16 == 0 && (uintptr_t)d.in % 16 == 0 && (uintptr_t)d.out % 16 == 0 &&
+    const Filter &f = *d.filter;
+    return f.resize_mode == MI_BLUR_RESIZE_BILINEAR && d.channels <= 4 && f.resize_w >= d.width && f.resize_h >= d.band_rows &&
+           (long long)d.width * d.channels % 16 == 0 && resize_opitch(d) % 16 == 0 && (uintptr_t)d.in % 16 == 0 && (uintptr_t)d.out % 16 == 0 &&
            d.in_stride % 16 == 0 && d.out_stride % 16 == 0;
 }
 
 // The tile decomposition of a launch and its largest input footprint (rows, 16-byte chunks), exactly as the kernel
 // computes them: the host walks the strips and the tile rows with resize_axis.
 struct ResizeTiles { int cpr, nstrips, ncols, ntiles_y, max_nsc, max_nsr; };
-ResizeTiles resize_tiles(const LaunchDesc &d, const ResizeGeom &og)
+ResizeTiles resize_tiles(const LaunchDesc &d)
 {
-    const int C = d.channels, W = d.width, H = d.band_rows;
+    const int C = d.channels, W = d.width, H = d.band_rows, Wo = d.filter->resize_w, Ho = d.filter->resize_h;
     ResizeTiles t{};
-    t.cpr = (int)(og.opitch / 16);
+    t.cpr = (int)(resize_opitch(d) / 16);
     t.nstrips = (t.cpr + TILE_NCOLS - 1) / TILE_NCOLS;
     t.ncols = (t.cpr + t.nstrips - 1) / t.nstrips;
-    t.ntiles_y = (og.Ho + TILE_TH - 1) / TILE_TH;
+    t.ntiles_y = (Ho + TILE_TH - 1) / TILE_TH;
     t.max_nsc = t.max_nsr = 1;
     for (int s = 0; s < t.nstrips; s++) {
         const int x0c = s * t.ncols, nc = std::min(t.ncols, t.cpr - x0c);
         if (nc <= 0) continue;
         const int px0 = (x0c * 16) / C, px1 = ((x0c + nc) * 16 - 1) / C;
-        const int sc0 = (resize_axis(W, og.Wo, MI_BLUR_RESIZE_BILINEAR, px0).a * C) >> 4;
-        const int sc1 = (resize_axis(W, og.Wo, MI_BLUR_RESIZE_BILINEAR, px1).b * C + C - 1) >> 4;
+        const int sc0 = (resize_axis(W, Wo, MI_BLUR_RESIZE_BILINEAR, px0).a * C) >> 4;
+        const int sc1 = (resize_axis(W, Wo, MI_BLUR_RESIZE_BILINEAR, px1).b * C + C - 1) >> 4;
         t.max_nsc = std::max(t.max_nsc, sc1 - sc0 + 1);
     }
     for (int ty = 0; ty < t.ntiles_y; ty++) {
-        const int ty0 = ty * TILE_TH, rows = std::min(TILE_TH, og.Ho - ty0);
-        const int r0 = resize_axis(H, og.Ho, MI_BLUR_RESIZE_BILINEAR, ty0).a, r1 = resize_axis(H, og.Ho, MI_BLUR_RESIZE_BILINEAR, ty0 + rows - 1).b;
+        const int ty0 = ty * TILE_TH, rows = std::min(TILE_TH, Ho - ty0);
+        const int r0 = resize_axis(H, Ho, MI_BLUR_RESIZE_BILINEAR, ty0).a, r1 = resize_axis(H, Ho, MI_BLUR_RESIZE_BILINEAR, ty0 + rows - 1).b;
         t.max_nsr = std::max(t.max_nsr, r1 - r0 + 1);
     }
     return t;
@@ -222,15 +216,15 @@ ResizeTiles resize_tiles(const LaunchDesc &d, const ResizeGeom &og)
 // stays far inside (at most 34 rows x 35 chunks); a launch that does not fit goes to the generic kernel.
 bool resize_tiles_fit(const ResizeTiles &t) { return t.max_nsc <= 64 && t.max_nsr <= 255; }
 
-int launch_resize_tiled(const LaunchDesc &d, const ResizeGeom &og, const ResizeTiles &t)
+int launch_resize_tiled(const LaunchDesc &d, const ResizeTiles &t)
 {
     const int C = d.channels;
     ResizeTiledParams p{};
     p.in = d.in; p.out = d.out;
-    p.W = d.width; p.H = d.band_rows; p.Wo = og.Wo; p.Ho = og.Ho;
-    p.pitch = d.width * C; p.opitch = (int)og.opitch;
+    p.W = d.width; p.H = d.band_rows; p.Wo = d.filter->resize_w; p.Ho = d.filter->resize_h;
+    p.pitch = d.width * C; p.opitch = (int)resize_opitch(d);
     p.in_stride = d.in_stride ? d.in_stride : dense_in(d);
-    p.out_stride = d.out_stride ? d.out_stride : og.dense;
+    p.out_stride = d.out_stride ? d.out_stride : dense_out(d);
     p.cpr = t.cpr; p.nstrips = t.nstrips; p.ncols = t.ncols; p.ntiles_y = t.ntiles_y;
     const long long nblocks = (long long)d.n_images * p.ntiles_y * p.nstrips;
     if (nblocks > 0x7fffffffLL) return MI_BLUR_ERR_INVALID;
@@ -243,40 +237,35 @@ int launch_resize_tiled(const LaunchDesc &d, const ResizeGeom &og, const ResizeT
     return dispatch<1, 2, 3, 4>(C, [&](auto CC) { return do_launch(blur_resize_tiled_kernel<CC>, grid, block, lds, d, p); });
 }
 
-int launch_resize_generic(const LaunchDesc &d, const ResizeGeom &og)
+int launch_resize_generic(const LaunchDesc &d)
 {
     set_last_kernel("blur_resize_generic_kernel");
     ResizeGenericParams p{};
     p.in = d.in; p.out = d.out;
-    p.W = d.width; p.H = d.band_rows; p.Wo = og.Wo; p.Ho = og.Ho; p.channels = d.channels;
-    p.pitch = d.width * d.channels; p.opitch = (int)og.opitch; p.mode = d.filter->resize_mode;
+    p.W = d.width; p.H = d.band_rows; p.Wo = d.filter->resize_w; p.Ho = d.filter->resize_h; p.channels = d.channels;
+    p.pitch = d.width * d.channels; p.opitch = (int)resize_opitch(d); p.mode = d.filter->resize_mode;
     p.in_stride = d.in_stride ? d.in_stride : dense_in(d);
-    p.out_stride = d.out_stride ? d.out_stride : og.dense;
-    p.block = og.dense;
+    p.block = dense_out(d);
+    p.out_stride = d.out_stride ? d.out_stride : p.block;
     p.total = p.block * d.n_images;
     return do_launch(blur_resize_generic_kernel, byte_grid(p.total), dim3(256), 0, d, p);
 }
 
 }  // namespace
 
-// Answers in the order of launch_sep_down(): rows other than the whole image are MI_BLUR_ERR_UNSUPPORTED, and out_stride
-// is measured against the RESIZED image.
+// Only whole images (launch_checks()); out_stride is measured against the RESIZED image (dense_out()).
 int launch_resize(const LaunchDesc &d)
 {
-    if (const int st = check_desc(d, FilterKind::RESIZE)) return st;
-    const Filter &f = *d.filter;
-    const mi_blur_resize r{f.resize_w, f.resize_h, f.resize_mode};
-    if (!resize_ok(&r, d.width, d.band_rows, d.channels)) return MI_BLUR_ERR_INVALID;
-    if (d.halo_top || d.halo_bottom || d.y0 != 0 || d.y1 != d.band_rows) return MI_BLUR_ERR_UNSUPPORTED;
-    const ResizeGeom og = resize_geom(d);
-    if (d.in_stride < 0 || d.out_stride < 0 || (d.in_stride && d.in_stride < dense_in(d)) || (d.out_stride && d.out_stride < og.dense))
-        return MI_BLUR_ERR_INVALID;
-    if (d.n_images == 0) return MI_BLUR_OK;
-    if (resize_tile_aligned(d, og)) {
-        const ResizeTiles t = resize_tiles(d, og);
-        if (resize_tiles_fit(t)) return launch_resize_tiled(d, og, t);
+    const int st = launch_checks(d, FilterKind::RESIZE, [&](const Filter &f) {
+        const mi_blur_resize r{f.resize_w, f.resize_h, f.resize_mode};
+        return resize_ok(&r, d.width, d.band_rows, d.channels);
+    });
+    if (st != LAUNCH_GO) return st;
+    if (resize_tile_aligned(d)) {
+        const ResizeTiles t = resize_tiles(d);
+        if (resize_tiles_fit(t)) return launch_resize_tiled(d, t);
     }
-    return launch_resize_generic(d, og);
+    return launch_resize_generic(d);
 }
 
 }  // namespace mi_blur

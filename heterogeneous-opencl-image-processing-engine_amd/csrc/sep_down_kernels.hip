@@ -221,18 +221,8 @@ __global__ __launch_bounds__(256) void blur_sep_down_generic_kernel(const SepDow
     }
 }
 
-// Output geometry of the launch, from the filter (the new family's own: dense_out() / fill_band() speak of the old kinds).
-struct DownGeom { int Wo, Ho; long long opitch, dense; };
-DownGeom down_geom(const LaunchDesc &d)
-{
-    const Filter &f = *d.filter;
-    DownGeom g;
-    g.Wo = down_cols(d.width, f.down_sx, f.down_ox);
-    g.Ho = down_rows(d.band_rows, f.down_sy, f.down_oy);
-    g.opitch = (long long)g.Wo * d.channels;
-    g.dense = g.opitch * g.Ho;
-    return g;
-}
+// Bytes of one row of the decimated image.
+int down_opitch(const LaunchDesc &d) { return out_shape(*d.filter, d.width, d.band_rows, d.y0, d.y1).width * d.channels; }
 
 // Stride 2 both ways, 1-4 channels, input rows of whole 32-byte chunk pairs, 16-byte aligned buffers and strides.
 bool down_tile_aligned(const LaunchDesc &d)
@@ -242,17 +232,15 @@ bool down_tile_aligned(const LaunchDesc &d)
            (uintptr_t)d.in % 16 == 0 && (uintptr_t)d.out % 16 == 0 && d.in_stride % 16 == 0 && d.out_stride % 16 == 0;
 }
 
-int launch_sep_down_tiled(const LaunchDesc &d, const DownGeom &og)
+int launch_sep_down_tiled(const LaunchDesc &d)
 {
     set_last_kernel("blur_sep_down_tiled_kernel");
     const Filter &f = *d.filter;
     const SepTaps &k = f.taps;
     SepDownTiledParams p{};
-    p.in = d.in; p.out = d.out;
-    p.pitch = d.width * d.channels; p.H = d.band_rows; p.y0 = 0; p.y1 = d.band_rows;
-    p.in_stride = d.in_stride ? d.in_stride : dense_in(d);
-    p.out_stride = d.out_stride ? d.out_stride : og.dense;
-    p.opitch = (int)og.opitch; p.oy = f.down_oy;
+    fill_band(p, d);                                  // y0 = 0: the whole image
+    p.y1 = d.band_rows;
+    p.opitch = down_opitch(d); p.oy = f.down_oy;
     // strips of whole groups: 2 G input chunks each, at most TILE_NCOLS chunks per strip
     // 3 channels: 4 groups = 24 chunks per strip, so that 16 kept rows x 4 groups fill the 64 lanes of a wave-iteration of the horizontal pass
     const int unit = 2 * down_group(d.channels), max_units = d.channels == 3 ? 4 : TILE_NCOLS / unit;
@@ -279,7 +267,7 @@ int launch_sep_down_tiled(const LaunchDesc &d, const DownGeom &og)
     });
 }
 
-int launch_sep_down_generic(const LaunchDesc &d, const DownGeom &og)
+int launch_sep_down_generic(const LaunchDesc &d)
 {
     set_last_kernel("blur_sep_down_generic_kernel");
     const Filter &f = *d.filter;
@@ -288,9 +276,9 @@ int launch_sep_down_generic(const LaunchDesc &d, const DownGeom &og)
     p.in = d.in; p.out = d.out;
     p.pitch = d.width * d.channels; p.H = d.band_rows; p.width = d.width; p.channels = d.channels;
     p.in_stride = d.in_stride ? d.in_stride : dense_in(d);
-    p.out_stride = d.out_stride ? d.out_stride : og.dense;
-    p.opitch = (int)og.opitch;
-    p.block = og.dense;
+    p.block = dense_out(d);
+    p.out_stride = d.out_stride ? d.out_stride : p.block;
+    p.opitch = down_opitch(d);
     p.total = p.block * d.n_images;
     p.sx = f.down_sx; p.sy = f.down_sy; p.ox = f.down_ox; p.oy = f.down_oy;
     p.rx = k.rx; p.ry = k.ry; p.shift = k.shift;
@@ -300,22 +288,18 @@ int launch_sep_down_generic(const LaunchDesc &d, const DownGeom &og)
 
 }  // namespace
 
-// Answers in the order of launch_checks(); on top of it: rows other than the whole image are MI_BLUR_ERR_UNSUPPORTED
-// (a band's phase would depend on where it starts), and out_stride is measured against the DECIMATED image.
+// A band's phase would depend on where it starts, so only whole images (launch_checks()); out_stride is measured against
+// the DECIMATED image (dense_out()).
 int launch_sep_down(const LaunchDesc &d)
 {
-    if (const int st = check_desc(d, FilterKind::SEP_DOWN)) return st;
-    const Filter &f = *d.filter;
-    const SepTaps &k = f.taps;
-    if (!(k.rx >= 0 && k.rx <= SEP_MAX_R && k.ry >= 0 && k.ry <= SEP_MAX_R && k.shift >= 0 && k.shift <= 16)) return MI_BLUR_ERR_INVALID;
-    const mi_blur_decimation dec{f.down_sx, f.down_sy, f.down_ox, f.down_oy};
-    if (!down_ok(&dec, d.width, d.band_rows)) return MI_BLUR_ERR_INVALID;
-    if (d.halo_top || d.halo_bottom || d.y0 != 0 || d.y1 != d.band_rows) return MI_BLUR_ERR_UNSUPPORTED;
-    const DownGeom og = down_geom(d);
-    if (d.in_stride < 0 || d.out_stride < 0 || (d.in_stride && d.in_stride < dense_in(d)) || (d.out_stride && d.out_stride < og.dense))
-        return MI_BLUR_ERR_INVALID;
-    if (d.n_images == 0) return MI_BLUR_OK;
-    return down_tile_aligned(d) ? launch_sep_down_tiled(d, og) : launch_sep_down_generic(d, og);
+    const int st = launch_checks(d, FilterKind::SEP_DOWN, [&](const Filter &f) {
+        const SepTaps &k = f.taps;
+        const mi_blur_decimation dec{f.down_sx, f.down_sy, f.down_ox, f.down_oy};
+        return k.rx >= 0 && k.rx <= SEP_MAX_R && k.ry >= 0 && k.ry <= SEP_MAX_R && k.shift >= 0 && k.shift <= 16 &&
+               down_ok(&dec, d.width, d.band_rows);
+    });
+    if (st != LAUNCH_GO) return st;
+    return down_tile_aligned(d) ? launch_sep_down_tiled(d) : launch_sep_down_generic(d);
 }
 
 }  // namespace mi_blur
