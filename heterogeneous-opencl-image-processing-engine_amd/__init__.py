@@ -46,6 +46,9 @@ DOWN_PYR, DOWN_AREA2, DOWN_AREA4 = 0, 1, 2
 RESIZE_MAX_DIM = 32768
 RESIZE_NEAREST, RESIZE_BILINEAR = 0, 1
 RESIZE_MODES = {"nearest": RESIZE_NEAREST, "bilinear": RESIZE_BILINEAR}
+WARP_Q = 16
+WARP_CLAMP, WARP_CONSTANT = 0, 1
+WARP_BORDERS = {"clamp": WARP_CLAMP, "constant": WARP_CONSTANT}
 PEER_HANDLE_BYTES = 64
 
 
@@ -58,7 +61,7 @@ def _newer(target: str, sources: list[str]) -> bool:
 
 def build_native(force: bool = False, verbose: bool = False) -> str:
     """Compile libmi_blur.so (hipcc, --offload-arch=gfx950) and the C++ hosts, in-tree."""
-    srcs = [os.path.join(CSRC, f) for f in ("blur_kernels.hip", "sep_kernels.hip", "median_kernels.hip", "morph_kernels.hip", "bilateral_kernels.hip", "conv_kernels.hip", "sep_down_kernels.hip", "resize_kernels.hip", "layout_kernels.hip", "mi_blur_api.cpp", "comm_api.cpp", "cpu_device.cpp")]
+    srcs = [os.path.join(CSRC, f) for f in ("blur_kernels.hip", "sep_kernels.hip", "median_kernels.hip", "morph_kernels.hip", "bilateral_kernels.hip", "conv_kernels.hip", "sep_down_kernels.hip", "resize_kernels.hip", "warp_kernels.hip", "layout_kernels.hip", "mi_blur_api.cpp", "comm_api.cpp", "cpu_device.cpp")]
     deps = srcs + [os.path.join(CSRC, f) for f in ("api_internal.h", "blur_launch.h", "kernel_common.h", "cpu_device.h", "filter.h")] + [HEADER]
     if force or not _newer(LIB_PATH, deps):
         cmd = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra",
@@ -227,10 +230,36 @@ class Resize(C.Structure):
     _fields_ = [("out_width", C.c_int), ("out_height", C.c_int), ("mode", C.c_int)]
 
 
-def _resize_mode(mode) -> int:
+class Warp(C.Structure):
+    """mi_blur_warp: the output size, the mode (RESIZE_NEAREST | RESIZE_BILINEAR), the border (WARP_CLAMP | WARP_CONSTANT),
+    the fill byte and the OUTPUT -> INPUT map in Q16, row-major 2 x 3."""
+    _fields_ = [("out_width", C.c_int), ("out_height", C.c_int), ("mode", C.c_int), ("border", C.c_int), ("fill", C.c_int),
+                ("m", C.c_int64 * 6)]
+
+    @classmethod
+    def from_matrix(cls, M, out_width: int, out_height: int, mode="bilinear", border="constant", fill: int = 0, inverse: bool = False) -> "Warp":
+        """M: a real 2 x 3 matrix, input -> output (inverse=False: what OpenCV's warpAffine takes) or output -> input
+        (inverse=True: WARP_INVERSE_MAP); quantised by mi_blur_warp_set_matrix."""
+        w = cls(int(out_width), int(out_height), _resize_mode(mode, "warp_affine"), _warp_border(border), int(fill))
+        flat = [float(v) for row in M for v in (row if hasattr(row, "__len__") else [row])]
+        if len(flat) != 6:
+            raise ValueError("warp_affine: M is a 2 x 3 matrix")
+        check(lib().mi_blur_warp_set_matrix(C.byref(w), (C.c_double * 6)(*flat), int(bool(inverse))), "mi_blur_warp_set_matrix")
+        return w
+
+
+def _warp_border(border) -> int:
+    if isinstance(border, str):
+        if border not in WARP_BORDERS:
+            raise ValueError("warp_affine: border is 'constant' or 'clamp'")
+        return WARP_BORDERS[border]
+    return int(border)
+
+
+def _resize_mode(mode, name: str = "resize") -> int:
     if isinstance(mode, str):
         if mode not in RESIZE_MODES:
-            raise ValueError("resize: mode is 'bilinear' or 'nearest'")
+            raise ValueError(f"{name}: mode is 'bilinear' or 'nearest'")
         return RESIZE_MODES[mode]
     return int(mode)
 
@@ -332,6 +361,12 @@ def lib() -> C.CDLL:
         "mi_blur_enqueue_resize": (i, [u8p, u8p, i, i, i, i, C.POINTER(Resize), vp]),
         "mi_blur_cpu_run_resize": (i, [u8p, u8p, i, i, i, i, C.POINTER(Resize), i]),
         "mi_blur_ctx_set_resize": (i, [vp, C.POINTER(Resize)]),
+        "mi_blur_warp_coord": (i, [C.POINTER(Warp), i, i, C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i)]),
+        "mi_blur_warp_rotation": (i, [C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double)]),
+        "mi_blur_warp_set_matrix": (i, [C.POINTER(Warp), C.POINTER(C.c_double), i]),
+        "mi_blur_enqueue_warp": (i, [u8p, u8p, i, i, i, i, C.POINTER(Warp), vp]),
+        "mi_blur_cpu_run_warp": (i, [u8p, u8p, i, i, i, i, C.POINTER(Warp), i]),
+        "mi_blur_ctx_set_warp": (i, [vp, C.POINTER(Warp)]),
         "mi_blur_conv_preset": (i, [i, C.POINTER(Conv)]),
         "mi_blur_enqueue_conv": (i, [u8p, u8p, i, i, i, i, C.POINTER(Conv), vp]),
         "mi_blur_enqueue_conv_band": (i, [u8p, u8p, i, i, i, i, i, C.POINTER(Conv), vp]),
@@ -488,6 +523,12 @@ class Context:
         r = Resize(int(out_width), int(out_height), _resize_mode(mode))
         check(lib().mi_blur_ctx_set_resize(self.h, C.byref(r)), "mi_blur_ctx_set_resize")
         self.resize_spec = r
+
+    def set_warp(self, warp: "Warp") -> None:
+        """The affine warp in place of the blur (before the first submit only): submit() then writes images of
+        warp.out_width x warp.out_height."""
+        check(lib().mi_blur_ctx_set_warp(self.h, C.byref(warp)), "mi_blur_ctx_set_warp")
+        self.warp_spec = warp
 
     def submit_bands(self, host_in, host_out, n_images: int, host_image_stride: int, band_rows: int,
                      halo_top: int, halo_bottom: int) -> None:
@@ -828,3 +869,57 @@ def resize(images, size, mode="bilinear", device: int = 0, batch: int = 0):
         raise ValueError("resize: size is (out_width, out_height), both at least 1")
     out = _filter_images(a, 1, device, batch, lambda ctx: ctx.set_resize(wo, ho, m), (ho, wo))
     return out[0, :, :, 0] if rank == 2 else out[0] if rank == 3 else out
+
+
+def warp_coord(warp: "Warp", X: int, Y: int) -> tuple[int, int, int, int]:
+    """(x0, y0, fx, fy) of output pixel (X, Y) under warp's mode and matrix (mi_blur_warp_coord): the unclamped tap
+    origin and the weights 0..2047 of the taps x0 + 1 and y0 + 1; nearest gives (xi, yi, 0, 0)."""
+    x0, y0, fx, fy = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    check(lib().mi_blur_warp_coord(C.byref(warp), int(X), int(Y), C.byref(x0), C.byref(y0), C.byref(fx), C.byref(fy)), "mi_blur_warp_coord")
+    return x0.value, y0.value, fx.value, fy.value
+
+
+def rotation_matrix(center, angle: float, scale: float = 1.0):
+    """The forward 2 x 3 matrix of OpenCV's getRotationMatrix2D as nested lists (mi_blur_warp_rotation): angle in
+    degrees, positive = counter-clockwise with y pointing down."""
+    fwd = (C.c_double * 6)()
+    check(lib().mi_blur_warp_rotation(float(center[0]), float(center[1]), float(angle), float(scale), fwd), "mi_blur_warp_rotation")
+    return [list(fwd[0:3]), list(fwd[3:6])]
+
+
+def warp_affine(images, M, dsize=None, mode="bilinear", border="constant", fill: int = 0, inverse: bool = False, device: int = 0, batch: int = 0):
+    """Affine warp, numpy in -> numpy out, after OpenCV's warpAffine: M is a real 2 x 3 matrix from input to output
+    coordinates (inverse=True: from output to input), pixel (x, y) at integer coordinates (x, y); dsize = (out_w, out_h),
+    the input's size by default.  Exact fixed-point bilinear (the matrix in Q16, 11 fraction bits, one final rounding) or
+    nearest; border 'constant' (taps outside the image are `fill`) or 'clamp' (include/mi_blur.h has the definition).
+
+    images: (H, W), (H, W, C) or (N, H, W, C) uint8; the result has the same rank with out_h and out_w.  device: HIP
+    ordinal, or DEVICE_CPU.  Goes through mi_blur_create / mi_blur_ctx_set_warp / mi_blur_submit / mi_blur_sync."""
+    a = _images(images, "warp_affine")
+    rank = a.ndim
+    if rank == 2:
+        a = a[None, :, :, None]
+    elif rank == 3:
+        a = a[None]
+    n, h, w, c = a.shape
+    if h == 0 or w == 0 or c == 0:
+        raise ValueError("warp_affine: images must not be empty")
+    wo, ho = (w, h) if dsize is None else (int(dsize[0]), int(dsize[1]))
+    if wo < 1 or ho < 1:
+        raise ValueError("warp_affine: dsize is (out_w, out_h), both at least 1")
+    if not 0 <= int(fill) <= 255:
+        raise ValueError("warp_affine: fill is 0..255")
+    wp = Warp.from_matrix(M, wo, ho, mode, border, fill, inverse)
+    out = _filter_images(a, 1, device, batch, lambda ctx: ctx.set_warp(wp), (ho, wo))
+    return out[0, :, :, 0] if rank == 2 else out[0] if rank == 3 else out
+
+
+def rotate(images, angle: float, scale: float = 1.0, center=None, dsize=None, mode="bilinear", border="constant", fill: int = 0,
+           device: int = 0, batch: int = 0):
+    """warp_affine with the matrix of rotation_matrix(center, angle, scale): a rotation by `angle` degrees (positive =
+    counter-clockwise) about `center`, by default the image's centre ((W - 1) / 2, (H - 1) / 2), at the input's size."""
+    a = _images(images, "rotate")
+    h, w = (a.shape[0], a.shape[1]) if a.ndim < 4 else (a.shape[1], a.shape[2])
+    if center is None:
+        center = ((w - 1) / 2.0, (h - 1) / 2.0)
+    return warp_affine(a, rotation_matrix(center, angle, scale), dsize, mode, border, fill, False, device, batch)

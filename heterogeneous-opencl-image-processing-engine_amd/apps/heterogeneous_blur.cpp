@@ -1,7 +1,7 @@
 // heterogeneous_blur — Approach 1 (image-level distribution) host, MI355X-native.
 //
 //   heterogeneous_blur {cpu|gpu|both} [gpu_ratio] [batch]  [--image F | --synthetic | --size WxH] [--channels C]
-//                      [--ksize 3|5 | --sigma S [--sigma-y S] [--radius R] | --median K | --erode K | --dilate K | --morph-gradient K | --bilateral K [--sigma-color S] [--sigma-space S] | --conv NAME | --pyr-down | --resize WxH [--nearest]] [--images N] [--gpus G] [--slots S] [--threads T] [--resident [--fused]]
+//                      [--ksize 3|5 | --sigma S [--sigma-y S] [--radius R] | --median K | --erode K | --dilate K | --morph-gradient K | --bilateral K [--sigma-color S] [--sigma-space S] | --conv NAME | --pyr-down | --resize WxH [--nearest] | --rotate DEG [--nearest] [--border-fill V]] [--images N] [--gpus G] [--slots S] [--threads T] [--resident [--fused]]
 //                      [--verbose] [--csv FILE] [--save FILE]
 //                      [--frames DIR|PATTERN|FILE [--save-dir DIR] [--planar-out | --native-layout]]   (cpu | gpu)
 //
@@ -94,7 +94,7 @@ int main(int argc, char **argv)
     printf("Number of batches: %d\n", NUM_BATCHES);
     printf("Work-group size: %dx%d\n", local_work_size, local_work_size);
     printf("Execution mode : %d\n", mode);
-    const HostFilter filter = filter_of(opt);
+    HostFilter filter = filter_of(opt);              // --rotate: print_warp() completes it once the image is loaded
     print_filter(filter);
     printf("================================================\n\n");
 
@@ -115,6 +115,7 @@ int main(int argc, char **argv)
     int out_width = width, out_height = height;
     if (filter.pyr_down) print_pyr_down(filter, width, height, &out_width, &out_height);
     if (filter.resize) print_resize(filter, width, height, &out_width, &out_height);
+    if (filter.warp) print_warp(filter, width, height);
     const size_t out_image_size = (size_t)out_width * out_height * channels;
     printf("Original image source: %s\n\n", img.source.c_str());
     const uint8_t *original_image = img.px.data();

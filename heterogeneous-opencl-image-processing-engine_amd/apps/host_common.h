@@ -175,6 +175,9 @@ struct Options {
     bool pyr_down = false;               // --pyr-down: one pyramid level (MI_BLUR_DOWN_PYR) instead of --ksize: mi_blur_ctx_set_sep_down on every
                                          //              context, outputs of the decimated size (heterogeneous_blur only: no bands)
     int resize_w = 0, resize_h = 0;      // --resize WxH [--nearest]: resize every image to W x H (bilinear; --nearest: nearest) instead of --ksize:
+    bool rotate_given = false;           // --rotate DEG [--nearest] [--border-fill V]: rotate every image by DEG degrees about its centre, same size
+    double rotate_deg = 0.0;             //              (mi_blur_ctx_set_warp; bilinear, --nearest: nearest; CLAMP border, --border-fill V: CONSTANT with fill V;
+    int border_fill = -1;                //              heterogeneous_blur only: no bands)
     bool nearest = false;                //              mi_blur_ctx_set_resize on every context, outputs of that size (heterogeneous_blur only: no bands)
     int images = 5000;                   // --images N   (NUM_IMAGES, heterogeneous_blur.c:44)
     bool images_given = false;
@@ -253,6 +256,15 @@ inline int parse_flags(int argc, char **argv, Options &o)
                 o.resize_w > MI_BLUR_RESIZE_MAX_DIM || o.resize_h > MI_BLUR_RESIZE_MAX_DIM) { printf("Error: --resize WxH, each 1..%d\n", MI_BLUR_RESIZE_MAX_DIM); exit(-1); }
         }
         else if (a == "--nearest") o.nearest = true;
+        else if (a == "--rotate") {
+            char tail = 0;
+            if (sscanf(next("--rotate"), "%lf%c", &o.rotate_deg, &tail) != 1 || !(o.rotate_deg >= -36000.0 && o.rotate_deg <= 36000.0)) { printf("Error: --rotate DEG, degrees counter-clockwise\n"); exit(-1); }
+            o.rotate_given = true;
+        }
+        else if (a == "--border-fill") {
+            char tail = 0;
+            if (sscanf(next("--border-fill"), "%d%c", &o.border_fill, &tail) != 1 || o.border_fill < 0 || o.border_fill > 255) { printf("Error: --border-fill V, 0..255\n"); exit(-1); }
+        }
         else if (a == "--sigma-color") { o.sigma_color = atof(next("--sigma-color")); o.sigma_color_given = true; if (!(o.sigma_color > 0.0)) { printf("Error: --sigma-color must be > 0\n"); exit(-1); } }
         else if (a == "--sigma-space") { o.sigma_space = atof(next("--sigma-space")); o.sigma_space_given = true; if (!(o.sigma_space >= 0.0)) { printf("Error: --sigma-space must be >= 0\n"); exit(-1); } }
         else if (a == "--sigma") { o.sigma = atof(next("--sigma")); if (!(o.sigma > 0.0)) { printf("Error: --sigma must be > 0\n"); exit(-1); } }
@@ -296,7 +308,10 @@ inline int parse_flags(int argc, char **argv, Options &o)
     if (o.pyr_down && (o.resident || !o.frames.empty())) { printf("Error: --pyr-down excludes --resident and --frames\n"); exit(-1); }
     if (o.resize_w && (o.ksize_given || o.sigma > 0.0 || o.median || o.morph || o.bilateral || o.conv_preset >= 0 || o.pyr_down)) { printf("Error: --resize excludes --ksize, --sigma, --median, --erode, --dilate, --morph-gradient, --bilateral, --conv and --pyr-down\n"); exit(-1); }
     if (o.resize_w && (o.resident || !o.frames.empty())) { printf("Error: --resize excludes --resident and --frames\n"); exit(-1); }
-    if (o.nearest && !o.resize_w) { printf("Error: --nearest needs --resize\n"); exit(-1); }
+    if (o.rotate_given && (o.resize_w || o.ksize_given || o.sigma > 0.0 || o.median || o.morph || o.bilateral || o.conv_preset >= 0 || o.pyr_down)) { printf("Error: --rotate excludes --resize, --ksize, --sigma, --median, --erode, --dilate, --morph-gradient, --bilateral, --conv and --pyr-down\n"); exit(-1); }
+    if (o.rotate_given && (o.resident || !o.frames.empty())) { printf("Error: --rotate excludes --resident and --frames\n"); exit(-1); }
+    if (o.border_fill >= 0 && !o.rotate_given) { printf("Error: --border-fill needs --rotate\n"); exit(-1); }
+    if (o.nearest && !o.resize_w && !o.rotate_given) { printf("Error: --nearest needs --resize\n"); exit(-1); }
     return npos;
 }
 
@@ -320,6 +335,9 @@ struct HostFilter {
     mi_blur_decimation down_d{};
     bool resize = false;        // --resize WxH [--nearest]: the resize `rs` (mi_blur_ctx_set_resize)
     mi_blur_resize rs{};
+    bool warp = false;          // --rotate DEG [--nearest] [--border-fill V]: the warp `wp` (mi_blur_ctx_set_warp); its size and matrix
+    double rotate_deg = 0.0;    // come from the image: print_warp() fills them in
+    mi_blur_warp wp{};
 };
 
 inline HostFilter filter_of(const Options &o)
@@ -344,6 +362,11 @@ inline HostFilter filter_of(const Options &o)
     }
     f.resize = o.resize_w > 0;
     f.rs = mi_blur_resize{o.resize_w, o.resize_h, o.nearest ? MI_BLUR_RESIZE_NEAREST : MI_BLUR_RESIZE_BILINEAR};
+    f.warp = o.rotate_given;
+    f.rotate_deg = o.rotate_deg;
+    f.wp.mode = o.nearest ? MI_BLUR_RESIZE_NEAREST : MI_BLUR_RESIZE_BILINEAR;
+    f.wp.border = o.border_fill >= 0 ? MI_BLUR_WARP_CONSTANT : MI_BLUR_WARP_CLAMP;
+    f.wp.fill = o.border_fill >= 0 ? o.border_fill : 0;
     return f;
 }
 
@@ -357,6 +380,18 @@ inline void set_filter(mi_blur_ctx *ctx, const HostFilter &f)
     if (f.conv_preset >= 0) mi_check(mi_blur_ctx_set_conv(ctx, &f.conv), "Failed to set the convolution");
     if (f.pyr_down) mi_check(mi_blur_ctx_set_sep_down(ctx, &f.down_k, &f.down_d), "Failed to set the pyramid filter");
     if (f.resize) mi_check(mi_blur_ctx_set_resize(ctx, &f.rs), "Failed to set the resize");
+    if (f.warp) mi_check(mi_blur_ctx_set_warp(ctx, &f.wp), "Failed to set the warp");
+}
+
+// --rotate, once the image size is known: the warp of f becomes the rotation about the image's centre at the image's
+// own size (mi_blur_warp_rotation, then mi_blur_warp_set_matrix of that forward matrix), and the banner's "Blur kernel" line.
+inline void print_warp(HostFilter &f, int width, int height)
+{
+    double fwd[6];
+    f.wp.out_width = width; f.wp.out_height = height;
+    mi_check(mi_blur_warp_rotation((width - 1) / 2.0, (height - 1) / 2.0, f.rotate_deg, 1.0, fwd), "No rotation matrix");
+    mi_check(mi_blur_warp_set_matrix(&f.wp, fwd, 0), "No warp matrix for --rotate");
+    printf("Blur kernel: %s warp, rotate %g deg, %dx%d -> %dx%d\n", f.wp.mode == MI_BLUR_RESIZE_NEAREST ? "nearest" : "bilinear", f.rotate_deg, width, height, width, height);
 }
 
 // The banner's "Blur kernel" line of --resize (after the image is loaded, like print_pyr_down()); *wo, *ho: the size of
@@ -382,7 +417,7 @@ inline int filter_halo(const HostFilter &f) { return f.conv_preset >= 0 ? f.conv
 // The banner's "Blur kernel" line (with the taps of a Gaussian).
 inline void print_filter(const HostFilter &f)
 {
-    if (f.pyr_down || f.resize) return;     // print_pyr_down() / print_resize(), once the image size is known
+    if (f.pyr_down || f.resize || f.warp) return;     // print_pyr_down() / print_resize() / print_warp(), once the image size is known
     if (f.median) { printf("Blur kernel: %dx%d median\n", f.median, f.median); return; }
     if (f.conv_preset >= 0) { printf("Blur kernel: %dx%d convolution (%s)\n", 2 * f.conv.rx + 1, 2 * f.conv.ry + 1, f.conv_name.c_str()); return; }
     if (f.bilateral) { printf("Blur kernel: %dx%d bilateral (sigma_color %g, sigma_space %g)\n", f.bilateral, f.bilateral, f.sigma_color, f.sigma_space); return; }

@@ -1642,6 +1642,7 @@ int launch(const LaunchDesc &d)
     case FilterKind::CONV: return launch_conv(d);
     case FilterKind::SEP_DOWN: return launch_sep_down(d);
     case FilterKind::RESIZE: return launch_resize(d);
+    case FilterKind::WARP: return launch_warp(d);
     }
     return MI_BLUR_ERR_INVALID;
 }

@@ -410,6 +410,22 @@ void cpu_resize_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, const
     }
 }
 
+// Output rows [Y_begin, Y_end) of the affine warp of f (f.warp_*) on one W x H image; out = the warped image (dense).
+// Every byte through warp_coord() and warp_sample() (filter.h), the functions of the GPU's generic kernel.
+void cpu_warp_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, const Filter &f, int Y_begin, int Y_end)
+{
+    const int Wo = f.warp_w;
+    const size_t pitch = (size_t)W * C, opitch = (size_t)Wo * C;
+    for (int Y = Y_begin; Y < Y_end; Y++) {
+        uint8_t *o = out + (size_t)Y * opitch;
+        for (int X = 0; X < Wo; X++) {
+            const WarpCoord q = warp_coord(f.warp_m, f.warp_mode, W, H, X, Y);
+            for (int c = 0; c < C; c++)
+                o[(size_t)X * C + c] = (uint8_t)warp_sample(in + c, pitch, C, W, H, f.warp_border, (unsigned)f.warp_fill, q);
+        }
+    }
+}
+
 // Empty for any filter but a resize.
 std::vector<ResizeCoord> resize_xtable(int W, const Filter &f)
 {
@@ -459,6 +475,7 @@ void cpu_blur_batch(const uint8_t *in, uint8_t *out, int W, int band_rows, int C
             case FilterKind::CONV: cpu_conv_rows(src, dst, W, band_rows, C, f, ys, ye, y0); break;
             case FilterKind::SEP_DOWN: cpu_sep_down_rows(src, dst, W, band_rows, C, f, ys, ye); break;
             case FilterKind::RESIZE: cpu_resize_rows(src, dst, W, band_rows, C, f, ys, ye, xtab.data()); break;
+            case FilterKind::WARP: cpu_warp_rows(src, dst, W, band_rows, C, f, ys, ye); break;
             }
         }
     };

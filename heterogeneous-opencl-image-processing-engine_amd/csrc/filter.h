@@ -17,7 +17,7 @@ struct SepTaps {
     unsigned wx[2 * SEP_MAX_R + 1], wy[2 * SEP_MAX_R + 1];
 };
 
-enum class FilterKind { BOX, SEP, MEDIAN, MORPH, BILATERAL, CONV, SEP_DOWN, RESIZE };
+enum class FilterKind { BOX, SEP, MEDIAN, MORPH, BILATERAL, CONV, SEP_DOWN, RESIZE, WARP };
 
 // BOX: the fixed 3x3 / 5x5 kernel of `radius` 1|2.  SEP: the separable kernel `taps`.  MEDIAN: the median of `radius` 1..7.
 // MORPH: the window minimum / maximum / their difference (`morph_op`) over (2 morph_rx + 1) x (2 morph_ry + 1).
@@ -29,6 +29,9 @@ enum class FilterKind { BOX, SEP, MEDIAN, MORPH, BILATERAL, CONV, SEP_DOWN, RESI
 // down_oy + Y * down_sy are kept (mi_blur_decimation): its output is smaller than its input.
 // RESIZE: the fixed-point resize (mi_blur_resize) to resize_w x resize_h in `resize_mode`: the output may be smaller or
 // larger than the input, in either axis.
+// WARP: the affine warp (mi_blur_warp) to warp_w x warp_h: output pixel (X, Y) samples the input at the Q16 position
+// warp_m maps it to, in `warp_mode`, with the border rule `warp_border` / `warp_fill`.  warp_m is the only map source
+// there is; whatever produces positions goes through warp_position() below, so another source would slot in there.
 struct Filter {
     FilterKind kind;
     int radius;             // BOX and MEDIAN
@@ -40,7 +43,9 @@ struct Filter {
     int32_t conv_bias = 0;
     int16_t conv_k[2][15 * 15] = {};
     int down_sx = 1, down_sy = 1, down_ox = 0, down_oy = 0;   // SEP_DOWN (strides 1..4, phases below them); after the older fields, so the initialisers above stay
-    int resize_w = 0, resize_h = 0, resize_mode = 0;          // RESIZE (1..MI_BLUR_RESIZE_MAX_DIM each way, mi_blur_resize_mode); last, for the same reason
+    int resize_w = 0, resize_h = 0, resize_mode = 0;          // RESIZE (1..MI_BLUR_RESIZE_MAX_DIM each way, mi_blur_resize_mode); after them, for the same reason
+    int warp_w = 0, warp_h = 0, warp_mode = 0, warp_border = 0, warp_fill = 0;   // WARP (size and mode as RESIZE, mi_blur_warp_border, fill 0..255); last, for the same reason
+    int64_t warp_m[6] = {};                                   // WARP: the OUTPUT -> INPUT map, Q16, row-major 2 x 3
 };
 
 #if defined(__HIP__)
@@ -83,6 +88,99 @@ inline bool resize_ok(const mi_blur_resize *r, int W, int H, int C)
            (long long)r->out_width * C <= INT_MAX / 2 && (long long)r->out_width * C * r->out_height <= INT_MAX;
 }
 
+// ---- the affine warp (include/mi_blur.h, "Affine warp").  The GPU kernels, the CPU device and mi_blur_warp_coord all
+// take their coordinates from warp_position() and warp_axis().
+// The Q16 input position of output pixel (X, Y): |m| within the limits of warp_ok() keeps both below 2^47.
+struct WarpPos { int64_t sx, sy; };
+MI_BLUR_HD inline WarpPos warp_position(const int64_t *m, int X, int Y)
+{
+    return {m[0] * X + m[1] * Y + m[2], m[3] * X + m[4] * Y + m[5]};
+}
+// One axis of a position S: the first tap i0 and the weight f (0..2047) of tap i0 + 1.  BILINEAR: the position rounded
+// to 11 fraction bits, p = (S + 16) >> 5, i0 = p >> 11, f = p & 2047.  NEAREST: i0 = (S + 32768) >> 16, f = 0.  All shifts
+// floor.  n > 0: p is clamped into [-2 * 2048, (n + 1) * 2048] first (NEAREST: i0 into [-2, n + 1]), which changes no
+// output byte of an axis of n samples under either border rule (both taps of a position out there lie on the same
+// side outside the axis) and lets the callers go on in 32 bits.  n == 0: not clamped (|S| < 2^47, so i0 fits an int).
+struct WarpAxis { int i0, f; };
+MI_BLUR_HD inline WarpAxis warp_axis(int64_t S, int mode, int n)
+{
+    int64_t p = mode == MI_BLUR_RESIZE_NEAREST ? (S + 32768) >> 5 : (S + 16) >> 5;    // NEAREST: i0 = p >> 11 all the same
+    if (n > 0) {
+        const int64_t lo = -2 * 2048, hi = ((int64_t)n + 1) * 2048;
+        p = p < lo ? lo : p > hi ? hi : p;
+    }
+    return {(int)(p >> 11), mode == MI_BLUR_RESIZE_NEAREST ? 0 : (int)(p & 2047)};
+}
+struct WarpCoord { int x0, y0, fx, fy; };
+MI_BLUR_HD inline WarpCoord warp_coord(const int64_t *m, int mode, int W, int H, int X, int Y)
+{
+    const WarpPos s = warp_position(m, X, Y);
+    const WarpAxis ax = warp_axis(s.sx, mode, W), ay = warp_axis(s.sy, mode, H);
+    return {ax.i0, ay.i0, ax.f, ay.f};
+}
+// The blend of four taps, one rounding.  NEAREST comes through with fx = fy = 0, which gives tap a back exactly.
+MI_BLUR_HD inline unsigned warp_blend(unsigned a, unsigned b, unsigned c, unsigned d, unsigned fx, unsigned fy)
+{
+    const unsigned top = (2048u - fx) * a + fx * b, bot = (2048u - fx) * c + fx * d;
+    return ((2048u - fy) * top + fy * bot + (1u << 21)) >> 22;
+}
+// One output byte from the W x H image whose channel-c bytes start at img (pitch bytes per row, C per pixel), for
+// coordinates clamped by warp_axis (n > 0).  Each tap is decided on its own: CLAMP clamps its index, CONSTANT makes it
+// `fill` when it lies outside the image.
+MI_BLUR_HD inline unsigned warp_sample(const uint8_t *img, size_t pitch, int C, int W, int H, int border, unsigned fill, const WarpCoord &q)
+{
+    const int xa = q.x0 < 0 ? 0 : q.x0 > W - 1 ? W - 1 : q.x0, xb = q.x0 + 1 < 0 ? 0 : q.x0 + 1 > W - 1 ? W - 1 : q.x0 + 1;
+    const int ya = q.y0 < 0 ? 0 : q.y0 > H - 1 ? H - 1 : q.y0, yb = q.y0 + 1 < 0 ? 0 : q.y0 + 1 > H - 1 ? H - 1 : q.y0 + 1;
+    const uint8_t *ra = img + (size_t)ya * pitch, *rb = img + (size_t)yb * pitch;
+    unsigned a = ra[(size_t)xa * C], b = ra[(size_t)xb * C], c = rb[(size_t)xa * C], d = rb[(size_t)xb * C];
+    if (border == MI_BLUR_WARP_CONSTANT) {
+        const bool ixa = xa == q.x0, ixb = xb == q.x0 + 1, iya = ya == q.y0, iyb = yb == q.y0 + 1;
+        a = ixa && iya ? a : fill; b = ixb && iya ? b : fill; c = ixa && iyb ? c : fill; d = ixb && iyb ? d : fill;
+    }
+    return warp_blend(a, b, c, d, (unsigned)q.fx, (unsigned)q.fy);
+}
+// The input pixels the taps of output pixels [X0, X1] x [Y0, Y1] (inclusive) can touch: an affine map has its extrema
+// at the four corners and warp_axis is monotone in S, so the box of the corners' taps, with the + 1 tap, holds them all.
+// CLAMP: the box clamped into the image (clamping is monotone, so clamped taps stay inside it; never empty).  CONSTANT:
+// the box intersected with the image (taps outside it are `fill`); empty (x0 > x1 or y0 > y1) when it misses the image.
+struct WarpBox { int x0, x1, y0, y1; };
+MI_BLUR_HD inline WarpBox warp_footprint(const int64_t *m, int mode, int border, int W, int H, int X0, int X1, int Y0, int Y1)
+{
+    const WarpPos c0 = warp_position(m, X0, Y0), c1 = warp_position(m, X1, Y0), c2 = warp_position(m, X0, Y1), c3 = warp_position(m, X1, Y1);
+    const int64_t sx_lo = c0.sx < c1.sx ? c0.sx : c1.sx, sx_lo2 = c2.sx < c3.sx ? c2.sx : c3.sx;
+    const int64_t sx_hi = c0.sx > c1.sx ? c0.sx : c1.sx, sx_hi2 = c2.sx > c3.sx ? c2.sx : c3.sx;
+    const int64_t sy_lo = c0.sy < c1.sy ? c0.sy : c1.sy, sy_lo2 = c2.sy < c3.sy ? c2.sy : c3.sy;
+    const int64_t sy_hi = c0.sy > c1.sy ? c0.sy : c1.sy, sy_hi2 = c2.sy > c3.sy ? c2.sy : c3.sy;
+    WarpBox b;
+    b.x0 = warp_axis(sx_lo < sx_lo2 ? sx_lo : sx_lo2, mode, W).i0;
+    b.x1 = warp_axis(sx_hi > sx_hi2 ? sx_hi : sx_hi2, mode, W).i0 + 1;
+    b.y0 = warp_axis(sy_lo < sy_lo2 ? sy_lo : sy_lo2, mode, H).i0;
+    b.y1 = warp_axis(sy_hi > sy_hi2 ? sy_hi : sy_hi2, mode, H).i0 + 1;
+    if (border == MI_BLUR_WARP_CONSTANT) {
+        b.x0 = b.x0 < 0 ? 0 : b.x0; b.x1 = b.x1 > W - 1 ? W - 1 : b.x1;
+        b.y0 = b.y0 < 0 ? 0 : b.y0; b.y1 = b.y1 > H - 1 ? H - 1 : b.y1;
+    } else {
+        b.x0 = b.x0 < 0 ? 0 : b.x0 > W - 1 ? W - 1 : b.x0; b.x1 = b.x1 < 0 ? 0 : b.x1 > W - 1 ? W - 1 : b.x1;
+        b.y0 = b.y0 < 0 ? 0 : b.y0 > H - 1 ? H - 1 : b.y0; b.y1 = b.y1 < 0 ? 0 : b.y1 > H - 1 ? H - 1 : b.y1;
+    }
+    return b;
+}
+// A warp that is valid for a W x H image of C channels: the sizes, mode and byte limits of resize_ok(), a known border,
+// fill 0..255, the linear part within 2^26 and the translation within 2^46 (Q16), so positions stay below 2^47.
+inline bool warp_ok(const mi_blur_warp *w, int W, int H, int C)
+{
+    if (!w) return false;
+    const mi_blur_resize r{w->out_width, w->out_height, w->mode};
+    if (!resize_ok(&r, W, H, C)) return false;
+    if ((w->border != MI_BLUR_WARP_CLAMP && w->border != MI_BLUR_WARP_CONSTANT) || w->fill < 0 || w->fill > 255) return false;
+    const int64_t lin = (int64_t)1 << 26, off = (int64_t)1 << 46;
+    for (int i = 0; i < 6; i++) {
+        const int64_t lim = i % 3 == 2 ? off : lin;
+        if (w->m[i] > lim || w->m[i] < -lim) return false;
+    }
+    return true;
+}
+
 // Output size of a decimation of a W x H image: kept columns / rows (> 0 for a valid decimation, down_ok()).
 inline int down_cols(int W, int sx, int ox) { return (W - ox + sx - 1) / sx; }
 inline int down_rows(int H, int sy, int oy) { return (H - oy + sy - 1) / sy; }
@@ -96,7 +194,7 @@ inline bool down_ok(const mi_blur_decimation *d, int W, int H)
 // The output geometry of a filter, for everything above the kernels (launch checks, slot sizes, counters, the CPU device).
 // whole_image_only: the output image is not the input's size, so the filter takes whole images only: no bands, no halo
 // rows, no planar or resident forms (a band's phase or source rows would depend on where it starts).
-inline bool whole_image_only(const Filter &f) { return f.kind == FilterKind::SEP_DOWN || f.kind == FilterKind::RESIZE; }
+inline bool whole_image_only(const Filter &f) { return f.kind == FilterKind::SEP_DOWN || f.kind == FilterKind::RESIZE || f.kind == FilterKind::WARP; }
 // Width and rows of the output block of one band of band_rows rows x W of which rows [y0, y1) are asked for: those rows
 // at the input's width, or the filter's own output image (of the whole band) for a whole_image_only filter.
 struct OutShape { int width, rows; };
@@ -104,6 +202,7 @@ inline OutShape out_shape(const Filter &f, int W, int band_rows, int y0, int y1)
 {
     if (f.kind == FilterKind::SEP_DOWN) return {down_cols(W, f.down_sx, f.down_ox), down_rows(band_rows, f.down_sy, f.down_oy)};
     if (f.kind == FilterKind::RESIZE) return {f.resize_w, f.resize_h};
+    if (f.kind == FilterKind::WARP) return {f.warp_w, f.warp_h};
     return {W, y1 - y0};
 }
 
@@ -148,6 +247,16 @@ inline int filter_resize(const mi_blur_resize *r, Filter *f)
     if (!f || !resize_ok(r, 1, 1, 1)) return MI_BLUR_ERR_INVALID;
     *f = Filter{FilterKind::RESIZE, 0, {}};
     f->resize_w = r->out_width; f->resize_h = r->out_height; f->resize_mode = r->mode;
+    return MI_BLUR_OK;
+}
+
+// The target size, mode, border and map of *w (the image size is checked where it is known: warp_ok()).
+inline int filter_warp(const mi_blur_warp *w, Filter *f)
+{
+    if (!f || !warp_ok(w, 1, 1, 1)) return MI_BLUR_ERR_INVALID;
+    *f = Filter{FilterKind::WARP, 0, {}};
+    f->warp_w = w->out_width; f->warp_h = w->out_height; f->warp_mode = w->mode; f->warp_border = w->border; f->warp_fill = w->fill;
+    for (int i = 0; i < 6; i++) f->warp_m[i] = w->m[i];
     return MI_BLUR_OK;
 }
 

@@ -96,7 +96,7 @@ enum class PreCheck {
     FILTER,     // sep: the constructor's status
     ARGS,       // median, morph, bilateral, conv: + pointers, dimensions, image count
     ARGS_ROWS,  // conv_band: + the row range
-    ARGS_SIZE,  // sep_down, resize: + the image within INT_MAX bytes
+    ARGS_SIZE,  // sep_down, resize, warp: + the image within INT_MAX bytes
 };
 
 // Every mi_blur_enqueue* export: one launch of f on device memory.  built: the status of f's constructor.
@@ -118,8 +118,8 @@ static int enqueue_filter(int built, const Filter &f, PreCheck level, const uint
     return launch(d);
 }
 
-// The two filters whose validity depends on the image they are applied to: the constructor, then down_ok / resize_ok
-// against it.  The enqueue and cpu_run exports and the context setters all build them here.
+// The three filters whose validity depends on the image they are applied to: the constructor, then down_ok / resize_ok /
+// warp_ok against it.  The enqueue and cpu_run exports and the context setters all build them here.
 static int sep_down_for(const mi_blur_sep_kernel *k, const mi_blur_decimation *d, int W, int H, Filter *f)
 {
     const int rc = filter_sep_down(k, d, f);
@@ -129,6 +129,12 @@ static int resize_for(const mi_blur_resize *r, int W, int H, int C, Filter *f)
 {
     const int rc = filter_resize(r, f);
     return rc ? rc : resize_ok(r, W, H, C) ? MI_BLUR_OK : MI_BLUR_ERR_INVALID;
+}
+
+static int warp_for(const mi_blur_warp *w, int W, int H, int C, Filter *f)
+{
+    const int rc = filter_warp(w, f);
+    return rc ? rc : warp_ok(w, W, H, C) ? MI_BLUR_OK : MI_BLUR_ERR_INVALID;
 }
 
 // The box radius is not checked here: launch() rejects a bad one, after the device check.
@@ -269,6 +275,60 @@ extern "C" int mi_blur_enqueue_resize(const uint8_t *d_in, uint8_t *d_out, int w
 {
     Filter f;
     return enqueue_filter(resize_for(r, width, height, channels, &f), f, PreCheck::ARGS_SIZE, d_in, d_out, width, height,
+                          channels, n_images, 0, height, MI_BLUR_VARIANT_AUTO, stream);
+}
+
+// ----------------------------------------------------------------------------------
+// affine warp: fixed-point rotate, scale, shear, translate (no reference analogue)
+// ----------------------------------------------------------------------------------
+extern "C" int mi_blur_warp_coord(const mi_blur_warp *w, int X, int Y, int *x0, int *y0, int *fx, int *fy)
+{
+    if (!w || !x0 || !y0 || !fx || !fy || X < 0 || Y < 0 || X >= MI_BLUR_RESIZE_MAX_DIM || Y >= MI_BLUR_RESIZE_MAX_DIM) return MI_BLUR_ERR_INVALID;
+    mi_blur_warp probe = *w;                            // only the mode and the matrix count here
+    probe.out_width = probe.out_height = 1; probe.border = MI_BLUR_WARP_CLAMP; probe.fill = 0;
+    if (!warp_ok(&probe, 1, 1, 1)) return MI_BLUR_ERR_INVALID;
+    const WarpPos s = warp_position(w->m, X, Y);
+    const WarpAxis ax = warp_axis(s.sx, w->mode, 0), ay = warp_axis(s.sy, w->mode, 0);
+    *x0 = ax.i0; *y0 = ay.i0; *fx = ax.f; *fy = ay.f;
+    return MI_BLUR_OK;
+}
+
+extern "C" int mi_blur_warp_rotation(double cx, double cy, double angle_deg, double scale, double fwd[6])
+{
+    if (!fwd || !std::isfinite(cx) || !std::isfinite(cy) || !std::isfinite(angle_deg) || !std::isfinite(scale)) return MI_BLUR_ERR_INVALID;
+    const double rad = angle_deg * 3.14159265358979323846 / 180.0, a = scale * std::cos(rad), b = scale * std::sin(rad);
+    fwd[0] = a; fwd[1] = b; fwd[2] = (1.0 - a) * cx - b * cy;
+    fwd[3] = -b; fwd[4] = a; fwd[5] = b * cx + (1.0 - a) * cy;
+    return MI_BLUR_OK;
+}
+
+extern "C" int mi_blur_warp_set_matrix(mi_blur_warp *w, const double m[6], int inverse)
+{
+    if (!w || !m) return MI_BLUR_ERR_INVALID;
+    double v[6];
+    for (int i = 0; i < 6; i++) { if (!std::isfinite(m[i])) return MI_BLUR_ERR_INVALID; v[i] = m[i]; }
+    if (!inverse) {
+        const double det = m[0] * m[4] - m[1] * m[3];
+        if (det == 0.0 || !std::isfinite(1.0 / det)) return MI_BLUR_ERR_INVALID;
+        v[0] = m[4] / det; v[1] = -m[1] / det; v[3] = -m[3] / det; v[4] = m[0] / det;
+        v[2] = -(v[0] * m[2] + v[1] * m[5]); v[5] = -(v[3] * m[2] + v[4] * m[5]);
+    }
+    int64_t q[6];
+    for (int i = 0; i < 6; i++) {
+        const double lim = i % 3 == 2 ? 70368744177664.0 : 67108864.0;      // 2^46, 2^26
+        const double r = std::floor(v[i] * 65536.0 + 0.5);
+        if (!(r >= -lim && r <= lim)) return MI_BLUR_ERR_INVALID;           // NaN fails both
+        q[i] = (int64_t)r;
+    }
+    for (int i = 0; i < 6; i++) w->m[i] = q[i];
+    return MI_BLUR_OK;
+}
+
+extern "C" int mi_blur_enqueue_warp(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int n_images,
+                                    const mi_blur_warp *w, void *stream)
+{
+    Filter f;
+    return enqueue_filter(warp_for(w, width, height, channels, &f), f, PreCheck::ARGS_SIZE, d_in, d_out, width, height,
                           channels, n_images, 0, height, MI_BLUR_VARIANT_AUTO, stream);
 }
 
@@ -1354,7 +1414,7 @@ extern "C" int mi_blur_submit_planar(mi_blur_ctx *c, const uint8_t *host_planar_
 
 // Every mi_blur_ctx_set_*: the filter that build(&f) makes in place of the context's, for every submit from now on (before the
 // first one only; the whole_image_only ones for mi_blur_submit only).  null_arg: a required pointer argument is null,
-// which set_kernel, set_sep_down and set_resize answer before they look at the state; the other setters leave a null
+// which set_kernel, set_sep_down, set_resize and set_warp answer before they look at the state; the other setters leave a null
 // table to the constructor, behind the state.
 template <typename B>
 static int ctx_set_filter(mi_blur_ctx *c, bool null_arg, B &&build)
@@ -1380,6 +1440,11 @@ extern "C" int mi_blur_ctx_set_sep_down(mi_blur_ctx *c, const mi_blur_sep_kernel
 extern "C" int mi_blur_ctx_set_resize(mi_blur_ctx *c, const mi_blur_resize *r)
 {
     return ctx_set_filter(c, !r, [&](Filter *f) { return resize_for(r, c->W, c->H, c->C, f); });
+}
+
+extern "C" int mi_blur_ctx_set_warp(mi_blur_ctx *c, const mi_blur_warp *w)
+{
+    return ctx_set_filter(c, !w, [&](Filter *f) { return warp_for(w, c->W, c->H, c->C, f); });
 }
 
 extern "C" int mi_blur_ctx_set_median(mi_blur_ctx *c, int radius)
@@ -1842,6 +1907,13 @@ extern "C" int mi_blur_cpu_run_resize(const uint8_t *in, uint8_t *out, int width
 {
     Filter f;
     return cpu_run_filter(resize_for(r, width, height, channels, &f), f, in, out, width, height, channels, n_images, n_threads);
+}
+
+extern "C" int mi_blur_cpu_run_warp(const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,
+                                    const mi_blur_warp *w, int n_threads)
+{
+    Filter f;
+    return cpu_run_filter(warp_for(w, width, height, channels, &f), f, in, out, width, height, channels, n_images, n_threads);
 }
 
 extern "C" int mi_blur_cpu_run_median(const uint8_t *in, uint8_t *out, int width, int height, int channels, int radius,

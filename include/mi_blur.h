@@ -69,7 +69,8 @@ int mi_blur_version(void);
  * "blur_sep_generic_kernel", "blur_median_fast_kernel", "blur_median_generic_kernel", "blur_morph_tiled_kernel",
  * "blur_morph_generic_kernel", "blur_bilateral_tiled_kernel", "blur_bilateral_generic_kernel", "blur_conv_tiled_kernel",
  * "blur_conv_generic_kernel", "blur_sep_down_tiled_kernel", "blur_sep_down_generic_kernel",
- * "blur_resize_tiled_kernel", "blur_resize_generic_kernel"; "" before the first):
+ * "blur_resize_tiled_kernel", "blur_resize_generic_kernel", "blur_warp_tiled_kernel", "blur_warp_generic_kernel";
+ * "" before the first):
  * reports name the kernel a profiler will show.  Static string, never NULL. */
 const char *mi_blur_last_kernel(void);
 
@@ -187,7 +188,7 @@ typedef struct mi_blur_timing {      /* cumulative since create / last reset; mi
     double d2h_ms;                   /* transfer OUT (time_*_transfer_out) */
     uint64_t bytes_h2d, bytes_d2h;
     uint64_t bytes_alg;              /* algorithmic bytes = 2*W*rows*C per image processed; for a context with
-                                        mi_blur_ctx_set_sep_down or mi_blur_ctx_set_resize: input bytes + output bytes, W*H*C + Wo*Ho*C per image */
+                                        mi_blur_ctx_set_sep_down, mi_blur_ctx_set_resize or mi_blur_ctx_set_warp: input bytes + output bytes, W*H*C + Wo*Ho*C per image */
     uint64_t images;
     uint64_t launches;
 } mi_blur_timing;
@@ -517,6 +518,97 @@ int mi_blur_cpu_run_resize(const uint8_t *in, uint8_t *out, int width, int heigh
  * or the CPU device.  mi_blur_submit_band, _bands, _planar and both resident runs return MI_BLUR_ERR_UNSUPPORTED for
  * such a context. */
 int mi_blur_ctx_set_resize(mi_blur_ctx *ctx, const mi_blur_resize *r);
+
+/* ------------------------------------------------------------------------
+ * Affine warp: exact fixed-point rotate, scale, shear and translate, any output size (no reference analogue).  The
+ * definition is exact integers; the GPU, the CPU device and a numpy restatement agree byte for byte.  It reuses the
+ * resize's arithmetic: 11 fraction bits, a four-tap blend, one final rounding.
+ *
+ * Coordinates: pixel (x, y) sits at integer coordinates (x, y), which is OpenCV's warpAffine convention; there is no
+ * half-pixel shift.  m is the OUTPUT -> INPUT map in Q16 (MI_BLUR_WARP_Q fraction bits), row-major 2 x 3.  For output
+ * pixel (X, Y), in int64:
+ *   Sx = m[0]*X + m[1]*Y + m[2]             Sy = m[3]*X + m[4]*Y + m[5]
+ *
+ * MI_BLUR_RESIZE_BILINEAR:
+ *   px = (Sx + 16) >> 5                     (arithmetic shift: floors; the position rounded to 11 fraction bits)
+ *   x0 = px >> 11                           fx = px & 2047          py, y0, fy from Sy in the same way
+ *   taps T(y0, x0), T(y0, x0+1), T(y0+1, x0), T(y0+1, x0+1); per channel, with the expression of the resize:
+ *   s   = (2048-fy) * ((2048-fx) * T(y0,x0) + fx * T(y0,x0+1)) + fy * ((2048-fx) * T(y0+1,x0) + fx * T(y0+1,x0+1))
+ *   out = (s + (1 << 21)) >> 22
+ * MI_BLUR_RESIZE_NEAREST: xi = (Sx + 32768) >> 16, likewise yi, out = T(yi, xi).
+ *
+ * Taps: under MI_BLUR_WARP_CLAMP T(y, x) = in[clamp(y, 0, H-1)][clamp(x, 0, W-1)][c].  Under MI_BLUR_WARP_CONSTANT a
+ * tap outside [0, W-1] x [0, H-1] is `fill`; each tap is decided on its own (OpenCV's BORDER_CONSTANT).  Channels
+ * never mix.
+ *
+ * Valid: out_width, out_height in 1..MI_BLUR_RESIZE_MAX_DIM; width, height <= MI_BLUR_RESIZE_MAX_DIM; the resize's
+ * per-image byte limits on both images; a known mode and border; 0 <= fill <= 255; |m[0]|, |m[1]|, |m[3]|, |m[4]| <= 2^26
+ * and |m[2]|, |m[5]| <= 2^46, so |Sx|, |Sy| < 2^47 and x0, y0 fit an int.  An all-zero linear part is valid: it samples
+ * one constant position.  Implementations clamp px into [-2*2048, (W+1)*2048] (py likewise with H) before they split
+ * it: under either border rule a position out there gives the bytes of the nearest one inside, and 32 bits do from
+ * there on.
+ *
+ * Properties (Q = 1 << 16; all but the last checked in tests/test_warp_host.py):
+ *   m = {Q,0,0, 0,Q,0} with the input's size is the identity;
+ *   m = {0,-Q,(W-1)*Q, Q,0,0} with an output of H x W (width H, height W) is np.rot90;
+ *   integer translations give a shifted copy;
+ *   under CLAMP, m = {s,0,t, 0,s,t} with s = Q*num/den and t = (s - Q)/2 gives the bytes of mi_blur_enqueue_resize at
+ *   that ratio whenever s and t are integers (x2, x4, /2, /4, /8);
+ *   the result differs from real-valued bilinear interpolation at the exact Q16 position by less than
+ *   0.5 + 255 * 2^-11 ~ 0.6245 (each axis rounded by at most 2^-12, blend slope at most 255 per axis, one final rounding);
+ *   it is NOT OpenCV's INTER_LINEAR bit for bit: OpenCV quantises the position to 5 bits.
+ * The output is interleaved and dense: its pitch is out_width*C and images lie out_width*out_height*C bytes apart.
+ * ---------------------------------------------------------------------- */
+#define MI_BLUR_WARP_Q 16                     /* fraction bits of the matrix */
+typedef enum mi_blur_warp_border { MI_BLUR_WARP_CLAMP = 0, MI_BLUR_WARP_CONSTANT = 1 } mi_blur_warp_border;
+typedef struct mi_blur_warp {
+    int out_width, out_height;                /* 1 .. MI_BLUR_RESIZE_MAX_DIM each */
+    int mode;                                 /* MI_BLUR_RESIZE_NEAREST | MI_BLUR_RESIZE_BILINEAR */
+    int border;                               /* mi_blur_warp_border */
+    int fill;                                 /* 0..255, every channel; CONSTANT only */
+    int64_t m[6];                             /* OUTPUT -> INPUT map, Q16, row-major 2 x 3 */
+} mi_blur_warp;
+
+/* The UNCLAMPED tap origin (x0, y0) and the fractions (fx, fy) of output pixel (X, Y), through the function the
+ * kernels and the CPU device use; NEAREST gives xi, yi, 0, 0.  Only mode and m of *w are read.  MI_BLUR_ERR_INVALID: a
+ * null pointer, an unknown mode, m outside its limits, X or Y outside 0..MI_BLUR_RESIZE_MAX_DIM-1. */
+int mi_blur_warp_coord(const mi_blur_warp *w, int X, int Y, int *x0, int *y0, int *fx, int *fy);
+/* The FORWARD (input -> output) matrix of OpenCV's getRotationMatrix2D: a rotation by angle_deg about (cx, cy) with
+ * an isotropic scale; a positive angle is counter-clockwise with y pointing down.  With a = scale*cos, b = scale*sin:
+ * fwd = {a, b, (1-a)*cx - b*cy,  -b, a, b*cx + (1-a)*cy}.  MI_BLUR_ERR_INVALID: fwd null or an argument not finite. */
+int mi_blur_warp_rotation(double cx, double cy, double angle_deg, double scale, double fwd[6]);
+/* Sets w->m from a real 2 x 3 matrix.  inverse == 0: m maps input to output (what getRotationMatrix2D and
+ * getAffineTransform give) and is inverted in double; inverse != 0: m already maps output to input.  Either way every
+ * entry is quantised q = floor(v*65536 + 0.5) and range-checked.  MI_BLUR_ERR_INVALID (w->m untouched): a null pointer,
+ * an entry not finite, a singular matrix (inverse == 0), an entry outside the limits above. */
+int mi_blur_warp_set_matrix(mi_blur_warp *w, const double m[6], int inverse);
+
+/* n_images images of width x height in, n_images images of w->out_width x w->out_height out (device memory,
+ * asynchronous; n_images == 0 is MI_BLUR_OK; image offsets are 64-bit).  Every argument is checked before a device is
+ * asked for: MI_BLUR_ERR_INVALID comes before MI_BLUR_ERR_NO_DEVICE.
+ * blur_warp_tiled_kernel: one workgroup = one tile of 32 output rows x at most 4*C output 16-byte chunk columns (64
+ * pixels; the chunk columns of a row are cut into ceil(cpr / (4*C)) equal strips, for 3 channels of whole groups of 3
+ * chunks = 16 pixels).  It stages the tile's source footprint in LDS: the bounding box of the taps of the tile's four
+ * corner pixels with the + 1 tap, clamped into the image (CLAMP) or intersected with it (CONSTANT), widened to whole
+ * 16-byte chunks, 16 bytes per staged chunk.  It takes exactly the launches with BILINEAR mode, 1-4 channels,
+ * width*channels and out_width*channels multiples of 16, both pointers 16-byte aligned (and image strides that are
+ * multiples of 16, which this export's dense ones then are), and whose largest footprint over the tiles of one image
+ * is at most 65520 bytes (64 KiB of LDS less 16 bytes that the kernel's 8-byte tap reads may touch behind it).  That admits every launch of that alignment with |m[0]|+|m[1]| <= 3*Q/2 and
+ * |m[3]|+|m[4]| <= 3*Q/2 (every rotation, every enlargement, shears up to 0.5: at most 98 rows x 27 chunks); beyond it
+ * the exact walk over the tiles decides.  Every other launch (NEAREST, 5+ channels, odd rows or pointers, a larger
+ * footprint) goes to blur_warp_generic_kernel (one output byte per thread).  mi_blur_last_kernel() says which ran. */
+int mi_blur_enqueue_warp(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int n_images,
+                         const mi_blur_warp *w, void *stream);
+/* The same on the CPU device's threads (synchronous). */
+int mi_blur_cpu_run_warp(const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,
+                         const mi_blur_warp *w, int n_threads);
+/* Give a context (created with the INPUT width, height, channels) the warp, with the rules of mi_blur_ctx_set_resize:
+ * only before the first submit (MI_BLUR_ERR_STATE after); it replaces what another setter set and is replaced by them;
+ * the context keeps a copy.  MI_BLUR_ERR_INVALID also when *w is not valid for the context's size.  mi_blur_submit then
+ * writes n_images * Wo*Ho*C bytes to host_out: pageable caller memory, or pinned memory on both sides (in place, one
+ * launch per submit, never the batch server), on the GPU or the CPU device.  mi_blur_submit_band, _bands, _planar and
+ * both resident runs return MI_BLUR_ERR_UNSUPPORTED for such a context. */
+int mi_blur_ctx_set_warp(mi_blur_ctx *ctx, const mi_blur_warp *w);
 
 /* ------------------------------------------------------------------------
  * Median blur, windows 3x3 to 15x15 (no reference analogue).  For a radius r in 1..MI_BLUR_MEDIAN_MAX_RADIUS, with

@@ -1,0 +1,424 @@
+"""The affine warp (mi_blur_warp_coord, mi_blur_warp_rotation, mi_blur_warp_set_matrix, mi_blur_cpu_run_warp,
+mi_blur_enqueue_warp's argument checks, mi_blur_ctx_set_warp, warp_affine() / rotate() / warp_coord()), CPU only: against
+the numpy restatement of the header's definition (warp_ref.py), independent of the product.  All comparisons are exact
+unless stated."""
+import ctypes as C
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from filter_harness import MEDIAN, cpu_run
+from resize_ref import ref_resize
+from warp_ref import (BILINEAR, CLAMP, CONSTANT, LIN_MAX, MAX_DIM, NEAREST, OFF_MAX, Q, cpu_warp_run, float_warp, identity, in_the_admitted_region,
+                      invert, make_warp, max_footprint, quantise, ref_coord, ref_warp, rot90_matrix, rotation_forward, rotation_m, scale_matrix,
+                      takes_tiled)
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+MODES = (BILINEAR, NEAREST)
+BORDERS = (CLAMP, CONSTANT)
+
+
+def shear_m(kx, ky, tx=0.0, ty=0.0):
+    return quantise([1.0, kx, tx, ky, 1.0, ty])
+
+
+def test_coord_equals_the_restatement(pkg, L):
+    rng = np.random.default_rng(1)
+    x0, y0, fx, fy = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    mats = [identity(), rot90_matrix(17), [0] * 6, [LIN_MAX, -LIN_MAX, OFF_MAX, -LIN_MAX, LIN_MAX, -OFF_MAX], [-LIN_MAX] * 2 + [-OFF_MAX] + [LIN_MAX] * 2 + [OFF_MAX],
+            [1, -1, 15, -1, 1, -17], [Q, 0, -16, 0, Q, -17], [Q, 0, 32767, 0, Q, 32768]]
+    for _ in range(40):
+        lin = rng.integers(-LIN_MAX, LIN_MAX + 1, size=4) if rng.random() < 0.5 else rng.integers(-2 * Q, 2 * Q + 1, size=4)
+        off = rng.integers(-OFF_MAX, OFF_MAX + 1, size=2) if rng.random() < 0.5 else rng.integers(-300 * Q, 300 * Q, size=2)
+        mats.append([int(lin[0]), int(lin[1]), int(off[0]), int(lin[2]), int(lin[3]), int(off[1])])
+    pts = [(0, 0), (1, 0), (0, 1), (13, 7), (MAX_DIM - 1, MAX_DIM - 1), (MAX_DIM - 1, 0)]
+    for m in mats:
+        for mode in MODES:
+            wp = make_warp(pkg, m, 1, 1, mode)
+            for X, Y in pts:
+                assert L.mi_blur_warp_coord(C.byref(wp), X, Y, C.byref(x0), C.byref(y0), C.byref(fx), C.byref(fy)) == pkg.OK
+                want = tuple(int(v) for v in ref_coord(m, mode, X, Y))
+                assert (x0.value, y0.value, fx.value, fy.value) == want, (m, mode, X, Y)
+                assert 0 <= fx.value <= 2047 and 0 <= fy.value <= 2047 and (mode == BILINEAR or (fx.value, fy.value) == (0, 0))
+                assert pkg.warp_coord(wp, X, Y) == want
+    good = make_warp(pkg, identity(), 1, 1)
+    for X, Y in ((-1, 0), (0, -1), (MAX_DIM, 0), (0, MAX_DIM)):
+        assert L.mi_blur_warp_coord(C.byref(good), X, Y, C.byref(x0), C.byref(y0), C.byref(fx), C.byref(fy)) == pkg.ERR_INVALID
+    assert L.mi_blur_warp_coord(None, 0, 0, C.byref(x0), C.byref(y0), C.byref(fx), C.byref(fy)) == pkg.ERR_INVALID
+    assert L.mi_blur_warp_coord(C.byref(good), 0, 0, None, C.byref(y0), C.byref(fx), C.byref(fy)) == pkg.ERR_INVALID
+    assert L.mi_blur_warp_coord(C.byref(make_warp(pkg, identity(), 1, 1, 2)), 0, 0, C.byref(x0), C.byref(y0), C.byref(fx), C.byref(fy)) == pkg.ERR_INVALID
+    over = identity()
+    over[1] = LIN_MAX + 1
+    assert L.mi_blur_warp_coord(C.byref(make_warp(pkg, over, 1, 1)), 0, 0, C.byref(x0), C.byref(y0), C.byref(fx), C.byref(fy)) == pkg.ERR_INVALID
+
+
+def test_properties_of_the_definition(pkg, L):
+    rng = np.random.default_rng(2)
+    img = rng.integers(0, 256, size=(2, 13, 17, 3), dtype=np.uint8)
+    n, h, w, c = img.shape
+    for mode in MODES:
+        for border in BORDERS:
+            run = lambda m, wo, ho, fill=7: cpu_warp_run(pkg, L, img, m, wo, ho, mode, border, fill)
+            assert np.array_equal(run(identity(), w, h), img)                                      # the identity
+            # the four right-angle rotations, each from the header's rot90 matrix composed with itself
+            assert np.array_equal(run(rot90_matrix(w), h, w), np.rot90(img, 1, axes=(1, 2)))
+            assert np.array_equal(run([-Q, 0, (w - 1) * Q, 0, -Q, (h - 1) * Q], w, h), np.rot90(img, 2, axes=(1, 2)))
+            assert np.array_equal(run([0, Q, 0, -Q, 0, (h - 1) * Q], h, w), np.rot90(img, 3, axes=(1, 2)))
+            assert np.array_equal(run([Q, 0, 0, 0, Q, 0], w, h), np.rot90(img, 4, axes=(1, 2)))
+            # flips and the transpose
+            assert np.array_equal(run([-Q, 0, (w - 1) * Q, 0, Q, 0], w, h), img[:, :, ::-1])
+            assert np.array_equal(run([Q, 0, 0, 0, -Q, (h - 1) * Q], w, h), img[:, ::-1])
+            assert np.array_equal(run([0, Q, 0, Q, 0, 0], h, w), img.transpose(0, 2, 1, 3))
+            # integer shifts: output (X, Y) = input (X + dx, Y + dy), the rest by the border rule
+            for dx, dy in ((3, 0), (0, -2), (-5, 4), (20, 0), (0, -30)):
+                got = run(identity(dx, dy), w, h)
+                ys, xs = np.arange(h) + dy, np.arange(w) + dx
+                want = img[:, np.clip(ys, 0, h - 1)][:, :, np.clip(xs, 0, w - 1)].copy()
+                if border == CONSTANT:
+                    want[:, (ys < 0) | (ys >= h)] = 7
+                    want[:, :, (xs < 0) | (xs >= w)] = 7
+                assert np.array_equal(got, want), (mode, border, dx, dy)
+            # a zero linear part samples one position
+            got = run([0, 0, 5 * Q, 0, 0, 3 * Q], 9, 4)
+            assert (got == img[:, 3:4, 5:6]).all()
+    flat = np.full((1, 9, 16, 2), 255, np.uint8)
+    for m in (rotation_m(16, 9, 33.0), shear_m(0.4, -0.3, 2.5, -1.25), scale_matrix(2, 1), identity(-40, 3)):
+        for mode in MODES:
+            assert (cpu_warp_run(pkg, L, flat, m, 21, 14, mode, CLAMP, 0) == 255).all()
+            assert (cpu_warp_run(pkg, L, flat, m, 21, 14, mode, CONSTANT, 255) == 255).all()
+            assert (ref_warp(flat, m, 21, 14, mode, CONSTANT, 255) == 255).all()
+
+
+@pytest.mark.parametrize("ratio", [(2, 1), (4, 1), (1, 2), (1, 4), (1, 8)], ids=lambda r: f"{r[0]}over{r[1]}")
+def test_clamp_scale_equals_the_resize(pkg, L, ratio):
+    num, den = ratio
+    img = np.random.default_rng(3).integers(0, 256, size=(2, 24, 40, 3), dtype=np.uint8)
+    wo, ho = 40 * num // den, 24 * num // den
+    want = ref_resize(img, wo, ho)
+    m = scale_matrix(num, den)
+    assert np.array_equal(ref_warp(img, m, wo, ho, BILINEAR, CLAMP), want)
+    assert np.array_equal(cpu_warp_run(pkg, L, img, m, wo, ho, BILINEAR, CLAMP), want)
+
+
+@pytest.mark.parametrize("case", ["rot30", "rot-17.3", "rot45x1.3", "shear", "shear2"])
+def test_bilinear_is_within_the_bound_of_float_bilinear(pkg, L, case):
+    """The header's bound: less than 0.5 + 255 * 2^-11 from real-valued bilinear at the exact Q16 position (each axis
+    rounded by at most 2^-12 at slope at most 255, one final rounding), on a 0/255 checkerboard with noise."""
+    h, w = 33, 48
+    m = {"rot30": rotation_m(w, h, 30.0), "rot-17.3": rotation_m(w, h, -17.3), "rot45x1.3": rotation_m(w, h, 45.0, 1.3),
+         "shear": shear_m(0.5, 0.0, -3.3, 1.7), "shear2": shear_m(-0.25, 0.4, 6.1, -2.9)}[case]
+    rng = np.random.default_rng(len(case))
+    yy, xx = np.mgrid[0:h, 0:w]
+    board = (((yy + xx) & 1) * 255).astype(np.int64)[None, :, :, None] + rng.integers(-20, 21, size=(2, h, w, 3))
+    img = np.clip(board, 0, 255).astype(np.uint8)
+    for border in BORDERS:
+        real = float_warp(img, m, 61, 40, border, 90)
+        restated = ref_warp(img, m, 61, 40, BILINEAR, border, 90)
+        assert np.array_equal(cpu_warp_run(pkg, L, img, m, 61, 40, BILINEAR, border, 90), restated)
+        assert np.abs(restated.astype(np.float64) - real).max() < 0.5 + 255 * 2.0 ** -11
+
+
+def cpu_cases(h, w):
+    """(m, Wo, Ho): inside, partly outside and wholly outside the input; a reduction; extreme entries."""
+    return [(rotation_m(w, h, 30.0), w, h), (rotation_m(w, h, -75.0, 0.7), w + 5, h + 3), (shear_m(0.5, -0.2, -4.5, 3.25), 2 * w + 1, max(1, h // 2)),
+            (identity(w + 10, 0), w, h), (identity(-3 * w, -3 * h), 7, 5), (scale_matrix(1, 8), max(1, w // 8), max(1, h // 8)),
+            ([LIN_MAX, -LIN_MAX, OFF_MAX, -LIN_MAX, LIN_MAX, -OFF_MAX], 5, 4), ([3, -2, (w - 1) * Q + 65535, 1, 5, -1], 9, 9), (identity(), 1, 1)]
+
+
+@pytest.mark.parametrize("shape", [(3, 33, 40, 3), (1, 1, 1, 3), (2, 9, 5, 1), (1, 17, 16, 4), (1, 20, 7, 5), (1, 31, 48, 2)], ids=lambda s: "x".join(map(str, s)))
+def test_cpu_run_matches_the_restatement(pkg, L, shape):
+    img = np.random.default_rng(sum(shape)).integers(0, 256, size=shape, dtype=np.uint8)
+    n, h, w, c = shape
+    for m, wo, ho in cpu_cases(h, w):
+        for mode in MODES:
+            for border in BORDERS:
+                want = ref_warp(img, m, wo, ho, mode, border, 201)
+                assert want.shape == (n, ho, wo, c)
+                for nt in (1, 3):
+                    assert np.array_equal(cpu_warp_run(pkg, L, img, m, wo, ho, mode, border, 201, nt), want), (shape, m, wo, ho, mode, border, nt)
+
+
+def test_set_matrix_and_rotation(pkg, L):
+    img = np.random.default_rng(5).integers(0, 256, size=(1, 30, 44, 3), dtype=np.uint8)
+    fwd = (C.c_double * 6)()
+    for cx, cy, ang, sc in ((21.5, 14.5, 30.0, 1.0), (0.0, 0.0, -17.3, 0.67), (10.0, 40.0, 135.0, 1.5), (21.5, 14.5, 90.0, 1.0)):
+        assert L.mi_blur_warp_rotation(cx, cy, ang, sc, fwd) == pkg.OK
+        want_fwd = rotation_forward(cx, cy, ang, sc)
+        assert np.allclose(list(fwd), want_fwd, rtol=0, atol=1e-9)
+        assert np.allclose(pkg.rotation_matrix((cx, cy), ang, sc), [want_fwd[:3], want_fwd[3:]], rtol=0, atol=1e-9)
+        a, b = pkg.Warp(44, 30, BILINEAR, CONSTANT, 0), pkg.Warp(44, 30, BILINEAR, CONSTANT, 0)
+        assert L.mi_blur_warp_set_matrix(C.byref(a), fwd, 0) == pkg.OK
+        inv = invert(list(fwd))
+        assert L.mi_blur_warp_set_matrix(C.byref(b), (C.c_double * 6)(*inv), 1) == pkg.OK
+        assert max(abs(x - y) for x, y in zip(a.m, b.m)) <= 1              # the same inverse, computed twice in double
+        assert max(abs(x - y) for x, y in zip(b.m, quantise(inv))) == 0
+        # the forward and the inverse matrix give the same warp (bytes: the library's own inverse against numpy's)
+        got_a = cpu_warp_run(pkg, L, img, list(a.m), 44, 30)
+        assert np.array_equal(got_a, ref_warp(img, list(a.m), 44, 30))
+        if list(a.m) == list(b.m):
+            assert np.array_equal(got_a, cpu_warp_run(pkg, L, img, list(b.m), 44, 30))
+    # a right angle about the centre of a square is exact: np.rot90
+    sq = np.random.default_rng(6).integers(0, 256, size=(1, 12, 12, 2), dtype=np.uint8)
+    assert np.array_equal(pkg.rotate(sq, 90.0, device=pkg.DEVICE_CPU), np.rot90(sq, 1, axes=(1, 2)))
+    assert np.array_equal(pkg.rotate(sq, 180.0, device=pkg.DEVICE_CPU), np.rot90(sq, 2, axes=(1, 2)))
+    wp = pkg.Warp(4, 4, BILINEAR, CLAMP, 0)
+    keep = (C.c_int64 * 6)(1, 2, 3, 4, 5, 6)
+    wp.m = keep
+    d6 = lambda *v: (C.c_double * 6)(*v)
+    for bad, inverse in ((d6(1, 2, 0, 2, 4, 0), 0), (d6(0, 0, 0, 0, 0, 0), 0), (d6(float("nan"), 0, 0, 0, 1, 0), 1), (d6(1, 0, float("inf"), 0, 1, 0), 1),
+                         (d6(1025.0, 0, 0, 0, 1, 0), 1), (d6(1, 0, 2.0 ** 30 + 1, 0, 1, 0), 1), (d6(1e-4, 0, 0, 0, 1e-4, 0), 0), (d6(1, 0, 0, 0, 1, -2.0 ** 31), 1)):
+        assert L.mi_blur_warp_set_matrix(C.byref(wp), bad, inverse) == pkg.ERR_INVALID, list(bad)
+        assert list(wp.m) == [1, 2, 3, 4, 5, 6]
+    assert L.mi_blur_warp_set_matrix(None, d6(1, 0, 0, 0, 1, 0), 1) == pkg.ERR_INVALID
+    assert L.mi_blur_warp_set_matrix(C.byref(wp), None, 1) == pkg.ERR_INVALID
+    assert L.mi_blur_warp_rotation(0.0, 0.0, 10.0, 1.0, None) == pkg.ERR_INVALID
+    assert L.mi_blur_warp_rotation(float("nan"), 0.0, 10.0, 1.0, fwd) == pkg.ERR_INVALID
+    assert L.mi_blur_warp_set_matrix(C.byref(wp), d6(1024.0, 0, 2.0 ** 30, 0, -1024.0, -2.0 ** 30), 1) == pkg.OK      # the limits themselves
+    assert list(wp.m) == [LIN_MAX, 0, OFF_MAX, 0, -LIN_MAX, -OFF_MAX]
+
+
+def bad_calls(pkg, call):
+    """call(in, out, w, h, c, warp) -> status: every argument set the header calls invalid."""
+    a = np.zeros((8, 8, 3), np.uint8)
+    b = np.zeros((16, 16, 3), np.uint8)
+    mk = lambda wo=16, ho=16, mode=BILINEAR, border=CONSTANT, fill=0, m=None: make_warp(pkg, m or identity(), wo, ho, mode, border, fill)
+    good = mk()
+    ref = lambda s: None if s is None else C.byref(s)
+    ia, ib = a.ctypes.data, b.ctypes.data
+    bad = [(ia, ib, 8, 8, 3, None), (None, ib, 8, 8, 3, good), (ia, None, 8, 8, 3, good), (ia, ia, 8, 8, 3, good)]
+    for kw in [dict(wo=0), dict(ho=0), dict(wo=-3), dict(ho=-1), dict(wo=MAX_DIM + 1, ho=1), dict(wo=1, ho=MAX_DIM + 1), dict(mode=2), dict(mode=-1),
+               dict(border=2), dict(border=-1), dict(fill=-1), dict(fill=256)]:
+        bad.append((ia, ib, 8, 8, 3, mk(**kw)))
+    for i in range(6):
+        lim = OFF_MAX if i % 3 == 2 else LIN_MAX
+        for v in (lim + 1, -lim - 1):
+            m = identity()
+            m[i] = v
+            bad.append((ia, ib, 8, 8, 3, mk(m=m)))
+    for w, h, c in [(0, 8, 3), (8, 0, 3), (8, 8, 0), (-1, 8, 3), (MAX_DIM + 1, 1, 1), (1, MAX_DIM + 1, 1)]:
+        bad.append((ia, ib, w, h, c, good))
+    bad.append((ia, ib, 8, 8, 3, mk(MAX_DIM, MAX_DIM)))                     # the output image: 3 GiB, over the per-image limit
+    bad.append((ia, ib, 8, 8, 40000, mk(MAX_DIM, 1)))                       # the output row: over INT_MAX / 2
+    for i, o, w, h, c, r in bad:
+        assert call(i, o, w, h, c, ref(r)) == pkg.ERR_INVALID, (i, o, w, h, c, r and (r.out_width, r.out_height, r.mode, r.border, r.fill, list(r.m)))
+    return a, b, good
+
+
+def test_cpu_run_refuses_invalid_arguments(pkg, L):
+    a, b, r = bad_calls(pkg, lambda i, o, w, h, c, r: L.mi_blur_cpu_run_warp(i, o, w, h, c, 1, r, 1))
+    assert L.mi_blur_cpu_run_warp(a.ctypes.data, b.ctypes.data, 8, 8, 3, -1, C.byref(r), 1) == pkg.ERR_INVALID
+    assert L.mi_blur_cpu_run_warp(a.ctypes.data, b.ctypes.data, 8, 8, 3, 1, C.byref(r), 1) == pkg.OK
+    assert L.mi_blur_cpu_run_warp(a.ctypes.data, b.ctypes.data, 8, 8, 3, 0, C.byref(r), 1) == pkg.OK
+    lim = make_warp(pkg, [LIN_MAX, -LIN_MAX, -OFF_MAX, 0, 0, OFF_MAX], 16, 16, BILINEAR, CLAMP, 255)      # the limits themselves are valid
+    assert L.mi_blur_cpu_run_warp(a.ctypes.data, b.ctypes.data, 8, 8, 3, 1, C.byref(lim), 1) == pkg.OK
+
+
+def test_enqueue_invalid_comes_before_no_device(pkg, L):
+    """Every argument is checked before a device is asked for; without a GPU a good call is ERR_NO_DEVICE (with one, the
+    null stream of an empty batch is MI_BLUR_OK)."""
+    a, b, r = bad_calls(pkg, lambda i, o, w, h, c, r: L.mi_blur_enqueue_warp(i, o, w, h, c, 1, r, None))
+    assert L.mi_blur_enqueue_warp(a.ctypes.data, b.ctypes.data, 8, 8, 3, -1, C.byref(r), None) == pkg.ERR_INVALID
+    if L.mi_blur_device_count() <= 0:
+        assert L.mi_blur_enqueue_warp(a.ctypes.data, b.ctypes.data, 8, 8, 3, 1, C.byref(r), None) == pkg.ERR_NO_DEVICE
+        assert L.mi_blur_enqueue_warp(a.ctypes.data, b.ctypes.data, 8, 8, 3, 0, C.byref(r), None) == pkg.ERR_NO_DEVICE
+    else:
+        assert L.mi_blur_enqueue_warp(a.ctypes.data, b.ctypes.data, 8, 8, 3, 0, C.byref(r), None) == pkg.OK
+
+
+def test_ctx_set_refuses_invalid_arguments(pkg, L):
+    """The table of mi_blur_ctx_set_resize: a null context or struct is ERR_INVALID whatever the state, an invalid struct
+    ERR_INVALID before the first submit, anything ERR_STATE after it; a refused set leaves the filter in place."""
+    mk = lambda wo=16, ho=16, mode=BILINEAR, border=CONSTANT, fill=0, m=None: make_warp(pkg, m or identity(), wo, ho, mode, border, fill)
+    with pkg.Context(pkg.DEVICE_CPU, 8, 8, 3, 1, max_batch=1) as ctx:
+        assert L.mi_blur_ctx_set_warp(None, C.byref(mk())) == pkg.ERR_INVALID
+        assert L.mi_blur_ctx_set_warp(ctx.h, None) == pkg.ERR_INVALID
+        over = identity()
+        over[5] = OFF_MAX + 1
+        for bad in [mk(wo=0), mk(ho=0), mk(MAX_DIM + 1, 1), mk(1, MAX_DIM + 1), mk(mode=2), mk(border=2), mk(fill=256), mk(fill=-1), mk(m=over), mk(MAX_DIM, MAX_DIM)]:
+            assert L.mi_blur_ctx_set_warp(ctx.h, C.byref(bad)) == pkg.ERR_INVALID
+        img = np.random.default_rng(2).integers(0, 256, size=(1, 8, 8, 3), dtype=np.uint8)   # refused sets leave the box blur in place
+        out, box = np.empty_like(img), np.empty_like(img)
+        ctx.submit(img.ctypes.data, out.ctypes.data, 1)
+        t = ctx.sync()
+        assert L.mi_blur_cpu_run(img.ctypes.data, box.ctypes.data, 8, 8, 3, 1, 1, 1) == pkg.OK
+        assert np.array_equal(out, box) and t["bytes_alg"] == 2 * img.size
+        assert L.mi_blur_ctx_set_warp(ctx.h, C.byref(mk())) == pkg.ERR_STATE
+        assert L.mi_blur_ctx_set_warp(ctx.h, C.byref(mk(wo=0))) == pkg.ERR_STATE
+        assert L.mi_blur_ctx_set_warp(ctx.h, None) == pkg.ERR_INVALID
+    with pkg.Context(pkg.DEVICE_CPU, MAX_DIM + 1, 2, 1, 1, max_batch=1) as wide:      # the context's own size over MAX_DIM
+        assert L.mi_blur_ctx_set_warp(wide.h, C.byref(mk())) == pkg.ERR_INVALID
+
+
+@pytest.mark.parametrize("target", [(42, 37), (63, 74), (25, 22)], ids=lambda t: "x".join(map(str, t)))
+def test_cpu_context(pkg, L, target):
+    img = np.random.default_rng(23).integers(0, 256, size=(5, 37, 42, 3), dtype=np.uint8)
+    n, h, w, c = img.shape
+    wo, ho = target
+    m = rotation_m(w, h, 25.0, 1.1)
+    for mode in MODES:
+        for border in BORDERS:
+            want = ref_warp(img, m, wo, ho, mode, border, 33)
+            with pkg.Context(pkg.DEVICE_CPU, w, h, c, 1, max_batch=n, n_threads=3) as ctx:
+                wp = make_warp(pkg, m, wo, ho, mode, border, 33)
+                assert L.mi_blur_ctx_set_warp(ctx.h, C.byref(wp)) == pkg.OK
+                C.memset(C.byref(wp), 0xFF, C.sizeof(wp))                    # the context keeps a copy
+                out = np.full(want.size + 128, 0xA5, np.uint8)
+                ctx.submit(img.ctypes.data, out.ctypes.data + 64, n)         # pageable memory, guards either side
+                t = ctx.sync()
+                assert np.array_equal(out[64:64 + want.size].reshape(want.shape), want)
+                assert (out[:64] == 0xA5).all() and (out[64 + want.size:] == 0xA5).all()
+                assert t["bytes_alg"] == img.size + want.size and t["images"] == n
+                pitch = w * c
+                o = np.zeros_like(img)
+                assert L.mi_blur_submit_band(ctx.h, img.ctypes.data, o.ctypes.data, 20, 2, 2) == pkg.ERR_UNSUPPORTED
+                assert L.mi_blur_submit_bands(ctx.h, img.ctypes.data, o.ctypes.data, n, h * pitch, 20, 2, 2) == pkg.ERR_UNSUPPORTED
+                assert L.mi_blur_submit_planar(ctx.h, img.ctypes.data, o.ctypes.data, n, 0) == pkg.ERR_UNSUPPORTED
+                assert L.mi_blur_resident_run(ctx.h, 1, 1, 0) == pkg.ERR_UNSUPPORTED
+                assert L.mi_blur_resident_run_fused(ctx.h, 1, 1, 0) == pkg.ERR_UNSUPPORTED
+                assert not o.any()
+                assert L.mi_blur_ctx_set_warp(ctx.h, C.byref(make_warp(pkg, m, wo, ho, mode, border, 33))) == pkg.ERR_STATE
+
+
+def test_setters_replace_each_other(pkg, L):
+    img = np.random.default_rng(29).integers(0, 256, size=(2, 20, 24, 3), dtype=np.uint8)
+    n, h, w, c = img.shape
+    m = rotation_m(w, h, -40.0)
+
+    def run(setters, want):
+        with pkg.Context(pkg.DEVICE_CPU, w, h, c, 1, max_batch=n) as ctx:
+            for s in setters:
+                s(ctx)
+            out = np.full(want.size + 64, 0xA5, np.uint8)
+            ctx.submit(img.ctypes.data, out.ctypes.data, n)
+            t = ctx.sync()
+            assert np.array_equal(out[:want.size].reshape(want.shape), want) and (out[want.size:] == 0xA5).all()
+            return t
+    warp = lambda ctx: ctx.set_warp(make_warp(pkg, m, 40, 31, BILINEAR, CLAMP))
+    median = lambda ctx: ctx.set_median(1)
+    resize = lambda ctx: ctx.set_resize(30, 11)
+    rot, med, small = ref_warp(img, m, 40, 31, BILINEAR, CLAMP), cpu_run(MEDIAN, pkg, L, img, 1, 1), ref_resize(img, 30, 11)
+    assert run([warp, median], med)["bytes_alg"] == 2 * img.size          # the last one wins
+    assert run([median, warp], rot)["bytes_alg"] == img.size + rot.size
+    assert run([warp, resize], small)["bytes_alg"] == img.size + small.size
+    assert run([resize, warp], rot)["bytes_alg"] == img.size + rot.size
+
+
+def test_numpy_functions_on_the_cpu_device(pkg, L):
+    rng = np.random.default_rng(31)
+    stack = rng.integers(0, 256, size=(4, 45, 71, 3), dtype=np.uint8)
+    fwd = rotation_forward(20.0, 10.0, 33.0, 0.9)
+    M = [fwd[:3], fwd[3:]]
+    m = quantise(invert(fwd))
+    for img in (stack, stack[0], np.ascontiguousarray(stack[0, :, :, 0])):
+        as4 = img if img.ndim == 4 else img[None] if img.ndim == 3 else img[None, :, :, None]
+        shape = lambda want: want.reshape(want.shape if img.ndim == 4 else want.shape[1:] if img.ndim == 3 else want.shape[1:3])
+        for dsize in (None, (100, 33)):
+            wo, ho = dsize or (71, 45)
+            for mode, mo in (("bilinear", BILINEAR), ("nearest", NEAREST)):
+                for border, bo in (("constant", CONSTANT), ("clamp", CLAMP)):
+                    got = pkg.warp_affine(img, M, dsize, mode, border, 9, device=pkg.DEVICE_CPU, batch=3)
+                    want = shape(ref_warp(as4, m, wo, ho, mo, bo, 9))
+                    assert got.shape == want.shape and got.ndim == img.ndim and np.array_equal(got, want), (img.ndim, dsize, mode, border)
+    inv = invert(fwd)
+    assert np.array_equal(pkg.warp_affine(stack, [inv[:3], inv[3:]], inverse=True, device=pkg.DEVICE_CPU), ref_warp(stack, quantise(inv), 71, 45))
+    assert np.array_equal(pkg.warp_affine(stack, np.array(M), device=pkg.DEVICE_CPU), ref_warp(stack, m, 71, 45))          # bilinear, constant 0 by default
+    assert np.array_equal(pkg.rotate(stack, 30.0, device=pkg.DEVICE_CPU), ref_warp(stack, rotation_m(71, 45, 30.0), 71, 45))  # about the centre
+    assert np.array_equal(pkg.rotate(stack[0], -12.5, 1.2, (3.0, 4.0), (50, 60), "nearest", "clamp", device=pkg.DEVICE_CPU),
+                          ref_warp(stack[:1], rotation_m(71, 45, -12.5, 1.2, (3.0, 4.0)), 50, 60, NEAREST, CLAMP)[0])
+    empty = pkg.warp_affine(np.zeros((0, 45, 71, 3), np.uint8), M, (10, 20), device=pkg.DEVICE_CPU)
+    assert empty.shape == (0, 20, 10, 3) and empty.dtype == np.uint8
+    for bad in (dict(mode="cubic"), dict(border="reflect"), dict(dsize=(0, 20)), dict(fill=256)):
+        with pytest.raises(ValueError):
+            pkg.warp_affine(stack, M, device=pkg.DEVICE_CPU, **bad)
+    with pytest.raises(ValueError):
+        pkg.warp_affine(stack, [[1, 0, 0]], device=pkg.DEVICE_CPU)
+    with pytest.raises(ValueError):
+        pkg.warp_affine(stack.astype(np.float32), M, device=pkg.DEVICE_CPU)
+    with pytest.raises(pkg.MiBlurError):
+        pkg.warp_affine(stack, [[1, 2, 0], [2, 4, 0]], device=pkg.DEVICE_CPU)      # singular
+    with pytest.raises(pkg.MiBlurError):
+        pkg.warp_affine(stack, M, (MAX_DIM + 1, 20), device=pkg.DEVICE_CPU)
+
+
+def test_the_admitted_region_fits_the_lds():
+    """The header's claim, through the restated walk: aligned BILINEAR launches with |m0|+|m1| <= 3Q/2 and |m3|+|m4| <= 3Q/2
+    take the tiled kernel (rotations, enlargements, shears to 0.5, the corners of the region), within 98 rows x 27 chunks."""
+    mats = [rotation_m(256, 192, a) for a in (0, 30, 45, 90, -17.3, 135)] + [scale_matrix(2, 1), scale_matrix(4, 1), shear_m(0.5, 0.5), shear_m(-0.5, 0.5, 9.5, -3.25)]
+    mats += [[3 * Q // 2, 0, 0, 0, 3 * Q // 2, 0], [0, -3 * Q // 2, 255 * Q, 3 * Q // 2, 0, 0], [3 * Q // 4, 3 * Q // 4, 11, -3 * Q // 4, 3 * Q // 4, 100 * Q + 7]]
+    for m in mats:
+        assert in_the_admitted_region(m), m
+        for c in (1, 2, 3, 4):
+            for border in BORDERS:
+                shape = (1, 192, 256, c)
+                assert max_footprint(shape, m, 272, 200, border) <= 98 * 27 * 16
+                assert takes_tiled(shape, m, 272, 200, BILINEAR, border)
+    assert not takes_tiled((1, 512, 512, 1), scale_matrix(1, 8), 64, 64, BILINEAR, CLAMP)         # 512 x 256 pixels under one tile
+    assert not takes_tiled((1, 192, 256, 3), rotation_m(256, 192, 30), 272, 200, NEAREST)
+    assert not takes_tiled((1, 192, 256, 5), rotation_m(256, 192, 30), 272, 200)
+
+
+def test_hosts_refuse_rotate_with_other_filters(pkg, tmp_path):
+    """The command lines are refused while the flags are parsed, before any device is asked for."""
+    pkg.build_native()
+    het, split = os.path.join(pkg.APPS, "heterogeneous_blur"), os.path.join(pkg.APPS, "split_image_blur")
+    base = ["cpu", "0", "35", "--size", "32x24", "--images", "4", "--rotate", "30"]
+    for extra in (["--sigma", "1.0"], ["--median", "3"], ["--erode", "3"], ["--dilate", "3"], ["--morph-gradient", "3"], ["--bilateral", "5"],
+                  ["--conv", "sobel"], ["--pyr-down"], ["--ksize", "5"], ["--resize", "64x48"], ["--resident"], ["--frames", str(tmp_path)]):
+        r = subprocess.run([het, *base, *extra], capture_output=True, text=True, timeout=60)
+        assert r.returncode != 0 and "Error: --rotate excludes" in r.stdout, extra
+    r = subprocess.run([het, "cpu", "0", "35", "--size", "32x24", "--images", "4", "--border-fill", "9"], capture_output=True, text=True, timeout=60)
+    assert r.returncode != 0 and "Error: --border-fill needs --rotate" in r.stdout
+    r = subprocess.run([het, "cpu", "0", "35", "--size", "32x24", "--images", "4", "--nearest"], capture_output=True, text=True, timeout=60)
+    assert r.returncode != 0 and "Error: --nearest needs --resize" in r.stdout
+    for bad in (["--rotate", "abc"], ["--rotate", "30x"], ["--rotate", "30", "--border-fill", "256"], ["--rotate", "30", "--border-fill", "-1"]):
+        r = subprocess.run([het, "cpu", "0", "35", "--size", "32x24", "--images", "4", *bad], capture_output=True, text=True, timeout=60)
+        assert r.returncode != 0 and ("Error: --rotate DEG" in r.stdout or "Error: --border-fill V" in r.stdout), bad
+    r = subprocess.run([split, "0.5", "35", "--size", "32x24", "--images", "4", "--rotate", "30"], capture_output=True, text=True, timeout=60)
+    assert r.returncode != 0 and "--rotate" in r.stdout and "bands are not supported" in r.stdout
+
+
+def test_host_rotates_on_the_cpu_device(pkg, tmp_path):
+    from filter_harness import read_ppm, write_ppm
+    pkg.build_native()
+    het = os.path.join(pkg.APPS, "heterogeneous_blur")
+    img = np.random.default_rng(19).integers(0, 256, size=(48, 64, 3), dtype=np.uint8)
+    src = tmp_path / "in.ppm"
+    write_ppm(src, img)
+    for flags, mode, border, fill, name in (([], BILINEAR, CLAMP, 0, "bilinear"), (["--nearest", "--border-fill", "77"], NEAREST, CONSTANT, 77, "nearest")):
+        dst = tmp_path / f"{name}.ppm"
+        r = subprocess.run([het, "cpu", "0", "35", "--image", str(src), "--images", "4", "--rotate", "30", *flags, "--save", str(dst)],
+                           capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        assert f"Blur kernel: {name} warp, rotate 30 deg, 64x48 -> 64x48" in r.stdout
+        assert np.array_equal(read_ppm(dst), ref_warp(img[None], rotation_m(64, 48, 30.0), 64, 48, mode, border, fill)[0]), name
+
+
+def test_tiled_kernels_use_no_scratch(pkg, tmp_path):
+    """Compiles warp_kernels.hip to gfx950 assembly (no GPU needed): the taps are read from LDS at run-time addresses, but
+    no tiled instantiation may spill or index registers at run time."""
+    out = tmp_path / "k.s"
+    r = subprocess.run([pkg.HIPCC, f"--offload-arch={pkg.ARCH}", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-o", str(out),
+                        os.path.join(pkg.CSRC, "warp_kernels.hip")], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    text = out.read_text()
+    kernels = re.findall(r"\.amdhsa_kernel (\S*blur_warp_tiled_kernel\S*)(.*?)\.end_amdhsa_kernel", text, re.S)
+    assert len(kernels) == 4, [k for k, _ in kernels]                        # 1-4 channels
+    for name, body in kernels:
+        assert re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", body).group(1) == "0", name
+        assert re.search(r"\.amdhsa_group_segment_fixed_size (\d+)", body).group(1) == "0", name     # all LDS is dynamic: sized per launch
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
+def test_cpu_warp_clean_under_asan_ubsan(pkg, tmp_path):
+    exe = tmp_path / "san_warp"
+    cmd = ["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+           "-fno-omit-frame-pointer", "-I", pkg.CSRC, os.path.join(ROOT, "tests", "san_warp.cpp"),
+           os.path.join(pkg.CSRC, "cpu_device.cpp"), "-lpthread", "-o", str(exe)]
+    subprocess.run(cmd, check=True, capture_output=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "random and edge warp cases clean" in r.stdout, r.stdout + r.stderr
+    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr
