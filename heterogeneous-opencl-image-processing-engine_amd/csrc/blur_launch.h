@@ -47,11 +47,11 @@ int launch_conv(const LaunchDesc &d);
 // are MI_BLUR_ERR_UNSUPPORTED.
 int launch_sep_down(const LaunchDesc &d);
 // The resize (FilterKind::RESIZE, resize_kernels.hip): d.in = n_images images of band_rows x width, d.out = n_images
-// images of resize_h x resize_w (out_stride, when given, is measured against that, and may exceed in_stride).  The
+// images of out_h x out_w (out_stride, when given, is measured against that, and may exceed in_stride).  The
 // contract of launch_sep_down: only the whole image, bands and halo pointers are MI_BLUR_ERR_UNSUPPORTED.
 int launch_resize(const LaunchDesc &d);
 // The affine warp (FilterKind::WARP, warp_kernels.hip): d.in = n_images images of band_rows x width, d.out = n_images
-// images of warp_h x warp_w.  The contract of launch_resize.
+// images of out_h x out_w.  The contract of launch_resize.
 int launch_warp(const LaunchDesc &d);
 // Sets what last_kernel() reports for the calling thread.
 void set_last_kernel(const char *name);

@@ -382,30 +382,26 @@ void cpu_sep_down_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, con
     }
 }
 
-// Output rows [Y_begin, Y_end) of the resize of f (f.resize_*) on one W x H image; out = the resized image (dense).
+// Output rows [Y_begin, Y_end) of the resize of f (f.out_w, f.out_h, f.sample_mode) on one W x H image; out = the resized image (dense).
 // xtab: resize_axis of every output column (resize_xtable: built once per call, shared by the threads).  BILINEAR blends
-// the two input rows at the two input columns in 32-bit unsigned, one rounding shift; NEAREST copies pixels.
+// the two input rows at the two input columns with bilinear_blend() (filter.h); NEAREST copies pixels.
 void cpu_resize_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, const Filter &f, int Y_begin, int Y_end, const ResizeCoord *xtab)
 {
-    const int Wo = f.resize_w, Ho = f.resize_h;
+    const int Wo = f.out_w, Ho = f.out_h;
     const size_t pitch = (size_t)W * C, opitch = (size_t)Wo * C;
     for (int Y = Y_begin; Y < Y_end; Y++) {
-        const ResizeCoord cy = resize_axis(H, Ho, f.resize_mode, Y);
+        const ResizeCoord cy = resize_axis(H, Ho, f.sample_mode, Y);
         const uint8_t *ra = in + (size_t)cy.a * pitch, *rb = in + (size_t)cy.b * pitch;
         uint8_t *o = out + (size_t)Y * opitch;
-        if (f.resize_mode == MI_BLUR_RESIZE_NEAREST) {
+        if (f.sample_mode == MI_BLUR_RESIZE_NEAREST) {
             for (int X = 0; X < Wo; X++)
                 for (int c = 0; c < C; c++) o[(size_t)X * C + c] = ra[(size_t)xtab[X].a * C + c];
             continue;
         }
-        const uint32_t fy = (uint32_t)cy.f, gy = 2048u - fy;
         for (int X = 0; X < Wo; X++) {
-            const uint32_t fx = (uint32_t)xtab[X].f, gx = 2048u - fx;
             const size_t xa = (size_t)xtab[X].a * C, xb = (size_t)xtab[X].b * C;
-            for (int c = 0; c < C; c++) {
-                const uint32_t top = gx * ra[xa + c] + fx * ra[xb + c], bot = gx * rb[xa + c] + fx * rb[xb + c];
-                o[(size_t)X * C + c] = (uint8_t)((gy * top + fy * bot + (1u << 21)) >> 22);
-            }
+            for (int c = 0; c < C; c++)
+                o[(size_t)X * C + c] = (uint8_t)bilinear_blend(ra[xa + c], ra[xb + c], rb[xa + c], rb[xb + c], (unsigned)xtab[X].f, (unsigned)cy.f);
         }
     }
 }
@@ -414,12 +410,12 @@ void cpu_resize_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, const
 // Every byte through warp_coord() and warp_sample() (filter.h), the functions of the GPU's generic kernel.
 void cpu_warp_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, const Filter &f, int Y_begin, int Y_end)
 {
-    const int Wo = f.warp_w;
+    const int Wo = f.out_w;
     const size_t pitch = (size_t)W * C, opitch = (size_t)Wo * C;
     for (int Y = Y_begin; Y < Y_end; Y++) {
         uint8_t *o = out + (size_t)Y * opitch;
         for (int X = 0; X < Wo; X++) {
-            const WarpCoord q = warp_coord(f.warp_m, f.warp_mode, W, H, X, Y);
+            const WarpCoord q = warp_coord(f.warp_m, f.sample_mode, W, H, X, Y);
             for (int c = 0; c < C; c++)
                 o[(size_t)X * C + c] = (uint8_t)warp_sample(in + c, pitch, C, W, H, f.warp_border, (unsigned)f.warp_fill, q);
         }
@@ -430,8 +426,8 @@ void cpu_warp_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, const F
 std::vector<ResizeCoord> resize_xtable(int W, const Filter &f)
 {
     if (f.kind != FilterKind::RESIZE) return {};
-    std::vector<ResizeCoord> t((size_t)f.resize_w);
-    for (int X = 0; X < f.resize_w; X++) t[(size_t)X] = resize_axis(W, f.resize_w, f.resize_mode, X);
+    std::vector<ResizeCoord> t((size_t)f.out_w);
+    for (int X = 0; X < f.out_w; X++) t[(size_t)X] = resize_axis(W, f.out_w, f.sample_mode, X);
     return t;
 }
 

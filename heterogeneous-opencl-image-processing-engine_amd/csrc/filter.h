@@ -1,10 +1,13 @@
 // filter.h — internal: the one filter a launch, a context or a CPU run applies, in the form the GPU kernels (the .hip
-// files) and the CPU device (cpu_device.cpp) take it, and the size of its output.  Plain C++, no HIP.
+// files) and the CPU device (cpu_device.cpp) take it, the size of its output, and (last section) the tile geometry the
+// tiled kernels and their host-side LDS sizing share.  Plain C++, no HIP: g++ compiles it (tests/san_*.cpp).
 #pragma once
 
 #include "../../include/mi_blur.h"
 
 #include <limits.h>
+#include <stddef.h>
+#include <stdint.h>
 
 namespace mi_blur {
 
@@ -27,10 +30,10 @@ enum class FilterKind { BOX, SEP, MEDIAN, MORPH, BILATERAL, CONV, SEP_DOWN, RESI
 // conv_k[t][(j + 7) * 15 + (i + 7)] = K[j][i] (t = 0) or K2[j][i] (t = 1, MAG only; zeros otherwise), 0 beyond the radii.
 // SEP_DOWN: the separable kernel `taps` on the whole image, of whose result only column down_ox + X * down_sx and row
 // down_oy + Y * down_sy are kept (mi_blur_decimation): its output is smaller than its input.
-// RESIZE: the fixed-point resize (mi_blur_resize) to resize_w x resize_h in `resize_mode`: the output may be smaller or
+// RESIZE: the fixed-point resize (mi_blur_resize) to out_w x out_h in `sample_mode`: the output may be smaller or
 // larger than the input, in either axis.
-// WARP: the affine warp (mi_blur_warp) to warp_w x warp_h: output pixel (X, Y) samples the input at the Q16 position
-// warp_m maps it to, in `warp_mode`, with the border rule `warp_border` / `warp_fill`.  warp_m is the only map source
+// WARP: the affine warp (mi_blur_warp) to out_w x out_h: output pixel (X, Y) samples the input at the Q16 position
+// warp_m maps it to, in `sample_mode`, with the border rule `warp_border` / `warp_fill`.  warp_m is the only map source
 // there is; whatever produces positions goes through warp_position() below, so another source would slot in there.
 struct Filter {
     FilterKind kind;
@@ -43,8 +46,8 @@ struct Filter {
     int32_t conv_bias = 0;
     int16_t conv_k[2][15 * 15] = {};
     int down_sx = 1, down_sy = 1, down_ox = 0, down_oy = 0;   // SEP_DOWN (strides 1..4, phases below them); after the older fields, so the initialisers above stay
-    int resize_w = 0, resize_h = 0, resize_mode = 0;          // RESIZE (1..MI_BLUR_RESIZE_MAX_DIM each way, mi_blur_resize_mode); after them, for the same reason
-    int warp_w = 0, warp_h = 0, warp_mode = 0, warp_border = 0, warp_fill = 0;   // WARP (size and mode as RESIZE, mi_blur_warp_border, fill 0..255); last, for the same reason
+    int out_w = 0, out_h = 0, sample_mode = 0;                // RESIZE and WARP: the output image (1..MI_BLUR_RESIZE_MAX_DIM each way) and mi_blur_resize_mode; after them, for the same reason
+    int warp_border = 0, warp_fill = 0;                       // WARP (mi_blur_warp_border, fill 0..255); last, for the same reason
     int64_t warp_m[6] = {};                                   // WARP: the OUTPUT -> INPUT map, Q16, row-major 2 x 3
 };
 
@@ -77,15 +80,26 @@ MI_BLUR_HD inline ResizeCoord resize_axis(int n_in, int n_out, int mode, int X)
     r.b = i0 + 1 > n_in - 1 ? n_in - 1 : i0 + 1;
     return r;
 }
-// A resize that is valid for a W x H image of C channels: sizes 1..MI_BLUR_RESIZE_MAX_DIM both sides, a known mode, and
-// input and output images inside the per-image byte limits of a launch.
-inline bool resize_ok(const mi_blur_resize *r, int W, int H, int C)
+// A resize to out_w x out_h in `mode` that is valid for a W x H image of C channels: sizes 1..MI_BLUR_RESIZE_MAX_DIM both
+// sides, a known mode, and input and output images inside the per-image byte limits of a launch.  (A Filter's fields or the ABI struct's.)
+inline bool resize_ok(int out_w, int out_h, int mode, int W, int H, int C)
 {
-    return r && r->out_width >= 1 && r->out_height >= 1 && r->out_width <= MI_BLUR_RESIZE_MAX_DIM && r->out_height <= MI_BLUR_RESIZE_MAX_DIM &&
+    return out_w >= 1 && out_h >= 1 && out_w <= MI_BLUR_RESIZE_MAX_DIM && out_h <= MI_BLUR_RESIZE_MAX_DIM &&
            W >= 1 && H >= 1 && C >= 1 && W <= MI_BLUR_RESIZE_MAX_DIM && H <= MI_BLUR_RESIZE_MAX_DIM &&
-           (r->mode == MI_BLUR_RESIZE_NEAREST || r->mode == MI_BLUR_RESIZE_BILINEAR) &&
+           (mode == MI_BLUR_RESIZE_NEAREST || mode == MI_BLUR_RESIZE_BILINEAR) &&
            (long long)W * C <= INT_MAX / 2 && (long long)W * C * H <= INT_MAX &&
-           (long long)r->out_width * C <= INT_MAX / 2 && (long long)r->out_width * C * r->out_height <= INT_MAX;
+           (long long)out_w * C <= INT_MAX / 2 && (long long)out_w * C * out_h <= INT_MAX;
+}
+inline bool resize_ok(const mi_blur_resize *r, int W, int H, int C) { return r && resize_ok(r->out_width, r->out_height, r->mode, W, H, C); }
+
+// The blend of four taps a b / c d with the weights fx, fy (0..BLEND_ONE) of the right column and the lower row, one
+// rounding: the one every bilinear sample of RESIZE and WARP goes through (the tiled kernels in its v_mad_u32_u24 form,
+// lerp24() of kernel_common.h, on the same constants).  fx = fy = 0 (NEAREST) gives tap a back exactly.
+constexpr unsigned BLEND_ONE = 2048u, BLEND_SHIFT = 22, BLEND_BIAS = 1u << (BLEND_SHIFT - 1);   // BLEND_ONE^2 = 1 << BLEND_SHIFT
+MI_BLUR_HD inline unsigned bilinear_blend(unsigned a, unsigned b, unsigned c, unsigned d, unsigned fx, unsigned fy)
+{
+    const unsigned top = (BLEND_ONE - fx) * a + fx * b, bot = (BLEND_ONE - fx) * c + fx * d;
+    return ((BLEND_ONE - fy) * top + fy * bot + BLEND_BIAS) >> BLEND_SHIFT;
 }
 
 // ---- the affine warp (include/mi_blur.h, "Affine warp").  The GPU kernels, the CPU device and mi_blur_warp_coord all
@@ -118,12 +132,6 @@ MI_BLUR_HD inline WarpCoord warp_coord(const int64_t *m, int mode, int W, int H,
     const WarpAxis ax = warp_axis(s.sx, mode, W), ay = warp_axis(s.sy, mode, H);
     return {ax.i0, ay.i0, ax.f, ay.f};
 }
-// The blend of four taps, one rounding.  NEAREST comes through with fx = fy = 0, which gives tap a back exactly.
-MI_BLUR_HD inline unsigned warp_blend(unsigned a, unsigned b, unsigned c, unsigned d, unsigned fx, unsigned fy)
-{
-    const unsigned top = (2048u - fx) * a + fx * b, bot = (2048u - fx) * c + fx * d;
-    return ((2048u - fy) * top + fy * bot + (1u << 21)) >> 22;
-}
 // One output byte from the W x H image whose channel-c bytes start at img (pitch bytes per row, C per pixel), for
 // coordinates clamped by warp_axis (n > 0).  Each tap is decided on its own: CLAMP clamps its index, CONSTANT makes it
 // `fill` when it lies outside the image.
@@ -137,7 +145,7 @@ MI_BLUR_HD inline unsigned warp_sample(const uint8_t *img, size_t pitch, int C, 
         const bool ixa = xa == q.x0, ixb = xb == q.x0 + 1, iya = ya == q.y0, iyb = yb == q.y0 + 1;
         a = ixa && iya ? a : fill; b = ixb && iya ? b : fill; c = ixa && iyb ? c : fill; d = ixb && iyb ? d : fill;
     }
-    return warp_blend(a, b, c, d, (unsigned)q.fx, (unsigned)q.fy);
+    return bilinear_blend(a, b, c, d, (unsigned)q.fx, (unsigned)q.fy);
 }
 // The input pixels the taps of output pixels [X0, X1] x [Y0, Y1] (inclusive) can touch: an affine map has its extrema
 // at the four corners and warp_axis is monotone in S, so the box of the corners' taps, with the + 1 tap, holds them all.
@@ -165,20 +173,22 @@ MI_BLUR_HD inline WarpBox warp_footprint(const int64_t *m, int mode, int border,
     }
     return b;
 }
-// A warp that is valid for a W x H image of C channels: the sizes, mode and byte limits of resize_ok(), a known border,
-// fill 0..255, the linear part within 2^26 and the translation within 2^46 (Q16), so positions stay below 2^47.
-inline bool warp_ok(const mi_blur_warp *w, int W, int H, int C)
+// A warp that is valid for a W x H image of C channels: the sizes, mode and byte limits of resize_ok(), and what
+// warp_map_ok() adds: a known border, fill 0..255, the linear part within 2^26 and the translation within 2^46 (Q16), so
+// positions stay below 2^47.
+inline bool warp_map_ok(int border, int fill, const int64_t *m)
 {
-    if (!w) return false;
-    const mi_blur_resize r{w->out_width, w->out_height, w->mode};
-    if (!resize_ok(&r, W, H, C)) return false;
-    if ((w->border != MI_BLUR_WARP_CLAMP && w->border != MI_BLUR_WARP_CONSTANT) || w->fill < 0 || w->fill > 255) return false;
+    if ((border != MI_BLUR_WARP_CLAMP && border != MI_BLUR_WARP_CONSTANT) || fill < 0 || fill > 255) return false;
     const int64_t lin = (int64_t)1 << 26, off = (int64_t)1 << 46;
     for (int i = 0; i < 6; i++) {
         const int64_t lim = i % 3 == 2 ? off : lin;
-        if (w->m[i] > lim || w->m[i] < -lim) return false;
+        if (m[i] > lim || m[i] < -lim) return false;
     }
     return true;
+}
+inline bool warp_ok(const mi_blur_warp *w, int W, int H, int C)
+{
+    return w && resize_ok(w->out_width, w->out_height, w->mode, W, H, C) && warp_map_ok(w->border, w->fill, w->m);
 }
 
 // Output size of a decimation of a W x H image: kept columns / rows (> 0 for a valid decimation, down_ok()).
@@ -201,8 +211,7 @@ struct OutShape { int width, rows; };
 inline OutShape out_shape(const Filter &f, int W, int band_rows, int y0, int y1)
 {
     if (f.kind == FilterKind::SEP_DOWN) return {down_cols(W, f.down_sx, f.down_ox), down_rows(band_rows, f.down_sy, f.down_oy)};
-    if (f.kind == FilterKind::RESIZE) return {f.resize_w, f.resize_h};
-    if (f.kind == FilterKind::WARP) return {f.warp_w, f.warp_h};
+    if (f.kind == FilterKind::RESIZE || f.kind == FilterKind::WARP) return {f.out_w, f.out_h};
     return {W, y1 - y0};
 }
 
@@ -246,7 +255,7 @@ inline int filter_resize(const mi_blur_resize *r, Filter *f)
 {
     if (!f || !resize_ok(r, 1, 1, 1)) return MI_BLUR_ERR_INVALID;
     *f = Filter{FilterKind::RESIZE, 0, {}};
-    f->resize_w = r->out_width; f->resize_h = r->out_height; f->resize_mode = r->mode;
+    f->out_w = r->out_width; f->out_h = r->out_height; f->sample_mode = r->mode;
     return MI_BLUR_OK;
 }
 
@@ -255,7 +264,7 @@ inline int filter_warp(const mi_blur_warp *w, Filter *f)
 {
     if (!f || !warp_ok(w, 1, 1, 1)) return MI_BLUR_ERR_INVALID;
     *f = Filter{FilterKind::WARP, 0, {}};
-    f->warp_w = w->out_width; f->warp_h = w->out_height; f->warp_mode = w->mode; f->warp_border = w->border; f->warp_fill = w->fill;
+    f->out_w = w->out_width; f->out_h = w->out_height; f->sample_mode = w->mode; f->warp_border = w->border; f->warp_fill = w->fill;
     for (int i = 0; i < 6; i++) f->warp_m[i] = w->m[i];
     return MI_BLUR_OK;
 }
@@ -311,6 +320,134 @@ inline int filter_conv(const mi_blur_conv *k, Filter *f)
         for (int j = 0; j < ny; j++)
             for (int i = 0; i < nx; i++) f->conv_k[t][(j - k->ry + 7) * 15 + (i - k->rx + 7)] = (t ? k->k2 : k->k)[j * nx + i];
     return MI_BLUR_OK;
+}
+
+// ---- Tile geometry of the tiled kernels, and the LDS arithmetic of the two that stage a footprint they compute
+// (blur_resize_tiled_kernel, blur_warp_tiled_kernel).  The kernels index their LDS with these functions and the host sizes
+// it with the same ones, walking the tiles of a launch, so the two agree by construction; tests/san_tile_bounds.cpp
+// walks them again on the CPU under sanitizers and checks every position against the size.
+constexpr int TILE_TH = 32;         // rows per tile
+constexpr int TILE_NCOLS = 32;      // at most this many 16-byte chunk columns per tile
+
+// Rows of cpr chunks x `rows` rows cut into tiles: strips of whole units of `unit` chunks, at most max_units of them,
+// all strips but the last equally wide; TILE_TH rows.  kernel_common.h: fill_tiles() hands it to the kernels, whose
+// tile_coords() gives block L the tile tile_at(g, rows, L % nstrips, L / nstrips % ntiles_y).
+struct TileGrid { int cpr, nstrips, ncols, ntiles_y; };
+inline TileGrid tile_grid(int cpr, int rows, int unit = 1, int max_units = TILE_NCOLS)
+{
+    const int units = cpr / unit, nstrips = (units + max_units - 1) / max_units;
+    return {cpr, nstrips, unit * ((units + nstrips - 1) / nstrips), (rows + TILE_TH - 1) / TILE_TH};
+}
+struct Tile { int ty0, rows_out, x0c, nc; };      // first row and rows, first chunk column and chunk columns
+inline Tile tile_at(const TileGrid &g, int rows, int strip, int ty)
+{
+    const int ty0 = ty * TILE_TH, x0c = strip * g.ncols;
+    return {ty0, rows - ty0 < TILE_TH ? rows - ty0 : TILE_TH, x0c, g.cpr - x0c < g.ncols ? g.cpr - x0c : g.ncols};
+}
+// The pixels of C bytes that begin in chunks [x0c, x0c + nc) (all of the pixels of a strip that starts and ends on
+// one), and the 16-byte chunks that hold pixels x0..x1.  A tile stages rows r.lo..r.hi of chunks sc.lo..sc.hi of the
+// input, row after row: slot (row - r.lo) * sc.n() + (chunk - sc.lo).
+struct Span { int lo, hi; MI_BLUR_HD int n() const { return hi - lo + 1; } };
+MI_BLUR_HD inline Span tile_pixels(int x0c, int nc, int C) { return {(x0c * 16) / C, ((x0c + nc) * 16 - 1) / C}; }
+MI_BLUR_HD inline Span chunk_span(int x0, int x1, int C) { return {(x0 * C) >> 4, (x1 * C + C - 1) >> 4}; }
+
+// ---- blur_resize_tiled_kernel.  LDS: the x table (one dword per output byte of a tile row), the y table (one per output
+// row), the staged box, then RS_GROUP V rows of one dword per staged byte of a row.  a and b of resize_axis are clamped
+// already, so the box lies inside the image.
+constexpr int RS_GROUP = 8;                         // output rows per pass
+constexpr int RS_XTAB = TILE_NCOLS * 16 * 4;        // bytes of the x table
+constexpr int RS_YTAB = TILE_TH * 4;                // bytes of the y table
+MI_BLUR_HD inline Span resize_stage_rows(int H, int Ho, int ty0, int rows_out)
+{
+    return {resize_axis(H, Ho, MI_BLUR_RESIZE_BILINEAR, ty0).a, resize_axis(H, Ho, MI_BLUR_RESIZE_BILINEAR, ty0 + rows_out - 1).b};
+}
+MI_BLUR_HD inline Span resize_stage_chunks(int W, int Wo, int C, int x0c, int nc)
+{
+    const Span px = tile_pixels(x0c, nc, C);
+    return chunk_span(resize_axis(W, Wo, MI_BLUR_RESIZE_BILINEAR, px.lo).a, resize_axis(W, Wo, MI_BLUR_RESIZE_BILINEAR, px.hi).b, C);
+}
+// x table entry of channel c of an output pixel with the coordinate rc: the V dword position of input byte (a, c) |
+// that of (b, c) << 10 | f << 20, the position of staged byte q being plane (q >> 2) & 3, chunk q >> 4, byte q & 3 (a V
+// row is 4 planes of nsc x 4 dwords).  y table entry of an output row: the staged rows a - r0 | b - r0 << 8 | f << 16.
+// Positions below 1024 (nsc <= 64) and rows below 256 are what the fields hold: resize_tiles_fit().
+MI_BLUR_HD inline uint32_t resize_v_pos(int q, int nsc) { return (uint32_t)(((q >> 2) & 3) * nsc * 4 + (q >> 4) * 4 + (q & 3)); }
+MI_BLUR_HD inline uint32_t resize_x_entry(const ResizeCoord &rc, int C, int c, int sc0, int nsc)
+{
+    return resize_v_pos(rc.a * C + c - sc0 * 16, nsc) | (resize_v_pos(rc.b * C + c - sc0 * 16, nsc) << 10) | ((uint32_t)rc.f << 20);
+}
+MI_BLUR_HD inline uint32_t resize_x_pos_a(uint32_t e) { return e & 1023u; }
+MI_BLUR_HD inline uint32_t resize_x_pos_b(uint32_t e) { return (e >> 10) & 1023u; }
+MI_BLUR_HD inline uint32_t resize_x_f(uint32_t e) { return e >> 20; }
+MI_BLUR_HD inline uint32_t resize_y_entry(const ResizeCoord &rc, int r0) { return (uint32_t)(rc.a - r0) | ((uint32_t)(rc.b - r0) << 8) | ((uint32_t)rc.f << 16); }
+MI_BLUR_HD inline uint32_t resize_y_row_a(uint32_t e) { return e & 0xffu; }
+MI_BLUR_HD inline uint32_t resize_y_row_b(uint32_t e) { return (e >> 8) & 0xffu; }
+MI_BLUR_HD inline uint32_t resize_y_f(uint32_t e) { return e >> 16; }
+// The largest box of a launch, per axis (rows depend on the tile row only, chunks on the strip), whether the table fields
+// hold it (an enlargement stays far inside: at most 34 rows x 35 chunks; else the generic kernel), and the LDS it takes.
+struct ResizeTiles { int max_nsc, max_nsr; };
+inline ResizeTiles resize_tiles(const TileGrid &g, int W, int H, int Wo, int Ho, int C)
+{
+    ResizeTiles t{1, 1};
+    for (int s = 0; s < g.nstrips; s++) {
+        const Tile tl = tile_at(g, Ho, s, 0);
+        const Span sc = resize_stage_chunks(W, Wo, C, tl.x0c, tl.nc);
+        if (sc.n() > t.max_nsc) t.max_nsc = sc.n();
+    }
+    for (int ty = 0; ty < g.ntiles_y; ty++) {
+        const Tile tl = tile_at(g, Ho, 0, ty);
+        const Span r = resize_stage_rows(H, Ho, tl.ty0, tl.rows_out);
+        if (r.n() > t.max_nsr) t.max_nsr = r.n();
+    }
+    return t;
+}
+inline bool resize_tiles_fit(const ResizeTiles &t) { return t.max_nsc <= 64 && t.max_nsr <= 255; }
+inline int resize_v_off(const ResizeTiles &t) { return RS_XTAB + RS_YTAB + t.max_nsr * t.max_nsc * 16; }       // LDS byte offset of the V rows
+inline size_t resize_lds_bytes(const ResizeTiles &t) { return (size_t)resize_v_off(t) + (size_t)RS_GROUP * t.max_nsc * 64u; }
+
+// ---- blur_warp_tiled_kernel.  LDS: the staged box alone, then WARP_LDS_SLACK bytes.  A tile is at most WARP_TILE_PX
+// output pixels wide, in strips of whole units: the smallest run of chunks that starts and ends on a pixel.
+constexpr int WARP_TILE_PX = 64;
+constexpr int warp_unit(int C) { return C == 3 ? 3 : 1; }
+constexpr int warp_max_cols(int C) { return WARP_TILE_PX * C / 16; }
+inline TileGrid warp_grid(int cpr, int Ho, int C) { return tile_grid(cpr, Ho, warp_unit(C), warp_max_cols(C) / warp_unit(C)); }
+// The input pixels a tile's taps can touch (warp_footprint() of its pixels) and whether they miss the image (CONSTANT
+// only: the tile is `fill`).  The box lies inside the image; rows b.y0..b.y1 of chunk_span(b.x0, b.x1, C) are staged.
+MI_BLUR_HD inline WarpBox warp_tile_box(const int64_t *m, int border, int W, int H, int C, int ty0, int rows_out, int x0c, int nc)
+{
+    const Span px = tile_pixels(x0c, nc, C);
+    return warp_footprint(m, MI_BLUR_RESIZE_BILINEAR, border, W, H, px.lo, px.hi, ty0, ty0 + rows_out - 1);
+}
+MI_BLUR_HD inline bool warp_box_empty(const WarpBox &b) { return b.x0 > b.x1 || b.y0 > b.y1; }
+// The taps of a position whose first tap is pixel (x0, y0), clamped into the box b: under CLAMP that is the clamp into
+// the image, under CONSTANT a tap the clamp moves lies outside the image and the kernel replaces it.  off_a, off_b: the
+// LDS byte offsets of pixel xa on rows ya and yb; the tap at xb is the pixel behind it, or the same pixel (`one`) where
+// the clamp met the edge of the box.  The kernel reads warp_read_bytes(C) bytes from the 4-byte aligned address at or
+// below each offset: at most 11 bytes past the start of a pixel inside the box, which WARP_LDS_SLACK keeps inside the LDS.
+struct WarpTap { int off_a, off_b; bool one; };
+MI_BLUR_HD inline int clamp_int(int v, int lo, int hi) { const int u = v > lo ? v : lo; return u < hi ? u : hi; }   // min(max(v, lo), hi)
+MI_BLUR_HD inline WarpTap warp_tap(const WarpBox &b, const Span &sc, int C, int x0, int y0)
+{
+    const int xa = clamp_int(x0, b.x0, b.x1), xb = clamp_int(x0 + 1, b.x0, b.x1);
+    const int ya = clamp_int(y0, b.y0, b.y1), yb = clamp_int(y0 + 1, b.y0, b.y1);
+    const int rowb = sc.n() * 16, col0 = sc.lo * 16;               // bytes of a staged row; image byte column of staged byte 0
+    return {(ya - b.y0) * rowb - col0 + xa * C, (yb - b.y0) * rowb - col0 + xa * C, xb == xa};
+}
+constexpr int warp_read_bytes(int C) { return C == 3 ? 12 : 8; }
+constexpr long long WARP_LDS_SLACK = 16;            // LDS behind the staged box that the tap reads may touch
+constexpr long long WARP_LDS_MAX = 65536 - WARP_LDS_SLACK;   // largest box: with the slack, the dynamic LDS a launch may ask for without raising the limit
+// LDS bytes of the largest box of a launch (the walk stops at the first one over WARP_LDS_MAX: the launch is not admitted).
+inline long long warp_tiles_max_bytes(const TileGrid &g, const int64_t *m, int border, int W, int H, int Ho, int C)
+{
+    long long max_bytes = 0;
+    for (int ty = 0; ty < g.ntiles_y && max_bytes <= WARP_LDS_MAX; ty++)
+        for (int s = 0; s < g.nstrips; s++) {
+            const Tile tl = tile_at(g, Ho, s, ty);
+            const WarpBox b = warp_tile_box(m, border, W, H, C, tl.ty0, tl.rows_out, tl.x0c, tl.nc);
+            if (warp_box_empty(b)) continue;
+            const long long bytes = (long long)(b.y1 - b.y0 + 1) * chunk_span(b.x0, b.x1, C).n() * 16;
+            max_bytes = bytes > max_bytes ? bytes : max_bytes;
+        }
+    return max_bytes;
 }
 
 }  // namespace mi_blur

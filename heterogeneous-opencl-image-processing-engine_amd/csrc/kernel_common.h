@@ -1,6 +1,8 @@
 // kernel_common.h — internal (not part of the C ABI): what the .hip files share below launch(): the launch call, the
-// blockIdx -> tile maps, the template dispatch, the argument checks and parameter fill every family repeats, the host side of the direct layout, and the
-// LDS tile of the sep, morph, bilateral and conv kernels (its coordinates, its staging, its launch geometry).
+// blockIdx -> tile maps, the template dispatch, the argument checks and parameter fill every family repeats, the host side of the direct layout,
+// the tile of all seven tiled kernels (its coordinates and its launch geometry: fill_tiles(), on tile_grid() of filter.h), the
+// staging of the sep, morph, bilateral, conv and sep_down kernels' LDS tile (stage_tile) and of the resize and warp kernels'
+// footprint (stage_box), and the v_mad_u32_u24 form of the bilinear blend (lerp24).
 // Everything here has internal linkage, so libmi_blur.so exports nothing from it.
 #pragma once
 #include "blur_launch.h"
@@ -50,10 +52,11 @@ __device__ __forceinline__ uint32_t window_byte(const uint32_t (&W)[N], int idx)
 
 // The LDS tile blur_sep_tiled_kernel, blur_morph_tiled_kernel, blur_bilateral_tiled_kernel, blur_conv_tiled_kernel and
 // (in input coordinates) blur_sep_down_tiled_kernel work on: rows of whole 16-byte chunks, one workgroup of TILE_THREADS = one tile of TILE_TH output rows x ncols
-// (<= TILE_NCOLS) chunk columns, staged with ry rows above and below and HC halo chunks either side.  The helpers take
+// (<= TILE_NCOLS) chunk columns, staged with ry rows above and below and HC halo chunks either side.  blur_resize_tiled_kernel
+// and blur_warp_tiled_kernel take the tile from the same tile_coords (HC = 0, ry = 0, on the OUTPUT image) and stage the
+// input box under it with stage_box.  The helpers take
 // the kernel arguments they need as scalars: handed the parameter struct by reference the kernels grow by a third.
-constexpr int TILE_TH = 32;         // output rows per tile
-constexpr int TILE_NCOLS = 32;      // at most this many output chunk columns per tile
+// TILE_TH rows x at most TILE_NCOLS chunk columns (filter.h).
 constexpr int TILE_THREADS = 256;
 
 struct TileCoords {
@@ -139,8 +142,26 @@ __device__ __forceinline__ void stage_tile(uint8_t *tile, const uint8_t *img_in,
     }
 }
 
+// Stages nsr rows x nsc chunks that lie inside the image (no clamp), from src = the first chunk of the first row, rows
+// `pitch` bytes apart, at dst: slot s = row * nsc + chunk (filter.h, "Tile geometry").  No barrier: the caller's follows.
+__device__ __forceinline__ void stage_box(uint8_t *dst, const uint8_t *src, int pitch, int nsr, int nsc, int t)
+{
+    const int nslots = nsr * nsc;
+#pragma unroll 2
+    for (int s = t; s < nslots; s += TILE_THREADS) {
+        const int row = s / nsc, cc = s - row * nsc;
+        const uint4 v = *reinterpret_cast<const uint4 *>(src + ((unsigned)row * (unsigned)pitch + (unsigned)cc * 16u));
+        *reinterpret_cast<uint4 *>(dst + (size_t)s * 16u) = v;
+    }
+}
+
+// bilinear_blend() (filter.h) one axis at a time, for operands below 2^24 (bytes, or the first axis' sums < 2^20), so
+// that each product is one v_mad_u32_u24: (BLEND_ONE - f) * a + f * b, and the same with the rounding of the second axis.
+__device__ __forceinline__ uint32_t lerp24(uint32_t a, uint32_t b, uint32_t f) { return __umul24(a, BLEND_ONE - f) + __umul24(b, f); }
+__device__ __forceinline__ uint32_t lerp24_round(uint32_t a, uint32_t b, uint32_t f) { return (lerp24(a, b, f) + BLEND_BIAS) >> BLEND_SHIFT; }
+
 // Output byte idx of a byte-per-thread (generic) kernel: block = output bytes per band, so idx = img * block + rem and
-// rem = (y - y0) * pitch + b, b = x * channels + c.  src = the image's band.
+// rem = (y - y0) * pitch + b, b = x * channels + c (pitch: of the OUTPUT row, where that is not the input's).  src = the image's band.
 struct BytePos {
     long long img, rem;
     int y, b, x, c;
@@ -238,27 +259,34 @@ static inline bool tile_aligned(const LaunchDesc &d)
            d.in_stride % 16 == 0 && d.out_stride % 16 == 0;
 }
 
+// Bytes of one output row: the input's, or the output image's of a whole_image_only filter (out_shape(), filter.h).
+static inline int out_pitch(const LaunchDesc &d) { return out_shape(*d.filter, d.width, d.band_rows, d.y0, d.y1).width * d.channels; }
+
 // The members most kernels' parameter structs have under the same names (a template, not a base struct: the structs'
-// names and layouts are the kernels' mangled names and kernarg layouts).  Stride 0 = laid end to end.
+// names and layouts are the kernels' mangled names and kernarg layouts).  Stride 0 = laid end to end.  A struct with
+// `opitch` belongs to a whole_image_only filter: it gets the output pitch, and its launch sets the y0 (0), y1 or width it carries.
+template <typename P, typename = void> struct has_opitch : std::false_type {};
+template <typename P> struct has_opitch<P, std::void_t<decltype(P::opitch)>> : std::true_type {};
 template <typename P>
 static void fill_band(P &p, const LaunchDesc &d)
 {
     p.in = d.in; p.out = d.out;
-    p.pitch = d.width * d.channels; p.H = d.band_rows; p.y0 = d.y0;
+    p.pitch = d.width * d.channels; p.H = d.band_rows;
+    if constexpr (has_opitch<P>::value) p.opitch = out_pitch(d);
+    else p.y0 = d.y0;
     p.in_stride = d.in_stride ? d.in_stride : dense_in(d);
     p.out_stride = d.out_stride ? d.out_stride : dense_out(d);
 }
 
-// fill_band plus the tile decomposition of the tiled kernels' parameter structs (tile_coords() is the device side) and
-// the grid, one workgroup per tile.  MI_BLUR_ERR_INVALID when the tiles do not number in 31 bits.
+// fill_band plus the tile decomposition g of the tiled kernels' parameter structs (tile_coords() is the device side) and
+// the grid, one workgroup per tile.  MI_BLUR_ERR_INVALID when the tiles do not number in 31 bits.  Without g: the rows
+// [y0, y1) of the band and the chunks of its rows, in strips of up to TILE_NCOLS chunks.
 template <typename P>
-static int fill_tiles(P &p, const LaunchDesc &d, dim3 *grid)
+static int fill_tiles(P &p, const LaunchDesc &d, dim3 *grid, const TileGrid &g)
 {
     fill_band(p, d);
-    p.cpr = p.pitch / 16; p.y1 = d.y1;
-    p.nstrips = (p.cpr + TILE_NCOLS - 1) / TILE_NCOLS;
-    p.ncols = (p.cpr + p.nstrips - 1) / p.nstrips;
-    p.ntiles_y = (d.y1 - d.y0 + TILE_TH - 1) / TILE_TH;
+    if constexpr (!has_opitch<P>::value) p.y1 = d.y1;
+    p.cpr = g.cpr; p.nstrips = g.nstrips; p.ncols = g.ncols; p.ntiles_y = g.ntiles_y;
     const long long nblocks = (long long)d.n_images * p.ntiles_y * p.nstrips;
     if (nblocks > 0x7fffffffLL) return MI_BLUR_ERR_INVALID;
     p.nblocks = (unsigned)nblocks;
@@ -266,6 +294,8 @@ static int fill_tiles(P &p, const LaunchDesc &d, dim3 *grid)
     *grid = dim3((unsigned)nblocks);
     return MI_BLUR_OK;
 }
+template <typename P>
+static int fill_tiles(P &p, const LaunchDesc &d, dim3 *grid) { return fill_tiles(p, d, grid, tile_grid(d.width * d.channels / 16, d.y1 - d.y0)); }
 
 // Grid of a byte-per-thread kernel: 256 threads per block, capped; the kernel grid-strides the rest.
 static inline dim3 byte_grid(long long total)
@@ -280,7 +310,8 @@ static dim3 fill_generic(P &p, const LaunchDesc &d)
     fill_band(p, d);
     p.block = dense_out(d);
     p.total = p.block * d.n_images;
-    p.width = d.width; p.channels = d.channels;
+    p.channels = d.channels;
+    if constexpr (!has_opitch<P>::value) p.width = d.width;
     return byte_grid(p.total);
 }
 

@@ -4,7 +4,9 @@
 //
 // Tiled kernel (blur_resize_tiled_kernel<C>): BILINEAR, 1-4 channels, Wo >= W and Ho >= H, input and output rows of
 // whole 16-byte chunks, 16-byte aligned buffers and strides.  One workgroup = one tile of TILE_TH OUTPUT rows x nc
-// (<= TILE_NCOLS) OUTPUT chunk columns, laid out by tile_coords (kernel_common.h, unchanged, no halo):
+// (<= TILE_NCOLS) OUTPUT chunk columns: the shared fill_tiles / tile_coords (kernel_common.h, no halo) on the OUTPUT image.
+// What a tile stages and where a tap lies in LDS comes from filter.h ("Tile geometry"), as does the host's sizing; the
+// staging is the shared stage_box, the blend the shared lerp24:
 //   * the first threads compute the tile's tables with the exact integer division of resize_axis: one dword per output
 //     BYTE of a tile row (the V positions of its two input bytes and fx), one per output row (the two staged rows and
 //     fy).  No device-side table, no allocation;
@@ -16,22 +18,15 @@
 //     every chunk side by side (V row = 4 planes of nsc x 16 bytes), so a wave's 16-byte writes are contiguous;
 //   * horizontal pass: one output chunk per thread, its 16 table entries held in registers across the groups.  Per output
 //     byte two ds_read_b32 at run-time addresses, two v_mad_u32_u24, one rounding shift; one 16-byte store per chunk.
-//   The host sizes the LDS from the exact largest footprint of the launch (it walks the strips and tile rows with
-//   resize_axis), so no bound on the footprint is assumed.  4 instantiations.
+//   The host sizes the LDS from the exact largest footprint of the launch (resize_tiles(), filter.h: it walks the strips
+//   and tile rows with the kernel's own functions), so no bound on the footprint is assumed.  4 instantiations.
 //
 // Generic kernel (blur_resize_generic_kernel): one output byte per thread, any shape, ratio, mode and alignment.
 #include "kernel_common.h"
 
-#include <algorithm>
-
 namespace mi_blur {
 
 namespace {
-
-constexpr int RS_GROUP = 8;                         // output rows per pass of the tiled kernel
-constexpr int RS_XTAB = TILE_NCOLS * 16 * 4;        // bytes of the x table: one dword per output byte of a tile row
-constexpr int RS_YTAB = TILE_TH * 4;                // bytes of the y table
-constexpr int RS_BIAS = 1 << 21, RS_SHIFT = 22, RS_ONE = 2048;
 
 struct ResizeTiledParams {
     const uint8_t *in;
@@ -59,38 +54,17 @@ __global__ __launch_bounds__(TILE_THREADS) void blur_resize_tiled_kernel(const R
     const int ty0 = tc.ty0, rows_out = tc.rows_out, x0c = tc.x0c, nc = tc.nc;
 
     // footprint: staged rows r0..r1 and staged chunks sc0..sc1 of the input image (uniform)
-    const int r0 = resize_axis(p.H, p.Ho, MI_BLUR_RESIZE_BILINEAR, ty0).a;
-    const int r1 = resize_axis(p.H, p.Ho, MI_BLUR_RESIZE_BILINEAR, ty0 + rows_out - 1).b;
-    const int px0 = (x0c * 16) / C, px1 = ((x0c + nc) * 16 - 1) / C;
-    const int sc0 = (resize_axis(p.W, p.Wo, MI_BLUR_RESIZE_BILINEAR, px0).a * C) >> 4;
-    const int sc1 = (resize_axis(p.W, p.Wo, MI_BLUR_RESIZE_BILINEAR, px1).b * C + C - 1) >> 4;
-    const int nsr = r1 - r0 + 1, nsc = sc1 - sc0 + 1;
+    const Span sr = resize_stage_rows(p.H, p.Ho, ty0, rows_out), sc = resize_stage_chunks(p.W, p.Wo, C, x0c, nc);
+    const int r0 = sr.lo, sc0 = sc.lo, nsr = sr.n(), nsc = sc.n();
 
-    // ---- tables.  x entry of output byte ob: V dword position of in byte (xa, c) | that of (xb, c) << 10 | fx << 20,
-    // the position of staged byte q being plane (q >> 2) & 3, chunk q >> 4, byte q & 3.  y entry: ya - r0 | yb - r0 << 8 | fy << 16
+    // ---- tables (resize_x_entry, resize_y_entry: filter.h): one x entry per output byte of a tile row, one y entry per row
     for (int ob = t; ob < nc * 16; ob += TILE_THREADS) {
         const int gb = x0c * 16 + ob, X = gb / C, c = gb - X * C;
-        const ResizeCoord rc = resize_axis(p.W, p.Wo, MI_BLUR_RESIZE_BILINEAR, X);
-        const int qa = rc.a * C + c - sc0 * 16, qb = rc.b * C + c - sc0 * 16;
-        const uint32_t pa = (uint32_t)(((qa >> 2) & 3) * nsc * 4 + (qa >> 4) * 4 + (qa & 3));
-        const uint32_t pb = (uint32_t)(((qb >> 2) & 3) * nsc * 4 + (qb >> 4) * 4 + (qb & 3));
-        xtab[ob] = pa | (pb << 10) | ((uint32_t)rc.f << 20);
+        xtab[ob] = resize_x_entry(resize_axis(p.W, p.Wo, MI_BLUR_RESIZE_BILINEAR, X), C, c, sc0, nsc);
     }
-    if (t < rows_out) {
-        const ResizeCoord rc = resize_axis(p.H, p.Ho, MI_BLUR_RESIZE_BILINEAR, ty0 + t);
-        ytab[t] = (uint32_t)(rc.a - r0) | ((uint32_t)(rc.b - r0) << 8) | ((uint32_t)rc.f << 16);
-    }
+    if (t < rows_out) ytab[t] = resize_y_entry(resize_axis(p.H, p.Ho, MI_BLUR_RESIZE_BILINEAR, ty0 + t), r0);
     // ---- stage the footprint: nsr rows x nsc chunks, all inside the image
-    {
-        const uint8_t *src = p.in + (long long)tc.img * p.in_stride + ((unsigned)r0 * (unsigned)p.pitch + (unsigned)sc0 * 16u);
-        const int nslots = nsr * nsc;
-#pragma unroll 2
-        for (int s = t; s < nslots; s += TILE_THREADS) {
-            const int row = s / nsc, cc = s - row * nsc;
-            const uint4 v = *reinterpret_cast<const uint4 *>(src + ((unsigned)row * (unsigned)p.pitch + (unsigned)cc * 16u));
-            *reinterpret_cast<uint4 *>(stage + (size_t)s * 16u) = v;
-        }
-    }
+    stage_box(stage, p.in + (long long)tc.img * p.in_stride + ((unsigned)r0 * (unsigned)p.pitch + (unsigned)sc0 * 16u), p.pitch, nsr, nsc, t);
     __syncthreads();
 
     // this thread's output chunk in every group: row hk of the group, chunk column hcc; its 16 table entries
@@ -111,18 +85,18 @@ __global__ __launch_bounds__(TILE_THREADS) void blur_resize_tiled_kernel(const R
         for (int i = t; i < ng * nsc; i += TILE_THREADS) {
             const int k = i / nsc, sc = i - k * nsc;
             const uint32_t ye = ytab[g0 + k];
-            const uint32_t fy = ye >> 16, gy = RS_ONE - fy;
-            const uint4 A = *reinterpret_cast<const uint4 *>(stage + ((size_t)(ye & 0xffu) * nsc + sc) * 16u);
-            const uint4 B = *reinterpret_cast<const uint4 *>(stage + ((size_t)((ye >> 8) & 0xffu) * nsc + sc) * 16u);
+            const uint32_t fy = resize_y_f(ye);
+            const uint4 A = *reinterpret_cast<const uint4 *>(stage + ((size_t)resize_y_row_a(ye) * nsc + sc) * 16u);
+            const uint4 B = *reinterpret_cast<const uint4 *>(stage + ((size_t)resize_y_row_b(ye) * nsc + sc) * 16u);
             const uint32_t a[4] = {A.x, A.y, A.z, A.w}, b[4] = {B.x, B.y, B.z, B.w};
             uint32_t *vp = vbuf + (size_t)k * vrow + sc * 4;
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 uint4 v;
-                v.x = __umul24(a[j] & 0xffu, gy) + __umul24(b[j] & 0xffu, fy);
-                v.y = __umul24((a[j] >> 8) & 0xffu, gy) + __umul24((b[j] >> 8) & 0xffu, fy);
-                v.z = __umul24((a[j] >> 16) & 0xffu, gy) + __umul24((b[j] >> 16) & 0xffu, fy);
-                v.w = __umul24(a[j] >> 24, gy) + __umul24(b[j] >> 24, fy);
+                v.x = lerp24(a[j] & 0xffu, b[j] & 0xffu, fy);
+                v.y = lerp24((a[j] >> 8) & 0xffu, (b[j] >> 8) & 0xffu, fy);
+                v.z = lerp24((a[j] >> 16) & 0xffu, (b[j] >> 16) & 0xffu, fy);
+                v.w = lerp24(a[j] >> 24, b[j] >> 24, fy);
                 *reinterpret_cast<uint4 *>(vp + j * nsc * 4) = v;
             }
         }
@@ -136,9 +110,8 @@ __global__ __launch_bounds__(TILE_THREADS) void blur_resize_tiled_kernel(const R
                 uint32_t w = 0;
 #pragma unroll
                 for (int e = 0; e < 4; e++) {
-                    const uint32_t x = tx[4 * q + e], fx = x >> 20;
-                    const uint32_t s = __umul24(vr[x & 1023u], RS_ONE - fx) + __umul24(vr[(x >> 10) & 1023u], fx);
-                    w |= ((s + RS_BIAS) >> RS_SHIFT) << (8 * e);
+                    const uint32_t x = tx[4 * q + e];
+                    w |= lerp24_round(vr[resize_x_pos_a(x)], vr[resize_x_pos_b(x)], resize_x_f(x)) << (8 * e);
                 }
                 o[q] = w;
             }
@@ -165,90 +138,37 @@ __global__ __launch_bounds__(256) void blur_resize_generic_kernel(const ResizeGe
         const ResizeCoord cx = resize_axis(p.W, p.Wo, p.mode, q.x), cy = resize_axis(p.H, p.Ho, p.mode, q.y);
         const uint8_t *ra = q.src + (size_t)cy.a * (size_t)p.pitch + q.c, *rb = q.src + (size_t)cy.b * (size_t)p.pitch + q.c;
         const size_t xa = (size_t)cx.a * (size_t)p.channels, xb = (size_t)cx.b * (size_t)p.channels;
-        const unsigned fx = (unsigned)cx.f, fy = (unsigned)cy.f;
-        const unsigned top = (RS_ONE - fx) * ra[xa] + fx * ra[xb], bot = (RS_ONE - fx) * rb[xa] + fx * rb[xb];
-        const unsigned s = (RS_ONE - fy) * top + fy * bot;      // NEAREST: fx = fy = 0, a = b, s = in << 22
-        p.out[q.img * p.out_stride + q.rem] = (uint8_t)((s + RS_BIAS) >> RS_SHIFT);
+        p.out[q.img * p.out_stride + q.rem] = (uint8_t)bilinear_blend(ra[xa], ra[xb], rb[xa], rb[xb], (unsigned)cx.f, (unsigned)cy.f);   // NEAREST: fx = fy = 0, a = b
     }
 }
 
-// Bytes of one row of the resized image.
-long long resize_opitch(const LaunchDesc &d) { return (long long)d.filter->resize_w * d.channels; }
-
-// BILINEAR, 1-4 channels, no reduction on either axis, input and output rows of whole 16-byte chunks, 16-byte aligned
-// buffers and strides.
+// tile_aligned (kernel_common.h) with output rows of whole chunks too, BILINEAR, no reduction on either axis.
 bool resize_tile_aligned(const LaunchDesc &d)
 {
     const Filter &f = *d.filter;
-    return f.resize_mode == MI_BLUR_RESIZE_BILINEAR && d.channels <= 4 && f.resize_w >= d.width && f.resize_h >= d.band_rows &&
-           (long long)d.width * d.channels % 16 == 0 && resize_opitch(d) % 16 == 0 && (uintptr_t)d.in % 16 == 0 && (uintptr_t)d.out % 16 == 0 &&
-           d.in_stride % 16 == 0 && d.out_stride % 16 == 0;
+    return tile_aligned(d) && out_pitch(d) % 16 == 0 && f.sample_mode == MI_BLUR_RESIZE_BILINEAR && f.out_w >= d.width && f.out_h >= d.band_rows;
 }
 
-// The tile decomposition of a launch and its largest input footprint (rows, 16-byte chunks), exactly as the kernel
-// computes them: the host walks the strips and the tile rows with resize_axis.
-struct ResizeTiles { int cpr, nstrips, ncols, ntiles_y, max_nsc, max_nsr; };
-ResizeTiles resize_tiles(const LaunchDesc &d)
+// g: the tiles of the OUTPUT image; t: its largest footprint (resize_tiles(), filter.h), which fits.
+int launch_resize_tiled(const LaunchDesc &d, const TileGrid &g, const ResizeTiles &t)
 {
-    const int C = d.channels, W = d.width, H = d.band_rows, Wo = d.filter->resize_w, Ho = d.filter->resize_h;
-    ResizeTiles t{};
-    t.cpr = (int)(resize_opitch(d) / 16);
-    t.nstrips = (t.cpr + TILE_NCOLS - 1) / TILE_NCOLS;
-    t.ncols = (t.cpr + t.nstrips - 1) / t.nstrips;
-    t.ntiles_y = (Ho + TILE_TH - 1) / TILE_TH;
-    t.max_nsc = t.max_nsr = 1;
-    for (int s = 0; s < t.nstrips; s++) {
-        const int x0c = s * t.ncols, nc = std::min(t.ncols, t.cpr - x0c);
-        if (nc <= 0) continue;
-        const int px0 = (x0c * 16) / C, px1 = ((x0c + nc) * 16 - 1) / C;
-        const int sc0 = (resize_axis(W, Wo, MI_BLUR_RESIZE_BILINEAR, px0).a * C) >> 4;
-        const int sc1 = (resize_axis(W, Wo, MI_BLUR_RESIZE_BILINEAR, px1).b * C + C - 1) >> 4;
-        t.max_nsc = std::max(t.max_nsc, sc1 - sc0 + 1);
-    }
-    for (int ty = 0; ty < t.ntiles_y; ty++) {
-        const int ty0 = ty * TILE_TH, rows = std::min(TILE_TH, Ho - ty0);
-        const int r0 = resize_axis(H, Ho, MI_BLUR_RESIZE_BILINEAR, ty0).a, r1 = resize_axis(H, Ho, MI_BLUR_RESIZE_BILINEAR, ty0 + rows - 1).b;
-        t.max_nsr = std::max(t.max_nsr, r1 - r0 + 1);
-    }
-    return t;
-}
-// What the kernel's table entries can hold: V positions below 1024 (64 chunks), staged rows below 256.  An enlargement
-// stays far inside (at most 34 rows x 35 chunks); a launch that does not fit goes to the generic kernel.
-bool resize_tiles_fit(const ResizeTiles &t) { return t.max_nsc <= 64 && t.max_nsr <= 255; }
-
-int launch_resize_tiled(const LaunchDesc &d, const ResizeTiles &t)
-{
-    const int C = d.channels;
     ResizeTiledParams p{};
-    p.in = d.in; p.out = d.out;
-    p.W = d.width; p.H = d.band_rows; p.Wo = d.filter->resize_w; p.Ho = d.filter->resize_h;
-    p.pitch = d.width * C; p.opitch = (int)resize_opitch(d);
-    p.in_stride = d.in_stride ? d.in_stride : dense_in(d);
-    p.out_stride = d.out_stride ? d.out_stride : dense_out(d);
-    p.cpr = t.cpr; p.nstrips = t.nstrips; p.ncols = t.ncols; p.ntiles_y = t.ntiles_y;
-    const long long nblocks = (long long)d.n_images * p.ntiles_y * p.nstrips;
-    if (nblocks > 0x7fffffffLL) return MI_BLUR_ERR_INVALID;
+    dim3 grid;
+    if (const int st = fill_tiles(p, d, &grid, g)) return st;
     set_last_kernel("blur_resize_tiled_kernel");
-    p.nblocks = (unsigned)nblocks;
-    p.xcd = nblocks >= 16 ? 1 : 0;
-    p.v_off = RS_XTAB + RS_YTAB + t.max_nsr * t.max_nsc * 16;
-    const size_t lds = (size_t)p.v_off + (size_t)RS_GROUP * t.max_nsc * 64u;
-    const dim3 grid((unsigned)nblocks), block(TILE_THREADS);
-    return dispatch<1, 2, 3, 4>(C, [&](auto CC) { return do_launch(blur_resize_tiled_kernel<CC>, grid, block, lds, d, p); });
+    p.W = d.width; p.Wo = d.filter->out_w; p.Ho = d.filter->out_h;
+    p.v_off = resize_v_off(t);
+    const size_t lds = resize_lds_bytes(t);
+    return dispatch<1, 2, 3, 4>(d.channels, [&](auto CC) { return do_launch(blur_resize_tiled_kernel<CC>, grid, dim3(TILE_THREADS), lds, d, p); });
 }
 
 int launch_resize_generic(const LaunchDesc &d)
 {
     set_last_kernel("blur_resize_generic_kernel");
     ResizeGenericParams p{};
-    p.in = d.in; p.out = d.out;
-    p.W = d.width; p.H = d.band_rows; p.Wo = d.filter->resize_w; p.Ho = d.filter->resize_h; p.channels = d.channels;
-    p.pitch = d.width * d.channels; p.opitch = (int)resize_opitch(d); p.mode = d.filter->resize_mode;
-    p.in_stride = d.in_stride ? d.in_stride : dense_in(d);
-    p.block = dense_out(d);
-    p.out_stride = d.out_stride ? d.out_stride : p.block;
-    p.total = p.block * d.n_images;
-    return do_launch(blur_resize_generic_kernel, byte_grid(p.total), dim3(256), 0, d, p);
+    const dim3 grid = fill_generic(p, d);
+    p.W = d.width; p.Wo = d.filter->out_w; p.Ho = d.filter->out_h; p.mode = d.filter->sample_mode;
+    return do_launch(blur_resize_generic_kernel, grid, dim3(256), 0, d, p);
 }
 
 }  // namespace
@@ -256,14 +176,13 @@ int launch_resize_generic(const LaunchDesc &d)
 // Only whole images (launch_checks()); out_stride is measured against the RESIZED image (dense_out()).
 int launch_resize(const LaunchDesc &d)
 {
-    const int st = launch_checks(d, FilterKind::RESIZE, [&](const Filter &f) {
-        const mi_blur_resize r{f.resize_w, f.resize_h, f.resize_mode};
-        return resize_ok(&r, d.width, d.band_rows, d.channels);
-    });
+    const int st = launch_checks(d, FilterKind::RESIZE, [&](const Filter &f) { return resize_ok(f.out_w, f.out_h, f.sample_mode, d.width, d.band_rows, d.channels); });
     if (st != LAUNCH_GO) return st;
     if (resize_tile_aligned(d)) {
-        const ResizeTiles t = resize_tiles(d);
-        if (resize_tiles_fit(t)) return launch_resize_tiled(d, t);
+        const Filter &f = *d.filter;
+        const TileGrid g = tile_grid(out_pitch(d) / 16, f.out_h);
+        const ResizeTiles t = resize_tiles(g, d.width, d.band_rows, f.out_w, f.out_h, d.channels);
+        if (resize_tiles_fit(t)) return launch_resize_tiled(d, g, t);
     }
     return launch_resize_generic(d);
 }

@@ -8,7 +8,8 @@
 // workgroup = one tile of TILE_TH INPUT rows x ncols (<= 32, even; 6, 12, 18 or 24 for C = 3) input chunk columns, which
 // holds TILE_TH / 2 kept rows x ncols / 2 output chunks:
 //   * stage (TILE_TH + 2 ry) rows x (ncols + 2 HC) chunks in LDS with the shared stager (stage_tile, kernel_common.h),
-//     tile rows counted in input coordinates, x-clamp included;
+//     tile rows counted in input coordinates, x-clamp included; the host cuts the INPUT image into these tiles with the
+//     shared fill_tiles, in strips of whole groups;
 //   * VERTICAL PASS FIRST, over the kept rows only and all staged columns: it is the pass that can work in packed
 //     16-bit fields (v_pk_mad_u16, two MACs per lane-op, as in blur_sep_tiled_kernel) on whole chunks exactly as they lie
 //     in LDS, and skipping rows costs it nothing, so it halves.  Horizontal first would have to gather bytes 2 pixels
@@ -221,15 +222,11 @@ __global__ __launch_bounds__(256) void blur_sep_down_generic_kernel(const SepDow
     }
 }
 
-// Bytes of one row of the decimated image.
-int down_opitch(const LaunchDesc &d) { return out_shape(*d.filter, d.width, d.band_rows, d.y0, d.y1).width * d.channels; }
-
-// Stride 2 both ways, 1-4 channels, input rows of whole 32-byte chunk pairs, 16-byte aligned buffers and strides.
+// tile_aligned (kernel_common.h), stride 2 both ways, input rows of whole 32-byte chunk pairs.
 bool down_tile_aligned(const LaunchDesc &d)
 {
     const Filter &f = *d.filter;
-    return f.down_sx == 2 && f.down_sy == 2 && d.channels <= 4 && (long long)d.width * d.channels % 32 == 0 &&
-           (uintptr_t)d.in % 16 == 0 && (uintptr_t)d.out % 16 == 0 && d.in_stride % 16 == 0 && d.out_stride % 16 == 0;
+    return tile_aligned(d) && f.down_sx == 2 && f.down_sy == 2 && (long long)d.width * d.channels % 32 == 0;
 }
 
 int launch_sep_down_tiled(const LaunchDesc &d)
@@ -238,26 +235,17 @@ int launch_sep_down_tiled(const LaunchDesc &d)
     const Filter &f = *d.filter;
     const SepTaps &k = f.taps;
     SepDownTiledParams p{};
-    fill_band(p, d);                                  // y0 = 0: the whole image
-    p.y1 = d.band_rows;
-    p.opitch = down_opitch(d); p.oy = f.down_oy;
-    // strips of whole groups: 2 G input chunks each, at most TILE_NCOLS chunks per strip
+    // tiles of the INPUT image; strips of whole groups: 2 G input chunks each, at most TILE_NCOLS chunks per strip
     // 3 channels: 4 groups = 24 chunks per strip, so that 16 kept rows x 4 groups fill the 64 lanes of a wave-iteration of the horizontal pass
     const int unit = 2 * down_group(d.channels), max_units = d.channels == 3 ? 4 : TILE_NCOLS / unit;
-    p.cpr = p.pitch / 16;
-    const int units = p.cpr / unit;
-    p.nstrips = (units + max_units - 1) / max_units;
-    p.ncols = unit * ((units + p.nstrips - 1) / p.nstrips);
-    p.ntiles_y = (d.band_rows + TILE_TH - 1) / TILE_TH;
-    const long long nblocks = (long long)d.n_images * p.ntiles_y * p.nstrips;
-    if (nblocks > 0x7fffffffLL) return MI_BLUR_ERR_INVALID;
-    p.nblocks = (unsigned)nblocks;
-    p.xcd = nblocks >= 16 ? 1 : 0;
+    dim3 grid;
+    if (const int st = fill_tiles(p, d, &grid, tile_grid(d.width * d.channels / 16, d.band_rows, unit, max_units))) return st;
+    p.y1 = d.band_rows; p.oy = f.down_oy;             // y0 = 0: the whole image
     p.rx = k.rx; p.ry = k.ry; p.shift = k.shift;
     p.dlo = f.down_ox - k.rx; p.dhi = f.down_ox + k.rx;
     for (int D = p.dlo; D <= p.dhi; D++) p.wx[SEP_MAX_R + D] = k.wx[SEP_MAX_R + D - f.down_ox];
     for (int i = 0; i <= 2 * SEP_MAX_R; i++) p.wy2[i] = k.wy[i] | (k.wy[i] << 16);
-    const dim3 grid((unsigned)nblocks), block(TILE_THREADS);
+    const dim3 block(TILE_THREADS);
     return dispatch<1, 2, 3, 4>(d.channels, [&](auto C) {
         return dispatch<4, 8, 16>(k.rx <= 4 ? 4 : k.rx <= 8 ? 8 : 16, [&](auto RB) {
             const int ncw = p.ncols + 2 * down_halo_chunks(C, RB);
@@ -273,17 +261,12 @@ int launch_sep_down_generic(const LaunchDesc &d)
     const Filter &f = *d.filter;
     const SepTaps &k = f.taps;
     SepDownGenericParams p{};
-    p.in = d.in; p.out = d.out;
-    p.pitch = d.width * d.channels; p.H = d.band_rows; p.width = d.width; p.channels = d.channels;
-    p.in_stride = d.in_stride ? d.in_stride : dense_in(d);
-    p.block = dense_out(d);
-    p.out_stride = d.out_stride ? d.out_stride : p.block;
-    p.opitch = down_opitch(d);
-    p.total = p.block * d.n_images;
+    const dim3 grid = fill_generic(p, d);
+    p.width = d.width;
     p.sx = f.down_sx; p.sy = f.down_sy; p.ox = f.down_ox; p.oy = f.down_oy;
     p.rx = k.rx; p.ry = k.ry; p.shift = k.shift;
     for (int i = 0; i <= 2 * SEP_MAX_R; i++) { p.wx[i] = k.wx[i]; p.wy[i] = k.wy[i]; }
-    return do_launch(blur_sep_down_generic_kernel, byte_grid(p.total), dim3(256), 0, d, p);
+    return do_launch(blur_sep_down_generic_kernel, grid, dim3(256), 0, d, p);
 }
 
 }  // namespace

@@ -13,7 +13,9 @@ include/mi_blur.h (kernel_proofs.py), never from the product; every launch also 
     witness every (byte position, offset) pair at every radius (test_kernel_proofs_host.py checks that they do).
   * blur_morph_tiled_kernel, blur_bilateral_tiled_kernel, blur_conv_tiled_kernel: the sep kernel's geometry sweep, bands
     and grids, each filter walking its own kernel's bucket edges; blur_sep_down_tiled_kernel and blur_resize_tiled_kernel:
-    chunk and row counts around their tiles, every phase, the sizes around 1x, 2x and 3x."""
+    chunk and row counts around their tiles, every phase, the sizes around 1x, 2x and 3x; blur_warp_tiled_kernel: output
+    widths around its 64-pixel strips and heights around its tile rows, under translations, a rotation, an enlargement, a
+    reduction and a map that leaves the image, both borders."""
 import math
 
 import numpy as np
@@ -26,6 +28,7 @@ from filter_harness import (BILATERAL, CONV, MORPH, SEP, check_bands_and_grids, 
                             torch_cuda)
 from resize_ref import gpu_resize_run, ref_resize, takes_tiled
 from sep_down_ref import gpu_down_run
+import warp_ref as wr
 
 pytestmark = pytest.mark.gpu
 
@@ -438,3 +441,45 @@ def test_resize_tiled_geometry_sweep(pkg, L, torch_cuda, c):
         assert L.mi_blur_last_kernel().decode() == RESIZE_TILED, (c, ci, co, h, ho)
         assert np.array_equal(got, ref_resize(img, wo, ho)), (c, ci, co, h, ho)
     assert len(used_x) == len(xs) and len(used_y) == len(ys)
+
+
+# ---------------------------------------------------------------- warp: geometry
+WARP_WO = (16, 48, 64, 80, 128, 144)      # output pixels per row: whole chunks (groups of three for 3 channels) for 1..4 channels; one strip, its 64-pixel edge, at and next to two strips
+WARP_HO = (1, 2, 31, 32, 33, 65)
+WARP_IN = (80, 96)                        # input rows, pixels per row
+WARP_TILED = "blur_warp_tiled_kernel"
+
+
+def warp_maps():
+    """(m, borders): a sub-pixel translation, a rotation by 30 degrees about the centre, the x2 CLAMP scale, a x1/2
+    reduction, and a translation that puts the tiles on the right and at the bottom wholly outside the image."""
+    h, w = WARP_IN
+    both = (wr.CLAMP, wr.CONSTANT)
+    return [([wr.Q, 0, 3 * wr.Q // 8 + 1, 0, wr.Q, -5 * wr.Q // 8 - 1], both), (wr.rotation_m(w, h, 30.0), both), (wr.scale_matrix(2, 1), both),
+            (wr.scale_matrix(1, 2), both), ([wr.Q, 0, 40 * wr.Q + 123, 0, wr.Q, 45 * wr.Q - 77], both)]
+
+
+@pytest.mark.parametrize("c", [1, 2, 3, 4])
+def test_warp_tiled_geometry_sweep(pkg, L, torch_cuda, c):
+    """Every output width x every output height paired cyclically (every one of either list occurs), each under every map
+    and both borders, through the tiled kernel, byte for byte against warp_ref.ref_warp."""
+    h, w = WARP_IN
+    img = np.random.default_rng(100 + c).integers(0, 256, size=(1, h, w, c), dtype=np.uint8)
+    used_w, used_h, missed = set(), set(), False
+    for k in range(max(len(WARP_WO), len(WARP_HO))):
+        wo, ho = WARP_WO[k % len(WARP_WO)], WARP_HO[(k + c) % len(WARP_HO)]
+        used_w.add(wo)
+        used_h.add(ho)
+        for i, (m, borders) in enumerate(warp_maps()):
+            for border in borders:
+                assert wr.takes_tiled(img.shape, m, wo, ho, wr.BILINEAR, border), (c, wo, ho, i, border)
+                got = wr.gpu_warp_run(pkg, L, torch_cuda, img, m, wo, ho, wr.BILINEAR, border, 201)
+                assert L.mi_blur_last_kernel().decode() == WARP_TILED, (c, wo, ho, i, border)
+                want = wr.ref_warp(img, m, wo, ho, wr.BILINEAR, border, 201)
+                assert np.array_equal(got, want), (c, wo, ho, i, border)
+                if i == 4 and border == wr.CONSTANT:
+                    ncols, cpr, trows = wr.tile_geometry(wo, ho, c)
+                    missed = missed or any(wr.footprint(m, border, w, h, c, x0c * 16 // c, (min(x0c + ncols, cpr) * 16 - 1) // c, ty0, min(ty0 + trows, ho) - 1) == 0
+                                           for ty0 in range(0, ho, trows) for x0c in range(0, cpr, ncols))
+    assert len(used_w) == len(WARP_WO) and len(used_h) == len(WARP_HO)
+    assert missed                                                      # some tile lay wholly outside the image

@@ -422,3 +422,16 @@ def test_cpu_warp_clean_under_asan_ubsan(pkg, tmp_path):
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "random and edge warp cases clean" in r.stdout, r.stdout + r.stderr
     assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
+def test_tile_geometry_stays_inside_the_lds_under_asan_ubsan(pkg, tmp_path):
+    """The footprint and tap arithmetic the resize and warp tiled kernels share with their host-side LDS sizing
+    (filter.h), walked tile by tile on the CPU: tests/san_tile_bounds.cpp."""
+    exe = tmp_path / "san_tile_bounds"
+    cmd = ["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+           "-fno-omit-frame-pointer", "-I", pkg.CSRC, os.path.join(ROOT, "tests", "san_tile_bounds.cpp"), "-o", str(exe)]
+    subprocess.run(cmd, check=True, capture_output=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "taps inside their LDS" in r.stdout and "FAILED" not in r.stdout, r.stdout + r.stderr
+    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr

@@ -2,7 +2,7 @@
 """Rate of the decimating separable kernel (mi_blur_enqueue_sep_down) on one GPU, beside what a caller had to launch
 before it existed: mi_blur_enqueue_sep with the same taps on the same input (and then subsample).
 
-    python tools/sep_down_rate.py [--seconds 1.0] [--json FILE] [--once]
+    python tools/sep_down_rate.py [--seconds 1.0] [--json FILE] [--once] [--lib PATH]
 
 Per point three figures are taken one after the other: the baseline, the decimating launch, the baseline again; each
 is launches back to back on one stream for at least --seconds between two events, reported as us per launch and
@@ -12,31 +12,18 @@ baseline figures is the spread any gap has to exceed.  floor_tb_s (8192x8192x3 a
 launch has to move at least, over the measured time: compare it with the measured copy ceiling (tools/copy_ceiling.py,
 ~6.29 TB/s), not with a data-sheet peak.  Shapes: one 8192x8192x3 image, and a batch of 8 1920x1080x3 frames.  Kernels: MI_BLUR_DOWN_PYR, Gaussian
 sigma 1 and 2 at stride 2, MI_BLUR_DOWN_AREA2.  --once: five launches of each per point, in order, and nothing else (for a kernel trace).
+--lib PATH: time that build of libmi_blur.so instead of the tree's (rate_common.py).
 """
-import argparse
 import ctypes as C
-import json
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import __graft_entry__ as entry  # noqa: E402
+from rate_common import once, rate, save, setup
 
 SHAPES = [("8192x8192x3", 1, 8192, 8192, 3), ("1920x1080x3 x8", 8, 1080, 1920, 3)]
 HBM_FLOOR_8192 = 252e6        # bytes one 8192x8192x3 launch at stride 2 has to move: 201.3 MB in + 50.3 MB out
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--seconds", type=float, default=1.0)
-    ap.add_argument("--json", default="")
-    ap.add_argument("--once", action="store_true")
-    args = ap.parse_args()
-    import torch
-    pkg = entry.load_package()
-    L = pkg.lib()
-    torch.cuda.set_device(0)
+    args, torch, pkg, L = setup()
 
     def preset(which):
         k, d = pkg.SepKernel(), pkg.Decimation()
@@ -64,35 +51,15 @@ def main():
                 pkg.check(L.mi_blur_enqueue_sep_down(d_in.data_ptr(), d_down.data_ptr(), w, h, c, n, C.byref(k), C.byref(d), s.cuda_stream), kname)
 
             if args.once:                            # 5 + 5 dispatches per point, in this order
-                for go in (sep, down):
-                    for _ in range(5):
-                        go()
-                torch.cuda.synchronize()
+                once(torch, sep, down)
                 continue
 
-            def rate(go, ramp):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                for _ in range(3):
-                    go()
-                e0.record()
-                for _ in range(10):
-                    go()
-                e1.record()
-                torch.cuda.synchronize()
-                reps = max(20, int(args.seconds * 1e3 / max(e0.elapsed_time(e1) / 10, 1e-3)) + 1)
-                if ramp:
-                    for _ in range(reps):
-                        go()
-                e0.record()
-                for _ in range(reps):
-                    go()
-                e1.record()
-                torch.cuda.synchronize()
-                return e0.elapsed_time(e1) * 1e3 / reps, reps, L.mi_blur_last_kernel().decode()
+            def timed(go, ramp=False):
+                return (*rate(torch, go, args.seconds, ramp, warm=3, probe=10, min_reps=20), L.mi_blur_last_kernel().decode())
 
-            sep_us, _, sep_kernel = rate(sep, True)
-            down_us, reps, down_kernel = rate(down, False)
-            sep_again, _, _ = rate(sep, False)
+            sep_us, _, sep_kernel = timed(sep, True)
+            down_us, reps, down_kernel = timed(down)
+            sep_again, _, _ = timed(sep)
             sep_bytes, down_bytes = 2 * d_in.numel(), d_in.numel() + d_down.numel()
             base = 0.5 * (sep_us + sep_again)
             spread = abs(sep_us - sep_again) / base
@@ -109,9 +76,7 @@ def main():
             del d_down
         del d_in, d_full
         torch.cuda.empty_cache()
-    if args.json:
-        with open(args.json, "w") as f:
-            json.dump(rows, f, indent=1)
+    save(args, rows)
 
 
 if __name__ == "__main__":

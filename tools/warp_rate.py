@@ -3,7 +3,7 @@
 same number of bytes in the same run (the method of tools/copy_ceiling.py: torch's copy_ of an int32 view, which reads
 N and writes N bytes; here N = (input + output bytes) / 2) and beside the generic kernel on the same launch.
 
-    python tools/warp_rate.py [--seconds 1.0] [--json FILE] [--once]
+    python tools/warp_rate.py [--seconds 1.0] [--json FILE] [--once] [--lib PATH]
 
 Per point the figures are taken one after the other: the launch, the copy, the generic kernel, the launch again; each
 is calls back to back on one stream for at least --seconds between two events, reported as us per call and
@@ -14,17 +14,12 @@ the misalignment costs it nothing); where the launch itself takes the generic ke
 Points: 8 x 1920x1080x3 and 8192x8192x3 rotated 30 degrees about the centre at the same size (CONSTANT border),
 8 x 1920x1080x4 rotated 45 degrees, and 1920x1080x3 under the x2 CLAMP warp, which gives the bytes of the x2 resize:
 that point also times blur_resize_tiled_kernel on the same images (the last column, after the generic kernel).
---once: five launches of each kernel per point, in order, and nothing else (for a kernel trace).
+--once: five launches of each kernel per point, in order, and nothing else (for a kernel trace).  --lib PATH: time that
+build of libmi_blur.so instead of the tree's (rate_common.py).
 """
-import argparse
 import ctypes as C
-import json
-import os
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import __graft_entry__ as entry  # noqa: E402
+from rate_common import once, rate, save, setup
 
 Q = 1 << 16
 # name, images, H, W, C, Wo, Ho, rotation in degrees (None: the x2 CLAMP warp {Q/2, 0, -Q/4, 0, Q/2, -Q/4})
@@ -33,15 +28,7 @@ POINTS = [("1920x1080x3 x8 rotate 30", 8, 1080, 1920, 3, 1920, 1080, 30.0), ("81
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--seconds", type=float, default=1.0)
-    ap.add_argument("--json", default="")
-    ap.add_argument("--once", action="store_true")
-    args = ap.parse_args()
-    import torch
-    pkg = entry.load_package()
-    L = pkg.lib()
-    torch.cuda.set_device(0)
+    args, torch, pkg, L = setup()
     rows = []
     print(f"{torch.cuda.get_device_name(0)}; >= {args.seconds:.1f} s of back-to-back calls per figure, after one ramp of the same length per point")
     print(f"{'point':30s} | {'us':>9s} {'again':>9s} {'TB/s':>5s} {'spread':>7s} | {'copy us':>9s} {'TB/s':>5s} {'of copy':>7s} | {'generic us':>10s} {'x':>6s} | {'resize us':>9s} {'x':>6s}  kernel")
@@ -74,42 +61,22 @@ def main():
             c_dst.copy_(c_src)
 
         if args.once:
-            for go in (launch, generic):
-                for _ in range(5):
-                    go()
-            torch.cuda.synchronize()
+            once(torch, launch, generic)
             continue
 
-        def rate(go, ramp):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            for _ in range(2):
-                go()
-            e0.record()
-            for _ in range(3):
-                go()
-            e1.record()
-            torch.cuda.synchronize()
-            reps = max(5, int(args.seconds * 1e3 / max(e0.elapsed_time(e1) / 3, 1e-3)) + 1)
-            if ramp:
-                for _ in range(reps):
-                    go()
-            e0.record()
-            for _ in range(reps):
-                go()
-            e1.record()
-            torch.cuda.synchronize()
-            return e0.elapsed_time(e1) * 1e3 / reps, reps
+        def timed(go, ramp=False):
+            return rate(torch, go, args.seconds, ramp)
 
-        us, reps = rate(launch, True)
+        us, reps = timed(launch, True)
         kernel = L.mi_blur_last_kernel().decode()
-        copy_us, _ = rate(copy, False)
-        gen_us, _ = rate(generic, False)
+        copy_us, _ = timed(copy)
+        gen_us, _ = timed(generic)
         assert L.mi_blur_last_kernel().decode() == "blur_warp_generic_kernel"
         resize_us = None
         if angle is None:
-            resize_us, _ = rate(resize, False)
+            resize_us, _ = timed(resize)
             assert L.mi_blur_last_kernel().decode() == "blur_resize_tiled_kernel"
-        again, _ = rate(launch, False)
+        again, _ = timed(launch)
         base = 0.5 * (us + again)
         spread = abs(us - again) / base
         moved = in_bytes + out_bytes
@@ -122,9 +89,7 @@ def main():
                      "resize_us": resize_us and round(resize_us, 2), "resize_over_launch": resize_us and round(resize_us / base, 3), "kernel": kernel})
         del d_in, d_off, d_out, c_src, c_dst
         torch.cuda.empty_cache()
-    if args.json:
-        with open(args.json, "w") as f:
-            json.dump(rows, f, indent=1)
+    save(args, rows)
 
 
 if __name__ == "__main__":
