@@ -4,9 +4,13 @@
 // checks (a) that every staged row and chunk lies inside the input image, (b) that the staged box fits the LDS the host's
 // sizing returned, (c) that every position and row the tap functions return, for every output pixel, lies inside the
 // staged box (for the warp with the bytes its reads touch behind it, within the slack), and (d) that a launch the sweep
-// expects to be admitted is admitted.  UBSan sees any overflow of the coordinate arithmetic on the way.
+// expects to be admitted is admitted.  UBSan sees any overflow of the coordinate arithmetic on the way.  The warp sweep
+// includes the extreme shapes, one-chunk inputs and maps at the header's limits of tests/warp_ref.py (EXTREME,
+// narrow_cases(), LIMIT_MAPS) and the two near-2-GiB launches of tests/test_large_shapes_gpu.py; where the output is the
+// image near 2^31 bytes (700 M pixels) every tile's box is checked and the taps of three tile rows.
 #include "filter.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -141,8 +145,9 @@ static Mat rotation_m(double cx, double cy, double deg, double scale = 1.0)
 static Mat centre_rotation(int w, int h, double deg, double scale = 1.0) { return rotation_m((w - 1) / 2.0, (h - 1) / 2.0, deg, scale); }
 static Mat scale_m(int num, int den) { const i64 s = Q * den / num, t = (s - Q) / 2; return {{s, 0, t, 0, s, t}}; }
 
-// Returns whether the launch is admitted; every tile of an admitted launch is checked.
-static bool check_warp(int W, int H, int Wo, int Ho, int C, const Mat &mat, int border)
+// Returns whether the launch is admitted; every tile of an admitted launch is checked: its grid position and box, and
+// the taps of every pixel (tap_tile_rows: of the pixels of those tile rows only).
+static bool check_warp(int W, int H, int Wo, int Ho, int C, const Mat &mat, int border, std::initializer_list<int> tap_tile_rows = {})
 {
     const i64 *m = mat.m;
     CHECK(W * C % 16 == 0 && Wo * C % 16 == 0, "not a launch of the tiled kernel");
@@ -174,7 +179,10 @@ static bool check_warp(int W, int H, int Wo, int Ho, int C, const Mat &mat, int 
                 CHECK(0 <= b.x0 && b.x1 < W && 0 <= b.y0 && b.y1 < H && 0 <= sc.lo && sc.hi < W * C / 16, "(a) tile %d,%d", s, ty);
                 CHECK(sc.lo * 16 <= b.x0 * C && (b.x1 + 1) * C <= (sc.hi + 1) * 16, "(a) the chunks hold the box, tile %d,%d", s, ty);
                 CHECK(box_bytes <= max_bytes, "(b) tile %d,%d: %lld > %lld", s, ty, (long long)box_bytes, (long long)max_bytes);
+                // the offsets the kernel forms in 32 bits: the first staged chunk, the last output byte of the tile
+                CHECK((i64)b.y0 * W * C + (i64)sc.lo * 16 <= 0x7fffffffLL && (i64)(tl.ty0 + tl.rows_out) * Wo * C <= 0x7fffffffLL, "an offset over 2^31, tile %d,%d", s, ty);
             }
+            if (tap_tile_rows.size() && std::find(tap_tile_rows.begin(), tap_tile_rows.end(), ty) == tap_tile_rows.end()) continue;
             for (int Y = tl.ty0; Y < tl.ty0 + tl.rows_out; Y++)
                 for (int X = px.lo; X <= px.hi; X++) {
                     const WarpPos p = warp_position(m, X, Y);
@@ -260,11 +268,58 @@ static void sweep_warp()
     }
 }
 
+// tests/warp_ref.py: EXTREME, narrow_cases(), LIMIT_MAPS, and the near-2-GiB launches of test_large_shapes_gpu.py.  All
+// are launches the GPU tests expect on the tiled kernel, under both borders.
+static void sweep_warp_extremes()
+{
+    const int BORDERS[] = {MI_BLUR_WARP_CLAMP, MI_BLUR_WARP_CONSTANT};
+    const i64 L = (i64)1 << 26, O = (i64)1 << 46;
+    // 32768 pixels along one axis: (H, W, C, Wo, Ho) and the map
+    struct { int H, W, C, Wo, Ho; Mat m; } extreme[] = {
+        {1, 32768, 1, 32768, 1, {{Q, 0, 3 * Q / 8 + 1, 0, Q, 0}}},
+        {2, 32768, 1, 16384, 2, {{2 * Q, 0, Q / 2, 0, Q, Q / 3}}},
+        {32768, 16, 1, 16, 32768, centre_rotation(16, 32768, 0.02)},
+        {16, 32768, 1, 16, 32768, {{0, -Q, 32767 * Q, Q, 0, 0}}},
+        {32768, 16, 1, 32768, 16, {{0, Q, 0, -Q, 0, 32767 * Q}}},
+        {3, 16384, 4, 32768, 3, {{Q / 2, 0, -Q / 4, 0, Q, 0}}},
+        {2, 32768, 3, 32768, 2, {{Q, 0, -5 * Q / 8, 0, Q, Q / 2}}},
+        {2, 32768, 1, 16384, 2, {{2 * Q, 0, 40 * Q + Q / 2, 0, Q, Q / 3}}},          // these two pass 2^31, beyond the right and the bottom edge
+        {32768, 16, 1, 16, 32768, {{Q, 0, Q / 3, 0, Q, 40 * Q + Q / 2}}}};
+    for (const auto &e : extreme)
+        for (int border : BORDERS) CHECK(check_warp(e.W, e.H, e.Wo, e.Ho, e.C, e.m, border), "(d) an extreme shape, H %d W %d", e.H, e.W);
+    // inputs of one chunk per row (3 channels: one group of three): the box is the whole row or image
+    const int rows[][2] = {{16, 1}, {8, 2}, {16, 3}, {4, 4}};
+    for (const auto &r : rows)
+        for (int H : {1, 2, 33}) {
+            const int W = r[0], C = r[1], Wo = C == 4 ? 132 : 144, Ho = 33;
+            const Mat maps[] = {scale_m(4, 1), centre_rotation(W, H, 30), {{Q, 0, -3 * Q / 8, 0, Q, 5 * Q / 8}}, {{Q, 0, (-W - 3) * Q, 0, Q, Q}}};
+            for (const Mat &m : maps)
+                for (int border : BORDERS) CHECK(check_warp(W, H, Wo, Ho, C, m, border), "(d) a one-chunk input, W %d C %d H %d", W, C, H);
+        }
+    // maps at the limits of the header and degenerate maps on 64 x 64: the whole image fits, so all are admitted
+    const Mat limits[] = {{{L, 0, 0, 0, L, 0}}, {{-L, L, 63 * Q, L, -L, 63 * Q}}, {{L, 0, -79 * L + 5 * Q, 0, L, -39 * L + 7 * Q + 123}}, {{Q, 0, O, 0, Q, O}},
+                          {{-Q, 0, -O, 0, -Q, -O}}, {{Q, 0, -O, 0, Q, 3 * Q}}, {{L, L, O, -L, -L, -O}}, {{0, 0, 10 * Q + 777, 0, 0, 20 * Q + 31111}},
+                          {{Q, 0, 0, Q, 0, Q / 3}}, {{1, 0, 5 * Q, 0, 1, 6 * Q + 65535}}, {{L, 0, -40 * L + 30 * Q, 0, Q, 0}}, {{Q, 0, 0, L, Q, -20 * L}}};
+    for (const Mat &m : limits)
+        for (int c = 1; c <= 4; c++)
+            for (int border : BORDERS) CHECK(check_warp(64, 64, c == 3 ? 96 : 80, 40, c, m, border), "(d) a map at the limits, m0 %lld m2 %lld", (long long)m.m[0], (long long)m.m[2]);
+    // the OUTPUT within 75 kB of 2^31 bytes: every tile's box; the taps of the first tile row, the one at the 2^30-byte
+    // offset (output row 13380) and the last
+    const int BIG_H = 26757, BIG_W = 26752;
+    for (int border : BORDERS)
+        CHECK(check_warp(BIG_W, BIG_H / 2 + 1, BIG_W, BIG_H, 3, {{Q, 0, 0, -655, Q / 2, 133 * Q}}, border, {0, 13380 / TILE_TH, (BIG_H - 1) / TILE_TH}), "(d) the output near 2^31 bytes");
+    // the INPUT near 2^31 bytes, 64 output rows from its first rows, those at the 2^30-byte offset, its last rows and beyond
+    for (int first_row : {0, 13376, BIG_H - 60})
+        for (int border : BORDERS)
+            CHECK(check_warp(BIG_W, BIG_H, BIG_W, 64, 3, {{Q, 0, 3 * Q / 8 + 1, 0, Q, first_row * Q + 5 * Q / 8}}, border), "(d) the input near 2^31 bytes");
+}
+
 int main()
 {
     sweep_sep_down_grid();
     sweep_resize();
     sweep_warp();
+    sweep_warp_extremes();
     printf("%ld launches, %ld tiles (%ld outside the image), %ld taps inside their LDS\n", launches, tiles, empty_tiles, taps);
     return 0;
 }

@@ -1,6 +1,6 @@
 // host-only sanitizer run: the CPU device's affine warp (cpu_blur_batch with a WARP filter) against a scalar loop written
-// here from the header's text, on random small shapes and on edge maps (the range limits, far-away and degenerate maps),
-// exact-size heap buffers so ASan sees any over-read / over-write and UBSan any overflow of the coordinate arithmetic.
+// here from the header's text, on random small shapes, on edge maps (the range limits, far-away and degenerate maps) and
+// on the maps at the header's limits that the GPU tests run (LIMIT_MAPS of tests/warp_ref.py), with exact-size heap buffers so ASan sees any over-read / over-write and UBSan any overflow of the coordinate arithmetic.
 #include "cpu_device.h"
 #include <cstdio>
 #include <cstdlib>
@@ -80,6 +80,20 @@ int main()
                     mi_blur_warp w{shape == 0 ? 1 : 7, shape == 0 ? 1 : 6, mode, border, 200, {}};
                     for (int i = 0; i < 6; i++) w.m[i] = m[i];
                     if (run_case(W, H, 1 + shape, 2, 2, w, &s)) return 1;
+                    cases++;
+                }
+    // the maps of tests/warp_ref.py's LIMIT_MAPS on its shapes: 64 x 64 to 80 x 40 (96 x 40 for 3 channels), 1-4 channels
+    const i64 limits[][6] = {{LIN, 0, 0, 0, LIN, 0}, {-LIN, LIN, 63 * Q, LIN, -LIN, 63 * Q}, {LIN, 0, -79 * LIN + 5 * Q, 0, LIN, -39 * LIN + 7 * Q + 123},
+                             {Q, 0, OFF, 0, Q, OFF}, {-Q, 0, -OFF, 0, -Q, -OFF}, {Q, 0, -OFF, 0, Q, 3 * Q}, {LIN, LIN, OFF, -LIN, -LIN, -OFF},
+                             {0, 0, 10 * Q + 777, 0, 0, 20 * Q + 31111}, {Q, 0, 0, Q, 0, Q / 3}, {1, 0, 5 * Q, 0, 1, 6 * Q + 65535},
+                             {LIN, 0, -40 * LIN + 30 * Q, 0, Q, 0}, {Q, 0, 0, LIN, Q, -20 * LIN}};
+    for (const auto &m : limits)
+        for (int mode = 0; mode < 2; mode++)
+            for (int border = 0; border < 2; border++)
+                for (int C = 1; C <= 4; C++) {
+                    mi_blur_warp w{C == 3 ? 96 : 80, 40, mode, border, 173, {}};
+                    for (int i = 0; i < 6; i++) w.m[i] = m[i];
+                    if (run_case(64, 64, C, 2, 3, w, &s)) return 1;
                     cases++;
                 }
     printf("%d random and edge warp cases clean\n", cases);

@@ -1,7 +1,8 @@
-"""Large and extreme shapes on a real MI355X (-m gpu) for the seven families beside the box blur (sep, median, morph,
-bilateral, conv, sep_down, resize): one-row, one-column, very wide and very tall frames, resize at MI_BLUR_RESIZE_MAX_DIM,
-and one image within 75 kB of 2^31 bytes.  What is under test is the offset arithmetic: strips times tile rows in the
-thousands, strips cut from 16384 chunks per row, source row times pitch past 2^30 and near 2^31.  Byte for byte against
+"""Large and extreme shapes on a real MI355X (-m gpu) for the eight families beside the box blur (sep, median, morph,
+bilateral, conv, sep_down, resize, warp): one-row, one-column, very wide and very tall frames, resize and warp at
+MI_BLUR_RESIZE_MAX_DIM, and one image within 75 kB of 2^31 bytes (for the warp on either side).  What is under test is the
+offset arithmetic: strips times tile rows in the thousands, strips cut from 16384 chunks per row, source row times pitch
+past 2^30 and near 2^31, and for the warp Q16 positions at and past 2^31.  Byte for byte against
 the numpy restatements; at the largest radii, where those take too long on these frames, against the library's CPU device
 (which test_*_host.py tie to the same restatements), as each case says."""
 import ctypes as C
@@ -15,12 +16,14 @@ from morph_ref import GRADIENT
 from resize_ref import BILINEAR, MAX_DIM, NEAREST, gpu_resize_run, ref_axis, ref_resize, takes_tiled
 from sep_down_ref import cpu_down_run, gpu_down_run, ref_sep_down
 from sep_ref import rand_taps
+import warp_ref as wr
 
 pytestmark = pytest.mark.gpu
 
 CPU_THREADS = 16
 DOWN_TILED, DOWN_GENERIC = "blur_sep_down_tiled_kernel", "blur_sep_down_generic_kernel"
 RESIZE_TILED, RESIZE_GENERIC = "blur_resize_tiled_kernel", "blur_resize_generic_kernel"
+WARP_TILED, WARP_GENERIC = "blur_warp_tiled_kernel", "blur_warp_generic_kernel"
 
 # (h, w, c): one row; one column; 16384 chunks per row (512 strips); one chunk per row and 2188 tile rows; a ragged row of a
 # million pixels; 6 chunks per row and one row more than 2^16
@@ -115,6 +118,26 @@ def test_extreme_aspect_ratios_resize(pkg, L, torch_cuda, case):
     assert L.mi_blur_enqueue_resize(d.data_ptr(), d.data_ptr() + 32, MAX_DIM + 1, shape[0], shape[2], 1, C.byref(r), None) == pkg.ERR_INVALID
 
 
+@pytest.mark.parametrize("border", [wr.CLAMP, wr.CONSTANT], ids=["clamp", "constant"])
+@pytest.mark.parametrize("case", wr.EXTREME, ids=wr.extreme_id)
+def test_extreme_aspect_ratios_warp(pkg, L, torch_cuda, case, border):
+    """32768 pixels along one axis: Q16 positions reach 2^31 and there are hundreds of strips or tile rows.  BILINEAR on the
+    tiled kernel, NEAREST and an output 7 bytes off alignment on the generic one; guard bytes either side of the output."""
+    shape, (wo, ho), m, quarter_turns = case
+    h, w, c = shape
+    assert max(h, w, wo, ho) == MAX_DIM
+    img = np.random.default_rng(sum(shape)).integers(0, 256, size=(1,) + shape, dtype=np.uint8)
+    assert wr.outside_share(m, BILINEAR, w, h, wo, 0, ho) < 0.16           # the reference is real pixels, not fill
+    assert wr.takes_tiled(img.shape, m, wo, ho, BILINEAR, border, 0, 64) and not wr.takes_tiled(img.shape, m, wo, ho, BILINEAR, border, 0, 7)
+    want = wr.ref_warp(img, m, wo, ho, BILINEAR, border, 173)
+    for mode, offset_out, kernel in ((BILINEAR, 64, WARP_TILED), (NEAREST, 64, WARP_GENERIC), (BILINEAR, 7, WARP_GENERIC)):
+        got = wr.gpu_warp_run(pkg, L, torch_cuda, img, m, wo, ho, mode, border, 173, offset_out=offset_out)
+        assert L.mi_blur_last_kernel().decode() == kernel, (mode, offset_out)
+        assert np.array_equal(got, want if mode == BILINEAR else wr.ref_warp(img, m, wo, ho, NEAREST, border, 173)), (mode, offset_out)
+        if quarter_turns is not None:
+            assert np.array_equal(got, np.rot90(img, quarter_turns, axes=(1, 2))), (mode, offset_out)
+
+
 # ---------------------------------------------------------------- one image near 2^31 bytes
 BIG_H, BIG_W, BIG_C = 26757, 26752, 3          # 80256-byte rows: whole 32-byte pairs and whole groups of six chunks
 BAND = 8
@@ -205,6 +228,65 @@ def test_single_image_near_the_2gib_limit_resize(pkg, L, torch_cuda):
             assert np.array_equal(d_out[Y0:Y0 + BAND].cpu().numpy(), want), Y0
         r = pkg.Resize(BIG_W, BIG_H + 1, BILINEAR)
         assert L.mi_blur_enqueue_resize(d_in.data_ptr(), d_out.data_ptr(), BIG_W, h, BIG_C, 1, C.byref(r), None) == pkg.ERR_INVALID
+    finally:
+        del d_in, d_out
+        torch.cuda.empty_cache()
+
+
+def enqueue_warp(pkg, L, torch, d_in, d_out, w, h, wp):
+    return L.mi_blur_enqueue_warp(d_in, d_out, w, h, BIG_C, 1, C.byref(wp), torch.cuda.current_stream().cuda_stream)
+
+
+def test_single_image_near_the_2gib_limit_warp(pkg, L, torch_cuda):
+    """The OUTPUT near 2^31 bytes: 13379 rows to 26752 x 26757 under a sheared map (every tile's box differs, two corners of
+    the output leave the image), bands against ref_warp_band under CONSTANT.  Then the INPUT near 2^31 bytes: 64 output rows
+    read from its first rows, from the rows around the 2^30-byte offset and from its last rows and beyond them."""
+    torch = torch_cuda
+    h = BIG_H // 2 + 1
+    m = [wr.Q, 0, 0, -655, wr.Q // 2, 133 * wr.Q]
+    # on the reference only: the compared bands see real pixels
+    first, last = wr.outside_share(m, BILINEAR, BIG_W, h, BIG_W, 0, BAND), wr.outside_share(m, BILINEAR, BIG_W, h, BIG_W, BIG_H - BAND, BIG_H)
+    assert 0 < first < 0.5 and 0 < last < 0.5                                  # both leave the image, at opposite corners
+    assert all(wr.outside_share(m, BILINEAR, BIG_W, h, BIG_W, Y0, Y0 + BAND) < 0.5 for Y0 in band_starts(BIG_H))
+    assert wr.outside_share(m, BILINEAR, BIG_W, h, BIG_W, 13376, 13376 + BAND) == 0
+    d_in = big_random(torch, h)
+    d_out = torch.empty((BIG_H, BIG_W, BIG_C), dtype=torch.uint8, device="cuda")
+    try:
+        wp = wr.make_warp(pkg, m, BIG_W, BIG_H, BILINEAR, wr.CONSTANT, 173)
+        pkg.check(enqueue_warp(pkg, L, torch, d_in.data_ptr(), d_out.data_ptr(), BIG_W, h, wp), "warp")
+        torch.cuda.synchronize()
+        assert L.mi_blur_last_kernel().decode() == WARP_TILED
+        for Y0 in band_starts(BIG_H):
+            want = wr.ref_warp_band(lambda lo, hi: slab(d_in, lo, hi), h, m, BIG_W, Y0, Y0 + BAND, BILINEAR, wr.CONSTANT, 173)[0]
+            assert np.array_equal(d_out[Y0:Y0 + BAND].cpu().numpy(), want), Y0
+        wp = wr.make_warp(pkg, m, BIG_W, BIG_H + 1, BILINEAR, wr.CONSTANT, 173)
+        assert enqueue_warp(pkg, L, torch, d_in.data_ptr(), d_out.data_ptr(), BIG_W, h, wp) == pkg.ERR_INVALID
+    finally:
+        del d_in, d_out
+        torch.cuda.empty_cache()
+
+    ho, guard = 64, 64
+    size = ho * BIG_W * BIG_C
+    d_in = big_random(torch, BIG_H)
+    d_out = torch.empty(size + 2 * guard, dtype=torch.uint8, device="cuda")
+    try:
+        for mode, kernel in ((BILINEAR, WARP_TILED), (NEAREST, WARP_GENERIC)):
+            for first_row in (0, 13376, BIG_H - 60):                           # the last: output rows 60.. read past the last input row
+                m = [wr.Q, 0, 3 * wr.Q // 8 + 1, 0, wr.Q, first_row * wr.Q + 5 * wr.Q // 8]
+                for border in (wr.CLAMP, wr.CONSTANT):
+                    d_out.fill_(0x5A)
+                    wp = wr.make_warp(pkg, m, BIG_W, ho, mode, border, 173)
+                    pkg.check(enqueue_warp(pkg, L, torch, d_in.data_ptr(), d_out.data_ptr() + guard, BIG_W, BIG_H, wp), "warp")
+                    torch.cuda.synchronize()
+                    assert L.mi_blur_last_kernel().decode() == kernel, (mode, first_row, border)
+                    assert bool((d_out[:guard] == 0x5A).all()) and bool((d_out[guard + size:] == 0x5A).all()), "wrote outside the output"
+                    got = d_out[guard:guard + size].reshape(ho, BIG_W, BIG_C)
+                    for Y0 in (0, 28, ho - BAND):                              # 28: across the two tile rows
+                        want = wr.ref_warp_band(lambda lo, hi: slab(d_in, lo, hi), BIG_H, m, BIG_W, Y0, Y0 + BAND, mode, border, 173)[0]
+                        assert np.array_equal(got[Y0:Y0 + BAND].cpu().numpy(), want), (mode, first_row, border, Y0)
+        assert 0 < wr.outside_share(m, BILINEAR, BIG_W, BIG_H, BIG_W, ho - BAND, ho) < 1       # the last band runs off the bottom
+        wp = wr.make_warp(pkg, m, BIG_W, ho, BILINEAR, wr.CONSTANT, 173)
+        assert enqueue_warp(pkg, L, torch, d_in.data_ptr(), d_out.data_ptr() + guard, BIG_W, BIG_H + 1, wp) == pkg.ERR_INVALID
     finally:
         del d_in, d_out
         torch.cuda.empty_cache()

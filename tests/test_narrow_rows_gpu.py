@@ -4,7 +4,12 @@ With 1-3 chunks per row the only strip has halo chunks outside the row on BOTH s
 a row that is the whole tile.  Byte for byte against the library's CPU device.
 
 blur_sep_down_tiled_kernel stages with the same stager and needs rows of whole chunk pairs: its narrowest rows are one and
-two pairs wide, with up to 4 halo chunks outside the row on both sides at the largest radius."""
+two pairs wide, with up to 4 halo chunks outside the row on both sides at the largest radius.
+
+blur_warp_tiled_kernel has no halo; its corner is the staged box (stage_box, warp_tap of filter.h): with one chunk per input
+row (3 channels: one group of three) and 1, 2 or 33 rows, the box is the whole row or the whole image, and both the + 1 tap
+and the one-pixel case of warp_tap meet the edge of the box on both sides at once.  Byte for byte against the numpy
+restatement of the header."""
 import numpy as np
 import pytest
 
@@ -12,6 +17,7 @@ import conv_ref as cr
 from filter_harness import BILATERAL, CONV, MORPH, SEP, cpu_run, gpu_run, torch_cuda  # noqa: F401
 from sep_down_ref import cpu_down_run, gpu_down_run
 from sep_ref import rand_taps
+from warp_ref import BILINEAR, CLAMP, CONSTANT, gpu_warp_run, narrow_cases, ref_warp, takes_tiled
 
 pytestmark = pytest.mark.gpu
 
@@ -82,3 +88,14 @@ def test_sep_down_rows_narrower_than_the_halo(pkg, L, torch_cuda, r):
                     got = gpu_down_run(pkg, L, torch_cuda, img, k, dec, offset_out=64)       # 64 guard bytes either side
                     assert L.mi_blur_last_kernel().decode() == "blur_sep_down_tiled_kernel", (w, c, h, dec)
                     assert np.array_equal(got, want), (w, c, h, dec)
+
+
+def test_warp_inputs_of_one_chunk_per_row(pkg, L, torch_cuda):
+    """Three 64-pixel strips and two tile rows of output from inputs 16 bytes wide (48 for 3 channels), 1, 2 and 33 rows high:
+    an enlargement, a rotation, a sub-pixel shift and a map wholly left of the image, under both borders."""
+    for img, name, m, wo, ho in narrow_cases():
+        for border in (CLAMP, CONSTANT):
+            assert takes_tiled(img.shape, m, wo, ho, BILINEAR, border), (img.shape, name, border)
+            got = gpu_warp_run(pkg, L, torch_cuda, img, m, wo, ho, BILINEAR, border, 173, offset_out=64)      # 64 guard bytes either side
+            assert L.mi_blur_last_kernel().decode() == "blur_warp_tiled_kernel", (img.shape, name, border)
+            assert np.array_equal(got, ref_warp(img, m, wo, ho, BILINEAR, border, 173)), (img.shape, name, border)

@@ -9,8 +9,8 @@ import pytest
 
 from filter_harness import apps, read_ppm, torch_cuda, write_ppm  # noqa: F401
 from resize_ref import ref_resize
-from warp_ref import (BILINEAR, CLAMP, CONSTANT, NEAREST, Q, cpu_warp_run, gpu_warp_run, identity, in_the_admitted_region, make_warp, quantise,
-                      ref_warp, rotation_m, scale_matrix, takes_tiled, tile_geometry)
+from warp_ref import (BILINEAR, CLAMP, CONSTANT, LIMIT_FILL, LIMIT_MAPS, NEAREST, Q, cpu_warp_run, gpu_warp_run, identity, in_the_admitted_region,
+                      limit_out, limit_references, make_warp, quantise, ref_warp, rotation_m, scale_matrix, takes_tiled, tile_geometry)
 
 pytestmark = pytest.mark.gpu
 
@@ -144,6 +144,23 @@ def test_a_footprint_over_64_kib_takes_the_generic_kernel(pkg, L, torch_cuda):
     assert last(L) == TILED and np.array_equal(got, ref_resize(img, 128, 128))
 
 
+@pytest.mark.parametrize("c", [1, 2, 3, 4])
+def test_maps_at_the_limits_of_the_header(pkg, L, torch_cuda, c):
+    """Linear coefficients of 2^26 and translations of 2^46 in every sign, zero and rank-one linear parts, steps of 1 / 65536
+    pixel (LIMIT_MAPS), on two 64 x 64 images with distinct corners and edges: at most 16 KiB, so the whole image fits the
+    LDS and every BILINEAR launch is tiled.  limit_references() asserts, on the reference alone, that these outputs tell a
+    right kernel from one that writes `fill` or a wrong corner."""
+    img, refs = limit_references(2, c)
+    wo, ho = limit_out(c)
+    for name, (m, _, _) in LIMIT_MAPS.items():
+        for border in BORDERS:
+            assert takes_tiled(img.shape, m, wo, ho, BILINEAR, border), (name, border)
+            for mode, kernel in ((BILINEAR, TILED), (NEAREST, GENERIC)):
+                got = gpu_warp_run(pkg, L, torch_cuda, img, m, wo, ho, mode, border, LIMIT_FILL)
+                assert last(L) == kernel, (name, border, mode)
+                assert np.array_equal(got, refs[name, mode, border]), (name, border, mode)
+
+
 def test_x2_clamp_warp_equals_the_resize(pkg, L, torch_cuda):
     img = np.random.default_rng(9).integers(0, 256, size=(2, 45, 64, 3), dtype=np.uint8)
     got = gpu_warp_run(pkg, L, torch_cuda, img, scale_matrix(2, 1), 128, 90, BILINEAR, CLAMP)
@@ -205,6 +222,44 @@ def test_gpu_context(pkg, L, torch_cuda, target):
             assert L.mi_blur_resident_run(ctx.h, 2, 1, 0) == pkg.ERR_UNSUPPORTED
             assert L.mi_blur_resident_run_fused(ctx.h, 2, 1, 0) == pkg.ERR_UNSUPPORTED
             assert L.mi_blur_ctx_set_warp(ctx.h, C.byref(make_warp(pkg, m, wo, ho))) == pkg.ERR_STATE
+        finally:
+            L.mi_blur_host_free(pin_in)
+            L.mi_blur_host_free(pin_out)
+
+
+def test_gpu_context_enlarging(pkg, L, torch_cuda):
+    """160 x 120 to 320 x 240, rotated: the output is four times the input, so slots sized by the input would be overrun."""
+    shape = (6, 120, 160, 3)
+    n, h, w, c = shape
+    wo, ho = 320, 240
+    img = np.random.default_rng(14).integers(0, 256, size=shape, dtype=np.uint8)
+    m = rotation_m(w, h, 30.0, 2.0)
+    want = ref_warp(img, m, wo, ho, BILINEAR, CONSTANT, 40)
+    assert want.size == 4 * img.size and takes_tiled(shape, m, wo, ho)
+    assert (want != 40).mean() > 0.5                                     # mostly image, not fill
+    with pkg.Context(0, w, h, c, 1, max_batch=n, n_slots=3) as ctx:
+        ctx.set_warp(make_warp(pkg, m, wo, ho, BILINEAR, CONSTANT, 40))
+        cap = want.size + 4096                                           # guard bytes behind the output, pageable and pinned
+        out = np.full(cap, 0xA5, np.uint8)
+        ctx.submit(img.ctypes.data, out.ctypes.data, n)                  # pageable
+        t = ctx.sync()
+        assert np.array_equal(out[:want.size].reshape(want.shape), want) and (out[want.size:] == 0xA5).all()
+        assert last(L) == TILED
+        assert t["bytes_alg"] == img.size + want.size
+        pin_in, pin_out = L.mi_blur_host_alloc(img.size), L.mi_blur_host_alloc(cap)
+        try:
+            a = np.ctypeslib.as_array((C.c_uint8 * img.size).from_address(pin_in)).reshape(img.shape)
+            b = np.ctypeslib.as_array((C.c_uint8 * cap).from_address(pin_out))
+            a[:] = img
+            z0 = L.mi_blur_zero_copy_launches(ctx.h)
+            for k in range(3):
+                b[:] = 0xA5
+                ctx.submit(pin_in, pin_out, n)
+                t = ctx.sync()
+                assert np.array_equal(b[:want.size].reshape(want.shape), want) and (b[want.size:] == 0xA5).all()
+                assert t["bytes_alg"] == (k + 2) * (img.size + want.size)   # cumulative since the context was made
+            assert L.mi_blur_zero_copy_launches(ctx.h) == z0 + 3
+            assert last(L) == TILED
         finally:
             L.mi_blur_host_free(pin_in)
             L.mi_blur_host_free(pin_out)

@@ -13,9 +13,10 @@ import pytest
 
 from filter_harness import MEDIAN, cpu_run
 from resize_ref import ref_resize
-from warp_ref import (BILINEAR, CLAMP, CONSTANT, LIN_MAX, MAX_DIM, NEAREST, OFF_MAX, Q, cpu_warp_run, float_warp, identity, in_the_admitted_region,
-                      invert, make_warp, max_footprint, quantise, ref_coord, ref_warp, rot90_matrix, rotation_forward, rotation_m, scale_matrix,
-                      takes_tiled)
+from warp_ref import (BILINEAR, CLAMP, CONSTANT, EXTREME, LIMIT_FILL, LIMIT_MAPS, LIN_MAX, MAX_DIM, NEAREST, OFF_MAX, Q, corner_pixels, cpu_warp_run,
+                      extreme_id, float_warp, identity, in_the_admitted_region, invert, limit_out, limit_references, make_warp, max_footprint,
+                      narrow_cases, outside_share, quantise, ref_coord, ref_warp, ref_warp_band, rot90_matrix, rotation_forward, rotation_m,
+                      scale_matrix, takes_tiled)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MODES = (BILINEAR, NEAREST)
@@ -140,6 +141,70 @@ def test_cpu_run_matches_the_restatement(pkg, L, shape):
                 assert want.shape == (n, ho, wo, c)
                 for nt in (1, 3):
                     assert np.array_equal(cpu_warp_run(pkg, L, img, m, wo, ho, mode, border, 201, nt), want), (shape, m, wo, ho, mode, border, nt)
+
+
+def test_band_reference_equals_the_whole_image_reference():
+    """ref_warp_band() against ref_warp() of the whole image: the first band, one in the middle and the last, under a
+    sheared map that leaves the image at a corner, both modes and borders.  What the near-2-GiB GPU tests compare with."""
+    img = np.random.default_rng(41).integers(0, 256, size=(1, 700, 1024, 3), dtype=np.uint8)
+    n, h, w, c = img.shape
+    wo, ho, m = 1024, 1399, [Q, 0, 0, 17030, Q // 2, -Q // 4]
+    for mode in MODES:
+        for border in BORDERS:
+            whole = ref_warp(img, m, wo, ho, mode, border, 173)
+            assert 0 < outside_share(m, mode, w, h, wo, ho - 8, ho) < 1          # the last band leaves the image in part
+            for Y0 in (0, 600, ho - 8):
+                got = ref_warp_band(lambda lo, hi: img[:, lo:hi], h, m, wo, Y0, Y0 + 8, mode, border, 173)
+                assert np.array_equal(got, whole[:, Y0:Y0 + 8]), (mode, border, Y0)
+    # a band wholly below, and one wholly above, the image: the slab is the image's last / first row
+    for m2 in ([Q, 0, 0, 0, Q, 800 * Q], [Q, 0, 0, 0, Q, -50 * Q - 7]):
+        for border in BORDERS:
+            got = ref_warp_band(lambda lo, hi: img[:, lo:hi], h, m2, wo, 16, 24, BILINEAR, border, 173)
+            assert np.array_equal(got, ref_warp(img, m2, wo, 24, BILINEAR, border, 173)[:, 16:24]), (m2, border)
+
+
+def coords_equal_the_restatement(pkg, L, m, wo, ho):
+    """mi_blur_warp_coord at the four corner pixels of the output, both modes."""
+    for mode in MODES:
+        wp = make_warp(pkg, m, wo, ho, mode)
+        for X, Y in corner_pixels(wo, ho):
+            assert pkg.warp_coord(wp, X, Y) == tuple(int(v) for v in ref_coord(m, mode, X, Y)), (m, mode, X, Y)
+
+
+@pytest.mark.parametrize("case", EXTREME, ids=extreme_id)
+def test_cpu_device_on_extreme_shapes(pkg, L, case):
+    """The shapes of test_large_shapes_gpu.py's warp cases: 32768 pixels along one axis, positions up to 2^31."""
+    shape, (wo, ho), m, quarter_turns = case
+    img = np.random.default_rng(sum(shape)).integers(0, 256, size=(1,) + shape, dtype=np.uint8)
+    coords_equal_the_restatement(pkg, L, m, wo, ho)
+    for mode in MODES:
+        for border in BORDERS:
+            want = ref_warp(img, m, wo, ho, mode, border, 173)
+            assert np.array_equal(cpu_warp_run(pkg, L, img, m, wo, ho, mode, border, 173, 4), want), (mode, border)
+            if quarter_turns is not None:
+                assert np.array_equal(want, np.rot90(img, quarter_turns, axes=(1, 2)))
+
+
+def test_cpu_device_on_inputs_of_one_chunk_per_row(pkg, L):
+    for img, name, m, wo, ho in narrow_cases():
+        coords_equal_the_restatement(pkg, L, m, wo, ho)
+        for mode in MODES:
+            for border in BORDERS:
+                want = ref_warp(img, m, wo, ho, mode, border, 173)
+                assert np.array_equal(cpu_warp_run(pkg, L, img, m, wo, ho, mode, border, 173), want), (img.shape, name, mode, border)
+
+
+@pytest.mark.parametrize("c", [1, 2, 3, 4])
+def test_cpu_device_on_maps_at_the_limits_of_the_header(pkg, L, c):
+    """LIMIT_MAPS: coefficients of 2^26 and 2^46, zero and rank-one linear parts, steps of 1 / 65536 pixel."""
+    img, refs = limit_references(2, c)
+    wo, ho = limit_out(c)
+    for name, (m, _, _) in LIMIT_MAPS.items():
+        coords_equal_the_restatement(pkg, L, m, wo, ho)
+        for mode in MODES:
+            for border in BORDERS:
+                got = cpu_warp_run(pkg, L, img, m, wo, ho, mode, border, LIMIT_FILL, 3)
+                assert np.array_equal(got, refs[name, mode, border]), (name, mode, border)
 
 
 def test_set_matrix_and_rotation(pkg, L):

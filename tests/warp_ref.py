@@ -2,7 +2,10 @@
 the product's — with the runners tests/test_warp_host.py and tests/test_warp_gpu.py share (not a test module).  The
 runners keep resize_ref's guards: the input offset into a padded buffer, the output surrounded by 0x5A (GPU) or
 prefilled with 0xA5 with a guard region either side (CPU).  takes_tiled() restates the eligibility rule of the header
-(the exact walk over the tiles included) and tile_geometry() the tiles of blur_warp_tiled_kernel."""
+(the exact walk over the tiles included) and tile_geometry() the tiles of blur_warp_tiled_kernel.  ref_warp_band() gives
+a band of output rows from the input rows it needs alone, for images too large to restate whole; EXTREME, narrow_cases()
+and LIMIT_MAPS are the extreme shapes, one-chunk rows and maps at the header's limits that the GPU tests, the CPU-device
+tests and tests/san_tile_bounds.cpp all walk."""
 import ctypes as C
 import math
 
@@ -94,6 +97,37 @@ def ref_warp(img, m, wo, ho, mode=BILINEAR, border=CONSTANT, fill=0):
     return ((s + (1 << 21)) >> 22).astype(np.uint8)
 
 
+def band_rows(m, mode, h, wo, Y0, Y1):
+    """(lo, hi): the input rows lo..hi (inclusive) that output rows [Y0, Y1) of a warp to `wo` columns need from an image
+    of h rows.  An affine map has its extrema at the band's four corner pixels, so every first tap lies between their
+    smallest and largest y0, every second tap at most one row further; both ends clamped into the image."""
+    _, y0, _, _ = ref_coord(m, mode, [0, wo - 1, 0, wo - 1], [Y0, Y0, Y1 - 1, Y1 - 1])
+    return int(np.clip(y0.min(), 0, h - 1)), int(np.clip(y0.max() + 1, 0, h - 1))
+
+
+def ref_warp_band(rows, h, m, wo, Y0, Y1, mode=BILINEAR, border=CONSTANT, fill=0):
+    """Output rows [Y0, Y1) of ref_warp(img, m, wo, Ho >= Y1, ...) for an image of h rows, from the slab of input rows
+    band_rows() names alone: rows(lo, hi) returns input rows lo..hi - 1 as N x (hi - lo) x W x C.  The band is the warp of
+    the slab under m moved by Y0 output rows and lo input rows.  A tap misses the slab only where it misses the image on
+    the same side (the slab ends inside the image only beyond the band's last tap), so CLAMP repeats the image's own edge
+    row and CONSTANT fills the same taps."""
+    lo, hi = band_rows(m, mode, h, wo, Y0, Y1)
+    slab = rows(lo, hi + 1)
+    assert slab.shape[1] == hi - lo + 1
+    mb = list(m)
+    mb[2] += m[1] * Y0
+    mb[5] += m[4] * Y0 - lo * Q
+    return ref_warp(slab, mb, wo, Y1 - Y0, mode, border, fill)
+
+
+def outside_share(m, mode, w, h, wo, Y0, Y1):
+    """The share of output pixels of rows [Y0, Y1) none of whose taps lies inside the W x H image: `fill` under CONSTANT."""
+    Y, X = np.mgrid[Y0:Y1, 0:wo].astype(np.int64)
+    x0, y0, _, _ = ref_coord(m, mode, X, Y)
+    k = 0 if mode == NEAREST else 1
+    return float(((x0 + k < 0) | (x0 > w - 1) | (y0 + k < 0) | (y0 > h - 1)).mean())
+
+
 def float_warp(img, m, wo, ho, border=CONSTANT, fill=0):
     """Real-valued bilinear at the exact Q16 position in float64, not rounded."""
     n, h, w, c = img.shape
@@ -161,6 +195,152 @@ def takes_tiled(shape, m, wo, ho, mode=BILINEAR, border=CONSTANT, offset_in=0, o
 def in_the_admitted_region(m):
     """|m[0]| + |m[1]| <= 3Q/2 and |m[3]| + |m[4]| <= 3Q/2: every aligned BILINEAR launch in here takes the tiled kernel."""
     return abs(m[0]) + abs(m[1]) <= 3 * Q // 2 and abs(m[3]) + abs(m[4]) <= 3 * Q // 2
+
+
+# ---------------------------------------------------------------- cases the GPU tests, the CPU-device tests and
+# tests/san_tile_bounds.cpp share
+# Extreme shapes: ((input h, w, c), (Wo, Ho), m, k where the map is np.rot90(img, k) exactly).  All take the tiled kernel
+# under both borders; positions (Q16) reach 2^31 along the 32768-long axis (the last two pass it).
+EXTREME = [((1, 32768, 1), (32768, 1), [Q, 0, 3 * Q // 8 + 1, 0, Q, 0], None),                 # one row, 512 strips
+           ((2, 32768, 1), (16384, 2), [2 * Q, 0, Q // 2, 0, Q, Q // 3], None),                # 2x reduction: sx passes 2^31
+           ((32768, 16, 1), (16, 32768), rotation_m(16, 32768, 0.02), None),                   # 1024 tile rows of one chunk per row
+           ((16, 32768, 1), (16, 32768), rot90_matrix(32768), 1),                              # m[2] = 2^31 - 2^16: columns become rows
+           ((32768, 16, 1), (32768, 16), [0, Q, 0, -Q, 0, 32767 * Q], 3),                      # the transpose back
+           ((3, 16384, 4), (32768, 3), [Q // 2, 0, -Q // 4, 0, Q, 0], None),                   # 8192 output chunks per row
+           ((2, 32768, 3), (32768, 2), [Q, 0, -5 * Q // 8, 0, Q, Q // 2], None),               # 2048 groups of three chunks
+           # the cases above stay just below 2^31; these two pass it by 40 pixels, beyond the right and the bottom edge, where a
+           # position kept in 32 bits wraps to the opposite edge (what CLAMP repeats tells them apart)
+           ((2, 32768, 1), (16384, 2), [2 * Q, 0, 40 * Q + Q // 2, 0, Q, Q // 3], None),
+           ((32768, 16, 1), (16, 32768), [Q, 0, Q // 3, 0, Q, 40 * Q + Q // 2], None)]
+
+
+def extreme_id(case):
+    return "x".join(map(str, case[0])) + f"-{case[1][0]}x{case[1][1]}-at{case[2][2] >> 16},{case[2][5] >> 16}"       # input, output, the pixel output (0, 0) reads
+
+
+def corner_pixels(wo, ho):
+    return [(0, 0), (wo - 1, 0), (0, ho - 1), (wo - 1, ho - 1)]
+
+
+# Inputs of one 16-byte chunk per row (3 channels: one group of three chunks): the staged box of the tiled kernel is the whole row, or the whole image.
+NARROW_ROWS = [(16, 1), (8, 2), (16, 3), (4, 4)]        # (w, c)
+NARROW_HEIGHTS = (1, 2, 33)
+NARROW_N = 2
+
+
+def impulse_rows(rng, n, h, w, c):
+    """N x h x w x c random bytes with 0 / 255 impulses in the first and the last pixel of every row."""
+    img = rng.integers(0, 256, size=(n, h, w, c), dtype=np.uint8)
+    flip = (np.arange(n)[:, None] + np.arange(h)[None, :]) % 2 == 1
+    img[:, :, 0, :] = np.where(flip, 255, 0)[:, :, None]
+    img[:, :, -1, :] = np.where(flip, 0, 255)[:, :, None]
+    return img
+
+
+def narrow_cases():
+    """(img, name, m, Wo, Ho): three 64-pixel strips and two tile rows out of every one-chunk row; an enlargement, a
+    rotation, a sub-pixel shift and a map that lies wholly left of the image."""
+    rng = np.random.default_rng(78)
+    for w, c in NARROW_ROWS:
+        assert w * c == (48 if c == 3 else 16)              # one chunk; for 3 channels one group of three
+        wo, ho = (132 if c == 4 else 144), 33
+        for h in NARROW_HEIGHTS:
+            img = impulse_rows(rng, NARROW_N, h, w, c)
+            for name, m in (("x4", scale_matrix(4, 1)), ("rot30", rotation_m(w, h, 30)), ("subpixel", [Q, 0, -3 * Q // 8, 0, Q, 5 * Q // 8]),
+                            ("far-left", identity(-w - 3, 1))):
+                yield img, name, m, wo, ho
+
+
+# Maps at the limits of the header (linear part 2^26, translation 2^46) and degenerate maps, on a LIMIT_HW x LIMIT_HW input:
+# name -> (m, class (classify()), for a wholly-outside map what CLAMP repeats (limit_clamp_want())).  The last two carry a
+# limit coefficient and still put a whole output column, or row, inside the image.
+LIMIT_HW = 64
+_L, _O = LIN_MAX, OFF_MAX
+LIMIT_MAPS = {
+    "L-scale": ([_L, 0, 0, 0, _L, 0], "single", None),
+    "L-antidiagonal": ([-_L, _L, 63 * Q, _L, -_L, 63 * Q], "single", None),
+    "L-last-pixel": ([_L, 0, -79 * _L + 5 * Q, 0, _L, -39 * _L + 7 * Q + 123], "single", None),          # only output (79, 39) lands in the image
+    "O-far": ([Q, 0, _O, 0, Q, _O], "outside", "bottom-right"),
+    "O-far-negative": ([-Q, 0, -_O, 0, -Q, -_O], "outside", "top-left"),
+    "O-left": ([Q, 0, -_O, 0, Q, 3 * Q], "outside", "left-edge"),
+    "L-O-all": ([_L, _L, _O, -_L, -_L, -_O], "outside", "top-right"),
+    "zero-linear": ([0, 0, 10 * Q + 777, 0, 0, 20 * Q + 31111], "single", None),
+    "rank-one": ([Q, 0, 0, Q, 0, Q // 3], "varied", None),
+    "step-1/65536": ([1, 0, 5 * Q, 0, 1, 6 * Q + 65535], "single", None),
+    "L-one-column": ([_L, 0, -40 * _L + 30 * Q, 0, Q, 0], "varied", None),
+    "L-one-row": ([Q, 0, 0, _L, Q, -20 * _L], "varied", None),
+}
+LIMIT_INSIDE = ("L-one-column", "L-one-row")
+LIMIT_FILL = 173
+
+
+def limit_out(c):
+    """80 x 40, or 96 x 40 for 3 channels: whole groups of three chunks."""
+    return (96 if c == 3 else 80), 40
+
+
+def limit_corners(n, c):
+    """The corner bytes of limit_image(): top-left, top-right, bottom-left, bottom-right of image i are 1 + 4 i .. 4 + 4 i."""
+    return [[1 + 4 * i, 2 + 4 * i, 3 + 4 * i, 4 + 4 * i] for i in range(n)]
+
+
+def limit_image(n, c):
+    """N x 64 x 64 x c: interior bytes 16..159, the four edges 200 / 210 (top / bottom rows) and 220 / 230 (left / right
+    columns), four distinct corner bytes per image, none of them LIMIT_FILL: a clamp to the wrong side shows."""
+    img = np.random.default_rng(64 + c).integers(16, 160, size=(n, LIMIT_HW, LIMIT_HW, c), dtype=np.uint8)
+    img[:, 0], img[:, -1] = 200, 210
+    img[:, 1:-1, 0], img[:, 1:-1, -1] = 220, 230
+    for i, (tl, tr, bl, br) in enumerate(limit_corners(n, c)):
+        img[i, 0, 0], img[i, 0, -1], img[i, -1, 0], img[i, -1, -1] = tl, tr, bl, br
+    return img
+
+
+def classify(m, mode, w, h, wo, ho):
+    """"outside": no output pixel has a tap inside the image; "single": those that have one all share one first tap (x0, y0);
+    "varied": they read more than one."""
+    Y, X = np.mgrid[0:ho, 0:wo].astype(np.int64)
+    x0, y0, _, _ = ref_coord(m, mode, X, Y)
+    k = 0 if mode == NEAREST else 1
+    inside = (x0 + k >= 0) & (x0 <= w - 1) & (y0 + k >= 0) & (y0 <= h - 1)
+    firsts = set(zip(x0[inside].tolist(), y0[inside].tolist()))
+    return "outside" if not firsts else "single" if len(firsts) == 1 else "varied"
+
+
+def limit_clamp_want(img, what, wo, ho):
+    """What CLAMP gives for a wholly-outside map of LIMIT_MAPS: one corner of each image, or rows 3.. of its left edge."""
+    n, h, w, c = img.shape
+    if what == "left-edge":
+        return np.broadcast_to(img[:, 3:3 + ho, :1], (n, ho, wo, c))
+    y, x = {"top-left": (0, 0), "top-right": (0, w - 1), "bottom-left": (h - 1, 0), "bottom-right": (h - 1, w - 1)}[what]
+    return np.broadcast_to(img[:, y:y + 1, x:x + 1], (n, ho, wo, c))
+
+
+def limit_references(n, c):
+    """(img, {(name, mode, border): ref_warp}) for LIMIT_MAPS on limit_image(n, c).  Many of these outputs are nearly constant,
+    which a kernel that writes only `fill` or only one corner would give too; so, on the reference alone: every map is of
+    the class LIMIT_MAPS states; a wholly-outside map gives the stated corner or edge under CLAMP (and `fill` under
+    CONSTANT); no two wholly-outside maps that repeat different parts of the image share an output; the maps of
+    LIMIT_INSIDE put at least 30 output pixels inside the image that are neither `fill` nor a corner byte."""
+    img = limit_image(n, c)
+    wo, ho = limit_out(c)
+    corner_bytes = [LIMIT_FILL] + sum(limit_corners(n, c), [])
+    refs = {}
+    for name, (m, cls, what) in LIMIT_MAPS.items():
+        for mode in (BILINEAR, NEAREST):
+            assert classify(m, mode, LIMIT_HW, LIMIT_HW, wo, ho) == cls, (name, mode)
+            for border in (CLAMP, CONSTANT):
+                ref = refs[name, mode, border] = ref_warp(img, m, wo, ho, mode, border, LIMIT_FILL)
+                if cls == "outside":
+                    assert np.array_equal(ref, limit_clamp_want(img, what, wo, ho) if border == CLAMP else np.full_like(ref, LIMIT_FILL)), (name, mode, border)
+                if name in LIMIT_INSIDE:
+                    assert (~np.isin(ref, corner_bytes)).all(axis=3).sum() >= 30 * n, (name, mode, border)
+    outside = [(name, what) for name, (_, cls, what) in LIMIT_MAPS.items() if cls == "outside"]
+    assert len({what for _, what in outside}) == len(outside) == 4
+    for mode in (BILINEAR, NEAREST):
+        for i, (a, _) in enumerate(outside):
+            for b, _ in outside[i + 1:]:
+                assert not np.array_equal(refs[a, mode, CLAMP], refs[b, mode, CLAMP]), (a, b, mode)
+    return img, refs
 
 
 def make_warp(pkg, m, wo, ho, mode=BILINEAR, border=CONSTANT, fill=0):
