@@ -248,6 +248,24 @@ class Warp(C.Structure):
         return w
 
 
+class WarpPerspective(C.Structure):
+    """mi_blur_warp_perspective: the output size, the mode, the border, the fill byte (as Warp) and the OUTPUT -> INPUT
+    homography, row-major 3 x 3 int64, free scale."""
+    _fields_ = [("out_width", C.c_int), ("out_height", C.c_int), ("mode", C.c_int), ("border", C.c_int), ("fill", C.c_int),
+                ("h", C.c_int64 * 9)]
+
+    @classmethod
+    def from_matrix(cls, M, out_width: int, out_height: int, mode="bilinear", border="constant", fill: int = 0, inverse: bool = False) -> "WarpPerspective":
+        """M: a real 3 x 3 matrix, input -> output (inverse=False: what OpenCV's warpPerspective takes) or output -> input
+        (inverse=True: WARP_INVERSE_MAP); normalised and quantised by mi_blur_warp_perspective_set_matrix for this output size."""
+        w = cls(int(out_width), int(out_height), _resize_mode(mode, "warp_perspective"), _warp_border(border), int(fill))
+        flat = [float(v) for row in M for v in (row if hasattr(row, "__len__") else [row])]
+        if len(flat) != 9:
+            raise ValueError("warp_perspective: M is a 3 x 3 matrix")
+        check(lib().mi_blur_warp_perspective_set_matrix(C.byref(w), (C.c_double * 9)(*flat), int(bool(inverse))), "mi_blur_warp_perspective_set_matrix")
+        return w
+
+
 def _warp_border(border) -> int:
     if isinstance(border, str):
         if border not in WARP_BORDERS:
@@ -367,6 +385,12 @@ def lib() -> C.CDLL:
         "mi_blur_enqueue_warp": (i, [u8p, u8p, i, i, i, i, C.POINTER(Warp), vp]),
         "mi_blur_cpu_run_warp": (i, [u8p, u8p, i, i, i, i, C.POINTER(Warp), i]),
         "mi_blur_ctx_set_warp": (i, [vp, C.POINTER(Warp)]),
+        "mi_blur_warp_perspective_coord": (i, [C.POINTER(WarpPerspective), i, i, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(i), C.POINTER(i)]),
+        "mi_blur_warp_perspective_quad": (i, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "mi_blur_warp_perspective_set_matrix": (i, [C.POINTER(WarpPerspective), C.POINTER(C.c_double), i]),
+        "mi_blur_enqueue_warp_perspective": (i, [u8p, u8p, i, i, i, i, C.POINTER(WarpPerspective), vp]),
+        "mi_blur_cpu_run_warp_perspective": (i, [u8p, u8p, i, i, i, i, C.POINTER(WarpPerspective), i]),
+        "mi_blur_ctx_set_warp_perspective": (i, [vp, C.POINTER(WarpPerspective)]),
         "mi_blur_conv_preset": (i, [i, C.POINTER(Conv)]),
         "mi_blur_enqueue_conv": (i, [u8p, u8p, i, i, i, i, C.POINTER(Conv), vp]),
         "mi_blur_enqueue_conv_band": (i, [u8p, u8p, i, i, i, i, i, C.POINTER(Conv), vp]),
@@ -528,6 +552,12 @@ class Context:
         """The affine warp in place of the blur (before the first submit only): submit() then writes images of
         warp.out_width x warp.out_height."""
         check(lib().mi_blur_ctx_set_warp(self.h, C.byref(warp)), "mi_blur_ctx_set_warp")
+        self.warp_spec = warp
+
+    def set_warp_perspective(self, warp: "WarpPerspective") -> None:
+        """The perspective warp in place of the blur (before the first submit only): submit() then writes images of
+        warp.out_width x warp.out_height."""
+        check(lib().mi_blur_ctx_set_warp_perspective(self.h, C.byref(warp)), "mi_blur_ctx_set_warp_perspective")
         self.warp_spec = warp
 
     def submit_bands(self, host_in, host_out, n_images: int, host_image_stride: int, band_rows: int,
@@ -923,3 +953,48 @@ def rotate(images, angle: float, scale: float = 1.0, center=None, dsize=None, mo
     if center is None:
         center = ((w - 1) / 2.0, (h - 1) / 2.0)
     return warp_affine(a, rotation_matrix(center, angle, scale), dsize, mode, border, fill, False, device, batch)
+
+
+def warp_perspective_coord(warp: "WarpPerspective", X: int, Y: int) -> tuple[int, int, int, int]:
+    """(x0, y0, fx, fy) of output pixel (X, Y) under warp's mode and homography (mi_blur_warp_perspective_coord): the
+    unclamped tap origin (it can reach 2^50) and the weights 0..2047; nearest gives (xi, yi, 0, 0)."""
+    x0, y0, fx, fy = C.c_int64(), C.c_int64(), C.c_int(), C.c_int()
+    check(lib().mi_blur_warp_perspective_coord(C.byref(warp), int(X), int(Y), C.byref(x0), C.byref(y0), C.byref(fx), C.byref(fy)), "mi_blur_warp_perspective_coord")
+    return x0.value, y0.value, fx.value, fy.value
+
+
+def perspective_matrix(src_quad, dst_quad):
+    """The forward 3 x 3 matrix that takes the four points of src_quad to those of dst_quad, as nested lists, M[2][2] = 1
+    (mi_blur_warp_perspective_quad; OpenCV's getPerspectiveTransform).  Each quad: four (x, y) pairs."""
+    src = [float(v) for pt in src_quad for v in pt]
+    dst = [float(v) for pt in dst_quad for v in pt]
+    if len(src) != 8 or len(dst) != 8:
+        raise ValueError("perspective_matrix: a quad is four (x, y) points")
+    H = (C.c_double * 9)()
+    check(lib().mi_blur_warp_perspective_quad((C.c_double * 8)(*src), (C.c_double * 8)(*dst), H), "mi_blur_warp_perspective_quad")
+    return [list(H[0:3]), list(H[3:6]), list(H[6:9])]
+
+
+def warp_perspective(images, M, dsize=None, mode="bilinear", border="constant", fill: int = 0, inverse: bool = False, device: int = 0, batch: int = 0):
+    """Perspective warp, numpy in -> numpy out, after OpenCV's warpPerspective: M is a real 3 x 3 matrix from input to
+    output coordinates (inverse=True: from output to input); dsize = (out_w, out_h), the input's size by default.  Exact
+    fixed-point bilinear (the homography with up to 30 fraction bits, positions rounded to 11, one final rounding) or
+    nearest; border 'constant' or 'clamp' (include/mi_blur.h has the definition).  A horizon that crosses the output is
+    an error.  images, device, batch and the result as warp_affine()."""
+    a = _images(images, "warp_perspective")
+    rank = a.ndim
+    if rank == 2:
+        a = a[None, :, :, None]
+    elif rank == 3:
+        a = a[None]
+    n, h, w, c = a.shape
+    if h == 0 or w == 0 or c == 0:
+        raise ValueError("warp_perspective: images must not be empty")
+    wo, ho = (w, h) if dsize is None else (int(dsize[0]), int(dsize[1]))
+    if wo < 1 or ho < 1:
+        raise ValueError("warp_perspective: dsize is (out_w, out_h), both at least 1")
+    if not 0 <= int(fill) <= 255:
+        raise ValueError("warp_perspective: fill is 0..255")
+    wp = WarpPerspective.from_matrix(M, wo, ho, mode, border, fill, inverse)
+    out = _filter_images(a, 1, device, batch, lambda ctx: ctx.set_warp_perspective(wp), (ho, wo))
+    return out[0, :, :, 0] if rank == 2 else out[0] if rank == 3 else out

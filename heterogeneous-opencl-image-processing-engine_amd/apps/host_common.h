@@ -178,6 +178,9 @@ struct Options {
     bool rotate_given = false;           // --rotate DEG [--nearest] [--border-fill V]: rotate every image by DEG degrees about its centre, same size
     double rotate_deg = 0.0;             //              (mi_blur_ctx_set_warp; bilinear, --nearest: nearest; CLAMP border, --border-fill V: CONSTANT with fill V;
     int border_fill = -1;                //              heterogeneous_blur only: no bands)
+    bool persp_given = false;            // --perspective x0,y0,..,x3,y3 [--nearest] [--border-fill V]: the source quad (top-left, top-right, bottom-right, bottom-left;
+    double persp_quad[8] = {};           //              input pixels, reals) is mapped onto the corners of an output of the input's size
+                                         //              (mi_blur_ctx_set_warp_perspective; mode and border as --rotate; heterogeneous_blur only: no bands)
     bool nearest = false;                //              mi_blur_ctx_set_resize on every context, outputs of that size (heterogeneous_blur only: no bands)
     int images = 5000;                   // --images N   (NUM_IMAGES, heterogeneous_blur.c:44)
     bool images_given = false;
@@ -261,6 +264,12 @@ inline int parse_flags(int argc, char **argv, Options &o)
             if (sscanf(next("--rotate"), "%lf%c", &o.rotate_deg, &tail) != 1 || !(o.rotate_deg >= -36000.0 && o.rotate_deg <= 36000.0)) { printf("Error: --rotate DEG, degrees counter-clockwise\n"); exit(-1); }
             o.rotate_given = true;
         }
+        else if (a == "--perspective") {
+            char tail = 0;
+            double *q = o.persp_quad;
+            if (sscanf(next("--perspective"), "%lf,%lf,%lf,%lf,%lf,%lf,%lf,%lf%c", q, q + 1, q + 2, q + 3, q + 4, q + 5, q + 6, q + 7, &tail) != 8) { printf("Error: --perspective x0,y0,x1,y1,x2,y2,x3,y3: the source quad, top-left, top-right, bottom-right, bottom-left\n"); exit(-1); }
+            o.persp_given = true;
+        }
         else if (a == "--border-fill") {
             char tail = 0;
             if (sscanf(next("--border-fill"), "%d%c", &o.border_fill, &tail) != 1 || o.border_fill < 0 || o.border_fill > 255) { printf("Error: --border-fill V, 0..255\n"); exit(-1); }
@@ -310,8 +319,10 @@ inline int parse_flags(int argc, char **argv, Options &o)
     if (o.resize_w && (o.resident || !o.frames.empty())) { printf("Error: --resize excludes --resident and --frames\n"); exit(-1); }
     if (o.rotate_given && (o.resize_w || o.ksize_given || o.sigma > 0.0 || o.median || o.morph || o.bilateral || o.conv_preset >= 0 || o.pyr_down)) { printf("Error: --rotate excludes --resize, --ksize, --sigma, --median, --erode, --dilate, --morph-gradient, --bilateral, --conv and --pyr-down\n"); exit(-1); }
     if (o.rotate_given && (o.resident || !o.frames.empty())) { printf("Error: --rotate excludes --resident and --frames\n"); exit(-1); }
-    if (o.border_fill >= 0 && !o.rotate_given) { printf("Error: --border-fill needs --rotate\n"); exit(-1); }
-    if (o.nearest && !o.resize_w && !o.rotate_given) { printf("Error: --nearest needs --resize\n"); exit(-1); }
+    if (o.persp_given && (o.rotate_given || o.resize_w || o.ksize_given || o.sigma > 0.0 || o.median || o.morph || o.bilateral || o.conv_preset >= 0 || o.pyr_down)) { printf("Error: --perspective excludes --rotate, --resize, --ksize, --sigma, --median, --erode, --dilate, --morph-gradient, --bilateral, --conv and --pyr-down\n"); exit(-1); }
+    if (o.persp_given && (o.resident || !o.frames.empty())) { printf("Error: --perspective excludes --resident and --frames\n"); exit(-1); }
+    if (o.border_fill >= 0 && !o.rotate_given && !o.persp_given) { printf("Error: --border-fill needs --rotate\n"); exit(-1); }
+    if (o.nearest && !o.resize_w && !o.rotate_given && !o.persp_given) { printf("Error: --nearest needs --resize\n"); exit(-1); }
     return npos;
 }
 
@@ -338,6 +349,9 @@ struct HostFilter {
     bool warp = false;          // --rotate DEG [--nearest] [--border-fill V]: the warp `wp` (mi_blur_ctx_set_warp); its size and matrix
     double rotate_deg = 0.0;    // come from the image: print_warp() fills them in
     mi_blur_warp wp{};
+    bool persp = false;         // --perspective QUAD [--nearest] [--border-fill V]: the perspective warp `pp` (mi_blur_ctx_set_warp_perspective);
+    double persp_quad[8] = {};  // its size and homography come from the image: print_warp_perspective() fills them in
+    mi_blur_warp_perspective pp{};
 };
 
 inline HostFilter filter_of(const Options &o)
@@ -367,6 +381,9 @@ inline HostFilter filter_of(const Options &o)
     f.wp.mode = o.nearest ? MI_BLUR_RESIZE_NEAREST : MI_BLUR_RESIZE_BILINEAR;
     f.wp.border = o.border_fill >= 0 ? MI_BLUR_WARP_CONSTANT : MI_BLUR_WARP_CLAMP;
     f.wp.fill = o.border_fill >= 0 ? o.border_fill : 0;
+    f.persp = o.persp_given;
+    std::copy(o.persp_quad, o.persp_quad + 8, f.persp_quad);
+    f.pp.mode = f.wp.mode; f.pp.border = f.wp.border; f.pp.fill = f.wp.fill;
     return f;
 }
 
@@ -381,6 +398,7 @@ inline void set_filter(mi_blur_ctx *ctx, const HostFilter &f)
     if (f.pyr_down) mi_check(mi_blur_ctx_set_sep_down(ctx, &f.down_k, &f.down_d), "Failed to set the pyramid filter");
     if (f.resize) mi_check(mi_blur_ctx_set_resize(ctx, &f.rs), "Failed to set the resize");
     if (f.warp) mi_check(mi_blur_ctx_set_warp(ctx, &f.wp), "Failed to set the warp");
+    if (f.persp) mi_check(mi_blur_ctx_set_warp_perspective(ctx, &f.pp), "Failed to set the perspective warp");
 }
 
 // --rotate, once the image size is known: the warp of f becomes the rotation about the image's centre at the image's
@@ -392,6 +410,19 @@ inline void print_warp(HostFilter &f, int width, int height)
     mi_check(mi_blur_warp_rotation((width - 1) / 2.0, (height - 1) / 2.0, f.rotate_deg, 1.0, fwd), "No rotation matrix");
     mi_check(mi_blur_warp_set_matrix(&f.wp, fwd, 0), "No warp matrix for --rotate");
     printf("Blur kernel: %s warp, rotate %g deg, %dx%d -> %dx%d\n", f.wp.mode == MI_BLUR_RESIZE_NEAREST ? "nearest" : "bilinear", f.rotate_deg, width, height, width, height);
+}
+
+// --perspective, once the image size is known: the homography that takes the source quad onto the corners of an output
+// of the image's size (mi_blur_warp_perspective_quad, then mi_blur_warp_perspective_set_matrix of that forward matrix),
+// and the banner's "Blur kernel" line.  A quad with three corners in line, or one whose horizon crosses the output, ends the run with a message.
+inline void print_warp_perspective(HostFilter &f, int width, int height)
+{
+    const double dst[8] = {0.0, 0.0, width - 1.0, 0.0, width - 1.0, height - 1.0, 0.0, height - 1.0};
+    double fwd[9];
+    f.pp.out_width = width; f.pp.out_height = height;
+    if (mi_blur_warp_perspective_quad(f.persp_quad, dst, fwd) != MI_BLUR_OK) { printf("Error: --perspective: no homography takes this quad to the image's corners (three corners in line?)\n"); exit(-1); }
+    if (mi_blur_warp_perspective_set_matrix(&f.pp, fwd, 0) != MI_BLUR_OK) { printf("Error: --perspective: the quad's horizon crosses the %dx%d output, or its map is outside the limits\n", width, height); exit(-1); }
+    printf("Blur kernel: %s warp, perspective, %dx%d -> %dx%d\n", f.pp.mode == MI_BLUR_RESIZE_NEAREST ? "nearest" : "bilinear", width, height, width, height);
 }
 
 // The banner's "Blur kernel" line of --resize (after the image is loaded, like print_pyr_down()); *wo, *ho: the size of
@@ -417,7 +448,7 @@ inline int filter_halo(const HostFilter &f) { return f.conv_preset >= 0 ? f.conv
 // The banner's "Blur kernel" line (with the taps of a Gaussian).
 inline void print_filter(const HostFilter &f)
 {
-    if (f.pyr_down || f.resize || f.warp) return;     // print_pyr_down() / print_resize() / print_warp(), once the image size is known
+    if (f.pyr_down || f.resize || f.warp || f.persp) return;     // print_pyr_down() / print_resize() / print_warp() / print_warp_perspective(), once the image size is known
     if (f.median) { printf("Blur kernel: %dx%d median\n", f.median, f.median); return; }
     if (f.conv_preset >= 0) { printf("Blur kernel: %dx%d convolution (%s)\n", 2 * f.conv.rx + 1, 2 * f.conv.ry + 1, f.conv_name.c_str()); return; }
     if (f.bilateral) { printf("Blur kernel: %dx%d bilateral (sigma_color %g, sigma_space %g)\n", f.bilateral, f.bilateral, f.sigma_color, f.sigma_space); return; }

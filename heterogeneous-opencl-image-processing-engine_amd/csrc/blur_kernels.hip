@@ -1643,6 +1643,7 @@ int launch(const LaunchDesc &d)
     case FilterKind::SEP_DOWN: return launch_sep_down(d);
     case FilterKind::RESIZE: return launch_resize(d);
     case FilterKind::WARP: return launch_warp(d);
+    case FilterKind::WARP_PERSP: return launch_warp_persp(d);
     }
     return MI_BLUR_ERR_INVALID;
 }

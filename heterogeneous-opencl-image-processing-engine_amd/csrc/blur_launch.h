@@ -53,6 +53,8 @@ int launch_resize(const LaunchDesc &d);
 // The affine warp (FilterKind::WARP, warp_kernels.hip): d.in = n_images images of band_rows x width, d.out = n_images
 // images of out_h x out_w.  The contract of launch_resize.
 int launch_warp(const LaunchDesc &d);
+// The perspective warp (FilterKind::WARP_PERSP, warp_kernels.hip).  The contract of launch_resize.
+int launch_warp_persp(const LaunchDesc &d);
 // Sets what last_kernel() reports for the calling thread.
 void set_last_kernel(const char *name);
 

@@ -422,6 +422,24 @@ void cpu_warp_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, const F
     }
 }
 
+// The same for the perspective warp of f (f.warp_h): every byte through persp_coord_at() and warp_sample() (filter.h), the
+// functions of the GPU's generic kernel; the numerators and the denominator step along a row as the tiled kernel's do.
+void cpu_warp_persp_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, const Filter &f, int Y_begin, int Y_end)
+{
+    const int Wo = f.out_w;
+    const size_t pitch = (size_t)W * C, opitch = (size_t)Wo * C;
+    for (int Y = Y_begin; Y < Y_end; Y++) {
+        uint8_t *o = out + (size_t)Y * opitch;
+        PerspPos s = persp_position(f.warp_h, 0, Y);
+        for (int X = 0; X < Wo; X++) {
+            const WarpCoord q = persp_coord_at(s, f.sample_mode, W, H);
+            for (int c = 0; c < C; c++)
+                o[(size_t)X * C + c] = (uint8_t)warp_sample(in + c, pitch, C, W, H, f.warp_border, (unsigned)f.warp_fill, q);
+            s.nx += f.warp_h[0]; s.ny += f.warp_h[3]; s.d += f.warp_h[6];
+        }
+    }
+}
+
 // Empty for any filter but a resize.
 std::vector<ResizeCoord> resize_xtable(int W, const Filter &f)
 {
@@ -472,6 +490,7 @@ void cpu_blur_batch(const uint8_t *in, uint8_t *out, int W, int band_rows, int C
             case FilterKind::SEP_DOWN: cpu_sep_down_rows(src, dst, W, band_rows, C, f, ys, ye); break;
             case FilterKind::RESIZE: cpu_resize_rows(src, dst, W, band_rows, C, f, ys, ye, xtab.data()); break;
             case FilterKind::WARP: cpu_warp_rows(src, dst, W, band_rows, C, f, ys, ye); break;
+            case FilterKind::WARP_PERSP: cpu_warp_persp_rows(src, dst, W, band_rows, C, f, ys, ye); break;
             }
         }
     };

@@ -20,7 +20,7 @@ struct SepTaps {
     unsigned wx[2 * SEP_MAX_R + 1], wy[2 * SEP_MAX_R + 1];
 };
 
-enum class FilterKind { BOX, SEP, MEDIAN, MORPH, BILATERAL, CONV, SEP_DOWN, RESIZE, WARP };
+enum class FilterKind { BOX, SEP, MEDIAN, MORPH, BILATERAL, CONV, SEP_DOWN, RESIZE, WARP, WARP_PERSP };
 
 // BOX: the fixed 3x3 / 5x5 kernel of `radius` 1|2.  SEP: the separable kernel `taps`.  MEDIAN: the median of `radius` 1..7.
 // MORPH: the window minimum / maximum / their difference (`morph_op`) over (2 morph_rx + 1) x (2 morph_ry + 1).
@@ -33,8 +33,10 @@ enum class FilterKind { BOX, SEP, MEDIAN, MORPH, BILATERAL, CONV, SEP_DOWN, RESI
 // RESIZE: the fixed-point resize (mi_blur_resize) to out_w x out_h in `sample_mode`: the output may be smaller or
 // larger than the input, in either axis.
 // WARP: the affine warp (mi_blur_warp) to out_w x out_h: output pixel (X, Y) samples the input at the Q16 position
-// warp_m maps it to, in `sample_mode`, with the border rule `warp_border` / `warp_fill`.  warp_m is the only map source
-// there is; whatever produces positions goes through warp_position() below, so another source would slot in there.
+// warp_m maps it to, in `sample_mode`, with the border rule `warp_border` / `warp_fill`.  Whatever produces positions
+// goes through a position function (warp_position() below for warp_m), so another map source slots in beside it:
+// WARP_PERSP: the perspective warp (mi_blur_warp_perspective): as WARP, but the position of output pixel (X, Y) is the
+// quotient of two linear forms of warp_h (persp_position(), persp_axis() below): the second map source.
 struct Filter {
     FilterKind kind;
     int radius;             // BOX and MEDIAN
@@ -49,6 +51,7 @@ struct Filter {
     int out_w = 0, out_h = 0, sample_mode = 0;                // RESIZE and WARP: the output image (1..MI_BLUR_RESIZE_MAX_DIM each way) and mi_blur_resize_mode; after them, for the same reason
     int warp_border = 0, warp_fill = 0;                       // WARP (mi_blur_warp_border, fill 0..255); last, for the same reason
     int64_t warp_m[6] = {};                                   // WARP: the OUTPUT -> INPUT map, Q16, row-major 2 x 3
+    int64_t warp_h[9] = {};                                   // WARP_PERSP: the OUTPUT -> INPUT homography, row-major 3 x 3, free scale; out_w .. warp_fill as WARP
 };
 
 #if defined(__HIP__)
@@ -191,6 +194,116 @@ inline bool warp_ok(const mi_blur_warp *w, int W, int H, int C)
     return w && resize_ok(w->out_width, w->out_height, w->mode, W, H, C) && warp_map_ok(w->border, w->fill, w->m);
 }
 
+// ---- the perspective warp (include/mi_blur.h, "Perspective warp").  The GPU kernels, the CPU device and
+// mi_blur_warp_perspective_coord all take their coordinates from persp_position() and persp_axis(); the taps, the blend
+// and the border rules are the affine warp's (warp_sample(), warp_tap()).
+// The numerators and the denominator of output pixel (X, Y): |h| within the limits of persp_map_ok() keeps all three below 2^49.
+struct PerspPos { int64_t nx, ny, d; };
+MI_BLUR_HD inline PerspPos persp_position(const int64_t *h, int X, int Y)
+{
+    return {h[0] * X + h[1] * Y + h[2], h[3] * X + h[4] * Y + h[5], h[6] * X + h[7] * Y + h[8]};
+}
+// floor(a / b) for b > 0.
+MI_BLUR_HD inline int64_t floor_div(int64_t a, int64_t b)
+{
+    const int64_t q = a / b, r = a - q * b;
+    return r < 0 ? q - 1 : q;
+}
+// min(max(floor(num / den), lo), hi) for |num| < 2^62, 0 < den < 2^51, |lo|, |hi| < 2^27 and rden = 1.0 / (double)den,
+// without a 64-bit division: the double estimate est = num * rden is within 2^-51 of the quotient t in relative terms
+// (den is exact in a double, num and the reciprocal are rounded once each, the product once).  est >= hi + 2 means
+// t > hi + 1 and est <= lo - 2 means t < lo - 1: the clamp decides alone.  Otherwise |t| < 2^27 + 3, the estimate is off
+// by less than 2^-23, floor(est) is floor(t) or one beside it, and the exact remainder (|q * den| <= |num| + den < 2^63)
+// says which.  The same bytes on the CPU and the GPU whatever the last bit of either's double division: the remainder decides.
+MI_BLUR_HD inline int64_t floor_div_clamped(int64_t num, int64_t den, double rden, int64_t lo, int64_t hi)
+{
+    const double est = (double)num * rden;
+    if (est >= (double)(hi + 2)) return hi;
+    if (est <= (double)(lo - 2)) return lo;
+    int64_t q = (int64_t)__builtin_floor(est);
+    const int64_t r = num - q * den;
+    q = r < 0 ? q - 1 : r >= den ? q + 1 : q;
+    return q < lo ? lo : q > hi ? hi : q;
+}
+// One axis of a position N / D (D >= 1): the first tap i0 and the weight f (0..2047) of tap i0 + 1.  BILINEAR: the position
+// rounded to 11 fraction bits, p = floor((N * 4096 + D) / (2 D)), i0 = p >> 11, f = p & 2047.  NEAREST:
+// i0 = floor((2 N + D) / (2 D)), f = 0.  n > 0: p is clamped into [-2 * 2048, (n + 1) * 2048] (NEAREST: i0 into
+// [-2, n + 1]) as warp_axis() does, for the same reason, and rden = 1.0 / (double)(2 D) (one reciprocal serves both
+// axes of a pixel).  n == 0: not clamped, the plain 64-bit division, rden unused; i0 can reach 2^50.
+struct PerspAxis { int64_t i0; int f; };
+MI_BLUR_HD inline PerspAxis persp_axis(int64_t N, int64_t D, double rden, int mode, int n)
+{
+    const bool nearest = mode == MI_BLUR_RESIZE_NEAREST;
+    const int64_t num = nearest ? 2 * N + D : N * 4096 + D, den = 2 * D;
+    if (n == 0) {
+        const int64_t p = floor_div(num, den);
+        return nearest ? PerspAxis{p, 0} : PerspAxis{p >> 11, (int)(p & 2047)};
+    }
+    if (nearest) return {floor_div_clamped(num, den, rden, -2, (int64_t)n + 1), 0};
+    const int64_t p = floor_div_clamped(num, den, rden, -2 * 2048, ((int64_t)n + 1) * 2048);
+    return {p >> 11, (int)(p & 2047)};
+}
+MI_BLUR_HD inline double persp_rden(int64_t D) { return 1.0 / (double)(2 * D); }
+// The clamped coordinates of a position (W, H > 0), in the form warp_sample() and warp_tap() take.
+MI_BLUR_HD inline WarpCoord persp_coord_at(const PerspPos &s, int mode, int W, int H)
+{
+    const double rden = persp_rden(s.d);
+    const PerspAxis ax = persp_axis(s.nx, s.d, rden, mode, W), ay = persp_axis(s.ny, s.d, rden, mode, H);
+    return {(int)ax.i0, (int)ay.i0, ax.f, ay.f};
+}
+MI_BLUR_HD inline WarpCoord persp_coord(const int64_t *h, int mode, int W, int H, int X, int Y)
+{
+    return persp_coord_at(persp_position(h, X, Y), mode, W, H);
+}
+// The input pixels the taps of output pixels [X0, X1] x [Y0, Y1] (inclusive) can touch, as warp_footprint(): the box of
+// the four corners' taps with the + 1 tap.  Why the corners still do for a projective map: along any straight segment
+// of output pixels on which D > 0 (every segment inside a valid output: D is linear and >= 1 at its corners),
+// N / D = (a + b t) / (c + d t) has the derivative (b c - a d) / (c + d t)^2, of one sign, so it is monotone; p is a
+// floor of 2048 N / D + 1/2 and the clamp and the shift are monotone too.  A pixel of the rectangle lies on a horizontal
+// segment between two pixels of its left and right edges, and those on vertical segments between corners: its x0 is
+// between the x0 of two edge pixels, each between those of two corners.  Likewise y0.
+MI_BLUR_HD inline WarpBox persp_footprint(const int64_t *h, int mode, int border, int W, int H, int X0, int X1, int Y0, int Y1)
+{
+    const WarpCoord c0 = persp_coord(h, mode, W, H, X0, Y0), c1 = persp_coord(h, mode, W, H, X1, Y0);
+    const WarpCoord c2 = persp_coord(h, mode, W, H, X0, Y1), c3 = persp_coord(h, mode, W, H, X1, Y1);
+    const int x_lo = c0.x0 < c1.x0 ? c0.x0 : c1.x0, x_lo2 = c2.x0 < c3.x0 ? c2.x0 : c3.x0;
+    const int x_hi = c0.x0 > c1.x0 ? c0.x0 : c1.x0, x_hi2 = c2.x0 > c3.x0 ? c2.x0 : c3.x0;
+    const int y_lo = c0.y0 < c1.y0 ? c0.y0 : c1.y0, y_lo2 = c2.y0 < c3.y0 ? c2.y0 : c3.y0;
+    const int y_hi = c0.y0 > c1.y0 ? c0.y0 : c1.y0, y_hi2 = c2.y0 > c3.y0 ? c2.y0 : c3.y0;
+    WarpBox b;
+    b.x0 = x_lo < x_lo2 ? x_lo : x_lo2; b.x1 = (x_hi > x_hi2 ? x_hi : x_hi2) + 1;
+    b.y0 = y_lo < y_lo2 ? y_lo : y_lo2; b.y1 = (y_hi > y_hi2 ? y_hi : y_hi2) + 1;
+    if (border == MI_BLUR_WARP_CONSTANT) {
+        b.x0 = b.x0 < 0 ? 0 : b.x0; b.x1 = b.x1 > W - 1 ? W - 1 : b.x1;
+        b.y0 = b.y0 < 0 ? 0 : b.y0; b.y1 = b.y1 > H - 1 ? H - 1 : b.y1;
+    } else {
+        b.x0 = b.x0 < 0 ? 0 : b.x0 > W - 1 ? W - 1 : b.x0; b.x1 = b.x1 < 0 ? 0 : b.x1 > W - 1 ? W - 1 : b.x1;
+        b.y0 = b.y0 < 0 ? 0 : b.y0 > H - 1 ? H - 1 : b.y0; b.y1 = b.y1 < 0 ? 0 : b.y1 > H - 1 ? H - 1 : b.y1;
+    }
+    return b;
+}
+// A homography that is valid for an output of out_w x out_h (1..MI_BLUR_RESIZE_MAX_DIM each): a known border, fill
+// 0..255, the six coefficients of X and Y within 2^32, the three constants within 2^48, and D >= 1 at the four corner
+// pixels of the output, so (D is linear) at every output pixel: no horizon crosses the output.
+inline bool persp_map_ok(int border, int fill, const int64_t *h, int out_w, int out_h)
+{
+    if ((border != MI_BLUR_WARP_CLAMP && border != MI_BLUR_WARP_CONSTANT) || fill < 0 || fill > 255) return false;
+    const int64_t lin = (int64_t)1 << 32, off = (int64_t)1 << 48;
+    for (int i = 0; i < 9; i++) {
+        const int64_t lim = i % 3 == 2 ? off : lin;
+        if (h[i] > lim || h[i] < -lim) return false;
+    }
+    const int xs[2] = {0, out_w - 1}, ys[2] = {0, out_h - 1};
+    for (int j = 0; j < 2; j++)
+        for (int i = 0; i < 2; i++)
+            if (persp_position(h, xs[i], ys[j]).d < 1) return false;
+    return true;
+}
+inline bool persp_ok(const mi_blur_warp_perspective *w, int W, int H, int C)
+{
+    return w && resize_ok(w->out_width, w->out_height, w->mode, W, H, C) && persp_map_ok(w->border, w->fill, w->h, w->out_width, w->out_height);
+}
+
 // Output size of a decimation of a W x H image: kept columns / rows (> 0 for a valid decimation, down_ok()).
 inline int down_cols(int W, int sx, int ox) { return (W - ox + sx - 1) / sx; }
 inline int down_rows(int H, int sy, int oy) { return (H - oy + sy - 1) / sy; }
@@ -204,14 +317,17 @@ inline bool down_ok(const mi_blur_decimation *d, int W, int H)
 // The output geometry of a filter, for everything above the kernels (launch checks, slot sizes, counters, the CPU device).
 // whole_image_only: the output image is not the input's size, so the filter takes whole images only: no bands, no halo
 // rows, no planar or resident forms (a band's phase or source rows would depend on where it starts).
-inline bool whole_image_only(const Filter &f) { return f.kind == FilterKind::SEP_DOWN || f.kind == FilterKind::RESIZE || f.kind == FilterKind::WARP; }
+inline bool whole_image_only(const Filter &f)
+{
+    return f.kind == FilterKind::SEP_DOWN || f.kind == FilterKind::RESIZE || f.kind == FilterKind::WARP || f.kind == FilterKind::WARP_PERSP;
+}
 // Width and rows of the output block of one band of band_rows rows x W of which rows [y0, y1) are asked for: those rows
 // at the input's width, or the filter's own output image (of the whole band) for a whole_image_only filter.
 struct OutShape { int width, rows; };
 inline OutShape out_shape(const Filter &f, int W, int band_rows, int y0, int y1)
 {
     if (f.kind == FilterKind::SEP_DOWN) return {down_cols(W, f.down_sx, f.down_ox), down_rows(band_rows, f.down_sy, f.down_oy)};
-    if (f.kind == FilterKind::RESIZE || f.kind == FilterKind::WARP) return {f.out_w, f.out_h};
+    if (f.kind == FilterKind::RESIZE || f.kind == FilterKind::WARP || f.kind == FilterKind::WARP_PERSP) return {f.out_w, f.out_h};
     return {W, y1 - y0};
 }
 
@@ -266,6 +382,16 @@ inline int filter_warp(const mi_blur_warp *w, Filter *f)
     *f = Filter{FilterKind::WARP, 0, {}};
     f->out_w = w->out_width; f->out_h = w->out_height; f->sample_mode = w->mode; f->warp_border = w->border; f->warp_fill = w->fill;
     for (int i = 0; i < 6; i++) f->warp_m[i] = w->m[i];
+    return MI_BLUR_OK;
+}
+
+// The target size, mode, border and homography of *w (the image size is checked where it is known: persp_ok()).
+inline int filter_warp_persp(const mi_blur_warp_perspective *w, Filter *f)
+{
+    if (!f || !persp_ok(w, 1, 1, 1)) return MI_BLUR_ERR_INVALID;
+    *f = Filter{FilterKind::WARP_PERSP, 0, {}};
+    f->out_w = w->out_width; f->out_h = w->out_height; f->sample_mode = w->mode; f->warp_border = w->border; f->warp_fill = w->fill;
+    for (int i = 0; i < 9; i++) f->warp_h[i] = w->h[i];
     return MI_BLUR_OK;
 }
 
@@ -443,6 +569,27 @@ inline long long warp_tiles_max_bytes(const TileGrid &g, const int64_t *m, int b
         for (int s = 0; s < g.nstrips; s++) {
             const Tile tl = tile_at(g, Ho, s, ty);
             const WarpBox b = warp_tile_box(m, border, W, H, C, tl.ty0, tl.rows_out, tl.x0c, tl.nc);
+            if (warp_box_empty(b)) continue;
+            const long long bytes = (long long)(b.y1 - b.y0 + 1) * chunk_span(b.x0, b.x1, C).n() * 16;
+            max_bytes = bytes > max_bytes ? bytes : max_bytes;
+        }
+    return max_bytes;
+}
+
+// ---- blur_warp_persp_tiled_kernel: the tiles, the LDS layout, warp_tap() and the slack of blur_warp_tiled_kernel; the box
+// of a tile comes from persp_footprint(), so boxes differ from tile to tile and the walk takes the largest.
+MI_BLUR_HD inline WarpBox persp_tile_box(const int64_t *h, int border, int W, int H, int C, int ty0, int rows_out, int x0c, int nc)
+{
+    const Span px = tile_pixels(x0c, nc, C);
+    return persp_footprint(h, MI_BLUR_RESIZE_BILINEAR, border, W, H, px.lo, px.hi, ty0, ty0 + rows_out - 1);
+}
+inline long long persp_tiles_max_bytes(const TileGrid &g, const int64_t *h, int border, int W, int H, int Ho, int C)
+{
+    long long max_bytes = 0;
+    for (int ty = 0; ty < g.ntiles_y && max_bytes <= WARP_LDS_MAX; ty++)
+        for (int s = 0; s < g.nstrips; s++) {
+            const Tile tl = tile_at(g, Ho, s, ty);
+            const WarpBox b = persp_tile_box(h, border, W, H, C, tl.ty0, tl.rows_out, tl.x0c, tl.nc);
             if (warp_box_empty(b)) continue;
             const long long bytes = (long long)(b.y1 - b.y0 + 1) * chunk_span(b.x0, b.x1, C).n() * 16;
             max_bytes = bytes > max_bytes ? bytes : max_bytes;

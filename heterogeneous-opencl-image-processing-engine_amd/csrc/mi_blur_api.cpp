@@ -96,7 +96,7 @@ enum class PreCheck {
     FILTER,     // sep: the constructor's status
     ARGS,       // median, morph, bilateral, conv: + pointers, dimensions, image count
     ARGS_ROWS,  // conv_band: + the row range
-    ARGS_SIZE,  // sep_down, resize, warp: + the image within INT_MAX bytes
+    ARGS_SIZE,  // sep_down, resize, warp, warp_perspective: + the image within INT_MAX bytes
 };
 
 // Every mi_blur_enqueue* export: one launch of f on device memory.  built: the status of f's constructor.
@@ -329,6 +329,110 @@ extern "C" int mi_blur_enqueue_warp(const uint8_t *d_in, uint8_t *d_out, int wid
 {
     Filter f;
     return enqueue_filter(warp_for(w, width, height, channels, &f), f, PreCheck::ARGS_SIZE, d_in, d_out, width, height,
+                          channels, n_images, 0, height, MI_BLUR_VARIANT_AUTO, stream);
+}
+
+// ----------------------------------------------------------------------------------
+// perspective warp: fixed-point homography (no reference analogue)
+// ----------------------------------------------------------------------------------
+static int warp_persp_for(const mi_blur_warp_perspective *w, int W, int H, int C, Filter *f)
+{
+    const int rc = filter_warp_persp(w, f);
+    return rc ? rc : persp_ok(w, W, H, C) ? MI_BLUR_OK : MI_BLUR_ERR_INVALID;
+}
+
+extern "C" int mi_blur_warp_perspective_coord(const mi_blur_warp_perspective *w, int X, int Y, int64_t *x0, int64_t *y0, int *fx, int *fy)
+{
+    if (!w || !x0 || !y0 || !fx || !fy || X < 0 || Y < 0 || X >= MI_BLUR_RESIZE_MAX_DIM || Y >= MI_BLUR_RESIZE_MAX_DIM) return MI_BLUR_ERR_INVALID;
+    if (w->mode != MI_BLUR_RESIZE_NEAREST && w->mode != MI_BLUR_RESIZE_BILINEAR) return MI_BLUR_ERR_INVALID;
+    if (!persp_map_ok(MI_BLUR_WARP_CLAMP, 0, w->h, 1, 1)) return MI_BLUR_ERR_INVALID;     // the limits, and h8 >= 1
+    const PerspPos s = persp_position(w->h, X, Y);
+    if (s.d < 1) return MI_BLUR_ERR_INVALID;
+    const PerspAxis ax = persp_axis(s.nx, s.d, 0.0, w->mode, 0), ay = persp_axis(s.ny, s.d, 0.0, w->mode, 0);
+    *x0 = ax.i0; *y0 = ay.i0; *fx = ax.f; *fy = ay.f;
+    return MI_BLUR_OK;
+}
+
+// The 8 x 8 system of getPerspectiveTransform, by elimination with partial pivoting.
+extern "C" int mi_blur_warp_perspective_quad(const double src[8], const double dst[8], double H[9])
+{
+    if (!src || !dst || !H) return MI_BLUR_ERR_INVALID;
+    double scale = 0.0;
+    for (int i = 0; i < 8; i++) {
+        if (!std::isfinite(src[i]) || !std::isfinite(dst[i])) return MI_BLUR_ERR_INVALID;
+        scale = std::max(scale, std::max(std::fabs(src[i]), std::fabs(dst[i])));
+    }
+    for (const double *p : {src, dst})                  // three collinear points: twice the triangle's area is 0
+        for (int skip = 0; skip < 4; skip++) {
+            const int a = skip == 0 ? 1 : 0, b = skip <= 1 ? 2 : 1, c = skip <= 2 ? 3 : 2;
+            const double cross = (p[2 * b] - p[2 * a]) * (p[2 * c + 1] - p[2 * a + 1]) - (p[2 * b + 1] - p[2 * a + 1]) * (p[2 * c] - p[2 * a]);
+            if (!(std::fabs(cross) > 1e-12 * scale * scale)) return MI_BLUR_ERR_INVALID;
+        }
+    double A[8][9];
+    for (int i = 0; i < 4; i++) {
+        const double x = src[2 * i], y = src[2 * i + 1], u = dst[2 * i], v = dst[2 * i + 1];
+        const double r0[9] = {x, y, 1, 0, 0, 0, -u * x, -u * y, u}, r1[9] = {0, 0, 0, x, y, 1, -v * x, -v * y, v};
+        std::copy(r0, r0 + 9, A[2 * i]);
+        std::copy(r1, r1 + 9, A[2 * i + 1]);
+    }
+    for (int col = 0; col < 8; col++) {
+        int piv = col;
+        for (int r = col + 1; r < 8; r++)
+            if (std::fabs(A[r][col]) > std::fabs(A[piv][col])) piv = r;
+        if (A[piv][col] == 0.0) return MI_BLUR_ERR_INVALID;
+        if (piv != col) std::swap_ranges(A[piv], A[piv] + 9, A[col]);
+        for (int r = 0; r < 8; r++) {
+            if (r == col) continue;
+            const double f = A[r][col] / A[col][col];
+            for (int k = col; k < 9; k++) A[r][k] -= f * A[col][k];
+        }
+    }
+    double out[9];
+    for (int i = 0; i < 8; i++) {
+        out[i] = A[i][8] / A[i][i];
+        if (!std::isfinite(out[i])) return MI_BLUR_ERR_INVALID;
+    }
+    out[8] = 1.0;
+    std::copy(out, out + 9, H);
+    return MI_BLUR_OK;
+}
+
+extern "C" int mi_blur_warp_perspective_set_matrix(mi_blur_warp_perspective *w, const double H[9], int inverse)
+{
+    if (!w || !H) return MI_BLUR_ERR_INVALID;
+    double v[9];
+    for (int i = 0; i < 9; i++) { if (!std::isfinite(H[i])) return MI_BLUR_ERR_INVALID; v[i] = H[i]; }
+    if (!inverse) {                                     // the adjugate; the determinant only scales it, and the division by v[8] below takes any scale out
+        const double det = H[0] * (H[4] * H[8] - H[5] * H[7]) - H[1] * (H[3] * H[8] - H[5] * H[6]) + H[2] * (H[3] * H[7] - H[4] * H[6]);
+        if (det == 0.0 || !std::isfinite(det)) return MI_BLUR_ERR_INVALID;
+        v[0] = H[4] * H[8] - H[5] * H[7]; v[1] = H[2] * H[7] - H[1] * H[8]; v[2] = H[1] * H[5] - H[2] * H[4];
+        v[3] = H[5] * H[6] - H[3] * H[8]; v[4] = H[0] * H[8] - H[2] * H[6]; v[5] = H[2] * H[3] - H[0] * H[5];
+        v[6] = H[3] * H[7] - H[4] * H[6]; v[7] = H[1] * H[6] - H[0] * H[7]; v[8] = H[0] * H[4] - H[1] * H[3];
+    }
+    const double v8 = v[8];
+    if (v8 == 0.0 || !std::isfinite(v8)) return MI_BLUR_ERR_INVALID;
+    for (int i = 0; i < 9; i++) { v[i] /= v8; if (!std::isfinite(v[i])) return MI_BLUR_ERR_INVALID; }
+    int k = 30;
+    for (; k >= 0; k--) {
+        bool fits = true;
+        for (int i = 0; i < 9; i++) fits = fits && std::fabs(v[i]) * std::ldexp(1.0, k) <= (i % 3 == 2 ? 281474976710655.0 : 4294967295.0);   // 2^48 - 1, 2^32 - 1
+        if (fits) break;
+    }
+    if (k < 0) return MI_BLUR_ERR_INVALID;
+    mi_blur_warp_perspective q = *w;
+    for (int i = 0; i < 9; i++) q.h[i] = (int64_t)std::floor(std::ldexp(v[i], k) + 0.5);
+    if (q.out_width < 1 || q.out_height < 1 || q.out_width > MI_BLUR_RESIZE_MAX_DIM || q.out_height > MI_BLUR_RESIZE_MAX_DIM ||
+        !persp_map_ok(MI_BLUR_WARP_CLAMP, 0, q.h, q.out_width, q.out_height))
+        return MI_BLUR_ERR_INVALID;
+    for (int i = 0; i < 9; i++) w->h[i] = q.h[i];
+    return MI_BLUR_OK;
+}
+
+extern "C" int mi_blur_enqueue_warp_perspective(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int n_images,
+                                                const mi_blur_warp_perspective *w, void *stream)
+{
+    Filter f;
+    return enqueue_filter(warp_persp_for(w, width, height, channels, &f), f, PreCheck::ARGS_SIZE, d_in, d_out, width, height,
                           channels, n_images, 0, height, MI_BLUR_VARIANT_AUTO, stream);
 }
 
@@ -1414,7 +1518,7 @@ extern "C" int mi_blur_submit_planar(mi_blur_ctx *c, const uint8_t *host_planar_
 
 // Every mi_blur_ctx_set_*: the filter that build(&f) makes in place of the context's, for every submit from now on (before the
 // first one only; the whole_image_only ones for mi_blur_submit only).  null_arg: a required pointer argument is null,
-// which set_kernel, set_sep_down, set_resize and set_warp answer before they look at the state; the other setters leave a null
+// which set_kernel, set_sep_down, set_resize, set_warp and set_warp_perspective answer before they look at the state; the other setters leave a null
 // table to the constructor, behind the state.
 template <typename B>
 static int ctx_set_filter(mi_blur_ctx *c, bool null_arg, B &&build)
@@ -1445,6 +1549,11 @@ extern "C" int mi_blur_ctx_set_resize(mi_blur_ctx *c, const mi_blur_resize *r)
 extern "C" int mi_blur_ctx_set_warp(mi_blur_ctx *c, const mi_blur_warp *w)
 {
     return ctx_set_filter(c, !w, [&](Filter *f) { return warp_for(w, c->W, c->H, c->C, f); });
+}
+
+extern "C" int mi_blur_ctx_set_warp_perspective(mi_blur_ctx *c, const mi_blur_warp_perspective *w)
+{
+    return ctx_set_filter(c, !w, [&](Filter *f) { return warp_persp_for(w, c->W, c->H, c->C, f); });
 }
 
 extern "C" int mi_blur_ctx_set_median(mi_blur_ctx *c, int radius)
@@ -1914,6 +2023,13 @@ extern "C" int mi_blur_cpu_run_warp(const uint8_t *in, uint8_t *out, int width, 
 {
     Filter f;
     return cpu_run_filter(warp_for(w, width, height, channels, &f), f, in, out, width, height, channels, n_images, n_threads);
+}
+
+extern "C" int mi_blur_cpu_run_warp_perspective(const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,
+                                                const mi_blur_warp_perspective *w, int n_threads)
+{
+    Filter f;
+    return cpu_run_filter(warp_persp_for(w, width, height, channels, &f), f, in, out, width, height, channels, n_images, n_threads);
 }
 
 extern "C" int mi_blur_cpu_run_median(const uint8_t *in, uint8_t *out, int width, int height, int channels, int radius,

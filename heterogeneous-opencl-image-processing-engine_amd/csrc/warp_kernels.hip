@@ -24,6 +24,8 @@
 //   tiles of one image with the kernel's own warp_tile_box), so no bound on the footprint is assumed.  4 instantiations, no scratch.
 //
 // Generic kernel (blur_warp_generic_kernel): one output byte per thread, any shape, map, mode, border and alignment.
+//
+// The perspective warp (mi_blur_enqueue_warp_perspective) has the same two kernels on its own position source: at the end of this file.
 #include "kernel_common.h"
 
 #include <algorithm>    // std::equal, std::copy
@@ -230,6 +232,186 @@ int launch_warp(const LaunchDesc &d)
         if (max_bytes <= WARP_LDS_MAX) return launch_warp_tiled(d, g, max_bytes);
     }
     return launch_warp_generic(d);
+}
+
+// ----------------------------------------------------------------------------------
+// The perspective warp (mi_blur_enqueue_warp_perspective): the two kernels above with the second map source of filter.h,
+// persp_position() / persp_axis().  blur_warp_persp_tiled_kernel<C> keeps the tiles, the staging, the tap reads, the
+// blend and the stores of blur_warp_tiled_kernel; a work item computes Nx, Ny, D once in 64 bits, adds h[0], h[3], h[6]
+// per pixel, and divides twice per pixel: one double reciprocal of 2 D, two double products, and the exact 64-bit
+// remainder that corrects each estimate (floor_div_clamped(), filter.h), so no 64-bit integer division is expanded.
+// The box of a tile is persp_tile_box(): boxes differ from tile to tile, the host's walk (persp_tiles_max_bytes()) sizes
+// the LDS for the largest.  No scratch.
+// ----------------------------------------------------------------------------------
+namespace {
+
+struct WarpPerspTiledParams {
+    const uint8_t *in;
+    uint8_t *out;
+    long long in_stride, out_stride;  // bytes per input image / output image
+    long long h[9];
+    int W, H, Wo, Ho;
+    int pitch, opitch;                // bytes per input row / output row
+    int cpr;                          // OUTPUT 16-byte chunks per row
+    int ncols, nstrips, ntiles_y;
+    unsigned nblocks;
+    int xcd;
+    int border;
+    unsigned fill;                    // the fill byte in all four bytes
+};
+
+template <int C>
+__global__ __launch_bounds__(TILE_THREADS) void blur_warp_persp_tiled_kernel(const WarpPerspTiledParams p)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    constexpr int U = warp_unit(C), NPIX = C == 1 || C == 3 ? 8 : 16 / C, NITEM = U * 16 / (NPIX * C);   // as blur_warp_tiled_kernel
+    const int t = threadIdx.x;
+    const TileCoords tc = tile_coords<0>(p.xcd, p.nblocks, p.nstrips, p.ntiles_y, p.ncols, p.cpr, 0, p.Ho, 0);
+    const int ty0 = tc.ty0, rows_out = tc.rows_out, x0c = tc.x0c, nc = tc.nc;
+    const int64_t h[9] = {p.h[0], p.h[1], p.h[2], p.h[3], p.h[4], p.h[5], p.h[6], p.h[7], p.h[8]};
+
+    const int px0 = tile_pixels(x0c, nc, C).lo;
+    const WarpBox b = persp_tile_box(h, p.border, p.W, p.H, C, ty0, rows_out, x0c, nc);
+    const int nu = nc / U * NITEM, nitems = rows_out * nu;
+    uint8_t *out_img = p.out + (long long)tc.img * p.out_stride;
+
+    if (warp_box_empty(b)) {                            // CONSTANT, every tap outside the image
+        u32x4 v;
+        v.x = v.y = v.z = v.w = p.fill;
+        for (int i = t; i < rows_out * nc; i += TILE_THREADS) {
+            const int row = i / nc, cc = i - row * nc;
+            *reinterpret_cast<u32x4 *>(out_img + ((unsigned)(ty0 + row) * (unsigned)p.opitch + (unsigned)(x0c + cc) * 16u)) = v;
+        }
+        return;
+    }
+    const Span sc = chunk_span(b.x0, b.x1, C);
+    stage_box(lds, p.in + (long long)tc.img * p.in_stride + ((unsigned)b.y0 * (unsigned)p.pitch + (unsigned)sc.lo * 16u), p.pitch, b.y1 - b.y0 + 1, sc.n(), t);
+    __syncthreads();
+
+    const bool constant = p.border == MI_BLUR_WARP_CONSTANT;
+    const uint32_t fillp = p.fill;
+    for (int i = t; i < nitems; i += TILE_THREADS) {
+        const int row = i / nu, u = i - row * nu;
+        const int Y = ty0 + row, X = px0 + u * NPIX;
+        PerspPos s = persp_position(h, X, Y);           // every pixel of the item lies in the output: s.d >= 1 throughout
+        uint32_t o[NPIX * C / 4];
+#pragma unroll
+        for (int q = 0; q < NPIX * C / 4; q++) o[q] = 0;
+#pragma unroll
+        for (int k = 0; k < NPIX; k++) {
+            const WarpCoord wc = persp_coord_at(s, MI_BLUR_RESIZE_BILINEAR, p.W, p.H);
+            const WarpTap wt = warp_tap(b, sc, C, wc.x0, wc.y0);
+            uint32_t ta, tb, tc2, td;
+            warp_taps<C>(lds, wt.off_a, ta, tb);
+            warp_taps<C>(lds, wt.off_b, tc2, td);
+            if (wt.one) { tb = ta; td = tc2; }
+            if (constant) {
+                const bool ixa = (unsigned)wc.x0 < (unsigned)p.W, ixb = (unsigned)(wc.x0 + 1) < (unsigned)p.W;
+                const bool iya = (unsigned)wc.y0 < (unsigned)p.H, iyb = (unsigned)(wc.y0 + 1) < (unsigned)p.H;
+                ta = ixa && iya ? ta : fillp; tb = ixb && iya ? tb : fillp;
+                tc2 = ixa && iyb ? tc2 : fillp; td = ixb && iyb ? td : fillp;
+            }
+            const uint32_t fx = (uint32_t)wc.fx, fy = (uint32_t)wc.fy;
+#pragma unroll
+            for (int c = 0; c < C; c++) {
+                const uint32_t top = lerp24((ta >> (8 * c)) & 0xffu, (tb >> (8 * c)) & 0xffu, fx);
+                const uint32_t bot = lerp24((tc2 >> (8 * c)) & 0xffu, (td >> (8 * c)) & 0xffu, fx);
+                const uint32_t v = lerp24_round(top, bot, fy);
+                const int e = k * C + c;
+                o[e >> 2] |= v << (8 * (e & 3));
+            }
+            s.nx += h[0]; s.ny += h[3]; s.d += h[6];
+        }
+        uint8_t *dst = out_img + ((unsigned)Y * (unsigned)p.opitch + (unsigned)x0c * 16u + (unsigned)u * (unsigned)(NPIX * C));
+        if constexpr (C == 3) {
+            const bool second = u & 1;                  // 24 bytes as 16 + 8 or 8 + 16, as blur_warp_tiled_kernel
+            u32x4 v;
+            u32x2 hh;
+            v.x = second ? o[2] : o[0]; v.y = second ? o[3] : o[1]; v.z = second ? o[4] : o[2]; v.w = second ? o[5] : o[3];
+            hh.x = second ? o[0] : o[4]; hh.y = second ? o[1] : o[5];
+            *reinterpret_cast<u32x4 *>(dst + (second ? 8 : 0)) = v;
+            *reinterpret_cast<u32x2 *>(dst + (second ? 0 : 16)) = hh;
+        } else if constexpr (C == 1) {
+            u32x2 hh;
+            hh.x = o[0]; hh.y = o[1];
+            *reinterpret_cast<u32x2 *>(dst) = hh;
+        } else {
+            u32x4 v;
+            v.x = o[0]; v.y = o[1]; v.z = o[2]; v.w = o[3];
+            *reinterpret_cast<u32x4 *>(dst) = v;
+        }
+    }
+}
+
+struct WarpPerspGenericParams {
+    const uint8_t *in;
+    uint8_t *out;
+    long long in_stride, out_stride, block, total;   // block = output bytes per image (Ho * opitch)
+    long long h[9];
+    int W, H, channels, pitch, opitch, mode, border;
+    unsigned fill;
+};
+
+__global__ __launch_bounds__(256) void blur_warp_persp_generic_kernel(const WarpPerspGenericParams p)
+{
+    const int64_t h[9] = {p.h[0], p.h[1], p.h[2], p.h[3], p.h[4], p.h[5], p.h[6], p.h[7], p.h[8]};
+    const long long step = (long long)gridDim.x * blockDim.x;
+    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < p.total; idx += step) {
+        const BytePos q = byte_pos(idx, p.block, p.opitch, p.channels, 0, p.in, p.in_stride);   // q.y, q.x: the OUTPUT pixel
+        const WarpCoord wc = persp_coord(h, p.mode, p.W, p.H, q.x, q.y);
+        p.out[q.img * p.out_stride + q.rem] = (uint8_t)warp_sample(q.src + q.c, (size_t)p.pitch, p.channels, p.W, p.H, p.border, p.fill, wc);
+    }
+}
+
+// warp_tiles() for the perspective warp: the key holds the nine entries.
+long long warp_persp_tiles(const LaunchDesc &d, const TileGrid &g)
+{
+    const Filter &f = *d.filter;
+    const int64_t *h = f.warp_h, key[15] = {d.width, d.band_rows, d.channels, f.out_w, f.out_h, f.warp_border, h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], h[8]};
+    thread_local int64_t last_key[15];
+    thread_local long long last = -1;
+    if (last >= 0 && std::equal(key, key + 15, last_key)) return last;
+    std::copy(key, key + 15, last_key);
+    return last = persp_tiles_max_bytes(g, f.warp_h, f.warp_border, d.width, d.band_rows, f.out_h, d.channels);
+}
+
+int launch_warp_persp_tiled(const LaunchDesc &d, const TileGrid &g, long long max_bytes)
+{
+    const Filter &f = *d.filter;
+    WarpPerspTiledParams p{};
+    dim3 grid;
+    if (const int st = fill_tiles(p, d, &grid, g)) return st;
+    set_last_kernel("blur_warp_persp_tiled_kernel");
+    std::copy(f.warp_h, f.warp_h + 9, p.h);
+    p.W = d.width; p.Wo = f.out_w; p.Ho = f.out_h; p.border = f.warp_border; p.fill = (unsigned)f.warp_fill * 0x01010101u;
+    return dispatch<1, 2, 3, 4>(d.channels, [&](auto CC) { return do_launch(blur_warp_persp_tiled_kernel<CC>, grid, dim3(TILE_THREADS), (size_t)(max_bytes + WARP_LDS_SLACK), d, p); });
+}
+
+int launch_warp_persp_generic(const LaunchDesc &d)
+{
+    const Filter &f = *d.filter;
+    set_last_kernel("blur_warp_persp_generic_kernel");
+    WarpPerspGenericParams p{};
+    const dim3 grid = fill_generic(p, d);
+    std::copy(f.warp_h, f.warp_h + 9, p.h);
+    p.W = d.width; p.mode = f.sample_mode; p.border = f.warp_border; p.fill = (unsigned)f.warp_fill;
+    return do_launch(blur_warp_persp_generic_kernel, grid, dim3(256), 0, d, p);
+}
+
+}  // namespace
+
+int launch_warp_persp(const LaunchDesc &d)
+{
+    const int st = launch_checks(d, FilterKind::WARP_PERSP, [&](const Filter &f) {
+        return resize_ok(f.out_w, f.out_h, f.sample_mode, d.width, d.band_rows, d.channels) && persp_map_ok(f.warp_border, f.warp_fill, f.warp_h, f.out_w, f.out_h);
+    });
+    if (st != LAUNCH_GO) return st;
+    if (warp_tile_aligned(d)) {
+        const TileGrid g = warp_grid(out_pitch(d) / 16, d.filter->out_h, d.channels);
+        const long long max_bytes = warp_persp_tiles(d, g);
+        if (max_bytes <= WARP_LDS_MAX) return launch_warp_persp_tiled(d, g, max_bytes);
+    }
+    return launch_warp_persp_generic(d);
 }
 
 }  // namespace mi_blur

@@ -69,8 +69,8 @@ int mi_blur_version(void);
  * "blur_sep_generic_kernel", "blur_median_fast_kernel", "blur_median_generic_kernel", "blur_morph_tiled_kernel",
  * "blur_morph_generic_kernel", "blur_bilateral_tiled_kernel", "blur_bilateral_generic_kernel", "blur_conv_tiled_kernel",
  * "blur_conv_generic_kernel", "blur_sep_down_tiled_kernel", "blur_sep_down_generic_kernel",
- * "blur_resize_tiled_kernel", "blur_resize_generic_kernel", "blur_warp_tiled_kernel", "blur_warp_generic_kernel";
- * "" before the first):
+ * "blur_resize_tiled_kernel", "blur_resize_generic_kernel", "blur_warp_tiled_kernel", "blur_warp_generic_kernel",
+ * "blur_warp_persp_tiled_kernel", "blur_warp_persp_generic_kernel"; "" before the first):
  * reports name the kernel a profiler will show.  Static string, never NULL. */
 const char *mi_blur_last_kernel(void);
 
@@ -609,6 +609,83 @@ int mi_blur_cpu_run_warp(const uint8_t *in, uint8_t *out, int width, int height,
  * launch per submit, never the batch server), on the GPU or the CPU device.  mi_blur_submit_band, _bands, _planar and
  * both resident runs return MI_BLUR_ERR_UNSUPPORTED for such a context. */
 int mi_blur_ctx_set_warp(mi_blur_ctx *ctx, const mi_blur_warp *w);
+
+/* ------------------------------------------------------------------------
+ * Perspective warp: exact fixed-point homography, any output size (no reference analogue; OpenCV's warpPerspective is
+ * the model).  Exact integers again: the GPU, the CPU device and a numpy restatement agree byte for byte.
+ *
+ * h[9] is the OUTPUT -> INPUT homography, row-major 3 x 3, int64.  The scale is free: h and c*h (c > 0) are the same
+ * map.  For output pixel (X, Y), all in int64:
+ *   Nx = h0*X + h1*Y + h2      Ny = h3*X + h4*Y + h5      D = h6*X + h7*Y + h8
+ *   BILINEAR:  px = floor((Nx*4096 + D) / (2*D))     (= the position Nx/D rounded to 11 fraction bits)
+ *              x0 = px >> 11,  fx = px & 2047        (py, y0, fy from Ny likewise)
+ *   NEAREST:   xi = floor((2*Nx + D) / (2*D)),  yi likewise
+ * Everything else is the affine warp's: the four taps, the blend expression and its one rounding, the CLAMP / CONSTANT
+ * border with `fill`, the clamp of px into [-2*2048, (W+1)*2048] (py likewise with H), applied after the division and
+ * before the split, channels never mix, dense output.
+ *
+ * Valid: the sizes, mode, border, fill and byte limits of the affine warp; |h0|,|h1|,|h3|,|h4|,|h6|,|h7| <= 2^32 and
+ * |h2|,|h5|,|h8| <= 2^48; D >= 1 at the four corner pixels of the output.  D is linear, so it is then >= 1 at every
+ * output pixel; in particular h8 >= 1.  With X, Y < 2^15 this gives |N|, D < 2^49, |N*4096 + 2048*D| < 2^62, 2D < 2^50:
+ * signed 64 bits hold every intermediate; a quotient can reach 2^61 before the clamp.  An output whose horizon
+ * (D <= 0) crosses it is MI_BLUR_ERR_INVALID, never garbage.
+ *
+ * Properties (checked in tests/test_warp_perspective_host.py):
+ *   h = {s*m0..s*m5, 0, 0, s*65536} gives the bytes of mi_blur_enqueue_warp with the Q16 matrix m, in both modes and
+ *   both borders, for any s >= 1 that keeps the limits;
+ *   over any rectangle of output pixels the smallest and largest x0 and y0 occur at its four corners (a
+ *   linear-fractional function is monotone along every segment where D > 0, and floor is monotone): the tiled kernel
+ *   stages the box of a tile's corners;
+ *   the result differs from real-valued bilinear interpolation at the exact rational position by less than
+ *   0.5 + 255 * 2^-11, the affine warp's bound, for the same reason;
+ *   it is NOT OpenCV's INTER_LINEAR bit for bit (5-bit positions there).
+ * ---------------------------------------------------------------------- */
+typedef struct mi_blur_warp_perspective {
+    int out_width, out_height;                /* 1 .. MI_BLUR_RESIZE_MAX_DIM each */
+    int mode;                                 /* MI_BLUR_RESIZE_NEAREST | MI_BLUR_RESIZE_BILINEAR */
+    int border;                               /* mi_blur_warp_border */
+    int fill;                                 /* 0..255, every channel; CONSTANT only */
+    int64_t h[9];                             /* OUTPUT -> INPUT homography, row-major 3 x 3, free scale */
+} mi_blur_warp_perspective;
+
+/* The UNCLAMPED tap origin (x0, y0; 64 bits: they can reach 2^50) and the fractions (fx, fy) of output pixel (X, Y),
+ * through the function the kernels and the CPU device use; NEAREST gives xi, yi, 0, 0.  Only mode and h of *w are read.
+ * MI_BLUR_ERR_INVALID: a null pointer, an unknown mode, h outside its limits, X or Y outside
+ * 0..MI_BLUR_RESIZE_MAX_DIM-1, D < 1 at (X, Y). */
+int mi_blur_warp_perspective_coord(const mi_blur_warp_perspective *w, int X, int Y, int64_t *x0, int64_t *y0, int *fx, int *fy);
+/* The FORWARD (input -> output) matrix H, H[8] = 1, that takes the four points src (x0,y0, .. x3,y3) to the four points
+ * dst: OpenCV's getPerspectiveTransform.  MI_BLUR_ERR_INVALID: a null pointer, a value not finite, three collinear
+ * points on either side (no such matrix, or none with H[8] = 1). */
+int mi_blur_warp_perspective_quad(const double src[8], const double dst[8], double H[9]);
+/* Sets w->h from a real 3 x 3 matrix, for w's output size.  inverse == 0: H maps input to output (what
+ * getPerspectiveTransform gives) and is inverted in double by the adjugate; inverse != 0: H already maps output to
+ * input.  Then v = H / H[8]; k = the largest integer in 0..30 with |v_i| * 2^k <= limit_i - 1 for all nine entries
+ * (limit 2^32 or 2^48 as above); h_i = floor(v_i * 2^k + 0.5); then the validity check above.  30 fraction bits matter: a
+ * perspective term of 5e-4 per pixel is 33 in Q16 (0.7 % off) and 536871 at k = 30.  MI_BLUR_ERR_INVALID (w->h
+ * untouched): a null pointer, an entry not finite, a determinant that is 0 or not finite (inverse == 0), H[8] zero or
+ * not finite after the inversion, no such k, out_width or out_height outside 1..MI_BLUR_RESIZE_MAX_DIM, D < 1 at a
+ * corner pixel of the output (a horizon crosses it). */
+int mi_blur_warp_perspective_set_matrix(mi_blur_warp_perspective *w, const double H[9], int inverse);
+
+/* As mi_blur_enqueue_warp, argument for argument and status for status (MI_BLUR_ERR_INVALID before
+ * MI_BLUR_ERR_NO_DEVICE).  blur_warp_persp_tiled_kernel has the tiles, the staging and the stores of
+ * blur_warp_tiled_kernel; a work item computes Nx, Ny, D once, adds h0, h3, h6 per pixel and divides twice per pixel,
+ * exactly (a double-precision estimate corrected by the exact 64-bit remainder).  It takes the launches the affine
+ * tiled kernel's rule admits (BILINEAR, 1-4 channels, both rows whole 16-byte chunks, aligned pointers and strides)
+ * whose largest tile footprint, found by walking the tiles of one image, is at most 65520 bytes; footprints differ
+ * from tile to tile under a projective map.  Every other launch goes to blur_warp_persp_generic_kernel (one output byte
+ * per thread) as a whole.  mi_blur_last_kernel() says which ran. */
+int mi_blur_enqueue_warp_perspective(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int n_images,
+                                     const mi_blur_warp_perspective *w, void *stream);
+/* The same on the CPU device's threads (synchronous). */
+int mi_blur_cpu_run_warp_perspective(const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,
+                                     const mi_blur_warp_perspective *w, int n_threads);
+/* Give a context the perspective warp, with the rules of mi_blur_ctx_set_warp: only before the first submit
+ * (MI_BLUR_ERR_STATE after); it replaces what another setter set and is replaced by them; the context keeps a copy.
+ * mi_blur_submit writes n_images * Wo*Ho*C bytes (pageable, or pinned in place: one launch per submit, never the batch
+ * server); bytes_alg counts input + output bytes; mi_blur_submit_band, _bands, _planar and both resident runs return
+ * MI_BLUR_ERR_UNSUPPORTED. */
+int mi_blur_ctx_set_warp_perspective(mi_blur_ctx *ctx, const mi_blur_warp_perspective *w);
 
 /* ------------------------------------------------------------------------
  * Median blur, windows 3x3 to 15x15 (no reference analogue).  For a radius r in 1..MI_BLUR_MEDIAN_MAX_RADIUS, with
