@@ -61,7 +61,7 @@ def _newer(target: str, sources: list[str]) -> bool:
 
 def build_native(force: bool = False, verbose: bool = False) -> str:
     """Compile libmi_blur.so (hipcc, --offload-arch=gfx950) and the C++ hosts, in-tree."""
-    srcs = [os.path.join(CSRC, f) for f in ("blur_kernels.hip", "sep_kernels.hip", "median_kernels.hip", "morph_kernels.hip", "bilateral_kernels.hip", "conv_kernels.hip", "sep_down_kernels.hip", "resize_kernels.hip", "warp_kernels.hip", "layout_kernels.hip", "mi_blur_api.cpp", "comm_api.cpp", "cpu_device.cpp")]
+    srcs = [os.path.join(CSRC, f) for f in ("blur_kernels.hip", "sep_kernels.hip", "median_kernels.hip", "morph_kernels.hip", "bilateral_kernels.hip", "conv_kernels.hip", "sep_down_kernels.hip", "resize_kernels.hip", "warp_kernels.hip", "remap_kernels.hip", "layout_kernels.hip", "mi_blur_api.cpp", "comm_api.cpp", "cpu_device.cpp")]
     deps = srcs + [os.path.join(CSRC, f) for f in ("api_internal.h", "blur_launch.h", "kernel_common.h", "cpu_device.h", "filter.h")] + [HEADER]
     if force or not _newer(LIB_PATH, deps):
         cmd = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra",
@@ -266,6 +266,22 @@ class WarpPerspective(C.Structure):
         return w
 
 
+class Remap(C.Structure):
+    """mi_blur_remap: the output size, the mode, the border and the fill byte (as Warp), and stage_bytes: the largest tile
+    footprint the tiled kernel stages in LDS (0 = 65520).  The map itself is a separate int32 (Ho, Wo, 2) array."""
+    _fields_ = [("out_width", C.c_int), ("out_height", C.c_int), ("mode", C.c_int), ("border", C.c_int), ("fill", C.c_int),
+                ("stage_bytes", C.c_int)]
+
+
+class RemapTiles(C.Structure):
+    """mi_blur_remap_tiles: what mi_blur_remap_plan reports."""
+    _fields_ = [("tiled", C.c_int), ("tiles", C.c_int), ("staged", C.c_int), ("direct", C.c_int), ("empty", C.c_int),
+                ("max_box_bytes", C.c_longlong), ("max_staged_bytes", C.c_longlong)]
+
+    def as_dict(self) -> dict:
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 def _warp_border(border) -> int:
     if isinstance(border, str):
         if border not in WARP_BORDERS:
@@ -391,6 +407,13 @@ def lib() -> C.CDLL:
         "mi_blur_enqueue_warp_perspective": (i, [u8p, u8p, i, i, i, i, C.POINTER(WarpPerspective), vp]),
         "mi_blur_cpu_run_warp_perspective": (i, [u8p, u8p, i, i, i, i, C.POINTER(WarpPerspective), i]),
         "mi_blur_ctx_set_warp_perspective": (i, [vp, C.POINTER(WarpPerspective)]),
+        "mi_blur_remap_coord": (i, [C.POINTER(Remap), i, i, C.c_int32, C.c_int32, C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i)]),
+        "mi_blur_remap_from_float": (i, [vp, vp, C.c_size_t, vp]),
+        "mi_blur_remap_undistort": (i, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), i, i, vp]),
+        "mi_blur_remap_plan": (i, [vp, i, i, i, C.POINTER(Remap), C.POINTER(RemapTiles)]),
+        "mi_blur_enqueue_remap": (i, [u8p, u8p, i, i, i, i, C.POINTER(Remap), vp, vp]),
+        "mi_blur_cpu_run_remap": (i, [u8p, u8p, i, i, i, i, C.POINTER(Remap), vp, i]),
+        "mi_blur_ctx_set_remap": (i, [vp, C.POINTER(Remap), vp]),
         "mi_blur_conv_preset": (i, [i, C.POINTER(Conv)]),
         "mi_blur_enqueue_conv": (i, [u8p, u8p, i, i, i, i, C.POINTER(Conv), vp]),
         "mi_blur_enqueue_conv_band": (i, [u8p, u8p, i, i, i, i, i, C.POINTER(Conv), vp]),
@@ -559,6 +582,16 @@ class Context:
         warp.out_width x warp.out_height."""
         check(lib().mi_blur_ctx_set_warp_perspective(self.h, C.byref(warp)), "mi_blur_ctx_set_warp_perspective")
         self.warp_spec = warp
+
+    def set_remap(self, remap: "Remap", map) -> None:
+        """The remap in place of the blur (before the first submit only): map is an int32 array of shape
+        (remap.out_height, remap.out_width, 2), of which the context keeps its own copy; submit() then writes images of
+        remap.out_width x remap.out_height."""
+        m = _fixed_map(map, "set_remap")
+        if m.shape[:2] != (remap.out_height, remap.out_width):
+            raise ValueError("set_remap: the map is (out_height, out_width, 2)")
+        check(lib().mi_blur_ctx_set_remap(self.h, C.byref(remap), m.ctypes.data), "mi_blur_ctx_set_remap")
+        self.remap_spec = remap
 
     def submit_bands(self, host_in, host_out, n_images: int, host_image_stride: int, band_rows: int,
                      halo_top: int, halo_bottom: int) -> None:
@@ -998,3 +1031,108 @@ def warp_perspective(images, M, dsize=None, mode="bilinear", border="constant", 
     wp = WarpPerspective.from_matrix(M, wo, ho, mode, border, fill, inverse)
     out = _filter_images(a, 1, device, batch, lambda ctx: ctx.set_warp_perspective(wp), (ho, wo))
     return out[0, :, :, 0] if rank == 2 else out[0] if rank == 3 else out
+
+
+REMAP_FRAC = 11
+
+
+def _fixed_map(map, name: str):
+    """map as a contiguous int32 array of shape (Ho, Wo, 2); ValueError otherwise."""
+    import numpy as np
+    m = np.asarray(map)
+    if m.dtype != np.int32 or m.ndim != 3 or m.shape[2] != 2 or m.shape[0] < 1 or m.shape[1] < 1:
+        raise ValueError(f"{name}: a fixed-point map is an int32 array of shape (Ho, Wo, 2)")
+    return np.ascontiguousarray(m)
+
+
+def remap_map(map_x, map_y):
+    """The fixed-point map of two real arrays of one 2-D shape (OpenCV's CV_32FC1 map pair): int32 (Ho, Wo, 2), entry
+    (Y, X) = (q(map_x[Y, X]), q(map_y[Y, X])), q(v) = floor(v * 2048 + 0.5) clamped into +-2^30 (mi_blur_remap_from_float).
+    A value that is not finite is an error."""
+    import numpy as np
+    x, y = np.ascontiguousarray(map_x, dtype=np.float32), np.ascontiguousarray(map_y, dtype=np.float32)
+    if x.ndim != 2 or x.shape != y.shape or x.size == 0:
+        raise ValueError("remap_map: map_x and map_y are two arrays of one shape (Ho, Wo)")
+    out = np.empty(x.shape + (2,), dtype=np.int32)
+    check(lib().mi_blur_remap_from_float(x.ctypes.data, y.ctypes.data, x.size, out.ctypes.data), "mi_blur_remap_from_float")
+    return out
+
+
+def remap_coord(W: int, H: int, px: int, py: int, mode="bilinear") -> tuple[int, int, int, int]:
+    """(x0, y0, fx, fy) of the map entry (px, py) on a W x H image (mi_blur_remap_coord): the clamped tap origin and the
+    weights 0..2047 of the taps x0 + 1 and y0 + 1; nearest gives (xi, yi, 0, 0)."""
+    r = Remap(1, 1, _resize_mode(mode, "remap"), WARP_CLAMP, 0, 0)
+    x0, y0, fx, fy = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    check(lib().mi_blur_remap_coord(C.byref(r), int(W), int(H), int(px), int(py), C.byref(x0), C.byref(y0), C.byref(fx), C.byref(fy)), "mi_blur_remap_coord")
+    return x0.value, y0.value, fx.value, fy.value
+
+
+def remap_plan(map, width: int, height: int, channels: int, mode="bilinear", border="constant", fill: int = 0, stage_bytes: int = 0) -> dict:
+    """What blur_remap_tiled_kernel would do with the tiles of one output image (mi_blur_remap_plan): 'tiled' (eligible by
+    shape), and if so 'tiles', 'staged', 'direct', 'empty', 'max_box_bytes', 'max_staged_bytes'."""
+    m = _fixed_map(map, "remap_plan")
+    r = Remap(m.shape[1], m.shape[0], _resize_mode(mode, "remap"), _warp_border(border), int(fill), int(stage_bytes))
+    t = RemapTiles()
+    check(lib().mi_blur_remap_plan(m.ctypes.data, int(width), int(height), int(channels), C.byref(r), C.byref(t)), "mi_blur_remap_plan")
+    return t.as_dict()
+
+
+def remap(images, map_x, map_y=None, mode="bilinear", border="constant", fill: int = 0, device: int = 0, batch: int = 0, stage_bytes: int = 0):
+    """Remap, numpy in -> numpy out, after OpenCV's remap: output pixel (X, Y) samples the input at (map_x[Y, X],
+    map_y[Y, X]), pixel (x, y) at integer coordinates.  map_x: an int32 (Ho, Wo, 2) array is a fixed-point map (11
+    fraction bits, map_y None); otherwise map_x and map_y are two real (Ho, Wo) arrays, quantised by remap_map().  Exact
+    fixed-point bilinear (one final rounding) or nearest; border 'constant' or 'clamp' (include/mi_blur.h has the
+    definition).  images, device, batch and the result as warp_affine(); the output is (Ho, Wo)."""
+    import numpy as np
+    a = _images(images, "remap")
+    if map_y is None:
+        m = _fixed_map(map_x, "remap")
+    else:
+        m = remap_map(map_x, map_y)
+    rank = a.ndim
+    if rank == 2:
+        a = a[None, :, :, None]
+    elif rank == 3:
+        a = a[None]
+    n, h, w, c = a.shape
+    if h == 0 or w == 0 or c == 0:
+        raise ValueError("remap: images must not be empty")
+    if not 0 <= int(fill) <= 255:
+        raise ValueError("remap: fill is 0..255")
+    ho, wo = m.shape[:2]
+    r = Remap(wo, ho, _resize_mode(mode, "remap"), _warp_border(border), int(fill), int(stage_bytes))
+    out = _filter_images(a, 1, device, batch, lambda ctx: ctx.set_remap(r, m), (ho, wo))
+    return out[0, :, :, 0] if rank == 2 else out[0] if rank == 3 else out
+
+
+def undistort_map(K, dist, size, new_K=None):
+    """The fixed-point undistortion map of a pinhole camera (mi_blur_remap_undistort; OpenCV's initUndistortRectifyMap
+    with R = I): K and new_K are (fx, fy, cx, cy) or a 3 x 3 camera matrix, new_K None = K; dist is up to five of
+    (k1, k2, p1, p2, k3); size = (out_w, out_h).  int32 (out_h, out_w, 2)."""
+    import numpy as np
+
+    def intrinsics(k, name):
+        k = np.asarray(k, dtype=np.float64)
+        if k.shape == (3, 3):
+            k = np.array([k[0, 0], k[1, 1], k[0, 2], k[1, 2]])
+        if k.shape != (4,):
+            raise ValueError(f"undistort_map: {name} is (fx, fy, cx, cy) or a 3 x 3 camera matrix")
+        return (C.c_double * 4)(*k.tolist())
+    d = [float(v) for v in np.asarray(dist, dtype=np.float64).reshape(-1)]
+    if len(d) > 5:
+        raise ValueError("undistort_map: dist is up to five coefficients (k1, k2, p1, p2, k3)")
+    d += [0.0] * (5 - len(d))
+    wo, ho = int(size[0]), int(size[1])
+    if wo < 1 or ho < 1 or wo > RESIZE_MAX_DIM or ho > RESIZE_MAX_DIM:
+        raise ValueError("undistort_map: size is (out_w, out_h), both 1..32768")
+    out = np.empty((ho, wo, 2), dtype=np.int32)
+    check(lib().mi_blur_remap_undistort(intrinsics(K, "K"), (C.c_double * 5)(*d), None if new_K is None else intrinsics(new_K, "new_K"), wo, ho, out.ctypes.data),
+          "mi_blur_remap_undistort")
+    return out
+
+
+def undistort(images, K, dist, new_K=None, size=None, mode="bilinear", border="constant", fill: int = 0, device: int = 0, batch: int = 0):
+    """remap() through undistort_map(K, dist, size, new_K): OpenCV's undistort.  size = (out_w, out_h), the input's by default."""
+    a = _images(images, "undistort")
+    h, w = (a.shape[0], a.shape[1]) if a.ndim < 4 else (a.shape[1], a.shape[2])
+    return remap(a, undistort_map(K, dist, size or (w, h), new_K), None, mode, border, fill, device, batch)

@@ -181,6 +181,9 @@ struct Options {
     bool persp_given = false;            // --perspective x0,y0,..,x3,y3 [--nearest] [--border-fill V]: the source quad (top-left, top-right, bottom-right, bottom-left;
     double persp_quad[8] = {};           //              input pixels, reals) is mapped onto the corners of an output of the input's size
                                          //              (mi_blur_ctx_set_warp_perspective; mode and border as --rotate; heterogeneous_blur only: no bands)
+    bool undistort_given = false;        // --undistort k1[,k2[,p1,p2[,k3]]] [--nearest] [--border-fill V]: undo the lens distortion of a camera with fx = fy = W
+    double undistort_dist[5] = {};       //              and the principal point at the image's centre, same size (mi_blur_remap_undistort, mi_blur_ctx_set_remap;
+                                         //              mode and border as --rotate; heterogeneous_blur only: no bands)
     bool nearest = false;                //              mi_blur_ctx_set_resize on every context, outputs of that size (heterogeneous_blur only: no bands)
     int images = 5000;                   // --images N   (NUM_IMAGES, heterogeneous_blur.c:44)
     bool images_given = false;
@@ -270,6 +273,26 @@ inline int parse_flags(int argc, char **argv, Options &o)
             if (sscanf(next("--perspective"), "%lf,%lf,%lf,%lf,%lf,%lf,%lf,%lf%c", q, q + 1, q + 2, q + 3, q + 4, q + 5, q + 6, q + 7, &tail) != 8) { printf("Error: --perspective x0,y0,x1,y1,x2,y2,x3,y3: the source quad, top-left, top-right, bottom-right, bottom-left\n"); exit(-1); }
             o.persp_given = true;
         }
+        else if (a == "--undistort") {
+            double *k = o.undistort_dist;
+            std::fill(k, k + 5, 0.0);
+            const char *p = next("--undistort");
+            int got = 0;
+            bool ok = true;
+            while (ok) {                                // numbers separated by single commas, nothing else
+                char *end = nullptr;
+                const double v = strtod(p, &end);
+                ok = end != p && got < 5 && std::isfinite(v);
+                if (!ok) break;
+                k[got++] = v;
+                if (*end == 0) break;
+                ok = *end == ',';
+                p = end + 1;
+            }
+            ok = ok && (got == 1 || got == 2 || got == 4 || got == 5);
+            if (!ok) { printf("Error: --undistort k1[,k2[,p1,p2[,k3]]]: the distortion coefficients of the lens\n"); exit(-1); }
+            o.undistort_given = true;
+        }
         else if (a == "--border-fill") {
             char tail = 0;
             if (sscanf(next("--border-fill"), "%d%c", &o.border_fill, &tail) != 1 || o.border_fill < 0 || o.border_fill > 255) { printf("Error: --border-fill V, 0..255\n"); exit(-1); }
@@ -321,8 +344,10 @@ inline int parse_flags(int argc, char **argv, Options &o)
     if (o.rotate_given && (o.resident || !o.frames.empty())) { printf("Error: --rotate excludes --resident and --frames\n"); exit(-1); }
     if (o.persp_given && (o.rotate_given || o.resize_w || o.ksize_given || o.sigma > 0.0 || o.median || o.morph || o.bilateral || o.conv_preset >= 0 || o.pyr_down)) { printf("Error: --perspective excludes --rotate, --resize, --ksize, --sigma, --median, --erode, --dilate, --morph-gradient, --bilateral, --conv and --pyr-down\n"); exit(-1); }
     if (o.persp_given && (o.resident || !o.frames.empty())) { printf("Error: --perspective excludes --resident and --frames\n"); exit(-1); }
-    if (o.border_fill >= 0 && !o.rotate_given && !o.persp_given) { printf("Error: --border-fill needs --rotate\n"); exit(-1); }
-    if (o.nearest && !o.resize_w && !o.rotate_given && !o.persp_given) { printf("Error: --nearest needs --resize\n"); exit(-1); }
+    if (o.undistort_given && (o.persp_given || o.rotate_given || o.resize_w || o.ksize_given || o.sigma > 0.0 || o.median || o.morph || o.bilateral || o.conv_preset >= 0 || o.pyr_down)) { printf("Error: --undistort excludes --perspective, --rotate, --resize, --ksize, --sigma, --median, --erode, --dilate, --morph-gradient, --bilateral, --conv and --pyr-down\n"); exit(-1); }
+    if (o.undistort_given && (o.resident || !o.frames.empty())) { printf("Error: --undistort excludes --resident and --frames\n"); exit(-1); }
+    if (o.border_fill >= 0 && !o.rotate_given && !o.persp_given && !o.undistort_given) { printf("Error: --border-fill needs --rotate\n"); exit(-1); }
+    if (o.nearest && !o.resize_w && !o.rotate_given && !o.persp_given && !o.undistort_given) { printf("Error: --nearest needs --resize\n"); exit(-1); }
     return npos;
 }
 
@@ -352,6 +377,10 @@ struct HostFilter {
     bool persp = false;         // --perspective QUAD [--nearest] [--border-fill V]: the perspective warp `pp` (mi_blur_ctx_set_warp_perspective);
     double persp_quad[8] = {};  // its size and homography come from the image: print_warp_perspective() fills them in
     mi_blur_warp_perspective pp{};
+    bool remap = false;         // --undistort K [--nearest] [--border-fill V]: the remap `rm` through `remap_map` (mi_blur_ctx_set_remap);
+    double undistort_dist[5] = {};   // its size and map come from the image: print_undistort() fills them in
+    mi_blur_remap rm{};
+    std::vector<int32_t> remap_map{};
 };
 
 inline HostFilter filter_of(const Options &o)
@@ -384,6 +413,9 @@ inline HostFilter filter_of(const Options &o)
     f.persp = o.persp_given;
     std::copy(o.persp_quad, o.persp_quad + 8, f.persp_quad);
     f.pp.mode = f.wp.mode; f.pp.border = f.wp.border; f.pp.fill = f.wp.fill;
+    f.remap = o.undistort_given;
+    std::copy(o.undistort_dist, o.undistort_dist + 5, f.undistort_dist);
+    f.rm.mode = f.wp.mode; f.rm.border = f.wp.border; f.rm.fill = f.wp.fill;
     return f;
 }
 
@@ -399,6 +431,18 @@ inline void set_filter(mi_blur_ctx *ctx, const HostFilter &f)
     if (f.resize) mi_check(mi_blur_ctx_set_resize(ctx, &f.rs), "Failed to set the resize");
     if (f.warp) mi_check(mi_blur_ctx_set_warp(ctx, &f.wp), "Failed to set the warp");
     if (f.persp) mi_check(mi_blur_ctx_set_warp_perspective(ctx, &f.pp), "Failed to set the perspective warp");
+    if (f.remap) mi_check(mi_blur_ctx_set_remap(ctx, &f.rm, f.remap_map.data()), "Failed to set the remap");
+}
+
+// --undistort, once the image size is known: the undistortion map of a camera with fx = fy = W and the principal point at
+// the image's centre, at the image's own size (mi_blur_remap_undistort), and the banner's "Blur kernel" line.
+inline void print_undistort(HostFilter &f, int width, int height)
+{
+    const double K[4] = {(double)width, (double)width, (width - 1) / 2.0, (height - 1) / 2.0};
+    f.rm.out_width = width; f.rm.out_height = height;
+    f.remap_map.resize((size_t)width * height * 2);
+    mi_check(mi_blur_remap_undistort(K, f.undistort_dist, nullptr, width, height, f.remap_map.data()), "No undistortion map for --undistort");
+    printf("Blur kernel: %s remap, undistort k1=%g, %dx%d -> %dx%d\n", f.rm.mode == MI_BLUR_RESIZE_NEAREST ? "nearest" : "bilinear", f.undistort_dist[0], width, height, width, height);
 }
 
 // --rotate, once the image size is known: the warp of f becomes the rotation about the image's centre at the image's
@@ -448,7 +492,7 @@ inline int filter_halo(const HostFilter &f) { return f.conv_preset >= 0 ? f.conv
 // The banner's "Blur kernel" line (with the taps of a Gaussian).
 inline void print_filter(const HostFilter &f)
 {
-    if (f.pyr_down || f.resize || f.warp || f.persp) return;     // print_pyr_down() / print_resize() / print_warp() / print_warp_perspective(), once the image size is known
+    if (f.pyr_down || f.resize || f.warp || f.persp || f.remap) return;     // print_pyr_down() / print_resize() / print_warp() / print_warp_perspective() / print_undistort(), once the image size is known
     if (f.median) { printf("Blur kernel: %dx%d median\n", f.median, f.median); return; }
     if (f.conv_preset >= 0) { printf("Blur kernel: %dx%d convolution (%s)\n", 2 * f.conv.rx + 1, 2 * f.conv.ry + 1, f.conv_name.c_str()); return; }
     if (f.bilateral) { printf("Blur kernel: %dx%d bilateral (sigma_color %g, sigma_space %g)\n", f.bilateral, f.bilateral, f.sigma_color, f.sigma_space); return; }

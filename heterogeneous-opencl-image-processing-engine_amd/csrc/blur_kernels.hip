@@ -1644,6 +1644,7 @@ int launch(const LaunchDesc &d)
     case FilterKind::RESIZE: return launch_resize(d);
     case FilterKind::WARP: return launch_warp(d);
     case FilterKind::WARP_PERSP: return launch_warp_persp(d);
+    case FilterKind::REMAP: return launch_remap(d);
     }
     return MI_BLUR_ERR_INVALID;
 }

@@ -55,6 +55,9 @@ int launch_resize(const LaunchDesc &d);
 int launch_warp(const LaunchDesc &d);
 // The perspective warp (FilterKind::WARP_PERSP, warp_kernels.hip).  The contract of launch_resize.
 int launch_warp_persp(const LaunchDesc &d);
+// The remap (FilterKind::REMAP, remap_kernels.hip): d.filter->remap_map is DEVICE memory, out_h x out_w int32 pairs, read by
+// the kernels of this launch only.  The contract of launch_resize.
+int launch_remap(const LaunchDesc &d);
 // Sets what last_kernel() reports for the calling thread.
 void set_last_kernel(const char *name);
 

@@ -440,6 +440,23 @@ void cpu_warp_persp_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, c
     }
 }
 
+// The same for the remap of f (f.remap_map, host memory here): every byte through remap_coord() and warp_sample() (filter.h),
+// the functions of the GPU's generic kernel.
+void cpu_remap_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, const Filter &f, int Y_begin, int Y_end)
+{
+    const int Wo = f.out_w;
+    const size_t pitch = (size_t)W * C, opitch = (size_t)Wo * C;
+    for (int Y = Y_begin; Y < Y_end; Y++) {
+        uint8_t *o = out + (size_t)Y * opitch;
+        const int32_t *e = f.remap_map + (size_t)Y * (size_t)Wo * 2;
+        for (int X = 0; X < Wo; X++) {
+            const WarpCoord q = remap_coord(e[2 * X], e[2 * X + 1], f.sample_mode, W, H);
+            for (int c = 0; c < C; c++)
+                o[(size_t)X * C + c] = (uint8_t)warp_sample(in + c, pitch, C, W, H, f.warp_border, (unsigned)f.warp_fill, q);
+        }
+    }
+}
+
 // Empty for any filter but a resize.
 std::vector<ResizeCoord> resize_xtable(int W, const Filter &f)
 {
@@ -491,6 +508,7 @@ void cpu_blur_batch(const uint8_t *in, uint8_t *out, int W, int band_rows, int C
             case FilterKind::RESIZE: cpu_resize_rows(src, dst, W, band_rows, C, f, ys, ye, xtab.data()); break;
             case FilterKind::WARP: cpu_warp_rows(src, dst, W, band_rows, C, f, ys, ye); break;
             case FilterKind::WARP_PERSP: cpu_warp_persp_rows(src, dst, W, band_rows, C, f, ys, ye); break;
+            case FilterKind::REMAP: cpu_remap_rows(src, dst, W, band_rows, C, f, ys, ye); break;
             }
         }
     };

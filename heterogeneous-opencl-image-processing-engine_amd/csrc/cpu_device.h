@@ -35,6 +35,8 @@ std::vector<ResizeCoord> resize_xtable(int W, const Filter &f);
 void cpu_warp_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, const Filter &f, int Y_begin, int Y_end);
 // Output rows [Y_begin, Y_end) of the perspective warp of f (f.warp_h).
 void cpu_warp_persp_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, const Filter &f, int Y_begin, int Y_end);
+// Output rows [Y_begin, Y_end) of the remap of f (f.remap_map: host memory).
+void cpu_remap_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, const Filter &f, int Y_begin, int Y_end);
 void cpu_blur_batch(const uint8_t *in, uint8_t *out, int W, int band_rows, int C, const Filter &f, int n_images,
                     int y0, int y1, int n_threads, size_t in_stride = 0, size_t out_stride = 0);
 // The box blur of radius R (1|2): the form the host-only sanitizer harness (tests/san_cpu_device.cpp) drives.

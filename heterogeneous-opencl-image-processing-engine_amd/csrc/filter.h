@@ -20,7 +20,7 @@ struct SepTaps {
     unsigned wx[2 * SEP_MAX_R + 1], wy[2 * SEP_MAX_R + 1];
 };
 
-enum class FilterKind { BOX, SEP, MEDIAN, MORPH, BILATERAL, CONV, SEP_DOWN, RESIZE, WARP, WARP_PERSP };
+enum class FilterKind { BOX, SEP, MEDIAN, MORPH, BILATERAL, CONV, SEP_DOWN, RESIZE, WARP, WARP_PERSP, REMAP };
 
 // BOX: the fixed 3x3 / 5x5 kernel of `radius` 1|2.  SEP: the separable kernel `taps`.  MEDIAN: the median of `radius` 1..7.
 // MORPH: the window minimum / maximum / their difference (`morph_op`) over (2 morph_rx + 1) x (2 morph_ry + 1).
@@ -37,6 +37,9 @@ enum class FilterKind { BOX, SEP, MEDIAN, MORPH, BILATERAL, CONV, SEP_DOWN, RESI
 // goes through a position function (warp_position() below for warp_m), so another map source slots in beside it:
 // WARP_PERSP: the perspective warp (mi_blur_warp_perspective): as WARP, but the position of output pixel (X, Y) is the
 // quotient of two linear forms of warp_h (persp_position(), persp_axis() below): the second map source.
+// REMAP: the remap (mi_blur_remap): as WARP, but output pixel (X, Y) samples the position entry (Y, X) of the table
+// remap_map gives it, 11 fraction bits (remap_axis() below): the third map source.  The table is NOT owned by the Filter:
+// device memory for a launch, host memory for the CPU device; whoever builds the Filter keeps it alive.
 struct Filter {
     FilterKind kind;
     int radius;             // BOX and MEDIAN
@@ -52,6 +55,8 @@ struct Filter {
     int warp_border = 0, warp_fill = 0;                       // WARP (mi_blur_warp_border, fill 0..255); last, for the same reason
     int64_t warp_m[6] = {};                                   // WARP: the OUTPUT -> INPUT map, Q16, row-major 2 x 3
     int64_t warp_h[9] = {};                                   // WARP_PERSP: the OUTPUT -> INPUT homography, row-major 3 x 3, free scale; out_w .. warp_fill as WARP
+    const int32_t *remap_map = nullptr;                       // REMAP: int32[out_h][out_w][2] = (px, py), MI_BLUR_REMAP_FRAC fraction bits; out_w .. warp_fill as WARP
+    int remap_stage_bytes = 0;                                // REMAP: the largest tile footprint the tiled kernel stages in LDS (16..REMAP_STAGE_MAX; the constructor resolves 0)
 };
 
 #if defined(__HIP__)
@@ -304,6 +309,49 @@ inline bool persp_ok(const mi_blur_warp_perspective *w, int W, int H, int C)
     return w && resize_ok(w->out_width, w->out_height, w->mode, W, H, C) && persp_map_ok(w->border, w->fill, w->h, w->out_width, w->out_height);
 }
 
+// ---- the remap (include/mi_blur.h, "Remap").  The GPU kernels, the CPU device, mi_blur_remap_coord and mi_blur_remap_plan
+// all take their coordinates from remap_axis(); the taps, the blend and the border rules are the affine warp's.
+// One axis of a map entry pv (11 fraction bits) on an axis of n >= 1 samples: p = pv clamped into [-2 * 2048, (n + 1) * 2048]
+// (the clamp of warp_axis(), for the same reason: any int32 is a valid entry, and (n + 1) * 2048 < 2^27), then BILINEAR
+// i0 = p >> 11, f = p & 2047; NEAREST i0 = (p + 1024) >> 11, f = 0.
+MI_BLUR_HD inline WarpAxis remap_axis(int32_t pv, int mode, int n)
+{
+    const int32_t lo = -2 * 2048, hi = (n + 1) * 2048;
+    const int32_t p = pv < lo ? lo : pv > hi ? hi : pv;
+    if (mode == MI_BLUR_RESIZE_NEAREST) return {(p + 1024) >> 11, 0};
+    return {p >> 11, p & 2047};
+}
+MI_BLUR_HD inline WarpCoord remap_coord(int32_t px, int32_t py, int mode, int W, int H)
+{
+    const WarpAxis ax = remap_axis(px, mode, W), ay = remap_axis(py, mode, H);
+    return {ax.i0, ay.i0, ax.f, ay.f};
+}
+// The input pixels the taps of a set of output pixels can touch, from the extrema of their first taps (x0, y0): the box
+// [x_lo, x_hi + 1] x [y_lo, y_hi + 1], finished exactly as warp_footprint() finishes its own: clamped into the image
+// (CLAMP; never empty) or intersected with it (CONSTANT; empty when it misses the image).  blur_remap_tiled_kernel
+// reduces the extrema over a tile's map entries, mi_blur_remap_plan walks the same tiles on the host: one function.
+MI_BLUR_HD inline WarpBox remap_box(int x_lo, int x_hi, int y_lo, int y_hi, int border, int W, int H)
+{
+    WarpBox b{x_lo, x_hi + 1, y_lo, y_hi + 1};
+    if (border == MI_BLUR_WARP_CONSTANT) {
+        b.x0 = b.x0 < 0 ? 0 : b.x0; b.x1 = b.x1 > W - 1 ? W - 1 : b.x1;
+        b.y0 = b.y0 < 0 ? 0 : b.y0; b.y1 = b.y1 > H - 1 ? H - 1 : b.y1;
+    } else {
+        b.x0 = b.x0 < 0 ? 0 : b.x0 > W - 1 ? W - 1 : b.x0; b.x1 = b.x1 < 0 ? 0 : b.x1 > W - 1 ? W - 1 : b.x1;
+        b.y0 = b.y0 < 0 ? 0 : b.y0 > H - 1 ? H - 1 : b.y0; b.y1 = b.y1 < 0 ? 0 : b.y1 > H - 1 ? H - 1 : b.y1;
+    }
+    return b;
+}
+// A remap that is valid for a W x H image of C channels: the sizes, mode and byte limits of resize_ok(), a known border,
+// fill 0..255, stage_bytes 0 (the default) or 16..REMAP_STAGE_MAX.  The map's entries are not looked at: every one is valid.
+constexpr int REMAP_STAGE_MAX = 65520;
+inline bool remap_ok(const mi_blur_remap *r, int W, int H, int C)
+{
+    return r && resize_ok(r->out_width, r->out_height, r->mode, W, H, C) &&
+           (r->border == MI_BLUR_WARP_CLAMP || r->border == MI_BLUR_WARP_CONSTANT) && r->fill >= 0 && r->fill <= 255 &&
+           (r->stage_bytes == 0 || (r->stage_bytes >= 16 && r->stage_bytes <= REMAP_STAGE_MAX));
+}
+
 // Output size of a decimation of a W x H image: kept columns / rows (> 0 for a valid decimation, down_ok()).
 inline int down_cols(int W, int sx, int ox) { return (W - ox + sx - 1) / sx; }
 inline int down_rows(int H, int sy, int oy) { return (H - oy + sy - 1) / sy; }
@@ -319,7 +367,8 @@ inline bool down_ok(const mi_blur_decimation *d, int W, int H)
 // rows, no planar or resident forms (a band's phase or source rows would depend on where it starts).
 inline bool whole_image_only(const Filter &f)
 {
-    return f.kind == FilterKind::SEP_DOWN || f.kind == FilterKind::RESIZE || f.kind == FilterKind::WARP || f.kind == FilterKind::WARP_PERSP;
+    return f.kind == FilterKind::SEP_DOWN || f.kind == FilterKind::RESIZE || f.kind == FilterKind::WARP || f.kind == FilterKind::WARP_PERSP ||
+           f.kind == FilterKind::REMAP;
 }
 // Width and rows of the output block of one band of band_rows rows x W of which rows [y0, y1) are asked for: those rows
 // at the input's width, or the filter's own output image (of the whole band) for a whole_image_only filter.
@@ -327,7 +376,7 @@ struct OutShape { int width, rows; };
 inline OutShape out_shape(const Filter &f, int W, int band_rows, int y0, int y1)
 {
     if (f.kind == FilterKind::SEP_DOWN) return {down_cols(W, f.down_sx, f.down_ox), down_rows(band_rows, f.down_sy, f.down_oy)};
-    if (f.kind == FilterKind::RESIZE || f.kind == FilterKind::WARP || f.kind == FilterKind::WARP_PERSP) return {f.out_w, f.out_h};
+    if (f.kind == FilterKind::RESIZE || f.kind == FilterKind::WARP || f.kind == FilterKind::WARP_PERSP || f.kind == FilterKind::REMAP) return {f.out_w, f.out_h};
     return {W, y1 - y0};
 }
 
@@ -392,6 +441,17 @@ inline int filter_warp_persp(const mi_blur_warp_perspective *w, Filter *f)
     *f = Filter{FilterKind::WARP_PERSP, 0, {}};
     f->out_w = w->out_width; f->out_h = w->out_height; f->sample_mode = w->mode; f->warp_border = w->border; f->warp_fill = w->fill;
     for (int i = 0; i < 9; i++) f->warp_h[i] = w->h[i];
+    return MI_BLUR_OK;
+}
+
+// The target size, mode, border and staging limit of *r and the table `map` (not copied; the image size is checked where
+// it is known: remap_ok()).
+inline int filter_remap(const mi_blur_remap *r, const int32_t *map, Filter *f)
+{
+    if (!f || !map || !remap_ok(r, 1, 1, 1)) return MI_BLUR_ERR_INVALID;
+    *f = Filter{FilterKind::REMAP, 0, {}};
+    f->out_w = r->out_width; f->out_h = r->out_height; f->sample_mode = r->mode; f->warp_border = r->border; f->warp_fill = r->fill;
+    f->remap_map = map; f->remap_stage_bytes = r->stage_bytes ? r->stage_bytes : REMAP_STAGE_MAX;
     return MI_BLUR_OK;
 }
 
@@ -595,6 +655,49 @@ inline long long persp_tiles_max_bytes(const TileGrid &g, const int64_t *h, int 
             max_bytes = bytes > max_bytes ? bytes : max_bytes;
         }
     return max_bytes;
+}
+
+// ---- blur_remap_tiled_kernel: the tiles, warp_tap() and the slack of blur_warp_tiled_kernel.  The map lives in device
+// memory, so the workgroup finds its box itself (remap_tile_box() is what its reduction computes) and decides per tile:
+// empty (CONSTANT, `fill`), staged (the box takes at most stage_bytes of LDS) or direct (taps from global memory).
+// LDS: REMAP_RED_BYTES of reduction words (4 waves x 4 extrema), then the staged box, then WARP_LDS_SLACK.
+constexpr int REMAP_RED_BYTES = 64;
+inline size_t remap_lds_bytes(int stage_bytes) { return (size_t)REMAP_RED_BYTES + (size_t)stage_bytes + (size_t)WARP_LDS_SLACK; }
+// Whether the shape is the tiled kernel's (pointers and strides assumed aligned): BILINEAR, 1-4 channels, rows of whole chunks both sides.
+inline bool remap_shape_tiled(int W, int C, int Wo, int mode)
+{
+    return mode == MI_BLUR_RESIZE_BILINEAR && C >= 1 && C <= 4 && (long long)W * C % 16 == 0 && (long long)Wo * C % 16 == 0;
+}
+// The box of the tile of output rows ty0 .. ty0 + rows_out - 1 x chunk columns x0c .. x0c + nc - 1, from the host's copy of the map.
+inline WarpBox remap_tile_box(const int32_t *map, int border, int W, int H, int Wo, int C, int ty0, int rows_out, int x0c, int nc)
+{
+    const Span px = tile_pixels(x0c, nc, C);
+    int x_lo = INT_MAX, x_hi = INT_MIN, y_lo = INT_MAX, y_hi = INT_MIN;
+    for (int Y = ty0; Y < ty0 + rows_out; Y++)
+        for (int X = px.lo; X <= px.hi; X++) {
+            const int32_t *e = map + ((size_t)Y * (size_t)Wo + (size_t)X) * 2;
+            const WarpCoord q = remap_coord(e[0], e[1], MI_BLUR_RESIZE_BILINEAR, W, H);
+            x_lo = q.x0 < x_lo ? q.x0 : x_lo; x_hi = q.x0 > x_hi ? q.x0 : x_hi;
+            y_lo = q.y0 < y_lo ? q.y0 : y_lo; y_hi = q.y0 > y_hi ? q.y0 : y_hi;
+        }
+    return remap_box(x_lo, x_hi, y_lo, y_hi, border, W, H);
+}
+inline long long remap_box_bytes(const WarpBox &b, int C) { return (long long)(b.y1 - b.y0 + 1) * chunk_span(b.x0, b.x1, C).n() * 16; }
+// The walk of mi_blur_remap_plan over the tiles of one output image (remap_shape_tiled() holds).
+inline void remap_walk(const int32_t *map, int W, int H, int C, int Wo, int Ho, int border, int stage_bytes, mi_blur_remap_tiles *t)
+{
+    const TileGrid g = warp_grid(Wo * C / 16, Ho, C);
+    for (int ty = 0; ty < g.ntiles_y; ty++)
+        for (int s = 0; s < g.nstrips; s++) {
+            const Tile tl = tile_at(g, Ho, s, ty);
+            const WarpBox b = remap_tile_box(map, border, W, H, Wo, C, tl.ty0, tl.rows_out, tl.x0c, tl.nc);
+            t->tiles++;
+            if (warp_box_empty(b)) { t->empty++; continue; }
+            const long long bytes = remap_box_bytes(b, C);
+            t->max_box_bytes = bytes > t->max_box_bytes ? bytes : t->max_box_bytes;
+            if (bytes <= stage_bytes) { t->staged++; t->max_staged_bytes = bytes > t->max_staged_bytes ? bytes : t->max_staged_bytes; }
+            else t->direct++;
+        }
 }
 
 }  // namespace mi_blur

@@ -160,6 +160,26 @@ __device__ __forceinline__ void stage_box(uint8_t *dst, const uint8_t *src, int 
 __device__ __forceinline__ uint32_t lerp24(uint32_t a, uint32_t b, uint32_t f) { return __umul24(a, BLEND_ONE - f) + __umul24(b, f); }
 __device__ __forceinline__ uint32_t lerp24_round(uint32_t a, uint32_t b, uint32_t f) { return (lerp24(a, b, f) + BLEND_BIAS) >> BLEND_SHIFT; }
 
+// Pixels xa and xa + 1 of a staged row, pixel xa starting at byte offset `off` of the footprint: a (and b) = their C
+// bytes, lowest channel lowest.  Two dword reads at the 4-byte aligned address below `off` (one ds_read2_b32) and a 64-bit
+// shift; 3 channels can straddle a third dword (bytes 3 .. 8 of the two): warp_read_bytes(C) bytes in all, the extent
+// warp_tap() (filter.h) states and WARP_LDS_SLACK keeps inside the launch's LDS.  The warp, perspective and remap tiled kernels.
+template <int C>
+__device__ __forceinline__ void warp_taps(const uint8_t *lds, int off, uint32_t &a, uint32_t &b)
+{
+    constexpr uint32_t PIX = C == 4 ? 0xffffffffu : (1u << (8 * (C & 3))) - 1u;
+    const uint32_t *q = reinterpret_cast<const uint32_t *>(lds + (off & ~3));
+    const int sh = 8 * (off & 3);
+    const uint64_t v = (((uint64_t)q[1] << 32) | q[0]) >> sh;
+    a = (uint32_t)v & PIX;
+    if constexpr (C == 3) {
+        const uint64_t v2 = (((uint64_t)q[2] << 32) | q[1]) >> sh;      // the bytes from off + 4 on; pixel b starts at off + 3
+        b = (((uint32_t)v >> 24) | ((uint32_t)v2 << 8)) & PIX;
+    } else {
+        b = (uint32_t)(v >> (8 * C)) & PIX;
+    }
+}
+
 // Output byte idx of a byte-per-thread (generic) kernel: block = output bytes per band, so idx = img * block + rem and
 // rem = (y - y0) * pitch + b, b = x * channels + c (pitch: of the OUTPUT row, where that is not the input's).  src = the image's band.
 struct BytePos {

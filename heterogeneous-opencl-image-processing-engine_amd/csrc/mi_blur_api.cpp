@@ -96,7 +96,7 @@ enum class PreCheck {
     FILTER,     // sep: the constructor's status
     ARGS,       // median, morph, bilateral, conv: + pointers, dimensions, image count
     ARGS_ROWS,  // conv_band: + the row range
-    ARGS_SIZE,  // sep_down, resize, warp, warp_perspective: + the image within INT_MAX bytes
+    ARGS_SIZE,  // sep_down, resize, warp, warp_perspective, remap: + the image within INT_MAX bytes
 };
 
 // Every mi_blur_enqueue* export: one launch of f on device memory.  built: the status of f's constructor.
@@ -437,6 +437,85 @@ extern "C" int mi_blur_enqueue_warp_perspective(const uint8_t *d_in, uint8_t *d_
 }
 
 // ----------------------------------------------------------------------------------
+// remap: fixed-point sampling through a per-pixel map (no reference analogue)
+// ----------------------------------------------------------------------------------
+// map: device memory for a launch, host memory for the CPU device; the Filter points at it, it is not copied here.
+static int remap_for(const mi_blur_remap *r, const int32_t *map, int W, int H, int C, Filter *f)
+{
+    const int rc = filter_remap(r, map, f);
+    return rc ? rc : remap_ok(r, W, H, C) && (uintptr_t)map % 4 == 0 ? MI_BLUR_OK : MI_BLUR_ERR_INVALID;
+}
+
+extern "C" int mi_blur_remap_coord(const mi_blur_remap *r, int W, int H, int32_t px, int32_t py, int *x0, int *y0, int *fx, int *fy)
+{
+    if (!r || !x0 || !y0 || !fx || !fy || W < 1 || H < 1 || W > MI_BLUR_RESIZE_MAX_DIM || H > MI_BLUR_RESIZE_MAX_DIM) return MI_BLUR_ERR_INVALID;
+    if (r->mode != MI_BLUR_RESIZE_NEAREST && r->mode != MI_BLUR_RESIZE_BILINEAR) return MI_BLUR_ERR_INVALID;
+    const WarpCoord q = remap_coord(px, py, r->mode, W, H);
+    *x0 = q.x0; *y0 = q.y0; *fx = q.fx; *fy = q.fy;
+    return MI_BLUR_OK;
+}
+
+// q(v) = floor(v * 2048 + 0.5) clamped into [-2^30, 2^30]; v finite.
+static int32_t remap_quantise(double v)
+{
+    const double q = std::floor(v * 2048.0 + 0.5), lim = 1073741824.0;
+    return (int32_t)(q < -lim ? -lim : q > lim ? lim : q);
+}
+
+extern "C" int mi_blur_remap_from_float(const float *map_x, const float *map_y, size_t n, int32_t *map)
+{
+    if (!map_x || !map_y || !map) return MI_BLUR_ERR_INVALID;
+    for (size_t i = 0; i < n; i++)
+        if (!std::isfinite(map_x[i]) || !std::isfinite(map_y[i])) return MI_BLUR_ERR_INVALID;
+    for (size_t i = 0; i < n; i++) { map[2 * i] = remap_quantise((double)map_x[i]); map[2 * i + 1] = remap_quantise((double)map_y[i]); }
+    return MI_BLUR_OK;
+}
+
+extern "C" int mi_blur_remap_undistort(const double K[4], const double dist[5], const double new_K[4], int out_width, int out_height, int32_t *map)
+{
+#pragma clang fp contract(off)      // every product and sum rounded on its own: a restatement in any language can match it
+    if (!K || !dist || !map || out_width < 1 || out_height < 1 || out_width > MI_BLUR_RESIZE_MAX_DIM || out_height > MI_BLUR_RESIZE_MAX_DIM)
+        return MI_BLUR_ERR_INVALID;
+    const double *N = new_K ? new_K : K;
+    for (int i = 0; i < 4; i++) if (!std::isfinite(K[i]) || !std::isfinite(N[i])) return MI_BLUR_ERR_INVALID;
+    for (int i = 0; i < 5; i++) if (!std::isfinite(dist[i])) return MI_BLUR_ERR_INVALID;
+    if (N[0] == 0.0 || N[1] == 0.0) return MI_BLUR_ERR_INVALID;
+    const double fx = K[0], fy = K[1], cx = K[2], cy = K[3], k1 = dist[0], k2 = dist[1], p1 = dist[2], p2 = dist[3], k3 = dist[4];
+    for (int Y = 0; Y < out_height; Y++)
+        for (int X = 0; X < out_width; X++) {
+            const double x = ((double)X - N[2]) / N[0], y = ((double)Y - N[3]) / N[1];
+            const double r2 = x * x + y * y;
+            const double rad = 1.0 + k1 * r2 + k2 * r2 * r2 + k3 * r2 * r2 * r2;
+            const double xd = x * rad + 2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x);
+            const double yd = y * rad + p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y;
+            const double u = fx * xd + cx, v = fy * yd + cy;
+            if (!std::isfinite(u) || !std::isfinite(v)) return MI_BLUR_ERR_INVALID;
+            int32_t *e = map + ((size_t)Y * (size_t)out_width + (size_t)X) * 2;
+            e[0] = remap_quantise(u); e[1] = remap_quantise(v);
+        }
+    return MI_BLUR_OK;
+}
+
+extern "C" int mi_blur_remap_plan(const int32_t *host_map, int width, int height, int channels, const mi_blur_remap *r, mi_blur_remap_tiles *tiles)
+{
+    Filter f;
+    if (!tiles || remap_for(r, host_map, width, height, channels, &f)) return MI_BLUR_ERR_INVALID;
+    *tiles = mi_blur_remap_tiles{};
+    if (!remap_shape_tiled(width, channels, f.out_w, f.sample_mode)) return MI_BLUR_OK;
+    tiles->tiled = 1;
+    remap_walk(host_map, width, height, channels, f.out_w, f.out_h, f.warp_border, f.remap_stage_bytes, tiles);
+    return MI_BLUR_OK;
+}
+
+extern "C" int mi_blur_enqueue_remap(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int n_images,
+                                     const mi_blur_remap *r, const int32_t *d_map, void *stream)
+{
+    Filter f;
+    const int built = (const void *)d_map == (const void *)d_out ? MI_BLUR_ERR_INVALID : remap_for(r, d_map, width, height, channels, &f);
+    return enqueue_filter(built, f, PreCheck::ARGS_SIZE, d_in, d_out, width, height, channels, n_images, 0, height, MI_BLUR_VARIANT_AUTO, stream);
+}
+
+// ----------------------------------------------------------------------------------
 // median blur, radius 1..7 (no reference analogue)
 // ----------------------------------------------------------------------------------
 extern "C" int mi_blur_enqueue_median_band(const uint8_t *d_in, uint8_t *d_out, int width, int band_rows, int channels,
@@ -725,8 +804,20 @@ struct mi_blur_ctx {
     std::vector<CpuJob *> cpu_jobs;
     CpuWorker *cpu_worker = nullptr;
     bool submitted = false;                                      // the mi_blur_ctx_set_* work only before this
+    // the context's copy of a remap's map (mi_blur_ctx_set_remap; filter.remap_map points at it): device memory on a GPU
+    // context, the vector on the CPU device.  ctx_drop_map() frees it: when another setter replaces the remap, and in mi_blur_destroy
+    int32_t *remap_dev = nullptr;
+    std::vector<int32_t> remap_host;
     bool is_cpu() const { return device == MI_BLUR_DEVICE_CPU; }
 };
+
+// Frees the context's copy of a remap's map, if it has one.  Only before the first submit or in mi_blur_destroy (after the
+// streams and the CPU worker have been waited for), so nothing in flight reads it.
+static void ctx_drop_map(mi_blur_ctx *c)
+{
+    if (c->remap_dev) { (void)hipSetDevice(c->device); (void)hipFree(c->remap_dev); c->remap_dev = nullptr; }
+    std::vector<int32_t>().swap(c->remap_host);
+}
 
 static bool is_pinned(const void *p)
 {
@@ -1123,6 +1214,7 @@ extern "C" void mi_blur_destroy(mi_blur_ctx *c)
         if (c->fused_ev) (void)hipEventDestroy(c->fused_ev);
         if (c->pool_in) (void)hipFree(c->pool_in);
         if (c->pool_out) (void)hipFree(c->pool_out);
+        ctx_drop_map(c);
         (void)hipGetLastError();
     }
     delete c;
@@ -1528,6 +1620,7 @@ static int ctx_set_filter(mi_blur_ctx *c, bool null_arg, B &&build)
     Filter f;
     if (const int rc = build(&f)) return rc;
     c->filter = f;
+    ctx_drop_map(c);                                    // the remap it replaced, if any, owned a map
     return MI_BLUR_OK;
 }
 
@@ -1554,6 +1647,34 @@ extern "C" int mi_blur_ctx_set_warp(mi_blur_ctx *c, const mi_blur_warp *w)
 extern "C" int mi_blur_ctx_set_warp_perspective(mi_blur_ctx *c, const mi_blur_warp_perspective *w)
 {
     return ctx_set_filter(c, !w, [&](Filter *f) { return warp_persp_for(w, c->W, c->H, c->C, f); });
+}
+
+// The copy of the map is made first, so a failure leaves the old filter and the old map in place.
+extern "C" int mi_blur_ctx_set_remap(mi_blur_ctx *c, const mi_blur_remap *r, const int32_t *host_map)
+{
+    if (!c || !r || !host_map) return MI_BLUR_ERR_INVALID;
+    if (c->submitted) return MI_BLUR_ERR_STATE;
+    Filter f;
+    if (const int rc = remap_for(r, host_map, c->W, c->H, c->C, &f)) return rc;
+    const size_t n = (size_t)f.out_w * (size_t)f.out_h * 2;
+    if (c->is_cpu()) {
+        std::vector<int32_t> copy;
+        try { copy.assign(host_map, host_map + n); } catch (...) { return MI_BLUR_ERR_NOMEM; }
+        ctx_drop_map(c);
+        c->remap_host.swap(copy);
+        f.remap_map = c->remap_host.data();
+    } else {
+        HIP_TRY(hipSetDevice(c->device));
+        int32_t *dev = nullptr;
+        HIP_TRY(hipMalloc((void **)&dev, n * sizeof(int32_t)));
+        const hipError_t e = hipMemcpy(dev, host_map, n * sizeof(int32_t), hipMemcpyHostToDevice);     // synchronous: host_map is free again on return
+        if (e != hipSuccess) { (void)hipFree(dev); (void)hipGetLastError(); return MI_BLUR_ERR_HIP_BASE - (int)e; }
+        ctx_drop_map(c);
+        c->remap_dev = dev;
+        f.remap_map = dev;
+    }
+    c->filter = f;
+    return MI_BLUR_OK;
 }
 
 extern "C" int mi_blur_ctx_set_median(mi_blur_ctx *c, int radius)
@@ -2030,6 +2151,14 @@ extern "C" int mi_blur_cpu_run_warp_perspective(const uint8_t *in, uint8_t *out,
 {
     Filter f;
     return cpu_run_filter(warp_persp_for(w, width, height, channels, &f), f, in, out, width, height, channels, n_images, n_threads);
+}
+
+extern "C" int mi_blur_cpu_run_remap(const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,
+                                     const mi_blur_remap *r, const int32_t *host_map, int n_threads)
+{
+    Filter f;
+    const int built = (const void *)host_map == (const void *)out ? MI_BLUR_ERR_INVALID : remap_for(r, host_map, width, height, channels, &f);
+    return cpu_run_filter(built, f, in, out, width, height, channels, n_images, n_threads);
 }
 
 extern "C" int mi_blur_cpu_run_median(const uint8_t *in, uint8_t *out, int width, int height, int channels, int radius,

@@ -49,26 +49,7 @@ struct WarpTiledParams {
     unsigned fill;                    // the fill byte in all four bytes
 };
 
-// Pixels xa and xa + 1 of a staged row, pixel xa starting at byte offset `off` of the footprint: a (and b) = their C
-// bytes, lowest channel lowest.  Two dword reads at the 4-byte aligned address below `off` (one ds_read2_b32) and a 64-bit
-// shift; 3 channels can straddle a third dword (bytes 3 .. 8 of the two): warp_read_bytes(C) bytes in all, the extent
-// warp_tap() (filter.h) states and WARP_LDS_SLACK keeps inside the launch's LDS.
-template <int C>
-__device__ __forceinline__ void warp_taps(const uint8_t *lds, int off, uint32_t &a, uint32_t &b)
-{
-    constexpr uint32_t PIX = C == 4 ? 0xffffffffu : (1u << (8 * (C & 3))) - 1u;
-    const uint32_t *q = reinterpret_cast<const uint32_t *>(lds + (off & ~3));
-    const int sh = 8 * (off & 3);
-    const uint64_t v = (((uint64_t)q[1] << 32) | q[0]) >> sh;
-    a = (uint32_t)v & PIX;
-    if constexpr (C == 3) {
-        const uint64_t v2 = (((uint64_t)q[2] << 32) | q[1]) >> sh;      // the bytes from off + 4 on; pixel b starts at off + 3
-        b = (((uint32_t)v >> 24) | ((uint32_t)v2 << 8)) & PIX;
-    } else {
-        b = (uint32_t)(v >> (8 * C)) & PIX;
-    }
-}
-
+// warp_taps<C>, the read of the two taps of a staged row, is in kernel_common.h: blur_remap_tiled_kernel shares it.
 template <int C>
 __global__ __launch_bounds__(TILE_THREADS) void blur_warp_tiled_kernel(const WarpTiledParams p)
 {

@@ -70,7 +70,8 @@ int mi_blur_version(void);
  * "blur_morph_generic_kernel", "blur_bilateral_tiled_kernel", "blur_bilateral_generic_kernel", "blur_conv_tiled_kernel",
  * "blur_conv_generic_kernel", "blur_sep_down_tiled_kernel", "blur_sep_down_generic_kernel",
  * "blur_resize_tiled_kernel", "blur_resize_generic_kernel", "blur_warp_tiled_kernel", "blur_warp_generic_kernel",
- * "blur_warp_persp_tiled_kernel", "blur_warp_persp_generic_kernel"; "" before the first):
+ * "blur_warp_persp_tiled_kernel", "blur_warp_persp_generic_kernel", "blur_remap_tiled_kernel",
+ * "blur_remap_generic_kernel"; "" before the first):
  * reports name the kernel a profiler will show.  Static string, never NULL. */
 const char *mi_blur_last_kernel(void);
 
@@ -686,6 +687,103 @@ int mi_blur_cpu_run_warp_perspective(const uint8_t *in, uint8_t *out, int width,
  * server); bytes_alg counts input + output bytes; mi_blur_submit_band, _bands, _planar and both resident runs return
  * MI_BLUR_ERR_UNSUPPORTED. */
 int mi_blur_ctx_set_warp_perspective(mi_blur_ctx *ctx, const mi_blur_warp_perspective *w);
+
+/* ------------------------------------------------------------------------
+ * Remap: exact fixed-point sampling through a per-pixel map (no reference analogue; OpenCV's remap is the model): lens
+ * undistortion, rectification, fisheye and cylindrical unwrapping, mesh warps, any map computed elsewhere.  Exact integers
+ * again: the GPU, the CPU device and a numpy restatement agree byte for byte.
+ *
+ * map is int32_t[out_height][out_width][2], dense.  Entry (Y, X) is (px, py): the input position of output pixel (X, Y)
+ * with MI_BLUR_REMAP_FRAC = 11 fraction bits, px = x * 2048, pixel (x, y) at integer coordinates (the warps' convention and
+ * OpenCV's).  One map serves every image of a launch.  EVERY int32 pair is a valid entry, INT32_MIN and INT32_MAX
+ * included: the library cannot validate device memory, so nothing is out of range.  Per axis, with n = W or H:
+ *   p = min(max(px, -2*2048), (n+1)*2048)          (the clamp of the affine warp, for the same reason: under either border
+ *                                                   rule a position out there gives the bytes of the nearest one inside)
+ *   BILINEAR:  x0 = p >> 11,  fx = p & 2047        NEAREST:  xi = (p + 1024) >> 11,  f = 0
+ * Everything else is the affine warp's: the four taps, the blend expression and its one rounding, the CLAMP / CONSTANT
+ * border with `fill`, each tap decided on its own, channels never mix, and the output is interleaved and dense: pitch
+ * out_width*C, images out_width*out_height*C bytes apart.
+ *
+ * Properties (checked in tests/test_remap_host.py):
+ *   a map with px = X*2048, py = Y*2048 at the input's size is the identity;
+ *   a BILINEAR map built as px = clip(x0*2048 + fx), py likewise, with x0, fx from mi_blur_warp_coord (clip: into the int32
+ *   range) gives the bytes of mi_blur_enqueue_warp under both borders, and with mi_blur_warp_perspective_coord those of
+ *   mi_blur_enqueue_warp_perspective; so, through the warp, the x2 / x4 / /2 / /4 / /8 CLAMP maps give the resize's bytes;
+ *   the result differs from real-valued bilinear interpolation at the map's exact position by less than
+ *   0.5 + 255 * 2^-11, the warp's bound; for a map quantised from real numbers (mi_blur_remap_from_float) the bound holds
+ *   against the REAL positions, because each axis is then rounded by at most 2^-12;
+ *   it is NOT OpenCV's remap bit for bit: OpenCV quantises positions to 5 bits.
+ * ---------------------------------------------------------------------- */
+#define MI_BLUR_REMAP_FRAC 11                 /* fraction bits of a map entry */
+typedef struct mi_blur_remap {
+    int out_width, out_height;                /* 1 .. MI_BLUR_RESIZE_MAX_DIM each */
+    int mode;                                 /* MI_BLUR_RESIZE_NEAREST | MI_BLUR_RESIZE_BILINEAR */
+    int border;                               /* mi_blur_warp_border */
+    int fill;                                 /* 0..255, every channel; CONSTANT only */
+    int stage_bytes;                          /* 0 = 65520; else 16..65520: the largest tile footprint the tiled kernel stages in LDS */
+} mi_blur_remap;
+typedef struct mi_blur_remap_tiles {
+    int tiled;                                /* 1: the shape is blur_remap_tiled_kernel's (pointers assumed aligned); 0: the rest stays 0 */
+    int tiles, staged, direct, empty;         /* tiles of one output image; staged + direct + empty == tiles */
+    long long max_box_bytes, max_staged_bytes;/* the largest footprint of any tile, and of any staged tile */
+} mi_blur_remap_tiles;
+
+/* The CLAMPED tap origin (x0, y0) and the fractions (fx, fy) of the map entry (px, py) on a W x H image, through the
+ * function the kernels and the CPU device use; NEAREST gives xi, yi, 0, 0.  Only r->mode is read.  MI_BLUR_ERR_INVALID: a
+ * null pointer, an unknown mode, W or H outside 1..MI_BLUR_RESIZE_MAX_DIM. */
+int mi_blur_remap_coord(const mi_blur_remap *r, int W, int H, int32_t px, int32_t py, int *x0, int *y0, int *fx, int *fy);
+/* A map from n pairs of real positions (OpenCV's CV_32FC1 map_x, map_y): map[2i] = q(map_x[i]), map[2i+1] = q(map_y[i]),
+ * q(v) = floor(v*2048 + 0.5) in double, clamped into [-2^30, 2^30].  MI_BLUR_ERR_INVALID (map untouched): a null
+ * pointer, a value that is not finite. */
+int mi_blur_remap_from_float(const float *map_x, const float *map_y, size_t n, int32_t *map);
+/* The undistortion map of a pinhole camera with radial and tangential distortion: OpenCV's initUndistortRectifyMap with
+ * R = I.  K and new_K are {fx, fy, cx, cy} (new_K null: K); dist is {k1, k2, p1, p2, k3}.  Per output pixel (X, Y), all in
+ * double, in this order, without contraction into fused multiply-adds:
+ *   x = (X - cx') / fx'     y = (Y - cy') / fy'     r2 = x*x + y*y     rad = 1 + k1*r2 + k2*r2*r2 + k3*r2*r2*r2
+ *   xd = x*rad + 2*p1*x*y + p2*(r2 + 2*x*x)         yd = y*rad + p1*(r2 + 2*y*y) + 2*p2*x*y
+ *   u = fx*xd + cx          v = fy*yd + cy          map[Y][X] = (q(u), q(v)), q as in mi_blur_remap_from_float
+ * MI_BLUR_ERR_INVALID: a null pointer (new_K may be), out_width or out_height outside 1..MI_BLUR_RESIZE_MAX_DIM, a
+ * parameter that is not finite, fx' or fy' equal to 0 (map untouched in all of these); a position that is not finite
+ * (the map is then partly written). */
+int mi_blur_remap_undistort(const double K[4], const double dist[5], const double new_K[4], int out_width, int out_height, int32_t *map);
+/* A host-only walk of the tiles of one output image of a remap of width x height x channels images through host_map,
+ * with the kernel's own box function.  tiles->tiled: whether the launch is eligible for blur_remap_tiled_kernel by shape.
+ * If so: how many tiles stage their box in LDS, how many sample directly (box over stage_bytes), how many are empty
+ * (CONSTANT, every tap outside), and the largest boxes.  A caller picks stage_bytes with it.  MI_BLUR_ERR_INVALID: a null
+ * pointer, *r not valid for the image. */
+int mi_blur_remap_plan(const int32_t *host_map, int width, int height, int channels, const mi_blur_remap *r, mi_blur_remap_tiles *tiles);
+
+/* As mi_blur_enqueue_warp, argument for argument and status for status (MI_BLUR_ERR_INVALID before
+ * MI_BLUR_ERR_NO_DEVICE; n_images == 0 is MI_BLUR_OK).  d_map: DEVICE memory, out_height*out_width int32 pairs; null,
+ * equal to d_out, or not 4-byte aligned is MI_BLUR_ERR_INVALID.
+ * blur_remap_tiled_kernel takes the launches of the affine tiled kernel's rule (BILINEAR, 1-4 channels, width*channels
+ * and out_width*channels multiples of 16, 16-byte aligned pointers and strides) whose d_map is 16-byte aligned too.  Its
+ * tiles are the warp's (32 output rows x 64 pixels).  The host cannot know a tile's footprint, so each workgroup reduces
+ * the extrema of its map entries (kept in registers), builds the box [min x0, max x0 + 1] x [min y0, max y0 + 1], clamped
+ * into the image (CLAMP) or intersected with it (CONSTANT), and decides for its tile: an empty box stores `fill`; a box
+ * of at most stage_bytes (rows x 16-byte chunks x 16) is staged in LDS and sampled as the warp kernel samples; a larger
+ * one is sampled straight from global memory.  The launch asks for 64 + stage_bytes + 16 bytes of LDS: the default 65520
+ * admits every footprint the affine tiled kernel admits and lets two workgroups share a CU's 160 KiB; a smaller value buys
+ * occupancy and sends more tiles down the direct path (mi_blur_remap_plan counts them).  A caller who holds the map on
+ * the host should pass the plan's max_box_bytes: the smallest value that still stages every tile.  Measured
+ * (profiles/r16_remap.md): 72.7 -> 42.5 us on 4096x4096x1 and 13.9 -> 11.9 us on 1920x1080x3 under a rotation by 30
+ * degrees; one of seven measured rows got slower (35 x 256x256x3, 17.4 -> 20.3 us).  Every other launch (NEAREST,
+ * 5+ channels, odd rows or pointers, a map 4 or 8 bytes off) goes to blur_remap_generic_kernel (one output byte per
+ * thread).  mi_blur_last_kernel() says which ran. */
+int mi_blur_enqueue_remap(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int n_images,
+                          const mi_blur_remap *r, const int32_t *d_map, void *stream);
+/* The same on the CPU device's threads (synchronous); host_map is host memory. */
+int mi_blur_cpu_run_remap(const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,
+                          const mi_blur_remap *r, const int32_t *host_map, int n_threads);
+/* Give a context the remap, with the rules of mi_blur_ctx_set_warp: only before the first submit (MI_BLUR_ERR_STATE
+ * after); it replaces what another setter set and is replaced by them.  The context keeps a COPY of *r and of the map:
+ * a GPU context allocates device memory and copies synchronously inside the call (MI_BLUR_ERR_NOMEM or a HIP status when
+ * that fails), a CPU-device context keeps a host copy; the copy is freed when another setter replaces it and in
+ * mi_blur_destroy.  A setter that fails leaves the old filter and the old map in place.  mi_blur_submit writes
+ * n_images * Wo*Ho*C bytes (pageable, or pinned in place: one launch per submit, never the batch server); bytes_alg counts
+ * input + output bytes, NOT the map's 8 bytes per output pixel; mi_blur_submit_band, _bands, _planar and both resident
+ * runs return MI_BLUR_ERR_UNSUPPORTED. */
+int mi_blur_ctx_set_remap(mi_blur_ctx *ctx, const mi_blur_remap *r, const int32_t *host_map);
 
 /* ------------------------------------------------------------------------
  * Median blur, windows 3x3 to 15x15 (no reference analogue).  For a radius r in 1..MI_BLUR_MEDIAN_MAX_RADIUS, with
