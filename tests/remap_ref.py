@@ -1,9 +1,7 @@
 """The remap of include/mi_blur.h ("Remap") restated in numpy int64 from the header's text, and nothing of the product's
 -- with the box function and the tile walk of blur_remap_tiled_kernel restated (ref_box(), ref_plan()), the undistortion
-formula in numpy float64 (ref_undistort()), the maps tests/test_remap_host.py and tests/test_remap_gpu.py share (MAPS /
-build_map()) and their runners, which keep warp_ref's guards (not a test module)."""
-import ctypes as C
-
+formula in numpy float64 (ref_undistort()) and the maps tests/test_remap_host.py and tests/test_remap_gpu.py share (MAPS /
+build_map()) (not a test module; tests/resample_harness.py launches the filter)."""
 import numpy as np
 
 import warp_perspective_ref as pr
@@ -267,47 +265,5 @@ def mixed_map():
     return m
 
 
-# ---------------------------------------------------------------- runners
 def make_remap(pkg, wo, ho, mode=BILINEAR, border=CONSTANT, fill=0, stage_bytes=0):
     return pkg.Remap(wo, ho, mode, border, fill, stage_bytes)
-
-
-def gpu_remap_run(pkg, L, torch, host, fmap, mode=BILINEAR, border=CONSTANT, fill=0, stage_bytes=0, offset_in=0, offset_out=0, offset_map=0):
-    """host: N x H x W x C -> mi_blur_enqueue_remap.  warp_ref.gpu_warp_run's guards: the input offset_in bytes into a buffer
-    with 64 spare bytes, the output offset_out bytes into one with 128 bytes of 0x5A to spare, the map offset_map bytes
-    (a multiple of 4) into one with 64 spare."""
-    n, h, w, c = host.shape
-    ho, wo = fmap.shape[:2]
-    oshape = (n, ho, wo, c)
-    size_out = int(np.prod(oshape))
-    d_in = torch.zeros(host.size + 64, dtype=torch.uint8, device="cuda")
-    d_in[offset_in:offset_in + host.size] = torch.from_numpy(np.ascontiguousarray(host).reshape(-1)).cuda()
-    d_out = torch.full((size_out + 128,), 0x5A, dtype=torch.uint8, device="cuda")
-    mbytes = np.ascontiguousarray(fmap, dtype=np.int32).view(np.uint8).reshape(-1)
-    d_map = torch.zeros(mbytes.size + 64, dtype=torch.uint8, device="cuda")
-    d_map[offset_map:offset_map + mbytes.size] = torch.from_numpy(mbytes).cuda()
-    assert d_in.data_ptr() % 16 == 0 and d_out.data_ptr() % 16 == 0 and d_map.data_ptr() % 16 == 0
-    r = make_remap(pkg, wo, ho, mode, border, fill, stage_bytes)
-    rc = L.mi_blur_enqueue_remap(d_in.data_ptr() + offset_in, d_out.data_ptr() + offset_out, w, h, c, n, C.byref(r), d_map.data_ptr() + offset_map,
-                                 torch.cuda.current_stream().cuda_stream)
-    pkg.check(rc, "mi_blur_enqueue_remap")
-    torch.cuda.synchronize()
-    o = d_out.cpu().numpy()
-    assert (o[:offset_out] == 0x5A).all() and (o[offset_out + size_out:] == 0x5A).all(), "wrote outside the output"
-    return o[offset_out:offset_out + size_out].reshape(oshape)
-
-
-def cpu_remap_run(pkg, L, img, fmap, mode=BILINEAR, border=CONSTANT, fill=0, n_threads=2, guard=256):
-    """img: N x H x W x C -> mi_blur_cpu_run_remap.  The output starts as 0xA5 and the `guard` bytes before and after it must
-    still hold 0xA5."""
-    a = np.ascontiguousarray(img)
-    fm = np.ascontiguousarray(fmap, dtype=np.int32)
-    n, h, w, c = a.shape
-    ho, wo = fm.shape[:2]
-    oshape = (n, ho, wo, c)
-    size_out = int(np.prod(oshape))
-    buf = np.full(size_out + 2 * guard, 0xA5, np.uint8)
-    r = make_remap(pkg, wo, ho, mode, border, fill)
-    pkg.check(L.mi_blur_cpu_run_remap(a.ctypes.data, buf.ctypes.data + guard, w, h, c, n, C.byref(r), fm.ctypes.data, n_threads), "mi_blur_cpu_run_remap")
-    assert (buf[:guard] == 0xA5).all() and (buf[guard + size_out:] == 0xA5).all(), "wrote outside the remapped output"
-    return buf[guard:guard + size_out].reshape(oshape)

@@ -1,10 +1,6 @@
 """The image resize of include/mi_blur.h ("Image resize") restated in numpy int64 from the header's text, and nothing of
-the product's — with the runners tests/test_resize_host.py and tests/test_resize_gpu.py share (not a test module).
-The runners keep sep_down_ref's guards: the input offset into a padded buffer, the output surrounded by 0x5A (GPU) or
-prefilled with 0xA5 with a guard region after it (CPU).  takes_tiled() mirrors the eligibility rule of the header, and
-tile_geometry() restates the tiles of blur_resize_tiled_kernel for placing seams."""
-import ctypes as C
-
+the product's (not a test module; tests/resample_harness.py launches the filter).  takes_tiled() mirrors the eligibility
+rule of the header, and tile_geometry() restates the tiles of blur_resize_tiled_kernel for placing seams."""
 import numpy as np
 
 NEAREST, BILINEAR = 0, 1
@@ -79,36 +75,3 @@ def tile_geometry(wo, ho, c):
     cpr = wo * c // 16
     nstrips = -(-cpr // TILE_CHUNKS)
     return -(-cpr // nstrips), cpr, TILE_ROWS
-
-
-def gpu_resize_run(pkg, L, torch, host, wo, ho, mode=BILINEAR, offset_in=0, offset_out=0):
-    """host: N x H x W x C -> mi_blur_enqueue_resize.  The input lies offset_in bytes into a buffer with 64 spare bytes, the
-    output offset_out bytes into one with 128 bytes of 0x5A to spare: guards either side."""
-    n, h, w, c = host.shape
-    oshape = (n, ho, wo, c)
-    size_out = int(np.prod(oshape))
-    d_in = torch.zeros(host.size + 64, dtype=torch.uint8, device="cuda")
-    d_in[offset_in:offset_in + host.size] = torch.from_numpy(np.ascontiguousarray(host).reshape(-1)).cuda()
-    d_out = torch.full((size_out + 128,), 0x5A, dtype=torch.uint8, device="cuda")
-    r = pkg.Resize(wo, ho, mode)
-    rc = L.mi_blur_enqueue_resize(d_in.data_ptr() + offset_in, d_out.data_ptr() + offset_out, w, h, c, n, C.byref(r),
-                                  torch.cuda.current_stream().cuda_stream)
-    pkg.check(rc, "mi_blur_enqueue_resize")
-    torch.cuda.synchronize()
-    o = d_out.cpu().numpy()
-    assert (o[:offset_out] == 0x5A).all() and (o[offset_out + size_out:] == 0x5A).all(), "wrote outside the output"
-    return o[offset_out:offset_out + size_out].reshape(oshape)
-
-
-def cpu_resize_run(pkg, L, img, wo, ho, mode, n_threads, guard=256):
-    """img: N x H x W x C -> mi_blur_cpu_run_resize.  The output starts as 0xA5, so a byte left unwritten shows (the
-    callers' images avoid being 0xA5 everywhere), and the `guard` bytes before and after it must still hold 0xA5."""
-    a = np.ascontiguousarray(img)
-    n, h, w, c = a.shape
-    oshape = (n, ho, wo, c)
-    size_out = int(np.prod(oshape))
-    buf = np.full(size_out + 2 * guard, 0xA5, np.uint8)
-    r = pkg.Resize(wo, ho, mode)
-    pkg.check(L.mi_blur_cpu_run_resize(a.ctypes.data, buf.ctypes.data + guard, w, h, c, n, C.byref(r), n_threads), "mi_blur_cpu_run_resize")
-    assert (buf[:guard] == 0xA5).all() and (buf[guard + size_out:] == 0xA5).all(), "wrote outside the resized output"
-    return buf[guard:guard + size_out].reshape(oshape)

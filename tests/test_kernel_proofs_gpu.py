@@ -26,8 +26,8 @@ import kernel_proofs as kp
 import morph_ref as mr
 from filter_harness import (BILATERAL, CONV, MORPH, SEP, check_bands_and_grids, check_tiled_geometry_sweep, dev_run, random_bytes,  # noqa: F401
                             torch_cuda)
-from resize_ref import gpu_resize_run, ref_resize, takes_tiled
-from sep_down_ref import gpu_down_run
+import resample_harness as rh
+from resize_ref import BILINEAR, ref_resize, takes_tiled
 import warp_ref as wr
 
 pytestmark = pytest.mark.gpu
@@ -390,7 +390,7 @@ def test_sep_down_tiled_geometry_sweep(pkg, L, torch_cuda):
                 phases.add((4 if rx <= 4 else 8 if rx <= 8 else 16, ox, oy))
                 wx, wy = kp.rand_taps(rng, rx, int(rng.integers(0, 9))), kp.rand_taps(rng, ry, int(rng.integers(0, 9)))
                 img = rng.integers(0, 256, size=(1, rows, w, c), dtype=np.uint8)
-                got = gpu_down_run(pkg, L, torch_cuda, img, pkg.SepKernel.from_taps(wx, wy), (2, 2, ox, oy))
+                got = rh.gpu_run(rh.SEP_DOWN, pkg, L, torch_cuda, img, (pkg.SepKernel.from_taps(wx, wy), (2, 2, ox, oy)))
                 assert L.mi_blur_last_kernel().decode() == DOWN_TILED, (c, pairs, rows)
                 assert np.array_equal(got, kp.ref_sep(img, wx, wy)[:, oy::2, ox::2]), (c, pairs, rows, rx, ry, ox, oy)
         assert len(seen) == 24 and len(phases) == 12, c                   # every bucket-edge pair; every phase in every bucket
@@ -437,7 +437,7 @@ def test_resize_tiled_geometry_sweep(pkg, L, torch_cuda, c):
         w, wo = ci * 16 // c, co * 16 // c
         img = rng.integers(0, 256, size=(1, h, w, c), dtype=np.uint8)
         assert takes_tiled(img.shape, wo, ho), (c, ci, co, h, ho)
-        got = gpu_resize_run(pkg, L, torch_cuda, img, wo, ho)
+        got = rh.gpu_run(rh.RESIZE, pkg, L, torch_cuda, img, (wo, ho, BILINEAR))
         assert L.mi_blur_last_kernel().decode() == RESIZE_TILED, (c, ci, co, h, ho)
         assert np.array_equal(got, ref_resize(img, wo, ho)), (c, ci, co, h, ho)
     assert len(used_x) == len(xs) and len(used_y) == len(ys)
@@ -473,7 +473,7 @@ def test_warp_tiled_geometry_sweep(pkg, L, torch_cuda, c):
         for i, (m, borders) in enumerate(warp_maps()):
             for border in borders:
                 assert wr.takes_tiled(img.shape, m, wo, ho, wr.BILINEAR, border), (c, wo, ho, i, border)
-                got = wr.gpu_warp_run(pkg, L, torch_cuda, img, m, wo, ho, wr.BILINEAR, border, 201)
+                got = rh.gpu_run(rh.WARP, pkg, L, torch_cuda, img, (m, wo, ho, wr.BILINEAR, border, 201))
                 assert L.mi_blur_last_kernel().decode() == WARP_TILED, (c, wo, ho, i, border)
                 want = wr.ref_warp(img, m, wo, ho, wr.BILINEAR, border, 201)
                 assert np.array_equal(got, want), (c, wo, ho, i, border)

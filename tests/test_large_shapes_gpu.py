@@ -13,8 +13,9 @@ import pytest
 import conv_ref as cr
 from filter_harness import BILATERAL, CONV, MEDIAN, MORPH, SEP, cpu_run, gpu_run, torch_cuda  # noqa: F401
 from morph_ref import GRADIENT
-from resize_ref import BILINEAR, MAX_DIM, NEAREST, gpu_resize_run, ref_axis, ref_resize, takes_tiled
-from sep_down_ref import cpu_down_run, gpu_down_run, ref_sep_down
+import resample_harness as rh
+from resize_ref import BILINEAR, MAX_DIM, NEAREST, ref_axis, ref_resize, takes_tiled
+from sep_down_ref import ref_sep_down
 from sep_ref import rand_taps
 import warp_ref as wr
 
@@ -91,8 +92,8 @@ def test_extreme_aspect_ratios_sep_down(pkg, L, torch_cuda, extreme_images, shap
         wx, wy = rand_taps(rng, r), rand_taps(rng, r)
         k = pkg.SepKernel.from_taps(wx, wy)
         for dec in ((2, 2, 0, 0), (2, 2, 1, 1)):
-            want = ref_sep_down(img, wx, wy, *dec) if r == 2 else cpu_down_run(pkg, L, img, k, dec, CPU_THREADS)
-            got = gpu_down_run(pkg, L, torch_cuda, img.copy(), k, dec, offset_out=64)
+            want = ref_sep_down(img, wx, wy, *dec) if r == 2 else rh.cpu_run(rh.SEP_DOWN, pkg, L, img, (k, dec), CPU_THREADS)
+            got = rh.gpu_run(rh.SEP_DOWN, pkg, L, torch_cuda, img.copy(), (k, dec), offset_out=64)
             assert L.mi_blur_last_kernel().decode() == kernel, (shape, r, dec)
             assert np.array_equal(got, want), (shape, r, dec)
 
@@ -108,7 +109,7 @@ def test_extreme_aspect_ratios_resize(pkg, L, torch_cuda, case):
     assert max(shape[0], shape[1], wo, ho) == MAX_DIM
     img = np.random.default_rng(wo + ho).integers(0, 256, size=(1,) + shape, dtype=np.uint8)
     for mode in (BILINEAR, NEAREST):
-        got = gpu_resize_run(pkg, L, torch_cuda, img, wo, ho, mode, offset_out=64)
+        got = rh.gpu_run(rh.RESIZE, pkg, L, torch_cuda, img, (wo, ho, mode), offset_out=64)
         assert L.mi_blur_last_kernel().decode() == (RESIZE_TILED if takes_tiled(img.shape, wo, ho, mode, 0, 64) else RESIZE_GENERIC), (case, mode)
         assert np.array_equal(got, ref_resize(img, wo, ho, mode)), (case, mode)
     d = torch_cuda.zeros(64, dtype=torch_cuda.uint8, device="cuda")  # never touched: one past the limit on either side is refused up front
@@ -131,7 +132,7 @@ def test_extreme_aspect_ratios_warp(pkg, L, torch_cuda, case, border):
     assert wr.takes_tiled(img.shape, m, wo, ho, BILINEAR, border, 0, 64) and not wr.takes_tiled(img.shape, m, wo, ho, BILINEAR, border, 0, 7)
     want = wr.ref_warp(img, m, wo, ho, BILINEAR, border, 173)
     for mode, offset_out, kernel in ((BILINEAR, 64, WARP_TILED), (NEAREST, 64, WARP_GENERIC), (BILINEAR, 7, WARP_GENERIC)):
-        got = wr.gpu_warp_run(pkg, L, torch_cuda, img, m, wo, ho, mode, border, 173, offset_out=offset_out)
+        got = rh.gpu_run(rh.WARP, pkg, L, torch_cuda, img, (m, wo, ho, mode, border, 173), offset_out=offset_out)
         assert L.mi_blur_last_kernel().decode() == kernel, (mode, offset_out)
         assert np.array_equal(got, want if mode == BILINEAR else wr.ref_warp(img, m, wo, ho, NEAREST, border, 173)), (mode, offset_out)
         if quarter_turns is not None:

@@ -15,9 +15,9 @@ import pytest
 
 import conv_ref as cr
 from filter_harness import BILATERAL, CONV, MORPH, SEP, cpu_run, gpu_run, torch_cuda  # noqa: F401
-from sep_down_ref import cpu_down_run, gpu_down_run
+import resample_harness as rh
 from sep_ref import rand_taps
-from warp_ref import BILINEAR, CLAMP, CONSTANT, gpu_warp_run, narrow_cases, ref_warp, takes_tiled
+from warp_ref import BILINEAR, CLAMP, CONSTANT, narrow_cases, ref_warp, takes_tiled
 
 pytestmark = pytest.mark.gpu
 
@@ -84,8 +84,8 @@ def test_sep_down_rows_narrower_than_the_halo(pkg, L, torch_cuda, r):
             for ox in (0, 1):
                 for oy in (0, 1) if h > 1 else (0,):
                     dec = (2, 2, ox, oy)
-                    want = cpu_down_run(pkg, L, img, k, dec, 8)
-                    got = gpu_down_run(pkg, L, torch_cuda, img, k, dec, offset_out=64)       # 64 guard bytes either side
+                    want = rh.cpu_run(rh.SEP_DOWN, pkg, L, img, (k, dec), 8)
+                    got = rh.gpu_run(rh.SEP_DOWN, pkg, L, torch_cuda, img, (k, dec), offset_out=64)       # 64 guard bytes either side
                     assert L.mi_blur_last_kernel().decode() == "blur_sep_down_tiled_kernel", (w, c, h, dec)
                     assert np.array_equal(got, want), (w, c, h, dec)
 
@@ -96,6 +96,6 @@ def test_warp_inputs_of_one_chunk_per_row(pkg, L, torch_cuda):
     for img, name, m, wo, ho in narrow_cases():
         for border in (CLAMP, CONSTANT):
             assert takes_tiled(img.shape, m, wo, ho, BILINEAR, border), (img.shape, name, border)
-            got = gpu_warp_run(pkg, L, torch_cuda, img, m, wo, ho, BILINEAR, border, 173, offset_out=64)      # 64 guard bytes either side
+            got = rh.gpu_run(rh.WARP, pkg, L, torch_cuda, img, (m, wo, ho, BILINEAR, border, 173), offset_out=64)      # 64 guard bytes either side
             assert L.mi_blur_last_kernel().decode() == "blur_warp_tiled_kernel", (img.shape, name, border)
             assert np.array_equal(got, ref_warp(img, m, wo, ho, BILINEAR, border, 173)), (img.shape, name, border)

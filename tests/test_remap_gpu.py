@@ -2,7 +2,6 @@
 bytes against the numpy restatement of the header's definition (remap_ref.py), which of the two kernels took each launch
 against the restated eligibility rule, and, through mi_blur_remap_plan (itself checked against the restated walk in
 tests/test_remap_host.py), that the maps reach every branch of the tiled kernel: staged, direct and empty tiles."""
-import ctypes as C
 import subprocess
 
 import numpy as np
@@ -10,24 +9,16 @@ import pytest
 
 import warp_perspective_ref as pr
 import warp_ref as wr
-from filter_harness import apps, read_ppm, torch_cuda, write_ppm  # noqa: F401
-from remap_ref import (BARREL_DIST, BILINEAR, CLAMP, CONSTANT, MAPS, MIXED_OUT, MIXED_SHAPE, NEAREST, ONE, affine_map, barrel_K, barrel_map, build_map,
-                       cpu_remap_run, gpu_remap_run, identity_map, make_remap, mixed_map, perspective_map, quantise, ref_plan, ref_remap, takes_tiled, tile_geometry)
-from test_warp_gpu import TILED_SHAPES, edge_image
+from remap_ref import (BARREL_DIST, BILINEAR, CLAMP, CONSTANT, MAPS, MIXED_OUT, MIXED_SHAPE, NEAREST, affine_map, barrel_K, barrel_map, build_map,
+                       make_remap, mixed_map, perspective_map, quantise, ref_plan, ref_remap, takes_tiled)
+from resample_harness import (PERSP, REMAP, WARP, apps, blocks, check_gpu_context, check_gpu_context_enlarging, check_pointer_offsets,  # noqa: F401
+                              check_synthetic_stream, gpu_run, last, read_ppm, torch_cuda, write_ppm)
+from warp_ref import TILED_SHAPES, edge_image
 
 pytestmark = pytest.mark.gpu
 
-TILED, GENERIC = "blur_remap_tiled_kernel", "blur_remap_generic_kernel"
+TILED, GENERIC = REMAP.tiled, REMAP.generic
 BORDERS = (CLAMP, CONSTANT)
-
-
-def last(L):
-    return L.mi_blur_last_kernel().decode()
-
-
-def blocks(n, wo, ho, c):
-    ncols, cpr, rows = tile_geometry(wo, ho, c)
-    return n * -(-cpr // ncols) * -(-ho // rows)
 
 
 def plan(pkg, fmap, shape, border, stage_bytes=0):
@@ -52,7 +43,7 @@ def test_aligned_launches_take_the_tiled_kernel(pkg, L, torch_cuda, case):
                 assert p["staged"] == p["tiles"] - p["empty"] >= 8 and (border == CONSTANT or p["empty"] == 0)
             if name == "outside":
                 assert p["empty"] == (p["tiles"] if border == CONSTANT else 0)
-            got = gpu_remap_run(pkg, L, torch_cuda, img, fmap, BILINEAR, border, 173)
+            got = gpu_run(REMAP, pkg, L, torch_cuda, img, (fmap, BILINEAR, border, 173, 0))
             assert last(L) == TILED, (name, border)
             assert np.array_equal(got, ref_remap(img, fmap, BILINEAR, border, 173)), (name, border)
 
@@ -72,7 +63,7 @@ def test_a_small_stage_bytes_takes_both_branches_and_changes_no_byte(pkg, L, tor
             p = plan(pkg, fmap, shape, border, 4096)
             staged, direct = staged + p["staged"], direct + p["direct"]
             assert name != "wild" or p["direct"] == p["tiles"], (border, p)
-            got = gpu_remap_run(pkg, L, torch_cuda, img, fmap, BILINEAR, border, 173, stage_bytes=4096)
+            got = gpu_run(REMAP, pkg, L, torch_cuda, img, (fmap, BILINEAR, border, 173, 4096))
             assert last(L) == TILED, (name, border)
             assert np.array_equal(got, ref_remap(img, fmap, BILINEAR, border, 173)), (name, border)
     assert staged >= 1 and direct >= 1, (staged, direct)
@@ -85,7 +76,7 @@ def test_the_mixed_map_stages_and_samples_directly_in_one_launch(pkg, L, torch_c
     for border in BORDERS:
         p = plan(pkg, fmap, MIXED_SHAPE, border)
         assert p["direct"] >= 1 and p["staged"] >= 1 and p["max_box_bytes"] >= 128 * 1024 - 8 * 512
-        got = gpu_remap_run(pkg, L, torch_cuda, img, fmap, BILINEAR, border, 31)
+        got = gpu_run(REMAP, pkg, L, torch_cuda, img, (fmap, BILINEAR, border, 31, 0))
         assert last(L) == TILED and np.array_equal(got, ref_remap(img, fmap, BILINEAR, border, 31)), border
 
 
@@ -97,7 +88,7 @@ def test_xcd_remap_on_and_off(pkg, L, torch_cuda):
             assert (blocks(n, wo, ho, c) >= 16) == (n == 3)
             img = edge_image(rng, n, h, w, c)
             fmap = affine_map(wr.rotation_m(w, h, 33.0, 1.1), wo, ho)
-            got = gpu_remap_run(pkg, L, torch_cuda, img, fmap, BILINEAR, CONSTANT, 60)
+            got = gpu_run(REMAP, pkg, L, torch_cuda, img, (fmap, BILINEAR, CONSTANT, 60, 0))
             assert last(L) == TILED and np.array_equal(got, ref_remap(img, fmap, BILINEAR, CONSTANT, 60)), (c, n)
 
 
@@ -114,7 +105,7 @@ def test_one_tile_and_narrow_inputs(pkg, L, torch_cuda):
                     fmap = build_map(name, wi, hi, wo, ho)
                     for border in BORDERS:
                         assert takes_tiled(shape, wo, ho)
-                        got = gpu_remap_run(pkg, L, torch_cuda, img, fmap, BILINEAR, border, 99)
+                        got = gpu_run(REMAP, pkg, L, torch_cuda, img, (fmap, BILINEAR, border, 99, 0))
                         assert last(L) == TILED, (shape, wo, ho, name)
                         assert np.array_equal(got, ref_remap(img, fmap, BILINEAR, border, 99)), (shape, wo, ho, name, border)
 
@@ -131,19 +122,13 @@ def test_other_launches_take_the_generic_kernel(pkg, L, torch_cuda):
             fmap = build_map(name, w, h, wo, ho)
             for border in BORDERS:
                 assert not takes_tiled(shape, wo, ho, mode)
-                got = gpu_remap_run(pkg, L, torch_cuda, img, fmap, mode, border, 99)
+                got = gpu_run(REMAP, pkg, L, torch_cuda, img, (fmap, mode, border, 99, 0))
                 assert last(L) == GENERIC, (shape, wo, ho, mode)
                 assert np.array_equal(got, ref_remap(img, fmap, mode, border, 99)), (shape, name, wo, ho, mode, border)
-    # an aligned shape with pointers off 16 bytes, and a map 8 (and 4) bytes off: guards checked inside gpu_remap_run
+    # an aligned shape with pointers off 16 bytes, and a map 8 (and 4) bytes off: guards checked inside gpu_run
     img = edge_image(rng, 2, 35, 48, 2)
-    fmap = build_map("rot30", 48, 35, 56, 70)
-    want = ref_remap(img, fmap, BILINEAR, CONSTANT, 5)
-    assert np.array_equal(gpu_remap_run(pkg, L, torch_cuda, img, fmap, BILINEAR, CONSTANT, 5), want) and last(L) == TILED
-    for oi, oo, om in ((1, 0, 0), (0, 7, 0), (3, 5, 0), (0, 0, 8), (0, 0, 4), (7, 3, 8)):
-        assert not takes_tiled(img.shape, 56, 70, BILINEAR, oi, oo, om)
-        got = gpu_remap_run(pkg, L, torch_cuda, img, fmap, BILINEAR, CONSTANT, 5, 0, oi, oo, om)
-        assert np.array_equal(got, want), (oi, oo, om)
-        assert last(L) == GENERIC, (oi, oo, om)
+    check_pointer_offsets(REMAP, pkg, L, torch_cuda, img, (build_map("rot30", 48, 35, 56, 70), BILINEAR, CONSTANT, 5, 0),
+                          offsets=((1, 0, 0), (0, 7, 0), (3, 5, 0), (0, 0, 8), (0, 0, 4), (7, 3, 8)))
 
 
 def test_equivalences_on_the_gpu(pkg, L, torch_cuda):
@@ -155,29 +140,22 @@ def test_equivalences_on_the_gpu(pkg, L, torch_cuda):
     m = wr.rotation_m(w, h, 30.0)
     hm = pr.named_maps(w, h, wo, ho)["keystone"]
     for border in BORDERS:
-        got = gpu_remap_run(pkg, L, torch_cuda, img, affine_map(m, wo, ho), BILINEAR, border, 40)
+        got = gpu_run(REMAP, pkg, L, torch_cuda, img, (affine_map(m, wo, ho), BILINEAR, border, 40, 0))
         assert last(L) == TILED
-        assert np.array_equal(got, wr.gpu_warp_run(pkg, L, torch_cuda, img, m, wo, ho, BILINEAR, border, 40)) and last(L) == "blur_warp_tiled_kernel"
-        got = gpu_remap_run(pkg, L, torch_cuda, img, perspective_map(hm, wo, ho), BILINEAR, border, 40)
+        assert np.array_equal(got, gpu_run(WARP, pkg, L, torch_cuda, img, (m, wo, ho, BILINEAR, border, 40))) and last(L) == "blur_warp_tiled_kernel"
+        got = gpu_run(REMAP, pkg, L, torch_cuda, img, (perspective_map(hm, wo, ho), BILINEAR, border, 40, 0))
         assert last(L) == TILED
-        assert np.array_equal(got, pr.gpu_persp_run(pkg, L, torch_cuda, img, hm, wo, ho, BILINEAR, border, 40)) and last(L) == "blur_warp_persp_tiled_kernel"
+        assert np.array_equal(got, gpu_run(PERSP, pkg, L, torch_cuda, img, (hm, wo, ho, BILINEAR, border, 40))) and last(L) == "blur_warp_persp_tiled_kernel"
     img = np.random.default_rng(9).integers(0, 256, size=(2, 45, 64, 3), dtype=np.uint8)
-    got = gpu_remap_run(pkg, L, torch_cuda, img, affine_map(wr.scale_matrix(2, 1), 128, 90), BILINEAR, CLAMP)
+    got = gpu_run(REMAP, pkg, L, torch_cuda, img, (affine_map(wr.scale_matrix(2, 1), 128, 90), BILINEAR, CLAMP, 0, 0))
     assert last(L) == TILED
     assert np.array_equal(got, pkg.resize(img, (128, 90)))
     assert last(L) == "blur_resize_tiled_kernel"
 
 
 def test_gpu_equals_cpu_device_on_the_synthetic_stream(pkg, L, torch_cuda):
-    shape = (4, 240, 320, 3)
-    host = np.empty(shape, np.uint8)
-    L.mi_blur_fill_synthetic(host.ctypes.data, 320, 240, 3, 0, 4, 4)
     fmap = barrel_map(320, 240, 320, 240)
-    for mode in (BILINEAR, NEAREST):
-        want = cpu_remap_run(pkg, L, host, fmap, mode, CONSTANT, 128, 4)
-        assert np.array_equal(want, ref_remap(host, fmap, mode, CONSTANT, 128)), mode
-        assert np.array_equal(gpu_remap_run(pkg, L, torch_cuda, host, fmap, mode, CONSTANT, 128), want), mode
-        assert last(L) == (TILED if mode == BILINEAR else GENERIC)
+    check_synthetic_stream(REMAP, pkg, L, torch_cuda, [(fmap, mode, CONSTANT, 128, 0) for mode in (BILINEAR, NEAREST)])
 
 
 @pytest.mark.parametrize("target", [(160, 120), (100, 75)], ids=lambda t: "x".join(map(str, t)))
@@ -187,44 +165,9 @@ def test_gpu_context(pkg, L, torch_cuda, target):
     wo, ho = target
     img = np.random.default_rng(13).integers(0, 256, size=shape, dtype=np.uint8)
     fmap = barrel_map(w, h, wo, ho)
-    want = ref_remap(img, fmap, BILINEAR, CONSTANT, 40)
     kernel = TILED if takes_tiled(shape, wo, ho) else GENERIC
     assert (kernel == TILED) == (target == (160, 120))              # 100 x 3 bytes is no whole number of chunks
-    with pkg.Context(0, w, h, c, 1, max_batch=n, n_slots=3) as ctx:
-        mine = fmap.copy()
-        ctx.set_remap(make_remap(pkg, wo, ho, BILINEAR, CONSTANT, 40), mine)
-        mine[:] = 0x7F7F7F7F                                             # the context copied the map inside the setter
-        out = np.full(want.size + 64, 0xA5, np.uint8)
-        ctx.submit(img.ctypes.data, out.ctypes.data, n)                  # pageable
-        t = ctx.sync()
-        assert np.array_equal(out[:want.size].reshape(want.shape), want) and (out[want.size:] == 0xA5).all()
-        assert last(L) == kernel
-        assert t["bytes_alg"] == img.size + want.size                   # the map is not counted
-        cap = want.size + 4096                                           # pinned, in place, with guard bytes behind the output
-        pin_in, pin_out = L.mi_blur_host_alloc(img.size), L.mi_blur_host_alloc(cap)
-        try:
-            a = np.ctypeslib.as_array((C.c_uint8 * img.size).from_address(pin_in)).reshape(img.shape)
-            b = np.ctypeslib.as_array((C.c_uint8 * cap).from_address(pin_out))
-            a[:] = img
-            z0 = L.mi_blur_zero_copy_launches(ctx.h)
-            for _ in range(3):
-                b[:] = 0xA5
-                ctx.submit(pin_in, pin_out, n)
-                ctx.sync()
-                assert np.array_equal(b[:want.size].reshape(want.shape), want) and (b[want.size:] == 0xA5).all()
-            assert L.mi_blur_zero_copy_launches(ctx.h) == z0 + 3
-            assert last(L) == kernel
-            pitch = w * c
-            assert L.mi_blur_submit_band(ctx.h, pin_in, pin_out, 60, 2, 2) == pkg.ERR_UNSUPPORTED
-            assert L.mi_blur_submit_bands(ctx.h, pin_in, pin_out, n, h * pitch, 60, 2, 2) == pkg.ERR_UNSUPPORTED
-            assert L.mi_blur_submit_planar(ctx.h, pin_in, pin_out, n, 0) == pkg.ERR_UNSUPPORTED
-            ctx.resident_alloc(2)
-            assert L.mi_blur_resident_run(ctx.h, 2, 1, 0) == pkg.ERR_UNSUPPORTED
-            assert L.mi_blur_resident_run_fused(ctx.h, 2, 1, 0) == pkg.ERR_UNSUPPORTED
-            assert L.mi_blur_ctx_set_remap(ctx.h, C.byref(make_remap(pkg, wo, ho)), fmap.ctypes.data) == pkg.ERR_STATE
-        finally:
-            L.mi_blur_host_free(pin_in)
-            L.mi_blur_host_free(pin_out)
+    check_gpu_context(REMAP, pkg, L, img, (fmap, BILINEAR, CONSTANT, 40, 0), kernel)
 
 
 def test_gpu_context_enlarging(pkg, L, torch_cuda):
@@ -234,33 +177,7 @@ def test_gpu_context_enlarging(pkg, L, torch_cuda):
     wo, ho = 320, 240
     img = np.random.default_rng(14).integers(0, 256, size=shape, dtype=np.uint8)
     fmap = barrel_map(w, h, wo, ho)
-    want = ref_remap(img, fmap, BILINEAR, CONSTANT, 40)
-    assert want.size == 4 * img.size and takes_tiled(shape, wo, ho)
-    assert (want != 40).mean() > 0.5                                     # mostly image, not fill
-    with pkg.Context(0, w, h, c, 1, max_batch=n, n_slots=3) as ctx:
-        ctx.set_remap(make_remap(pkg, wo, ho, BILINEAR, CONSTANT, 40), fmap)
-        cap = want.size + 4096                                           # guard bytes behind the output, pageable and pinned
-        out = np.full(cap, 0xA5, np.uint8)
-        ctx.submit(img.ctypes.data, out.ctypes.data, n)                  # pageable
-        t = ctx.sync()
-        assert np.array_equal(out[:want.size].reshape(want.shape), want) and (out[want.size:] == 0xA5).all()
-        assert last(L) == TILED
-        assert t["bytes_alg"] == img.size + want.size
-        pin_in, pin_out = L.mi_blur_host_alloc(img.size), L.mi_blur_host_alloc(cap)
-        try:
-            a = np.ctypeslib.as_array((C.c_uint8 * img.size).from_address(pin_in)).reshape(img.shape)
-            b = np.ctypeslib.as_array((C.c_uint8 * cap).from_address(pin_out))
-            a[:] = img
-            for k in range(3):
-                b[:] = 0xA5
-                ctx.submit(pin_in, pin_out, n)
-                t = ctx.sync()
-                assert np.array_equal(b[:want.size].reshape(want.shape), want) and (b[want.size:] == 0xA5).all()
-                assert t["bytes_alg"] == (k + 2) * (img.size + want.size)   # cumulative since the context was made
-            assert last(L) == TILED
-        finally:
-            L.mi_blur_host_free(pin_in)
-            L.mi_blur_host_free(pin_out)
+    check_gpu_context_enlarging(REMAP, pkg, L, img, (fmap, BILINEAR, CONSTANT, 40, 0), fill=40)
 
 
 def test_two_contexts_keep_their_own_maps(pkg, L, torch_cuda):

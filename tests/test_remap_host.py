@@ -5,8 +5,6 @@ the product, and against the two oracles already in the tree: every affine and p
 came from mi_blur_warp_coord / mi_blur_warp_perspective_coord.  All comparisons are exact unless stated."""
 import ctypes as C
 import os
-import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -14,13 +12,14 @@ import pytest
 
 import warp_perspective_ref as pr
 import warp_ref as wr
-from filter_harness import MEDIAN, cpu_run
-from remap_ref import (BARREL_DIST, BILINEAR, CLAMP, CONSTANT, I32_MAX, I32_MIN, MAX_DIM, MIXED_OUT, MIXED_SHAPE, NEAREST, ONE, QUANT_LIMIT, STAGE_MAX,
-                       abi_affine_map, abi_perspective_map, affine_map, barrel_K, build_map, cpu_remap_run, extreme_entries, float_remap, identity_map,
+from filter_harness import MEDIAN, cpu_run as cpu_run_same_size
+from remap_ref import (BARREL_DIST, BILINEAR, CLAMP, CONSTANT, I32_MAX, I32_MIN, MAX_DIM, MIXED_SHAPE, NEAREST, ONE, QUANT_LIMIT, STAGE_MAX,
+                       abi_affine_map, abi_perspective_map, affine_map, barrel_K, build_map, extreme_entries, float_remap, identity_map,
                        make_remap, mixed_map, quantise, ref_coord, ref_plan, ref_remap, ref_undistort, ref_undistort_real)
+from resample_harness import (PERSP, REMAP, WARP, check_cpu_context, check_cpu_run_refuses, check_ctx_set_refuses, check_enqueue_invalid_before_no_device,
+                              check_setters_replace_each_other, cpu_run, needs_gxx, no_scratch, run_sanitized, sampler_rows, size_rows)
 from resize_ref import ref_resize
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MODES = (BILINEAR, NEAREST)
 BORDERS = (CLAMP, CONSTANT)
 
@@ -32,7 +31,7 @@ def wild(rng, w, h, wo, ho):
 @pytest.mark.parametrize("c", [1, 2, 3, 5])
 def test_cpu_device_equals_the_restatement(pkg, L, c):
     """Both modes, both borders, one and three images, odd shapes, a 1 x 1 input and a 1 x 1 output; the guard bytes either
-    side of the output are checked inside cpu_remap_run."""
+    side of the output are checked inside cpu_run."""
     rng = np.random.default_rng(40 + c)
     for (h, w), (wo, ho) in (((17, 33), (48, 29)), ((1, 1), (9, 7)), ((17, 33), (1, 1))):
         for n in (1, 3):
@@ -40,7 +39,7 @@ def test_cpu_device_equals_the_restatement(pkg, L, c):
             for fmap in (wild(rng, w, h, wo, ho), build_map("barrel", w, h, wo, ho), build_map("extremes", w, h, wo, ho)):
                 for mode in MODES:
                     for border in BORDERS:
-                        got = cpu_remap_run(pkg, L, img, fmap, mode, border, 201, n_threads=3)
+                        got = cpu_run(REMAP, pkg, L, img, (fmap, mode, border, 201, 0), 3)
                         assert np.array_equal(got, ref_remap(img, fmap, mode, border, 201)), (h, w, wo, ho, n, mode, border)
 
 
@@ -48,7 +47,7 @@ def test_the_identity_map(pkg, L):
     img = np.random.default_rng(2).integers(0, 256, size=(2, 13, 17, 3), dtype=np.uint8)
     for mode in MODES:
         for border in BORDERS:
-            assert np.array_equal(cpu_remap_run(pkg, L, img, identity_map(17, 13), mode, border, 7), img)
+            assert np.array_equal(cpu_run(REMAP, pkg, L, img, (identity_map(17, 13), mode, border, 7, 0), 2), img)
 
 
 def far_right(w):
@@ -66,8 +65,8 @@ def test_maps_from_warp_coord_give_the_warp(pkg, L, name):
     fmap = abi_affine_map(pkg, L, m, wo, ho)
     assert np.array_equal(fmap, affine_map(m, wo, ho))                      # the numpy builder the GPU tests use is the same map
     for border in BORDERS:
-        want = wr.cpu_warp_run(pkg, L, img, m, wo, ho, BILINEAR, border, 99)
-        assert np.array_equal(cpu_remap_run(pkg, L, img, fmap, BILINEAR, border, 99), want), border
+        want = cpu_run(WARP, pkg, L, img, (m, wo, ho, BILINEAR, border, 99), 2)
+        assert np.array_equal(cpu_run(REMAP, pkg, L, img, (fmap, BILINEAR, border, 99, 0), 2), want), border
         assert np.array_equal(ref_remap(img, fmap, BILINEAR, border, 99), want), border
 
 
@@ -78,8 +77,8 @@ def test_a_map_from_warp_perspective_coord_gives_the_perspective_warp(pkg, L):
     hm = pr.named_maps(w, h, wo, ho)["keystone"]
     fmap = abi_perspective_map(pkg, L, hm, wo, ho)
     for border in BORDERS:
-        want = pr.cpu_persp_run(pkg, L, img, hm, wo, ho, BILINEAR, border, 99)
-        assert np.array_equal(cpu_remap_run(pkg, L, img, fmap, BILINEAR, border, 99), want), border
+        want = cpu_run(PERSP, pkg, L, img, (hm, wo, ho, BILINEAR, border, 99), 2)
+        assert np.array_equal(cpu_run(REMAP, pkg, L, img, (fmap, BILINEAR, border, 99, 0), 2), want), border
 
 
 @pytest.mark.parametrize("ratio", [(2, 1), (4, 1), (1, 2), (1, 4), (1, 8)], ids=lambda r: f"{r[0]}over{r[1]}")
@@ -89,7 +88,7 @@ def test_clamp_scale_maps_give_the_resize(pkg, L, ratio):
     wo, ho = 40 * num // den, 24 * num // den
     fmap = affine_map(wr.scale_matrix(num, den), wo, ho)
     want = ref_resize(img, wo, ho)
-    assert np.array_equal(cpu_remap_run(pkg, L, img, fmap, BILINEAR, CLAMP), want)
+    assert np.array_equal(cpu_run(REMAP, pkg, L, img, (fmap, BILINEAR, CLAMP, 0, 0), 2), want)
     if ratio == (2, 1):
         assert np.array_equal(pkg.resize(img, (wo, ho), device=pkg.DEVICE_CPU), want)
 
@@ -112,8 +111,8 @@ def test_extreme_entries_give_the_nearest_position_in_range(pkg, L):
     assert (raw != near).sum() == 16
     for mode in MODES:
         for border in BORDERS:
-            got = cpu_remap_run(pkg, L, img, raw, mode, border, 44)
-            assert np.array_equal(got, cpu_remap_run(pkg, L, img, near, mode, border, 44)), (mode, border)
+            got = cpu_run(REMAP, pkg, L, img, (raw, mode, border, 44, 0), 2)
+            assert np.array_equal(got, cpu_run(REMAP, pkg, L, img, (near, mode, border, 44, 0), 2)), (mode, border)
             assert np.array_equal(got, ref_remap(img, raw, mode, border, 44)), (mode, border)
 
 
@@ -218,7 +217,7 @@ def test_bilinear_is_within_the_bound_of_float_bilinear(pkg, L, border):
     u, v = ref_undistort_real(K, BARREL_DIST, (w, h))
     fmap = pkg.undistort_map(K, BARREL_DIST, (w, h))
     real = float_remap(img, u, v, border, 90)
-    got = cpu_remap_run(pkg, L, img, fmap, BILINEAR, border, 90).astype(np.float64)
+    got = cpu_run(REMAP, pkg, L, img, (fmap, BILINEAR, border, 90, 0), 2).astype(np.float64)
     err = np.abs(got - real).max()
     print("remap against float64 bilinear at the real positions: max error", err)
     assert err < 0.5 + 255 * 2.0 ** -11
@@ -259,75 +258,44 @@ def test_plan_equals_the_restated_walk(pkg, L):
 
 
 # ---------------------------------------------------------------- statuses
-def bad_calls(pkg, call):
-    """call(in, out, w, h, c, remap or None, map) for every invalid argument: all ERR_INVALID.  Returns two good buffers, a
-    good struct and a good map."""
-    a = np.random.default_rng(1).integers(0, 256, size=(8, 8, 3), dtype=np.uint8)
-    b = np.zeros((16, 16, 3), np.uint8)
-    fmap = identity_map(16, 16)
-    mk = lambda wo=16, ho=16, mode=BILINEAR, border=CONSTANT, fill=0, stage=0: make_remap(pkg, wo, ho, mode, border, fill, stage)
-    good = mk()
-    ref = lambda s: None if s is None else C.byref(s)
-    ia, ib, im = a.ctypes.data, b.ctypes.data, fmap.ctypes.data
-    bad = [(ia, ib, 8, 8, 3, None, im), (None, ib, 8, 8, 3, good, im), (ia, None, 8, 8, 3, good, im), (ia, ia, 8, 8, 3, good, im),
-           (ia, ib, 8, 8, 3, good, None), (ia, ib, 8, 8, 3, good, ib), (ia, ib, 8, 8, 3, good, im + 1), (ia, ib, 8, 8, 3, good, im + 2)]
-    for kw in [dict(wo=0), dict(ho=0), dict(wo=-3), dict(ho=-1), dict(wo=MAX_DIM + 1, ho=1), dict(wo=1, ho=MAX_DIM + 1), dict(mode=2), dict(mode=-1),
-               dict(border=2), dict(border=-1), dict(fill=-1), dict(fill=256), dict(stage=8), dict(stage=15), dict(stage=65521), dict(stage=-16)]:
-        bad.append((ia, ib, 8, 8, 3, mk(**kw), im))
-    for w, h, c in [(0, 8, 3), (8, 0, 3), (8, 8, 0), (-1, 8, 3), (MAX_DIM + 1, 1, 1), (1, MAX_DIM + 1, 1)]:
-        bad.append((ia, ib, w, h, c, good, im))
-    bad.append((ia, ib, 8, 8, 3, mk(MAX_DIM, MAX_DIM), im))                 # the output image: 3 GiB, over the per-image limit
-    bad.append((ia, ib, 8, 8, 40000, mk(MAX_DIM, 1), im))                   # the output row: over INT_MAX / 2
-    for i, o, w, h, c, r, m in bad:
-        assert call(i, o, w, h, c, ref(r), m) == pkg.ERR_INVALID, (i, o, w, h, c, r and (r.out_width, r.out_height, r.mode, r.border, r.fill, r.stage_bytes), m)
-    return a, b, good, fmap
+def mk(pkg, wo=16, ho=16, mode=BILINEAR, border=CONSTANT, fill=0, stage=0):
+    return make_remap(pkg, wo, ho, mode, border, fill, stage)
+
+
+def bad_rows(pkg, fmap):
+    """(good, rows) for resample_harness.bad_calls with the map fmap; the remap's own rows: a map that is the output buffer
+    (so the rows are a function of its address) or is not aligned to its entries, and stage_bytes outside 16..65520."""
+    im = fmap.ctypes.data
+    make = lambda **kw: mk(pkg, **kw)
+    good = (C.byref(mk(pkg)), im)
+
+    def rows(out):
+        own = [(8, 8, 3, (good[0], m)) for m in (out, im + 1, im + 2)]
+        own += [(8, 8, 3, (C.byref(mk(pkg, stage=st)), im)) for st in (8, 15, 65521, -16)]
+        return size_rows(make, (im,)) + sampler_rows(make, (im,)) + own
+    return good, rows
 
 
 def test_cpu_run_refuses_invalid_arguments(pkg, L):
-    a, b, r, fmap = bad_calls(pkg, lambda i, o, w, h, c, r, m: L.mi_blur_cpu_run_remap(i, o, w, h, c, 1, r, m, 1))
-    run = lambda n, rr=r: L.mi_blur_cpu_run_remap(a.ctypes.data, b.ctypes.data, 8, 8, 3, n, C.byref(rr), fmap.ctypes.data, 1)
-    assert run(-1) == pkg.ERR_INVALID
-    assert run(1) == pkg.OK and run(0) == pkg.OK
+    fmap = identity_map(16, 16)
+    a, b = check_cpu_run_refuses(REMAP, pkg, L, *bad_rows(pkg, fmap))
     for stage in (16, 4096, STAGE_MAX):
-        assert run(1, make_remap(pkg, 16, 16, stage_bytes=stage)) == pkg.OK
+        assert L.mi_blur_cpu_run_remap(a.ctypes.data, b.ctypes.data, 8, 8, 3, 1, C.byref(mk(pkg, stage=stage)), fmap.ctypes.data, 1) == pkg.OK
 
 
 def test_enqueue_invalid_comes_before_no_device(pkg, L):
     """Every argument is checked before a device is asked for; without a GPU a good call is ERR_NO_DEVICE (with one, the
     null stream of an empty batch is MI_BLUR_OK)."""
-    a, b, r, fmap = bad_calls(pkg, lambda i, o, w, h, c, r, m: L.mi_blur_enqueue_remap(i, o, w, h, c, 1, r, m, None))
-    run = lambda n: L.mi_blur_enqueue_remap(a.ctypes.data, b.ctypes.data, 8, 8, 3, n, C.byref(r), fmap.ctypes.data, None)
-    assert run(-1) == pkg.ERR_INVALID
-    if L.mi_blur_device_count() <= 0:
-        assert run(1) == pkg.ERR_NO_DEVICE and run(0) == pkg.ERR_NO_DEVICE
-    else:
-        assert run(0) == pkg.OK
+    check_enqueue_invalid_before_no_device(REMAP, pkg, L, *bad_rows(pkg, identity_map(16, 16)))
 
 
 def test_ctx_set_refuses_invalid_arguments(pkg, L):
     """A null context, struct or map is ERR_INVALID whatever the state, an invalid struct ERR_INVALID before the first
     submit, anything ERR_STATE after it; a refused set leaves the filter in place."""
-    mk = lambda wo=16, ho=16, mode=BILINEAR, border=CONSTANT, fill=0, stage=0: make_remap(pkg, wo, ho, mode, border, fill, stage)
     fmap = identity_map(16, 16)
-    im = fmap.ctypes.data
-    with pkg.Context(pkg.DEVICE_CPU, 8, 8, 3, 1, max_batch=1) as ctx:
-        assert L.mi_blur_ctx_set_remap(None, C.byref(mk()), im) == pkg.ERR_INVALID
-        assert L.mi_blur_ctx_set_remap(ctx.h, None, im) == pkg.ERR_INVALID
-        assert L.mi_blur_ctx_set_remap(ctx.h, C.byref(mk()), None) == pkg.ERR_INVALID
-        for bad in [mk(wo=0), mk(ho=0), mk(MAX_DIM + 1, 1), mk(1, MAX_DIM + 1), mk(mode=2), mk(border=2), mk(fill=256), mk(fill=-1), mk(stage=8), mk(stage=65521),
-                    mk(MAX_DIM, MAX_DIM)]:
-            assert L.mi_blur_ctx_set_remap(ctx.h, C.byref(bad), im) == pkg.ERR_INVALID
-        img = np.random.default_rng(2).integers(0, 256, size=(1, 8, 8, 3), dtype=np.uint8)   # refused sets leave the box blur in place
-        out, box = np.empty_like(img), np.empty_like(img)
-        ctx.submit(img.ctypes.data, out.ctypes.data, 1)
-        t = ctx.sync()
-        assert L.mi_blur_cpu_run(img.ctypes.data, box.ctypes.data, 8, 8, 3, 1, 1, 1) == pkg.OK
-        assert np.array_equal(out, box) and t["bytes_alg"] == 2 * img.size
-        assert L.mi_blur_ctx_set_remap(ctx.h, C.byref(mk()), im) == pkg.ERR_STATE
-        assert L.mi_blur_ctx_set_remap(ctx.h, C.byref(mk(wo=0)), im) == pkg.ERR_STATE
-        assert L.mi_blur_ctx_set_remap(ctx.h, None, im) == pkg.ERR_INVALID
-    with pkg.Context(pkg.DEVICE_CPU, MAX_DIM + 1, 2, 1, 1, max_batch=1) as wide:      # the context's own size over MAX_DIM
-        assert L.mi_blur_ctx_set_remap(wide.h, C.byref(mk()), im) == pkg.ERR_INVALID
+    bad = [dict(wo=0), dict(ho=0), dict(wo=MAX_DIM + 1, ho=1), dict(wo=1, ho=MAX_DIM + 1), dict(mode=2), dict(border=2), dict(fill=256), dict(fill=-1), dict(stage=8),
+           dict(stage=65521), dict(wo=MAX_DIM, ho=MAX_DIM)]
+    check_ctx_set_refuses(REMAP, pkg, L, (C.byref(mk(pkg)), fmap.ctypes.data), [(C.byref(mk(pkg, **kw)), fmap.ctypes.data) for kw in bad])
 
 
 def test_a_failed_setter_keeps_the_previous_remap_working(pkg, L):
@@ -356,27 +324,7 @@ def test_cpu_context(pkg, L, target):
     fmap = build_map("barrel", w, h, wo, ho)
     for mode in MODES:
         for border in BORDERS:
-            want = ref_remap(img, fmap, mode, border, 33)
-            with pkg.Context(pkg.DEVICE_CPU, w, h, c, 1, max_batch=n, n_threads=3) as ctx:
-                r, mine = make_remap(pkg, wo, ho, mode, border, 33), fmap.copy()
-                assert L.mi_blur_ctx_set_remap(ctx.h, C.byref(r), mine.ctypes.data) == pkg.OK
-                C.memset(C.byref(r), 0xFF, C.sizeof(r))                      # the context keeps a copy of the struct and of the map
-                mine[:] = 0x7F7F7F7F
-                out = np.full(want.size + 128, 0xA5, np.uint8)
-                ctx.submit(img.ctypes.data, out.ctypes.data + 64, n)         # pageable memory, guards either side
-                t = ctx.sync()
-                assert np.array_equal(out[64:64 + want.size].reshape(want.shape), want)
-                assert (out[:64] == 0xA5).all() and (out[64 + want.size:] == 0xA5).all()
-                assert t["bytes_alg"] == img.size + want.size and t["images"] == n          # the map's bytes are not counted
-                pitch = w * c
-                o = np.zeros_like(img)
-                assert L.mi_blur_submit_band(ctx.h, img.ctypes.data, o.ctypes.data, 20, 2, 2) == pkg.ERR_UNSUPPORTED
-                assert L.mi_blur_submit_bands(ctx.h, img.ctypes.data, o.ctypes.data, n, h * pitch, 20, 2, 2) == pkg.ERR_UNSUPPORTED
-                assert L.mi_blur_submit_planar(ctx.h, img.ctypes.data, o.ctypes.data, n, 0) == pkg.ERR_UNSUPPORTED
-                assert L.mi_blur_resident_run(ctx.h, 1, 1, 0) == pkg.ERR_UNSUPPORTED
-                assert L.mi_blur_resident_run_fused(ctx.h, 1, 1, 0) == pkg.ERR_UNSUPPORTED
-                assert not o.any()
-                assert L.mi_blur_ctx_set_remap(ctx.h, C.byref(make_remap(pkg, wo, ho, mode, border, 33)), fmap.ctypes.data) == pkg.ERR_STATE
+            check_cpu_context(REMAP, pkg, L, img, (fmap, mode, border, 33, 0))
 
 
 def test_setters_replace_each_other(pkg, L):
@@ -386,27 +334,14 @@ def test_setters_replace_each_other(pkg, L):
     rng = np.random.default_rng(30)
     map_a, map_b = wild(rng, w, h, 40, 31), wild(rng, w, h, 17, 9)
 
-    def run(setters, want):
-        with pkg.Context(pkg.DEVICE_CPU, w, h, c, 1, max_batch=n) as ctx:
-            for s in setters:
-                s(ctx)
-            out = np.full(want.size + 64, 0xA5, np.uint8)
-            ctx.submit(img.ctypes.data, out.ctypes.data, n)
-            t = ctx.sync()
-            assert np.array_equal(out[:want.size].reshape(want.shape), want) and (out[want.size:] == 0xA5).all()
-            return t
     remap_a = lambda ctx: ctx.set_remap(make_remap(pkg, 40, 31, BILINEAR, CLAMP), map_a)
     remap_b = lambda ctx: ctx.set_remap(make_remap(pkg, 17, 9, NEAREST, CONSTANT, 5), map_b)
     warp = lambda ctx: ctx.set_warp(wr.make_warp(pkg, m, 40, 31, BILINEAR, CLAMP))
     median = lambda ctx: ctx.set_median(1)
     ra, rb = ref_remap(img, map_a, BILINEAR, CLAMP), ref_remap(img, map_b, NEAREST, CONSTANT, 5)
-    rot, med = wr.ref_warp(img, m, 40, 31, BILINEAR, CLAMP), cpu_run(MEDIAN, pkg, L, img, 1, 1)
-    assert run([remap_a, warp], rot)["bytes_alg"] == img.size + rot.size         # the last one wins
-    assert run([warp, remap_a], ra)["bytes_alg"] == img.size + ra.size
-    assert run([remap_a, median], med)["bytes_alg"] == 2 * img.size
-    assert run([median, remap_b], rb)["bytes_alg"] == img.size + rb.size
-    assert run([remap_a, remap_b], rb)["bytes_alg"] == img.size + rb.size        # a remap replaces a remap: the first map is freed
-    assert run([remap_b, remap_a, remap_b, remap_a], ra)["bytes_alg"] == img.size + ra.size
+    rot, med = wr.ref_warp(img, m, 40, 31, BILINEAR, CLAMP), cpu_run_same_size(MEDIAN, pkg, L, img, 1, 1)
+    check_setters_replace_each_other(pkg, L, img, [([remap_a, warp], rot), ([warp, remap_a], ra), ([remap_a, median], med), ([median, remap_b], rb),      # the last one wins
+                                                   ([remap_a, remap_b], rb), ([remap_b, remap_a, remap_b, remap_a], ra)])   # a remap replaces a remap: the first map is freed
 
 
 def test_numpy_functions_on_the_cpu_device(pkg, L):
@@ -463,7 +398,7 @@ def test_hosts_refuse_undistort_with_other_filters(pkg, tmp_path):
 
 
 def test_host_undistorts_on_the_cpu_device(pkg, tmp_path):
-    from filter_harness import read_ppm, write_ppm
+    from resample_harness import read_ppm, write_ppm
     pkg.build_native()
     het = os.path.join(pkg.APPS, "heterogeneous_blur")
     img = np.random.default_rng(19).integers(0, 256, size=(48, 64, 3), dtype=np.uint8)
@@ -483,27 +418,11 @@ def test_host_undistorts_on_the_cpu_device(pkg, tmp_path):
 def test_tiled_kernels_use_no_scratch(pkg, tmp_path):
     """Compiles remap_kernels.hip to gfx950 assembly (no GPU needed): the map entries stay in registers, so no tiled
     instantiation may spill or index registers at run time; all LDS is dynamic."""
-    out = tmp_path / "k.s"
-    r = subprocess.run([pkg.HIPCC, f"--offload-arch={pkg.ARCH}", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-o", str(out),
-                        os.path.join(pkg.CSRC, "remap_kernels.hip")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    text = out.read_text()
-    kernels = re.findall(r"\.amdhsa_kernel (\S*blur_remap_tiled_kernel\S*)(.*?)\.end_amdhsa_kernel", text, re.S)
-    assert len(kernels) == 4, [k for k, _ in kernels]                        # 1-4 channels
-    for name, body in kernels:
-        assert re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", body).group(1) == "0", name
-        assert re.search(r"\.amdhsa_group_segment_fixed_size (\d+)", body).group(1) == "0", name
+    no_scratch(pkg, tmp_path, "remap_kernels.hip", "blur_remap_tiled_kernel", 4, dynamic_lds_only=True)     # 1-4 channels
 
 
-@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
+@needs_gxx
 def test_cpu_remap_and_the_tile_walk_clean_under_asan_ubsan(pkg, tmp_path):
     """tests/san_remap.cpp: the CPU device in exact-size heap buffers on random, extreme and the GPU tests' maps, and every
     LDS offset a staged tile of the mixed, rot30 and wild maps would read, against stage_bytes + WARP_LDS_SLACK."""
-    exe = tmp_path / "san_remap"
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           "-fno-omit-frame-pointer", "-I", pkg.CSRC, os.path.join(ROOT, "tests", "san_remap.cpp"),
-           os.path.join(pkg.CSRC, "cpu_device.cpp"), "-lpthread", "-o", str(exe)]
-    subprocess.run(cmd, check=True, capture_output=True)
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "remap cases clean" in r.stdout and "taps inside their LDS" in r.stdout and "FAILED" not in r.stdout, r.stdout + r.stderr
-    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr
+    run_sanitized(pkg, tmp_path, ("san_remap.cpp", "cpu_device.cpp"), ["remap cases clean", "taps inside their LDS"])

@@ -1,27 +1,18 @@
 """The image resize on the GPU (mi_blur_enqueue_resize, mi_blur_ctx_set_resize, resize(), the hosts' --resize): exact bytes
 against the numpy restatement of the header's definition (resize_ref.py), and which of the two kernels took each launch."""
-import ctypes as C
 import subprocess
 
 import numpy as np
 import pytest
 
-from filter_harness import apps, read_ppm, torch_cuda, write_ppm  # noqa: F401
-from resize_ref import BILINEAR, NEAREST, cpu_resize_run, gpu_resize_run, ref_axis, ref_resize, takes_tiled, tile_geometry
+from resample_harness import (RESIZE, apps, check_gpu_context, check_pointer_offsets, check_synthetic_stream, gpu_run, last, pinned, read_ppm,  # noqa: F401
+                              spans_tiles, torch_cuda, write_ppm)
+from resize_ref import BILINEAR, NEAREST, ref_axis, ref_resize, takes_tiled, tile_geometry
 
 pytestmark = pytest.mark.gpu
 
-TILED, GENERIC = "blur_resize_tiled_kernel", "blur_resize_generic_kernel"
+TILED, GENERIC = RESIZE.tiled, RESIZE.generic
 MODES = (BILINEAR, NEAREST)
-
-
-def last(L):
-    return L.mi_blur_last_kernel().decode()
-
-
-def spans_tiles(wo, ho, c):
-    ncols, cpr, rows = tile_geometry(wo, ho, c)
-    return cpr > ncols and ho > rows
 
 
 @pytest.mark.parametrize("case", [((2, 33, 32, 1), 64, 66, False), ((1, 33, 48, 3), 96, 67, False), ((2, 35, 48, 2), 56, 35, False),
@@ -31,9 +22,9 @@ def spans_tiles(wo, ho, c):
 def test_aligned_enlargements_take_the_tiled_kernel(pkg, L, torch_cuda, case):
     """Both axes, x only, y only, a large ratio, the same size; the last three span more than one tile both ways."""
     shape, wo, ho, many_tiles = case
-    assert takes_tiled(shape, wo, ho) and spans_tiles(wo, ho, shape[3]) == many_tiles
+    assert takes_tiled(shape, wo, ho) and spans_tiles(wo, ho, shape[3], tile_geometry) == many_tiles
     img = np.random.default_rng(sum(shape) + wo).integers(0, 256, size=shape, dtype=np.uint8)
-    got = gpu_resize_run(pkg, L, torch_cuda, img, wo, ho)
+    got = gpu_run(RESIZE, pkg, L, torch_cuda, img, (wo, ho, BILINEAR))
     assert last(L) == TILED, case
     assert np.array_equal(got, ref_resize(img, wo, ho)), case
     if (wo, ho) == (shape[2], shape[1]):
@@ -79,7 +70,7 @@ def test_tile_seams(pkg, L, torch_cuda, case):
     assert ho > trows and (cpr > ncols or (w, c, wo) == (176, 1, 400))   # more than one tile both ways (176 -> 400 x 1 channel: 25 chunks, rows only)
     img = seam_images(np.random.default_rng(7), h, w, c, wo, ho)
     assert takes_tiled(img.shape, wo, ho)
-    got = gpu_resize_run(pkg, L, torch_cuda, img, wo, ho)
+    got = gpu_run(RESIZE, pkg, L, torch_cuda, img, (wo, ho, BILINEAR))
     assert last(L) == TILED
     assert (got[2] == 255).all(), case
     assert np.array_equal(got, ref_resize(img, wo, ho)), case
@@ -93,16 +84,11 @@ def test_other_launches_take_the_generic_kernel(pkg, L, torch_cuda):
         img = rng.integers(0, 256, size=shape, dtype=np.uint8)
         for mode in MODES:
             assert not takes_tiled(shape, wo, ho, mode)
-            got = gpu_resize_run(pkg, L, torch_cuda, img, wo, ho, mode)
+            got = gpu_run(RESIZE, pkg, L, torch_cuda, img, (wo, ho, mode))
             assert last(L) == GENERIC, (shape, wo, ho, mode)
             assert np.array_equal(got, ref_resize(img, wo, ho, mode)), (shape, wo, ho, mode)
     img = rng.integers(0, 256, size=(2, 35, 48, 2), dtype=np.uint8)              # aligned shape, pointers off 16 bytes
-    want = ref_resize(img, 112, 70)
-    assert np.array_equal(gpu_resize_run(pkg, L, torch_cuda, img, 112, 70), want) and last(L) == TILED
-    for oi, oo in ((1, 0), (0, 7), (3, 5)):
-        assert not takes_tiled(img.shape, 112, 70, BILINEAR, oi, oo)
-        assert np.array_equal(gpu_resize_run(pkg, L, torch_cuda, img, 112, 70, BILINEAR, oi, oo), want), (oi, oo)    # guards checked inside
-        assert last(L) == GENERIC, (oi, oo)
+    check_pointer_offsets(RESIZE, pkg, L, torch_cuda, img, (112, 70, BILINEAR))
 
 
 def test_reductions_and_nearest(pkg, L, torch_cuda):
@@ -113,24 +99,16 @@ def test_reductions_and_nearest(pkg, L, torch_cuda):
         img = rng.integers(0, 256, size=shape, dtype=np.uint8)
         for wo, ho in ((w, h), (2 * w, 2 * h), (w // 2, h // 2), (w * 2 // 3 // 16 * 16 + 16, h), (w, h - 1), (2 * w, h // 2), (w // 4, 3 * h), (3 * w, 3 * h), (1, 1)):
             for mode in MODES:
-                got = gpu_resize_run(pkg, L, torch_cuda, img, wo, ho, mode)
+                got = gpu_run(RESIZE, pkg, L, torch_cuda, img, (wo, ho, mode))
                 assert last(L) == (TILED if takes_tiled(shape, wo, ho, mode) else GENERIC), (shape, wo, ho, mode)
                 assert np.array_equal(got, ref_resize(img, wo, ho, mode)), (shape, wo, ho, mode)
     img = rng.integers(0, 256, size=(1, 20, 32, 1), dtype=np.uint8)
     for k in (2, 3):
-        assert np.array_equal(gpu_resize_run(pkg, L, torch_cuda, img, 32 * k, 20 * k, NEAREST), np.repeat(np.repeat(img, k, axis=1), k, axis=2))
+        assert np.array_equal(gpu_run(RESIZE, pkg, L, torch_cuda, img, (32 * k, 20 * k, NEAREST)), np.repeat(np.repeat(img, k, axis=1), k, axis=2))
 
 
 def test_gpu_equals_cpu_device_on_the_synthetic_stream(pkg, L, torch_cuda):
-    shape = (4, 240, 320, 3)
-    host = np.empty(shape, np.uint8)
-    L.mi_blur_fill_synthetic(host.ctypes.data, 320, 240, 3, 0, 4, 4)
-    for wo, ho in ((640, 480), (427, 320), (200, 150)):
-        for mode in MODES:
-            want = cpu_resize_run(pkg, L, host, wo, ho, mode, 4)
-            assert np.array_equal(want, ref_resize(host, wo, ho, mode)), (wo, ho, mode)
-            assert np.array_equal(gpu_resize_run(pkg, L, torch_cuda, host, wo, ho, mode), want), (wo, ho, mode)
-            assert last(L) == (TILED if takes_tiled(shape, wo, ho, mode) else GENERIC)
+    check_synthetic_stream(RESIZE, pkg, L, torch_cuda, [(wo, ho, mode) for wo, ho in ((640, 480), (427, 320), (200, 150)) for mode in MODES])
 
 
 @pytest.mark.parametrize("target", [(320, 240), (100, 75)], ids=lambda t: "x".join(map(str, t)))
@@ -139,68 +117,29 @@ def test_gpu_context(pkg, L, torch_cuda, target):
     n, h, w, c = shape
     wo, ho = target
     img = np.random.default_rng(13).integers(0, 256, size=shape, dtype=np.uint8)
-    want = ref_resize(img, wo, ho)
     kernel = TILED if takes_tiled(shape, wo, ho) else GENERIC
     assert (kernel == TILED) == (target == (320, 240))
-    with pkg.Context(0, w, h, c, 1, max_batch=n, n_slots=3) as ctx:
-        ctx.set_resize(wo, ho)
-        out = np.full(want.size + 64, 0xA5, np.uint8)
-        ctx.submit(img.ctypes.data, out.ctypes.data, n)                  # pageable: the slot's output buffers hold the larger of the two sizes
-        t = ctx.sync()
-        assert np.array_equal(out[:want.size].reshape(want.shape), want) and (out[want.size:] == 0xA5).all()
-        assert last(L) == kernel
-        assert t["bytes_alg"] == img.size + want.size
-        # pinned, in place: the output buffer is sized for the OUTPUT (an input-sized one would be overrun by the enlargement),
-        # with guard bytes behind it; the plain context below writes input-sized images into the same buffer
-        cap = max(img.size, want.size) + 4096
-        pin_in, pin_out = L.mi_blur_host_alloc(img.size), L.mi_blur_host_alloc(cap)
-        try:
-            a = np.ctypeslib.as_array((C.c_uint8 * img.size).from_address(pin_in)).reshape(img.shape)
-            b = np.ctypeslib.as_array((C.c_uint8 * cap).from_address(pin_out))
-            a[:] = img
-            z0 = L.mi_blur_zero_copy_launches(ctx.h)
-            for _ in range(3):
-                b[:] = 0xA5
-                ctx.submit(pin_in, pin_out, n)
-                ctx.sync()
-                assert np.array_equal(b[:want.size].reshape(want.shape), want) and (b[want.size:] == 0xA5).all()
-            assert L.mi_blur_zero_copy_launches(ctx.h) == z0 + 3
-            assert last(L) == kernel
-            pitch = w * c
-            assert L.mi_blur_submit_band(ctx.h, pin_in, pin_out, 60, 2, 2) == pkg.ERR_UNSUPPORTED
-            assert L.mi_blur_submit_bands(ctx.h, pin_in, pin_out, n, h * pitch, 60, 2, 2) == pkg.ERR_UNSUPPORTED
-            assert L.mi_blur_submit_planar(ctx.h, pin_in, pin_out, n, 0) == pkg.ERR_UNSUPPORTED
-            ctx.resident_alloc(2)
-            assert L.mi_blur_resident_run(ctx.h, 2, 1, 0) == pkg.ERR_UNSUPPORTED
-            assert L.mi_blur_resident_run_fused(ctx.h, 2, 1, 0) == pkg.ERR_UNSUPPORTED
-            assert L.mi_blur_ctx_set_resize(ctx.h, C.byref(pkg.Resize(wo, ho, BILINEAR))) == pkg.ERR_STATE
-            # a context without the setter is what it was: the same pinned submit gives the box blur, and a pinned submit
-            # above the batch server's threshold (zero_copy_server_min_kb, 1280 KiB of output: these 6 frames are 338 KiB,
-            # which has always been one launch, so four times the batch) still takes blur_server_kernel
-            box = np.empty_like(img)
-            assert L.mi_blur_cpu_run(img.ctypes.data, box.ctypes.data, w, h, c, 1, n, 4) == pkg.OK
-            big_in, big_out = L.mi_blur_host_alloc(4 * img.size), L.mi_blur_host_alloc(4 * img.size)
-            try:
-                with pkg.Context(0, w, h, c, 1, max_batch=4 * n, n_slots=3) as plain:
-                    b[:] = 0
-                    plain.submit(pin_in, pin_out, n)
-                    plain.sync()
-                    assert np.array_equal(b[:img.size].reshape(img.shape), box)
-                    ba = np.ctypeslib.as_array((C.c_uint8 * (4 * img.size)).from_address(big_in)).reshape((4,) + img.shape)
-                    bb = np.ctypeslib.as_array((C.c_uint8 * (4 * img.size)).from_address(big_out)).reshape((4,) + img.shape)
-                    ba[:] = img
-                    bb[:] = 0
-                    assert 4 * img.size >= 1280 * 1024
-                    plain.submit(big_in, big_out, 4 * n)
-                    plain.sync()
-                    assert last(L) == "blur_server_kernel"
-                    assert all(np.array_equal(bb[i], box) for i in range(4))
-            finally:
-                L.mi_blur_host_free(big_in)
-                L.mi_blur_host_free(big_out)
-        finally:
-            L.mi_blur_host_free(pin_in)
-            L.mi_blur_host_free(pin_out)
+    check_gpu_context(RESIZE, pkg, L, img, (wo, ho, BILINEAR), kernel)
+    # a context without the setter is what it was: the same pinned submit gives the box blur, and a pinned submit
+    # above the batch server's threshold (zero_copy_server_min_kb, 1280 KiB of output: these 6 frames are 338 KiB,
+    # which has always been one launch, so four times the batch) still takes blur_server_kernel
+    box = np.empty_like(img)
+    assert L.mi_blur_cpu_run(img.ctypes.data, box.ctypes.data, w, h, c, 1, n, 4) == pkg.OK
+    with pinned(L, img.size, img.size, 4 * img.size, 4 * img.size) as ((pin_in, a), (pin_out, b), (big_in, ba), (big_out, bb)):
+        with pkg.Context(0, w, h, c, 1, max_batch=4 * n, n_slots=3) as plain:
+            a[:] = img.reshape(-1)
+            b[:] = 0
+            plain.submit(pin_in, pin_out, n)
+            plain.sync()
+            assert np.array_equal(b.reshape(img.shape), box)
+            ba, bb = ba.reshape((4,) + img.shape), bb.reshape((4,) + img.shape)
+            ba[:] = img
+            bb[:] = 0
+            assert 4 * img.size >= 1280 * 1024
+            plain.submit(big_in, big_out, 4 * n)
+            plain.sync()
+            assert last(L) == "blur_server_kernel"
+            assert all(np.array_equal(bb[i], box) for i in range(4))
 
 
 def test_numpy_function_on_the_gpu(pkg, L, torch_cuda):

@@ -3,19 +3,18 @@ mi_blur_ctx_set_resize, resize() / resize_coord()), CPU only: against the numpy 
 (resize_ref.py), independent of the product.  All comparisons are exact unless stated."""
 import ctypes as C
 import os
-import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
-from filter_harness import MEDIAN, cpu_run
-from resize_ref import BILINEAR, MAX_DIM, NEAREST, cpu_resize_run, float_bilinear, ref_axis, ref_resize
+from filter_harness import MEDIAN, cpu_run as cpu_run_same_size
+from resample_harness import (RESIZE, check_cpu_context, check_cpu_run_refuses, check_ctx_set_refuses, check_enqueue_invalid_before_no_device,
+                              check_setters_replace_each_other, cpu_run, needs_gxx, no_scratch, run_sanitized, size_rows)
+from resize_ref import BILINEAR, MAX_DIM, NEAREST, float_bilinear, ref_axis, ref_resize
 from sep_down_ref import ref_sep_down
 from sep_ref import rand_taps
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHAPES = [(3, 33, 40, 3), (1, 1, 1, 3), (2, 9, 5, 1), (1, 17, 16, 4), (1, 50, 7, 5), (1, 64, 96, 2)]
 MODES = (BILINEAR, NEAREST)
 
@@ -61,15 +60,15 @@ def test_properties_of_the_definition(pkg, L):
     rng = np.random.default_rng(1)
     img = rng.integers(0, 256, size=(2, 13, 17, 3), dtype=np.uint8)
     for mode in MODES:
-        assert np.array_equal(cpu_resize_run(pkg, L, img, 17, 13, mode, 2), img)                   # same size: the identity
+        assert np.array_equal(cpu_run(RESIZE, pkg, L, img, (17, 13, mode), 2), img)                   # same size: the identity
         for v in (0, 200, 255):
             flat = np.full((1, 9, 11, 2), v, np.uint8)
             for wo, ho in ((11, 9), (30, 31), (5, 4), (1, 1), (64, 3)):
-                assert (cpu_resize_run(pkg, L, flat, wo, ho, mode, 1) == v).all(), (mode, v, wo, ho)
+                assert (cpu_run(RESIZE, pkg, L, flat, (wo, ho, mode), 1) == v).all(), (mode, v, wo, ho)
                 assert (ref_resize(flat, wo, ho, mode) == v).all()
     for k in (2, 3):
         want = np.repeat(np.repeat(img, k, axis=1), k, axis=2)
-        assert np.array_equal(cpu_resize_run(pkg, L, img, 17 * k, 13 * k, NEAREST, 2), want), k
+        assert np.array_equal(cpu_run(RESIZE, pkg, L, img, (17 * k, 13 * k, NEAREST), 2), want), k
 
 
 @pytest.mark.parametrize("case", [(33, 48, 67, 131), (40, 64, 25, 37), (31, 17, 93, 51), (7, 5, 64, 64)], ids=lambda c: "x".join(map(str, c)))
@@ -84,7 +83,7 @@ def test_bilinear_is_within_one_of_float_bilinear(pkg, L, case):
     real = float_bilinear(img, wo, ho)
     exact = np.floor(real + 0.5).astype(np.int64)
     restated = ref_resize(img, wo, ho)
-    got = cpu_resize_run(pkg, L, img, wo, ho, BILINEAR, 2)
+    got = cpu_run(RESIZE, pkg, L, img, (wo, ho, BILINEAR), 2)
     assert np.array_equal(got, restated)
     assert np.abs(restated.astype(np.int64) - exact).max() <= 1
     assert np.abs(restated.astype(np.float64) - real).max() < 0.5 + 2 * 255 / 4096
@@ -100,115 +99,49 @@ def test_cpu_run_matches_the_restatement(pkg, L, shape):
             want = ref_resize(img, wo, ho, mode)
             assert want.shape == (n, ho, wo, c)
             for nt in (1, 4):
-                assert np.array_equal(cpu_resize_run(pkg, L, img, wo, ho, mode, nt), want), (shape, wo, ho, mode, nt)
+                assert np.array_equal(cpu_run(RESIZE, pkg, L, img, (wo, ho, mode), nt), want), (shape, wo, ho, mode, nt)
 
 
-def bad_calls(pkg, call):
-    """call(in, out, w, h, c, r) -> status: every argument set the header calls invalid."""
-    a = np.zeros((8, 8, 3), np.uint8)
-    b = np.zeros((16, 16, 3), np.uint8)
-    good = pkg.Resize(16, 16, BILINEAR)
-    ref = lambda s: None if s is None else C.byref(s)
-    ia, ib = a.ctypes.data, b.ctypes.data
-    bad = [(ia, ib, 8, 8, 3, None), (None, ib, 8, 8, 3, good), (ia, None, 8, 8, 3, good), (ia, ia, 8, 8, 3, good)]
-    for r in [(0, 16, 1), (16, 0, 1), (-3, 16, 1), (16, -1, 1), (MAX_DIM + 1, 1, 1), (1, MAX_DIM + 1, 1), (16, 16, 2), (16, 16, -1)]:
-        bad.append((ia, ib, 8, 8, 3, pkg.Resize(*r)))
-    for w, h, c in [(0, 8, 3), (8, 0, 3), (8, 8, 0), (-1, 8, 3), (MAX_DIM + 1, 1, 1), (1, MAX_DIM + 1, 1)]:
-        bad.append((ia, ib, w, h, c, good))
-    bad.append((ia, ib, 8, 8, 3, pkg.Resize(MAX_DIM, MAX_DIM, 1)))          # the output image: 3 GiB, over the per-image limit
-    bad.append((ia, ib, 8, 8, 40000, pkg.Resize(MAX_DIM, 1, 1)))           # the output row: over INT_MAX / 2
-    for i, o, w, h, c, r in bad:
-        assert call(i, o, w, h, c, ref(r)) == pkg.ERR_INVALID, (i, o, w, h, c, r and (r.out_width, r.out_height, r.mode))
-    return a, b, good
+def bad_rows(pkg):
+    """(good, rows) for resample_harness.bad_calls: resize has no rows of its own."""
+    mk = lambda wo=16, ho=16, mode=BILINEAR: pkg.Resize(wo, ho, mode)
+    return (C.byref(mk()),), size_rows(mk)
 
 
 def test_cpu_run_refuses_invalid_arguments(pkg, L):
-    a, b, r = bad_calls(pkg, lambda i, o, w, h, c, r: L.mi_blur_cpu_run_resize(i, o, w, h, c, 1, r, 1))
-    assert L.mi_blur_cpu_run_resize(a.ctypes.data, b.ctypes.data, 8, 8, 3, -1, C.byref(r), 1) == pkg.ERR_INVALID
-    assert L.mi_blur_cpu_run_resize(a.ctypes.data, b.ctypes.data, 8, 8, 3, 1, C.byref(r), 1) == pkg.OK
-    assert L.mi_blur_cpu_run_resize(a.ctypes.data, b.ctypes.data, 8, 8, 3, 0, C.byref(r), 1) == pkg.OK
+    check_cpu_run_refuses(RESIZE, pkg, L, *bad_rows(pkg))
 
 
 def test_enqueue_invalid_comes_before_no_device(pkg, L):
     """Every argument is checked before a device is asked for; without a GPU a good call is ERR_NO_DEVICE (with one, the
     null stream of an empty batch is MI_BLUR_OK)."""
-    a, b, r = bad_calls(pkg, lambda i, o, w, h, c, r: L.mi_blur_enqueue_resize(i, o, w, h, c, 1, r, None))
-    assert L.mi_blur_enqueue_resize(a.ctypes.data, b.ctypes.data, 8, 8, 3, -1, C.byref(r), None) == pkg.ERR_INVALID
-    if L.mi_blur_device_count() <= 0:
-        assert L.mi_blur_enqueue_resize(a.ctypes.data, b.ctypes.data, 8, 8, 3, 1, C.byref(r), None) == pkg.ERR_NO_DEVICE
-        assert L.mi_blur_enqueue_resize(a.ctypes.data, b.ctypes.data, 8, 8, 3, 0, C.byref(r), None) == pkg.ERR_NO_DEVICE
-    else:
-        assert L.mi_blur_enqueue_resize(a.ctypes.data, b.ctypes.data, 8, 8, 3, 0, C.byref(r), None) == pkg.OK
+    check_enqueue_invalid_before_no_device(RESIZE, pkg, L, *bad_rows(pkg))
 
 
 def test_ctx_set_refuses_invalid_arguments(pkg, L):
-    with pkg.Context(pkg.DEVICE_CPU, 8, 8, 3, 1, max_batch=1) as ctx:
-        assert L.mi_blur_ctx_set_resize(None, C.byref(pkg.Resize(16, 16, 1))) == pkg.ERR_INVALID
-        assert L.mi_blur_ctx_set_resize(ctx.h, None) == pkg.ERR_INVALID
-        for r in [(0, 16, 1), (16, 0, 1), (MAX_DIM + 1, 1, 1), (1, MAX_DIM + 1, 1), (16, 16, 2), (MAX_DIM, MAX_DIM, 1)]:
-            assert L.mi_blur_ctx_set_resize(ctx.h, C.byref(pkg.Resize(*r))) == pkg.ERR_INVALID, r
-        img = np.random.default_rng(2).integers(0, 256, size=(1, 8, 8, 3), dtype=np.uint8)   # refused sets leave the box blur in place
-        out, box = np.empty_like(img), np.empty_like(img)
-        ctx.submit(img.ctypes.data, out.ctypes.data, 1)
-        t = ctx.sync()
-        assert L.mi_blur_cpu_run(img.ctypes.data, box.ctypes.data, 8, 8, 3, 1, 1, 1) == pkg.OK
-        assert np.array_equal(out, box) and t["bytes_alg"] == 2 * img.size
-    with pkg.Context(pkg.DEVICE_CPU, MAX_DIM + 1, 2, 1, 1, max_batch=1) as wide:      # the context's own size over MAX_DIM
-        assert L.mi_blur_ctx_set_resize(wide.h, C.byref(pkg.Resize(16, 16, 1))) == pkg.ERR_INVALID
+    bad = [(C.byref(pkg.Resize(*r)),) for r in [(0, 16, 1), (16, 0, 1), (MAX_DIM + 1, 1, 1), (1, MAX_DIM + 1, 1), (16, 16, 2), (MAX_DIM, MAX_DIM, 1)]]
+    check_ctx_set_refuses(RESIZE, pkg, L, (C.byref(pkg.Resize(16, 16, 1)),), bad)
 
 
 @pytest.mark.parametrize("target", [(84, 70), (63, 74), (25, 22), (60, 20)], ids=lambda t: "x".join(map(str, t)))
 def test_cpu_context(pkg, L, target):
     rng = np.random.default_rng(23)
     img = rng.integers(0, 256, size=(5, 37, 42, 3), dtype=np.uint8)
-    n, h, w, c = img.shape
     wo, ho = target
     for mode in MODES:
-        want = ref_resize(img, wo, ho, mode)
-        with pkg.Context(pkg.DEVICE_CPU, w, h, c, 1, max_batch=n, n_threads=3) as ctx:
-            r = pkg.Resize(wo, ho, mode)
-            assert L.mi_blur_ctx_set_resize(ctx.h, C.byref(r)) == pkg.OK
-            C.memset(C.byref(r), 0xFF, C.sizeof(r))                      # the context keeps a copy
-            out = np.full(want.size + 128, 0xA5, np.uint8)
-            ctx.submit(img.ctypes.data, out.ctypes.data + 64, n)         # pageable memory, guards either side
-            t = ctx.sync()
-            assert np.array_equal(out[64:64 + want.size].reshape(want.shape), want)
-            assert (out[:64] == 0xA5).all() and (out[64 + want.size:] == 0xA5).all()
-            assert t["bytes_alg"] == img.size + want.size and t["images"] == n
-            pitch = w * c
-            o = np.zeros_like(img)
-            assert L.mi_blur_submit_band(ctx.h, img.ctypes.data, o.ctypes.data, 20, 2, 2) == pkg.ERR_UNSUPPORTED
-            assert L.mi_blur_submit_bands(ctx.h, img.ctypes.data, o.ctypes.data, n, h * pitch, 20, 2, 2) == pkg.ERR_UNSUPPORTED
-            assert L.mi_blur_submit_planar(ctx.h, img.ctypes.data, o.ctypes.data, n, 0) == pkg.ERR_UNSUPPORTED
-            assert L.mi_blur_resident_run(ctx.h, 1, 1, 0) == pkg.ERR_UNSUPPORTED
-            assert L.mi_blur_resident_run_fused(ctx.h, 1, 1, 0) == pkg.ERR_UNSUPPORTED
-            assert not o.any()
-            assert L.mi_blur_ctx_set_resize(ctx.h, C.byref(pkg.Resize(wo, ho, mode))) == pkg.ERR_STATE
+        check_cpu_context(RESIZE, pkg, L, img, (wo, ho, mode))
 
 
 def test_setters_replace_each_other(pkg, L):
     rng = np.random.default_rng(29)
     img = rng.integers(0, 256, size=(2, 20, 24, 3), dtype=np.uint8)
-    n, h, w, c = img.shape
     k = pkg.SepKernel.from_taps(rand_taps(rng, 2), rand_taps(rng, 1))
 
-    def run(setters, want):
-        with pkg.Context(pkg.DEVICE_CPU, w, h, c, 1, max_batch=n) as ctx:
-            for s in setters:
-                s(ctx)
-            out = np.full(want.size + 64, 0xA5, np.uint8)
-            ctx.submit(img.ctypes.data, out.ctypes.data, n)
-            t = ctx.sync()
-            assert np.array_equal(out[:want.size].reshape(want.shape), want) and (out[want.size:] == 0xA5).all()
-            return t
     resize = lambda ctx: ctx.set_resize(40, 31)
     median = lambda ctx: ctx.set_median(1)
     down = lambda ctx: ctx.set_sep_down(k, 2, 2, 1, 0)
-    big, med, dec = ref_resize(img, 40, 31), cpu_run(MEDIAN, pkg, L, img, 1, 1), ref_sep_down(img, *k.taps(), 2, 2, 1, 0)
-    assert run([resize, median], med)["bytes_alg"] == 2 * img.size       # the last one wins
-    assert run([median, resize], big)["bytes_alg"] == img.size + big.size
-    assert run([resize, down], dec)["bytes_alg"] == img.size + dec.size
-    assert run([down, resize], big)["bytes_alg"] == img.size + big.size
+    big, med, dec = ref_resize(img, 40, 31), cpu_run_same_size(MEDIAN, pkg, L, img, 1, 1), ref_sep_down(img, *k.taps(), 2, 2, 1, 0)
+    check_setters_replace_each_other(pkg, L, img, [([resize, median], med), ([median, resize], big), ([resize, down], dec), ([down, resize], big)])   # the last one wins
 
 
 def test_numpy_function_on_the_cpu_device(pkg, L):
@@ -256,24 +189,9 @@ def test_hosts_refuse_resize_with_other_filters(pkg, tmp_path):
 def test_tiled_kernels_use_no_scratch(pkg, tmp_path):
     """Compiles resize_kernels.hip to gfx950 assembly (no GPU needed): the gather of the horizontal pass reads LDS at
     run-time addresses, but no tiled instantiation may spill or index registers at run time."""
-    out = tmp_path / "k.s"
-    r = subprocess.run([pkg.HIPCC, f"--offload-arch={pkg.ARCH}", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-o", str(out),
-                        os.path.join(pkg.CSRC, "resize_kernels.hip")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    text = out.read_text()
-    kernels = re.findall(r"\.amdhsa_kernel (\S*blur_resize_tiled_kernel\S*)(.*?)\.end_amdhsa_kernel", text, re.S)
-    assert len(kernels) == 4, [k for k, _ in kernels]                        # 1-4 channels
-    for name, body in kernels:
-        assert re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", body).group(1) == "0", name
+    no_scratch(pkg, tmp_path, "resize_kernels.hip", "blur_resize_tiled_kernel", 4)       # 1-4 channels
 
 
-@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
+@needs_gxx
 def test_cpu_resize_clean_under_asan_ubsan(pkg, tmp_path):
-    exe = tmp_path / "san_resize"
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           "-fno-omit-frame-pointer", "-I", pkg.CSRC, os.path.join(ROOT, "tests", "san_resize.cpp"),
-           os.path.join(pkg.CSRC, "cpu_device.cpp"), "-lpthread", "-o", str(exe)]
-    subprocess.run(cmd, check=True, capture_output=True)
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "400 random resize cases clean" in r.stdout, r.stdout + r.stderr
-    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr
+    run_sanitized(pkg, tmp_path, ("san_resize.cpp", "cpu_device.cpp"), ["400 random resize cases clean"])

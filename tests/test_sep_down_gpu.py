@@ -7,13 +7,13 @@ import subprocess
 import numpy as np
 import pytest
 
-from filter_harness import apps, read_ppm, torch_cuda, write_ppm  # noqa: F401
-from sep_down_ref import PRESETS, cpu_down_run, gpu_down_run, ref_sep_down
+from resample_harness import SEP_DOWN, apps, check_gpu_context, check_pointer_offsets, check_synthetic_stream, gpu_run, last, pinned, read_ppm, torch_cuda, write_ppm  # noqa: F401
+from sep_down_ref import PRESETS, ref_sep_down
 from sep_ref import rand_taps, ref_sep
 
 pytestmark = pytest.mark.gpu
 
-TILED, GENERIC = "blur_sep_down_tiled_kernel", "blur_sep_down_generic_kernel"
+TILED, GENERIC = SEP_DOWN.tiled, SEP_DOWN.generic
 PHASES2 = [(2, 2, 0, 0), (2, 2, 1, 0), (2, 2, 0, 1), (2, 2, 1, 1)]
 RADII = [(0, 0), (1, 1), (2, 2), (3, 5), (4, 0), (0, 4), (8, 3), (12, 16), (16, 16)]
 # blur_sep_down_tiled_kernel's tile (sep_down_kernels.hip, launch_sep_down_tiled; TILE_TH / TILE_NCOLS of kernel_common.h):
@@ -44,8 +44,8 @@ def test_aligned_stride_two_takes_the_tiled_kernel(pkg, L, torch_cuda, shape):
         k, wx, wy = kernel_of(pkg, rng, rx, ry)
         full = ref_sep(img, wx, wy)
         for dec in PHASES2:
-            got = gpu_down_run(pkg, L, torch_cuda, img, k, dec)
-            assert L.mi_blur_last_kernel().decode() == TILED, (shape, rx, ry, dec)
+            got = gpu_run(SEP_DOWN, pkg, L, torch_cuda, img, (k, dec))
+            assert last(L) == TILED, (shape, rx, ry, dec)
             assert np.array_equal(got, full[:, dec[3]::2, dec[2]::2, :]), (shape, rx, ry, dec)
 
 
@@ -56,16 +56,11 @@ def test_other_shapes_take_the_generic_kernel(pkg, L, torch_cuda):
         for j, (rx, ry) in enumerate(RADII):
             k, wx, wy = kernel_of(pkg, rng, rx, ry)
             dec = (2, 2, 0, 0) if shape[1] == 1 else PHASES2[(i + j) % 4]      # phases cycle across the radii; 1 x 1: phase 0 only
-            got = gpu_down_run(pkg, L, torch_cuda, img, k, dec)
-            assert L.mi_blur_last_kernel().decode() == GENERIC, (shape, rx, ry, dec)
+            got = gpu_run(SEP_DOWN, pkg, L, torch_cuda, img, (k, dec))
+            assert last(L) == GENERIC, (shape, rx, ry, dec)
             assert np.array_equal(got, ref_sep_down(img, wx, wy, *dec)), (shape, rx, ry, dec)
     img = rng.integers(0, 256, size=(2, 70, 96, 2), dtype=np.uint8)             # aligned shape, pointers off 16 bytes
-    k, wx, wy = kernel_of(pkg, rng, 3, 5)
-    want = ref_sep_down(img, wx, wy, 2, 2, 1, 1)
-    assert np.array_equal(gpu_down_run(pkg, L, torch_cuda, img, k, (2, 2, 1, 1)), want) and L.mi_blur_last_kernel().decode() == TILED
-    for oi, oo in ((1, 0), (0, 7)):
-        assert np.array_equal(gpu_down_run(pkg, L, torch_cuda, img, k, (2, 2, 1, 1), oi, oo), want), (oi, oo)
-        assert L.mi_blur_last_kernel().decode() == GENERIC, (oi, oo)
+    check_pointer_offsets(SEP_DOWN, pkg, L, torch_cuda, img, (kernel_of(pkg, rng, 3, 5)[0], (2, 2, 1, 1)), offsets=((1, 0), (0, 7)))
 
 
 def test_other_strides_and_narrow_output_rows(pkg, L, torch_cuda):
@@ -75,7 +70,7 @@ def test_other_strides_and_narrow_output_rows(pkg, L, torch_cuda):
     for j, (rx, ry) in enumerate(RADII):
         k, wx, wy = kernel_of(pkg, rng, rx, ry)
         dec = PHASES2[j % 4]
-        assert np.array_equal(gpu_down_run(pkg, L, torch_cuda, img, k, dec), ref_sep_down(img, wx, wy, *dec)), (rx, ry, dec)
+        assert np.array_equal(gpu_run(SEP_DOWN, pkg, L, torch_cuda, img, (k, dec)), ref_sep_down(img, wx, wy, *dec)), (rx, ry, dec)
     for shape in ((2, 70, 96, 2), (1, 17, 33, 3)):
         img = rng.integers(0, 256, size=shape, dtype=np.uint8)
         for j, (sx, sy) in enumerate([(1, 1), (2, 1), (1, 2), (3, 3), (4, 4), (4, 2)]):
@@ -84,7 +79,7 @@ def test_other_strides_and_narrow_output_rows(pkg, L, torch_cuda):
             full = ref_sep(img, wx, wy)
             for ox in range(sx):
                 for oy in range(sy):
-                    got = gpu_down_run(pkg, L, torch_cuda, img, k, (sx, sy, ox, oy))
+                    got = gpu_run(SEP_DOWN, pkg, L, torch_cuda, img, (k, (sx, sy, ox, oy)))
                     assert np.array_equal(got, full[:, oy::sy, ox::sx, :]), (shape, sx, sy, ox, oy, rx, ry)
             if (sx, sy) == (1, 1):                                           # ... and the bytes of mi_blur_enqueue_sep
                 n, h, w, c = shape
@@ -92,7 +87,7 @@ def test_other_strides_and_narrow_output_rows(pkg, L, torch_cuda):
                 d_out = torch_cuda.zeros_like(d_in)
                 pkg.check(L.mi_blur_enqueue_sep(d_in.data_ptr(), d_out.data_ptr(), w, h, c, n, C.byref(k), None), "mi_blur_enqueue_sep")
                 torch_cuda.cuda.synchronize()
-                assert np.array_equal(gpu_down_run(pkg, L, torch_cuda, img, k, (1, 1, 0, 0)), d_out.cpu().numpy())
+                assert np.array_equal(gpu_run(SEP_DOWN, pkg, L, torch_cuda, img, (k, (1, 1, 0, 0))), d_out.cpu().numpy())
 
 
 def seam_images(rng, h, w, c):
@@ -133,8 +128,8 @@ def test_tile_seams(pkg, L, torch_cuda, shape):
         full = ref_sep(img, wx, wy)
         assert (full[2] == 255).all()
         for dec in ((2, 2, 0, 0), (2, 2, 1, 1)):
-            got = gpu_down_run(pkg, L, torch_cuda, img, k, dec)
-            assert L.mi_blur_last_kernel().decode() == TILED
+            got = gpu_run(SEP_DOWN, pkg, L, torch_cuda, img, (k, dec))
+            assert last(L) == TILED
             assert (got[2] == 255).all(), (shape, r, dec)
             assert np.array_equal(got, full[:, dec[3]::2, dec[2]::2, :]), (shape, r, dec)
 
@@ -149,63 +144,25 @@ def presets(pkg, L):
 
 
 def test_gpu_equals_cpu_device_on_the_synthetic_stream(pkg, L, torch_cuda):
-    shape = (4, 240, 320, 3)
-    host = np.empty(shape, np.uint8)
-    L.mi_blur_fill_synthetic(host.ctypes.data, 320, 240, 3, 0, 4, 4)
     rng = np.random.default_rng(9)
-    for k, dec in presets(pkg, L) + [(kernel_of(pkg, rng, 5, 9)[0], (2, 2, 1, 0))]:
-        want = cpu_down_run(pkg, L, host, k, dec, 4)
-        assert np.array_equal(want, ref_sep_down(host, *k.taps(), *dec))
-        assert np.array_equal(gpu_down_run(pkg, L, torch_cuda, host, k, dec), want), dec
+    check_synthetic_stream(SEP_DOWN, pkg, L, torch_cuda, presets(pkg, L) + [(kernel_of(pkg, rng, 5, 9)[0], (2, 2, 1, 0))])
 
 
 def test_gpu_context(pkg, L, torch_cuda):
     shape = (6, 240, 320, 3)
     n, h, w, c = shape
     img = np.random.default_rng(13).integers(0, 256, size=shape, dtype=np.uint8)
-    (k, dec), = presets(pkg, L)[:1]
-    want = ref_sep_down(img, *k.taps(), *dec)
-    with pkg.Context(0, w, h, c, 1, max_batch=n, n_slots=3) as ctx:
-        ctx.set_sep_down(k, *dec)
-        out = np.full(want.size + 64, 0xA5, np.uint8)
-        ctx.submit(img.ctypes.data, out.ctypes.data, n)                  # pageable
-        t = ctx.sync()
-        assert np.array_equal(out[:want.size].reshape(want.shape), want) and (out[want.size:] == 0xA5).all()
-        assert L.mi_blur_last_kernel().decode() == TILED
-        assert t["bytes_alg"] == img.size + want.size
-        pin_in, pin_out = L.mi_blur_host_alloc(img.size), L.mi_blur_host_alloc(img.size)
-        try:
-            a = np.ctypeslib.as_array((C.c_uint8 * img.size).from_address(pin_in)).reshape(img.shape)
-            b = np.ctypeslib.as_array((C.c_uint8 * img.size).from_address(pin_out))
-            a[:] = img
-            z0 = L.mi_blur_zero_copy_launches(ctx.h)
-            for _ in range(3):
-                b[:] = 0xA5
-                ctx.submit(pin_in, pin_out, n)
-                ctx.sync()
-                assert np.array_equal(b[:want.size].reshape(want.shape), want) and (b[want.size:] == 0xA5).all()
-            assert L.mi_blur_zero_copy_launches(ctx.h) == z0 + 3
-            assert L.mi_blur_last_kernel().decode() == TILED
-            pitch = w * c
-            assert L.mi_blur_submit_band(ctx.h, pin_in, pin_out, 60, 2, 2) == pkg.ERR_UNSUPPORTED
-            assert L.mi_blur_submit_bands(ctx.h, pin_in, pin_out, n, h * pitch, 60, 2, 2) == pkg.ERR_UNSUPPORTED
-            assert L.mi_blur_submit_planar(ctx.h, pin_in, pin_out, n, 0) == pkg.ERR_UNSUPPORTED
-            ctx.resident_alloc(2)
-            assert L.mi_blur_resident_run(ctx.h, 2, 1, 0) == pkg.ERR_UNSUPPORTED
-            assert L.mi_blur_resident_run_fused(ctx.h, 2, 1, 0) == pkg.ERR_UNSUPPORTED
-            assert L.mi_blur_ctx_set_sep_down(ctx.h, C.byref(k), C.byref(pkg.Decimation(*dec))) == pkg.ERR_STATE
-            # a context without the setter still takes the batch server for the same pinned submit
-            with pkg.Context(0, w, h, c, 1, max_batch=n, n_slots=3) as plain:
-                b[:] = 0
-                plain.submit(pin_in, pin_out, n)
-                plain.sync()
-                assert L.mi_blur_last_kernel().decode() == "blur_server_kernel"
-                box = np.empty_like(img)
-                assert L.mi_blur_cpu_run(img.ctypes.data, box.ctypes.data, w, h, c, 1, n, 4) == pkg.OK
-                assert np.array_equal(b.reshape(img.shape), box)
-        finally:
-            L.mi_blur_host_free(pin_in)
-            L.mi_blur_host_free(pin_out)
+    check_gpu_context(SEP_DOWN, pkg, L, img, presets(pkg, L)[0], TILED)
+    # a context without the setter still takes the batch server for the same pinned submit
+    with pinned(L, img.size, img.size) as ((pin_in, a), (pin_out, b)), pkg.Context(0, w, h, c, 1, max_batch=n, n_slots=3) as plain:
+        a[:] = img.reshape(-1)
+        b[:] = 0
+        plain.submit(pin_in, pin_out, n)
+        plain.sync()
+        assert last(L) == "blur_server_kernel"
+        box = np.empty_like(img)
+        assert L.mi_blur_cpu_run(img.ctypes.data, box.ctypes.data, w, h, c, 1, n, 4) == pkg.OK
+        assert np.array_equal(b.reshape(img.shape), box)
 
 
 def test_numpy_functions_on_the_gpu(pkg, L, torch_cuda):

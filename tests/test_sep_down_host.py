@@ -2,15 +2,14 @@
 mi_blur_ctx_set_sep_down, pyr_down / area_down / sep_down), CPU only: against sep_ref.ref_sep followed by the subsampling
 (sep_down_ref.py), independent of the product.  All comparisons are exact."""
 import ctypes as C
-import os
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
-from filter_harness import MEDIAN, cpu_run
-from sep_down_ref import PHASES, PRESETS, cpu_down_run, down_shape, ref_sep_down
+from filter_harness import MEDIAN, cpu_run as cpu_run_same_size
+from resample_harness import (SEP_DOWN, check_cpu_context, check_cpu_run_refuses, check_enqueue_invalid_before_no_device, check_setters_replace_each_other,
+                              cpu_run, no_scratch)
+from sep_down_ref import PHASES, PRESETS, down_shape, ref_sep_down
 from sep_ref import rand_taps, ref_sep
 
 SHAPES = [(3, 33, 40, 3), (1, 1, 1, 3), (2, 9, 5, 1), (1, 17, 16, 4), (1, 50, 7, 5), (1, 64, 96, 2)]
@@ -43,46 +42,28 @@ def test_decimated_size_matches_the_formula(pkg, L):
     assert L.mi_blur_decimated_size(0, 8, C.byref(d), C.byref(wo), C.byref(ho)) == pkg.ERR_INVALID
 
 
-def bad_calls(pkg, call):
-    """call(in, out, w, h, k, d) -> status: every argument set the header calls invalid."""
-    a = np.zeros((8, 8, 3), np.uint8)
-    b = np.zeros_like(a)
-    good_k = pkg.SepKernel.from_taps([1, 2, 1])
-    good_d = pkg.Decimation(2, 2, 0, 0)
-    ref = lambda s: None if s is None else C.byref(s)
-    bad = []
-    for dec in [(0, 2, 0, 0), (2, 0, 0, 0), (5, 2, 0, 0), (2, 5, 0, 0), (2, 2, 2, 0), (2, 2, 0, 2), (3, 3, 3, 1), (2, 2, -1, 0), (2, 2, 0, -1)]:
-        bad.append((a.ctypes.data, b.ctypes.data, 8, 8, good_k, pkg.Decimation(*dec)))
-    bad.append((a.ctypes.data, b.ctypes.data, 2, 8, good_k, pkg.Decimation(4, 1, 2, 0)))      # ox >= W
-    bad.append((a.ctypes.data, b.ctypes.data, 8, 3, good_k, pkg.Decimation(1, 4, 0, 3)))      # oy >= H
-    bad.append((a.ctypes.data, b.ctypes.data, 8, 8, None, good_d))
-    bad.append((a.ctypes.data, b.ctypes.data, 8, 8, good_k, None))
-    k = pkg.SepKernel.from_taps([1, 2, 1]); k.wx[0] = 2; bad.append((a.ctypes.data, b.ctypes.data, 8, 8, k, good_d))     # sum 5
-    k = pkg.SepKernel.from_taps([1, 2, 1]); k.rx = 17; bad.append((a.ctypes.data, b.ctypes.data, 8, 8, k, good_d))
-    k = pkg.SepKernel.from_taps([1, 2, 1]); k.by = 3; bad.append((a.ctypes.data, b.ctypes.data, 8, 8, k, good_d))
-    bad.append((a.ctypes.data, a.ctypes.data, 8, 8, good_k, good_d))                         # in == out
-    for i, o, w, h, k, d in bad:
-        assert call(i, o, w, h, ref(k), ref(d)) == pkg.ERR_INVALID, (w, h, k and (k.rx, k.ry, k.bx, k.by), d and (d.sx, d.sy, d.ox, d.oy))
-    return a, b, good_k, good_d
+def bad_rows(pkg):
+    """(good, rows) for resample_harness.bad_calls: the strides, phases and taps the header calls invalid."""
+    good_k, good_d = pkg.SepKernel.from_taps([1, 2, 1]), pkg.Decimation(2, 2, 0, 0)
+    row = lambda w, h, k, d: (w, h, 3, (C.byref(k), C.byref(d)))
+    rows = [row(8, 8, good_k, pkg.Decimation(*dec))
+            for dec in [(0, 2, 0, 0), (2, 0, 0, 0), (5, 2, 0, 0), (2, 5, 0, 0), (2, 2, 2, 0), (2, 2, 0, 2), (3, 3, 3, 1), (2, 2, -1, 0), (2, 2, 0, -1)]]
+    rows.append(row(2, 8, good_k, pkg.Decimation(4, 1, 2, 0)))      # ox >= W
+    rows.append(row(8, 3, good_k, pkg.Decimation(1, 4, 0, 3)))      # oy >= H
+    k = pkg.SepKernel.from_taps([1, 2, 1]); k.wx[0] = 2; rows.append(row(8, 8, k, good_d))     # sum 5
+    k = pkg.SepKernel.from_taps([1, 2, 1]); k.rx = 17; rows.append(row(8, 8, k, good_d))
+    k = pkg.SepKernel.from_taps([1, 2, 1]); k.by = 3; rows.append(row(8, 8, k, good_d))
+    return (C.byref(good_k), C.byref(good_d)), rows
 
 
 def test_cpu_run_refuses_invalid_arguments(pkg, L):
-    a, b, k, d = bad_calls(pkg, lambda i, o, w, h, k, d: L.mi_blur_cpu_run_sep_down(i, o, w, h, 3, 1, k, d, 1))
-    assert L.mi_blur_cpu_run_sep_down(a.ctypes.data, b.ctypes.data, 8, 8, 3, 1, C.byref(k), C.byref(d), 1) == pkg.OK
-    assert L.mi_blur_cpu_run_sep_down(a.ctypes.data, b.ctypes.data, 8, 8, 3, 0, C.byref(k), C.byref(d), 1) == pkg.OK
+    check_cpu_run_refuses(SEP_DOWN, pkg, L, *bad_rows(pkg))
 
 
 def test_enqueue_invalid_comes_before_no_device(pkg, L):
     """Every argument is checked before a device is asked for; without a GPU a good call is ERR_NO_DEVICE (with one, the
     null stream of an empty batch is MI_BLUR_OK)."""
-    a, b, k, d = bad_calls(pkg, lambda i, o, w, h, k, d: L.mi_blur_enqueue_sep_down(i, o, w, h, 3, 1, k, d, None))
-    assert L.mi_blur_enqueue_sep_down(None, b.ctypes.data, 8, 8, 3, 1, C.byref(k), C.byref(d), None) == pkg.ERR_INVALID
-    assert L.mi_blur_enqueue_sep_down(a.ctypes.data, b.ctypes.data, 8, 8, 3, -1, C.byref(k), C.byref(d), None) == pkg.ERR_INVALID
-    if L.mi_blur_device_count() <= 0:
-        assert L.mi_blur_enqueue_sep_down(a.ctypes.data, b.ctypes.data, 8, 8, 3, 1, C.byref(k), C.byref(d), None) == pkg.ERR_NO_DEVICE
-        assert L.mi_blur_enqueue_sep_down(a.ctypes.data, b.ctypes.data, 8, 8, 3, 0, C.byref(k), C.byref(d), None) == pkg.ERR_NO_DEVICE
-    else:
-        assert L.mi_blur_enqueue_sep_down(a.ctypes.data, b.ctypes.data, 8, 8, 3, 0, C.byref(k), C.byref(d), None) == pkg.OK
+    check_enqueue_invalid_before_no_device(SEP_DOWN, pkg, L, *bad_rows(pkg))
 
 
 @pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(map(str, s)))
@@ -103,7 +84,7 @@ def test_cpu_run_matches_the_reference(pkg, L, shape):
             want = full[:, oy::sy, ox::sx, :]
             assert want.shape == down_shape(shape, *dec)
             for nt in (1, 4):
-                assert np.array_equal(cpu_down_run(pkg, L, img, k, dec, nt), want), (shape, rx, ry, dec, nt)
+                assert np.array_equal(cpu_run(SEP_DOWN, pkg, L, img, (k, dec), nt), want), (shape, rx, ry, dec, nt)
 
 
 def test_stride_one_is_the_separable_filter(pkg, L):
@@ -112,7 +93,7 @@ def test_stride_one_is_the_separable_filter(pkg, L):
     k = pkg.SepKernel.from_taps(rand_taps(rng, 3), rand_taps(rng, 2))
     full = np.empty_like(img)
     assert L.mi_blur_cpu_run_sep(img.ctypes.data, full.ctypes.data, 19, 21, 3, 2, C.byref(k), 2) == pkg.OK
-    assert np.array_equal(cpu_down_run(pkg, L, img, k, (1, 1, 0, 0), 2), full)
+    assert np.array_equal(cpu_run(SEP_DOWN, pkg, L, img, (k, (1, 1, 0, 0)), 2), full)
 
 
 def test_presets(pkg, L):
@@ -130,10 +111,10 @@ def test_presets(pkg, L):
         k, dec = preset(pkg, L, which)
         blocks = rng.integers(0, 256, size=(2, 6, 5, 3), dtype=np.uint8)
         img = np.repeat(np.repeat(blocks, f, axis=1), f, axis=2)
-        assert np.array_equal(cpu_down_run(pkg, L, img, k, dec, 2), blocks)
+        assert np.array_equal(cpu_run(SEP_DOWN, pkg, L, img, (k, dec), 2), blocks)
         img = rng.integers(0, 256, size=(2, 6 * f, 5 * f, 3), dtype=np.uint8)
         means = img.reshape(2, 6, f, 5, f, 3).astype(np.int64).sum(axis=(2, 4)) // (f * f)
-        assert np.array_equal(cpu_down_run(pkg, L, img, k, dec, 2), means.astype(np.uint8))
+        assert np.array_equal(cpu_run(SEP_DOWN, pkg, L, img, (k, dec), 2), means.astype(np.uint8))
         assert np.array_equal(ref_sep_down(img, *k.taps(), *dec), means.astype(np.uint8))
 
 
@@ -143,27 +124,7 @@ def test_cpu_context(pkg, L):
     n, h, w, c = img.shape
     wx, wy = rand_taps(rng, 3), rand_taps(rng, 5)
     dec = (2, 3, 1, 2)
-    want = ref_sep_down(img, wx, wy, *dec)
-    with pkg.Context(pkg.DEVICE_CPU, w, h, c, 1, max_batch=n, n_threads=3) as ctx:
-        k, d = pkg.SepKernel.from_taps(wx, wy), pkg.Decimation(*dec)
-        assert L.mi_blur_ctx_set_sep_down(ctx.h, C.byref(k), C.byref(d)) == pkg.OK
-        C.memset(C.byref(k), 0xFF, C.sizeof(k))                      # the context keeps a copy
-        C.memset(C.byref(d), 0xFF, C.sizeof(d))
-        out = np.full(want.size + 64, 0xA5, np.uint8)
-        ctx.submit(img.ctypes.data, out.ctypes.data, n)
-        t = ctx.sync()
-        assert np.array_equal(out[:want.size].reshape(want.shape), want) and (out[want.size:] == 0xA5).all()
-        assert t["bytes_alg"] == img.size + want.size and t["images"] == n
-        pitch = w * c
-        o = np.zeros_like(img)
-        assert L.mi_blur_submit_band(ctx.h, img.ctypes.data, o.ctypes.data, 20, 2, 2) == pkg.ERR_UNSUPPORTED
-        assert L.mi_blur_submit_bands(ctx.h, img.ctypes.data, o.ctypes.data, n, h * pitch, 20, 2, 2) == pkg.ERR_UNSUPPORTED
-        assert L.mi_blur_submit_planar(ctx.h, img.ctypes.data, o.ctypes.data, n, 0) == pkg.ERR_UNSUPPORTED
-        assert L.mi_blur_resident_run(ctx.h, 1, 1, 0) == pkg.ERR_UNSUPPORTED
-        assert L.mi_blur_resident_run_fused(ctx.h, 1, 1, 0) == pkg.ERR_UNSUPPORTED
-        assert not o.any()
-        good = pkg.SepKernel.from_taps(wx, wy)
-        assert L.mi_blur_ctx_set_sep_down(ctx.h, C.byref(good), C.byref(pkg.Decimation(*dec))) == pkg.ERR_STATE
+    check_cpu_context(SEP_DOWN, pkg, L, img, (pkg.SepKernel.from_taps(wx, wy), dec))
     with pkg.Context(pkg.DEVICE_CPU, w, h, c, 1, max_batch=n) as ctx:     # refused sets leave the context as it was
         good = pkg.SepKernel.from_taps(wx, wy)
         assert L.mi_blur_ctx_set_sep_down(None, C.byref(good), C.byref(pkg.Decimation(*dec))) == pkg.ERR_INVALID
@@ -181,23 +142,11 @@ def test_cpu_context(pkg, L):
 def test_setters_replace_each_other(pkg, L):
     rng = np.random.default_rng(29)
     img = rng.integers(0, 256, size=(2, 20, 24, 3), dtype=np.uint8)
-    n, h, w, c = img.shape
     k = pkg.SepKernel.from_taps(rand_taps(rng, 2), rand_taps(rng, 1))
-    with pkg.Context(pkg.DEVICE_CPU, w, h, c, 1, max_batch=n) as ctx:
-        ctx.set_sep_down(k, 2, 2, 1, 0)
-        ctx.set_median(1)
-        out = np.zeros_like(img)
-        ctx.submit(img.ctypes.data, out.ctypes.data, n)
-        ctx.sync()
-        assert np.array_equal(out, cpu_run(MEDIAN, pkg, L, img, 1, 1))      # the median at full size
-    with pkg.Context(pkg.DEVICE_CPU, w, h, c, 1, max_batch=n) as ctx:
-        ctx.set_median(1)
-        ctx.set_sep_down(k, 2, 2, 1, 0)
-        want = ref_sep_down(img, *k.taps(), 2, 2, 1, 0)
-        out = np.zeros(want.shape, np.uint8)
-        ctx.submit(img.ctypes.data, out.ctypes.data, n)
-        ctx.sync()
-        assert np.array_equal(out, want)
+    down = lambda ctx: ctx.set_sep_down(k, 2, 2, 1, 0)
+    median = lambda ctx: ctx.set_median(1)
+    med, dec = cpu_run_same_size(MEDIAN, pkg, L, img, 1, 1), ref_sep_down(img, *k.taps(), 2, 2, 1, 0)
+    check_setters_replace_each_other(pkg, L, img, [([down, median], med), ([median, down], dec)])      # the last one wins: the median at full size
 
 
 def test_numpy_functions_on_the_cpu_device(pkg, L):
@@ -229,12 +178,4 @@ def test_numpy_functions_on_the_cpu_device(pkg, L):
 def test_tiled_kernels_use_no_scratch(pkg, tmp_path):
     """Compiles sep_down_kernels.hip to gfx950 assembly (no GPU needed): the gather of the horizontal pass is all
     compile-time positions, so no tiled instantiation may spill or index registers at run time."""
-    out = tmp_path / "k.s"
-    r = subprocess.run([pkg.HIPCC, f"--offload-arch={pkg.ARCH}", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-o", str(out),
-                        os.path.join(pkg.CSRC, "sep_down_kernels.hip")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    text = out.read_text()
-    kernels = re.findall(r"\.amdhsa_kernel (\S*blur_sep_down_tiled_kernel\S*)(.*?)\.end_amdhsa_kernel", text, re.S)
-    assert len(kernels) == 12, [k for k, _ in kernels]                       # 4 channel counts x 3 radius buckets
-    for name, body in kernels:
-        assert re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", body).group(1) == "0", name
+    no_scratch(pkg, tmp_path, "sep_down_kernels.hip", "blur_sep_down_tiled_kernel", 12)      # 4 channel counts x 3 radius buckets

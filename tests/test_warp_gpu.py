@@ -1,40 +1,21 @@
 """The affine warp on the GPU (mi_blur_enqueue_warp, mi_blur_ctx_set_warp, warp_affine() / rotate(), the host's --rotate):
 exact bytes against the numpy restatement of the header's definition (warp_ref.py), and which of the two kernels took
 each launch against the restated eligibility rule."""
-import ctypes as C
 import subprocess
 
 import numpy as np
 import pytest
 
-from filter_harness import apps, read_ppm, torch_cuda, write_ppm  # noqa: F401
+from resample_harness import (WARP, apps, blocks, check_gpu_context, check_gpu_context_enlarging, check_pointer_offsets, check_synthetic_stream,  # noqa: F401
+                              gpu_run, last, read_ppm, spans_tiles, torch_cuda, write_ppm)
 from resize_ref import ref_resize
-from warp_ref import (BILINEAR, CLAMP, CONSTANT, LIMIT_FILL, LIMIT_MAPS, NEAREST, Q, cpu_warp_run, gpu_warp_run, identity, in_the_admitted_region,
-                      limit_out, limit_references, make_warp, quantise, ref_warp, rotation_m, scale_matrix, takes_tiled, tile_geometry)
+from warp_ref import (BILINEAR, CLAMP, CONSTANT, LIMIT_FILL, LIMIT_MAPS, NEAREST, Q, TILED_SHAPES, edge_image, identity, in_the_admitted_region,
+                      limit_out, limit_references, quantise, ref_warp, rotation_m, scale_matrix, takes_tiled)
 
 pytestmark = pytest.mark.gpu
 
-TILED, GENERIC = "blur_warp_tiled_kernel", "blur_warp_generic_kernel"
+TILED, GENERIC = WARP.tiled, WARP.generic
 BORDERS = (CLAMP, CONSTANT)
-
-
-def last(L):
-    return L.mi_blur_last_kernel().decode()
-
-
-def blocks(n, wo, ho, c):
-    ncols, cpr, rows = tile_geometry(wo, ho, c)
-    return n * -(-cpr // ncols) * -(-ho // rows)
-
-
-def edge_image(rng, n, h, w, c):
-    """Noise, with 0 / 255 on the outermost rows and columns of image 0 (what CLAMP repeats and CONSTANT blends with the
-    fill) and an all-255 last image when there are two."""
-    img = rng.integers(0, 256, size=(n, h, w, c), dtype=np.uint8)
-    img[0, 0], img[0, -1], img[0, :, 0], img[0, :, -1] = 255, 0, 0, 255
-    if n > 1:
-        img[-1] = 255
-    return img
 
 
 def maps(w, h):
@@ -53,30 +34,24 @@ def maps(w, h):
     return out
 
 
-# (input shape, (Wo, Ho)): 144 x 70 pixels out of 96 x 80 for one channel is 9 chunks x 70 rows = 3 x 3 tiles; the others
-# likewise span more than one tile both ways, with output sizes that differ from the input's
-TILED_SHAPES = [((1, 80, 96, 1), (144, 70)), ((2, 80, 96, 2), (136, 70)), ((1, 80, 96, 3), (144, 70)), ((2, 80, 96, 4), (132, 70))]
-
-
 @pytest.mark.parametrize("case", TILED_SHAPES, ids=lambda c: "x".join(map(str, c[0])) + f"-{c[1][0]}x{c[1][1]}")
 def test_aligned_launches_take_the_tiled_kernel(pkg, L, torch_cuda, case):
     shape, (wo, ho) = case
     n, h, w, c = shape
-    ncols, cpr, trows = tile_geometry(wo, ho, c)
-    assert cpr > ncols and ho > trows                               # more than one tile both ways
+    assert spans_tiles(wo, ho, c)                                   # more than one tile both ways
     img = edge_image(np.random.default_rng(sum(shape)), n, h, w, c)
     for name, m in maps(w, h).items():
         assert in_the_admitted_region(m), name
         for border in BORDERS:
             assert takes_tiled(shape, m, wo, ho, BILINEAR, border), (name, border)
-            got = gpu_warp_run(pkg, L, torch_cuda, img, m, wo, ho, BILINEAR, border, 173)
+            got = gpu_run(WARP, pkg, L, torch_cuda, img, (m, wo, ho, BILINEAR, border, 173))
             assert last(L) == TILED, (name, border)
             assert np.array_equal(got, ref_warp(img, m, wo, ho, BILINEAR, border, 173)), (name, border)
     # one image at the input's own size
     for name in ("rot0", "rot30", "rot90", "far-right", "half-out"):
         m = maps(w, h)[name]
         one = img[:1]
-        got = gpu_warp_run(pkg, L, torch_cuda, one, m, w, h, BILINEAR, CONSTANT, 9)
+        got = gpu_run(WARP, pkg, L, torch_cuda, one, (m, w, h, BILINEAR, CONSTANT, 9))
         assert last(L) == TILED and np.array_equal(got, ref_warp(one, m, w, h, BILINEAR, CONSTANT, 9)), name
         if name == "rot0":
             assert np.array_equal(got, one)
@@ -90,15 +65,15 @@ def test_xcd_remap_on_and_off(pkg, L, torch_cuda):
             assert (blocks(n, wo, ho, c) >= 16) == (n == 3)
             img = edge_image(rng, n, h, w, c)
             m = rotation_m(w, h, 33.0, 1.1)
-            got = gpu_warp_run(pkg, L, torch_cuda, img, m, wo, ho, BILINEAR, CONSTANT, 60)
+            got = gpu_run(WARP, pkg, L, torch_cuda, img, (m, wo, ho, BILINEAR, CONSTANT, 60))
             assert last(L) == TILED and np.array_equal(got, ref_warp(img, m, wo, ho, BILINEAR, CONSTANT, 60)), (c, n)
 
 
 def test_exact_right_angles_and_the_identity(pkg, L, torch_cuda):
     img = np.random.default_rng(12).integers(0, 256, size=(2, 64, 96, 4), dtype=np.uint8)
     for border in BORDERS:
-        assert np.array_equal(gpu_warp_run(pkg, L, torch_cuda, img, identity(), 96, 64, BILINEAR, border), img) and last(L) == TILED
-        got = gpu_warp_run(pkg, L, torch_cuda, img, [0, -Q, 95 * Q, Q, 0, 0], 64, 96, BILINEAR, border)
+        assert np.array_equal(gpu_run(WARP, pkg, L, torch_cuda, img, (identity(), 96, 64, BILINEAR, border, 0)), img) and last(L) == TILED
+        got = gpu_run(WARP, pkg, L, torch_cuda, img, ([0, -Q, 95 * Q, Q, 0, 0], 64, 96, BILINEAR, border, 0))
         assert last(L) == TILED and np.array_equal(got, np.rot90(img, 1, axes=(1, 2)))
 
 
@@ -113,18 +88,12 @@ def test_other_launches_take_the_generic_kernel(pkg, L, torch_cuda):
         for m in (rotation_m(w, h, 30.0), rotation_m(w, h, -100.0, 0.8, (1.0, 2.0)), identity(w + 3, -2), quantise([1.0, 0.5, -0.75 * w, 0.25, 1.0, 0.4 * h])):
             for border in BORDERS:
                 assert not takes_tiled(shape, m, wo, ho, mode, border)
-                got = gpu_warp_run(pkg, L, torch_cuda, img, m, wo, ho, mode, border, 99)
+                got = gpu_run(WARP, pkg, L, torch_cuda, img, (m, wo, ho, mode, border, 99))
                 assert last(L) == GENERIC, (shape, wo, ho, mode)
                 assert np.array_equal(got, ref_warp(img, m, wo, ho, mode, border, 99)), (shape, m, wo, ho, mode, border)
-    # aligned shape, pointers off 16 bytes: guards checked inside gpu_warp_run
+    # aligned shape, pointers off 16 bytes: guards checked inside gpu_run
     img = edge_image(rng, 2, 35, 48, 2)
-    m = rotation_m(48, 35, 30.0)
-    want = ref_warp(img, m, 56, 70, BILINEAR, CONSTANT, 5)
-    assert np.array_equal(gpu_warp_run(pkg, L, torch_cuda, img, m, 56, 70, BILINEAR, CONSTANT, 5), want) and last(L) == TILED
-    for oi, oo in ((1, 0), (0, 7), (3, 5)):
-        assert not takes_tiled(img.shape, m, 56, 70, BILINEAR, CONSTANT, oi, oo)
-        assert np.array_equal(gpu_warp_run(pkg, L, torch_cuda, img, m, 56, 70, BILINEAR, CONSTANT, 5, oi, oo), want), (oi, oo)
-        assert last(L) == GENERIC, (oi, oo)
+    check_pointer_offsets(WARP, pkg, L, torch_cuda, img, (rotation_m(48, 35, 30.0), 56, 70, BILINEAR, CONSTANT, 5))
 
 
 def test_a_footprint_over_64_kib_takes_the_generic_kernel(pkg, L, torch_cuda):
@@ -134,13 +103,13 @@ def test_a_footprint_over_64_kib_takes_the_generic_kernel(pkg, L, torch_cuda):
     m = scale_matrix(1, 8)
     for border in BORDERS:
         assert not takes_tiled(shape, m, 64, 64, BILINEAR, border)
-        got = gpu_warp_run(pkg, L, torch_cuda, img, m, 64, 64, BILINEAR, border)
+        got = gpu_run(WARP, pkg, L, torch_cuda, img, (m, 64, 64, BILINEAR, border, 0))
         assert last(L) == GENERIC and np.array_equal(got, ref_warp(img, m, 64, 64, BILINEAR, border))
     assert np.array_equal(ref_warp(img, m, 64, 64, BILINEAR, CLAMP), ref_resize(img, 64, 64))
     # a 4x reduction still fits (256 x 128 pixels of one byte: 32 KiB), outside the admitted region: the walk decides
     m4 = scale_matrix(1, 4)
     assert not in_the_admitted_region(m4) and takes_tiled(shape, m4, 128, 128, BILINEAR, CLAMP)
-    got = gpu_warp_run(pkg, L, torch_cuda, img, m4, 128, 128, BILINEAR, CLAMP)
+    got = gpu_run(WARP, pkg, L, torch_cuda, img, (m4, 128, 128, BILINEAR, CLAMP, 0))
     assert last(L) == TILED and np.array_equal(got, ref_resize(img, 128, 128))
 
 
@@ -156,30 +125,23 @@ def test_maps_at_the_limits_of_the_header(pkg, L, torch_cuda, c):
         for border in BORDERS:
             assert takes_tiled(img.shape, m, wo, ho, BILINEAR, border), (name, border)
             for mode, kernel in ((BILINEAR, TILED), (NEAREST, GENERIC)):
-                got = gpu_warp_run(pkg, L, torch_cuda, img, m, wo, ho, mode, border, LIMIT_FILL)
+                got = gpu_run(WARP, pkg, L, torch_cuda, img, (m, wo, ho, mode, border, LIMIT_FILL))
                 assert last(L) == kernel, (name, border, mode)
                 assert np.array_equal(got, refs[name, mode, border]), (name, border, mode)
 
 
 def test_x2_clamp_warp_equals_the_resize(pkg, L, torch_cuda):
     img = np.random.default_rng(9).integers(0, 256, size=(2, 45, 64, 3), dtype=np.uint8)
-    got = gpu_warp_run(pkg, L, torch_cuda, img, scale_matrix(2, 1), 128, 90, BILINEAR, CLAMP)
+    got = gpu_run(WARP, pkg, L, torch_cuda, img, (scale_matrix(2, 1), 128, 90, BILINEAR, CLAMP, 0))
     assert last(L) == TILED
     assert np.array_equal(got, pkg.resize(img, (128, 90)))
     assert L.mi_blur_last_kernel().decode() == "blur_resize_tiled_kernel"
 
 
 def test_gpu_equals_cpu_device_on_the_synthetic_stream(pkg, L, torch_cuda):
-    shape = (4, 240, 320, 3)
-    host = np.empty(shape, np.uint8)
-    L.mi_blur_fill_synthetic(host.ctypes.data, 320, 240, 3, 0, 4, 4)
-    for m, (wo, ho), border in ((rotation_m(320, 240, 30.0), (320, 240), CONSTANT), (quantise([0.8, 0.3, -20.5, -0.2, 0.7, 31.25]), (400, 300), CLAMP),
-                                (scale_matrix(1, 2), (160, 120), CLAMP)):
-        for mode in (BILINEAR, NEAREST):
-            want = cpu_warp_run(pkg, L, host, m, wo, ho, mode, border, 128, 4)
-            assert np.array_equal(want, ref_warp(host, m, wo, ho, mode, border, 128)), (m, mode)
-            assert np.array_equal(gpu_warp_run(pkg, L, torch_cuda, host, m, wo, ho, mode, border, 128), want), (m, mode)
-            assert last(L) == (TILED if takes_tiled(shape, m, wo, ho, mode, border) else GENERIC)
+    cases = ((rotation_m(320, 240, 30.0), (320, 240), CONSTANT), (quantise([0.8, 0.3, -20.5, -0.2, 0.7, 31.25]), (400, 300), CLAMP),
+             (scale_matrix(1, 2), (160, 120), CLAMP))
+    check_synthetic_stream(WARP, pkg, L, torch_cuda, [(m, wo, ho, mode, border, 128) for m, (wo, ho), border in cases for mode in (BILINEAR, NEAREST)])
 
 
 @pytest.mark.parametrize("target", [(160, 120), (100, 75)], ids=lambda t: "x".join(map(str, t)))
@@ -189,42 +151,9 @@ def test_gpu_context(pkg, L, torch_cuda, target):
     wo, ho = target
     img = np.random.default_rng(13).integers(0, 256, size=shape, dtype=np.uint8)
     m = rotation_m(w, h, 30.0)
-    want = ref_warp(img, m, wo, ho, BILINEAR, CONSTANT, 40)
     kernel = TILED if takes_tiled(shape, m, wo, ho) else GENERIC
     assert (kernel == TILED) == (target == (160, 120))              # 100 x 3 bytes is no whole number of chunks
-    with pkg.Context(0, w, h, c, 1, max_batch=n, n_slots=3) as ctx:
-        ctx.set_warp(make_warp(pkg, m, wo, ho, BILINEAR, CONSTANT, 40))
-        out = np.full(want.size + 64, 0xA5, np.uint8)
-        ctx.submit(img.ctypes.data, out.ctypes.data, n)                  # pageable
-        t = ctx.sync()
-        assert np.array_equal(out[:want.size].reshape(want.shape), want) and (out[want.size:] == 0xA5).all()
-        assert last(L) == kernel
-        assert t["bytes_alg"] == img.size + want.size
-        cap = want.size + 4096                                           # pinned, in place, with guard bytes behind the output
-        pin_in, pin_out = L.mi_blur_host_alloc(img.size), L.mi_blur_host_alloc(cap)
-        try:
-            a = np.ctypeslib.as_array((C.c_uint8 * img.size).from_address(pin_in)).reshape(img.shape)
-            b = np.ctypeslib.as_array((C.c_uint8 * cap).from_address(pin_out))
-            a[:] = img
-            z0 = L.mi_blur_zero_copy_launches(ctx.h)
-            for _ in range(3):
-                b[:] = 0xA5
-                ctx.submit(pin_in, pin_out, n)
-                ctx.sync()
-                assert np.array_equal(b[:want.size].reshape(want.shape), want) and (b[want.size:] == 0xA5).all()
-            assert L.mi_blur_zero_copy_launches(ctx.h) == z0 + 3
-            assert last(L) == kernel
-            pitch = w * c
-            assert L.mi_blur_submit_band(ctx.h, pin_in, pin_out, 60, 2, 2) == pkg.ERR_UNSUPPORTED
-            assert L.mi_blur_submit_bands(ctx.h, pin_in, pin_out, n, h * pitch, 60, 2, 2) == pkg.ERR_UNSUPPORTED
-            assert L.mi_blur_submit_planar(ctx.h, pin_in, pin_out, n, 0) == pkg.ERR_UNSUPPORTED
-            ctx.resident_alloc(2)
-            assert L.mi_blur_resident_run(ctx.h, 2, 1, 0) == pkg.ERR_UNSUPPORTED
-            assert L.mi_blur_resident_run_fused(ctx.h, 2, 1, 0) == pkg.ERR_UNSUPPORTED
-            assert L.mi_blur_ctx_set_warp(ctx.h, C.byref(make_warp(pkg, m, wo, ho))) == pkg.ERR_STATE
-        finally:
-            L.mi_blur_host_free(pin_in)
-            L.mi_blur_host_free(pin_out)
+    check_gpu_context(WARP, pkg, L, img, (m, wo, ho, BILINEAR, CONSTANT, 40), kernel)
 
 
 def test_gpu_context_enlarging(pkg, L, torch_cuda):
@@ -234,35 +163,7 @@ def test_gpu_context_enlarging(pkg, L, torch_cuda):
     wo, ho = 320, 240
     img = np.random.default_rng(14).integers(0, 256, size=shape, dtype=np.uint8)
     m = rotation_m(w, h, 30.0, 2.0)
-    want = ref_warp(img, m, wo, ho, BILINEAR, CONSTANT, 40)
-    assert want.size == 4 * img.size and takes_tiled(shape, m, wo, ho)
-    assert (want != 40).mean() > 0.5                                     # mostly image, not fill
-    with pkg.Context(0, w, h, c, 1, max_batch=n, n_slots=3) as ctx:
-        ctx.set_warp(make_warp(pkg, m, wo, ho, BILINEAR, CONSTANT, 40))
-        cap = want.size + 4096                                           # guard bytes behind the output, pageable and pinned
-        out = np.full(cap, 0xA5, np.uint8)
-        ctx.submit(img.ctypes.data, out.ctypes.data, n)                  # pageable
-        t = ctx.sync()
-        assert np.array_equal(out[:want.size].reshape(want.shape), want) and (out[want.size:] == 0xA5).all()
-        assert last(L) == TILED
-        assert t["bytes_alg"] == img.size + want.size
-        pin_in, pin_out = L.mi_blur_host_alloc(img.size), L.mi_blur_host_alloc(cap)
-        try:
-            a = np.ctypeslib.as_array((C.c_uint8 * img.size).from_address(pin_in)).reshape(img.shape)
-            b = np.ctypeslib.as_array((C.c_uint8 * cap).from_address(pin_out))
-            a[:] = img
-            z0 = L.mi_blur_zero_copy_launches(ctx.h)
-            for k in range(3):
-                b[:] = 0xA5
-                ctx.submit(pin_in, pin_out, n)
-                t = ctx.sync()
-                assert np.array_equal(b[:want.size].reshape(want.shape), want) and (b[want.size:] == 0xA5).all()
-                assert t["bytes_alg"] == (k + 2) * (img.size + want.size)   # cumulative since the context was made
-            assert L.mi_blur_zero_copy_launches(ctx.h) == z0 + 3
-            assert last(L) == TILED
-        finally:
-            L.mi_blur_host_free(pin_in)
-            L.mi_blur_host_free(pin_out)
+    check_gpu_context_enlarging(WARP, pkg, L, img, (m, wo, ho, BILINEAR, CONSTANT, 40), fill=40)
 
 
 def test_numpy_functions_on_the_gpu(pkg, L, torch_cuda):

@@ -4,21 +4,20 @@ the numpy restatement of the header's definition (warp_ref.py), independent of t
 unless stated."""
 import ctypes as C
 import os
-import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
-from filter_harness import MEDIAN, cpu_run
+from filter_harness import MEDIAN, cpu_run as cpu_run_same_size
+from resample_harness import (WARP, check_cpu_context, check_cpu_run_refuses, check_ctx_set_refuses, check_enqueue_invalid_before_no_device,
+                              check_setters_replace_each_other, cpu_run, needs_gxx, no_scratch, run_sanitized, sampler_rows, size_rows)
 from resize_ref import ref_resize
-from warp_ref import (BILINEAR, CLAMP, CONSTANT, EXTREME, LIMIT_FILL, LIMIT_MAPS, LIN_MAX, MAX_DIM, NEAREST, OFF_MAX, Q, corner_pixels, cpu_warp_run,
+from warp_ref import (BILINEAR, CLAMP, CONSTANT, EXTREME, LIMIT_FILL, LIMIT_MAPS, LIN_MAX, MAX_DIM, NEAREST, OFF_MAX, Q, corner_pixels,
                       extreme_id, float_warp, identity, in_the_admitted_region, invert, limit_out, limit_references, make_warp, max_footprint,
                       narrow_cases, outside_share, quantise, ref_coord, ref_warp, ref_warp_band, rot90_matrix, rotation_forward, rotation_m,
                       scale_matrix, takes_tiled)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MODES = (BILINEAR, NEAREST)
 BORDERS = (CLAMP, CONSTANT)
 
@@ -63,7 +62,7 @@ def test_properties_of_the_definition(pkg, L):
     n, h, w, c = img.shape
     for mode in MODES:
         for border in BORDERS:
-            run = lambda m, wo, ho, fill=7: cpu_warp_run(pkg, L, img, m, wo, ho, mode, border, fill)
+            run = lambda m, wo, ho, fill=7: cpu_run(WARP, pkg, L, img, (m, wo, ho, mode, border, fill), 2)
             assert np.array_equal(run(identity(), w, h), img)                                      # the identity
             # the four right-angle rotations, each from the header's rot90 matrix composed with itself
             assert np.array_equal(run(rot90_matrix(w), h, w), np.rot90(img, 1, axes=(1, 2)))
@@ -89,8 +88,8 @@ def test_properties_of_the_definition(pkg, L):
     flat = np.full((1, 9, 16, 2), 255, np.uint8)
     for m in (rotation_m(16, 9, 33.0), shear_m(0.4, -0.3, 2.5, -1.25), scale_matrix(2, 1), identity(-40, 3)):
         for mode in MODES:
-            assert (cpu_warp_run(pkg, L, flat, m, 21, 14, mode, CLAMP, 0) == 255).all()
-            assert (cpu_warp_run(pkg, L, flat, m, 21, 14, mode, CONSTANT, 255) == 255).all()
+            assert (cpu_run(WARP, pkg, L, flat, (m, 21, 14, mode, CLAMP, 0), 2) == 255).all()
+            assert (cpu_run(WARP, pkg, L, flat, (m, 21, 14, mode, CONSTANT, 255), 2) == 255).all()
             assert (ref_warp(flat, m, 21, 14, mode, CONSTANT, 255) == 255).all()
 
 
@@ -102,7 +101,7 @@ def test_clamp_scale_equals_the_resize(pkg, L, ratio):
     want = ref_resize(img, wo, ho)
     m = scale_matrix(num, den)
     assert np.array_equal(ref_warp(img, m, wo, ho, BILINEAR, CLAMP), want)
-    assert np.array_equal(cpu_warp_run(pkg, L, img, m, wo, ho, BILINEAR, CLAMP), want)
+    assert np.array_equal(cpu_run(WARP, pkg, L, img, (m, wo, ho, BILINEAR, CLAMP, 0), 2), want)
 
 
 @pytest.mark.parametrize("case", ["rot30", "rot-17.3", "rot45x1.3", "shear", "shear2"])
@@ -119,7 +118,7 @@ def test_bilinear_is_within_the_bound_of_float_bilinear(pkg, L, case):
     for border in BORDERS:
         real = float_warp(img, m, 61, 40, border, 90)
         restated = ref_warp(img, m, 61, 40, BILINEAR, border, 90)
-        assert np.array_equal(cpu_warp_run(pkg, L, img, m, 61, 40, BILINEAR, border, 90), restated)
+        assert np.array_equal(cpu_run(WARP, pkg, L, img, (m, 61, 40, BILINEAR, border, 90), 2), restated)
         assert np.abs(restated.astype(np.float64) - real).max() < 0.5 + 255 * 2.0 ** -11
 
 
@@ -140,7 +139,7 @@ def test_cpu_run_matches_the_restatement(pkg, L, shape):
                 want = ref_warp(img, m, wo, ho, mode, border, 201)
                 assert want.shape == (n, ho, wo, c)
                 for nt in (1, 3):
-                    assert np.array_equal(cpu_warp_run(pkg, L, img, m, wo, ho, mode, border, 201, nt), want), (shape, m, wo, ho, mode, border, nt)
+                    assert np.array_equal(cpu_run(WARP, pkg, L, img, (m, wo, ho, mode, border, 201), nt), want), (shape, m, wo, ho, mode, border, nt)
 
 
 def test_band_reference_equals_the_whole_image_reference():
@@ -180,7 +179,7 @@ def test_cpu_device_on_extreme_shapes(pkg, L, case):
     for mode in MODES:
         for border in BORDERS:
             want = ref_warp(img, m, wo, ho, mode, border, 173)
-            assert np.array_equal(cpu_warp_run(pkg, L, img, m, wo, ho, mode, border, 173, 4), want), (mode, border)
+            assert np.array_equal(cpu_run(WARP, pkg, L, img, (m, wo, ho, mode, border, 173), 4), want), (mode, border)
             if quarter_turns is not None:
                 assert np.array_equal(want, np.rot90(img, quarter_turns, axes=(1, 2)))
 
@@ -191,7 +190,7 @@ def test_cpu_device_on_inputs_of_one_chunk_per_row(pkg, L):
         for mode in MODES:
             for border in BORDERS:
                 want = ref_warp(img, m, wo, ho, mode, border, 173)
-                assert np.array_equal(cpu_warp_run(pkg, L, img, m, wo, ho, mode, border, 173), want), (img.shape, name, mode, border)
+                assert np.array_equal(cpu_run(WARP, pkg, L, img, (m, wo, ho, mode, border, 173), 2), want), (img.shape, name, mode, border)
 
 
 @pytest.mark.parametrize("c", [1, 2, 3, 4])
@@ -203,7 +202,7 @@ def test_cpu_device_on_maps_at_the_limits_of_the_header(pkg, L, c):
         coords_equal_the_restatement(pkg, L, m, wo, ho)
         for mode in MODES:
             for border in BORDERS:
-                got = cpu_warp_run(pkg, L, img, m, wo, ho, mode, border, LIMIT_FILL, 3)
+                got = cpu_run(WARP, pkg, L, img, (m, wo, ho, mode, border, LIMIT_FILL), 3)
                 assert np.array_equal(got, refs[name, mode, border]), (name, mode, border)
 
 
@@ -222,10 +221,10 @@ def test_set_matrix_and_rotation(pkg, L):
         assert max(abs(x - y) for x, y in zip(a.m, b.m)) <= 1              # the same inverse, computed twice in double
         assert max(abs(x - y) for x, y in zip(b.m, quantise(inv))) == 0
         # the forward and the inverse matrix give the same warp (bytes: the library's own inverse against numpy's)
-        got_a = cpu_warp_run(pkg, L, img, list(a.m), 44, 30)
+        got_a = cpu_run(WARP, pkg, L, img, (list(a.m), 44, 30, BILINEAR, CONSTANT, 0), 2)
         assert np.array_equal(got_a, ref_warp(img, list(a.m), 44, 30))
         if list(a.m) == list(b.m):
-            assert np.array_equal(got_a, cpu_warp_run(pkg, L, img, list(b.m), 44, 30))
+            assert np.array_equal(got_a, cpu_run(WARP, pkg, L, img, (list(b.m), 44, 30, BILINEAR, CONSTANT, 0), 2))
     # a right angle about the centre of a square is exact: np.rot90
     sq = np.random.default_rng(6).integers(0, 256, size=(1, 12, 12, 2), dtype=np.uint8)
     assert np.array_equal(pkg.rotate(sq, 90.0, device=pkg.DEVICE_CPU), np.rot90(sq, 1, axes=(1, 2)))
@@ -246,38 +245,25 @@ def test_set_matrix_and_rotation(pkg, L):
     assert list(wp.m) == [LIN_MAX, 0, OFF_MAX, 0, -LIN_MAX, -OFF_MAX]
 
 
-def bad_calls(pkg, call):
-    """call(in, out, w, h, c, warp) -> status: every argument set the header calls invalid."""
-    a = np.zeros((8, 8, 3), np.uint8)
-    b = np.zeros((16, 16, 3), np.uint8)
-    mk = lambda wo=16, ho=16, mode=BILINEAR, border=CONSTANT, fill=0, m=None: make_warp(pkg, m or identity(), wo, ho, mode, border, fill)
-    good = mk()
-    ref = lambda s: None if s is None else C.byref(s)
-    ia, ib = a.ctypes.data, b.ctypes.data
-    bad = [(ia, ib, 8, 8, 3, None), (None, ib, 8, 8, 3, good), (ia, None, 8, 8, 3, good), (ia, ia, 8, 8, 3, good)]
-    for kw in [dict(wo=0), dict(ho=0), dict(wo=-3), dict(ho=-1), dict(wo=MAX_DIM + 1, ho=1), dict(wo=1, ho=MAX_DIM + 1), dict(mode=2), dict(mode=-1),
-               dict(border=2), dict(border=-1), dict(fill=-1), dict(fill=256)]:
-        bad.append((ia, ib, 8, 8, 3, mk(**kw)))
+def mk(pkg, wo=16, ho=16, mode=BILINEAR, border=CONSTANT, fill=0, m=None):
+    return make_warp(pkg, m or identity(), wo, ho, mode, border, fill)
+
+
+def bad_rows(pkg):
+    """(good, rows) for resample_harness.bad_calls; the warp's own rows: every entry of m one past its limit, either sign."""
+    make = lambda **kw: mk(pkg, **kw)
+    rows = size_rows(make) + sampler_rows(make)
     for i in range(6):
         lim = OFF_MAX if i % 3 == 2 else LIN_MAX
         for v in (lim + 1, -lim - 1):
             m = identity()
             m[i] = v
-            bad.append((ia, ib, 8, 8, 3, mk(m=m)))
-    for w, h, c in [(0, 8, 3), (8, 0, 3), (8, 8, 0), (-1, 8, 3), (MAX_DIM + 1, 1, 1), (1, MAX_DIM + 1, 1)]:
-        bad.append((ia, ib, w, h, c, good))
-    bad.append((ia, ib, 8, 8, 3, mk(MAX_DIM, MAX_DIM)))                     # the output image: 3 GiB, over the per-image limit
-    bad.append((ia, ib, 8, 8, 40000, mk(MAX_DIM, 1)))                       # the output row: over INT_MAX / 2
-    for i, o, w, h, c, r in bad:
-        assert call(i, o, w, h, c, ref(r)) == pkg.ERR_INVALID, (i, o, w, h, c, r and (r.out_width, r.out_height, r.mode, r.border, r.fill, list(r.m)))
-    return a, b, good
+            rows.append((8, 8, 3, (C.byref(mk(pkg, m=m)),)))
+    return (C.byref(mk(pkg)),), rows
 
 
 def test_cpu_run_refuses_invalid_arguments(pkg, L):
-    a, b, r = bad_calls(pkg, lambda i, o, w, h, c, r: L.mi_blur_cpu_run_warp(i, o, w, h, c, 1, r, 1))
-    assert L.mi_blur_cpu_run_warp(a.ctypes.data, b.ctypes.data, 8, 8, 3, -1, C.byref(r), 1) == pkg.ERR_INVALID
-    assert L.mi_blur_cpu_run_warp(a.ctypes.data, b.ctypes.data, 8, 8, 3, 1, C.byref(r), 1) == pkg.OK
-    assert L.mi_blur_cpu_run_warp(a.ctypes.data, b.ctypes.data, 8, 8, 3, 0, C.byref(r), 1) == pkg.OK
+    a, b = check_cpu_run_refuses(WARP, pkg, L, *bad_rows(pkg))
     lim = make_warp(pkg, [LIN_MAX, -LIN_MAX, -OFF_MAX, 0, 0, OFF_MAX], 16, 16, BILINEAR, CLAMP, 255)      # the limits themselves are valid
     assert L.mi_blur_cpu_run_warp(a.ctypes.data, b.ctypes.data, 8, 8, 3, 1, C.byref(lim), 1) == pkg.OK
 
@@ -285,37 +271,17 @@ def test_cpu_run_refuses_invalid_arguments(pkg, L):
 def test_enqueue_invalid_comes_before_no_device(pkg, L):
     """Every argument is checked before a device is asked for; without a GPU a good call is ERR_NO_DEVICE (with one, the
     null stream of an empty batch is MI_BLUR_OK)."""
-    a, b, r = bad_calls(pkg, lambda i, o, w, h, c, r: L.mi_blur_enqueue_warp(i, o, w, h, c, 1, r, None))
-    assert L.mi_blur_enqueue_warp(a.ctypes.data, b.ctypes.data, 8, 8, 3, -1, C.byref(r), None) == pkg.ERR_INVALID
-    if L.mi_blur_device_count() <= 0:
-        assert L.mi_blur_enqueue_warp(a.ctypes.data, b.ctypes.data, 8, 8, 3, 1, C.byref(r), None) == pkg.ERR_NO_DEVICE
-        assert L.mi_blur_enqueue_warp(a.ctypes.data, b.ctypes.data, 8, 8, 3, 0, C.byref(r), None) == pkg.ERR_NO_DEVICE
-    else:
-        assert L.mi_blur_enqueue_warp(a.ctypes.data, b.ctypes.data, 8, 8, 3, 0, C.byref(r), None) == pkg.OK
+    check_enqueue_invalid_before_no_device(WARP, pkg, L, *bad_rows(pkg))
 
 
 def test_ctx_set_refuses_invalid_arguments(pkg, L):
     """The table of mi_blur_ctx_set_resize: a null context or struct is ERR_INVALID whatever the state, an invalid struct
     ERR_INVALID before the first submit, anything ERR_STATE after it; a refused set leaves the filter in place."""
-    mk = lambda wo=16, ho=16, mode=BILINEAR, border=CONSTANT, fill=0, m=None: make_warp(pkg, m or identity(), wo, ho, mode, border, fill)
-    with pkg.Context(pkg.DEVICE_CPU, 8, 8, 3, 1, max_batch=1) as ctx:
-        assert L.mi_blur_ctx_set_warp(None, C.byref(mk())) == pkg.ERR_INVALID
-        assert L.mi_blur_ctx_set_warp(ctx.h, None) == pkg.ERR_INVALID
-        over = identity()
-        over[5] = OFF_MAX + 1
-        for bad in [mk(wo=0), mk(ho=0), mk(MAX_DIM + 1, 1), mk(1, MAX_DIM + 1), mk(mode=2), mk(border=2), mk(fill=256), mk(fill=-1), mk(m=over), mk(MAX_DIM, MAX_DIM)]:
-            assert L.mi_blur_ctx_set_warp(ctx.h, C.byref(bad)) == pkg.ERR_INVALID
-        img = np.random.default_rng(2).integers(0, 256, size=(1, 8, 8, 3), dtype=np.uint8)   # refused sets leave the box blur in place
-        out, box = np.empty_like(img), np.empty_like(img)
-        ctx.submit(img.ctypes.data, out.ctypes.data, 1)
-        t = ctx.sync()
-        assert L.mi_blur_cpu_run(img.ctypes.data, box.ctypes.data, 8, 8, 3, 1, 1, 1) == pkg.OK
-        assert np.array_equal(out, box) and t["bytes_alg"] == 2 * img.size
-        assert L.mi_blur_ctx_set_warp(ctx.h, C.byref(mk())) == pkg.ERR_STATE
-        assert L.mi_blur_ctx_set_warp(ctx.h, C.byref(mk(wo=0))) == pkg.ERR_STATE
-        assert L.mi_blur_ctx_set_warp(ctx.h, None) == pkg.ERR_INVALID
-    with pkg.Context(pkg.DEVICE_CPU, MAX_DIM + 1, 2, 1, 1, max_batch=1) as wide:      # the context's own size over MAX_DIM
-        assert L.mi_blur_ctx_set_warp(wide.h, C.byref(mk())) == pkg.ERR_INVALID
+    over = identity()
+    over[5] = OFF_MAX + 1
+    bad = [dict(wo=0), dict(ho=0), dict(wo=MAX_DIM + 1, ho=1), dict(wo=1, ho=MAX_DIM + 1), dict(mode=2), dict(border=2), dict(fill=256), dict(fill=-1), dict(m=over),
+           dict(wo=MAX_DIM, ho=MAX_DIM)]
+    check_ctx_set_refuses(WARP, pkg, L, (C.byref(mk(pkg)),), [(C.byref(mk(pkg, **kw)),) for kw in bad])
 
 
 @pytest.mark.parametrize("target", [(42, 37), (63, 74), (25, 22)], ids=lambda t: "x".join(map(str, t)))
@@ -326,26 +292,7 @@ def test_cpu_context(pkg, L, target):
     m = rotation_m(w, h, 25.0, 1.1)
     for mode in MODES:
         for border in BORDERS:
-            want = ref_warp(img, m, wo, ho, mode, border, 33)
-            with pkg.Context(pkg.DEVICE_CPU, w, h, c, 1, max_batch=n, n_threads=3) as ctx:
-                wp = make_warp(pkg, m, wo, ho, mode, border, 33)
-                assert L.mi_blur_ctx_set_warp(ctx.h, C.byref(wp)) == pkg.OK
-                C.memset(C.byref(wp), 0xFF, C.sizeof(wp))                    # the context keeps a copy
-                out = np.full(want.size + 128, 0xA5, np.uint8)
-                ctx.submit(img.ctypes.data, out.ctypes.data + 64, n)         # pageable memory, guards either side
-                t = ctx.sync()
-                assert np.array_equal(out[64:64 + want.size].reshape(want.shape), want)
-                assert (out[:64] == 0xA5).all() and (out[64 + want.size:] == 0xA5).all()
-                assert t["bytes_alg"] == img.size + want.size and t["images"] == n
-                pitch = w * c
-                o = np.zeros_like(img)
-                assert L.mi_blur_submit_band(ctx.h, img.ctypes.data, o.ctypes.data, 20, 2, 2) == pkg.ERR_UNSUPPORTED
-                assert L.mi_blur_submit_bands(ctx.h, img.ctypes.data, o.ctypes.data, n, h * pitch, 20, 2, 2) == pkg.ERR_UNSUPPORTED
-                assert L.mi_blur_submit_planar(ctx.h, img.ctypes.data, o.ctypes.data, n, 0) == pkg.ERR_UNSUPPORTED
-                assert L.mi_blur_resident_run(ctx.h, 1, 1, 0) == pkg.ERR_UNSUPPORTED
-                assert L.mi_blur_resident_run_fused(ctx.h, 1, 1, 0) == pkg.ERR_UNSUPPORTED
-                assert not o.any()
-                assert L.mi_blur_ctx_set_warp(ctx.h, C.byref(make_warp(pkg, m, wo, ho, mode, border, 33))) == pkg.ERR_STATE
+            check_cpu_context(WARP, pkg, L, img, (m, wo, ho, mode, border, 33))
 
 
 def test_setters_replace_each_other(pkg, L):
@@ -353,23 +300,11 @@ def test_setters_replace_each_other(pkg, L):
     n, h, w, c = img.shape
     m = rotation_m(w, h, -40.0)
 
-    def run(setters, want):
-        with pkg.Context(pkg.DEVICE_CPU, w, h, c, 1, max_batch=n) as ctx:
-            for s in setters:
-                s(ctx)
-            out = np.full(want.size + 64, 0xA5, np.uint8)
-            ctx.submit(img.ctypes.data, out.ctypes.data, n)
-            t = ctx.sync()
-            assert np.array_equal(out[:want.size].reshape(want.shape), want) and (out[want.size:] == 0xA5).all()
-            return t
     warp = lambda ctx: ctx.set_warp(make_warp(pkg, m, 40, 31, BILINEAR, CLAMP))
     median = lambda ctx: ctx.set_median(1)
     resize = lambda ctx: ctx.set_resize(30, 11)
-    rot, med, small = ref_warp(img, m, 40, 31, BILINEAR, CLAMP), cpu_run(MEDIAN, pkg, L, img, 1, 1), ref_resize(img, 30, 11)
-    assert run([warp, median], med)["bytes_alg"] == 2 * img.size          # the last one wins
-    assert run([median, warp], rot)["bytes_alg"] == img.size + rot.size
-    assert run([warp, resize], small)["bytes_alg"] == img.size + small.size
-    assert run([resize, warp], rot)["bytes_alg"] == img.size + rot.size
+    rot, med, small = ref_warp(img, m, 40, 31, BILINEAR, CLAMP), cpu_run_same_size(MEDIAN, pkg, L, img, 1, 1), ref_resize(img, 30, 11)
+    check_setters_replace_each_other(pkg, L, img, [([warp, median], med), ([median, warp], rot), ([warp, resize], small), ([resize, warp], rot)])   # the last one wins
 
 
 def test_numpy_functions_on_the_cpu_device(pkg, L):
@@ -447,7 +382,7 @@ def test_hosts_refuse_rotate_with_other_filters(pkg, tmp_path):
 
 
 def test_host_rotates_on_the_cpu_device(pkg, tmp_path):
-    from filter_harness import read_ppm, write_ppm
+    from resample_harness import read_ppm, write_ppm
     pkg.build_native()
     het = os.path.join(pkg.APPS, "heterogeneous_blur")
     img = np.random.default_rng(19).integers(0, 256, size=(48, 64, 3), dtype=np.uint8)
@@ -465,38 +400,16 @@ def test_host_rotates_on_the_cpu_device(pkg, tmp_path):
 def test_tiled_kernels_use_no_scratch(pkg, tmp_path):
     """Compiles warp_kernels.hip to gfx950 assembly (no GPU needed): the taps are read from LDS at run-time addresses, but
     no tiled instantiation may spill or index registers at run time."""
-    out = tmp_path / "k.s"
-    r = subprocess.run([pkg.HIPCC, f"--offload-arch={pkg.ARCH}", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-o", str(out),
-                        os.path.join(pkg.CSRC, "warp_kernels.hip")], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    text = out.read_text()
-    kernels = re.findall(r"\.amdhsa_kernel (\S*blur_warp_tiled_kernel\S*)(.*?)\.end_amdhsa_kernel", text, re.S)
-    assert len(kernels) == 4, [k for k, _ in kernels]                        # 1-4 channels
-    for name, body in kernels:
-        assert re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", body).group(1) == "0", name
-        assert re.search(r"\.amdhsa_group_segment_fixed_size (\d+)", body).group(1) == "0", name     # all LDS is dynamic: sized per launch
+    no_scratch(pkg, tmp_path, "warp_kernels.hip", "blur_warp_tiled_kernel", 4, dynamic_lds_only=True)       # 1-4 channels; all LDS is sized per launch
 
 
-@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
+@needs_gxx
 def test_cpu_warp_clean_under_asan_ubsan(pkg, tmp_path):
-    exe = tmp_path / "san_warp"
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           "-fno-omit-frame-pointer", "-I", pkg.CSRC, os.path.join(ROOT, "tests", "san_warp.cpp"),
-           os.path.join(pkg.CSRC, "cpu_device.cpp"), "-lpthread", "-o", str(exe)]
-    subprocess.run(cmd, check=True, capture_output=True)
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "random and edge warp cases clean" in r.stdout, r.stdout + r.stderr
-    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr
+    run_sanitized(pkg, tmp_path, ("san_warp.cpp", "cpu_device.cpp"), ["random and edge warp cases clean"])
 
 
-@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
+@needs_gxx
 def test_tile_geometry_stays_inside_the_lds_under_asan_ubsan(pkg, tmp_path):
     """The footprint and tap arithmetic the resize and warp tiled kernels share with their host-side LDS sizing
     (filter.h), walked tile by tile on the CPU: tests/san_tile_bounds.cpp."""
-    exe = tmp_path / "san_tile_bounds"
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           "-fno-omit-frame-pointer", "-I", pkg.CSRC, os.path.join(ROOT, "tests", "san_tile_bounds.cpp"), "-o", str(exe)]
-    subprocess.run(cmd, check=True, capture_output=True)
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "taps inside their LDS" in r.stdout and "FAILED" not in r.stdout, r.stdout + r.stderr
-    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr
+    run_sanitized(pkg, tmp_path, ("san_tile_bounds.cpp",), ["taps inside their LDS"])

@@ -1,32 +1,21 @@
 """The perspective warp on the GPU (mi_blur_enqueue_warp_perspective, mi_blur_ctx_set_warp_perspective,
 warp_perspective(), the host's --perspective): exact bytes against the numpy restatement of the header's definition
 (warp_perspective_ref.py), and which of the two kernels took each launch against the restated eligibility rule."""
-import ctypes as C
 import subprocess
 
 import numpy as np
 import pytest
 
-from filter_harness import apps, read_ppm, torch_cuda, write_ppm  # noqa: F401
-from warp_ref import LIMIT_FILL, NARROW_HEIGHTS, NARROW_N, NARROW_ROWS, impulse_rows, limit_out, tile_geometry
-from warp_perspective_ref import (BIG_QUAD, BILINEAR, CLAMP, CONSTANT, EXTREME, LIMIT_MAPS, NEAREST, Q, affine_h, cpu_persp_run, gpu_persp_run,
-                                  limit_references, make_persp, max_footprint, named_maps, named_quads, out_corners, quad_h, ref_warp, set_matrix,
-                                  takes_tiled, tile_footprints, valid)
-from test_warp_gpu import TILED_SHAPES, edge_image
+from resample_harness import (PERSP, apps, blocks, check_gpu_context, check_gpu_context_enlarging, check_pointer_offsets, check_synthetic_stream,  # noqa: F401
+                              gpu_run, last, read_ppm, torch_cuda, write_ppm)
+from warp_ref import LIMIT_FILL, NARROW_HEIGHTS, NARROW_N, NARROW_ROWS, TILED_SHAPES, edge_image, impulse_rows, limit_out
+from warp_perspective_ref import (BIG_QUAD, BILINEAR, CLAMP, CONSTANT, EXTREME, LIMIT_MAPS, NEAREST, Q, affine_h, limit_references, max_footprint,
+                                  named_maps, named_quads, out_corners, quad_h, ref_warp, set_matrix, takes_tiled, valid)
 
 pytestmark = pytest.mark.gpu
 
-TILED, GENERIC = "blur_warp_persp_tiled_kernel", "blur_warp_persp_generic_kernel"
+TILED, GENERIC = PERSP.tiled, PERSP.generic
 BORDERS = (CLAMP, CONSTANT)
-
-
-def last(L):
-    return L.mi_blur_last_kernel().decode()
-
-
-def blocks(n, wo, ho, c):
-    ncols, cpr, rows = tile_geometry(wo, ho, c)
-    return n * -(-cpr // ncols) * -(-ho // rows)
 
 
 @pytest.mark.parametrize("case", TILED_SHAPES, ids=lambda c: "x".join(map(str, c[0])) + f"-{c[1][0]}x{c[1][1]}")
@@ -37,7 +26,7 @@ def test_aligned_launches_take_the_tiled_kernel(pkg, L, torch_cuda, case):
     for name, hh in named_maps(w, h, wo, ho).items():
         for border in BORDERS:
             assert valid(hh, wo, ho) and takes_tiled(shape, hh, wo, ho, BILINEAR, border), (name, border)
-            got = gpu_persp_run(pkg, L, torch_cuda, img, hh, wo, ho, BILINEAR, border, 173)
+            got = gpu_run(PERSP, pkg, L, torch_cuda, img, (hh, wo, ho, BILINEAR, border, 173))
             assert last(L) == TILED, (name, border)
             assert np.array_equal(got, ref_warp(img, hh, wo, ho, BILINEAR, border, 173)), (name, border)
 
@@ -51,7 +40,7 @@ def test_xcd_remap_on_and_off(pkg, L, torch_cuda):
             img = edge_image(rng, n, h, w, c)
             hh = named_maps(w, h, wo, ho)["tilt"]
             assert takes_tiled(img.shape, hh, wo, ho)
-            got = gpu_persp_run(pkg, L, torch_cuda, img, hh, wo, ho, BILINEAR, CONSTANT, 60)
+            got = gpu_run(PERSP, pkg, L, torch_cuda, img, (hh, wo, ho, BILINEAR, CONSTANT, 60))
             assert last(L) == TILED and np.array_equal(got, ref_warp(img, hh, wo, ho, BILINEAR, CONSTANT, 60)), (c, n)
 
 
@@ -66,7 +55,7 @@ def test_maps_at_the_limits_of_the_header(pkg, L, torch_cuda, c):
         for border in BORDERS:
             assert takes_tiled(img.shape, hh, wo, ho, BILINEAR, border), (name, border)
             for mode, kernel in ((BILINEAR, TILED), (NEAREST, GENERIC)):
-                got = gpu_persp_run(pkg, L, torch_cuda, img, hh, wo, ho, mode, border, LIMIT_FILL)
+                got = gpu_run(PERSP, pkg, L, torch_cuda, img, (hh, wo, ho, mode, border, LIMIT_FILL))
                 assert last(L) == kernel, (name, border, mode)
                 assert np.array_equal(got, refs[name, mode, border]), (name, border, mode)
 
@@ -85,18 +74,12 @@ def test_other_launches_take_the_generic_kernel(pkg, L, torch_cuda):
         for hh in maps:
             for border in BORDERS:
                 assert valid(hh, wo, ho) and not takes_tiled(shape, hh, wo, ho, mode, border)
-                got = gpu_persp_run(pkg, L, torch_cuda, img, hh, wo, ho, mode, border, 99)
+                got = gpu_run(PERSP, pkg, L, torch_cuda, img, (hh, wo, ho, mode, border, 99))
                 assert last(L) == GENERIC, (shape, wo, ho, mode)
                 assert np.array_equal(got, ref_warp(img, hh, wo, ho, mode, border, 99)), (shape, hh, wo, ho, mode, border)
-    # aligned shape, pointers off 16 bytes: guards checked inside gpu_persp_run
+    # aligned shape, pointers off 16 bytes: guards checked inside gpu_run
     img = edge_image(rng, 2, 35, 48, 2)
-    hh = named_maps(48, 35, 56, 70)["tilt"]
-    want = ref_warp(img, hh, 56, 70, BILINEAR, CONSTANT, 5)
-    assert np.array_equal(gpu_persp_run(pkg, L, torch_cuda, img, hh, 56, 70, BILINEAR, CONSTANT, 5), want) and last(L) == TILED
-    for oi, oo in ((1, 0), (0, 7), (3, 5)):
-        assert not takes_tiled(img.shape, hh, 56, 70, BILINEAR, CONSTANT, oi, oo)
-        assert np.array_equal(gpu_persp_run(pkg, L, torch_cuda, img, hh, 56, 70, BILINEAR, CONSTANT, 5, oi, oo), want), (oi, oo)
-        assert last(L) == GENERIC, (oi, oo)
+    check_pointer_offsets(PERSP, pkg, L, torch_cuda, img, (named_maps(48, 35, 56, 70)["tilt"], 56, 70, BILINEAR, CONSTANT, 5))
 
 
 def test_a_footprint_over_64_kib_takes_the_generic_kernel(pkg, L, torch_cuda):
@@ -108,7 +91,7 @@ def test_a_footprint_over_64_kib_takes_the_generic_kernel(pkg, L, torch_cuda):
         hh = quad_h(512, 512, size, size, BIG_QUAD)
         for border in BORDERS:
             assert max_footprint(shape, hh, size, size, border) == stages and takes_tiled(shape, hh, size, size, BILINEAR, border) == (kernel == TILED)
-            got = gpu_persp_run(pkg, L, torch_cuda, img, hh, size, size, BILINEAR, border)
+            got = gpu_run(PERSP, pkg, L, torch_cuda, img, (hh, size, size, BILINEAR, border, 0))
             assert last(L) == kernel and np.array_equal(got, ref_warp(img, hh, size, size, BILINEAR, border)), (size, border)
 
 
@@ -118,7 +101,7 @@ def test_extreme_shapes(pkg, L, torch_cuda, case):
     img = np.random.default_rng(5).integers(0, 256, size=(1,) + ishape, dtype=np.uint8)
     for b in BORDERS if border is None else (border,):
         assert valid(hh, wo, ho) and takes_tiled(img.shape, hh, wo, ho, BILINEAR, b)
-        got = gpu_persp_run(pkg, L, torch_cuda, img, hh, wo, ho, BILINEAR, b, 7)
+        got = gpu_run(PERSP, pkg, L, torch_cuda, img, (hh, wo, ho, BILINEAR, b, 7))
         assert last(L) == TILED and np.array_equal(got, ref_warp(img, hh, wo, ho, BILINEAR, b, 7)), b
 
 
@@ -133,21 +116,14 @@ def test_one_chunk_inputs(pkg, L, torch_cuda):
             hh = named_maps(w, max(h, 2), wo, ho)["keystone"]
             for border in BORDERS:
                 assert valid(hh, wo, ho) and takes_tiled(img.shape, hh, wo, ho, BILINEAR, border), (w, c, h)
-                got = gpu_persp_run(pkg, L, torch_cuda, img, hh, wo, ho, BILINEAR, border, 173)
+                got = gpu_run(PERSP, pkg, L, torch_cuda, img, (hh, wo, ho, BILINEAR, border, 173))
                 assert last(L) == TILED and np.array_equal(got, ref_warp(img, hh, wo, ho, BILINEAR, border, 173)), (w, c, h, border)
 
 
 def test_gpu_equals_cpu_device_on_the_synthetic_stream(pkg, L, torch_cuda):
-    shape = (4, 240, 320, 3)
-    host = np.empty(shape, np.uint8)
-    L.mi_blur_fill_synthetic(host.ctypes.data, 320, 240, 3, 0, 4, 4)
-    for name, (wo, ho), border in (("keystone", (320, 240), CONSTANT), ("tilt", (400, 300), CLAMP), ("half-out", (160, 120), CLAMP)):
-        hh = named_maps(320, 240, wo, ho)[name]
-        for mode in (BILINEAR, NEAREST):
-            want = cpu_persp_run(pkg, L, host, hh, wo, ho, mode, border, 128, 4)
-            assert np.array_equal(want, ref_warp(host, hh, wo, ho, mode, border, 128)), (name, mode)
-            assert np.array_equal(gpu_persp_run(pkg, L, torch_cuda, host, hh, wo, ho, mode, border, 128), want), (name, mode)
-            assert last(L) == (TILED if takes_tiled(shape, hh, wo, ho, mode, border) else GENERIC)
+    cases = (("keystone", (320, 240), CONSTANT), ("tilt", (400, 300), CLAMP), ("half-out", (160, 120), CLAMP))
+    check_synthetic_stream(PERSP, pkg, L, torch_cuda, [(named_maps(320, 240, wo, ho)[name], wo, ho, mode, border, 128)
+                                                       for name, (wo, ho), border in cases for mode in (BILINEAR, NEAREST)])
 
 
 @pytest.mark.parametrize("target", [(160, 120), (100, 75)], ids=lambda t: "x".join(map(str, t)))
@@ -157,42 +133,9 @@ def test_gpu_context(pkg, L, torch_cuda, target):
     wo, ho = target
     img = np.random.default_rng(13).integers(0, 256, size=shape, dtype=np.uint8)
     hh = named_maps(w, h, wo, ho)["tilt"]
-    want = ref_warp(img, hh, wo, ho, BILINEAR, CONSTANT, 40)
     kernel = TILED if takes_tiled(shape, hh, wo, ho) else GENERIC
     assert (kernel == TILED) == (target == (160, 120))              # 100 x 3 bytes is no whole number of chunks
-    with pkg.Context(0, w, h, c, 1, max_batch=n, n_slots=3) as ctx:
-        ctx.set_warp_perspective(make_persp(pkg, hh, wo, ho, BILINEAR, CONSTANT, 40))
-        out = np.full(want.size + 64, 0xA5, np.uint8)
-        ctx.submit(img.ctypes.data, out.ctypes.data, n)                  # pageable
-        t = ctx.sync()
-        assert np.array_equal(out[:want.size].reshape(want.shape), want) and (out[want.size:] == 0xA5).all()
-        assert last(L) == kernel
-        assert t["bytes_alg"] == img.size + want.size
-        cap = want.size + 4096                                           # pinned, in place, with guard bytes behind the output
-        pin_in, pin_out = L.mi_blur_host_alloc(img.size), L.mi_blur_host_alloc(cap)
-        try:
-            a = np.ctypeslib.as_array((C.c_uint8 * img.size).from_address(pin_in)).reshape(img.shape)
-            b = np.ctypeslib.as_array((C.c_uint8 * cap).from_address(pin_out))
-            a[:] = img
-            z0 = L.mi_blur_zero_copy_launches(ctx.h)
-            for _ in range(3):
-                b[:] = 0xA5
-                ctx.submit(pin_in, pin_out, n)
-                ctx.sync()
-                assert np.array_equal(b[:want.size].reshape(want.shape), want) and (b[want.size:] == 0xA5).all()
-            assert L.mi_blur_zero_copy_launches(ctx.h) == z0 + 3
-            assert last(L) == kernel
-            pitch = w * c
-            assert L.mi_blur_submit_band(ctx.h, pin_in, pin_out, 60, 2, 2) == pkg.ERR_UNSUPPORTED
-            assert L.mi_blur_submit_bands(ctx.h, pin_in, pin_out, n, h * pitch, 60, 2, 2) == pkg.ERR_UNSUPPORTED
-            assert L.mi_blur_submit_planar(ctx.h, pin_in, pin_out, n, 0) == pkg.ERR_UNSUPPORTED
-            ctx.resident_alloc(2)
-            assert L.mi_blur_resident_run(ctx.h, 2, 1, 0) == pkg.ERR_UNSUPPORTED
-            assert L.mi_blur_resident_run_fused(ctx.h, 2, 1, 0) == pkg.ERR_UNSUPPORTED
-            assert L.mi_blur_ctx_set_warp_perspective(ctx.h, C.byref(make_persp(pkg, hh, wo, ho))) == pkg.ERR_STATE
-        finally:
-            L.mi_blur_host_free(pin_in)
-            L.mi_blur_host_free(pin_out)
+    check_gpu_context(PERSP, pkg, L, img, (hh, wo, ho, BILINEAR, CONSTANT, 40), kernel)
 
 
 def test_gpu_context_enlarging(pkg, L, torch_cuda):
@@ -202,34 +145,7 @@ def test_gpu_context_enlarging(pkg, L, torch_cuda):
     wo, ho = 320, 240
     img = np.random.default_rng(14).integers(0, 256, size=shape, dtype=np.uint8)
     hh = named_maps(w, h, wo, ho)["keystone"]
-    want = ref_warp(img, hh, wo, ho, BILINEAR, CONSTANT, 40)
-    assert want.size == 4 * img.size and takes_tiled(shape, hh, wo, ho)
-    with pkg.Context(0, w, h, c, 1, max_batch=n, n_slots=3) as ctx:
-        ctx.set_warp_perspective(make_persp(pkg, hh, wo, ho, BILINEAR, CONSTANT, 40))
-        cap = want.size + 4096                                           # guard bytes behind the output, pageable and pinned
-        out = np.full(cap, 0xA5, np.uint8)
-        ctx.submit(img.ctypes.data, out.ctypes.data, n)                  # pageable
-        t = ctx.sync()
-        assert np.array_equal(out[:want.size].reshape(want.shape), want) and (out[want.size:] == 0xA5).all()
-        assert last(L) == TILED
-        assert t["bytes_alg"] == img.size + want.size
-        pin_in, pin_out = L.mi_blur_host_alloc(img.size), L.mi_blur_host_alloc(cap)
-        try:
-            a = np.ctypeslib.as_array((C.c_uint8 * img.size).from_address(pin_in)).reshape(img.shape)
-            b = np.ctypeslib.as_array((C.c_uint8 * cap).from_address(pin_out))
-            a[:] = img
-            z0 = L.mi_blur_zero_copy_launches(ctx.h)
-            for k in range(3):
-                b[:] = 0xA5
-                ctx.submit(pin_in, pin_out, n)
-                t = ctx.sync()
-                assert np.array_equal(b[:want.size].reshape(want.shape), want) and (b[want.size:] == 0xA5).all()
-                assert t["bytes_alg"] == (k + 2) * (img.size + want.size)   # cumulative since the context was made
-            assert L.mi_blur_zero_copy_launches(ctx.h) == z0 + 3
-            assert last(L) == TILED
-        finally:
-            L.mi_blur_host_free(pin_in)
-            L.mi_blur_host_free(pin_out)
+    check_gpu_context_enlarging(PERSP, pkg, L, img, (hh, wo, ho, BILINEAR, CONSTANT, 40), fill=40)
 
 
 def test_numpy_functions_on_the_gpu(pkg, L, torch_cuda):

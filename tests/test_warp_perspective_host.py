@@ -4,23 +4,22 @@ perspective_matrix() / warp_perspective_coord(), the hosts' --perspective), CPU 
 header's definition (warp_perspective_ref.py), independent of the product.  All comparisons are exact unless stated."""
 import ctypes as C
 import os
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
-from filter_harness import MEDIAN, cpu_run
-from warp_ref import LIMIT_FILL, LIMIT_MAPS as AFFINE_LIMIT_MAPS, limit_image, limit_out, make_warp, cpu_warp_run, ref_warp as ref_affine, rotation_m, quantise
-from warp_perspective_ref import (BIG_QUAD, BILINEAR, CLAMP, CONSTANT, EXTREME, LIMIT_MAPS, LIN_MAX, MAX_DIM, NAMED, NEAREST, OFF_MAX, Q, adjugate, affine_h,
-                                  box, cpu_persp_run, float_warp, fraction_bits, limit_references, make_persp, max_footprint, named_maps, named_quads,
+from filter_harness import MEDIAN, cpu_run as cpu_run_same_size
+from resample_harness import (PERSP, WARP, check_cpu_context, check_cpu_run_refuses, check_ctx_set_refuses, check_enqueue_invalid_before_no_device,
+                              check_setters_replace_each_other, cpu_run, needs_gxx, run_sanitized, sampler_rows, size_rows)
+from warp_ref import LIMIT_FILL, LIMIT_MAPS as AFFINE_LIMIT_MAPS, TILED_SHAPES, limit_image, limit_out, make_warp, ref_warp as ref_affine, rotation_m, quantise
+from warp_perspective_ref import (BIG_QUAD, BILINEAR, CLAMP, CONSTANT, EXTREME, LIMIT_MAPS, LIN_MAX, MAX_DIM, NAMED, NEAREST, OFF_MAX, Q, affine_h,
+                                  box, float_warp, fraction_bits, limit_references, make_persp, max_footprint, named_maps, named_quads,
                                   normalised, out_corners, outside_share, quad_forward, quad_h, ref_coord, ref_warp, set_matrix, takes_tiled,
                                   tile_footprints, tiles, valid)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MODES = (BILINEAR, NEAREST)
 BORDERS = (CLAMP, CONSTANT)
-TILED_SHAPES = [((1, 80, 96, 1), (144, 70)), ((2, 80, 96, 2), (136, 70)), ((1, 80, 96, 3), (144, 70)), ((2, 80, 96, 4), (132, 70))]   # test_warp_gpu.py's
 
 
 def coord(L, wp, X, Y):
@@ -255,7 +254,7 @@ def test_cpu_device_named_maps(pkg, L, case):
     for name, hh in named_maps(w, h, wo, ho).items():
         for mode in MODES:
             for border in BORDERS:
-                got = cpu_persp_run(pkg, L, img, hh, wo, ho, mode, border, 173, n_threads=3)
+                got = cpu_run(PERSP, pkg, L, img, (hh, wo, ho, mode, border, 173), 3)
                 assert np.array_equal(got, ref_warp(img, hh, wo, ho, mode, border, 173)), (name, mode, border)
 
 
@@ -267,7 +266,7 @@ def test_cpu_device_limit_maps(pkg, L, c):
         for mode in MODES:
             for border in BORDERS:
                 for nt in (1, 5):
-                    got = cpu_persp_run(pkg, L, img, hf(wo), wo, ho, mode, border, LIMIT_FILL, n_threads=nt)
+                    got = cpu_run(PERSP, pkg, L, img, (hf(wo), wo, ho, mode, border, LIMIT_FILL), nt)
                     assert np.array_equal(got, refs[name, mode, border]), (name, mode, border, nt)
 
 
@@ -285,11 +284,11 @@ def test_cpu_device_odd_shapes_and_thread_counts(pkg, L):
                 for border in BORDERS:
                     want = ref_warp(img, hh, wo, ho, mode, border, 99)
                     for nt in (1, 2, 7):
-                        assert np.array_equal(cpu_persp_run(pkg, L, img, hh, wo, ho, mode, border, 99, n_threads=nt), want), ((n, h, w, c), hh, mode, border, nt)
+                        assert np.array_equal(cpu_run(PERSP, pkg, L, img, (hh, wo, ho, mode, border, 99), nt), want), ((n, h, w, c), hh, mode, border, nt)
     for ishape, (wo, ho), hh, border in EXTREME:                                 # the extreme shapes of the GPU tests
         img = rng.integers(0, 256, size=(1,) + ishape, dtype=np.uint8)
         for b in BORDERS if border is None else (border,):
-            assert np.array_equal(cpu_persp_run(pkg, L, img, hh, wo, ho, BILINEAR, b, 7, n_threads=4), ref_warp(img, hh, wo, ho, BILINEAR, b, 7))
+            assert np.array_equal(cpu_run(PERSP, pkg, L, img, (hh, wo, ho, BILINEAR, b, 7), 4), ref_warp(img, hh, wo, ho, BILINEAR, b, 7))
     assert L.mi_blur_cpu_run_warp_perspective(img.ctypes.data, img.ctypes.data, 16, 32768, 1, 1, C.byref(make_persp(pkg, EXTREME[1][2], 16, 32768)), 1) == pkg.ERR_INVALID   # in == out
 
 
@@ -305,10 +304,10 @@ def test_affine_homographies_give_the_affine_warp(pkg, L):
             assert valid(hh, 63, 50), (m, s)
             for mode in MODES:
                 for border in BORDERS:
-                    want = cpu_warp_run(pkg, L, img, m, 63, 50, mode, border, 33)
+                    want = cpu_run(WARP, pkg, L, img, (m, 63, 50, mode, border, 33), 2)
                     assert np.array_equal(want, ref_affine(img, m, 63, 50, mode, border, 33))
                     assert np.array_equal(ref_warp(img, hh, 63, 50, mode, border, 33), want), (m, s, mode, border)
-                    assert np.array_equal(cpu_persp_run(pkg, L, img, hh, 63, 50, mode, border, 33), want), (m, s, mode, border)
+                    assert np.array_equal(cpu_run(PERSP, pkg, L, img, (hh, 63, 50, mode, border, 33), 2), want), (m, s, mode, border)
     lim = limit_image(2, 3)
     wo, ho = limit_out(3)
     for name, (m, _, _) in AFFINE_LIMIT_MAPS.items():
@@ -316,9 +315,9 @@ def test_affine_homographies_give_the_affine_warp(pkg, L):
         assert valid(hh, wo, ho), name
         for mode in MODES:
             for border in BORDERS:
-                want = cpu_warp_run(pkg, L, lim, m, wo, ho, mode, border, LIMIT_FILL)
+                want = cpu_run(WARP, pkg, L, lim, (m, wo, ho, mode, border, LIMIT_FILL), 2)
                 assert np.array_equal(ref_warp(lim, hh, wo, ho, mode, border, LIMIT_FILL), want), (name, mode, border)
-                assert np.array_equal(cpu_persp_run(pkg, L, lim, hh, wo, ho, mode, border, LIMIT_FILL), want), (name, mode, border)
+                assert np.array_equal(cpu_run(PERSP, pkg, L, lim, (hh, wo, ho, mode, border, LIMIT_FILL), 2), want), (name, mode, border)
 
 
 def test_a_rectangles_taps_lie_in_the_box_of_its_corners():
@@ -354,39 +353,18 @@ def test_error_bound_against_real_valued_bilinear():
 
 def test_entry_statuses(pkg, L):
     """INVALID before NO_DEVICE, argument for argument as mi_blur_enqueue_warp."""
-    a, b = np.zeros(8 * 8 * 3 + 16, np.uint8), np.zeros(16 * 16 * 3 + 16, np.uint8)
     ident = affine_h([Q, 0, 0, 0, Q, 0])
     mk = lambda wo=16, ho=16, mode=BILINEAR, border=CONSTANT, fill=0, h=None: make_persp(pkg, h or ident, wo, ho, mode, border, fill)
-    enq = lambda wp, i=a.ctypes.data, o=b.ctypes.data, w=8, h=8, c=3, n=1: L.mi_blur_enqueue_warp_perspective(i, o, w, h, c, n, C.byref(wp) if wp is not None else None, None)
-    run = lambda wp, i=a.ctypes.data, o=b.ctypes.data, w=8, h=8, c=3, n=1: L.mi_blur_cpu_run_warp_perspective(i, o, w, h, c, n, C.byref(wp) if wp is not None else None, 1)
     horizon = [Q, 0, 0, 0, Q, 0, -Q // 8, 0, Q]                                        # D = 0 at X = 8
     over = list(ident)
     over[5] = OFF_MAX + 1
-    bads = [mk(wo=0), mk(ho=0), mk(MAX_DIM + 1, 1), mk(1, MAX_DIM + 1), mk(mode=2), mk(border=2), mk(fill=256), mk(fill=-1), mk(h=over), mk(h=horizon),
-            mk(h=[Q, 0, 0, 0, Q, 0, 0, 0, 0]), mk(MAX_DIM, MAX_DIM)]
-    for f in (enq, run):
-        for bad in bads:
-            assert f(bad) == pkg.ERR_INVALID
-        assert f(None) == pkg.ERR_INVALID
-        assert f(mk(), i=None) == pkg.ERR_INVALID and f(mk(), o=None) == pkg.ERR_INVALID and f(mk(), o=a.ctypes.data) == pkg.ERR_INVALID
-        assert f(mk(), w=0) == pkg.ERR_INVALID and f(mk(), h=0) == pkg.ERR_INVALID and f(mk(), c=0) == pkg.ERR_INVALID and f(mk(), n=-1) == pkg.ERR_INVALID
-        assert f(mk(), w=MAX_DIM + 1, h=1, c=1) == pkg.ERR_INVALID
-    assert run(mk(h=horizon, wo=8)) == pkg.OK                                          # the same map, an output that ends before the horizon
-    assert run(mk(), n=0) == pkg.OK
-    if L.mi_blur_device_count() <= 0:
-        assert enq(mk()) == pkg.ERR_NO_DEVICE
-    with pkg.Context(pkg.DEVICE_CPU, 8, 8, 3, 1, max_batch=1) as ctx:
-        assert L.mi_blur_ctx_set_warp_perspective(None, C.byref(mk())) == pkg.ERR_INVALID
-        assert L.mi_blur_ctx_set_warp_perspective(ctx.h, None) == pkg.ERR_INVALID
-        for bad in bads:
-            assert L.mi_blur_ctx_set_warp_perspective(ctx.h, C.byref(bad)) == pkg.ERR_INVALID
-        img = np.random.default_rng(2).integers(0, 256, size=(1, 8, 8, 3), dtype=np.uint8)   # refused sets leave the box blur in place
-        out, box_out = np.empty_like(img), np.empty_like(img)
-        ctx.submit(img.ctypes.data, out.ctypes.data, 1)
-        ctx.sync()
-        assert L.mi_blur_cpu_run(img.ctypes.data, box_out.ctypes.data, 8, 8, 3, 1, 1, 1) == pkg.OK and np.array_equal(out, box_out)
-        assert L.mi_blur_ctx_set_warp_perspective(ctx.h, C.byref(mk())) == pkg.ERR_STATE
-        assert L.mi_blur_ctx_set_warp_perspective(ctx.h, None) == pkg.ERR_INVALID
+    own = [(C.byref(mk(h=hh)),) for hh in (over, horizon, [Q, 0, 0, 0, Q, 0, 0, 0, 0])]
+    good, rows = (C.byref(mk()),), size_rows(mk) + sampler_rows(mk) + [(8, 8, 3, args) for args in own]
+    a, b = check_cpu_run_refuses(PERSP, pkg, L, good, rows)
+    check_enqueue_invalid_before_no_device(PERSP, pkg, L, good, rows)
+    assert L.mi_blur_cpu_run_warp_perspective(a.ctypes.data, b.ctypes.data, 8, 8, 3, 1, C.byref(mk(h=horizon, wo=8)), 1) == pkg.OK   # the same map, an output that ends before the horizon
+    bad = [dict(wo=0), dict(ho=0), dict(wo=MAX_DIM + 1, ho=1), dict(wo=1, ho=MAX_DIM + 1), dict(mode=2), dict(border=2), dict(fill=256), dict(fill=-1)]
+    check_ctx_set_refuses(PERSP, pkg, L, good, [(C.byref(mk(**kw)),) for kw in bad] + own + [(C.byref(mk(MAX_DIM, MAX_DIM)),)])
 
 
 @pytest.mark.parametrize("target", [(42, 37), (63, 74)], ids=lambda t: "x".join(map(str, t)))
@@ -397,26 +375,7 @@ def test_cpu_context(pkg, L, target):
     hh = named_maps(w, h, wo, ho)["tilt"]
     for mode in MODES:
         for border in BORDERS:
-            want = ref_warp(img, hh, wo, ho, mode, border, 33)
-            with pkg.Context(pkg.DEVICE_CPU, w, h, c, 1, max_batch=n, n_threads=3) as ctx:
-                wp = make_persp(pkg, hh, wo, ho, mode, border, 33)
-                assert L.mi_blur_ctx_set_warp_perspective(ctx.h, C.byref(wp)) == pkg.OK
-                C.memset(C.byref(wp), 0xFF, C.sizeof(wp))                    # the context keeps a copy
-                out = np.full(want.size + 128, 0xA5, np.uint8)
-                ctx.submit(img.ctypes.data, out.ctypes.data + 64, n)         # pageable memory, guards either side
-                t = ctx.sync()
-                assert np.array_equal(out[64:64 + want.size].reshape(want.shape), want)
-                assert (out[:64] == 0xA5).all() and (out[64 + want.size:] == 0xA5).all()
-                assert t["bytes_alg"] == img.size + want.size and t["images"] == n
-                pitch = w * c
-                o = np.zeros_like(img)
-                assert L.mi_blur_submit_band(ctx.h, img.ctypes.data, o.ctypes.data, 20, 2, 2) == pkg.ERR_UNSUPPORTED
-                assert L.mi_blur_submit_bands(ctx.h, img.ctypes.data, o.ctypes.data, n, h * pitch, 20, 2, 2) == pkg.ERR_UNSUPPORTED
-                assert L.mi_blur_submit_planar(ctx.h, img.ctypes.data, o.ctypes.data, n, 0) == pkg.ERR_UNSUPPORTED
-                assert L.mi_blur_resident_run(ctx.h, 1, 1, 0) == pkg.ERR_UNSUPPORTED
-                assert L.mi_blur_resident_run_fused(ctx.h, 1, 1, 0) == pkg.ERR_UNSUPPORTED
-                assert not o.any()
-                assert L.mi_blur_ctx_set_warp_perspective(ctx.h, C.byref(make_persp(pkg, hh, wo, ho, mode, border, 33))) == pkg.ERR_STATE
+            check_cpu_context(PERSP, pkg, L, img, (hh, wo, ho, mode, border, 33))
 
 
 def test_setters_replace_each_other(pkg, L):
@@ -425,23 +384,11 @@ def test_setters_replace_each_other(pkg, L):
     hh = named_maps(w, h, 40, 31)["keystone"]
     m = rotation_m(w, h, -40.0)
 
-    def run(setters, want):
-        with pkg.Context(pkg.DEVICE_CPU, w, h, c, 1, max_batch=n) as ctx:
-            for s in setters:
-                s(ctx)
-            out = np.full(want.size + 64, 0xA5, np.uint8)
-            ctx.submit(img.ctypes.data, out.ctypes.data, n)
-            t = ctx.sync()
-            assert np.array_equal(out[:want.size].reshape(want.shape), want) and (out[want.size:] == 0xA5).all()
-            return t
     persp = lambda ctx: ctx.set_warp_perspective(make_persp(pkg, hh, 40, 31, BILINEAR, CLAMP))
     affine = lambda ctx: ctx.set_warp(make_warp(pkg, m, 30, 11, BILINEAR, CLAMP))
     median = lambda ctx: ctx.set_median(1)
-    key, rot, med = ref_warp(img, hh, 40, 31, BILINEAR, CLAMP), ref_affine(img, m, 30, 11, BILINEAR, CLAMP), cpu_run(MEDIAN, pkg, L, img, 1, 1)
-    assert run([persp, median], med)["bytes_alg"] == 2 * img.size          # the last one wins
-    assert run([median, persp], key)["bytes_alg"] == img.size + key.size
-    assert run([persp, affine], rot)["bytes_alg"] == img.size + rot.size
-    assert run([affine, persp], key)["bytes_alg"] == img.size + key.size
+    key, rot, med = ref_warp(img, hh, 40, 31, BILINEAR, CLAMP), ref_affine(img, m, 30, 11, BILINEAR, CLAMP), cpu_run_same_size(MEDIAN, pkg, L, img, 1, 1)
+    check_setters_replace_each_other(pkg, L, img, [([persp, median], med), ([median, persp], key), ([persp, affine], rot), ([affine, persp], key)])   # the last one wins
 
 
 def test_numpy_functions_on_the_cpu_device(pkg, L):
@@ -477,7 +424,7 @@ def test_numpy_functions_on_the_cpu_device(pkg, L):
 
 
 def test_hosts_and_the_perspective_option(pkg, tmp_path):
-    from filter_harness import read_ppm, write_ppm
+    from resample_harness import read_ppm, write_ppm
     pkg.build_native()
     het, split = os.path.join(pkg.APPS, "heterogeneous_blur"), os.path.join(pkg.APPS, "split_image_blur")
     quad = named_quads(64, 48)["keystone"]
@@ -509,21 +456,14 @@ def test_hosts_and_the_perspective_option(pkg, tmp_path):
         assert r.returncode not in (0, -6, -11, 134, 139) and "Error: --perspective:" in r.stdout, (bad, r.stdout[-500:])
 
 
-@pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not available")
+@needs_gxx
 def test_cpu_device_and_tile_walk_clean_under_asan_ubsan(pkg, tmp_path):
     """tests/san_warp_perspective.cpp: the CPU device against a plain restatement in exact-size heap buffers, and every
     warp_tap offset of every tile of the named, limit and extreme cases against the LDS size the host walk returns."""
-    exe = tmp_path / "san_warp_perspective"
-    cmd = ["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-           "-fno-omit-frame-pointer", "-I", pkg.CSRC, os.path.join(ROOT, "tests", "san_warp_perspective.cpp"),
-           os.path.join(pkg.CSRC, "cpu_device.cpp"), "-lpthread", "-o", str(exe)]
-    subprocess.run(cmd, check=True, capture_output=True)
     lines = []                                                                   # the named maps need the setter: handed over as data
     for (n, h, w, c), (wo, ho) in TILED_SHAPES:
         lines += [" ".join(map(str, [w, h, c, wo, ho] + hh)) for hh in named_maps(w, h, wo, ho).values()]
     lines.append(" ".join(map(str, [512, 512, 1, 128, 128] + quad_h(512, 512, 128, 128, BIG_QUAD))))
     cases = tmp_path / "cases.txt"
     cases.write_text("\n".join(lines) + "\n")
-    r = subprocess.run([str(exe), str(cases)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "perspective warp cases clean" in r.stdout and "taps inside their LDS" in r.stdout and "FAILED" not in r.stdout, r.stdout + r.stderr
-    assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr
+    run_sanitized(pkg, tmp_path, ("san_warp_perspective.cpp", "cpu_device.cpp"), ["perspective warp cases clean", "taps inside their LDS"], [cases])

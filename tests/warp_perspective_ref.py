@@ -1,6 +1,6 @@
 """The perspective warp of include/mi_blur.h ("Perspective warp") restated in numpy int64 from the header's text (`//`
 floors), with the setter's normalisation in float64, and nothing of the product's (not a test module).  It shares the
-tile geometry, the limit image and the guard conventions of warp_ref.py.  footprint() / max_footprint() / takes_tiled()
+tile geometry and the limit image of warp_ref.py.  footprint() / max_footprint() / takes_tiled()
 restate the eligibility rule with the corner rule; named_maps(), LIMIT_MAPS and EXTREME are the cases the host tests, the
 GPU tests and tests/san_warp_perspective.cpp walk."""
 import ctypes as C
@@ -294,39 +294,5 @@ EXTREME = [((1, 32768, 1), (32768, 1), [1 << 30, 0, 0, 0, 1 << 30, 0, 1 << 14, 0
 BIG_QUAD = [(100.0, 0.0), (411.0, 0.0), (511.0, 511.0), (0.0, 511.0)]
 
 
-# ---------------------------------------------------------------- runners (warp_ref's guards)
 def make_persp(pkg, h, wo, ho, mode=BILINEAR, border=CONSTANT, fill=0):
     return pkg.WarpPerspective(wo, ho, mode, border, fill, (C.c_int64 * 9)(*[int(v) for v in h]))
-
-
-def gpu_persp_run(pkg, L, torch, host, h, wo, ho, mode=BILINEAR, border=CONSTANT, fill=0, offset_in=0, offset_out=0):
-    """host: N x H x W x C -> mi_blur_enqueue_warp_perspective.  The input lies offset_in bytes into a buffer with 64 spare
-    bytes, the output offset_out bytes into one with 128 bytes of 0x5A to spare: guards either side."""
-    n, hh, w, c = host.shape
-    oshape = (n, ho, wo, c)
-    size_out = int(np.prod(oshape))
-    d_in = torch.zeros(host.size + 64, dtype=torch.uint8, device="cuda")
-    d_in[offset_in:offset_in + host.size] = torch.from_numpy(np.ascontiguousarray(host).reshape(-1)).cuda()
-    d_out = torch.full((size_out + 128,), 0x5A, dtype=torch.uint8, device="cuda")
-    wp = make_persp(pkg, h, wo, ho, mode, border, fill)
-    rc = L.mi_blur_enqueue_warp_perspective(d_in.data_ptr() + offset_in, d_out.data_ptr() + offset_out, w, hh, c, n, C.byref(wp),
-                                            torch.cuda.current_stream().cuda_stream)
-    pkg.check(rc, "mi_blur_enqueue_warp_perspective")
-    torch.cuda.synchronize()
-    o = d_out.cpu().numpy()
-    assert (o[:offset_out] == 0x5A).all() and (o[offset_out + size_out:] == 0x5A).all(), "wrote outside the output"
-    return o[offset_out:offset_out + size_out].reshape(oshape)
-
-
-def cpu_persp_run(pkg, L, img, h, wo, ho, mode=BILINEAR, border=CONSTANT, fill=0, n_threads=2, guard=256):
-    """img: N x H x W x C -> mi_blur_cpu_run_warp_perspective.  The output starts as 0xA5 and the `guard` bytes before and
-    after it must still hold 0xA5."""
-    a = np.ascontiguousarray(img)
-    n, hh, w, c = a.shape
-    oshape = (n, ho, wo, c)
-    size_out = int(np.prod(oshape))
-    buf = np.full(size_out + 2 * guard, 0xA5, np.uint8)
-    wp = make_persp(pkg, h, wo, ho, mode, border, fill)
-    pkg.check(L.mi_blur_cpu_run_warp_perspective(a.ctypes.data, buf.ctypes.data + guard, w, hh, c, n, C.byref(wp), n_threads), "mi_blur_cpu_run_warp_perspective")
-    assert (buf[:guard] == 0xA5).all() and (buf[guard + size_out:] == 0xA5).all(), "wrote outside the warped output"
-    return buf[guard:guard + size_out].reshape(oshape)

@@ -1,7 +1,5 @@
 """The affine warp of include/mi_blur.h ("Affine warp") restated in numpy int64 from the header's text, and nothing of
-the product's — with the runners tests/test_warp_host.py and tests/test_warp_gpu.py share (not a test module).  The
-runners keep resize_ref's guards: the input offset into a padded buffer, the output surrounded by 0x5A (GPU) or
-prefilled with 0xA5 with a guard region either side (CPU).  takes_tiled() restates the eligibility rule of the header
+the product's (not a test module; tests/resample_harness.py launches the filter).  takes_tiled() restates the eligibility rule of the header
 (the exact walk over the tiles included) and tile_geometry() the tiles of blur_warp_tiled_kernel.  ref_warp_band() gives
 a band of output rows from the input rows it needs alone, for images too large to restate whole; EXTREME, narrow_cases()
 and LIMIT_MAPS are the extreme shapes, one-chunk rows and maps at the header's limits that the GPU tests, the CPU-device
@@ -222,6 +220,21 @@ def corner_pixels(wo, ho):
     return [(0, 0), (wo - 1, 0), (0, ho - 1), (wo - 1, ho - 1)]
 
 
+# (input shape, (Wo, Ho)) of the warp, perspective and remap tests: 144 x 70 pixels out of 96 x 80 for one channel is
+# 9 chunks x 70 rows = 3 x 3 tiles; the others likewise span more than one tile both ways, with output sizes that differ from the input's
+TILED_SHAPES = [((1, 80, 96, 1), (144, 70)), ((2, 80, 96, 2), (136, 70)), ((1, 80, 96, 3), (144, 70)), ((2, 80, 96, 4), (132, 70))]
+
+
+def edge_image(rng, n, h, w, c):
+    """Noise, with 0 / 255 on the outermost rows and columns of image 0 (what CLAMP repeats and CONSTANT blends with the
+    fill) and an all-255 last image when there are two."""
+    img = rng.integers(0, 256, size=(n, h, w, c), dtype=np.uint8)
+    img[0, 0], img[0, -1], img[0, :, 0], img[0, :, -1] = 255, 0, 0, 255
+    if n > 1:
+        img[-1] = 255
+    return img
+
+
 # Inputs of one 16-byte chunk per row (3 channels: one group of three chunks): the staged box of the tiled kernel is the whole row, or the whole image.
 NARROW_ROWS = [(16, 1), (8, 2), (16, 3), (4, 4)]        # (w, c)
 NARROW_HEIGHTS = (1, 2, 33)
@@ -345,36 +358,3 @@ def limit_references(n, c):
 
 def make_warp(pkg, m, wo, ho, mode=BILINEAR, border=CONSTANT, fill=0):
     return pkg.Warp(wo, ho, mode, border, fill, (C.c_int64 * 6)(*[int(v) for v in m]))
-
-
-def gpu_warp_run(pkg, L, torch, host, m, wo, ho, mode=BILINEAR, border=CONSTANT, fill=0, offset_in=0, offset_out=0):
-    """host: N x H x W x C -> mi_blur_enqueue_warp.  The input lies offset_in bytes into a buffer with 64 spare bytes, the
-    output offset_out bytes into one with 128 bytes of 0x5A to spare: guards either side."""
-    n, h, w, c = host.shape
-    oshape = (n, ho, wo, c)
-    size_out = int(np.prod(oshape))
-    d_in = torch.zeros(host.size + 64, dtype=torch.uint8, device="cuda")
-    d_in[offset_in:offset_in + host.size] = torch.from_numpy(np.ascontiguousarray(host).reshape(-1)).cuda()
-    d_out = torch.full((size_out + 128,), 0x5A, dtype=torch.uint8, device="cuda")
-    wp = make_warp(pkg, m, wo, ho, mode, border, fill)
-    rc = L.mi_blur_enqueue_warp(d_in.data_ptr() + offset_in, d_out.data_ptr() + offset_out, w, h, c, n, C.byref(wp),
-                                torch.cuda.current_stream().cuda_stream)
-    pkg.check(rc, "mi_blur_enqueue_warp")
-    torch.cuda.synchronize()
-    o = d_out.cpu().numpy()
-    assert (o[:offset_out] == 0x5A).all() and (o[offset_out + size_out:] == 0x5A).all(), "wrote outside the output"
-    return o[offset_out:offset_out + size_out].reshape(oshape)
-
-
-def cpu_warp_run(pkg, L, img, m, wo, ho, mode=BILINEAR, border=CONSTANT, fill=0, n_threads=2, guard=256):
-    """img: N x H x W x C -> mi_blur_cpu_run_warp.  The output starts as 0xA5, so a byte left unwritten shows (the callers'
-    images and fills avoid giving 0xA5 everywhere), and the `guard` bytes before and after it must still hold 0xA5."""
-    a = np.ascontiguousarray(img)
-    n, h, w, c = a.shape
-    oshape = (n, ho, wo, c)
-    size_out = int(np.prod(oshape))
-    buf = np.full(size_out + 2 * guard, 0xA5, np.uint8)
-    wp = make_warp(pkg, m, wo, ho, mode, border, fill)
-    pkg.check(L.mi_blur_cpu_run_warp(a.ctypes.data, buf.ctypes.data + guard, w, h, c, n, C.byref(wp), n_threads), "mi_blur_cpu_run_warp")
-    assert (buf[:guard] == 0xA5).all() and (buf[guard + size_out:] == 0xA5).all(), "wrote outside the warped output"
-    return buf[guard:guard + size_out].reshape(oshape)
