@@ -46,6 +46,7 @@ DOWN_PYR, DOWN_AREA2, DOWN_AREA4 = 0, 1, 2
 RESIZE_MAX_DIM = 32768
 RESIZE_NEAREST, RESIZE_BILINEAR = 0, 1
 RESIZE_MODES = {"nearest": RESIZE_NEAREST, "bilinear": RESIZE_BILINEAR}
+AREA_MAX_RATIO = 64
 WARP_Q = 16
 WARP_CLAMP, WARP_CONSTANT = 0, 1
 WARP_BORDERS = {"clamp": WARP_CLAMP, "constant": WARP_CONSTANT}
@@ -61,7 +62,7 @@ def _newer(target: str, sources: list[str]) -> bool:
 
 def build_native(force: bool = False, verbose: bool = False) -> str:
     """Compile libmi_blur.so (hipcc, --offload-arch=gfx950) and the C++ hosts, in-tree."""
-    srcs = [os.path.join(CSRC, f) for f in ("blur_kernels.hip", "sep_kernels.hip", "median_kernels.hip", "morph_kernels.hip", "bilateral_kernels.hip", "conv_kernels.hip", "sep_down_kernels.hip", "resize_kernels.hip", "warp_kernels.hip", "remap_kernels.hip", "layout_kernels.hip", "mi_blur_api.cpp", "comm_api.cpp", "cpu_device.cpp")]
+    srcs = [os.path.join(CSRC, f) for f in ("blur_kernels.hip", "sep_kernels.hip", "median_kernels.hip", "morph_kernels.hip", "bilateral_kernels.hip", "conv_kernels.hip", "sep_down_kernels.hip", "resize_kernels.hip", "warp_kernels.hip", "remap_kernels.hip", "area_kernels.hip", "layout_kernels.hip", "mi_blur_api.cpp", "comm_api.cpp", "cpu_device.cpp")]
     deps = srcs + [os.path.join(CSRC, f) for f in ("api_internal.h", "blur_launch.h", "kernel_common.h", "cpu_device.h", "filter.h")] + [HEADER]
     if force or not _newer(LIB_PATH, deps):
         cmd = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra",
@@ -230,6 +231,11 @@ class Resize(C.Structure):
     _fields_ = [("out_width", C.c_int), ("out_height", C.c_int), ("mode", C.c_int)]
 
 
+class Area(C.Structure):
+    """mi_blur_area: the output size of the area resize."""
+    _fields_ = [("out_width", C.c_int), ("out_height", C.c_int)]
+
+
 class Warp(C.Structure):
     """mi_blur_warp: the output size, the mode (RESIZE_NEAREST | RESIZE_BILINEAR), the border (WARP_CLAMP | WARP_CONSTANT),
     the fill byte and the OUTPUT -> INPUT map in Q16, row-major 2 x 3."""
@@ -395,6 +401,10 @@ def lib() -> C.CDLL:
         "mi_blur_enqueue_resize": (i, [u8p, u8p, i, i, i, i, C.POINTER(Resize), vp]),
         "mi_blur_cpu_run_resize": (i, [u8p, u8p, i, i, i, i, C.POINTER(Resize), i]),
         "mi_blur_ctx_set_resize": (i, [vp, C.POINTER(Resize)]),
+        "mi_blur_area_coord": (i, [i, i, i, C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i)]),
+        "mi_blur_enqueue_area": (i, [u8p, u8p, i, i, i, i, C.POINTER(Area), vp]),
+        "mi_blur_cpu_run_area": (i, [u8p, u8p, i, i, i, i, C.POINTER(Area), i]),
+        "mi_blur_ctx_set_area": (i, [vp, C.POINTER(Area)]),
         "mi_blur_warp_coord": (i, [C.POINTER(Warp), i, i, C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i)]),
         "mi_blur_warp_rotation": (i, [C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double)]),
         "mi_blur_warp_set_matrix": (i, [C.POINTER(Warp), C.POINTER(C.c_double), i]),
@@ -570,6 +580,13 @@ class Context:
         r = Resize(int(out_width), int(out_height), _resize_mode(mode))
         check(lib().mi_blur_ctx_set_resize(self.h, C.byref(r)), "mi_blur_ctx_set_resize")
         self.resize_spec = r
+
+    def set_area(self, out_width: int, out_height: int) -> None:
+        """The area resize in place of the blur (before the first submit only): submit() then writes images of
+        out_width x out_height; the band, planar and resident forms are not supported."""
+        r = Area(int(out_width), int(out_height))
+        check(lib().mi_blur_ctx_set_area(self.h, C.byref(r)), "mi_blur_ctx_set_area")
+        self.area_spec = r
 
     def set_warp(self, warp: "Warp") -> None:
         """The affine warp in place of the blur (before the first submit only): submit() then writes images of
@@ -931,6 +948,39 @@ def resize(images, size, mode="bilinear", device: int = 0, batch: int = 0):
     if wo < 1 or ho < 1:
         raise ValueError("resize: size is (out_width, out_height), both at least 1")
     out = _filter_images(a, 1, device, batch, lambda ctx: ctx.set_resize(wo, ho, m), (ho, wo))
+    return out[0, :, :, 0] if rank == 2 else out[0] if rank == 3 else out
+
+
+def area_coord(n_in: int, n_out: int, X: int) -> tuple[int, int, int, int]:
+    """(i_lo, i_hi, w_lo, w_hi) of one axis of the area resize for output index X of n_out over n_in input samples
+    (mi_blur_area_coord): the first and the last tap and their weights; w_hi = 0 when there is one tap (w_lo = n_in then);
+    every tap between them weighs n_out."""
+    i_lo, i_hi, w_lo, w_hi = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    check(lib().mi_blur_area_coord(int(n_in), int(n_out), int(X), C.byref(i_lo), C.byref(i_hi), C.byref(w_lo), C.byref(w_hi)),
+          "mi_blur_area_coord")
+    return i_lo.value, i_hi.value, w_lo.value, w_hi.value
+
+
+def area_resize(images, size, device: int = 0, batch: int = 0):
+    """Area resize to size = (out_width, out_height), numpy in -> numpy out: every output pixel is the exact box average
+    of the input area under it, rounded once, half up (include/mi_blur.h has the definition): the anti-aliased reduction
+    at any ratio up to AREA_MAX_RATIO per axis.  Enlarging is valid and replicates pixels at integer ratios.
+
+    images: (H, W), (H, W, C) or (N, H, W, C) uint8; the result has the same rank with out_height and out_width.
+    device: HIP ordinal, or DEVICE_CPU.  Goes through mi_blur_create / mi_blur_ctx_set_area / mi_blur_submit / mi_blur_sync."""
+    a = _images(images, "area_resize")
+    wo, ho = int(size[0]), int(size[1])
+    rank = a.ndim
+    if rank == 2:
+        a = a[None, :, :, None]
+    elif rank == 3:
+        a = a[None]
+    n, h, w, c = a.shape
+    if h == 0 or w == 0 or c == 0:
+        raise ValueError("area_resize: images must not be empty")
+    if wo < 1 or ho < 1:
+        raise ValueError("area_resize: size is (out_width, out_height), both at least 1")
+    out = _filter_images(a, 1, device, batch, lambda ctx: ctx.set_area(wo, ho), (ho, wo))
     return out[0, :, :, 0] if rank == 2 else out[0] if rank == 3 else out
 
 

@@ -1,7 +1,7 @@
 // heterogeneous_blur — Approach 1 (image-level distribution) host, MI355X-native.
 //
 //   heterogeneous_blur {cpu|gpu|both} [gpu_ratio] [batch]  [--image F | --synthetic | --size WxH] [--channels C]
-//                      [--ksize 3|5 | --sigma S [--sigma-y S] [--radius R] | --median K | --erode K | --dilate K | --morph-gradient K | --bilateral K [--sigma-color S] [--sigma-space S] | --conv NAME | --pyr-down | --resize WxH [--nearest] | --rotate DEG [--nearest] [--border-fill V] | --perspective x0,y0,x1,y1,x2,y2,x3,y3 [--nearest] [--border-fill V] | --undistort k1[,k2[,p1,p2[,k3]]] [--nearest] [--border-fill V]] [--images N] [--gpus G] [--slots S] [--threads T] [--resident [--fused]]
+//                      [--ksize 3|5 | --sigma S [--sigma-y S] [--radius R] | --median K | --erode K | --dilate K | --morph-gradient K | --bilateral K [--sigma-color S] [--sigma-space S] | --conv NAME | --pyr-down | --resize WxH [--nearest | --area] | --rotate DEG [--nearest] [--border-fill V] | --perspective x0,y0,x1,y1,x2,y2,x3,y3 [--nearest] [--border-fill V] | --undistort k1[,k2[,p1,p2[,k3]]] [--nearest] [--border-fill V]] [--images N] [--gpus G] [--slots S] [--threads T] [--resident [--fused]]
 //                      [--verbose] [--csv FILE] [--save FILE]
 //                      [--frames DIR|PATTERN|FILE [--save-dir DIR] [--planar-out | --native-layout]]   (cpu | gpu)
 //

@@ -184,6 +184,7 @@ struct Options {
     bool undistort_given = false;        // --undistort k1[,k2[,p1,p2[,k3]]] [--nearest] [--border-fill V]: undo the lens distortion of a camera with fx = fy = W
     double undistort_dist[5] = {};       //              and the principal point at the image's centre, same size (mi_blur_remap_undistort, mi_blur_ctx_set_remap;
                                          //              mode and border as --rotate; heterogeneous_blur only: no bands)
+    bool area = false;                   // --resize WxH --area: the area resize (mi_blur_ctx_set_area: exact box average, reductions up to 64x) instead of bilinear
     bool nearest = false;                //              mi_blur_ctx_set_resize on every context, outputs of that size (heterogeneous_blur only: no bands)
     int images = 5000;                   // --images N   (NUM_IMAGES, heterogeneous_blur.c:44)
     bool images_given = false;
@@ -262,6 +263,7 @@ inline int parse_flags(int argc, char **argv, Options &o)
                 o.resize_w > MI_BLUR_RESIZE_MAX_DIM || o.resize_h > MI_BLUR_RESIZE_MAX_DIM) { printf("Error: --resize WxH, each 1..%d\n", MI_BLUR_RESIZE_MAX_DIM); exit(-1); }
         }
         else if (a == "--nearest") o.nearest = true;
+        else if (a == "--area") o.area = true;
         else if (a == "--rotate") {
             char tail = 0;
             if (sscanf(next("--rotate"), "%lf%c", &o.rotate_deg, &tail) != 1 || !(o.rotate_deg >= -36000.0 && o.rotate_deg <= 36000.0)) { printf("Error: --rotate DEG, degrees counter-clockwise\n"); exit(-1); }
@@ -347,6 +349,8 @@ inline int parse_flags(int argc, char **argv, Options &o)
     if (o.undistort_given && (o.persp_given || o.rotate_given || o.resize_w || o.ksize_given || o.sigma > 0.0 || o.median || o.morph || o.bilateral || o.conv_preset >= 0 || o.pyr_down)) { printf("Error: --undistort excludes --perspective, --rotate, --resize, --ksize, --sigma, --median, --erode, --dilate, --morph-gradient, --bilateral, --conv and --pyr-down\n"); exit(-1); }
     if (o.undistort_given && (o.resident || !o.frames.empty())) { printf("Error: --undistort excludes --resident and --frames\n"); exit(-1); }
     if (o.border_fill >= 0 && !o.rotate_given && !o.persp_given && !o.undistort_given) { printf("Error: --border-fill needs --rotate\n"); exit(-1); }
+    if (o.area && !o.resize_w) { printf("Error: --area needs --resize\n"); exit(-1); }
+    if (o.area && o.nearest) { printf("Error: --area excludes --nearest\n"); exit(-1); }
     if (o.nearest && !o.resize_w && !o.rotate_given && !o.persp_given && !o.undistort_given) { printf("Error: --nearest needs --resize\n"); exit(-1); }
     return npos;
 }
@@ -371,6 +375,7 @@ struct HostFilter {
     mi_blur_decimation down_d{};
     bool resize = false;        // --resize WxH [--nearest]: the resize `rs` (mi_blur_ctx_set_resize)
     mi_blur_resize rs{};
+    bool area = false;          // ... --area: the area resize to the size of `rs` instead (mi_blur_ctx_set_area)
     bool warp = false;          // --rotate DEG [--nearest] [--border-fill V]: the warp `wp` (mi_blur_ctx_set_warp); its size and matrix
     double rotate_deg = 0.0;    // come from the image: print_warp() fills them in
     mi_blur_warp wp{};
@@ -404,6 +409,7 @@ inline HostFilter filter_of(const Options &o)
         exit(-1);
     }
     f.resize = o.resize_w > 0;
+    f.area = o.area;
     f.rs = mi_blur_resize{o.resize_w, o.resize_h, o.nearest ? MI_BLUR_RESIZE_NEAREST : MI_BLUR_RESIZE_BILINEAR};
     f.warp = o.rotate_given;
     f.rotate_deg = o.rotate_deg;
@@ -428,7 +434,10 @@ inline void set_filter(mi_blur_ctx *ctx, const HostFilter &f)
     if (f.bilateral) mi_check(mi_blur_ctx_set_bilateral(ctx, &f.bil), "Failed to set the bilateral filter");
     if (f.conv_preset >= 0) mi_check(mi_blur_ctx_set_conv(ctx, &f.conv), "Failed to set the convolution");
     if (f.pyr_down) mi_check(mi_blur_ctx_set_sep_down(ctx, &f.down_k, &f.down_d), "Failed to set the pyramid filter");
-    if (f.resize) mi_check(mi_blur_ctx_set_resize(ctx, &f.rs), "Failed to set the resize");
+    if (f.resize && f.area) {
+        const mi_blur_area ar{f.rs.out_width, f.rs.out_height};
+        mi_check(mi_blur_ctx_set_area(ctx, &ar), "Failed to set the area resize");
+    } else if (f.resize) mi_check(mi_blur_ctx_set_resize(ctx, &f.rs), "Failed to set the resize");
     if (f.warp) mi_check(mi_blur_ctx_set_warp(ctx, &f.wp), "Failed to set the warp");
     if (f.persp) mi_check(mi_blur_ctx_set_warp_perspective(ctx, &f.pp), "Failed to set the perspective warp");
     if (f.remap) mi_check(mi_blur_ctx_set_remap(ctx, &f.rm, f.remap_map.data()), "Failed to set the remap");
@@ -474,7 +483,7 @@ inline void print_warp_perspective(HostFilter &f, int width, int height)
 inline void print_resize(const HostFilter &f, int width, int height, int *wo, int *ho)
 {
     *wo = f.rs.out_width; *ho = f.rs.out_height;
-    printf("Blur kernel: %s resize, %dx%d -> %dx%d\n", f.rs.mode == MI_BLUR_RESIZE_NEAREST ? "nearest" : "bilinear", width, height, *wo, *ho);
+    printf("Blur kernel: %s resize, %dx%d -> %dx%d\n", f.area ? "area" : f.rs.mode == MI_BLUR_RESIZE_NEAREST ? "nearest" : "bilinear", width, height, *wo, *ho);
 }
 
 // The banner's "Blur kernel" line of --pyr-down, which needs the image size (print_filter() comes before the image is

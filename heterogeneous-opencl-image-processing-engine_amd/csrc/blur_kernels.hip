@@ -1645,6 +1645,7 @@ int launch(const LaunchDesc &d)
     case FilterKind::WARP: return launch_warp(d);
     case FilterKind::WARP_PERSP: return launch_warp_persp(d);
     case FilterKind::REMAP: return launch_remap(d);
+    case FilterKind::AREA: return launch_area(d);
     }
     return MI_BLUR_ERR_INVALID;
 }

@@ -58,6 +58,8 @@ int launch_warp_persp(const LaunchDesc &d);
 // The remap (FilterKind::REMAP, remap_kernels.hip): d.filter->remap_map is DEVICE memory, out_h x out_w int32 pairs, read by
 // the kernels of this launch only.  The contract of launch_resize.
 int launch_remap(const LaunchDesc &d);
+// The area resize (FilterKind::AREA, area_kernels.hip).  The contract of launch_resize.
+int launch_area(const LaunchDesc &d);
 // Sets what last_kernel() reports for the calling thread.
 void set_last_kernel(const char *name);
 

@@ -406,6 +406,42 @@ void cpu_resize_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, const
     }
 }
 
+// Output rows [Y_begin, Y_end) of the area resize of f (f.out_w, f.out_h) on one W x H image; out = the resized image (dense).
+// Separable: the vertical sums V[q] = sum_j wy(Y, j) * in[j][q] of a whole input row of bytes (at most 255 H < 2^23), then
+// per output byte S = sum_i wx(X, i) * V[i * C + c] in 64 bits and the one rounding of area_round() (filter.h): the
+// arithmetic of blur_area_tiled_kernel.  xtab, ytab: area_xtable / area_ytable, built once per call, shared by the threads.
+void cpu_area_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, const Filter &f, int Y_begin, int Y_end, const AreaAxis *xtab, const AreaAxis *ytab)
+{
+    const int Wo = f.out_w, Ho = f.out_h;
+    const size_t pitch = (size_t)W * C, opitch = (size_t)Wo * C;
+    const int64_t D = (int64_t)W * H;
+    const double rden = area_rden(W, H);
+    std::vector<uint32_t> V(pitch);
+    for (int Y = Y_begin; Y < Y_end; Y++) {
+        const AreaAxis ay = ytab[Y];
+        for (int j = ay.i_lo; j <= ay.i_hi; j++) {
+            const uint8_t *r = in + (size_t)j * pitch;
+            const uint32_t w = area_weight(ay, Ho, j);
+            if (j == ay.i_lo) for (size_t q = 0; q < pitch; q++) V[q] = w * r[q];
+            else for (size_t q = 0; q < pitch; q++) V[q] += w * r[q];
+        }
+        uint8_t *o = out + (size_t)Y * opitch;
+        for (int X = 0; X < Wo; X++) {
+            const AreaAxis ax = xtab[X];
+            for (int c = 0; c < C; c++) {
+                const uint32_t *v = V.data() + (size_t)ax.i_lo * C + c;
+                uint64_t S = (uint64_t)(uint32_t)ax.w_lo * v[0];
+                uint32_t mid = 0;                                       // at most 63 taps of less than 2^23
+                const int n = ax.i_hi - ax.i_lo;
+                for (int k = 1; k < n; k++) mid += v[(size_t)k * C];
+                S += (uint64_t)(uint32_t)Wo * mid;
+                if (n > 0) S += (uint64_t)(uint32_t)ax.w_hi * v[(size_t)n * C];
+                o[(size_t)X * C + c] = (uint8_t)area_round(S, D, rden);
+            }
+        }
+    }
+}
+
 // Output rows [Y_begin, Y_end) of the affine warp of f (f.warp_*) on one W x H image; out = the warped image (dense).
 // Every byte through warp_coord() and warp_sample() (filter.h), the functions of the GPU's generic kernel.
 void cpu_warp_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, const Filter &f, int Y_begin, int Y_end)
@@ -466,6 +502,22 @@ std::vector<ResizeCoord> resize_xtable(int W, const Filter &f)
     return t;
 }
 
+// Empty for any filter but an area resize.
+std::vector<AreaAxis> area_xtable(int W, const Filter &f)
+{
+    if (f.kind != FilterKind::AREA) return {};
+    std::vector<AreaAxis> t((size_t)f.out_w);
+    for (int X = 0; X < f.out_w; X++) t[(size_t)X] = area_axis(W, f.out_w, X);
+    return t;
+}
+std::vector<AreaAxis> area_ytable(int H, const Filter &f)
+{
+    if (f.kind != FilterKind::AREA) return {};
+    std::vector<AreaAxis> t((size_t)f.out_h);
+    for (int Y = 0; Y < f.out_h; Y++) t[(size_t)Y] = area_axis(H, f.out_h, Y);
+    return t;
+}
+
 // n_images bands of band_rows rows; output rows [y0,y1) of each.  Threads take whole
 // images when there are enough of them, else row slices of each image.  A whole_image_only filter (filter.h): y0 = 0,
 // y1 = band_rows; the output blocks are the filter's own output images and the row slices are cut in output rows.
@@ -479,6 +531,7 @@ void cpu_blur_batch(const uint8_t *in, uint8_t *out, int W, int band_rows, int C
     if (whole_image_only(f)) { y0 = 0; y1 = o.rows; }           // from here on: output rows
     if (out_stride == 0) out_stride = (size_t)o.width * C * o.rows;
     const std::vector<ResizeCoord> xtab = resize_xtable(W, f);
+    const std::vector<AreaAxis> area_x = area_xtable(W, f), area_y = area_ytable(band_rows, f);
     const int rows = y1 - y0;
     // work items: (image, row slice)
     // enough items for the threads to end together: a batch of 35 images on 16 threads is three rounds of whole images with the
@@ -509,6 +562,7 @@ void cpu_blur_batch(const uint8_t *in, uint8_t *out, int W, int band_rows, int C
             case FilterKind::WARP: cpu_warp_rows(src, dst, W, band_rows, C, f, ys, ye); break;
             case FilterKind::WARP_PERSP: cpu_warp_persp_rows(src, dst, W, band_rows, C, f, ys, ye); break;
             case FilterKind::REMAP: cpu_remap_rows(src, dst, W, band_rows, C, f, ys, ye); break;
+            case FilterKind::AREA: cpu_area_rows(src, dst, W, band_rows, C, f, ys, ye, area_x.data(), area_y.data()); break;
             }
         }
     };

@@ -31,6 +31,11 @@ void cpu_sep_down_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, con
 // Output rows [Y_begin, Y_end) of the resize of f (f.resize_*); xtab = resize_xtable(W, f), the x axis of every output column.
 void cpu_resize_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, const Filter &f, int Y_begin, int Y_end, const ResizeCoord *xtab);
 std::vector<ResizeCoord> resize_xtable(int W, const Filter &f);
+// Output rows [Y_begin, Y_end) of the area resize of f (f.out_w, f.out_h); xtab = area_xtable(W, f), ytab = area_ytable(H, f):
+// area_axis of every output column / row.
+void cpu_area_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, const Filter &f, int Y_begin, int Y_end, const AreaAxis *xtab, const AreaAxis *ytab);
+std::vector<AreaAxis> area_xtable(int W, const Filter &f);
+std::vector<AreaAxis> area_ytable(int H, const Filter &f);
 // Output rows [Y_begin, Y_end) of the affine warp of f (f.warp_*).
 void cpu_warp_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, const Filter &f, int Y_begin, int Y_end);
 // Output rows [Y_begin, Y_end) of the perspective warp of f (f.warp_h).

@@ -20,7 +20,7 @@ struct SepTaps {
     unsigned wx[2 * SEP_MAX_R + 1], wy[2 * SEP_MAX_R + 1];
 };
 
-enum class FilterKind { BOX, SEP, MEDIAN, MORPH, BILATERAL, CONV, SEP_DOWN, RESIZE, WARP, WARP_PERSP, REMAP };
+enum class FilterKind { BOX, SEP, MEDIAN, MORPH, BILATERAL, CONV, SEP_DOWN, RESIZE, WARP, WARP_PERSP, REMAP, AREA };
 
 // BOX: the fixed 3x3 / 5x5 kernel of `radius` 1|2.  SEP: the separable kernel `taps`.  MEDIAN: the median of `radius` 1..7.
 // MORPH: the window minimum / maximum / their difference (`morph_op`) over (2 morph_rx + 1) x (2 morph_ry + 1).
@@ -40,6 +40,8 @@ enum class FilterKind { BOX, SEP, MEDIAN, MORPH, BILATERAL, CONV, SEP_DOWN, RESI
 // REMAP: the remap (mi_blur_remap): as WARP, but output pixel (X, Y) samples the position entry (Y, X) of the table
 // remap_map gives it, 11 fraction bits (remap_axis() below): the third map source.  The table is NOT owned by the Filter:
 // device memory for a launch, host memory for the CPU device; whoever builds the Filter keeps it alive.
+// AREA: the area resize (mi_blur_area) to out_w x out_h: every output pixel is the box average of the input pixels its
+// footprint covers, partly covered ones by their share (area_axis() below), one rounding.  No mode, no border.
 struct Filter {
     FilterKind kind;
     int radius;             // BOX and MEDIAN
@@ -51,7 +53,7 @@ struct Filter {
     int32_t conv_bias = 0;
     int16_t conv_k[2][15 * 15] = {};
     int down_sx = 1, down_sy = 1, down_ox = 0, down_oy = 0;   // SEP_DOWN (strides 1..4, phases below them); after the older fields, so the initialisers above stay
-    int out_w = 0, out_h = 0, sample_mode = 0;                // RESIZE and WARP: the output image (1..MI_BLUR_RESIZE_MAX_DIM each way) and mi_blur_resize_mode; after them, for the same reason
+    int out_w = 0, out_h = 0, sample_mode = 0;                // RESIZE, WARP and AREA (no mode): the output image (1..MI_BLUR_RESIZE_MAX_DIM each way) and mi_blur_resize_mode; after them, for the same reason
     int warp_border = 0, warp_fill = 0;                       // WARP (mi_blur_warp_border, fill 0..255); last, for the same reason
     int64_t warp_m[6] = {};                                   // WARP: the OUTPUT -> INPUT map, Q16, row-major 2 x 3
     int64_t warp_h[9] = {};                                   // WARP_PERSP: the OUTPUT -> INPUT homography, row-major 3 x 3, free scale; out_w .. warp_fill as WARP
@@ -352,6 +354,36 @@ inline bool remap_ok(const mi_blur_remap *r, int W, int H, int C)
            (r->stage_bytes == 0 || (r->stage_bytes >= 16 && r->stage_bytes <= REMAP_STAGE_MAX));
 }
 
+// ---- the area resize (include/mi_blur.h, "Area resize").  The GPU kernels, the CPU device and mi_blur_area_coord all take
+// their taps from area_axis().
+// One axis: output X of n_out samples over n_in input samples, in units where an input pixel is n_out long and an output
+// pixel n_in.  Taps i_lo..i_hi; the first weighs w_lo, the last w_hi (0 when i_hi == i_lo: w_lo is then n_in), every tap
+// between them n_out.  1 <= n_in, n_out <= MI_BLUR_RESIZE_MAX_DIM keeps everything in 32 bits ((X + 1) * n_in <= 2^30).
+struct AreaAxis { int i_lo, i_hi, w_lo, w_hi; };
+MI_BLUR_HD inline AreaAxis area_axis(int n_in, int n_out, int X)
+{
+    const unsigned a = (unsigned)X * (unsigned)n_in, b = a + (unsigned)n_in;
+    AreaAxis r;
+    r.i_lo = (int)(a / (unsigned)n_out);
+    r.i_hi = (int)((b - 1u) / (unsigned)n_out);
+    if (r.i_hi == r.i_lo) { r.w_lo = n_in; r.w_hi = 0; }
+    else { r.w_lo = (int)((unsigned)(r.i_lo + 1) * (unsigned)n_out - a); r.w_hi = (int)(b - (unsigned)r.i_hi * (unsigned)n_out); }
+    return r;
+}
+MI_BLUR_HD inline unsigned area_weight(const AreaAxis &ax, int n_out, int i) { return (unsigned)(i == ax.i_lo ? ax.w_lo : i == ax.i_hi ? ax.w_hi : n_out); }
+// The one rounding: floor((2 S + D) / (2 D)) for the weighted sum S <= 255 D of a W x H image, D = W * H <= 2^30, and
+// rden = area_rden(W, H).  floor_div_clamped() gives the same byte whatever the last bit of the double estimate.
+MI_BLUR_HD inline double area_rden(int W, int H) { return 1.0 / (double)(2 * ((int64_t)W * H)); }
+MI_BLUR_HD inline unsigned area_round(uint64_t S, int64_t D, double rden) { return (unsigned)floor_div_clamped((int64_t)(2 * S) + D, 2 * D, rden, 0, 255); }
+// An area resize to out_w x out_h that is valid for a W x H image of C channels: the sizes and byte limits of resize_ok()
+// and a reduction of at most MI_BLUR_AREA_MAX_RATIO on either axis (enlargements are valid).
+inline bool area_ok(int out_w, int out_h, int W, int H, int C)
+{
+    return resize_ok(out_w, out_h, MI_BLUR_RESIZE_BILINEAR, W, H, C) && (long long)W <= (long long)MI_BLUR_AREA_MAX_RATIO * out_w &&
+           (long long)H <= (long long)MI_BLUR_AREA_MAX_RATIO * out_h;
+}
+inline bool area_ok(const mi_blur_area *r, int W, int H, int C) { return r && area_ok(r->out_width, r->out_height, W, H, C); }
+
 // Output size of a decimation of a W x H image: kept columns / rows (> 0 for a valid decimation, down_ok()).
 inline int down_cols(int W, int sx, int ox) { return (W - ox + sx - 1) / sx; }
 inline int down_rows(int H, int sy, int oy) { return (H - oy + sy - 1) / sy; }
@@ -368,7 +400,7 @@ inline bool down_ok(const mi_blur_decimation *d, int W, int H)
 inline bool whole_image_only(const Filter &f)
 {
     return f.kind == FilterKind::SEP_DOWN || f.kind == FilterKind::RESIZE || f.kind == FilterKind::WARP || f.kind == FilterKind::WARP_PERSP ||
-           f.kind == FilterKind::REMAP;
+           f.kind == FilterKind::REMAP || f.kind == FilterKind::AREA;
 }
 // Width and rows of the output block of one band of band_rows rows x W of which rows [y0, y1) are asked for: those rows
 // at the input's width, or the filter's own output image (of the whole band) for a whole_image_only filter.
@@ -376,7 +408,7 @@ struct OutShape { int width, rows; };
 inline OutShape out_shape(const Filter &f, int W, int band_rows, int y0, int y1)
 {
     if (f.kind == FilterKind::SEP_DOWN) return {down_cols(W, f.down_sx, f.down_ox), down_rows(band_rows, f.down_sy, f.down_oy)};
-    if (f.kind == FilterKind::RESIZE || f.kind == FilterKind::WARP || f.kind == FilterKind::WARP_PERSP || f.kind == FilterKind::REMAP) return {f.out_w, f.out_h};
+    if (f.kind == FilterKind::RESIZE || f.kind == FilterKind::WARP || f.kind == FilterKind::WARP_PERSP || f.kind == FilterKind::REMAP || f.kind == FilterKind::AREA) return {f.out_w, f.out_h};
     return {W, y1 - y0};
 }
 
@@ -452,6 +484,15 @@ inline int filter_remap(const mi_blur_remap *r, const int32_t *map, Filter *f)
     *f = Filter{FilterKind::REMAP, 0, {}};
     f->out_w = r->out_width; f->out_h = r->out_height; f->sample_mode = r->mode; f->warp_border = r->border; f->warp_fill = r->fill;
     f->remap_map = map; f->remap_stage_bytes = r->stage_bytes ? r->stage_bytes : REMAP_STAGE_MAX;
+    return MI_BLUR_OK;
+}
+
+// The target size of *r (the image size, and with it the ratio, is checked where it is known: area_ok()).
+inline int filter_area(const mi_blur_area *r, Filter *f)
+{
+    if (!f || !area_ok(r, 1, 1, 1)) return MI_BLUR_ERR_INVALID;
+    *f = Filter{FilterKind::AREA, 0, {}};
+    f->out_w = r->out_width; f->out_h = r->out_height;
     return MI_BLUR_OK;
 }
 
@@ -699,5 +740,64 @@ inline void remap_walk(const int32_t *map, int W, int H, int C, int Wo, int Ho, 
             else t->direct++;
         }
 }
+
+// ---- blur_area_tiled_kernel.  A tile is AREA_TH output rows x a strip of output chunks (whole units, warp_unit()).  Its
+// 256 threads are 256 / span row groups of `span` (64 | 128 | 256) threads: a group owns AREA_TH / (256 / span)
+// consecutive output rows, thread `col` of it the input chunk column sc.lo + col of the strip's input span sc.  LDS: the x
+// table (two dwords per output byte of a tile row), then one V row per group: one dword per input byte of the span, the
+// dword of byte q at area_v_pos(q).  Nothing of the input is staged.
+constexpr int AREA_TH = 4;                          // output rows per tile
+constexpr int AREA_THREADS = 256;
+constexpr int AREA_MAX_SPAN = 256;                  // input chunks under a strip: one per thread of the widest group
+constexpr int AREA_WAVE_SPAN = 64;                  // what strips are cut for: one input chunk per lane of one wave
+// The input chunks under output chunks [x0c, x0c + nc): the first tap of their first pixel to the last tap of their last.
+MI_BLUR_HD inline Span area_stage_chunks(int W, int Wo, int C, int x0c, int nc)
+{
+    const Span px = tile_pixels(x0c, nc, C);
+    return chunk_span(area_axis(W, Wo, px.lo).i_lo, area_axis(W, Wo, px.hi).i_hi, C);
+}
+// V dword of input byte q of the span: one spare dword every eight, so that the horizontal pass's reads (lanes four
+// output bytes = 4 * ratio input bytes apart) and the vertical pass's writes (lanes 16 bytes apart) spread over the banks.
+MI_BLUR_HD inline uint32_t area_v_pos(int q) { return (uint32_t)(q + (q >> 3)); }
+MI_BLUR_HD inline int area_v_row(int nsc) { return nsc * 18; }      // dwords of a V row of nsc chunks: area_v_pos(16 nsc - 1) + 1 <= 18 nsc
+// x table entry of channel c of output pixel X: the span byte of its first tap | taps << 16, then w_lo | w_hi << 16.
+MI_BLUR_HD inline uint32_t area_x_entry0(const AreaAxis &ax, int C, int c, int sc0) { return (uint32_t)(ax.i_lo * C + c - sc0 * 16) | ((uint32_t)(ax.i_hi - ax.i_lo + 1) << 16); }
+MI_BLUR_HD inline uint32_t area_x_entry1(const AreaAxis &ax) { return (uint32_t)ax.w_lo | ((uint32_t)ax.w_hi << 16); }
+// The tiles of a launch (Wo <= W, rows of whole chunks both sides): strips as wide as keep every strip's input span within
+// AREA_WAVE_SPAN chunks, at least one unit, and narrower still while the horizontal pass of a 64-thread group (one output
+// dword per thread and step) would take a last step less than half full: a strip of 18 chunks is two steps for 72
+// dwords, one of 15 is one.  max_nsc is the largest span of the launch (the walk below), span the group size that holds
+// it.  One unit at the ratio cap spans at most 194 chunks (C = 3: 16 pixels, 1025 input pixels), so
+// max_nsc <= AREA_MAX_SPAN for every valid launch; area_tiles_fit() is the guard all the same.
+struct AreaTiles { TileGrid g; int max_nsc, span; };
+inline int area_max_span(const TileGrid &g, int W, int Wo, int C)
+{
+    int m = 1;
+    for (int s = 0; s < g.nstrips; s++) {
+        const int x0c = s * g.ncols, nc = g.cpr - x0c < g.ncols ? g.cpr - x0c : g.ncols;
+        const int n = area_stage_chunks(W, Wo, C, x0c, nc).n();
+        m = n > m ? n : m;
+    }
+    return m;
+}
+inline AreaTiles area_tiles(int W, int Wo, int Ho, int C)
+{
+    const int cpr = (int)((long long)Wo * C / 16), unit = warp_unit(C), units = cpr / unit;
+    long long m = (long long)(AREA_WAVE_SPAN - 3) * Wo / ((long long)W * unit);
+    m = m < 1 ? 1 : m > units ? units : m;
+    AreaTiles t;
+    for (;; m--) {
+        t.g = tile_grid(cpr, Ho, unit, (int)m);
+        t.g.ntiles_y = (Ho + AREA_TH - 1) / AREA_TH;
+        t.max_nsc = area_max_span(t.g, W, Wo, C);
+        const int dwords = t.g.ncols * 4, last_step = (dwords - 1) % AREA_WAVE_SPAN + 1;
+        if (m == 1 || (t.max_nsc <= AREA_WAVE_SPAN && (dwords <= AREA_WAVE_SPAN || 2 * last_step >= AREA_WAVE_SPAN))) break;
+    }
+    t.span = t.max_nsc <= 64 ? 64 : t.max_nsc <= 128 ? 128 : 256;
+    return t;
+}
+inline bool area_tiles_fit(const AreaTiles &t) { return t.max_nsc <= AREA_MAX_SPAN; }
+inline int area_xtab_bytes(const AreaTiles &t) { return t.g.ncols * 16 * 8; }
+inline size_t area_lds_bytes(const AreaTiles &t) { return (size_t)area_xtab_bytes(t) + (size_t)(AREA_THREADS / t.span) * (size_t)area_v_row(t.max_nsc) * 4u; }
 
 }  // namespace mi_blur

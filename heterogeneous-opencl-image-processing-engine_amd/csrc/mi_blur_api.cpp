@@ -96,7 +96,7 @@ enum class PreCheck {
     FILTER,     // sep: the constructor's status
     ARGS,       // median, morph, bilateral, conv: + pointers, dimensions, image count
     ARGS_ROWS,  // conv_band: + the row range
-    ARGS_SIZE,  // sep_down, resize, warp, warp_perspective, remap: + the image within INT_MAX bytes
+    ARGS_SIZE,  // sep_down, resize, warp, warp_perspective, remap, area: + the image within INT_MAX bytes
 };
 
 // Every mi_blur_enqueue* export: one launch of f on device memory.  built: the status of f's constructor.
@@ -129,6 +129,11 @@ static int resize_for(const mi_blur_resize *r, int W, int H, int C, Filter *f)
 {
     const int rc = filter_resize(r, f);
     return rc ? rc : resize_ok(r, W, H, C) ? MI_BLUR_OK : MI_BLUR_ERR_INVALID;
+}
+static int area_for(const mi_blur_area *r, int W, int H, int C, Filter *f)
+{
+    const int rc = filter_area(r, f);
+    return rc ? rc : area_ok(r, W, H, C) ? MI_BLUR_OK : MI_BLUR_ERR_INVALID;
 }
 
 static int warp_for(const mi_blur_warp *w, int W, int H, int C, Filter *f)
@@ -275,6 +280,27 @@ extern "C" int mi_blur_enqueue_resize(const uint8_t *d_in, uint8_t *d_out, int w
 {
     Filter f;
     return enqueue_filter(resize_for(r, width, height, channels, &f), f, PreCheck::ARGS_SIZE, d_in, d_out, width, height,
+                          channels, n_images, 0, height, MI_BLUR_VARIANT_AUTO, stream);
+}
+
+// ----------------------------------------------------------------------------------
+// area resize: exact box average, any output size, reductions up to 64x (no reference analogue)
+// ----------------------------------------------------------------------------------
+extern "C" int mi_blur_area_coord(int n_in, int n_out, int X, int *i_lo, int *i_hi, int *w_lo, int *w_hi)
+{
+    if (!i_lo || !i_hi || !w_lo || !w_hi || n_in < 1 || n_out < 1 || n_in > MI_BLUR_RESIZE_MAX_DIM || n_out > MI_BLUR_RESIZE_MAX_DIM ||
+        X < 0 || X >= n_out)
+        return MI_BLUR_ERR_INVALID;
+    const AreaAxis a = area_axis(n_in, n_out, X);
+    *i_lo = a.i_lo; *i_hi = a.i_hi; *w_lo = a.w_lo; *w_hi = a.w_hi;
+    return MI_BLUR_OK;
+}
+
+extern "C" int mi_blur_enqueue_area(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int n_images,
+                                    const mi_blur_area *r, void *stream)
+{
+    Filter f;
+    return enqueue_filter(area_for(r, width, height, channels, &f), f, PreCheck::ARGS_SIZE, d_in, d_out, width, height,
                           channels, n_images, 0, height, MI_BLUR_VARIANT_AUTO, stream);
 }
 
@@ -1610,7 +1636,7 @@ extern "C" int mi_blur_submit_planar(mi_blur_ctx *c, const uint8_t *host_planar_
 
 // Every mi_blur_ctx_set_*: the filter that build(&f) makes in place of the context's, for every submit from now on (before the
 // first one only; the whole_image_only ones for mi_blur_submit only).  null_arg: a required pointer argument is null,
-// which set_kernel, set_sep_down, set_resize, set_warp and set_warp_perspective answer before they look at the state; the other setters leave a null
+// which set_kernel, set_sep_down, set_resize, set_area, set_warp and set_warp_perspective answer before they look at the state; the other setters leave a null
 // table to the constructor, behind the state.
 template <typename B>
 static int ctx_set_filter(mi_blur_ctx *c, bool null_arg, B &&build)
@@ -1637,6 +1663,11 @@ extern "C" int mi_blur_ctx_set_sep_down(mi_blur_ctx *c, const mi_blur_sep_kernel
 extern "C" int mi_blur_ctx_set_resize(mi_blur_ctx *c, const mi_blur_resize *r)
 {
     return ctx_set_filter(c, !r, [&](Filter *f) { return resize_for(r, c->W, c->H, c->C, f); });
+}
+
+extern "C" int mi_blur_ctx_set_area(mi_blur_ctx *c, const mi_blur_area *r)
+{
+    return ctx_set_filter(c, !r, [&](Filter *f) { return area_for(r, c->W, c->H, c->C, f); });
 }
 
 extern "C" int mi_blur_ctx_set_warp(mi_blur_ctx *c, const mi_blur_warp *w)
@@ -2137,6 +2168,13 @@ extern "C" int mi_blur_cpu_run_resize(const uint8_t *in, uint8_t *out, int width
 {
     Filter f;
     return cpu_run_filter(resize_for(r, width, height, channels, &f), f, in, out, width, height, channels, n_images, n_threads);
+}
+
+extern "C" int mi_blur_cpu_run_area(const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,
+                                    const mi_blur_area *r, int n_threads)
+{
+    Filter f;
+    return cpu_run_filter(area_for(r, width, height, channels, &f), f, in, out, width, height, channels, n_images, n_threads);
 }
 
 extern "C" int mi_blur_cpu_run_warp(const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,

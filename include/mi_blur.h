@@ -71,7 +71,7 @@ int mi_blur_version(void);
  * "blur_conv_generic_kernel", "blur_sep_down_tiled_kernel", "blur_sep_down_generic_kernel",
  * "blur_resize_tiled_kernel", "blur_resize_generic_kernel", "blur_warp_tiled_kernel", "blur_warp_generic_kernel",
  * "blur_warp_persp_tiled_kernel", "blur_warp_persp_generic_kernel", "blur_remap_tiled_kernel",
- * "blur_remap_generic_kernel"; "" before the first):
+ * "blur_remap_generic_kernel", "blur_area_tiled_kernel", "blur_area_generic_kernel"; "" before the first):
  * reports name the kernel a profiler will show.  Static string, never NULL. */
 const char *mi_blur_last_kernel(void);
 
@@ -484,7 +484,8 @@ int mi_blur_ctx_set_sep_down(mi_blur_ctx *ctx, const mi_blur_sep_kernel *k, cons
  * apply to both the input image and the output image.  Any ratio is valid.
  * This is NOT OpenCV's INTER_LINEAR bit for bit: the grid and the 11 fraction bits are the same, but the rounding is a
  * single final one.  A reduction by more than 2x aliases (bilinear reads 2 x 2 input pixels whatever the ratio):
- * mi_blur_enqueue_sep_down's area_down / pyr_down presets should come first for such reductions.
+ * mi_blur_enqueue_sep_down's area_down / pyr_down presets should come first for such reductions, or the reduction
+ * be an area resize (mi_blur_enqueue_area, below), which is anti-aliased at every ratio.
  * The output is interleaved and dense: its pitch is Wo*C and images lie Wo*Ho*C bytes apart.
  * ---------------------------------------------------------------------- */
 #define MI_BLUR_RESIZE_MAX_DIM 32768
@@ -519,6 +520,71 @@ int mi_blur_cpu_run_resize(const uint8_t *in, uint8_t *out, int width, int heigh
  * or the CPU device.  mi_blur_submit_band, _bands, _planar and both resident runs return MI_BLUR_ERR_UNSUPPORTED for
  * such a context. */
 int mi_blur_ctx_set_resize(mi_blur_ctx *ctx, const mi_blur_resize *r);
+
+/* ------------------------------------------------------------------------
+ * Area resize: exact box-average resize to any output size, reductions up to 64x per axis (no reference analogue).
+ * The anti-aliased reduction: every output pixel is the average of the input area under it, input pixels that it covers
+ * partly counted by their share.  The definition is a ratio of integers with a single rounding; the GPU, the CPU device
+ * and a numpy restatement agree byte for byte.
+ *
+ * One axis with n_in input and n_out output samples, measured in units where an input pixel is n_out long and an output
+ * pixel n_in long (both images are then n_in * n_out long).  Output X covers [X*n_in, (X+1)*n_in), input i covers
+ * [i*n_out, (i+1)*n_out):
+ *   i_lo = floor(X*n_in / n_out)              i_hi = floor(((X+1)*n_in - 1) / n_out)
+ *   w(X,i) = min((X+1)*n_in, (i+1)*n_out) - max(X*n_in, i*n_out)     for i_lo <= i <= i_hi, else 0
+ * Every w in the range is positive; sum_i w(X,i) = n_in and sum_X w(X,i) = n_out; the taps between the first and the
+ * last all weigh n_out, only those two are partial; there are at most ceil(n_in/n_out) + 1 taps; nothing clamps, the
+ * taps always lie inside the image.
+ *
+ * With (wx, wy) from the two axes and D = W*H, per channel:
+ *   S   = sum_j wy(Y,j) * sum_i wx(X,i) * in[j][i][c]          (<= 255 * D < 2^38: 64 bits)
+ *   out = floor((2*S + D) / (2*D))                             (one rounding, half up)
+ * The order of the two passes cannot change S.  Equal sizes are the identity; a constant image stays constant; an integer
+ * reduction by k is the mean of every k x k block rounded half up (at k = 2 that is (sum + 2) >> 2: never below the
+ * MI_BLUR_DOWN_AREA2 preset, which truncates, and at most 1 above it); an integer enlargement by k replicates pixels.  The
+ * result is within 0.5 of the real-valued box average.
+ * The definition holds at any ratio, so enlarging is valid; there it is NOT OpenCV's INTER_AREA, which switches to
+ * bilinear when enlarging.  On reductions it is not OpenCV's bit for bit either: OpenCV weighs in float.
+ *
+ * Valid: out_width, out_height, width, height in 1..MI_BLUR_RESIZE_MAX_DIM (so X*n_in <= 2^30: one axis stays in 32
+ * bits); the resize's per-image byte limits on both images; width <= MI_BLUR_AREA_MAX_RATIO * out_width and height <=
+ * MI_BLUR_AREA_MAX_RATIO * out_height.  The cap on the ratio is a condition of the definition's use here, not a tuning
+ * number: it bounds the taps one thread of the byte-per-thread kernel walks at 65 x 65 (without it a 1 x 1 output of a
+ * 2 GiB image would be two billion serial loads in one thread) and the input under one output chunk at 66 chunks, so the
+ * tiled kernel needs no rule about what fits.  A larger reduction is two calls.
+ * The output is interleaved and dense: its pitch is Wo*C and images lie Wo*Ho*C bytes apart.
+ * ---------------------------------------------------------------------- */
+#define MI_BLUR_AREA_MAX_RATIO 64
+typedef struct mi_blur_area { int out_width, out_height; } mi_blur_area;
+
+/* The first and the last tap of output index X on one axis and their weights, through the same function the kernels
+ * and the CPU device use.  *w_hi = 0 when *i_hi == *i_lo (one tap: *w_lo is then n_in); every tap between the two
+ * weighs n_out.  MI_BLUR_ERR_INVALID: a null pointer, n_in or n_out outside 1..MI_BLUR_RESIZE_MAX_DIM, X outside
+ * [0, n_out).  (The ratio is not looked at: the axis is defined at any.) */
+int mi_blur_area_coord(int n_in, int n_out, int X, int *i_lo, int *i_hi, int *w_lo, int *w_hi);
+
+/* n_images images of width x height in, n_images images of r->out_width x r->out_height out (device memory,
+ * asynchronous; n_images == 0 is MI_BLUR_OK; image offsets are 64-bit).  Every argument is checked before a device is
+ * asked for: MI_BLUR_ERR_INVALID comes before MI_BLUR_ERR_NO_DEVICE.
+ * blur_area_tiled_kernel (every input byte read once, coalesced; vertical sums in registers, handed to the horizontal
+ * pass through LDS; nothing staged) takes exactly the launches with 1-4 channels, out_width <= width and out_height <=
+ * height (reduction or equality on both axes), width*channels and out_width*channels multiples of 16 (input and output
+ * rows are whole 16-byte chunks) and both pointers 16-byte aligned (and, where a context's in-place submit gives image
+ * strides, strides that are multiples of 16; this export's are dense, which they then are); every other launch (any
+ * enlargement, 5+ channels, odd rows or pointers) goes to blur_area_generic_kernel (one output byte per thread).
+ * mi_blur_last_kernel() says which one ran. */
+int mi_blur_enqueue_area(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int n_images,
+                         const mi_blur_area *r, void *stream);
+/* The same on the CPU device's threads (synchronous). */
+int mi_blur_cpu_run_area(const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,
+                         const mi_blur_area *r, int n_threads);
+/* Give a context (created with the INPUT width, height, channels) the area resize, with the rules of
+ * mi_blur_ctx_set_resize: only before the first submit (MI_BLUR_ERR_STATE after); it replaces what another setter set
+ * and is replaced by them; the context keeps a copy.  MI_BLUR_ERR_INVALID also when *r is not valid for the context's
+ * size.  mi_blur_submit then writes n_images * Wo*Ho*C bytes to host_out: pageable caller memory, or pinned memory on
+ * both sides (in place, one launch per submit, never the batch server), on the GPU or the CPU device.
+ * mi_blur_submit_band, _bands, _planar and both resident runs return MI_BLUR_ERR_UNSUPPORTED for such a context. */
+int mi_blur_ctx_set_area(mi_blur_ctx *ctx, const mi_blur_area *r);
 
 /* ------------------------------------------------------------------------
  * Affine warp: exact fixed-point rotate, scale, shear and translate, any output size (no reference analogue).  The
