@@ -47,6 +47,9 @@ RESIZE_MAX_DIM = 32768
 RESIZE_NEAREST, RESIZE_BILINEAR = 0, 1
 RESIZE_MODES = {"nearest": RESIZE_NEAREST, "bilinear": RESIZE_BILINEAR}
 AREA_MAX_RATIO = 64
+COLOR_MAX_CHANNELS = 4
+COLOR_CODES = {"rgb2gray": 0, "bgr2gray": 1, "gray2rgb": 2, "rgb2bgr": 3, "rgba2bgra": 4, "rgba2rgb": 5, "rgb2rgba": 6,
+               "rgb2ycbcr": 7, "ycbcr2rgb": 8}
 WARP_Q = 16
 WARP_CLAMP, WARP_CONSTANT = 0, 1
 WARP_BORDERS = {"clamp": WARP_CLAMP, "constant": WARP_CONSTANT}
@@ -62,7 +65,7 @@ def _newer(target: str, sources: list[str]) -> bool:
 
 def build_native(force: bool = False, verbose: bool = False) -> str:
     """Compile libmi_blur.so (hipcc, --offload-arch=gfx950) and the C++ hosts, in-tree."""
-    srcs = [os.path.join(CSRC, f) for f in ("blur_kernels.hip", "sep_kernels.hip", "median_kernels.hip", "morph_kernels.hip", "bilateral_kernels.hip", "conv_kernels.hip", "sep_down_kernels.hip", "resize_kernels.hip", "warp_kernels.hip", "remap_kernels.hip", "area_kernels.hip", "layout_kernels.hip", "mi_blur_api.cpp", "comm_api.cpp", "cpu_device.cpp")]
+    srcs = [os.path.join(CSRC, f) for f in ("blur_kernels.hip", "sep_kernels.hip", "median_kernels.hip", "morph_kernels.hip", "bilateral_kernels.hip", "conv_kernels.hip", "sep_down_kernels.hip", "resize_kernels.hip", "warp_kernels.hip", "remap_kernels.hip", "area_kernels.hip", "color_kernels.hip", "layout_kernels.hip", "mi_blur_api.cpp", "comm_api.cpp", "cpu_device.cpp")]
     deps = srcs + [os.path.join(CSRC, f) for f in ("api_internal.h", "blur_launch.h", "kernel_common.h", "cpu_device.h", "filter.h")] + [HEADER]
     if force or not _newer(LIB_PATH, deps):
         cmd = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra",
@@ -236,6 +239,13 @@ class Area(C.Structure):
     _fields_ = [("out_width", C.c_int), ("out_height", C.c_int)]
 
 
+class Color(C.Structure):
+    """mi_blur_color: out_channels, the shift, the matrix m[o][i], the bias per output channel, and the tables lut[o][v]
+    that are read when lut_on."""
+    _fields_ = [("out_channels", C.c_int), ("shift", C.c_int), ("m", (C.c_int32 * 4) * 4), ("bias", C.c_int32 * 4),
+                ("lut_on", C.c_int), ("lut", (C.c_uint8 * 256) * 4)]
+
+
 class Warp(C.Structure):
     """mi_blur_warp: the output size, the mode (RESIZE_NEAREST | RESIZE_BILINEAR), the border (WARP_CLAMP | WARP_CONSTANT),
     the fill byte and the OUTPUT -> INPUT map in Q16, row-major 2 x 3."""
@@ -405,6 +415,13 @@ def lib() -> C.CDLL:
         "mi_blur_enqueue_area": (i, [u8p, u8p, i, i, i, i, C.POINTER(Area), vp]),
         "mi_blur_cpu_run_area": (i, [u8p, u8p, i, i, i, i, C.POINTER(Area), i]),
         "mi_blur_ctx_set_area": (i, [vp, C.POINTER(Area)]),
+        "mi_blur_color_preset": (i, [i, C.POINTER(Color)]),
+        "mi_blur_color_identity": (i, [i, C.POINTER(Color)]),
+        "mi_blur_color_lut_gamma": (i, [C.c_double, u8p]),
+        "mi_blur_color_lut_threshold": (i, [i, i, i, u8p]),
+        "mi_blur_enqueue_color": (i, [u8p, u8p, i, i, i, i, C.POINTER(Color), vp]),
+        "mi_blur_cpu_run_color": (i, [u8p, u8p, i, i, i, i, C.POINTER(Color), i]),
+        "mi_blur_ctx_set_color": (i, [vp, C.POINTER(Color)]),
         "mi_blur_warp_coord": (i, [C.POINTER(Warp), i, i, C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i)]),
         "mi_blur_warp_rotation": (i, [C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double)]),
         "mi_blur_warp_set_matrix": (i, [C.POINTER(Warp), C.POINTER(C.c_double), i]),
@@ -588,6 +605,12 @@ class Context:
         check(lib().mi_blur_ctx_set_area(self.h, C.byref(r)), "mi_blur_ctx_set_area")
         self.area_spec = r
 
+    def set_color(self, color: "Color") -> None:
+        """The colour transform in place of the blur (before the first submit only): submit() then writes images of
+        color.out_channels channels; the band, planar and resident forms are not supported."""
+        check(lib().mi_blur_ctx_set_color(self.h, C.byref(color)), "mi_blur_ctx_set_color")
+        self.color_spec = color
+
     def set_warp(self, warp: "Warp") -> None:
         """The affine warp in place of the blur (before the first submit only): submit() then writes images of
         warp.out_width x warp.out_height."""
@@ -705,10 +728,11 @@ def _images(images, name: str):
     return a
 
 
-def _filter_images(a, radius: int, device: int, batch: int, configure=None, out_size=None):
+def _filter_images(a, radius: int, device: int, batch: int, configure=None, out_size=None, out_channels=None):
     """The numpy driver of every filter function: a (from _images) through mi_blur_create (radius) / configure(ctx) /
     mi_blur_submit / mi_blur_sync.  Returns the output as (N, H, W, C), or as (N, Ho, Wo, C) for a filter whose output
-    has a size of its own: out_size = (Ho, Wo)."""
+    has a size of its own: out_size = (Ho, Wo), and with out_channels in place of C for one whose output has a channel
+    count of its own."""
     import numpy as np
     if a.ndim == 2:
         a = a[None, :, :, None]
@@ -716,11 +740,12 @@ def _filter_images(a, radius: int, device: int, batch: int, configure=None, out_
         a = a[None]
     n, h, w, c = a.shape
     ho, wo = out_size or (h, w)
-    out = np.empty((n, ho, wo, c), dtype=np.uint8)
+    co = out_channels or c
+    out = np.empty((n, ho, wo, co), dtype=np.uint8)
     if n == 0 or a.size == 0:
         return out
     per = min(n, batch if batch > 0 else 4096)
-    isz, osz = h * w * c, ho * wo * c
+    isz, osz = h * w * c, ho * wo * co
     with Context(device, w, h, c, radius, max_batch=per, n_slots=2) as ctx:
         if configure:
             configure(ctx)
@@ -982,6 +1007,115 @@ def area_resize(images, size, device: int = 0, batch: int = 0):
         raise ValueError("area_resize: size is (out_width, out_height), both at least 1")
     out = _filter_images(a, 1, device, batch, lambda ctx: ctx.set_area(wo, ho), (ho, wo))
     return out[0, :, :, 0] if rank == 2 else out[0] if rank == 3 else out
+
+
+def color_preset(name) -> "Color":
+    """The preset `name` (a key of COLOR_CODES, or its id) as a Color (mi_blur_color_preset)."""
+    k = Color()
+    code = COLOR_CODES.get(name.lower()) if isinstance(name, str) else int(name)
+    if code is None:
+        raise ValueError(f"color_preset: one of {sorted(COLOR_CODES)}")
+    check(lib().mi_blur_color_preset(code, C.byref(k)), "mi_blur_color_preset")
+    return k
+
+
+def _color_set_lut(k: "Color", lut, name: str) -> None:
+    """lut (256 entries for every channel, or out_channels x 256) into k, lut_on = 1."""
+    import numpy as np
+    t = np.asarray(lut)
+    if t.shape == (256,):
+        t = np.broadcast_to(t, (k.out_channels, 256))
+    if t.shape != (k.out_channels, 256) or t.min() < 0 or t.max() > 255:
+        raise ValueError(f"{name}: lut is 256 entries, or out_channels x 256, each 0..255")
+    t = np.ascontiguousarray(t, dtype=np.uint8)
+    for o in range(k.out_channels):
+        C.memmove(k.lut[o], t[o].ctypes.data, 256)
+    k.lut_on = 1
+
+
+def _color_run(images, make, device: int, batch: int, name: str):
+    """images through the Color that make(channels) returns: (H, W), (H, W, C) or (N, H, W, C) in; (N, H, W, Co) out of a
+    stack, (H, W, Co) out of a single image, and (H, W) where that has one channel."""
+    a = _images(images, name)
+    rank = a.ndim
+    if rank == 2:
+        a = a[None, :, :, None]
+    elif rank == 3:
+        a = a[None]
+    n, h, w, c = a.shape
+    if h == 0 or w == 0 or c == 0:
+        raise ValueError(f"{name}: images must not be empty")
+    if c > COLOR_MAX_CHANNELS:
+        raise ValueError(f"{name}: at most {COLOR_MAX_CHANNELS} channels")
+    k = make(c)
+    out = _filter_images(a, 1, device, batch, lambda ctx: ctx.set_color(k), None, k.out_channels)
+    if rank == 4:
+        return out
+    return out[0, :, :, 0] if k.out_channels == 1 else out[0]
+
+
+def color_transform(images, matrix, bias=None, shift: int = 0, lut=None, device: int = 0, batch: int = 0):
+    """The colour transform, numpy in -> numpy out (include/mi_blur.h has the definition): per pixel and output channel o
+    clamp((bias[o] + sum_i matrix[o][i] * in[i]) >> shift, 0, 255), then through lut when one is given.
+
+    matrix: Co x C integers (Co 1..4, C the images' channels); bias: Co integers (default 0); shift 0..16; lut: 256 entries
+    for every channel, or Co x 256.  images: (H, W), (H, W, C) or (N, H, W, C) uint8; the result has Co channels (a
+    one-channel result of a 2-D or 3-D input comes back as (H, W)).  device: HIP ordinal, or DEVICE_CPU.
+    Goes through mi_blur_create / mi_blur_ctx_set_color / mi_blur_submit / mi_blur_sync."""
+    import numpy as np
+    m = np.asarray(matrix, dtype=np.int64)
+    if m.ndim != 2 or not 1 <= m.shape[0] <= COLOR_MAX_CHANNELS:
+        raise ValueError("color_transform: matrix is Co x C integers, Co 1..4")
+    b = np.zeros(m.shape[0], np.int64) if bias is None else np.asarray(bias, dtype=np.int64)
+    if b.shape != (m.shape[0],) or np.abs(m).max(initial=0) >= 2**31 or np.abs(b).max(initial=0) >= 2**31:
+        raise ValueError("color_transform: bias is Co integers; every entry within 32 bits")
+
+    def make(c):
+        if m.shape[1] != c:
+            raise ValueError(f"color_transform: matrix has {m.shape[1]} columns, the images {c} channels")
+        k = Color()
+        k.out_channels, k.shift = m.shape[0], int(shift)
+        for o in range(m.shape[0]):
+            for i in range(c):
+                k.m[o][i] = int(m[o, i])
+            k.bias[o] = int(b[o])
+        if lut is not None:
+            _color_set_lut(k, lut, "color_transform")
+        return k
+    return _color_run(images, make, device, batch, "color_transform")
+
+
+def cvt_color(images, code: str, device: int = 0, batch: int = 0):
+    """Colour conversion by preset, numpy in -> numpy out: code is one of COLOR_CODES ("rgb2gray", "bgr2gray", "gray2rgb",
+    "rgb2bgr", "rgba2bgra", "rgba2rgb", "rgb2rgba", "rgb2ycbcr", "ycbcr2rgb"; include/mi_blur.h has the table).  A 2-D
+    array is one grey image; a one-channel result of a 3-D input comes back as (H, W).  Not OpenCV's cvtColor bit for bit."""
+    k = color_preset(code)
+    return _color_run(images, lambda c: k, device, batch, "cvt_color")
+
+
+def apply_lut(images, lut, device: int = 0, batch: int = 0):
+    """Every byte through a table (OpenCV's LUT): lut is 256 entries for every channel, or C x 256."""
+    def make(c):
+        k = Color()
+        check(lib().mi_blur_color_identity(c, C.byref(k)), "mi_blur_color_identity")
+        _color_set_lut(k, lut, "apply_lut")
+        return k
+    return _color_run(images, make, device, batch, "apply_lut")
+
+
+def gamma_correct(images, gamma: float, device: int = 0, batch: int = 0):
+    """out = round(255 * (in / 255) ** gamma), through the table of mi_blur_color_lut_gamma."""
+    t = (C.c_uint8 * 256)()
+    check(lib().mi_blur_color_lut_gamma(float(gamma), t), "mi_blur_color_lut_gamma")
+    return apply_lut(images, list(t), device, batch)
+
+
+def threshold(images, t: int, lo: int = 0, hi: int = 255, device: int = 0, batch: int = 0):
+    """out = hi where in > t, else lo (OpenCV's THRESH_BINARY with two levels), through the table of
+    mi_blur_color_lut_threshold."""
+    tab = (C.c_uint8 * 256)()
+    check(lib().mi_blur_color_lut_threshold(int(t), int(lo), int(hi), tab), "mi_blur_color_lut_threshold")
+    return apply_lut(images, list(tab), device, batch)
 
 
 def warp_coord(warp: "Warp", X: int, Y: int) -> tuple[int, int, int, int]:

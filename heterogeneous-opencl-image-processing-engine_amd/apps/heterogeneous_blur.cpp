@@ -1,7 +1,7 @@
 // heterogeneous_blur — Approach 1 (image-level distribution) host, MI355X-native.
 //
 //   heterogeneous_blur {cpu|gpu|both} [gpu_ratio] [batch]  [--image F | --synthetic | --size WxH] [--channels C]
-//                      [--ksize 3|5 | --sigma S [--sigma-y S] [--radius R] | --median K | --erode K | --dilate K | --morph-gradient K | --bilateral K [--sigma-color S] [--sigma-space S] | --conv NAME | --pyr-down | --resize WxH [--nearest | --area] | --rotate DEG [--nearest] [--border-fill V] | --perspective x0,y0,x1,y1,x2,y2,x3,y3 [--nearest] [--border-fill V] | --undistort k1[,k2[,p1,p2[,k3]]] [--nearest] [--border-fill V]] [--images N] [--gpus G] [--slots S] [--threads T] [--resident [--fused]]
+//                      [--ksize 3|5 | --sigma S [--sigma-y S] [--radius R] | --median K | --erode K | --dilate K | --morph-gradient K | --bilateral K [--sigma-color S] [--sigma-space S] | --conv NAME | --pyr-down | --resize WxH [--nearest | --area] | --rotate DEG [--nearest] [--border-fill V] | --perspective x0,y0,x1,y1,x2,y2,x3,y3 [--nearest] [--border-fill V] | --undistort k1[,k2[,p1,p2[,k3]]] [--nearest] [--border-fill V] | --color gray|bgr|ycbcr|from-ycbcr [--gamma G | --threshold T] | --gamma G | --threshold T] [--images N] [--gpus G] [--slots S] [--threads T] [--resident [--fused]]
 //                      [--verbose] [--csv FILE] [--save FILE]
 //                      [--frames DIR|PATTERN|FILE [--save-dir DIR] [--planar-out | --native-layout]]   (cpu | gpu)
 //
@@ -118,7 +118,9 @@ int main(int argc, char **argv)
     if (filter.warp) print_warp(filter, width, height);
     if (filter.persp) print_warp_perspective(filter, width, height);
     if (filter.remap) print_undistort(filter, width, height);
-    const size_t out_image_size = (size_t)out_width * out_height * channels;
+    int out_channels = channels;                     // --color: every output image has the transform's channel count
+    if (filter.color) print_color(filter, channels, &out_channels);
+    const size_t out_image_size = (size_t)out_width * out_height * out_channels;
     printf("Original image source: %s\n\n", img.source.c_str());
     const uint8_t *original_image = img.px.data();
 
@@ -438,7 +440,7 @@ int main(int argc, char **argv)
     printf("All batches finished!\n\n");
     if (opt.auto_ratio && mode == 0) printf("Auto ratio after %d per-batch updates: %.1f%% GPU\n\n", rebalances, gpu_ratio * 100);
     if (opt.save.size() && !first_output.empty()) {
-        save_one_image(opt.save.c_str(), first_output.data(), out_width, out_height, channels);
+        save_one_image(opt.save.c_str(), first_output.data(), out_width, out_height, out_channels);
         printf("Saved example output: %s\n\n", opt.save.c_str());
     }
 

@@ -184,6 +184,11 @@ struct Options {
     bool undistort_given = false;        // --undistort k1[,k2[,p1,p2[,k3]]] [--nearest] [--border-fill V]: undo the lens distortion of a camera with fx = fy = W
     double undistort_dist[5] = {};       //              and the principal point at the image's centre, same size (mi_blur_remap_undistort, mi_blur_ctx_set_remap;
                                          //              mode and border as --rotate; heterogeneous_blur only: no bands)
+    std::string color;                   // --color gray|bgr|ycbcr|from-ycbcr [--gamma G | --threshold T]: the colour transform (mi_blur_ctx_set_color) instead of
+    bool gamma_given = false, threshold_given = false;   //     --ksize: that preset, then the table of --gamma G (mi_blur_color_lut_gamma) or of --threshold T
+    double gamma = 1.0;                  //              (mi_blur_color_lut_threshold, 0 | 255); either table flag alone: on the identity matrix.  Outputs of the
+    int threshold = 0;                   //              preset's channel count (heterogeneous_blur only: no bands)
+    bool color_any() const { return !color.empty() || gamma_given || threshold_given; }
     bool area = false;                   // --resize WxH --area: the area resize (mi_blur_ctx_set_area: exact box average, reductions up to 64x) instead of bilinear
     bool nearest = false;                //              mi_blur_ctx_set_resize on every context, outputs of that size (heterogeneous_blur only: no bands)
     int images = 5000;                   // --images N   (NUM_IMAGES, heterogeneous_blur.c:44)
@@ -264,6 +269,20 @@ inline int parse_flags(int argc, char **argv, Options &o)
         }
         else if (a == "--nearest") o.nearest = true;
         else if (a == "--area") o.area = true;
+        else if (a == "--color") {
+            o.color = next("--color");
+            if (o.color != "gray" && o.color != "bgr" && o.color != "ycbcr" && o.color != "from-ycbcr") { printf("Error: --color gray|bgr|ycbcr|from-ycbcr\n"); exit(-1); }
+        }
+        else if (a == "--gamma") {
+            char tail = 0;
+            if (sscanf(next("--gamma"), "%lf%c", &o.gamma, &tail) != 1 || !(o.gamma > 0.0 && o.gamma <= 1e6)) { printf("Error: --gamma G, a positive number\n"); exit(-1); }
+            o.gamma_given = true;
+        }
+        else if (a == "--threshold") {
+            char tail = 0;
+            if (sscanf(next("--threshold"), "%d%c", &o.threshold, &tail) != 1 || o.threshold < -1 || o.threshold > 255) { printf("Error: --threshold T, -1..255\n"); exit(-1); }
+            o.threshold_given = true;
+        }
         else if (a == "--rotate") {
             char tail = 0;
             if (sscanf(next("--rotate"), "%lf%c", &o.rotate_deg, &tail) != 1 || !(o.rotate_deg >= -36000.0 && o.rotate_deg <= 36000.0)) { printf("Error: --rotate DEG, degrees counter-clockwise\n"); exit(-1); }
@@ -349,6 +368,9 @@ inline int parse_flags(int argc, char **argv, Options &o)
     if (o.undistort_given && (o.persp_given || o.rotate_given || o.resize_w || o.ksize_given || o.sigma > 0.0 || o.median || o.morph || o.bilateral || o.conv_preset >= 0 || o.pyr_down)) { printf("Error: --undistort excludes --perspective, --rotate, --resize, --ksize, --sigma, --median, --erode, --dilate, --morph-gradient, --bilateral, --conv and --pyr-down\n"); exit(-1); }
     if (o.undistort_given && (o.resident || !o.frames.empty())) { printf("Error: --undistort excludes --resident and --frames\n"); exit(-1); }
     if (o.border_fill >= 0 && !o.rotate_given && !o.persp_given && !o.undistort_given) { printf("Error: --border-fill needs --rotate\n"); exit(-1); }
+    if (o.color_any() && (o.undistort_given || o.persp_given || o.rotate_given || o.resize_w || o.ksize_given || o.sigma > 0.0 || o.median || o.morph || o.bilateral || o.conv_preset >= 0 || o.pyr_down)) { printf("Error: --color, --gamma and --threshold exclude --undistort, --perspective, --rotate, --resize, --ksize, --sigma, --median, --erode, --dilate, --morph-gradient, --bilateral, --conv and --pyr-down\n"); exit(-1); }
+    if (o.color_any() && (o.resident || !o.frames.empty())) { printf("Error: --color, --gamma and --threshold exclude --resident and --frames\n"); exit(-1); }
+    if (o.gamma_given && o.threshold_given) { printf("Error: --gamma excludes --threshold\n"); exit(-1); }
     if (o.area && !o.resize_w) { printf("Error: --area needs --resize\n"); exit(-1); }
     if (o.area && o.nearest) { printf("Error: --area excludes --nearest\n"); exit(-1); }
     if (o.nearest && !o.resize_w && !o.rotate_given && !o.persp_given && !o.undistort_given) { printf("Error: --nearest needs --resize\n"); exit(-1); }
@@ -386,6 +408,12 @@ struct HostFilter {
     double undistort_dist[5] = {};   // its size and map come from the image: print_undistort() fills them in
     mi_blur_remap rm{};
     std::vector<int32_t> remap_map{};
+    bool color = false;         // --color NAME [--gamma G | --threshold T], or a table flag alone: the colour transform `ck` (mi_blur_ctx_set_color);
+    std::string color_name{};   // its matrix depends on the image's channels: print_color() fills it in
+    bool gamma_given = false, threshold_given = false;
+    double gamma = 1.0;
+    int threshold = 0;
+    mi_blur_color ck{};
 };
 
 inline HostFilter filter_of(const Options &o)
@@ -422,6 +450,9 @@ inline HostFilter filter_of(const Options &o)
     f.remap = o.undistort_given;
     std::copy(o.undistort_dist, o.undistort_dist + 5, f.undistort_dist);
     f.rm.mode = f.wp.mode; f.rm.border = f.wp.border; f.rm.fill = f.wp.fill;
+    f.color = o.color_any();
+    f.color_name = o.color;
+    f.gamma_given = o.gamma_given; f.threshold_given = o.threshold_given; f.gamma = o.gamma; f.threshold = o.threshold;
     return f;
 }
 
@@ -441,6 +472,30 @@ inline void set_filter(mi_blur_ctx *ctx, const HostFilter &f)
     if (f.warp) mi_check(mi_blur_ctx_set_warp(ctx, &f.wp), "Failed to set the warp");
     if (f.persp) mi_check(mi_blur_ctx_set_warp_perspective(ctx, &f.pp), "Failed to set the perspective warp");
     if (f.remap) mi_check(mi_blur_ctx_set_remap(ctx, &f.rm, f.remap_map.data()), "Failed to set the remap");
+    if (f.color) mi_check(mi_blur_ctx_set_color(ctx, &f.ck), "Failed to set the colour transform");
+}
+
+// --color / --gamma / --threshold, once the image's channels are known: the preset for that channel count (gray and
+// ycbcr read the first three channels; bgr swaps them and keeps a fourth), or the identity under a table flag alone; the
+// table on every output channel; and the banner's "Blur kernel" line.  *co: the channels of every output image.
+inline void print_color(HostFilter &f, int channels, int *co)
+{
+    std::string name = f.color_name;
+    if (name.empty()) mi_check(mi_blur_color_identity(channels, &f.ck), "No colour transform for this channel count");
+    else {
+        if (channels < 3 || channels > MI_BLUR_COLOR_MAX_CHANNELS) { printf("Error: --color %s needs an image of 3 or 4 channels\n", name.c_str()); exit(-1); }
+        const int id = name == "gray" ? MI_BLUR_COLOR_RGB2GRAY : name == "ycbcr" ? MI_BLUR_COLOR_RGB2YCBCR : name == "from-ycbcr" ? MI_BLUR_COLOR_YCBCR2RGB
+                       : channels == 4 ? MI_BLUR_COLOR_RGBA2BGRA : MI_BLUR_COLOR_RGB2BGR;
+        mi_check(mi_blur_color_preset(id, &f.ck), "No such colour preset");
+    }
+    if (f.gamma_given || f.threshold_given) {
+        mi_check(f.gamma_given ? mi_blur_color_lut_gamma(f.gamma, f.ck.lut[0]) : mi_blur_color_lut_threshold(f.threshold, 0, 255, f.ck.lut[0]), "No such table");
+        for (int o = 1; o < f.ck.out_channels; o++) std::copy(f.ck.lut[0], f.ck.lut[0] + 256, f.ck.lut[o]);
+        f.ck.lut_on = 1;
+        name += std::string(name.empty() ? "" : "+") + (f.gamma_given ? "gamma" : "threshold");
+    }
+    *co = f.ck.out_channels;
+    printf("Blur kernel: colour transform %s, %d -> %d channels\n", name.c_str(), channels, *co);
 }
 
 // --undistort, once the image size is known: the undistortion map of a camera with fx = fy = W and the principal point at
@@ -501,7 +556,7 @@ inline int filter_halo(const HostFilter &f) { return f.conv_preset >= 0 ? f.conv
 // The banner's "Blur kernel" line (with the taps of a Gaussian).
 inline void print_filter(const HostFilter &f)
 {
-    if (f.pyr_down || f.resize || f.warp || f.persp || f.remap) return;     // print_pyr_down() / print_resize() / print_warp() / print_warp_perspective() / print_undistort(), once the image size is known
+    if (f.pyr_down || f.resize || f.warp || f.persp || f.remap || f.color) return;     // print_pyr_down() / print_resize() / print_warp() / print_warp_perspective() / print_undistort() / print_color(), once the image is known
     if (f.median) { printf("Blur kernel: %dx%d median\n", f.median, f.median); return; }
     if (f.conv_preset >= 0) { printf("Blur kernel: %dx%d convolution (%s)\n", 2 * f.conv.rx + 1, 2 * f.conv.ry + 1, f.conv_name.c_str()); return; }
     if (f.bilateral) { printf("Blur kernel: %dx%d bilateral (sigma_color %g, sigma_space %g)\n", f.bilateral, f.bilateral, f.sigma_color, f.sigma_space); return; }

@@ -46,6 +46,7 @@ int main(int argc, char **argv)
     if (opt.rotate_given) { printf("Error: --rotate: bands are not supported (this host cuts every image into bands; use heterogeneous_blur)\n"); return -1; }
     if (opt.persp_given) { printf("Error: --perspective: bands are not supported (this host cuts every image into bands; use heterogeneous_blur)\n"); return -1; }
     if (opt.undistort_given) { printf("Error: --undistort: bands are not supported (this host cuts every image into bands; use heterogeneous_blur)\n"); return -1; }
+    if (opt.color_any()) { printf("Error: --color: bands are not supported (this host cuts every image into bands; use heterogeneous_blur)\n"); return -1; }
     if (opt.resize_w) { printf("Error: --resize: bands are not supported (this host cuts every image into bands; use heterogeneous_blur)\n"); return -1; }
     if (opt.resident) return run_resident(opt);
     const int NUM_IMAGES = opt.images;

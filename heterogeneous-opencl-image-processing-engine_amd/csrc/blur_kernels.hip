@@ -1646,6 +1646,7 @@ int launch(const LaunchDesc &d)
     case FilterKind::WARP_PERSP: return launch_warp_persp(d);
     case FilterKind::REMAP: return launch_remap(d);
     case FilterKind::AREA: return launch_area(d);
+    case FilterKind::COLOR: return launch_color(d);
     }
     return MI_BLUR_ERR_INVALID;
 }

@@ -60,6 +60,9 @@ int launch_warp_persp(const LaunchDesc &d);
 int launch_remap(const LaunchDesc &d);
 // The area resize (FilterKind::AREA, area_kernels.hip).  The contract of launch_resize.
 int launch_area(const LaunchDesc &d);
+// The colour transform (FilterKind::COLOR, color_kernels.hip).  The contract of launch_resize; out_stride is measured
+// against the image with the OUTPUT's channel count.
+int launch_color(const LaunchDesc &d);
 // Sets what last_kernel() reports for the calling thread.
 void set_last_kernel(const char *name);
 

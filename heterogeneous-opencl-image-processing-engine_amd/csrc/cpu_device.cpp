@@ -442,6 +442,19 @@ void cpu_area_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, const F
     }
 }
 
+// Rows [Y_begin, Y_end) of the colour transform f.color on one image of W pixels x C channels per row; out = the
+// transformed image (dense, f.color.co channels).  Every byte through color_channel() (filter.h), the function of the
+// GPU's generic kernel.
+void cpu_color_rows(const uint8_t *in, uint8_t *out, int W, int C, const Filter &f, int Y_begin, int Y_end)
+{
+    const ColorSpec &k = f.color;
+    const int co = k.co;
+    const uint8_t *px = in + (size_t)Y_begin * W * C;
+    uint8_t *o = out + (size_t)Y_begin * W * co;
+    for (size_t n = (size_t)(Y_end - Y_begin) * W; n > 0; n--, px += C, o += co)
+        for (int c = 0; c < co; c++) o[c] = color_channel(k, C, px, c);
+}
+
 // Output rows [Y_begin, Y_end) of the affine warp of f (f.warp_*) on one W x H image; out = the warped image (dense).
 // Every byte through warp_coord() and warp_sample() (filter.h), the functions of the GPU's generic kernel.
 void cpu_warp_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, const Filter &f, int Y_begin, int Y_end)
@@ -527,9 +540,9 @@ void cpu_blur_batch(const uint8_t *in, uint8_t *out, int W, int band_rows, int C
     if (n_images <= 0) return;
     if (n_threads <= 0) n_threads = hardware_threads();
     if (in_stride == 0) in_stride = (size_t)W * C * band_rows;
-    const OutShape o = out_shape(f, W, band_rows, y0, y1);
+    const OutShape o = out_shape(f, W, band_rows, C, y0, y1);
     if (whole_image_only(f)) { y0 = 0; y1 = o.rows; }           // from here on: output rows
-    if (out_stride == 0) out_stride = (size_t)o.width * C * o.rows;
+    if (out_stride == 0) out_stride = (size_t)o.width * o.channels * o.rows;
     const std::vector<ResizeCoord> xtab = resize_xtable(W, f);
     const std::vector<AreaAxis> area_x = area_xtable(W, f), area_y = area_ytable(band_rows, f);
     const int rows = y1 - y0;
@@ -563,6 +576,7 @@ void cpu_blur_batch(const uint8_t *in, uint8_t *out, int W, int band_rows, int C
             case FilterKind::WARP_PERSP: cpu_warp_persp_rows(src, dst, W, band_rows, C, f, ys, ye); break;
             case FilterKind::REMAP: cpu_remap_rows(src, dst, W, band_rows, C, f, ys, ye); break;
             case FilterKind::AREA: cpu_area_rows(src, dst, W, band_rows, C, f, ys, ye, area_x.data(), area_y.data()); break;
+            case FilterKind::COLOR: cpu_color_rows(src, dst, W, C, f, ys, ye); break;
             }
         }
     };

@@ -36,6 +36,8 @@ std::vector<ResizeCoord> resize_xtable(int W, const Filter &f);
 void cpu_area_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, const Filter &f, int Y_begin, int Y_end, const AreaAxis *xtab, const AreaAxis *ytab);
 std::vector<AreaAxis> area_xtable(int W, const Filter &f);
 std::vector<AreaAxis> area_ytable(int H, const Filter &f);
+// Rows [Y_begin, Y_end) of the colour transform f.color: the output has f.color.co channels.
+void cpu_color_rows(const uint8_t *in, uint8_t *out, int W, int C, const Filter &f, int Y_begin, int Y_end);
 // Output rows [Y_begin, Y_end) of the affine warp of f (f.warp_*).
 void cpu_warp_rows(const uint8_t *in, uint8_t *out, int W, int H, int C, const Filter &f, int Y_begin, int Y_end);
 // Output rows [Y_begin, Y_end) of the perspective warp of f (f.warp_h).

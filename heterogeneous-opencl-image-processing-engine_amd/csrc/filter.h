@@ -20,7 +20,7 @@ struct SepTaps {
     unsigned wx[2 * SEP_MAX_R + 1], wy[2 * SEP_MAX_R + 1];
 };
 
-enum class FilterKind { BOX, SEP, MEDIAN, MORPH, BILATERAL, CONV, SEP_DOWN, RESIZE, WARP, WARP_PERSP, REMAP, AREA };
+enum class FilterKind { BOX, SEP, MEDIAN, MORPH, BILATERAL, CONV, SEP_DOWN, RESIZE, WARP, WARP_PERSP, REMAP, AREA, COLOR };
 
 // BOX: the fixed 3x3 / 5x5 kernel of `radius` 1|2.  SEP: the separable kernel `taps`.  MEDIAN: the median of `radius` 1..7.
 // MORPH: the window minimum / maximum / their difference (`morph_op`) over (2 morph_rx + 1) x (2 morph_ry + 1).
@@ -42,6 +42,14 @@ enum class FilterKind { BOX, SEP, MEDIAN, MORPH, BILATERAL, CONV, SEP_DOWN, RESI
 // device memory for a launch, host memory for the CPU device; whoever builds the Filter keeps it alive.
 // AREA: the area resize (mi_blur_area) to out_w x out_h: every output pixel is the box average of the input pixels its
 // footprint covers, partly covered ones by their share (area_axis() below), one rounding.  No mode, no border.
+// COLOR: the colour transform (mi_blur_color) `color`: pointwise, every output pixel a channel matrix of the input pixel
+// at the same place, optionally through a table (color_channel() below).  The image keeps its size; its channel count
+// becomes color.co: the one filter whose output has another channel count than its input (out_shape()).
+struct ColorSpec {
+    int co = 0, shift = 0, lut_on = 0;      // validated: co 1..4, shift 0..16, lut_on 0 | 1
+    int32_t m[4][4] = {}, bias[4] = {};     // rows >= co are zero
+    uint8_t lut[4][256] = {};               // zero unless lut_on
+};
 struct Filter {
     FilterKind kind;
     int radius;             // BOX and MEDIAN
@@ -59,6 +67,7 @@ struct Filter {
     int64_t warp_h[9] = {};                                   // WARP_PERSP: the OUTPUT -> INPUT homography, row-major 3 x 3, free scale; out_w .. warp_fill as WARP
     const int32_t *remap_map = nullptr;                       // REMAP: int32[out_h][out_w][2] = (px, py), MI_BLUR_REMAP_FRAC fraction bits; out_w .. warp_fill as WARP
     int remap_stage_bytes = 0;                                // REMAP: the largest tile footprint the tiled kernel stages in LDS (16..REMAP_STAGE_MAX; the constructor resolves 0)
+    ColorSpec color = {};                                     // COLOR; last, for the same reason
 };
 
 #if defined(__HIP__)
@@ -384,6 +393,58 @@ inline bool area_ok(int out_w, int out_h, int W, int H, int C)
 }
 inline bool area_ok(const mi_blur_area *r, int W, int H, int C) { return r && area_ok(r->out_width, r->out_height, W, H, C); }
 
+// ---- the colour transform (include/mi_blur.h, "Colour transform").  The GPU's generic kernel and the CPU device take
+// every byte from color_channel(); the tiled kernel does the same sum with its channel counts as template arguments and
+// ends in the same color_clamp().
+// v = clamp(acc >> shift, 0, 255); the shift is arithmetic, so it floors.
+// On the device the empty asm keeps the shift and the clamp apart, as conv_pack() (conv_kernels.hip) does and for its
+// reason: left together, hipcc fuses the shift-and-clamp of two neighbouring bytes into v_ashr_pk_u8_i32 and ORs the
+// other two bytes of the dword onto its result as if the upper half of that register were zero, which on the MI355X it
+// is not: bytes 2 and 3 of every output dword of blur_color_tiled_kernel came out ORed with stale bits.
+MI_BLUR_HD inline int color_clamp(int32_t acc, int shift)
+{
+    int32_t v = acc >> shift;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(v));
+#endif
+    return v < 0 ? 0 : v > 255 ? 255 : v;
+}
+// One output channel of the input pixel px[0 .. C - 1], C <= 4: m = the channel's row of weights, lut = its table or null.
+// |acc| < 2^27 for a valid transform: 32 bits are exact.
+MI_BLUR_HD inline uint8_t color_channel(const int32_t *m, int32_t bias, int shift, const uint8_t *lut, int C, const uint8_t *px)
+{
+    int32_t acc = bias;
+    for (int i = 0; i < C; i++) acc += m[i] * (int32_t)px[i];
+    const int v = color_clamp(acc, shift);
+    return lut ? lut[v] : (uint8_t)v;
+}
+inline uint8_t color_channel(const ColorSpec &k, int C, const uint8_t *px, int o)
+{
+    return color_channel(k.m[o], k.bias[o], k.shift, k.lut_on ? k.lut[o] : nullptr, C, px);
+}
+// A colour transform that is valid whatever the image: the fields' ranges, and per used row sum |m| <= 2^18 over all
+// four columns (C is not known yet) and |bias| <= 2^26.  Rows >= out_channels are not read.
+constexpr int64_t COLOR_ROW_MAX = (int64_t)1 << 18, COLOR_BIAS_MAX = (int64_t)1 << 26;
+inline bool color_ok(const mi_blur_color *k)
+{
+    if (!k || k->out_channels < 1 || k->out_channels > MI_BLUR_COLOR_MAX_CHANNELS || k->shift < 0 || k->shift > 16 ||
+        (k->lut_on != 0 && k->lut_on != 1))
+        return false;
+    for (int o = 0; o < k->out_channels; o++) {
+        int64_t sum = 0;
+        for (int i = 0; i < MI_BLUR_COLOR_MAX_CHANNELS; i++) sum += k->m[o][i] < 0 ? -(int64_t)k->m[o][i] : (int64_t)k->m[o][i];
+        if (sum > COLOR_ROW_MAX || k->bias[o] > COLOR_BIAS_MAX || k->bias[o] < -COLOR_BIAS_MAX) return false;
+    }
+    return true;
+}
+// ... and for a W x H image of C channels: 1..4 channels in, and the per-image byte limits of resize_ok() on the input
+// (with C) and on the output (with co).
+inline bool color_image_ok(int co, int W, int H, int C)
+{
+    return C >= 1 && C <= MI_BLUR_COLOR_MAX_CHANNELS && resize_ok(W, H, MI_BLUR_RESIZE_BILINEAR, W, H, C) &&
+           resize_ok(W, H, MI_BLUR_RESIZE_BILINEAR, W, H, co);
+}
+
 // Output size of a decimation of a W x H image: kept columns / rows (> 0 for a valid decimation, down_ok()).
 inline int down_cols(int W, int sx, int ox) { return (W - ox + sx - 1) / sx; }
 inline int down_rows(int H, int sy, int oy) { return (H - oy + sy - 1) / sy; }
@@ -395,21 +456,24 @@ inline bool down_ok(const mi_blur_decimation *d, int W, int H)
 }
 
 // The output geometry of a filter, for everything above the kernels (launch checks, slot sizes, counters, the CPU device).
-// whole_image_only: the output image is not the input's size, so the filter takes whole images only: no bands, no halo
-// rows, no planar or resident forms (a band's phase or source rows would depend on where it starts).
+// whole_image_only: the output image is not the input's size or channel count, so the filter takes whole images only: no
+// bands, no halo rows, no planar or resident forms (a band's phase or source rows would depend on where it starts, and a
+// band of another channel count has no place in those forms).
 inline bool whole_image_only(const Filter &f)
 {
     return f.kind == FilterKind::SEP_DOWN || f.kind == FilterKind::RESIZE || f.kind == FilterKind::WARP || f.kind == FilterKind::WARP_PERSP ||
-           f.kind == FilterKind::REMAP || f.kind == FilterKind::AREA;
+           f.kind == FilterKind::REMAP || f.kind == FilterKind::AREA || f.kind == FilterKind::COLOR;
 }
-// Width and rows of the output block of one band of band_rows rows x W of which rows [y0, y1) are asked for: those rows
-// at the input's width, or the filter's own output image (of the whole band) for a whole_image_only filter.
-struct OutShape { int width, rows; };
-inline OutShape out_shape(const Filter &f, int W, int band_rows, int y0, int y1)
+// Width, rows and channels of the output block of one band of band_rows rows x W x C of which rows [y0, y1) are asked
+// for: those rows at the input's width, or the filter's own output image (of the whole band) for a whole_image_only
+// filter.  The channels are the input's for every filter but COLOR, whose output has its own count.
+struct OutShape { int width, rows, channels; };
+inline OutShape out_shape(const Filter &f, int W, int band_rows, int C, int y0, int y1)
 {
-    if (f.kind == FilterKind::SEP_DOWN) return {down_cols(W, f.down_sx, f.down_ox), down_rows(band_rows, f.down_sy, f.down_oy)};
-    if (f.kind == FilterKind::RESIZE || f.kind == FilterKind::WARP || f.kind == FilterKind::WARP_PERSP || f.kind == FilterKind::REMAP || f.kind == FilterKind::AREA) return {f.out_w, f.out_h};
-    return {W, y1 - y0};
+    if (f.kind == FilterKind::SEP_DOWN) return {down_cols(W, f.down_sx, f.down_ox), down_rows(band_rows, f.down_sy, f.down_oy), C};
+    if (f.kind == FilterKind::RESIZE || f.kind == FilterKind::WARP || f.kind == FilterKind::WARP_PERSP || f.kind == FilterKind::REMAP || f.kind == FilterKind::AREA) return {f.out_w, f.out_h, C};
+    if (f.kind == FilterKind::COLOR) return {W, band_rows, f.color.co};
+    return {W, y1 - y0, C};
 }
 
 // The constructors validate: MI_BLUR_OK, or MI_BLUR_ERR_INVALID with *f untouched.
@@ -493,6 +557,22 @@ inline int filter_area(const mi_blur_area *r, Filter *f)
     if (!f || !area_ok(r, 1, 1, 1)) return MI_BLUR_ERR_INVALID;
     *f = Filter{FilterKind::AREA, 0, {}};
     f->out_w = r->out_width; f->out_h = r->out_height;
+    return MI_BLUR_OK;
+}
+
+// *k, copied: rows beyond out_channels as zeros, the tables only when lut_on (what the image must satisfy is checked
+// where it is known: color_image_ok()).
+inline int filter_color(const mi_blur_color *k, Filter *f)
+{
+    if (!f || !color_ok(k)) return MI_BLUR_ERR_INVALID;
+    *f = Filter{FilterKind::COLOR, 0, {}};
+    ColorSpec &c = f->color;
+    c.co = k->out_channels; c.shift = k->shift; c.lut_on = k->lut_on;
+    for (int o = 0; o < c.co; o++) {
+        for (int i = 0; i < 4; i++) c.m[o][i] = k->m[o][i];
+        c.bias[o] = k->bias[o];
+        if (c.lut_on) for (int v = 0; v < 256; v++) c.lut[o][v] = k->lut[o][v];
+    }
     return MI_BLUR_OK;
 }
 
@@ -799,5 +879,13 @@ inline AreaTiles area_tiles(int W, int Wo, int Ho, int C)
 inline bool area_tiles_fit(const AreaTiles &t) { return t.max_nsc <= AREA_MAX_SPAN; }
 inline int area_xtab_bytes(const AreaTiles &t) { return t.g.ncols * 16 * 8; }
 inline size_t area_lds_bytes(const AreaTiles &t) { return (size_t)area_xtab_bytes(t) + (size_t)(AREA_THREADS / t.span) * (size_t)area_v_row(t.max_nsc) * 4u; }
+
+// ---- blur_color_tiled_kernel.  A pointwise filter on dense images does not care about rows: per image it works on the
+// flat run of W * H pixels.  A group is 16 pixels: exactly C input chunks and co output chunks of 16 bytes.  One thread
+// owns one group, one workgroup a run of COLOR_RUN consecutive groups of one image (the last run of an image may be short).
+constexpr int COLOR_GROUP = 16;                     // pixels per group
+constexpr int COLOR_RUN = 256;                      // groups per workgroup = its threads
+inline bool color_flat_ok(int W, int H) { return (long long)W * H % COLOR_GROUP == 0; }
+inline int color_runs(int W, int H) { return (int)(((long long)W * H / COLOR_GROUP + COLOR_RUN - 1) / COLOR_RUN); }
 
 }  // namespace mi_blur

@@ -248,8 +248,8 @@ static inline int check_desc(const LaunchDesc &d, FilterKind kind)
 static inline long long dense_in(const LaunchDesc &d) { return (long long)d.band_rows * d.width * d.channels; }
 static inline long long dense_out(const LaunchDesc &d)
 {
-    const OutShape o = out_shape(*d.filter, d.width, d.band_rows, d.y0, d.y1);
-    return (long long)o.rows * o.width * d.channels;
+    const OutShape o = out_shape(*d.filter, d.width, d.band_rows, d.channels, d.y0, d.y1);
+    return (long long)o.rows * o.width * o.channels;
 }
 static inline bool strides_too_small(const LaunchDesc &d)
 {
@@ -280,7 +280,11 @@ static inline bool tile_aligned(const LaunchDesc &d)
 }
 
 // Bytes of one output row: the input's, or the output image's of a whole_image_only filter (out_shape(), filter.h).
-static inline int out_pitch(const LaunchDesc &d) { return out_shape(*d.filter, d.width, d.band_rows, d.y0, d.y1).width * d.channels; }
+static inline int out_pitch(const LaunchDesc &d)
+{
+    const OutShape o = out_shape(*d.filter, d.width, d.band_rows, d.channels, d.y0, d.y1);
+    return o.width * o.channels;
+}
 
 // The members most kernels' parameter structs have under the same names (a template, not a base struct: the structs'
 // names and layouts are the kernels' mangled names and kernarg layouts).  Stride 0 = laid end to end.  A struct with

@@ -96,7 +96,7 @@ enum class PreCheck {
     FILTER,     // sep: the constructor's status
     ARGS,       // median, morph, bilateral, conv: + pointers, dimensions, image count
     ARGS_ROWS,  // conv_band: + the row range
-    ARGS_SIZE,  // sep_down, resize, warp, warp_perspective, remap, area: + the image within INT_MAX bytes
+    ARGS_SIZE,  // sep_down, resize, warp, warp_perspective, remap, area, color: + the image within INT_MAX bytes
 };
 
 // Every mi_blur_enqueue* export: one launch of f on device memory.  built: the status of f's constructor.
@@ -134,6 +134,11 @@ static int area_for(const mi_blur_area *r, int W, int H, int C, Filter *f)
 {
     const int rc = filter_area(r, f);
     return rc ? rc : area_ok(r, W, H, C) ? MI_BLUR_OK : MI_BLUR_ERR_INVALID;
+}
+static int color_for(const mi_blur_color *k, int W, int H, int C, Filter *f)
+{
+    const int rc = filter_color(k, f);
+    return rc ? rc : color_image_ok(k->out_channels, W, H, C) ? MI_BLUR_OK : MI_BLUR_ERR_INVALID;
 }
 
 static int warp_for(const mi_blur_warp *w, int W, int H, int C, Filter *f)
@@ -301,6 +306,85 @@ extern "C" int mi_blur_enqueue_area(const uint8_t *d_in, uint8_t *d_out, int wid
 {
     Filter f;
     return enqueue_filter(area_for(r, width, height, channels, &f), f, PreCheck::ARGS_SIZE, d_in, d_out, width, height,
+                          channels, n_images, 0, height, MI_BLUR_VARIANT_AUTO, stream);
+}
+
+// ----------------------------------------------------------------------------------
+// colour transform: exact channel matrix + table, 1-4 channels in and out (no reference analogue)
+// ----------------------------------------------------------------------------------
+namespace {
+// q(x) = floor(x * 65536 + 0.5) of the JFIF constants (include/mi_blur.h, the table of presets).
+constexpr int32_t CQ = 65536, CR = 32768;
+constexpr int32_t LUMA[3] = {19595, 38470, 7471};
+
+void color_rows(mi_blur_color *k, int co, int shift) { *k = mi_blur_color{}; k->out_channels = co; k->shift = shift; }
+void color_permute(mi_blur_color *k, int co, const int *src)
+{
+    color_rows(k, co, 0);
+    for (int o = 0; o < co; o++) if (src[o] >= 0) k->m[o][src[o]] = 1;
+}
+}  // namespace
+
+extern "C" int mi_blur_color_preset(int preset, mi_blur_color *k)
+{
+    if (!k) return MI_BLUR_ERR_INVALID;
+    switch (preset) {
+    case MI_BLUR_COLOR_RGB2GRAY:
+    case MI_BLUR_COLOR_BGR2GRAY:
+        color_rows(k, 1, 16);
+        for (int i = 0; i < 3; i++) k->m[0][i] = LUMA[preset == MI_BLUR_COLOR_RGB2GRAY ? i : 2 - i];
+        k->bias[0] = CR;
+        return MI_BLUR_OK;
+    case MI_BLUR_COLOR_GRAY2RGB: { const int s[3] = {0, 0, 0}; color_permute(k, 3, s); return MI_BLUR_OK; }
+    case MI_BLUR_COLOR_RGB2BGR: { const int s[3] = {2, 1, 0}; color_permute(k, 3, s); return MI_BLUR_OK; }
+    case MI_BLUR_COLOR_RGBA2BGRA: { const int s[4] = {2, 1, 0, 3}; color_permute(k, 4, s); return MI_BLUR_OK; }
+    case MI_BLUR_COLOR_RGBA2RGB: { const int s[3] = {0, 1, 2}; color_permute(k, 3, s); return MI_BLUR_OK; }
+    case MI_BLUR_COLOR_RGB2RGBA: { const int s[4] = {0, 1, 2, -1}; color_permute(k, 4, s); k->bias[3] = 255; return MI_BLUR_OK; }
+    case MI_BLUR_COLOR_RGB2YCBCR: {
+        color_rows(k, 3, 16);
+        const int32_t cb[3] = {-11058, -21710, 32768}, cr[3] = {32768, -27439, -5329};
+        for (int i = 0; i < 3; i++) { k->m[0][i] = LUMA[i]; k->m[1][i] = cb[i]; k->m[2][i] = cr[i]; }
+        k->bias[0] = CR; k->bias[1] = k->bias[2] = 128 * CQ + CR;
+        return MI_BLUR_OK;
+    }
+    case MI_BLUR_COLOR_YCBCR2RGB: {
+        color_rows(k, 3, 16);
+        const int32_t r[3] = {CQ, 0, 91881}, g[3] = {CQ, -22553, -46802}, b[3] = {CQ, 116130, 0};
+        for (int i = 0; i < 3; i++) { k->m[0][i] = r[i]; k->m[1][i] = g[i]; k->m[2][i] = b[i]; }
+        k->bias[0] = CR - 128 * 91881; k->bias[1] = CR + 128 * (22553 + 46802); k->bias[2] = CR - 128 * 116130;
+        return MI_BLUR_OK;
+    }
+    }
+    return MI_BLUR_ERR_INVALID;
+}
+
+extern "C" int mi_blur_color_identity(int channels, mi_blur_color *k)
+{
+    if (!k || channels < 1 || channels > MI_BLUR_COLOR_MAX_CHANNELS) return MI_BLUR_ERR_INVALID;
+    const int s[4] = {0, 1, 2, 3};
+    color_permute(k, channels, s);
+    return MI_BLUR_OK;
+}
+
+extern "C" int mi_blur_color_lut_gamma(double gamma, uint8_t lut[256])
+{
+    if (!lut || !std::isfinite(gamma) || !(gamma > 0.0)) return MI_BLUR_ERR_INVALID;
+    for (int v = 0; v < 256; v++) lut[v] = (uint8_t)std::floor(255.0 * std::pow((double)v / 255.0, gamma) + 0.5);
+    return MI_BLUR_OK;
+}
+
+extern "C" int mi_blur_color_lut_threshold(int t, int lo, int hi, uint8_t lut[256])
+{
+    if (!lut || t < -1 || t > 255 || lo < 0 || lo > 255 || hi < 0 || hi > 255) return MI_BLUR_ERR_INVALID;
+    for (int v = 0; v < 256; v++) lut[v] = (uint8_t)(v > t ? hi : lo);
+    return MI_BLUR_OK;
+}
+
+extern "C" int mi_blur_enqueue_color(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int n_images,
+                                     const mi_blur_color *k, void *stream)
+{
+    Filter f;
+    return enqueue_filter(color_for(k, width, height, channels, &f), f, PreCheck::ARGS_SIZE, d_in, d_out, width, height,
                           channels, n_images, 0, height, MI_BLUR_VARIANT_AUTO, stream);
 }
 
@@ -1051,10 +1135,10 @@ extern "C" int mi_blur_create(mi_blur_ctx **out_ctx, int device, int width, int 
 // Bytes of the output block of one band of the context's filter (out_shape(), filter.h).
 static size_t out_band_bytes(const mi_blur_ctx *c, int band_rows, int y0, int y1)
 {
-    const OutShape o = out_shape(c->filter, c->W, band_rows, y0, y1);
-    return (size_t)o.width * c->C * (size_t)o.rows;
+    const OutShape o = out_shape(c->filter, c->W, band_rows, c->C, y0, y1);
+    return (size_t)o.width * (size_t)o.channels * (size_t)o.rows;
 }
-// Bytes of a slot's output buffers per image: a resize may write more than it reads.  The filter is known by the time a
+// Bytes of a slot's output buffers per image: a resize, or a colour transform to more channels, may write more than it reads.  The filter is known by the time a
 // slot's buffers are made (setters work only before the first submit); every other context: image_bytes, as before.
 static size_t slot_out_image_bytes(const mi_blur_ctx *c) { return std::max(c->image_bytes, out_band_bytes(c, c->H, 0, c->H)); }
 
@@ -1636,7 +1720,7 @@ extern "C" int mi_blur_submit_planar(mi_blur_ctx *c, const uint8_t *host_planar_
 
 // Every mi_blur_ctx_set_*: the filter that build(&f) makes in place of the context's, for every submit from now on (before the
 // first one only; the whole_image_only ones for mi_blur_submit only).  null_arg: a required pointer argument is null,
-// which set_kernel, set_sep_down, set_resize, set_area, set_warp and set_warp_perspective answer before they look at the state; the other setters leave a null
+// which set_kernel, set_sep_down, set_resize, set_area, set_color, set_warp and set_warp_perspective answer before they look at the state; the other setters leave a null
 // table to the constructor, behind the state.
 template <typename B>
 static int ctx_set_filter(mi_blur_ctx *c, bool null_arg, B &&build)
@@ -1668,6 +1752,11 @@ extern "C" int mi_blur_ctx_set_resize(mi_blur_ctx *c, const mi_blur_resize *r)
 extern "C" int mi_blur_ctx_set_area(mi_blur_ctx *c, const mi_blur_area *r)
 {
     return ctx_set_filter(c, !r, [&](Filter *f) { return area_for(r, c->W, c->H, c->C, f); });
+}
+
+extern "C" int mi_blur_ctx_set_color(mi_blur_ctx *c, const mi_blur_color *k)
+{
+    return ctx_set_filter(c, !k, [&](Filter *f) { return color_for(k, c->W, c->H, c->C, f); });
 }
 
 extern "C" int mi_blur_ctx_set_warp(mi_blur_ctx *c, const mi_blur_warp *w)
@@ -2175,6 +2264,13 @@ extern "C" int mi_blur_cpu_run_area(const uint8_t *in, uint8_t *out, int width, 
 {
     Filter f;
     return cpu_run_filter(area_for(r, width, height, channels, &f), f, in, out, width, height, channels, n_images, n_threads);
+}
+
+extern "C" int mi_blur_cpu_run_color(const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,
+                                     const mi_blur_color *k, int n_threads)
+{
+    Filter f;
+    return cpu_run_filter(color_for(k, width, height, channels, &f), f, in, out, width, height, channels, n_images, n_threads);
 }
 
 extern "C" int mi_blur_cpu_run_warp(const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,

@@ -71,7 +71,8 @@ int mi_blur_version(void);
  * "blur_conv_generic_kernel", "blur_sep_down_tiled_kernel", "blur_sep_down_generic_kernel",
  * "blur_resize_tiled_kernel", "blur_resize_generic_kernel", "blur_warp_tiled_kernel", "blur_warp_generic_kernel",
  * "blur_warp_persp_tiled_kernel", "blur_warp_persp_generic_kernel", "blur_remap_tiled_kernel",
- * "blur_remap_generic_kernel", "blur_area_tiled_kernel", "blur_area_generic_kernel"; "" before the first):
+ * "blur_remap_generic_kernel", "blur_area_tiled_kernel", "blur_area_generic_kernel", "blur_color_tiled_kernel",
+ * "blur_color_generic_kernel"; "" before the first):
  * reports name the kernel a profiler will show.  Static string, never NULL. */
 const char *mi_blur_last_kernel(void);
 
@@ -585,6 +586,97 @@ int mi_blur_cpu_run_area(const uint8_t *in, uint8_t *out, int width, int height,
  * both sides (in place, one launch per submit, never the batch server), on the GPU or the CPU device.
  * mi_blur_submit_band, _bands, _planar and both resident runs return MI_BLUR_ERR_UNSUPPORTED for such a context. */
 int mi_blur_ctx_set_area(mi_blur_ctx *ctx, const mi_blur_area *r);
+
+/* ------------------------------------------------------------------------
+ * Colour transform: an exact channel matrix and an optional lookup table, 1-4 channels in, 1-4 channels out (no reference
+ * analogue): grey conversion, BGR <-> RGB, YCbCr, dropping or adding alpha, and gamma, threshold, invert or levels
+ * through a table.  The one filter that mixes channels, and the one whose output has another channel count than its
+ * input.  The definition is exact integers; the GPU, the CPU device and a numpy restatement agree byte for byte.
+ * Pointwise: an output pixel depends on the input pixel at the same (x, y) only.
+ *
+ * For an input pixel in[0..C-1] and each o < Co = out_channels:
+ *   acc    = bias[o] + sum_{i < C} m[o][i] * in[i]          (int32)
+ *   v      = clamp(acc >> shift, 0, 255)                    (arithmetic shift: floors)
+ *   out[o] = lut_on ? lut[o][v] : v
+ *
+ * Valid: 1 <= out_channels <= 4; 0 <= shift <= 16; lut_on 0 or 1; for every row o < out_channels
+ * sum_{i<4} |m[o][i]| <= 2^18 and |bias[o]| <= 2^26.  Then |acc| < 255 * 2^18 + 2^26 < 2^27: every weight fits a signed
+ * 24-bit operand and 32-bit sums are exact.  Rows >= out_channels are not read.  Columns >= C are not used by the
+ * arithmetic but count in the row sum: the struct is validated before C is known.  The input has 1..4 channels (C > 4 is
+ * MI_BLUR_ERR_INVALID, checked where C is known), and the image obeys the resize's per-image byte limits, on the input
+ * with C and on the output with Co.
+ * The output is interleaved and dense: its pitch is W*Co and images lie W*H*Co bytes apart.  The image size does not change.
+ *
+ * Presets (mi_blur_color_preset), with Q = 65536, R = 32768 and q(x) = floor(x * 65536 + 0.5) of the JFIF constants
+ * 0.299, 0.587, 0.114, 0.168736, 0.331264, 0.5, 0.418688, 0.081312, 1.402, 0.344136, 0.714136, 1.772; lut_on = 0:
+ *   RGB2GRAY   Co 1, shift 16: {19595, 38470, 7471}; bias R        (BT.601 luma; the weights sum to Q)
+ *   BGR2GRAY   Co 1, shift 16: {7471, 38470, 19595}; bias R
+ *   GRAY2RGB   Co 3, shift 0:  every row {1}
+ *   RGB2BGR    Co 3, shift 0:  the permutation 2, 1, 0
+ *   RGBA2BGRA  Co 4, shift 0:  the permutation 2, 1, 0, 3
+ *   RGBA2RGB   Co 3, shift 0:  the identity on 0..2
+ *   RGB2RGBA   Co 4, shift 0:  the identity on 0..2; row 3 all zero, bias 255
+ *   RGB2YCBCR  Co 3, shift 16 (JFIF, full range): Y {19595, 38470, 7471}; R   Cb {-11058, -21710, 32768}; 128 Q + R
+ *              Cr {32768, -27439, -5329}; 128 Q + R
+ *   YCBCR2RGB  Co 3, shift 16: R {Q, 0, 91881}; R - 128 * 91881   G {Q, -22553, -46802}; R + 128 * (22553 + 46802)
+ *              B {Q, 116130, 0}; R - 128 * 116130
+ * The presets do not fix C: RGB2GRAY on a 4-channel image ignores alpha (column 3 is 0).
+ * Properties (checked over all 2^24 colours): grey (v, v, v) gives v under RGB2GRAY and (v, 128, 128) under RGB2YCBCR,
+ * and YCBCR2RGB of that gives (v, v, v) back, for every v; the Y of RGB2YCBCR equals RGB2GRAY; the clamp is live in the
+ * forward direction (pure blue gives Cb = 256 before it); YCBCR2RGB(RGB2YCBCR(p)) differs from p by at most 1 in every
+ * channel.
+ * This is NOT claimed to be OpenCV's cvtColor bit for bit: OpenCV's fixed-point widths differ between versions.
+ * ---------------------------------------------------------------------- */
+#define MI_BLUR_COLOR_MAX_CHANNELS 4
+typedef struct mi_blur_color {
+    int out_channels;            /* Co in 1..4 */
+    int shift;                   /* 0..16 */
+    int32_t m[4][4];             /* m[o][i]: weight of input channel i in output channel o */
+    int32_t bias[4];             /* added before the shift */
+    int lut_on;                  /* 0 | 1 */
+    uint8_t lut[4][256];         /* lut[o][v], read only when lut_on */
+} mi_blur_color;
+typedef enum mi_blur_color_preset_id {
+    MI_BLUR_COLOR_RGB2GRAY = 0, MI_BLUR_COLOR_BGR2GRAY = 1, MI_BLUR_COLOR_GRAY2RGB = 2, MI_BLUR_COLOR_RGB2BGR = 3,
+    MI_BLUR_COLOR_RGBA2BGRA = 4, MI_BLUR_COLOR_RGBA2RGB = 5, MI_BLUR_COLOR_RGB2RGBA = 6, MI_BLUR_COLOR_RGB2YCBCR = 7,
+    MI_BLUR_COLOR_YCBCR2RGB = 8
+} mi_blur_color_preset_id;
+
+/* Fill *k with a preset of the table above.  MI_BLUR_ERR_INVALID: an unknown id, a null k. */
+int mi_blur_color_preset(int preset, mi_blur_color *k);
+/* Fill *k with the identity matrix on `channels` (1..4) channels: shift 0, Co = channels, lut_on = 0.  The base of a pure
+ * table look-up (OpenCV's LUT), invert and the like: set lut_on and fill lut[o] for o < channels. */
+int mi_blur_color_identity(int channels, mi_blur_color *k);
+/* One 256-entry table (host only).  gamma: lut[v] = floor(255 * pow(v / 255.0, gamma) + 0.5), in double; gamma <= 0 or not
+ * finite is MI_BLUR_ERR_INVALID.  threshold: lut[v] = v > t ? hi : lo (OpenCV's THRESH_BINARY with two output levels); t in
+ * -1..255, lo and hi in 0..255.  A null table is MI_BLUR_ERR_INVALID. */
+int mi_blur_color_lut_gamma(double gamma, uint8_t lut[256]);
+int mi_blur_color_lut_threshold(int t, int lo, int hi, uint8_t lut[256]);
+
+/* n_images images of width x height x channels in, n_images images of width x height x k->out_channels out (device
+ * memory, asynchronous; n_images == 0 is MI_BLUR_OK; image offsets are 64-bit).  Every argument is checked before a
+ * device is asked for: MI_BLUR_ERR_INVALID comes before MI_BLUR_ERR_NO_DEVICE.  *k travels in the kernel arguments
+ * (about 1.1 KiB with the tables): nothing is allocated, and *k may change as soon as the call returns.
+ * blur_color_tiled_kernel takes exactly the launches with width*height a multiple of 16 and both pointers 16-byte aligned
+ * (and, where a context's in-place submit gives image strides, strides that are multiples of 16).  The rule is FLAT,
+ * unlike the other tiled kernels': rows need not be whole 16-byte chunks, because a pointwise filter on dense images
+ * works on the run of width*height pixels, of which 16 are exactly C input chunks and Co output chunks.  One thread
+ * owns such a group of 16 pixels (C loads and Co stores of 16 bytes), one workgroup 256 consecutive groups of one image;
+ * the kernel is instantiated on (C, Co, lut_on), 32 forms, with the table in LDS where there is one.  Every other launch
+ * goes to blur_color_generic_kernel (one output pixel per thread).  mi_blur_last_kernel() says which one ran. */
+int mi_blur_enqueue_color(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int n_images,
+                          const mi_blur_color *k, void *stream);
+/* The same on the CPU device's threads (synchronous). */
+int mi_blur_cpu_run_color(const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,
+                          const mi_blur_color *k, int n_threads);
+/* Give a context (created with the INPUT width, height, channels) the colour transform, with the rules of
+ * mi_blur_ctx_set_area: only before the first submit (MI_BLUR_ERR_STATE after); it replaces what another setter set
+ * and is replaced by them; the context keeps a copy.  MI_BLUR_ERR_INVALID also when *k is not valid for the context's
+ * image.  mi_blur_submit then writes n_images * W*H*Co bytes to host_out: pageable caller memory, or pinned memory on
+ * both sides (in place, one launch per submit, never the batch server), on the GPU or the CPU device; bytes_alg counts
+ * W*H*(C+Co) per image.  mi_blur_submit_band, _bands, _planar and both resident runs return MI_BLUR_ERR_UNSUPPORTED for
+ * such a context: a band of another channel count has no place in those forms. */
+int mi_blur_ctx_set_color(mi_blur_ctx *ctx, const mi_blur_color *k);
 
 /* ------------------------------------------------------------------------
  * Affine warp: exact fixed-point rotate, scale, shear and translate, any output size (no reference analogue).  The
