@@ -50,6 +50,9 @@ AREA_MAX_RATIO = 64
 COLOR_MAX_CHANNELS = 4
 COLOR_CODES = {"rgb2gray": 0, "bgr2gray": 1, "gray2rgb": 2, "rgb2bgr": 3, "rgba2bgra": 4, "rgba2rgb": 5, "rgb2rgba": 6,
                "rgb2ycbcr": 7, "ycbcr2rgb": 8}
+HIST_BINS = 256
+TONE_EQUALIZE, TONE_STRETCH = 0, 1
+TONE_MODES = {"equalize": TONE_EQUALIZE, "stretch": TONE_STRETCH}
 WARP_Q = 16
 WARP_CLAMP, WARP_CONSTANT = 0, 1
 WARP_BORDERS = {"clamp": WARP_CLAMP, "constant": WARP_CONSTANT}
@@ -65,7 +68,7 @@ def _newer(target: str, sources: list[str]) -> bool:
 
 def build_native(force: bool = False, verbose: bool = False) -> str:
     """Compile libmi_blur.so (hipcc, --offload-arch=gfx950) and the C++ hosts, in-tree."""
-    srcs = [os.path.join(CSRC, f) for f in ("blur_kernels.hip", "sep_kernels.hip", "median_kernels.hip", "morph_kernels.hip", "bilateral_kernels.hip", "conv_kernels.hip", "sep_down_kernels.hip", "resize_kernels.hip", "warp_kernels.hip", "remap_kernels.hip", "area_kernels.hip", "color_kernels.hip", "layout_kernels.hip", "mi_blur_api.cpp", "comm_api.cpp", "cpu_device.cpp")]
+    srcs = [os.path.join(CSRC, f) for f in ("blur_kernels.hip", "sep_kernels.hip", "median_kernels.hip", "morph_kernels.hip", "bilateral_kernels.hip", "conv_kernels.hip", "sep_down_kernels.hip", "resize_kernels.hip", "warp_kernels.hip", "remap_kernels.hip", "area_kernels.hip", "color_kernels.hip", "hist_kernels.hip", "layout_kernels.hip", "mi_blur_api.cpp", "comm_api.cpp", "cpu_device.cpp")]
     deps = srcs + [os.path.join(CSRC, f) for f in ("api_internal.h", "blur_launch.h", "kernel_common.h", "cpu_device.h", "filter.h")] + [HEADER]
     if force or not _newer(LIB_PATH, deps):
         cmd = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra",
@@ -246,6 +249,11 @@ class Color(C.Structure):
                 ("lut_on", C.c_int), ("lut", (C.c_uint8 * 256) * 4)]
 
 
+class Tone(C.Structure):
+    """mi_blur_tone: the mode, the two clips (Q16 shares, STRETCH only), joint and the channel mask (0 = all)."""
+    _fields_ = [("mode", C.c_int), ("clip_lo", C.c_int), ("clip_hi", C.c_int), ("joint", C.c_int), ("channel_mask", C.c_int)]
+
+
 class Warp(C.Structure):
     """mi_blur_warp: the output size, the mode (RESIZE_NEAREST | RESIZE_BILINEAR), the border (WARP_CLAMP | WARP_CONSTANT),
     the fill byte and the OUTPUT -> INPUT map in Q16, row-major 2 x 3."""
@@ -422,6 +430,16 @@ def lib() -> C.CDLL:
         "mi_blur_enqueue_color": (i, [u8p, u8p, i, i, i, i, C.POINTER(Color), vp]),
         "mi_blur_cpu_run_color": (i, [u8p, u8p, i, i, i, i, C.POINTER(Color), i]),
         "mi_blur_ctx_set_color": (i, [vp, C.POINTER(Color)]),
+        "mi_blur_enqueue_hist": (i, [u8p, vp, i, i, i, i, vp]),
+        "mi_blur_cpu_run_hist": (i, [u8p, vp, i, i, i, i, i]),
+        "mi_blur_tone_tables": (i, [vp, i, C.POINTER(Tone), u8p]),
+        "mi_blur_enqueue_tables": (i, [u8p, u8p, i, i, i, i, u8p, vp]),
+        "mi_blur_tone_work_bytes": (C.c_size_t, [i, i]),
+        "mi_blur_enqueue_tone": (i, [u8p, u8p, i, i, i, i, C.POINTER(Tone), vp, vp]),
+        "mi_blur_cpu_run_tables": (i, [u8p, u8p, i, i, i, i, u8p, i]),
+        "mi_blur_cpu_run_tone": (i, [u8p, u8p, i, i, i, i, C.POINTER(Tone), vp, i]),
+        "mi_blur_run_hist": (i, [i, u8p, vp, i, i, i, i]),
+        "mi_blur_run_tone": (i, [i, u8p, u8p, vp, i, i, i, i, C.POINTER(Tone)]),
         "mi_blur_warp_coord": (i, [C.POINTER(Warp), i, i, C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i)]),
         "mi_blur_warp_rotation": (i, [C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double)]),
         "mi_blur_warp_set_matrix": (i, [C.POINTER(Warp), C.POINTER(C.c_double), i]),
@@ -1116,6 +1134,120 @@ def threshold(images, t: int, lo: int = 0, hi: int = 255, device: int = 0, batch
     tab = (C.c_uint8 * 256)()
     check(lib().mi_blur_color_lut_threshold(int(t), int(lo), int(hi), tab), "mi_blur_color_lut_threshold")
     return apply_lut(images, list(tab), device, batch)
+
+
+def _tone_stack(images, name: str):
+    """(images as (N, H, W, C), the rank they came with) for the histogram family: non-empty images of 1..4 channels."""
+    a = _images(images, name)
+    rank = a.ndim
+    if rank == 2:
+        a = a[None, :, :, None]
+    elif rank == 3:
+        a = a[None]
+    n, h, w, c = a.shape
+    if h == 0 or w == 0 or c == 0:
+        raise ValueError(f"{name}: images must not be empty")
+    if c > COLOR_MAX_CHANNELS:
+        raise ValueError(f"{name}: at most {COLOR_MAX_CHANNELS} channels")
+    return a, rank
+
+
+def _tone(mode, clip_q16, joint, channels, c: int, name: str) -> "Tone":
+    """A Tone for images of c channels.  mode: a key of TONE_MODES; clip_q16: (lo, hi) Q16 integers; channels: None (all)
+    or the indices of the channels to transform."""
+    if mode not in TONE_MODES:
+        raise ValueError(f"{name}: mode is one of {sorted(TONE_MODES)}")
+    mask = 0
+    for ch in (() if channels is None else channels):
+        if not 0 <= int(ch) < c:
+            raise ValueError(f"{name}: channel {ch} of {c}")
+        mask |= 1 << int(ch)
+    lo, hi = (int(v) for v in clip_q16)
+    return Tone(TONE_MODES[mode], lo, hi, int(bool(joint)), mask)
+
+
+def _clip_q16(clip, name: str) -> tuple[int, int]:
+    """A fraction of the pixels, or a (lo, hi) pair of fractions, each in [0, 0.5), as Q16 integers (floor)."""
+    import math
+    pair = tuple(clip) if isinstance(clip, (tuple, list)) else (clip, clip)
+    if len(pair) != 2 or not all(0.0 <= float(v) < 0.5 for v in pair):
+        raise ValueError(f"{name}: clip is a fraction in [0, 0.5), or a (lo, hi) pair of them")
+    return tuple(int(math.floor(float(v) * 65536.0)) for v in pair)
+
+
+def _tone_run(a, tone: "Tone", device: int, batch: int, name: str):
+    """a (N, H, W, C) through mi_blur_run_tone, `batch` images per call (0 = all at once)."""
+    import numpy as np
+    n, h, w, c = a.shape
+    out = np.empty_like(a)
+    per = batch if batch > 0 else max(n, 1)
+    for i in range(0, n, per):
+        k = min(per, n - i)
+        check(lib().mi_blur_run_tone(device, a[i:].ctypes.data, out[i:].ctypes.data, None, w, h, c, k, C.byref(tone)), name)
+    return out
+
+
+def histogram(images, device: int = 0, batch: int = 0):
+    """The histogram of every image and channel (mi_blur_run_hist): uint32 of shape (N, C, 256) for a stack (N, H, W, C),
+    (C, 256) for one image (H, W, C) or (H, W).  Exact counts.  device: HIP ordinal, or DEVICE_CPU; batch: images per
+    call (0 = all at once)."""
+    import numpy as np
+    a, rank = _tone_stack(images, "histogram")
+    n, h, w, c = a.shape
+    out = np.empty((n, c, HIST_BINS), np.uint32)
+    per = batch if batch > 0 else max(n, 1)
+    for i in range(0, n, per):
+        check(lib().mi_blur_run_hist(device, a[i:].ctypes.data, out[i:].ctypes.data, w, h, c, min(per, n - i)), "mi_blur_run_hist")
+    return out if rank == 4 else out[0]
+
+
+def tone_tables(hist, mode: str = "equalize", clip=(0, 0), joint: bool = False, channels=None):
+    """The tone tables of histograms (mi_blur_tone_tables; include/mi_blur.h has the definition): hist uint32 (C, 256) or
+    (N, C, 256) -> uint8 of the same shape.  mode: "equalize" | "stretch"; clip: the (lo, hi) shares of the pixels clipped
+    by "stretch", Q16 INTEGERS 0..32767 as the ABI takes them; joint: one table from the summed histograms; channels:
+    the indices of the channels to transform (None = all), the others get the identity."""
+    import numpy as np
+    h = np.ascontiguousarray(hist, dtype=np.uint32)
+    if h.ndim not in (2, 3) or h.shape[-1] != HIST_BINS or not 1 <= h.shape[-2] <= COLOR_MAX_CHANNELS:
+        raise ValueError("tone_tables: hist is uint32 of shape (C, 256) or (N, C, 256), C 1..4")
+    c = h.shape[-2]
+    t = _tone(mode, clip, joint, channels, c, "tone_tables")
+    out = np.empty(h.shape, np.uint8)
+    hs, os_ = h.reshape(-1, c, HIST_BINS), out.reshape(-1, c, HIST_BINS)
+    for i in range(hs.shape[0]):
+        check(lib().mi_blur_tone_tables(hs[i].ctypes.data, c, C.byref(t), os_[i].ctypes.data), "mi_blur_tone_tables")
+    return out
+
+
+def equalize_hist(images, mode: str = "channel", device: int = 0, batch: int = 0):
+    """Histogram equalisation with one table per image (mi_blur_run_tone, MI_BLUR_TONE_EQUALIZE), numpy in -> numpy out of
+    the same shape.  mode "channel": every channel by its own histogram; "joint": one table per image from the sum of
+    its channels' histograms; "luma" (3 channels): cvt_color(rgb2ycbcr), Y equalised, cvt_color(ycbcr2rgb).  OpenCV's
+    equalizeHist formula as an exact ratio, not its bytes."""
+    if mode not in ("channel", "joint", "luma"):
+        raise ValueError('equalize_hist: mode is "channel", "joint" or "luma"')
+    a, rank = _tone_stack(images, "equalize_hist")
+    c = a.shape[3]
+    if mode == "luma":
+        if c != 3:
+            raise ValueError('equalize_hist: "luma" needs 3 channels')
+        ycc = cvt_color(a, "rgb2ycbcr", device, batch)
+        out = cvt_color(_tone_run(ycc, _tone("equalize", (0, 0), False, (0,), 3, "equalize_hist"), device, batch, "equalize_hist"),
+                        "ycbcr2rgb", device, batch)
+    else:
+        out = _tone_run(a, _tone("equalize", (0, 0), mode == "joint", None, c, "equalize_hist"), device, batch, "equalize_hist")
+    return out if rank == 4 else out[0] if rank == 3 else out[0, :, :, 0]
+
+
+def auto_levels(images, clip=0.0, joint: bool = True, channels=None, device: int = 0, batch: int = 0):
+    """Contrast stretch with one table per image (mi_blur_run_tone, MI_BLUR_TONE_STRETCH): the darkest `clip` share of
+    the pixels goes to 0, the brightest to 255, linear between them; clip = 0 is min-max normalisation.  clip: a
+    fraction in [0, 0.5) or a (lo, hi) pair, converted to Q16 with floor.  joint (default): one table per image from
+    all transformed channels, which keeps the colour balance; channels: indices to transform (None = all)."""
+    a, rank = _tone_stack(images, "auto_levels")
+    t = _tone("stretch", _clip_q16(clip, "auto_levels"), joint, channels, a.shape[3], "auto_levels")
+    out = _tone_run(a, t, device, batch, "auto_levels")
+    return out if rank == 4 else out[0] if rank == 3 else out[0, :, :, 0]
 
 
 def warp_coord(warp: "Warp", X: int, Y: int) -> tuple[int, int, int, int]:

@@ -63,6 +63,13 @@ int launch_area(const LaunchDesc &d);
 // The colour transform (FilterKind::COLOR, color_kernels.hip).  The contract of launch_resize; out_stride is measured
 // against the image with the OUTPUT's channel count.
 int launch_color(const LaunchDesc &d);
+// The histogram family (hist_kernels.hip); no Filter and no LaunchDesc: histograms are not images.  Dense images of
+// W x H x C (hist_image_ok(), filter.h), n_images of them; every argument is checked (MI_BLUR_ERR_INVALID), an empty
+// batch is MI_BLUR_OK.  launch_hist: hist = uint32[n][C][256], 16-byte aligned, zeroed on the stream and then added
+// into.  launch_tone_tables: hist -> tables = uint8[n][C][256], by t.  launch_tables: image i through tables[i].
+int launch_hist(const uint8_t *in, uint32_t *hist, int W, int H, int C, int n_images, hipStream_t stream);
+int launch_tone_tables(const uint32_t *hist, uint8_t *tables, int C, int n_images, const mi_blur_tone &t, hipStream_t stream);
+int launch_tables(const uint8_t *in, uint8_t *out, int W, int H, int C, int n_images, const uint8_t *tables, hipStream_t stream);
 // Sets what last_kernel() reports for the calling thread.
 void set_last_kernel(const char *name);
 

@@ -584,6 +584,73 @@ void cpu_blur_batch(const uint8_t *in, uint8_t *out, int W, int band_rows, int C
     Pool::get().run(nt, [&](int) { worker(); });
 }
 
+// The histogram family works on the flat run of an image's W * H pixels: items are (image, slice of pixels), at least
+// 4096 pixels a slice and about four items per thread.
+namespace {
+template <typename F>
+void for_pixel_slices(size_t pixels, int n_images, int n_threads, F &&body)
+{
+    if (n_threads <= 0) n_threads = hardware_threads();
+    int slices = 1;
+    if (n_images < 4 * n_threads)
+        slices = (int)std::max<size_t>(1, std::min<size_t>(pixels / 4096, (size_t)(4 * n_threads + n_images - 1) / (size_t)n_images));
+    const long long items = (long long)n_images * slices;
+    std::atomic<long long> next{0};
+    Pool::get().run((int)std::min<long long>(n_threads, items), [&](int) {
+        for (;;) {
+            const long long it = next.fetch_add(1, std::memory_order_relaxed);
+            if (it >= items) break;
+            const int img = (int)(it / slices), s = (int)(it % slices);
+            body(img, pixels * (size_t)s / (size_t)slices, pixels * (size_t)(s + 1) / (size_t)slices);
+        }
+    });
+}
+}  // namespace
+
+// hist[i][c][v] = the pixels of image i whose channel c holds v: every slice counts on its own and adds its non-zero
+// counters to the image's with atomic adds (integer adds commute: the result does not depend on the threads).
+void cpu_hist(const uint8_t *in, uint32_t *hist, int W, int H, int C, int n_images, int n_threads)
+{
+    if (n_images <= 0) return;
+    const size_t pixels = (size_t)W * H;
+    memset(hist, 0, (size_t)n_images * C * MI_BLUR_HIST_BINS * sizeof(uint32_t));
+    for_pixel_slices(pixels, n_images, n_threads, [&](int img, size_t p0, size_t p1) {
+        uint32_t local[MI_BLUR_COLOR_MAX_CHANNELS * MI_BLUR_HIST_BINS] = {};
+        const uint8_t *px = in + ((size_t)img * pixels + p0) * C;
+        for (size_t n = p1 - p0; n > 0; n--, px += C)
+            for (int c = 0; c < C; c++) local[c * MI_BLUR_HIST_BINS + px[c]]++;
+        uint32_t *dst = hist + (size_t)img * C * MI_BLUR_HIST_BINS;
+        for (int i = 0; i < C * MI_BLUR_HIST_BINS; i++)
+            if (local[i]) __atomic_fetch_add(dst + i, local[i], __ATOMIC_RELAXED);
+    });
+}
+
+// out[i][p][c] = tables[i][c][in[i][p][c]].
+void cpu_tables(const uint8_t *in, uint8_t *out, int W, int H, int C, int n_images, const uint8_t *tables, int n_threads)
+{
+    if (n_images <= 0) return;
+    const size_t pixels = (size_t)W * H;
+    for_pixel_slices(pixels, n_images, n_threads, [&](int img, size_t p0, size_t p1) {
+        const uint8_t *tab = tables + (size_t)img * C * MI_BLUR_HIST_BINS;
+        const uint8_t *px = in + ((size_t)img * pixels + p0) * C;
+        uint8_t *o = out + ((size_t)img * pixels + p0) * C;
+        for (size_t n = p1 - p0; n > 0; n--, px += C, o += C)
+            for (int c = 0; c < C; c++) o[c] = tab[c * MI_BLUR_HIST_BINS + px[c]];
+    });
+}
+
+// Histogram -> tables (tone_tables(), filter.h) -> look-up; work = the histograms, then the tables.
+void cpu_tone(const uint8_t *in, uint8_t *out, int W, int H, int C, int n_images, const mi_blur_tone &t, void *work, int n_threads)
+{
+    if (n_images <= 0) return;
+    uint32_t *hist = static_cast<uint32_t *>(work);
+    uint8_t *tables = reinterpret_cast<uint8_t *>(hist + (size_t)n_images * C * MI_BLUR_HIST_BINS);
+    cpu_hist(in, hist, W, H, C, n_images, n_threads);
+    for (int i = 0; i < n_images; i++)
+        tone_tables(t, hist + (size_t)i * C * MI_BLUR_HIST_BINS, C, tables + (size_t)i * C * MI_BLUR_HIST_BINS);
+    cpu_tables(in, out, W, H, C, n_images, tables, n_threads);
+}
+
 // Synthetic stream: image i = LCG bytes, seed 0x9E3779B9 ^ i.
 void fill_synthetic(uint8_t *host, int W, int H, int C, int first_index, int n_images, int n_threads)
 {

@@ -52,6 +52,13 @@ inline void cpu_blur_batch(const uint8_t *in, uint8_t *out, int W, int band_rows
 {
     cpu_blur_batch(in, out, W, band_rows, C, Filter{FilterKind::BOX, R, {}}, n_images, y0, y1, n_threads, in_stride, out_stride);
 }
+// The histogram family (include/mi_blur.h, "Histogram, and tone tables made from it") on n_images dense W x H x C images;
+// the callers have checked the arguments.  cpu_hist: hist = uint32[n][C][256], overwritten.  cpu_tables: image i through
+// tables[i] = uint8[C][256].  cpu_tone: both with tone_tables() (filter.h) between them; work (4-byte aligned,
+// n * C * 256 * 5 bytes) receives the histograms, then the tables.
+void cpu_hist(const uint8_t *in, uint32_t *hist, int W, int H, int C, int n_images, int n_threads);
+void cpu_tables(const uint8_t *in, uint8_t *out, int W, int H, int C, int n_images, const uint8_t *tables, int n_threads);
+void cpu_tone(const uint8_t *in, uint8_t *out, int W, int H, int C, int n_images, const mi_blur_tone &t, void *work, int n_threads);
 // planar (CImg storage: all of channel 0, then channel 1, ...) <-> interleaved, n_images frames, a few pool threads
 void cpu_repack(const uint8_t *src, uint8_t *dst, int W, int H, int C, int n_images, bool planar_to_interleaved, int n_threads);
 void copy_blocks(uint8_t *dst, size_t dst_stride, const uint8_t *src, size_t src_stride, size_t bytes, int n, int n_threads);

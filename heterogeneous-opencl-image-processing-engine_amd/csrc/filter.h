@@ -445,6 +445,81 @@ inline bool color_image_ok(int co, int W, int H, int C)
            resize_ok(W, H, MI_BLUR_RESIZE_BILINEAR, W, H, co);
 }
 
+// ---- histogram and tone tables (include/mi_blur.h, "Histogram, and tone tables made from it").  The host export, the
+// CPU device and blur_tone_table_kernel all take a table's bytes from tone_entry(), and lo / hi from the two predicates
+// below: c(v) is monotone, so lo = the number of v with tone_below_lo() and hi = the number with tone_upto_hi() minus 1,
+// which the kernel counts across its threads and tone_table() in a loop.
+// An image the family takes: 1..4 channels and the per-image byte limits of resize_ok(), so a count fits 32 bits.
+inline bool hist_image_ok(int W, int H, int C)
+{
+    return C >= 1 && C <= MI_BLUR_COLOR_MAX_CHANNELS && resize_ok(W, H, MI_BLUR_RESIZE_BILINEAR, W, H, C);
+}
+constexpr int TONE_CLIP_MAX = 32767;
+inline bool tone_ok(const mi_blur_tone *t, int C)
+{
+    if (!t || C < 1 || C > MI_BLUR_COLOR_MAX_CHANNELS) return false;
+    if (t->mode != MI_BLUR_TONE_EQUALIZE && t->mode != MI_BLUR_TONE_STRETCH) return false;
+    if (t->clip_lo < 0 || t->clip_hi < 0 || t->clip_lo > TONE_CLIP_MAX || t->clip_hi > TONE_CLIP_MAX) return false;
+    if (t->mode == MI_BLUR_TONE_EQUALIZE && (t->clip_lo || t->clip_hi)) return false;
+    return (t->joint == 0 || t->joint == 1) && t->channel_mask >= 0 && t->channel_mask < (1 << C);
+}
+// The channels *t transforms, as a mask without the "0 = all" form.
+MI_BLUR_HD inline int tone_mask(int channel_mask, int C) { return channel_mask ? channel_mask : (1 << C) - 1; }
+// k = floor(N * clip / 65536): N <= 2^33, clip < 2^15.  EQUALIZE: clips of 0, so k = 0 and lo = m, the first level present.
+MI_BLUR_HD inline uint64_t tone_clip_count(uint64_t N, int clip) { return (N * (uint64_t)clip) >> 16; }
+MI_BLUR_HD inline bool tone_below_lo(uint64_t cv, uint64_t k_lo) { return cv <= k_lo; }                                 // v < lo
+MI_BLUR_HD inline bool tone_upto_hi(uint64_t N, uint64_t c_prev, uint64_t k_hi) { return N - c_prev > k_hi; }           // v <= hi
+// lut[v], from c(v), N > 0, lo, hi and c(lo) (EQUALIZE: lo = m and c(lo) = h(m); hi is not used).
+MI_BLUR_HD inline uint8_t tone_entry(int mode, int v, uint64_t cv, uint64_t N, int lo, int hi, uint64_t c_lo)
+{
+    if (mode == MI_BLUR_TONE_EQUALIZE) {
+        const uint64_t D = N - c_lo;
+        if (D == 0) return (uint8_t)v;
+        return v < lo ? 0 : (uint8_t)((510u * (cv - c_lo) + D) / (2u * D));
+    }
+    if (lo == hi) return (uint8_t)v;
+    if (v <= lo) return 0;
+    if (v >= hi) return 255;
+    const unsigned d = (unsigned)(hi - lo);
+    return (uint8_t)((510u * (unsigned)(v - lo) + d) / (2u * d));
+}
+// One table from the cumulative histogram cum[v] = c(v).
+inline void tone_table(const mi_blur_tone &t, const uint64_t *cum, uint8_t *lut)
+{
+    const uint64_t N = cum[MI_BLUR_HIST_BINS - 1];
+    if (N == 0) { for (int v = 0; v < MI_BLUR_HIST_BINS; v++) lut[v] = (uint8_t)v; return; }
+    const uint64_t k_lo = tone_clip_count(N, t.clip_lo), k_hi = tone_clip_count(N, t.clip_hi);
+    int lo = 0, n_hi = 0;
+    for (int v = 0; v < MI_BLUR_HIST_BINS; v++) {
+        lo += tone_below_lo(cum[v], k_lo);
+        n_hi += tone_upto_hi(N, v ? cum[v - 1] : 0, k_hi);
+    }
+    for (int v = 0; v < MI_BLUR_HIST_BINS; v++) lut[v] = tone_entry(t.mode, v, cum[v], N, lo, n_hi - 1, cum[lo]);
+}
+// The tables of one image: hist uint32[C][256] -> tables uint8[C][256] (t valid for C: tone_ok()).
+inline void tone_tables(const mi_blur_tone &t, const uint32_t *hist, int C, uint8_t *tables)
+{
+    const int mask = tone_mask(t.channel_mask, C);
+    uint64_t cum[MI_BLUR_HIST_BINS];
+    uint8_t joint_lut[MI_BLUR_HIST_BINS];
+    if (t.joint) {
+        uint64_t run = 0;
+        for (int v = 0; v < MI_BLUR_HIST_BINS; v++) {
+            for (int c = 0; c < C; c++) if ((mask >> c) & 1) run += hist[c * MI_BLUR_HIST_BINS + v];
+            cum[v] = run;
+        }
+        tone_table(t, cum, joint_lut);
+    }
+    for (int c = 0; c < C; c++) {
+        uint8_t *lut = tables + c * MI_BLUR_HIST_BINS;
+        if (!((mask >> c) & 1)) { for (int v = 0; v < MI_BLUR_HIST_BINS; v++) lut[v] = (uint8_t)v; continue; }
+        if (t.joint) { for (int v = 0; v < MI_BLUR_HIST_BINS; v++) lut[v] = joint_lut[v]; continue; }
+        uint64_t run = 0;
+        for (int v = 0; v < MI_BLUR_HIST_BINS; v++) { run += hist[c * MI_BLUR_HIST_BINS + v]; cum[v] = run; }
+        tone_table(t, cum, lut);
+    }
+}
+
 // Output size of a decimation of a W x H image: kept columns / rows (> 0 for a valid decimation, down_ok()).
 inline int down_cols(int W, int sx, int ox) { return (W - ox + sx - 1) / sx; }
 inline int down_rows(int H, int sy, int oy) { return (H - oy + sy - 1) / sy; }
@@ -887,5 +962,18 @@ constexpr int COLOR_GROUP = 16;                     // pixels per group
 constexpr int COLOR_RUN = 256;                      // groups per workgroup = its threads
 inline bool color_flat_ok(int W, int H) { return (long long)W * H % COLOR_GROUP == 0; }
 inline int color_runs(int W, int H) { return (int)(((long long)W * H / COLOR_GROUP + COLOR_RUN - 1) / COLOR_RUN); }
+
+// ---- blur_hist_tiled_kernel and blur_tables_tiled_kernel: the flat rule and the groups of the colour kernel, but a
+// workgroup of HIST_THREADS threads owns a run of HIST_RUN consecutive groups of one image and loops over it, thread t
+// taking groups t, t + HIST_THREADS, ... of the run: the flush of the histogram kernel's bins and the load of the tables
+// kernel's tables are paid once per run.
+constexpr int HIST_THREADS = 512;
+constexpr int HIST_RUN = 512;                       // groups per workgroup
+inline int hist_runs(int W, int H) { return (int)(((long long)W * H / COLOR_GROUP + HIST_RUN - 1) / HIST_RUN); }
+// The histogram kernel alone gives an image at most HIST_IMAGE_BLOCKS workgroups (one per CU): workgroup b of a larger
+// image takes runs b, b + HIST_IMAGE_BLOCKS, ... and flushes once.  Every flush lands on the image's one C KiB of
+// counters, and that row takes about one flush per 16 ns whoever sends it (profiles/r19_hist.md).
+constexpr int HIST_IMAGE_BLOCKS = 256;
+inline int hist_blocks(int W, int H) { const int r = hist_runs(W, H); return r < HIST_IMAGE_BLOCKS ? r : HIST_IMAGE_BLOCKS; }
 
 }  // namespace mi_blur

@@ -2323,6 +2323,151 @@ extern "C" int mi_blur_cpu_run_conv(const uint8_t *in, uint8_t *out, int width, 
     return cpu_run_filter(filter_conv(k, &f), f, in, out, width, height, channels, n_images, n_threads);
 }
 
+// ----------------------------------------------------------------------------------
+// histogram, tone tables and per-image tables (no reference analogue).  Not a FilterKind: a histogram is not an image,
+// so the family has its own launches (hist_kernels.hip) and CPU loops and goes through no context.  Every export checks
+// all of its arguments first (MI_BLUR_ERR_INVALID), answers an empty batch next (MI_BLUR_OK) and asks for a device last.
+// ----------------------------------------------------------------------------------
+static bool hist_args_ok(const void *in, int W, int H, int C, int n_images) { return in && n_images >= 0 && hist_image_ok(W, H, C); }
+static bool aligned_to(const void *p, uintptr_t a) { return p && (uintptr_t)p % a == 0; }
+static size_t hist_words(int C, int n_images) { return (size_t)n_images * (size_t)C * MI_BLUR_HIST_BINS; }
+static bool tables_args_ok(const uint8_t *in, const uint8_t *out, int W, int H, int C, int n_images)
+{
+    return out && in != out && hist_args_ok(in, W, H, C, n_images);
+}
+
+extern "C" int mi_blur_enqueue_hist(const uint8_t *d_in, uint32_t *d_hist, int width, int height, int channels, int n_images, void *stream)
+{
+    if (!hist_args_ok(d_in, width, height, channels, n_images) || !aligned_to(d_hist, 16)) return MI_BLUR_ERR_INVALID;
+    if (n_images == 0) return MI_BLUR_OK;
+    if (mi_blur_device_count() <= 0) return MI_BLUR_ERR_NO_DEVICE;
+    return launch_hist(d_in, d_hist, width, height, channels, n_images, (hipStream_t)stream);
+}
+
+extern "C" int mi_blur_cpu_run_hist(const uint8_t *in, uint32_t *hist, int width, int height, int channels, int n_images, int n_threads)
+{
+    if (!hist_args_ok(in, width, height, channels, n_images) || !aligned_to(hist, 4)) return MI_BLUR_ERR_INVALID;
+    cpu_hist(in, hist, width, height, channels, n_images, n_threads);
+    return MI_BLUR_OK;
+}
+
+extern "C" int mi_blur_tone_tables(const uint32_t *hist, int channels, const mi_blur_tone *t, uint8_t *tables)
+{
+    if (!hist || !tables || !tone_ok(t, channels)) return MI_BLUR_ERR_INVALID;
+    tone_tables(*t, hist, channels, tables);
+    return MI_BLUR_OK;
+}
+
+extern "C" int mi_blur_enqueue_tables(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int n_images,
+                                      const uint8_t *d_tables, void *stream)
+{
+    if (!tables_args_ok(d_in, d_out, width, height, channels, n_images) || !d_tables) return MI_BLUR_ERR_INVALID;
+    if (n_images == 0) return MI_BLUR_OK;
+    if (mi_blur_device_count() <= 0) return MI_BLUR_ERR_NO_DEVICE;
+    return launch_tables(d_in, d_out, width, height, channels, n_images, d_tables, (hipStream_t)stream);
+}
+
+extern "C" size_t mi_blur_tone_work_bytes(int channels, int n_images)
+{
+    if (channels < 1 || channels > MI_BLUR_COLOR_MAX_CHANNELS || n_images < 0) return 0;
+    return hist_words(channels, n_images) * (sizeof(uint32_t) + 1);
+}
+
+// The three dispatches of mi_blur_enqueue_tone on buffers that are known to be good.
+static int enqueue_tone(const uint8_t *d_in, uint8_t *d_out, int W, int H, int C, int n_images, const mi_blur_tone &t, void *d_work, hipStream_t stream)
+{
+    uint32_t *hist = static_cast<uint32_t *>(d_work);
+    uint8_t *tables = reinterpret_cast<uint8_t *>(hist + hist_words(C, n_images));
+    if (const int rc = launch_hist(d_in, hist, W, H, C, n_images, stream)) return rc;
+    if (const int rc = launch_tone_tables(hist, tables, C, n_images, t, stream)) return rc;
+    return launch_tables(d_in, d_out, W, H, C, n_images, tables, stream);
+}
+
+extern "C" int mi_blur_enqueue_tone(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int n_images,
+                                    const mi_blur_tone *t, void *d_work, void *stream)
+{
+    if (!tables_args_ok(d_in, d_out, width, height, channels, n_images) || !tone_ok(t, channels) || !aligned_to(d_work, 16))
+        return MI_BLUR_ERR_INVALID;
+    if (n_images == 0) return MI_BLUR_OK;
+    if (mi_blur_device_count() <= 0) return MI_BLUR_ERR_NO_DEVICE;
+    return enqueue_tone(d_in, d_out, width, height, channels, n_images, *t, d_work, (hipStream_t)stream);
+}
+
+extern "C" int mi_blur_cpu_run_tables(const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,
+                                      const uint8_t *tables, int n_threads)
+{
+    if (!tables_args_ok(in, out, width, height, channels, n_images) || !tables) return MI_BLUR_ERR_INVALID;
+    cpu_tables(in, out, width, height, channels, n_images, tables, n_threads);
+    return MI_BLUR_OK;
+}
+
+extern "C" int mi_blur_cpu_run_tone(const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,
+                                    const mi_blur_tone *t, void *work, int n_threads)
+{
+    if (!tables_args_ok(in, out, width, height, channels, n_images) || !tone_ok(t, channels) || (work && !aligned_to(work, 4)))
+        return MI_BLUR_ERR_INVALID;
+    std::vector<uint32_t> own;
+    if (!work) {
+        try { own.resize((mi_blur_tone_work_bytes(channels, n_images) + 3) / 4); } catch (...) { return MI_BLUR_ERR_NOMEM; }
+        work = own.data();
+    }
+    cpu_tone(in, out, width, height, channels, n_images, *t, work, n_threads);
+    return MI_BLUR_OK;
+}
+
+namespace {
+// Device memory of a blocking export: freed when the export returns, whichever way.
+struct DeviceBuffer {
+    void *p = nullptr;
+    ~DeviceBuffer() { if (p) (void)hipFree(p); }
+    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
+};
+int use_device(int device)
+{
+    const int ndev = mi_blur_device_count();
+    if (ndev <= 0 || device < 0 || device >= ndev) return MI_BLUR_ERR_NO_DEVICE;
+    HIP_TRY(hipSetDevice(device));
+    return MI_BLUR_OK;
+}
+}  // namespace
+
+extern "C" int mi_blur_run_hist(int device, const uint8_t *host_in, uint32_t *host_hist, int width, int height, int channels, int n_images)
+{
+    if (device == MI_BLUR_DEVICE_CPU) return mi_blur_cpu_run_hist(host_in, host_hist, width, height, channels, n_images, 0);
+    if (!hist_args_ok(host_in, width, height, channels, n_images) || !aligned_to(host_hist, 4)) return MI_BLUR_ERR_INVALID;
+    if (n_images == 0) return MI_BLUR_OK;
+    if (const int rc = use_device(device)) return rc;
+    const size_t in_bytes = (size_t)n_images * width * height * channels, hist_bytes = hist_words(channels, n_images) * sizeof(uint32_t);
+    DeviceBuffer in, hist;
+    HIP_TRY(in.alloc(in_bytes));
+    HIP_TRY(hist.alloc(hist_bytes));
+    HIP_TRY(hipMemcpy(in.p, host_in, in_bytes, hipMemcpyHostToDevice));
+    if (const int rc = launch_hist(static_cast<const uint8_t *>(in.p), static_cast<uint32_t *>(hist.p), width, height, channels, n_images, nullptr)) return rc;
+    HIP_TRY(hipMemcpy(host_hist, hist.p, hist_bytes, hipMemcpyDeviceToHost));        // on the null stream: behind the kernels
+    return MI_BLUR_OK;
+}
+
+extern "C" int mi_blur_run_tone(int device, const uint8_t *host_in, uint8_t *host_out, void *host_work, int width, int height,
+                                int channels, int n_images, const mi_blur_tone *t)
+{
+    if (device == MI_BLUR_DEVICE_CPU) return mi_blur_cpu_run_tone(host_in, host_out, width, height, channels, n_images, t, host_work, 0);
+    if (!tables_args_ok(host_in, host_out, width, height, channels, n_images) || !tone_ok(t, channels) || (host_work && !aligned_to(host_work, 4)))
+        return MI_BLUR_ERR_INVALID;
+    if (n_images == 0) return MI_BLUR_OK;
+    if (const int rc = use_device(device)) return rc;
+    const size_t bytes = (size_t)n_images * width * height * channels, work_bytes = mi_blur_tone_work_bytes(channels, n_images);
+    DeviceBuffer in, out, work;
+    HIP_TRY(in.alloc(bytes));
+    HIP_TRY(out.alloc(bytes));
+    HIP_TRY(work.alloc(work_bytes));
+    HIP_TRY(hipMemcpy(in.p, host_in, bytes, hipMemcpyHostToDevice));
+    if (const int rc = enqueue_tone(static_cast<const uint8_t *>(in.p), static_cast<uint8_t *>(out.p), width, height, channels, n_images, *t, work.p, nullptr))
+        return rc;
+    HIP_TRY(hipMemcpy(host_out, out.p, bytes, hipMemcpyDeviceToHost));
+    if (host_work) HIP_TRY(hipMemcpy(host_work, work.p, work_bytes, hipMemcpyDeviceToHost));
+    return MI_BLUR_OK;
+}
+
 extern "C" void mi_blur_fill_synthetic(uint8_t *host, int width, int height, int channels, int first_index,
                                        int n_images, int n_threads)
 {

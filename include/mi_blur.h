@@ -72,7 +72,8 @@ int mi_blur_version(void);
  * "blur_resize_tiled_kernel", "blur_resize_generic_kernel", "blur_warp_tiled_kernel", "blur_warp_generic_kernel",
  * "blur_warp_persp_tiled_kernel", "blur_warp_persp_generic_kernel", "blur_remap_tiled_kernel",
  * "blur_remap_generic_kernel", "blur_area_tiled_kernel", "blur_area_generic_kernel", "blur_color_tiled_kernel",
- * "blur_color_generic_kernel"; "" before the first):
+ * "blur_color_generic_kernel", "blur_hist_tiled_kernel", "blur_hist_generic_kernel", "blur_tone_table_kernel",
+ * "blur_tables_tiled_kernel", "blur_tables_generic_kernel"; "" before the first):
  * reports name the kernel a profiler will show.  Static string, never NULL. */
 const char *mi_blur_last_kernel(void);
 
@@ -677,6 +678,100 @@ int mi_blur_cpu_run_color(const uint8_t *in, uint8_t *out, int width, int height
  * W*H*(C+Co) per image.  mi_blur_submit_band, _bands, _planar and both resident runs return MI_BLUR_ERR_UNSUPPORTED for
  * such a context: a band of another channel count has no place in those forms. */
 int mi_blur_ctx_set_color(mi_blur_ctx *ctx, const mi_blur_color *k);
+
+/* ------------------------------------------------------------------------
+ * Histogram, and tone tables made from it: equalisation, min-max and percentile stretch, with one table per image and
+ * channel (no reference analogue).  The first operation here that measures an image instead of mapping it.  Counts are
+ * integers and the tables are integer ratios rounded once, so the GPU, the CPU device and a numpy / Python-integer
+ * restatement agree exactly, whatever the order of the adds.  Not a filter of a context: histograms are not images, so
+ * none of this goes through contexts, slots or the batch server.
+ *
+ * Images are interleaved and dense, 1..4 channels (MI_BLUR_COLOR_MAX_CHANNELS), within the resize's per-image byte
+ * limits (width, height <= MI_BLUR_RESIZE_MAX_DIM; width*channels <= INT_MAX/2; width*height*channels <= INT_MAX), so
+ * every count fits uint32_t.  n_images == 0 is MI_BLUR_OK and launches nothing.  Image offsets are 64-bit.
+ *
+ * Histogram: hist[i][c][v] = the number of pixels of image i whose channel c holds v; uint32[n_images][channels][256].
+ *
+ * Tone table of ONE image from its histogram uint32[channels][256], by *t (mi_blur_tone):
+ *   The channels that are transformed are those whose bit is set in channel_mask; 0 means all of them.  Every other
+ *   channel gets the identity table (lut[v] = v).
+ *   joint == 0: every transformed channel gets the table of its own histogram h(v) = hist[c][v].
+ *   joint == 1: every transformed channel gets the SAME table, of h(v) = the sum of hist[c][v] over the transformed
+ *   channels (64-bit).
+ *   N = sum_v h(v);  c(v) = sum_{u <= v} h(u), c(-1) = 0.  N == 0 (an all-zero histogram, which no image has) gives the
+ *   identity.
+ *   MI_BLUR_TONE_EQUALIZE:  m = the first v with h(v) > 0;  D = N - h(m).
+ *     D == 0 (one grey level): the identity.  Otherwise lut[v] = 0 for v < m, and
+ *     lut[v] = floor((510 * (c(v) - h(m)) + D) / (2 * D)) for v >= m.
+ *     This is OpenCV's equalizeHist formula as an exact ratio rounded once, half up; it is NOT claimed to be OpenCV's
+ *     bytes, which come from a multiplication by a float scale.
+ *   MI_BLUR_TONE_STRETCH:  k_lo = floor(N * clip_lo / 65536), lo = the smallest v with c(v) > k_lo;
+ *     k_hi = floor(N * clip_hi / 65536), hi = the largest v with N - c(v - 1) > k_hi.
+ *     lo <= hi always: at most k_lo pixels lie below lo, at most k_hi above hi, and k_lo + k_hi < N.
+ *     lo == hi: the identity.  Otherwise lut[v] = 0 for v <= lo, 255 for v >= hi, and
+ *     lut[v] = floor((510 * (v - lo) + (hi - lo)) / (2 * (hi - lo))) between them.  Clips of 0: min-max normalisation.
+ *   Everything stays below 2^49 in 64 bits (N <= 2^33 for four summed channels).
+ * Valid *t: mode EQUALIZE or STRETCH; clip_lo, clip_hi in 0..32767 (Q16 shares of the pixels), both 0 with EQUALIZE;
+ * joint 0 or 1; channel_mask without bits at or above `channels`.  Anything else is MI_BLUR_ERR_INVALID, the output
+ * untouched.
+ * ---------------------------------------------------------------------- */
+#define MI_BLUR_HIST_BINS 256
+typedef enum { MI_BLUR_TONE_EQUALIZE = 0, MI_BLUR_TONE_STRETCH = 1 } mi_blur_tone_mode;
+typedef struct mi_blur_tone {
+    int mode;               /* mi_blur_tone_mode */
+    int clip_lo, clip_hi;   /* STRETCH: share of the pixels clipped at each end, Q16, 0..32767 each; EQUALIZE: must be 0 */
+    int joint;              /* 0: every channel its own table | 1: one table from the SUM of the masked channels' histograms */
+    int channel_mask;       /* bit c = channel c is transformed; others get the identity table (copied); 0 = all channels */
+} mi_blur_tone;
+
+/* The histograms of n_images images (device memory, asynchronous).  d_hist: uint32[n_images][channels][256], 16-byte
+ * aligned, OVERWRITTEN: the caller need not zero it (the call zeroes it on `stream`, then the kernel adds into it).
+ * MI_BLUR_ERR_INVALID (before MI_BLUR_ERR_NO_DEVICE): a null pointer, channels outside 1..4, a size outside the limits
+ * above, n_images < 0, d_hist not 16-byte aligned.
+ * blur_hist_tiled_kernel takes exactly the launches with width*height a multiple of 16 and d_in 16-byte aligned (the
+ * colour transform's flat rule): a workgroup owns a run of 512 consecutive groups of 16 pixels of one image (an image of
+ * more than 256 runs has 256 workgroups, each taking every 256th run), reads them in 16-byte chunks, counts in LDS (one
+ * set of channels x 256 counters per wave, 32-bit) and adds its non-zero counters to d_hist with atomic adds.  Every
+ * other launch goes to blur_hist_generic_kernel (one byte per thread and step).
+ * mi_blur_last_kernel() says which one ran. */
+int mi_blur_enqueue_hist(const uint8_t *d_in, uint32_t *d_hist, int width, int height, int channels, int n_images, void *stream);
+/* The same on the CPU device's threads (synchronous); hist in host memory, 4-byte aligned, overwritten. */
+int mi_blur_cpu_run_hist(const uint8_t *in, uint32_t *hist, int width, int height, int channels, int n_images, int n_threads);
+
+/* The tables of ONE image (host only): hist uint32[channels][256] -> tables uint8[channels][256], by the definition
+ * above.  MI_BLUR_ERR_INVALID: a null pointer, channels outside 1..4, an invalid *t. */
+int mi_blur_tone_tables(const uint32_t *hist, int channels, const mi_blur_tone *t, uint8_t *tables);
+
+/* Every image through its OWN tables (device memory, asynchronous): out[i][p][c] = d_tables[i][c][in[i][p][c]].
+ * d_tables: uint8[n_images][channels][256] in device memory, any alignment; read by the kernel of this launch only.
+ * d_in == d_out is MI_BLUR_ERR_INVALID, as are the argument errors of mi_blur_enqueue_hist.
+ * blur_tables_tiled_kernel takes the launches with width*height a multiple of 16 and d_in and d_out 16-byte aligned
+ * (an image's tables go to LDS once per workgroup; a thread owns groups of 16 pixels: C loads of 16 bytes, byte
+ * look-ups in LDS, C stores); every other launch goes to blur_tables_generic_kernel. */
+int mi_blur_enqueue_tables(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int n_images,
+                           const uint8_t *d_tables, void *stream);
+/* Bytes of the work buffer of mi_blur_enqueue_tone: n_images*channels*256*4 for the histograms, then
+ * n_images*channels*256 for the tables.  0 for channels outside 1..4 or n_images < 0. */
+size_t mi_blur_tone_work_bytes(int channels, int n_images);
+/* Histogram -> tables -> apply as one call: three dispatches on `stream` (mi_blur_enqueue_hist, blur_tone_table_kernel:
+ * one workgroup per table, a prefix sum over the bins and the arithmetic of mi_blur_tone_tables; mi_blur_enqueue_tables),
+ * no host round trip.  d_work (device memory, 16-byte aligned, mi_blur_tone_work_bytes() bytes) holds the histograms,
+ * then the tables, in the layouts above; both are valid for the caller to read once the stream has drained.
+ * MI_BLUR_ERR_INVALID also for an invalid *t, a null or misaligned d_work, d_in == d_out. */
+int mi_blur_enqueue_tone(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int n_images,
+                         const mi_blur_tone *t, void *d_work, void *stream);
+/* The same two on the CPU device's threads (synchronous).  work: host memory laid out as d_work, 4-byte aligned, or
+ * NULL (the call then allocates its own and drops it). */
+int mi_blur_cpu_run_tables(const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,
+                           const uint8_t *tables, int n_threads);
+int mi_blur_cpu_run_tone(const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,
+                         const mi_blur_tone *t, void *work /* may be NULL */, int n_threads);
+/* Blocking, host memory in and out: allocate on `device` (a HIP ordinal), copy in, enqueue, copy out, free.
+ * device == MI_BLUR_DEVICE_CPU calls the cpu_run forms with all threads.  MI_BLUR_ERR_NO_DEVICE where there is no such
+ * device, after the argument checks.  host_work: as `work` above (receives the histograms and the tables), or NULL. */
+int mi_blur_run_hist(int device, const uint8_t *host_in, uint32_t *host_hist, int width, int height, int channels, int n_images);
+int mi_blur_run_tone(int device, const uint8_t *host_in, uint8_t *host_out, void *host_work /* may be NULL */,
+                     int width, int height, int channels, int n_images, const mi_blur_tone *t);
 
 /* ------------------------------------------------------------------------
  * Affine warp: exact fixed-point rotate, scale, shear and translate, any output size (no reference analogue).  The
