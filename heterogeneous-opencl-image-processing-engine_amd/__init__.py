@@ -53,6 +53,8 @@ COLOR_CODES = {"rgb2gray": 0, "bgr2gray": 1, "gray2rgb": 2, "rgb2bgr": 3, "rgba2
 HIST_BINS = 256
 TONE_EQUALIZE, TONE_STRETCH = 0, 1
 TONE_MODES = {"equalize": TONE_EQUALIZE, "stretch": TONE_STRETCH}
+ARITH_LINEAR, ARITH_ABSDIFF, ARITH_MIN, ARITH_MAX, ARITH_MUL, ARITH_LERP = range(6)
+ARITH_PRESETS = {"add": 0, "sub": 1, "avg": 2, "diff128": 3, "absdiff": 4, "min": 5, "max": 6, "mul255": 7, "mulq7": 8, "lerp": 9}
 WARP_Q = 16
 WARP_CLAMP, WARP_CONSTANT = 0, 1
 WARP_BORDERS = {"clamp": WARP_CLAMP, "constant": WARP_CONSTANT}
@@ -68,7 +70,7 @@ def _newer(target: str, sources: list[str]) -> bool:
 
 def build_native(force: bool = False, verbose: bool = False) -> str:
     """Compile libmi_blur.so (hipcc, --offload-arch=gfx950) and the C++ hosts, in-tree."""
-    srcs = [os.path.join(CSRC, f) for f in ("blur_kernels.hip", "sep_kernels.hip", "median_kernels.hip", "morph_kernels.hip", "bilateral_kernels.hip", "conv_kernels.hip", "sep_down_kernels.hip", "resize_kernels.hip", "warp_kernels.hip", "remap_kernels.hip", "area_kernels.hip", "color_kernels.hip", "hist_kernels.hip", "layout_kernels.hip", "mi_blur_api.cpp", "comm_api.cpp", "cpu_device.cpp")]
+    srcs = [os.path.join(CSRC, f) for f in ("blur_kernels.hip", "sep_kernels.hip", "median_kernels.hip", "morph_kernels.hip", "bilateral_kernels.hip", "conv_kernels.hip", "sep_down_kernels.hip", "resize_kernels.hip", "warp_kernels.hip", "remap_kernels.hip", "area_kernels.hip", "color_kernels.hip", "hist_kernels.hip", "arith_kernels.hip", "layout_kernels.hip", "mi_blur_api.cpp", "comm_api.cpp", "cpu_device.cpp")]
     deps = srcs + [os.path.join(CSRC, f) for f in ("api_internal.h", "blur_launch.h", "kernel_common.h", "cpu_device.h", "filter.h")] + [HEADER]
     if force or not _newer(LIB_PATH, deps):
         cmd = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra",
@@ -252,6 +254,13 @@ class Color(C.Structure):
 class Tone(C.Structure):
     """mi_blur_tone: the mode, the two clips (Q16 shares, STRETCH only), joint and the channel mask (0 = all)."""
     _fields_ = [("mode", C.c_int), ("clip_lo", C.c_int), ("clip_hi", C.c_int), ("joint", C.c_int), ("channel_mask", C.c_int)]
+
+
+class Arith(C.Structure):
+    """mi_blur_arith: the operation (ARITH_*), its weights wa, wb, bias and shift, and the plane / shared flags of B and
+    of the mask (include/mi_blur.h, "Two-image arithmetic")."""
+    _fields_ = [("op", C.c_int), ("wa", C.c_int32), ("wb", C.c_int32), ("bias", C.c_int32), ("shift", C.c_int),
+                ("b_plane", C.c_int), ("b_shared", C.c_int), ("m_plane", C.c_int), ("m_shared", C.c_int)]
 
 
 class Warp(C.Structure):
@@ -440,6 +449,12 @@ def lib() -> C.CDLL:
         "mi_blur_cpu_run_tone": (i, [u8p, u8p, i, i, i, i, C.POINTER(Tone), vp, i]),
         "mi_blur_run_hist": (i, [i, u8p, vp, i, i, i, i]),
         "mi_blur_run_tone": (i, [i, u8p, u8p, vp, i, i, i, i, C.POINTER(Tone)]),
+        "mi_blur_arith_preset": (i, [i, C.POINTER(Arith)]),
+        "mi_blur_arith_weighted": (i, [C.c_double, C.c_double, C.c_double, C.POINTER(Arith)]),
+        "mi_blur_arith_value": (i, [C.POINTER(Arith), i, i, i]),
+        "mi_blur_enqueue_arith": (i, [u8p, u8p, u8p, u8p, i, i, i, i, C.POINTER(Arith), vp]),
+        "mi_blur_cpu_run_arith": (i, [u8p, u8p, u8p, u8p, i, i, i, i, C.POINTER(Arith), i]),
+        "mi_blur_run_arith": (i, [i, u8p, u8p, u8p, u8p, i, i, i, i, C.POINTER(Arith)]),
         "mi_blur_warp_coord": (i, [C.POINTER(Warp), i, i, C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i)]),
         "mi_blur_warp_rotation": (i, [C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double)]),
         "mi_blur_warp_set_matrix": (i, [C.POINTER(Warp), C.POINTER(C.c_double), i]),
@@ -1248,6 +1263,172 @@ def auto_levels(images, clip=0.0, joint: bool = True, channels=None, device: int
     t = _tone("stretch", _clip_q16(clip, "auto_levels"), joint, channels, a.shape[3], "auto_levels")
     out = _tone_run(a, t, device, batch, "auto_levels")
     return out if rank == 4 else out[0] if rank == 3 else out[0, :, :, 0]
+
+
+def arith_preset(name) -> "Arith":
+    """The preset `name` (a key of ARITH_PRESETS, or its id) as an Arith (mi_blur_arith_preset), plane and shared flags 0."""
+    k = Arith()
+    code = ARITH_PRESETS.get(name.lower()) if isinstance(name, str) else int(name)
+    if code is None:
+        raise ValueError(f"arith_preset: one of {sorted(ARITH_PRESETS)}")
+    check(lib().mi_blur_arith_preset(code, C.byref(k)), "mi_blur_arith_preset")
+    return k
+
+
+def arith_value(k: "Arith", a: int, b: int, m: int = 0) -> int:
+    """The output byte of k for the operand bytes a, b and (LERP) m: mi_blur_arith_value, the definition for one byte.
+    -1 for an invalid k or an operand outside 0..255."""
+    return lib().mi_blur_arith_value(C.byref(k), int(a), int(b), int(m))
+
+
+def _arith_operand(x, shape, name: str, what: str):
+    """(x as a contiguous uint8 array, plane, shared) for an operand of images of the stack shape (N, H, W, C):
+    (N, H, W, C) full; (H, W, C) one image for all; (N, H, W, 1) a plane; (H, W, 1) or (H, W) one plane for all.  A
+    one-channel or single image makes "plane" or "shared" another name of the same bytes."""
+    n, h, w, c = shape
+    x = _images(x, name)
+    if x.ndim == 4 and x.shape in ((n, h, w, c), (n, h, w, 1)):
+        return x, int(x.shape[3] != c), 0
+    if x.ndim == 3 and x.shape in ((h, w, c), (h, w, 1)):
+        return x, int(x.shape[2] != c), 1
+    if x.ndim == 2 and x.shape == (h, w):
+        return x, int(c != 1), 1
+    raise ValueError(f"{name}: {what} of shape {x.shape} does not go with images of shape {shape}: (N, H, W, C), (H, W, C), "
+                     "(N, H, W, 1), (H, W, 1) or (H, W)")
+
+
+def arith(a, b, k: "Arith", mask=None, device: int = 0, batch: int = 0):
+    """Two-image arithmetic (mi_blur_run_arith; include/mi_blur.h, "Two-image arithmetic", has the definition): every
+    byte of `a` combined with the byte of `b` (and, for ARITH_LERP, of `mask`) by k's operation, numpy in -> numpy out
+    of a's shape.  a: (N, H, W, C), (H, W, C) or (H, W) uint8.  b and mask, against a's stack shape (N, H, W, C):
+    (N, H, W, C) full; (H, W, C) one image shared by the batch; (N, H, W, 1) one plane per image, applied to every
+    channel; (H, W, 1) or (H, W) one shared plane.  k's plane and shared flags are set from these shapes.  mask is
+    required for ARITH_LERP and refused otherwise.  device: HIP ordinal, or DEVICE_CPU; batch: images per call (0 = all
+    at once), which cuts all unshared operands alike."""
+    import numpy as np
+    a, rank = _tone_stack(a, "arith")
+    n, h, w, c = a.shape
+    q = Arith.from_buffer_copy(k)
+    if (q.op == ARITH_LERP) != (mask is not None):
+        raise ValueError("arith: a mask goes with ARITH_LERP and with nothing else")
+    b, q.b_plane, q.b_shared = _arith_operand(b, a.shape, "arith", "b")
+    m_step = 0
+    if mask is not None:
+        mask, q.m_plane, q.m_shared = _arith_operand(mask, a.shape, "arith", "mask")
+        m_step = 0 if q.m_shared else h * w * (1 if q.m_plane else c)
+    b_step = 0 if q.b_shared else h * w * (1 if q.b_plane else c)
+    out = np.empty_like(a)
+    per = batch if batch > 0 else max(n, 1)
+    for i in range(0, n, per):
+        check(lib().mi_blur_run_arith(device, a[i:].ctypes.data, b.ctypes.data + i * b_step, None if mask is None else mask.ctypes.data + i * m_step,
+                                      out[i:].ctypes.data, w, h, c, min(per, n - i), C.byref(q)), "mi_blur_run_arith")
+    return out if rank == 4 else out[0] if rank == 3 else out[0, :, :, 0]
+
+
+def add(a, b, device: int = 0, batch: int = 0):
+    """min(a + b, 255) per byte (preset ADD); shapes as arith()."""
+    return arith(a, b, arith_preset("add"), None, device, batch)
+
+
+def subtract(a, b, device: int = 0, batch: int = 0):
+    """max(a - b, 0) per byte (preset SUB); shapes as arith()."""
+    return arith(a, b, arith_preset("sub"), None, device, batch)
+
+
+def absdiff(a, b, device: int = 0, batch: int = 0):
+    """|a - b| per byte (preset ABSDIFF); shapes as arith()."""
+    return arith(a, b, arith_preset("absdiff"), None, device, batch)
+
+
+def average(a, b, device: int = 0, batch: int = 0):
+    """(a + b + 1) >> 1 per byte (preset AVG); shapes as arith()."""
+    return arith(a, b, arith_preset("avg"), None, device, batch)
+
+
+def minimum(a, b, device: int = 0, batch: int = 0):
+    """min(a, b) per byte; shapes as arith()."""
+    return arith(a, b, arith_preset("min"), None, device, batch)
+
+
+def maximum(a, b, device: int = 0, batch: int = 0):
+    """max(a, b) per byte; shapes as arith()."""
+    return arith(a, b, arith_preset("max"), None, device, batch)
+
+
+def multiply(a, b, mode: str = "255", device: int = 0, batch: int = 0):
+    """mode "255": floor((2 a b + 255) / 510), the product of two shares of 255 rounded once (preset MUL255);
+    mode "q7": min((a b + 64) >> 7, 255), b a gain image with 128 = unity (preset MULQ7).  Shapes as arith()."""
+    if mode not in ("255", "q7"):
+        raise ValueError('multiply: mode is "255" or "q7"')
+    return arith(a, b, arith_preset("mul255" if mode == "255" else "mulq7"), None, device, batch)
+
+
+def add_weighted(a, alpha: float, b, beta: float, gamma: float = 0.0, device: int = 0, batch: int = 0):
+    """OpenCV's addWeighted in Q12 (mi_blur_arith_weighted): clamp((wa a + wb b + bias) >> 12) with
+    wa = floor(alpha 4096 + 0.5), wb = floor(beta 4096 + 0.5), bias = floor(gamma 4096 + 0.5) + 2048.  |alpha|, |beta| <= 16,
+    |gamma| <= 8192.  Shapes as arith()."""
+    k = Arith()
+    if lib().mi_blur_arith_weighted(float(alpha), float(beta), float(gamma), C.byref(k)) != OK:
+        raise ValueError("add_weighted: finite weights, |alpha|, |beta| <= 16 and |gamma| <= 8192")
+    return arith(a, b, k, None, device, batch)
+
+
+def blend(a, b, mask, device: int = 0, batch: int = 0):
+    """The blend of a and b through a mask (ARITH_LERP): floor((2 (a m + b (255 - m)) + 255) / 510) per byte, one
+    rounding, half up; m = 255 gives a, m = 0 gives b.  mask: shapes as arith()'s operands (a grey mask (H, W) serves
+    every image and channel), or one int 0..255 for a constant weight."""
+    import numpy as np
+    import operator
+    if not hasattr(mask, "shape") and not isinstance(mask, (list, tuple)):
+        level = operator.index(mask)
+        if not 0 <= level <= 255:
+            raise ValueError("blend: a constant mask is 0..255")
+        stack, _ = _tone_stack(a, "blend")
+        mask = np.full(stack.shape[1:3], level, np.uint8)
+    return arith(a, b, arith_preset("lerp"), mask, device, batch)
+
+
+def unsharp_mask(images, sigma: float, amount: float = 1.0, device: int = 0, batch: int = 0):
+    """Unsharp masking: clamp(((256 + g) a - g blur(a) + 128) >> 8) with g = floor(amount 256 + 0.5), amount in [0, 16],
+    and blur(a) = gaussian_blur(images, sigma): ARITH_LINEAR with wa = 256 + g, wb = -g, bias 128, shift 8."""
+    import math
+    if not 0.0 <= float(amount) <= 16.0:
+        raise ValueError("unsharp_mask: amount in [0, 16]")
+    g = int(math.floor(float(amount) * 256.0 + 0.5))
+    a = _images(images, "unsharp_mask")
+    return arith(a, gaussian_blur(a, sigma, device=device, batch=batch), Arith(ARITH_LINEAR, 256 + g, -g, 128, 8), None, device, batch)
+
+
+def top_hat(images, ksize=3, device: int = 0, batch: int = 0):
+    """White top-hat: max(a - open(a), 0) with open(a) = dilate(erode(a, ksize), ksize): preset SUB of the image and its
+    opening.  ksize as erode()."""
+    a = _images(images, "top_hat")
+    return subtract(a, dilate(erode(a, ksize, device, batch), ksize, device, batch), device, batch)
+
+
+def black_hat(images, ksize=3, device: int = 0, batch: int = 0):
+    """Black top-hat: max(close(a) - a, 0) with close(a) = erode(dilate(a, ksize), ksize): preset SUB of the closing and
+    the image.  ksize as erode()."""
+    a = _images(images, "black_hat")
+    return subtract(erode(dilate(a, ksize, device, batch), ksize, device, batch), a, device, batch)
+
+
+def difference_of_gaussians(images, sigma1: float, sigma2: float, device: int = 0, batch: int = 0):
+    """clamp(gaussian_blur(a, sigma1) - gaussian_blur(a, sigma2) + 128): preset DIFF128 of the two blurs, the signed
+    difference around grey."""
+    a = _images(images, "difference_of_gaussians")
+    return arith(gaussian_blur(a, sigma1, device=device, batch=batch), gaussian_blur(a, sigma2, device=device, batch=batch),
+                 arith_preset("diff128"), None, device, batch)
+
+
+def running_average(acc, frame, shift: int, device: int = 0, batch: int = 0):
+    """One step of a running-average background: ((2^shift - 1) acc + frame + 2^(shift - 1)) >> shift, shift in 1..8:
+    ARITH_LINEAR with wa = 2^shift - 1, wb = 1, bias = 2^(shift - 1).  Returns the new accumulator."""
+    import operator
+    shift = operator.index(shift)
+    if not 1 <= shift <= 8:
+        raise ValueError("running_average: shift in 1..8")
+    return arith(acc, frame, Arith(ARITH_LINEAR, (1 << shift) - 1, 1, 1 << (shift - 1), shift), None, device, batch)
 
 
 def warp_coord(warp: "Warp", X: int, Y: int) -> tuple[int, int, int, int]:

@@ -70,6 +70,11 @@ int launch_color(const LaunchDesc &d);
 int launch_hist(const uint8_t *in, uint32_t *hist, int W, int H, int C, int n_images, hipStream_t stream);
 int launch_tone_tables(const uint32_t *hist, uint8_t *tables, int C, int n_images, const mi_blur_tone &t, hipStream_t stream);
 int launch_tables(const uint8_t *in, uint8_t *out, int W, int H, int C, int n_images, const uint8_t *tables, hipStream_t stream);
+// The two-image arithmetic (arith_kernels.hip); no Filter and no LaunchDesc either: it has more than one input.  Dense
+// images of W x H x C, n_images of them; b and m as *k's plane and shared flags say, m null unless the operation is
+// LERP.  Every argument is checked (arith_args_ok(), filter.h: MI_BLUR_ERR_INVALID), an empty batch is MI_BLUR_OK.
+int launch_arith(const uint8_t *a, const uint8_t *b, const uint8_t *m, uint8_t *out, int W, int H, int C, int n_images, const mi_blur_arith &k,
+                 hipStream_t stream);
 // Sets what last_kernel() reports for the calling thread.
 void set_last_kernel(const char *name);
 

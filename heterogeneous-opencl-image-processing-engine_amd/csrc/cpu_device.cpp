@@ -651,6 +651,43 @@ void cpu_tone(const uint8_t *in, uint8_t *out, int W, int H, int C, int n_images
     cpu_tables(in, out, W, H, C, n_images, tables, n_threads);
 }
 
+// out[i][p][c] = arith_byte(a, b, m) of the operands' bytes; a plane operand has one byte per pixel, a shared one a
+// single image.  Slices of pixels as above; the operation is a constant inside each loop.
+namespace {
+template <int OP>
+void arith_slices(const uint8_t *a, const uint8_t *b, const uint8_t *m, uint8_t *out, size_t pixels, int C, int n_images, const mi_blur_arith &k, int n_threads)
+{
+    const size_t bc = k.b_plane ? 1 : (size_t)C, mc = k.m_plane ? 1 : (size_t)C;
+    for_pixel_slices(pixels, n_images, n_threads, [&](int img, size_t p0, size_t p1) {
+        const uint8_t *pa = a + ((size_t)img * pixels + p0) * C;
+        const uint8_t *pb = b + ((k.b_shared ? 0 : (size_t)img * pixels) + p0) * bc;
+        const uint8_t *pm = OP == MI_BLUR_ARITH_LERP ? m + ((k.m_shared ? 0 : (size_t)img * pixels) + p0) * mc : nullptr;
+        uint8_t *o = out + ((size_t)img * pixels + p0) * C;
+        for (size_t n = p1 - p0; n > 0; n--, pa += C, pb += bc, o += C) {
+            for (int c = 0; c < C; c++) {
+                const int vm = OP == MI_BLUR_ARITH_LERP ? pm[k.m_plane ? 0 : c] : 0;
+                o[c] = (uint8_t)arith_byte(OP, k.wa, k.wb, k.bias, k.shift, pa[c], pb[k.b_plane ? 0 : c], vm);
+            }
+            if (OP == MI_BLUR_ARITH_LERP) pm += mc;
+        }
+    });
+}
+}  // namespace
+
+void cpu_arith(const uint8_t *a, const uint8_t *b, const uint8_t *m, uint8_t *out, int W, int H, int C, int n_images, const mi_blur_arith &k, int n_threads)
+{
+    if (n_images <= 0) return;
+    const size_t pixels = (size_t)W * H;
+    switch (k.op) {
+    case MI_BLUR_ARITH_LINEAR: return arith_slices<MI_BLUR_ARITH_LINEAR>(a, b, m, out, pixels, C, n_images, k, n_threads);
+    case MI_BLUR_ARITH_ABSDIFF: return arith_slices<MI_BLUR_ARITH_ABSDIFF>(a, b, m, out, pixels, C, n_images, k, n_threads);
+    case MI_BLUR_ARITH_MIN: return arith_slices<MI_BLUR_ARITH_MIN>(a, b, m, out, pixels, C, n_images, k, n_threads);
+    case MI_BLUR_ARITH_MAX: return arith_slices<MI_BLUR_ARITH_MAX>(a, b, m, out, pixels, C, n_images, k, n_threads);
+    case MI_BLUR_ARITH_MUL: return arith_slices<MI_BLUR_ARITH_MUL>(a, b, m, out, pixels, C, n_images, k, n_threads);
+    default: return arith_slices<MI_BLUR_ARITH_LERP>(a, b, m, out, pixels, C, n_images, k, n_threads);
+    }
+}
+
 // Synthetic stream: image i = LCG bytes, seed 0x9E3779B9 ^ i.
 void fill_synthetic(uint8_t *host, int W, int H, int C, int first_index, int n_images, int n_threads)
 {

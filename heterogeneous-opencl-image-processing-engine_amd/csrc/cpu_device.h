@@ -59,6 +59,10 @@ inline void cpu_blur_batch(const uint8_t *in, uint8_t *out, int W, int band_rows
 void cpu_hist(const uint8_t *in, uint32_t *hist, int W, int H, int C, int n_images, int n_threads);
 void cpu_tables(const uint8_t *in, uint8_t *out, int W, int H, int C, int n_images, const uint8_t *tables, int n_threads);
 void cpu_tone(const uint8_t *in, uint8_t *out, int W, int H, int C, int n_images, const mi_blur_tone &t, void *work, int n_threads);
+// The two-image arithmetic (include/mi_blur.h, "Two-image arithmetic") on n_images dense W x H x C images; the callers
+// have checked the arguments (arith_args_ok(), filter.h).  Every byte is arith_byte(); a thread reads a byte's operands
+// before it writes the byte, so out may be a, or b where b has the output's extent.
+void cpu_arith(const uint8_t *a, const uint8_t *b, const uint8_t *m, uint8_t *out, int W, int H, int C, int n_images, const mi_blur_arith &k, int n_threads);
 // planar (CImg storage: all of channel 0, then channel 1, ...) <-> interleaved, n_images frames, a few pool threads
 void cpu_repack(const uint8_t *src, uint8_t *dst, int W, int H, int C, int n_images, bool planar_to_interleaved, int n_threads);
 void copy_blocks(uint8_t *dst, size_t dst_stride, const uint8_t *src, size_t src_stride, size_t bytes, int n, int n_threads);

@@ -520,6 +520,81 @@ inline void tone_tables(const mi_blur_tone &t, const uint32_t *hist, int C, uint
     }
 }
 
+// ---- two-image arithmetic (include/mi_blur.h, "Two-image arithmetic").  The host export mi_blur_arith_value, the CPU
+// device and all three kernels take an output byte from arith_byte(); the tiled kernels call it with a constant op.
+constexpr int32_t ARITH_MAX_W = 1 << 16, ARITH_MAX_W_MUL = 1 << 10, ARITH_MAX_BIAS = 1 << 26;
+constexpr int ARITH_MAX_SHIFT = 16;
+inline bool arith_ok(const mi_blur_arith *k)
+{
+    if (!k) return false;
+    const auto flag = [](int f) { return f == 0 || f == 1; };
+    const auto within = [](int32_t v, int32_t lim) { return v >= -lim && v <= lim; };
+    if (!flag(k->b_plane) || !flag(k->b_shared) || !flag(k->m_plane) || !flag(k->m_shared)) return false;
+    if (k->op != MI_BLUR_ARITH_LERP && (k->m_plane || k->m_shared)) return false;
+    switch (k->op) {
+    case MI_BLUR_ARITH_LINEAR:
+        return within(k->wa, ARITH_MAX_W) && within(k->wb, ARITH_MAX_W) && within(k->bias, ARITH_MAX_BIAS) && k->shift >= 0 && k->shift <= ARITH_MAX_SHIFT;
+    case MI_BLUR_ARITH_ABSDIFF:
+    case MI_BLUR_ARITH_MUL:
+        return within(k->wa, k->op == MI_BLUR_ARITH_MUL ? ARITH_MAX_W_MUL : ARITH_MAX_W) && k->wb == 0 && within(k->bias, ARITH_MAX_BIAS) &&
+               k->shift >= 0 && k->shift <= ARITH_MAX_SHIFT;
+    case MI_BLUR_ARITH_MIN:
+    case MI_BLUR_ARITH_MAX:
+    case MI_BLUR_ARITH_LERP:
+        return k->wa == 0 && k->wb == 0 && k->bias == 0 && k->shift == 0;
+    default:
+        return false;
+    }
+}
+// w * v for |w| <= 2^16 and 0 <= v <= 65025.  Both fit a signed 24-bit operand; the sign extension from bit 23 changes
+// no valid w and lets the device compiler see that, so it takes v_mad_i32_i24 (v comes from bytes, which it sees itself).
+MI_BLUR_HD inline int32_t arith_mul(int32_t w, int32_t v) { return ((int32_t)((uint32_t)w << 8) >> 8) * v; }
+// floor((2 t + 255) / 510) for t = a * m + b * (255 - m) <= 65025, as (257 t + 32896) >> 16 (< 2^24 before the shift).
+MI_BLUR_HD inline int arith_lerp(int a, int b, int m) { return (arith_mul(257, arith_mul(a, m) + arith_mul(b, 255 - m)) + 32896) >> 16; }
+// The output byte of a valid struct's fields for the operand bytes a, b, m.  The shift and the clamp are color_clamp(),
+// which keeps them apart on the device.
+MI_BLUR_HD inline int arith_byte(int op, int32_t wa, int32_t wb, int32_t bias, int shift, int a, int b, int m)
+{
+    switch (op) {
+    case MI_BLUR_ARITH_LINEAR: return color_clamp(arith_mul(wa, a) + arith_mul(wb, b) + bias, shift);
+    case MI_BLUR_ARITH_ABSDIFF: return color_clamp(arith_mul(wa, a > b ? a - b : b - a) + bias, shift);
+    case MI_BLUR_ARITH_MIN: return a < b ? a : b;
+    case MI_BLUR_ARITH_MAX: return a > b ? a : b;
+    case MI_BLUR_ARITH_MUL: return color_clamp(arith_mul(wa, arith_mul(a, b)) + bias, shift);
+    default: return arith_lerp(a, b, m);
+    }
+}
+// The flags as the launches see them: a plane of a one-channel image is a full operand, a shared operand of one image
+// is its own.
+inline mi_blur_arith arith_normalised(const mi_blur_arith &k, int C, int n_images)
+{
+    mi_blur_arith r = k;
+    if (C == 1) r.b_plane = r.m_plane = 0;
+    if (n_images <= 1) r.b_shared = r.m_shared = 0;
+    return r;
+}
+// Bytes of one image of an operand and of the whole operand.
+inline long long arith_image_bytes(int W, int H, int C, int plane) { return (long long)W * H * (plane ? 1 : C); }
+inline long long arith_operand_bytes(int W, int H, int C, int n_images, int plane, int shared) { return arith_image_bytes(W, H, C, plane) * (shared ? 1 : n_images); }
+// "Aliasing": the output may be A, and B where B has the output's extent; no other overlap with an operand.
+inline bool arith_alias_ok(const uint8_t *a, const uint8_t *b, const uint8_t *m, const uint8_t *out, int W, int H, int C, int n_images, const mi_blur_arith &k)
+{
+    const mi_blur_arith q = arith_normalised(k, C, n_images);
+    const uintptr_t o0 = (uintptr_t)out, ob = (uintptr_t)arith_operand_bytes(W, H, C, n_images, 0, 0);
+    const auto apart = [&](const uint8_t *p, long long bytes) { return (uintptr_t)p + (uintptr_t)bytes <= o0 || o0 + ob <= (uintptr_t)p; };
+    if (ob == 0) return true;
+    if (a != out && !apart(a, (long long)ob)) return false;
+    if (!(b == out && !q.b_plane && !q.b_shared) && !apart(b, arith_operand_bytes(W, H, C, n_images, q.b_plane, q.b_shared))) return false;
+    return !m || apart(m, arith_operand_bytes(W, H, C, n_images, q.m_plane, q.m_shared));
+}
+// Every argument of the three entry points but the device: the pointers, the image, the struct and the aliasing.
+inline bool arith_args_ok(const uint8_t *a, const uint8_t *b, const uint8_t *m, const uint8_t *out, int W, int H, int C, int n_images, const mi_blur_arith *k)
+{
+    if (!a || !b || !out || n_images < 0 || !arith_ok(k) || !hist_image_ok(W, H, C)) return false;
+    if ((k->op == MI_BLUR_ARITH_LERP) != (m != nullptr)) return false;
+    return arith_alias_ok(a, b, m, out, W, H, C, n_images, *k);
+}
+
 // Output size of a decimation of a W x H image: kept columns / rows (> 0 for a valid decimation, down_ok()).
 inline int down_cols(int W, int sx, int ox) { return (W - ox + sx - 1) / sx; }
 inline int down_rows(int H, int sy, int oy) { return (H - oy + sy - 1) / sy; }
@@ -975,5 +1050,19 @@ inline int hist_runs(int W, int H) { return (int)(((long long)W * H / COLOR_GROU
 // counters, and that row takes about one flush per 16 ns whoever sends it (profiles/r19_hist.md).
 constexpr int HIST_IMAGE_BLOCKS = 256;
 inline int hist_blocks(int W, int H) { const int r = hist_runs(W, H); return r < HIST_IMAGE_BLOCKS ? r : HIST_IMAGE_BLOCKS; }
+
+// ---- blur_arith_flat_kernel: the flat rule one step flatter.  With every operand at the image's channel count the
+// operation is bytewise, so an image is the run of its W * H * C bytes cut into chunks of ARITH_CHUNK bytes and the
+// channel count does not enter: W * H * C a multiple of ARITH_CHUNK, 16-byte aligned pointers.  A thread owns one chunk,
+// a workgroup of ARITH_THREADS threads a run of ARITH_RUN consecutive chunks of one image.
+// blur_arith_plane_kernel (a one-channel operand on an image of 2..4 channels): the colour kernel's rule and units, one
+// thread per group of COLOR_GROUP pixels, a workgroup per run of ARITH_PLANE_RUN groups.
+constexpr int ARITH_CHUNK = 16;
+constexpr int ARITH_THREADS = 256;
+constexpr int ARITH_RUN = 256;                      // chunks per workgroup = its threads
+constexpr int ARITH_PLANE_RUN = 256;                // groups per workgroup = its threads
+inline bool arith_flat_ok(int W, int H, int C) { return (long long)W * H * C % ARITH_CHUNK == 0; }
+inline long long arith_flat_runs(int W, int H, int C) { return ((long long)W * H * C / ARITH_CHUNK + ARITH_RUN - 1) / ARITH_RUN; }
+inline long long arith_plane_runs(int W, int H) { return ((long long)W * H / COLOR_GROUP + ARITH_PLANE_RUN - 1) / ARITH_PLANE_RUN; }
 
 }  // namespace mi_blur

@@ -2468,6 +2468,83 @@ extern "C" int mi_blur_run_tone(int device, const uint8_t *host_in, uint8_t *hos
     return MI_BLUR_OK;
 }
 
+// ----------------------------------------------------------------------------------
+// two-image arithmetic (no reference analogue).  Not a FilterKind either: a context has one input stream.  The same
+// order as the histogram family: all arguments (arith_args_ok(), filter.h), the empty batch, the device.
+// ----------------------------------------------------------------------------------
+extern "C" int mi_blur_arith_preset(int preset, mi_blur_arith *k)
+{
+    static const struct { int op; int32_t wa, wb, bias; int shift; } PRESETS[] = {
+        {MI_BLUR_ARITH_LINEAR, 1, 1, 0, 0},   {MI_BLUR_ARITH_LINEAR, 1, -1, 0, 0}, {MI_BLUR_ARITH_LINEAR, 1, 1, 1, 1},
+        {MI_BLUR_ARITH_LINEAR, 1, -1, 128, 0}, {MI_BLUR_ARITH_ABSDIFF, 1, 0, 0, 0}, {MI_BLUR_ARITH_MIN, 0, 0, 0, 0},
+        {MI_BLUR_ARITH_MAX, 0, 0, 0, 0},      {MI_BLUR_ARITH_MUL, 257, 0, 32896, 16}, {MI_BLUR_ARITH_MUL, 1, 0, 64, 7},
+        {MI_BLUR_ARITH_LERP, 0, 0, 0, 0}};
+    if (!k || preset < 0 || preset > MI_BLUR_ARITH_PRESET_LERP) return MI_BLUR_ERR_INVALID;
+    *k = mi_blur_arith{PRESETS[preset].op, PRESETS[preset].wa, PRESETS[preset].wb, PRESETS[preset].bias, PRESETS[preset].shift, 0, 0, 0, 0};
+    return MI_BLUR_OK;
+}
+
+extern "C" int mi_blur_arith_weighted(double alpha, double beta, double gamma, mi_blur_arith *k)
+{
+    if (!k || !std::isfinite(alpha) || !std::isfinite(beta) || !std::isfinite(gamma)) return MI_BLUR_ERR_INVALID;
+    if (std::fabs(alpha) > 16.0 || std::fabs(beta) > 16.0 || std::fabs(gamma) > 8192.0) return MI_BLUR_ERR_INVALID;
+    const auto q12 = [](double v) { return (int32_t)std::floor(v * 4096.0 + 0.5); };
+    *k = mi_blur_arith{MI_BLUR_ARITH_LINEAR, q12(alpha), q12(beta), q12(gamma) + 2048, 12, 0, 0, 0, 0};
+    return MI_BLUR_OK;
+}
+
+extern "C" int mi_blur_arith_value(const mi_blur_arith *k, int a, int b, int m)
+{
+    if (!arith_ok(k) || a < 0 || a > 255 || b < 0 || b > 255) return -1;
+    if (k->op != MI_BLUR_ARITH_LERP) m = 0;
+    if (m < 0 || m > 255) return -1;
+    return arith_byte(k->op, k->wa, k->wb, k->bias, k->shift, a, b, m);
+}
+
+extern "C" int mi_blur_enqueue_arith(const uint8_t *d_a, const uint8_t *d_b, const uint8_t *d_m, uint8_t *d_out, int width, int height,
+                                     int channels, int n_images, const mi_blur_arith *k, void *stream)
+{
+    if (!arith_args_ok(d_a, d_b, d_m, d_out, width, height, channels, n_images, k)) return MI_BLUR_ERR_INVALID;
+    if (n_images == 0) return MI_BLUR_OK;
+    if (mi_blur_device_count() <= 0) return MI_BLUR_ERR_NO_DEVICE;
+    return launch_arith(d_a, d_b, d_m, d_out, width, height, channels, n_images, *k, (hipStream_t)stream);
+}
+
+extern "C" int mi_blur_cpu_run_arith(const uint8_t *a, const uint8_t *b, const uint8_t *m, uint8_t *out, int width, int height, int channels,
+                                     int n_images, const mi_blur_arith *k, int n_threads)
+{
+    if (!arith_args_ok(a, b, m, out, width, height, channels, n_images, k)) return MI_BLUR_ERR_INVALID;
+    cpu_arith(a, b, m, out, width, height, channels, n_images, *k, n_threads);
+    return MI_BLUR_OK;
+}
+
+extern "C" int mi_blur_run_arith(int device, const uint8_t *host_a, const uint8_t *host_b, const uint8_t *host_m, uint8_t *host_out, int width,
+                                 int height, int channels, int n_images, const mi_blur_arith *k)
+{
+    if (device == MI_BLUR_DEVICE_CPU) return mi_blur_cpu_run_arith(host_a, host_b, host_m, host_out, width, height, channels, n_images, k, 0);
+    if (!arith_args_ok(host_a, host_b, host_m, host_out, width, height, channels, n_images, k)) return MI_BLUR_ERR_INVALID;
+    if (n_images == 0) return MI_BLUR_OK;
+    if (const int rc = use_device(device)) return rc;
+    const size_t bytes = (size_t)arith_operand_bytes(width, height, channels, n_images, 0, 0);
+    const size_t b_bytes = (size_t)arith_operand_bytes(width, height, channels, n_images, k->b_plane, k->b_shared);      // a shared operand: one image
+    const size_t m_bytes = host_m ? (size_t)arith_operand_bytes(width, height, channels, n_images, k->m_plane, k->m_shared) : 0;
+    DeviceBuffer a, b, m, out;
+    HIP_TRY(a.alloc(bytes));
+    HIP_TRY(b.alloc(b_bytes));
+    HIP_TRY(out.alloc(bytes));
+    HIP_TRY(hipMemcpy(a.p, host_a, bytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b.p, host_b, b_bytes, hipMemcpyHostToDevice));
+    if (host_m) {
+        HIP_TRY(m.alloc(m_bytes));
+        HIP_TRY(hipMemcpy(m.p, host_m, m_bytes, hipMemcpyHostToDevice));
+    }
+    if (const int rc = launch_arith(static_cast<const uint8_t *>(a.p), static_cast<const uint8_t *>(b.p), static_cast<const uint8_t *>(m.p),
+                                    static_cast<uint8_t *>(out.p), width, height, channels, n_images, *k, nullptr))
+        return rc;
+    HIP_TRY(hipMemcpy(host_out, out.p, bytes, hipMemcpyDeviceToHost));               // on the null stream: behind the kernel
+    return MI_BLUR_OK;
+}
+
 extern "C" void mi_blur_fill_synthetic(uint8_t *host, int width, int height, int channels, int first_index,
                                        int n_images, int n_threads)
 {

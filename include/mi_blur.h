@@ -73,7 +73,8 @@ int mi_blur_version(void);
  * "blur_warp_persp_tiled_kernel", "blur_warp_persp_generic_kernel", "blur_remap_tiled_kernel",
  * "blur_remap_generic_kernel", "blur_area_tiled_kernel", "blur_area_generic_kernel", "blur_color_tiled_kernel",
  * "blur_color_generic_kernel", "blur_hist_tiled_kernel", "blur_hist_generic_kernel", "blur_tone_table_kernel",
- * "blur_tables_tiled_kernel", "blur_tables_generic_kernel"; "" before the first):
+ * "blur_tables_tiled_kernel", "blur_tables_generic_kernel", "blur_arith_flat_kernel", "blur_arith_plane_kernel",
+ * "blur_arith_generic_kernel"; "" before the first):
  * reports name the kernel a profiler will show.  Static string, never NULL. */
 const char *mi_blur_last_kernel(void);
 
@@ -772,6 +773,99 @@ int mi_blur_cpu_run_tone(const uint8_t *in, uint8_t *out, int width, int height,
 int mi_blur_run_hist(int device, const uint8_t *host_in, uint32_t *host_hist, int width, int height, int channels, int n_images);
 int mi_blur_run_tone(int device, const uint8_t *host_in, uint8_t *host_out, void *host_work /* may be NULL */,
                      int width, int height, int channels, int n_images, const mi_blur_tone *t);
+
+/* ------------------------------------------------------------------------
+ * Two-image arithmetic: add, subtract, absolute difference, weighted sum, min / max, multiply and the blend through a
+ * mask (no reference analogue).  The first operation here with more than one image per output image.  Integers only,
+ * rounded once, so the GPU, the CPU device and a numpy restatement agree byte for byte.  Like the histogram family it is
+ * not a filter of a context (a context has one input stream): nothing here goes through contexts, slots or the batch
+ * server.
+ *
+ * Operands.  A: n_images interleaved dense images of width x height x channels, channels 1..4, within the histogram
+ * family's limits (width, height <= MI_BLUR_RESIZE_MAX_DIM; width*channels <= INT_MAX/2; width*height*channels <=
+ * INT_MAX).  B: the same width x height with (b_plane ? 1 : channels) channels, (b_shared ? 1 : n_images) images.
+ * M, the mask: present only for MI_BLUR_ARITH_LERP; m_plane and m_shared as for B.  Output: n_images images like A's.
+ * For output byte (i, p, c) (image, pixel, channel):
+ *     a = A[i][p][c],   b = B[b_shared ? 0 : i][p][b_plane ? 0 : c],   m = M[m_shared ? 0 : i][p][m_plane ? 0 : c].
+ * A shared operand is the one background, gain image or watermark of a whole batch; a plane operand is a grey mask or
+ * weight applied to every channel.  Image offsets are 64-bit.
+ *
+ * Operations (all int32; >> is arithmetic, so it floors; clamp is to 0..255):
+ *   LINEAR   clamp((wa*a + wb*b + bias) >> shift)        |wa|, |wb| <= 2^16; |bias| <= 2^26
+ *   ABSDIFF  clamp((wa*|a - b| + bias) >> shift)         wb = 0; |wa| <= 2^16; |bias| <= 2^26
+ *   MIN, MAX min(a, b), max(a, b)                        wa, wb, bias, shift all 0
+ *   MUL      clamp((wa*a*b + bias) >> shift)             wb = 0; |wa| <= 2^10; |bias| <= 2^26
+ *   LERP     floor((2*(a*m + b*(255 - m)) + 255) / 510)  wa, wb, bias, shift all 0; M required
+ * shift is 0..16 wherever it is not required to be 0.  Every sum stays below 2^27 and every multiplicand fits a signed
+ * 24-bit operand.  LERP is the convex blend with one rounding, half up: m = 255 gives a, m = 0 gives b.  For every
+ * t in 0..65025, floor((2t + 255) / 510) == (257*t + 32896) >> 16, which is the form the code uses.
+ * The plane and shared flags are 0 or 1; m_plane and m_shared are 0 unless the operation is LERP.  Any other field
+ * value is MI_BLUR_ERR_INVALID, the output untouched.
+ *
+ * Presets (mi_blur_arith_preset; plane and shared flags 0):          op       wa   wb  bias   shift
+ *   ADD                                                              LINEAR    1    1     0      0
+ *   SUB                                                              LINEAR    1   -1     0      0
+ *   AVG       (a + b + 1) >> 1                                       LINEAR    1    1     1      1
+ *   DIFF128   the signed difference around grey                      LINEAR    1   -1   128      0
+ *   ABSDIFF                                                          ABSDIFF   1    0     0      0
+ *   MIN, MAX                                                         MIN, MAX  0    0     0      0
+ *   MUL255    a*b/255 rounded once (the identity above)              MUL     257    0 32896     16
+ *   MULQ7     a gain image, 128 = unity, saturating                  MUL       1    0    64      7
+ *   LERP                                                             LERP      0    0     0      0
+ *
+ * Aliasing.  d_out == d_a is allowed (the running accumulator).  d_out == d_b is allowed when B has the output's
+ * extent: not plane (or channels == 1) and not shared (or n_images <= 1).  Any other overlap of the output's byte
+ * range with an operand's range is MI_BLUR_ERR_INVALID, any overlap with M included.  Every implementation reads the
+ * bytes a thread owns before it writes them, so the allowed cases are exact.
+ * ---------------------------------------------------------------------- */
+typedef enum { MI_BLUR_ARITH_LINEAR = 0, MI_BLUR_ARITH_ABSDIFF = 1, MI_BLUR_ARITH_MIN = 2,
+               MI_BLUR_ARITH_MAX = 3, MI_BLUR_ARITH_MUL = 4, MI_BLUR_ARITH_LERP = 5 } mi_blur_arith_op;
+typedef struct mi_blur_arith {
+    int op;                 /* mi_blur_arith_op */
+    int32_t wa, wb, bias;   /* see the table above */
+    int shift;              /* 0..16, arithmetic (floors) */
+    int b_plane, b_shared;  /* 0 | 1 */
+    int m_plane, m_shared;  /* LERP only; otherwise must be 0 */
+} mi_blur_arith;
+typedef enum mi_blur_arith_preset_id {
+    MI_BLUR_ARITH_ADD = 0, MI_BLUR_ARITH_SUB = 1, MI_BLUR_ARITH_AVG = 2, MI_BLUR_ARITH_DIFF128 = 3,
+    MI_BLUR_ARITH_PRESET_ABSDIFF = 4, MI_BLUR_ARITH_PRESET_MIN = 5, MI_BLUR_ARITH_PRESET_MAX = 6,
+    MI_BLUR_ARITH_MUL255 = 7, MI_BLUR_ARITH_MULQ7 = 8, MI_BLUR_ARITH_PRESET_LERP = 9
+} mi_blur_arith_preset_id;
+
+/* *k = the preset; MI_BLUR_ERR_INVALID for another id or a null k. */
+int mi_blur_arith_preset(int preset, mi_blur_arith *k);
+/* OpenCV's addWeighted in Q12: LINEAR with wa = floor(alpha*4096 + 0.5), wb = floor(beta*4096 + 0.5),
+ * bias = floor(gamma*4096 + 0.5) + 2048, shift 12.  |alpha|, |beta| <= 16, |gamma| <= 8192; anything else, a
+ * non-finite value or a null k is MI_BLUR_ERR_INVALID. */
+int mi_blur_arith_weighted(double alpha, double beta, double gamma, mi_blur_arith *k);
+/* The definition for one byte (host only): the output byte for operand bytes a, b and m (m is ignored unless the
+ * operation is LERP); -1 for an invalid *k or an operand outside 0..255. */
+int mi_blur_arith_value(const mi_blur_arith *k, int a, int b, int m);
+
+/* out = A op B on device memory, asynchronous on `stream`.  d_m: the mask, NULL unless the operation is LERP.
+ * n_images == 0 is MI_BLUR_OK.  MI_BLUR_ERR_INVALID (every argument is checked before a device is asked for, so before
+ * MI_BLUR_ERR_NO_DEVICE): a null d_a, d_b, d_out or k; d_m null with LERP or non-null without it; channels outside
+ * 1..4; a size outside the limits; n_images < 0; an invalid *k; an overlap that "Aliasing" above does not allow.  *k is
+ * copied into the kernel arguments: it need not outlive the call.
+ * Which kernel takes a launch (mi_blur_last_kernel() says which one ran); plane flags with channels == 1 count as 0:
+ *   blur_arith_flat_kernel: no plane flag, width*height*channels a multiple of 16, every pointer 16-byte aligned.  The
+ *     operation is bytewise, so an image is a flat run of bytes: a thread owns one chunk of 16 bytes (one 16-byte load per
+ *     operand, one store), a workgroup a run of 256 consecutive chunks of one image.
+ *   blur_arith_plane_kernel: channels 2..4, at least one plane flag, width*height a multiple of 16, every pointer
+ *     16-byte aligned.  A thread owns a group of 16 pixels: `channels` chunks of every full operand, one chunk of every
+ *     plane operand, `channels` stores.
+ *   blur_arith_generic_kernel: everything else, one output byte per thread. */
+int mi_blur_enqueue_arith(const uint8_t *d_a, const uint8_t *d_b, const uint8_t *d_m /* NULL unless LERP */, uint8_t *d_out,
+                          int width, int height, int channels, int n_images, const mi_blur_arith *k, void *stream);
+/* The same on the CPU device's threads (synchronous), host memory. */
+int mi_blur_cpu_run_arith(const uint8_t *a, const uint8_t *b, const uint8_t *m /* NULL unless LERP */, uint8_t *out,
+                          int width, int height, int channels, int n_images, const mi_blur_arith *k, int n_threads);
+/* Blocking, host memory in and out: allocate on `device` (a HIP ordinal), copy in (a shared operand once), enqueue, copy
+ * out, free.  device == MI_BLUR_DEVICE_CPU calls the cpu_run form with all threads.  MI_BLUR_ERR_NO_DEVICE where there is
+ * no such device, after the argument checks. */
+int mi_blur_run_arith(int device, const uint8_t *host_a, const uint8_t *host_b, const uint8_t *host_m /* NULL unless LERP */,
+                      uint8_t *host_out, int width, int height, int channels, int n_images, const mi_blur_arith *k);
 
 /* ------------------------------------------------------------------------
  * Affine warp: exact fixed-point rotate, scale, shear and translate, any output size (no reference analogue).  The
