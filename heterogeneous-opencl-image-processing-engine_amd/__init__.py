@@ -54,6 +54,8 @@ HIST_BINS = 256
 TONE_EQUALIZE, TONE_STRETCH = 0, 1
 TONE_MODES = {"equalize": TONE_EQUALIZE, "stretch": TONE_STRETCH}
 ARITH_LINEAR, ARITH_ABSDIFF, ARITH_MIN, ARITH_MAX, ARITH_MUL, ARITH_LERP = range(6)
+BOX_MEAN, BOX_STDDEV, BOX_THRESHOLD = range(3)
+BOX_MAX_RADIUS = 127
 ARITH_PRESETS = {"add": 0, "sub": 1, "avg": 2, "diff128": 3, "absdiff": 4, "min": 5, "max": 6, "mul255": 7, "mulq7": 8, "lerp": 9}
 WARP_Q = 16
 WARP_CLAMP, WARP_CONSTANT = 0, 1
@@ -70,7 +72,7 @@ def _newer(target: str, sources: list[str]) -> bool:
 
 def build_native(force: bool = False, verbose: bool = False) -> str:
     """Compile libmi_blur.so (hipcc, --offload-arch=gfx950) and the C++ hosts, in-tree."""
-    srcs = [os.path.join(CSRC, f) for f in ("blur_kernels.hip", "sep_kernels.hip", "median_kernels.hip", "morph_kernels.hip", "bilateral_kernels.hip", "conv_kernels.hip", "sep_down_kernels.hip", "resize_kernels.hip", "warp_kernels.hip", "remap_kernels.hip", "area_kernels.hip", "color_kernels.hip", "hist_kernels.hip", "arith_kernels.hip", "layout_kernels.hip", "mi_blur_api.cpp", "comm_api.cpp", "cpu_device.cpp")]
+    srcs = [os.path.join(CSRC, f) for f in ("blur_kernels.hip", "sep_kernels.hip", "median_kernels.hip", "morph_kernels.hip", "bilateral_kernels.hip", "conv_kernels.hip", "sep_down_kernels.hip", "resize_kernels.hip", "warp_kernels.hip", "remap_kernels.hip", "area_kernels.hip", "color_kernels.hip", "hist_kernels.hip", "arith_kernels.hip", "integral_kernels.hip", "layout_kernels.hip", "mi_blur_api.cpp", "comm_api.cpp", "cpu_device.cpp")]
     deps = srcs + [os.path.join(CSRC, f) for f in ("api_internal.h", "blur_launch.h", "kernel_common.h", "cpu_device.h", "filter.h")] + [HEADER]
     if force or not _newer(LIB_PATH, deps):
         cmd = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra",
@@ -261,6 +263,12 @@ class Arith(C.Structure):
     of the mask (include/mi_blur.h, "Two-image arithmetic")."""
     _fields_ = [("op", C.c_int), ("wa", C.c_int32), ("wb", C.c_int32), ("bias", C.c_int32), ("shift", C.c_int),
                 ("b_plane", C.c_int), ("b_shared", C.c_int), ("m_plane", C.c_int), ("m_shared", C.c_int)]
+
+
+class Box(C.Structure):
+    """mi_blur_box: the operation (BOX_MEAN | BOX_STDDEV | BOX_THRESHOLD), the radii of the (2 rx + 1) x (2 ry + 1) window
+    and, for BOX_THRESHOLD only, the offset (-255..255) and invert (include/mi_blur.h, "Integral images, and box filters")."""
+    _fields_ = [("op", C.c_int), ("rx", C.c_int), ("ry", C.c_int), ("offset", C.c_int), ("invert", C.c_int)]
 
 
 class Warp(C.Structure):
@@ -455,6 +463,16 @@ def lib() -> C.CDLL:
         "mi_blur_enqueue_arith": (i, [u8p, u8p, u8p, u8p, i, i, i, i, C.POINTER(Arith), vp]),
         "mi_blur_cpu_run_arith": (i, [u8p, u8p, u8p, u8p, i, i, i, i, C.POINTER(Arith), i]),
         "mi_blur_run_arith": (i, [i, u8p, u8p, u8p, u8p, i, i, i, i, C.POINTER(Arith)]),
+        "mi_blur_box_value": (i, [C.POINTER(Box), i, C.c_uint32, C.c_uint32, i]),
+        "mi_blur_integral_work_bytes": (C.c_size_t, [i, i, i, i, i]),
+        "mi_blur_enqueue_integral": (i, [u8p, vp, vp, i, i, i, i, vp, vp]),
+        "mi_blur_cpu_run_integral": (i, [u8p, vp, vp, i, i, i, i, i]),
+        "mi_blur_enqueue_box_from_integral": (i, [u8p, vp, vp, u8p, i, i, i, i, C.POINTER(Box), vp]),
+        "mi_blur_box_work_bytes": (C.c_size_t, [i, i, i, i, C.POINTER(Box)]),
+        "mi_blur_enqueue_box": (i, [u8p, u8p, i, i, i, i, C.POINTER(Box), vp, vp]),
+        "mi_blur_cpu_run_box": (i, [u8p, u8p, i, i, i, i, C.POINTER(Box), i]),
+        "mi_blur_run_integral": (i, [i, u8p, vp, vp, i, i, i, i]),
+        "mi_blur_run_box": (i, [i, u8p, u8p, i, i, i, i, C.POINTER(Box)]),
         "mi_blur_warp_coord": (i, [C.POINTER(Warp), i, i, C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i)]),
         "mi_blur_warp_rotation": (i, [C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double)]),
         "mi_blur_warp_set_matrix": (i, [C.POINTER(Warp), C.POINTER(C.c_double), i]),
@@ -1263,6 +1281,83 @@ def auto_levels(images, clip=0.0, joint: bool = True, channels=None, device: int
     t = _tone("stretch", _clip_q16(clip, "auto_levels"), joint, channels, a.shape[3], "auto_levels")
     out = _tone_run(a, t, device, batch, "auto_levels")
     return out if rank == 4 else out[0] if rank == 3 else out[0, :, :, 0]
+
+
+def integral(images, square: bool = False, pad: bool = False, device: int = 0, batch: int = 0):
+    """The integral image of every image and channel (mi_blur_run_integral; include/mi_blur.h, "Integral images, and box
+    filters", has the definition): uint32 of the images' own shape, entry (y, x) = the sum over rows <= y and columns <= x,
+    modulo 2^32.  square=True: of the squares instead.  pad=True: OpenCV's layout, one row and one column of zeros in
+    front, (H + 1) x (W + 1), padded on the host.  device: HIP ordinal, or DEVICE_CPU; batch: images per call (0 = all)."""
+    import numpy as np
+    a, rank = _tone_stack(images, "integral")
+    n, h, w, c = a.shape
+    out = np.empty((n, h, w, c), np.uint32)
+    per = batch if batch > 0 else max(n, 1)
+    for i in range(0, n, per):
+        t = out[i:].ctypes.data
+        check(lib().mi_blur_run_integral(device, a[i:].ctypes.data, None if square else t, t if square else None, w, h, c, min(per, n - i)),
+              "mi_blur_run_integral")
+    if pad:
+        out = np.pad(out, ((0, 0), (1, 0), (1, 0), (0, 0)))
+    return out if rank == 4 else out[0] if rank == 3 else out[0, :, :, 0]
+
+
+def rect_sum(table, x0: int, y0: int, x1: int, y1: int):
+    """The sum over columns x0..x1 and rows y0..y1 (inclusive) from a table of integral() (pad=False), modulo 2^32: exact
+    whenever the true sum is below 2^32.  table: (..., H, W) for grey images or (..., H, W, C); numpy only."""
+    import numpy as np
+    t = np.asarray(table)
+    if t.dtype != np.uint32 or t.ndim < 2:
+        raise ValueError("rect_sum: table is a uint32 array from integral()")
+    grey = t.ndim == 2
+    if grey:
+        t = t[:, :, None]
+    h, w = t.shape[-3], t.shape[-2]
+    if not (0 <= x0 <= x1 < w and 0 <= y0 <= y1 < h):
+        raise ValueError("rect_sum: 0 <= x0 <= x1 < W and 0 <= y0 <= y1 < H")
+    at = lambda y, x: t[..., y, x, :] if x >= 0 and y >= 0 else np.zeros(t.shape[:-3] + t.shape[-1:], np.uint32)
+    s = at(y1, x1) - at(y0 - 1, x1) - at(y1, x0 - 1) + at(y0 - 1, x0 - 1)          # uint32: wraps, as the definition says
+    return s[..., 0] if grey else s
+
+
+def _box(ksize, op: int, offset: int, invert: bool, name: str) -> "Box":
+    pair = tuple(ksize) if isinstance(ksize, (tuple, list)) else (ksize, ksize)
+    kx, ky = pair if len(pair) == 2 else (0, 0)
+    for k in (kx, ky):
+        if not isinstance(k, int) or k < 1 or k % 2 == 0 or k > 2 * BOX_MAX_RADIUS + 1:
+            raise ValueError(f"{name}: ksize is an odd integer 1..{2 * BOX_MAX_RADIUS + 1}, or a pair (kx, ky) of them")
+    if not -255 <= int(offset) <= 255:
+        raise ValueError(f"{name}: offset is -255..255")
+    return Box(op, kx // 2, ky // 2, int(offset), int(bool(invert)))
+
+
+def _box_run(images, k: "Box", device: int, batch: int, name: str):
+    import numpy as np
+    a, rank = _tone_stack(images, name)
+    n, h, w, c = a.shape
+    out = np.empty_like(a)
+    per = batch if batch > 0 else max(n, 1)
+    for i in range(0, n, per):
+        check(lib().mi_blur_run_box(device, a[i:].ctypes.data, out[i:].ctypes.data, w, h, c, min(per, n - i), C.byref(k)), "mi_blur_run_box")
+    return out if rank == 4 else out[0] if rank == 3 else out[0, :, :, 0]
+
+
+def box_blur(images, ksize, device: int = 0, batch: int = 0):
+    """The box mean over a kx x ky window (mi_blur_run_box, BOX_MEAN), clamp-to-edge, rounded once, half up; numpy in ->
+    numpy out of the same shape.  ksize: an odd int or (kx, ky), each at most 255.  The cost does not depend on the window."""
+    return _box_run(images, _box(ksize, BOX_MEAN, 0, False, "box_blur"), device, batch, "box_blur")
+
+
+def local_stddev(images, ksize, device: int = 0, batch: int = 0):
+    """The standard deviation over a kx x ky window (BOX_STDDEV), clamp-to-edge, rounded once, half up: 0..128."""
+    return _box_run(images, _box(ksize, BOX_STDDEV, 0, False, "local_stddev"), device, batch, "local_stddev")
+
+
+def adaptive_threshold(images, ksize, offset: int = 0, invert: bool = False, device: int = 0, batch: int = 0):
+    """The adaptive threshold (BOX_THRESHOLD): 255 where a pixel exceeds the mean of its kx x ky window minus `offset`
+    (the mean not rounded), else 0; invert swaps the two.  OpenCV's adaptiveThreshold with ADAPTIVE_THRESH_MEAN_C and
+    C = offset, but not its bytes, which round the mean first."""
+    return _box_run(images, _box(ksize, BOX_THRESHOLD, offset, invert, "adaptive_threshold"), device, batch, "adaptive_threshold")
 
 
 def arith_preset(name) -> "Arith":

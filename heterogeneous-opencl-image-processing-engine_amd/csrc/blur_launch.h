@@ -75,6 +75,14 @@ int launch_tables(const uint8_t *in, uint8_t *out, int W, int H, int C, int n_im
 // LERP.  Every argument is checked (arith_args_ok(), filter.h: MI_BLUR_ERR_INVALID), an empty batch is MI_BLUR_OK.
 int launch_arith(const uint8_t *a, const uint8_t *b, const uint8_t *m, uint8_t *out, int W, int H, int C, int n_images, const mi_blur_arith &k,
                  hipStream_t stream);
+// The integral images and the box filters made from them (integral_kernels.hip); no Filter and no LaunchDesc.  Dense
+// images of W x H x C, n_images of them; every argument is checked (integral_args_ok(), box_from_args_ok(), filter.h:
+// MI_BLUR_ERR_INVALID), an empty batch is MI_BLUR_OK.  launch_integral: sum and / or sqsum = uint32[n][H][W][C], 16-byte
+// aligned; work = integral_work_bytes() bytes for the band in force (tunables().integral_band), 16-byte aligned.
+// launch_box_from_integral: in only for THRESHOLD, sqsum only for STDDEV.
+int launch_integral(const uint8_t *in, uint32_t *sum, uint32_t *sqsum, int W, int H, int C, int n_images, void *work, hipStream_t stream);
+int launch_box_from_integral(const uint8_t *in, const uint32_t *sum, const uint32_t *sqsum, uint8_t *out, int W, int H, int C, int n_images,
+                             const mi_blur_box &k, hipStream_t stream);
 // Sets what last_kernel() reports for the calling thread.
 void set_last_kernel(const char *name);
 
@@ -207,6 +215,8 @@ struct Tunables {
                          // wrap of its batch and tile numbers — 80 minutes into a continuous batch-35 stream — happens at once (0 = off)
     int zero_copy_events; // zero-copy submits: 1 = the dispatch carries start/stop timestamp events (kernel bucket + completion),
                          // 0 = plain launch, completion by stream synchronise (timing experiment: no kernel bucket)
+    int integral_band;   // blur_integral_tiled_kernel: rows per band (default INTEGRAL_BAND of filter.h; A/B runs)
+    int box_bytes;       // blur_box_tiled_kernel: consecutive output bytes of a row per thread, 4 (default) | 16 (A/B runs)
 };
 // Every knob once: its mi_blur_set_option key, its field, what values it takes, its default and the environment variable
 // (or nullptr) that may replace the default when the library starts.  FLAG: any value, stored as 0 | 1.  RANGE: lo .. hi.
@@ -251,6 +261,8 @@ static constexpr Knob KNOBS[] = {
     {"zero_copy_idle_us", &Tunables::zero_copy_idle_us, KnobKind::RANGE, 10, 100000, 300, nullptr},
     {"zero_copy_budget", &Tunables::zero_copy_budget, KnobKind::RANGE, 1, 1 << 20, 256, nullptr},
     {"xcd_run", &Tunables::xcd_run, KnobKind::RANGE, 0, 1 << 20, 0, nullptr},
+    {"integral_band", &Tunables::integral_band, KnobKind::RANGE, 1, 256, 16, nullptr},    // the default is INTEGRAL_BAND of filter.h
+    {"box_bytes", &Tunables::box_bytes, KnobKind::ONE_OF, knob_bits(4, 16, 4, 16), 0, 4, nullptr},
 };
 // Stores `value` in the knob's field of t if the knob accepts it; false (t untouched) otherwise.
 static inline bool knob_set(const Knob &k, Tunables &t, int value)

@@ -688,6 +688,105 @@ void cpu_arith(const uint8_t *a, const uint8_t *b, const uint8_t *m, uint8_t *ou
     }
 }
 
+// Integral images: items are (image, band of rows), about four per thread and at least 16 rows a band.
+namespace {
+template <typename F>
+void for_items(long long items, int n_threads, F &&body)
+{
+    std::atomic<long long> next{0};
+    Pool::get().run((int)std::min<long long>(n_threads, items), [&](int) {
+        for (;;) {
+            const long long it = next.fetch_add(1, std::memory_order_relaxed);
+            if (it >= items) break;
+            body(it);
+        }
+    });
+}
+}  // namespace
+
+bool cpu_integral(const uint8_t *in, uint32_t *sum, uint32_t *sqsum, int W, int H, int C, int n_images, int n_threads)
+{
+    if (n_images <= 0) return true;
+    if (n_threads <= 0) n_threads = hardware_threads();
+    const size_t row_e = (size_t)W * C;
+    const int want = std::max(1, std::min(std::max(1, H / 16), (4 * n_threads + n_images - 1) / n_images));
+    const int band = (H + want - 1) / want, nb = (H + band - 1) / band;
+    uint32_t *const tab[2] = {sum ? sum : sqsum, sum ? sqsum : nullptr};
+    const bool squares[2] = {!sum, true};
+    const int nt = tab[1] ? 2 : 1;
+    // carry[image][band][table][W * C]: first the column sums of the band, then S (or Q) of the row above the band
+    std::vector<uint32_t> carry;
+    try { carry.assign((size_t)n_images * nb * nt * row_e, 0u); } catch (...) { return false; }
+    const long long items = (long long)n_images * nb;
+    for_items(items, n_threads, [&](long long it) {
+        const int img = (int)(it / nb), b = (int)(it % nb);
+        if (b == nb - 1) return;                                            // nothing lies below the last band
+        uint32_t *c0 = carry.data() + (size_t)it * nt * row_e;
+        const uint8_t *src = in + ((size_t)img * H + (size_t)b * band) * row_e;
+        for (int y = 0; y < band; y++, src += row_e)
+            for (int k = 0; k < nt; k++) {
+                uint32_t *c = c0 + k * row_e;
+                if (squares[k]) for (size_t e = 0; e < row_e; e++) c[e] += (uint32_t)src[e] * src[e];
+                else for (size_t e = 0; e < row_e; e++) c[e] += src[e];
+            }
+    });
+    // the exclusive prefix over an image's bands, then along the row: the table's row above each band
+    for_items((long long)n_images * nt, n_threads, [&](long long it) {
+        const int img = (int)(it / nt), k = (int)(it % nt);
+        std::vector<uint32_t> run(row_e, 0u);
+        for (int b = 0; b < nb; b++) {
+            uint32_t *c = carry.data() + (((size_t)img * nb + b) * nt + k) * row_e;
+            uint32_t along[MI_BLUR_COLOR_MAX_CHANNELS] = {0, 0, 0, 0};
+            for (size_t e = 0; e < row_e; e++) {
+                const uint32_t below = c[e];
+                along[e % C] += run[e];
+                c[e] = along[e % C];
+                run[e] += below;
+            }
+        }
+    });
+    for_items(items, n_threads, [&](long long it) {
+        const int img = (int)(it / nb), b = (int)(it % nb);
+        const int y0 = b * band, y1 = std::min(H, y0 + band);
+        const uint8_t *src = in + ((size_t)img * H + y0) * row_e;
+        for (int k = 0; k < nt; k++) {
+            uint32_t *above = carry.data() + ((size_t)it * nt + k) * row_e;
+            uint32_t *dst = tab[k] + ((size_t)img * H + y0) * row_e;
+            const uint8_t *s = src;
+            for (int y = y0; y < y1; y++, s += row_e, dst += row_e) {
+                uint32_t along[MI_BLUR_COLOR_MAX_CHANNELS] = {0, 0, 0, 0};
+                for (size_t e = 0; e < row_e; e++) {
+                    const uint32_t v = s[e];
+                    along[e % C] += squares[k] ? v * v : v;
+                    dst[e] = above[e] += along[e % C];
+                }
+            }
+        }
+    });
+    return true;
+}
+
+void cpu_box_from_integral(const uint8_t *in, const uint32_t *sum, const uint32_t *sqsum, uint8_t *out, int W, int H, int C, int n_images,
+                           const mi_blur_box &k, int n_threads)
+{
+    if (n_images <= 0) return;
+    if (n_threads <= 0) n_threads = hardware_threads();
+    const BoxConst bc = box_const(k);
+    const size_t row_e = (size_t)W * C;
+    for_items((long long)n_images * H, n_threads, [&](long long row) {
+        const long long img = row / H;
+        const int y = (int)(row - img * H);
+        const uint32_t *S = sum + (size_t)img * H * row_e, *Q = k.op == MI_BLUR_BOX_STDDEV ? sqsum + (size_t)img * H * row_e : nullptr;
+        const size_t at = (size_t)row * row_e;
+        for (int x = 0; x < W; x++)
+            for (int c = 0; c < C; c++) {
+                const size_t e = at + (size_t)x * C + c;
+                const uint32_t s = box_window(S, W, H, C, x, y, c, k.rx, k.ry), q = Q ? box_window(Q, W, H, C, x, y, c, k.rx, k.ry) : 0u;
+                out[e] = (uint8_t)box_byte(k.op, k.offset, k.invert, bc.A, bc.inv_2a, bc.inv_a, s, q, k.op == MI_BLUR_BOX_THRESHOLD ? in[e] : 0);
+            }
+    });
+}
+
 // Synthetic stream: image i = LCG bytes, seed 0x9E3779B9 ^ i.
 void fill_synthetic(uint8_t *host, int W, int H, int C, int first_index, int n_images, int n_threads)
 {

@@ -63,6 +63,15 @@ void cpu_tone(const uint8_t *in, uint8_t *out, int W, int H, int C, int n_images
 // have checked the arguments (arith_args_ok(), filter.h).  Every byte is arith_byte(); a thread reads a byte's operands
 // before it writes the byte, so out may be a, or b where b has the output's extent.
 void cpu_arith(const uint8_t *a, const uint8_t *b, const uint8_t *m, uint8_t *out, int W, int H, int C, int n_images, const mi_blur_arith &k, int n_threads);
+// The integral images and the box filters made from them (include/mi_blur.h, "Integral images, and box filters") on
+// n_images dense W x H x C images; the callers have checked the arguments.  cpu_integral: sum and / or sqsum =
+// uint32[n][H][W][C] (either may be null), rows in bands across the threads: the bands' column sums, their prefix over
+// the bands of an image, then every band on its own from that carry; false when the carries cannot be allocated.
+// cpu_box_from_integral: every output byte is box_byte() of box_window() (filter.h); in is read only by THRESHOLD and only
+// at the byte that is written, sqsum only by STDDEV.
+bool cpu_integral(const uint8_t *in, uint32_t *sum, uint32_t *sqsum, int W, int H, int C, int n_images, int n_threads);
+void cpu_box_from_integral(const uint8_t *in, const uint32_t *sum, const uint32_t *sqsum, uint8_t *out, int W, int H, int C, int n_images,
+                           const mi_blur_box &k, int n_threads);
 // planar (CImg storage: all of channel 0, then channel 1, ...) <-> interleaved, n_images frames, a few pool threads
 void cpu_repack(const uint8_t *src, uint8_t *dst, int W, int H, int C, int n_images, bool planar_to_interleaved, int n_threads);
 void copy_blocks(uint8_t *dst, size_t dst_stride, const uint8_t *src, size_t src_stride, size_t bytes, int n, int n_threads);

@@ -6,6 +6,7 @@
 #include "../../include/mi_blur.h"
 
 #include <limits.h>
+#include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 
@@ -595,6 +596,108 @@ inline bool arith_args_ok(const uint8_t *a, const uint8_t *b, const uint8_t *m, 
     return arith_alias_ok(a, b, m, out, W, H, C, n_images, *k);
 }
 
+// ---- integral images and the box filters made from them (include/mi_blur.h, "Integral images, and box filters").  The
+// host export mi_blur_box_value, the CPU device and both consumer kernels take a window's sum from box_axis() /
+// box_window() and an output byte from box_byte(); the tiled kernel calls box_byte() with a constant op and, in the
+// interior, with the sum of its own four reads.
+inline bool box_ok(const mi_blur_box *k)
+{
+    if (!k || k->op < MI_BLUR_BOX_MEAN || k->op > MI_BLUR_BOX_THRESHOLD) return false;
+    if (k->rx < 0 || k->rx > MI_BLUR_BOX_MAX_RADIUS || k->ry < 0 || k->ry > MI_BLUR_BOX_MAX_RADIUS) return false;
+    if (k->op != MI_BLUR_BOX_THRESHOLD) return k->offset == 0 && k->invert == 0;
+    return k->offset >= -255 && k->offset <= 255 && (k->invert == 0 || k->invert == 1);
+}
+inline int box_tables(const mi_blur_box &k) { return k.op == MI_BLUR_BOX_STDDEV ? 2 : 1; }
+// The five terms of one axis at position X (extent N, radius r): the clamped sum is the sum of coef[t] * F(idx[t]).  A
+// term that the definition skips (coefficient 0, or a read at -1) has coef 0 and idx 0.
+struct BoxAxis { int idx[5]; int coef[5]; };
+MI_BLUR_HD inline BoxAxis box_axis(int X, int N, int r)
+{
+    const int a = X - r > 0 ? X - r : 0, b = X + r < N - 1 ? X + r : N - 1;
+    const int e0 = r - X > 0 ? r - X : 0, e1 = X + r - (N - 1) > 0 ? X + r - (N - 1) : 0;
+    BoxAxis q;
+    q.idx[0] = b; q.coef[0] = 1;
+    q.idx[1] = a > 0 ? a - 1 : 0; q.coef[1] = a > 0 ? -1 : 0;
+    q.idx[2] = 0; q.coef[2] = e0;
+    q.idx[3] = N - 1; q.coef[3] = e1;
+    q.idx[4] = N > 1 ? N - 2 : 0; q.coef[4] = N > 1 ? -e1 : 0;
+    return q;
+}
+// Sum (or SumSq) of the window around (X, Y) in channel c of one image's table T = uint32[H][W][C], in uint32.
+MI_BLUR_HD inline uint32_t box_window(const uint32_t *T, int W, int H, int C, int X, int Y, int c, int rx, int ry)
+{
+    const BoxAxis ax = box_axis(X, W, rx), ay = box_axis(Y, H, ry);
+    uint32_t s = 0;
+    for (int j = 0; j < 5; j++) {
+        if (!ay.coef[j]) continue;
+        const uint32_t *row = T + (size_t)ay.idx[j] * W * C + c;
+        uint32_t t = 0;
+        for (int i = 0; i < 5; i++)
+            if (ax.coef[i]) t += (uint32_t)ax.coef[i] * row[(size_t)ax.idx[i] * C];
+        s += (uint32_t)ay.coef[j] * t;
+    }
+    return s;
+}
+// floor(n / d) for n < 2^26 and 2 <= d <= 2^17 with inv = 1.0f / d: the float estimate is within 1 of the quotient
+// (n / d <= 2^25 only matters below 2^23: here the quotient is at most 256), the exact remainder corrects it.
+MI_BLUR_HD inline uint32_t box_div(uint32_t n, uint32_t d, float inv)
+{
+    uint32_t q = (uint32_t)((float)n * inv);
+    const int32_t r = (int32_t)(n - q * d);
+    if (r < 0) q--;
+    else if ((uint32_t)r >= d) q++;
+    return q;
+}
+// sqrt(D) / A rounded half up for D < 2^49, as the largest s in 0..128 with s == 0 or (2 s - 1)^2 A^2 <= 4 D: the
+// double estimate, then the exact comparison either way ((2 * 128 + 1)^2 * 65025^2 < 2^49).
+MI_BLUR_HD inline int box_root(uint64_t D, uint32_t A, double inv_a)
+{
+    const uint64_t a2 = (uint64_t)A * A, d4 = 4u * D;
+    int s = (int)(sqrt((double)D) * inv_a + 0.5);
+    s = s < 0 ? 0 : s > 128 ? 128 : s;
+    while (s > 0 && (uint64_t)((2 * s - 1) * (2 * s - 1)) * a2 > d4) s--;
+    while (s < 128 && (uint64_t)((2 * s + 1) * (2 * s + 1)) * a2 <= d4) s++;
+    return s;
+}
+// What a launch derives from A once.
+struct BoxConst { uint32_t A; float inv_2a; double inv_a; };
+inline BoxConst box_const(const mi_blur_box &k)
+{
+    BoxConst q;
+    q.A = (uint32_t)((2 * k.rx + 1) * (2 * k.ry + 1));
+    q.inv_2a = 1.0f / (float)(2u * q.A);
+    q.inv_a = 1.0 / (double)q.A;
+    return q;
+}
+// The output byte of a valid struct's fields for a window's sums and the centre byte a.
+MI_BLUR_HD inline int box_byte(int op, int offset, int invert, uint32_t A, float inv_2a, double inv_a, uint32_t sum, uint32_t sqsum, int a)
+{
+    switch (op) {
+    case MI_BLUR_BOX_MEAN: return (int)box_div(2u * sum + A, 2u * A, inv_2a);
+    case MI_BLUR_BOX_STDDEV: return box_root((uint64_t)A * sqsum - (uint64_t)sum * sum, A, inv_a);
+    default: return ((int32_t)A * (a + offset) > (int32_t)sum) != (invert != 0) ? 255 : 0;
+    }
+}
+// Every argument of the integral's entry points but the work buffer and the device; `align` = 16 on the device, 4 on
+// the host.
+inline bool integral_args_ok(const void *in, const void *sum, const void *sqsum, int W, int H, int C, int n_images, uintptr_t align)
+{
+    if (!in || (!sum && !sqsum) || n_images < 0 || !hist_image_ok(W, H, C)) return false;
+    return (uintptr_t)sum % align == 0 && (uintptr_t)sqsum % align == 0;
+}
+// ... and of mi_blur_enqueue_box_from_integral: S always, Q exactly for STDDEV, the images exactly for THRESHOLD.
+inline bool box_from_args_ok(const void *in, const void *sum, const void *sqsum, const void *out, int W, int H, int C, int n_images, const mi_blur_box *k)
+{
+    if (!sum || !out || n_images < 0 || !box_ok(k) || !hist_image_ok(W, H, C)) return false;
+    if ((k->op == MI_BLUR_BOX_STDDEV) != (sqsum != nullptr) || (k->op == MI_BLUR_BOX_THRESHOLD) != (in != nullptr)) return false;
+    return (uintptr_t)sum % 16 == 0 && (uintptr_t)sqsum % 16 == 0;
+}
+// ... and of the forms that make their own tables.
+inline bool box_args_ok(const void *in, const void *out, int W, int H, int C, int n_images, const mi_blur_box *k)
+{
+    return in && out && n_images >= 0 && box_ok(k) && hist_image_ok(W, H, C);
+}
+
 // Output size of a decimation of a W x H image: kept columns / rows (> 0 for a valid decimation, down_ok()).
 inline int down_cols(int W, int sx, int ox) { return (W - ox + sx - 1) / sx; }
 inline int down_rows(int H, int sy, int oy) { return (H - oy + sy - 1) / sy; }
@@ -1064,5 +1167,27 @@ constexpr int ARITH_PLANE_RUN = 256;                // groups per workgroup = it
 inline bool arith_flat_ok(int W, int H, int C) { return (long long)W * H * C % ARITH_CHUNK == 0; }
 inline long long arith_flat_runs(int W, int H, int C) { return ((long long)W * H * C / ARITH_CHUNK + ARITH_RUN - 1) / ARITH_RUN; }
 inline long long arith_plane_runs(int W, int H) { return ((long long)W * H / COLOR_GROUP + ARITH_PLANE_RUN - 1) / ARITH_PLANE_RUN; }
+
+// ---- blur_integral_tiled_kernel: one workgroup per (image, band of rows) spans the whole row, a thread owns
+// INTEGRAL_PIXELS pixels, so the widest image it takes is INTEGRAL_PIXELS * INTEGRAL_MAX_THREADS pixels; its workgroup
+// has the fewest whole waves that cover the row.  A band is INTEGRAL_BAND rows ("integral_band" replaces it in A/B
+// runs): the bands kernel leaves one row of W * C column sums per band and table in the work buffer.
+constexpr int INTEGRAL_PIXELS = 16;
+constexpr int INTEGRAL_MAX_THREADS = 512;
+constexpr int INTEGRAL_MAX_W = 8192;
+constexpr int INTEGRAL_BAND = 16;
+static_assert(INTEGRAL_MAX_W == INTEGRAL_PIXELS * INTEGRAL_MAX_THREADS, "the tiled cap is what one workgroup spans");
+inline bool integral_tiled_ok(int W) { return W % INTEGRAL_PIXELS == 0 && W <= INTEGRAL_MAX_W; }
+inline int integral_threads(int W) { return (W / INTEGRAL_PIXELS + 63) / 64 * 64; }
+inline int integral_bands(int H, int band) { return (H + band - 1) / band; }
+inline size_t integral_work_bytes(int W, int H, int C, int n_images, int tables, int band)
+{
+    return (size_t)n_images * (size_t)integral_bands(H, band) * (size_t)tables * (size_t)W * (size_t)C * sizeof(uint32_t);
+}
+// Dwords of one table.
+inline size_t integral_words(int W, int H, int C, int n_images) { return (size_t)n_images * (size_t)H * (size_t)W * (size_t)C; }
+// blur_box_tiled_kernel: rows of whole 16-byte chunks, a thread per chunk, BOX_THREADS chunks of one row per workgroup.
+constexpr int BOX_THREADS = 256;
+inline bool box_tiled_ok(int W, int C) { return (long long)W * C % 16 == 0; }
 
 }  // namespace mi_blur

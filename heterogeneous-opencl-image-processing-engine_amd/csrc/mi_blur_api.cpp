@@ -2545,6 +2545,147 @@ extern "C" int mi_blur_run_arith(int device, const uint8_t *host_a, const uint8_
     return MI_BLUR_OK;
 }
 
+// ----------------------------------------------------------------------------------
+// integral images and the box filters made from them (no reference analogue).  Not a FilterKind either: a table is not
+// an image and the box filters need a work buffer.  The same order as the histogram family: all arguments
+// (integral_args_ok(), box_from_args_ok(), box_args_ok(): filter.h), the empty batch, the device.
+// ----------------------------------------------------------------------------------
+static size_t round16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
+// Bytes of one table inside the work buffer of mi_blur_enqueue_box.
+static size_t box_table_bytes(int W, int H, int C, int n_images) { return round16(integral_words(W, H, C, n_images) * sizeof(uint32_t)); }
+
+extern "C" int mi_blur_box_value(const mi_blur_box *k, int A, uint32_t sum, uint32_t sqsum, int a)
+{
+    if (!box_ok(k) || A != (2 * k->rx + 1) * (2 * k->ry + 1) || sum > 255u * (uint32_t)A) return -1;
+    if (k->op == MI_BLUR_BOX_STDDEV) {
+        if ((uint64_t)sqsum > 65025ull * (uint64_t)A || (uint64_t)sum * sum > (uint64_t)A * sqsum) return -1;
+    } else {
+        sqsum = 0;
+    }
+    if (k->op != MI_BLUR_BOX_THRESHOLD) a = 0;
+    if (a < 0 || a > 255) return -1;
+    const BoxConst bc = box_const(*k);
+    return box_byte(k->op, k->offset, k->invert, bc.A, bc.inv_2a, bc.inv_a, sum, sqsum, a);
+}
+
+extern "C" size_t mi_blur_integral_work_bytes(int width, int height, int channels, int n_images, int both)
+{
+    if (!hist_image_ok(width, height, channels) || n_images < 0) return 0;
+    return integral_work_bytes(width, height, channels, n_images, both ? 2 : 1, tunables().integral_band);
+}
+
+extern "C" int mi_blur_enqueue_integral(const uint8_t *d_in, uint32_t *d_sum, uint32_t *d_sqsum, int width, int height, int channels, int n_images,
+                                        void *d_work, void *stream)
+{
+    if (!integral_args_ok(d_in, d_sum, d_sqsum, width, height, channels, n_images, 16) || !aligned_to(d_work, 16)) return MI_BLUR_ERR_INVALID;
+    if (n_images == 0) return MI_BLUR_OK;
+    if (mi_blur_device_count() <= 0) return MI_BLUR_ERR_NO_DEVICE;
+    return launch_integral(d_in, d_sum, d_sqsum, width, height, channels, n_images, d_work, (hipStream_t)stream);
+}
+
+extern "C" int mi_blur_cpu_run_integral(const uint8_t *in, uint32_t *sum, uint32_t *sqsum, int width, int height, int channels, int n_images, int n_threads)
+{
+    if (!integral_args_ok(in, sum, sqsum, width, height, channels, n_images, 4)) return MI_BLUR_ERR_INVALID;
+    return cpu_integral(in, sum, sqsum, width, height, channels, n_images, n_threads) ? MI_BLUR_OK : MI_BLUR_ERR_NOMEM;
+}
+
+extern "C" int mi_blur_enqueue_box_from_integral(const uint8_t *d_in, const uint32_t *d_sum, const uint32_t *d_sqsum, uint8_t *d_out, int width,
+                                                 int height, int channels, int n_images, const mi_blur_box *k, void *stream)
+{
+    if (!box_from_args_ok(d_in, d_sum, d_sqsum, d_out, width, height, channels, n_images, k)) return MI_BLUR_ERR_INVALID;
+    if (n_images == 0) return MI_BLUR_OK;
+    if (mi_blur_device_count() <= 0) return MI_BLUR_ERR_NO_DEVICE;
+    return launch_box_from_integral(d_in, d_sum, d_sqsum, d_out, width, height, channels, n_images, *k, (hipStream_t)stream);
+}
+
+extern "C" size_t mi_blur_box_work_bytes(int width, int height, int channels, int n_images, const mi_blur_box *k)
+{
+    if (!box_ok(k) || !hist_image_ok(width, height, channels) || n_images < 0) return 0;
+    const int tables = box_tables(*k);
+    return tables * box_table_bytes(width, height, channels, n_images) +
+           integral_work_bytes(width, height, channels, n_images, tables, tunables().integral_band);
+}
+
+// The dispatches of mi_blur_enqueue_box on buffers that are known to be good: work = S [Q] and the integral's own work.
+static int enqueue_box(const uint8_t *d_in, uint8_t *d_out, int W, int H, int C, int n_images, const mi_blur_box &k, void *d_work, hipStream_t stream)
+{
+    const size_t table = box_table_bytes(W, H, C, n_images);
+    uint8_t *base = static_cast<uint8_t *>(d_work);
+    uint32_t *sum = reinterpret_cast<uint32_t *>(base);
+    uint32_t *sqsum = k.op == MI_BLUR_BOX_STDDEV ? reinterpret_cast<uint32_t *>(base + table) : nullptr;
+    if (const int rc = launch_integral(d_in, sum, sqsum, W, H, C, n_images, base + box_tables(k) * table, stream)) return rc;
+    return launch_box_from_integral(k.op == MI_BLUR_BOX_THRESHOLD ? d_in : nullptr, sum, sqsum, d_out, W, H, C, n_images, k, stream);
+}
+
+extern "C" int mi_blur_enqueue_box(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int n_images, const mi_blur_box *k,
+                                   void *d_work, void *stream)
+{
+    if (!box_args_ok(d_in, d_out, width, height, channels, n_images, k) || !aligned_to(d_work, 16)) return MI_BLUR_ERR_INVALID;
+    if (n_images == 0) return MI_BLUR_OK;
+    if (mi_blur_device_count() <= 0) return MI_BLUR_ERR_NO_DEVICE;
+    return enqueue_box(d_in, d_out, width, height, channels, n_images, *k, d_work, (hipStream_t)stream);
+}
+
+extern "C" int mi_blur_cpu_run_box(const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images, const mi_blur_box *k,
+                                   int n_threads)
+{
+    if (!box_args_ok(in, out, width, height, channels, n_images, k)) return MI_BLUR_ERR_INVALID;
+    if (n_images == 0) return MI_BLUR_OK;
+    const size_t words = integral_words(width, height, channels, n_images);
+    std::vector<uint32_t> sum, sqsum;
+    try {
+        sum.resize(words);
+        if (k->op == MI_BLUR_BOX_STDDEV) sqsum.resize(words);
+    } catch (...) {
+        return MI_BLUR_ERR_NOMEM;
+    }
+    uint32_t *q = k->op == MI_BLUR_BOX_STDDEV ? sqsum.data() : nullptr;
+    if (!cpu_integral(in, sum.data(), q, width, height, channels, n_images, n_threads)) return MI_BLUR_ERR_NOMEM;
+    cpu_box_from_integral(in, sum.data(), q, out, width, height, channels, n_images, *k, n_threads);
+    return MI_BLUR_OK;
+}
+
+extern "C" int mi_blur_run_integral(int device, const uint8_t *host_in, uint32_t *host_sum, uint32_t *host_sqsum, int width, int height, int channels,
+                                    int n_images)
+{
+    if (device == MI_BLUR_DEVICE_CPU) return mi_blur_cpu_run_integral(host_in, host_sum, host_sqsum, width, height, channels, n_images, 0);
+    if (!integral_args_ok(host_in, host_sum, host_sqsum, width, height, channels, n_images, 4)) return MI_BLUR_ERR_INVALID;
+    if (n_images == 0) return MI_BLUR_OK;
+    if (const int rc = use_device(device)) return rc;
+    const size_t in_bytes = (size_t)n_images * width * height * channels, table = integral_words(width, height, channels, n_images) * sizeof(uint32_t);
+    DeviceBuffer in, sum, sqsum, work;
+    HIP_TRY(in.alloc(in_bytes));
+    if (host_sum) HIP_TRY(sum.alloc(table));
+    if (host_sqsum) HIP_TRY(sqsum.alloc(table));
+    HIP_TRY(work.alloc(mi_blur_integral_work_bytes(width, height, channels, n_images, host_sum && host_sqsum)));
+    HIP_TRY(hipMemcpy(in.p, host_in, in_bytes, hipMemcpyHostToDevice));
+    if (const int rc = launch_integral(static_cast<const uint8_t *>(in.p), static_cast<uint32_t *>(sum.p), static_cast<uint32_t *>(sqsum.p), width,
+                                       height, channels, n_images, work.p, nullptr))
+        return rc;
+    if (host_sum) HIP_TRY(hipMemcpy(host_sum, sum.p, table, hipMemcpyDeviceToHost));           // on the null stream: behind the kernels
+    if (host_sqsum) HIP_TRY(hipMemcpy(host_sqsum, sqsum.p, table, hipMemcpyDeviceToHost));
+    return MI_BLUR_OK;
+}
+
+extern "C" int mi_blur_run_box(int device, const uint8_t *host_in, uint8_t *host_out, int width, int height, int channels, int n_images,
+                               const mi_blur_box *k)
+{
+    if (device == MI_BLUR_DEVICE_CPU) return mi_blur_cpu_run_box(host_in, host_out, width, height, channels, n_images, k, 0);
+    if (!box_args_ok(host_in, host_out, width, height, channels, n_images, k)) return MI_BLUR_ERR_INVALID;
+    if (n_images == 0) return MI_BLUR_OK;
+    if (const int rc = use_device(device)) return rc;
+    const size_t bytes = (size_t)n_images * width * height * channels;
+    DeviceBuffer in, out, work;
+    HIP_TRY(in.alloc(bytes));
+    HIP_TRY(out.alloc(bytes));
+    HIP_TRY(work.alloc(mi_blur_box_work_bytes(width, height, channels, n_images, k)));
+    HIP_TRY(hipMemcpy(in.p, host_in, bytes, hipMemcpyHostToDevice));
+    if (const int rc = enqueue_box(static_cast<const uint8_t *>(in.p), static_cast<uint8_t *>(out.p), width, height, channels, n_images, *k, work.p, nullptr))
+        return rc;
+    HIP_TRY(hipMemcpy(host_out, out.p, bytes, hipMemcpyDeviceToHost));
+    return MI_BLUR_OK;
+}
+
 extern "C" void mi_blur_fill_synthetic(uint8_t *host, int width, int height, int channels, int first_index,
                                        int n_images, int n_threads)
 {

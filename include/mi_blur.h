@@ -74,7 +74,8 @@ int mi_blur_version(void);
  * "blur_remap_generic_kernel", "blur_area_tiled_kernel", "blur_area_generic_kernel", "blur_color_tiled_kernel",
  * "blur_color_generic_kernel", "blur_hist_tiled_kernel", "blur_hist_generic_kernel", "blur_tone_table_kernel",
  * "blur_tables_tiled_kernel", "blur_tables_generic_kernel", "blur_arith_flat_kernel", "blur_arith_plane_kernel",
- * "blur_arith_generic_kernel"; "" before the first):
+ * "blur_arith_generic_kernel", "blur_integral_tiled_kernel", "blur_integral_generic_kernel", "blur_box_tiled_kernel",
+ * "blur_box_generic_kernel"; "" before the first):
  * reports name the kernel a profiler will show.  Static string, never NULL. */
 const char *mi_blur_last_kernel(void);
 
@@ -144,7 +145,11 @@ const char *mi_blur_last_kernel(void);
  *                      counters and what mi_blur_resident_batches_done reports do not depend on it; a pass's own start-to-stop
  *                      time gets longer by about the overlap (profiles/r09_fused_overlap.md).  0 = every pass on one stream
  *   "fused_release"    0 (default) | 1: how a block of the fused stream publishes "my outputs are in memory" — see
- *                      mi_blur_resident_run_fused */
+ *                      mi_blur_resident_run_fused
+ *   "integral_band"    16 (default) | 1 .. 256: rows per band of blur_integral_tiled_kernel (A/B runs; the work buffer's size
+ *                      follows it: mi_blur_integral_work_bytes and mi_blur_box_work_bytes answer for the value in force)
+ *   "box_bytes"        4 (default) | 16: consecutive output bytes of a row that a thread of blur_box_tiled_kernel owns (A/B
+ *                      runs): with 4 a wave's 16-byte loads of a table row are contiguous, with 16 they lie 64 bytes apart */
 int mi_blur_set_option(const char *key, int value);
 
 /* Number of visible HIP devices (0 is a valid answer: CPU-device contexts still work).
@@ -866,6 +871,129 @@ int mi_blur_cpu_run_arith(const uint8_t *a, const uint8_t *b, const uint8_t *m /
  * no such device, after the argument checks. */
 int mi_blur_run_arith(int device, const uint8_t *host_a, const uint8_t *host_b, const uint8_t *host_m /* NULL unless LERP */,
                       uint8_t *host_out, int width, int height, int channels, int n_images, const mi_blur_arith *k);
+
+/* ------------------------------------------------------------------------
+ * Integral images, and box filters of any window up to 255 x 255 made from them: the box mean, the local standard
+ * deviation and the adaptive threshold (no reference analogue).  The first operation here whose cost does not depend on
+ * the window.  Integers only, so the GPU, the CPU device and a numpy / Python-integer restatement agree exactly.  Like
+ * the histogram family it is not a filter of a context: an integral image is not an image, and the box filters need a
+ * work buffer.
+ *
+ * Images: n_images interleaved dense images of width x height x channels (W x H x C below), channels 1..4, within the
+ * histogram family's limits (width, height <= MI_BLUR_RESIZE_MAX_DIM; width*channels <= INT_MAX/2;
+ * width*height*channels <= INT_MAX).  n_images == 0 is MI_BLUR_OK and launches nothing.  Image offsets are 64-bit.
+ *
+ * Integral image (inclusive, with the image's own shape, so rows keep their alignment):
+ *   S[i][y][x][c] = (sum over y' <= y, x' <= x of in[i][y'][x'][c]) mod 2^32,   uint32[n_images][H][W][C];
+ *   Q[i][y][x][c] = the same over the squares in^2, also mod 2^32.
+ *   An index of -1 on either axis reads as 0.
+ * The modulus is part of the definition: any combination of entries with integer coefficients, computed in uint32, is
+ * exact whenever its true value is below 2^32.  So images of any allowed size are valid (not only those with
+ * W*H*255 < 2^32), and a window of at most 255 x 255 pixels is always exact for S (65025 * 255 < 2^32) and for Q
+ * (65025 * 65025 = 4 228 250 625 < 2^32): one 32-bit table serves the squares too.
+ *
+ * Box window with clamp-to-edge (the border rule of every filter here).  rx, ry in 0..MI_BLUR_BOX_MAX_RADIUS,
+ * A = (2 rx + 1)(2 ry + 1);
+ *   Sum(X, Y, c)   = sum over |dy| <= ry, |dx| <= rx of in[clamp(Y + dy, 0, H - 1)][clamp(X + dx, 0, W - 1)][c],
+ *   SumSq(X, Y, c) = the same over the squares.
+ * Per axis, with N the extent, r the radius and F the inclusive prefix along that axis (F(-1) = 0):
+ *   a = max(X - r, 0),  b = min(X + r, N - 1),  e0 = max(0, r - X),  e1 = max(0, X + r - (N - 1));
+ *   the clamped sum is  F(b) - F(a - 1) + e0 * F(0) + e1 * (F(N - 1) - F(N - 2)).
+ * In two dimensions Sum is the outer product of the two five-term forms over S (SumSq: over Q), in uint32: 4 reads in
+ * the interior, at most 25 at a corner; terms with coefficient 0 (and reads at index -1) are skipped.  This holds for
+ * windows larger than the image.  Every implementation here uses this form.
+ *
+ * Operations (mi_blur_box.op), per output byte:
+ *   MEAN       out = floor((2 Sum + A) / (2 A)): the mean rounded once, half up (the area resize's rounding).
+ *   STDDEV     D = A * SumSq - Sum^2 in 64 bits (>= 0, below 2^49); out = the largest s in 0..128 with s == 0 or
+ *              (2 s - 1)^2 A^2 <= 4 D: sqrt(D) / A rounded once, half up, decided in integers.
+ *   THRESHOLD  the adaptive threshold: with a = in[Y][X][c] and offset in -255..255, out = 255 if A * (a + offset) > Sum,
+ *              else 0; invert (0 | 1) swaps the two outputs.  This is "a > mean - offset" with the mean NOT rounded; it is
+ *              not claimed to be the bytes of OpenCV's adaptiveThreshold, which rounds the mean first.
+ * Fields a mode does not use (offset and invert outside THRESHOLD) must be 0.  An op outside the enum, a radius outside
+ * 0..127, an offset outside -255..255, an invert outside 0 | 1 or a non-zero unused field is MI_BLUR_ERR_INVALID, the
+ * output untouched.
+ * ---------------------------------------------------------------------- */
+#define MI_BLUR_BOX_MAX_RADIUS 127
+typedef enum { MI_BLUR_BOX_MEAN = 0, MI_BLUR_BOX_STDDEV = 1, MI_BLUR_BOX_THRESHOLD = 2 } mi_blur_box_op;
+typedef struct mi_blur_box {
+    int op;                 /* mi_blur_box_op */
+    int rx, ry;             /* 0..MI_BLUR_BOX_MAX_RADIUS: a window of (2 rx + 1) x (2 ry + 1) pixels */
+    int offset;             /* THRESHOLD: -255..255; otherwise must be 0 */
+    int invert;             /* THRESHOLD: 0 | 1; otherwise must be 0 */
+} mi_blur_box;
+
+/* The definition for one output byte (host only): the byte for a window of A pixels whose sum is `sum` and whose sum of
+ * squares is `sqsum` (read only by STDDEV), with centre byte a (read only by THRESHOLD).  -1 for an invalid *k, an A
+ * other than (2 rx + 1)(2 ry + 1), sum > 255 A, and where they are read: sqsum > 65025 A, sum^2 > A * sqsum (no window
+ * has such sums), a outside 0..255. */
+int mi_blur_box_value(const mi_blur_box *k, int A, uint32_t sum, uint32_t sqsum, int a);
+
+/* Bytes of the work buffer of mi_blur_enqueue_integral: the column sums of every band of the "integral_band" rows in
+ * force (16 by default), uint32[n_images][ceil(H / band)][both ? 2 : 1][W * C].  0 for an image outside the limits or
+ * n_images < 0. */
+size_t mi_blur_integral_work_bytes(int width, int height, int channels, int n_images, int both);
+/* The integral images of n_images images (device memory, asynchronous on `stream`).  d_sum receives S, d_sqsum Q;
+ * either may be NULL, not both; both come from one read of the input.  Each is uint32[n_images][H][W][C], 16-byte
+ * aligned, OVERWRITTEN.  d_work: device memory, 16-byte aligned, mi_blur_integral_work_bytes(..., both outputs given)
+ * bytes.  MI_BLUR_ERR_INVALID (every argument is checked before a device is asked for, so before
+ * MI_BLUR_ERR_NO_DEVICE): a null d_in or d_work, both outputs null, an output or d_work not 16-byte aligned, channels
+ * outside 1..4, a size outside the limits, n_images < 0.
+ * No workgroup of these kernels ever waits for another: what one band hands the next crosses a dispatch boundary on the
+ * stream, through d_work.
+ * blur_integral_tiled_kernel takes exactly the launches with W a multiple of 16, W <= 8192 and d_in 16-byte aligned,
+ * as three dispatches.  (1) blur_integral_bands_kernel: per band of rows, the column sums of the bytes (and of their
+ * squares) to d_work.  (2) blur_integral_band_prefix_kernel: their exclusive prefix over the bands of an image, in
+ * place.  (3) blur_integral_tiled_kernel: one workgroup per (image, band) spans the whole row, a thread owns 16 pixels
+ * (C loads of 16 bytes); it keeps the running column sums of its pixels in registers, seeded from (2), adds each row of
+ * the band to them and takes the horizontal prefix of them for every row: in registers within the thread, across the
+ * wave by lane shifts, across the waves through LDS; 4 C stores of 16 bytes per table.  The input is read twice and the
+ * tables are written once.
+ * Every other launch goes to blur_integral_generic_kernel (one wave per row: the prefix along each row into the
+ * tables) followed by blur_integral_generic_cols_kernel (one thread per column and channel walks down the table, in
+ * place); d_work is not written.  mi_blur_last_kernel() says which of the two forms ran. */
+int mi_blur_enqueue_integral(const uint8_t *d_in, uint32_t *d_sum /* may be NULL */, uint32_t *d_sqsum /* may be NULL */,
+                             int width, int height, int channels, int n_images, void *d_work, void *stream);
+/* The same on the CPU device's threads (synchronous), host memory; the tables 4-byte aligned; no work buffer (rows in
+ * bands across the threads, with the same carry from band to band). */
+int mi_blur_cpu_run_integral(const uint8_t *in, uint32_t *sum /* may be NULL */, uint32_t *sqsum /* may be NULL */,
+                             int width, int height, int channels, int n_images, int n_threads);
+
+/* The box filter *k from integral images that are already there (device memory, asynchronous): d_sum = S of the input,
+ * always; d_sqsum = Q, non-null exactly for STDDEV; d_in = the images, non-null exactly for THRESHOLD (read only at the
+ * byte a thread writes, so d_out == d_in is allowed).  MI_BLUR_ERR_INVALID (before MI_BLUR_ERR_NO_DEVICE): a null
+ * d_sum, d_out or k; d_sqsum or d_in given or missing against the rule; a table not 16-byte aligned; an invalid *k;
+ * the image and n_images as above.
+ * blur_box_tiled_kernel takes the launches whose rows are whole 16-byte chunks (W * C a multiple of 16) with d_out (and
+ * d_in) 16-byte aligned: a thread owns 4 consecutive output bytes of a row ("box_bytes": 16 in A/B runs), which is 4
+ * consecutive dwords at each corner of the window: one 16-byte load per corner, contiguous across a wave.  Where all of
+ * its pixels are more than rx columns and ry rows from every border it takes the 4-read form, elsewhere the general form
+ * per byte.  The division by A is a float estimate corrected by the exact
+ * remainder; STDDEV's root is a double estimate corrected by the exact 64-bit comparison.  Every other launch goes to
+ * blur_box_generic_kernel, one output byte per thread. */
+int mi_blur_enqueue_box_from_integral(const uint8_t *d_in /* THRESHOLD only */, const uint32_t *d_sum,
+                                      const uint32_t *d_sqsum /* STDDEV only */, uint8_t *d_out, int width, int height,
+                                      int channels, int n_images, const mi_blur_box *k, void *stream);
+/* Bytes of the work buffer of mi_blur_enqueue_box: the tables the mode needs (S; S and Q for STDDEV), each
+ * n_images * H * W * C * 4 bytes, then mi_blur_integral_work_bytes() for them.  0 for an invalid *k, an image outside the
+ * limits or n_images < 0. */
+size_t mi_blur_box_work_bytes(int width, int height, int channels, int n_images, const mi_blur_box *k);
+/* The integral images the mode needs and the box filter from them as one call: the dispatches of
+ * mi_blur_enqueue_integral and mi_blur_enqueue_box_from_integral on `stream`, no host round trip.  d_work: device
+ * memory, 16-byte aligned, mi_blur_box_work_bytes() bytes.  d_out == d_in is allowed.  MI_BLUR_ERR_INVALID: a null or
+ * misaligned d_work, a null d_in, d_out or k, an invalid *k, the image and n_images as above. */
+int mi_blur_enqueue_box(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int n_images,
+                        const mi_blur_box *k, void *d_work, void *stream);
+/* The same on the CPU device's threads (synchronous); the call allocates its tables (MI_BLUR_ERR_NOMEM if it cannot). */
+int mi_blur_cpu_run_box(const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,
+                        const mi_blur_box *k, int n_threads);
+/* Blocking, host memory in and out: allocate on `device` (a HIP ordinal), copy in, enqueue, copy out, free.
+ * device == MI_BLUR_DEVICE_CPU calls the cpu_run forms with all threads.  MI_BLUR_ERR_NO_DEVICE where there is no such
+ * device, after the argument checks. */
+int mi_blur_run_integral(int device, const uint8_t *host_in, uint32_t *host_sum /* may be NULL */,
+                         uint32_t *host_sqsum /* may be NULL */, int width, int height, int channels, int n_images);
+int mi_blur_run_box(int device, const uint8_t *host_in, uint8_t *host_out, int width, int height, int channels, int n_images,
+                    const mi_blur_box *k);
 
 /* ------------------------------------------------------------------------
  * Affine warp: exact fixed-point rotate, scale, shear and translate, any output size (no reference analogue).  The
