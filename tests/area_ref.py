@@ -42,6 +42,32 @@ def ref_area(img, wo, ho):
     return ((2 * s + d) // (2 * d)).astype(np.uint8)
 
 
+def prefix_sums(v, axis, n_in, n_out, X0, X1, first=0):
+    """The weighted sums of outputs X0 .. X1 - 1 along `axis` of the int64 array v, which holds inputs first, first + 1, ...
+    of n_in along that axis, from prefix sums and without a weight matrix: over the n_in * n_out fine units of the axis,
+    P(t) = n_out * cum[t // n_out] + (t mod n_out) * v[t // n_out], and output X sums P((X + 1) n_in) - P(X n_in)."""
+    v = np.moveaxis(v, axis, 0)
+    cum = np.concatenate([np.zeros_like(v[:1]), np.cumsum(v, axis=0)])
+    pad = np.concatenate([v, np.zeros_like(v[:1])])                       # P(n_in * n_out) reads one past the end, times 0
+    t = np.arange(X0, X1 + 1, dtype=np.int64) * n_in
+    k, r = t // n_out - first, t % n_out
+    assert k.min() >= 0 and k.max() <= v.shape[0] and (k[r > 0] < v.shape[0]).all()
+    P = n_out * cum[k] + r.reshape((-1,) + (1,) * (v.ndim - 1)) * pad[k]
+    return np.moveaxis(np.diff(P, axis=0), 0, axis)
+
+
+def ref_area_rows(slab, first_row, h, wo, ho, rows):
+    """Output rows rows[0] .. rows[1] - 1 of ref_area for an image of h rows, of which slab (N, ., W, C) holds the rows from
+    first_row on: at least the input rows i_lo(rows[0]) .. i_hi(rows[1] - 1) of ref_axis(h, ho).  int64 prefix sums, so it
+    works at 32768 columns, where ref_weights() would not fit."""
+    w = slab.shape[2]
+    s = prefix_sums(slab.astype(np.int64), 1, h, ho, rows[0], rows[1], first_row)
+    s = prefix_sums(s, 2, w, wo, 0, wo)
+    d = w * h
+    assert s.min(initial=0) >= 0 and s.max(initial=0) <= 255 * d
+    return ((2 * s + d) // (2 * d)).astype(np.uint8)
+
+
 def float_area(img, wo, ho):
     """The real-valued box average in float64, not rounded."""
     n, h, w, c = img.shape

@@ -23,6 +23,39 @@ def ref_integral(img, square=False):
     return (np.cumsum(np.cumsum(v, axis=1, dtype=np.uint64), axis=2, dtype=np.uint64) % M32).astype(np.uint32)
 
 
+def ref_integral_rows(img, starts, band, square=False, chunk=64):
+    """Rows r .. r + band - 1 of the table of ONE image (H x W x C uint8) for every r of `starts`, without the table: the
+    column sums of all rows above r as int64, taken `chunk` rows at a time and carried from one start to the next, then a
+    cumulative sum down the band and along the row, modulo 2^32.  {r: uint32 band x W x C}.  The numpy twin of
+    torch_integral_rows()."""
+    above, done, out = np.zeros(img.shape[1:], np.int64), 0, {}
+    for r in sorted(starts):
+        while done < r:
+            v = img[done:min(done + chunk, r)].astype(np.int64)
+            above += (v * v if square else v).sum(axis=0)
+            done += v.shape[0]
+        v = img[r:r + band].astype(np.int64)
+        rows = above[None] + np.cumsum(v * v if square else v, axis=0)
+        out[r] = (np.cumsum(rows, axis=1) % M32).astype(np.uint32)
+    return out
+
+
+def torch_integral_rows(torch, d_img, starts, band, square=False, chunk=2048):
+    """ref_integral_rows() on a device tensor (H x W x C uint8), in torch and nothing of the product's: {r: int64 band x W x C
+    on the device, values modulo 2^32}.  A chunk of 2048 rows of 32768 bytes is 512 MiB as int64."""
+    above, done, out = torch.zeros(d_img.shape[1:], dtype=torch.int64, device=d_img.device), 0, {}
+    for r in sorted(starts):
+        while done < r:
+            v = d_img[done:min(done + chunk, r)].to(torch.int64)
+            above += (v * v if square else v).sum(dim=0)
+            done += v.shape[0]
+            del v
+        v = d_img[r:r + band].to(torch.int64)
+        rows = above.unsqueeze(0) + torch.cumsum(v * v if square else v, dim=0)
+        out[r] = torch.cumsum(rows, dim=1) % M32
+    return out
+
+
 def window_sums(img, rx, ry, square=False):
     """Sum (or SumSq) of every clamped window, int64 N x H x W x C: the image padded with its edge, then differences of an
     int64 cumulative sum of the padded image (exact: at most 65025 * 65025 per window)."""

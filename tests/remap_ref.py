@@ -44,6 +44,26 @@ def ref_remap(img, fmap, mode=BILINEAR, border=CONSTANT, fill=0):
     return ((s + (1 << 21)) >> 22).astype(np.uint8)
 
 
+def map_rows(fmap, mode, w, h):
+    """(lo, hi): the input rows lo .. hi (inclusive) that the taps of fmap read from a W x H image, clamped into it."""
+    _, y0, _, _ = ref_coord(fmap[:, :, 0], fmap[:, :, 1], mode, w, h)
+    k = 0 if mode == NEAREST else 1
+    return int(np.clip(y0.min(), 0, h - 1)), int(np.clip(y0.max() + k, 0, h - 1))
+
+
+def ref_remap_slab(slab, first_row, h, fmap, mode=BILINEAR, border=CONSTANT, fill=0):
+    """ref_remap of an image of h rows from the slab (N, ., W, C) of its rows from first_row on, which must hold the rows
+    map_rows() names: the map's y entries, clamped as the image clamps them, shifted by first_row rows.  A tap misses the
+    slab only where it misses the image on the same side, so where the slab ends at the image's edge the border is the
+    image's own."""
+    n, hs, w, c = slab.shape
+    lo, hi = map_rows(fmap, mode, w, h)
+    assert first_row <= lo and hi < first_row + hs and first_row + hs <= h
+    shifted = np.asarray(fmap, dtype=np.int64).copy()
+    shifted[:, :, 1] = np.clip(shifted[:, :, 1], -2 * ONE, (h + 1) * ONE) - first_row * ONE
+    return ref_remap(slab, shifted, mode, border, fill)
+
+
 def float_remap(img, xs, ys, border=CONSTANT, fill=0):
     """Real-valued bilinear at the real positions (xs, ys) (float64 (Ho, Wo) arrays), not rounded."""
     n, h, w, c = img.shape
