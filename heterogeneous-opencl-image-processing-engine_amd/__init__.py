@@ -56,6 +56,11 @@ TONE_MODES = {"equalize": TONE_EQUALIZE, "stretch": TONE_STRETCH}
 ARITH_LINEAR, ARITH_ABSDIFF, ARITH_MIN, ARITH_MAX, ARITH_MUL, ARITH_LERP = range(6)
 BOX_MEAN, BOX_STDDEV, BOX_THRESHOLD = range(3)
 BOX_MAX_RADIUS = 127
+DIST_L2, DIST_L1, DIST_LINF = range(3)
+DIST_METRICS = {"l2": DIST_L2, "l1": DIST_L1, "linf": DIST_LINF}
+DIST_BYTE, DIST_WITHIN = 0, 1
+DIST_MAX_LIMIT = 32767
+DIST_NONE = 0xFFFFFFFF
 ARITH_PRESETS = {"add": 0, "sub": 1, "avg": 2, "diff128": 3, "absdiff": 4, "min": 5, "max": 6, "mul255": 7, "mulq7": 8, "lerp": 9}
 WARP_Q = 16
 WARP_CLAMP, WARP_CONSTANT = 0, 1
@@ -72,7 +77,7 @@ def _newer(target: str, sources: list[str]) -> bool:
 
 def build_native(force: bool = False, verbose: bool = False) -> str:
     """Compile libmi_blur.so (hipcc, --offload-arch=gfx950) and the C++ hosts, in-tree."""
-    srcs = [os.path.join(CSRC, f) for f in ("blur_kernels.hip", "sep_kernels.hip", "median_kernels.hip", "morph_kernels.hip", "bilateral_kernels.hip", "conv_kernels.hip", "sep_down_kernels.hip", "resize_kernels.hip", "warp_kernels.hip", "remap_kernels.hip", "area_kernels.hip", "color_kernels.hip", "hist_kernels.hip", "arith_kernels.hip", "integral_kernels.hip", "layout_kernels.hip", "mi_blur_api.cpp", "comm_api.cpp", "cpu_device.cpp")]
+    srcs = [os.path.join(CSRC, f) for f in ("blur_kernels.hip", "sep_kernels.hip", "median_kernels.hip", "morph_kernels.hip", "bilateral_kernels.hip", "conv_kernels.hip", "sep_down_kernels.hip", "resize_kernels.hip", "warp_kernels.hip", "remap_kernels.hip", "area_kernels.hip", "color_kernels.hip", "hist_kernels.hip", "arith_kernels.hip", "integral_kernels.hip", "dist_kernels.hip", "layout_kernels.hip", "mi_blur_api.cpp", "comm_api.cpp", "cpu_device.cpp")]
     deps = srcs + [os.path.join(CSRC, f) for f in ("api_internal.h", "blur_launch.h", "kernel_common.h", "cpu_device.h", "filter.h")] + [HEADER]
     if force or not _newer(LIB_PATH, deps):
         cmd = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra",
@@ -269,6 +274,13 @@ class Box(C.Structure):
     """mi_blur_box: the operation (BOX_MEAN | BOX_STDDEV | BOX_THRESHOLD), the radii of the (2 rx + 1) x (2 ry + 1) window
     and, for BOX_THRESHOLD only, the offset (-255..255) and invert (include/mi_blur.h, "Integral images, and box filters")."""
     _fields_ = [("op", C.c_int), ("rx", C.c_int), ("ry", C.c_int), ("offset", C.c_int), ("invert", C.c_int)]
+
+
+class Dist(C.Structure):
+    """mi_blur_dist: the metric (DIST_L2 | DIST_L1 | DIST_LINF), whether a site is a non-zero pixel (0: a zero pixel), the
+    limit (0 = none, 1..32767) and, for the byte calls, byte_op (DIST_BYTE | DIST_WITHIN) and, for DIST_WITHIN only, invert
+    (include/mi_blur.h, "Exact distance transform")."""
+    _fields_ = [("metric", C.c_int), ("sites_nonzero", C.c_int), ("limit", C.c_int), ("byte_op", C.c_int), ("invert", C.c_int)]
 
 
 class Warp(C.Structure):
@@ -473,6 +485,14 @@ def lib() -> C.CDLL:
         "mi_blur_cpu_run_box": (i, [u8p, u8p, i, i, i, i, C.POINTER(Box), i]),
         "mi_blur_run_integral": (i, [i, u8p, vp, vp, i, i, i, i]),
         "mi_blur_run_box": (i, [i, u8p, u8p, i, i, i, i, C.POINTER(Box)]),
+        "mi_blur_dist_value": (i, [C.POINTER(Dist), C.c_uint32]),
+        "mi_blur_dist_work_bytes": (C.c_size_t, [i, i, i, i, C.POINTER(Dist)]),
+        "mi_blur_enqueue_dist": (i, [u8p, vp, i, i, i, i, C.POINTER(Dist), vp, vp]),
+        "mi_blur_enqueue_dist_u8": (i, [u8p, u8p, i, i, i, i, C.POINTER(Dist), vp, vp]),
+        "mi_blur_cpu_run_dist": (i, [u8p, vp, i, i, i, i, C.POINTER(Dist), i]),
+        "mi_blur_cpu_run_dist_u8": (i, [u8p, u8p, i, i, i, i, C.POINTER(Dist), i]),
+        "mi_blur_run_dist": (i, [i, u8p, vp, i, i, i, i, C.POINTER(Dist)]),
+        "mi_blur_run_dist_u8": (i, [i, u8p, u8p, i, i, i, i, C.POINTER(Dist)]),
         "mi_blur_warp_coord": (i, [C.POINTER(Warp), i, i, C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i)]),
         "mi_blur_warp_rotation": (i, [C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double)]),
         "mi_blur_warp_set_matrix": (i, [C.POINTER(Warp), C.POINTER(C.c_double), i]),
@@ -1358,6 +1378,69 @@ def adaptive_threshold(images, ksize, offset: int = 0, invert: bool = False, dev
     (the mean not rounded), else 0; invert swaps the two.  OpenCV's adaptiveThreshold with ADAPTIVE_THRESH_MEAN_C and
     C = offset, but not its bytes, which round the mean first."""
     return _box_run(images, _box(ksize, BOX_THRESHOLD, offset, invert, "adaptive_threshold"), device, batch, "adaptive_threshold")
+
+
+def _dist(metric, sites, limit: int, byte_op: int, invert: bool, name: str) -> "Dist":
+    code = DIST_METRICS.get(metric.lower()) if isinstance(metric, str) else None
+    if code is None:
+        raise ValueError(f"{name}: metric is one of {sorted(DIST_METRICS)}")
+    if sites not in ("zero", "nonzero"):
+        raise ValueError(f'{name}: sites is "zero" or "nonzero"')
+    if not isinstance(limit, int) or not 0 <= limit <= DIST_MAX_LIMIT:
+        raise ValueError(f"{name}: a limit or radius is an integer 0..{DIST_MAX_LIMIT}")
+    return Dist(code, int(sites == "nonzero"), limit, byte_op, int(bool(invert)))
+
+
+def _dist_run(images, k: "Dist", table: bool, device: int, batch: int, name: str):
+    import numpy as np
+    a, rank = _tone_stack(images, name)
+    n, h, w, c = a.shape
+    out = np.empty(a.shape, np.uint32 if table else np.uint8)
+    run, export = (lib().mi_blur_run_dist, "mi_blur_run_dist") if table else (lib().mi_blur_run_dist_u8, "mi_blur_run_dist_u8")
+    per = batch if batch > 0 else max(n, 1)
+    for i in range(0, n, per):
+        check(run(device, a[i:].ctypes.data, out[i:].ctypes.data, w, h, c, min(per, n - i), C.byref(k)), export)
+    return out if rank == 4 else out[0] if rank == 3 else out[0, :, :, 0]
+
+
+def distance_transform(images, metric: str = "l2", sites: str = "zero", limit: int = 0, device: int = 0, batch: int = 0):
+    """The exact distance of every pixel to the nearest site of its image and channel (mi_blur_run_dist; include/mi_blur.h,
+    "Exact distance transform", has the definition): uint32 of the images' shape.  metric "l2": the SQUARED Euclidean
+    distance; "l1": city block; "linf": chessboard.  sites "zero" (OpenCV's distanceTransform): the zero pixels are the
+    sites; "nonzero": the others.  A channel without a site, and with a limit every pixel farther than `limit` from one,
+    holds DIST_NONE.  device: HIP ordinal, or DEVICE_CPU; batch: images per call (0 = all)."""
+    return _dist_run(images, _dist(metric, sites, limit, DIST_BYTE, False, "distance_transform"), True, device, batch, "distance_transform")
+
+
+def distance_transform_u8(images, metric: str = "l2", sites: str = "zero", limit: int = 0, device: int = 0, batch: int = 0):
+    """The same as bytes (mi_blur_run_dist_u8, DIST_BYTE): the distance itself, saturated at 255; for "l2" the square root
+    rounded once, half up.  255 where distance_transform() holds DIST_NONE."""
+    return _dist_run(images, _dist(metric, sites, limit, DIST_BYTE, False, "distance_transform_u8"), False, device, batch, "distance_transform_u8")
+
+
+def _disc(images, radius: int, metric, sites: str, invert: bool, device: int, batch: int, name: str):
+    if radius == 0:
+        raise ValueError(f"{name}: radius is an integer 1..{DIST_MAX_LIMIT}")
+    return _dist_run(images, _dist(metric, sites, radius, DIST_WITHIN, invert, name), False, device, batch, name)
+
+
+def disc_dilate(images, radius: int, metric: str = "l2", device: int = 0, batch: int = 0):
+    """Dilation of MASKS (zero / non-zero pixels) by the metric's ball of `radius` (1..32767): a disc ("l2"), a diamond
+    ("l1") or a (2 radius + 1)-square ("linf").  255 where a non-zero pixel lies within `radius`, else 0
+    (mi_blur_run_dist_u8, DIST_WITHIN).  The cost does not grow with the area of the element.  Opening is disc_erode then
+    disc_dilate, closing disc_dilate then disc_erode: two calls."""
+    return _disc(images, radius, metric, "nonzero", False, device, batch, "disc_dilate")
+
+
+def disc_erode(images, radius: int, metric: str = "l2", device: int = 0, batch: int = 0):
+    """Erosion of MASKS (zero / non-zero pixels) by the same element: 255 where no zero pixel lies within `radius`, else 0.
+    Pixels outside the image do not count as zero.  Opening and closing are two calls: see disc_dilate."""
+    return _disc(images, radius, metric, "zero", True, device, batch, "disc_erode")
+
+
+def dist_value(k: "Dist", t: int) -> int:
+    """The byte of the byte struct k for the table value t (mi_blur_dist_value); -1 for an invalid k or a t no image gives."""
+    return lib().mi_blur_dist_value(C.byref(k), int(t))
 
 
 def arith_preset(name) -> "Arith":

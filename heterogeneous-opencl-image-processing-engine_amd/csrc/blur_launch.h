@@ -83,6 +83,11 @@ int launch_arith(const uint8_t *a, const uint8_t *b, const uint8_t *m, uint8_t *
 int launch_integral(const uint8_t *in, uint32_t *sum, uint32_t *sqsum, int W, int H, int C, int n_images, void *work, hipStream_t stream);
 int launch_box_from_integral(const uint8_t *in, const uint32_t *sum, const uint32_t *sqsum, uint8_t *out, int W, int H, int C, int n_images,
                              const mi_blur_box &k, hipStream_t stream);
+// The distance transform (dist_kernels.hip); no Filter and no LaunchDesc.  Dense images of W x H x C, n_images of them;
+// exactly one of table (uint32[n][H][W][C], 16-byte aligned) and out (the byte form, which may be `in`) is given, and k
+// is the struct of that call.  Every argument is checked (dist_args_ok(), filter.h: MI_BLUR_ERR_INVALID), an empty batch
+// is MI_BLUR_OK.  work = dist_work_bytes() bytes for the band in force (tunables().dist_band), 16-byte aligned.
+int launch_dist(const uint8_t *in, uint32_t *table, uint8_t *out, int W, int H, int C, int n_images, const mi_blur_dist &k, void *work, hipStream_t stream);
 // Sets what last_kernel() reports for the calling thread.
 void set_last_kernel(const char *name);
 
@@ -217,6 +222,8 @@ struct Tunables {
                          // 0 = plain launch, completion by stream synchronise (timing experiment: no kernel bucket)
     int integral_band;   // blur_integral_tiled_kernel: rows per band (default INTEGRAL_BAND of filter.h; A/B runs)
     int box_bytes;       // blur_box_tiled_kernel: consecutive output bytes of a row per thread, 4 (default) | 16 (A/B runs)
+    int dist_band;       // the distance transform's column pass: rows per band (default DIST_BAND of filter.h; A/B runs)
+    int dist_chunk_log2; // blur_dist_tiled_kernel: log2 of the columns per search chunk (default DIST_CHUNK_LOG2 of filter.h; A/B runs)
 };
 // Every knob once: its mi_blur_set_option key, its field, what values it takes, its default and the environment variable
 // (or nullptr) that may replace the default when the library starts.  FLAG: any value, stored as 0 | 1.  RANGE: lo .. hi.
@@ -263,6 +270,8 @@ static constexpr Knob KNOBS[] = {
     {"xcd_run", &Tunables::xcd_run, KnobKind::RANGE, 0, 1 << 20, 0, nullptr},
     {"integral_band", &Tunables::integral_band, KnobKind::RANGE, 1, 256, 16, nullptr},    // the default is INTEGRAL_BAND of filter.h
     {"box_bytes", &Tunables::box_bytes, KnobKind::ONE_OF, knob_bits(4, 16, 4, 16), 0, 4, nullptr},
+    {"dist_band", &Tunables::dist_band, KnobKind::RANGE, 1, 256, 32, nullptr},            // the default is DIST_BAND of filter.h
+    {"dist_chunk_log2", &Tunables::dist_chunk_log2, KnobKind::RANGE, 3, 5, 4, nullptr},   // the default is DIST_CHUNK_LOG2 of filter.h
 };
 // Stores `value` in the knob's field of t if the knob accepts it; false (t untouched) otherwise.
 static inline bool knob_set(const Knob &k, Tunables &t, int value)

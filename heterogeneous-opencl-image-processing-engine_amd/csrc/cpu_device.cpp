@@ -787,6 +787,91 @@ void cpu_box_from_integral(const uint8_t *in, const uint32_t *sum, const uint32_
     });
 }
 
+// The distance transform.  The column pass: items are (image, strip of DIST_CPU_STRIP columns and channels), each walks
+// its strip down the image and up again.  The row pass: items are (image, band of rows); a row is laid out as the tiled
+// kernel lays it out in LDS, one padded plane per channel and the chunks' minima, and searched by the same dist_search().
+namespace {
+constexpr int DIST_CPU_STRIP = 256;
+constexpr int DIST_CPU_CHUNK = 1 << DIST_CHUNK_LOG2;
+
+template <int METRIC>
+void dist_row(const uint16_t *plane, const uint16_t *cm, int nch, int W, int C, uint32_t start, const mi_blur_dist &k, uint32_t *table, uint8_t *out)
+{
+    const size_t wp = (size_t)nch * DIST_CPU_CHUNK;
+    for (int c = 0; c < C; c++)
+        for (int x = 0; x < W; x++) {
+            const uint32_t T = dist_final(dist_search<METRIC, DIST_CPU_CHUNK>(plane + c * wp, cm + (size_t)c * nch, nch, x, start), start);
+            if (table) table[(size_t)x * C + c] = T;
+            else out[(size_t)x * C + c] = (uint8_t)dist_byte(k.metric, k.byte_op, k.invert, T);
+        }
+}
+}  // namespace
+
+bool cpu_dist(const uint8_t *in, uint32_t *table, uint8_t *out, int W, int H, int C, int n_images, const mi_blur_dist &k, int n_threads)
+{
+    if (n_images <= 0) return true;
+    if (n_threads <= 0) n_threads = hardware_threads();
+    const size_t row_e = (size_t)W * C;
+    std::vector<uint16_t> g;
+    try { g.resize((size_t)n_images * H * row_e); } catch (...) { return false; }
+    const uint32_t cap = dist_cap(k.limit);
+    const long long strips = ((long long)row_e + DIST_CPU_STRIP - 1) / DIST_CPU_STRIP;
+    for_items((long long)n_images * strips, n_threads, [&](long long it) {
+        const long long img = it / strips;
+        const size_t e0 = (size_t)(it - img * strips) * DIST_CPU_STRIP, e1 = std::min(row_e, e0 + DIST_CPU_STRIP);
+        const uint8_t *src = in + (size_t)img * H * row_e;
+        uint16_t *dst = g.data() + (size_t)img * H * row_e;
+        uint32_t site[DIST_CPU_STRIP];
+        for (size_t e = e0; e < e1; e++) site[e - e0] = DIST_G_NONE;
+        for (int y = 0; y < H; y++)
+            for (size_t e = e0; e < e1; e++) {
+                uint32_t &s = site[e - e0];
+                if ((src[(size_t)y * row_e + e] != 0) == (k.sites_nonzero != 0)) s = (uint32_t)y;
+                dst[(size_t)y * row_e + e] = (uint16_t)(s == DIST_G_NONE ? DIST_G_NONE : (uint32_t)y - s);
+            }
+        for (size_t e = e0; e < e1; e++) site[e - e0] = DIST_G_NONE;
+        for (int y = H - 1; y >= 0; y--)
+            for (size_t e = e0; e < e1; e++) {
+                uint32_t &s = site[e - e0];
+                uint32_t d = dst[(size_t)y * row_e + e];
+                if (d == 0) s = (uint32_t)y;
+                const uint32_t up = s == DIST_G_NONE ? DIST_G_NONE : s - (uint32_t)y;
+                d = up < d ? up : d;
+                dst[(size_t)y * row_e + e] = (uint16_t)dist_g_cap(d, cap);
+            }
+    });
+    const int want = std::max(1, std::min(std::max(1, H / 16), (4 * n_threads + n_images - 1) / n_images));
+    const int band = (H + want - 1) / want, nb = (H + band - 1) / band;
+    const int nch = dist_chunks(W, DIST_CPU_CHUNK);
+    const size_t wp = (size_t)nch * DIST_CPU_CHUNK;
+    const uint32_t start = dist_start(k.metric, k.limit);
+    std::atomic<bool> ok{true};
+    for_items((long long)n_images * nb, n_threads, [&](long long it) {
+        const int img = (int)(it / nb), b = (int)(it % nb);
+        std::vector<uint16_t> plane, cm;
+        try { plane.assign((size_t)C * wp, (uint16_t)DIST_G_NONE); cm.resize((size_t)C * nch); } catch (...) { ok = false; return; }
+        for (int y = b * band; y < std::min(H, (b + 1) * band); y++) {
+            const size_t at = ((size_t)img * H + y) * row_e;
+            const uint16_t *row = g.data() + at;
+            for (int x = 0; x < W; x++)
+                for (int c = 0; c < C; c++) plane[c * wp + x] = row[(size_t)x * C + c];
+            for (size_t q = 0; q < (size_t)C * nch; q++) {
+                uint32_t m = DIST_G_NONE;
+                for (int j = 0; j < DIST_CPU_CHUNK; j++) m = std::min<uint32_t>(m, plane[q * DIST_CPU_CHUNK + j]);
+                cm[q] = (uint16_t)m;
+            }
+            uint32_t *t = table ? table + at : nullptr;
+            uint8_t *o = out ? out + at : nullptr;
+            switch (k.metric) {
+            case MI_BLUR_DIST_L2: dist_row<MI_BLUR_DIST_L2>(plane.data(), cm.data(), nch, W, C, start, k, t, o); break;
+            case MI_BLUR_DIST_L1: dist_row<MI_BLUR_DIST_L1>(plane.data(), cm.data(), nch, W, C, start, k, t, o); break;
+            default: dist_row<MI_BLUR_DIST_LINF>(plane.data(), cm.data(), nch, W, C, start, k, t, o); break;
+            }
+        }
+    });
+    return ok;
+}
+
 // Synthetic stream: image i = LCG bytes, seed 0x9E3779B9 ^ i.
 void fill_synthetic(uint8_t *host, int W, int H, int C, int first_index, int n_images, int n_threads)
 {

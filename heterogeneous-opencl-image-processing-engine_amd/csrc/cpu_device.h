@@ -72,6 +72,12 @@ void cpu_arith(const uint8_t *a, const uint8_t *b, const uint8_t *m, uint8_t *ou
 bool cpu_integral(const uint8_t *in, uint32_t *sum, uint32_t *sqsum, int W, int H, int C, int n_images, int n_threads);
 void cpu_box_from_integral(const uint8_t *in, const uint32_t *sum, const uint32_t *sqsum, uint8_t *out, int W, int H, int C, int n_images,
                            const mi_blur_box &k, int n_threads);
+// The distance transform (include/mi_blur.h, "Exact distance transform") on n_images dense W x H x C images; the callers
+// have checked the arguments (dist_args_ok(), filter.h).  Exactly one of table (uint32[n][H][W][C]) and out (the byte form
+// of k; it may be `in`: the column pass has read the whole input before a row is written) is given.  g, the column
+// distances, is allocated here: false when that fails.  Columns in strips across the threads, then rows in bands; every
+// value is dist_final() of dist_search(), every byte dist_byte() of it (filter.h).
+bool cpu_dist(const uint8_t *in, uint32_t *table, uint8_t *out, int W, int H, int C, int n_images, const mi_blur_dist &k, int n_threads);
 // planar (CImg storage: all of channel 0, then channel 1, ...) <-> interleaved, n_images frames, a few pool threads
 void cpu_repack(const uint8_t *src, uint8_t *dst, int W, int H, int C, int n_images, bool planar_to_interleaved, int n_threads);
 void copy_blocks(uint8_t *dst, size_t dst_stride, const uint8_t *src, size_t src_stride, size_t bytes, int n, int n_threads);

@@ -698,6 +698,134 @@ inline bool box_args_ok(const void *in, const void *out, int W, int H, int C, in
     return in && out && n_images >= 0 && box_ok(k) && hist_image_ok(W, H, C);
 }
 
+// ---- distance transform (include/mi_blur.h, "Exact distance transform").  The host export mi_blur_dist_value, the CPU
+// device and both row-pass kernels take a candidate from dist_cand(), the value a search starts from and ends with from
+// dist_start() / dist_final(), the search itself from dist_search() / dist_search_plain() and a byte from dist_byte().
+// g, the column distance, is 16 bits: 0..32767, or DIST_G_NONE, which is never squared or added: every use selects on it.
+constexpr uint32_t DIST_G_NONE = 0xFFFFu;
+constexpr int DIST_G_MAX = 32767;                   // H <= 32768
+// bytes: the struct of a byte call; otherwise of a table call, where byte_op and invert are unused.
+inline bool dist_ok(const mi_blur_dist *k, bool bytes)
+{
+    if (!k || k->metric < MI_BLUR_DIST_L2 || k->metric > MI_BLUR_DIST_LINF) return false;
+    if ((k->sites_nonzero != 0 && k->sites_nonzero != 1) || k->limit < 0 || k->limit > MI_BLUR_DIST_MAX_LIMIT) return false;
+    if (!bytes || k->byte_op == MI_BLUR_DIST_BYTE) return k->byte_op == MI_BLUR_DIST_BYTE && k->invert == 0;
+    return k->byte_op == MI_BLUR_DIST_WITHIN && k->limit >= 1 && (k->invert == 0 || k->invert == 1);
+}
+// The candidate a site dx columns away offers through its column distance g (dx, g <= 32767, g not the marker): at most
+// 2 * 32767^2 < 2^31, in unsigned arithmetic throughout.
+template <int METRIC>
+MI_BLUR_HD inline uint32_t dist_cand(uint32_t dx, uint32_t g)
+{
+    if (METRIC == MI_BLUR_DIST_L2) return dx * dx + g * g;
+    if (METRIC == MI_BLUR_DIST_L1) return dx + g;
+    return dx > g ? dx : g;
+}
+MI_BLUR_HD inline uint32_t dist_cand(int metric, uint32_t dx, uint32_t g)
+{
+    return metric == MI_BLUR_DIST_L2 ? dist_cand<MI_BLUR_DIST_L2>(dx, g) : metric == MI_BLUR_DIST_L1 ? dist_cand<MI_BLUR_DIST_L1>(dx, g) : dist_cand<MI_BLUR_DIST_LINF>(dx, g);
+}
+// The largest T any image gives.
+inline uint32_t dist_max(int metric) { return dist_cand(metric, DIST_G_MAX, DIST_G_MAX); }
+// A search starts from the first value beyond the limit (limit^2 + 1 <= 32767^2 + 1 fits) and only smaller candidates
+// replace it; what is left at the end is T, or NONE if nothing did.
+MI_BLUR_HD inline uint32_t dist_start(int metric, int limit) { return limit ? dist_cand(metric, (uint32_t)limit, 0u) + 1u : MI_BLUR_DIST_NONE; }
+MI_BLUR_HD inline uint32_t dist_final(uint32_t best, uint32_t start) { return best < start ? best : MI_BLUR_DIST_NONE; }
+// What the column pass stores for a column distance d (or the marker): with a limit, anything above it offers nothing.
+MI_BLUR_HD inline uint32_t dist_g_cap(uint32_t d, uint32_t cap) { return d > cap ? DIST_G_NONE : d; }
+inline uint32_t dist_cap(int limit) { return limit ? (uint32_t)limit : (uint32_t)DIST_G_MAX; }
+// T over one row from a PLANE of g: the row's g of one channel, x-major, padded with the marker to nch whole chunks of
+// CHUNK columns, and cm[ch] = the minimum of chunk ch.  First the columns nearer than CHUNK, one dx at a time on both
+// sides: where sites are dense the search ends there, after a few reads.  That covers x's own chunk; then the other
+// chunks outwards, left and right in turn: a side ends when its chunk's nearest dx alone cannot beat `best`, a chunk is
+// skipped when its minimum cannot.  At most CHUNK + nch steps.
+template <int METRIC, int CHUNK>
+MI_BLUR_HD inline uint32_t dist_search(const uint16_t *g, const uint16_t *cm, int nch, int x, uint32_t start)
+{
+    const int cx = x / CHUNK, wp = nch * CHUNK;
+    uint32_t best = start;
+    for (int dx = 0; dx < CHUNK; dx++) {
+        if (dist_cand<METRIC>((uint32_t)dx, 0u) >= best) return best;
+        const uint32_t gl = x - dx >= 0 ? g[x - dx] : DIST_G_NONE, gr = x + dx < wp ? g[x + dx] : DIST_G_NONE;
+        const uint32_t gg = gl < gr ? gl : gr;                         // the same dx: the smaller g offers the smaller candidate
+        const uint32_t v = gg == DIST_G_NONE ? MI_BLUR_DIST_NONE : dist_cand<METRIC>((uint32_t)dx, gg);
+        best = v < best ? v : best;
+    }
+    for (int k = 1; k < nch; k++) {
+        bool open = false;
+        for (int side = 0; side < 2; side++) {
+            const int ch = side ? cx + k : cx - k;
+            if (ch < 0 || ch >= nch) continue;
+            const int x0 = ch * CHUNK;
+            const uint32_t near = side ? (uint32_t)(x0 - x) : (uint32_t)(x - (x0 + CHUNK - 1));
+            if (dist_cand<METRIC>(near, 0u) >= best) continue;
+            open = true;
+            const uint32_t m = cm[ch];
+            if (m == DIST_G_NONE || dist_cand<METRIC>(near, m) >= best) continue;
+            const uint16_t *q = g + x0;
+#pragma unroll
+            for (int j = 0; j < CHUNK; j++) {
+                const uint32_t gg = q[j];
+                const uint32_t dx = (uint32_t)(x0 + j > x ? x0 + j - x : x - (x0 + j));
+                const uint32_t v = gg == DIST_G_NONE ? MI_BLUR_DIST_NONE : dist_cand<METRIC>(dx, gg);
+                best = v < best ? v : best;
+            }
+        }
+        if (!open) break;
+    }
+    return best;
+}
+// The same from g as it lies in memory (entry x of the row and channel at g[x * stride]), without minima: dx outwards,
+// both sides in step, until dx alone cannot beat `best` or both sides have left the row.  At most W steps.
+template <int METRIC>
+MI_BLUR_HD inline uint32_t dist_search_plain(const uint16_t *g, int stride, int W, int x, uint32_t start)
+{
+    uint32_t best = start;
+    for (int dx = 0; dx < W; dx++) {
+        const int xl = x - dx, xr = x + dx;
+        if (dist_cand<METRIC>((uint32_t)dx, 0u) >= best || (xl < 0 && xr >= W)) break;
+        if (xl >= 0) {
+            const uint32_t gg = g[(size_t)xl * stride];
+            const uint32_t v = gg == DIST_G_NONE ? MI_BLUR_DIST_NONE : dist_cand<METRIC>((uint32_t)dx, gg);
+            best = v < best ? v : best;
+        }
+        if (dx && xr < W) {
+            const uint32_t gg = g[(size_t)xr * stride];
+            const uint32_t v = gg == DIST_G_NONE ? MI_BLUR_DIST_NONE : dist_cand<METRIC>((uint32_t)dx, gg);
+            best = v < best ? v : best;
+        }
+    }
+    return best;
+}
+// sqrt(T) rounded half up, capped at 255: the largest s with s == 0 or (2 s - 1)^2 <= 4 T.  509^2 <= 4 T from T = 64771
+// on; below that T is exact as a float and its root is within 2^-15 of the float root, so the estimate is the answer or
+// one off it, and one exact comparison either way settles it (no loop: the kernels take four roots a thread).
+MI_BLUR_HD inline int dist_root(uint32_t T)
+{
+    if (T >= 64771u) return 255;
+    int s = (int)(sqrtf((float)T) + 0.5f);
+    s -= s > 0 && (uint32_t)((2 * s - 1) * (2 * s - 1)) > 4u * T;
+    s += (uint32_t)((2 * s + 1) * (2 * s + 1)) <= 4u * T;
+    return s;
+}
+// The byte of a valid byte struct's fields for the table value T.
+MI_BLUR_HD inline int dist_byte(int metric, int byte_op, int invert, uint32_t T)
+{
+    if (byte_op == MI_BLUR_DIST_WITHIN) return (T != MI_BLUR_DIST_NONE) != (invert != 0) ? 255 : 0;
+    if (T == MI_BLUR_DIST_NONE) return 255;
+    if (metric == MI_BLUR_DIST_L2) return dist_root(T);
+    return T > 255u ? 255 : (int)T;
+}
+// Every argument of the family's entry points but the work buffer and the device; `align` of the table = 16 on the
+// device, 4 on the host.  The byte form may be written over the input; no other overlap of the two.
+inline bool dist_args_ok(const uint8_t *in, const void *out, int W, int H, int C, int n_images, const mi_blur_dist *k, bool bytes, uintptr_t align)
+{
+    if (!in || !out || n_images < 0 || !dist_ok(k, bytes) || !hist_image_ok(W, H, C)) return false;
+    if (!bytes) return (uintptr_t)out % align == 0;
+    const uintptr_t i0 = (uintptr_t)in, o0 = (uintptr_t)out, size = (uintptr_t)W * H * C * (uintptr_t)n_images;
+    return i0 == o0 || i0 + size <= o0 || o0 + size <= i0;
+}
+
 // Output size of a decimation of a W x H image: kept columns / rows (> 0 for a valid decimation, down_ok()).
 inline int down_cols(int W, int sx, int ox) { return (W - ox + sx - 1) / sx; }
 inline int down_rows(int H, int sy, int oy) { return (H - oy + sy - 1) / sy; }
@@ -1189,5 +1317,34 @@ inline size_t integral_words(int W, int H, int C, int n_images) { return (size_t
 // blur_box_tiled_kernel: rows of whole 16-byte chunks, a thread per chunk, BOX_THREADS chunks of one row per workgroup.
 constexpr int BOX_THREADS = 256;
 inline bool box_tiled_ok(int W, int C) { return (long long)W * C % 16 == 0; }
+
+// ---- the distance transform's kernels.  The column pass works in bands of DIST_BAND rows ("dist_band" replaces it in
+// A/B runs) and leaves, next to g, two rows of W * C row numbers per band.  blur_dist_tiled_kernel: a workgroup of
+// DIST_THREADS threads owns dist_rows() whole rows (about DIST_TILE_ELEMS elements, at most DIST_MAX_ROWS rows), rows of
+// whole 16-byte chunks of g (W * C a multiple of 8) of at most DIST_MAX_ROW elements: a row's planes, padded to whole
+// search chunks of 2^DIST_CHUNK_LOG2 columns ("dist_chunk_log2": 3..5), and their minima then fit 64 KiB of LDS.
+constexpr int DIST_BAND = 32;
+constexpr int DIST_THREADS = 256;
+constexpr int DIST_TILE_ELEMS = 4096;
+constexpr int DIST_MAX_ROWS = 8;
+constexpr int DIST_MAX_ROW = 24576;
+constexpr int DIST_CHUNK_LOG2 = 4;
+inline bool dist_tiled_ok(int W, int C) { return (long long)W * C % 8 == 0 && (long long)W * C <= DIST_MAX_ROW; }
+inline int dist_rows(int W, int C) { const int r = DIST_TILE_ELEMS / (W * C); return r < 1 ? 1 : r > DIST_MAX_ROWS ? DIST_MAX_ROWS : r; }
+inline int dist_chunks(int W, int chunk) { return (W + chunk - 1) / chunk; }
+// LDS of one workgroup: the planes (uint16 [rows][C][nch * chunk]) and the minima (uint16 [rows][C][nch]), to 16 bytes.
+inline size_t dist_lds_bytes(int W, int C, int rows, int chunk)
+{
+    const size_t nch = (size_t)dist_chunks(W, chunk);
+    return ((size_t)rows * C * nch * (chunk + 1) * sizeof(uint16_t) + 15) & ~(size_t)15;
+}
+// C * nch <= W * C / chunk + C: the smallest chunk is the largest case (55 368 bytes; 52 360 at 16).
+static_assert((DIST_MAX_ROW / 8 + 4) * (8 + 1) * 2 <= 65536, "one row of DIST_MAX_ROW elements fits 64 KiB at every chunk size");
+inline int dist_bands(int H, int band) { return (H + band - 1) / band; }
+inline size_t dist_g_bytes(int W, int H, int C, int n_images) { return ((size_t)n_images * (size_t)H * (size_t)W * (size_t)C * sizeof(uint16_t) + 15) & ~(size_t)15; }
+inline size_t dist_work_bytes(int W, int H, int C, int n_images, int band)
+{
+    return dist_g_bytes(W, H, C, n_images) + (size_t)n_images * (size_t)dist_bands(H, band) * 2u * (size_t)W * (size_t)C * sizeof(uint16_t);
+}
 
 }  // namespace mi_blur

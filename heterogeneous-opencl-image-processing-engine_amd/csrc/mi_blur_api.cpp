@@ -2686,6 +2686,90 @@ extern "C" int mi_blur_run_box(int device, const uint8_t *host_in, uint8_t *host
     return MI_BLUR_OK;
 }
 
+// ----------------------------------------------------------------------------------
+// exact distance transform (no reference analogue).  Not a FilterKind either: it produces a table and needs a work
+// buffer.  The same order as the integral family: all arguments (dist_args_ok(): filter.h), the empty batch, the device.
+// ----------------------------------------------------------------------------------
+extern "C" int mi_blur_dist_value(const mi_blur_dist *k, uint32_t t)
+{
+    if (!dist_ok(k, true)) return -1;
+    if (t != MI_BLUR_DIST_NONE && (t > dist_max(k->metric) || t >= dist_start(k->metric, k->limit))) return -1;
+    return dist_byte(k->metric, k->byte_op, k->invert, t);
+}
+
+extern "C" size_t mi_blur_dist_work_bytes(int width, int height, int channels, int n_images, const mi_blur_dist *k)
+{
+    if (!dist_ok(k, true) || !hist_image_ok(width, height, channels) || n_images < 0) return 0;
+    return dist_work_bytes(width, height, channels, n_images, tunables().dist_band);
+}
+
+extern "C" int mi_blur_enqueue_dist(const uint8_t *d_in, uint32_t *d_table, int width, int height, int channels, int n_images, const mi_blur_dist *k,
+                                    void *d_work, void *stream)
+{
+    if (!dist_args_ok(d_in, d_table, width, height, channels, n_images, k, false, 16) || !aligned_to(d_work, 16)) return MI_BLUR_ERR_INVALID;
+    if (n_images == 0) return MI_BLUR_OK;
+    if (mi_blur_device_count() <= 0) return MI_BLUR_ERR_NO_DEVICE;
+    return launch_dist(d_in, d_table, nullptr, width, height, channels, n_images, *k, d_work, (hipStream_t)stream);
+}
+
+extern "C" int mi_blur_enqueue_dist_u8(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int n_images, const mi_blur_dist *k,
+                                       void *d_work, void *stream)
+{
+    if (!dist_args_ok(d_in, d_out, width, height, channels, n_images, k, true, 1) || !aligned_to(d_work, 16)) return MI_BLUR_ERR_INVALID;
+    if (n_images == 0) return MI_BLUR_OK;
+    if (mi_blur_device_count() <= 0) return MI_BLUR_ERR_NO_DEVICE;
+    return launch_dist(d_in, nullptr, d_out, width, height, channels, n_images, *k, d_work, (hipStream_t)stream);
+}
+
+extern "C" int mi_blur_cpu_run_dist(const uint8_t *in, uint32_t *table, int width, int height, int channels, int n_images, const mi_blur_dist *k,
+                                    int n_threads)
+{
+    if (!dist_args_ok(in, table, width, height, channels, n_images, k, false, 4)) return MI_BLUR_ERR_INVALID;
+    return cpu_dist(in, table, nullptr, width, height, channels, n_images, *k, n_threads) ? MI_BLUR_OK : MI_BLUR_ERR_NOMEM;
+}
+
+extern "C" int mi_blur_cpu_run_dist_u8(const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images, const mi_blur_dist *k,
+                                       int n_threads)
+{
+    if (!dist_args_ok(in, out, width, height, channels, n_images, k, true, 1)) return MI_BLUR_ERR_INVALID;
+    return cpu_dist(in, nullptr, out, width, height, channels, n_images, *k, n_threads) ? MI_BLUR_OK : MI_BLUR_ERR_NOMEM;
+}
+
+// The blocking forms on a HIP device, the arguments checked: the byte form, or the table (4 bytes an element).
+static int run_dist(int device, const uint8_t *host_in, void *host_out, bool bytes, int W, int H, int C, int n_images, const mi_blur_dist &k)
+{
+    if (const int rc = use_device(device)) return rc;
+    const size_t in_bytes = (size_t)n_images * W * H * C, out_bytes = in_bytes * (bytes ? 1 : sizeof(uint32_t));
+    DeviceBuffer in, out, work;
+    HIP_TRY(in.alloc(in_bytes));
+    HIP_TRY(out.alloc(out_bytes));
+    HIP_TRY(work.alloc(mi_blur_dist_work_bytes(W, H, C, n_images, &k)));
+    HIP_TRY(hipMemcpy(in.p, host_in, in_bytes, hipMemcpyHostToDevice));
+    if (const int rc = launch_dist(static_cast<const uint8_t *>(in.p), bytes ? nullptr : static_cast<uint32_t *>(out.p),
+                                   bytes ? static_cast<uint8_t *>(out.p) : nullptr, W, H, C, n_images, k, work.p, nullptr))
+        return rc;
+    HIP_TRY(hipMemcpy(host_out, out.p, out_bytes, hipMemcpyDeviceToHost));            // on the null stream: behind the kernels
+    return MI_BLUR_OK;
+}
+
+extern "C" int mi_blur_run_dist(int device, const uint8_t *host_in, uint32_t *host_table, int width, int height, int channels, int n_images,
+                                const mi_blur_dist *k)
+{
+    if (device == MI_BLUR_DEVICE_CPU) return mi_blur_cpu_run_dist(host_in, host_table, width, height, channels, n_images, k, 0);
+    if (!dist_args_ok(host_in, host_table, width, height, channels, n_images, k, false, 4)) return MI_BLUR_ERR_INVALID;
+    if (n_images == 0) return MI_BLUR_OK;
+    return run_dist(device, host_in, host_table, false, width, height, channels, n_images, *k);
+}
+
+extern "C" int mi_blur_run_dist_u8(int device, const uint8_t *host_in, uint8_t *host_out, int width, int height, int channels, int n_images,
+                                   const mi_blur_dist *k)
+{
+    if (device == MI_BLUR_DEVICE_CPU) return mi_blur_cpu_run_dist_u8(host_in, host_out, width, height, channels, n_images, k, 0);
+    if (!dist_args_ok(host_in, host_out, width, height, channels, n_images, k, true, 1)) return MI_BLUR_ERR_INVALID;
+    if (n_images == 0) return MI_BLUR_OK;
+    return run_dist(device, host_in, host_out, true, width, height, channels, n_images, *k);
+}
+
 extern "C" void mi_blur_fill_synthetic(uint8_t *host, int width, int height, int channels, int first_index,
                                        int n_images, int n_threads)
 {

@@ -75,7 +75,7 @@ int mi_blur_version(void);
  * "blur_color_generic_kernel", "blur_hist_tiled_kernel", "blur_hist_generic_kernel", "blur_tone_table_kernel",
  * "blur_tables_tiled_kernel", "blur_tables_generic_kernel", "blur_arith_flat_kernel", "blur_arith_plane_kernel",
  * "blur_arith_generic_kernel", "blur_integral_tiled_kernel", "blur_integral_generic_kernel", "blur_box_tiled_kernel",
- * "blur_box_generic_kernel"; "" before the first):
+ * "blur_box_generic_kernel", "blur_dist_tiled_kernel", "blur_dist_generic_kernel"; "" before the first):
  * reports name the kernel a profiler will show.  Static string, never NULL. */
 const char *mi_blur_last_kernel(void);
 
@@ -149,7 +149,11 @@ const char *mi_blur_last_kernel(void);
  *   "integral_band"    16 (default) | 1 .. 256: rows per band of blur_integral_tiled_kernel (A/B runs; the work buffer's size
  *                      follows it: mi_blur_integral_work_bytes and mi_blur_box_work_bytes answer for the value in force)
  *   "box_bytes"        4 (default) | 16: consecutive output bytes of a row that a thread of blur_box_tiled_kernel owns (A/B
- *                      runs): with 4 a wave's 16-byte loads of a table row are contiguous, with 16 they lie 64 bytes apart */
+ *                      runs): with 4 a wave's 16-byte loads of a table row are contiguous, with 16 they lie 64 bytes apart
+ *   "dist_band"        32 (default) | 1 .. 256: rows per band of the distance transform's column pass (A/B runs; the work
+ *                      buffer's size follows it: mi_blur_dist_work_bytes answers for the value in force)
+ *   "dist_chunk_log2"  4 (default) | 3 | 5: blur_dist_tiled_kernel keeps one minimum per 2^v columns of a staged row and
+ *                      skips a chunk whose minimum cannot beat the best distance so far (A/B runs) */
 int mi_blur_set_option(const char *key, int value);
 
 /* Number of visible HIP devices (0 is a valid answer: CPU-device contexts still work).
@@ -994,6 +998,105 @@ int mi_blur_run_integral(int device, const uint8_t *host_in, uint32_t *host_sum 
                          uint32_t *host_sqsum /* may be NULL */, int width, int height, int channels, int n_images);
 int mi_blur_run_box(int device, const uint8_t *host_in, uint8_t *host_out, int width, int height, int channels, int n_images,
                     const mi_blur_box *k);
+
+/* ------------------------------------------------------------------------
+ * Exact distance transform (squared Euclidean, city block, chessboard) and, from it, dilation and erosion of masks by a
+ * disc, diamond or square of any radius up to 32767 (OpenCV's distanceTransform; no reference analogue).  Integers only:
+ * the GPU, the CPU device and a numpy / brute-force restatement agree word for word.  Like the histogram and integral
+ * families it is not a filter of a context: it produces a table and needs a work buffer.
+ *
+ * Images: n_images interleaved dense images of W x H x C, channels 1..4, within the histogram family's limits.
+ * n_images == 0 is MI_BLUR_OK and launches nothing.  Channels are independent, and so are images.
+ *
+ * Sites: in image i and channel c, pixel (x, y) is a site when in == 0; with sites_nonzero = 1, when in != 0.  Zero is
+ * OpenCV's convention.  Only pixels inside the image can be sites: there is no border rule.
+ *
+ * Table value T(x, y, c), uint32[n_images][H][W][C], over the sites (x', y') of the same image and channel:
+ *   MI_BLUR_DIST_L2    min of (x - x')^2 + (y - y')^2: the SQUARED Euclidean distance, at most 2 * 32767^2 < 2^31;
+ *   MI_BLUR_DIST_L1    min of |x - x'| + |y - y'|;
+ *   MI_BLUR_DIST_LINF  min of max(|x - x'|, |y - y'|).
+ * A channel with no site has MI_BLUR_DIST_NONE everywhere.  limit is 0 (none) or 1..MI_BLUR_DIST_MAX_LIMIT: with a limit
+ * L, T is exact where the distance is at most L (T <= L^2 for L2, T <= L for the other two) and MI_BLUR_DIST_NONE
+ * everywhere else.  The limit is part of the definition; it bounds the search to 2 L + 1 columns.
+ *
+ * Byte forms, made from T by byte_op:
+ *   MI_BLUR_DIST_BYTE    NONE -> 255.  L2: min(255, s) with s the largest integer with s == 0 or (2 s - 1)^2 <= 4 T:
+ *                        sqrt(T) rounded once, half up, decided in integers (BOX_STDDEV's convention).  L1, LINF: min(255, T).
+ *   MI_BLUR_DIST_WITHIN  needs limit >= 1: 255 where T != NONE, else 0; invert (0 | 1) swaps the two.  With sites_nonzero
+ *                        this is the dilation of a mask by the metric's ball of radius limit (a disc, a diamond, a
+ *                        square); with zero sites and invert, its erosion.
+ * Fields a call does not use must be 0: byte_op and invert in the table calls, invert outside WITHIN.  A value outside
+ * its range, a non-zero unused field or WITHIN with limit == 0 is MI_BLUR_ERR_INVALID, the output untouched.
+ *
+ * Method, everywhere: g(x, y, c) = the distance along the column to the nearest site of that column (or "none"; with a
+ * limit, anything above it is "none" too), then T = min over x' of dx^2 + g^2 (L2), dx + g (L1), max(dx, g) (LINF) with
+ * dx = |x - x'| and g = g(x', y, c): exact for all three, and a search outwards from dx = 0 may stop as soon as dx alone
+ * (dx^2 for L2) reaches the best value so far.
+ * ---------------------------------------------------------------------- */
+#define MI_BLUR_DIST_MAX_LIMIT 32767
+#define MI_BLUR_DIST_NONE 0xFFFFFFFFu
+typedef enum { MI_BLUR_DIST_L2 = 0, MI_BLUR_DIST_L1 = 1, MI_BLUR_DIST_LINF = 2 } mi_blur_dist_metric;
+typedef enum { MI_BLUR_DIST_BYTE = 0, MI_BLUR_DIST_WITHIN = 1 } mi_blur_dist_byte_op;
+typedef struct mi_blur_dist {
+    int metric;             /* mi_blur_dist_metric */
+    int sites_nonzero;      /* 0: a site is in == 0 (OpenCV) | 1: a site is in != 0 */
+    int limit;              /* 0 = none | 1..MI_BLUR_DIST_MAX_LIMIT */
+    int byte_op;            /* mi_blur_dist_byte_op; the table calls: must be 0 */
+    int invert;             /* WITHIN: 0 | 1; otherwise must be 0 */
+} mi_blur_dist;
+
+/* The definition of the byte forms for one table value (host only): the byte for T = t.  -1 for a *k that is invalid for
+ * the byte calls, or a t that no image can give under *k: above the metric's maximum (2 * 32767^2, 2 * 32767, 32767) or
+ * above the limit (limit^2 for L2), and not MI_BLUR_DIST_NONE. */
+int mi_blur_dist_value(const mi_blur_dist *k, uint32_t t);
+
+/* Bytes of the work buffer of the two enqueue calls: g as uint16[n_images][H][W * C] (rounded up to 16 bytes), then per
+ * band of the "dist_band" rows in force (32 by default) the first and the last site row of every column,
+ * uint16[n_images][ceil(H / band)][2][W * C].  0 for an invalid *k (as mi_blur_dist_value), an image outside the limits
+ * or n_images < 0. */
+size_t mi_blur_dist_work_bytes(int width, int height, int channels, int n_images, const mi_blur_dist *k);
+/* The table T of n_images images (device memory, asynchronous on `stream`): d_table = uint32[n_images][H][W][C], 16-byte
+ * aligned, OVERWRITTEN; d_work: device memory, 16-byte aligned, mi_blur_dist_work_bytes() bytes.  MI_BLUR_ERR_INVALID
+ * (every argument is checked before a device is asked for, so before MI_BLUR_ERR_NO_DEVICE): a null d_in, d_table, k or
+ * d_work, d_table or d_work not 16-byte aligned, an invalid *k (byte_op and invert must be 0), channels outside 1..4, a
+ * size outside the limits, n_images < 0.
+ * No workgroup of these kernels ever waits for another; the dispatches on the one stream do the ordering.  Every loop has
+ * a bound known at launch.  Four dispatches:
+ *  (1) blur_dist_bands_kernel: per (image, band of rows, column and channel) the first and the last site row, to d_work.
+ *  (2) blur_dist_carry_kernel: per column the walk over the bands of an image, both ways, in place: the last site row
+ *      above each band and the first one below it.
+ *  (3) blur_dist_cols_kernel: every band sweeps down and up from those carries: g, to d_work.  Threads of (1)-(3) run
+ *      along W * C; any shape and alignment.
+ *  (4) the row pass.  blur_dist_tiled_kernel takes exactly the launches with W * C a multiple of 8 and at most 24576
+ *      (and, for the byte form, d_out 16-byte aligned): a workgroup of 256 threads owns max(1, min(8, 4096 / (W * C)))
+ *      whole rows, stages their g in LDS one plane per channel (rows padded with "none" to whole chunks of 16 columns:
+ *      at most 34 bytes per 16 elements, 52.4 KiB), keeps the minimum of every chunk next to it, and a thread owns 4
+ *      consecutive outputs: per output first the columns nearer than 16, one dx at a time on both sides (with dense
+ *      sites the search ends there), then the other chunks outwards, left and right in turn: it stops a side when the
+ *      chunk's nearest dx alone cannot beat the best value so far, skips a chunk whose minimum cannot, and reads the 16
+ *      entries of the others; one 16-byte store of 4 words (or one 4-byte store of 4 bytes).  Every other launch goes to
+ *      blur_dist_generic_kernel: one output per thread (a capped grid that strides), searching g outwards in global
+ *      memory, at most W steps.  mi_blur_last_kernel() says which of the two ran. */
+int mi_blur_enqueue_dist(const uint8_t *d_in, uint32_t *d_table, int width, int height, int channels, int n_images,
+                         const mi_blur_dist *k, void *d_work, void *stream);
+/* The byte form *k of the same (byte_op, invert): it goes straight from the row pass, the 32-bit table never reaches
+ * memory.  d_out = uint8 of the images' shape, any alignment.  d_out == d_in is allowed (the column pass has consumed the
+ * input before the row pass stores); every other overlap of the two is MI_BLUR_ERR_INVALID. */
+int mi_blur_enqueue_dist_u8(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int n_images,
+                            const mi_blur_dist *k, void *d_work, void *stream);
+/* The same on the CPU device's threads (synchronous), host memory; the table 4-byte aligned; the call allocates g
+ * (MI_BLUR_ERR_NOMEM if it cannot).  Columns in strips across the threads, then rows. */
+int mi_blur_cpu_run_dist(const uint8_t *in, uint32_t *table, int width, int height, int channels, int n_images,
+                         const mi_blur_dist *k, int n_threads);
+int mi_blur_cpu_run_dist_u8(const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,
+                            const mi_blur_dist *k, int n_threads);
+/* Blocking, host memory in and out: allocate on `device` (a HIP ordinal), copy in, enqueue, copy out, free.
+ * device == MI_BLUR_DEVICE_CPU calls the cpu_run forms with all threads.  MI_BLUR_ERR_NO_DEVICE where there is no such
+ * device, after the argument checks. */
+int mi_blur_run_dist(int device, const uint8_t *host_in, uint32_t *host_table, int width, int height, int channels,
+                     int n_images, const mi_blur_dist *k);
+int mi_blur_run_dist_u8(int device, const uint8_t *host_in, uint8_t *host_out, int width, int height, int channels,
+                        int n_images, const mi_blur_dist *k);
 
 /* ------------------------------------------------------------------------
  * Affine warp: exact fixed-point rotate, scale, shear and translate, any output size (no reference analogue).  The
