@@ -51,6 +51,7 @@ COLOR_MAX_CHANNELS = 4
 COLOR_CODES = {"rgb2gray": 0, "bgr2gray": 1, "gray2rgb": 2, "rgb2bgr": 3, "rgba2bgra": 4, "rgba2rgb": 5, "rgb2rgba": 6,
                "rgb2ycbcr": 7, "ycbcr2rgb": 8}
 HIST_BINS = 256
+CLAHE_MAX_TILES = 64
 TONE_EQUALIZE, TONE_STRETCH = 0, 1
 TONE_MODES = {"equalize": TONE_EQUALIZE, "stretch": TONE_STRETCH}
 ARITH_LINEAR, ARITH_ABSDIFF, ARITH_MIN, ARITH_MAX, ARITH_MUL, ARITH_LERP = range(6)
@@ -77,7 +78,7 @@ def _newer(target: str, sources: list[str]) -> bool:
 
 def build_native(force: bool = False, verbose: bool = False) -> str:
     """Compile libmi_blur.so (hipcc, --offload-arch=gfx950) and the C++ hosts, in-tree."""
-    srcs = [os.path.join(CSRC, f) for f in ("blur_kernels.hip", "sep_kernels.hip", "median_kernels.hip", "morph_kernels.hip", "bilateral_kernels.hip", "conv_kernels.hip", "sep_down_kernels.hip", "resize_kernels.hip", "warp_kernels.hip", "remap_kernels.hip", "area_kernels.hip", "color_kernels.hip", "hist_kernels.hip", "arith_kernels.hip", "integral_kernels.hip", "dist_kernels.hip", "layout_kernels.hip", "mi_blur_api.cpp", "comm_api.cpp", "cpu_device.cpp")]
+    srcs = [os.path.join(CSRC, f) for f in ("blur_kernels.hip", "sep_kernels.hip", "median_kernels.hip", "morph_kernels.hip", "bilateral_kernels.hip", "conv_kernels.hip", "sep_down_kernels.hip", "resize_kernels.hip", "warp_kernels.hip", "remap_kernels.hip", "area_kernels.hip", "color_kernels.hip", "hist_kernels.hip", "clahe_kernels.hip", "arith_kernels.hip", "integral_kernels.hip", "dist_kernels.hip", "layout_kernels.hip", "mi_blur_api.cpp", "comm_api.cpp", "cpu_device.cpp")]
     deps = srcs + [os.path.join(CSRC, f) for f in ("api_internal.h", "blur_launch.h", "kernel_common.h", "cpu_device.h", "filter.h")] + [HEADER]
     if force or not _newer(LIB_PATH, deps):
         cmd = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra",
@@ -261,6 +262,11 @@ class Color(C.Structure):
 class Tone(C.Structure):
     """mi_blur_tone: the mode, the two clips (Q16 shares, STRETCH only), joint and the channel mask (0 = all)."""
     _fields_ = [("mode", C.c_int), ("clip_lo", C.c_int), ("clip_hi", C.c_int), ("joint", C.c_int), ("channel_mask", C.c_int)]
+
+
+class Clahe(C.Structure):
+    """mi_blur_clahe: the tile grid, the clip limit in Q8 (0 = none) and the channel mask (0 = all)."""
+    _fields_ = [("tiles_x", C.c_int), ("tiles_y", C.c_int), ("clip_q8", C.c_int), ("channel_mask", C.c_int)]
 
 
 class Arith(C.Structure):
@@ -469,6 +475,16 @@ def lib() -> C.CDLL:
         "mi_blur_cpu_run_tone": (i, [u8p, u8p, i, i, i, i, C.POINTER(Tone), vp, i]),
         "mi_blur_run_hist": (i, [i, u8p, vp, i, i, i, i]),
         "mi_blur_run_tone": (i, [i, u8p, u8p, vp, i, i, i, i, C.POINTER(Tone)]),
+        "mi_blur_clahe_coord": (i, [i, i, i, C.POINTER(i), C.POINTER(i), C.POINTER(i)]),
+        "mi_blur_clahe_table": (i, [vp, C.c_uint32, i, u8p]),
+        "mi_blur_clahe_work_bytes": (C.c_size_t, [i, i, i, i, C.POINTER(Clahe)]),
+        "mi_blur_enqueue_clahe_tables": (i, [u8p, i, i, i, i, C.POINTER(Clahe), vp, vp]),
+        "mi_blur_enqueue_clahe_apply": (i, [u8p, u8p, i, i, i, i, C.POINTER(Clahe), u8p, vp]),
+        "mi_blur_enqueue_clahe": (i, [u8p, u8p, i, i, i, i, C.POINTER(Clahe), vp, vp]),
+        "mi_blur_cpu_run_clahe_tables": (i, [u8p, i, i, i, i, C.POINTER(Clahe), vp, i]),
+        "mi_blur_cpu_run_clahe_apply": (i, [u8p, u8p, i, i, i, i, C.POINTER(Clahe), u8p, i]),
+        "mi_blur_cpu_run_clahe": (i, [u8p, u8p, i, i, i, i, C.POINTER(Clahe), vp, i]),
+        "mi_blur_run_clahe": (i, [i, u8p, u8p, vp, i, i, i, i, C.POINTER(Clahe)]),
         "mi_blur_arith_preset": (i, [i, C.POINTER(Arith)]),
         "mi_blur_arith_weighted": (i, [C.c_double, C.c_double, C.c_double, C.POINTER(Arith)]),
         "mi_blur_arith_value": (i, [C.POINTER(Arith), i, i, i]),
@@ -1301,6 +1317,77 @@ def auto_levels(images, clip=0.0, joint: bool = True, channels=None, device: int
     t = _tone("stretch", _clip_q16(clip, "auto_levels"), joint, channels, a.shape[3], "auto_levels")
     out = _tone_run(a, t, device, batch, "auto_levels")
     return out if rank == 4 else out[0] if rank == 3 else out[0, :, :, 0]
+
+
+def _clahe(clip_limit, tiles, channels, c: int, name: str) -> "Clahe":
+    """A Clahe for images of c channels.  clip_limit: OpenCV's clipLimit, 0..256 (0 = no clipping), taken as
+    floor(clip_limit * 256); tiles: (tiles_x, tiles_y); channels: None (all) or the indices of the channels to transform."""
+    import math
+    if not 0.0 <= float(clip_limit) <= 256.0:
+        raise ValueError(f"{name}: clip_limit is in 0..256")
+    tx, ty = (int(v) for v in tiles)
+    mask = 0
+    for ch in (() if channels is None else channels):
+        if not 0 <= int(ch) < c:
+            raise ValueError(f"{name}: channel {ch} of {c}")
+        mask |= 1 << int(ch)
+    return Clahe(tx, ty, int(math.floor(float(clip_limit) * 256.0)), mask)
+
+
+def _clahe_run(a, k: "Clahe", device: int, batch: int, name: str, want_work: bool = False):
+    """a (N, H, W, C) through mi_blur_run_clahe, `batch` images per call (0 = all at once): the output, and with want_work
+    the tile histograms uint32 (N, TY, TX, C, 256) and the tile tables uint8 of the same shape."""
+    import numpy as np
+    n, h, w, c = a.shape
+    out = np.empty_like(a)
+    shape = (n, k.tiles_y, k.tiles_x, c, HIST_BINS)
+    hist, tables = (np.empty(shape, np.uint32), np.empty(shape, np.uint8)) if want_work else (None, None)
+    per = batch if batch > 0 else max(n, 1)
+    for i in range(0, n, per):
+        m = min(per, n - i)
+        words = m * k.tiles_y * k.tiles_x * c * HIST_BINS
+        work = np.empty(5 * words, np.uint8) if want_work else None
+        check(lib().mi_blur_run_clahe(device, a[i:].ctypes.data, out[i:].ctypes.data, None if work is None else work.ctypes.data,
+                                      w, h, c, m, C.byref(k)), name)
+        if want_work:
+            hist[i:i + m] = work[:4 * words].view(np.uint32).reshape((m,) + shape[1:])
+            tables[i:i + m] = work[4 * words:].reshape((m,) + shape[1:])
+    return (out, hist, tables) if want_work else out
+
+
+def clahe(images, clip_limit: float = 2.0, tiles=(8, 8), mode: str = "channel", channels=None, device: int = 0, batch: int = 0):
+    """CLAHE (mi_blur_run_clahe; include/mi_blur.h, "CLAHE" has the definition), numpy in -> numpy out of the same shape:
+    every tile of a tiles = (tiles_x, tiles_y) grid gets its own table from its histogram clipped at clip_limit (OpenCV's
+    clipLimit; 0 = no clipping), and every pixel the blend of the four tables around it.  mode "channel": every channel
+    (or those of `channels`) on its own; "luma" (3 channels): cvt_color(rgb2ycbcr), CLAHE on Y, cvt_color(ycbcr2rgb).
+    The tiles are the image's own (no padding) and the arithmetic is integer: OpenCV's formula, not its bytes."""
+    if mode not in ("channel", "luma"):
+        raise ValueError('clahe: mode is "channel" or "luma"')
+    a, rank = _tone_stack(images, "clahe")
+    c = a.shape[3]
+    if mode == "luma":
+        if c != 3:
+            raise ValueError('clahe: "luma" needs 3 channels')
+        ycc = cvt_color(a, "rgb2ycbcr", device, batch)
+        out = cvt_color(_clahe_run(ycc, _clahe(clip_limit, tiles, (0,), 3, "clahe"), device, batch, "clahe"), "ycbcr2rgb", device, batch)
+    else:
+        out = _clahe_run(a, _clahe(clip_limit, tiles, channels, c, "clahe"), device, batch, "clahe")
+    return out if rank == 4 else out[0] if rank == 3 else out[0, :, :, 0]
+
+
+def clahe_tables(images, clip_limit: float = 2.0, tiles=(8, 8), channels=None, device: int = 0, batch: int = 0):
+    """(hist, tables) of clahe(): the raw tile histograms uint32 (N, TY, TX, C, 256) and the tile tables uint8 of the same
+    shape (without the leading N for one image)."""
+    a, rank = _tone_stack(images, "clahe_tables")
+    _, hist, tables = _clahe_run(a, _clahe(clip_limit, tiles, channels, a.shape[3], "clahe_tables"), device, batch, "clahe_tables", True)
+    return (hist, tables) if rank == 4 else (hist[0], tables[0])
+
+
+def clahe_coord(size: int, tiles: int, x: int) -> tuple[int, int, int]:
+    """(t0, t1, frac) of pixel x on an axis of `size` pixels and `tiles` tiles (mi_blur_clahe_coord)."""
+    t0, t1, f = C.c_int(), C.c_int(), C.c_int()
+    check(lib().mi_blur_clahe_coord(int(size), int(tiles), int(x), C.byref(t0), C.byref(t1), C.byref(f)), "mi_blur_clahe_coord")
+    return t0.value, t1.value, f.value
 
 
 def integral(images, square: bool = False, pad: bool = False, device: int = 0, batch: int = 0):

@@ -88,6 +88,14 @@ int launch_box_from_integral(const uint8_t *in, const uint32_t *sum, const uint3
 // is the struct of that call.  Every argument is checked (dist_args_ok(), filter.h: MI_BLUR_ERR_INVALID), an empty batch
 // is MI_BLUR_OK.  work = dist_work_bytes() bytes for the band in force (tunables().dist_band), 16-byte aligned.
 int launch_dist(const uint8_t *in, uint32_t *table, uint8_t *out, int W, int H, int C, int n_images, const mi_blur_dist &k, void *work, hipStream_t stream);
+// CLAHE (clahe_kernels.hip); no Filter and no LaunchDesc.  Dense images of W x H x C, n_images of them; every argument
+// is checked (clahe_ok(), hist_image_ok(), filter.h: MI_BLUR_ERR_INVALID), an empty batch is MI_BLUR_OK.
+// launch_clahe_tables: hist = uint32[n][TY][TX][C][256], 16-byte aligned, and tables = uint8[n][TY][TX][C][256], both
+// overwritten.  launch_clahe_apply: every pixel through the four tables around it; tables at any alignment.
+int launch_clahe_tables(const uint8_t *in, uint32_t *hist, uint8_t *tables, int W, int H, int C, int n_images, const mi_blur_clahe &k,
+                        hipStream_t stream);
+int launch_clahe_apply(const uint8_t *in, uint8_t *out, int W, int H, int C, int n_images, const mi_blur_clahe &k, const uint8_t *tables,
+                       hipStream_t stream);
 // Sets what last_kernel() reports for the calling thread.
 void set_last_kernel(const char *name);
 

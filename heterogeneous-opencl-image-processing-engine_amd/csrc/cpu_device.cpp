@@ -704,6 +704,71 @@ void for_items(long long items, int n_threads, F &&body)
 }
 }  // namespace
 
+// CLAHE.  Items (for_items() above) are (image, tile) for the tables and (image, band of 16 rows) for the look-up.
+// A tile's histogram by a walk over its rows, then clahe_table() (filter.h) per transformed channel.
+void cpu_clahe_tables(const uint8_t *in, uint32_t *hist, uint8_t *tables, int W, int H, int C, int n_images, const mi_blur_clahe &k, int n_threads)
+{
+    if (n_images <= 0) return;
+    if (n_threads <= 0) n_threads = hardware_threads();
+    const int TX = k.tiles_x, TY = k.tiles_y, mask = tone_mask(k.channel_mask, C);
+    for_items((long long)n_images * TY * TX, n_threads, [&](long long job) {
+        const int img = (int)(job / (TY * TX)), tile = (int)(job % (TY * TX)), ty = tile / TX, tx = tile % TX;
+        const int x0 = clahe_edge(W, TX, tx), x1 = clahe_edge(W, TX, tx + 1), y0 = clahe_edge(H, TY, ty), y1 = clahe_edge(H, TY, ty + 1);
+        uint32_t *h = hist + (size_t)job * C * MI_BLUR_HIST_BINS;
+        uint8_t *lut = tables + (size_t)job * C * MI_BLUR_HIST_BINS;
+        memset(h, 0, (size_t)C * MI_BLUR_HIST_BINS * sizeof(uint32_t));
+        for (int y = y0; y < y1; y++) {
+            const uint8_t *px = in + (((size_t)img * H + y) * W + x0) * C;
+            for (int x = x0; x < x1; x++, px += C)
+                for (int c = 0; c < C; c++) h[c * MI_BLUR_HIST_BINS + px[c]]++;
+        }
+        const uint32_t A = (uint32_t)(x1 - x0) * (uint32_t)(y1 - y0);
+        for (int c = 0; c < C; c++) {
+            if ((mask >> c) & 1) clahe_table(h + c * MI_BLUR_HIST_BINS, A, k.clip_q8, lut + c * MI_BLUR_HIST_BINS);
+            else for (int v = 0; v < MI_BLUR_HIST_BINS; v++) lut[c * MI_BLUR_HIST_BINS + v] = (uint8_t)v;
+        }
+    });
+}
+
+// out = bilinear_blend() of the four tables' bytes; the columns' (t0, t1, frac) are worked out once.
+void cpu_clahe_apply(const uint8_t *in, uint8_t *out, int W, int H, int C, int n_images, const mi_blur_clahe &k, const uint8_t *tables, int n_threads)
+{
+    if (n_images <= 0) return;
+    if (n_threads <= 0) n_threads = hardware_threads();
+    const int TX = k.tiles_x, TY = k.tiles_y, BAND = 16, bands = (H + BAND - 1) / BAND;
+    struct Col { int t0, t1, f; };
+    std::vector<Col> cols((size_t)W);
+    for (int x = 0; x < W; x++) clahe_axis(W, TX, x, cols[x].t0, cols[x].t1, cols[x].f);
+    const size_t tile = (size_t)C * MI_BLUR_HIST_BINS;
+    for_items((long long)n_images * bands, n_threads, [&](long long it) {
+        const int img = (int)(it / bands), band = (int)(it % bands);
+        const uint8_t *tab = tables + (size_t)img * TY * TX * tile;
+        for (int y = band * BAND; y < std::min(H, (band + 1) * BAND); y++) {
+            int ty0, ty1, fy;
+            clahe_axis(H, TY, y, ty0, ty1, fy);
+            const uint8_t *r0 = tab + (size_t)ty0 * TX * tile, *r1 = tab + (size_t)ty1 * TX * tile;
+            const uint8_t *px = in + ((size_t)img * H + y) * W * C;
+            uint8_t *o = out + ((size_t)img * H + y) * W * C;
+            for (int x = 0; x < W; x++, px += C, o += C) {
+                const size_t a = cols[x].t0 * tile, b = cols[x].t1 * tile;
+                for (int c = 0; c < C; c++) {
+                    const size_t e = (size_t)c * MI_BLUR_HIST_BINS + px[c];
+                    o[c] = (uint8_t)bilinear_blend(r0[a + e], r0[b + e], r1[a + e], r1[b + e], (unsigned)cols[x].f, (unsigned)fy);
+                }
+            }
+        }
+    });
+}
+
+void cpu_clahe(const uint8_t *in, uint8_t *out, int W, int H, int C, int n_images, const mi_blur_clahe &k, void *work, int n_threads)
+{
+    if (n_images <= 0) return;
+    uint32_t *hist = static_cast<uint32_t *>(work);
+    uint8_t *tables = reinterpret_cast<uint8_t *>(hist + clahe_tables_of(n_images, k, C) * MI_BLUR_HIST_BINS);
+    cpu_clahe_tables(in, hist, tables, W, H, C, n_images, k, n_threads);
+    cpu_clahe_apply(in, out, W, H, C, n_images, k, tables, n_threads);
+}
+
 bool cpu_integral(const uint8_t *in, uint32_t *sum, uint32_t *sqsum, int W, int H, int C, int n_images, int n_threads)
 {
     if (n_images <= 0) return true;

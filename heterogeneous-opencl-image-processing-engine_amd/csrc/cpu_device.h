@@ -59,6 +59,12 @@ inline void cpu_blur_batch(const uint8_t *in, uint8_t *out, int W, int band_rows
 void cpu_hist(const uint8_t *in, uint32_t *hist, int W, int H, int C, int n_images, int n_threads);
 void cpu_tables(const uint8_t *in, uint8_t *out, int W, int H, int C, int n_images, const uint8_t *tables, int n_threads);
 void cpu_tone(const uint8_t *in, uint8_t *out, int W, int H, int C, int n_images, const mi_blur_tone &t, void *work, int n_threads);
+// CLAHE (include/mi_blur.h, "CLAHE"); the callers have checked the arguments.  cpu_clahe_tables: hist =
+// uint32[n][TY][TX][C][256] and tables = uint8[n][TY][TX][C][256], both overwritten.  cpu_clahe_apply: every pixel through
+// the four tables around it.  cpu_clahe: both; work (4-byte aligned) receives the histograms, then the tables.
+void cpu_clahe_tables(const uint8_t *in, uint32_t *hist, uint8_t *tables, int W, int H, int C, int n_images, const mi_blur_clahe &k, int n_threads);
+void cpu_clahe_apply(const uint8_t *in, uint8_t *out, int W, int H, int C, int n_images, const mi_blur_clahe &k, const uint8_t *tables, int n_threads);
+void cpu_clahe(const uint8_t *in, uint8_t *out, int W, int H, int C, int n_images, const mi_blur_clahe &k, void *work, int n_threads);
 // The two-image arithmetic (include/mi_blur.h, "Two-image arithmetic") on n_images dense W x H x C images; the callers
 // have checked the arguments (arith_args_ok(), filter.h).  Every byte is arith_byte(); a thread reads a byte's operands
 // before it writes the byte, so out may be a, or b where b has the output's extent.

@@ -521,6 +521,76 @@ inline void tone_tables(const mi_blur_tone &t, const uint32_t *hist, int C, uint
     }
 }
 
+// ---- CLAHE (include/mi_blur.h, "CLAHE").  The host exports mi_blur_clahe_coord and mi_blur_clahe_table, the CPU device
+// and the four kernels take a tile's edges from clahe_edge(), a bin after clipping from clahe_bin(), a table's byte from
+// clahe_entry(), a pixel's tiles and weight on one axis from clahe_axis() and the output byte from bilinear_blend().
+inline bool clahe_ok(const mi_blur_clahe *k, int W, int H, int C)
+{
+    if (!k || C < 1 || C > MI_BLUR_COLOR_MAX_CHANNELS) return false;
+    if (k->tiles_x < 1 || k->tiles_y < 1 || k->tiles_x > MI_BLUR_CLAHE_MAX_TILES || k->tiles_y > MI_BLUR_CLAHE_MAX_TILES) return false;
+    if (k->tiles_x > W || k->tiles_y > H) return false;
+    return k->clip_q8 >= 0 && k->clip_q8 <= 65536 && k->channel_mask >= 0 && k->channel_mask < (1 << C);
+}
+// b_t = floor(t * S / T): S <= 32768 and t <= T <= 64, so 32 bits hold it.
+MI_BLUR_HD inline int clahe_edge(int S, int T, int t) { return (int)((unsigned)t * (unsigned)S / (unsigned)T); }
+// m_t = b_t + b_(t+1): the centre of tile t in half-pixels.
+MI_BLUR_HD inline int clahe_mid(int S, int T, int t) { return clahe_edge(S, T, t) + clahe_edge(S, T, t + 1); }
+// (t0, t1, frac) of pixel x on an axis of S pixels and T <= S tiles.  x lies in tile t = ceil((x + 1) T / S) - 1, and
+// with p = 2x + 1: 2 b_t < p < 2 b_(t+1), so m_(t-1) < p < m_(t+1) (no tile is empty) and t0 is t or t - 1.
+MI_BLUR_HD inline void clahe_axis(int S, int T, int x, int &t0, int &t1, int &frac)
+{
+    const int p = 2 * x + 1;
+    if (T == 1 || p <= clahe_mid(S, T, 0)) { t0 = t1 = 0; frac = 0; return; }
+    if (p >= clahe_mid(S, T, T - 1)) { t0 = t1 = T - 1; frac = 0; return; }
+    const int t = (int)((((unsigned)x + 1u) * (unsigned)T - 1u) / (unsigned)S);
+    int m0 = clahe_mid(S, T, t);
+    t0 = t;
+    if (m0 > p) { t0 = t - 1; m0 = clahe_mid(S, T, t0); }
+    t1 = t0 + 1;
+    frac = (int)((unsigned)(p - m0) * BLEND_ONE / (unsigned)(clahe_mid(S, T, t1) - m0));      // (p - m0) < 2 S <= 2^16
+}
+// Pixels on an axis fall into T + 1 classes by the tiles they blend: class k = the number of centres m_t <= p, whose
+// pixels take the tiles max(k - 1, 0) and min(k, T - 1) (at p == m_0 that is (0, 1) with frac 0 where clahe_axis() says
+// (0, 0): the same byte).  Class k is the pixels [clahe_class_lo(k), clahe_class_lo(k + 1)); it may be empty.
+MI_BLUR_HD inline int clahe_class_lo(int S, int T, int k) { return k <= 0 ? 0 : k > T ? S : clahe_mid(S, T, k - 1) >> 1; }
+// The clip of a tile of A pixels.  clip_q8 == 0 (no clipping) is the clip A: no bin holds more.
+MI_BLUR_HD inline uint32_t clahe_clip(uint32_t A, int clip_q8)
+{
+    if (clip_q8 == 0) return A;
+    const uint64_t c = ((uint64_t)(unsigned)clip_q8 * A) >> 16;
+    return c < 1 ? 1u : (uint32_t)c;
+}
+MI_BLUR_HD inline uint32_t clahe_over(uint32_t h, uint32_t clip) { return h > clip ? h - clip : 0u; }
+// h'(v): bin v clipped, plus its share of `excess` = the sum of clahe_over() over the bins.
+MI_BLUR_HD inline uint32_t clahe_bin(uint32_t h, uint32_t clip, uint32_t excess, int v)
+{
+    const uint32_t residual = excess % MI_BLUR_HIST_BINS;
+    uint32_t r = (h < clip ? h : clip) + excess / MI_BLUR_HIST_BINS;
+    if (residual) {
+        const uint32_t q = MI_BLUR_HIST_BINS / residual, step = q < 1 ? 1u : q;
+        if ((uint32_t)v % step == 0 && (uint32_t)v / step < residual) r++;
+    }
+    return r;
+}
+// lut[v] from c(v) and the area: 255 c / A rounded once, half up.
+MI_BLUR_HD inline uint8_t clahe_entry(uint64_t cv, uint64_t A)
+{
+    if (A < (1u << 22)) return (uint8_t)((510u * (uint32_t)cv + (uint32_t)A) / (2u * (uint32_t)A));     // the same value in 32 bits: cv <= A
+    return (uint8_t)((510u * cv + A) / (2u * A));
+}
+// One table from one histogram whose bins sum to A > 0.
+inline void clahe_table(const uint32_t *hist, uint32_t A, int clip_q8, uint8_t *lut)
+{
+    const uint32_t clip = clahe_clip(A, clip_q8);
+    uint64_t excess = 0, run = 0;
+    for (int v = 0; v < MI_BLUR_HIST_BINS; v++) excess += clahe_over(hist[v], clip);
+    for (int v = 0; v < MI_BLUR_HIST_BINS; v++) {
+        run += clahe_bin(hist[v], clip, (uint32_t)excess, v);
+        lut[v] = clahe_entry(run, A);
+    }
+}
+inline size_t clahe_tables_of(int n_images, const mi_blur_clahe &k, int C) { return (size_t)n_images * (size_t)k.tiles_y * (size_t)k.tiles_x * (size_t)C; }
+
 // ---- two-image arithmetic (include/mi_blur.h, "Two-image arithmetic").  The host export mi_blur_arith_value, the CPU
 // device and all three kernels take an output byte from arith_byte(); the tiled kernels call it with a constant op.
 constexpr int32_t ARITH_MAX_W = 1 << 16, ARITH_MAX_W_MUL = 1 << 10, ARITH_MAX_BIAS = 1 << 26;
@@ -1281,6 +1351,48 @@ inline int hist_runs(int W, int H) { return (int)(((long long)W * H / COLOR_GROU
 // counters, and that row takes about one flush per 16 ns whoever sends it (profiles/r19_hist.md).
 constexpr int HIST_IMAGE_BLOCKS = 256;
 inline int hist_blocks(int W, int H) { const int r = hist_runs(W, H); return r < HIST_IMAGE_BLOCKS ? r : HIST_IMAGE_BLOCKS; }
+
+// ---- the CLAHE kernels.  Both tiled kernels take rows of whole groups of COLOR_GROUP pixels (W a multiple of 16) and
+// 16-byte aligned images, so a group is C chunks of 16 bytes and never straddles a row; tile edges fall anywhere.
+// blur_clahe_tables_tiled_kernel and its generic form: one workgroup of CLAHE_THREADS threads (= bins) per (image, tile);
+// the generic form has at most CLAHE_GENERIC_BLOCKS workgroups, which stride over the tiles.
+// blur_clahe_apply_tiled_kernel: a workgroup owns up to CLAHE_ROWS rows of one row class (clahe_class_lo()) and a span of
+// CLAHE_SPAN pixels; it stages the tables of both tile rows for the tile columns from t0 of the span's first pixel to t1
+// of its last.  The launch is tiled when the widest such run of columns, times 2 * C * 256 bytes, fits
+// CLAHE_LDS_TABLE_BYTES.
+constexpr int CLAHE_THREADS = 256;
+constexpr int CLAHE_GENERIC_BLOCKS = 256 * 64;
+constexpr int CLAHE_SPAN = 256;                     // pixels: 16 groups
+constexpr int CLAHE_ROWS = 32;
+constexpr int CLAHE_LDS_TABLE_BYTES = 32768;
+constexpr int CLAHE_LDS_TABLE = MI_BLUR_HIST_BINS + 4;      // a staged table's stride: one bank on from its neighbour
+static_assert(CLAHE_THREADS == MI_BLUR_HIST_BINS && CLAHE_SPAN == CLAHE_THREADS, "thread v is bin v, and column v of a span");
+inline bool clahe_tiled_ok(int W) { return W % COLOR_GROUP == 0; }
+inline int clahe_spans(int W) { return (W + CLAHE_SPAN - 1) / CLAHE_SPAN; }
+// The most tile columns one span needs.
+inline int clahe_span_cols(int W, int TX)
+{
+    int most = 1;
+    for (int s = 0; s < clahe_spans(W); s++) {
+        const int xa = s * CLAHE_SPAN, xb = (xa + CLAHE_SPAN < W ? xa + CLAHE_SPAN : W) - 1;
+        int a0, a1, b0, b1, f;
+        clahe_axis(W, TX, xa, a0, a1, f);
+        clahe_axis(W, TX, xb, b0, b1, f);
+        most = b1 - a0 + 1 > most ? b1 - a0 + 1 : most;
+    }
+    return most;
+}
+inline size_t clahe_table_lds(int W, int TX, int C) { return (size_t)clahe_span_cols(W, TX) * 2u * (size_t)C * MI_BLUR_HIST_BINS; }
+// LDS bytes of the staged tables with their padding, to 16 bytes (the entries behind them are read 16 bytes at a time).
+MI_BLUR_HD inline size_t clahe_apply_lds_tables(int max_cols, int C) { return ((size_t)2 * max_cols * C * CLAHE_LDS_TABLE + 15) & ~(size_t)15; }
+inline bool clahe_apply_tiled_ok(int W, int TX, int C) { return clahe_tiled_ok(W) && clahe_table_lds(W, TX, C) <= (size_t)CLAHE_LDS_TABLE_BYTES; }
+// Slices of up to CLAHE_ROWS rows of all row classes of an image.
+inline int clahe_slices(int H, int TY)
+{
+    int n = 0;
+    for (int k = 0; k <= TY; k++) n += (clahe_class_lo(H, TY, k + 1) - clahe_class_lo(H, TY, k) + CLAHE_ROWS - 1) / CLAHE_ROWS;
+    return n;
+}
 
 // ---- blur_arith_flat_kernel: the flat rule one step flatter.  With every operand at the image's channel count the
 // operation is bytewise, so an image is the run of its W * H * C bytes cut into chunks of ARITH_CHUNK bytes and the

@@ -2469,6 +2469,134 @@ extern "C" int mi_blur_run_tone(int device, const uint8_t *host_in, uint8_t *hos
 }
 
 // ----------------------------------------------------------------------------------
+// CLAHE (no reference analogue).  Not a FilterKind; its own launches (clahe_kernels.hip) and CPU loops.  The same order
+// as the histogram family: all arguments, the empty batch, the device.
+// ----------------------------------------------------------------------------------
+static bool clahe_args_ok(const uint8_t *in, int W, int H, int C, int n_images, const mi_blur_clahe *k)
+{
+    return hist_args_ok(in, W, H, C, n_images) && clahe_ok(k, W, H, C);
+}
+// The tables of a work buffer, behind its histograms.
+static uint8_t *clahe_work_tables(void *work, int C, int n_images, const mi_blur_clahe &k)
+{
+    return reinterpret_cast<uint8_t *>(static_cast<uint32_t *>(work) + clahe_tables_of(n_images, k, C) * MI_BLUR_HIST_BINS);
+}
+
+extern "C" int mi_blur_clahe_coord(int size, int tiles, int x, int *t0, int *t1, int *frac)
+{
+    if (!t0 || !t1 || !frac || size < 1 || size > MI_BLUR_RESIZE_MAX_DIM || tiles < 1 || tiles > MI_BLUR_CLAHE_MAX_TILES || tiles > size ||
+        x < 0 || x >= size)
+        return MI_BLUR_ERR_INVALID;
+    clahe_axis(size, tiles, x, *t0, *t1, *frac);
+    return MI_BLUR_OK;
+}
+
+extern "C" int mi_blur_clahe_table(const uint32_t hist[256], uint32_t area, int clip_q8, uint8_t lut[256])
+{
+    if (!hist || !lut || clip_q8 < 0 || clip_q8 > 65536 || area == 0) return MI_BLUR_ERR_INVALID;
+    uint64_t sum = 0;
+    for (int v = 0; v < MI_BLUR_HIST_BINS; v++) sum += hist[v];
+    if (sum != area) return MI_BLUR_ERR_INVALID;
+    clahe_table(hist, area, clip_q8, lut);
+    return MI_BLUR_OK;
+}
+
+extern "C" size_t mi_blur_clahe_work_bytes(int width, int height, int channels, int n_images, const mi_blur_clahe *k)
+{
+    if (!hist_image_ok(width, height, channels) || n_images < 0 || !clahe_ok(k, width, height, channels)) return 0;
+    return clahe_tables_of(n_images, *k, channels) * MI_BLUR_HIST_BINS * (sizeof(uint32_t) + 1);
+}
+
+extern "C" int mi_blur_enqueue_clahe_tables(const uint8_t *d_in, int width, int height, int channels, int n_images,
+                                            const mi_blur_clahe *k, void *d_work, void *stream)
+{
+    if (!clahe_args_ok(d_in, width, height, channels, n_images, k) || !aligned_to(d_work, 16)) return MI_BLUR_ERR_INVALID;
+    if (n_images == 0) return MI_BLUR_OK;
+    if (mi_blur_device_count() <= 0) return MI_BLUR_ERR_NO_DEVICE;
+    return launch_clahe_tables(d_in, static_cast<uint32_t *>(d_work), clahe_work_tables(d_work, channels, n_images, *k), width, height, channels,
+                               n_images, *k, (hipStream_t)stream);
+}
+
+extern "C" int mi_blur_enqueue_clahe_apply(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int n_images,
+                                           const mi_blur_clahe *k, const uint8_t *d_tables, void *stream)
+{
+    if (!clahe_args_ok(d_in, width, height, channels, n_images, k) || !d_out || d_in == d_out || !d_tables) return MI_BLUR_ERR_INVALID;
+    if (n_images == 0) return MI_BLUR_OK;
+    if (mi_blur_device_count() <= 0) return MI_BLUR_ERR_NO_DEVICE;
+    return launch_clahe_apply(d_in, d_out, width, height, channels, n_images, *k, d_tables, (hipStream_t)stream);
+}
+
+// The two dispatches of mi_blur_enqueue_clahe on buffers that are known to be good.
+static int enqueue_clahe(const uint8_t *d_in, uint8_t *d_out, int W, int H, int C, int n_images, const mi_blur_clahe &k, void *d_work, hipStream_t stream)
+{
+    uint8_t *tables = clahe_work_tables(d_work, C, n_images, k);
+    if (const int rc = launch_clahe_tables(d_in, static_cast<uint32_t *>(d_work), tables, W, H, C, n_images, k, stream)) return rc;
+    return launch_clahe_apply(d_in, d_out, W, H, C, n_images, k, tables, stream);
+}
+
+extern "C" int mi_blur_enqueue_clahe(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int n_images,
+                                     const mi_blur_clahe *k, void *d_work, void *stream)
+{
+    if (!clahe_args_ok(d_in, width, height, channels, n_images, k) || !d_out || d_in == d_out || !aligned_to(d_work, 16))
+        return MI_BLUR_ERR_INVALID;
+    if (n_images == 0) return MI_BLUR_OK;
+    if (mi_blur_device_count() <= 0) return MI_BLUR_ERR_NO_DEVICE;
+    return enqueue_clahe(d_in, d_out, width, height, channels, n_images, *k, d_work, (hipStream_t)stream);
+}
+
+extern "C" int mi_blur_cpu_run_clahe_tables(const uint8_t *in, int width, int height, int channels, int n_images,
+                                            const mi_blur_clahe *k, void *work, int n_threads)
+{
+    if (!clahe_args_ok(in, width, height, channels, n_images, k) || !aligned_to(work, 4)) return MI_BLUR_ERR_INVALID;
+    cpu_clahe_tables(in, static_cast<uint32_t *>(work), clahe_work_tables(work, channels, n_images, *k), width, height, channels, n_images, *k,
+                     n_threads);
+    return MI_BLUR_OK;
+}
+
+extern "C" int mi_blur_cpu_run_clahe_apply(const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,
+                                           const mi_blur_clahe *k, const uint8_t *tables, int n_threads)
+{
+    if (!clahe_args_ok(in, width, height, channels, n_images, k) || !out || in == out || !tables) return MI_BLUR_ERR_INVALID;
+    cpu_clahe_apply(in, out, width, height, channels, n_images, *k, tables, n_threads);
+    return MI_BLUR_OK;
+}
+
+extern "C" int mi_blur_cpu_run_clahe(const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,
+                                     const mi_blur_clahe *k, void *work, int n_threads)
+{
+    if (!clahe_args_ok(in, width, height, channels, n_images, k) || !out || in == out || (work && !aligned_to(work, 4)))
+        return MI_BLUR_ERR_INVALID;
+    std::vector<uint32_t> own;
+    if (!work) {
+        try { own.resize((mi_blur_clahe_work_bytes(width, height, channels, n_images, k) + 3) / 4); } catch (...) { return MI_BLUR_ERR_NOMEM; }
+        work = own.data();
+    }
+    cpu_clahe(in, out, width, height, channels, n_images, *k, work, n_threads);
+    return MI_BLUR_OK;
+}
+
+extern "C" int mi_blur_run_clahe(int device, const uint8_t *host_in, uint8_t *host_out, void *host_work, int width, int height,
+                                 int channels, int n_images, const mi_blur_clahe *k)
+{
+    if (device == MI_BLUR_DEVICE_CPU) return mi_blur_cpu_run_clahe(host_in, host_out, width, height, channels, n_images, k, host_work, 0);
+    if (!clahe_args_ok(host_in, width, height, channels, n_images, k) || !host_out || host_in == host_out || (host_work && !aligned_to(host_work, 4)))
+        return MI_BLUR_ERR_INVALID;
+    if (n_images == 0) return MI_BLUR_OK;
+    if (const int rc = use_device(device)) return rc;
+    const size_t bytes = (size_t)n_images * width * height * channels, work_bytes = mi_blur_clahe_work_bytes(width, height, channels, n_images, k);
+    DeviceBuffer in, out, work;
+    HIP_TRY(in.alloc(bytes));
+    HIP_TRY(out.alloc(bytes));
+    HIP_TRY(work.alloc(work_bytes));
+    HIP_TRY(hipMemcpy(in.p, host_in, bytes, hipMemcpyHostToDevice));
+    if (const int rc = enqueue_clahe(static_cast<const uint8_t *>(in.p), static_cast<uint8_t *>(out.p), width, height, channels, n_images, *k, work.p, nullptr))
+        return rc;
+    HIP_TRY(hipMemcpy(host_out, out.p, bytes, hipMemcpyDeviceToHost));
+    if (host_work) HIP_TRY(hipMemcpy(host_work, work.p, work_bytes, hipMemcpyDeviceToHost));
+    return MI_BLUR_OK;
+}
+
+// ----------------------------------------------------------------------------------
 // two-image arithmetic (no reference analogue).  Not a FilterKind either: a context has one input stream.  The same
 // order as the histogram family: all arguments (arith_args_ok(), filter.h), the empty batch, the device.
 // ----------------------------------------------------------------------------------

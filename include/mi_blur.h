@@ -75,7 +75,8 @@ int mi_blur_version(void);
  * "blur_color_generic_kernel", "blur_hist_tiled_kernel", "blur_hist_generic_kernel", "blur_tone_table_kernel",
  * "blur_tables_tiled_kernel", "blur_tables_generic_kernel", "blur_arith_flat_kernel", "blur_arith_plane_kernel",
  * "blur_arith_generic_kernel", "blur_integral_tiled_kernel", "blur_integral_generic_kernel", "blur_box_tiled_kernel",
- * "blur_box_generic_kernel", "blur_dist_tiled_kernel", "blur_dist_generic_kernel"; "" before the first):
+ * "blur_box_generic_kernel", "blur_dist_tiled_kernel", "blur_dist_generic_kernel", "blur_clahe_tables_tiled_kernel",
+ * "blur_clahe_tables_generic_kernel", "blur_clahe_apply_tiled_kernel", "blur_clahe_apply_generic_kernel"; "" before the first):
  * reports name the kernel a profiler will show.  Static string, never NULL. */
 const char *mi_blur_last_kernel(void);
 
@@ -782,6 +783,105 @@ int mi_blur_cpu_run_tone(const uint8_t *in, uint8_t *out, int width, int height,
 int mi_blur_run_hist(int device, const uint8_t *host_in, uint32_t *host_hist, int width, int height, int channels, int n_images);
 int mi_blur_run_tone(int device, const uint8_t *host_in, uint8_t *host_out, void *host_work /* may be NULL */,
                      int width, int height, int channels, int n_images, const mi_blur_tone *t);
+
+/* ------------------------------------------------------------------------
+ * CLAHE: tile-wise adaptive equalisation with a clip limit (no reference analogue).  The image is cut into a grid of
+ * tiles, every tile gets its own table from its own clipped histogram, and every pixel goes through the tables of the
+ * four tiles around it, blended by its position.  The first operation here that gives two regions of one image
+ * different tables.  Integers only, rounded once (11 fraction bits per axis, one final rounding), so the GPU, the CPU
+ * device and a numpy / Python-integer restatement agree byte for byte.  Not a filter of a context.
+ *
+ * Images: interleaved, dense, 1..4 channels, within the histogram family's limits.  Image offsets are 64-bit.
+ * n_images == 0 is MI_BLUR_OK and launches nothing.
+ *
+ * Valid *k (mi_blur_clahe) for an image of width x height: tiles_x, tiles_y in 1..MI_BLUR_CLAHE_MAX_TILES with
+ * tiles_x <= width and tiles_y <= height; clip_q8 in 0..65536; channel_mask without bits at or above `channels`.
+ * Anything else is MI_BLUR_ERR_INVALID, the output untouched.
+ *
+ * Tile geometry.  On an axis of S pixels and T tiles, tile t covers the pixels [b_t, b_(t+1)) with b_t = floor(t*S/T);
+ * T <= S makes every tile non-empty.  A tile's area A is its own pixel count.  There is NO padding: OpenCV reflect-pads
+ * the image to a multiple of the grid and gives every tile the same area; here the tiles differ by up to one row and one
+ * column and the image is never extended.
+ *
+ * Tile table, per (image, tile, transformed channel), from the tile's histogram h:
+ *   1. clip_q8 == 0: h' = h (plain adaptive equalisation).
+ *   2. Otherwise clip = max(1, floor(clip_q8 * A / 65536)) (clip_q8 = OpenCV's clipLimit in Q8; its clip is
+ *      clipLimit * A / 256), excess = sum_v max(h(v) - clip, 0),
+ *        h'(v) = min(h(v), clip) + floor(excess / 256),  residual = excess mod 256,
+ *      and if residual > 0: step = max(floor(256 / residual), 1), and h'(v) += 1 for every v with v mod step == 0 and
+ *      v / step < residual.  This is OpenCV's single redistribution pass in closed form.  sum_v h'(v) = A.  Bins may
+ *      exceed clip afterwards; that is part of the definition.
+ *   3. c(v) = sum_{u <= v} h'(u);  lut[v] = floor((510 * c(v) + A) / (2 * A)): 255 * c(v) / A rounded once, half up,
+ *      in 64 bits.
+ * A channel that is not transformed gets the identity table.  The histograms of ALL channels are counted.
+ *
+ * Position, per axis (mi_blur_clahe_coord): with p = 2x + 1 and m_t = b_t + b_(t+1) (the tile centres in half-pixels),
+ *   p <= m_0, or tiles == 1:   (t0, t1, frac) = (0, 0, 0);
+ *   p >= m_(T-1):              (T-1, T-1, 0);
+ *   otherwise t0 = the largest t with m_t <= p, t1 = t0 + 1, frac = floor((p - m_t0) * 2048 / (m_t1 - m_t0)), 0..2047.
+ *
+ * Blend.  With (tx0, tx1, fx) and (ty0, ty1, fy) of the pixel and Lij = lut[tile (ty_i, tx_j)][c][in]:
+ *   out = ((2048-fx)*(2048-fy)*L00 + fx*(2048-fy)*L01 + (2048-fx)*fy*L10 + fx*fy*L11 + 2^21) >> 22
+ * which stays below 2^31; the weights sum to 2^22, so equal tables give the table's value exactly.
+ *
+ * The results are NOT claimed to be OpenCV's bytes: OpenCV uses float weights and a float scale, and padded tiles.
+ * ---------------------------------------------------------------------- */
+#define MI_BLUR_CLAHE_MAX_TILES 64
+typedef struct mi_blur_clahe {
+    int tiles_x, tiles_y;   /* 1..MI_BLUR_CLAHE_MAX_TILES (64) each; tiles_x <= width, tiles_y <= height */
+    int clip_q8;            /* OpenCV's clipLimit in Q8, 0..65536; 0 = no clipping (plain AHE) */
+    int channel_mask;       /* as mi_blur_tone: bit c = channel c is transformed, others are copied; 0 = all */
+} mi_blur_clahe;
+
+/* (t0, t1, frac) of pixel x on an axis of `size` pixels and `tiles` tiles (host only).  MI_BLUR_ERR_INVALID: a null
+ * pointer, size outside 1..MI_BLUR_RESIZE_MAX_DIM, tiles outside 1..min(MI_BLUR_CLAHE_MAX_TILES, size), x outside
+ * 0..size-1. */
+int mi_blur_clahe_coord(int size, int tiles, int x, int *t0, int *t1, int *frac);
+/* One tile table from one histogram (host only), by steps 1 to 3 above.  MI_BLUR_ERR_INVALID: a null pointer, clip_q8
+ * outside 0..65536, area == 0, or bins that do not sum to area. */
+int mi_blur_clahe_table(const uint32_t hist[256], uint32_t area, int clip_q8, uint8_t lut[256]);
+/* Bytes of the work buffer: n_images*tiles_y*tiles_x*channels*256*4 for the raw tile histograms
+ * uint32[n_images][tiles_y][tiles_x][channels][256], then n_images*tiles_y*tiles_x*channels*256 for the tables
+ * uint8[n_images][tiles_y][tiles_x][channels][256].  0 for invalid arguments. */
+size_t mi_blur_clahe_work_bytes(int width, int height, int channels, int n_images, const mi_blur_clahe *k);
+/* The tile histograms and the tile tables into d_work (device memory, 16-byte aligned, the layout above; asynchronous).
+ * Both are valid for the caller to read once the stream has drained.  MI_BLUR_ERR_INVALID (before
+ * MI_BLUR_ERR_NO_DEVICE): a null pointer, d_work not 16-byte aligned, the size errors of mi_blur_enqueue_hist, an
+ * invalid *k.
+ * blur_clahe_tables_tiled_kernel takes exactly the launches with width a multiple of 16 and d_in 16-byte aligned: one
+ * workgroup per (image, tile) reads the tile's rows in aligned 16-byte chunks (a chunk that straddles a tile edge is
+ * read by both neighbours and masked per pixel), counts in LDS (one set of channels x 256 counters per wave), sums the
+ * sets, writes the histogram, clips, redistributes, runs the prefix sum and writes the tables: no global atomic, no
+ * zeroing, no wait for another workgroup.  Every other launch goes to blur_clahe_tables_generic_kernel (one byte per
+ * thread and step, at most 16384 workgroups that stride over the tiles). */
+int mi_blur_enqueue_clahe_tables(const uint8_t *d_in, int width, int height, int channels, int n_images,
+                                 const mi_blur_clahe *k, void *d_work, void *stream);
+/* Every pixel through the four tables around it.  d_tables: uint8[n_images][tiles_y][tiles_x][channels][256] in device
+ * memory, any alignment; ANY tables, not only ones this library made; clip_q8 and channel_mask are checked and not used.
+ * MI_BLUR_ERR_INVALID: as above, and d_in == d_out.
+ * blur_clahe_apply_tiled_kernel takes exactly the launches with width a multiple of 16, d_in and d_out 16-byte aligned
+ * and this LDS rule: cut the row into spans of 256 pixels from pixel 0; a span needs the tile columns from t0 of its
+ * first pixel to t1 of its last (mi_blur_clahe_coord); the launch is tiled when (the most columns any span needs) *
+ * 2 * channels * 256 <= 32768 bytes.  A workgroup owns up to 32 rows between two tile-row centres and one span, stages
+ * those tables and the span's column entries in LDS, and per group of 16 pixels does C loads of 16 bytes, four LDS byte
+ * look-ups and one blend per byte, and C stores.  Every other launch goes to blur_clahe_apply_generic_kernel (one byte
+ * per thread, the tables read from device memory). */
+int mi_blur_enqueue_clahe_apply(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int n_images,
+                                const mi_blur_clahe *k, const uint8_t *d_tables, void *stream);
+/* Both steps on one stream, no host round trip: two dispatches.  d_work as for mi_blur_enqueue_clahe_tables. */
+int mi_blur_enqueue_clahe(const uint8_t *d_in, uint8_t *d_out, int width, int height, int channels, int n_images,
+                          const mi_blur_clahe *k, void *d_work, void *stream);
+/* The same three on the CPU device's threads (synchronous).  work: host memory laid out as d_work, 4-byte aligned; it
+ * may be NULL for mi_blur_cpu_run_clahe (the call then allocates its own and drops it). */
+int mi_blur_cpu_run_clahe_tables(const uint8_t *in, int width, int height, int channels, int n_images,
+                                 const mi_blur_clahe *k, void *work, int n_threads);
+int mi_blur_cpu_run_clahe_apply(const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,
+                                const mi_blur_clahe *k, const uint8_t *tables, int n_threads);
+int mi_blur_cpu_run_clahe(const uint8_t *in, uint8_t *out, int width, int height, int channels, int n_images,
+                          const mi_blur_clahe *k, void *work /* may be NULL */, int n_threads);
+/* Blocking, host memory in and out, like mi_blur_run_tone.  host_work: receives the histograms and the tables, or NULL. */
+int mi_blur_run_clahe(int device, const uint8_t *host_in, uint8_t *host_out, void *host_work /* may be NULL */,
+                      int width, int height, int channels, int n_images, const mi_blur_clahe *k);
 
 /* ------------------------------------------------------------------------
  * Two-image arithmetic: add, subtract, absolute difference, weighted sum, min / max, multiply and the blend through a
