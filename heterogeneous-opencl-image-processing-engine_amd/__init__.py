@@ -78,7 +78,7 @@ def _newer(target: str, sources: list[str]) -> bool:
 
 def build_native(force: bool = False, verbose: bool = False) -> str:
     """Compile libmi_blur.so (hipcc, --offload-arch=gfx950) and the C++ hosts, in-tree."""
-    srcs = [os.path.join(CSRC, f) for f in ("blur_kernels.hip", "sep_kernels.hip", "median_kernels.hip", "morph_kernels.hip", "bilateral_kernels.hip", "conv_kernels.hip", "sep_down_kernels.hip", "resize_kernels.hip", "warp_kernels.hip", "remap_kernels.hip", "area_kernels.hip", "color_kernels.hip", "hist_kernels.hip", "clahe_kernels.hip", "arith_kernels.hip", "integral_kernels.hip", "dist_kernels.hip", "layout_kernels.hip", "mi_blur_api.cpp", "comm_api.cpp", "cpu_device.cpp")]
+    srcs = [os.path.join(CSRC, f) for f in ("blur_kernels.hip", "sep_kernels.hip", "median_kernels.hip", "morph_kernels.hip", "bilateral_kernels.hip", "conv_kernels.hip", "sep_down_kernels.hip", "resize_kernels.hip", "warp_kernels.hip", "remap_kernels.hip", "area_kernels.hip", "color_kernels.hip", "hist_kernels.hip", "clahe_kernels.hip", "arith_kernels.hip", "integral_kernels.hip", "dist_kernels.hip", "layout_kernels.hip", "mi_blur_api.cpp", "table_api.cpp", "comm_api.cpp", "cpu_device.cpp")]
     deps = srcs + [os.path.join(CSRC, f) for f in ("api_internal.h", "blur_launch.h", "kernel_common.h", "cpu_device.h", "filter.h")] + [HEADER]
     if force or not _newer(LIB_PATH, deps):
         cmd = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra",
@@ -1123,18 +1123,8 @@ def _color_set_lut(k: "Color", lut, name: str) -> None:
 def _color_run(images, make, device: int, batch: int, name: str):
     """images through the Color that make(channels) returns: (H, W), (H, W, C) or (N, H, W, C) in; (N, H, W, Co) out of a
     stack, (H, W, Co) out of a single image, and (H, W) where that has one channel."""
-    a = _images(images, name)
-    rank = a.ndim
-    if rank == 2:
-        a = a[None, :, :, None]
-    elif rank == 3:
-        a = a[None]
-    n, h, w, c = a.shape
-    if h == 0 or w == 0 or c == 0:
-        raise ValueError(f"{name}: images must not be empty")
-    if c > COLOR_MAX_CHANNELS:
-        raise ValueError(f"{name}: at most {COLOR_MAX_CHANNELS} channels")
-    k = make(c)
+    a, rank = _tone_stack(images, name)
+    k = make(a.shape[3])
     out = _filter_images(a, 1, device, batch, lambda ctx: ctx.set_color(k), None, k.out_channels)
     if rank == 4:
         return out
@@ -1206,7 +1196,8 @@ def threshold(images, t: int, lo: int = 0, hi: int = 255, device: int = 0, batch
 
 
 def _tone_stack(images, name: str):
-    """(images as (N, H, W, C), the rank they came with) for the histogram family: non-empty images of 1..4 channels."""
+    """(images as (N, H, W, C), the rank they came with) for the colour transform and the families outside Filter:
+    non-empty images of 1..4 channels."""
     a = _images(images, name)
     rank = a.ndim
     if rank == 2:
@@ -1221,18 +1212,36 @@ def _tone_stack(images, name: str):
     return a, rank
 
 
-def _tone(mode, clip_q16, joint, channels, c: int, name: str) -> "Tone":
-    """A Tone for images of c channels.  mode: a key of TONE_MODES; clip_q16: (lo, hi) Q16 integers; channels: None (all)
-    or the indices of the channels to transform."""
-    if mode not in TONE_MODES:
-        raise ValueError(f"{name}: mode is one of {sorted(TONE_MODES)}")
+def _batches(n: int, batch: int):
+    """(first image, images) of every call on n images, `batch` images per call (0 = all at once)."""
+    per = batch if batch > 0 else max(n, 1)
+    for i in range(0, n, per):
+        yield i, min(per, n - i)
+
+
+def _unstack(out, rank: int, pixels: bool = True):
+    """out, one entry per image, in the rank the images came with (_tone_stack): a stack's, or one image's; of one grey
+    image (H, W) without the channel axis too where out is pixels (N, H, W, C) and not tables."""
+    return out if rank == 4 else out[0, :, :, 0] if pixels and rank == 2 else out[0]
+
+
+def _channel_mask(channels, c: int, name: str) -> int:
+    """The mask of the channel indices `channels` of c channels; None (all) is 0."""
     mask = 0
     for ch in (() if channels is None else channels):
         if not 0 <= int(ch) < c:
             raise ValueError(f"{name}: channel {ch} of {c}")
         mask |= 1 << int(ch)
+    return mask
+
+
+def _tone(mode, clip_q16, joint, channels, c: int, name: str) -> "Tone":
+    """A Tone for images of c channels.  mode: a key of TONE_MODES; clip_q16: (lo, hi) Q16 integers; channels: None (all)
+    or the indices of the channels to transform."""
+    if mode not in TONE_MODES:
+        raise ValueError(f"{name}: mode is one of {sorted(TONE_MODES)}")
     lo, hi = (int(v) for v in clip_q16)
-    return Tone(TONE_MODES[mode], lo, hi, int(bool(joint)), mask)
+    return Tone(TONE_MODES[mode], lo, hi, int(bool(joint)), _channel_mask(channels, c, name))
 
 
 def _clip_q16(clip, name: str) -> tuple[int, int]:
@@ -1249,9 +1258,7 @@ def _tone_run(a, tone: "Tone", device: int, batch: int, name: str):
     import numpy as np
     n, h, w, c = a.shape
     out = np.empty_like(a)
-    per = batch if batch > 0 else max(n, 1)
-    for i in range(0, n, per):
-        k = min(per, n - i)
+    for i, k in _batches(n, batch):
         check(lib().mi_blur_run_tone(device, a[i:].ctypes.data, out[i:].ctypes.data, None, w, h, c, k, C.byref(tone)), name)
     return out
 
@@ -1264,10 +1271,9 @@ def histogram(images, device: int = 0, batch: int = 0):
     a, rank = _tone_stack(images, "histogram")
     n, h, w, c = a.shape
     out = np.empty((n, c, HIST_BINS), np.uint32)
-    per = batch if batch > 0 else max(n, 1)
-    for i in range(0, n, per):
-        check(lib().mi_blur_run_hist(device, a[i:].ctypes.data, out[i:].ctypes.data, w, h, c, min(per, n - i)), "mi_blur_run_hist")
-    return out if rank == 4 else out[0]
+    for i, k in _batches(n, batch):
+        check(lib().mi_blur_run_hist(device, a[i:].ctypes.data, out[i:].ctypes.data, w, h, c, k), "mi_blur_run_hist")
+    return _unstack(out, rank, False)
 
 
 def tone_tables(hist, mode: str = "equalize", clip=(0, 0), joint: bool = False, channels=None):
@@ -1305,7 +1311,7 @@ def equalize_hist(images, mode: str = "channel", device: int = 0, batch: int = 0
                         "ycbcr2rgb", device, batch)
     else:
         out = _tone_run(a, _tone("equalize", (0, 0), mode == "joint", None, c, "equalize_hist"), device, batch, "equalize_hist")
-    return out if rank == 4 else out[0] if rank == 3 else out[0, :, :, 0]
+    return _unstack(out, rank)
 
 
 def auto_levels(images, clip=0.0, joint: bool = True, channels=None, device: int = 0, batch: int = 0):
@@ -1316,7 +1322,7 @@ def auto_levels(images, clip=0.0, joint: bool = True, channels=None, device: int
     a, rank = _tone_stack(images, "auto_levels")
     t = _tone("stretch", _clip_q16(clip, "auto_levels"), joint, channels, a.shape[3], "auto_levels")
     out = _tone_run(a, t, device, batch, "auto_levels")
-    return out if rank == 4 else out[0] if rank == 3 else out[0, :, :, 0]
+    return _unstack(out, rank)
 
 
 def _clahe(clip_limit, tiles, channels, c: int, name: str) -> "Clahe":
@@ -1326,12 +1332,7 @@ def _clahe(clip_limit, tiles, channels, c: int, name: str) -> "Clahe":
     if not 0.0 <= float(clip_limit) <= 256.0:
         raise ValueError(f"{name}: clip_limit is in 0..256")
     tx, ty = (int(v) for v in tiles)
-    mask = 0
-    for ch in (() if channels is None else channels):
-        if not 0 <= int(ch) < c:
-            raise ValueError(f"{name}: channel {ch} of {c}")
-        mask |= 1 << int(ch)
-    return Clahe(tx, ty, int(math.floor(float(clip_limit) * 256.0)), mask)
+    return Clahe(tx, ty, int(math.floor(float(clip_limit) * 256.0)), _channel_mask(channels, c, name))
 
 
 def _clahe_run(a, k: "Clahe", device: int, batch: int, name: str, want_work: bool = False):
@@ -1342,9 +1343,7 @@ def _clahe_run(a, k: "Clahe", device: int, batch: int, name: str, want_work: boo
     out = np.empty_like(a)
     shape = (n, k.tiles_y, k.tiles_x, c, HIST_BINS)
     hist, tables = (np.empty(shape, np.uint32), np.empty(shape, np.uint8)) if want_work else (None, None)
-    per = batch if batch > 0 else max(n, 1)
-    for i in range(0, n, per):
-        m = min(per, n - i)
+    for i, m in _batches(n, batch):
         words = m * k.tiles_y * k.tiles_x * c * HIST_BINS
         work = np.empty(5 * words, np.uint8) if want_work else None
         check(lib().mi_blur_run_clahe(device, a[i:].ctypes.data, out[i:].ctypes.data, None if work is None else work.ctypes.data,
@@ -1372,7 +1371,7 @@ def clahe(images, clip_limit: float = 2.0, tiles=(8, 8), mode: str = "channel", 
         out = cvt_color(_clahe_run(ycc, _clahe(clip_limit, tiles, (0,), 3, "clahe"), device, batch, "clahe"), "ycbcr2rgb", device, batch)
     else:
         out = _clahe_run(a, _clahe(clip_limit, tiles, channels, c, "clahe"), device, batch, "clahe")
-    return out if rank == 4 else out[0] if rank == 3 else out[0, :, :, 0]
+    return _unstack(out, rank)
 
 
 def clahe_tables(images, clip_limit: float = 2.0, tiles=(8, 8), channels=None, device: int = 0, batch: int = 0):
@@ -1380,7 +1379,7 @@ def clahe_tables(images, clip_limit: float = 2.0, tiles=(8, 8), channels=None, d
     shape (without the leading N for one image)."""
     a, rank = _tone_stack(images, "clahe_tables")
     _, hist, tables = _clahe_run(a, _clahe(clip_limit, tiles, channels, a.shape[3], "clahe_tables"), device, batch, "clahe_tables", True)
-    return (hist, tables) if rank == 4 else (hist[0], tables[0])
+    return _unstack(hist, rank, False), _unstack(tables, rank, False)
 
 
 def clahe_coord(size: int, tiles: int, x: int) -> tuple[int, int, int]:
@@ -1399,14 +1398,12 @@ def integral(images, square: bool = False, pad: bool = False, device: int = 0, b
     a, rank = _tone_stack(images, "integral")
     n, h, w, c = a.shape
     out = np.empty((n, h, w, c), np.uint32)
-    per = batch if batch > 0 else max(n, 1)
-    for i in range(0, n, per):
+    for i, k in _batches(n, batch):
         t = out[i:].ctypes.data
-        check(lib().mi_blur_run_integral(device, a[i:].ctypes.data, None if square else t, t if square else None, w, h, c, min(per, n - i)),
-              "mi_blur_run_integral")
+        check(lib().mi_blur_run_integral(device, a[i:].ctypes.data, None if square else t, t if square else None, w, h, c, k), "mi_blur_run_integral")
     if pad:
         out = np.pad(out, ((0, 0), (1, 0), (1, 0), (0, 0)))
-    return out if rank == 4 else out[0] if rank == 3 else out[0, :, :, 0]
+    return _unstack(out, rank)
 
 
 def rect_sum(table, x0: int, y0: int, x1: int, y1: int):
@@ -1443,10 +1440,9 @@ def _box_run(images, k: "Box", device: int, batch: int, name: str):
     a, rank = _tone_stack(images, name)
     n, h, w, c = a.shape
     out = np.empty_like(a)
-    per = batch if batch > 0 else max(n, 1)
-    for i in range(0, n, per):
-        check(lib().mi_blur_run_box(device, a[i:].ctypes.data, out[i:].ctypes.data, w, h, c, min(per, n - i), C.byref(k)), "mi_blur_run_box")
-    return out if rank == 4 else out[0] if rank == 3 else out[0, :, :, 0]
+    for i, m in _batches(n, batch):
+        check(lib().mi_blur_run_box(device, a[i:].ctypes.data, out[i:].ctypes.data, w, h, c, m, C.byref(k)), "mi_blur_run_box")
+    return _unstack(out, rank)
 
 
 def box_blur(images, ksize, device: int = 0, batch: int = 0):
@@ -1484,10 +1480,9 @@ def _dist_run(images, k: "Dist", table: bool, device: int, batch: int, name: str
     n, h, w, c = a.shape
     out = np.empty(a.shape, np.uint32 if table else np.uint8)
     run, export = (lib().mi_blur_run_dist, "mi_blur_run_dist") if table else (lib().mi_blur_run_dist_u8, "mi_blur_run_dist_u8")
-    per = batch if batch > 0 else max(n, 1)
-    for i in range(0, n, per):
-        check(run(device, a[i:].ctypes.data, out[i:].ctypes.data, w, h, c, min(per, n - i), C.byref(k)), export)
-    return out if rank == 4 else out[0] if rank == 3 else out[0, :, :, 0]
+    for i, m in _batches(n, batch):
+        check(run(device, a[i:].ctypes.data, out[i:].ctypes.data, w, h, c, m, C.byref(k)), export)
+    return _unstack(out, rank)
 
 
 def distance_transform(images, metric: str = "l2", sites: str = "zero", limit: int = 0, device: int = 0, batch: int = 0):
@@ -1583,11 +1578,10 @@ def arith(a, b, k: "Arith", mask=None, device: int = 0, batch: int = 0):
         m_step = 0 if q.m_shared else h * w * (1 if q.m_plane else c)
     b_step = 0 if q.b_shared else h * w * (1 if q.b_plane else c)
     out = np.empty_like(a)
-    per = batch if batch > 0 else max(n, 1)
-    for i in range(0, n, per):
+    for i, m in _batches(n, batch):
         check(lib().mi_blur_run_arith(device, a[i:].ctypes.data, b.ctypes.data + i * b_step, None if mask is None else mask.ctypes.data + i * m_step,
-                                      out[i:].ctypes.data, w, h, c, min(per, n - i), C.byref(q)), "mi_blur_run_arith")
-    return out if rank == 4 else out[0] if rank == 3 else out[0, :, :, 0]
+                                      out[i:].ctypes.data, w, h, c, m, C.byref(q)), "mi_blur_run_arith")
+    return _unstack(out, rank)
 
 
 def add(a, b, device: int = 0, batch: int = 0):

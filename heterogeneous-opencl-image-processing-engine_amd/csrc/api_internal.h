@@ -1,4 +1,4 @@
-// api_internal.h — internal: what the files that implement the C ABI (mi_blur_api.cpp, comm_api.cpp) share.
+// api_internal.h — internal: what the files that implement the C ABI (mi_blur_api.cpp, comm_api.cpp, table_api.cpp) share.
 #pragma once
 #include "../../include/mi_blur.h"
 

@@ -70,18 +70,6 @@ __global__ __launch_bounds__(ARITH_THREADS) void blur_arith_flat_kernel(const Ar
     *reinterpret_cast<uint4 *>(p.out + (long long)img * p.stride + off) = arith_chunk<OP>(p.k, a, b, m);
 }
 
-// The dwords of group g of an operand: 4 N of them, N = C chunks of a full operand or 1 of a plane.
-template <int N>
-__device__ __forceinline__ void load_chunks(uint32_t (&w)[4 * N], const uint8_t *img, unsigned g)
-{
-    const uint4 *src = reinterpret_cast<const uint4 *>(img + (size_t)g * (16u * N));
-#pragma unroll
-    for (int j = 0; j < N; j++) {
-        const uint4 v = src[j];
-        w[4 * j] = v.x; w[4 * j + 1] = v.y; w[4 * j + 2] = v.z; w[4 * j + 3] = v.w;
-    }
-}
-
 template <int OP, int C, int B_PLANE, int M_PLANE>
 __global__ __launch_bounds__(ARITH_THREADS) void blur_arith_plane_kernel(const ArithTiledParams p)
 {
@@ -92,9 +80,9 @@ __global__ __launch_bounds__(ARITH_THREADS) void blur_arith_plane_kernel(const A
     const unsigned g = run * ARITH_PLANE_RUN + threadIdx.x;
     if (g >= p.units) return;
     uint32_t a[4 * C], b[4 * NB], m[4 * NM], r[4 * C];
-    load_chunks<C>(a, p.a + (long long)img * p.stride, g);
-    load_chunks<NB>(b, p.b + (long long)img * p.b_stride, g);
-    if constexpr (LERP) load_chunks<NM>(m, p.m + (long long)img * p.m_stride, g);
+    load_group<C>(a, p.a + (long long)img * p.stride, g);          // C chunks of a full operand, 1 of a plane
+    load_group<NB>(b, p.b + (long long)img * p.b_stride, g);
+    if constexpr (LERP) load_group<NM>(m, p.m + (long long)img * p.m_stride, g);
     else m[0] = m[1] = m[2] = m[3] = 0;
 #pragma unroll
     for (int q = 0; q < 4 * C; q++) r[q] = 0;
@@ -104,9 +92,7 @@ __global__ __launch_bounds__(ARITH_THREADS) void blur_arith_plane_kernel(const A
         const int vm = LERP ? (int)window_byte(m, M_PLANE ? j / C : j) : 0;
         r[j >> 2] |= (uint32_t)arith_byte(OP, p.k.wa, p.k.wb, p.k.bias, p.k.shift, (int)window_byte(a, j), vb, vm) << (8 * (j & 3));
     }
-    uint4 *dst = reinterpret_cast<uint4 *>(p.out + (long long)img * p.stride + (size_t)g * (16u * C));
-#pragma unroll
-    for (int j = 0; j < C; j++) dst[j] = make_uint4(r[4 * j], r[4 * j + 1], r[4 * j + 2], r[4 * j + 3]);
+    store_group<C>(r, p.out + (long long)img * p.stride, g);
 }
 
 struct ArithGenericParams {
@@ -130,8 +116,6 @@ __global__ __launch_bounds__(256) void blur_arith_generic_kernel(const ArithGene
     }
 }
 
-bool aligned16(const void *q) { return (uintptr_t)q % 16 == 0; }
-
 }  // namespace
 
 int launch_arith(const uint8_t *a, const uint8_t *b, const uint8_t *m, uint8_t *out, int W, int H, int C, int n_images, const mi_blur_arith &k,
@@ -152,12 +136,8 @@ int launch_arith(const uint8_t *a, const uint8_t *b, const uint8_t *m, uint8_t *
         p.a = a; p.b = b; p.m = m; p.out = out;
         p.stride = bytes; p.b_stride = b_stride; p.m_stride = m_stride;
         p.units = (unsigned)(plane ? (long long)W * H / COLOR_GROUP : bytes / ARITH_CHUNK);
-        const long long runs = plane ? arith_plane_runs(W, H) : arith_flat_runs(W, H, C);
-        const long long nblocks = (long long)n_images * runs;
-        if (nblocks > 0x7fffffffLL) return MI_BLUR_ERR_INVALID;
-        p.runs = (unsigned)runs;
-        p.nblocks = (unsigned)nblocks;
-        p.xcd = nblocks >= 16 ? 1 : 0;
+        p.runs = (unsigned)(plane ? arith_plane_runs(W, H) : arith_flat_runs(W, H, C));
+        if (const int st = fill_flat(p, n_images, p.runs)) return st;
         p.k = wts;
         const dim3 grid(p.nblocks), block(ARITH_THREADS);
         if (!plane) {

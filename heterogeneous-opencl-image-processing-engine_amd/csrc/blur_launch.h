@@ -1,5 +1,5 @@
 // blur_launch.h — internal (not part of the C ABI): launch interface between the files that implement the C ABI
-// (mi_blur_api.cpp, comm_api.cpp) and the gfx950 kernels in the .hip files (what those share among themselves: kernel_common.h).
+// (mi_blur_api.cpp, table_api.cpp, comm_api.cpp) and the gfx950 kernels in the .hip files (what those share among themselves: kernel_common.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

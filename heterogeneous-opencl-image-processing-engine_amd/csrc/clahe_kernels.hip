@@ -43,7 +43,7 @@ struct ClaheTablesParams {
     long long in_stride;              // bytes per image
     int W, H, channels, TX, TY;
     int clip_q8, mask;                // mask without the "0 = all" form
-    unsigned jobs;                    // n * TY * TX
+    unsigned nblocks;                 // the jobs, one per tile: n * TY * TX
     int xcd;
 };
 
@@ -103,7 +103,7 @@ __global__ __launch_bounds__(CLAHE_THREADS) void blur_clahe_tables_tiled_kernel(
     const int t = threadIdx.x;
     for (int i = t; i < WAVES * C * BINS; i += CLAHE_THREADS) bins[i] = 0;
     __syncthreads();
-    const unsigned job = p.xcd ? xcd_contiguous(blockIdx.x, p.jobs) : blockIdx.x;
+    const unsigned job = p.xcd ? xcd_contiguous(blockIdx.x, p.nblocks) : blockIdx.x;
     const ClaheTile q = clahe_tile(job, p.W, p.H, p.TX, p.TY);
     const uint8_t *src = p.in + (long long)q.img * p.in_stride;
     uint32_t *mine = bins + (t >> 6) * (C * BINS);
@@ -112,13 +112,9 @@ __global__ __launch_bounds__(CLAHE_THREADS) void blur_clahe_tables_tiled_kernel(
 
     for (unsigned i = (unsigned)t; i < items; i += CLAHE_THREADS) {
         const unsigned r = i / ngx, g = g0 + (i - r * ngx);
-        const uint4 *chunk = reinterpret_cast<const uint4 *>(src + ((size_t)(q.y0 + (int)r) * p.W + (size_t)g * COLOR_GROUP) * C);
+        const uint8_t *chunk = src + ((size_t)(q.y0 + (int)r) * p.W + (size_t)g * COLOR_GROUP) * C;
         uint32_t w[4 * C];
-#pragma unroll
-        for (int j = 0; j < C; j++) {
-            const uint4 u = chunk[j];
-            w[4 * j] = u.x; w[4 * j + 1] = u.y; w[4 * j + 2] = u.z; w[4 * j + 3] = u.w;
-        }
+        load_group<C>(w, chunk, 0);
         const int px0 = (int)g * COLOR_GROUP;
         const bool full = px0 >= q.x0 && px0 + COLOR_GROUP <= q.x1;               // the whole group lies inside the tile
         const unsigned long long active = __ballot(1);
@@ -163,7 +159,7 @@ __global__ __launch_bounds__(CLAHE_THREADS) void blur_clahe_tables_generic_kerne
     __shared__ uint32_t exc[MI_BLUR_COLOR_MAX_CHANNELS];
     const int t = threadIdx.x, C = p.channels;
     const unsigned pitch = (unsigned)(p.W * C);
-    for (unsigned job = blockIdx.x; job < p.jobs; job += gridDim.x) {
+    for (unsigned job = blockIdx.x; job < p.nblocks; job += gridDim.x) {
         for (int i = t; i < C * BINS; i += CLAHE_THREADS) bins[i] = 0;
         __syncthreads();
         const ClaheTile q = clahe_tile(job, p.W, p.H, p.TX, p.TY);
@@ -263,13 +259,8 @@ __global__ __launch_bounds__(CLAHE_THREADS) void blur_clahe_apply_tiled_kernel(c
         const int r = i / (CLAHE_SPAN / COLOR_GROUP), g = i % (CLAHE_SPAN / COLOR_GROUP);
         if (g >= ng) continue;                                                   // the last span of a row may be short
         const size_t at = ((size_t)(lo + r) * p.W + (size_t)(xa + g * COLOR_GROUP)) * C;
-        const uint4 *chunk = reinterpret_cast<const uint4 *>(src + at);
         uint32_t w[4 * C], o[4 * C], e[COLOR_GROUP];
-#pragma unroll
-        for (int j = 0; j < C; j++) {
-            const uint4 v = chunk[j];
-            w[4 * j] = v.x; w[4 * j + 1] = v.y; w[4 * j + 2] = v.z; w[4 * j + 3] = v.w;
-        }
+        load_group<C>(w, src + at, 0);
 #pragma unroll
         for (int j = 0; j < COLOR_GROUP / 4; j++) {
             const uint4 v = reinterpret_cast<const uint4 *>(xent + g * COLOR_GROUP)[j];
@@ -287,9 +278,7 @@ __global__ __launch_bounds__(CLAHE_THREADS) void blur_clahe_apply_tiled_kernel(c
             const unsigned q = bilinear_blend(b0[0], b0[next], b0[rowbytes], b0[rowbytes + next], fx, fy);
             o[j >> 2] |= q << (8 * (j & 3));
         }
-        uint4 *d = reinterpret_cast<uint4 *>(dst + at);
-#pragma unroll
-        for (int j = 0; j < C; j++) d[j] = make_uint4(o[4 * j], o[4 * j + 1], o[4 * j + 2], o[4 * j + 3]);
+        store_group<C>(o, dst + at, 0);
     }
 }
 
@@ -318,8 +307,6 @@ __global__ __launch_bounds__(256) void blur_clahe_apply_generic_kernel(const Cla
     }
 }
 
-bool aligned16(const void *q) { return (uintptr_t)q % 16 == 0; }
-
 }  // namespace
 
 int launch_clahe_tables(const uint8_t *in, uint32_t *hist, uint8_t *tables, int W, int H, int C, int n_images, const mi_blur_clahe &k,
@@ -327,22 +314,19 @@ int launch_clahe_tables(const uint8_t *in, uint32_t *hist, uint8_t *tables, int 
 {
     if (!in || !hist || !tables || !aligned16(hist) || !hist_image_ok(W, H, C) || !clahe_ok(&k, W, H, C) || n_images < 0) return MI_BLUR_ERR_INVALID;
     if (n_images == 0) return MI_BLUR_OK;
-    const long long jobs = (long long)n_images * k.tiles_y * k.tiles_x;
-    if (jobs > 0x7fffffffLL) return MI_BLUR_ERR_INVALID;
     ClaheTablesParams p{};
+    if (const int st = fill_flat(p, n_images, (long long)k.tiles_y * k.tiles_x)) return st;       // the generic kernel does not read p.xcd
     p.in = in; p.hist = hist; p.tables = tables; p.in_stride = (long long)W * H * C;
     p.W = W; p.H = H; p.channels = C; p.TX = k.tiles_x; p.TY = k.tiles_y;
     p.clip_q8 = k.clip_q8; p.mask = tone_mask(k.channel_mask, C);
-    p.jobs = (unsigned)jobs;
     if (clahe_tiled_ok(W) && aligned16(in)) {
-        p.xcd = jobs >= 16 ? 1 : 0;
         set_last_kernel("blur_clahe_tables_tiled_kernel");
         return dispatch<1, 2, 3, 4>(C, [&](auto CC) {
-            return do_launch(blur_clahe_tables_tiled_kernel<CC>, dim3(p.jobs), dim3(CLAHE_THREADS), 0, stream, p);
+            return do_launch(blur_clahe_tables_tiled_kernel<CC>, dim3(p.nblocks), dim3(CLAHE_THREADS), 0, stream, p);
         });
     }
     set_last_kernel("blur_clahe_tables_generic_kernel");
-    const unsigned blocks = jobs > CLAHE_GENERIC_BLOCKS ? (unsigned)CLAHE_GENERIC_BLOCKS : (unsigned)jobs;
+    const unsigned blocks = p.nblocks > (unsigned)CLAHE_GENERIC_BLOCKS ? (unsigned)CLAHE_GENERIC_BLOCKS : p.nblocks;
     return do_launch(blur_clahe_tables_generic_kernel, dim3(blocks), dim3(CLAHE_THREADS), 0, stream, p);
 }
 
@@ -358,10 +342,7 @@ int launch_clahe_apply(const uint8_t *in, uint8_t *out, int W, int H, int C, int
         p.W = W; p.H = H; p.TX = k.tiles_x; p.TY = k.tiles_y;
         p.nspans = clahe_spans(W); p.slices = clahe_slices(H, k.tiles_y);
         p.max_cols = clahe_span_cols(W, k.tiles_x);
-        const long long nblocks = (long long)n_images * p.slices * p.nspans;
-        if (nblocks > 0x7fffffffLL) return MI_BLUR_ERR_INVALID;
-        p.nblocks = (unsigned)nblocks;
-        p.xcd = nblocks >= 16 ? 1 : 0;
+        if (const int st = fill_flat(p, n_images, (long long)p.slices * p.nspans)) return st;
         const size_t lds = clahe_apply_lds_tables(p.max_cols, C) + (size_t)(CLAHE_SPAN + CLAHE_ROWS) * sizeof(uint32_t);
         set_last_kernel("blur_clahe_apply_tiled_kernel");
         return dispatch<1, 2, 3, 4>(C, [&](auto CC) {

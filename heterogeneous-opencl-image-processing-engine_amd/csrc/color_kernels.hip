@@ -140,15 +140,12 @@ int launch_color_tiled(const LaunchDesc &d)
     p.out_stride = d.out_stride ? d.out_stride : dense_out(d);
     p.groups = (unsigned)((long long)d.width * d.band_rows / COLOR_GROUP);
     p.runs = (unsigned)color_runs(d.width, d.band_rows);
-    const long long nblocks = (long long)d.n_images * p.runs;
-    if (nblocks > 0x7fffffffLL) return MI_BLUR_ERR_INVALID;
-    p.nblocks = (unsigned)nblocks;
-    p.xcd = nblocks >= 16 ? 1 : 0;
+    if (const int st = fill_flat(p, d.n_images, p.runs)) return st;
     fill_matrix(p.k, c);
     ColorTable<LUT> tab{};
     if constexpr (LUT != 0) memcpy(tab.w, c.lut, sizeof c.lut);
     set_last_kernel("blur_color_tiled_kernel");
-    const dim3 grid((unsigned)nblocks);
+    const dim3 grid(p.nblocks);
     return dispatch<1, 2, 3, 4>(d.channels, [&](auto CC) {
         return dispatch<1, 2, 3, 4>(c.co, [&](auto CO) {
             return do_launch(blur_color_tiled_kernel<CC, CO, LUT>, grid, dim3(COLOR_RUN), 0, d, p, tab);

@@ -209,10 +209,6 @@ __global__ __launch_bounds__(256) void blur_dist_generic_kernel(const DistRowPar
     }
 }
 
-bool aligned16(const void *q) { return (uintptr_t)q % 16 == 0; }
-// Workgroups of 256 threads for `threads` threads; 0 when they do not number in 31 bits.
-unsigned blocks_of(long long threads) { const long long b = (threads + 255) / 256; return b > 0x7fffffffLL ? 0u : (unsigned)b; }
-
 }  // namespace
 
 int launch_dist(const uint8_t *in, uint32_t *table, uint8_t *out, int W, int H, int C, int n_images, const mi_blur_dist &k, void *work, hipStream_t stream)

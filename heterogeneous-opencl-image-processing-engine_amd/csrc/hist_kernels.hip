@@ -44,18 +44,6 @@ struct HistTiledParams {
     int xcd;
 };
 
-// The 4 C dwords of group g of an image.
-template <int C>
-__device__ __forceinline__ void load_group(uint32_t (&w)[4 * C], const uint8_t *img, unsigned g)
-{
-    const uint4 *src = reinterpret_cast<const uint4 *>(img + (size_t)g * (16u * C));
-#pragma unroll
-    for (int j = 0; j < C; j++) {
-        const uint4 v = src[j];
-        w[4 * j] = v.x; w[4 * j + 1] = v.y; w[4 * j + 2] = v.z; w[4 * j + 3] = v.w;
-    }
-}
-
 template <int C>
 __global__ __launch_bounds__(HIST_THREADS) void blur_hist_tiled_kernel(const HistTiledParams p)
 {
@@ -207,9 +195,7 @@ __global__ __launch_bounds__(HIST_THREADS) void blur_tables_tiled_kernel(const T
         for (int q = 0; q < 4 * C; q++) r[q] = 0;
 #pragma unroll
         for (int j = 0; j < 16 * C; j++) r[j >> 2] |= (uint32_t)lut[(j % C) * BINS + (int)window_byte(w, j)] << (8 * (j & 3));
-        uint4 *dst = reinterpret_cast<uint4 *>(out + (size_t)g * (16u * C));
-#pragma unroll
-        for (int j = 0; j < C; j++) dst[j] = make_uint4(r[4 * j], r[4 * j + 1], r[4 * j + 2], r[4 * j + 3]);
+        store_group<C>(r, out, g);
     }
 }
 
@@ -231,20 +217,14 @@ __global__ __launch_bounds__(256) void blur_tables_generic_kernel(const TablesGe
     }
 }
 
-// (image, run) grids of the two tiled kernels: false when the workgroups do not number in 31 bits.
+// The groups and runs of an image and the flat grid of the two tiled kernels, per_image workgroups an image.
 template <typename P>
-bool fill_runs(P &p, int W, int H, int n_images)
+int fill_runs(P &p, int W, int H, int n_images, unsigned per_image)
 {
     p.groups = (unsigned)((long long)W * H / COLOR_GROUP);
     p.runs = (unsigned)hist_runs(W, H);
-    const long long nblocks = (long long)n_images * p.runs;
-    if (nblocks > 0x7fffffffLL) return false;
-    p.nblocks = (unsigned)nblocks;
-    p.xcd = nblocks >= 16 ? 1 : 0;
-    return true;
+    return fill_flat(p, n_images, per_image);
 }
-
-bool aligned16(const void *q) { return (uintptr_t)q % 16 == 0; }
 
 }  // namespace
 
@@ -260,10 +240,8 @@ int launch_hist(const uint8_t *in, uint32_t *hist, int W, int H, int C, int n_im
     if (color_flat_ok(W, H) && aligned16(in)) {
         HistTiledParams p{};
         p.in = in; p.hist = hist; p.in_stride = bytes;
-        if (!fill_runs(p, W, H, n_images)) return MI_BLUR_ERR_INVALID;
-        p.per_image = (unsigned)hist_blocks(W, H);                         // fill_runs() counted one workgroup per run
-        p.nblocks = (unsigned)n_images * p.per_image;
-        p.xcd = p.nblocks >= 16 ? 1 : 0;
+        p.per_image = (unsigned)hist_blocks(W, H);
+        if (const int st = fill_runs(p, W, H, n_images, p.per_image)) return st;
         set_last_kernel("blur_hist_tiled_kernel");
         return dispatch<1, 2, 3, 4>(C, [&](auto CC) {
             return do_launch(blur_hist_tiled_kernel<CC>, dim3(p.nblocks), dim3(HIST_THREADS), 0, stream, p);
@@ -299,7 +277,7 @@ int launch_tables(const uint8_t *in, uint8_t *out, int W, int H, int C, int n_im
     if (color_flat_ok(W, H) && aligned16(in) && aligned16(out)) {
         TablesTiledParams p{};
         p.in = in; p.out = out; p.tables = tables; p.stride = bytes;
-        if (!fill_runs(p, W, H, n_images)) return MI_BLUR_ERR_INVALID;
+        if (const int st = fill_runs(p, W, H, n_images, (unsigned)hist_runs(W, H))) return st;
         set_last_kernel("blur_tables_tiled_kernel");
         return dispatch<1, 2, 3, 4>(C, [&](auto CC) {
             return do_launch(blur_tables_tiled_kernel<CC>, dim3(p.nblocks), dim3(HIST_THREADS), 0, stream, p);

@@ -1,5 +1,6 @@
 // kernel_common.h — internal (not part of the C ABI): what the .hip files share below launch(): the launch call, the
 // blockIdx -> tile maps, the template dispatch, the argument checks and parameter fill every family repeats, the host side of the direct layout,
+// the flat grid and the 16-pixel group of the families outside Filter (fill_flat(), load_group(), store_group()),
 // the tile of all seven tiled kernels (its coordinates and its launch geometry: fill_tiles(), on tile_grid() of filter.h), the
 // staging of the sep, morph, bilateral, conv and sep_down kernels' LDS tile (stage_tile) and of the resize and warp kernels'
 // footprint (stage_box), and the v_mad_u32_u24 form of the bilinear blend (lerp24).
@@ -42,6 +43,28 @@ __device__ __forceinline__ unsigned xcd_runs(unsigned L, unsigned n, unsigned ru
 __device__ __forceinline__ unsigned xcd_map(unsigned L, unsigned n, int mode)
 {
     return mode == 0 ? L : mode == 1 ? xcd_contiguous(L, n) : xcd_runs(L, n, (unsigned)mode);
+}
+
+// The flat rule's group g of an image (color_flat_ok(), filter.h): N chunks of 16 bytes, as 4 N dwords of a local array.
+// The hist, arith and CLAHE kernels.  blur_color_tiled_kernel and blur_integral_tiled_kernel write the same loops out:
+// with these helpers their code objects come out in another instruction order
+// (profiles/r25_table_api_code_objects.md).
+template <int N>
+__device__ __forceinline__ void load_group(uint32_t (&w)[4 * N], const uint8_t *img, unsigned g)
+{
+    const uint4 *src = reinterpret_cast<const uint4 *>(img + (size_t)g * (16u * N));
+#pragma unroll
+    for (int j = 0; j < N; j++) {
+        const uint4 v = src[j];
+        w[4 * j] = v.x; w[4 * j + 1] = v.y; w[4 * j + 2] = v.z; w[4 * j + 3] = v.w;
+    }
+}
+template <int N>
+__device__ __forceinline__ void store_group(const uint32_t (&r)[4 * N], uint8_t *img, unsigned g)
+{
+    uint4 *dst = reinterpret_cast<uint4 *>(img + (size_t)g * (16u * N));
+#pragma unroll
+    for (int j = 0; j < N; j++) dst[j] = make_uint4(r[4 * j], r[4 * j + 1], r[4 * j + 2], r[4 * j + 3]);
 }
 
 __device__ __forceinline__ u16x2 pk16(uint32_t x) { return __builtin_bit_cast(u16x2, x); }
@@ -302,6 +325,19 @@ static void fill_band(P &p, const LaunchDesc &d)
     p.out_stride = d.out_stride ? d.out_stride : dense_out(d);
 }
 
+// The flat grid of the kernels that number their workgroups (image, workgroup of the image), one workgroup each:
+// p.nblocks, and p.xcd = the XCD-contiguous order for grids of 16 workgroups and more (the kernels decode it with
+// xcd_contiguous()).  MI_BLUR_ERR_INVALID when the workgroups do not number in 31 bits.
+template <typename P>
+static int fill_flat(P &p, long long n_images, long long per_image)
+{
+    const long long nblocks = n_images * per_image;
+    if (nblocks > 0x7fffffffLL) return MI_BLUR_ERR_INVALID;
+    p.nblocks = (unsigned)nblocks;
+    p.xcd = nblocks >= 16 ? 1 : 0;
+    return MI_BLUR_OK;
+}
+
 // fill_band plus the tile decomposition g of the tiled kernels' parameter structs (tile_coords() is the device side) and
 // the grid, one workgroup per tile.  MI_BLUR_ERR_INVALID when the tiles do not number in 31 bits.  Without g: the rows
 // [y0, y1) of the band and the chunks of its rows, in strips of up to TILE_NCOLS chunks.
@@ -311,15 +347,16 @@ static int fill_tiles(P &p, const LaunchDesc &d, dim3 *grid, const TileGrid &g)
     fill_band(p, d);
     if constexpr (!has_opitch<P>::value) p.y1 = d.y1;
     p.cpr = g.cpr; p.nstrips = g.nstrips; p.ncols = g.ncols; p.ntiles_y = g.ntiles_y;
-    const long long nblocks = (long long)d.n_images * p.ntiles_y * p.nstrips;
-    if (nblocks > 0x7fffffffLL) return MI_BLUR_ERR_INVALID;
-    p.nblocks = (unsigned)nblocks;
-    p.xcd = nblocks >= 16 ? 1 : 0;
-    *grid = dim3((unsigned)nblocks);
+    if (const int st = fill_flat(p, d.n_images, (long long)p.ntiles_y * p.nstrips)) return st;
+    *grid = dim3(p.nblocks);
     return MI_BLUR_OK;
 }
 template <typename P>
 static int fill_tiles(P &p, const LaunchDesc &d, dim3 *grid) { return fill_tiles(p, d, grid, tile_grid(d.width * d.channels / 16, d.y1 - d.y0)); }
+
+static inline bool aligned16(const void *q) { return (uintptr_t)q % 16 == 0; }
+// Workgroups of 256 threads for `threads` threads, none of them spare; 0 when they do not number in 31 bits.
+static inline unsigned blocks_of(long long threads) { const long long b = (threads + 255) / 256; return b > 0x7fffffffLL ? 0u : (unsigned)b; }
 
 // Grid of a byte-per-thread kernel: 256 threads per block, capped; the kernel grid-strides the rest.
 static inline dim3 byte_grid(long long total)

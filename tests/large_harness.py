@@ -19,6 +19,7 @@ import resize_ref
 import warp_perspective_ref as pr
 import warp_ref as wr
 from sep_down_ref import down_shape
+from table_harness import stream, upload  # noqa: F401  (the tests take them as lh.stream, lh.upload)
 
 BAND = 8                                        # rows of a compared band
 ONES = 0xFFFFFFFF
@@ -34,10 +35,6 @@ GREY9 = (9, 1051, 887, 1)                       # 8 390 133 PIXELS: the colour t
 ROWS_SHAPE = (9, 29128, 5, 3)                   # 262 152 rows = 65536 * 4 + 8: two workgroups of 4 waves make a second trip
 ROWS_REFUSED = (3, 87382, 5, 3)                 # 262 146 rows in 3 images: over the family's limit of 32768 rows an image
 PARTS_SHAPE = (1, 1673, 1673, 3)                # 8 396 787 bytes in one image, 1673^2 odd
-
-
-def stream(torch):
-    return torch.cuda.current_stream().cuda_stream
 
 
 def own_ranges(rng, shape):
@@ -99,14 +96,6 @@ def check_past_the_caps(cap, row_cap, hist_parts, part_bytes):
 
 
 # ---------------------------------------------------------------- one launch
-def upload(torch, host, offset=0):
-    """host at `offset` bytes into a zeroed device buffer with 64 spare bytes; (tensor, address of the data)."""
-    d = torch.zeros(host.size + 64, dtype=torch.uint8, device="cuda")
-    d[offset:offset + host.size] = torch.from_numpy(np.ascontiguousarray(host).reshape(-1)).cuda()
-    assert d.data_ptr() % 16 == 0
-    return d, d.data_ptr() + offset
-
-
 def guarded_bytes(torch, size, guard=64):
     """A device buffer of 0x5A with `guard` bytes either side of `size` bytes; (tensor, address of the data)."""
     d = torch.full((size + 2 * guard,), 0x5A, dtype=torch.uint8, device="cuda")

@@ -9,6 +9,7 @@ import pytest
 import arith_ref as R
 from arith_ref import FLAT, GENERIC, PLANE, PLANE_RUN, RUN
 from resample_harness import last, torch_cuda  # noqa: F401
+from table_harness import Guarded, stream, upload
 
 pytestmark = pytest.mark.gpu
 
@@ -16,18 +17,6 @@ OPS = (R.LINEAR, R.ABSDIFF, R.MIN, R.MAX, R.MUL, R.LERP)
 # units of a kernel per image: one; one below a workgroup's run, exactly a run, one above it; two runs plus one
 UNITS = (1, RUN - 1, RUN, RUN + 1, 2 * RUN + 1)
 UNIT_BLOCKS = (1, 1, 1, 2, 3)
-
-
-def stream(torch):
-    return torch.cuda.current_stream().cuda_stream
-
-
-def upload(torch, host, offset=0):
-    """host at `offset` bytes into a zeroed device buffer with 64 spare bytes; (tensor, address of the data)."""
-    d = torch.zeros(host.size + 64, dtype=torch.uint8, device="cuda")
-    d[offset:offset + host.size] = torch.from_numpy(np.ascontiguousarray(host).reshape(-1)).cuda()
-    assert d.data_ptr() % 16 == 0
-    return d, d.data_ptr() + offset
 
 
 def cpu_arith(pkg, L, k, a, b, m=None):

@@ -8,6 +8,7 @@ import pytest
 
 import box_ref as R
 from resample_harness import last, torch_cuda  # noqa: F401
+from table_harness import Guarded, stream, upload
 
 pytestmark = pytest.mark.gpu
 
@@ -21,46 +22,25 @@ UNITS = [(16, 1), (16, 2 * B + 1), (1008, B - 1), (1024, B), (1040, B + 1), (102
          (R.MAX_W + 16, B + 1)]
 
 
-def stream(torch):
-    return torch.cuda.current_stream().cuda_stream
-
-
-def upload(torch, host, offset=0):
-    """host at `offset` bytes into a device buffer with 64 spare bytes; (tensor, address of the data)."""
-    d = torch.zeros(host.size + 64, dtype=torch.uint8, device="cuda")
-    d[offset:offset + host.size] = torch.from_numpy(np.ascontiguousarray(host).reshape(-1)).cuda()
-    assert d.data_ptr() % 16 == 0
-    return d, d.data_ptr() + offset
-
-
 def spec(pkg, op, rx, ry):
     return pkg.Box(op, rx, ry, -3, rx & 1) if op == R.THRESHOLD else pkg.Box(op, rx, ry, 0, 0)
 
 
 def device_tables(pkg, L, torch, ptr, shape, want_s=True, want_q=True):
     """mi_blur_enqueue_integral on the images at ptr: every table inside 0xFFFFFFFF words, the work buffer inside 0x5A bytes.
-    Returns (S, Q, work as uint32, the device tensors of S and Q): None where not asked."""
+    Returns (S, Q, work as uint32, the device buffers of S and Q): None where not asked."""
     n, h, w, c = shape
     words = n * h * w * c
-    bufs = [torch.full((words + 2 * GUARD,), -1, dtype=torch.int32, device="cuda") if on else None for on in (want_s, want_q)]
-    ptrs = [None if b is None else b.data_ptr() + 4 * GUARD for b in bufs]
+    bufs = [Guarded(torch, words, "the table", np.uint32, ONES, GUARD, GUARD) if on else None for on in (want_s, want_q)]
+    ptrs = [None if b is None else b.ptr for b in bufs]
     nwork = L.mi_blur_integral_work_bytes(w, h, c, n, int(want_s and want_q))
     assert nwork == R.work_bytes(shape, 2 if want_s and want_q else 1)
-    d_work = torch.full((nwork + 64,), 0x5A, dtype=torch.uint8, device="cuda")
-    assert all(p is None or p % 16 == 0 for p in ptrs) and d_work.data_ptr() % 16 == 0
-    pkg.check(L.mi_blur_enqueue_integral(ptr, ptrs[0], ptrs[1], w, h, c, n, d_work.data_ptr(), stream(torch)), "mi_blur_enqueue_integral")
+    d_work = Guarded(torch, nwork, "the work buffer")
+    assert all(p is None or p % 16 == 0 for p in ptrs)
+    pkg.check(L.mi_blur_enqueue_integral(ptr, ptrs[0], ptrs[1], w, h, c, n, d_work.ptr, stream(torch)), "mi_blur_enqueue_integral")
     torch.cuda.synchronize()
-    out = []
-    for b in bufs:
-        if b is None:
-            out.append(None)
-            continue
-        o = b.cpu().numpy().view(np.uint32)
-        assert (o[:GUARD] == ONES).all() and (o[GUARD + words:] == ONES).all(), "wrote outside the table"
-        out.append(o[GUARD:GUARD + words].reshape(shape))
-    wk = d_work.cpu().numpy()
-    assert (wk[nwork:] == 0x5A).all(), "wrote outside the work buffer"
-    return out[0], out[1], wk[:nwork].view(np.uint32), bufs
+    out = [None if b is None else b.payload().reshape(shape) for b in bufs]
+    return out[0], out[1], d_work.payload().view(np.uint32), bufs
 
 
 def cpu_tables(pkg, L, img):
@@ -99,17 +79,15 @@ def device_box(pkg, L, torch, p_in, tabs, shape, k, offset_out=0, in_place=False
     0x5A with 128 bytes to spare, or is the input itself."""
     n, h, w, c = shape
     size = n * h * w * c
-    d_out = torch.full((size + 128,), 0x5A, dtype=torch.uint8, device="cuda")
-    p_out = p_in if in_place else d_out.data_ptr() + offset_out
-    pS, pQ = (t.data_ptr() + 4 * GUARD for t in tabs)
+    d_out = Guarded(torch, size, "the output", front=offset_out, back=128 - offset_out)
+    p_out = p_in if in_place else d_out.ptr
+    pS, pQ = (t.ptr for t in tabs)
     pkg.check(L.mi_blur_enqueue_box_from_integral(p_in if k.op == R.THRESHOLD else None, pS, pQ if k.op == R.STDDEV else None, p_out, w, h, c, n,
                                                   C.byref(k), stream(torch)), "mi_blur_enqueue_box_from_integral")
     torch.cuda.synchronize()
     if in_place:
         return None
-    o = d_out.cpu().numpy()
-    assert (o[:offset_out] == 0x5A).all() and (o[offset_out + size:] == 0x5A).all(), "wrote outside the output"
-    return o[offset_out:offset_out + size].reshape(shape)
+    return d_out.payload().reshape(shape)
 
 
 def cpu_box(pkg, L, img, k):

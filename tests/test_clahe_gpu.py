@@ -9,6 +9,7 @@ import pytest
 from clahe_ref import (APPLY_GENERIC, APPLY_TILED, BINS, GENERIC_BLOCKS, LDS_TABLE_BYTES, TABLES_GENERIC, TABLES_TILED, apply_takes_tiled, ref_apply,
                        ref_clahe, ref_table, ref_tables, span_cols, split_work, tables_take_tiled, tile_box, work_words)
 from resample_harness import last, torch_cuda  # noqa: F401
+from table_harness import Guarded, stream, upload
 
 pytestmark = pytest.mark.gpu
 
@@ -17,32 +18,17 @@ BYTE_CAP = 16384 * 256          # byte_grid(), csrc/kernel_common.h: workgroups 
 CPU_THREADS = 16
 
 
-def stream(torch):
-    return torch.cuda.current_stream().cuda_stream
-
-
-def upload(torch, host, offset=0):
-    """host at `offset` bytes into a device buffer with 64 spare bytes; (tensor, address of the data)."""
-    host = np.ascontiguousarray(host)
-    d = torch.zeros(host.size + 64, dtype=torch.uint8, device="cuda")
-    d[offset:offset + host.size] = torch.from_numpy(host.reshape(-1)).cuda()
-    assert d.data_ptr() % 16 == 0
-    return d, d.data_ptr() + offset
-
-
 def gpu_tables(pkg, L, torch, img, tiles, clip_q8, mask=0, offset_in=0):
     """mi_blur_enqueue_clahe_tables: (hist, tables, the kernel's name); the work buffer ends in 64 bytes of 0x5A."""
     n, h, w, c = img.shape
     d_in, p_in = upload(torch, img, offset_in)
     words = work_words(n, tiles, c)
-    d_work = torch.full((5 * words + GUARD,), 0x5A, dtype=torch.uint8, device="cuda")
+    d_work = Guarded(torch, 5 * words, "the work buffer", back=GUARD)
     k = pkg.Clahe(tiles[0], tiles[1], clip_q8, mask)
-    pkg.check(L.mi_blur_enqueue_clahe_tables(p_in, w, h, c, n, C.byref(k), d_work.data_ptr(), stream(torch)), "mi_blur_enqueue_clahe_tables")
+    pkg.check(L.mi_blur_enqueue_clahe_tables(p_in, w, h, c, n, C.byref(k), d_work.ptr, stream(torch)), "mi_blur_enqueue_clahe_tables")
     torch.cuda.synchronize()
     name = last(L)
-    wk = d_work.cpu().numpy()
-    assert (wk[5 * words:] == 0x5A).all(), "wrote outside the work buffer"
-    hist, tables = split_work(wk, n, tiles, c)
+    hist, tables = split_work(d_work.payload(), n, tiles, c)
     return hist, tables, name
 
 
@@ -52,15 +38,12 @@ def gpu_apply(pkg, L, torch, img, tiles, tables, offset_in=0, offset_out=0, offs
     n, h, w, c = img.shape
     d_in, p_in = upload(torch, img, offset_in)
     d_tab, p_tab = upload(torch, np.ascontiguousarray(tables, dtype=np.uint8), offset_tab)
-    d_out = torch.full((img.size + 2 * GUARD + 16,), 0x5A, dtype=torch.uint8, device="cuda")
-    at = GUARD + offset_out
+    d_out = Guarded(torch, img.size, "the output", front=GUARD + offset_out, back=GUARD + 16 - offset_out)
     k = pkg.Clahe(tiles[0], tiles[1], 0, 0)
-    pkg.check(L.mi_blur_enqueue_clahe_apply(p_in, d_out.data_ptr() + at, w, h, c, n, C.byref(k), p_tab, stream(torch)), "mi_blur_enqueue_clahe_apply")
+    pkg.check(L.mi_blur_enqueue_clahe_apply(p_in, d_out.ptr, w, h, c, n, C.byref(k), p_tab, stream(torch)), "mi_blur_enqueue_clahe_apply")
     torch.cuda.synchronize()
     name = last(L)
-    o = d_out.cpu().numpy()
-    assert (o[:at] == 0x5A).all() and (o[at + img.size:] == 0x5A).all(), "wrote outside the output"
-    return o[at:at + img.size].reshape(img.shape), name
+    return d_out.payload().reshape(img.shape), name
 
 
 def cpu_clahe(pkg, L, img, tiles, clip_q8, mask=0):

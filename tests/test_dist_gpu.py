@@ -10,6 +10,7 @@ import dist_ref as R
 from large_harness import BAND as CMP_BAND
 from large_harness import BASE, bands_of
 from resample_harness import last, torch_cuda  # noqa: F401
+from table_harness import Guarded, stream, upload
 
 pytestmark = pytest.mark.gpu
 
@@ -18,55 +19,39 @@ B = R.BAND
 CAP = 16384 * 256                             # byte_grid(), csrc/kernel_common.h: workgroups x threads
 
 
-def stream(torch):
-    return torch.cuda.current_stream().cuda_stream
-
-
-def upload(torch, host):
-    d = torch.from_numpy(np.ascontiguousarray(host).reshape(-1)).cuda()
-    assert d.data_ptr() % 16 == 0
-    return d
-
-
 def work_buffer(pkg, L, torch, shape, k, band=B):
     n, h, w, c = shape
     nwork = L.mi_blur_dist_work_bytes(w, h, c, n, C.byref(k))
     assert nwork == R.work_bytes(shape, band)
-    d_work = torch.full((nwork + 64,), 0x5A, dtype=torch.uint8, device="cuda")
-    assert d_work.data_ptr() % 16 == 0
-    return d_work, nwork
+    return Guarded(torch, nwork, "the work buffer")
 
 
 def gpu_table(pkg, L, torch, img, k, band=B):
     """mi_blur_enqueue_dist: the table inside 0xFFFFFFFF words, the work buffer with 64 bytes of 0x5A behind it."""
     n, h, w, c = img.shape
-    d_in = upload(torch, img)
-    buf = torch.full((img.size + 2 * GUARD,), -1, dtype=torch.int32, device="cuda")
-    d_work, nwork = work_buffer(pkg, L, torch, img.shape, k, band)
-    pkg.check(L.mi_blur_enqueue_dist(d_in.data_ptr(), buf.data_ptr() + 4 * GUARD, w, h, c, n, C.byref(k), d_work.data_ptr(), stream(torch)), "mi_blur_enqueue_dist")
+    d_in, p_in = upload(torch, img)
+    buf = Guarded(torch, img.size, "the table", np.uint32, 0xFFFFFFFF, GUARD, GUARD)
+    d_work = work_buffer(pkg, L, torch, img.shape, k, band)
+    pkg.check(L.mi_blur_enqueue_dist(p_in, buf.ptr, w, h, c, n, C.byref(k), d_work.ptr, stream(torch)), "mi_blur_enqueue_dist")
     torch.cuda.synchronize()
-    assert bool((buf[:GUARD] == -1).all()) and bool((buf[GUARD + img.size:] == -1).all()), "wrote outside the table"
-    assert bool((d_work[nwork:] == 0x5A).all()), "wrote outside the work buffer"
-    assert bool((d_in == upload(torch, img)).all()), "wrote to the input"
-    return buf[GUARD:GUARD + img.size].cpu().numpy().view(np.uint32).reshape(img.shape)
+    d_work.payload()
+    assert bool((d_in == upload(torch, img)[0]).all()), "wrote to the input"
+    return buf.payload().reshape(img.shape)
 
 
 def gpu_bytes(pkg, L, torch, img, k, offset_out=0, in_place=False, band=B):
     """mi_blur_enqueue_dist_u8: the output offset_out bytes into a buffer of 0x5A with 128 bytes to spare, or the input itself."""
     n, h, w, c = img.shape
-    d_in = upload(torch, img)
-    d_out = torch.full((img.size + 128,), 0x5A, dtype=torch.uint8, device="cuda")
-    d_work, nwork = work_buffer(pkg, L, torch, img.shape, k, band)
-    p_out = d_in.data_ptr() if in_place else d_out.data_ptr() + offset_out
-    pkg.check(L.mi_blur_enqueue_dist_u8(d_in.data_ptr(), p_out, w, h, c, n, C.byref(k), d_work.data_ptr(), stream(torch)), "mi_blur_enqueue_dist_u8")
+    d_in, p_in = upload(torch, img)
+    d_out = Guarded(torch, img.size, "the output", front=offset_out, back=128 - offset_out)
+    d_work = work_buffer(pkg, L, torch, img.shape, k, band)
+    pkg.check(L.mi_blur_enqueue_dist_u8(p_in, d_out.ptr if not in_place else p_in, w, h, c, n, C.byref(k), d_work.ptr, stream(torch)), "mi_blur_enqueue_dist_u8")
     torch.cuda.synchronize()
-    assert bool((d_work[nwork:] == 0x5A).all()), "wrote outside the work buffer"
-    o = d_out.cpu().numpy()
+    d_work.payload()
     if in_place:
-        assert (o == 0x5A).all()
-        return d_in.cpu().numpy().reshape(img.shape)
-    assert (o[:offset_out] == 0x5A).all() and (o[offset_out + img.size:] == 0x5A).all(), "wrote outside the output"
-    return o[offset_out:offset_out + img.size].reshape(img.shape)
+        assert bool((d_out.tensor == 0x5A).all())
+        return d_in[:img.size].cpu().numpy().reshape(img.shape)
+    return d_out.payload().reshape(img.shape)
 
 
 def cpu_table(pkg, L, img, k):

@@ -10,6 +10,7 @@ from color_ref import ref_preset
 from hist_ref import (BINS, EQUALIZE, HIST_GENERIC, HIST_TILED, IMAGE_BLOCKS, RUN, STRETCH, TABLES_GENERIC, TABLES_TILED, blocks, hist_blocks, ref_apply,
                       ref_hist, ref_tone, takes_tiled)
 from resample_harness import last, torch_cuda  # noqa: F401
+from table_harness import Guarded, stream, upload
 
 pytestmark = pytest.mark.gpu
 
@@ -20,30 +21,15 @@ UNITS = [(4, 4), (RUN - 1, 16), (RUN, 16), (RUN + 1, 16), (2 * RUN + 1, 16), (2,
 UNIT_BLOCKS = (1, 1, 1, 2, 3, 1)
 
 
-def stream(torch):
-    return torch.cuda.current_stream().cuda_stream
-
-
-def upload(torch, host, offset=0):
-    """host at `offset` bytes into a device buffer with 64 spare bytes; (tensor, address of the data)."""
-    d = torch.zeros(host.size + 64, dtype=torch.uint8, device="cuda")
-    d[offset:offset + host.size] = torch.from_numpy(np.ascontiguousarray(host).reshape(-1)).cuda()
-    assert d.data_ptr() % 16 == 0
-    return d, d.data_ptr() + offset
-
-
 def hist_on_device(pkg, L, torch, ptr, shape):
     """mi_blur_enqueue_hist on the images at ptr into a buffer of 0xFFFFFFFF words with 32 more behind it: the histogram is
     overwritten, not added to, and the words behind it stay."""
     n, h, w, c = shape
     words = n * c * BINS
-    d_hist = torch.full((words + 32,), -1, dtype=torch.int32, device="cuda")
-    assert d_hist.data_ptr() % 16 == 0
-    pkg.check(L.mi_blur_enqueue_hist(ptr, d_hist.data_ptr(), w, h, c, n, stream(torch)), "mi_blur_enqueue_hist")
+    d_hist = Guarded(torch, words, "the histogram", np.uint32, ONES, back=32)
+    pkg.check(L.mi_blur_enqueue_hist(ptr, d_hist.ptr, w, h, c, n, stream(torch)), "mi_blur_enqueue_hist")
     torch.cuda.synchronize()
-    o = d_hist.cpu().numpy().view(np.uint32)
-    assert (o[words:] == ONES).all(), "wrote outside the histogram"
-    return o[:words].reshape(n, c, BINS)
+    return d_hist.payload().reshape(n, c, BINS)
 
 
 def gpu_hist(pkg, L, torch, host, offset_in=0):
@@ -56,12 +42,10 @@ def gpu_tables(pkg, L, torch, host, tables, offset_in=0, offset_out=0, offset_ta
     n, h, w, c = host.shape
     d_in, p_in = upload(torch, host, offset_in)
     d_tab, p_tab = upload(torch, np.ascontiguousarray(tables, dtype=np.uint8), offset_tab)
-    d_out = torch.full((host.size + 128,), 0x5A, dtype=torch.uint8, device="cuda")
-    pkg.check(L.mi_blur_enqueue_tables(p_in, d_out.data_ptr() + offset_out, w, h, c, n, p_tab, stream(torch)), "mi_blur_enqueue_tables")
+    d_out = Guarded(torch, host.size, "the output", front=offset_out, back=128 - offset_out)
+    pkg.check(L.mi_blur_enqueue_tables(p_in, d_out.ptr, w, h, c, n, p_tab, stream(torch)), "mi_blur_enqueue_tables")
     torch.cuda.synchronize()
-    o = d_out.cpu().numpy()
-    assert (o[:offset_out] == 0x5A).all() and (o[offset_out + host.size:] == 0x5A).all(), "wrote outside the output"
-    return o[offset_out:offset_out + host.size].reshape(host.shape)
+    return d_out.payload().reshape(host.shape)
 
 
 @pytest.mark.parametrize("c", [1, 2, 3, 4])
