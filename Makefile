@@ -9,7 +9,7 @@ PKG     := heterogeneous-opencl-image-processing-engine_amd
 CSRC    := $(PKG)/csrc
 APPS    := $(PKG)/apps
 LIB     := $(PKG)/libmi_blur.so
-LIBSRC  := $(CSRC)/blur_kernels.hip $(CSRC)/sep_kernels.hip $(CSRC)/median_kernels.hip $(CSRC)/morph_kernels.hip $(CSRC)/bilateral_kernels.hip $(CSRC)/conv_kernels.hip $(CSRC)/sep_down_kernels.hip $(CSRC)/resize_kernels.hip $(CSRC)/warp_kernels.hip $(CSRC)/remap_kernels.hip $(CSRC)/area_kernels.hip $(CSRC)/color_kernels.hip $(CSRC)/hist_kernels.hip $(CSRC)/clahe_kernels.hip $(CSRC)/arith_kernels.hip $(CSRC)/integral_kernels.hip $(CSRC)/dist_kernels.hip $(CSRC)/layout_kernels.hip $(CSRC)/mi_blur_api.cpp $(CSRC)/table_api.cpp $(CSRC)/comm_api.cpp $(CSRC)/cpu_device.cpp
+LIBSRC  := $(CSRC)/blur_kernels.hip $(CSRC)/sep_kernels.hip $(CSRC)/median_kernels.hip $(CSRC)/morph_kernels.hip $(CSRC)/bilateral_kernels.hip $(CSRC)/conv_kernels.hip $(CSRC)/sep_down_kernels.hip $(CSRC)/resize_kernels.hip $(CSRC)/warp_kernels.hip $(CSRC)/remap_kernels.hip $(CSRC)/area_kernels.hip $(CSRC)/color_kernels.hip $(CSRC)/hist_kernels.hip $(CSRC)/clahe_kernels.hip $(CSRC)/arith_kernels.hip $(CSRC)/integral_kernels.hip $(CSRC)/dist_kernels.hip $(CSRC)/match_kernels.hip $(CSRC)/layout_kernels.hip $(CSRC)/mi_blur_api.cpp $(CSRC)/table_api.cpp $(CSRC)/comm_api.cpp $(CSRC)/cpu_device.cpp
 LIBDEPS := $(LIBSRC) $(CSRC)/api_internal.h $(CSRC)/blur_launch.h $(CSRC)/kernel_common.h $(CSRC)/cpu_device.h $(CSRC)/filter.h include/mi_blur.h
 APPFLAGS := -O2 -std=c++17 -Wall -Wextra -I include
 ifdef CIMG

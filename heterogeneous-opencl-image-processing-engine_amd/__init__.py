@@ -62,6 +62,10 @@ DIST_METRICS = {"l2": DIST_L2, "l1": DIST_L1, "linf": DIST_LINF}
 DIST_BYTE, DIST_WITHIN = 0, 1
 DIST_MAX_LIMIT = 32767
 DIST_NONE = 0xFFFFFFFF
+MATCH_SQDIFF, MATCH_CCORR, MATCH_SAD, MATCH_NCC, MATCH_ZNCC = range(5)
+MATCH_METHODS = {"sqdiff": MATCH_SQDIFF, "ccorr": MATCH_CCORR, "sad": MATCH_SAD, "ncc": MATCH_NCC, "zncc": MATCH_ZNCC}
+MATCH_MAX_SIDE, MATCH_MAX_AREA, MATCH_ONE = 255, 65536, 16384
+MATCH_PEAK_PARTS = 256
 ARITH_PRESETS = {"add": 0, "sub": 1, "avg": 2, "diff128": 3, "absdiff": 4, "min": 5, "max": 6, "mul255": 7, "mulq7": 8, "lerp": 9}
 WARP_Q = 16
 WARP_CLAMP, WARP_CONSTANT = 0, 1
@@ -78,7 +82,7 @@ def _newer(target: str, sources: list[str]) -> bool:
 
 def build_native(force: bool = False, verbose: bool = False) -> str:
     """Compile libmi_blur.so (hipcc, --offload-arch=gfx950) and the C++ hosts, in-tree."""
-    srcs = [os.path.join(CSRC, f) for f in ("blur_kernels.hip", "sep_kernels.hip", "median_kernels.hip", "morph_kernels.hip", "bilateral_kernels.hip", "conv_kernels.hip", "sep_down_kernels.hip", "resize_kernels.hip", "warp_kernels.hip", "remap_kernels.hip", "area_kernels.hip", "color_kernels.hip", "hist_kernels.hip", "clahe_kernels.hip", "arith_kernels.hip", "integral_kernels.hip", "dist_kernels.hip", "layout_kernels.hip", "mi_blur_api.cpp", "table_api.cpp", "comm_api.cpp", "cpu_device.cpp")]
+    srcs = [os.path.join(CSRC, f) for f in ("blur_kernels.hip", "sep_kernels.hip", "median_kernels.hip", "morph_kernels.hip", "bilateral_kernels.hip", "conv_kernels.hip", "sep_down_kernels.hip", "resize_kernels.hip", "warp_kernels.hip", "remap_kernels.hip", "area_kernels.hip", "color_kernels.hip", "hist_kernels.hip", "clahe_kernels.hip", "arith_kernels.hip", "integral_kernels.hip", "dist_kernels.hip", "match_kernels.hip", "layout_kernels.hip", "mi_blur_api.cpp", "table_api.cpp", "comm_api.cpp", "cpu_device.cpp")]
     deps = srcs + [os.path.join(CSRC, f) for f in ("api_internal.h", "blur_launch.h", "kernel_common.h", "cpu_device.h", "filter.h")] + [HEADER]
     if force or not _newer(LIB_PATH, deps):
         cmd = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra",
@@ -287,6 +291,12 @@ class Dist(C.Structure):
     limit (0 = none, 1..32767) and, for the byte calls, byte_op (DIST_BYTE | DIST_WITHIN) and, for DIST_WITHIN only, invert
     (include/mi_blur.h, "Exact distance transform")."""
     _fields_ = [("metric", C.c_int), ("sites_nonzero", C.c_int), ("limit", C.c_int), ("byte_op", C.c_int), ("invert", C.c_int)]
+
+
+class Match(C.Structure):
+    """mi_blur_match: the method (MATCH_SQDIFF | MATCH_CCORR | MATCH_SAD | MATCH_NCC | MATCH_ZNCC), the template's size and
+    whether one template serves every image (include/mi_blur.h, "Template matching and peak search")."""
+    _fields_ = [("method", C.c_int), ("tw", C.c_int), ("th", C.c_int), ("t_shared", C.c_int)]
 
 
 class Warp(C.Structure):
@@ -509,6 +519,15 @@ def lib() -> C.CDLL:
         "mi_blur_cpu_run_dist_u8": (i, [u8p, u8p, i, i, i, i, C.POINTER(Dist), i]),
         "mi_blur_run_dist": (i, [i, u8p, vp, i, i, i, i, C.POINTER(Dist)]),
         "mi_blur_run_dist_u8": (i, [i, u8p, u8p, i, i, i, i, C.POINTER(Dist)]),
+        "mi_blur_match_value": (C.c_int32, [i, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
+        "mi_blur_match_work_bytes": (C.c_size_t, [i, i, i, i, C.POINTER(Match)]),
+        "mi_blur_enqueue_match": (i, [u8p, u8p, vp, i, i, i, i, C.POINTER(Match), vp, vp]),
+        "mi_blur_cpu_run_match": (i, [u8p, u8p, vp, i, i, i, i, C.POINTER(Match), i]),
+        "mi_blur_run_match": (i, [i, u8p, u8p, vp, i, i, i, i, C.POINTER(Match)]),
+        "mi_blur_match_peak_work_bytes": (C.c_size_t, [i, i, i]),
+        "mi_blur_enqueue_match_peak": (i, [vp, i, i, i, i, vp, vp, vp]),
+        "mi_blur_cpu_run_match_peak": (i, [vp, i, i, i, i, vp, i]),
+        "mi_blur_run_match_peak": (i, [i, vp, i, i, i, i, vp]),
         "mi_blur_warp_coord": (i, [C.POINTER(Warp), i, i, C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i)]),
         "mi_blur_warp_rotation": (i, [C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double)]),
         "mi_blur_warp_set_matrix": (i, [C.POINTER(Warp), C.POINTER(C.c_double), i]),
@@ -1523,6 +1542,83 @@ def disc_erode(images, radius: int, metric: str = "l2", device: int = 0, batch: 
 def dist_value(k: "Dist", t: int) -> int:
     """The byte of the byte struct k for the table value t (mi_blur_dist_value); -1 for an invalid k or a t no image gives."""
     return lib().mi_blur_dist_value(C.byref(k), int(t))
+
+
+def _match_method(method, name: str) -> int:
+    code = MATCH_METHODS.get(method.lower()) if isinstance(method, str) else None
+    if code is None:
+        raise ValueError(f"{name}: method is one of {sorted(MATCH_METHODS)}")
+    return code
+
+
+def match_template(images, template, method: str = "zncc", device: int = 0, batch: int = 0):
+    """Every position's match of `template` in its image (mi_blur_run_match; include/mi_blur.h, "Template matching and
+    peak search", has the definition): (N, Ho, Wo) or (Ho, Wo), Ho = H - th + 1, Wo = W - tw + 1, the channels summed.
+    method "sqdiff" | "ccorr" | "sad": the exact sums, uint32; "ncc" | "zncc": int32 scores, MATCH_ONE = 1.0.  images:
+    (H, W), (H, W, C) or (N, H, W, C) uint8.  template: (th, tw[, C]), one for every image, or (N, th, tw[, C]), one per
+    image; th, tw <= 255 and th * tw * C <= 65536.  device: HIP ordinal, or DEVICE_CPU; batch: images per call (0 = all)."""
+    import numpy as np
+    code = _match_method(method, "match_template")
+    a, rank = _tone_stack(images, "match_template")
+    n, h, w, c = a.shape
+    t = np.ascontiguousarray(template)
+    if t.dtype != np.uint8:
+        raise ValueError("match_template: the template is uint8")
+    if c == 1 and (t.ndim == 2 or (rank == 2 and t.ndim == 3)):
+        t = t[..., None]                                                # grey images given without the channel axis: so is the template
+    if t.ndim == 3:
+        shared = True
+    elif t.ndim == 4:
+        shared = False
+    else:
+        raise ValueError("match_template: the template is (th, tw[, C]) or (N, th, tw[, C])")
+    if t.shape[-1] != c or (not shared and t.shape[0] != n):
+        raise ValueError("match_template: the template has the images' channels and, per image, their number")
+    th, tw = t.shape[-3], t.shape[-2]
+    if not (1 <= tw <= min(w, MATCH_MAX_SIDE) and 1 <= th <= min(h, MATCH_MAX_SIDE) and tw * th * c <= MATCH_MAX_AREA):
+        raise ValueError(f"match_template: a template is 1..{MATCH_MAX_SIDE} a side, inside the image, and th * tw * C <= {MATCH_MAX_AREA}")
+    k = Match(code, tw, th, int(shared))
+    out = np.empty((n, h - th + 1, w - tw + 1), np.int32 if code >= MATCH_NCC else np.uint32)
+    for i, m in _batches(n, batch):
+        check(lib().mi_blur_run_match(device, a[i:].ctypes.data, (t if shared else t[i:]).ctypes.data, out[i:].ctypes.data, w, h, c, m, C.byref(k)),
+              "mi_blur_run_match")
+    return out if rank == 4 else out[0]
+
+
+def match_peak(table, device: int = 0):
+    """minMaxLoc of a match table (mi_blur_run_match_peak): per image (min, (x, y), max, (x, y)), ties to the first entry in
+    row-major order.  table: (Ho, Wo) or (N, Ho, Wo), uint32 or int32; one tuple, or a list of N."""
+    import numpy as np
+    t = np.ascontiguousarray(table)
+    if t.dtype not in (np.uint32, np.int32) or t.ndim not in (2, 3) or t.size == 0:
+        raise ValueError("match_peak: a non-empty uint32 or int32 table, (Ho, Wo) or (N, Ho, Wo)")
+    stack = t if t.ndim == 3 else t[None]
+    n, ho, wo = stack.shape
+    peaks = np.empty((n, 6), np.int64)
+    check(lib().mi_blur_run_match_peak(device, stack.ctypes.data, int(t.dtype == np.int32), wo, ho, n, peaks.ctypes.data), "mi_blur_run_match_peak")
+    res = [(int(p[0]), (int(p[1]), int(p[2])), int(p[3]), (int(p[4]), int(p[5]))) for p in peaks]
+    return res if t.ndim == 3 else res[0]
+
+
+def find_template(images, template, method: str = "zncc", device: int = 0):
+    """The best position of the template in every image and its value: ((x, y), value), the maximum for "ccorr", "ncc" and
+    "zncc", the minimum for "sqdiff" and "sad"; one pair, or a list of N."""
+    table = match_template(images, template, method, device)
+    peaks = match_peak(table, device)
+    least = _match_method(method, "find_template") in (MATCH_SQDIFF, MATCH_SAD)
+    pick = lambda p: (p[1], p[0]) if least else (p[3], p[2])
+    return [pick(p) for p in peaks] if isinstance(peaks, list) else pick(peaks)
+
+
+def match_value(method, A: int, sum_at: int, sum_a: int, sum_aa: int, sum_t: int, sum_tt: int):
+    """The score of the sums (mi_blur_match_value), method "ncc" | "zncc" or its code; None for anything the export refuses,
+    sums beyond 32 bits included."""
+    code = MATCH_METHODS.get(method.lower(), -1) if isinstance(method, str) else int(method)
+    args = (A, sum_at, sum_a, sum_aa, sum_t, sum_tt)
+    if any(not 0 <= int(v) < 1 << 32 for v in args):
+        return None
+    v = lib().mi_blur_match_value(code, *(int(v) for v in args))
+    return None if v == -(1 << 31) else v
 
 
 def arith_preset(name) -> "Arith":

@@ -96,6 +96,12 @@ int launch_clahe_tables(const uint8_t *in, uint32_t *hist, uint8_t *tables, int 
                         hipStream_t stream);
 int launch_clahe_apply(const uint8_t *in, uint8_t *out, int W, int H, int C, int n_images, const mi_blur_clahe &k, const uint8_t *tables,
                        hipStream_t stream);
+// Template matching and the peak search (match_kernels.hip); no Filter and no LaunchDesc.  Every argument is checked
+// (match_args_ok(), match_peak_args_ok(), filter.h: MI_BLUR_ERR_INVALID), an empty batch is MI_BLUR_OK.  launch_match:
+// out = 32-bit words [n][Ho][Wo], 16-byte aligned; work = mi_blur_match_work_bytes() bytes, 16-byte aligned.
+// launch_match_peak: peaks = int64[n][6] and work = mi_blur_match_peak_work_bytes() bytes, both 16-byte aligned.
+int launch_match(const uint8_t *in, const uint8_t *t, void *out, int W, int H, int C, int n_images, const mi_blur_match &k, void *work, hipStream_t stream);
+int launch_match_peak(const void *table, int is_signed, int Wo, int Ho, int n_images, int64_t *peaks, void *work, hipStream_t stream);
 // Sets what last_kernel() reports for the calling thread.
 void set_last_kernel(const char *name);
 
@@ -232,6 +238,7 @@ struct Tunables {
     int box_bytes;       // blur_box_tiled_kernel: consecutive output bytes of a row per thread, 4 (default) | 16 (A/B runs)
     int dist_band;       // the distance transform's column pass: rows per band (default DIST_BAND of filter.h; A/B runs)
     int dist_chunk_log2; // blur_dist_tiled_kernel: log2 of the columns per search chunk (default DIST_CHUNK_LOG2 of filter.h; A/B runs)
+    int match_tiled;     // 1 (default) = raw match launches go to blur_match_tiled_kernel where it is eligible, 0 = always the generic kernel
 };
 // Every knob once: its mi_blur_set_option key, its field, what values it takes, its default and the environment variable
 // (or nullptr) that may replace the default when the library starts.  FLAG: any value, stored as 0 | 1.  RANGE: lo .. hi.
@@ -280,6 +287,7 @@ static constexpr Knob KNOBS[] = {
     {"box_bytes", &Tunables::box_bytes, KnobKind::ONE_OF, knob_bits(4, 16, 4, 16), 0, 4, nullptr},
     {"dist_band", &Tunables::dist_band, KnobKind::RANGE, 1, 256, 32, nullptr},            // the default is DIST_BAND of filter.h
     {"dist_chunk_log2", &Tunables::dist_chunk_log2, KnobKind::RANGE, 3, 5, 4, nullptr},   // the default is DIST_CHUNK_LOG2 of filter.h
+    {"match_tiled", &Tunables::match_tiled, KnobKind::FLAG, 0, 1, 1, nullptr},
 };
 // Stores `value` in the knob's field of t if the knob accepts it; false (t untouched) otherwise.
 static inline bool knob_set(const Knob &k, Tunables &t, int value)

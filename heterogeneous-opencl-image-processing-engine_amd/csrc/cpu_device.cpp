@@ -997,6 +997,63 @@ void cpu_repack(const uint8_t *src, uint8_t *dst, int W, int H, int C, int n_ima
     });
 }
 
+// ---- template matching and the peak search (include/mi_blur.h, "Template matching and peak search")
+void cpu_match(const uint8_t *in, const uint8_t *t, void *out, int W, int H, int C, int n_images, const mi_blur_match &k, int n_threads)
+{
+    if (n_images <= 0) return;
+    if (n_threads <= 0) n_threads = hardware_threads();
+    const int Wo = W - k.tw + 1, Ho = H - k.th + 1, tb = k.tw * C;
+    const size_t row_e = (size_t)W * C;
+    const uint32_t A = (uint32_t)(k.tw * k.th * C);
+    for_items((long long)n_images * Ho, n_threads, [&](long long it) {
+        const long long img = it / Ho;
+        const int y = (int)(it - img * Ho);
+        const uint8_t *T = t + (k.t_shared ? 0 : (size_t)img * k.th * tb);
+        uint32_t sum_t = 0, sum_tt = 0;
+        for (int i = 0; i < k.th * tb; i++) { sum_t += T[i]; sum_tt += (uint32_t)T[i] * T[i]; }
+        uint32_t *dst = static_cast<uint32_t *>(out) + ((size_t)img * Ho + y) * Wo;
+        for (int x = 0; x < Wo; x++) {
+            const uint8_t *a = in + ((size_t)img * H + y) * row_e + (size_t)x * C;
+            const uint8_t *tr = T;
+            uint32_t at = 0, sq = 0, sad = 0, sa = 0, saa = 0;
+            for (int dy = 0; dy < k.th; dy++, a += row_e, tr += tb)
+                for (int b = 0; b < tb; b++) {
+                    const int av = a[b], tv = tr[b], d = av - tv;
+                    at += (uint32_t)(av * tv);
+                    sq += (uint32_t)(d * d);
+                    sad += (uint32_t)(d < 0 ? -d : d);
+                    sa += (uint32_t)av;
+                    saa += (uint32_t)(av * av);
+                }
+            switch (k.method) {
+            case MI_BLUR_MATCH_SQDIFF: dst[x] = sq; break;
+            case MI_BLUR_MATCH_CCORR: dst[x] = at; break;
+            case MI_BLUR_MATCH_SAD: dst[x] = sad; break;
+            default: dst[x] = (uint32_t)match_score(k.method, A, at, sa, saa, sum_t, sum_tt); break;
+            }
+        }
+    });
+}
+
+void cpu_match_peak(const void *table, int is_signed, int Wo, int Ho, int n_images, int64_t *peaks, int n_threads)
+{
+    if (n_images <= 0) return;
+    if (n_threads <= 0) n_threads = hardware_threads();
+    const size_t entries = (size_t)Wo * Ho;
+    for_items(n_images, n_threads, [&](long long img) {
+        const uint32_t *src = static_cast<const uint32_t *>(table) + (size_t)img * entries;
+        const auto value = [&](size_t i) { return is_signed ? (int64_t)(int32_t)src[i] : (int64_t)src[i]; };
+        size_t lo = 0, hi = 0;
+        for (size_t i = 1; i < entries; i++) {                          // strict comparisons: the first entry keeps a tie
+            if (value(i) < value(lo)) lo = i;
+            if (value(i) > value(hi)) hi = i;
+        }
+        int64_t *o = peaks + 6 * (size_t)img;
+        o[0] = value(lo); o[1] = (int64_t)(lo % (size_t)Wo); o[2] = (int64_t)(lo / (size_t)Wo);
+        o[3] = value(hi); o[4] = (int64_t)(hi % (size_t)Wo); o[5] = (int64_t)(hi / (size_t)Wo);
+    });
+}
+
 uint64_t fnv1a64(const uint8_t *p, size_t n)
 {
     uint64_t h = 0xcbf29ce484222325ull;

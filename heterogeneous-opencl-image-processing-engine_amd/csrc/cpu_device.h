@@ -84,6 +84,11 @@ void cpu_box_from_integral(const uint8_t *in, const uint32_t *sum, const uint32_
 // distances, is allocated here: false when that fails.  Columns in strips across the threads, then rows in bands; every
 // value is dist_final() of dist_search(), every byte dist_byte() of it (filter.h).
 bool cpu_dist(const uint8_t *in, uint32_t *table, uint8_t *out, int W, int H, int C, int n_images, const mi_blur_dist &k, int n_threads);
+// Template matching and the peak search (include/mi_blur.h, "Template matching and peak search"); the callers have checked
+// the arguments (match_args_ok(), match_peak_args_ok(), filter.h).  cpu_match: the definition's loops, every window's
+// sums made directly, output rows across the threads; a score is match_score().  cpu_match_peak: images across the threads.
+void cpu_match(const uint8_t *in, const uint8_t *t, void *out, int W, int H, int C, int n_images, const mi_blur_match &k, int n_threads);
+void cpu_match_peak(const void *table, int is_signed, int Wo, int Ho, int n_images, int64_t *peaks, int n_threads);
 // planar (CImg storage: all of channel 0, then channel 1, ...) <-> interleaved, n_images frames, a few pool threads
 void cpu_repack(const uint8_t *src, uint8_t *dst, int W, int H, int C, int n_images, bool planar_to_interleaved, int n_threads);
 void copy_blocks(uint8_t *dst, size_t dst_stride, const uint8_t *src, size_t src_stride, size_t bytes, int n, int n_threads);

@@ -1459,4 +1459,71 @@ inline size_t dist_work_bytes(int W, int H, int C, int n_images, int band)
     return dist_g_bytes(W, H, C, n_images) + (size_t)n_images * (size_t)dist_bands(H, band) * 2u * (size_t)W * (size_t)C * sizeof(uint16_t);
 }
 
+// ---- template matching and peak search (include/mi_blur.h, "Template matching and peak search").  The host export
+// mi_blur_match_value, the CPU device and blur_match_score_kernel take a score from match_score(); the raw sums are
+// plain loops wherever they are made.
+inline bool match_ok(const mi_blur_match *k, int W, int H, int C)
+{
+    if (!k || k->method < MI_BLUR_MATCH_SQDIFF || k->method > MI_BLUR_MATCH_ZNCC || (k->t_shared != 0 && k->t_shared != 1)) return false;
+    if (k->tw < 1 || k->th < 1 || k->tw > MI_BLUR_MATCH_MAX_SIDE || k->th > MI_BLUR_MATCH_MAX_SIDE || k->tw > W || k->th > H) return false;
+    return (long long)k->tw * k->th * C <= MI_BLUR_MATCH_MAX_AREA;
+}
+inline bool match_is_score(int method) { return method == MI_BLUR_MATCH_NCC || method == MI_BLUR_MATCH_ZNCC; }
+// The arguments of the three match exports: out = 32-bit words, `align` bytes aligned, and neither input.
+inline bool match_args_ok(const void *in, const void *t, const void *out, int W, int H, int C, int n_images, const mi_blur_match *k, uintptr_t align)
+{
+    if (!in || !t || !out || out == in || out == t || n_images < 0 || !hist_image_ok(W, H, C) || !match_ok(k, W, H, C)) return false;
+    return (uintptr_t)out % align == 0;
+}
+// ... and of the peak search: peaks = int64[n][6].
+inline bool match_peak_args_ok(const void *table, int is_signed, int Wo, int Ho, int n_images, const void *peaks, uintptr_t table_align, uintptr_t peaks_align)
+{
+    if (!table || !peaks || table == peaks || n_images < 0 || (is_signed != 0 && is_signed != 1)) return false;
+    if (Wo < 1 || Ho < 1 || (long long)Wo * Ho > INT_MAX) return false;
+    return (uintptr_t)table % table_align == 0 && (uintptr_t)peaks % peaks_align == 0;
+}
+// The score of consistent sums (the caller's business): sign(N) k, k the largest integer in 0..16384 that is 0 or has
+// (2k - 1)^2 D <= 2^30 N^2.  A double-precision estimate, then the exact comparison in 128 bits moves it as far as it
+// must (the estimate is within one of k; the loops do not rely on that).
+MI_BLUR_HD inline int32_t match_score(int method, uint32_t A, uint32_t sum_at, uint32_t sum_a, uint32_t sum_aa, uint32_t sum_t, uint32_t sum_tt)
+{
+    typedef unsigned __int128 u128;
+    int64_t N;
+    uint64_t Da, Dt;
+    if (method == MI_BLUR_MATCH_NCC) {
+        N = (int64_t)sum_at; Da = sum_aa; Dt = sum_tt;
+    } else {
+        N = (int64_t)((uint64_t)A * sum_at) - (int64_t)((uint64_t)sum_a * sum_t);
+        Da = (uint64_t)A * sum_aa - (uint64_t)sum_a * sum_a;
+        Dt = (uint64_t)A * sum_tt - (uint64_t)sum_t * sum_t;
+    }
+    if (Da == 0 || Dt == 0 || N == 0) return 0;
+    const uint64_t n = (uint64_t)(N < 0 ? -N : N);
+    const u128 D = (u128)Da * Dt, rhs = ((u128)n * n) << 30;
+    const double est = 16384.0 * (double)n / (sqrt((double)Da) * sqrt((double)Dt));
+    int k = est >= 16384.0 ? MI_BLUR_MATCH_ONE : (int)(est + 0.5);
+    const auto holds = [&](int kk) { const u128 o = (u128)(uint64_t)(2 * kk - 1); return o * o * D <= rhs; };
+    while (k > 0 && !holds(k)) k--;
+    while (k < MI_BLUR_MATCH_ONE && holds(k + 1)) k++;
+    return N < 0 ? -k : k;
+}
+// blur_match_tiled_kernel: a workgroup of MATCH_THREADS = MATCH_TX lanes x MATCH_THREADS / 64 waves owns MATCH_TX x
+// MATCH_TY outputs, MATCH_R output rows a thread; it stages the input rows of as many template rows as MATCH_LDS_BYTES
+// hold at a time.  Rows of whole 16-byte chunks; the template rows zero-padded to MATCH_ROW_PAD bytes.
+constexpr int MATCH_THREADS = 256, MATCH_TX = 64, MATCH_R = 4, MATCH_TY = MATCH_THREADS / 64 * MATCH_R;
+constexpr int MATCH_ROW_PAD = 16, MATCH_LDS_BYTES = 48 * 1024, MATCH_LDS_SLACK = 64;
+inline bool match_tiled_ok(int W, int C) { return (long long)W * C % 16 == 0; }
+inline size_t match_round16(size_t b) { return (b + 15) & ~(size_t)15; }
+inline int match_templates(const mi_blur_match &k, int n_images) { return k.t_shared ? 1 : n_images; }
+inline size_t match_row_pad(const mi_blur_match &k, int C) { return ((size_t)k.tw * C + MATCH_ROW_PAD - 1) / MATCH_ROW_PAD * MATCH_ROW_PAD; }
+// The work buffer: sums[templates][4] (sum_t, sum_tt, 0, 0), the padded templates, then for a score the CCORR table, S, Q
+// and the integral's own work.
+inline size_t match_sums_bytes(const mi_blur_match &k, int n_images) { return (size_t)match_templates(k, n_images) * 16u; }
+inline size_t match_pad_bytes(const mi_blur_match &k, int C, int n_images) { return (size_t)match_templates(k, n_images) * k.th * match_row_pad(k, C); }
+inline size_t match_table_bytes(const mi_blur_match &k, int W, int H, int n_images)
+{
+    return match_round16((size_t)n_images * (size_t)(H - k.th + 1) * (size_t)(W - k.tw + 1) * sizeof(uint32_t));
+}
+constexpr int MATCH_PEAK_THREADS = 256;
+
 }  // namespace mi_blur

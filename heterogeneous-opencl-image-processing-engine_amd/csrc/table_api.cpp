@@ -572,3 +572,103 @@ extern "C" int mi_blur_run_dist_u8(int device, const uint8_t *host_in, uint8_t *
     return run_dist(device, host_in, host_out, true, dist_args_ok(host_in, host_out, width, height, channels, n_images, k, true, 1), width, height,
                     channels, n_images, k);
 }
+
+// ----------------------------------------------------------------------------------
+// template matching and the peak search.  The arguments: match_args_ok(), match_peak_args_ok() (filter.h).
+// ----------------------------------------------------------------------------------
+static bool match_sums_ok(uint32_t A, uint32_t s, uint32_t ss)
+{
+    return (uint64_t)s <= 255ull * A && (uint64_t)ss <= 65025ull * A && (uint64_t)s * s <= (uint64_t)A * ss;
+}
+
+extern "C" int32_t mi_blur_match_value(int method, uint32_t A, uint32_t sum_at, uint32_t sum_a, uint32_t sum_aa, uint32_t sum_t, uint32_t sum_tt)
+{
+    if (!match_is_score(method) || A < 1 || A > MI_BLUR_MATCH_MAX_AREA) return INT32_MIN;
+    if (!match_sums_ok(A, sum_a, sum_aa) || !match_sums_ok(A, sum_t, sum_tt)) return INT32_MIN;
+    if ((unsigned __int128)sum_at * sum_at > (unsigned __int128)sum_aa * sum_tt) return INT32_MIN;
+    return match_score(method, A, sum_at, sum_a, sum_aa, sum_t, sum_tt);
+}
+
+extern "C" size_t mi_blur_match_work_bytes(int width, int height, int channels, int n_images, const mi_blur_match *k)
+{
+    if (!hist_image_ok(width, height, channels) || n_images < 0 || !match_ok(k, width, height, channels)) return 0;
+    size_t bytes = round16(match_sums_bytes(*k, n_images)) + round16(match_pad_bytes(*k, channels, n_images));
+    if (match_is_score(k->method))
+        bytes += match_table_bytes(*k, width, height, n_images) + 2 * box_table_bytes(width, height, channels, n_images) +
+                 round16(mi_blur_integral_work_bytes(width, height, channels, n_images, 1));
+    return bytes ? bytes : 16;
+}
+
+static size_t match_out_bytes(int W, int H, int n_images, const mi_blur_match &k)
+{
+    return (size_t)n_images * (size_t)(H - k.th + 1) * (size_t)(W - k.tw + 1) * sizeof(uint32_t);
+}
+
+extern "C" int mi_blur_enqueue_match(const uint8_t *d_in, const uint8_t *d_t, void *d_out, int width, int height, int channels, int n_images,
+                                     const mi_blur_match *k, void *d_work, void *stream)
+{
+    if (const int st = go(match_args_ok(d_in, d_t, d_out, width, height, channels, n_images, k, 16) && aligned_to(d_work, 16), n_images); st != GO) return st;
+    return launch_match(d_in, d_t, d_out, width, height, channels, n_images, *k, d_work, (hipStream_t)stream);
+}
+
+extern "C" int mi_blur_cpu_run_match(const uint8_t *in, const uint8_t *t, void *out, int width, int height, int channels, int n_images,
+                                     const mi_blur_match *k, int n_threads)
+{
+    if (!match_args_ok(in, t, out, width, height, channels, n_images, k, 4)) return MI_BLUR_ERR_INVALID;
+    cpu_match(in, t, out, width, height, channels, n_images, *k, n_threads);
+    return MI_BLUR_OK;
+}
+
+extern "C" int mi_blur_run_match(int device, const uint8_t *host_in, const uint8_t *host_t, void *host_out, int width, int height, int channels,
+                                 int n_images, const mi_blur_match *k)
+{
+    if (device == MI_BLUR_DEVICE_CPU) return mi_blur_cpu_run_match(host_in, host_t, host_out, width, height, channels, n_images, k, 0);
+    if (const int st = go(match_args_ok(host_in, host_t, host_out, width, height, channels, n_images, k, 4), n_images, device); st != GO) return st;
+    const size_t in_bytes = image_bytes(width, height, channels, n_images), out_bytes = match_out_bytes(width, height, n_images, *k);
+    const size_t t_bytes = (size_t)match_templates(*k, n_images) * k->th * k->tw * channels;
+    DeviceCall dc;
+    uint8_t *in = dc.make<uint8_t>(in_bytes), *t = dc.make<uint8_t>(t_bytes);
+    void *out = dc.make<void>(out_bytes), *work = dc.make<void>(mi_blur_match_work_bytes(width, height, channels, n_images, k));
+    dc.put(in, host_in, in_bytes);
+    dc.put(t, host_t, t_bytes);
+    if (!dc.status) dc.status = launch_match(in, t, out, width, height, channels, n_images, *k, work, nullptr);
+    dc.get(host_out, out, out_bytes);
+    return dc.status;
+}
+
+extern "C" size_t mi_blur_match_peak_work_bytes(int out_width, int out_height, int n_images)
+{
+    if (out_width < 1 || out_height < 1 || (long long)out_width * out_height > INT_MAX || n_images < 0) return 0;
+    const size_t bytes = (size_t)n_images * MI_BLUR_MATCH_PEAK_PARTS * 2 * sizeof(uint64_t);
+    return bytes ? bytes : 16;
+}
+
+extern "C" int mi_blur_enqueue_match_peak(const void *d_table, int is_signed, int out_width, int out_height, int n_images, int64_t *d_peaks,
+                                          void *d_work, void *stream)
+{
+    if (const int st = go(match_peak_args_ok(d_table, is_signed, out_width, out_height, n_images, d_peaks, 16, 16) && aligned_to(d_work, 16), n_images); st != GO)
+        return st;
+    return launch_match_peak(d_table, is_signed, out_width, out_height, n_images, d_peaks, d_work, (hipStream_t)stream);
+}
+
+extern "C" int mi_blur_cpu_run_match_peak(const void *table, int is_signed, int out_width, int out_height, int n_images, int64_t *peaks, int n_threads)
+{
+    if (!match_peak_args_ok(table, is_signed, out_width, out_height, n_images, peaks, 4, 8)) return MI_BLUR_ERR_INVALID;
+    cpu_match_peak(table, is_signed, out_width, out_height, n_images, peaks, n_threads);
+    return MI_BLUR_OK;
+}
+
+extern "C" int mi_blur_run_match_peak(int device, const void *host_table, int is_signed, int out_width, int out_height, int n_images,
+                                      int64_t *host_peaks)
+{
+    if (device == MI_BLUR_DEVICE_CPU) return mi_blur_cpu_run_match_peak(host_table, is_signed, out_width, out_height, n_images, host_peaks, 0);
+    if (const int st = go(match_peak_args_ok(host_table, is_signed, out_width, out_height, n_images, host_peaks, 4, 8), n_images, device); st != GO) return st;
+    const size_t table_bytes = (size_t)n_images * out_width * out_height * sizeof(uint32_t), peak_bytes = (size_t)n_images * 6 * sizeof(int64_t);
+    DeviceCall dc;
+    void *table = dc.make<void>(table_bytes), *work = dc.make<void>(mi_blur_match_peak_work_bytes(out_width, out_height, n_images));
+    int64_t *peaks = dc.make<int64_t>(peak_bytes);
+    dc.put(table, host_table, table_bytes);
+    if (!dc.status) dc.status = launch_match_peak(table, is_signed, out_width, out_height, n_images, peaks, work, nullptr);
+    dc.get(host_peaks, peaks, peak_bytes);
+    return dc.status;
+}

@@ -154,7 +154,9 @@ const char *mi_blur_last_kernel(void);
  *   "dist_band"        32 (default) | 1 .. 256: rows per band of the distance transform's column pass (A/B runs; the work
  *                      buffer's size follows it: mi_blur_dist_work_bytes answers for the value in force)
  *   "dist_chunk_log2"  4 (default) | 3 | 5: blur_dist_tiled_kernel keeps one minimum per 2^v columns of a staged row and
- *                      skips a chunk whose minimum cannot beat the best distance so far (A/B runs) */
+ *                      skips a chunk whose minimum cannot beat the best distance so far (A/B runs)
+ *   "match_tiled"      1 (default) | 0: SQDIFF, CCORR and SAD launches that blur_match_tiled_kernel can take go to it; 0 sends
+ *                      every launch to blur_match_generic_kernel (tests and A/B runs) */
 int mi_blur_set_option(const char *key, int value);
 
 /* Number of visible HIP devices (0 is a valid answer: CPU-device contexts still work).
@@ -1197,6 +1199,88 @@ int mi_blur_run_dist(int device, const uint8_t *host_in, uint32_t *host_table, i
                      int n_images, const mi_blur_dist *k);
 int mi_blur_run_dist_u8(int device, const uint8_t *host_in, uint8_t *host_out, int width, int height, int channels,
                         int n_images, const mi_blur_dist *k);
+
+/* ------------------------------------------------------------------------
+ * Template matching and peak search (OpenCV's matchTemplate and minMaxLoc; no reference analogue).  Defined in integers
+ * and exact: the GPU, the CPU device and a Python-integer restatement agree word for word.  None of it is claimed to be
+ * OpenCV's bytes, which are float.
+ *
+ * Operands.  Images are uint8[n][H][W][C], within the histogram family's limits, C = 1..4.  The template is
+ * uint8[th][tw][C] when t_shared = 1 and uint8[n][th][tw][C] (one per image) when t_shared = 0.  The output has
+ * Wo = W - tw + 1 columns and Ho = H - th + 1 rows and ONE entry per position: the channels are summed, as OpenCV does.
+ * Every window lies inside the image: there is no border rule.
+ *
+ * A spec is valid when method is in the enum, 1 <= tw <= min(W, 255), 1 <= th <= min(H, 255), tw * th * C <= 65536
+ * and t_shared is 0 or 1.  With A = tw * th * C <= 65536 every raw sum fits uint32: 255^2 * 65536 = 4 261 478 400 < 2^32;
+ * the sides stay within 255 because that is where the integral tables S and Q are exact.
+ *
+ * Raw methods, uint32[n][Ho][Wo].  With a = in[y + dy][x + dx][c] and t = T[dy][dx][c], summed over dy < th, dx < tw
+ * and every c:   CCORR = sum a t      SQDIFF = sum (a - t)^2      SAD = sum |a - t|.
+ * (The kernels form SQDIFF as sum a^2 + sum t^2 - 2 sum a t in uint32: exact modulo 2^32, and so exact.)
+ *
+ * Scores, int32[n][Ho][Wo], -16384 .. 16384 (MI_BLUR_MATCH_ONE = 1.0).  With sum_a, sum_aa, sum_at of the window and
+ * sum_t, sum_tt of the template:
+ *   NCC  (TM_CCORR_NORMED):   N = sum_at,                              D = sum_aa * sum_tt               < 2^64
+ *   ZNCC (TM_CCOEFF_NORMED):  N = A sum_at - sum_a sum_t  (|N| < 2^48), D = Da * Dt                      < 2^96
+ *                             Da = A sum_aa - sum_a^2, Dt = A sum_tt - sum_t^2, each in [0, 2^48)
+ * The score is sign(N) k, k the largest integer in 0..16384 that is 0 or satisfies (2k - 1)^2 D <= 2^30 N^2: that is
+ * 2^14 |N| / sqrt(D) rounded once, half away from zero, decided in integers (both sides are below 2^126).  N^2 <= D by
+ * Cauchy-Schwarz, so nothing is clamped.  D = 0 (a flat window or a flat template) gives 0.
+ *
+ * Peak search over a table of 32-bit words [n][Ho][Wo], taken as unsigned or signed: per image int64[6] = min, min_x,
+ * min_y, max, max_x, max_y.  Ties go to the FIRST entry in row-major order, for both.
+ *
+ * Kernels.  blur_match_tiled_kernel takes SQDIFF, CCORR and SAD when the images are 16-byte aligned and a row is whole
+ * 16-byte chunks (W * C a multiple of 16); blur_match_generic_kernel takes the rest, and everything when "match_tiled"
+ * is 0.  The scores are made of the integral tables, a CCORR launch, the template's sums and an elementwise kernel.
+ *
+ * Out of scope: FFT matching for templates beyond the area limit, masks, sub-pixel refinement of the peak, a host CLI
+ * flag and context filters. */
+typedef enum { MI_BLUR_MATCH_SQDIFF = 0, MI_BLUR_MATCH_CCORR = 1, MI_BLUR_MATCH_SAD = 2,
+               MI_BLUR_MATCH_NCC = 3, MI_BLUR_MATCH_ZNCC = 4 } mi_blur_match_method;
+typedef struct mi_blur_match { int method; int tw, th; int t_shared; } mi_blur_match;
+#define MI_BLUR_MATCH_MAX_SIDE 255
+#define MI_BLUR_MATCH_MAX_AREA 65536      /* tw * th * C */
+#define MI_BLUR_MATCH_ONE 16384           /* a score of 1.0 */
+
+/* The definition of a score, host only: method NCC | ZNCC, A = tw * th * C and the five sums.  INT32_MIN for another
+ * method, A outside 1..65536, or sums no window or template can have: sum_a > 255 A, sum_aa > 65025 A,
+ * sum_a^2 > A sum_aa, the same three for t, and sum_at^2 > sum_aa sum_tt. */
+int32_t mi_blur_match_value(int method, uint32_t A, uint32_t sum_at, uint32_t sum_a, uint32_t sum_aa, uint32_t sum_t,
+                            uint32_t sum_tt);
+
+/* Bytes of the work buffer of mi_blur_enqueue_match; 0 for a spec or an image that is not valid.  A raw method: the
+ * templates' sums (16 bytes each) and the templates with every row zero-padded to whole 16-byte chunks, which the tiled
+ * kernel reads.  A score adds the CCORR table, S and Q and mi_blur_integral_work_bytes(.., both), each rounded to 16. */
+size_t mi_blur_match_work_bytes(int width, int height, int channels, int n_images, const mi_blur_match *k);
+
+/* d_out = 32-bit words [n][Ho][Wo], 16-byte aligned, uint32 for a raw method and int32 for a score; d_work = non-null,
+ * 16-byte aligned, mi_blur_match_work_bytes bytes.  d_out equal to d_in or d_t is refused.  Everything goes on `stream`
+ * with no host round trip: a score issues the integral dispatches, the template's sums, the CCORR launch into the work
+ * buffer and the elementwise score kernel.  Statuses in the order of every table export: the arguments
+ * (MI_BLUR_ERR_INVALID), the empty batch (MI_BLUR_OK), the device (MI_BLUR_ERR_NO_DEVICE). */
+int mi_blur_enqueue_match(const uint8_t *d_in, const uint8_t *d_t, void *d_out, int width, int height, int channels,
+                          int n_images, const mi_blur_match *k, void *d_work, void *stream);
+/* The CPU device: the definition's loops, rows across n_threads (0 = all); out 4-byte aligned; no work buffer. */
+int mi_blur_cpu_run_match(const uint8_t *in, const uint8_t *t, void *out, int width, int height, int channels,
+                          int n_images, const mi_blur_match *k, int n_threads);
+/* The blocking form on host memory: a HIP ordinal or MI_BLUR_DEVICE_CPU. */
+int mi_blur_run_match(int device, const uint8_t *host_in, const uint8_t *host_t, void *host_out, int width, int height,
+                      int channels, int n_images, const mi_blur_match *k);
+
+/* Peak search.  out_width x out_height = the table's extent (1.., out_width * out_height <= INT_MAX), is_signed 0 | 1.
+ * Two dispatches: MI_BLUR_MATCH_PEAK_PARTS workgroups per image leave keys (value << 32 | index for the minimum,
+ * value << 32 | ~index for the maximum, the value biased by 2^31 when signed) in the work buffer, one workgroup per image
+ * finishes and decodes; no workgroup waits for another.  d_table and d_work 16-byte aligned; d_peaks = int64[n][6],
+ * 16-byte aligned (8 on the host). */
+#define MI_BLUR_MATCH_PEAK_PARTS 256
+size_t mi_blur_match_peak_work_bytes(int out_width, int out_height, int n_images);
+int mi_blur_enqueue_match_peak(const void *d_table, int is_signed, int out_width, int out_height, int n_images,
+                               int64_t *d_peaks, void *d_work, void *stream);
+int mi_blur_cpu_run_match_peak(const void *table, int is_signed, int out_width, int out_height, int n_images,
+                               int64_t *peaks, int n_threads);
+int mi_blur_run_match_peak(int device, const void *host_table, int is_signed, int out_width, int out_height,
+                           int n_images, int64_t *host_peaks);
 
 /* ------------------------------------------------------------------------
  * Affine warp: exact fixed-point rotate, scale, shear and translate, any output size (no reference analogue).  The
